@@ -6,8 +6,11 @@ streams, 48 kHz, presetDefault, 1.5x stretch, fp32, 10 s of input per stream), i
 N GPUs: one process per GPU, the batch of streams is sharded (256 streams per GPU, weak scaling), no collective on
 the data path; torch.distributed (RCCL) is used only for the barrier and the max-over-ranks clock.
 
-Prints ONE JSON line (rank 0) with `roofline` (dominant kernel, HIP-event timed on the engine's own stream) and
-`cpu_baseline` (the CPU reference timed on this box's host cores; N=1 only)."""
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times --steps steps and prints the headline figure
+(`value`, `ms_per_step`); `--dump-outputs DIR` also writes what the last timed step computed.  `--full` adds everything
+else to the line: the self-check of stream 0 against oracle/_ref, `roofline` (dominant kernel, HIP-event timed on the
+engine's own stream, plus a serialised per-kernel call), the short runs of the other configs, the real-time pattern,
+the drop-in objects and `cpu_baseline` (the CPU reference timed on the host's own cores; N=1 only)."""
 import argparse
 import importlib
 import json
@@ -353,7 +356,7 @@ def other_measurements():
     env = dict(os.environ)
     others = {}
     for cfg in ("3", "4b", "5"):
-        cmd = [sys.executable, os.path.abspath(__file__), "--config", cfg, "--steps", "2", "--warmup", "2", "--no-cpu-baseline", "--no-serial-pass", "--no-other-configs"]
+        cmd = [sys.executable, os.path.abspath(__file__), "--config", cfg, "--steps", "2", "--warmup", "2", "--full", "--no-cpu-baseline", "--no-serial-pass", "--no-other-configs"]
         t0 = time.perf_counter()
         try:
             r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=240)
@@ -387,11 +390,43 @@ def other_measurements():
     return others, realtime, dropin
 
 
+DUMP_MAX_STREAMS = 8
+DUMP_MAX_BYTES = 60_000_000  # the dump stays below 64 MB
+
+
+def dump_outputs(out_dir, y, n_out, rank=None):
+    """--dump-outputs: what the last timed step returned to its caller, for comparing two builds output for output.  The whole
+    output (streams x channels x samples, float32) is too large to keep, so a fixed sample of streams is written (PCG64(0) picks
+    them, the same for every run with the same arguments), every channel and sample of each, at most DUMP_MAX_BYTES in all.
+    Samples past a stream's own output length (config 5's per-stream stretch) are not written by the engine: zeroed here."""
+    import numpy as np
+    import torch
+    S, C, n_max = y.shape
+    n_keep = min(n_max, max(1, DUMP_MAX_BYTES//(4*C)))
+    k = max(1, min(S, DUMP_MAX_STREAMS, DUMP_MAX_BYTES//(4*C*n_keep)))
+    streams = np.sort(np.random.Generator(np.random.PCG64(0)).choice(S, k, replace=False))
+    out = y[torch.as_tensor(streams, device=y.device)][:, :, :n_keep].cpu().numpy().astype(np.float32, copy=True)
+    lengths = n_out if isinstance(n_out, (list, tuple)) else [n_out]*S
+    for i, s in enumerate(streams):
+        out[i, :, lengths[s]:] = 0.0
+    os.makedirs(out_dir, exist_ok=True)
+    suffix = "" if rank is None else ".rank%d" % rank
+    np.save(os.path.join(out_dir, "output%s.npy" % suffix), out)
+    np.save(os.path.join(out_dir, "output_streams%s.npy" % suffix), streams.astype(np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--steps", type=int, default=20, help="timed steps (>= 1)")
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true", help="everything besides the headline figure: the self-check against oracle/_ref, the in-place and "
+                    "serialised per-kernel timings (roofline), the short runs of configs 3 / 4b / 5, the real-time pattern, the drop-in objects and the "
+                    "CPU baseline (the --no-* options below switch single parts off again).  Without it the run only sets up, warms up, times --steps "
+                    "steps, writes --dump-outputs and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the LAST timed step computed into DIR "
+                    "as float32 .npy files: output.npy = the outputs of a fixed, seeded sample of the rank's streams (at most 8, < 64 MB in all), "
+                    "output_streams.npy = their stream indices")
     ap.add_argument("--streams", type=int, default=None, help="streams per GPU (default: the config's own count -- config 2 = BASELINE configs[1]: 256)")
     ap.add_argument("--seconds", type=float, default=10.0, help="seconds of input per stream per step")
     ap.add_argument("--stretch", type=float, default=1.5)
@@ -406,12 +441,17 @@ def main():
     ap.add_argument("--dump-output", default=None, help="write rank-local output of the first streams to this .npy prefix (oversubscribe cross-check)")
     ap.add_argument("--no-numa-pinning", action="store_true", help="with --gpus > 1: leave every rank's CPU affinity as the launcher set it (default: pin each rank's host scheduler to the CPUs of its GPU's NUMA node, and FAIL if that node cannot be read)")
     ap.add_argument("--half-state", action="store_true", help="BASELINE config 5 'fp16 internal': carried state and overlap-add sums stored in fp16 (SMST_FLAG_HALF_STATE)")
-    ap.add_argument("--no-other-configs", action="store_true", help="skip the short runs of configs 3 / 4b / 5 and of the real-time pattern that the default (config 2, one GPU) "
+    ap.add_argument("--no-other-configs", action="store_true", help="skip the short runs of configs 3 / 4b / 5 and of the real-time pattern that a --full (config 2, one GPU) "
                     "invocation appends to its line under `other_configs` / `realtime` (each in a process of its own, AFTER the timed region)")
     ap.add_argument("--config", default="2", choices=["2", "3", "4", "4b", "5"],
                     help="BASELINE.json config (default 2 = the one the headline metric is quoted on; the others are "
                          "reported in DESIGN.md, they are not the bench line)")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("bench: --steps must be >= 1")
+    if not args.full:  # a plain run: only what the headline figure needs
+        args.no_self_check = args.no_serial_pass = args.no_other_configs = args.no_cpu_baseline = True
+    live_timing = args.full  # in-place recurrence timing + per-step event stamps (roofline)
     preset, C, sr_cfg = "default", 2, SR
     setup = None
     per_stream = None
@@ -514,17 +554,20 @@ def main():
     torch.cuda.synchronize()
     # the recurrence kernel is timed IN PLACE over the timed region: a HIP-event pair on the stream it is launched on
     # (the engine's chain stream), the other streams keep overlapping it (two event records per 64-hop tile)
-    batch.enableProfiling(0 if os.environ.get("SMST_BENCH_NO_LIVE") else 2)
-    # per-step completion stamps: a side stream waits (by event) for the batch's stream after every call and records a timing
+    if live_timing:
+        batch.enableProfiling(0 if os.environ.get("SMST_BENCH_NO_LIVE") else 2)
+    # per-step completion stamps (--full): a side stream waits (by event) for the batch's stream after every call and records a timing
     # event -- the steps stay pipelined (no host synchronisation between them), the stamps give each step's device-side period
-    side = torch.cuda.Stream(device=device)
-    stamps = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)]
+    if live_timing:
+        side = torch.cuda.Stream(device=device)
+        stamps = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)]
     pkg_lib = batch.lib
     import ctypes
 
     def stamp(i):
-        pkg_lib.smst_batch_signal_stream(batch.h, ctypes.c_void_p(side.cuda_stream))
-        stamps[i].record(side)
+        if live_timing:
+            pkg_lib.smst_batch_signal_stream(batch.h, ctypes.c_void_p(side.cuda_stream))
+            stamps[i].record(side)
     stamp(0)
     t0 = time.perf_counter()
     # inputs are complete (synchronised above) and the outputs are only looked at after batch.synchronize(): no per-call
@@ -543,10 +586,11 @@ def main():
     torch.cuda.synchronize()
     barrier()
     elapsed = time.perf_counter() - t0
-    live_ms, live_launches = batch.takeTimings()
-    batch.enableProfiling(0)
-    step_periods = [stamps[i].elapsed_time(stamps[i + 1]) for i in range(args.steps)]  # in order: a slow FIRST step is a warm-up artefact, a slow one in the middle is jitter
-    step_ms = sorted(step_periods)
+    if live_timing:
+        live_ms, live_launches = batch.takeTimings()
+        batch.enableProfiling(0)
+        step_periods = [stamps[i].elapsed_time(stamps[i + 1]) for i in range(args.steps)]  # in order: a slow FIRST step is a warm-up artefact, a slow one in the middle is jitter
+        step_ms = sorted(step_periods)
     if use_dist:
         tt = torch.tensor([elapsed], dtype=torch.float64, device=red_device)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
@@ -555,6 +599,8 @@ def main():
     if args.dump_output:
         import numpy as np
         np.save("%s.rank%d.npy" % (args.dump_output, stream_rank), y[:4].cpu().numpy())
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, y, n_out, stream_rank if world > 1 else None)
 
     total_out = sum(n_out) if per_stream else S*n_out
     samples_local = C*(S*n_in + total_out)
@@ -573,7 +619,7 @@ def main():
     chops_per_step = S*C*hops_per_stream
 
     roofline = None
-    if rank == 0:
+    if rank == 0 and args.full:
         # per-kernel-class device time, each class ALONE on the GPU: one extra, serialised call with HIP events around every launch
         if args.no_serial_pass:
             ms = {k: 0.0 for k in ("analyse", "feed", "predict", "chain", "synth", "emit", "other")}
@@ -657,7 +703,8 @@ def main():
     check = None
     if rank == 0:
         if first_call is None:
-            check = dict(checked=False, reason="--no-self-check" if args.no_self_check else "no warm-up call to take the first output from")
+            check = dict(checked=False, reason=("not a --full run" if not args.full else "--no-self-check") if args.no_self_check
+                         else "no warm-up call to take the first output from")
         else:
             try:
                 ref_setup = None

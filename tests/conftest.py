@@ -47,14 +47,11 @@ def synth_input(stream, channels, n, sr):
 
 @pytest.fixture(scope="session")
 def ref():
-    """The checker: oracle/_ref = unmodified reference header + L1 restatement (prebuilt .so travels to the GPU box).
-    Where neither the prebuilt library nor the reference tree exists, fall back to the plain C++ port
+    """The checker: oracle/_ref = unmodified reference header + L1 restatement, built by __graft_entry__.build() (the
+    prebuilt .so travels to the GPU box).  Where the library was not built, fall back to the plain C++ port
     (oracle/stretch_port.cpp, pinned against oracle/_ref and the WASM golden vectors by test_oracle_golden.py); cases
     that need members the port does not restate skip themselves."""
     import ref_oracle
-    if not ref_oracle.available():
-        if os.path.exists("/root/reference/signalsmith-stretch.h"):
-            subprocess.run(["make", "-C", os.path.join(ROOT, "oracle"), "ref"], check=True, capture_output=True)
     if ref_oracle.available():
         return ref_oracle
     import types

@@ -16,7 +16,9 @@ def test_library_exports_every_declared_symbol():
     pkg = package()
     if not os.path.exists(pkg.LIBRARY_PATH):
         pkg.build()
-    lib = ctypes.CDLL(pkg.LIBRARY_PATH)
+    # through the package's loader, which brings in torch's HIP runtime first: a plain CDLL here would load a second HIP runtime
+    # into the process, and every GPU test after this one in the same session would then find no device
+    lib = pkg.load_library()
     names = header_symbols()
     assert len(names) >= 55
     missing = [n for n in names if not hasattr(lib, n)]

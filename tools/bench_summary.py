@@ -1,5 +1,5 @@
 """Prints the few numbers of a bench.py JSON line that matter while iterating:
-python bench.py ... | python tools/bench_summary.py [label]      or      python tools/bench_summary.py FILE.json [label]"""
+python bench.py --full ... | python tools/bench_summary.py [label]      or      python tools/bench_summary.py FILE.json [label]"""
 import json
 import os
 import sys

@@ -9,7 +9,7 @@ for round in 1 2; do
 for lib in "$@"; do
   name=$(basename $lib .so)
   if [ "$lib" = "product" ]; then unset SMST_LIBRARY; else export SMST_LIBRARY=$ROOT/$lib; fi
-  timeout 200 python bench.py --steps 20 --warmup 5 --no-cpu-baseline ${BENCH_ARGS:-} > $OUT/bench_${name}_$round.json 2> $OUT/bench_${name}_$round.err
+  timeout 200 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline ${BENCH_ARGS:-} > $OUT/bench_${name}_$round.json 2> $OUT/bench_${name}_$round.err
   python - <<PY
 import json
 try:

@@ -8,7 +8,7 @@ cd $ROOT
 for round in 1 2; do
 for spec in "$@"; do
   name=${spec%%|*}; envs=${spec#*|}
-  env $envs timeout 200 python bench.py --steps 20 --warmup 3 --no-cpu-baseline ${BENCH_ARGS:-} > $OUT/bench_${name}_$round.json 2> $OUT/bench_${name}_$round.err
+  env $envs timeout 200 python bench.py --full --steps 20 --warmup 3 --no-cpu-baseline ${BENCH_ARGS:-} > $OUT/bench_${name}_$round.json 2> $OUT/bench_${name}_$round.err
   python - <<PY
 import json
 try:

@@ -9,7 +9,7 @@ export SMST_LIBRARY_ALLOW_MISSING=1
 for c in $CONFIGS; do
 for name in "$@"; do
   if [ "$name" = "product" ]; then unset SMST_LIBRARY; else export SMST_LIBRARY=$ROOT/signalsmith-stretch_amd/variants/$name.so; fi
-  timeout 300 python bench.py --config $c --steps 5 --warmup 2 --no-cpu-baseline > $OUT/bench_${name}_c$c.json 2> $OUT/bench_${name}_c$c.err
+  timeout 300 python bench.py --full --config $c --steps 5 --warmup 2 --no-cpu-baseline > $OUT/bench_${name}_c$c.json 2> $OUT/bench_${name}_c$c.err
   python - <<PY
 import json
 try:

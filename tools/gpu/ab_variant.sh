@@ -10,7 +10,7 @@ export SMST_LIBRARY_ALLOW_MISSING=1
 for round in 1 2; do
 for name in product "$@"; do
   if [ "$name" = "product" ]; then unset SMST_LIBRARY; else export SMST_LIBRARY=$ROOT/signalsmith-stretch_amd/variants/$name.so; fi
-  timeout 300 python bench.py $ARGS --no-cpu-baseline --no-self-check > $OUT/${name}_$round.json 2> $OUT/${name}_$round.err
+  timeout 300 python bench.py --full $ARGS --no-cpu-baseline --no-self-check > $OUT/${name}_$round.json 2> $OUT/${name}_$round.err
   python -c "
 import json
 d = json.loads(open('$OUT/${name}_$round.json').read().strip().splitlines()[-1]); r = d['roofline']

@@ -8,7 +8,7 @@ cd $ROOT
 timeout 900 python -m pytest tests -m gpu -x -q > $OUT/gpu_tests.log 2>&1
 echo "pytest rc $?" >> $OUT/gpu_tests.log
 tail -n 15 $OUT/gpu_tests.log
-timeout 300 python bench.py --steps 20 --warmup 5 --no-cpu-baseline "$@" > $OUT/bench.json 2> $OUT/bench.err
+timeout 300 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline "$@" > $OUT/bench.json 2> $OUT/bench.err
 python - <<PY
 import json
 d = json.loads(open("$OUT/bench.json").read().strip().splitlines()[-1])

@@ -9,7 +9,7 @@ ROOT=${GRAFT_REPO_ROOT:-/root/repo}
 OUT=$ROOT/gpurun_out/$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-CMD="python $ROOT/bench.py --config 5 --streams $STREAMS --steps 1 --warmup 1 --no-cpu-baseline --no-serial-pass --no-self-check"
+CMD="python $ROOT/bench.py --full --config 5 --streams $STREAMS --steps 1 --warmup 1 --no-cpu-baseline --no-serial-pass --no-self-check"
 echo "streams $STREAMS" > $OUT/outcomes.txt
 timeout 300 rocprofv3 --kernel-trace --stats -d $OUT/trace -o t -f csv -- $CMD > $OUT/trace.log 2>&1; echo "trace rc $?" >> $OUT/outcomes.txt
 for K in kVocoderN kAnalyseFast kSynthFast kEmit kFeedScanA kCarry; do

@@ -12,7 +12,7 @@ mkdir -p "$OUT"
 export HSA_ENABLE_IPC_MODE_LEGACY=0
 for N in 1 2 4 8; do
   EXTRA=""; [ "$N" != 1 ] && EXTRA="--no-cpu-baseline"
-  MASTER_PORT=$((29600 + N)) python "$ROOT/bench.py" --gpus "$N" --config "$CONFIG" --steps 5 --warmup 2 $EXTRA > "$OUT/bench_c${CONFIG}_n${N}.json" 2> "$OUT/bench_c${CONFIG}_n${N}.err" \
+  MASTER_PORT=$((29600 + N)) python "$ROOT/bench.py" --full --gpus "$N" --config "$CONFIG" --steps 5 --warmup 2 $EXTRA > "$OUT/bench_c${CONFIG}_n${N}.json" 2> "$OUT/bench_c${CONFIG}_n${N}.err" \
     || { echo "N=$N: $(tail -n 1 "$OUT/bench_c${CONFIG}_n${N}.err")"; rm -f "$OUT/bench_c${CONFIG}_n${N}.json"; }
 done
 python - "$OUT" "$CONFIG" <<'PY'
