@@ -26,11 +26,12 @@
  * return SMST_ERR_INVALID with the limit in smst_last_error() beyond them:
  *   - 1 ... 16 channels per stream (the recurrence kernels size their per-lane channel arrays at compile time: 1-2 channels and 3-8 channels
  *     keep the per-bin records in LDS, 9-16 channels take the un-fused kernel pair with records through HBM -- slower, the same arithmetic);
- *   - fftSamples/2 = 2^k * {1, 3, 5} bands (the reference's own fast sizes), at most 19200: one FFT buffer of bands*8 bytes has to fit a
- *     CU's LDS.  Up to 9600 bands (every preset up to 96 kHz: presetDefault there has 6144) both ping-pong buffers do; beyond that --
+ *   - fftSamples/2 = 2^k * {1, 3, 5} bands (the reference's own fast sizes: {1, 2, 3, 4, 5, 6, 8} * 2^k), at most 16384 (the largest
+ *     of them below 19200: one FFT buffer of bands*8 bytes has to fit a CU's LDS).  Up to 9600 bands (every preset up to 96 kHz: presetDefault there has 6144) both ping-pong buffers do; beyond that --
  *     the presets at 176.4 / 192 kHz: 10240 / 12288 bands -- the second buffer lives in memory (slower per frame, the same arithmetic);
- *   - interval >= fftSamples/62 (the vertical step of the phase prediction, round(fftSamples/interval), has to fit the wavefront's
- *     skew); interval <= block.
+ *   - vertical step of the phase prediction, round(fftSamples/interval), at most 62 (interval >= fftSamples/62: it has to fit the
+ *     wavefront's skew) with 1-4 channels, at most 30 with 5-9 channels and at most 14 with 10-16 channels (the un-fused recurrence
+ *     keeps a history ring of a power of two >= step + 2 bins per channel in a CU's LDS); interval <= block.
  *   - Sample = float arithmetic only (the C++ drop-in accepts double buffers and converts at the boundary).
  *
  * Hardware queues: a call is pipelined over three HIP streams; in a process with streams of its own (an RCCL communicator is

@@ -123,7 +123,7 @@ struct IoArgs {
 // The generic FFT kernels ping-pong between two buffers of `bands` complex values: in LDS while both fit (150 KiB), else one of them in memory
 // (kAnalyse<true> / kSynth<true>: presetDefault / presetCheaper at 176.4 / 192 kHz).  One buffer must still fit.
 __host__ __device__ inline bool fftNeedsScratch(int bands) { return (size_t)bands*16 > (size_t)150*1024; }
-constexpr int kMaxBands = 150*1024/8; // 19200
+constexpr int kMaxBands = 150*1024/8; // 19200 bins of LDS; the largest band count {1,2,3,4,5,6,8}*2^k reaches below it is 16384
 
 struct WindowPad { int lo, hi; };
 __host__ __device__ inline WindowPad windowPad(int B, int M) {

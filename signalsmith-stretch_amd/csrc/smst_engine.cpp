@@ -112,16 +112,18 @@ Batch::Batch(int streams, int channels, int block, int interval, bool splitCompu
 	if (S < 1 || C < 1 || C > kMaxChannels || B < 4 || I < 1 || I > B) throw Error("invalid configuration (need 1.." + std::to_string(kMaxChannels) + " channels, interval <= block)");
 	N = 2*fastSizeAbove((B + 1)/2);
 	M = N/2;
-	if (M > kMaxBands) throw Error("block too long: " + std::to_string(M) + " bands, at most " + std::to_string(kMaxBands) + " (one FFT buffer of bands*8 bytes must fit a CU's LDS; up to 9600 bands both buffers do, beyond that the second one lives in memory)");
+	if (M > kMaxBands) throw Error("block too long: " + std::to_string(M) + " bands, at most 16384 (one FFT buffer of bands*8 bytes must fit a CU's LDS; up to 9600 bands both buffers do, beyond that the second one lives in memory)");
 	L = int(std::round(float(N)/float(I))); // longVerticalStep, signalsmith-stretch.h:636-637
 	if (L < 1) L = 1;
 	{
 		int ring = 4;
 		while (ring < L + 2) ring *= 2;
 		if (ring > 64) throw Error("interval too small relative to the FFT size (vertical step too long)");
-		// (9-16 channels, or a vertical step the fused kernels do not take: kChain keeps a ring of `ring` bins per channel and lane in LDS)
-		if (C > kMaxFusedChannels && ((size_t)C*ring*64 + (size_t)C*128)*sizeof(float2) > (size_t)160*1024)
-			throw Error("more than 8 channels need interval >= fftSamples/13 (the un-fused recurrence keeps a history ring per channel in LDS)");
+		// kChain (9-16 channels, a vertical step the fused kernels do not take, or SMST_NO_FUSE -- so any channel count) keeps a ring of
+		// `ring` bins per channel and lane in LDS: up to 4 channels the vertical step may be 62, 5-9 channels 30, 10-16 channels 14
+		if (((size_t)C*ring*64 + (size_t)C*128)*sizeof(float2) > (size_t)160*1024)
+			throw Error("vertical step round(fftSamples/interval) = " + std::to_string(L) + " too long for " + std::to_string(C) +
+			            " channels: at most 62 for 1-4 channels, 30 for 5-9, 14 for 10-16 (the un-fused recurrence keeps a history ring per channel in LDS)");
 	}
 	const FftPlan plan = makePlan(M, N);
 	try {

@@ -2,6 +2,7 @@
 This is NOT the product path (that is test_parity_gpu.py on a real gfx950); it runs in the GPU-less container."""
 import pytest
 
+import geometry_cases as gc
 import parity_cases as pc
 import scenarios
 
@@ -249,3 +250,32 @@ def test_continuous_equals_tiled_emu(emu, monkeypatch):
 
 def test_formant_stages_emu(emu, ref, monkeypatch):
     print(pc.case_formant_stages(emu, ref, monkeypatch, pc.SMALL, hops=14))
+
+
+# --- every accepted geometry (tests/geometry_cases.py): a subset here, the full grid in test_parity_gpu.py
+@pytest.mark.parametrize("M", [m for m in gc.band_counts() if m <= 1024] + [3072, 10240, 16384])
+def test_spectra_and_identity_every_band_count_emu(emu, ref, M):
+    """Band.input / .prevInput against a float64 DFT and the 1.0x identity: both blocks up to 1024 bands, block = fftSamples above."""
+    for block in (gc.blocks_for(M) if M <= 1024 else (2*M,)):
+        print(gc.case_spectra_and_identity(emu, ref, M, block))
+
+
+def test_fft_forms_spectra_emu(emu, ref, monkeypatch):
+    print(gc.case_fft_forms_spectra(emu, ref, monkeypatch, 2560))
+
+
+@pytest.mark.parametrize("C,L", [(1, 1), (2, 1), (1, 9), (2, 8), (3, 6), (3, 14), (5, 30), (2, 62), (9, 15), (16, 14)])
+def test_vertical_step_emu(emu, ref, C, L):
+    print(gc.case_vertical_step(emu, ref, C, L))
+
+
+def test_vertical_step_split_and_quanta_emu(emu, ref):
+    """split computation (the single-hop and across forms at their L edges) and 128-sample quanta"""
+    print(gc.case_vertical_step(emu, ref, 3, 5, split=True, legs=("forced", "free")))
+    gc.case_realtime_quanta_step(emu, ref, 3, 5)
+
+
+def test_accepted_geometries_run_emu(emu, monkeypatch):
+    """Dense (channels, bands, vertical step) grid: refused with the documented limit, or runs (the emulator checks every LDS request)."""
+    ran, refused = gc.case_accepted_geometries_run(emu, monkeypatch, range(1, 17), (2, 40, 2048), (1, 2, 5, 6, 7, 8, 14, 15, 30, 31, 59, 62, 63))
+    assert (5, 2048, 59) in refused and (8, 2048, 59) in refused and (4, 2048, 62) in ran and (9, 2048, 30) in ran

@@ -4,6 +4,7 @@ import numpy as np
 import pytest
 
 from conftest import package, rel_rms, synth_input
+import geometry_cases as gc
 import parity_cases as pc
 import scenarios
 
@@ -762,3 +763,40 @@ def test_presets_at_192k(hip, ref, preset):
     horizon-aware bound; the WASM fixtures of the same geometries run in test_golden."""
     n = 96000
     _batch_vs_ref(hip, ref, 3, 2, 192000, n, int(n*1.25), dict(preset=preset, sample_rate=192000.0), preset, "%s @ 192 kHz" % preset)
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# Every accepted geometry (tests/geometry_cases.py): every band count, every vertical-step form, the (channels, bands, step) boundary grid
+# ---------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("M,block", [(m, blk) for m in gc.band_counts() for blk in gc.blocks_for(m)])
+def test_spectra_and_identity_every_band_count(hip, ref, M, block):
+    """Band.input / .prevInput of every stream and channel against a float64 DFT (rel-RMS <= 1e-6, max bin <= 1e-5), and the 1.0x identity
+    (<= 2e-6), at all 39 band counts, with block = fftSamples and with the shortest block above the previous band count."""
+    print(gc.case_spectra_and_identity(hip, ref, M, block))
+
+
+@pytest.mark.parametrize("M", gc.FAST_SIZES)
+def test_fft_forms_spectra(hip, ref, monkeypatch, M):
+    print(gc.case_fft_forms_spectra(hip, ref, monkeypatch, M))
+
+
+@pytest.mark.parametrize("C,L", [(c, l) for l in sorted(gc.STEP_GEOMETRIES) for c in gc.SWEEP_CHANNELS if l <= gc.expected_limit(c)])
+def test_vertical_step(hip, ref, C, L):
+    print(gc.case_vertical_step(hip, ref, C, L))
+
+
+@pytest.mark.parametrize("C,L", [(2, 5), (2, 6), (3, 5), (3, 6), (8, 5), (1, 9)])
+def test_vertical_step_split(hip, ref, C, L):
+    """split computation: one hop per call, the single-hop and across forms up to their edge (L = 5) and the forms past it"""
+    print(gc.case_vertical_step(hip, ref, C, L, split=True, legs=("forced", "free")))
+
+
+@pytest.mark.parametrize("C,L", [(2, 5), (2, 6), (3, 5), (3, 6), (1, 9)])
+def test_vertical_step_realtime_quanta(hip, ref, C, L):
+    gc.case_realtime_quanta_step(hip, ref, C, L)
+
+
+def test_accepted_geometries_run(hip, monkeypatch):
+    """(channels, bands, vertical step) boundary grid under SMST_CHECK_LAUNCHES=1: refused with the documented limit, or runs."""
+    ran, refused = gc.case_accepted_geometries_run(hip, monkeypatch, range(1, 17), (2, 40, 2048, 16384), (1, 2, 5, 6, 7, 8, 14, 15, 30, 31, 59, 62, 63))
+    assert (5, 2048, 59) in refused and (4, 16384, 62) in ran and (9, 2048, 30) in ran and (16, 16384, 14) in ran
