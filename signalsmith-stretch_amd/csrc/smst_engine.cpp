@@ -1070,9 +1070,9 @@ void Batch::runTilesRange(const TileRun &run, int tile0, int tile1, int carryFir
 		}
 	}
 	if (!serial) { // everything the caller can observe is ordered on `st` again
-		for (int i = 0; i < 2 && i < q - tile0; ++i) {
-			SMST_HIP(hipStreamWaitEvent(st, evChain[i], 0));
-			SMST_HIP(hipStreamWaitEvent(st, evSynth[i], 0));
+		for (int i = 0; i < 2 && i < q - tile0; ++i) { // join the slots this range used: (tile0 + i) & 1, not i (tile0 may be odd)
+			SMST_HIP(hipStreamWaitEvent(st, evChain[(tile0 + i) & 1], 0));
+			SMST_HIP(hipStreamWaitEvent(st, evSynth[(tile0 + i) & 1], 0));
 		}
 	}
 }
@@ -1185,8 +1185,8 @@ void Batch::runTilesContinuous(const TileRun &run, int tile0, int tile1, int car
 	finishTile(tile1 - 1, tile1 - 1);
 	if (!serial) {
 		for (int i = 0; i < 3 && i < tile1 - tile0; ++i) { // everything the caller can observe is ordered on `st` again
-			SMST_HIP(hipStreamWaitEvent(st, evChain[i], 0));
-			SMST_HIP(hipStreamWaitEvent(st, evSynth[i], 0));
+			SMST_HIP(hipStreamWaitEvent(st, evChain[(tile0 + i)%3], 0)); // join the slots this segment used: (tile0 + i) % 3, not i
+			SMST_HIP(hipStreamWaitEvent(st, evSynth[(tile0 + i)%3], 0));
 		}
 	}
 }

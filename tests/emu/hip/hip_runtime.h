@@ -101,11 +101,7 @@ static inline hipError_t hipSetDevice(int) { return 0; }
 static inline hipError_t hipGetDeviceCount(int *n) { *n = 1; return 0; }
 enum hipDeviceAttribute_t { hipDeviceAttributeMultiprocessorCount };
 static inline hipError_t hipDeviceGetAttribute(int *v, hipDeviceAttribute_t, int) { *v = 8; return 0; } // a small machine: persistent kernels loop over their jobs
-static inline hipError_t hipStreamCreateWithFlags(hipStream_t *s, unsigned) { *s = (hipStream_t)1; return 0; }
-static inline hipError_t hipStreamSynchronize(hipStream_t) { return 0; }
-static inline hipError_t hipDeviceSynchronize() { return 0; }
 static inline hipError_t hipDeviceGetStreamPriorityRange(int *lo, int *hi) { *lo = 0; *hi = 0; return 0; }
-static inline hipError_t hipStreamCreateWithPriority(hipStream_t *s, unsigned, int) { *s = (hipStream_t)1; return 0; }
 #define __builtin_amdgcn_s_setprio(x) ((void)0)
 #define __builtin_amdgcn_readfirstlane(x) (x) /* used on wave-uniform values only */
 #define __builtin_amdgcn_s_sleep(x) emuSyncThreads()
@@ -125,31 +121,53 @@ static inline int atomicMax(int *p, int v) { int o = *p; if (v > o) *p = v; retu
 #define __hip_atomic_load(p, order, scope) (*(volatile int *)(p))
 #define __hip_atomic_store(p, v, order, scope) (*(volatile int *)(p) = (v))
 #define __hip_atomic_fetch_add(p, v, order, scope) atomicAdd((p), (v))
-static inline hipError_t hipStreamDestroy(hipStream_t) { return 0; }
 static inline hipError_t hipMemGetInfo(size_t *freeB, size_t *totalB) { *freeB = *totalB = (size_t)24 << 30; return 0; }
-static inline hipError_t hipMalloc(void **p, size_t n) { *p = std::calloc(n ? n : 1, 1); return *p ? 0 : 2; }
-static inline hipError_t hipFree(void *p) { std::free(p); return 0; }
 #define hipHostMallocDefault 0
-static inline hipError_t hipHostMalloc(void **p, size_t n, unsigned) { *p = std::calloc(n ? n : 1, 1); return *p ? 0 : 2; }
-static inline hipError_t hipHostFree(void *p) { std::free(p); return 0; }
 static inline hipError_t hipMemcpy(void *d, const void *s, size_t n, hipMemcpyKind) { std::memcpy(d, s, n); return 0; }
 static inline hipError_t hipMemcpy2D(void *d, size_t dpitch, const void *s, size_t spitch, size_t width, size_t height, hipMemcpyKind) {
 	for (size_t r = 0; r < height; ++r) std::memcpy(static_cast<char *>(d) + r*dpitch, static_cast<const char *>(s) + r*spitch, width);
 	return 0;
 }
-static inline hipError_t hipMemcpyAsync(void *d, const void *s, size_t n, hipMemcpyKind, hipStream_t) { std::memcpy(d, s, n); return 0; }
 static inline hipError_t hipMemset(void *d, int v, size_t n) { std::memset(d, v, n); return 0; }
-static inline hipError_t hipMemsetAsync(void *d, int v, size_t n, hipStream_t) { std::memset(d, v, n); return 0; }
-static inline hipError_t hipEventCreate(hipEvent_t *e) { *e = nullptr; return 0; }
 #define hipEventDisableTiming 2
 #define hipEventDisableSystemFence 0x20000000
-static inline hipError_t hipEventCreateWithFlags(hipEvent_t *e, unsigned) { *e = nullptr; return 0; }
-static inline hipError_t hipStreamWaitEvent(hipStream_t, hipEvent_t, unsigned) { return 0; }
-static inline hipError_t hipEventRecord(hipEvent_t, hipStream_t) { return 0; }
-static inline hipError_t hipEventSynchronize(hipEvent_t) { return 0; }
 static inline hipError_t hipEventElapsedTime(float *ms, hipEvent_t, hipEvent_t) { *ms = 0; return 0; }
-static inline hipError_t hipEventDestroy(hipEvent_t) { return 0; }
 
-void emuLaunch(dim3 grid, dim3 block, size_t ldsBytes, const std::function<void()> &body);
+// ---- streams and events (tests/emu/hip_emu.cpp).  A stream is a FIFO of operations; when they run is the schedule's choice
+// (SMST_EMU_SCHEDULE, read when a stream is created, or smst_emu_set_schedule):
+//   eager        every operation runs when it is enqueued (program order; the default)
+//   lazy         nothing runs until a host-blocking call needs it, and then only what the HIP contract says that call waits for
+//   random:SEED  as lazy, but what a host-blocking call needs runs in a seeded random order that keeps only each stream's FIFO order
+//                and the event edges (a later overwrite on one stream may overtake an earlier reader on another)
+// Modelled contract: an event record captures its stream's tail at that moment (re-recording replaces it); a wait binds to the
+// event's latest record at the time of the wait call (a never-recorded event is no wait at all); streams are non-blocking, so
+// the synchronous hipMemcpy / hipMemset (null stream) run at once; hipFree / hipHostFree synchronise the device.
+// hipMemcpyAsync reads / writes device and hipHostMalloc memory when the copy runs; a pageable source is staged at enqueue
+// (HIP may do either: the copy from pageable memory below is the one choice that cannot hide a missing edge on the device side).
+hipError_t hipStreamCreateWithFlags(hipStream_t *s, unsigned flags);
+hipError_t hipStreamCreateWithPriority(hipStream_t *s, unsigned flags, int priority);
+hipError_t hipStreamDestroy(hipStream_t s);
+hipError_t hipStreamSynchronize(hipStream_t s);
+hipError_t hipDeviceSynchronize();
+hipError_t hipMalloc(void **p, size_t n);
+hipError_t hipFree(void *p);
+hipError_t hipHostMalloc(void **p, size_t n, unsigned flags);
+hipError_t hipHostFree(void *p);
+hipError_t hipMemcpyAsync(void *d, const void *s, size_t n, hipMemcpyKind kind, hipStream_t stream);
+hipError_t hipMemsetAsync(void *d, int v, size_t n, hipStream_t stream);
+hipError_t hipEventCreate(hipEvent_t *e);
+hipError_t hipEventCreateWithFlags(hipEvent_t *e, unsigned flags);
+hipError_t hipEventDestroy(hipEvent_t e);
+hipError_t hipEventRecord(hipEvent_t e, hipStream_t s);
+hipError_t hipStreamWaitEvent(hipStream_t s, hipEvent_t e, unsigned flags);
+hipError_t hipEventSynchronize(hipEvent_t e);
+
+void emuLaunch(dim3 grid, dim3 block, size_t ldsBytes, const std::function<void()> &body, const char *name = "kernel");
+void emuEnqueue(hipStream_t stream, const char *name, std::function<void()> op);
+// the arguments are evaluated and copied at the launch, as HIP captures them (a lambda over the argument EXPRESSIONS would read
+// members of the launching object when the launch runs)
+template <typename K, typename... A> static inline void emuLaunchKernel(const char *name, hipStream_t stream, dim3 grid, dim3 block, size_t lds, K kernel, A... args) {
+	emuEnqueue(stream, name, [=]() mutable { emuLaunch(grid, block, lds, [&]() { kernel(args...); }, name); });
+}
 #define hipLaunchKernelGGL(kernel, grid, block, lds, stream, ...) \
-	emuLaunch((grid), (block), (lds), [=]() { kernel(__VA_ARGS__); })
+	emuLaunchKernel(#kernel, (stream), (grid), (block), (lds), kernel, ##__VA_ARGS__)

@@ -1184,14 +1184,73 @@ def case_synth_emit_equals_two_kernels(lib, monkeypatch, presets=(("cheaper", 48
             assert np.array_equal(outs[0], outs[1]), (preset, sr, split, float(np.abs(outs[0] - outs[1]).max()))
 
 
+# Tile patterns of SMST_CONTINUOUS=1 at interval 480 (N: a tile run tile by tile, C: a tile of the continuous wavefront): the calls, as
+# (output samples, input samples) per stream, and the launches of the LAST call -- (kVocoderCont, tile-by-tile kVocoder) -- that prove
+# the pattern.  A late N tile needs a hop that draws random time factors (an input interval below half the output interval) in that
+# tile only: the interval of a stream is the same for every hop of a call but for rounding, so stream 0 below runs at about 2x, where
+# its intervals are 240 samples except ONE of 239 (hop 209, tile 3).
+#   NCC    the first call after a reset (its first hop draws random time factors), 150 hops: the continuous run [1, 3) starts at an odd tile
+#   NCCN   stream 1 fires its first hop in call 2 (tile 0) and 256 hops; stream 0 makes tile 3 tile-by-tile: [1, 3) continuous, then tile 3
+#   NNNCC  stream 0 at 3x (random time factors in all its 150 hops: tiles 0-2), stream 1 at 1x for 300 hops: [3, 5) continuous
+_I480 = 480
+CONTINUOUS_PATTERNS = {
+    "NCC": ([([150*_I480], [150*_I480])], (2, 1)),
+    "NCCN": ([([1074, 0], [537, 0]), ([100707, 256*_I480], [50353, 256*_I480])], (2, 2)),
+    "NNNCC": ([([150*_I480, 300*_I480], [50*_I480, 300*_I480])], (2, 3)),
+}
+TILED_FORMS = ("vocoder_aligned", "vocoder_staged", "vocoder_gather")
+
+
+def case_continuous_pattern(lib, monkeypatch, pattern, channels=1, geometry=dict(block=1920, interval=480)):
+    """One tile pattern of CONTINUOUS_PATTERNS, continuous against tile by tile, through the host-memory path (the read-back on `st`
+    that the end of a call's tiles must be joined to): outputs of every call -- the pattern's and one call after it -- and the carried
+    state must be bit-identical, and the launch counters must show the pattern."""
+    pkg = package()
+    calls, expect = CONTINUOUS_PATTERNS[pattern]
+    assert geometry["interval"] == _I480
+    S = len(calls[0][0])
+    calls = calls + [([40*_I480]*S, [40*_I480]*S)]
+    x = np.stack([synth_input(s, channels, sum(max(c[1]) for c in calls), 48000) for s in range(S)])
+    results = []
+    for tiled in (False, True):
+        if tiled:
+            monkeypatch.delenv("SMST_CONTINUOUS", raising=False)
+        else:
+            monkeypatch.setenv("SMST_CONTINUOUS", "1")
+        b = pkg.StretchBatch(S, channels, lib=lib, **geometry)
+        outs, pos = [], 0
+        for i, (nout, nin) in enumerate(calls):
+            nout, nin = np.asarray(nout, np.int32), np.asarray(nin, np.int32)
+            before = pkg.launch_count("vocoder_continuous", lib), sum(pkg.launch_count(k, lib) for k in TILED_FORMS)
+            outs.append(np.array(b.process(np.ascontiguousarray(x[:, :, pos:pos + int(nin.max())]), nout, in_samples=nin), copy=True))
+            pos += int(nin.max())
+            grew = pkg.launch_count("vocoder_continuous", lib) - before[0], sum(pkg.launch_count(k, lib) for k in TILED_FORMS) - before[1]
+            if i == len(calls) - 2:
+                assert grew == ((0, sum(expect)) if tiled else expect), (pattern, "tiled" if tiled else "continuous", grew)
+        outs.append([np.concatenate([b.debug_state(s, w).ravel() for w in (0, 1, 2, 3)]) for s in range(S)])
+        b.close()
+        results.append(outs)
+    monkeypatch.delenv("SMST_CONTINUOUS", raising=False)
+    for i, (p, q) in enumerate(zip(results[0][:-1], results[1][:-1])):
+        assert np.array_equal(p, q), (pattern, "call", i, float(np.abs(p - q).max()), np.argwhere(p != q)[:4].tolist())
+    for s in range(S):
+        assert np.array_equal(results[0][-1][s], results[1][-1][s]), (pattern, "state", s)
+    assert float(np.abs(results[0][-2]).max()) > 0.05
+    return {pattern: "bit-identical, launches %s" % (expect,)}
+
+
 def case_continuous_equals_tiled(lib, monkeypatch, geometry=dict(block=1920, interval=480), channel_counts=(2, 1), streams=3, ratios=(1.5, 1.0),
-                                 seconds=None):
+                                 seconds=None, pattern=None):
     """The recurrence as ONE wavefront through all tiles of a call (kVocoderCont: lane r takes hops r, r + 64, ... without draining,
     a launch finishes tile t-1 and begins tile t; SMST_CONTINUOUS=1) against the tile-by-tile kernel (the default): same records, same
     arithmetic, so outputs AND the state a call leaves behind must be bit-identical -- over three calls (the second and third start
     from the state the continuous form handed over; the third is short: one tile, the tile form on both sides), with ragged stream
     lengths (a stream whose last tile is not the call's last), at 1.5x (every hop re-analyses its previous spectrum) and at 1.0x
-    (Band.prevInput = the hop before's input, across the tile boundary).  The launch counters prove which form ran."""
+    (Band.prevInput = the hop before's input, across the tile boundary).  The launch counters prove which form ran.
+    pattern: one of CONTINUOUS_PATTERNS instead (case_continuous_pattern), at interval 480."""
+    if pattern is not None:
+        return {"%s %dch" % (pattern, C): case_continuous_pattern(lib, monkeypatch, pattern, channels=C, geometry=geometry)[pattern]
+                for C in channel_counts}
     pkg = package()
     geometry = dict(geometry)
     sr = geometry.pop("sr", 48000)

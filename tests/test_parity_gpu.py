@@ -735,12 +735,14 @@ def test_split_freq_map_mid_interval(hip, ref):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("variant", ["small", "default48", "default96_mono"])
+@pytest.mark.parametrize("variant", ["small", "default48", "default96_mono", "pattern_NCC", "pattern_NCCN", "pattern_NNNCC"])
 def test_continuous_equals_tiled(hip, monkeypatch, variant):
     """kVocoderCont (one wavefront through the tiles of a call) against kVocoder tile by tile: bit-identical outputs and carried state;
     the launch counters prove which ran.  On the device this is also the test of the kernel's own load tracking (smst_async.h) and of
     row 0 reading back, through memory, what the same workgroup's writer wave stored a few hundred blocks earlier."""
-    if variant == "small":
+    if variant.startswith("pattern_"):  # the tile patterns that reach the end-of-segment joins (tests/test_stream_order_emu.py)
+        _report("continuous_equals_tiled/" + variant, pc.case_continuous_equals_tiled(hip, monkeypatch, channel_counts=(1, 2), pattern=variant[8:]))
+    elif variant == "small":
         _report("continuous_equals_tiled/small", pc.case_continuous_equals_tiled(hip, monkeypatch))
     elif variant == "default48":
         _report("continuous_equals_tiled/default48", pc.case_continuous_equals_tiled(hip, monkeypatch, geometry=dict(preset="default", interval=1440), channel_counts=(2,), streams=9))
