@@ -13,6 +13,7 @@
 #include <cmath>
 #include <cstddef>
 #include <functional>
+#include <memory>
 #include <random>
 #include <stdexcept>
 #include <type_traits>
@@ -45,6 +46,7 @@ struct SignalsmithStretch {
 	}
 	SignalsmithStretch &operator=(const SignalsmithStretch &other) {
 		if (this != &other) {
+			wait(); // (a request of processAsync() is delivered before the object is replaced)
 			smst_stretch *copy = nullptr;
 			if (smst_clone(&copy, other.h()) != SMST_OK) throw std::runtime_error(smst_last_error());
 			smst_destroy(handle);
@@ -55,18 +57,24 @@ struct SignalsmithStretch {
 		return *this;
 	}
 	SignalsmithStretch(SignalsmithStretch &&other) noexcept : handle(other.handle), channels(other.channels), seed(other.seed),
-		inPlanar(std::move(other.inPlanar)), outPlanar(std::move(other.outPlanar)), inPtrs(std::move(other.inPtrs)), outPtrs(std::move(other.outPtrs)) {
+		inPlanar(std::move(other.inPlanar)), outPlanar(std::move(other.outPlanar)), inPtrs(std::move(other.inPtrs)), outPtrs(std::move(other.outPtrs)),
+		asyncScatter(std::move(other.asyncScatter)) { // (a request of processAsync() moves along: the buffers it points to are the vectors' heap blocks)
 		other.handle = nullptr;
 		other.channels = 0;
+		other.asyncScatter = nullptr;
 	}
 	SignalsmithStretch &operator=(SignalsmithStretch &&other) noexcept {
 		if (this != &other) {
-			smst_destroy(handle);
+			smst_destroy(handle); // (runs a request that is still pending: its buffers are released only below)
 			handle = other.handle;
 			channels = other.channels;
 			seed = other.seed;
+			inPlanar = std::move(other.inPlanar); outPlanar = std::move(other.outPlanar);
+			inPtrs = std::move(other.inPtrs); outPtrs = std::move(other.outPtrs);
+			asyncScatter = std::move(other.asyncScatter);
 			other.handle = nullptr;
 			other.channels = 0;
+			other.asyncScatter = nullptr;
 		}
 		return *this;
 	}
@@ -110,12 +118,14 @@ struct SignalsmithStretch {
 
 	template <class Inputs>
 	void seek(Inputs &&inputs, int inputSamples, double playbackRate) {
+		wait();
 		gather(inputs, inputSamples, 0);
 		check(smst_seek(h(), inPtrs.data(), inputSamples, playbackRate));
 	}
 	int seekLength() const { return smst_seek_length(h()); }
 	template <class Inputs>
 	void outputSeek(Inputs &&inputs, int inputLength) {
+		wait();
 		gather(inputs, inputLength, 0);
 		check(smst_output_seek(h(), inPtrs.data(), inputLength));
 	}
@@ -129,6 +139,7 @@ struct SignalsmithStretch {
 #ifdef SIGNALSMITH_STRETCH_PROFILE_PROCESS_START
 		SIGNALSMITH_STRETCH_PROFILE_PROCESS_START(inputSamples, outputSamples);
 #endif
+		wait();
 		gather(inputs, inputSamples, 0);
 		prepareOut(outputSamples);
 		// The reference announces every step of a block (STEP(step, steps)) and closes it (ENDSTEP) as the steps run, interleaved with the
@@ -153,12 +164,14 @@ struct SignalsmithStretch {
 	}
 	template <class Outputs>
 	void flush(Outputs &&outputs, int outputSamples, Sample playbackRate = 0) {
+		wait();
 		prepareOut(outputSamples);
 		check(smst_flush(h(), outPtrs.data(), outputSamples, playbackRate));
 		scatter(outputs, outputSamples);
 	}
 	template <class Inputs, class Outputs>
 	bool exact(Inputs &&inputs, int inputSamples, Outputs &&outputs, int outputSamples) {
+		wait();
 		gather(inputs, inputSamples, 0);
 		prepareOut(outputSamples);
 		int rc = smst_exact(h(), inPtrs.data(), inputSamples, outPtrs.data(), outputSamples);
@@ -167,7 +180,60 @@ struct SignalsmithStretch {
 		return rc == SMST_OK;
 	}
 
+	// ---- EXTENSION: nothing below exists in the reference (include/smst.h, group 3) ----------------------------------------------
+	// N objects called in a loop cost N device round trips per step.  Objects added to a Pool record their call with processAsync();
+	// Pool::run() -- or the first wait() -- runs everything pending as ONE batched device submission per configuration.  Every object's
+	// output is bit for bit what process() gives.  Copying a pooled object gives an unpooled copy; moving keeps the membership.
+	struct Pool {
+		Pool() : Pool(defaultDevice()) {}
+		explicit Pool(int device) {
+			if (smst_pool_create(&pool, device) != SMST_OK) throw std::runtime_error(smst_last_error());
+		}
+		~Pool() { smst_pool_destroy(pool); } // runs what is pending; the members stay valid objects and keep their state
+		Pool(const Pool &) = delete;
+		Pool &operator=(const Pool &) = delete;
+		Pool(Pool &&other) noexcept : pool(other.pool) { other.pool = nullptr; }
+		void add(SignalsmithStretch &stretch) { check(smst_pool_attach(pool, stretch.h())); }
+		void remove(SignalsmithStretch &stretch) { check(smst_pool_detach(stretch.h())); }
+		void run() { check(smst_pool_run(pool)); }
+		int members() const { return smst_pool_members(pool); }
+		int pending() const { return smst_pool_pending(pool); }
+	private:
+		smst_pool *pool = nullptr;
+	};
+	// process() in two halves.  `outputs` is written by wait(): an lvalue must stay alive until then, an rvalue (a temporary array of
+	// pointers, a view) is kept by the object.  `inputs` is read here.  Between the two, any call on this object that carries samples
+	// (process, seek, flush, ...) waits first.  On an object that is in no pool this is process() itself (without the profiling hooks).
+	template <class Inputs, class Outputs>
+	void processAsync(Inputs &&inputs, int inputSamples, Outputs &&outputs, int outputSamples) {
+		wait();
+		gather(inputs, inputSamples, 0);
+		prepareOut(outputSamples);
+		// (the object keeps the pointer arrays and the converted planes -- inPtrs / outPtrs, inPlanar / outPlanar -- until wait())
+		asyncScatter = scatterLater(std::forward<Outputs>(outputs), outputSamples, std::is_lvalue_reference<Outputs>());
+		const int rc = smst_process_begin(h(), inPtrs.data(), inputSamples, outPtrs.data(), outputSamples);
+		if (rc != SMST_OK) { asyncScatter = nullptr; check(rc); }
+	}
+	void wait() {
+		if (!asyncScatter) return;
+		const int rc = smst_process_end(h());
+		std::function<void(SignalsmithStretch &)> deliver;
+		deliver.swap(asyncScatter);
+		check(rc);
+		deliver(*this);
+	}
+
 private:
+	template <class Outputs>
+	static std::function<void(SignalsmithStretch &)> scatterLater(Outputs &outputs, int n, std::true_type) {
+		Outputs *target = &outputs;
+		return [target, n](SignalsmithStretch &self) { self.scatter(*target, n); };
+	}
+	template <class Outputs>
+	static std::function<void(SignalsmithStretch &)> scatterLater(Outputs &&outputs, int n, std::false_type) {
+		auto kept = std::make_shared<typename std::decay<Outputs>::type>(std::move(outputs));
+		return [kept, n](SignalsmithStretch &self) { self.scatter(*kept, n); };
+	}
 	mutable smst_stretch *handle = nullptr; // null only in a moved-from object, until its next use
 	int channels = 0;
 	long seed = 0;
@@ -178,6 +244,7 @@ private:
 	std::vector<float> inPlanar, outPlanar;
 	std::vector<const float *> inPtrs;
 	std::vector<float *> outPtrs;
+	std::function<void(SignalsmithStretch &)> asyncScatter; // set between processAsync() and wait(): converts the planes back into the caller's buffers
 
 	static int defaultDevice() { return smst_default_device(); }
 	static void check(int rc) {

@@ -22,6 +22,9 @@
  *      until a stream passed to smst_batch_signal_stream() has caught up); the
  *      host-side part of a call (silence gate, block scheduler) overlaps the kernels of the previous call.
  *
+ *  (3) pool API -- an EXTENSION the reference does not have: single-stream handles register with a pool, process() is split into a
+ *      "begin" and an "end", and everything pending runs as ONE batched device submission per geometry.  See the section below.
+ *
  * Limits the reference does not have (signalsmith-stretch.h:71-94 accepts any channel count and block size); configure / create
  * return SMST_ERR_INVALID with the limit in smst_last_error() beyond them:
  *   - 1 ... 16 channels per stream (the recurrence kernels size their per-lane channel arrays at compile time: 1-2 channels and 3-8 channels
@@ -138,6 +141,55 @@ int smst_flush(smst_stretch *h, float *const *outputs, int outputSamples, float 
 /* outputSeek / exact: signalsmith-stretch.h:173-204, 468-491 */
 int smst_output_seek(smst_stretch *h, const float *const *inputs, int inputLength);
 int smst_exact(smst_stretch *h, const float *const *inputs, int inputSamples, float *const *outputs, int outputSamples);
+
+/* ---------------------------------------------------------------------------------------------------------
+ * (3) pool API -- EXTENSION: nothing in this section exists in the reference
+ *
+ * The reference's calling pattern -- one object per stream, process() in a loop -- costs one device round trip per object and call (two
+ * PCIe copies, ~60 launches, two synchronisations for ONE stream's work).  A synchronous per-object process() cannot be pooled behind the
+ * caller's back; this section makes the pooling explicit.  Handles are attached to a pool; smst_process_begin() records a request and
+ * returns; smst_pool_run() (or the first smst_process_end() that finds its request still pending) runs EVERYTHING pending: the members are
+ * grouped by (channels, block, interval, split), each group is one batch engine whose streams are the members' slots (the slot count grows
+ * geometrically, slots of detached members are reused), and a run issues exactly ONE engine call per group that has pending requests --
+ * each member with its own sample counts, members without a request masked out -- through the pool's own pinned staging: one gather of
+ * the members' planes, one host-to-device copy, one copy back, one scatter.  Steady-state runs allocate nothing.
+ *
+ * Identity: a member's output is bit for bit what the same handle, unattached, produces for the same sequence of calls, whatever the other
+ * members do -- seeded random time factors beyond 2x included.  Attaching, detaching, a regrowth of the group and the destruction of the
+ * pool in the middle of a stream change nothing in what follows.
+ *
+ * Program order per object: at most ONE request is pending per handle.  These calls on a member whose request is pending first run the
+ * pool, then act: a second smst_process_begin, smst_process, every setter, seek, flush, output_seek, exact, reset, configure / presets,
+ * smst_clone, smst_destroy, smst_block_steps, smst_blocks_started.  configure moves the member to its new geometry's group.  Every call of
+ * section (1) works unchanged on a member and is synchronous as ever; it runs on the member's slot alone.  A clone of a member is an
+ * unattached, independent handle.
+ *
+ * LIFETIME: `inputs` / `outputs` given to smst_process_begin -- the pointer arrays AND the planes they point to -- must stay valid and
+ * untouched until the request has run (smst_process_end on that handle, or a smst_pool_run, has returned).
+ *
+ * Threading: a pool and its members are used from one thread at a time, as a reference object is.
+ * ------------------------------------------------------------------------------------------------------- */
+typedef struct smst_pool smst_pool;
+int smst_pool_create(smst_pool **out, int device);
+/* runs what is pending, then detaches every member: the members stay valid handles and keep their state */
+void smst_pool_destroy(smst_pool *p);
+/* configured or not; the handle must live on the pool's device and not be attached already (SMST_ERR_INVALID) */
+int smst_pool_attach(smst_pool *p, smst_stretch *h);
+/* back to an engine of its own, the state carried over (a pending request runs first) */
+int smst_pool_detach(smst_stretch *h);
+int smst_pool_members(const smst_pool *p);
+int smst_pool_pending(const smst_pool *p);
+/* everything pending: ONE engine call per geometry group.  A failure is reported here and by smst_process_end of every member it affected. */
+int smst_pool_run(smst_pool *p);
+/* On a member: records the request (SMST_ERR_INVALID for an unconfigured handle, negative counts, or null buffers with a non-zero count).
+ * On an unattached handle: smst_process itself, so code written for the extension runs without a pool. */
+int smst_process_begin(smst_stretch *h, const float *const *inputs, int inputSamples, float *const *outputs, int outputSamples);
+/* Runs the pool if h's request is still pending; returns the status of h's newest request (unattached: what smst_process_begin returned). */
+int smst_process_end(smst_stretch *h);
+/* test hooks: engine calls issued by runs since the pool was created; device / pinned allocations and engine (re)constructions of the
+ * pool -- the latter must stand still across steady-state runs */
+long long smst_pool_debug_engine_calls(const smst_pool *p);
+long long smst_pool_debug_allocation_events(const smst_pool *p);
 
 /* ---------------------------------------------------------------------------------------------------------
  * (2) batch API

@@ -65,6 +65,18 @@ _SIGNATURES = {
     "smst_flush": (C.c_int, [C.c_void_p, C.POINTER(_fp), C.c_int, C.c_float]),
     "smst_output_seek": (C.c_int, [C.c_void_p, C.POINTER(_fp), C.c_int]),
     "smst_exact": (C.c_int, [C.c_void_p, C.POINTER(_fp), C.c_int, C.POINTER(_fp), C.c_int]),
+    # pool (extension)
+    "smst_pool_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_int]),
+    "smst_pool_destroy": (None, [C.c_void_p]),
+    "smst_pool_attach": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "smst_pool_detach": (C.c_int, [C.c_void_p]),
+    "smst_pool_members": (C.c_int, [C.c_void_p]),
+    "smst_pool_pending": (C.c_int, [C.c_void_p]),
+    "smst_pool_run": (C.c_int, [C.c_void_p]),
+    "smst_process_begin": (C.c_int, [C.c_void_p, C.POINTER(_fp), C.c_int, C.POINTER(_fp), C.c_int]),
+    "smst_process_end": (C.c_int, [C.c_void_p]),
+    "smst_pool_debug_engine_calls": (_ll, [C.c_void_p]),
+    "smst_pool_debug_allocation_events": (_ll, [C.c_void_p]),
     # batch
     "smst_batch_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_long]),
     "smst_batch_create_preset": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, C.c_long]),
@@ -536,6 +548,25 @@ class SignalsmithStretch:
         a, p = self._in(x)
         _check(self.lib, self.lib.smst_output_seek(self.h, p, a.shape[1]))
 
+    # --- extension (include/smst.h group 3): the two halves of process() for an object in a StretchPool
+    def processAsync(self, x, out_samples):
+        """Records process(x, out_samples) with the object's pool; wait() returns the output.  The buffers are kept alive here until then.
+        On an object that is in no pool this is process() itself, and wait() hands its result over."""
+        a, p = self._in(x)
+        out = np.zeros((self.channels, max(out_samples, 1)), np.float32)
+        po = self._planes(out)
+        self._request = (a, p, out, po, out_samples)
+        _check(self.lib, self.lib.smst_process_begin(self.h, p, a.shape[1], po, out_samples))
+
+    def wait(self):
+        """Runs the pool if the request is still pending; -> the [C, out_samples] output of the newest processAsync()."""
+        rc = self.lib.smst_process_end(self.h)
+        request, self._request = getattr(self, "_request", None), None
+        _check(self.lib, rc)
+        if request is None:
+            raise StretchError("wait() without processAsync()")
+        return request[2][:, :request[4]]
+
     def exact(self, x, out_samples):
         a, p = self._in(x)
         out = np.zeros((self.channels, max(out_samples, 1)), np.float32)
@@ -544,3 +575,35 @@ class SignalsmithStretch:
             return out[:, :out_samples], False
         _check(self.lib, rc)
         return out[:, :out_samples], True
+
+
+class StretchPool:
+    """EXTENSION (the reference has nothing like it): SignalsmithStretch objects added to a pool record their process() calls with
+    processAsync(); run() -- or the first wait() -- runs everything pending as ONE batched device submission per geometry.  Every
+    object's output is bit for bit what it would be unpooled (include/smst.h, group 3)."""
+
+    def __init__(self, device=0, lib=None):
+        self.lib = lib if lib is not None else load_library()
+        h = C.c_void_p()
+        _check(self.lib, self.lib.smst_pool_create(C.byref(h), device))
+        self.h = h
+
+    def close(self):
+        """Runs what is pending and detaches every member (they stay valid and keep their state)."""
+        if getattr(self, "h", None):
+            self.lib.smst_pool_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def add(self, stretch): _check(self.lib, self.lib.smst_pool_attach(self.h, stretch.h))
+    def remove(self, stretch): _check(self.lib, self.lib.smst_pool_detach(stretch.h))
+    def run(self): _check(self.lib, self.lib.smst_pool_run(self.h))
+    def members(self): return int(self.lib.smst_pool_members(self.h))
+    def pending(self): return int(self.lib.smst_pool_pending(self.h))
+    def engine_calls(self): return int(self.lib.smst_pool_debug_engine_calls(self.h))
+    def allocation_events(self): return int(self.lib.smst_pool_debug_allocation_events(self.h))

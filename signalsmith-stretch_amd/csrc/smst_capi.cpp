@@ -41,6 +41,41 @@ struct smst_stretch {
 	bool formantComp = false;
 	float formantBase = 0;
 	std::vector<float> mapTable;
+	// ---- pool membership (extension, include/smst.h group 3).  A member that is configured lives in slot `slot` of its group's engine and
+	// owns no engine (`batch` is null); one that is not configured yet is only registered.  A handle that never meets a pool has none of this set.
+	smst_pool *pool = nullptr;
+	struct PoolGroup *group = nullptr;
+	int slot = -1;
+	bool pending = false; // a request of smst_process_begin that has not run yet
+	const float *const *reqIn = nullptr;
+	float *const *reqOut = nullptr;
+	int reqIn_n = 0, reqOut_n = 0;
+	int reqStatus = SMST_OK; // of the newest request (smst_process_end reports it)
+	std::string reqError;
+};
+
+// One geometry (channels, block, interval, split) of a pool: ONE engine whose streams are the members' slots
+struct PoolGroup {
+	std::unique_ptr<smst_batch> batch;
+	std::vector<smst_stretch *> slots; // the member in each slot, null = free
+	std::vector<int> freeSlots;        // descending: the lowest free slot is taken first
+	int used = 0;
+	// per-run scratch, sized with the engine (nothing is allocated in a steady-state run)
+	std::vector<int> nIn, nOut;
+	std::vector<unsigned char> active;
+	float *hIn = nullptr, *hOut = nullptr; // pinned staging: the members' planes gathered as [slot][channel][longest count]
+	size_t hInCap = 0, hOutCap = 0;
+	~PoolGroup() {
+		if (hIn) hipHostFree(hIn);
+		if (hOut) hipHostFree(hOut);
+	}
+};
+struct smst_pool {
+	int device = 0;
+	std::vector<std::unique_ptr<PoolGroup>> groups;
+	std::vector<smst_stretch *> members;
+	long long engineCalls = 0; // Batch::process calls issued by smst_pool_run / smst_process_end
+	long long allocEvents = 0; // group engines created / regrown, staging growth, plus the counts of engines that have been retired
 };
 
 #define SMST_TRY try {
@@ -309,7 +344,6 @@ int smst_create(smst_stretch **out, long seed, int device) {
 	return SMST_OK;
 	SMST_CATCH
 }
-void smst_destroy(smst_stretch *h) { delete h; }
 
 // the device new single-stream handles are created on: SMST_DEVICE (validated against the device count, once) or the setter
 static std::atomic<int> g_defaultDevice{-1};
@@ -346,19 +380,306 @@ int smst_set_default_device(int device) {
 	g_defaultDevice.store(device, std::memory_order_release);
 	return SMST_OK;
 }
+// ---------------------------------------------------------------------------------------------------------
+// pool (extension): the machinery.  The single-stream calls below go through engineOf() / slotOf(): an unattached handle's own
+// one-stream engine and stream 0 -- what they always used -- or the member's slot of its group's engine.
+// ---------------------------------------------------------------------------------------------------------
+static Batch *engineOf(const smst_stretch *h) {
+	if (!h) return nullptr;
+	if (h->group) return h->group->batch->engine.get();
+	return h->batch ? h->batch->engine.get() : nullptr;
+}
+static int slotOf(const smst_stretch *h) { return h->group ? h->slot : 0; }
+
+static void ensurePinned(float *&ptr, size_t &cap, size_t need, int device, long long &allocs) {
+	if (need <= cap) return;
+	++allocs;
+	hipSetDevice(device);
+	if (ptr) hipHostFree(ptr);
+	ptr = nullptr;
+	cap = 0;
+	const size_t want = need + need/8 + 1024;
+	if (hipHostMalloc(reinterpret_cast<void **>(&ptr), want*sizeof(float), hipHostMallocDefault) != hipSuccess) throw smst::Error("hipHostMalloc (pool staging) failed", true);
+	cap = want;
+}
+
+static const int kPoolFirstSlots = 4;
+
+static void sizeGroupScratch(PoolGroup &g) {
+	const size_t S = size_t(g.batch->engine->streams());
+	g.slots.resize(S, nullptr);
+	g.nIn.assign(S, 0);
+	g.nOut.assign(S, 0);
+	g.active.assign(S, 0);
+}
+static std::unique_ptr<smst_batch> newGroupBatch(int streams, const Batch &like, int device) {
+	std::unique_ptr<smst_batch> b(new smst_batch());
+	b->engine.reset(new Batch(streams, like.channels(), like.blockSamples(), like.intervalSamples(), like.splitComputation(), device, 0));
+	return b;
+}
+static void retireCounts(smst_pool *p, const smst_batch &b) { p->allocEvents += (long long)b.engine->allocationEvents() + b.stagingAllocs; }
+
+// all members of the group into an engine of twice the slots, each into the slot it had: ONE launch moves them all (kMoveStreams)
+static void growGroup(smst_pool *p, PoolGroup &g) {
+	Batch &old = *g.batch->engine;
+	const int S = old.streams();
+	std::unique_ptr<smst_batch> b = newGroupBatch(2*S, old, p->device);
+	std::vector<int> rows;
+	for (int s = 0; s < S; ++s) if (g.slots[s]) rows.push_back(s);
+	b->engine->moveStreamsFrom(old, rows.data(), rows.data(), int(rows.size()));
+	retireCounts(p, *g.batch);
+	++p->allocEvents;
+	g.batch = std::move(b);
+	sizeGroupScratch(g);
+	for (int s = 2*S - 1; s >= S; --s) g.freeSlots.push_back(s);
+	std::sort(g.freeSlots.begin(), g.freeSlots.end(), [](int a, int b2) { return a > b2; });
+}
+
+// a configured member (it owns a one-stream engine) into a slot of its geometry's group; the engine of its own goes
+static void joinGroup(smst_pool *p, smst_stretch *h) {
+	Batch &own = *h->batch->engine;
+	PoolGroup *g = nullptr;
+	for (auto &c : p->groups) {
+		const Batch &e = *c->batch->engine;
+		if (e.channels() == own.channels() && e.blockSamples() == own.blockSamples() && e.intervalSamples() == own.intervalSamples() && e.splitComputation() == own.splitComputation()) { g = c.get(); break; }
+	}
+	if (!g) {
+		std::unique_ptr<PoolGroup> fresh(new PoolGroup());
+		fresh->batch = newGroupBatch(kPoolFirstSlots, own, p->device);
+		sizeGroupScratch(*fresh);
+		for (int s = kPoolFirstSlots - 1; s >= 0; --s) fresh->freeSlots.push_back(s);
+		++p->allocEvents;
+		p->groups.push_back(std::move(fresh));
+		g = p->groups.back().get();
+	}
+	if (g->freeSlots.empty()) growGroup(p, *g);
+	const int slot = g->freeSlots.back();
+	g->batch->engine->moveStreamFrom(own, 0, slot);
+	g->freeSlots.pop_back();
+	g->slots[slot] = h;
+	++g->used;
+	h->group = g;
+	h->slot = slot;
+	retireCounts(p, *h->batch);
+	++p->allocEvents;
+	h->batch.reset();
+}
+static void dropGroupIfEmpty(smst_pool *p, PoolGroup *g) {
+	if (g->used > 0) return;
+	for (size_t i = 0; i < p->groups.size(); ++i)
+		if (p->groups[i].get() == g) { retireCounts(p, *g->batch); p->groups.erase(p->groups.begin() + long(i)); return; }
+}
+static void freeSlot(smst_stretch *h) {
+	PoolGroup *g = h->group;
+	g->slots[h->slot] = nullptr;
+	g->freeSlots.push_back(h->slot);
+	std::sort(g->freeSlots.begin(), g->freeSlots.end(), [](int a, int b) { return a > b; });
+	--g->used;
+	h->group = nullptr;
+	h->slot = -1;
+	dropGroupIfEmpty(h->pool, g);
+}
+// ... and back: a one-stream engine of its own with the slot's state (the handle stays registered with the pool)
+static void leaveGroup(smst_stretch *h) {
+	Batch &e = *h->group->batch->engine;
+	std::unique_ptr<smst_batch> b(new smst_batch());
+	b->engine.reset(new Batch(1, e.channels(), e.blockSamples(), e.intervalSamples(), e.splitComputation(), h->device, h->seed));
+	b->engine->moveStreamFrom(e, h->slot, 0);
+	++h->pool->allocEvents;
+	h->batch = std::move(b);
+	freeSlot(h);
+}
+
+// ONE engine call for the group's pending requests (only != null: that member's alone -- the synchronous smst_process of a member; its
+// planes then are the whole staging image and every stream stride is 0).  Returns whether the engine was called; failures are thrown
+// after every affected member has its status.
+static bool runGroup(smst_pool *p, PoolGroup &g, smst_stretch *only) {
+	smst_batch *b = g.batch.get();
+	Batch &e = *b->engine;
+	const int S = e.streams(), C = e.channels();
+	int maxIn = 0, maxOut = 0, n = 0;
+	bool all = true;
+	for (int s = 0; s < S; ++s) {
+		smst_stretch *m = g.slots[s];
+		const bool on = m && m->pending && (!only || m == only);
+		g.active[s] = on ? 1 : 0;
+		g.nIn[s] = on ? m->reqIn_n : 0;
+		g.nOut[s] = on ? m->reqOut_n : 0;
+		if (!on) { all = false; continue; }
+		++n;
+		maxIn = std::max(maxIn, g.nIn[s]);
+		maxOut = std::max(maxOut, g.nOut[s]);
+	}
+	if (!n) return false;
+	maxIn = std::max(maxIn, 1);
+	maxOut = std::max(maxOut, 1);
+	const size_t rows = only ? size_t(C) : size_t(S)*C;
+	auto row = [&](int s, int c) { return only ? size_t(c) : size_t(s)*C + c; };
+	try {
+		hipSetDevice(e.device());
+		// gather -> one copy to the device
+		ensurePinned(g.hIn, g.hInCap, rows*maxIn, e.device(), p->allocEvents);
+		for (int s = 0; s < S; ++s) {
+			if (!g.active[s] || g.nIn[s] <= 0) continue;
+			const smst_stretch *m = g.slots[s];
+			for (int c = 0; c < C; ++c) std::copy(m->reqIn[c], m->reqIn[c] + g.nIn[s], g.hIn + row(s, c)*maxIn);
+		}
+		ensureStage(b->dIn, b->inCap, rows*maxIn, e.device(), b->stagingAllocs);
+		ensureStage(b->dOut, b->outCap, rows*maxOut, e.device(), b->stagingAllocs);
+		if (hipMemcpyAsync(b->dIn, g.hIn, rows*maxIn*sizeof(float), hipMemcpyHostToDevice, e.stream()) != hipSuccess) throw smst::Error("hipMemcpyAsync (H2D) failed", true);
+		if (hipStreamSynchronize(e.stream()) != hipSuccess) throw smst::Error("hipStreamSynchronize failed", true); // (the silence gate reads the input on another stream)
+		e.process(b->dIn, only ? 0 : (long long)C*maxIn, maxIn, g.nIn.data(), b->dOut, only ? 0 : (long long)C*maxOut, maxOut, g.nOut.data(), all ? nullptr : g.active.data());
+		// one copy back -> scatter
+		ensurePinned(g.hOut, g.hOutCap, rows*maxOut, e.device(), p->allocEvents);
+		if (hipMemcpyAsync(g.hOut, b->dOut, rows*maxOut*sizeof(float), hipMemcpyDeviceToHost, e.stream()) != hipSuccess) throw smst::Error("hipMemcpyAsync (D2H) failed", true);
+		if (hipStreamSynchronize(e.stream()) != hipSuccess) throw smst::Error("hipStreamSynchronize failed", true);
+		for (int s = 0; s < S; ++s) {
+			if (!g.active[s]) continue;
+			smst_stretch *m = g.slots[s];
+			for (int c = 0; c < C && g.nOut[s] > 0; ++c) std::copy(g.hOut + row(s, c)*maxOut, g.hOut + row(s, c)*maxOut + g.nOut[s], m->reqOut[c]);
+			m->pending = false;
+			m->reqStatus = SMST_OK;
+			m->reqError.clear();
+		}
+	} catch (const std::exception &err) {
+		const smst::Error *own = dynamic_cast<const smst::Error *>(&err);
+		for (int s = 0; s < S; ++s) {
+			if (!g.active[s]) continue;
+			smst_stretch *m = g.slots[s];
+			m->pending = false;
+			m->reqStatus = (own && own->device) ? SMST_ERR_DEVICE : SMST_ERR_INVALID;
+			m->reqError = err.what();
+		}
+		throw;
+	}
+	return true;
+}
+static int runPool(smst_pool *p) {
+	int rc = SMST_OK;
+	for (size_t i = 0; i < p->groups.size(); ++i) {
+		try {
+			if (runGroup(p, *p->groups[i], nullptr)) ++p->engineCalls;
+		} catch (const smst::Error &e) {
+			g_lastError = e.what();
+			if (rc == SMST_OK) rc = e.device ? SMST_ERR_DEVICE : SMST_ERR_INVALID;
+		} catch (const std::exception &e) {
+			g_lastError = e.what();
+			if (rc == SMST_OK) rc = SMST_ERR_INVALID;
+		}
+	}
+	return rc;
+}
+// program order per object: a call that reads or changes a member's state runs the pool first if the member's request is still pending
+static void settle(const smst_stretch *h) {
+	if (h && h->pool && h->pending) runPool(h->pool);
+}
+static void unregister(smst_stretch *h) {
+	smst_pool *p = h->pool;
+	p->members.erase(std::remove(p->members.begin(), p->members.end(), h), p->members.end());
+	h->pool = nullptr;
+}
+
+int smst_pool_create(smst_pool **out, int device) {
+	if (!out) return fail("null output pointer");
+	SMST_TRY
+	int n = 0;
+	if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) throw smst::Error("hipGetDeviceCount: no HIP device available (the gfx950 path has no CPU fallback)", true);
+	if (device < 0 || device >= n) throw smst::Error("device ordinal " + std::to_string(device) + " out of range: this process sees " + std::to_string(n) + " device(s)");
+	smst_pool *p = new smst_pool();
+	p->device = device;
+	*out = p;
+	return SMST_OK;
+	SMST_CATCH
+}
+void smst_pool_destroy(smst_pool *p) {
+	if (!p) return;
+	runPool(p); // (a failure stays with the members it affected: smst_process_end reports it)
+	while (!p->members.empty()) {
+		smst_stretch *h = p->members.back();
+		if (h->group) {
+			try {
+				leaveGroup(h);
+			} catch (const std::exception &e) { // no engine of its own could be made: the handle survives, unconfigured
+				g_lastError = e.what();
+				freeSlot(h);
+			}
+		}
+		unregister(h);
+	}
+	delete p;
+}
+int smst_pool_attach(smst_pool *p, smst_stretch *h) {
+	if (!p || !h) return fail("null pointer");
+	if (h->pool) return fail(h->pool == p ? "the handle is already attached to this pool" : "the handle is already attached to another pool");
+	if (h->device != p->device) return fail("the handle lives on another device than the pool");
+	SMST_TRY
+	p->members.push_back(h);
+	h->pool = p;
+	h->pending = false;
+	if (h->batch) {
+		try {
+			joinGroup(p, h);
+		} catch (...) {
+			unregister(h);
+			throw;
+		}
+	}
+	return SMST_OK;
+	SMST_CATCH
+}
+int smst_pool_detach(smst_stretch *h) {
+	if (!h) return fail("null handle");
+	if (!h->pool) return fail("the handle is not attached to a pool");
+	SMST_TRY
+	settle(h);
+	if (h->group) leaveGroup(h);
+	unregister(h);
+	return SMST_OK;
+	SMST_CATCH
+}
+int smst_pool_members(const smst_pool *p) { return p ? int(p->members.size()) : fail("null pool"); }
+int smst_pool_pending(const smst_pool *p) {
+	if (!p) return fail("null pool");
+	int n = 0;
+	for (const smst_stretch *h : p->members) n += h->pending ? 1 : 0;
+	return n;
+}
+int smst_pool_run(smst_pool *p) {
+	if (!p) return fail("null pool");
+	return runPool(p);
+}
+long long smst_pool_debug_engine_calls(const smst_pool *p) { return p ? p->engineCalls : fail("null pool"); }
+long long smst_pool_debug_allocation_events(const smst_pool *p) {
+	if (!p) return fail("null pool");
+	long long n = p->allocEvents;
+	for (const auto &g : p->groups) n += (long long)g->batch->engine->allocationEvents() + g->batch->stagingAllocs;
+	return n;
+}
+
+void smst_destroy(smst_stretch *h) {
+	if (h && h->pool) {
+		settle(h);
+		if (h->group) freeSlot(h);
+		unregister(h);
+	}
+	delete h;
+}
+
 int smst_clone(smst_stretch **out, const smst_stretch *src) {
 	if (!out || !src) return fail("null pointer");
 	SMST_TRY
+	settle(src);
 	std::unique_ptr<smst_stretch> h(new smst_stretch());
 	h->seed = src->seed; h->device = src->device;
 	h->transposeFactor = src->transposeFactor; h->tonalityLimit = src->tonalityLimit; h->transposeSet = src->transposeSet;
 	h->formantFactor = src->formantFactor; h->formantComp = src->formantComp; h->formantBase = src->formantBase;
 	h->mapTable = src->mapTable;
-	if (src->batch) {
-		Batch &e = *src->batch->engine;
+	if (Batch *ep = engineOf(src)) {
+		Batch &e = *ep;
 		std::unique_ptr<smst_batch> b(new smst_batch());
 		b->engine.reset(new Batch(1, e.channels(), e.blockSamples(), e.intervalSamples(), e.splitComputation(), src->device, src->seed, e.halfPrecisionState()));
-		b->engine->copyStateFrom(e);
+		if (src->group) b->engine->moveStreamFrom(e, src->slot, 0); // (the slot's rows stay as they are: the member goes on, the clone is unattached)
+		else b->engine->copyStateFrom(e);
 		h->batch = std::move(b);
 	}
 	*out = h.release();
@@ -376,6 +697,16 @@ static void applyParams(smst_stretch *h) {
 int smst_configure(smst_stretch *h, int channels, int block, int interval, int split) {
 	if (!h) return fail("null handle");
 	SMST_TRY
+	// a member is configured as an unattached handle is, on an engine of its own, and then takes a slot in its new geometry's group
+	smst_pool *pool = h->pool;
+	if (pool) {
+		settle(h);
+		if (h->group) leaveGroup(h);
+	}
+	struct Rejoin { // (also when the new geometry is refused: the member keeps its old one)
+		smst_pool *pool; smst_stretch *h;
+		~Rejoin() { if (pool && h->batch && !h->group) { try { joinGroup(pool, h); } catch (...) {} } }
+	} rejoin{pool, h};
 	std::unique_ptr<smst_batch> b(new smst_batch());
 	b->engine.reset(new Batch(1, channels, block, interval, split != 0, h->device, h->seed));
 	if (h->batch) b->engine->inheritAcrossConfigure(*h->batch->engine); // configure() does not reseed the engine (:38-39, :71-94)
@@ -391,44 +722,49 @@ int smst_preset_cheaper(smst_stretch *h, int channels, float sampleRate, int spl
 	return smst_configure(h, channels, int(sampleRate*0.1), int(sampleRate*0.04), split < 0 ? 1 : split);
 }
 
-#define STRETCH_Q(name, expr) int name(const smst_stretch *h) { if (!h || !h->batch) return fail("unconfigured handle"); const Batch &e = *h->batch->engine; return (expr); }
+#define STRETCH_Q(name, expr) int name(const smst_stretch *h) { const Batch *ep = engineOf(h); if (!ep) return fail("unconfigured handle"); const Batch &e = *ep; return (expr); }
 STRETCH_Q(smst_block_samples, e.blockSamples())
 STRETCH_Q(smst_interval_samples, e.intervalSamples())
 STRETCH_Q(smst_input_latency, e.inputLatency())
 STRETCH_Q(smst_output_latency, e.outputLatency())
 STRETCH_Q(smst_split_computation, e.splitComputation() ? 1 : 0)
-STRETCH_Q(smst_block_steps, e.lastBlockSteps(0))
-STRETCH_Q(smst_blocks_started, e.lastCallBlocks(0))
 STRETCH_Q(smst_seek_length, e.seekLength())
-int smst_output_seek_length(const smst_stretch *h, float rate) { if (!h || !h->batch) return fail("unconfigured handle"); return h->batch->engine->outputSeekLength(rate); }
+int smst_block_steps(const smst_stretch *h) { settle(h); const Batch *e = engineOf(h); if (!e) return fail("unconfigured handle"); return e->lastBlockSteps(slotOf(h)); }
+int smst_blocks_started(const smst_stretch *h) { settle(h); const Batch *e = engineOf(h); if (!e) return fail("unconfigured handle"); return e->lastCallBlocks(slotOf(h)); }
+int smst_output_seek_length(const smst_stretch *h, float rate) { const Batch *e = engineOf(h); if (!e) return fail("unconfigured handle"); return e->outputSeekLength(rate); }
 
-#define STRETCH_CALL(body) if (!h) return fail("null handle"); SMST_TRY body; return SMST_OK; SMST_CATCH
+#define STRETCH_CALL(body) if (!h) return fail("null handle"); SMST_TRY settle(h); body; return SMST_OK; SMST_CATCH
 
-int smst_reset(smst_stretch *h) { STRETCH_CALL(if (h->batch) h->batch->engine->reset()) }
+int smst_reset(smst_stretch *h) {
+	STRETCH_CALL({
+		if (h->group) h->group->batch->engine->resetStream(h->slot);
+		else if (h->batch) h->batch->engine->reset();
+	})
+}
 int smst_set_transpose_factor(smst_stretch *h, float m, float t) {
 	STRETCH_CALL({
 		h->transposeFactor = m; h->tonalityLimit = t; h->transposeSet = true; h->mapTable.clear();
-		if (h->batch) h->batch->engine->setTransposeFactor(0, m, t);
+		if (Batch *e = engineOf(h)) e->setTransposeFactor(slotOf(h), m, t);
 	})
 }
 int smst_set_transpose_semitones(smst_stretch *h, float st, float t) { return smst_set_transpose_factor(h, float(std::pow(2, st/12)), t); }
 int smst_set_formant_factor(smst_stretch *h, float m, int comp) {
 	STRETCH_CALL({
 		h->formantFactor = m; h->formantComp = comp != 0;
-		if (h->batch) h->batch->engine->setFormantFactor(0, m, comp != 0);
+		if (Batch *e = engineOf(h)) e->setFormantFactor(slotOf(h), m, comp != 0);
 	})
 }
 int smst_set_formant_semitones(smst_stretch *h, float st, int comp) { return smst_set_formant_factor(h, float(std::pow(2, st/12)), comp); }
 int smst_set_formant_base(smst_stretch *h, float f) {
 	STRETCH_CALL({
 		h->formantBase = f;
-		if (h->batch) h->batch->engine->setFormantBase(0, f);
+		if (Batch *e = engineOf(h)) e->setFormantBase(slotOf(h), f);
 	})
 }
 int smst_set_freq_map_table(smst_stretch *h, const float *table, int n) {
 	STRETCH_CALL({
 		if (table && n > 0) h->mapTable.assign(table, table + n); else h->mapTable.clear();
-		if (h->batch) h->batch->engine->setFreqMapTable(0, table, n);
+		if (Batch *e = engineOf(h)) e->setFreqMapTable(slotOf(h), table, n);
 	})
 }
 
@@ -441,14 +777,107 @@ static void scatterPlanes(const std::vector<float> &dense, float *const *planes,
 	for (int c = 0; c < C; ++c) if (n > 0) std::copy(dense.begin() + (size_t)c*n, dense.begin() + (size_t)(c + 1)*n, planes[c]);
 }
 
+// The synchronous calls on a MEMBER: the engine call of the unattached handle, on the member's slot alone (an `active` mask of one; the
+// member's planes are the whole staging image, every stream stride 0).
+static bool badPlanes(const void *const *planes, int C, int n) {
+	if (n <= 0) return false;
+	if (!planes) return true;
+	for (int c = 0; c < C; ++c) if (!planes[c]) return true;
+	return false;
+}
+static int memberSeek(smst_stretch *h, const float *const *inputs, int n, double rate) {
+	SMST_TRY
+	smst_batch *b = h->group->batch.get();
+	Batch &e = *b->engine;
+	const int S = e.streams(), C = e.channels(), len = std::max(n, 1);
+	if (n < 0 || badPlanes(reinterpret_cast<const void *const *>(inputs), C, n)) throw smst::Error("null buffers with a non-zero sample count");
+	std::vector<float> in;
+	gatherPlanes(inputs, C, n, in);
+	std::vector<int> counts(S, 0);
+	std::vector<double> rates(S, 1.0);
+	std::vector<unsigned char> mask(S, 0);
+	counts[h->slot] = n; rates[h->slot] = rate; mask[h->slot] = 1;
+	ensureStage(b->dIn, b->inCap, (size_t)C*len, e.device(), b->stagingAllocs);
+	hipSetDevice(e.device());
+	if (hipMemcpy(b->dIn, in.data(), (size_t)C*len*sizeof(float), hipMemcpyHostToDevice) != hipSuccess) throw smst::Error("hipMemcpy (H2D) failed", true);
+	e.seek(b->dIn, 0, len, counts.data(), rates.data(), mask.data());
+	e.synchronize();
+	return SMST_OK;
+	SMST_CATCH
+}
+static int memberFlush(smst_stretch *h, float *const *outputs, int n, float rate) {
+	SMST_TRY
+	smst_batch *b = h->group->batch.get();
+	Batch &e = *b->engine;
+	const int S = e.streams(), C = e.channels(), len = std::max(n, 1);
+	if (n < 0 || badPlanes(reinterpret_cast<const void *const *>(outputs), C, n)) throw smst::Error("null buffers with a non-zero sample count");
+	std::vector<int> counts(S, 0);
+	std::vector<float> rates(S, 0.0f);
+	std::vector<unsigned char> mask(S, 0);
+	counts[h->slot] = n; rates[h->slot] = rate; mask[h->slot] = 1;
+	ensureStage(b->dOut, b->outCap, (size_t)C*len, e.device(), b->stagingAllocs);
+	e.flush(b->dOut, 0, len, counts.data(), rates.data(), mask.data());
+	e.synchronize();
+	std::vector<float> out((size_t)C*len);
+	if (hipMemcpy(out.data(), b->dOut, out.size()*sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) throw smst::Error("hipMemcpy (D2H) failed", true);
+	scatterPlanes(out, outputs, C, n);
+	return SMST_OK;
+	SMST_CATCH
+}
+static int reportRequest(const smst_stretch *h) {
+	if (h->reqStatus != SMST_OK) g_lastError = h->reqError;
+	return h->reqStatus;
+}
+static int recordRequest(smst_stretch *h, const float *const *inputs, int inputSamples, float *const *outputs, int outputSamples) {
+	const int C = h->group->batch->engine->channels();
+	if (inputSamples < 0 || outputSamples < 0) return fail("negative sample count");
+	if (badPlanes(reinterpret_cast<const void *const *>(inputs), C, inputSamples) || badPlanes(reinterpret_cast<const void *const *>(outputs), C, outputSamples))
+		return fail("null buffers with a non-zero sample count");
+	h->reqIn = inputs; h->reqIn_n = inputSamples; h->reqOut = outputs; h->reqOut_n = outputSamples;
+	h->pending = true;
+	return SMST_OK;
+}
+static int memberProcess(smst_stretch *h, const float *const *inputs, int inputSamples, float *const *outputs, int outputSamples) {
+	int rc = recordRequest(h, inputs, inputSamples, outputs, outputSamples);
+	if (rc != SMST_OK) return rc;
+	SMST_TRY
+	runGroup(h->pool, *h->group, h);
+	return SMST_OK;
+	SMST_CATCH
+}
+
+int smst_process_begin(smst_stretch *h, const float *const *inputs, int inputSamples, float *const *outputs, int outputSamples) {
+	if (!h) return fail("null handle");
+	if (!h->pool) { // not attached: the synchronous call, its status kept for smst_process_end
+		h->reqStatus = smst_process(h, inputs, inputSamples, outputs, outputSamples);
+		h->reqError = h->reqStatus != SMST_OK ? g_lastError : std::string();
+		return h->reqStatus;
+	}
+	settle(h); // a second begin without an end: the first request runs now
+	if (!h->group) return fail("unconfigured handle");
+	return recordRequest(h, inputs, inputSamples, outputs, outputSamples);
+}
+int smst_process_end(smst_stretch *h) {
+	if (!h) return fail("null handle");
+	if (h->pool && h->pending) {
+		runPool(h->pool);
+		if (h->pending) { h->pending = false; h->reqStatus = SMST_ERR_INVALID; h->reqError = "the request did not run"; } // (cannot happen: a pending member sits in a group)
+	}
+	return reportRequest(h);
+}
+
 int smst_seek(smst_stretch *h, const float *const *inputs, int inputSamples, double playbackRate) {
-	if (!h || !h->batch) return fail("unconfigured handle");
+	settle(h);
+	if (!engineOf(h)) return fail("unconfigured handle");
+	if (h->group) return memberSeek(h, inputs, inputSamples, playbackRate);
 	std::vector<float> in;
 	gatherPlanes(inputs, h->batch->engine->channels(), inputSamples, in);
 	return smst_batch_seek(h->batch.get(), in.data(), 0, std::max(inputSamples, 1), &inputSamples, &playbackRate, SMST_MEM_HOST);
 }
 int smst_process(smst_stretch *h, const float *const *inputs, int inputSamples, float *const *outputs, int outputSamples) {
-	if (!h || !h->batch) return fail("unconfigured handle");
+	settle(h);
+	if (!engineOf(h)) return fail("unconfigured handle");
+	if (h->group) return memberProcess(h, inputs, inputSamples, outputs, outputSamples);
 	const int C = h->batch->engine->channels();
 	std::vector<float> in, out((size_t)C*std::max(outputSamples, 1));
 	gatherPlanes(inputs, C, inputSamples, in);
@@ -457,7 +886,9 @@ int smst_process(smst_stretch *h, const float *const *inputs, int inputSamples, 
 	return rc;
 }
 int smst_flush(smst_stretch *h, float *const *outputs, int outputSamples, float playbackRate) {
-	if (!h || !h->batch) return fail("unconfigured handle");
+	settle(h);
+	if (!engineOf(h)) return fail("unconfigured handle");
+	if (h->group) return memberFlush(h, outputs, outputSamples, playbackRate);
 	const int C = h->batch->engine->channels();
 	std::vector<float> out((size_t)C*std::max(outputSamples, 1));
 	int rc = smst_batch_flush(h->batch.get(), out.data(), 0, std::max(outputSamples, 1), &outputSamples, &playbackRate, SMST_MEM_HOST);
@@ -465,15 +896,29 @@ int smst_flush(smst_stretch *h, float *const *outputs, int outputSamples, float 
 	return rc;
 }
 int smst_output_seek(smst_stretch *h, const float *const *inputs, int inputLength) {
-	if (!h || !h->batch) return fail("unconfigured handle");
+	settle(h);
+	if (!engineOf(h)) return fail("unconfigured handle");
+	if (h->group) {
+		// outputSeek() is reset + seek + a pre-roll process + a fold-back over the whole engine (Batch::outputSeek has no stream mask): the
+		// member does it on an engine of its own and returns to its group -- two slot moves around a call that is rare and slow anyway
+		smst_pool *pool = h->pool;
+		SMST_TRY
+		leaveGroup(h);
+		struct Rejoin { smst_pool *pool; smst_stretch *h; ~Rejoin() { if (h->batch && !h->group) { try { joinGroup(pool, h); } catch (...) {} } } } rejoin{pool, h};
+		std::vector<float> in;
+		gatherPlanes(inputs, h->batch->engine->channels(), inputLength, in);
+		return smst_batch_output_seek(h->batch.get(), in.data(), 0, std::max(inputLength, 1), &inputLength, SMST_MEM_HOST);
+		SMST_CATCH
+	}
 	std::vector<float> in;
 	gatherPlanes(inputs, h->batch->engine->channels(), inputLength, in);
 	return smst_batch_output_seek(h->batch.get(), in.data(), 0, std::max(inputLength, 1), &inputLength, SMST_MEM_HOST);
 }
 int smst_exact(smst_stretch *h, const float *const *inputs, int inputSamples, float *const *outputs, int outputSamples) {
 	// signalsmith-stretch.h:468-491
-	if (!h || !h->batch) return fail("unconfigured handle");
-	Batch &e = *h->batch->engine;
+	settle(h);
+	if (!engineOf(h)) return fail("unconfigured handle");
+	Batch &e = *engineOf(h);
 	const int C = e.channels();
 	float playbackRate = inputSamples/float(outputSamples);
 	int seekLength = e.outputSeekLength(playbackRate);

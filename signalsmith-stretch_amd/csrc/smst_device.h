@@ -113,6 +113,21 @@ struct IoArgs {
 	const int *outSamples; // [S] device
 };
 
+// Moving the carried state of whole streams between two batches of one geometry (Batch::moveStreamsFrom): one segment per state
+// array, rows = streams.  Pair p copies `rowBytes` from src + pairs[2p]*srcPitch to dst + pairs[2p + 1]*dstPitch.
+struct MoveSeg {
+	const char *src;
+	char *dst;
+	unsigned long long srcPitch, dstPitch; // bytes from one stream's row to the next (the two batches differ in nothing else)
+	unsigned long long rowBytes;
+};
+constexpr int kMoveSegs = 16;
+struct MoveArgs {
+	MoveSeg seg[kMoveSegs];
+	int nSeg, nPairs;
+	const int *pairs; // [nPairs][2] device: (source stream, destination stream)
+};
+
 // The packed input of a frame: element m = (x[base + halfB + m] w[halfB + m], x[base + halfB - M + m] w[halfB - M + m]), the real part
 // present for m < B - halfB, the imaginary part for m >= M - halfB.  At 48 / 96 kHz (block = 15/16 of the FFT size) those edges are
 // element-slot boundaries: slot 0 has no imaginary part, slot 15 no real part, and kAnalyseTeams fetches exactly the window.  Other
@@ -187,5 +202,6 @@ void launchSeekHistory(const DevBatch &d, const IoArgs &io, const int *seekFlags
 void launchAddPreRoll(const DevBatch &d, const float *preRoll, int length, const int *offsets, hipStream_t st);
 void launchComplexSelfTest(const float *in, float *out, int n, hipStream_t st); // smst_complex.h against its documented formulas (test hook)
 void launchFlushTail(const DevBatch &d, const IoArgs &io, const int *tailOffset, const int *outOffset, hipStream_t st);
+void launchMoveStreams(const MoveArgs &a, hipStream_t st); // every segment of every pair in one launch
 
 } // namespace smst

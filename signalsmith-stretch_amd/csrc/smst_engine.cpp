@@ -600,6 +600,23 @@ void Batch::reset() { // signalsmith-stretch.h:49-60
 	}
 }
 
+void Batch::resetStream(int s) { // reset() for one stream; kResetStreams writes both halves of the double buffers, so which half is current does not matter
+	if (s < 0 || s >= S) throw Error("stream index out of range");
+	SMST_HIP(hipSetDevice(dev));
+	SMST_HIP(hipStreamSynchronize(st)); // (an earlier launch may still read the mask buffer)
+	SMST_HIP(hipMemsetAsync(d.stFreq + 2*(size_t)s, 0, 2*sizeof(float), st));
+	std::fill(resetBitsV.begin(), resetBitsV.end(), 0);
+	resetBitsV[s] = 1 | 2 | 4 | 8;
+	resetStreams(resetBitsV.data(), 0);
+	lastHop[s] = LastHop();
+	lastSteps[s] = 0;
+	lastStarts[s] = 0;
+	const unsigned seed = seedAfterDroppedBlock(s);
+	pend[s] = PendingBlock();
+	sched[s] = StreamSched();
+	sched[s].seed = seed;
+}
+
 // ---- parameters ------------------------------------------------------------------------------------------
 template <typename F> static void forStreams(int S, int stream, F &&f) {
 	if (stream < 0) { for (int s = 0; s < S; ++s) f(s); }
@@ -1747,6 +1764,94 @@ void Batch::copyStateFrom(Batch &o) {
 		d.mapTable = dMapTable;
 	}
 	for (auto &lh : lastHop) lh = LastHop();
+}
+
+void Batch::moveStreamsFrom(Batch &o, const int *from, const int *to, int n) {
+	if (&o == this) throw Error("moveStreamsFrom: source and destination are the same batch");
+	if (o.C != C || o.B != B || o.I != I || o.split != split || o.halfState != halfState || o.dev != dev) throw Error("moveStreamsFrom: the two batches differ in geometry or device");
+	if (n < 1) return;
+	for (int p = 0; p < n; ++p) {
+		if (from[p] < 0 || from[p] >= o.S || to[p] < 0 || to[p] >= S) throw Error("moveStreamsFrom: stream index out of range");
+		for (int q = 0; q < p; ++q) if (to[q] == to[p]) throw Error("moveStreamsFrom: a destination stream is named twice");
+	}
+	SMST_HIP(hipSetDevice(dev));
+	SMST_HIP(hipStreamSynchronize(o.st));
+	SMST_HIP(hipStreamSynchronize(st));
+	// (a row of the overlap-add carry moves with its carryBase entry: the window keeps its place in the row)
+	MoveArgs a{};
+	auto seg = [&](const void *src, void *dst, size_t rowBytes, size_t srcPitch, size_t dstPitch) {
+		if (a.nSeg >= kMoveSegs) throw Error("moveStreamsFrom: too many state arrays");
+		MoveSeg &g = a.seg[a.nSeg++];
+		g.src = static_cast<const char *>(src); g.dst = static_cast<char *>(dst);
+		g.rowBytes = rowBytes; g.srcPitch = srcPitch; g.dstPitch = dstPitch;
+	};
+	auto rows = [&](const void *src, void *dst, size_t rowBytes) { seg(src, dst, rowBytes, rowBytes, rowBytes); };
+	const size_t band = (size_t)C*M, scale = halfState ? 2 : 1;
+	rows(o.d.stInput, d.stInput, band*sizeof(float2));
+	rows(o.d.stPrev, d.stPrev, band*sizeof(float2));
+	rows(o.d.stOut, d.stOut, band*sizeof(float2)/scale);
+	rows(o.d.stEnergy, d.stEnergy, band*sizeof(float)/scale);
+	rows(o.d.hist, d.hist, (size_t)C*d.histPitch*sizeof(float));
+	rows(o.d.stFreq, d.stFreq, 2*sizeof(float));
+	for (int h = 0; h < 2; ++h) { // the source's current half into both halves
+		rows(o.d.histBase[o.d.histCur], d.histBase[h], sizeof(int));
+		rows(o.d.carryBase[o.d.carryCur], d.carryBase[h], sizeof(int));
+		rows(o.d.carrySum[o.d.carryCur], d.carrySum[h], (size_t)C*d.carryPitch*sizeof(float)/scale);
+		rows(o.d.carryWp[o.d.carryCur], d.carryWp[h], (size_t)d.carryPitch*sizeof(float));
+	}
+	if (split) {
+		rows(o.dPendIn, dPendIn, (size_t)C*d.Mp*sizeof(float2));
+		rows(o.dPendPrev, dPendPrev, (size_t)C*d.Mp*sizeof(float2));
+	}
+	std::vector<int> pairs((size_t)2*n);
+	for (int p = 0; p < n; ++p) { pairs[2*p] = from[p]; pairs[2*p + 1] = to[p]; }
+	int *dPairs = devAlloc<int>(pairs.size());
+	SMST_HIP(hipMemcpy(dPairs, pairs.data(), pairs.size()*sizeof(int), hipMemcpyHostToDevice));
+	const int kChunk = 32768; // (a grid's z extent)
+	for (int p0 = 0; p0 < n; p0 += kChunk) {
+		a.pairs = dPairs + 2*(size_t)p0;
+		a.nPairs = std::min(kChunk, n - p0);
+		launchMoveStreams(a, st);
+	}
+	SMST_HIP(hipGetLastError());
+	SMST_HIP(hipStreamSynchronize(st));
+	devFree(dPairs);
+	// the host's side of the same rows
+	for (int p = 0; p < n; ++p) {
+		const int f = from[p], t = to[p];
+		sched[t] = o.sched[f];
+		params[t] = o.params[f];
+		pend[t] = o.pend[f];
+		lastSteps[t] = o.lastSteps[f];
+		lastStarts[t] = o.lastStarts[f];
+		histBase[t] = o.histBase[f];
+		carryBase[t] = o.carryBase[f];
+		lastHop[t] = LastHop();
+	}
+	paramsDirty = true;
+	// the streams' own frequency-map tables, knot for knot: every row of the source's pitch fits the (possibly grown) pitch here
+	if (o.d.mapTableLen > 0) {
+		const int have = d.mapTableLen, need = std::max(have, o.d.mapTableLen);
+		if (need > have || hostMapTable.size() != (size_t)S*kMapSlots*need) {
+			std::vector<float> grown((size_t)S*kMapSlots*need, 0.0f);
+			for (size_t row = 0; row < (size_t)S*kMapSlots && have > 0 && hostMapTable.size() >= (size_t)S*kMapSlots*have; ++row)
+				std::copy(hostMapTable.begin() + row*have, hostMapTable.begin() + (row + 1)*have, grown.begin() + row*need);
+			if (dMapTable) devFree(dMapTable);
+			dMapTable = devAlloc<float>(grown.size());
+			hostMapTable.swap(grown);
+			d.mapTableLen = need;
+			d.mapTable = dMapTable;
+		}
+		const size_t op = (size_t)o.d.mapTableLen;
+		for (int p = 0; p < n; ++p)
+			for (int slot = 0; slot < kMapSlots; ++slot) {
+				float *dstRow = hostMapTable.data() + ((size_t)to[p]*kMapSlots + slot)*need;
+				const float *srcRow = o.hostMapTable.data() + ((size_t)from[p]*kMapSlots + slot)*op;
+				std::copy(srcRow, srcRow + op, dstRow);
+				std::fill(dstRow + op, dstRow + need, 0.0f);
+			}
+		SMST_HIP(hipMemcpy(dMapTable, hostMapTable.data(), hostMapTable.size()*sizeof(float), hipMemcpyHostToDevice));
+	}
 }
 
 void Batch::inheritAcrossConfigure(Batch &o) {

@@ -113,6 +113,16 @@ public:
 	// constructor only, :38-39), prevInputOffset, didSeek / seekTimeFactor, the silence counter and the pitch-estimate averages
 	// (all reset by reset(), :49-60, not by configure).  `other` is the stream's previous batch (same stream count).
 	void inheritAcrossConfigure(Batch &other);
+	// One stream's whole carried state from a batch of the SAME geometry and device but any stream count (a pool's group takes a member
+	// in, lets one go, regrows): everything copyStateFrom carries, for the rows of the listed streams -- Band.input / .prevInput / .output,
+	// Prediction.energy, the input history, the overlap-add carry (the source's CURRENT half, into both halves here: which half is
+	// current belongs to a batch, not to a stream), the pitch-estimate averages, the spectra of a split-computation block in flight, the
+	// scheduler state with the random engine, the parameters and the stream's own frequency-map tables.  The device part is ONE launch
+	// (kMoveStreams) however many streams move.  Both batches are synchronised; the source rows are left as they are.
+	void moveStreamFrom(Batch &src, int srcStream, int dstStream) { moveStreamsFrom(src, &srcStream, &dstStream, 1); }
+	void moveStreamsFrom(Batch &src, const int *srcStreams, const int *dstStreams, int n);
+	// reset() (:49-60) of ONE stream: its neighbours are not touched
+	void resetStream(int stream);
 
 	// test hooks: copy state rows to the host (which: 0 input, 1 prevInput, 2 output -> 2*C*M floats; 3 energy -> C*M)
 	void debugGetState(int stream, int which, float *dst);

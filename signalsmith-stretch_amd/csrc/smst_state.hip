@@ -125,6 +125,31 @@ __global__ __launch_bounds__(256) void kResetStreams(DevBatch d, const int *__re
 	}
 }
 
+// The carried state of whole streams from one batch to another of the same geometry (Batch::moveStreamsFrom: a pool's group takes a
+// member in, lets one go or regrows).  blockIdx.y = state array, blockIdx.z = (source stream, destination stream) pair, grid-stride along
+// the row.  The two batches have different stream counts, so a row of the same array may be 16-byte aligned in one and not in the
+// other (histBase / carryBase rows are 4 bytes, stFreq rows 8): 16-byte copies where both ends allow them, dwords where those do,
+// bytes for what is left (fp16 state: rows of an odd number of halves).
+__global__ __launch_bounds__(256) void kMoveStreams(MoveArgs a) {
+	const MoveSeg g = a.seg[blockIdx.y];
+	const char *src = g.src + (size_t)a.pairs[2*blockIdx.z]*g.srcPitch;
+	char *dst = g.dst + (size_t)a.pairs[2*blockIdx.z + 1]*g.dstPitch;
+	const size_t tid = (size_t)blockIdx.x*blockDim.x + threadIdx.x, stride = (size_t)gridDim.x*blockDim.x, bytes = g.rowBytes;
+	const size_t ends = reinterpret_cast<size_t>(src) | reinterpret_cast<size_t>(dst);
+	size_t done = 0;
+	if (ends%16 == 0) {
+		const size_t n = bytes/16;
+		for (size_t i = tid; i < n; i += stride) reinterpret_cast<float4 *>(dst)[i] = reinterpret_cast<const float4 *>(src)[i];
+		done = n*16;
+	}
+	if (ends%4 == 0) {
+		const size_t n = (bytes - done)/4;
+		for (size_t i = tid; i < n; i += stride) reinterpret_cast<unsigned *>(dst + done)[i] = reinterpret_cast<const unsigned *>(src + done)[i];
+		done += n*4;
+	}
+	for (size_t i = done + tid; i < bytes; i += stride) dst[i] = src[i];
+}
+
 // split computation: the block in flight was analysed when it started (:293, :332-373); its spectra wait in [S][C][Mp] buffers and enter the
 // tile that finally runs the block as row 0 (Xcur: Band.input, Xprev: the re-analysed Band.prevInput)
 __global__ __launch_bounds__(256) void kPendingToTile(DevBatch d, int sBase, const float2 *__restrict__ pendIn, const float2 *__restrict__ pendPrev) {
@@ -258,6 +283,16 @@ void launchSeekHistory(const DevBatch &d, const IoArgs &io, const int *seekFlags
 }
 void launchFlushTail(const DevBatch &d, const IoArgs &io, const int *tailOffset, const int *outOffset, hipStream_t st) {
 	hipLaunchKernelGGL(kFlushTail, dim3(d.S), dim3(64), 0, st, d, io, tailOffset, outOffset);
+}
+
+void launchMoveStreams(const MoveArgs &a, hipStream_t st) {
+	if (a.nSeg < 1 || a.nPairs < 1) return;
+	unsigned long long longest = 0;
+	for (int i = 0; i < a.nSeg; ++i) longest = a.seg[i].rowBytes > longest ? a.seg[i].rowBytes : longest;
+	int bx = int((longest/16 + 255)/256);
+	if (bx > 32) bx = 32;
+	if (bx < 1) bx = 1;
+	hipLaunchKernelGGL(kMoveStreams, dim3(bx, a.nSeg, a.nPairs), dim3(256), 0, st, a);
 }
 
 void launchAddPreRoll(const DevBatch &d, const float *preRoll, int length, const int *offsets, hipStream_t st) {
