@@ -15,6 +15,7 @@ namespace smst {
 
 static constexpr float kNoiseFloor = 1e-15f;     // signalsmith-stretch.h:508
 static constexpr float kMaxCleanStretch = 2.0f;  // :509
+static constexpr unsigned long long kEngineModulus = 2147483647ull; // 2^31 - 1: the random engine is libstdc++'s minstd_rand0 (:616; smst_kernels_common.h: engineDraw)
 
 // fftSamples chosen by the L1 layer: 2*fastSizeAbove(ceil(block/2)) with fast sizes {4,5,6,8}*2^k
 // (probe-verified for 5760/5292/4800/9600/11520).
@@ -239,7 +240,7 @@ void Batch::construct(const FftPlan &plan, long seed) {
 		std::vector<unsigned> pw(2*(size_t)M);
 		unsigned long long x = 1;
 		for (size_t j = 0; j < pw.size(); ++j) {
-			x = x*16807ull % 2147483647ull;
+			x = x*16807ull % kEngineModulus;
 			pw[j] = unsigned(x);
 		}
 		lcgHopJump = pw[2*(size_t)M - 3]; // 16807^(2M - 2): the draws of one randomised hop
@@ -365,7 +366,6 @@ void Batch::construct(const FftPlan &plan, long seed) {
 	hopCount.assign(S, 0);
 	leavesPendingV.assign(S, 0);
 	ridesV.assign(S, 0);
-	passV.assign(S, 0);
 	dInSamples = callSets[0].inSamples;
 	dOutSamples = callSets[0].outSamples;
 	dFlags = callSets[0].flags;
@@ -380,7 +380,7 @@ void Batch::construct(const FftPlan &plan, long seed) {
 	// std::default_random_engine (libstdc++: minstd_rand0) of a reference instance constructed with seed + s (:39; smst_kernels_common.h: engineDraw)
 	for (int s = 0; s < S; ++s) {
 		const unsigned long long u = (unsigned long long)(seed + s); // `long` -> the engine's unsigned 64-bit result_type
-		sched[s].seed = unsigned(u % 2147483647ull);
+		sched[s].seed = unsigned(u % kEngineModulus);
 		if (sched[s].seed == 0) sched[s].seed = 1;
 	}
 	StreamParams p{};
@@ -418,7 +418,7 @@ void Batch::construct(const FftPlan &plan, long seed) {
 		dZeroCounts = devAlloc<int>(S);
 		SMST_HIP(hipMemset(dZeroCounts, 0, S*sizeof(int)));
 		pendList.reserve(S);
-		pendTileHas.assign((size_t)nSub*kTileHasStride, 0);
+		pendTileHas.assign(nSub, TileSummary{});
 		pendMaxSpan.assign(nSub, 0);
 	}
 	SMST_HIP(hipDeviceSynchronize()); // the hipMemset calls above are ordered with the null stream only; the engine's streams are non-blocking
@@ -580,13 +580,13 @@ void Batch::resetStreams(const int *bitsHost, int allBits, const int *keepHost) 
 	if (bitsHost) SMST_HIP(hipMemcpy(dResetBits, bitsHost, S*sizeof(int), hipMemcpyHostToDevice));
 	if (keepHost) SMST_HIP(hipMemcpy(dKeep, keepHost, S*sizeof(int), hipMemcpyHostToDevice));
 	launchResetStreams(d, bitsHost ? dResetBits : nullptr, allBits, dSeedWp, st, keepHost ? dKeep : nullptr);
-	for (int s = 0; s < S; ++s) if ((bitsHost ? bitsHost[s] : allBits) & 1) histBase[s] = carryBase[s] = 0; // (the host's copies of DevBatch::histBase / carryBase)
+	for (int s = 0; s < S; ++s) if ((bitsHost ? bitsHost[s] : allBits) & RESET_STFT) histBase[s] = carryBase[s] = 0; // (the host's copies of DevBatch::histBase / carryBase)
 }
 
 void Batch::reset() { // signalsmith-stretch.h:49-60
 	SMST_HIP(hipSetDevice(dev));
 	SMST_HIP(hipMemsetAsync(d.stFreq, 0, (size_t)S*2*sizeof(float), st));
-	resetStreams(nullptr, 1 | 2 | 4 | 8);
+	resetStreams(nullptr, RESET_STFT | RESET_INPUT | RESET_PREV | RESET_OUTPUT);
 	for (auto &lh : lastHop) lh = LastHop();
 	std::fill(lastSteps.begin(), lastSteps.end(), 0);
 	std::fill(lastStarts.begin(), lastStarts.end(), 0);
@@ -606,7 +606,7 @@ void Batch::resetStream(int s) { // reset() for one stream; kResetStreams writes
 	SMST_HIP(hipStreamSynchronize(st)); // (an earlier launch may still read the mask buffer)
 	SMST_HIP(hipMemsetAsync(d.stFreq + 2*(size_t)s, 0, 2*sizeof(float), st));
 	std::fill(resetBitsV.begin(), resetBitsV.end(), 0);
-	resetBitsV[s] = 1 | 2 | 4 | 8;
+	resetBitsV[s] = RESET_STFT | RESET_INPUT | RESET_PREV | RESET_OUTPUT;
 	resetStreams(resetBitsV.data(), 0);
 	lastHop[s] = LastHop();
 	lastSteps[s] = 0;
@@ -815,10 +815,9 @@ size_t Batch::stepsExecuted(size_t steps, size_t k) const { // after k samples o
 // -- if reset(), a silent call or configure() drops it (blockProcess = {}) -- by the draws of the chunks that had run by then only.
 static unsigned lcgPower(unsigned long long n) { // 16807^n mod (2^31 - 1)
 	unsigned long long r = 1, b = 16807;
-	const unsigned long long m = 2147483647ull;
 	while (n) {
-		if (n & 1) r = r*b % m;
-		b = b*b % m;
+		if (n & 1) r = r*b % kEngineModulus;
+		b = b*b % kEngineModulus;
 		n >>= 1;
 	}
 	return unsigned(r);
@@ -833,8 +832,9 @@ unsigned Batch::seedAfterDroppedBlock(int s) const {
 	const size_t b0 = size_t(M)*chunks/8; // bins [0, b0) have drawn: one draw per bin for b > 0, one for b < M - 1
 	if (b0 == 0) return seed;
 	const unsigned long long draws = (b0 >= size_t(M)) ? 2ull*M - 2 : 2ull*b0 - 1;
-	return unsigned((unsigned long long)seed*lcgPower(draws) % 2147483647ull);
+	return unsigned((unsigned long long)seed*lcgPower(draws) % kEngineModulus);
 }
+unsigned Batch::advanceOneHop(unsigned seed) const { return unsigned((unsigned long long)seed*lcgHopJump % kEngineModulus); }
 
 // A setter is about to change params[s]: the steps of the block in flight that have already run saw the OLD values (:874, :982, :1020)
 void Batch::freezePendingParams(int s) {
@@ -846,6 +846,23 @@ void Batch::freezePendingParams(int s) {
 	if (l.peaks >= 0 && e > size_t(l.peaks) && !pb.frozenPeaks) { pb.peaks = params[s]; pb.frozenPeaks = true; }
 	if (l.form0 >= 0 && e > size_t(l.form0) && !pb.frozenForm0) { pb.form0 = params[s]; pb.frozenForm0 = true; }
 	if (l.form2 >= 0 && e > size_t(l.form2) && !pb.frozenForm2) { pb.form2 = params[s]; pb.frozenForm2 = true; }
+}
+
+// The block in flight of stream s as the hop that completes it: its spectra come from the pending buffers, and its frame lands where its
+// interval ends -- it began samplesSinceLast samples ago (outPos < 0; split computation delays every frame by one interval, :292-296)
+void Batch::pendingHop(int s, HopDesc &hd) const {
+	const PendingBlock &pb = pend[s];
+	hd.flags = pb.flags | HOP_PREANALYSED;
+	hd.timeFactor = pb.timeFactor;
+	hd.seed = pb.seed;
+	hd.startBin = pb.startBin; // (> 0 only in runPendingBlocks(): gateAndCount() sends such a block there; one that rides as a call's hop 0 has 0)
+	hd.outPos = -int(sched[s].samplesSinceLast);
+	const bool nw = (pb.flags & HOP_NEW_SPECTRUM) != 0;
+	hd.inSrc = nw ? 0 : SRC_STATE;
+	hd.prevSrc = (nw && (pb.flags & HOP_REANALYSE_PREV)) ? SRC_REANALYSED : SRC_STATE;
+}
+void Batch::noteLastHop(int s, int slot, int local, unsigned flags) { // where the stream's newest hop sits in the tile workspaces (debugGetMap)
+	lastHop[s] = LastHop{slot, local, s%subS, (flags & HOP_MAPPED) != 0, (flags & HOP_FORMANTS) != 0};
 }
 
 // The blocks in flight of the streams in `pendList` run to their end: one tile of one hop per stream whose spectra come from the
@@ -862,42 +879,30 @@ void Batch::runPendingBlocks(const int *synthChannels) {
 	std::memset(ps.hHops, 0, S*sizeof(HopDesc));
 	std::memset(ps.hEmit, 0, S*sizeof(EmitDesc));
 	std::memset(ps.hTileInfo, 0, (size_t)nSub*2*subS*sizeof(int));
-	std::fill(pendTileHas.begin(), pendTileHas.end(), 0);
+	std::fill(pendTileHas.begin(), pendTileHas.end(), TileSummary{});
 	std::fill(pendMaxSpan.begin(), pendMaxSpan.end(), 0);
 	bool anyFrozen = false, anyZeroPrev = false;
 	for (int s : pendList) {
 		const PendingBlock &pb = pend[s];
 		HopDesc &hd = ps.hHops[s];
-		hd.flags = pb.flags | HOP_PREANALYSED;
-		hd.timeFactor = pb.timeFactor;
-		hd.seed = pb.seed;
-		hd.startBin = pb.startBin;
-		hd.outPos = -int(sched[s].samplesSinceLast);
-		const bool nw = (pb.flags & HOP_NEW_SPECTRUM) != 0;
-		hd.inSrc = nw ? 0 : SRC_STATE;
-		hd.prevSrc = (nw && (pb.flags & HOP_REANALYSE_PREV)) ? SRC_REANALYSED : SRC_STATE;
+		pendingHop(s, hd);
 		EmitDesc &ed = ps.hEmit[s];
 		ed.firstHopPos = hd.outPos;
 		ed.hopCount = 1;
 		const int sub = s/subS, sl = s%subS;
 		int *info = ps.hTileInfo + (size_t)sub*2*subS;
 		info[sl] = 1;
-		info[subS + sl] = nw ? 0 : -1;
-		unsigned char *th = pendTileHas.data() + (size_t)sub*kTileHasStride;
-		th[0] = 1;
-		if (pb.flags & HOP_MAPPED) th[1] = 1;
-		if (pb.flags & HOP_FORMANTS) { th[2] = 1; th[10] = 1; } // (a block in flight may carry latched parameters: the three-kernel form decides per stream)
-		if (pb.flags & HOP_RANDOM_TF) th[4] = 1;
-		if (pb.startBin > 0) th[7] = 1;
-		th[8] = 1;
+		info[subS + sl] = (pb.flags & HOP_NEW_SPECTRUM) ? 0 : -1;
+		TileSummary &th = pendTileHas[sub];
+		th.anyHop = true;
+		if (pb.flags & HOP_MAPPED) th.mapped = true;
+		if (pb.flags & HOP_FORMANTS) th.formants = th.estimatesBase = true; // (a block in flight may carry latched parameters: the three-kernel form decides per stream)
+		if (pb.flags & HOP_RANDOM_TF) th.randomTimeFactor = true;
+		if (pb.startBin > 0) th.startBin = true;
+		th.preAnalysed = true;
 		anyFrozen = anyFrozen || pb.frozenPeaks || pb.frozenForm0 || pb.frozenForm2;
 		anyZeroPrev = anyZeroPrev || pb.zeroPrevAfter;
-		LastHop &lh = lastHop[s];
-		lh.slot = sub & 1;
-		lh.local = 0;
-		lh.subLocal = sl;
-		lh.mapped = (pb.flags & HOP_MAPPED) != 0;
-		lh.formants = (pb.flags & HOP_FORMANTS) != 0;
+		noteLastHop(s, sub & 1, 0, pb.flags);
 	}
 	SMST_HIP(hipMemcpyAsync(ps.hops, ps.hHops, S*sizeof(HopDesc), hipMemcpyHostToDevice, st));
 	SMST_HIP(hipMemcpyAsync(ps.emit, ps.hEmit, S*sizeof(EmitDesc), hipMemcpyHostToDevice, st));
@@ -927,14 +932,14 @@ void Batch::runPendingBlocks(const int *synthChannels) {
 	d.paramsPeaks = d.paramsForm0 = d.paramsForm2 = dParams;
 	if (anyZeroPrev) {
 		for (int s = 0; s < S; ++s) ps.hBits[s] = 0;
-		for (int s : pendList) if (pend[s].zeroPrevAfter) ps.hBits[s] = 4;
+		for (int s : pendList) if (pend[s].zeroPrevAfter) ps.hBits[s] = RESET_PREV;
 		SMST_HIP(hipMemcpyAsync(ps.bits, ps.hBits, S*sizeof(int), hipMemcpyHostToDevice, st));
 		launchResetStreams(d, ps.bits, 0, dSeedWp, st);
 	}
 	SMST_HIP(hipEventRecord(ps.done, st));
 	ps.used = true;
 	for (int s : pendList) {
-		if (pend[s].flags & HOP_RANDOM_TF) sched[s].seed = unsigned((unsigned long long)sched[s].seed*lcgHopJump % 2147483647ull); // its draws happen now
+		if (pend[s].flags & HOP_RANDOM_TF) sched[s].seed = advanceOneHop(sched[s].seed); // its draws happen now
 		pend[s] = PendingBlock();
 	}
 	pendList.clear();
@@ -972,6 +977,48 @@ void Batch::runTiles(const TileRun &run) {
 	d.carryCur = (carryFirst + nTiles) & 1;
 }
 
+// A segment of tiles begins: its three streams (all `st` when the run is serial), forked from what is already queued on `st`
+Batch::TileStreams Batch::forkTileStreams(const TileRun &run) {
+	const bool serial = profiling || !overlap || run.pendingRun;
+	const TileStreams ts{serial, st, serial ? st : stChain, serial ? st : stSynth};
+	if (!serial) {
+		SMST_HIP(hipEventRecord(evStart, st));
+		SMST_HIP(hipStreamWaitEvent(ts.sC, evStart, 0));
+		SMST_HIP(hipStreamWaitEvent(ts.sS, evStart, 0));
+	}
+	return ts;
+}
+// ... and ends: everything the caller can observe is ordered on `st` again -- `passes` tile passes over a ring of `depth` workspaces, from slot first % depth on
+void Batch::joinTileStreams(const TileStreams &ts, int first, int passes, int depth) {
+	if (ts.serial) return;
+	for (int i = 0; i < depth && i < passes; ++i) { // join the slots the segment used: (first + i) % depth, not i
+		SMST_HIP(hipStreamWaitEvent(st, evChain[(first + i)%depth], 0));
+		SMST_HIP(hipStreamWaitEvent(st, evSynth[(first + i)%depth], 0));
+	}
+}
+// The recurrence launch of a tile, timed as its class -- and in place, between two events on its own stream, where live timing is on
+template <typename F> void Batch::timedRecurrence(const TileStreams &ts, F &&launch) {
+	const bool live = liveTiming && !ts.serial;
+	if (live) {
+		if (liveEvents.size() == livePool.size()) growLivePool(livePool.size() + 64); // only if a run outgrows what enableProfiling() made
+		SMST_HIP(hipEventRecord(livePool[liveEvents.size()].first, ts.sC));
+	}
+	timed(timings.chainMs, [&] { launch(); if (profiling) ++timings.chainLaunches; });
+	if (live) {
+		SMST_HIP(hipEventRecord(livePool[liveEvents.size()].second, ts.sC));
+		liveEvents.push_back(livePool[liveEvents.size()]);
+	}
+}
+// The batch as the kernels of one tile see it: the tile's workspace, the half of the carry it writes, its rows of the tile-info table
+DevBatch Batch::tileView(const TileBuffers &w, int carryCur, const int *tileInfo) const {
+	DevBatch dd = d;
+	dd.Xcur = w.Xcur; dd.Xprev = w.Xprev; dd.PE = w.PE; dd.OUT = w.OUT; dd.REC = w.REC; dd.dump = w.dump;
+	dd.map = w.map; dd.ratio = w.ratio; dd.envelope = w.envelope; dd.energyT = w.energyT; dd.smoothT = w.smoothT; dd.peaksT = w.peaksT; dd.est = w.est; dd.freqEst = w.freqEst; dd.frames = w.frames; dd.fftScratch = w.fftScratch;
+	dd.carryCur = carryCur;
+	dd.nHops = tileInfo; dd.lastNewHop = tileInfo + subS;
+	return dd;
+}
+
 void Batch::runTilesRange(const TileRun &run, int tile0, int tile1, int carryFirst) {
 	const IoArgs &io = *run.io;
 	const int T = d.T, nTiles = run.nTiles, maxHops = run.maxHops;
@@ -979,129 +1026,98 @@ void Batch::runTilesRange(const TileRun &run, int tile0, int tile1, int carryFir
 	// Three HIP streams: `st` runs the feed-forward kernels of tile q, `stChain` the recurrence of tile q (a few
 	// hundred waves, instruction-issue bound), `stSynth` synthesis + emission.  Two workspaces alternate, so the bulk
 	// kernels of the next tile fill the machine while the recurrence of the current one is in flight.
-	const bool serial = profiling || !overlap || run.pendingRun;
+	const TileStreams ts = forkTileStreams(run);
 	const bool singleHop = singleHopSupported(d) && !noSingleHop;
-	hipStream_t sF = st, sC = serial ? st : stChain, sS = serial ? st : stSynth;
-	if (!serial) {
-		SMST_HIP(hipEventRecord(evStart, st));
-		SMST_HIP(hipStreamWaitEvent(sC, evStart, 0));
-		SMST_HIP(hipStreamWaitEvent(sS, evStart, 0));
-	}
 	int q = tile0; // (the workspace of tile t of a single sub-batch is slots[t & 1] whatever segment it runs in: debugGetMap relies on it)
 	for (int sub = 0; sub < nSub; ++sub) {
 		const int sBase = sub*subS;
 		const int ns = std::min(subS, S - sBase);
 		for (int t = tile0; t < tile1; ++t, ++q) {
-			const unsigned char *th = run.tileHas + (size_t)(sub*nTiles + t)*kTileHasStride;
+			const TileSummary &th = run.tileHas[(size_t)sub*nTiles + t];
 			const int hopBase = t*T;
 			const int tileHops = std::min(T, std::max(1, maxHops - hopBase));
 			const int slot = q & 1;
-			const bool plain = !(th[1] || th[2]);
+			const bool plain = th.plain();
 			const bool fused = fusedSupported(d) && !noFuse; // mono/stereo: records stay in LDS (kVocoder)
-			const TileBuffers &w = slots[slot];
-			DevBatch dd = d;
-			dd.Xcur = w.Xcur; dd.Xprev = w.Xprev; dd.PE = w.PE; dd.OUT = w.OUT; dd.REC = w.REC; dd.dump = w.dump;
-			dd.map = w.map; dd.ratio = w.ratio; dd.envelope = w.envelope; dd.energyT = w.energyT; dd.smoothT = w.smoothT; dd.peaksT = w.peaksT; dd.est = w.est; dd.freqEst = w.freqEst; dd.frames = w.frames; dd.fftScratch = w.fftScratch;
-			dd.carryCur = (carryFirst + t) & 1;
-			dd.nHops = run.dTileInfo + ((size_t)(sub*nTiles + t)*2)*subS;
-			dd.lastNewHop = dd.nHops + subS;
-			if (!serial && q - tile0 >= 2) { // this workspace was last used by tile q-2
-				SMST_HIP(hipStreamWaitEvent(sF, evChain[slot], 0));
-				SMST_HIP(hipStreamWaitEvent(sF, evSynth[slot], 0));
+			const DevBatch dd = tileView(slots[slot], (carryFirst + t) & 1, run.dTileInfo + ((size_t)(sub*nTiles + t)*2)*subS);
+			if (!ts.serial && q - tile0 >= 2) { // this workspace was last used by tile q-2
+				SMST_HIP(hipStreamWaitEvent(ts.sF, evChain[slot], 0));
+				SMST_HIP(hipStreamWaitEvent(ts.sF, evSynth[slot], 0));
 			}
-			if (!serial && fused && !plain && q - tile0 >= 1) SMST_HIP(hipStreamWaitEvent(sF, evChain[slot ^ 1], 0)); // pass A reads the carried state
-			if (th[0]) {
-				if (th[8]) timed(timings.otherMs, [&] { launchPendingToTile(dd, sBase, ns, dPendIn, dPendPrev, sF); }); // blocks that began in an earlier call: their spectra are waiting
-				if (th[3]) timed(timings.analyseMs, [&] { launchAnalyse(dd, io, sBase, ns, hopBase, tileHops, th[5] != 0, th[6] != 0, sF); if (profiling) ++timings.analyseLaunches; });
+			if (!ts.serial && fused && !plain && q - tile0 >= 1) SMST_HIP(hipStreamWaitEvent(ts.sF, evChain[slot ^ 1], 0)); // pass A reads the carried state
+			if (th.anyHop) {
+				if (th.preAnalysed) timed(timings.otherMs, [&] { launchPendingToTile(dd, sBase, ns, dPendIn, dPendPrev, ts.sF); }); // blocks that began in an earlier call: their spectra are waiting
+				if (th.newSpectrum) timed(timings.analyseMs, [&] { launchAnalyse(dd, io, sBase, ns, hopBase, tileHops, th.windowInCall, th.windowInHistory, ts.sF); if (profiling) ++timings.analyseLaunches; });
 				bool passADone = false;
-				if (th[1] || th[2]) timed(timings.feedMs, [&] { passADone = launchFeed(dd, sBase, ns, hopBase, tileHops, th[2] != 0, th[10] != 0, sF); });
+				if (!plain) timed(timings.feedMs, [&] { passADone = launchFeed(dd, sBase, ns, hopBase, tileHops, th.formants, th.estimatesBase, ts.sF); });
 				timed(timings.predictMs, [&] {
-					if (fused) launchPredictFused(dd, sBase, ns, hopBase, tileHops, plain, passADone, sF);
-					else launchPredict(dd, sBase, ns, hopBase, tileHops, plain, passADone, sF);
+					if (fused) launchPredictFused(dd, sBase, ns, hopBase, tileHops, plain, passADone, ts.sF);
+					else launchPredict(dd, sBase, ns, hopBase, tileHops, plain, passADone, ts.sF);
 					if (profiling) ++timings.predictLaunches;
 				});
 				// the carried feed-forward state (Band.input/.prevInput, Prediction.energy) may only move on once every
 				// reader of the OLD state has run: in the fused path the producers inside kVocoder still read it
-				if (!fused) timed(timings.otherMs, [&] { launchCarryFeed(dd, sBase, ns, hopBase, th[2] != 0, sF); });
+				if (!fused) timed(timings.otherMs, [&] { launchCarryFeed(dd, sBase, ns, hopBase, th.formants, ts.sF); });
 			}
 			checkLaunch("analysis / feed-forward kernels");
-			if (!serial) {
-				SMST_HIP(hipEventRecord(evFeed[slot], sF));
-				SMST_HIP(hipStreamWaitEvent(sC, evFeed[slot], 0));
+			if (!ts.serial) {
+				SMST_HIP(hipEventRecord(evFeed[slot], ts.sF));
+				SMST_HIP(hipStreamWaitEvent(ts.sC, evFeed[slot], 0));
 			}
 			// synthesis + overlap-add + emission in one kernel where the geometry and the batch allow it
-			const bool emitted = th[0] && !th[8] && synthEmitApplies(dd, ns, tileHops); // (th[8]: a hop that began before the call's first sample -- kSynthTeams + kEmit place its frame)
+			const bool emitted = th.anyHop && !th.preAnalysed && synthEmitApplies(dd, ns, tileHops); // (preAnalysed: a hop that began before the call's first sample -- kSynthTeams + kEmit place its frame)
 			const bool earlySynth = emitted || tileHops == 1;
-			if (th[0]) {
-				hipEvent_t liveA = nullptr, liveB = nullptr;
-				if (liveTiming && !serial) {
-					if (liveEvents.size() == livePool.size()) growLivePool(livePool.size() + 64); // only if a run outgrows what enableProfiling() made
-					liveA = livePool[liveEvents.size()].first;
-					liveB = livePool[liveEvents.size()].second;
-					SMST_HIP(hipEventRecord(liveA, sC));
-				}
-				timed(timings.chainMs, [&] {
-					// (th[7]: a block that a flush() interrupted inside its main prediction, HopDesc.startBin > 0.  Every form that forms its
+			if (th.anyHop) {
+				timedRecurrence(ts, [&] {
+					// (startBin: a block that a flush() interrupted inside its main prediction, HopDesc.startBin > 0.  Every form that forms its
 					// records through computeRecord honours it (all-zero records below the start bin); the staged / line-aligned producers of
 					// kVocoder do not go through it, so such a tile takes the gathering form -- `bounded` false)
-					if (fused && tileHops == 1 && singleHop && !noAcross && acrossSupported(dd) && !th[7]) launchVocoderAcross(dd, sBase, ns, hopBase, plain, sC);
-					else if (fused && tileHops == 1 && singleHop) launchVocoderOne(dd, sBase, ns, hopBase, plain, sC);
-					else if (fused) launchVocoder(dd, sBase, ns, hopBase, plain, !th[4] && !th[7], sC);
-					else launchChain(dd, sBase, ns, hopBase, sC);
-					if (profiling) ++timings.chainLaunches;
+					if (fused && tileHops == 1 && singleHop && !noAcross && acrossSupported(dd) && !th.startBin) launchVocoderAcross(dd, sBase, ns, hopBase, plain, ts.sC);
+					else if (fused && tileHops == 1 && singleHop) launchVocoderOne(dd, sBase, ns, hopBase, plain, ts.sC);
+					else if (fused) launchVocoder(dd, sBase, ns, hopBase, plain, !th.randomTimeFactor && !th.startBin, ts.sC);
+					else launchChain(dd, sBase, ns, hopBase, ts.sC);
 				});
-				if (liveA) {
-					SMST_HIP(hipEventRecord(liveB, sC));
-					liveEvents.emplace_back(liveA, liveB);
-				}
 				// synthesis needs the recurrence's rows only: the hand-over of the tile's last rows to the carried state (two copies at HBM rate --
 				// 250 us of a 4096-stream hop quantum) runs beside it, behind the event synthesis waits for.  Where synthesis is a grid of
 				// per-frame workgroups and more recurrence launches follow (config 5) the hand-over goes first, as before: it is what the NEXT
 				// recurrence waits for, and behind a machine full of synthesis workgroups it would start late (config 5: 99.6 -> 101 ms)
 				timed(timings.otherMs, [&] {
 					if (run.dSynthChannels || !earlySynth) { // (the carried output state takes the rows as the recurrence left them)
-						launchCarryOut(dd, sBase, ns, sC);
-						if (run.dSynthChannels) launchMaskOutRows(dd, sBase, ns, run.dSynthChannels, sC);
+						launchCarryOut(dd, sBase, ns, ts.sC);
+						if (run.dSynthChannels) launchMaskOutRows(dd, sBase, ns, run.dSynthChannels, ts.sC);
 					}
-					if (!earlySynth && fused) launchCarryFeed(dd, sBase, ns, hopBase, th[2] != 0, sC);
-					if (!serial) SMST_HIP(hipEventRecord(evOut[slot], sC));
-					if (earlySynth && fused) launchCarryFeed(dd, sBase, ns, hopBase, th[2] != 0, sC);
-					if (earlySynth && !run.dSynthChannels) launchCarryOut(dd, sBase, ns, sC);
+					if (!earlySynth && fused) launchCarryFeed(dd, sBase, ns, hopBase, th.formants, ts.sC);
+					if (!ts.serial) SMST_HIP(hipEventRecord(evOut[slot], ts.sC));
+					if (earlySynth && fused) launchCarryFeed(dd, sBase, ns, hopBase, th.formants, ts.sC);
+					if (earlySynth && !run.dSynthChannels) launchCarryOut(dd, sBase, ns, ts.sC);
 				});
 			}
 			checkLaunch("bin recurrence");
 			// kSynthEmitTeams' window products depend on nothing the recurrence writes: queued in front of the wait for it
-			if (emitted) timed(timings.otherMs, [&] { launchEmitProducts(dd, sBase, ns, t, sS); });
-			if (!serial) {
-				SMST_HIP(hipEventRecord(evChain[slot], sC));
-				SMST_HIP(hipStreamWaitEvent(sS, th[0] ? evOut[slot] : evChain[slot], 0));
+			if (emitted) timed(timings.otherMs, [&] { launchEmitProducts(dd, sBase, ns, t, ts.sS); });
+			if (!ts.serial) {
+				SMST_HIP(hipEventRecord(evChain[slot], ts.sC));
+				SMST_HIP(hipStreamWaitEvent(ts.sS, th.anyHop ? evOut[slot] : evChain[slot], 0));
 			}
-			if (th[0]) timed(timings.synthMs, [&] {
-				if (emitted) launchSynthEmit(dd, io, sBase, ns, t, sS);
-				else launchSynth(dd, sBase, ns, hopBase, tileHops, sS);
+			if (th.anyHop) timed(timings.synthMs, [&] {
+				if (emitted) launchSynthEmit(dd, io, sBase, ns, t, ts.sS);
+				else launchSynth(dd, sBase, ns, hopBase, tileHops, ts.sS);
 				if (profiling) ++timings.synthLaunches;
 			});
-			if (!emitted) timed(timings.emitMs, [&] { launchEmit(dd, io, sBase, ns, t, run.maxSpan[(size_t)sub*nTiles + t], sS); if (profiling) ++timings.emitLaunches; });
+			if (!emitted) timed(timings.emitMs, [&] { launchEmit(dd, io, sBase, ns, t, run.maxSpan[(size_t)sub*nTiles + t], ts.sS); if (profiling) ++timings.emitLaunches; });
 			checkLaunch("synthesis / emission");
-			if (!serial) SMST_HIP(hipEventRecord(evSynth[slot], sS));
+			if (!ts.serial) SMST_HIP(hipEventRecord(evSynth[slot], ts.sS));
 		}
 	}
-	if (!serial) { // everything the caller can observe is ordered on `st` again
-		for (int i = 0; i < 2 && i < q - tile0; ++i) { // join the slots this range used: (tile0 + i) & 1, not i (tile0 may be odd)
-			SMST_HIP(hipStreamWaitEvent(st, evChain[(tile0 + i) & 1], 0));
-			SMST_HIP(hipStreamWaitEvent(st, evSynth[(tile0 + i) & 1], 0));
-		}
-	}
+	joinTileStreams(ts, tile0, q - tile0, 2); // (passes, not tiles: q runs on through the sub-batches; tile0 may be odd)
 }
 
 // Whether a tile can be part of a continuous wavefront (kVocoderCont; runs of two or more such tiles are): the geometries of the
-// line-aligned producers, one sub-batch, the tile plain, bounded, whole-line -- what launchVocoder sends to the aligned form -- with a
-// new spectrum in every hop (the rows of a later tile then never read the carried feed-forward state).
+// line-aligned producers, one sub-batch, and what the tile's hops need (TileSummary::continuousCapable).
 bool Batch::continuousApplies(const TileRun &run, int t) const {
 	if (!slots[2].Xcur || run.pendingRun || run.carriedOnly || subS != S) return false;
 	if (!(d.L == 4 || d.alignAll)) return false; // (as launchVocoder chooses the aligned producers)
-	const unsigned char *th = run.tileHas + (size_t)t*kTileHasStride;
-	return th[0] && !th[1] && !th[2] && !th[4] && !th[7] && !th[8] && !th[9];
+	return run.tileHas[t].continuousCapable();
 }
 
 // The same pipeline as runTiles -- analysis of tile t+1, recurrence, synthesis + emission over three HIP streams -- with the recurrence as
@@ -1111,22 +1127,11 @@ bool Batch::continuousApplies(const TileRun &run, int t) const {
 void Batch::runTilesContinuous(const TileRun &run, int tile0, int tile1, int carryFirst) {
 	const IoArgs &io = *run.io;
 	const int T = d.T, maxHops = run.maxHops;
-	const bool serial = profiling || !overlap;
-	hipStream_t sF = st, sC = serial ? st : stChain, sS = serial ? st : stSynth;
-	if (!serial) {
-		SMST_HIP(hipEventRecord(evStart, st));
-		SMST_HIP(hipStreamWaitEvent(sC, evStart, 0));
-		SMST_HIP(hipStreamWaitEvent(sS, evStart, 0));
-	}
+	const TileStreams ts = forkTileStreams(run); // (a run of blocks in flight never comes here: continuousApplies)
 	const int P = continuousPeriod(d);
-	auto tileView = [&](int t) {
-		const TileBuffers &w = slots[t%3];
-		DevBatch dd = d;
-		dd.Xcur = w.Xcur; dd.Xprev = w.Xprev; dd.OUT = w.OUT; dd.frames = w.frames; dd.fftScratch = w.fftScratch;
-		dd.PE = nullptr; dd.REC = nullptr; dd.map = nullptr; dd.ratio = nullptr; // (plain tiles: never touched)
-		dd.carryCur = (carryFirst + t) & 1;
-		dd.nHops = run.dTileInfo + ((size_t)t*2)*subS;
-		dd.lastNewHop = dd.nHops + subS;
+	auto view = [&](int t) {
+		DevBatch dd = tileView(slots[t%3], (carryFirst + t) & 1, run.dTileInfo + ((size_t)t*2)*subS);
+		dd.PE = nullptr; dd.REC = nullptr; dd.map = nullptr; dd.ratio = nullptr; // (plain tiles: never touched -- nor are the slot's dump / envelope / serial-feed scratch / est / freqEst that tileView hands over: no kernel of this path reads them)
 		return dd;
 	};
 	auto tileHops = [&](int t) { return std::min(T, std::max(1, maxHops - t*T)); };
@@ -1135,39 +1140,39 @@ void Batch::runTilesContinuous(const TileRun &run, int tile0, int tile1, int car
 		for (int s = 0; s < S; ++s) if (hopCount[s] > 0 && (hopCount[s] - 1)/T == t) return true;
 		return false;
 	};
-	// tile t is complete (its last rows ran in the launch just enqueued on sC): hand-over to the carried state, synthesis + emission
+	// tile t is complete (its last rows ran in the launch just enqueued on ts.sC): hand-over to the carried state, synthesis + emission
 	auto finishTile = [&](int t, int launch) {
-		const DevBatch dd = tileView(t);
+		const DevBatch dd = view(t);
 		const bool emitted = synthEmitApplies(dd, S, tileHops(t));
 		if (lastOfSomeStream(t)) // (only a stream's last tile goes to the carried state)
 		 timed(timings.otherMs, [&] {
-			launchCarryFeed(dd, 0, S, t*T, false, sC);
-			launchCarryOut(dd, 0, S, sC);
+			launchCarryFeed(dd, 0, S, t*T, false, ts.sC);
+			launchCarryOut(dd, 0, S, ts.sC);
 		});
-		if (!serial) SMST_HIP(hipEventRecord(evChain[t%3], sC)); // (everything that reads tile t's workspace on sC is in front of this)
-		if (emitted) timed(timings.otherMs, [&] { launchEmitProducts(dd, 0, S, t, sS); });
-		if (!serial) SMST_HIP(hipStreamWaitEvent(sS, evOut[launch%3], 0));
+		if (!ts.serial) SMST_HIP(hipEventRecord(evChain[t%3], ts.sC)); // (everything that reads tile t's workspace on ts.sC is in front of this)
+		if (emitted) timed(timings.otherMs, [&] { launchEmitProducts(dd, 0, S, t, ts.sS); });
+		if (!ts.serial) SMST_HIP(hipStreamWaitEvent(ts.sS, evOut[launch%3], 0));
 		timed(timings.synthMs, [&] {
-			if (emitted) launchSynthEmit(dd, io, 0, S, t, sS);
-			else launchSynth(dd, 0, S, t*T, tileHops(t), sS);
+			if (emitted) launchSynthEmit(dd, io, 0, S, t, ts.sS);
+			else launchSynth(dd, 0, S, t*T, tileHops(t), ts.sS);
 			if (profiling) ++timings.synthLaunches;
 		});
-		if (!emitted) timed(timings.emitMs, [&] { launchEmit(dd, io, 0, S, t, run.maxSpan[t], sS); if (profiling) ++timings.emitLaunches; });
+		if (!emitted) timed(timings.emitMs, [&] { launchEmit(dd, io, 0, S, t, run.maxSpan[t], ts.sS); if (profiling) ++timings.emitLaunches; });
 		checkLaunch("synthesis / emission");
-		if (!serial) SMST_HIP(hipEventRecord(evSynth[t%3], sS));
+		if (!ts.serial) SMST_HIP(hipEventRecord(evSynth[t%3], ts.sS));
 	};
 	for (int t = tile0; t < tile1; ++t) {
-		const unsigned char *th = run.tileHas + (size_t)t*kTileHasStride;
-		const DevBatch dd = tileView(t);
-		if (!serial && t >= tile0 + 3) { // this workspace held tile t-3: its spectra were last read by launch t-2, its results by the synthesis of tile t-3
-			SMST_HIP(hipStreamWaitEvent(sF, evChain[t%3], 0));
-			SMST_HIP(hipStreamWaitEvent(sF, evSynth[t%3], 0));
+		const TileSummary &th = run.tileHas[t];
+		const DevBatch dd = view(t);
+		if (!ts.serial && t >= tile0 + 3) { // this workspace held tile t-3: its spectra were last read by launch t-2, its results by the synthesis of tile t-3
+			SMST_HIP(hipStreamWaitEvent(ts.sF, evChain[t%3], 0));
+			SMST_HIP(hipStreamWaitEvent(ts.sF, evSynth[t%3], 0));
 		}
-		timed(timings.analyseMs, [&] { launchAnalyse(dd, io, 0, S, t*T, tileHops(t), th[5] != 0, th[6] != 0, sF); if (profiling) ++timings.analyseLaunches; });
+		timed(timings.analyseMs, [&] { launchAnalyse(dd, io, 0, S, t*T, tileHops(t), th.windowInCall, th.windowInHistory, ts.sF); if (profiling) ++timings.analyseLaunches; });
 		checkLaunch("analysis");
-		if (!serial) {
-			SMST_HIP(hipEventRecord(evFeed[t%3], sF));
-			SMST_HIP(hipStreamWaitEvent(sC, evFeed[t%3], 0));
+		if (!ts.serial) {
+			SMST_HIP(hipEventRecord(evFeed[t%3], ts.sF));
+			SMST_HIP(hipStreamWaitEvent(ts.sC, evFeed[t%3], 0));
 		}
 		ContArgs a{};
 		const TileBuffers &w0 = slots[(t + 2)%3], &w1 = slots[t%3]; // tile t-1, tile t
@@ -1183,28 +1188,229 @@ void Batch::runTilesContinuous(const TileRun &run, int tile0, int tile1, int car
 		a.n1 = (t == tile1 - 1) ? P*(a.tile + 1) + 62 : P*(a.tile + 1); // the last launch runs until row 63 of the last tile is through
 		a.save = dContSave;
 		a.writerWave = contWriterWave;
-		hipEvent_t liveA = nullptr, liveB = nullptr;
-		if (liveTiming && !serial) {
-			if (liveEvents.size() == livePool.size()) growLivePool(livePool.size() + 64);
-			liveA = livePool[liveEvents.size()].first;
-			liveB = livePool[liveEvents.size()].second;
-			SMST_HIP(hipEventRecord(liveA, sC));
-		}
-		timed(timings.chainMs, [&] { launchVocoderContinuous(d, a, 0, S, sC); if (profiling) ++timings.chainLaunches; });
-		if (liveA) {
-			SMST_HIP(hipEventRecord(liveB, sC));
-			liveEvents.emplace_back(liveA, liveB);
-		}
+		timedRecurrence(ts, [&] { launchVocoderContinuous(d, a, 0, S, ts.sC); });
 		checkLaunch("bin recurrence (continuous)");
-		if (!serial) SMST_HIP(hipEventRecord(evOut[t%3], sC));
+		if (!ts.serial) SMST_HIP(hipEventRecord(evOut[t%3], ts.sC));
 		if (t > tile0) finishTile(t - 1, t);
 	}
 	finishTile(tile1 - 1, tile1 - 1);
-	if (!serial) {
-		for (int i = 0; i < 3 && i < tile1 - tile0; ++i) { // everything the caller can observe is ordered on `st` again
-			SMST_HIP(hipStreamWaitEvent(st, evChain[(tile0 + i)%3], 0)); // join the slots this segment used: (tile0 + i) % 3, not i
-			SMST_HIP(hipStreamWaitEvent(st, evSynth[(tile0 + i)%3], 0));
+	joinTileStreams(ts, tile0, tile1 - tile0, 3);
+}
+
+// K0, pass 1: silence gate (signalsmith-stretch.h:231-278) and the number of hops each stream fires in this call.  Host only.
+void Batch::gateAndCount(CallPlan &c) {
+	const CallSet &cs = *c.cs;
+	const int *nIn = cs.hInSamples, *nOut = cs.hOutSamples;
+	int *passFlags = cs.hFlags;
+	int *clearBits = cs.hResetBits; // per CALL (pinned + its own device copy): a shared buffer could be overwritten by the next call's upload before this call's kResetStreams has run
+	pendList.clear();
+	for (int s = 0; s < S; ++s) {
+		passFlags[s] = 0;
+		hopFirst[s] = 0;
+		hopCount[s] = 0;
+		leavesPendingV[s] = 0;
+		ridesV[s] = 0;
+		clearBits[s] = 0;
+		if (c.active && !c.active[s]) continue;
+		lastHop[s].slot = -1; // smst_batch_debug_get_map reports the newest hop of THIS call only
+		StreamSched &sc = sched[s];
+		float e = 0;
+		for (int p = 0; p < kEnergyParts; ++p) e += cs.hEnergy[(size_t)s*kEnergyParts + p];
+		if (e < kNoiseFloor) { // :240-278
+			if (sc.silenceCounter >= size_t(2*B)) {
+				if (sc.silenceFirst) {
+					sc.silenceFirst = false;
+					sc.seed = seedAfterDroppedBlock(s); // ... which drops the block in flight, with the draws it has made
+					sc.samplesSinceLast = SIZE_MAX; // blockProcess = {}
+					pend[s] = PendingBlock();
+					clearBits[s] = RESET_INPUT | RESET_PREV | RESET_OUTPUT; // Band.input / .prevInput / .output := 0
+					c.anyClear = true;
+				}
+				passFlags[s] = 1;
+				c.anyPass = true;
+				continue; // the input history is still updated, at the end of process() (copyInput, :270)
+			} else {
+				sc.silenceCounter += size_t(nIn[s]);
+			}
+		} else {
+			sc.silenceCounter = 0;
+			sc.silenceFirst = true;
 		}
+		const int first = (sc.samplesSinceLast >= size_t(I)) ? 0 : int(size_t(I) - sc.samplesSinceLast);
+		hopFirst[s] = first;
+		const int starts = (nOut[s] > first) ? (nOut[s] - first + I - 1)/I : 0; // blocks that begin in this call (:281)
+		lastStarts[s] = starts;
+		if (split) {
+			// split computation: a block is finished when its interval is (:321-325).  The block in flight from earlier calls runs now if
+			// this call reaches the end of its interval; the last block that begins here stays in flight unless its interval ends here too
+			// (a plain one becomes the stream's first hop of this call; one that a flush() interrupted or whose steps saw different parameters runs by itself first)
+			if (pend[s].valid && nOut[s] >= first) {
+				const PendingBlock &pb = pend[s];
+				if (pb.startBin > 0 || pb.zeroPrevAfter || pb.frozenPeaks || pb.frozenForm0 || pb.frozenForm2) pendList.push_back(s);
+				else ridesV[s] = 1;
+			}
+			const int complete = (nOut[s] > first) ? (nOut[s] - first)/I : 0;
+			leavesPendingV[s] = starts > complete;
+			hopCount[s] = complete + ridesV[s];
+		} else {
+			hopCount[s] = starts;
+		}
+		c.maxHops = std::max(c.maxHops, hopCount[s]);
+	}
+}
+
+// One of a call set's tables has to hold `need` elements: a table that is outgrown is replaced, device copy and pinned staging.  The old pair
+// of the set in use is free at once (its last call has finished); the other set's may still be read by the previous call's kernels
+template <typename T> void Batch::growCallTable(CallSet &t, bool mine, T *&dev, T *&host, size_t &cap, size_t need) {
+	if (need <= cap) return;
+	if (mine) { devFree(dev); pinnedFree(host); }
+	else { if (dev) t.retiredDevice.push_back(dev); if (host) t.retiredPinned.push_back(host); }
+	cap = need + need/4;
+	dev = devAlloc<T>(cap);
+	host = pinnedAlloc<T>(cap);
+}
+// per-call tables: pinned staging and device copies grow only when a call needs more hops than any earlier call -- and
+// then BOTH sets grow, so that the call after this one (which uses the other set) does not allocate either.  The other
+// set's old tables may still be read by the previous call's kernels: they are retired and freed when that set is next used.
+void Batch::growCallTables(const CallPlan &c) {
+	CallSet &cs = *c.cs;
+	for (void *q : cs.retiredDevice) devFree(q);
+	for (void *q : cs.retiredPinned) pinnedFree(q);
+	cs.retiredDevice.clear();
+	cs.retiredPinned.clear();
+	for (int which = 0; which < 2; ++which) {
+		CallSet &t = callSets[which ? callCur ^ 1 : callCur];
+		growCallTable(t, which == 0, t.hops, t.hHops, t.hopsCap, c.needHops);
+		growCallTable(t, which == 0, t.emit, t.hEmit, t.emitCap, c.needEmit);
+		growCallTable(t, which == 0, t.tileInfo, t.hTileInfo, t.tileInfoCap, c.needInfo);
+	}
+}
+
+// K0, pass 2: the block scheduler of stream s, exactly as signalsmith-stretch.h:280-319 does it, straight into the stream's row of the hop
+// table; the last block that begins in the call may stay in flight (PendingBlock).  Host only.
+void Batch::scheduleStream(CallPlan &c, int s) {
+	CallSet &cs = *c.cs;
+	const int *nIn = cs.hInSamples, *nOut = cs.hOutSamples;
+	const int T = d.T;
+	const bool on = !(c.active && !c.active[s]) && !cs.hFlags[s]; // (neither masked out nor passed through by the silence gate)
+	HopDesc *list = cs.hHops + (size_t)s*c.hopStride;
+	const int nh = hopCount[s];
+	const int rides = ridesV[s]; // split computation: the block in flight from an earlier call is this call's hop 0 ...
+	const int nStart = nh + (leavesPendingV[s] ? 1 : 0); // ... and the last block that begins here may stay in flight
+	if (split) cs.hPendHops[s] = HopDesc{};
+	int lastNew = -1;
+	if (rides) {
+		pendingHop(s, list[0]);
+		if (pend[s].flags & HOP_NEW_SPECTRUM) lastNew = 0;
+		if (pend[s].flags & HOP_RANDOM_TF) sched[s].seed = advanceOneHop(sched[s].seed); // its draws happen now
+		pend[s] = PendingBlock();
+	}
+	if (nStart > rides) {
+		StreamSched &sc = sched[s];
+		const StreamParams &prm = params[s];
+		const bool mapped = prm.hasCustomMap || prm.freqMultiplier != 1; // :300
+		const bool formants = prm.formantMultiplier != 1 || (prm.formantCompensation && mapped); // :310
+		int o = hopFirst[s];
+		for (int j = rides; j < nStart; ++j, o += I) {
+			HopDesc inFlight{};
+			HopDesc &hd = (j < nh) ? list[j] : inFlight;
+			int inputOffset = int(std::round(o*float(nIn[s])/nOut[s])); // :288 (fp32 on purpose)
+			int inputInterval = inputOffset - sc.prevInputOffset;
+			sc.prevInputOffset = inputOffset;
+			hd.inputOffset = inputOffset;
+			hd.outPos = o;
+			unsigned flags = HOP_ACTIVE;
+			const bool newSpectrum = sc.didSeek || inputInterval > 0; // :299
+			bool reanalyse = false;
+			if (newSpectrum) {
+				flags |= HOP_NEW_SPECTRUM;
+				reanalyse = sc.didSeek || std::abs(inputInterval - I) > 1; // :303
+				if (reanalyse) flags |= HOP_REANALYSE_PREV;
+			}
+			if (mapped) flags |= HOP_MAPPED;
+			if (formants) flags |= HOP_FORMANTS;
+			float tf = sc.didSeek ? sc.seekTimeFactor : float(I)/std::max<float>(1, float(inputInterval)); // :312
+			sc.didSeek = false;
+			tf = std::max<float>(tf, 1/kMaxCleanStretch); // :638
+			if (tf > kMaxCleanStretch) flags |= HOP_RANDOM_TF; // :639
+			hd.timeFactor = tf;
+			hd.flags = flags;
+			lastSteps[s] = stepLayout(flags).steps;
+			hd.seed = sc.seed; // the engine's state before this hop's draws
+			if ((flags & HOP_RANDOM_TF) && j < nh) sc.seed = advanceOneHop(sc.seed); // 2M - 2 draws later (a block left in flight draws when it runs: seedAfterDroppedBlock)
+			if (j == nh) {
+				// in flight at the end of the call: analysed now, from the input as it stands (:293 stashes it), into the pending buffers;
+				// everything else when its interval is complete -- or when a flush() needs to know how far it has come
+				PendingBlock &pb = pend[s];
+				pb = PendingBlock();
+				pb.valid = true;
+				pb.flags = flags;
+				pb.timeFactor = tf;
+				pb.seed = hd.seed;
+				HopDesc &ph = cs.hPendHops[s];
+				ph.inputOffset = inputOffset;
+				ph.flags = flags & (HOP_ACTIVE | HOP_NEW_SPECTRUM | HOP_REANALYSE_PREV);
+				if (newSpectrum) {
+					c.anyPendAnalysis = true;
+					for (int which = 0; which < (reanalyse ? 2 : 1); ++which) (analysisWindowInCall(d.B, d.M, d.I, inputOffset, which, nIn[s]) ? c.pendInCall : c.pendLate) = true;
+				}
+				continue;
+			}
+			const int tile = j/T;
+			const bool lastInTile = lastNew >= 0 && lastNew/T == tile;
+			hd.inSrc = newSpectrum ? j%T : (lastInTile ? lastNew%T : SRC_STATE);
+			if (newSpectrum && reanalyse) hd.prevSrc = SRC_REANALYSED;
+			else hd.prevSrc = lastInTile ? lastNew%T : SRC_STATE;
+			if (newSpectrum) lastNew = j;
+		}
+		sc.samplesSinceLast = size_t(nOut[s] - (o - I));
+	} else if (on && sched[s].samplesSinceLast != SIZE_MAX) {
+		sched[s].samplesSinceLast += size_t(nOut[s]);
+	}
+	if (on) sched[s].prevInputOffset -= nIn[s]; // :419
+}
+
+// What the hops that scheduleStream() gave stream s mean for each tile: the stream's emission windows, its rows of the tile-info table
+// (layout [sub][tile][2][subS]: nHops, lastNewHop), its share of the tiles' summaries and spans.  Host only.
+void Batch::summariseStreamTiles(const CallPlan &c, int s) {
+	const CallSet &cs = *c.cs;
+	const int T = d.T, nTiles = c.nTiles, sub = s/subS, sl = s%subS;
+	const int nIn = cs.hInSamples[s], nh = hopCount[s];
+	const HopDesc *list = cs.hHops + (size_t)s*c.hopStride;
+	for (int t = 0; t < nTiles; ++t) {
+		const int h0 = t*T, h1 = std::min(nh, h0 + T);
+		const int cnt = std::max(0, h1 - h0);
+		EmitDesc ed{};
+		const int total = cs.hFlags[s] ? 0 : cs.hOutSamples[s];
+		if (t == 0) ed.nLo = 0; else ed.nLo = (h0 < nh) ? list[h0].outPos : total;
+		ed.nHi = (h1 < nh && cnt > 0) ? list[h1].outPos : total;
+		if (cnt == 0 && t > 0) ed.nLo = ed.nHi = total;
+		ed.firstHopPos = cnt > 0 ? list[h0].outPos : 0;
+		ed.hopCount = cnt;
+		cs.hEmit[(size_t)s*nTiles + t] = ed;
+		int *info = cs.hTileInfo + ((size_t)(sub*nTiles + t)*2)*subS;
+		info[sl] = cnt;
+		int lastNewLocal = -1;
+		TileSummary &th = tileHasV[(size_t)sub*nTiles + t];
+		for (int h = h0; h < h1; ++h) {
+			const unsigned f = list[h].flags;
+			if (f & HOP_PREANALYSED) th.preAnalysed = true;
+			if ((f & HOP_NEW_SPECTRUM) && (f & HOP_PREANALYSED)) lastNewLocal = h - h0;
+			if ((f & HOP_NEW_SPECTRUM) && !(f & HOP_PREANALYSED)) {
+				lastNewLocal = h - h0; th.newSpectrum = true;
+				// analysis frames whose window lies in this call's input (taken by kAnalyseTeams) / reaches into the history
+				for (int which = 0; which < ((f & HOP_REANALYSE_PREV) ? 2 : 1); ++which) (analysisWindowInCall(d.B, d.M, d.I, list[h].inputOffset, which, nIn) ? th.windowInCall : th.windowInHistory) = true;
+			}
+			th.anyHop = true;
+			if (!(f & HOP_NEW_SPECTRUM)) th.reusedSpectrum = true; // (a hop that re-uses the spectrum before it: the continuous wavefront asks for a new one per hop)
+			if (f & HOP_MAPPED) th.mapped = true;
+			if (f & HOP_FORMANTS) { th.formants = true; if ((f & HOP_PREANALYSED) || params[s].formantBaseFreq <= 0) th.estimatesBase = true; } // (a stream that estimates its base frequency, :929-966)
+			if (f & HOP_RANDOM_TF) th.randomTimeFactor = true;
+		}
+		info[subS + sl] = lastNewLocal;
+		if (cnt > 0) noteLastHop(s, (sub*nTiles + t) & 1, cnt - 1, list[h1 - 1].flags);
+		int &span = maxSpanV[(size_t)sub*nTiles + t];
+		span = std::max(span, ed.nHi - ed.nLo);
 	}
 }
 
@@ -1242,276 +1448,55 @@ void Batch::process(const float *in, long long inSS, long long inCS, const int *
 	SMST_HIP(hipMemcpyAsync(cs.hEnergy, dEnergy, (size_t)S*kEnergyParts*sizeof(float), hipMemcpyDeviceToHost, stGate));
 	{ const auto t = std::chrono::steady_clock::now(); SMST_HIP(hipStreamSynchronize(stGate)); hostTimes.waitGateMs += msSince(t); }
 
-	// K0, pass 1: silence gate (signalsmith-stretch.h:231-278) and the number of hops each stream fires in this call
-	int *passFlags = cs.hFlags;
-	int *clearBits = cs.hResetBits; // per CALL (pinned + its own device copy): a shared buffer could be overwritten by the next call's upload before this call's kResetStreams has run
-	bool anyPass = false, anyClear = false;
-	int maxHops = 0;
-	pendList.clear();
-	for (int s = 0; s < S; ++s) {
-		passFlags[s] = 0;
-		hopFirst[s] = 0;
-		hopCount[s] = 0;
-		leavesPendingV[s] = 0;
-		ridesV[s] = 0;
-		clearBits[s] = 0;
-		if (active && !active[s]) continue;
-		lastHop[s].slot = -1; // smst_batch_debug_get_map reports the newest hop of THIS call only
-		StreamSched &sc = sched[s];
-		float e = 0;
-		for (int p = 0; p < kEnergyParts; ++p) e += cs.hEnergy[(size_t)s*kEnergyParts + p];
-		if (e < kNoiseFloor) { // :240-278
-			if (sc.silenceCounter >= size_t(2*B)) {
-				if (sc.silenceFirst) {
-					sc.silenceFirst = false;
-					sc.seed = seedAfterDroppedBlock(s); // ... which drops the block in flight, with the draws it has made
-					sc.samplesSinceLast = SIZE_MAX; // blockProcess = {}
-					pend[s] = PendingBlock();
-					clearBits[s] = 2 | 4 | 8;       // Band.input / .prevInput / .output := 0
-					anyClear = true;
-				}
-				passFlags[s] = 1;
-				anyPass = true;
-				continue; // history is still updated below (copyInput, :270)
-			} else {
-				sc.silenceCounter += size_t(nIn[s]);
-			}
-		} else {
-			sc.silenceCounter = 0;
-			sc.silenceFirst = true;
-		}
-		const int first = (sc.samplesSinceLast >= size_t(I)) ? 0 : int(size_t(I) - sc.samplesSinceLast);
-		hopFirst[s] = first;
-		const int starts = (nOut[s] > first) ? (nOut[s] - first + I - 1)/I : 0; // blocks that begin in this call (:281)
-		lastStarts[s] = starts;
-		if (split) {
-			// split computation: a block is finished when its interval is (:321-325).  The block in flight from earlier calls runs now if
-			// this call reaches the end of its interval; the last block that begins here stays in flight unless its interval ends here too
-			// (a plain one becomes the stream's first hop of this call; one that a flush() interrupted or whose steps saw different parameters runs by itself first)
-			ridesV[s] = 0;
-			if (pend[s].valid && nOut[s] >= first) {
-				const PendingBlock &pb = pend[s];
-				if (pb.startBin > 0 || pb.zeroPrevAfter || pb.frozenPeaks || pb.frozenForm0 || pb.frozenForm2) pendList.push_back(s);
-				else ridesV[s] = 1;
-			}
-			const int complete = (nOut[s] > first) ? (nOut[s] - first)/I : 0;
-			leavesPendingV[s] = starts > complete;
-			hopCount[s] = complete + ridesV[s];
-		} else {
-			hopCount[s] = starts;
-		}
-		maxHops = std::max(maxHops, hopCount[s]);
-	}
-	if (anyClear) { // asynchronous: the masks travel on `st`, ahead of the launch that reads them
-		SMST_HIP(hipMemcpyAsync(cs.resetBits, clearBits, S*sizeof(int), hipMemcpyHostToDevice, st));
+	CallPlan c{&cs, active}; // (everything else zero)
+	gateAndCount(c);
+	if (c.anyClear) { // asynchronous: the masks travel on `st`, ahead of the launch that reads them
+		SMST_HIP(hipMemcpyAsync(cs.resetBits, cs.hResetBits, S*sizeof(int), hipMemcpyHostToDevice, st));
 		launchResetStreams(d, cs.resetBits, 0, dSeedWp, st);
 	}
 	if (!pendList.empty()) runPendingBlocks(nullptr);
-	const int nTiles = std::max(1, (maxHops + T - 1)/T);
+	const int maxHops = c.maxHops, nTiles = std::max(1, (maxHops + T - 1)/T);
 	// One row of T hop descriptors per stream and tile -- except in the real-time calling pattern, where no stream fires more than one hop per
 	// call: the single-hop kernels index hop 0 only, so a row is ONE descriptor (4096 streams: 131 KB to clear and upload per 128-frame
 	// quantum instead of 8.4 MB -- a third of the quantum's cost).  (The wavefront kernels load a row of 64 blindly: they keep the full rows.)
 	const bool compactHops = maxHops <= 1 && singleHopSupported(d) && !noSingleHop && fusedSupported(d) && !noFuse;
-	const int hopStride = compactHops ? 1 : nTiles*T;
+	c.nTiles = nTiles;
+	c.hopStride = compactHops ? 1 : nTiles*T;
 	const int nSub = (S + subS - 1)/subS;
-
-	// per-call tables: pinned staging and device copies grow only when a call needs more hops than any earlier call -- and
-	// then BOTH sets grow, so that the call after this one (which uses the other set) does not allocate either.  The other
-	// set's old tables may still be read by the previous call's kernels: they are retired and freed when that set is next used.
-	for (void *q : cs.retiredDevice) devFree(q);
-	for (void *q : cs.retiredPinned) pinnedFree(q);
-	cs.retiredDevice.clear();
-	cs.retiredPinned.clear();
-	const size_t needHops = (size_t)S*hopStride, needEmit = (size_t)S*nTiles, needInfo = (size_t)nSub*nTiles*2*subS;
-	for (int which = 0; which < 2; ++which) {
-		CallSet &t = callSets[which ? callCur ^ 1 : callCur];
-		const bool mine = which == 0;
-		auto retire = [&](void *dev, void *host) {
-			if (mine) { devFree(dev); pinnedFree(host); }
-			else { if (dev) t.retiredDevice.push_back(dev); if (host) t.retiredPinned.push_back(host); }
-		};
-		if (needHops > t.hopsCap) {
-			retire(t.hops, t.hHops);
-			t.hopsCap = needHops + needHops/4;
-			t.hops = devAlloc<HopDesc>(t.hopsCap);
-			t.hHops = pinnedAlloc<HopDesc>(t.hopsCap);
-		}
-		if (needEmit > t.emitCap) {
-			retire(t.emit, t.hEmit);
-			t.emitCap = needEmit + needEmit/4;
-			t.emit = devAlloc<EmitDesc>(t.emitCap);
-			t.hEmit = pinnedAlloc<EmitDesc>(t.emitCap);
-		}
-		if (needInfo > t.tileInfoCap) {
-			retire(t.tileInfo, t.hTileInfo);
-			t.tileInfoCap = needInfo + needInfo/4;
-			t.tileInfo = devAlloc<int>(t.tileInfoCap);
-			t.hTileInfo = pinnedAlloc<int>(t.tileInfoCap);
-		}
-	}
+	c.needHops = (size_t)S*c.hopStride; c.needEmit = (size_t)S*nTiles; c.needInfo = (size_t)nSub*nTiles*2*subS;
+	growCallTables(c);
 	dHops = cs.hops; dEmit = cs.emit; dTileInfo = cs.tileInfo;
-	HopDesc *hopsAll = cs.hHops;
-	EmitDesc *emitAll = cs.hEmit;
-	int *tileInfo = cs.hTileInfo; // layout: [sub][tile][2][subS] (nHops, lastNewHop)
-	std::memset(hopsAll, 0, needHops*sizeof(HopDesc));
-	std::memset(tileInfo, 0, needInfo*sizeof(int));
+	std::memset(cs.hHops, 0, c.needHops*sizeof(HopDesc));
+	std::memset(cs.hTileInfo, 0, c.needInfo*sizeof(int));
 	ensureSize(maxSpanV, (size_t)nSub*nTiles, allocEvents);
-	ensureSize(tileHasV, (size_t)nSub*nTiles*kTileHasStride, allocEvents); // (smst_types.h: kTileHasStride)
+	ensureSize(tileHasV, (size_t)nSub*nTiles, allocEvents);
 	std::fill(maxSpanV.begin(), maxSpanV.end(), 0);
-	std::fill(tileHasV.begin(), tileHasV.end(), 0);
-
-	// K0, pass 2: block scheduler, exactly as signalsmith-stretch.h:280-319 does it per stream, straight into the tables
-	bool anyPendAnalysis = false, pendInCall = false, pendLate = false;
+	std::fill(tileHasV.begin(), tileHasV.end(), TileSummary{});
 	for (int s = 0; s < S; ++s) {
-		const int sub = s/subS, sl = s%subS;
-		HopDesc *list = hopsAll + (size_t)s*hopStride;
-		const int nh = hopCount[s];
-		const int rides = ridesV[s]; // split computation: the block in flight from an earlier call is this call's hop 0 ...
-		const int nStart = nh + (leavesPendingV[s] ? 1 : 0); // ... and the last block that begins here may stay in flight
-		if (split) cs.hPendHops[s] = HopDesc{};
-		int lastNew = -1;
-		if (rides) {
-			const PendingBlock &pb = pend[s];
-			HopDesc &hd = list[0];
-			hd.flags = pb.flags | HOP_PREANALYSED;
-			hd.timeFactor = pb.timeFactor;
-			hd.seed = pb.seed;
-			hd.outPos = -int(sched[s].samplesSinceLast); // it began that many samples ago: its frame lands where its interval ends (:292-296)
-			const bool nw = (pb.flags & HOP_NEW_SPECTRUM) != 0;
-			hd.inSrc = nw ? 0 : SRC_STATE;
-			hd.prevSrc = (nw && (pb.flags & HOP_REANALYSE_PREV)) ? SRC_REANALYSED : SRC_STATE;
-			if (nw) lastNew = 0;
-			if (pb.flags & HOP_RANDOM_TF) sched[s].seed = unsigned((unsigned long long)sched[s].seed*lcgHopJump % 2147483647ull); // its draws happen now
-			pend[s] = PendingBlock();
-		}
-		if (nStart > rides) {
-			StreamSched &sc = sched[s];
-			const StreamParams &prm = params[s];
-			const bool mapped = prm.hasCustomMap || prm.freqMultiplier != 1; // :300
-			const bool formants = prm.formantMultiplier != 1 || (prm.formantCompensation && mapped); // :310
-			int o = hopFirst[s];
-			for (int j = rides; j < nStart; ++j, o += I) {
-				HopDesc inFlight{};
-				HopDesc &hd = (j < nh) ? list[j] : inFlight;
-				int inputOffset = int(std::round(o*float(nIn[s])/nOut[s])); // :288 (fp32 on purpose)
-				int inputInterval = inputOffset - sc.prevInputOffset;
-				sc.prevInputOffset = inputOffset;
-				hd.inputOffset = inputOffset;
-				hd.outPos = o;
-				unsigned flags = HOP_ACTIVE;
-				const bool newSpectrum = sc.didSeek || inputInterval > 0; // :299
-				bool reanalyse = false;
-				if (newSpectrum) {
-					flags |= HOP_NEW_SPECTRUM;
-					reanalyse = sc.didSeek || std::abs(inputInterval - I) > 1; // :303
-					if (reanalyse) flags |= HOP_REANALYSE_PREV;
-				}
-				if (mapped) flags |= HOP_MAPPED;
-				if (formants) flags |= HOP_FORMANTS;
-				float tf = sc.didSeek ? sc.seekTimeFactor : float(I)/std::max<float>(1, float(inputInterval)); // :312
-				sc.didSeek = false;
-				tf = std::max<float>(tf, 1/kMaxCleanStretch); // :638
-				if (tf > kMaxCleanStretch) flags |= HOP_RANDOM_TF; // :639
-				hd.timeFactor = tf;
-				hd.flags = flags;
-				lastSteps[s] = stepLayout(flags).steps;
-				hd.seed = sc.seed; // the engine's state before this hop's draws
-				if ((flags & HOP_RANDOM_TF) && j < nh) sc.seed = unsigned((unsigned long long)sc.seed*lcgHopJump % 2147483647ull); // 2M - 2 draws later (a block left in flight draws when it runs: seedAfterDroppedBlock)
-				if (j == nh) {
-					// in flight at the end of the call: analysed now, from the input as it stands (:293 stashes it), into the pending buffers;
-					// everything else when its interval is complete -- or when a flush() needs to know how far it has come
-					PendingBlock &pb = pend[s];
-					pb = PendingBlock();
-					pb.valid = true;
-					pb.flags = flags;
-					pb.timeFactor = tf;
-					pb.seed = hd.seed;
-					HopDesc &ph = cs.hPendHops[s];
-					ph.inputOffset = inputOffset;
-					ph.flags = flags & (HOP_ACTIVE | HOP_NEW_SPECTRUM | HOP_REANALYSE_PREV);
-					if (newSpectrum) {
-						anyPendAnalysis = true;
-						for (int which = 0; which < (reanalyse ? 2 : 1); ++which) (analysisWindowInCall(d.B, d.M, d.I, inputOffset, which, nIn[s]) ? pendInCall : pendLate) = true;
-					}
-					continue;
-				}
-				const int tile = j/T;
-				const bool lastInTile = lastNew >= 0 && lastNew/T == tile;
-				hd.inSrc = newSpectrum ? j%T : (lastInTile ? lastNew%T : SRC_STATE);
-				if (newSpectrum && reanalyse) hd.prevSrc = SRC_REANALYSED;
-				else hd.prevSrc = lastInTile ? lastNew%T : SRC_STATE;
-				if (newSpectrum) lastNew = j;
-			}
-			sc.samplesSinceLast = size_t(nOut[s] - (o - I));
-		} else if (!passFlags[s] && !(active && !active[s])) {
-			StreamSched &sc = sched[s];
-			if (sc.samplesSinceLast != SIZE_MAX) sc.samplesSinceLast += size_t(nOut[s]);
-		}
-		if (!(active && !active[s]) && !passFlags[s]) sched[s].prevInputOffset -= nIn[s]; // :419
-		for (int t = 0; t < nTiles; ++t) {
-			const int h0 = t*T, h1 = std::min(nh, h0 + T);
-			const int cnt = std::max(0, h1 - h0);
-			EmitDesc ed{};
-			const int total = passFlags[s] ? 0 : nOut[s];
-			if (t == 0) ed.nLo = 0; else ed.nLo = (h0 < nh) ? list[h0].outPos : total;
-			ed.nHi = (h1 < nh && cnt > 0) ? list[h1].outPos : total;
-			if (cnt == 0 && t > 0) ed.nLo = ed.nHi = total;
-			ed.firstHopPos = cnt > 0 ? list[h0].outPos : 0;
-			ed.hopCount = cnt;
-			emitAll[(size_t)s*nTiles + t] = ed;
-			int *info = tileInfo + ((size_t)(sub*nTiles + t)*2)*subS;
-			info[sl] = cnt;
-			int lastNewLocal = -1;
-			unsigned char *th = tileHasV.data() + (size_t)(sub*nTiles + t)*kTileHasStride;
-			for (int h = h0; h < h1; ++h) {
-				const unsigned f = list[h].flags;
-				if (f & HOP_PREANALYSED) th[8] = 1;
-				if ((f & HOP_NEW_SPECTRUM) && (f & HOP_PREANALYSED)) lastNewLocal = h - h0;
-				if ((f & HOP_NEW_SPECTRUM) && !(f & HOP_PREANALYSED)) {
-					lastNewLocal = h - h0; th[3] = 1;
-					// analysis frames whose window lies in this call's input ([5], taken by kAnalyseTeams) / reaches into the history ([6])
-					for (int which = 0; which < ((f & HOP_REANALYSE_PREV) ? 2 : 1); ++which) th[analysisWindowInCall(d.B, d.M, d.I, list[h].inputOffset, which, nIn[s]) ? 5 : 6] = 1;
-				}
-				th[0] = 1;
-				if (!(f & HOP_NEW_SPECTRUM)) th[9] = 1; // (a hop that re-uses the spectrum before it: the continuous wavefront asks for a new one per hop)
-				if (f & HOP_MAPPED) th[1] = 1;
-				if (f & HOP_FORMANTS) { th[2] = 1; if ((f & HOP_PREANALYSED) || params[s].formantBaseFreq <= 0) th[10] = 1; } // [10]: a stream that estimates its base frequency (:929-966)
-				if (f & HOP_RANDOM_TF) th[4] = 1;
-			}
-			info[subS + sl] = lastNewLocal;
-			if (cnt > 0) {
-				LastHop &lh = lastHop[s];
-				lh.slot = (sub*nTiles + t) & 1;
-				lh.local = cnt - 1;
-				lh.subLocal = sl;
-				lh.mapped = (list[h1 - 1].flags & HOP_MAPPED) != 0;
-				lh.formants = (list[h1 - 1].flags & HOP_FORMANTS) != 0;
-			}
-			int &span = maxSpanV[(size_t)sub*nTiles + t];
-			span = std::max(span, ed.nHi - ed.nLo);
-		}
+		scheduleStream(c, s);
+		summariseStreamTiles(c, s);
 	}
-	SMST_HIP(hipMemcpyAsync(dHops, hopsAll, needHops*sizeof(HopDesc), hipMemcpyHostToDevice, stGate));
-	SMST_HIP(hipMemcpyAsync(dEmit, emitAll, needEmit*sizeof(EmitDesc), hipMemcpyHostToDevice, stGate));
-	SMST_HIP(hipMemcpyAsync(dTileInfo, tileInfo, needInfo*sizeof(int), hipMemcpyHostToDevice, stGate));
-	if (anyPass) SMST_HIP(hipMemcpyAsync(dFlags, passFlags, S*sizeof(int), hipMemcpyHostToDevice, stGate));
-	if (anyPendAnalysis) SMST_HIP(hipMemcpyAsync(cs.pendHops, cs.hPendHops, S*sizeof(HopDesc), hipMemcpyHostToDevice, stGate));
+	SMST_HIP(hipMemcpyAsync(dHops, cs.hHops, c.needHops*sizeof(HopDesc), hipMemcpyHostToDevice, stGate));
+	SMST_HIP(hipMemcpyAsync(dEmit, cs.hEmit, c.needEmit*sizeof(EmitDesc), hipMemcpyHostToDevice, stGate));
+	SMST_HIP(hipMemcpyAsync(dTileInfo, cs.hTileInfo, c.needInfo*sizeof(int), hipMemcpyHostToDevice, stGate));
+	if (c.anyPass) SMST_HIP(hipMemcpyAsync(dFlags, cs.hFlags, S*sizeof(int), hipMemcpyHostToDevice, stGate));
+	if (c.anyPendAnalysis) SMST_HIP(hipMemcpyAsync(cs.pendHops, cs.hPendHops, S*sizeof(HopDesc), hipMemcpyHostToDevice, stGate));
 	// the kernels below are ordered after the uploads by an event, not by the host
 	SMST_HIP(hipEventRecord(cs.tables, stGate));
 	SMST_HIP(hipStreamWaitEvent(st, cs.tables, 0));
 
 	d.hops = dHops;
 	d.emit = dEmit;
-	d.hopStride = hopStride;
+	d.hopStride = c.hopStride;
 	d.emitStride = nTiles;
 
 	// no stream fires a hop (most quanta of a real-time host): the output is the front of the carried sums, and -- while the rows have room --
 	// what is left of them stays in place (kEmitCarried)
 	bool carriedOnly = maxHops == 0 && carriedEmit;
-	for (int s = 0; s < S && carriedOnly; ++s) carriedOnly = carryBase[s] + (passFlags[s] ? 0 : nOut[s]) + d.carryLen <= d.carryPitch;
-	if (carriedOnly) for (int s = 0; s < S; ++s) carryBase[s] += passFlags[s] ? 0 : nOut[s];
+	for (int s = 0; s < S && carriedOnly; ++s) carriedOnly = carryBase[s] + (cs.hFlags[s] ? 0 : nOut[s]) + d.carryLen <= d.carryPitch;
+	if (carriedOnly) for (int s = 0; s < S; ++s) carryBase[s] += cs.hFlags[s] ? 0 : nOut[s];
 	runTiles(TileRun{&io, nTiles, maxHops, tileHasV.data(), maxSpanV.data(), dTileInfo, false, nullptr, carriedOnly});
-	if (anyPendAnalysis) timed(timings.analyseMs, [&] {
+	if (c.anyPendAnalysis) timed(timings.analyseMs, [&] {
 		// the blocks left in flight: their spectra (Band.input and, where :303 asks for it, the re-analysed Band.prevInput) into the pending
 		// buffers, laid out as a one-hop tile over ALL streams
 		DevBatch dp = d;
@@ -1520,11 +1505,11 @@ void Batch::process(const float *in, long long inSS, long long inCS, const int *
 		dp.T = 1;
 		dp.Xcur = dPendIn;
 		dp.Xprev = dPendPrev;
-		launchAnalyse(dp, io, 0, S, 0, 1, pendInCall, pendLate, st);
+		launchAnalyse(dp, io, 0, S, 0, 1, c.pendInCall, c.pendLate, st);
 		if (profiling) ++timings.analyseLaunches;
 	});
 	timed(timings.otherMs, [&] {
-		if (anyPass) launchPassThrough(d, io, dFlags, maxOut, st);
+		if (c.anyPass) launchPassThrough(d, io, dFlags, maxOut, st);
 		// the input history slides (kHistory): the host follows each stream's window to size the launch
 		int span = 0;
 		for (int s = 0; s < S; ++s) {
@@ -1589,6 +1574,11 @@ void Batch::seek(const float *in, long long inSS, long long inCS, const int *inS
 }
 
 // ---- flush ------------------------------------------------------------------------------------------------
+// How far the REAL output ring, which the reference's flush() / outputSeek() touch, is ahead of the stashed one that process() emits from (split computation: what is left of the interval)
+int Batch::aheadOffset(int s) const {
+	const size_t since = sched[s].samplesSinceLast;
+	return (split && since != SIZE_MAX && since < size_t(I)) ? int(size_t(I) - since) : 0;
+}
 void Batch::flush(float *out, long long outSS, long long outCS, const int *outSamples, const float *rates, const unsigned char *active) {
 	SMST_HIP(hipSetDevice(dev));
 	std::vector<int> blockOut(S, 0), blockIn(S, 0), tail(S, -1), tailOff(S, 0), outOff(S, 0);
@@ -1654,12 +1644,7 @@ void Batch::flush(float *out, long long outSS, long long outCS, const int *outSa
 		}
 	}
 	if (!pendList.empty()) runPendingBlocks(synthChannels.data());
-	for (int s = 0; s < S; ++s) {
-		if (!on[s]) continue;
-		const StreamSched &sc = sched[s];
-		// where the L1 output ring the reference reads here sits relative to our carry (split: the "ahead" ring)
-		tailOff[s] = (split && sc.samplesSinceLast != SIZE_MAX && sc.samplesSinceLast < size_t(I)) ? int(size_t(I) - sc.samplesSinceLast) : 0;
-	}
+	for (int s = 0; s < S; ++s) if (on[s]) tailOff[s] = aheadOffset(s);
 	SMST_HIP(hipMemcpyAsync(dOutSamples, tail.data(), S*sizeof(int), hipMemcpyHostToDevice, st));
 	SMST_HIP(hipMemcpyAsync(dAux0, tailOff.data(), S*sizeof(int), hipMemcpyHostToDevice, st));
 	SMST_HIP(hipMemcpyAsync(dAux1, outOff.data(), S*sizeof(int), hipMemcpyHostToDevice, st));
@@ -1669,7 +1654,7 @@ void Batch::flush(float *out, long long outSS, long long outCS, const int *outSa
 	launchFlushTail(d, io, dAux0, dAux1, st);
 	// stft.reset(0.1) + zero prevInput/output (:456-463).  Split computation: the samples up to the end of the interval still come from
 	// the stashed ring (:407-415), which the reset does not touch -- the fresh ring begins behind them
-	for (int s = 0; s < S; ++s) { resetBitsV[s] = on[s] ? (1 | 4 | 8) : 0; keepV[s] = on[s] ? tailOff[s] : 0; if (on[s]) lastHop[s] = LastHop(); }
+	for (int s = 0; s < S; ++s) { resetBitsV[s] = on[s] ? (RESET_STFT | RESET_PREV | RESET_OUTPUT) : 0; keepV[s] = on[s] ? tailOff[s] : 0; if (on[s]) lastHop[s] = LastHop(); }
 	resetStreams(resetBitsV.data(), 0, split ? keepV.data() : nullptr);
 	SMST_HIP(hipGetLastError());
 }
@@ -1697,8 +1682,6 @@ void Batch::outputSeek(const float *in, long long inSS, long long inCS, const in
 	}
 	// offset input per stream: seekSamples differ per stream, so pass per-stream start through a shifted base when uniform,
 	// otherwise run stream groups with equal offsets
-	std::vector<int> order(S);
-	for (int s = 0; s < S; ++s) order[s] = s;
 	std::vector<unsigned char> mask(S);
 	std::vector<int> done(S, 0);
 	for (int s0 = 0; s0 < S; ++s0) {
@@ -1709,10 +1692,7 @@ void Batch::outputSeek(const float *in, long long inSS, long long inCS, const in
 	}
 	// "put the thing down, flip it and reverse it" (:198-203): negate, reverse, add into the output ring
 	std::vector<int> off(S, 0);
-	for (int s = 0; s < S; ++s) {
-		const StreamSched &sc = sched[s];
-		off[s] = (split && sc.samplesSinceLast != SIZE_MAX && sc.samplesSinceLast < size_t(I)) ? int(size_t(I) - sc.samplesSinceLast) : 0;
-	}
+	for (int s = 0; s < S; ++s) off[s] = aheadOffset(s);
 	SMST_HIP(hipMemcpyAsync(dAux0, off.data(), S*sizeof(int), hipMemcpyHostToDevice, st));
 	SMST_HIP(hipStreamSynchronize(st));
 	settleCarry();

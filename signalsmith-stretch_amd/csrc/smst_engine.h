@@ -168,14 +168,17 @@ private:
 	int subS = 0;
 	// per-call host scratch, kept between calls (no heap traffic in steady state); growth events are counted
 	std::vector<int> hopFirst, hopCount, maxSpanV;
-	std::vector<unsigned char> tileHasV, passV, leavesPendingV, ridesV;
+	std::vector<TileSummary> tileHasV, pendTileHas; // [sub][tile] of a call, [sub] of a run of blocks in flight
+	std::vector<unsigned char> leavesPendingV, ridesV;
 	long allocEvents = 0; // device allocations + pinned allocations + host table growth since construction
 	size_t wsBytes = 0;
 	DevBatch d{};
 	std::vector<StreamSched> sched;
 	unsigned lcgHopJump = 1; // 16807^(2M - 2) mod (2^31 - 1): what one randomised hop advances a stream's engine by
+	unsigned advanceOneHop(unsigned seed) const;
 	struct LastHop { int slot = -1, local = -1, subLocal = 0; bool mapped = false, formants = false; };
 	std::vector<LastHop> lastHop; // where each stream's newest hop sits in the tile workspaces (debugGetMap)
+	void noteLastHop(int s, int slot, int local, unsigned flags);
 	std::vector<StreamParams> params;
 	bool paramsDirty = true;
 	// ---- split computation: the block in flight (see PendingBlock) ----
@@ -193,19 +196,36 @@ private:
 	int pendCur = 0;
 	int *dZeroCounts = nullptr; // [S] zeros: the sample counts of a run that consumes and emits nothing
 	std::vector<int> pendList;  // streams of the run being prepared
-	std::vector<unsigned char> pendTileHas;
 	std::vector<int> pendMaxSpan, keepV;
 	StepLayout stepLayout(unsigned flags) const;
 	size_t stepsExecuted(size_t steps, size_t samplesIntoInterval) const;
 	void freezePendingParams(int s);   // before a setter changes params[s]
 	unsigned seedAfterDroppedBlock(int s) const; // the random engine once the block in flight is dropped (reset / silence / configure)
+	void pendingHop(int s, HopDesc &hd) const; // the HopDesc of stream s's block in flight
+	int aheadOffset(int s) const;
 	void runPendingBlocks(const int *synthChannels); // runs the blocks of `pendList` (a tile of one hop per stream; no input, no output samples)
-	struct TileRun { const IoArgs *io; int nTiles, maxHops; const unsigned char *tileHas; const int *maxSpan; const int *dTileInfo; bool pendingRun; const int *dSynthChannels; bool carriedOnly; };
+	struct TileRun { const IoArgs *io; int nTiles, maxHops; const TileSummary *tileHas; const int *maxSpan; const int *dTileInfo; bool pendingRun; const int *dSynthChannels; bool carriedOnly; };
 	void settleCarry();
 	void runTiles(const TileRun &run);
+	struct TileStreams { bool serial; hipStream_t sF, sC, sS; }; // a segment's streams: feed-forward, recurrence, synthesis + emission (all `st` when serial)
+	TileStreams forkTileStreams(const TileRun &run);
+	void joinTileStreams(const TileStreams &ts, int first, int passes, int depth);
+	template <typename F> void timedRecurrence(const TileStreams &ts, F &&launch);
+	DevBatch tileView(const TileBuffers &w, int carryCur, const int *tileInfo) const;
 	void runTilesRange(const TileRun &run, int tile0, int tile1, int carryFirst); // tile by tile
 	bool continuousApplies(const TileRun &run, int tile) const;
 	void runTilesContinuous(const TileRun &run, int tile0, int tile1, int carryFirst); // the recurrence as ONE wavefront through the tiles [tile0, tile1) (kVocoderCont)
+	struct CallPlan { // what the stages of one process() call hand to each other
+		CallSet *cs; const unsigned char *active; // process(): the call's table set, the caller's stream mask (may be null)
+		int maxHops; bool anyPass, anyClear;      // gateAndCount(): most hops of any stream; a stream passed through / cleared by the silence gate
+		int nTiles, hopStride; size_t needHops, needEmit, needInfo; // process(): tiles, descriptors per stream row, elements of the hops / emit / tileInfo tables
+		bool anyPendAnalysis, pendInCall, pendLate; // scheduleStream(): a block left in flight needs analysing; its windows lie in the call / reach into the history
+	};
+	void gateAndCount(CallPlan &c);
+	template <typename T> void growCallTable(CallSet &t, bool mine, T *&dev, T *&host, size_t &cap, size_t need);
+	void growCallTables(const CallPlan &c);
+	void scheduleStream(CallPlan &c, int s);
+	void summariseStreamTiles(const CallPlan &c, int s);
 	bool profiling = false, liveTiming = false;
 	std::vector<std::pair<hipEvent_t, hipEvent_t>> liveEvents; // pairs recorded since the last takeTimings()
 	std::vector<std::pair<hipEvent_t, hipEvent_t>> livePool;   // every pair ever created; [0, liveEvents.size()) are in use

@@ -81,15 +81,15 @@ __global__ __launch_bounds__(256) void kPassThrough(DevBatch d, IoArgs io, const
 }
 
 // reset() / flush() / first silent block (signalsmith-stretch.h:49-60, :456-463, :244-251) for the selected streams in ONE
-// launch.  Per-stream bit mask: 1 = stft.reset(0.1) (overlap-add sums and input history cleared, window products re-seeded,
-// both halves of the double buffers), 2 / 4 / 8 = clear Band.input / .prevInput / .output.
+// launch.  Per-stream bit mask (smst_types.h): RESET_STFT = stft.reset(0.1) (overlap-add sums and input history cleared, window products
+// re-seeded, both halves of the double buffers), RESET_INPUT / RESET_PREV / RESET_OUTPUT = clear Band.input / .prevInput / .output.
 __global__ __launch_bounds__(256) void kResetStreams(DevBatch d, const int *__restrict__ flags, int allBits, const float *__restrict__ seedWp, const int *__restrict__ keep) {
 	const int sg = blockIdx.y;
 	const int bits = flags ? flags[sg] : allBits;
 	if (!bits) return;
 	const int i = blockIdx.x*blockDim.x + threadIdx.x;
 	const int CL = d.carryLen, HL = d.histLen, M = d.M, C = d.C;
-	if (bits & 1) {
+	if (bits & RESET_STFT) {
 		// split computation, between two interval boundaries: the samples up to the end of the interval are read from the stashed ring, which
 		// stft.reset() does not touch (:407-415); the real ring -- re-seeded -- begins behind them
 		// (the engine settles the carry before a reset that keeps samples: the window it reads from begins at the front of its rows, so no
@@ -114,13 +114,13 @@ __global__ __launch_bounds__(256) void kResetStreams(DevBatch d, const int *__re
 		}
 		if (i == 0) d.histBase[0][sg] = d.histBase[1][sg] = 0;
 	}
-	if (i < M && (bits & 14)) {
+	if (i < M && (bits & (RESET_INPUT | RESET_PREV | RESET_OUTPUT))) {
 		const float2 zero = make_float2(0.f, 0.f);
 		for (int c = 0; c < C; ++c) {
 			const size_t o = stateRow(d, sg, c) + i;
-			if (bits & 2) d.stInput[o] = zero;
-			if (bits & 4) d.stPrev[o] = zero;
-			if (bits & 8) storeCarriedOutput(d, o, zero);
+			if (bits & RESET_INPUT) d.stInput[o] = zero;
+			if (bits & RESET_PREV) d.stPrev[o] = zero;
+			if (bits & RESET_OUTPUT) storeCarriedOutput(d, o, zero);
 		}
 	}
 }

@@ -11,8 +11,30 @@ constexpr int kMaxFusedChannels = 8;
 // floats of one record of the bin recurrence (smst_recurrence.h: computeRecord / recordChannelFields): four twists, the maximum channel, then per-channel fields
 constexpr int recordFloats(int channels) { return channels <= 2 ? 9 + 3*channels : 12 + 2*channels; }
 constexpr int kMaxFftPasses = 12;
-constexpr int kTileHasStride = 12; // per-tile summary bytes of the host scheduler: any hop / mapped / formants / new spectrum / random time factor / analysis window in the call / reaching into the history / a start bin / a pre-analysed hop / a hop without a new spectrum / a formant hop that estimates its base frequency
 constexpr int kEnergyParts = 16; // partial sums per stream in the silence-gate reduction
+
+// What the hops of one tile of one sub-batch need, OR-ed over its streams.  Written by the host scheduler, read by the tile pipelines; host only.
+struct TileSummary {
+	bool anyHop;           // some stream fires a hop in this tile
+	bool mapped;           // a hop with a frequency map (HOP_MAPPED)
+	bool formants;         // a hop with formant processing (HOP_FORMANTS)
+	bool newSpectrum;      // a hop whose spectrum is analysed in this run (HOP_NEW_SPECTRUM and not pre-analysed)
+	bool randomTimeFactor; // a hop that draws its time factors (HOP_RANDOM_TF)
+	bool windowInCall;     // an analysis window that lies in the call's input (taken by kAnalyseTeams)
+	bool windowInHistory;  // an analysis window that reaches into the history
+	bool startBin;         // a hop with HopDesc.startBin > 0
+	bool preAnalysed;      // a hop that began in an earlier call (HOP_PREANALYSED): its spectra wait in the pending buffers
+	bool reusedSpectrum;   // a hop without a new spectrum: it re-uses the one before it
+	bool estimatesBase;    // a formant hop that estimates its base frequency (:929-966)
+	bool plain() const { return !(mapped || formants); }
+	// what the continuous wavefront (kVocoderCont) asks of a tile: plain, bounded, whole-line -- what launchVocoder sends to the aligned
+	// form -- with a new spectrum in every hop (the rows of a later tile then never read the carried feed-forward state)
+	bool continuousCapable() const { return anyHop && plain() && !randomTimeFactor && !startBin && !preAnalysed && !reusedSpectrum; }
+};
+
+// kResetStreams' per-stream mask: stft.reset(0.1) (overlap-add sums and input history cleared, window products re-seeded, both halves of
+// the double buffers); clear Band.input / .prevInput / .output
+enum : int { RESET_STFT = 1, RESET_INPUT = 2, RESET_PREV = 4, RESET_OUTPUT = 8 };
 
 // Hop flags (reference: signalsmith-stretch.h:299-313)
 enum : unsigned {

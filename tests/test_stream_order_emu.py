@@ -461,7 +461,7 @@ def _device_memory(lib, continuous):
     out.  The output is read on the consumer only, never after smst_batch_synchronize."""
     pkg = package()
     S, Cn, I = 2, 2, (I_ALIGNED if continuous else 128)
-    x = _inputs(S, Cn, 400*I)
+    x = _inputs(S, Cn, 400*I + 70)  # (130 + 70 + 200) I + 70: the longest input of each call below -- one sample less and the last upload reads past `x`
     b = pkg.StretchBatch(S, Cn, lib=lib, **(ALIGNED if continuous else dict(block=512, interval=128)))
     prod, cons = lib.smst_emu_stream_create(), lib.smst_emu_stream_create()
     keep, results, pos = [], [], 0
