@@ -199,8 +199,8 @@ __device__ __forceinline__ void feedPredictionRows(const DevBatch &d, const HopD
 	}
 }
 
-// previous-hop part of the prediction,  prevOut[b+1]*Cc + prevOut[b+L]*Dc : THE definition every recurrence kernel uses (first
-// operation of its accumulation), and what FOLD0 records carry in Cc's place
+// previous-hop part of the prediction,  prevOut[b+1]*Cc + prevOut[b+L]*Dc : the first operation of recurrenceOutputs' accumulation, and
+// what FOLD0 records carry in Cc's place (foldCarriedTaps, plainRecord)
 __device__ __forceinline__ float2 prevHopTerms(float2 p1, float2 Cc, float2 pL, float2 Dc) { return cfma(pL, Dc, cmul(p1, Cc)); }
 __device__ __forceinline__ void foldCarriedTaps(const CarriedOutput &prev, int mc, int b, int M, int L, float2 &Cc, float2 &Dc) {
 	// taps beyond the last bin multiply coefficients that are already zero (:765,:776): any finite value does
@@ -459,12 +459,82 @@ __device__ __forceinline__ float2 makeOutputFb(float2 phase, float2 fallback, fl
 	return (n <= 1e-15f) ? fallback : o;
 }
 
+// The record's channel word (float 8): the maximum channel in its low byte; 3 and more channels: bits 8.. flag the channels whose lock falls
+// back to their own input (recordChannelFields).  Clamped for the one reader whose records can be memory nobody wrote (kChain: the steps
+// past the tile in REC).
+template <int CH>
+__device__ __forceinline__ int recordMaxChannel(unsigned word) {
+	const int mc = int(word & 255u);
+	return (mc > CH - 1) ? CH - 1 : mc;
+}
+template <int NCH>
+__device__ __forceinline__ void unpackRecord(const float4 (&q)[NCH], float (&f)[NCH*4]) {
+#pragma unroll
+	for (int j = 0; j < NCH; ++j) { f[4*j] = q[j].x; f[4*j + 1] = q[j].y; f[4*j + 2] = q[j].z; f[4*j + 3] = q[j].w; }
+}
+
+// ONE step of the bin recurrence, THE definition every recurrence kernel calls (kVocoder, kVocoderCont, kVocoderN, kVocoderOne, kChain): the
+// record `f`, the maximum channel's four taps -- own outputs at b-1 (o1) and b-L (oL), the previous hop's at b+1 (p1) and b+L (pL) -- to the
+// CH channel outputs of bin b.  Where the taps come from (registers and DPP, an LDS ring, the staged carried output) and where the outputs
+// go is each kernel's business; the order of the accumulation, the choice of makeOutput and the channel lock (:791-800) are here alone.
+// f[9..11]: mono {P, sqrt(E)}; 2+ channels {the maximum channel's fallback output, sqrt(E_m)} (recordChannelFields).
+// An all-zero record gives exactly zero outputs, whatever the taps hold.
+template <int CH, int NFLOATS>
+__device__ __forceinline__ void recurrenceOutputs(const float (&f)[NFLOATS], int mc, float2 o1, float2 oL, float2 p1, float2 pL, float2 (&out)[CH]) {
+	const float2 pm = make_float2(f[9], f[10]);
+	const float sm = f[11];
+	float2 phi = prevHopTerms(p1, make_float2(f[4], f[5]), pL, make_float2(f[6], f[7])); // previous hop's part first (what FOLD0 records pre-compute)
+	phi = cfma(oL, make_float2(f[2], f[3]), phi);
+	phi = cfma(o1, make_float2(f[0], f[1]), phi); // the newest operand last: two dependent instructions behind it
+	if constexpr (CH == 1) {
+		out[0] = makeOutput(phi, pm, sm); // :788
+	} else {
+		const float2 om = makeOutputFb(phi, pm, sm); // :788
+		if constexpr (CH == 2) { // one locked channel, its makeOutput folded into the record
+			const float2 olock = lockedOutput(om, f);
+			out[0] = mc ? olock : om;
+			out[1] = mc ? om : olock;
+		} else {
+			const unsigned word = unsigned(__float_as_int(f[8]));
+#pragma unroll
+			for (int c = 0; c < CH; ++c) {
+				float2 oc = lockedOutputN(om, f, c, word); // one complex multiply, its normalisation is the producer's
+				if (c == mc) oc = om;
+				out[c] = oc;
+			}
+		}
+	}
+}
+
 // Hand-off words in LDS: relaxed workgroup-scope atomics.  (A `volatile` access makes the backend drain EVERY
 // outstanding memory operation -- s_waitcnt vmcnt(0) -- around it, which serialised the producers' prefetch loads
 // behind each poll.)  Ordering against the data they guard comes from the in-order LDS pipe plus compiler barriers.
 __device__ __forceinline__ int ldsPeek(volatile int *p) { return __hip_atomic_load(const_cast<int *>(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
 __device__ __forceinline__ void ldsPost(volatile int *p, int v) { __hip_atomic_store(const_cast<int *>(p), v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
 __device__ __forceinline__ void ldsCount(volatile int *p) { (void)__hip_atomic_fetch_add(const_cast<int *>(p), 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
+
+// Lanes of a wave exchange data through LDS: everything written before is visible to every lane after.  (A function, not a macro: the CPU
+// stand-in replaces the barrier builtin with its own lane rendezvous.)
+__device__ __forceinline__ void waveSync() {
+	__builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+	__builtin_amdgcn_wave_barrier();
+	__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// A record's place in the LDS ring of the fused kernels: recs[(slot*BS + step)*NCH + chunk][64 lanes], the lane rotated by the step -- the 8
+// lanes of a producer's row (same row, 8 steps = 8 LDS rows a multiple of 4 KB apart) land in 8 different 16-byte bank groups (a rotation
+// by 2*st, the first version, used only four of them)
+template <int BS, int NF4>
+__device__ __forceinline__ void storeRecord(float4 *recs, int slot, int st, int row, const float (&f)[NF4]) {
+	constexpr int NCH = NF4/4;
+#pragma unroll
+	for (int j = 0; j < NCH; ++j) recs[((slot*BS + st)*NCH + j)*64 + ((row + st) & 63)] = make_float4(f[4*j], f[4*j + 1], f[4*j + 2], f[4*j + 3]);
+}
+template <int BS, int NCH>
+__device__ __forceinline__ void storeZeroRecord(float4 *recs, int slot, int st, int row) {
+#pragma unroll
+	for (int j = 0; j < NCH; ++j) recs[((slot*BS + st)*NCH + j)*64 + ((row + st) & 63)] = make_float4(0.f, 0.f, 0.f, 0.f);
+}
 
 constexpr int kVocWaves = 16; // waves of a recurrence workgroup (kVocoder, kVocoderN)
 

@@ -6,8 +6,8 @@ namespace smst {
 // ------------------------------------------------------------------------------------------------------
 // K3 fused (mono / stereo): the recurrence and its coefficients in ONE kernel, so the records never touch HBM.
 // One workgroup of 16 waves per stream: wave 0 is the CONSUMER (the skewed wavefront, one lane per hop), wave 4 the
-// WRITER (results -> HBM), and 8 (staged) or 14 (gathering) of the others are PRODUCERS that compute the records (same
-// arithmetic as kPredictB, 8 rows x 8 steps per wave-pass) into an LDS ring of 2 or 3 blocks x 8 steps; unused waves
+// WRITER (results -> HBM), and 8 (staged) or 14 (gathering) of the others are PRODUCERS that compute the records (computeRecord,
+// or plainRecord from operands parked in LDS; 8 rows x 8 steps per wave-pass) into an LDS ring of 2 or 3 blocks x 8 steps; unused waves
 // retire at once.  Hand-off is by LDS counters (units produced per slot, blocks consumed, result blocks ready /
 // written); LDS operations of a wave execute in order, so a counter update issued after the data writes is seen after them.
 //
@@ -38,6 +38,19 @@ struct StageGeom {
 	static constexpr int TOTAL = 8*ROW_PIECES + CH*X_PIECES;
 	static constexpr int LOADS = (TOTAL + 63)/64;
 	static constexpr int ROWS = 9; // local rows -1..7
+};
+// Operands of plainRecord in a row's staged windows; `mine`, `up`: the row's and the row above's windows at the record's step (window start + st).
+// The row above is hop row-1 of the tile (its windows start lag = L+1 bins later), or the carried state's energies staged as (E, 0).
+template <int CH, int L>
+struct StageView {
+	using G = StageGeom<CH, L>;
+	const float2 *mine, *up;
+	bool upIsEnergy;
+	__device__ __forceinline__ float2 in(int c, int off) const { return mine[c*2*G::PIN + 2*L + off]; }
+	__device__ __forceinline__ float2 prev(int c, int off) const { return mine[G::PV_OFF + c*2*G::PPV + off - 1]; }
+	__device__ __forceinline__ float2 rot(int off) const { return mine[G::ROT_OFF + off - 1]; }
+	__device__ __forceinline__ float2 above(int c, int off) const { return up[c*2*G::PIN + off - (L + 1) + 2*L]; }
+	__device__ __forceinline__ bool aboveIsEnergy() const { return upIsEnergy; }
 };
 
 // two adjacent entries of the carried Prediction.energy, by element index (fp32: one 8-byte load)
@@ -176,9 +189,7 @@ __device__ __forceinline__ void vocoderProduceStaged(const DevBatch &d, int s, i
 #pragma unroll
 			for (int c = 0; c < CH; ++c) { car1[c] = carNext1[c]; carL[c] = carNextL[c]; }
 		}
-		__builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-		__builtin_amdgcn_wave_barrier();
-		__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+		waveSync();
 		if (n + NPB < totalBlocks) { issue(n + NPB); if (it == 0) issueCarried(n + NPB); }
 		const int slot = n%NB;
 		// (waiting only before the store, as the gathering producers do, was slower here: 8.2 -> 8.5 ms per step -- records
@@ -190,66 +201,13 @@ __device__ __forceinline__ void vocoderProduceStaged(const DevBatch &d, int s, i
 #pragma unroll
 		for (int j = 0; j < NCH*4; ++j) f[j] = 0.0f;
 		if (row < nh && b >= 0 && b < M && !SMST_SKIP_PRODUCER_MATH(d)) {
-			// same arithmetic as computeRecord<CH, true, false, false>, operands from the staged windows
-			auto IN = [&](int c, int x) { return mine[c*2*G::PIN + (x - b0 + 2*L)]; };
-			auto lerpIN = [&](int c, LerpIndex li) {
-				const float2 low = IN(c, li.lo), high = IN(c, li.lo + 1);
-				return clerp(low, high, li.fr);
-			};
-			float2 p[CH];
-			float e[CH];
-#pragma unroll
-			for (int c = 0; c < CH; ++c) { p[c] = IN(c, b); e[c] = cnorm(p[c]); }
-			int mc = 0;
-			float eMax = e[0];
-#pragma unroll
-			for (int c = 1; c < CH; ++c) if (e[c] > eMax) { mc = c; eMax = e[c]; }
-			float2 Pm = p[0];
-#pragma unroll
-			for (int c = 1; c < CH; ++c) if (c == mc) Pm = p[c];
-			const float fb = float(b);
-			float2 A = cmulc(Pm, lerpIN(mc, lerpIndex(fb - tf)));
-			float2 B = cmulc(Pm, lerpIN(mc, lerpIndex(fb - L*tf)));
-			auto twist = [&](int bx, float stepMul) {
-				const int bc = min(bx, M - 1);
-				const float2 rotB = rotate ? mine[G::ROT_OFF + (bx - b0 - 1)] : make_float2(1.f, 0.f);
-				const float2 Q = cmul(mine[G::PV_OFF + mc*2*G::PPV + (bx - b0 - 1)], rotB);
-				const float2 Px = IN(mc, bx);
-				const float2 TW = cmul(rotB, cmulc(Px, Q));
-				const float eNow = cnorm(Px);
-				// Prediction.energy of the previous hop: hop row-1's input (its window starts lag bins later), or the carried state
-				const float2 up = above[mc*2*G::PIN + (bx - b0 - lag + 2*L)];
-				const float ePrev = (row > 0) ? cnorm(up) : up.x;
-				const float den = fmaxf(ePrev, eNow) + 1e-15f;
-				const float2 down = cmulc(Px, lerpIN(mc, lerpIndex(float(bc) - stepMul*tf)));
-				const float2 rr = cmulc(TW, down);
-				const float inv = __builtin_amdgcn_rcpf(den); // 1-ulp hardware reciprocal (an IEEE division costs ten instructions per record)
-				return make_float2(rr.x*inv, rr.y*inv);
-			};
-			float2 Cc = twist(b + 1, 1.0f), Dc = twist(b + L, float(L));
-			const float2 zero = make_float2(0.f, 0.f);
-			if (!(b > 0)) A = zero;
-			if (!(b >= L)) B = zero;
-			if (!(b < M - 1)) Cc = zero;
-			if (!(b < M - L)) Dc = zero;
-			if (it == 0) { // FOLD0: row 0's record carries the previous-hop part ready-made (wave-uniform branch, lane select inside)
-				float2 c1 = car1[0], cL = carL[0];
-#pragma unroll
-				for (int c = 1; c < CH; ++c) if (c == mc) { c1 = car1[c]; cL = carL[c]; }
-				const float2 K = prevHopTerms(c1, Cc, cL, Dc);
-				if (r == 0) { Cc = K; Dc = zero; }
-			}
-			f[0] = A.x; f[1] = A.y; f[2] = B.x; f[3] = B.y; f[4] = Cc.x; f[5] = Cc.y; f[6] = Dc.x; f[7] = Dc.y;
-			f[8] = __int_as_float(mc);
-			recordChannelFields<CH>(f, p, e, mc);
+			const StageView<CH, L> view{mine + st, above + st, !(row > 0)}; // above the tile's first hop: the carried energies
+			plainRecord<CH, L, true>(view, b, M, tf, rotate, it == 0, r == 0, car1, carL, f); // FOLD0: a wave-uniform branch, a lane select inside
 		}
-#pragma unroll
-		for (int j = 0; j < NCH; ++j) recs[((slot*BS + st)*NCH + j)*64 + ((row + st) & 63)] = make_float4(f[4*j], f[4*j + 1], f[4*j + 2], f[4*j + 3]);
+		storeRecord<BS>(recs, slot, st, row, f);
 		asm volatile("" ::: "memory");
 		if (k == 0) ldsCount(&sync[slot]);
-		__builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-		__builtin_amdgcn_wave_barrier(); // every lane has read its operands before the next block's windows are parked
-		__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+		waveSync(); // every lane has read its operands before the next block's windows are parked
 	}
 }
 
@@ -273,8 +231,8 @@ __device__ __forceinline__ void vocoderProduceStaged(const DevBatch &d, int s, i
 // of a lane's two previous-hop bins travel in registers (the table's active region is 4 KB and stays in L1); the row above a
 // wave's first row (Prediction.energy of the previous hop, owned by the neighbouring wave) is staged as the 16 bins its block
 // needs.  The 8-bin lag costs 63*3 more steps per tile (+5.6 %) and puts rows r and r+1 on complementary halves of the LDS
-// banks with no row padding.  Same operands, same operations in the same order as vocoderProduceStaged / computeRecord:
-// bit-identical records.
+// banks with no row padding.  The records are plainRecord's, as the staged producers' (AlignView says where the
+// operands lie).
 template <int CH, int L, int NB, bool FIRST>
 __device__ __forceinline__ void vocoderProduceAligned(const DevBatch &d, int s, int sg, int nh, int it, int k, int totalBlocks,
                                                       float4 *recs, volatile int *sync, const HopDesc *hopsLds, float2 *sbuf, const CarriedOutput &stOut) {
@@ -286,9 +244,7 @@ __device__ __forceinline__ void vocoderProduceAligned(const DevBatch &d, int s, 
 	const int M = d.M, lines = M >> 4;
 	float2 *xbuf = sbuf + 8*G::ROWLEN;
 	for (int i = k; i < G::PER_PRODUCER/2; i += 64) reinterpret_cast<float4 *>(sbuf)[i] = make_float4(0.f, 0.f, 0.f, 0.f); // bins below 0 read as zero
-	__builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-	__builtin_amdgcn_wave_barrier();
-	__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+	waveSync();
 	// ---- block-invariant description of this lane's line pieces: [parity of the block][load]
 	const float2 *lsrc[2][G::LOADS];
 	int llds[2][G::LOADS], lrow[2][G::LOADS];
@@ -407,8 +363,7 @@ __device__ __forceinline__ void vocoderProduceAligned(const DevBatch &d, int s, 
 		const int slot = skip%NB;
 		while (skip - ldsPeek(&sync[NB]) >= NB) __builtin_amdgcn_s_sleep(2);
 		asm volatile("" ::: "memory");
-#pragma unroll
-		for (int j = 0; j < NCH; ++j) recs[((slot*BS + st)*NCH + j)*64 + ((row + st) & 63)] = make_float4(0.f, 0.f, 0.f, 0.f);
+		storeZeroRecord<BS, NCH>(recs, slot, st, row);
 		asm volatile("" ::: "memory");
 		if (k == 0) ldsCount(&sync[slot]);
 	}
@@ -423,17 +378,14 @@ __device__ __forceinline__ void vocoderProduceAligned(const DevBatch &d, int s, 
 	// condition inside the loop: n0 + 1 and the number of blocks are both even.
 	{
 		park(n0, 0, vE);
-		__builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-		__builtin_amdgcn_wave_barrier();
-		__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+		waveSync();
 		issueSmall(n0 + 1);
 		issueLines(n0 + 2, 0, vE);
 		if (!FIRST) {
 			const int slot = n0%NB;
 			while (n0 - ldsPeek(&sync[NB]) >= NB) __builtin_amdgcn_s_sleep(2);
 			asm volatile("" ::: "memory");
-#pragma unroll
-			for (int j = 0; j < NCH; ++j) recs[((slot*BS + st)*NCH + j)*64 + ((row + st) & 63)] = make_float4(0.f, 0.f, 0.f, 0.f);
+			storeZeroRecord<BS, NCH>(recs, slot, st, row);
 			asm volatile("" ::: "memory");
 			if (k == 0) ldsCount(&sync[slot]);
 		}
@@ -441,9 +393,7 @@ __device__ __forceinline__ void vocoderProduceAligned(const DevBatch &d, int s, 
 	}
 	auto step = [&](int n, int par, Async16 (&v)[G::LOADS], Async16 (&vNextBlock)[G::LOADS]) {
 		park(n, par, v);
-		__builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-		__builtin_amdgcn_wave_barrier();
-		__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+		waveSync();
 		issueSmall(n + 1);
 		issueLines(n + 2, par, v);
 		const int slot = n%NB;
@@ -454,72 +404,13 @@ __device__ __forceinline__ void vocoderProduceAligned(const DevBatch &d, int s, 
 #pragma unroll
 		for (int j = 0; j < NCH*4; ++j) f[j] = 0.0f;
 		if (row < nh && b >= 0 && b < M) {
-			// same arithmetic as computeRecord<CH, true, false, false>, operands from the line buffers.  This row's buffer holds the
-			// lines (j-1, j) in its even blocks (b0 = 16j) and (j, j+1) in its odd ones, so bin b sits at 16 + st resp. 8 + st; the row
-			// above runs 8 bins ahead (opposite parity): its buffer holds (j, j+1) either way, bin b at st resp. 8 + st.
-			const bool odd = (n - row) & 1;
-			const float2 *mine = sbuf + r*G::ROWLEN + (odd ? 8 : 16) + st;                               // bin b of channel 0's input
-			const float2 *above = (r > 0) ? sbuf + (r - 1)*G::ROWLEN + (odd ? 8 : 0) + st : xbuf + st; // bin b of the hop above (r == 0: the staged 16 bins start at b0)
-			const int abovePitch = (r > 0) ? G::RING : 16; // channel pitch of `above`
-			auto IN = [&](int c, int off) { return mine[c*G::RING + off]; }; // bin b + off
-			auto lerpIN = [&](int c, LerpIndex li) { // li.lo is an absolute bin
-				const float2 low = mine[c*G::RING + (li.lo - b)], high = mine[c*G::RING + (li.lo - b) + 1];
-				return clerp(low, high, li.fr);
-			};
-			float2 p[CH];
-			float e[CH];
-#pragma unroll
-			for (int c = 0; c < CH; ++c) { p[c] = IN(c, 0); e[c] = cnorm(p[c]); }
-			int mc = 0;
-			float eMax = e[0];
-#pragma unroll
-			for (int c = 1; c < CH; ++c) if (e[c] > eMax) { mc = c; eMax = e[c]; }
-			float2 Pm = p[0];
-#pragma unroll
-			for (int c = 1; c < CH; ++c) if (c == mc) Pm = p[c];
-			const float fb = float(b);
-			float2 A = cmulc(Pm, lerpIN(mc, lerpIndex(fb - tf)));
-			float2 B = cmulc(Pm, lerpIN(mc, lerpIndex(fb - L*tf)));
-			auto twist = [&](int off, float2 rotV, float stepMul) { // bx = b + off
-				const int bc = min(b + off, M - 1);
-				const float2 rotB = rotate ? rotV : make_float2(1.f, 0.f);
-				const float2 Q = cmul(mine[(CH + mc)*G::RING + off], rotB);
-				const float2 Px = IN(mc, off);
-				const float2 TW = cmul(rotB, cmulc(Px, Q));
-				const float eNow = cnorm(Px);
-				// Prediction.energy of the previous hop: hop row-1's input, or the carried state
-				const float2 up = above[mc*abovePitch + off];
-				const float ePrev = (row > 0) ? cnorm(up) : up.x;
-				const float den = fmaxf(ePrev, eNow) + 1e-15f;
-				const float2 down = cmulc(Px, lerpIN(mc, lerpIndex(float(bc) - stepMul*tf)));
-				const float2 rr = cmulc(TW, down);
-				const float inv = __builtin_amdgcn_rcpf(den); // 1-ulp hardware reciprocal (an IEEE division costs ten instructions per record)
-				return make_float2(rr.x*inv, rr.y*inv);
-			};
-			float2 Cc = twist(1, rot1, 1.0f), Dc = twist(L, rotL, float(L));
-			const float2 zero = make_float2(0.f, 0.f);
-			if (!(b > 0)) A = zero;
-			if (!(b >= L)) B = zero;
-			if (!(b < M - 1)) Cc = zero;
-			if (!(b < M - L)) Dc = zero;
-			if (FIRST) { // FOLD0: row 0's record carries the previous-hop part ready-made (lane select inside)
-				float2 c1 = car1[0], cL = carL[0];
-#pragma unroll
-				for (int c = 1; c < CH; ++c) if (c == mc) { c1 = car1[c]; cL = carL[c]; }
-				const float2 K = prevHopTerms(c1, Cc, cL, Dc);
-				if (r == 0) { Cc = K; Dc = zero; }
-			}
-			f[0] = A.x; f[1] = A.y; f[2] = B.x; f[3] = B.y; f[4] = Cc.x; f[5] = Cc.y; f[6] = Dc.x; f[7] = Dc.y;
-			f[8] = __int_as_float(mc);
-			recordChannelFields<CH>(f, p, e, mc);
+			const AlignView<CH, L> view(sbuf, xbuf, r, st, (n - row) & 1, !(row > 0), rot1, rotL); // above the tile's first hop: the carried energies
+			plainRecord<CH, L, FIRST>(view, b, M, tf, rotate, true, r == 0, car1, carL, f);
 		}
-#pragma unroll
-		for (int j = 0; j < NCH; ++j) recs[((slot*BS + st)*NCH + j)*64 + ((row + st) & 63)] = make_float4(f[4*j], f[4*j + 1], f[4*j + 2], f[4*j + 3]);
+		storeRecord<BS>(recs, slot, st, row, f);
 		asm volatile("" ::: "memory");
 		if (k == 0) ldsCount(&sync[slot]);
-		__builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-		__builtin_amdgcn_wave_barrier(); // every lane has read its operands before the next block's lines are parked
-		__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+		waveSync(); // every lane has read its operands before the next block's lines are parked
 		landed(vNextBlock);
 	};
 	for (int n = n0 + 1; n < totalBlocks; n += 2) {
@@ -533,8 +424,8 @@ __device__ __forceinline__ void vocoderProduceAligned(const DevBatch &d, int s, 
 // recurrence wave are 64 STREAMS (up to acrossRows of them per workgroup) instead of 64 hops of one stream.  Every row is the
 // first hop of its tile, so every record carries its previous-hop terms ready-made (FOLD0) and no lane needs another lane's
 // output: no skew (lag 0), no DPP, M steps per launch.  kVocoderOne runs one chain per WAVE (64 lanes computing the same
-// values); at 4096 streams that is four chain waves per SIMD and 1.57 ms per hop quantum.  Same records, same arithmetic:
-// bit-identical to the other recurrence kernels.
+// values); at 4096 streams that is four chain waves per SIMD and 1.57 ms per hop quantum.  Same records (computeRecord with FOLD0), same
+// step (wavefrontBlock).
 // ALIGNED (with STAGED): the line-aligned producers and a wavefront lag of 8 bins (vocoderProduceAligned).
 template <int CH, bool PLAIN, int L, bool STAGED, bool ROTL = false, bool ACROSS = false, bool ALIGNED = false>
 __global__ __launch_bounds__(64*kVocWaves) __attribute__((amdgpu_waves_per_eu(4, 4))) void kVocoder(DevBatch d, int sBase, int hopBase, int acrossRows, int acrossStreams) {
@@ -608,9 +499,7 @@ __global__ __launch_bounds__(64*kVocWaves) __attribute__((amdgpu_waves_per_eu(4,
 				if (k == 0) rowClass[q*64 + count[q]] = r;
 				++count[q];
 			}
-			__builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-			__builtin_amdgcn_wave_barrier();
-			__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+			waveSync();
 			const int g8 = k & 7, part = k >> 3; // eight consecutive lanes read eight consecutive rows of the ring (conflict-free); a store instruction still covers whole lines
 			for (int n = 0; n <= totalBlocks + 1; ++n) {
 				if (n < totalBlocks) {
@@ -689,8 +578,7 @@ __global__ __launch_bounds__(64*kVocWaves) __attribute__((amdgpu_waves_per_eu(4,
 					while (n - ldsPeek(&sync[NB]) >= NB) __builtin_amdgcn_s_sleep(2); // slot still being read
 					asm volatile("" ::: "memory");
 					if (half == h) {
-#pragma unroll
-						for (int j = 0; j < NCH; ++j) recs[((slot*BS + st)*NCH + j)*64 + ((row + st) & 63)] = make_float4(f[4*j], f[4*j + 1], f[4*j + 2], f[4*j + 3]);
+						storeRecord<BS>(recs, slot, st, row, f);
 					}
 					asm volatile("" ::: "memory");
 					if (k == 0) ldsCount(&sync[slot]); // LDS ops of a wave are in order: data first, then the count
@@ -717,10 +605,7 @@ __global__ __launch_bounds__(64*kVocWaves) __attribute__((amdgpu_waves_per_eu(4,
 			}
 			while (n - ldsPeek(&sync[NB]) >= NB) __builtin_amdgcn_s_sleep(2); // slot still being read (waited for AFTER the pass is computed)
 			asm volatile("" ::: "memory");
-#pragma unroll
-			// lane rotation by st: the 8 lanes of a row (same row, 8 steps = 8 LDS rows a multiple of 4 KB apart) land in 8 different
-			// 16-byte bank groups (a rotation by 2*st, the first version, used only four of them)
-			for (int j = 0; j < NCH; ++j) recs[((slot*BS + st)*NCH + j)*64 + ((row + st) & 63)] = make_float4(f[4*j], f[4*j + 1], f[4*j + 2], f[4*j + 3]);
+			storeRecord<BS>(recs, slot, st, row, f);
 			asm volatile("" ::: "memory");
 			if (k == 0) ldsCount(&sync[slot]); // LDS ops of a wave are in order: data first, then the count
 		}
@@ -755,66 +640,10 @@ __global__ __launch_bounds__(64*kVocWaves) __attribute__((amdgpu_waves_per_eu(4,
 		while (n - seenWritten >= 2) { __builtin_amdgcn_s_sleep(1); seenWritten = ldsPeek(&sync[NB + 2]); } // the writer still owns this result slot
 		asm volatile("" ::: "memory");
 		float2 *blockOut = outRing + (size_t)(n%OB)*BS*CH*kVocOutPitch + k;
-		float4 q[2][NCH]; // two register sets alternate, so the next step's record loads never overwrite live values
-#pragma unroll
-		for (int j = 0; j < NCH; ++j) q[0][j] = blockRecs[j*64 + k];
-#pragma unroll
-		for (int i = 0; i < BS; ++i) {
-			if (SMST_CONSUMER_ONLY_ACKNOWLEDGES(d)) break; // experiment builds only
-			if (i + 1 < BS) {
-#pragma unroll
-				for (int j = 0; j < NCH; ++j) q[(i + 1) & 1][j] = blockRecs[((i + 1)*NCH + j)*64 + ((k + (i + 1)) & 63)];
-			} else { // last step: look at the next block's hand-off words now, their latency hides under this step
-				seenProduced = ldsPeek(&sync[(n + 1)%NB]);
-				seenWritten = ldsPeek(&sync[NB + 2]);
-			}
-			float f[NCH*4];
-#pragma unroll
-			for (int j = 0; j < NCH; ++j) { f[4*j] = q[i & 1][j].x; f[4*j + 1] = q[i & 1][j].y; f[4*j + 2] = q[i & 1][j].z; f[4*j + 3] = q[i & 1][j].w; }
-			const int mc = __float_as_int(f[8]); // 0 .. CH-1: every record of the ring was written by a producer (all-zero outside the tile)
-			// taps: own history (bins b-1, b-L), and lane k-1's history: it runs L+1 bins ahead, so ITS b-L and b-1 taps are this
-			// lane's previous-hop taps at b+1 and b+L
-#pragma unroll
-			for (int c = 0; c < CH; ++c) {
-				if constexpr (!ACROSS) {
-					// lane k-1 finished its bin b+x (x = 1, L) lag - x steps ago
-					tap1[c] = fromLaneBelow(h[(i + 17 - lag) & 7][c], tap1[c]);
-					tapL[c] = fromLaneBelow(h[(i + 16 + L - lag) & 7][c], tapL[c]);
-				}
-			}
-			// the maximum channel's taps: explicit per-component selects (v_cndmask) -- written as an `if` the compiler makes a branch of
-			// it, with a register copy in front of every tap that must survive (14 moves against 8 selects)
-			float2 o1 = h[(i + 7) & 7][0], oL = h[(i + 8 - L) & 7][0], p1 = tap1[0], pL = tapL[0];
-#pragma unroll
-			for (int c = 1; c < CH; ++c) {
-				const bool pick = c == mc;
-				o1 = selectPair(pick, h[(i + 7) & 7][c], o1);
-				oL = selectPair(pick, h[(i + 8 - L) & 7][c], oL);
-				p1 = selectPair(pick, tap1[c], p1);
-				pL = selectPair(pick, tapL[c], pL);
-			}
-			const float2 pm = make_float2(f[9], f[10]); // mono: the channel's input; stereo: the maximum channel's fallback output (recordChannelFields)
-			const float sm = f[11];
-			float2 phi = prevHopTerms(p1, make_float2(f[4], f[5]), pL, make_float2(f[6], f[7])); // previous hop's part first (what FOLD0 records pre-compute)
-			phi = cfma(oL, make_float2(f[2], f[3]), phi);
-			phi = cfma(o1, make_float2(f[0], f[1]), phi); // the newest operand last: two dependent instructions behind it
-			const float2 om = (CH == 2) ? makeOutputFb(phi, pm, sm) : makeOutput(phi, pm, sm); // :788
-			if (CH == 2) { // one locked channel (:791-800), its makeOutput folded into the record
-				const float2 olock = lockedOutput(om, f);
-				// cells outside the tile (inactive hop, bin outside [0, M)) have all-zero records, which give exactly zero here
-				const float2 oc0 = mc ? olock : om, oc1 = mc ? om : olock;
-				h[i][0] = oc0;
-				h[i][CH - 1] = oc1;
-				blockOut[(i*CH)*kVocOutPitch] = oc0;
-				blockOut[(i*CH + CH - 1)*kVocOutPitch] = oc1;
-			} else {
-#pragma unroll
-				for (int c = 0; c < CH; ++c) {
-					h[i][c] = om;
-					blockOut[(i*CH + c)*kVocOutPitch] = om;
-				}
-			}
-		}
+		wavefrontBlock<CH, L, lag, ACROSS, NCH>(blockRecs, blockOut, k, h, tap1, tapL, SMST_CONSUMER_ONLY_ACKNOWLEDGES(d), [&] {
+			seenProduced = ldsPeek(&sync[(n + 1)%NB]);
+			seenWritten = ldsPeek(&sync[NB + 2]);
+		});
 		asm volatile("" ::: "memory");
 		if (k == 0) { ldsPost(&sync[NB], n + 1); ldsPost(&sync[NB + 1], n + 1); } // record slot may be refilled; results may be written out
 	}

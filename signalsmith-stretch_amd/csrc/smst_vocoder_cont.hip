@@ -1,6 +1,6 @@
 // K3 fused, mono / stereo, CONTINUOUS form: the skewed wavefront of kVocoder's line-aligned producers (smst_vocoder.hip) run through all
 // tiles of a call without draining (signalsmith-stretch.h:642-660 rotation, :714-716, :722-803 main prediction + channel lock,
-// makeOutput :596-603 -- the same lines kVocoder replaces, the same records, the same arithmetic in the same order: bit-identical).
+// makeOutput :596-603 -- the lines kVocoder replaces, through the same plainRecord and wavefrontBlock).
 //
 // The tile form fills and drains the wavefront once per 64-hop tile: M + 8*63 steps of which 8*63 (14 % at 3072 bins) run with part of
 // the 64 lanes idle -- and every one of those steps costs what a full one costs (the producer waves are the critical path).  Here lane r
@@ -74,9 +74,7 @@ __device__ __forceinline__ void contProduce(const DevBatch &d, const ContArgs &a
 	};
 	float2 *xbuf = sbuf + 8*G::ROWLEN;
 	for (int i = k; i < G::PER_PRODUCER/2; i += 64) reinterpret_cast<float4 *>(sbuf)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-	__builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-	__builtin_amdgcn_wave_barrier();
-	__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+	waveSync();
 	const int nS = n0 - 4; // warm-up: two parks per row fill its two-line buffer (no records, no hand-off words)
 	// ---- this lane's line pieces: [parity of the rows][load].  Rows of parity `par` take a new line in the blocks n with n + 1 = par (mod 2)
 	// (their m = n - row is odd there).  Per piece: the cursor of the NEXT request (lptr; line lline of its hop), whether that hop exists,
@@ -235,9 +233,7 @@ __device__ __forceinline__ void contProduce(const DevBatch &d, const ContArgs &a
 	auto step = [&](int n, int par, Async16 (&v)[G::LOADS], Async16 (&vNextBlock)[G::LOADS]) {
 		xKind = xKindNext;
 		park(par, v);
-		__builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-		__builtin_amdgcn_wave_barrier();
-		__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+		waveSync();
 		issueSmall(n + 1);
 		issueLines(par, v);
 		if (n >= n0) {
@@ -250,68 +246,11 @@ __device__ __forceinline__ void contProduce(const DevBatch &d, const ContArgs &a
 #pragma unroll
 			for (int j = 0; j < NCH*4; ++j) f[j] = 0.0f;
 			if ((flags & HOP_ACTIVE) && mmL < MB) {
-				// the arithmetic of vocoderProduceAligned (= computeRecord<CH, true, false, false>), operands from the line buffers: this row's
-				// buffer holds the lines (j-1, j) in its even blocks (b0 = 16j) and (j, j+1) in its odd ones; the row above runs 8 bins ahead
-				const bool rotate = flags & HOP_NEW_SPECTRUM;
-				const float tf = tfFlags.x;
-				const bool odd = mmL & 1;
-				const float2 *mine = sbuf + r*G::ROWLEN + (odd ? 8 : 16) + st;
-				const float2 *above = (r > 0) ? sbuf + (r - 1)*G::ROWLEN + (odd ? 8 : 0) + st : xbuf + st;
-				const int abovePitch = (r > 0) ? G::RING : 16;
-				auto IN = [&](int c, int off) { return mine[c*G::RING + off]; };
-				auto lerpIN = [&](int c, LerpIndex li) {
-					const float2 low = mine[c*G::RING + (li.lo - b)], high = mine[c*G::RING + (li.lo - b) + 1];
-					return clerp(low, high, li.fr);
-				};
-				float2 p[CH];
-				float e[CH];
-#pragma unroll
-				for (int c = 0; c < CH; ++c) { p[c] = IN(c, 0); e[c] = cnorm(p[c]); }
-				int mc = 0;
-				float eMax = e[0];
-#pragma unroll
-				for (int c = 1; c < CH; ++c) if (e[c] > eMax) { mc = c; eMax = e[c]; }
-				float2 Pm = p[0];
-#pragma unroll
-				for (int c = 1; c < CH; ++c) if (c == mc) Pm = p[c];
-				const float fb = float(b);
-				float2 A = cmulc(Pm, lerpIN(mc, lerpIndex(fb - tf)));
-				float2 B = cmulc(Pm, lerpIN(mc, lerpIndex(fb - L*tf)));
 				const bool energyAbove = FIRST && xKind == 1 && r == 0; // the carried Prediction.energy only above the run's very first hop
-				auto twist = [&](int off, float2 rotV, float stepMul) {
-					const int bc = min(b + off, M - 1);
-					const float2 rotB = rotate ? rotV : make_float2(1.f, 0.f);
-					const float2 Q = cmul(mine[(CH + mc)*G::RING + off], rotB);
-					const float2 Px = IN(mc, off);
-					const float2 TW = cmul(rotB, cmulc(Px, Q));
-					const float eNow = cnorm(Px);
-					const float2 up = above[mc*abovePitch + off];
-					const float ePrev = energyAbove ? up.x : cnorm(up);
-					const float den = fmaxf(ePrev, eNow) + 1e-15f;
-					const float2 down = cmulc(Px, lerpIN(mc, lerpIndex(float(bc) - stepMul*tf)));
-					const float2 rr = cmulc(TW, down);
-					const float inv = __builtin_amdgcn_rcpf(den);
-					return make_float2(rr.x*inv, rr.y*inv);
-				};
-				float2 Cc = twist(1, rot1, 1.0f), Dc = twist(L, rotL, float(L));
-				const float2 zero = make_float2(0.f, 0.f);
-				if (!(b > 0)) A = zero;
-				if (!(b >= L)) B = zero;
-				if (!(b < M - 1)) Cc = zero;
-				if (!(b < M - L)) Dc = zero;
-				if (FIRST) { // FOLD0: row 0's record carries the previous-hop part ready-made
-					float2 c1 = car1[0], cL = carL[0];
-#pragma unroll
-					for (int c = 1; c < CH; ++c) if (c == mc) { c1 = car1[c]; cL = carL[c]; }
-					const float2 K = prevHopTerms(c1, Cc, cL, Dc);
-					if (r == 0) { Cc = K; Dc = zero; }
-				}
-				f[0] = A.x; f[1] = A.y; f[2] = B.x; f[3] = B.y; f[4] = Cc.x; f[5] = Cc.y; f[6] = Dc.x; f[7] = Dc.y;
-				f[8] = __int_as_float(mc);
-				recordChannelFields<CH>(f, p, e, mc);
+				const AlignView<CH, L> view(sbuf, xbuf, r, st, mmL & 1, energyAbove, rot1, rotL);
+				plainRecord<CH, L, FIRST>(view, b, M, tfFlags.x, flags & HOP_NEW_SPECTRUM, true, r == 0, car1, carL, f);
 			}
-#pragma unroll
-			for (int j = 0; j < NCH; ++j) recs[((slot*BS + st)*NCH + j)*64 + ((row + st) & 63)] = make_float4(f[4*j], f[4*j + 1], f[4*j + 2], f[4*j + 3]);
+			storeRecord<BS>(recs, slot, st, row, f);
 			asm volatile("" ::: "memory");
 			if (k == 0) ldsCount(&sync[slot]);
 		}
@@ -319,9 +258,7 @@ __device__ __forceinline__ void contProduce(const DevBatch &d, const ContArgs &a
 		if (++mmA == P) { mmA = 0; ++relA; }
 		{ const bool wrap = mmL + 1 == P; mmL = wrap ? 0 : mmL + 1; relL += wrap ? 1 : 0; }
 		tfFlags = hopWords(); // (tf, flags) of the lane's hop in the next block: 8 bytes out of LDS, asked for a block ahead of their use
-		__builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-		__builtin_amdgcn_wave_barrier(); // every lane has read its operands before the next block's lines are parked
-		__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+		waveSync(); // every lane has read its operands before the next block's lines are parked
 		landed(vNextBlock);
 	};
 	// nS is even: its parking rows have parity 1 (register set "O"), block nS + 1 the others.  issueSmall(n) is called with the counters
@@ -449,7 +386,7 @@ __global__ __launch_bounds__(64*kContWaves) __attribute__((amdgpu_waves_per_eu(3
 		return;
 	}
 
-	// ---------------- consumer (wave 0): kVocoder's, over the global blocks [n0, n1) ----------------
+	// ---------------- consumer (wave 0): wavefrontBlock over the global blocks [n0, n1) ----------------
 	__builtin_amdgcn_s_setprio(3);
 	float2 h[8][CH];
 	float2 tap1[CH], tapL[CH];
@@ -483,57 +420,10 @@ __global__ __launch_bounds__(64*kContWaves) __attribute__((amdgpu_waves_per_eu(3
 		while (n - seenWritten >= 2) { __builtin_amdgcn_s_sleep(1); seenWritten = ldsPeek(&sync[NB + 2]); } // the writer still owns this result slot
 		asm volatile("" ::: "memory");
 		float2 *blockOut = outRing + (size_t)(n%OB)*BS*CH*kVocOutPitch + k;
-		float4 q[2][NCH];
-#pragma unroll
-		for (int j = 0; j < NCH; ++j) q[0][j] = blockRecs[j*64 + k];
-#pragma unroll
-		for (int i = 0; i < BS; ++i) {
-			if (i + 1 < BS) {
-#pragma unroll
-				for (int j = 0; j < NCH; ++j) q[(i + 1) & 1][j] = blockRecs[((i + 1)*NCH + j)*64 + ((k + (i + 1)) & 63)];
-			} else {
-				seenProduced = ldsPeek(&sync[(n + 1)%NB]);
-				seenWritten = ldsPeek(&sync[NB + 2]);
-			}
-			float f[NCH*4];
-#pragma unroll
-			for (int j = 0; j < NCH; ++j) { f[4*j] = q[i & 1][j].x; f[4*j + 1] = q[i & 1][j].y; f[4*j + 2] = q[i & 1][j].z; f[4*j + 3] = q[i & 1][j].w; }
-			const int mc = __float_as_int(f[8]);
-#pragma unroll
-			for (int c = 0; c < CH; ++c) {
-				tap1[c] = fromLaneBelow(h[(i + 17 - lag) & 7][c], tap1[c]);
-				tapL[c] = fromLaneBelow(h[(i + 16 + L - lag) & 7][c], tapL[c]);
-			}
-			float2 o1 = h[(i + 7) & 7][0], oL = h[(i + 8 - L) & 7][0], p1 = tap1[0], pL = tapL[0];
-#pragma unroll
-			for (int c = 1; c < CH; ++c) {
-				const bool pick = c == mc;
-				o1 = selectPair(pick, h[(i + 7) & 7][c], o1);
-				oL = selectPair(pick, h[(i + 8 - L) & 7][c], oL);
-				p1 = selectPair(pick, tap1[c], p1);
-				pL = selectPair(pick, tapL[c], pL);
-			}
-			const float2 pm = make_float2(f[9], f[10]);
-			const float sm = f[11];
-			float2 phi = prevHopTerms(p1, make_float2(f[4], f[5]), pL, make_float2(f[6], f[7]));
-			phi = cfma(oL, make_float2(f[2], f[3]), phi);
-			phi = cfma(o1, make_float2(f[0], f[1]), phi);
-			const float2 om = (CH == 2) ? makeOutputFb(phi, pm, sm) : makeOutput(phi, pm, sm);
-			if (CH == 2) {
-				const float2 olock = lockedOutput(om, f);
-				const float2 oc0 = mc ? olock : om, oc1 = mc ? om : olock;
-				h[i][0] = oc0;
-				h[i][CH - 1] = oc1;
-				blockOut[(i*CH)*kVocOutPitch] = oc0;
-				blockOut[(i*CH + CH - 1)*kVocOutPitch] = oc1;
-			} else {
-#pragma unroll
-				for (int c = 0; c < CH; ++c) {
-					h[i][c] = om;
-					blockOut[(i*CH + c)*kVocOutPitch] = om;
-				}
-			}
-		}
+		wavefrontBlock<CH, L, lag, false, NCH>(blockRecs, blockOut, k, h, tap1, tapL, false, [&] {
+			seenProduced = ldsPeek(&sync[(n + 1)%NB]);
+			seenWritten = ldsPeek(&sync[NB + 2]);
+		});
 		asm volatile("" ::: "memory");
 		if (k == 0) { ldsPost(&sync[NB], n + 1); ldsPost(&sync[NB + 1], n + 1); }
 	}

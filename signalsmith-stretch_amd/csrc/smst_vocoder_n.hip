@@ -134,25 +134,18 @@ __global__ __launch_bounds__(64) void kChain(DevBatch d, int sBase, int hopBase)
 				pf[c] = (bb < M) ? v : make_float2(0.f, 0.f);
 			}
 		}
-		__builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-		__builtin_amdgcn_wave_barrier();
-		__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+		waveSync();
 
 		for (int i = 0; i < 64/PD; ++i) {
 #pragma unroll
 			for (int u = 0; u < PD; ++u) {
 				const int t = tb + i*PD + u;
 				float f[NCH*4];
-#pragma unroll
-				for (int j = 0; j < NCH; ++j) { f[4*j] = q[u][j].x; f[4*j + 1] = q[u][j].y; f[4*j + 2] = q[u][j].z; f[4*j + 3] = q[u][j].w; }
+				unpackRecord(q[u], f);
 				const int b = t - lag*k;
 				const bool valid = active && b >= 0 && b < M;
-				const unsigned word = unsigned(__float_as_int(f[8])); // the maximum channel; 3+ channels: bits 8.. flag the channels whose lock falls back to their input
-				int mc = int(word & 255u);
-				mc = (mc > CH - 1) ? CH - 1 : mc; // records of out-of-range steps are not initialised
+				const int mc = recordMaxChannel<CH>(unsigned(__float_as_int(f[8]))); // records of out-of-range steps are not initialised
 				float2 o1 = own1[0];
-				const float2 pm = make_float2(f[9], f[10]); // mono: the input; 2+ channels: the maximum channel's fallback output (recordChannelFields)
-				const float sm = f[11];
 #pragma unroll
 				for (int c = 1; c < CH; ++c) {
 					if (c == mc) o1 = own1[c];
@@ -163,18 +156,11 @@ __global__ __launch_bounds__(64) void kChain(DevBatch d, int sBase, int hopBase)
 				const int aL = (k == 0) ? stageBase + mc*128 + ((b + L) & 127) : (ringRow + ((b + L) & Rm))*64 + k - 1;
 				const float2 p1 = lds[a1];
 				const float2 pL = lds[aL];
-				float2 phi = prevHopTerms(p1, make_float2(f[4], f[5]), pL, make_float2(f[6], f[7])); // previous hop's part first (what FOLD0 records pre-compute)
-				phi = cfma(oL, make_float2(f[2], f[3]), phi);
-				phi = cfma(o1, make_float2(f[0], f[1]), phi); // the newest operand last: two dependent instructions behind it
-				const float2 om = (CH >= 2) ? makeOutputFb(phi, pm, sm) : makeOutput(phi, pm, sm); // :788 (records of 2+ channels carry the fallback output in pm's place)
-				const float2 olock = (CH == 2) ? lockedOutput(om, f) : om; // stereo: see recordChannelFields
+				float2 out[CH];
+				recurrenceOutputs<CH>(f, mc, o1, oL, p1, pL, out);
 #pragma unroll
 				for (int c = 0; c < CH; ++c) {
-					float2 oc;
-					if constexpr (CH == 2) oc = olock;
-					else if constexpr (CH == 1) oc = om;
-					else oc = lockedOutputN(om, f, c, word); // channel lock, :791-800, pre-scaled by the record's producer
-					if (c == mc) oc = om;
+					float2 oc = out[c];
 					if (!valid) oc = make_float2(0.f, 0.f);
 					own1[c] = oc;
 					lds[(c*R + (b & Rm))*64 + k] = oc;
@@ -185,9 +171,7 @@ __global__ __launch_bounds__(64) void kChain(DevBatch d, int sBase, int hopBase)
 				// the same registers and nothing has to be copied (or waited for) at the loop back-edge
 #pragma unroll
 				for (int j = 0; j < NCH; ++j) q[u][j] = rec[(size_t)(t + PD)*recPitch + j*64];
-				__builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-				__builtin_amdgcn_wave_barrier();
-				__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+				waveSync();
 			}
 		}
 	}
@@ -202,7 +186,7 @@ __global__ __launch_bounds__(64) void kChain(DevBatch d, int sBase, int hopBase)
 //     channel in registers (the b-1 tap) and everything else in an LDS ring [CH][16 bins][64 lanes] indexed by the bin,
 //     which the next lane (the b+1 / b+L taps of the previous hop) and the writer read as well -- so there is no
 //     separate result buffer;
-//   * the producers gather (computeRecord), as the un-fused kPredictB does: same arithmetic, bit-identical results.
+//   * the producers gather (computeRecord), as the un-fused kPredictB does; the step is recurrenceOutputs, as everywhere.
 // It replaces kPredictB + kChain, whose records went through HBM (14 MB per stream and tile) and whose recurrence
 // issued CH scattered 8-byte stores per lane and step -- every record prefetch then waited behind those stores
 // (vmcnt counts both on gfx9): 4.4 us per step for 8 channels.
@@ -267,9 +251,7 @@ __global__ __launch_bounds__(64*kVocWaves) __attribute__((amdgpu_waves_per_eu(4,
 					}
 				}
 				static_assert(lag >= 2 && lag <= 7, "the whole-line writer's four classes of 16 rows");
-				__builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-				__builtin_amdgcn_wave_barrier();
-				__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+				waveSync();
 				for (int n = 0; n <= totalBlocks; ++n) {
 					if (n < totalBlocks) {
 						while (ldsPeek(&sync[NB + 1]) <= n) __builtin_amdgcn_s_sleep(2);
@@ -298,9 +280,7 @@ __global__ __launch_bounds__(64*kVocWaves) __attribute__((amdgpu_waves_per_eu(4,
 							}
 						}
 					}
-					__builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-					__builtin_amdgcn_wave_barrier(); // every lane has read the slabs this pass frees (the hardware's lanes run in lockstep; the CPU stand-in's do not)
-					__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+					waveSync(); // every lane has read the slabs this pass frees (the hardware's lanes run in lockstep; the CPU stand-in's do not)
 					{
 						const int idx = k >> 2, part = (k >> 1) & 1, odd = k & 1;
 #pragma unroll
@@ -318,9 +298,7 @@ __global__ __launch_bounds__(64*kVocWaves) __attribute__((amdgpu_waves_per_eu(4,
 							}
 						}
 					}
-					__builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-					__builtin_amdgcn_wave_barrier(); // ... and filed its groups before the next pass reads them
-					__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+					waveSync(); // ... and filed its groups before the next pass reads them
 					if (k == 0) ldsPost(&sync[NB + 2], n + 1);
 				}
 				return;
@@ -338,9 +316,7 @@ __global__ __launch_bounds__(64*kVocWaves) __attribute__((amdgpu_waves_per_eu(4,
 					if (k == 0) rowClass[q*64 + count[q]] = r;
 					++count[q];
 				}
-				__builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-				__builtin_amdgcn_wave_barrier();
-				__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+				waveSync();
 				constexpr int PASSES = 2; // 32 rows per class for every lag from 2 to 7 (ceil(lag*row/4) is odd for exactly half of the 64 rows)
 				static_assert(lag >= 2 && lag <= 7, "the half-line writer's two classes of rows");
 				const int rho = k >> 2, quarter = k & 3;
@@ -446,8 +422,7 @@ __global__ __launch_bounds__(64*kVocWaves) __attribute__((amdgpu_waves_per_eu(4,
 					while (n - ldsPeek(&sync[NB]) >= NB) __builtin_amdgcn_s_sleep(2); // slot still being read
 					asm volatile("" ::: "memory");
 					if (half == h) {
-#pragma unroll
-						for (int j = 0; j < NCH; ++j) recs[((h*BS + st)*NCH + j)*64 + ((row + st) & 63)] = make_float4(f[4*j], f[4*j + 1], f[4*j + 2], f[4*j + 3]);
+						storeRecord<BS>(recs, h, st, row, f);
 					}
 					asm volatile("" ::: "memory");
 					if (k == 0) ldsCount(&sync[h]); // LDS ops of a wave are in order: data first, then the count
@@ -472,8 +447,7 @@ __global__ __launch_bounds__(64*kVocWaves) __attribute__((amdgpu_waves_per_eu(4,
 			// 4 of the 14 producers work, and the recurrence wave waited 57 % of every block for records.
 			while (n - ldsPeek(&sync[NB]) >= NB) __builtin_amdgcn_s_sleep(2); // slot still being read
 			asm volatile("" ::: "memory");
-#pragma unroll
-			for (int j = 0; j < NCH; ++j) recs[((slot*BS + st)*NCH + j)*64 + ((row + st) & 63)] = make_float4(f[4*j], f[4*j + 1], f[4*j + 2], f[4*j + 3]);
+			storeRecord<BS>(recs, slot, st, row, f);
 			asm volatile("" ::: "memory");
 			if (k == 0) ldsCount(&sync[slot]); // LDS ops of a wave are in order: data first, then the count
 		}
@@ -502,9 +476,7 @@ __global__ __launch_bounds__(64*kVocWaves) __attribute__((amdgpu_waves_per_eu(4,
 				pf[c] = (bb < M) ? v : make_float2(0.f, 0.f);
 			}
 		}
-		__builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-		__builtin_amdgcn_wave_barrier();
-		__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+		waveSync();
 		for (int blk = 0; blk < 64/BS; ++blk) {
 			const int n = ch*(64/BS) + blk;
 			const int slot = n%NB;
@@ -519,19 +491,14 @@ __global__ __launch_bounds__(64*kVocWaves) __attribute__((amdgpu_waves_per_eu(4,
 			for (int i = 0; i < BS; ++i) {
 				if (SMST_CONSUMER_ONLY_ACKNOWLEDGES(d)) break; // experiment builds only
 				const int t = tb + blk*BS + i;
-				float f[NCH*4];
+				float4 q[NCH];
 #pragma unroll
-				for (int j = 0; j < NCH; ++j) {
-					const float4 q = blockRecs[(i*NCH + j)*64 + ((k + i) & 63)];
-					f[4*j] = q.x; f[4*j + 1] = q.y; f[4*j + 2] = q.z; f[4*j + 3] = q.w;
-				}
+				for (int j = 0; j < NCH; ++j) q[j] = blockRecs[(i*NCH + j)*64 + ((k + i) & 63)];
+				float f[NCH*4];
+				unpackRecord(q, f);
 				const int b = t - kLag;
-				const unsigned word = unsigned(__float_as_int(f[8])); // the maximum channel; bits 8..: channels whose lock falls back to their own input
-				int mc = int(word & 255u);
-				mc = (mc > CH - 1) ? CH - 1 : mc;
+				const int mc = recordMaxChannel<CH>(unsigned(__float_as_int(f[8]))); // (the mask for the flag bits; every record of the ring is a producer's: the clamp never acts)
 				float2 o1 = own1[0];
-				const float2 pm = make_float2(f[9], f[10]); // the maximum channel's fallback output (recordChannelFields)
-				const float sm = f[11];
 #pragma unroll
 				for (int c = 1; c < CH; ++c) {
 					if (c == mc) o1 = own1[c];
@@ -540,21 +507,14 @@ __global__ __launch_bounds__(64*kVocWaves) __attribute__((amdgpu_waves_per_eu(4,
 				const float2 oL = ring[(ringRow + ((b - L) & Rm))*64 + k];
 				const float2 p1 = (k == 0) ? stage[mc*128 + ((b + 1) & 127)] : ring[(ringRow + ((b + 1) & Rm))*64 + k - 1];
 				const float2 pL = (k == 0) ? stage[mc*128 + ((b + L) & 127)] : ring[(ringRow + ((b + L) & Rm))*64 + k - 1];
-				float2 phi = prevHopTerms(p1, make_float2(f[4], f[5]), pL, make_float2(f[6], f[7])); // previous hop's part first (what FOLD0 records pre-compute)
-				phi = cfma(oL, make_float2(f[2], f[3]), phi);
-				phi = cfma(o1, make_float2(f[0], f[1]), phi); // the newest operand last: two dependent instructions behind it
-				const float2 om = makeOutputFb(phi, pm, sm); // :788
+				float2 out[CH];
+				recurrenceOutputs<CH>(f, mc, o1, oL, p1, pL, out);
 #pragma unroll
-				for (int c = 0; c < CH; ++c) {
-					float2 oc = lockedOutputN(om, f, c, word); // channel lock, :791-800: one complex multiply, its normalisation is the producer's (recordChannelFields)
-					if (c == mc) oc = om;
-					// cells outside the tile (inactive hop, bin outside [0, M)) have all-zero records, which give exactly zero here
-					own1[c] = oc;
-					ring[(c*R + (b & Rm))*64 + k] = oc;
+				for (int c = 0; c < CH; ++c) { // cells outside the tile (inactive hop, bin outside [0, M)) have all-zero records, which give exactly zero here
+					own1[c] = out[c];
+					ring[(c*R + (b & Rm))*64 + k] = out[c];
 				}
-				__builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-				__builtin_amdgcn_wave_barrier(); // lane k+1 reads what lane k wrote lag-1 .. lag+L-1 steps ago
-				__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+				waveSync(); // lane k+1 reads what lane k wrote lag-1 .. lag+L-1 steps ago
 			}
 			asm volatile("" ::: "memory");
 			if (k == 0) { ldsPost(&sync[NB], n + 1); ldsPost(&sync[NB + 1], n + 1); }
@@ -570,7 +530,7 @@ __global__ __launch_bounds__(64*kVocWaves) __attribute__((amdgpu_waves_per_eu(4,
 // every load is one contiguous row segment) and stores the finished results; wave 0 runs the bin recurrence of the single
 // hop with its history in registers (every lane computes the same chain; lane 0 publishes).  All streams of a call are
 // resident at once (1024 stereo streams: 12 waves per CU), so the latency of the hop is the length of ONE chain.
-// Same records (computeRecord), same order of operations as kVocoder / kVocoderN: bit-identical results.
+// Same records (computeRecord), same step (recurrenceOutputs) as kVocoder / kVocoderN.
 // ------------------------------------------------------------------------------------------------------
 constexpr int kVocOneBlock = 64;
 
@@ -621,8 +581,7 @@ __global__ __launch_bounds__(128) void kVocoderOne(DevBatch d, int sBase, int ho
 #pragma unroll
 			for (int j = 0; j < NCH; ++j) dst[j] = make_float4(f[4*j], f[4*j + 1], f[4*j + 2], f[4*j + 3]);
 			asm volatile("" ::: "memory");
-			__builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-			__builtin_amdgcn_wave_barrier();
+			waveSync();
 			if (k == 0) ldsPost(&sync[0], n + 1);
 			if (n > 0) writeBlock(n - 1);
 		}
@@ -658,9 +617,7 @@ __global__ __launch_bounds__(128) void kVocoderOne(DevBatch d, int sBase, int ho
 				pf[c] = (bb < M) ? v : make_float2(0.f, 0.f);
 			}
 		}
-		__builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-		__builtin_amdgcn_wave_barrier();
-		__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+		waveSync();
 		while (ldsPeek(&sync[0]) <= n) __builtin_amdgcn_s_sleep(1);
 		asm volatile("" ::: "memory");
 		const float4 *blockRecs = recs + (size_t)(n % NB)*BS*NCH;
@@ -669,36 +626,24 @@ __global__ __launch_bounds__(128) void kVocoderOne(DevBatch d, int sBase, int ho
 #pragma unroll
 			for (int i = 0; i < 8; ++i) {
 				const int step = i8*8 + i, b = tb + step;
-				float f[NCH*4];
+				float4 q[NCH];
 #pragma unroll
-				for (int j = 0; j < NCH; ++j) {
-					const float4 q = blockRecs[step*NCH + j];
-					f[4*j] = q.x; f[4*j + 1] = q.y; f[4*j + 2] = q.z; f[4*j + 3] = q.w;
-				}
-				const unsigned word = unsigned(__float_as_int(f[8])); // the maximum channel; 3+ channels: bits 8.. flag the channels whose lock falls back to their input
-				int mc = int(word & 255u);
-				mc = (mc > CH - 1) ? CH - 1 : mc;
+				for (int j = 0; j < NCH; ++j) q[j] = blockRecs[step*NCH + j];
+				float f[NCH*4];
+				unpackRecord(q, f);
+				const int mc = recordMaxChannel<CH>(unsigned(__float_as_int(f[8]))); // (the mask for 3+ channels; every record is wave 1's: the clamp never acts)
 				float2 o1 = h[(i + 7) & 7][0], oL = h[(i + 8 - L) & 7][0];
 				float2 p1 = stage[(b + 1) & 127], pL = stage[(b + L) & 127];
-				const float2 pm = make_float2(f[9], f[10]); // mono: the input; 2+ channels: the maximum channel's fallback output
-				const float sm = f[11];
 #pragma unroll
 				for (int c = 1; c < CH; ++c) {
 					const float2 p1c = stage[c*128 + ((b + 1) & 127)], pLc = stage[c*128 + ((b + L) & 127)];
 					if (c == mc) { o1 = h[(i + 7) & 7][c]; oL = h[(i + 8 - L) & 7][c]; p1 = p1c; pL = pLc; }
 				}
-				float2 phi = prevHopTerms(p1, make_float2(f[4], f[5]), pL, make_float2(f[6], f[7])); // previous hop's part first (what FOLD0 records pre-compute)
-				phi = cfma(oL, make_float2(f[2], f[3]), phi);
-				phi = cfma(o1, make_float2(f[0], f[1]), phi); // the newest operand last: two dependent instructions behind it
-				const float2 om = (CH >= 2) ? makeOutputFb(phi, pm, sm) : makeOutput(phi, pm, sm); // :788 (records of 2+ channels carry the fallback output in pm's place)
-				const float2 olock = (CH == 2) ? lockedOutput(om, f) : om; // stereo: see recordChannelFields
+				float2 out[CH];
+				recurrenceOutputs<CH>(f, mc, o1, oL, p1, pL, out);
 #pragma unroll
 				for (int c = 0; c < CH; ++c) {
-					float2 oc;
-					if constexpr (CH == 2) oc = olock;
-					else if constexpr (CH == 1) oc = om;
-					else oc = lockedOutputN(om, f, c, word); // channel lock, :791-800, pre-scaled by the record's producer
-					if (c == mc) oc = om;
+					float2 oc = out[c];
 					if (b < startBin) oc = make_float2(0.f, 0.f);
 					h[i][c] = oc; // bins past the last one have all-zero records, which give exactly zero
 					if (k == 0) blockOut[c*BS + step] = oc;
@@ -706,8 +651,7 @@ __global__ __launch_bounds__(128) void kVocoderOne(DevBatch d, int sBase, int ho
 			}
 		}
 		asm volatile("" ::: "memory");
-		__builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-		__builtin_amdgcn_wave_barrier();
+		waveSync();
 		if (k == 0) ldsPost(&sync[1], n + 1);
 	}
 }
