@@ -39,14 +39,13 @@ struct DevBatch {
 	const float2 *twH;     // e^{-2 pi i j / H}
 	const float2 *halfTw;  // e^{-i pi m / N}
 	const float2 *rot;     // per-bin hop rotation (signalsmith-stretch.h:647-655)
-	const float2 *twA, *twB; // fast FFT (H = 256*R3): stage twiddles laid out [n-1][p]
 	const float2 *winA, *winB; // analysis window folded with e^{-i pi m/N}: u[m] = x[m+B/2]*winA[m] + x[m-H+B/2]*winB[m]
 	const float4 *win4;        // (winA[m], winB[m]) interleaved: one 16-byte load per element in the fast analysis kernel
 	const float4 *synTab;      // (halfTw[m], window[m+B/2] or 0, window[m-M+B/2] or 0): one 16-byte load per synthesis output
 	const float4 *twA4, *twB4; // stage twiddles of the register-blocked FFT, rows (2i, 2i+1) paired: [8][16*R3], [8][R3]
 	const unsigned *lcgPow;    // 16807^(j+1) mod (2^31 - 1), j < 2M: jump-ahead factors of the reference's random engine (smst_kernels_common.h: engineDraw)
 	const float4 *twA6;        // lean form of twA4: (w^1, w^2), (w^3, w^4), (w^8, w^12) per thread, [3][16*R3]
-	const float2 *win2, *syn2; // lean forms of win4 / synTab: the two window samples of an element only, [M]
+	const float2 *win2;        // lean form of win4 and of synTab: the two window samples of an element only, [M]
 	const float *window;   // analysis == synthesis window (Kaiser, perfect reconstruction)
 	const float *wprod;    // window[i]^2 * N
 	// per-stream state
@@ -138,6 +137,8 @@ struct MoveArgs {
 // The generic FFT kernels ping-pong between two buffers of `bands` complex values: in LDS while both fit (150 KiB), else one of them in memory
 // (kAnalyse<true> / kSynth<true>: presetDefault / presetCheaper at 176.4 / 192 kHz).  One buffer must still fit.
 __host__ __device__ inline bool fftNeedsScratch(int bands) { return (size_t)bands*16 > (size_t)150*1024; }
+// The register-blocked FFT's band counts, 256*R3 (smst_fft.hip)
+__host__ __device__ inline bool isFastSize(int bands) { return bands == 256*10 || bands == 256*12 || bands == 256*20 || bands == 256*24; }
 constexpr int kMaxBands = 150*1024/8; // 19200 bins of LDS; the largest band count {1,2,3,4,5,6,8}*2^k reaches below it is 16384
 
 struct WindowPad { int lo, hi; };

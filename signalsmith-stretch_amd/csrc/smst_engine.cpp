@@ -266,20 +266,14 @@ void Batch::construct(const FftPlan &plan, long seed) {
 		d.win4 = static_cast<float4 *>(upload(w4.data(), M*sizeof(float4)));
 		d.synTab = static_cast<float4 *>(upload(st4.data(), M*sizeof(float4)));
 		{ // lean tables: the window samples alone (the modulation e^{-i pi m/N} is generated from halfTw[t] and constants)
-			std::vector<float2> w2(M), s2(M);
-			for (int m = 0; m < M; ++m) {
-				const float a = (m < B - halfB) ? win[m + halfB] : 0.0f, b = (m >= M - halfB) ? win[m - M + halfB] : 0.0f;
-				w2[m] = make_float2(a, b);
-				s2[m] = make_float2(a, b);
-			}
+			std::vector<float2> w2(M);
+			for (int m = 0; m < M; ++m) w2[m] = make_float2((m < B - halfB) ? win[m + halfB] : 0.0f, (m >= M - halfB) ? win[m - M + halfB] : 0.0f);
 			d.win2 = static_cast<float2 *>(upload(w2.data(), M*sizeof(float2)));
-			d.syn2 = static_cast<float2 *>(upload(s2.data(), M*sizeof(float2)));
 		}
-		d.twA = d.twB = nullptr;
 		d.twA4 = d.twB4 = d.twA6 = nullptr;
-		if (M%256 == 0 && (M/256 == 10 || M/256 == 12 || M/256 == 20 || M/256 == 24)) { // the register-blocked FFT's sizes: 16 x 16 x R3
+		if (isFastSize(M)) { // the register-blocked FFT's sizes: 16 x 16 x R3
 			const int R3 = M/256, MA = 16*R3;
-			std::vector<float2> ta((size_t)15*MA), tb((size_t)15*R3);
+			std::vector<float2> ta((size_t)15*MA), tb((size_t)15*R3); // w^(n p), rows [n - 1][p]: host only, paired into the tables below
 			for (int n = 1; n < 16; ++n) {
 				for (int p = 0; p < MA; ++p) {
 					double a = -2*M_PI*double(p*n)/double(M);
@@ -290,8 +284,6 @@ void Batch::construct(const FftPlan &plan, long seed) {
 					tb[(size_t)(n - 1)*R3 + p] = make_float2(float(std::cos(a)), float(std::sin(a)));
 				}
 			}
-			d.twA = static_cast<float2 *>(upload(ta.data(), ta.size()*sizeof(float2)));
-			d.twB = static_cast<float2 *>(upload(tb.data(), tb.size()*sizeof(float2)));
 			std::vector<float4> ta4((size_t)8*MA), tb4((size_t)8*R3);
 			for (int i = 0; i < 8; ++i) {
 				for (int p = 0; p < MA; ++p) {

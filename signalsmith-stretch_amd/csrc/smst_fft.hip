@@ -1,5 +1,6 @@
 // Analysis and synthesis transforms, overlap-add and emission (K1, K4a, K4b, K5) and their launchers.  See smst_kernels_common.h.
 #include "smst_kernels_common.h"
+#include <type_traits>
 
 namespace smst {
 
@@ -16,92 +17,7 @@ __device__ __forceinline__ float2 twiddle(const float2 *__restrict__ tw, int idx
 	return w;
 }
 
-template <int SIGN>
-__device__ float2 *fftLds(float2 *src, float2 *dst, const FftPlan &plan, const float2 *__restrict__ tw) {
-	const int H = plan.H;
-	int nCur = H;
-	int shift = 0; // s = 1 << shift while radices are powers of two
-	for (int pass = 0; pass < plan.npass; ++pass) {
-		const int r = plan.radix[pass];
-		const int m = nCur/r;
-		const int nb = H/r;
-		const int twScale = H/nCur;
-		if (r == 4) {
-			const int s = 1 << shift;
-			for (int t = threadIdx.x; t < nb; t += blockDim.x) {
-				const int p = t >> shift, q0 = t & (s - 1);
-				const float2 *in = src + q0 + (p << shift);
-				const int inStride = m << shift;
-				float2 *out = dst + q0 + ((4*p) << shift);
-				float2 a = in[0], b = in[inStride], c = in[2*inStride], e = in[3*inStride];
-				float2 apc = cadd(a, c), amc = csub(a, c), bpe = cadd(b, e), bme = csub(b, e);
-				float2 jb = (SIGN < 0) ? mulNegI(bme) : mulI(bme);
-				const int ti = p*twScale;
-				out[0] = cadd(apc, bpe);
-				out[s] = cmulPlain(cadd(amc, jb), twiddle<SIGN>(tw, ti));
-				out[2*s] = cmulPlain(csub(apc, bpe), twiddle<SIGN>(tw, 2*ti));
-				out[3*s] = cmulPlain(csub(amc, jb), twiddle<SIGN>(tw, 3*ti));
-			}
-			shift += 2;
-		} else if (r == 2) {
-			const int s = 1 << shift;
-			for (int t = threadIdx.x; t < nb; t += blockDim.x) {
-				const int p = t >> shift, q0 = t & (s - 1);
-				const float2 *in = src + q0 + (p << shift);
-				const int inStride = m << shift;
-				float2 *out = dst + q0 + ((2*p) << shift);
-				float2 a = in[0], b = in[inStride];
-				out[0] = cadd(a, b);
-				out[s] = cmulPlain(csub(a, b), twiddle<SIGN>(tw, p*twScale));
-			}
-			shift += 1;
-		} else if (r == 3) { // last pass: m == 1, p == 0, all twiddles are 1
-			const int s = nb;
-			const float s3 = 0.86602540378443864676f;
-			for (int t = threadIdx.x; t < nb; t += blockDim.x) {
-				float2 a = src[t], b = src[t + s], c = src[t + 2*s];
-				float2 bpc = cadd(b, c), bmc = csub(b, c);
-				float2 tt = make_float2(a.x - 0.5f*bpc.x, a.y - 0.5f*bpc.y);
-				float2 u = cscale((SIGN < 0) ? mulNegI(bmc) : mulI(bmc), s3);
-				dst[t] = cadd(a, bpc);
-				dst[t + s] = cadd(tt, u);
-				dst[t + 2*s] = csub(tt, u);
-			}
-		} else { // r == 5, last pass
-			const int s = nb;
-			const float c1 = 0.30901699437494742410f, c2 = -0.80901699437494742410f;
-			const float s1 = 0.95105651629515357212f, s2 = 0.58778525229247312917f;
-			for (int t = threadIdx.x; t < nb; t += blockDim.x) {
-				float2 a = src[t], b = src[t + s], c = src[t + 2*s], e = src[t + 3*s], f = src[t + 4*s];
-				float2 bpf = cadd(b, f), bmf = csub(b, f), cpe = cadd(c, e), cme = csub(c, e);
-				float2 t1 = make_float2(a.x + c1*bpf.x + c2*cpe.x, a.y + c1*bpf.y + c2*cpe.y);
-				float2 t2 = make_float2(a.x + c2*bpf.x + c1*cpe.x, a.y + c2*bpf.y + c1*cpe.y);
-				float2 u1 = make_float2(s1*bmf.x + s2*cme.x, s1*bmf.y + s2*cme.y);
-				float2 u2 = make_float2(s2*bmf.x - s1*cme.x, s2*bmf.y - s1*cme.y);
-				float2 ju1 = (SIGN < 0) ? mulNegI(u1) : mulI(u1);
-				float2 ju2 = (SIGN < 0) ? mulNegI(u2) : mulI(u2);
-				dst[t] = cadd(a, cadd(bpf, cpe));
-				dst[t + s] = cadd(t1, ju1);
-				dst[t + 2*s] = cadd(t2, ju2);
-				dst[t + 3*s] = csub(t2, ju2);
-				dst[t + 4*s] = csub(t1, ju1);
-			}
-		}
-		__syncthreads();
-		float2 *tmp = src; src = dst; dst = tmp;
-		nCur = m;
-	}
-	return src;
-}
-
-// ------------------------------------------------------------------------------------------------------
-// Register-blocked FFT for H = 256*R3: three Stockham stages 16 x 16 x R3, each butterfly held in registers, so the data
-// (R3 = 10: 2560 bins = presetCheaper at 44.1/48 kHz; 12: 3072 = presetDefault at 44.1/48 kHz; 20: 5120 = presetCheaper at 88.2/96 kHz;
-// 24: 6144 = presetDefault at 88.2/96 kHz -- every size signalsmith-stretch.h:63-68 produces up to 96 kHz; R3 = {2,4,8} x {3,5})
-// crosses LDS only twice (vs. six times in the generic radix-4 ladder) and the stage-A output is padded by one
-// element per 16 so that neither the 128-byte-strided writes nor the stage-B reads conflict on LDS banks.
-// Twiddles come from per-stage tables laid out [n][p] (coalesced across the threads of a stage).
-// ------------------------------------------------------------------------------------------------------
+// the radix-4, -3 and -5 butterflies, in place, outputs in natural order (the generic ladder's and the register-blocked stages')
 template <int SIGN>
 __device__ __forceinline__ void dft4(float2 &a, float2 &b, float2 &c, float2 &d) {
 	float2 apc = cadd(a, c), amc = csub(a, c), bpd = cadd(b, d), bmd = csub(b, d);
@@ -110,30 +26,6 @@ __device__ __forceinline__ void dft4(float2 &a, float2 &b, float2 &c, float2 &d)
 	b = cadd(amc, jb);
 	c = csub(apc, bpd);
 	d = csub(amc, jb);
-}
-template <int SIGN>
-__device__ __forceinline__ float2 mulConst(float2 v, float re, float im) { // v * (re, SIGN<0 ? -im : +im)
-	const float s = (SIGN < 0) ? -im : im;
-	return make_float2(v.x*re - v.y*s, v.x*s + v.y*re);
-}
-// 16-point DFT in place; on return X[e + 4c] sits at v[c + 4e]
-template <int SIGN>
-__device__ __forceinline__ void dft16(float2 (&v)[16]) {
-#pragma unroll
-	for (int i = 0; i < 4; ++i) dft4<SIGN>(v[i], v[i + 4], v[i + 8], v[i + 12]);
-	const float c1 = 0.92387953251128675613f, s1 = 0.38268343236508977173f, h = 0.70710678118654752440f;
-	// t_i[e] (at v[i + 4e]) *= w16^(i e)
-	v[1 + 4] = mulConst<SIGN>(v[1 + 4], c1, s1);   // w^1
-	v[1 + 8] = mulConst<SIGN>(v[1 + 8], h, h);     // w^2
-	v[1 + 12] = mulConst<SIGN>(v[1 + 12], s1, c1); // w^3
-	v[2 + 4] = mulConst<SIGN>(v[2 + 4], h, h);     // w^2
-	v[2 + 8] = (SIGN < 0) ? mulNegI(v[2 + 8]) : mulI(v[2 + 8]); // w^4
-	v[2 + 12] = mulConst<SIGN>(v[2 + 12], -h, h);  // w^6
-	v[3 + 4] = mulConst<SIGN>(v[3 + 4], s1, c1);   // w^3
-	v[3 + 8] = mulConst<SIGN>(v[3 + 8], -h, h);    // w^6
-	v[3 + 12] = mulConst<SIGN>(v[3 + 12], -c1, -s1); // w^9
-#pragma unroll
-	for (int e = 0; e < 4; ++e) dft4<SIGN>(v[4*e], v[4*e + 1], v[4*e + 2], v[4*e + 3]);
 }
 template <int SIGN>
 __device__ __forceinline__ void dft3(float2 &a, float2 &b, float2 &c) {
@@ -161,6 +53,104 @@ __device__ __forceinline__ void dft5(float2 &a, float2 &b, float2 &c, float2 &d,
 	c = cadd(t2, ju2);
 	d = csub(t2, ju2);
 	e = csub(t1, ju1);
+}
+template <int SIGN>
+__device__ float2 *fftLds(float2 *src, float2 *dst, const FftPlan &plan, const float2 *__restrict__ tw) {
+	const int H = plan.H;
+	int nCur = H;
+	int shift = 0; // s = 1 << shift while radices are powers of two
+	for (int pass = 0; pass < plan.npass; ++pass) {
+		const int r = plan.radix[pass];
+		const int m = nCur/r;
+		const int nb = H/r;
+		const int twScale = H/nCur;
+		if (r == 4) {
+			const int s = 1 << shift;
+			for (int t = threadIdx.x; t < nb; t += blockDim.x) {
+				const int p = t >> shift, q0 = t & (s - 1);
+				const float2 *in = src + q0 + (p << shift);
+				const int inStride = m << shift;
+				float2 *out = dst + q0 + ((4*p) << shift);
+				float2 a = in[0], b = in[inStride], c = in[2*inStride], e = in[3*inStride];
+				dft4<SIGN>(a, b, c, e);
+				const int ti = p*twScale;
+				out[0] = a;
+				out[s] = cmulPlain(b, twiddle<SIGN>(tw, ti));
+				out[2*s] = cmulPlain(c, twiddle<SIGN>(tw, 2*ti));
+				out[3*s] = cmulPlain(e, twiddle<SIGN>(tw, 3*ti));
+			}
+			shift += 2;
+		} else if (r == 2) {
+			const int s = 1 << shift;
+			for (int t = threadIdx.x; t < nb; t += blockDim.x) {
+				const int p = t >> shift, q0 = t & (s - 1);
+				const float2 *in = src + q0 + (p << shift);
+				const int inStride = m << shift;
+				float2 *out = dst + q0 + ((2*p) << shift);
+				float2 a = in[0], b = in[inStride];
+				out[0] = cadd(a, b);
+				out[s] = cmulPlain(csub(a, b), twiddle<SIGN>(tw, p*twScale));
+			}
+			shift += 1;
+		} else if (r == 3) { // last pass: m == 1, p == 0, all twiddles are 1
+			const int s = nb;
+			for (int t = threadIdx.x; t < nb; t += blockDim.x) {
+				float2 a = src[t], b = src[t + s], c = src[t + 2*s];
+				dft3<SIGN>(a, b, c);
+				dst[t] = a;
+				dst[t + s] = b;
+				dst[t + 2*s] = c;
+			}
+		} else { // r == 5, last pass
+			const int s = nb;
+			for (int t = threadIdx.x; t < nb; t += blockDim.x) {
+				float2 a = src[t], b = src[t + s], c = src[t + 2*s], e = src[t + 3*s], f = src[t + 4*s];
+				dft5<SIGN>(a, b, c, e, f);
+				dst[t] = a;
+				dst[t + s] = b;
+				dst[t + 2*s] = c;
+				dst[t + 3*s] = e;
+				dst[t + 4*s] = f;
+			}
+		}
+		__syncthreads();
+		float2 *tmp = src; src = dst; dst = tmp;
+		nCur = m;
+	}
+	return src;
+}
+
+// ------------------------------------------------------------------------------------------------------
+// Register-blocked FFT for H = 256*R3: three Stockham stages 16 x 16 x R3, each butterfly held in registers, so the data
+// (R3 = 10: 2560 bins = presetCheaper at 44.1/48 kHz; 12: 3072 = presetDefault at 44.1/48 kHz; 20: 5120 = presetCheaper at 88.2/96 kHz;
+// 24: 6144 = presetDefault at 88.2/96 kHz -- every size signalsmith-stretch.h:63-68 produces up to 96 kHz; R3 = {2,4,8} x {3,5})
+// crosses LDS only twice (vs. six times in the generic radix-4 ladder) and the stage-A output is padded by one
+// element per 16 so that neither the 128-byte-strided writes nor the stage-B reads conflict on LDS banks.
+// Twiddles come from per-stage tables laid out [n][p] (coalesced across the threads of a stage).
+// ------------------------------------------------------------------------------------------------------
+template <int SIGN>
+__device__ __forceinline__ float2 mulConst(float2 v, float re, float im) { // v * (re, SIGN<0 ? -im : +im)
+	const float s = (SIGN < 0) ? -im : im;
+	return make_float2(v.x*re - v.y*s, v.x*s + v.y*re);
+}
+// 16-point DFT in place; on return X[e + 4c] sits at v[c + 4e]
+template <int SIGN>
+__device__ __forceinline__ void dft16(float2 (&v)[16]) {
+#pragma unroll
+	for (int i = 0; i < 4; ++i) dft4<SIGN>(v[i], v[i + 4], v[i + 8], v[i + 12]);
+	const float c1 = 0.92387953251128675613f, s1 = 0.38268343236508977173f, h = 0.70710678118654752440f;
+	// t_i[e] (at v[i + 4e]) *= w16^(i e)
+	v[1 + 4] = mulConst<SIGN>(v[1 + 4], c1, s1);   // w^1
+	v[1 + 8] = mulConst<SIGN>(v[1 + 8], h, h);     // w^2
+	v[1 + 12] = mulConst<SIGN>(v[1 + 12], s1, c1); // w^3
+	v[2 + 4] = mulConst<SIGN>(v[2 + 4], h, h);     // w^2
+	v[2 + 8] = (SIGN < 0) ? mulNegI(v[2 + 8]) : mulI(v[2 + 8]); // w^4
+	v[2 + 12] = mulConst<SIGN>(v[2 + 12], -h, h);  // w^6
+	v[3 + 4] = mulConst<SIGN>(v[3 + 4], s1, c1);   // w^3
+	v[3 + 8] = mulConst<SIGN>(v[3 + 8], -h, h);    // w^6
+	v[3 + 12] = mulConst<SIGN>(v[3 + 12], -c1, -s1); // w^9
+#pragma unroll
+	for (int e = 0; e < 4; ++e) dft4<SIGN>(v[4*e], v[4*e + 1], v[4*e + 2], v[4*e + 3]);
 }
 // RA-point DFT over v[base + stride*j], j < RA (RA = 2, 4 or 8), in place, outputs in natural order
 template <int SIGN, int RA, int N>
@@ -340,9 +330,64 @@ __device__ __forceinline__ void fftFast(float2 *lds, const float4 *__restrict__ 
 	}
 }
 
+// ------------------------------------------------------------------------------------------------------
+// What the frame kernels share: each step of a frame's way through analysis or synthesis is defined once.
+// ------------------------------------------------------------------------------------------------------
+constexpr int fastBlockThreads(int R3) { return 16*R3 > 256 ? 16*R3 : 256; } // stages A and B take 16*R3 threads, stage C 256
+
+// which hops a launch analyses: those with a new spectrum that no earlier call analysed; which = 1 (the window one interval earlier) only where asked for
+__device__ __forceinline__ bool hopWantsAnalysis(const HopDesc &hd, int which) {
+	return (hd.flags & HOP_ACTIVE) && (hd.flags & HOP_NEW_SPECTRUM) && !(hd.flags & HOP_PREANALYSED) && (!which || (hd.flags & HOP_REANALYSE_PREV));
+}
+
+// A spectrum row in half-bin order: element j of the H-point transform is bin 2j while that is below H, and the conjugate of bin N - 1 - 2j above
+__device__ __forceinline__ int halfBinIndex(int j, int H, int N) {
+	const int kk = 2*j;
+	return kk >= H ? N - 1 - kk : kk;
+}
+__device__ __forceinline__ float2 loadHalfBin(const float2 *X, int j, int H, int N) {
+	// one load at a selected address, conjugated afterwards: with a load in each arm of the conditional the
+	// compiler emitted 16 loads each followed by s_waitcnt vmcnt(0) -- sixteen memory round trips per FFT
+	float2 v = X[halfBinIndex(j, H, N)];
+	if (2*j >= H) v.y = -v.y;
+	return v;
+}
+__device__ __forceinline__ void storeHalfBin(float2 *dst, int j, float2 u, int H, int N) {
+	const int kk = 2*j;
+	if (kk < H) dst[kk] = u;
+	else dst[N - 1 - kk] = cconj(u);
+}
+
+// The windowed analysis element m = t + MA*slot from the full table w = (winA[m], winB[m]), where the window's halves change validity at
+// element-slot boundaries (slot 0 has no imaginary part, slot 15 no real part): the same roundings as kAnalyseFast's general path,
+// round(xi*b + round(xr*a)), with the absent half an exact zero
+__device__ __forceinline__ float2 analysisElement(float4 w, const float *x0, const float *x1, int m, int slot) {
+	float2 r = make_float2(0.f, 0.f);
+	if (slot < 15) { const float xr = x0[m]; r = make_float2(xr*w.x, xr*w.y); }
+	if (slot > 0) { const float xi = x1[m]; r = make_float2(fmaf(xi, w.z, r.x), fmaf(xi, w.w, r.y)); }
+	return r;
+}
+// The lean tables' generated modulation e^{-i pi m/N} of element m = t + stride*k, where e^{-i pi stride/N} = e^{-i pi/per}: hb = halfTw[t] times one
+// of `per` constants (compile-time after unrolling).  Analysis: k = slot, per = 32; synthesis: k = j, per = 2*R3.
+__device__ __forceinline__ float2 leanModulation(float2 hb, int k, int per) {
+	const float ang = 3.14159265358979323846f*float(k)/float(per);
+	return cmulPlain(hb, make_float2(__builtin_cosf(ang), -__builtin_sinf(ang)));
+}
+// Synthesis output m of a frame into dst (the frame in memory, or kSynthEmitTeams' copy in LDS): u * e^{+i pi m/N} (tw = e^{-i pi m/N}), its real
+// part under the window at m + B/2, its imaginary part at m - H + B/2
+__device__ __forceinline__ void storeWindowed(float *dst, int m, float2 u, float2 tw, float wRe, float wIm, int B, int H) {
+	const int halfB = B/2;
+	const float2 v = cmulcPlain(u, tw); // * e^{+i pi m / N}
+	if (m < B - halfB) dst[m + halfB] = (2*v.x)*wRe;
+	if (m >= H - halfB) dst[m - H + halfB] = (2*v.y)*wIm;
+}
+__device__ __forceinline__ void storeWindowed(float *dst, int m, float2 u, float4 r, int B, int H) { // r: the output's synTab entry
+	storeWindowed(dst, m, u, make_float2(r.x, r.y), r.z, r.w, B, H);
+}
+
 // (windowPad / analysisWindowInCall: smst_device.h -- the host scheduler evaluates the same condition)
 template <int R3, bool LEAN>
-__global__ __launch_bounds__(16*R3 > 256 ? 16*R3 : 256) __attribute__((amdgpu_waves_per_eu(4, 4))) void kAnalyseFast(DevBatch d, IoArgs io, int sBase, int hopBase, int lateOnly) {
+__global__ __launch_bounds__(fastBlockThreads(R3)) __attribute__((amdgpu_waves_per_eu(4, 4))) void kAnalyseFast(DevBatch d, IoArgs io, int sBase, int hopBase, int lateOnly) {
 	extern __shared__ __attribute__((aligned(16))) unsigned char smemRaw[];
 	float2 *lds = reinterpret_cast<float2 *>(smemRaw);
 	const BlockCoord bc = xcdAwareBlock();
@@ -351,8 +396,7 @@ __global__ __launch_bounds__(16*R3 > 256 ? 16*R3 : 256) __attribute__((amdgpu_wa
 	const int which = bc.y & 1;
 	const int s = bc.s;
 	const HopDesc hd = d.hops[(size_t)(sBase + s)*d.hopStride + hopBase + k];
-	if (!(hd.flags & HOP_ACTIVE) || !(hd.flags & HOP_NEW_SPECTRUM) || (hd.flags & HOP_PREANALYSED)) return;
-	if (which == 1 && !(hd.flags & HOP_REANALYSE_PREV)) return;
+	if (!hopWantsAnalysis(hd, which)) return;
 	if (lateOnly && analysisWindowInCall(d.B, d.M, d.I, hd.inputOffset, which, io.inSamples[sBase + s])) return; // kAnalyseTeams has taken this frame
 	const int B = d.B, H = d.M, halfB = B/2, N = d.N;
 	const int base = hd.inputOffset - (which ? d.I : 0) - B;
@@ -361,61 +405,44 @@ __global__ __launch_bounds__(16*R3 > 256 ? 16*R3 : 256) __attribute__((amdgpu_wa
 	const float2 *__restrict__ winA = d.winA, *__restrict__ winB = d.winB;
 	float2 *dst = (which ? d.Xprev : d.Xcur) + rowOf(d, s, k, c);
 	auto prep = [](int, int) { return 0; };
-	auto store = [&](int j, float2 u, int, int) {
-		const int kk = 2*j;
-		if (kk < H) dst[kk] = u;
-		else dst[N - 1 - kk] = cconj(u);
-	};
+	auto store = [&](int j, float2 u, int, int) { storeHalfBin(dst, j, u, H, N); };
 	constexpr int MA = 16*R3;
+	const float4 *__restrict__ twA = LEAN ? d.twA6 : d.twA4;
+	// LEAN: the folded window (w_re, w_im)(m) * e^{-i pi m/N} as TWO floats per element and the modulation generated: element
+	// m = t + MA*slot, and e^{-i pi MA/N} = e^{-i pi/32} whatever the size, so the modulation is halfTw[t] times one of
+	// sixteen constants (8 bytes per element instead of 16; six more multiply-adds per element, one more rounding)
+	const float2 *__restrict__ win2 = d.win2;
+	const float2 hb = LEAN ? d.halfTw[min((int)threadIdx.x, MA - 1)] : make_float2(0.f, 0.f);
 	if (base >= 0 && H - halfB == MA && B - halfB == 15*MA) {
 		// the usual case (both presets): the whole window lies in this call's input, and the two halves of the packed
 		// input change validity exactly at element-slot boundaries: slot 0 has no imaginary part, slot 15 no real part
 		const float *x0 = x + base + halfB, *x1 = x + base - H + halfB;
-		if constexpr (LEAN) {
-			// the folded window (w_re, w_im)(m) * e^{-i pi m/N} as TWO floats per element and the modulation generated: element
-			// m = t + MA*slot, and e^{-i pi MA/N} = e^{-i pi/32} whatever the size, so the modulation is halfTw[t] times one of
-			// sixteen constants (8 bytes per element instead of 16; six more multiply-adds per element, one more rounding)
-			const float2 *__restrict__ win2 = d.win2;
-			const float2 hb = d.halfTw[min((int)threadIdx.x, MA - 1)];
-			fftFast<-1, R3, true>(lds, d.twA6, d.twB4,
-				[&](int m, int slot) {
+		const float4 *__restrict__ win4 = d.win4;
+		fftFast<-1, R3, LEAN>(lds, twA, d.twB4,
+			[&](int m, int slot) {
+				if constexpr (LEAN) {
 					const float2 w = win2[m];
 					float2 z = make_float2(0.f, 0.f);
 					if (slot < 15) z.x = x0[m]*w.x;
 					if (slot > 0) z.y = x1[m]*w.y;
-					const float ang = 3.14159265358979323846f*float(slot)/32.0f; // compile-time constant after unrolling
-					const float2 h = cmulPlain(hb, make_float2(__builtin_cosf(ang), -__builtin_sinf(ang)));
-					return cmulPlain(z, h);
-				}, prep, store);
-			return;
-		}
-		const float4 *__restrict__ win4 = d.win4;
-		fftFast<-1, R3, false>(lds, d.twA4, d.twB4,
-			[&](int m, int slot) {
-				// same roundings as the general path below: round(xi*b + round(xr*a)), with the absent half an exact zero
-				const float4 w = win4[m]; // (winA, winB) in one 16-byte load
-				float2 r = make_float2(0.f, 0.f);
-				if (slot < 15) { const float xr = x0[m]; r = make_float2(xr*w.x, xr*w.y); }
-				if (slot > 0) { const float xi = x1[m]; r = make_float2(fmaf(xi, w.z, r.x), fmaf(xi, w.w, r.y)); }
-				return r;
+					return cmulPlain(z, leanModulation(hb, slot, 32));
+				} else {
+					return analysisElement(win4[m], x0, x1, m, slot); // (winA, winB) in one 16-byte load
+				}
 			}, prep, store);
 		return;
 	}
 	// the general case (a window that reaches into the carried history, or a block size whose halves do not fall on slot boundaries):
 	// bounds-checked sample fetches, THE SAME ARITHMETIC as the fast case above, element for element -- a hop analysed in a short
 	// call (history) and the same hop inside one long call must give the same bits (chunking invariance)
-	const float2 hbG = d.halfTw[min((int)threadIdx.x, MA - 1)];
-	fftFast<-1, R3, LEAN>(lds, LEAN ? d.twA6 : d.twA4, d.twB4,
+	fftFast<-1, R3, LEAN>(lds, twA, d.twB4,
 		[&](int m, int slot) {
 			float xr = 0, xi = 0;
 			if (m < B - halfB) { int src = base + m + halfB; xr = (src >= 0) ? x[src] : hist[src]; }
 			if (m >= H - halfB) { int src = base + m - H + halfB; xi = (src >= 0) ? x[src] : hist[src]; }
 			if constexpr (LEAN) {
-				const float2 w = d.win2[m];
-				const float2 z = make_float2(xr*w.x, xi*w.y);
-				const float ang = 3.14159265358979323846f*float(slot)/32.0f; // compile-time constant after unrolling
-				const float2 h = cmulPlain(hbG, make_float2(__builtin_cosf(ang), -__builtin_sinf(ang)));
-				return cmulPlain(z, h);
+				const float2 w = win2[m];
+				return cmulPlain(make_float2(xr*w.x, xi*w.y), leanModulation(hb, slot, 32));
 			} else {
 				const float2 a = winA[m], b = winB[m];
 				return make_float2(fmaf(xi, b.x, xr*a.x), fmaf(xi, b.y, xr*a.y));
@@ -443,171 +470,143 @@ struct TeamSync { // LDS operations of a wave complete in order: a wave's counte
 		asm volatile("" ::: "memory");
 	}
 };
+// A team workgroup's prologue (every thread of the workgroup constructs one): its LDS is the 16-byte table of the kernel's elements
+// (`source`: d.win4 or d.synTab, [H]), the first- and second-stage twiddles ([8][MA], [8][R3]), a transform buffer per team and the teams'
+// barrier words -- teamLdsBytes() on the host.  The tables are copied and the words cleared once per workgroup.
+template <int R3, int TEAMS>
+struct TeamWorkgroup {
+	static_assert(16*R3 <= 256, "a team is 256 threads");
+	static constexpr int MA = 16*R3, H = 256*R3;
+	float4 *table, *twA, *twB;
+	float2 *lds;         // this team's transform buffer, H + H/16
+	int team, t;         // the team, the thread within it
+	volatile int *word;  // the team's barrier word
+	int generation = 0;
+	__device__ __forceinline__ TeamWorkgroup(unsigned char *smem, const DevBatch &d, const float4 *__restrict__ source) {
+		team = __builtin_amdgcn_readfirstlane(threadIdx.x >> 8);
+		t = threadIdx.x & 255;
+		table = reinterpret_cast<float4 *>(smem);
+		twA = table + H;
+		twB = twA + 8*MA;
+		lds = reinterpret_cast<float2 *>(twB + 8*R3) + (size_t)team*(H + H/16);
+		volatile int *words = reinterpret_cast<volatile int *>(reinterpret_cast<float2 *>(twB + 8*R3) + (size_t)TEAMS*(H + H/16));
+		for (int i = threadIdx.x; i < H; i += blockDim.x) table[i] = source[i];
+		for (int i = threadIdx.x; i < 8*MA; i += blockDim.x) twA[i] = d.twA4[i];
+		for (int i = threadIdx.x; i < 8*R3; i += blockDim.x) twB[i] = d.twB4[i];
+		if (threadIdx.x < 16) words[threadIdx.x] = 0;
+		__syncthreads();
+		word = words + team;
+	}
+	TeamWorkgroup(const TeamWorkgroup &) = delete;
+	__device__ __forceinline__ TeamSync sync() { return TeamSync{word, &generation}; } // the team's barrier (it counts in this object)
+};
 
 // EXACT: block = 15/16 of the FFT size (windowPad = 0: the geometry is then a compile-time constant); otherwise see windowPad.
 // Either way the arithmetic is kAnalyseFast's, element for element (an absent half contributes a zero: sample x zero weight).
 template <int R3, int TEAMS, bool EXACT>
 __global__ __launch_bounds__(256*TEAMS) void kAnalyseTeams(DevBatch d, IoArgs io, const HopDesc *__restrict__ hopTable, int sBase, int hopBase, int tileHops, int nStreams) {
-	static_assert(16*R3 <= 256, "a team is 256 threads");
 	extern __shared__ __attribute__((aligned(16))) unsigned char smemRaw[];
 	constexpr int MA = 16*R3, H = 256*R3, N = 2*H;
 	const int B = EXACT ? 480*R3 : d.B, halfB = B/2; // EXACT: the geometry this kernel is launched for
-	const int team = __builtin_amdgcn_readfirstlane(threadIdx.x >> 8), t = threadIdx.x & 255, tA = t < MA ? t : 0;
 	const int total = tileHops*2*d.C*nStreams;
-	float4 *winLds = reinterpret_cast<float4 *>(smemRaw); // (winA, winB) of all elements
-	float4 *twALds = winLds + H;                           // first-stage twiddles, [8][MA]
-	float4 *twBLds = twALds + 8*MA;                        // second-stage twiddles, [8][R3]
-	float2 *lds = reinterpret_cast<float2 *>(twBLds + 8*R3) + (size_t)team*(H + H/16);
-	volatile int *words = reinterpret_cast<volatile int *>(reinterpret_cast<float2 *>(twBLds + 8*R3) + (size_t)TEAMS*(H + H/16));
-	for (int i = threadIdx.x; i < H; i += blockDim.x) winLds[i] = d.win4[i];
-	for (int i = threadIdx.x; i < 8*MA; i += blockDim.x) twALds[i] = d.twA4[i];
-	for (int i = threadIdx.x; i < 8*R3; i += blockDim.x) twBLds[i] = d.twB4[i];
-	if (threadIdx.x < 16) words[threadIdx.x] = 0;
-	__syncthreads();
-	int generation = 0;
-	const TeamSync sync{words + team, &generation};
+	TeamWorkgroup<R3, TEAMS> wg(smemRaw, d, d.win4); // table: (winA, winB) of all elements
+	const TeamSync sync = wg.sync();
+	const int t = wg.t, tA = t < MA ? t : 0;
 	const int stride = gridDim.x*TEAMS;
-	for (int lin = blockIdx.x + gridDim.x*team; lin < total; lin += stride) { // the same residue mod 8 for all of a workgroup's teams
+	for (int lin = blockIdx.x + gridDim.x*wg.team; lin < total; lin += stride) { // the same residue mod 8 for all of a workgroup's teams
 		const BlockCoord bc = xcdAwareCoord(lin, tileHops, 2*d.C, nStreams);
 		const HopDesc hd = hopTable[(size_t)(sBase + bc.s)*d.hopStride + hopBase + bc.x];
 		const int c = bc.y >> 1, which = bc.y & 1;
-		if (!(hd.flags & HOP_ACTIVE) || !(hd.flags & HOP_NEW_SPECTRUM) || (hd.flags & HOP_PREANALYSED) || (which && !(hd.flags & HOP_REANALYSE_PREV)) || !analysisWindowInCall(B, H, d.I, hd.inputOffset, which, io.inSamples[sBase + bc.s])) continue;
+		if (!hopWantsAnalysis(hd, which) || !analysisWindowInCall(B, H, d.I, hd.inputOffset, which, io.inSamples[sBase + bc.s])) continue;
 		const int base = hd.inputOffset - (which ? d.I : 0) - B;
 		const float *x = io.in + (size_t)(sBase + bc.s)*io.inStreamStride + (size_t)c*io.inChannelStride;
 		const float *x0 = x + base + halfB, *x1 = x + base - H + halfB;
 		float2 *dst = (which ? d.Xprev : d.Xcur) + rowOf(d, bc.s, bc.x, c);
-		fftFast<-1, R3, false>(lds, twALds, twBLds,
-			[&](int m, int slot) { // kAnalyseFast's roundings: round(xi*b + round(xr*a)), the absent half an exact zero
-				const float4 w = winLds[tA + MA*slot];
-				float2 r = make_float2(0.f, 0.f);
-				if (slot < 15) { const float xr = x0[m]; r = make_float2(xr*w.x, xr*w.y); }
-				if (slot > 0) { const float xi = x1[m]; r = make_float2(fmaf(xi, w.z, r.x), fmaf(xi, w.w, r.y)); }
-				return r;
-			},
+		fftFast<-1, R3, false>(wg.lds, wg.twA, wg.twB,
+			[&](int m, int slot) { return analysisElement(wg.table[tA + MA*slot], x0, x1, m, slot); },
 			[](int, int) { return 0; },
-			[&](int j, float2 u, int, int) {
-				const int kk = 2*j;
-				if (kk < H) dst[kk] = u;
-				else dst[N - 1 - kk] = cconj(u);
-			}, t, sync);
+			[&](int j, float2 u, int, int) { storeHalfBin(dst, j, u, H, N); }, t, sync);
 		sync(); // the last stage's LDS reads, before the next frame's first-stage writes
 	}
 }
 
 template <int R3, bool LEAN>
-__global__ __launch_bounds__(16*R3 > 256 ? 16*R3 : 256) void kSynthFast(DevBatch d, int sBase, int hopBase) {
+__global__ __launch_bounds__(fastBlockThreads(R3)) void kSynthFast(DevBatch d, int sBase, int hopBase) {
 	extern __shared__ __attribute__((aligned(16))) unsigned char smemRaw[];
 	float2 *lds = reinterpret_cast<float2 *>(smemRaw);
 	const int k = blockIdx.x, c = blockIdx.y, s = blockIdx.z;
 	const HopDesc hd = d.hops[(size_t)(sBase + s)*d.hopStride + hopBase + k];
 	if (!(hd.flags & HOP_ACTIVE)) return;
-	const int B = d.B, H = d.M, N = d.N, halfB = B/2;
+	const int B = d.B, H = d.M, N = d.N;
 	const float2 *X = d.OUT + rowOf(d, s, k, c);
-	float *__restrict__ frame = d.frames + ((size_t)((size_t)s*d.T + k)*d.C + c)*(size_t)B;
-	auto loadBin = [&](int j, int) {
-		// one load at a selected address, conjugated afterwards: with a load in each arm of the conditional the
-		// compiler emitted 16 loads each followed by s_waitcnt vmcnt(0) -- sixteen memory round trips per FFT
-		const int kk = 2*j;
-		const bool upper = kk >= H;
-		float2 v = X[upper ? N - 1 - kk : kk];
-		if (upper) v.y = -v.y;
-		return v;
-	};
+	float *__restrict__ frame = frameOf(d, s, k, c);
+	auto loadBin = [&](int j, int) { return loadHalfBin(X, j, H, N); };
 	if constexpr (LEAN) {
 		// an output needs e^{+i pi m/N} and its two window samples: the windows as one 8-byte load, the modulation generated --
-		// m = t + 256 j, so it is halfTw[t] times one of R3 constants e^{-i pi j/(2 R3)} (conjugated in the product below)
-		const float2 *__restrict__ syn2 = d.syn2;
+		// m = t + 256 j, so it is halfTw[t] times one of R3 constants e^{-i pi j/(2 R3)} (conjugated in the product of storeWindowed)
+		const float2 *__restrict__ win2 = d.win2;
 		const float2 hb = d.halfTw[min((int)threadIdx.x, 255)];
 		fftFast<+1, R3, true>(lds, d.twA6, d.twB4, loadBin,
-			[&](int m, int) { return syn2[m]; },
-			[&](int m, float2 u, float2 w, int j) {
-				const float ang = 3.14159265358979323846f*float(j)/float(2*R3); // compile-time constant after unrolling
-				const float2 h = cmulPlain(hb, make_float2(__builtin_cosf(ang), -__builtin_sinf(ang)));
-				const float2 v = cmulcPlain(u, h); // * e^{+i pi m / N}
-				if (m < B - halfB) frame[m + halfB] = (2*v.x)*w.x;
-				if (m >= H - halfB) frame[m - H + halfB] = (2*v.y)*w.y;
-			});
-		return;
+			[&](int m, int) { return win2[m]; },
+			[&](int m, float2 u, float2 w, int j) { storeWindowed(frame, m, u, leanModulation(hb, j, 2*R3), w.x, w.y, B, H); });
+	} else {
+		const float4 *__restrict__ synTab = d.synTab;
+		fftFast<+1, R3, false>(lds, d.twA4, d.twB4, loadBin,
+			[&](int m, int) { // everything an output needs from memory in ONE 16-byte load (twiddle + its two window samples),
+				// requested for all of a thread's outputs before the first store
+				return synTab[m];
+			},
+			[&](int m, float2 u, float4 r, int) { storeWindowed(frame, m, u, r, B, H); });
 	}
-	const float4 *__restrict__ synTab = d.synTab;
-	fftFast<+1, R3, false>(lds, d.twA4, d.twB4,
-		[&](int j, int) {
-			// one load at a selected address, conjugated afterwards: with a load in each arm of the conditional the
-			// compiler emitted 16 loads each followed by s_waitcnt vmcnt(0) -- sixteen memory round trips per FFT
-			const int kk = 2*j;
-			const bool upper = kk >= H;
-			float2 v = X[upper ? N - 1 - kk : kk];
-			if (upper) v.y = -v.y;
-			return v;
-		},
-		[&](int m, int) { // everything an output needs from memory in ONE 16-byte load (twiddle + its two window samples),
-			// requested for all of a thread's outputs before the first store
-			return synTab[m];
-		},
-		[&](int m, float2 u, float4 r, int) {
-			const float2 v = cmulcPlain(u, make_float2(r.x, r.y)); // * e^{+i pi m / N}
-			if (m < B - halfB) frame[m + halfB] = (2*v.x)*r.z;
-			if (m >= H - halfB) frame[m - H + halfB] = (2*v.y)*r.w;
-		});
 }
 
 // K4a by persistent teams (see kAnalyseTeams): kSynthFast's transform with kAnalyseTeams' organisation -- the (twiddle, window) table of
 // the outputs and the stage twiddles sit in LDS, a team synthesises frame after frame at its own pace.  Bit-identical to kSynthFast.
 template <int R3, int TEAMS>
 __global__ __launch_bounds__(256*TEAMS) void kSynthTeams(DevBatch d, const HopDesc *__restrict__ hopTable, int sBase, int hopBase, int tileHops, int nStreams) {
-	static_assert(16*R3 <= 256, "a team is 256 threads");
 	extern __shared__ __attribute__((aligned(16))) unsigned char smemRaw[];
-	constexpr int MA = 16*R3, H = 256*R3, N = 2*H;
-	const int team = __builtin_amdgcn_readfirstlane(threadIdx.x >> 8), t = threadIdx.x & 255;
-	const int B = d.B, halfB = B/2;
+	constexpr int H = 256*R3, N = 2*H;
+	const int B = d.B;
 	const int total = tileHops*d.C*nStreams;
-	float4 *synLds = reinterpret_cast<float4 *>(smemRaw); // (e^{+i pi m/N}, the two window samples of output m)
-	float4 *twALds = synLds + H;
-	float4 *twBLds = twALds + 8*MA;
-	float2 *lds = reinterpret_cast<float2 *>(twBLds + 8*R3) + (size_t)team*(H + H/16);
-	volatile int *words = reinterpret_cast<volatile int *>(reinterpret_cast<float2 *>(twBLds + 8*R3) + (size_t)TEAMS*(H + H/16));
-	for (int i = threadIdx.x; i < H; i += blockDim.x) synLds[i] = d.synTab[i];
-	for (int i = threadIdx.x; i < 8*MA; i += blockDim.x) twALds[i] = d.twA4[i];
-	for (int i = threadIdx.x; i < 8*R3; i += blockDim.x) twBLds[i] = d.twB4[i];
-	if (threadIdx.x < 16) words[threadIdx.x] = 0;
-	__syncthreads();
-	int generation = 0;
-	const TeamSync sync{words + team, &generation};
+	TeamWorkgroup<R3, TEAMS> wg(smemRaw, d, d.synTab); // table: (e^{-i pi m/N}, the two window samples of output m)
+	const TeamSync sync = wg.sync();
 	const int stride = gridDim.x*TEAMS;
-	for (int lin = blockIdx.x + gridDim.x*team; lin < total; lin += stride) {
+	for (int lin = blockIdx.x + gridDim.x*wg.team; lin < total; lin += stride) {
 		const BlockCoord bc = xcdAwareCoord(lin, tileHops, d.C, nStreams); // x: hop, y: channel
 		const HopDesc hd = hopTable[(size_t)(sBase + bc.s)*d.hopStride + hopBase + bc.x];
 		if (!(hd.flags & HOP_ACTIVE)) continue;
 		const float2 *X = d.OUT + rowOf(d, bc.s, bc.x, bc.y);
-		float *__restrict__ frame = d.frames + ((size_t)((size_t)bc.s*d.T + bc.x)*d.C + bc.y)*(size_t)B;
-		fftFast<+1, R3, false>(lds, twALds, twBLds,
-			[&](int j, int) { // one load at a selected address, conjugated afterwards (see kSynthFast)
-				const int kk = 2*j;
-				const bool upper = kk >= H;
-				float2 v = X[upper ? N - 1 - kk : kk];
-				if (upper) v.y = -v.y;
-				return v;
-			},
-			[&](int m, int) { return synLds[m]; },
-			[&](int m, float2 u, float4 r, int) {
-				const float2 v = cmulcPlain(u, make_float2(r.x, r.y)); // * e^{+i pi m / N}
-				if (m < B - halfB) frame[m + halfB] = (2*v.x)*r.z;
-				if (m >= H - halfB) frame[m - H + halfB] = (2*v.y)*r.w;
-			}, t, sync);
+		float *__restrict__ frame = frameOf(d, bc.s, bc.x, bc.y);
+		fftFast<+1, R3, false>(wg.lds, wg.twA, wg.twB,
+			[&](int j, int) { return loadHalfBin(X, j, H, N); },
+			[&](int m, int) { return wg.table[m]; },
+			[&](int m, float2 u, float4 r, int) { storeWindowed(frame, m, u, r, B, H); }, wg.t, sync);
 		sync(); // the last stage's LDS reads, before the next frame's first-stage writes
 	}
 }
 
+// The carried front of the overlap-add under sample i of a tile (counted from where the carry begins): what the previous tile left -- sums per
+// channel (`row`: the index of the row's first carried entry), window products per stream -- and behind it what an empty ring position holds
+__device__ __forceinline__ float carriedSumAt(const DevBatch &d, size_t row, int i) { return i < d.carryLen ? loadCarrySum(d, d.carryCur, row + i) : 0.0f; }
+__device__ __forceinline__ float carriedProductAt(const DevBatch &d, const float *__restrict__ carryWpOld, int i) { return i < d.carryLen ? carryWpOld[i] : 1e-30f; }
+// The frames q with pos_q <= n < pos_q + B, pos_q = firstHopPos + q*I + delta, that cover any of the samples relFirst .. relLast
+// (rel = n - firstHopPos - delta) among a tile's hopCount frames: empty where hi < lo
+struct FrameRange { int lo, hi; };
+__device__ __forceinline__ FrameRange coveringFrames(int relFirst, int relLast, int B, int I, int hopCount) {
+	FrameRange r;
+	r.hi = (relLast >= 0) ? relLast/I : -1;
+	r.lo = (relFirst - B + 1 > 0) ? (relFirst - B + 1 + I - 1)/I : 0;
+	if (r.hi > hopCount - 1) r.hi = hopCount - 1;
+	return r;
+}
 // The window-product sum under output sample i of a tile (i counted from the tile's first sample): what the carry holds there, then
 // the covering frames' products oldest first -- kEmit's sum, term for term.
 __device__ __forceinline__ float windowProductAt(const DevBatch &d, const EmitDesc &ed, const float *__restrict__ carryWpOld, int i) {
-	float wp = i < d.carryLen ? carryWpOld[i] : 1e-30f;
+	float wp = carriedProductAt(d, carryWpOld, i);
 	if (ed.hopCount > 0) {
-		const int rel = ed.nLo + i - ed.firstHopPos - d.delta, B = d.B, I = d.I;
-		int qHi = rel >= 0 ? rel/I : -1;
-		const int qLo = (rel - B + 1 > 0) ? (rel - B + 1 + I - 1)/I : 0;
-		if (qHi > ed.hopCount - 1) qHi = ed.hopCount - 1;
-		for (int q = qLo; q <= qHi; ++q) wp += d.wprod[rel - q*I];
+		const int rel = ed.nLo + i - ed.firstHopPos - d.delta;
+		const FrameRange q = coveringFrames(rel, rel, d.B, d.I, ed.hopCount);
+		for (int k = q.lo; k <= q.hi; ++k) wp += d.wprod[rel - k*d.I];
 	}
 	return wp;
 }
@@ -639,20 +638,11 @@ template <int R3, int QN, int SLOTS, bool SPLIT>
 __global__ __launch_bounds__(512) void kSynthEmitTeams(DevBatch d, IoArgs io, int sBase, int tileIndex, int nStreams) {
 	constexpr int TEAMS = 2, MA = 16*R3, H = 256*R3, N = 2*H, NI = QN + 1, DQ = SPLIT ? 1 : 0;
 	extern __shared__ __attribute__((aligned(16))) unsigned char smemRaw[];
-	const int team = __builtin_amdgcn_readfirstlane(threadIdx.x >> 8), t = threadIdx.x & 255;
-	const int B = d.B, halfB = B/2, I = d.I, CL = d.carryLen;
-	float4 *synLds = reinterpret_cast<float4 *>(smemRaw); // (e^{+i pi m/N}, the two window samples of output m)
-	float4 *twALds = synLds + H;
-	float4 *twBLds = twALds + 8*MA;
-	float2 *lds = reinterpret_cast<float2 *>(twBLds + 8*R3) + (size_t)team*(H + H/16);
-	volatile int *words = reinterpret_cast<volatile int *>(reinterpret_cast<float2 *>(twBLds + 8*R3) + (size_t)TEAMS*(H + H/16));
-	for (int i = threadIdx.x; i < H; i += blockDim.x) synLds[i] = d.synTab[i];
-	for (int i = threadIdx.x; i < 8*MA; i += blockDim.x) twALds[i] = d.twA4[i];
-	for (int i = threadIdx.x; i < 8*R3; i += blockDim.x) twBLds[i] = d.twB4[i];
-	if (threadIdx.x < 16) words[threadIdx.x] = 0;
-	__syncthreads();
-	int generation = 0;
-	const TeamSync sync{words + team, &generation};
+	const int B = d.B, I = d.I, CL = d.carryLen;
+	TeamWorkgroup<R3, TEAMS> wg(smemRaw, d, d.synTab); // table: (e^{-i pi m/N}, the two window samples of output m)
+	const TeamSync sync = wg.sync();
+	const int team = wg.team, t = wg.t;
+	float2 *lds = wg.lds;
 	float *ex = reinterpret_cast<float *>(lds); // the frame, B floats, in the transform buffer
 	float steady[SLOTS]; // the window products under a sample that only this tile's frames cover: oldest frame first, as the ring sums them
 #pragma unroll
@@ -671,29 +661,27 @@ __global__ __launch_bounds__(512) void kSynthEmitTeams(DevBatch d, IoArgs io, in
 		const EmitDesc ed = d.emit[(size_t)sg*d.emitStride + tileIndex];
 		const int cnt = ed.hopCount, span = ed.nHi - ed.nLo;
 		const int carryFrom = d.carryBase[d.carryCur][sg];
-		const size_t carryRow = carrySumRow(d, sg, c);
+		const size_t carryRow = carrySumRow(d, sg, c), carried = carryRow + carryFrom; // the new carry's row, the old carry's first entry
 		const float *wpOld = d.carryWp[d.carryCur] + carryWpRow(d, sg) + carryFrom;
 		const float *wpHead = d.wpHead + (size_t)sg*d.wpHeadLen; // (kEmitProducts; it also writes the new carry's products)
 		float *out = io.out + (size_t)sg*io.outStreamStride + (size_t)c*io.outChannelStride;
-		auto carryAt = [&](int i) { return i < CL ? loadCarrySum(d, d.carryCur, carryRow + carryFrom + i) : 0.0f; };
-		auto wpAt = [&](int i) { return i < CL ? wpOld[i] : 1e-30f; };
 		auto place = [&](int n, float sum, float wp) { // output sample n of the call: final, or part of what the next tile starts from
 			if (n < ed.nHi) out[n] = sum/wp;
 			else if (n - ed.nHi < CL) storeCarrySum(d, d.carryCur ^ 1, carryRow + (n - ed.nHi), sum);
 		};
 		if (cnt == 0) { // nothing synthesised for this stream in this tile: the carried sums are emitted / move up
-			for (int i = t; i < span + CL; i += 256) place(ed.nLo + i, carryAt(i), wpAt(i));
+			for (int i = t; i < span + CL; i += 256) place(ed.nLo + i, carriedSumAt(d, carried, i), carriedProductAt(d, wpOld, i));
 			continue;
 		}
 		const int off = ed.firstHopPos - ed.nLo; // samples in front of the tile's first hop (the first tile of a call only)
-		for (int i = t; i < off; i += 256) place(ed.nLo + i, carryAt(i), wpAt(i));
+		for (int i = t; i < off; i += 256) place(ed.nLo + i, carriedSumAt(d, carried, i), carriedProductAt(d, wpOld, i));
 		float acc[NI][SLOTS];
 #pragma unroll
 		for (int u = 0; u < NI; ++u) {
 #pragma unroll
 			for (int slot = 0; slot < SLOTS; ++slot) {
 				const int r = 256*slot + t, i = off + u*I + r;
-				acc[u][slot] = r < I ? carryAt(i) : 0.0f;
+				acc[u][slot] = r < I ? carriedSumAt(d, carried, i) : 0.0f;
 			}
 		}
 		// (waited for HERE: a register that is still "being loaded" when the hop loop is entered makes the compiler wait for ALL loads at
@@ -777,7 +765,7 @@ __global__ __launch_bounds__(512) void kSynthEmitTeams(DevBatch d, IoArgs io, in
 			const float2 *X = d.OUT + rowOf(d, s, q, c);
 			if (t < MA) {
 #pragma unroll
-				for (int k = 0; k < 16; ++k) { const int kk = 2*(t + MA*k); asyncLoad8(next[k], X + (kk >= H ? N - 1 - kk : kk)); } // one load at a selected address (see kSynthFast) ...
+				for (int k = 0; k < 16; ++k) asyncLoad8(next[k], X + halfBinIndex(t + MA*k, H, N)); // one load at a selected address (see loadHalfBin) ...
 			}
 		};
 		auto landed = [&]() { // at the END of a hop, in front of the back-edge: nothing of the compiler's may touch a register in flight
@@ -788,14 +776,10 @@ __global__ __launch_bounds__(512) void kSynthEmitTeams(DevBatch d, IoArgs io, in
 		request(0);
 		landed();
 		for (int q = 0; q < cnt; ++q) {
-			fftFast<+1, R3, false, 2>(lds, twALds, twBLds, // (two rounds of prepared outputs: the ring and the next spectrum need the registers)
+			fftFast<+1, R3, false, 2>(lds, wg.twA, wg.twB, // (two rounds of prepared outputs: the ring and the next spectrum need the registers)
 				[&](int, int k) { return asyncValue(next[k]); },
-				[&](int m, int) { return synLds[m]; },
-				[&](int m, float2 u, float4 r, int) {
-					const float2 v = cmulcPlain(u, make_float2(r.x, r.y)); // * e^{+i pi m / N}
-					if (m < B - halfB) ex[m + halfB] = (2*v.x)*r.z;
-					if (m >= H - halfB) ex[m - H + halfB] = (2*v.y)*r.w;
-				}, t, sync, sync,
+				[&](int m, int) { return wg.table[m]; },
+				[&](int m, float2 u, float4 r, int) { storeWindowed(ex, m, u, r, B, H); }, t, sync, sync,
 				[&]() {
 					if (q > 0) overlapAdd();
 					sync(); // the previous frame has been read (or the previous item's last one), before this transform's first-stage writes
@@ -878,8 +862,7 @@ __global__ __launch_bounds__(256) void kAnalyse(DevBatch d, IoArgs io, int sBase
 	const int which = bc.y & 1; // 0: current window, 1: window one interval earlier
 	const int s = bc.s;
 	const HopDesc hd = d.hops[(size_t)(sBase + s)*d.hopStride + hopBase + k];
-	if (!(hd.flags & HOP_ACTIVE) || !(hd.flags & HOP_NEW_SPECTRUM) || (hd.flags & HOP_PREANALYSED)) return;
-	if (which == 1 && !(hd.flags & HOP_REANALYSE_PREV)) return;
+	if (!hopWantsAnalysis(hd, which)) return;
 
 	const int B = d.B, H = d.M, halfB = B/2;
 	const int base = hd.inputOffset - (which ? d.I : 0) - B; // index of block element 0 in the call's input
@@ -913,12 +896,7 @@ __global__ __launch_bounds__(256) void kAnalyse(DevBatch d, IoArgs io, int sBase
 		res = bufA;
 	}
 	const int N = d.N;
-	for (int j = threadIdx.x; j < H; j += blockDim.x) {
-		float2 u = res[j];
-		int kk = 2*j;
-		if (kk < H) dst[kk] = u;
-		else dst[N - 1 - kk] = cconj(u);
-	}
+	for (int j = threadIdx.x; j < H; j += blockDim.x) storeHalfBin(dst, j, res[j], H, N);
 }
 
 // ------------------------------------------------------------------------------------------------------
@@ -937,24 +915,14 @@ __global__ __launch_bounds__(256) void kSynth(DevBatch d, int sBase, int hopBase
 	if (!(hd.flags & HOP_ACTIVE)) return;
 	const int B = d.B, H = d.M, N = d.N, halfB = B/2;
 	const float2 *X = d.OUT + rowOf(d, s, k, c);
-	for (int j = threadIdx.x; j < H; j += blockDim.x) {
-		int kk = 2*j;
-		bufA[j] = (kk < H) ? X[kk] : cconj(X[N - 1 - kk]);
-	}
+	for (int j = threadIdx.x; j < H; j += blockDim.x) bufA[j] = loadHalfBin(X, j, H, N);
 	__syncthreads();
 	float2 *res = fftLds<+1>(bufA, bufB, d.plan, d.twH);
-	float *frame = d.frames + ((size_t)((size_t)s*d.T + k)*d.C + c)*(size_t)B;
+	float *frame = frameOf(d, s, k, c);
 	const float *__restrict__ win = d.window;
 	for (int m = threadIdx.x; m < H; m += blockDim.x) {
-		float2 v = cmulcPlain(res[m], d.halfTw[m]); // * e^{+i pi m / N}
-		if (m < B - halfB) {
-			int i = m + halfB;
-			frame[i] = (2*v.x)*win[i];
-		}
-		if (m >= H - halfB) {
-			int i = m - H + halfB;
-			frame[i] = (2*v.y)*win[i];
-		}
+		const float wRe = (m < B - halfB) ? win[m + halfB] : 0.0f, wIm = (m >= H - halfB) ? win[m - H + halfB] : 0.0f; // (the absent halves are not stored)
+		storeWindowed(frame, m, res[m], d.halfTw[m], wRe, wIm, B, H);
 	}
 }
 
@@ -990,16 +958,15 @@ __global__ __launch_bounds__(256) void kEmit(DevBatch d, IoArgs io, int sBase, i
 #pragma unroll
 		for (int j = 0; j < 4; ++j) {
 			const int i = i0 + j;
-			sum[j] = (i < CL) ? loadCarrySum(d, d.carryCur, carryRow + carryFrom + i) : 0.0f;
-			wp[j] = (i < CL) ? carryWpOld[i] : 1e-30f;
+			sum[j] = carriedSumAt(d, carryRow + carryFrom, i);
+			wp[j] = carriedProductAt(d, carryWpOld, i);
 		}
 	}
 	if (ed.hopCount > 0) {
 		// frames q with pos_q <= n < pos_q + B, pos_q = firstHopPos + q*I + delta; summed in ascending q per sample
 		const int rel0 = ed.nLo + i0 - ed.firstHopPos - d.delta;
-		int qHi = (rel0 + 3 >= 0) ? (rel0 + 3)/I : -1;
-		const int qLo = (rel0 - B + 1 > 0) ? (rel0 - B + 1 + I - 1)/I : 0;
-		if (qHi > ed.hopCount - 1) qHi = ed.hopCount - 1;
+		const FrameRange cover = coveringFrames(rel0, rel0 + 3, B, I, ed.hopCount);
+		const int qLo = cover.lo, qHi = cover.hi;
 		// all covering frames' loads are issued before the first addition (a loop with a load per iteration costs one
 		// memory round trip per frame); the additions then run in ascending q, the order the reference sums in
 		float4 f[KMAX], w[KMAX];
@@ -1008,7 +975,7 @@ __global__ __launch_bounds__(256) void kEmit(DevBatch d, IoArgs io, int sBase, i
 		for (int k = 0; k < KMAX; ++k) {
 			const int q = qLo + k, idx0 = rel0 - q*I;
 			fast[k] = q <= qHi && idx0 >= 0 && idx0 + 3 < B;
-			const float *frame = d.frames + ((size_t)((size_t)s*d.T + (fast[k] ? q : 0))*d.C + c)*(size_t)B;
+			const float *frame = frameOf(d, s, fast[k] ? q : 0, c);
 			f[k] = *reinterpret_cast<const float4 *>(frame + (fast[k] ? idx0 : 0));
 			w[k] = *reinterpret_cast<const float4 *>(d.wprod + (fast[k] ? idx0 : 0));
 		}
@@ -1019,7 +986,7 @@ __global__ __launch_bounds__(256) void kEmit(DevBatch d, IoArgs io, int sBase, i
 				sum[0] += f[k].x; sum[1] += f[k].y; sum[2] += f[k].z; sum[3] += f[k].w;
 				wp[0] += w[k].x; wp[1] += w[k].y; wp[2] += w[k].z; wp[3] += w[k].w;
 			} else if (q <= qHi) { // a group that straddles a frame edge
-				const float *frame = d.frames + ((size_t)((size_t)s*d.T + q)*d.C + c)*(size_t)B;
+				const float *frame = frameOf(d, s, q, c);
 #pragma unroll
 				for (int j = 0; j < 4; ++j) {
 					const int idx = idx0 + j;
@@ -1029,7 +996,7 @@ __global__ __launch_bounds__(256) void kEmit(DevBatch d, IoArgs io, int sBase, i
 		}
 		for (int q = qLo + KMAX; q <= qHi; ++q) { // more than KMAX covering frames (block/interval > 5): plain loop
 			const int idx0 = rel0 - q*I;
-			const float *frame = d.frames + ((size_t)((size_t)s*d.T + q)*d.C + c)*(size_t)B;
+			const float *frame = frameOf(d, s, q, c);
 #pragma unroll
 			for (int j = 0; j < 4; ++j) {
 				const int idx = idx0 + j;
@@ -1060,14 +1027,13 @@ __global__ __launch_bounds__(256) void kEmit(DevBatch d, IoArgs io, int sBase, i
 __global__ __launch_bounds__(256) void kEmitCarried(DevBatch d, IoArgs io) {
 	const int sg = blockIdx.x;
 	const EmitDesc ed = d.emit[(size_t)sg*d.emitStride];
-	const int span = ed.nHi - ed.nLo, CL = d.carryLen, from = d.carryBase[d.carryCur][sg];
+	const int span = ed.nHi - ed.nLo, from = d.carryBase[d.carryCur][sg];
 	const float *wpRow = d.carryWp[d.carryCur] + carryWpRow(d, sg) + from;
 	for (int c = 0; c < d.C; ++c) {
 		const size_t row = carrySumRow(d, sg, c) + from;
 		float *out = io.out + (size_t)sg*io.outStreamStride + (size_t)c*io.outChannelStride + ed.nLo;
 		for (int i = threadIdx.x; i < span; i += blockDim.x) {
-			const float sum = (i < CL) ? loadCarrySum(d, d.carryCur, row + i) : 0.0f, wp = (i < CL) ? wpRow[i] : 1e-30f;
-			out[i] = sum/wp;
+			out[i] = carriedSumAt(d, row, i)/carriedProductAt(d, wpRow, i);
 		}
 	}
 	__syncthreads();
@@ -1082,66 +1048,76 @@ void launchEnergy(const DevBatch &d, const IoArgs &io, int sBase, int nStreams, 
 	const int parts = std::max(1, std::min(kEnergyParts, maxSamples/1024));
 	hipLaunchKernelGGL(kEnergy, dim3(nStreams, parts), dim3(256), 256*sizeof(float), st, d, io, sBase, energyOut);
 }
+// f(R3 = M/256 as a compile-time constant) where M/256 is one of R3S; false, and f not called, at any other size
+template <int... R3S, typename F>
+static bool withR3(int M, F f) { return ((M == 256*R3S && (f(std::integral_constant<int, R3S>()), true)) || ...); }
+// The register-blocked kernels exist at four sizes (isFastSize), the team kernels at the two whose stages A and B fit a team's 256 threads
+template <typename F> static bool withFastR3(int M, F f) { return withR3<10, 12, 20, 24>(M, f); }
+template <typename F> static bool withTeamR3(int M, F f) { return withR3<10, 12>(M, f); }
+template <typename F>
+static void withFlag(bool flag, F f) { // f(flag as a compile-time constant)
+	if (flag) f(std::true_type()); else f(std::false_type());
+}
+static size_t fastLdsBytes(int M) { return ((size_t)M + M/16)*sizeof(float2); } // fftFast's padded buffer
+static size_t teamLdsBytes(int M, int teams) { // TeamWorkgroup: element table, first- and second-stage twiddles, a buffer per team, barrier words
+	return ((size_t)M + M/2 + M/32)*sizeof(float4) + teams*fastLdsBytes(M) + 64;
+}
+static bool fastApplies(const DevBatch &d) { return !d.noFastFft && isFastSize(d.M); }
+// (asks withTeamR3 itself, so a launcher that finds the teams to apply always has a team kernel to launch)
+static bool teamsAvailable(const DevBatch &d) { return fastApplies(d) && withTeamR3(d.M, [](auto) {}) && d.fftTeams && !d.fftLean; }
+// persistent teams pay a 76-KB table copy per workgroup: only where every team gets a few frames
+static bool teamsApply(const DevBatch &d, int jobs) { return teamsAvailable(d) && (d.fftTeams == 2 || jobs >= 6*d.teamsGrid); }
+static int teamsWorkgroups(const DevBatch &d, int jobs) { // three teams each: one workgroup per CU, a multiple of 8 (one residue class of the job order per XCD)
+	return std::max(8, std::min((jobs + 2)/3/8*8, d.teamsGrid));
+}
+// kSynthEmitTeams' shape: the presets' block / interval ratios (2.5 and 4)
+constexpr int synthEmitQN(int R3) { return R3 == 10 ? 3 : 4; }
+constexpr int synthEmitSlots(int R3) { return R3 == 10 ? 8 : 6; }
+
 void launchAnalyse(const DevBatch &d, const IoArgs &io, int sBase, int nStreams, int hopBase, int tileHops, bool anyInCall, bool anyLate, hipStream_t st) {
 	const dim3 grid(tileHops, d.C*2, nStreams);
-	const size_t fastLds = ((size_t)d.M + d.M/16)*sizeof(float2);
-	// persistent teams pay a 76-KB table copy per workgroup: only where every team gets a few frames
-	const bool teams = !d.noFastFft && d.fftTeams && !d.fftLean && anyInCall && (d.M == 256*10 || d.M == 256*12) && (d.fftTeams == 2 || tileHops*d.C*2*nStreams >= 6*d.teamsGrid);
+	const int jobs = tileHops*d.C*2*nStreams;
+	const bool teams = anyInCall && teamsApply(d, jobs);
 	if (teams) {
-		const int jobs = tileHops*d.C*2*nStreams;
-		const int wgs = std::max(8, std::min((jobs + 2)/3/8*8, d.teamsGrid)); // one workgroup per CU, a multiple of 8 (one residue class of the job order per XCD)
-		const size_t lds = ((size_t)d.M + d.M/2 + d.M/32)*sizeof(float4) + 3*fastLds + 64; // window, first- and second-stage twiddles, a buffer per team, barrier words
 		const WindowPad pad = windowPad(d.B, d.M);
-		const bool slots = pad.lo == 0 && pad.hi == 0;
-		if (d.M == 256*10) {
-			if (slots) hipLaunchKernelGGL((kAnalyseTeams<10, 3, true>), dim3(wgs), dim3(768), lds, st, d, io, d.hops, sBase, hopBase, tileHops, nStreams);
-			else hipLaunchKernelGGL((kAnalyseTeams<10, 3, false>), dim3(wgs), dim3(768), lds, st, d, io, d.hops, sBase, hopBase, tileHops, nStreams);
-		} else {
-			if (slots) hipLaunchKernelGGL((kAnalyseTeams<12, 3, true>), dim3(wgs), dim3(768), lds, st, d, io, d.hops, sBase, hopBase, tileHops, nStreams);
-			else hipLaunchKernelGGL((kAnalyseTeams<12, 3, false>), dim3(wgs), dim3(768), lds, st, d, io, d.hops, sBase, hopBase, tileHops, nStreams);
-		}
+		withTeamR3(d.M, [&](auto r3) { withFlag(pad.lo == 0 && pad.hi == 0, [&](auto exact) {
+			hipLaunchKernelGGL((kAnalyseTeams<r3.value, 3, exact.value>), dim3(teamsWorkgroups(d, jobs)), dim3(768), teamLdsBytes(d.M, 3), st, d, io, d.hops, sBase, hopBase, tileHops, nStreams);
+		}); });
 		countLaunch(LK_ANALYSE_TEAMS);
 		if (!anyLate) return;
 	}
 	const int lateOnly = teams ? 1 : 0; // the frames whose windows reach into the carried history
-	if (!d.noFastFft && d.M%256 == 0 && (d.M/256 == 10 || d.M/256 == 12 || d.M/256 == 20 || d.M/256 == 24)) countLaunch(LK_ANALYSE_FAST); else countLaunch(LK_ANALYSE_GENERIC);
-	if (!d.noFastFft) { // every preset: presetCheaper at 44.1 / 48 kHz, presetDefault at 44.1 / 48 kHz, presetCheaper at 88.2 / 96 kHz, presetDefault at 88.2 / 96 kHz
-		if (d.M == 256*10) { if (d.fftLean) hipLaunchKernelGGL((kAnalyseFast<10, true>), grid, dim3(256), fastLds, st, d, io, sBase, hopBase, lateOnly); else hipLaunchKernelGGL((kAnalyseFast<10, false>), grid, dim3(256), fastLds, st, d, io, sBase, hopBase, lateOnly); return; }
-		if (d.M == 256*12) { if (d.fftLean) hipLaunchKernelGGL((kAnalyseFast<12, true>), grid, dim3(256), fastLds, st, d, io, sBase, hopBase, lateOnly); else hipLaunchKernelGGL((kAnalyseFast<12, false>), grid, dim3(256), fastLds, st, d, io, sBase, hopBase, lateOnly); return; }
-		if (d.M == 256*20) { if (d.fftLean) hipLaunchKernelGGL((kAnalyseFast<20, true>), grid, dim3(320), fastLds, st, d, io, sBase, hopBase, lateOnly); else hipLaunchKernelGGL((kAnalyseFast<20, false>), grid, dim3(320), fastLds, st, d, io, sBase, hopBase, lateOnly); return; }
-		if (d.M == 256*24) { if (d.fftLean) hipLaunchKernelGGL((kAnalyseFast<24, true>), grid, dim3(384), fastLds, st, d, io, sBase, hopBase, lateOnly); else hipLaunchKernelGGL((kAnalyseFast<24, false>), grid, dim3(384), fastLds, st, d, io, sBase, hopBase, lateOnly); return; }
-	}
+	countLaunch(fastApplies(d) ? LK_ANALYSE_FAST : LK_ANALYSE_GENERIC);
+	// every preset: presetCheaper at 44.1 / 48 kHz, presetDefault at 44.1 / 48 kHz, presetCheaper at 88.2 / 96 kHz, presetDefault at 88.2 / 96 kHz
+	if (!d.noFastFft && withFastR3(d.M, [&](auto r3) { withFlag(d.fftLean != 0, [&](auto lean) {
+			hipLaunchKernelGGL((kAnalyseFast<r3.value, lean.value>), grid, dim3(fastBlockThreads(r3.value)), fastLdsBytes(d.M), st, d, io, sBase, hopBase, lateOnly);
+		}); })) return;
 	size_t lds = 2*(size_t)d.M*sizeof(float2);
 	if (fftNeedsScratch(d.M)) hipLaunchKernelGGL(kAnalyse<true>, grid, dim3(256), lds/2, st, d, io, sBase, hopBase);
 	else hipLaunchKernelGGL(kAnalyse<false>, grid, dim3(256), lds, st, d, io, sBase, hopBase);
 }
 void launchSynth(const DevBatch &d, int sBase, int nStreams, int hopBase, int tileHops, hipStream_t st) {
 	const dim3 grid(tileHops, d.C, nStreams);
-	const size_t fastLds = ((size_t)d.M + d.M/16)*sizeof(float2);
-	if (!d.noFastFft && d.fftTeams && !d.fftLean && (d.M == 256*10 || d.M == 256*12) && (d.fftTeams == 2 || tileHops*d.C*nStreams >= 6*d.teamsGrid)) {
-		const int jobs = tileHops*d.C*nStreams;
-		const int wgs = std::max(8, std::min((jobs + 2)/3/8*8, d.teamsGrid));
-		const size_t lds = ((size_t)d.M + d.M/2 + d.M/32)*sizeof(float4) + 3*fastLds + 64;
-		if (d.M == 256*10) hipLaunchKernelGGL((kSynthTeams<10, 3>), dim3(wgs), dim3(768), lds, st, d, d.hops, sBase, hopBase, tileHops, nStreams);
-		else hipLaunchKernelGGL((kSynthTeams<12, 3>), dim3(wgs), dim3(768), lds, st, d, d.hops, sBase, hopBase, tileHops, nStreams);
+	const int jobs = tileHops*d.C*nStreams;
+	if (teamsApply(d, jobs)) {
+		withTeamR3(d.M, [&](auto r3) {
+			hipLaunchKernelGGL((kSynthTeams<r3.value, 3>), dim3(teamsWorkgroups(d, jobs)), dim3(768), teamLdsBytes(d.M, 3), st, d, d.hops, sBase, hopBase, tileHops, nStreams);
+		});
 		countLaunch(LK_SYNTH_TEAMS);
 		return;
 	}
-	if (!d.noFastFft && d.M%256 == 0 && (d.M/256 == 10 || d.M/256 == 12 || d.M/256 == 20 || d.M/256 == 24)) countLaunch(LK_SYNTH_FAST); else countLaunch(LK_SYNTH_GENERIC);
-	if (!d.noFastFft) {
-		if (d.M == 256*10) { if (d.fftLean) hipLaunchKernelGGL((kSynthFast<10, true>), grid, dim3(256), fastLds, st, d, sBase, hopBase); else hipLaunchKernelGGL((kSynthFast<10, false>), grid, dim3(256), fastLds, st, d, sBase, hopBase); return; }
-		if (d.M == 256*12) { if (d.fftLean) hipLaunchKernelGGL((kSynthFast<12, true>), grid, dim3(256), fastLds, st, d, sBase, hopBase); else hipLaunchKernelGGL((kSynthFast<12, false>), grid, dim3(256), fastLds, st, d, sBase, hopBase); return; }
-		if (d.M == 256*20) { if (d.fftLean) hipLaunchKernelGGL((kSynthFast<20, true>), grid, dim3(320), fastLds, st, d, sBase, hopBase); else hipLaunchKernelGGL((kSynthFast<20, false>), grid, dim3(320), fastLds, st, d, sBase, hopBase); return; }
-		if (d.M == 256*24) { if (d.fftLean) hipLaunchKernelGGL((kSynthFast<24, true>), grid, dim3(384), fastLds, st, d, sBase, hopBase); else hipLaunchKernelGGL((kSynthFast<24, false>), grid, dim3(384), fastLds, st, d, sBase, hopBase); return; }
-	}
+	countLaunch(fastApplies(d) ? LK_SYNTH_FAST : LK_SYNTH_GENERIC);
+	if (!d.noFastFft && withFastR3(d.M, [&](auto r3) { withFlag(d.fftLean != 0, [&](auto lean) {
+			hipLaunchKernelGGL((kSynthFast<r3.value, lean.value>), grid, dim3(fastBlockThreads(r3.value)), fastLdsBytes(d.M), st, d, sBase, hopBase);
+		}); })) return;
 	size_t lds = 2*(size_t)d.M*sizeof(float2);
 	if (fftNeedsScratch(d.M)) hipLaunchKernelGGL(kSynth<true>, grid, dim3(256), lds/2, st, d, sBase, hopBase);
 	else hipLaunchKernelGGL(kSynth<false>, grid, dim3(256), lds, st, d, sBase, hopBase);
 }
 bool synthEmitApplies(const DevBatch &d, int nStreams, int tileHops) {
-	if (d.noFastFft || !d.fftTeams || d.fftLean || !d.synthEmit || !(d.M == 256*10 || d.M == 256*12)) return false;
+	if (!teamsAvailable(d) || !d.synthEmit) return false;
 	if (!(d.delta == 0 || d.delta == d.I)) return false;
-	const int QN = d.M == 256*10 ? 3 : 4, SLOTS = d.M == 256*10 ? 8 : 6; // the presets' block / interval ratios (2.5 and 4)
+	const int QN = synthEmitQN(d.M/256), SLOTS = synthEmitSlots(d.M/256);
 	if (QN*d.I < d.B || d.I > 256*SLOTS || d.B > d.N) return false;
 	// the teams read wpHead[off + q*I + r] for q <= QN, r < I, with off = the samples in front of a tile's first hop (< I: a block begins at
 	// the latest I - 1 samples into a call, smst_engine.cpp): inside the (ceil(B/I) + 2)*I floats per stream only if QN >= ceil(B/I) -- stated, not assumed
@@ -1155,17 +1131,10 @@ void launchEmitProducts(const DevBatch &d, int sBase, int nStreams, int tileInde
 }
 void launchSynthEmit(const DevBatch &d, const IoArgs &io, int sBase, int nStreams, int tileIndex, hipStream_t st) {
 	const int items = nStreams*d.C;
-	const int wgs = std::min(divUp(items, 2), d.teamsGrid);
-	const size_t fastLds = ((size_t)d.M + d.M/16)*sizeof(float2);
-	const size_t lds = ((size_t)d.M + d.M/2 + d.M/32)*sizeof(float4) + 2*fastLds + 64;
-	const bool split = d.delta != 0;
-	if (d.M == 256*10) {
-		if (split) hipLaunchKernelGGL((kSynthEmitTeams<10, 3, 8, true>), dim3(wgs), dim3(512), lds, st, d, io, sBase, tileIndex, nStreams);
-		else hipLaunchKernelGGL((kSynthEmitTeams<10, 3, 8, false>), dim3(wgs), dim3(512), lds, st, d, io, sBase, tileIndex, nStreams);
-	} else {
-		if (split) hipLaunchKernelGGL((kSynthEmitTeams<12, 4, 6, true>), dim3(wgs), dim3(512), lds, st, d, io, sBase, tileIndex, nStreams);
-		else hipLaunchKernelGGL((kSynthEmitTeams<12, 4, 6, false>), dim3(wgs), dim3(512), lds, st, d, io, sBase, tileIndex, nStreams);
-	}
+	const int wgs = std::min(divUp(items, 2), d.teamsGrid); // two teams each
+	withTeamR3(d.M, [&](auto r3) { withFlag(d.delta != 0, [&](auto split) {
+		hipLaunchKernelGGL((kSynthEmitTeams<r3.value, synthEmitQN(r3.value), synthEmitSlots(r3.value), split.value>), dim3(wgs), dim3(512), teamLdsBytes(d.M, 2), st, d, io, sBase, tileIndex, nStreams);
+	}); });
 	countLaunch(LK_SYNTH_EMIT);
 }
 void launchEmit(const DevBatch &d, const IoArgs &io, int sBase, int nStreams, int tileIndex, int maxSpan, hipStream_t st) {

@@ -107,6 +107,9 @@ __device__ __forceinline__ void storeCarrySum(const DevBatch &d, int buf, size_t
 __device__ __forceinline__ size_t rowOf(const DevBatch &d, int s, int k, int c) {
 	return ((size_t)((size_t)s*d.T + k)*d.C + c)*(size_t)d.Mp; // Mp: padded row pitch (keeps lane strides off powers of two)
 }
+__device__ __forceinline__ float *frameOf(const DevBatch &d, int s, int k, int c) { // the synthesised frame of (stream, hop, channel), B samples
+	return d.frames + ((size_t)((size_t)s*d.T + k)*d.C + c)*(size_t)d.B;
+}
 __device__ __forceinline__ size_t stateRow(const DevBatch &d, int sGlobal, int c) {
 	return ((size_t)sGlobal*d.C + c)*(size_t)d.M;
 }

@@ -149,6 +149,36 @@ def case_spectra_and_identity(lib, ref, M, block, channels=2, streams=3, hops=No
     return worst
 
 
+def _one_long_call(lib, ref, M, block, channels, streams, label):
+    """One long call: hops at output indices 0, I, 2I, ... (samplesSinceLast starts past the interval), the last one at K*I, its frame
+    inside the call's own input: both spectra of every stream against the float64 DFT, and the identity.  Returns (worst spectrum, identity)."""
+    pkg = package()
+    b = pkg.StretchBatch(streams, channels, block=block, interval=block//4, lib=lib)
+    B, I, N = b.blockSamples(), b.intervalSamples(), b.fftSamples()
+    assert N == 2*M
+    K = 12
+    n = K*I + 1
+    xs = np.stack([synth_input(s, channels, n, 48000) for s in range(streams)])
+    y = np.asarray(b.process(xs, n))
+    r = ref.RefStretch(0)
+    r.configure(channels, B, I)
+    r.process(xs[0], n)
+    w = r.window()
+    long_worst = (0.0, 0.0)
+    for s in range(streams):
+        want = dft_spectrum(_block_ending(xs[s], K*I, B), w, N)
+        for which in (0, 1):
+            e = _assert_spectrum(b.debug_state(s, which), want, "%s M=%d one call, stream %d state %d" % (label, M, s, which))
+            long_worst = tuple(max(a, c) for a, c in zip(long_worst, e))
+            if s == 0:
+                _assert_spectrum(r.bands_complex(which), want, "%s M=%d one call (checker) state %d" % (label, M, which))
+    lat = b.inputLatency() + b.outputLatency()
+    ident = rel_rms(y[:, :, lat + 2*B:n], xs[:, :, 2*B:n - lat])
+    assert ident <= pc.TOL_EXACT, (label, M, ident)
+    b.close()
+    return long_worst, ident
+
+
 def case_fft_forms_spectra(lib, ref, monkeypatch, M, channels=2, streams=3):
     """At a register-blocked size: per-frame (SMST_FFT_TEAMS=0), team (=2) and generic (SMST_NO_FAST_FFT=1) kernels, each against the
     float64 DFT, at the preset's block (15/8 of the bands: the window leaves the padding the team kernels' element slots need) --
@@ -168,30 +198,7 @@ def case_fft_forms_spectra(lib, ref, monkeypatch, M, channels=2, streams=3):
             monkeypatch.setenv(key, v)
         before = {k: pkg.launch_count(k, lib) for k in names}
         worst = case_spectra_and_identity(lib, ref, M, block, channels, streams, label=form)
-        # one long call: hops at output indices 0, I, 2I, ... (samplesSinceLast starts past the interval), the last one at K*I
-        b = pkg.StretchBatch(streams, channels, block=block, interval=block//4, lib=lib)
-        B, I, N = b.blockSamples(), b.intervalSamples(), b.fftSamples()
-        assert N == 2*M
-        K = 12
-        n = K*I + 1
-        xs = np.stack([synth_input(s, channels, n, 48000) for s in range(streams)])
-        y = np.asarray(b.process(xs, n))
-        r = ref.RefStretch(0)
-        r.configure(channels, B, I)
-        r.process(xs[0], n)
-        w = r.window()
-        long_worst = (0.0, 0.0)
-        for s in range(streams):
-            want = dft_spectrum(_block_ending(xs[s], K*I, B), w, N)
-            for which in (0, 1):
-                e = _assert_spectrum(b.debug_state(s, which), want, "%s M=%d one call, stream %d state %d" % (form, M, s, which))
-                long_worst = tuple(max(a, c) for a, c in zip(long_worst, e))
-                if s == 0:
-                    _assert_spectrum(r.bands_complex(which), want, "%s M=%d one call (checker) state %d" % (form, M, which))
-        lat = b.inputLatency() + b.outputLatency()
-        ident = rel_rms(y[:, :, lat + 2*B:n], xs[:, :, 2*B:n - lat])
-        assert ident <= pc.TOL_EXACT, (form, M, ident)
-        b.close()
+        long_worst, ident = _one_long_call(lib, ref, M, block, channels, streams, form)
         grew = {k: pkg.launch_count(k, lib) - before[k] for k in names}
         if form == "generic":
             ok = grew["analyse_generic"] > 0 and grew["synth_generic"] > 0 and all(grew[k] == 0 for k in names if not k.endswith("generic"))
@@ -206,6 +213,26 @@ def case_fft_forms_spectra(lib, ref, monkeypatch, M, channels=2, streams=3):
     for key in ("SMST_FFT_TEAMS", "SMST_NO_FAST_FFT"):
         monkeypatch.delenv(key, raising=False)
     return results
+
+
+def case_lean_tables_spectra(lib, ref, monkeypatch, M, channels=2, streams=3):
+    """SMST_FFT_TABLES=lean at a register-blocked size, the preset's block, under the same bounds as the full tables: hop-aligned calls
+    (case_spectra_and_identity: every frame reaches into the carried history, the kernels' general path) and one long call (the frames
+    inside the call's input take the usual-case path).  SMST_FFT_TEAMS=2 asks for the team kernels wherever they are allowed, so the
+    launch counts -- the per-frame kernels ran, no team and no generic kernel did -- hold only because the lean tables are in force.
+    Returns the worst figures."""
+    pkg = package()
+    names = ("analyse_fast", "analyse_teams", "analyse_generic", "synth_fast", "synth_teams", "synth_generic", "synth_emit")
+    monkeypatch.setenv("SMST_FFT_TABLES", "lean")
+    monkeypatch.setenv("SMST_FFT_TEAMS", "2")
+    before = {k: pkg.launch_count(k, lib) for k in names}
+    worst = case_spectra_and_identity(lib, ref, M, 15*M//8, channels, streams, label="lean")
+    worst["one_call"], worst["one_call_identity"] = _one_long_call(lib, ref, M, 15*M//8, channels, streams, "lean")
+    grew = {k: pkg.launch_count(k, lib) - before[k] for k in names}
+    monkeypatch.delenv("SMST_FFT_TABLES")
+    monkeypatch.delenv("SMST_FFT_TEAMS")
+    assert grew["analyse_fast"] > 0 and grew["synth_fast"] > 0 and all(grew[k] == 0 for k in names if not k.endswith("_fast")), (M, "lean tables: unexpected FFT kernel forms", grew)
+    return worst
 
 
 # ---------------------------------------------------------------------------------------------------------------

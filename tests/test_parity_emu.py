@@ -264,6 +264,13 @@ def test_fft_forms_spectra_emu(emu, ref, monkeypatch):
     print(gc.case_fft_forms_spectra(emu, ref, monkeypatch, 2560))
 
 
+@pytest.mark.parametrize("M", [2560, 3072])
+def test_lean_tables_spectra_emu(emu, ref, monkeypatch, M):
+    """SMST_FFT_TABLES=lean (generated modulation, six loaded first-stage twiddles) at the two last-stage shapes 2 x 5 and 4 x 3: the
+    per-frame register-blocked kernels run (no team, no generic kernel), and meet the spectrum and identity bounds of the full tables."""
+    print(gc.case_lean_tables_spectra(emu, ref, monkeypatch, M))
+
+
 @pytest.mark.parametrize("C,L", [(1, 1), (2, 1), (1, 9), (2, 8), (3, 6), (3, 14), (5, 30), (2, 62), (9, 15), (16, 14)])
 def test_vertical_step_emu(emu, ref, C, L):
     print(gc.case_vertical_step(emu, ref, C, L))

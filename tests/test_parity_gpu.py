@@ -782,6 +782,12 @@ def test_fft_forms_spectra(hip, ref, monkeypatch, M):
     print(gc.case_fft_forms_spectra(hip, ref, monkeypatch, M))
 
 
+@pytest.mark.parametrize("M", gc.FAST_SIZES)
+def test_lean_tables_spectra(hip, ref, monkeypatch, M):
+    """SMST_FFT_TABLES=lean at every register-blocked size (5120 / 6144: the 4 x 5 and 8 x 3 last stages, outputs prepared in four rounds)."""
+    print(gc.case_lean_tables_spectra(hip, ref, monkeypatch, M))
+
+
 @pytest.mark.parametrize("C,L", [(c, l) for l in sorted(gc.STEP_GEOMETRIES) for c in gc.SWEEP_CHANNELS if l <= gc.expected_limit(c)])
 def test_vertical_step(hip, ref, C, L):
     print(gc.case_vertical_step(hip, ref, C, L))

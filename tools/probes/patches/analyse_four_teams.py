@@ -8,15 +8,9 @@ def rep(old, new, count=1):
     global s
     assert s.count(old) == count, (s.count(old), old)
     s = s.replace(old, new)
-i = s.index('void kAnalyseTeams(')
-j = s.index('void kSynthFast(')
-k = s[i:j]
-old = "float2 *lds = reinterpret_cast<float2 *>(twBLds + 8*R3) + (size_t)team*(H + H/16);"
-assert k.count(old) == 1
-k = k.replace(old, "float2 *lds = reinterpret_cast<float2 *>(twBLds + 8*R3) + (size_t)(team % 3)*(H + H/16);")
-old = "(size_t)TEAMS*(H + H/16));"
-assert k.count(old) == 1
-k = k.replace(old, "(size_t)3*(H + H/16));")
-s = s[:i] + k + s[j:]
-rep("hipLaunchKernelGGL((kAnalyseTeams<12, 3, true>), dim3(wgs), dim3(768)", "hipLaunchKernelGGL((kAnalyseTeams<12, 4, true>), dim3(wgs), dim3(1024)")
+# TeamWorkgroup carves the LDS for all three team kernels: at most three transform buffers, whatever TEAMS says (the others have two or three teams)
+rep("lds = reinterpret_cast<float2 *>(twB + 8*R3) + (size_t)team*(H + H/16);", "lds = reinterpret_cast<float2 *>(twB + 8*R3) + (size_t)(team % 3)*(H + H/16);")
+rep("(size_t)TEAMS*(H + H/16));", "(size_t)(TEAMS < 3 ? TEAMS : 3)*(H + H/16));")
+rep("hipLaunchKernelGGL((kAnalyseTeams<r3.value, 3, exact.value>), dim3(teamsWorkgroups(d, jobs)), dim3(768), teamLdsBytes(d.M, 3)",
+    "hipLaunchKernelGGL((kAnalyseTeams<r3.value, 4, exact.value>), dim3(teamsWorkgroups(d, jobs)), dim3(1024), teamLdsBytes(d.M, 3)")
 open(p, 'w').write(s)

@@ -2,14 +2,8 @@
 import sys
 p = sys.argv[1] + '/smst_kernels.hip'
 s = open(p).read()
-old = """	auto store = [&](int j, float2 u, int, int) {
-		const int kk = 2*j;
-		if (kk < H) dst[kk] = u;
-		else dst[N - 1 - kk] = cconj(u);
-	};"""
-new = """	auto store = [&](int j, float2 u, int, int) {
-		const int kk = 2*j;
-		if (u.x == 1234.5f) { if (kk < H) dst[kk] = u; else dst[N - 1 - kk] = cconj(u); }
-	};"""
-assert s.count(old) == 1
-open(p, 'w').write(s.replace(old, new))
+i = s.index('void kAnalyseFast(')
+old = "	auto store = [&](int j, float2 u, int, int) { storeHalfBin(dst, j, u, H, N); };\n"
+assert s.count(old, i) == 1
+new = "	auto store = [&](int j, float2 u, int, int) { if (u.x == 1234.5f) storeHalfBin(dst, j, u, H, N); };\n"
+open(p, 'w').write(s[:i] + s[i:].replace(old, new))

@@ -2,10 +2,10 @@
 import sys
 p = sys.argv[1] + '/smst_kernels.hip'
 s = open(p).read()
-old = "__global__ __launch_bounds__(16*R3 > 256 ? 16*R3 : 256) __attribute__((amdgpu_waves_per_eu(4, 4))) void kAnalyseFast("
+old = "__global__ __launch_bounds__(fastBlockThreads(R3)) __attribute__((amdgpu_waves_per_eu(4, 4))) void kAnalyseFast("
 assert s.count(old) == 1
-s = s.replace(old, "__global__ __launch_bounds__(16*R3 > 256 ? 16*R3 : 256) __attribute__((amdgpu_waves_per_eu(6, 6))) void kAnalyseFast(")
-old = "__global__ __launch_bounds__(16*R3 > 256 ? 16*R3 : 256) void kSynthFast("
+s = s.replace(old, "__global__ __launch_bounds__(fastBlockThreads(R3)) __attribute__((amdgpu_waves_per_eu(6, 6))) void kAnalyseFast(")
+old = "__global__ __launch_bounds__(fastBlockThreads(R3)) void kSynthFast("
 assert s.count(old) == 1
-s = s.replace(old, "__global__ __launch_bounds__(16*R3 > 256 ? 16*R3 : 256) __attribute__((amdgpu_waves_per_eu(6, 6))) void kSynthFast(")
+s = s.replace(old, "__global__ __launch_bounds__(fastBlockThreads(R3)) __attribute__((amdgpu_waves_per_eu(6, 6))) void kSynthFast(")
 open(p, 'w').write(s)
