@@ -241,6 +241,43 @@ int smst_batch_flush(smst_batch *b, float *out, long long outStreamStride, long 
                      const int *outSamples, const float *playbackRates, int memory);
 int smst_batch_output_seek(smst_batch *b, const float *in, long long inStreamStride, long long inChannelStride,
                            const int *inputLengths, int memory);
+/* ---- interleaved PCM (EXTENSION: the reference's process() is templated on its buffers, so a caller there can hand it an adaptor over an
+ * interleaved frame buffer; here the conversion is part of the call and runs on the GPU) ----
+ * The four calls above with FRAME buffers: sample (s, i, c) at base[s*streamStride + i*frameStride + c], strides in ELEMENTS of the
+ * format, frameStride >= channels; the pointers need the element's alignment only (2 bytes for int16), no stride need be a multiple of
+ * 16 bytes.  `format` holds for the input and the output of a call; counts, rates and lengths are as in the planar calls (frames per
+ * stream; flush_pcm keeps the negative-count rule).
+ *   SMST_PCM_S16  in: float(v)/32768 (exact).  out: q = roundf(v*32768), ties away from zero, clamped to [-32768, 32767], no dither --
+ *                 the rule the CLI writes WAV files with.  NaN gives 0 (the CLI has no such case: a NaN there ends as -32768).
+ *   SMST_PCM_F32  copied bit for bit.
+ * The engine still works on a planar fp32 image of the call, now the library's own: a conversion kernel in front of the call and one behind it.
+ * SMST_MEM_HOST: each stream's frames are gathered into pinned memory (one memcpy per stream; a frameStride > channels is gathered frame by
+ *   frame), cross PCIe as ONE copy per direction -- half the bytes of the planar call for int16 --, and the call returns with the output in place.
+ * SMST_MEM_DEVICE: the kernels read / write the caller's device pointers; the call is asynchronous exactly as smst_batch_process is.
+ * Ordering contract: the input conversion runs on the batch's stream behind everything smst_batch_wait_for_stream has ordered it after,
+ *   and every reader of the call's input -- the silence gate runs on a stream of its own -- is ordered behind it by the edge
+ *   smst_batch_wait_for_stream makes for a caller's producer; the output conversion runs behind the call's last emitting kernel and in front
+ *   of whatever smst_batch_synchronize / smst_batch_signal_stream wait for.  No host synchronisation is added.  The caller's part is the
+ *   planar calls': wait_for_stream before, buffers alive and untouched until synchronize / a signalled stream has caught up.
+ * SMST_ERR_INVALID with a message: an unknown format, frameStride < channels, a null buffer with a non-zero count. */
+#define SMST_PCM_S16 1 /* int16, full scale 32768 */
+#define SMST_PCM_F32 2 /* float32 */
+int smst_batch_process_pcm(smst_batch *b, const void *in, long long inStreamStride, long long inFrameStride, const int *inSamples,
+                           void *out, long long outStreamStride, long long outFrameStride, const int *outSamples,
+                           int format, int memory);
+int smst_batch_seek_pcm(smst_batch *b, const void *in, long long inStreamStride, long long inFrameStride, const int *inSamples,
+                        const double *playbackRates, int format, int memory);
+int smst_batch_flush_pcm(smst_batch *b, void *out, long long outStreamStride, long long outFrameStride, const int *outSamples,
+                         const float *playbackRates, int format, int memory);
+int smst_batch_output_seek_pcm(smst_batch *b, const void *in, long long inStreamStride, long long inFrameStride, const int *inputLengths,
+                               int format, int memory);
+/* test hook: the two conversion kernels alone, ragged counts, arbitrary strides; dir 0 = PCM -> planar, 1 = planar -> PCM.  Host pointers: the
+ * PCM side is (stream stride, frame stride), the planar side (stream stride, channel stride), in elements.  Both buffers are staged whole (what
+ * the kernel leaves alone in `dst` comes back as it was) into device buffers offset from a 16-byte boundary as the caller's pointers are.
+ * Synchronises before it returns. */
+int smst_debug_pcm_convert(int device, int dir, int format, int streams, int channels, const int *counts,
+                           const void *src, long long srcStreamStride, long long srcInnerStride,
+                           void *dst, long long dstStreamStride, long long dstInnerStride);
 int smst_batch_synchronize(smst_batch *b);
 /* raw hipStream_t the batch enqueues on (so callers can order their own device work against it) */
 void *smst_batch_hip_stream(smst_batch *b);
@@ -293,7 +330,7 @@ int smst_batch_debug_get_formants(smst_batch *b, int stream, float *ratio, float
 int smst_debug_complex_selftest(int device, const float *in, float *out, int n);
 /* launches, since the library was loaded, of one kernel variant: "vocoder_aligned", "vocoder_staged", "vocoder_gather",
  * "vocoder_n", "vocoder_one", "vocoder_across", "chain_unfused", "analyse_teams", "analyse_fast", "analyse_generic",
- * "synth_teams", "synth_fast", "synth_generic" (-1: unknown name).  The "this form is bit-identical to that form" tests
+ * "synth_teams", "synth_fast", "synth_generic", "pcm_in", "pcm_out" (the conversion kernels of the _pcm calls) (-1: unknown name).  The "this form is bit-identical to that form" tests
  * assert through it that both forms really ran. */
 long long smst_debug_launch_count(const char *name);
 

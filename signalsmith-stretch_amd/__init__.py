@@ -25,6 +25,7 @@ LIBRARY_PATH = os.environ.get("SMST_LIBRARY") or os.path.join(_HERE, "libsmst_hi
 CSRC_DIR = os.path.join(_HERE, "csrc")
 
 MEM_HOST, MEM_DEVICE = 0, 1
+PCM_S16, PCM_F32 = 1, 2  # frame formats of the *_pcm calls (include/smst.h)
 _fp = C.POINTER(C.c_float)
 _ip = C.POINTER(C.c_int)
 _dp = C.POINTER(C.c_double)
@@ -106,6 +107,11 @@ _SIGNATURES = {
     "smst_batch_process": (C.c_int, [C.c_void_p, C.c_void_p, _ll, _ll, _ip, C.c_void_p, _ll, _ll, _ip, C.c_int]),
     "smst_batch_flush": (C.c_int, [C.c_void_p, C.c_void_p, _ll, _ll, _ip, _fp, C.c_int]),
     "smst_batch_output_seek": (C.c_int, [C.c_void_p, C.c_void_p, _ll, _ll, _ip, C.c_int]),
+    "smst_batch_process_pcm": (C.c_int, [C.c_void_p, C.c_void_p, _ll, _ll, _ip, C.c_void_p, _ll, _ll, _ip, C.c_int, C.c_int]),
+    "smst_batch_seek_pcm": (C.c_int, [C.c_void_p, C.c_void_p, _ll, _ll, _ip, _dp, C.c_int, C.c_int]),
+    "smst_batch_flush_pcm": (C.c_int, [C.c_void_p, C.c_void_p, _ll, _ll, _ip, _fp, C.c_int, C.c_int]),
+    "smst_batch_output_seek_pcm": (C.c_int, [C.c_void_p, C.c_void_p, _ll, _ll, _ip, C.c_int, C.c_int]),
+    "smst_debug_pcm_convert": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _ip, C.c_void_p, _ll, _ll, C.c_void_p, _ll, _ll]),
     "smst_batch_synchronize": (C.c_int, [C.c_void_p]),
     "smst_batch_hip_stream": (C.c_void_p, [C.c_void_p]),
     "smst_batch_enable_profiling": (C.c_int, [C.c_void_p, C.c_int]),
@@ -398,6 +404,92 @@ class StretchBatch:
         if mem == MEM_DEVICE:
             self._order_after_torch(x)
         _check(self.lib, self.lib.smst_batch_output_seek(self.h, ptr, ss, cs, pin, mem))
+
+    # --- interleaved PCM frames (smst_batch_*_pcm): [S, n, C] of int16 or float32, the same dtype and layout back
+    def _describe_frames(self, x, what):
+        """-> (pointer, streamStride, frameStride, frames, format, memory, keepalive); strides in elements"""
+        if _is_torch(x):
+            if x.dim() != 3 or x.shape[0] != self.streams or x.shape[2] != self.channels:
+                raise StretchError("%s must be [S, n, C]" % what)
+            fmt = {"torch.int16": PCM_S16, "torch.float32": PCM_F32}.get(str(x.dtype))
+            if fmt is None or not x.is_cuda or x.stride(2) != 1:
+                raise StretchError("%s: need an int16 or float32 GPU tensor with contiguous channels" % what)
+            return C.c_void_p(x.data_ptr()), x.stride(0), x.stride(1), x.shape[1], fmt, MEM_DEVICE, x
+        a = np.asarray(x)
+        fmt = {"int16": PCM_S16, "float32": PCM_F32}.get(a.dtype.name)
+        if fmt is None:
+            raise StretchError("%s: frames are int16 or float32" % what)
+        if a.ndim != 3 or a.shape[0] != self.streams or a.shape[2] != self.channels:
+            raise StretchError("%s must be [S, n, C]" % what)
+        if a.size and (a.strides[2] != a.itemsize or a.strides[0] % a.itemsize or a.strides[1] % a.itemsize or a.strides[0] < 0 or a.strides[1] < a.itemsize*a.shape[2]):
+            a = np.ascontiguousarray(a)
+        if a.size == 0:  # (numpy gives an empty array zero strides)
+            return C.c_void_p(a.ctypes.data), a.shape[1]*a.shape[2], a.shape[2], a.shape[1], fmt, MEM_HOST, a
+        return C.c_void_p(a.ctypes.data), a.strides[0]//a.itemsize, a.strides[1]//a.itemsize, a.shape[1], fmt, MEM_HOST, a
+
+    def _new_frames(self, frames, fmt, like):
+        if like is not None and _is_torch(like):
+            import torch
+            return torch.zeros((self.streams, frames, self.channels), dtype=torch.int16 if fmt == PCM_S16 else torch.float32, device=like.device)
+        return np.zeros((self.streams, frames, self.channels), np.int16 if fmt == PCM_S16 else np.float32)
+
+    def processFrames(self, x, out_samples, in_samples=None, out=None, ordered=True):
+        """process() on interleaved frames: x is [S, n, C] int16 (full scale 32768) or float32, numpy (host memory) or a torch GPU tensor;
+        the result has the same dtype and layout.  int16 output is round-to-nearest, ties away from zero, clamped, no dither; NaN -> 0
+        (include/smst.h).  ``ordered`` as in process()."""
+        S = self.streams
+        ptr, ss, fs, n, fmt, mem, keep = self._describe_frames(x, "input")
+        nin, pin = _int_array(n if in_samples is None else in_samples, S)
+        nout, pout = _int_array(out_samples, S)
+        max_out = max(int(nout.max()), 1)
+        if out is None:
+            out = self._new_frames(max_out, fmt, x if mem == MEM_DEVICE else None)
+        optr, oss, ofs, on, ofmt, omem, okeep = self._describe_frames(out, "output")
+        if omem != mem or ofmt != fmt:
+            raise StretchError("input and output must have the same format and live in the same memory space")
+        if omem == MEM_HOST and okeep is not out:
+            raise StretchError("output: need an array the library can write in place")
+        if on < max_out or int(nin.max()) > n:
+            raise StretchError("buffer shorter than the requested sample count")
+        if mem == MEM_DEVICE and ordered:
+            self._order_after_torch(x, out)
+        _check(self.lib, self.lib.smst_batch_process_pcm(self.h, ptr, ss, fs, pin, optr, oss, ofs, pout, fmt, mem))
+        if mem == MEM_DEVICE and ordered:
+            import torch
+            _check(self.lib, self.lib.smst_batch_signal_stream(self.h, C.c_void_p(torch.cuda.current_stream(out.device).cuda_stream)))
+        return out
+
+    def seekFrames(self, x, rates, in_samples=None):
+        S = self.streams
+        ptr, ss, fs, n, fmt, mem, keep = self._describe_frames(x, "input")
+        nin, pin = _int_array(n if in_samples is None else in_samples, S)
+        r = np.ascontiguousarray(np.broadcast_to(np.asarray(rates, dtype=np.float64), (S,)))
+        if mem == MEM_DEVICE:
+            self._order_after_torch(x)
+        _check(self.lib, self.lib.smst_batch_seek_pcm(self.h, ptr, ss, fs, pin, r.ctypes.data_as(_dp), fmt, mem))
+
+    def flushFrames(self, out_samples, rates=0.0, like=None, dtype=np.int16):
+        """flush() into [S, n, C] frames of ``dtype`` (int16 or float32); a negative count leaves that stream alone"""
+        S = self.streams
+        fmt = {"int16": PCM_S16, "float32": PCM_F32}.get(np.dtype(dtype).name)
+        if fmt is None:
+            raise StretchError("frames are int16 or float32")
+        nout, pout = _int_array(out_samples, S)
+        r = np.ascontiguousarray(np.broadcast_to(np.asarray(rates, dtype=np.float32), (S,)))
+        out = self._new_frames(max(int(nout.max()), 1), fmt, like)
+        optr, oss, ofs, on, ofmt, omem, okeep = self._describe_frames(out, "output")
+        _check(self.lib, self.lib.smst_batch_flush_pcm(self.h, optr, oss, ofs, pout, r.ctypes.data_as(_fp), fmt, omem))
+        if omem == MEM_DEVICE:
+            self.synchronize()
+        return out
+
+    def outputSeekFrames(self, x, input_lengths=None):
+        S = self.streams
+        ptr, ss, fs, n, fmt, mem, keep = self._describe_frames(x, "input")
+        nin, pin = _int_array(n if input_lengths is None else input_lengths, S)
+        if mem == MEM_DEVICE:
+            self._order_after_torch(x)
+        _check(self.lib, self.lib.smst_batch_output_seek_pcm(self.h, ptr, ss, fs, pin, fmt, mem))
 
     # --- test hooks
     def debug_state(self, stream, which):

@@ -8,7 +8,9 @@
 #include <algorithm>
 #include <atomic>
 #include <cmath>
+#include <cstdint>
 #include <cstdlib>
+#include <cstring>
 #include <memory>
 #include <string>
 #include <vector>
@@ -23,10 +25,26 @@ struct smst_batch {
 	float *dIn = nullptr, *dOut = nullptr;
 	size_t inCap = 0, outCap = 0;
 	long long stagingAllocs = 0;
+	// interleaved PCM (smst_batch_*_pcm): the raw frames as they cross PCIe, one device and one pinned host buffer per direction (bytes); the
+	// planar image the engine works on is dIn / dOut above.  The per-stream frame counts of the conversion kernels exist twice, as the engine's
+	// per-call tables do: a device-memory call returns before its kernels have run
+	unsigned char *dPcmIn = nullptr, *dPcmOut = nullptr, *hPcmIn = nullptr, *hPcmOut = nullptr;
+	size_t dPcmInCap = 0, dPcmOutCap = 0, hPcmInCap = 0, hPcmOutCap = 0;
+	struct PcmCounts { int *host = nullptr, *dev = nullptr; hipEvent_t done = nullptr; bool used = false; } pcmCounts[2]; // [2*S]: input frames, output frames
+	int pcmCur = 0;
 	~smst_batch() {
 		if (engine) hipSetDevice(engine->device());
 		if (dIn) hipFree(dIn);
 		if (dOut) hipFree(dOut);
+		if (dPcmIn) hipFree(dPcmIn);
+		if (dPcmOut) hipFree(dPcmOut);
+		if (hPcmIn) hipHostFree(hPcmIn);
+		if (hPcmOut) hipHostFree(hPcmOut);
+		for (PcmCounts &c : pcmCounts) {
+			if (c.dev) hipFree(c.dev);
+			if (c.host) hipHostFree(c.host);
+			if (c.done) hipEventDestroy(c.done);
+		}
 	}
 };
 
@@ -322,6 +340,235 @@ int smst_batch_output_seek(smst_batch *b, const float *in, long long ss, long lo
 			b->engine->synchronize();
 		}
 	})
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// interleaved PCM: the four calls above with frame buffers of int16 / float32 (include/smst.h).  kPcmIn fills the planar image the engine
+// reads, kPcmOut empties the one it wrote; both run on the engine's stream.
+// ---------------------------------------------------------------------------------------------------------
+static size_t pcmElemBytes(int format) { return format == SMST_PCM_S16 ? sizeof(int16_t) : sizeof(float); }
+static void ensurePcmBytes(unsigned char *&ptr, size_t &cap, size_t need, bool pinned, int device, long long &allocs) {
+	if (need <= cap) return;
+	++allocs;
+	hipSetDevice(device);
+	if (ptr) { if (pinned) hipHostFree(ptr); else hipFree(ptr); }
+	ptr = nullptr;
+	cap = 0;
+	const size_t want = need + need/8 + 4096;
+	const hipError_t err = pinned ? hipHostMalloc(reinterpret_cast<void **>(&ptr), want, hipHostMallocDefault) : hipMalloc(reinterpret_cast<void **>(&ptr), want);
+	if (err != hipSuccess) throw smst::Error(pinned ? "hipHostMalloc (PCM staging) failed" : "hipMalloc (PCM staging) failed", true);
+	cap = want;
+}
+static void checkPcmSide(const void *buf, long long frameStride, const int *n, int S, int C, bool negativeSkips) {
+	if (!n) throw smst::Error("null sample counts");
+	if (frameStride < C) throw smst::Error("frame stride smaller than the channel count");
+	for (int s = 0; s < S; ++s) {
+		if (n[s] < 0 && !negativeSkips) throw smst::Error("negative sample count");
+		if (n[s] > 0 && !buf) throw smst::Error("null buffer with a non-zero sample count");
+	}
+}
+static void checkPcmFormat(int format, int memory) {
+	if (format != SMST_PCM_S16 && format != SMST_PCM_F32) throw smst::Error("unknown PCM format (SMST_PCM_S16 or SMST_PCM_F32)");
+	if (memory != SMST_MEM_HOST && memory != SMST_MEM_DEVICE) throw smst::Error("unknown memory kind");
+}
+// the count tables of this call: the set the call before the previous one used (its conversion kernels must have run)
+static smst_batch::PcmCounts &beginPcmCall(smst_batch *b) {
+	Batch &e = *b->engine;
+	hipSetDevice(e.device());
+	b->pcmCur ^= 1;
+	smst_batch::PcmCounts &c = b->pcmCounts[b->pcmCur];
+	if (!c.host) {
+		++b->stagingAllocs;
+		const size_t bytes = (size_t)2*e.streams()*sizeof(int);
+		if (hipHostMalloc(reinterpret_cast<void **>(&c.host), bytes, hipHostMallocDefault) != hipSuccess) throw smst::Error("hipHostMalloc (PCM counts) failed", true);
+		if (hipMalloc(reinterpret_cast<void **>(&c.dev), bytes) != hipSuccess) throw smst::Error("hipMalloc (PCM counts) failed", true);
+		if (hipEventCreateWithFlags(&c.done, hipEventDisableTiming) != hipSuccess) throw smst::Error("hipEventCreate failed", true);
+	}
+	if (c.used && hipEventSynchronize(c.done) != hipSuccess) throw smst::Error("hipEventSynchronize failed", true);
+	c.used = false;
+	return c;
+}
+static void endPcmCall(smst_batch *b, smst_batch::PcmCounts &c) {
+	if (hipEventRecord(c.done, b->engine->stream()) != hipSuccess) throw smst::Error("hipEventRecord failed", true);
+	c.used = true;
+}
+// a stream's row in the library's own raw buffers: its frames densely, rows a multiple of 32 bytes apart
+static long long pcmRowElems(int maxFrames, int C) { return ((long long)maxFrames*C + 7)/8*8; }
+
+// Raw frames -> the planar image b->dIn [S][C][maxLen] (returns maxLen), on the engine's stream and in front of every reader of the call's input
+static int pcmStageIn(smst_batch *b, smst_batch::PcmCounts &c, const void *in, long long ss, long long fs, const int *n, int format, int memory) {
+	Batch &e = *b->engine;
+	const int S = e.streams(), C = e.channels();
+	int most = 0;
+	for (int s = 0; s < S; ++s) { c.host[s] = n[s]; most = std::max(most, n[s]); }
+	const int maxLen = std::max(most, 1);
+	ensureStage(b->dIn, b->inCap, (size_t)S*C*maxLen, e.device(), b->stagingAllocs);
+	hipSetDevice(e.device());
+	if (hipMemcpyAsync(c.dev, c.host, S*sizeof(int), hipMemcpyHostToDevice, e.stream()) != hipSuccess) throw smst::Error("hipMemcpyAsync (H2D) failed", true);
+	const void *raw = in;
+	long long rawSS = ss, rawFS = fs;
+	if (memory == SMST_MEM_HOST && most > 0) {
+		const size_t esz = pcmElemBytes(format);
+		const long long row = pcmRowElems(most, C);
+		const size_t bytes = (size_t)S*row*esz;
+		ensurePcmBytes(b->hPcmIn, b->hPcmInCap, bytes, true, e.device(), b->stagingAllocs);
+		ensurePcmBytes(b->dPcmIn, b->dPcmInCap, bytes, false, e.device(), b->stagingAllocs);
+		for (int s = 0; s < S; ++s) {
+			if (n[s] <= 0) continue;
+			const unsigned char *src = static_cast<const unsigned char *>(in) + (size_t)s*ss*esz;
+			unsigned char *dst = b->hPcmIn + (size_t)s*row*esz;
+			if (fs == C) std::memcpy(dst, src, (size_t)n[s]*C*esz);
+			else for (int i = 0; i < n[s]; ++i) std::memcpy(dst + (size_t)i*C*esz, src + (size_t)i*fs*esz, (size_t)C*esz);
+		}
+		if (hipMemcpyAsync(b->dPcmIn, b->hPcmIn, bytes, hipMemcpyHostToDevice, e.stream()) != hipSuccess) throw smst::Error("hipMemcpyAsync (H2D) failed", true);
+		raw = b->dPcmIn; rawSS = row; rawFS = C;
+	}
+	smst::launchPcmIn(format, raw, rawSS, rawFS, b->dIn, (long long)C*maxLen, maxLen, c.dev, S, C, most, e.stream());
+	// the engine reads its input on more than one stream (the silence gate on its own): the edge a caller's producer stream gets
+	e.waitForStream(e.stream());
+	return maxLen;
+}
+// the output side's buffers, before the engine is called (a growth frees, which synchronises the device): returns maxLen of b->dOut [S][C][maxLen]
+static int pcmPrepareOut(smst_batch *b, smst_batch::PcmCounts &c, const int *n, int format, int memory) {
+	Batch &e = *b->engine;
+	const int S = e.streams(), C = e.channels();
+	int most = 0;
+	for (int s = 0; s < S; ++s) { c.host[S + s] = std::max(n[s], 0); most = std::max(most, n[s]); }
+	const int maxLen = std::max(most, 1);
+	ensureStage(b->dOut, b->outCap, (size_t)S*C*maxLen, e.device(), b->stagingAllocs);
+	if (memory == SMST_MEM_HOST && most > 0) {
+		const size_t bytes = (size_t)S*pcmRowElems(most, C)*pcmElemBytes(format);
+		ensurePcmBytes(b->hPcmOut, b->hPcmOutCap, bytes, true, e.device(), b->stagingAllocs);
+		ensurePcmBytes(b->dPcmOut, b->dPcmOutCap, bytes, false, e.device(), b->stagingAllocs);
+	}
+	hipSetDevice(e.device());
+	if (hipMemcpyAsync(c.dev + S, c.host + S, S*sizeof(int), hipMemcpyHostToDevice, e.stream()) != hipSuccess) throw smst::Error("hipMemcpyAsync (H2D) failed", true);
+	return maxLen;
+}
+// The planar image b->dOut -> raw frames, behind the engine's last emitting kernel (everything of a call is joined into the engine's stream,
+// which is what smst_batch_synchronize and smst_batch_signal_stream wait on).  Host memory: the call returns with the frames in place.
+static void pcmStageOut(smst_batch *b, smst_batch::PcmCounts &c, void *out, long long ss, long long fs, int maxLen, int format, int memory) {
+	Batch &e = *b->engine;
+	const int S = e.streams(), C = e.channels();
+	const int *n = c.host + S;
+	int most = 0;
+	for (int s = 0; s < S; ++s) most = std::max(most, n[s]);
+	hipSetDevice(e.device());
+	if (memory == SMST_MEM_DEVICE) {
+		smst::launchPcmOut(format, b->dOut, (long long)C*maxLen, maxLen, out, ss, fs, c.dev + S, S, C, most, e.stream());
+		return;
+	}
+	if (most < 1) return;
+	const size_t esz = pcmElemBytes(format);
+	const long long row = pcmRowElems(most, C);
+	smst::launchPcmOut(format, b->dOut, (long long)C*maxLen, maxLen, b->dPcmOut, row, C, c.dev + S, S, C, most, e.stream());
+	if (hipMemcpyAsync(b->hPcmOut, b->dPcmOut, (size_t)S*row*esz, hipMemcpyDeviceToHost, e.stream()) != hipSuccess) throw smst::Error("hipMemcpyAsync (D2H) failed", true);
+	if (hipStreamSynchronize(e.stream()) != hipSuccess) throw smst::Error("hipStreamSynchronize failed", true);
+	for (int s = 0; s < S; ++s) {
+		if (n[s] <= 0) continue;
+		const unsigned char *src = b->hPcmOut + (size_t)s*row*esz;
+		unsigned char *dst = static_cast<unsigned char *>(out) + (size_t)s*ss*esz;
+		if (fs == C) std::memcpy(dst, src, (size_t)n[s]*C*esz);
+		else for (int i = 0; i < n[s]; ++i) std::memcpy(dst + (size_t)i*fs*esz, src + (size_t)i*C*esz, (size_t)C*esz);
+	}
+}
+
+int smst_batch_process_pcm(smst_batch *b, const void *in, long long iss, long long ifs, const int *inSamples,
+                           void *out, long long oss, long long ofs, const int *outSamples, int format, int memory) {
+	BATCH_CALL({
+		Batch &e = *b->engine;
+		checkPcmFormat(format, memory);
+		checkPcmSide(in, ifs, inSamples, e.streams(), e.channels(), false);
+		checkPcmSide(out, ofs, outSamples, e.streams(), e.channels(), false);
+		smst_batch::PcmCounts &c = beginPcmCall(b);
+		const int maxIn = pcmStageIn(b, c, in, iss, ifs, inSamples, format, memory);
+		const int maxOut = pcmPrepareOut(b, c, outSamples, format, memory);
+		e.process(b->dIn, (long long)e.channels()*maxIn, maxIn, inSamples, b->dOut, (long long)e.channels()*maxOut, maxOut, outSamples);
+		pcmStageOut(b, c, out, oss, ofs, maxOut, format, memory);
+		endPcmCall(b, c);
+	})
+}
+int smst_batch_seek_pcm(smst_batch *b, const void *in, long long ss, long long fs, const int *inSamples, const double *rates, int format, int memory) {
+	BATCH_CALL({
+		Batch &e = *b->engine;
+		checkPcmFormat(format, memory);
+		checkPcmSide(in, fs, inSamples, e.streams(), e.channels(), false);
+		smst_batch::PcmCounts &c = beginPcmCall(b);
+		const int maxLen = pcmStageIn(b, c, in, ss, fs, inSamples, format, memory);
+		e.seek(b->dIn, (long long)e.channels()*maxLen, maxLen, inSamples, rates);
+		endPcmCall(b, c);
+		if (memory == SMST_MEM_HOST) e.synchronize();
+	})
+}
+int smst_batch_flush_pcm(smst_batch *b, void *out, long long oss, long long ofs, const int *outSamples, const float *rates, int format, int memory) {
+	BATCH_CALL({
+		Batch &e = *b->engine;
+		checkPcmFormat(format, memory);
+		checkPcmSide(out, ofs, outSamples, e.streams(), e.channels(), true);
+		// a NEGATIVE count leaves that stream out of the flush, as in smst_batch_flush
+		std::vector<unsigned char> active(e.streams(), 1);
+		std::vector<int> counts(outSamples, outSamples + e.streams());
+		bool all = true;
+		for (int s = 0; s < e.streams(); ++s) if (counts[s] < 0) { active[s] = 0; counts[s] = 0; all = false; }
+		smst_batch::PcmCounts &c = beginPcmCall(b);
+		const int maxOut = pcmPrepareOut(b, c, counts.data(), format, memory);
+		e.flush(b->dOut, (long long)e.channels()*maxOut, maxOut, counts.data(), rates, all ? nullptr : active.data());
+		pcmStageOut(b, c, out, oss, ofs, maxOut, format, memory);
+		endPcmCall(b, c);
+	})
+}
+int smst_batch_output_seek_pcm(smst_batch *b, const void *in, long long ss, long long fs, const int *inputLengths, int format, int memory) {
+	BATCH_CALL({
+		Batch &e = *b->engine;
+		checkPcmFormat(format, memory);
+		checkPcmSide(in, fs, inputLengths, e.streams(), e.channels(), false);
+		smst_batch::PcmCounts &c = beginPcmCall(b);
+		const int maxLen = pcmStageIn(b, c, in, ss, fs, inputLengths, format, memory);
+		e.outputSeek(b->dIn, (long long)e.channels()*maxLen, maxLen, inputLengths);
+		endPcmCall(b, c);
+		if (memory == SMST_MEM_HOST) e.synchronize();
+	})
+}
+int smst_debug_pcm_convert(int device, int dir, int format, int streams, int channels, const int *counts,
+                           const void *src, long long srcSS, long long srcInner, void *dst, long long dstSS, long long dstInner) {
+	SMST_TRY
+	checkPcmFormat(format, SMST_MEM_HOST);
+	if (dir != 0 && dir != 1) throw smst::Error("pcm convert: dir is 0 (PCM -> planar) or 1 (planar -> PCM)");
+	if (streams < 1 || channels < 1 || channels > 16 || !counts || !src || !dst || srcSS < 0 || dstSS < 0 || srcInner < 0 || dstInner < 0) throw smst::Error("pcm convert: bad arguments");
+	int most = 0;
+	for (int s = 0; s < streams; ++s) { if (counts[s] < 0) throw smst::Error("negative sample count"); most = std::max(most, counts[s]); }
+	const long long pcmFS = dir == 0 ? srcInner : dstInner;
+	if (pcmFS < channels) throw smst::Error("frame stride smaller than the channel count");
+	const size_t esz = pcmElemBytes(format);
+	// elements either side spans, from its base
+	const long long pcmSS = dir == 0 ? srcSS : dstSS, plSS = dir == 0 ? dstSS : srcSS, plCS = dir == 0 ? dstInner : srcInner;
+	const size_t pcmBytes = most ? size_t((streams - 1)*pcmSS + (most - 1)*pcmFS + channels)*esz : 0;
+	const size_t plBytes = most ? size_t((streams - 1)*plSS + (channels - 1)*plCS + most)*sizeof(float) : 0;
+	const size_t srcBytes = dir == 0 ? pcmBytes : plBytes, dstBytes = dir == 0 ? plBytes : pcmBytes;
+	if (hipSetDevice(device) != hipSuccess) throw smst::Error("hipSetDevice failed", true);
+	unsigned char *dSrc = nullptr, *dDst = nullptr;
+	int *dCounts = nullptr;
+	hipError_t err = hipMalloc(reinterpret_cast<void **>(&dSrc), srcBytes + 32);
+	if (err == hipSuccess) err = hipMalloc(reinterpret_cast<void **>(&dDst), dstBytes + 32);
+	if (err == hipSuccess) err = hipMalloc(reinterpret_cast<void **>(&dCounts), streams*sizeof(int));
+	// the device buffers sit as far behind a 16-byte boundary as the caller's do
+	unsigned char *s0 = dSrc + reinterpret_cast<uintptr_t>(src)%16, *d0 = dDst + reinterpret_cast<uintptr_t>(dst)%16;
+	if (err == hipSuccess && srcBytes) err = hipMemcpy(s0, src, srcBytes, hipMemcpyHostToDevice);
+	if (err == hipSuccess && dstBytes) err = hipMemcpy(d0, dst, dstBytes, hipMemcpyHostToDevice);
+	if (err == hipSuccess) err = hipMemcpy(dCounts, counts, streams*sizeof(int), hipMemcpyHostToDevice);
+	if (err == hipSuccess) {
+		if (dir == 0) smst::launchPcmIn(format, s0, srcSS, srcInner, reinterpret_cast<float *>(d0), dstSS, dstInner, dCounts, streams, channels, most, nullptr);
+		else smst::launchPcmOut(format, reinterpret_cast<const float *>(s0), srcSS, srcInner, d0, dstSS, dstInner, dCounts, streams, channels, most, nullptr);
+		err = hipGetLastError();
+	}
+	if (err == hipSuccess) err = hipStreamSynchronize(nullptr);
+	if (err == hipSuccess && dstBytes) err = hipMemcpy(dst, d0, dstBytes, hipMemcpyDeviceToHost);
+	if (dSrc) hipFree(dSrc);
+	if (dDst) hipFree(dDst);
+	if (dCounts) hipFree(dCounts);
+	if (err != hipSuccess) throw smst::Error(std::string("pcm convert: ") + hipGetErrorString(err), true);
+	return SMST_OK;
+	SMST_CATCH
 }
 
 // ---------------------------------------------------------------------------------------------------------

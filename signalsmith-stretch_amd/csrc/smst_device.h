@@ -161,7 +161,7 @@ __host__ __device__ inline bool analysisWindowInCall(int B, int M, int I, int in
 // form" tests assert through these that BOTH forms really ran.
 enum LaunchKind {
 	LK_VOC_ALIGNED, LK_VOC_STAGED, LK_VOC_GATHER, LK_VOC_N, LK_VOC_ONE, LK_VOC_ACROSS, LK_VOC_CONT, LK_CHAIN_UNFUSED,
-	LK_ANALYSE_TEAMS, LK_ANALYSE_FAST, LK_ANALYSE_GENERIC, LK_SYNTH_TEAMS, LK_SYNTH_FAST, LK_SYNTH_GENERIC, LK_SYNTH_EMIT, LK_EMIT_CARRIED, LK_FEED_ONE_PASS, LK_COUNT
+	LK_ANALYSE_TEAMS, LK_ANALYSE_FAST, LK_ANALYSE_GENERIC, LK_SYNTH_TEAMS, LK_SYNTH_FAST, LK_SYNTH_GENERIC, LK_SYNTH_EMIT, LK_EMIT_CARRIED, LK_FEED_ONE_PASS, LK_PCM_IN, LK_PCM_OUT, LK_COUNT
 };
 long long launchCount(const char *name); // -1: unknown name
 
@@ -204,5 +204,12 @@ void launchAddPreRoll(const DevBatch &d, const float *preRoll, int length, const
 void launchComplexSelfTest(const float *in, float *out, int n, hipStream_t st); // smst_complex.h against its documented formulas (test hook)
 void launchFlushTail(const DevBatch &d, const IoArgs &io, const int *tailOffset, const int *outOffset, hipStream_t st);
 void launchMoveStreams(const MoveArgs &a, hipStream_t st); // every segment of every pair in one launch
+// Interleaved PCM frames <-> the planar fp32 image (smst_pcm.h).  format: SMST_PCM_S16 / SMST_PCM_F32 of include/smst.h; strides in elements;
+// counts: [S] device, frames per stream; maxFrames: the largest of them (sizes the grid; nothing is launched for 0)
+constexpr int kPcmTileFrames = 512; // frames one workgroup moves
+void launchPcmIn(int format, const void *in, long long inStreamStride, long long inFrameStride, float *out, long long outStreamStride, long long outChannelStride,
+                 const int *counts, int S, int C, int maxFrames, hipStream_t st);
+void launchPcmOut(int format, const float *in, long long inStreamStride, long long inChannelStride, void *out, long long outStreamStride, long long outFrameStride,
+                  const int *counts, int S, int C, int maxFrames, hipStream_t st);
 
 } // namespace smst

@@ -1,0 +1,88 @@
+#!/usr/bin/env python3
+"""Wall time per step of the batch API fed with interleaved PCM frames, against the planar float calls (EXPERIMENTS.md, "Interleaved PCM").
+
+Workload: 256 stereo streams, 48 kHz, presetDefault, 1.5x, 10-second steps.  Variants, alternated step by step inside every round so
+that drift of the host or the device hits all of them alike:
+  a  smst_batch_process, SMST_MEM_HOST, planar float        (the path before the frame calls; also runs on an older library:
+                                                             SMST_LIBRARY=<libsmst_hip.so of that build> SMST_LIBRARY_ALLOW_MISSING=1 --variants a)
+  b  smst_batch_process_pcm, SMST_MEM_HOST, float32 frames
+  c  smst_batch_process_pcm, SMST_MEM_HOST, int16 frames
+  d  smst_batch_process_pcm, SMST_MEM_DEVICE, int16 frames  (torch tensors, batch synchronised per step)
+  e  smst_batch_process, SMST_MEM_DEVICE, planar float      (what d is compared with: d - e = the two conversion passes)
+A step's time is the host clock around one call that ends synchronised.  Prints one JSON line."""
+import argparse
+import importlib
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--streams", type=int, default=256)
+    ap.add_argument("--seconds", type=float, default=10.0)
+    ap.add_argument("--rate", type=float, default=1.5, help="time-stretch factor (output frames per input frame)")
+    ap.add_argument("--steps", type=int, default=5, help="timed steps per variant")
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--variants", default="a,b,c,d,e")
+    args = ap.parse_args()
+    pkg = importlib.import_module("signalsmith-stretch_amd")
+    variants = args.variants.split(",")
+    S, Cn, sr = args.streams, 2, 48000
+    n = int(args.seconds*sr)
+    m = int(n*args.rate)
+    rng = np.random.Generator(np.random.PCG64(7))
+    t = np.arange(n)/sr
+    base = np.stack([0.3*np.sin(2*np.pi*(110*2**(k/12))*t) for k in range(8)]).astype(np.float32)
+    planar = np.empty((S, Cn, n), np.float32)
+    for s in range(S):
+        for c in range(Cn):
+            planar[s, c] = base[(s + 3*c) % 8] + rng.uniform(-0.05, 0.05, n).astype(np.float32)
+    f32 = np.ascontiguousarray(planar.transpose(0, 2, 1))
+    s16 = np.clip(np.round(f32*32768.0), -32768, 32767).astype(np.int16)
+    runs = {}
+    if "a" in variants:
+        b, out = pkg.StretchBatch(S, Cn, preset="default", sample_rate=sr), np.zeros((S, Cn, m), np.float32)
+        runs["a"] = lambda b=b, out=out: b.process(planar, m, out=out)
+    if "b" in variants:
+        b, out = pkg.StretchBatch(S, Cn, preset="default", sample_rate=sr), np.zeros((S, m, Cn), np.float32)
+        runs["b"] = lambda b=b, out=out: b.processFrames(f32, m, out=out)
+    if "c" in variants:
+        b, out = pkg.StretchBatch(S, Cn, preset="default", sample_rate=sr), np.zeros((S, m, Cn), np.int16)
+        runs["c"] = lambda b=b, out=out: b.processFrames(s16, m, out=out)
+    if "d" in variants or "e" in variants:
+        import torch
+    if "d" in variants:
+        b, x, out = pkg.StretchBatch(S, Cn, preset="default", sample_rate=sr), torch.from_numpy(s16).cuda(), torch.zeros((S, m, Cn), dtype=torch.int16, device="cuda")
+        torch.cuda.synchronize()
+        runs["d"] = lambda b=b, x=x, out=out: (b.processFrames(x, m, out=out, ordered=False), b.synchronize())
+    if "e" in variants:
+        b, x, out = pkg.StretchBatch(S, Cn, preset="default", sample_rate=sr), torch.from_numpy(planar).cuda(), torch.zeros((S, Cn, m), dtype=torch.float32, device="cuda")
+        torch.cuda.synchronize()
+        runs["e"] = lambda b=b, x=x, out=out: (b.process(x, m, out=out, ordered=False), b.synchronize())
+    times = {k: [] for k in runs}
+    for step in range(args.warmup + args.steps):
+        for k, run in runs.items():
+            t0 = time.perf_counter()
+            run()
+            dt = time.perf_counter() - t0
+            if step >= args.warmup:
+                times[k].append(dt*1e3)
+    result = dict(streams=S, channels=Cn, in_frames=n, out_frames=m, steps=args.steps, warmup=args.warmup, library=pkg.library_path(), step_ms={})
+    for k, v in times.items():
+        v = sorted(v)
+        result["step_ms"][k] = dict(median=v[len(v)//2], min=v[0], max=v[-1], msamples_per_s=S*n/(v[len(v)//2]*1e-3)/1e6)
+    if "d" in times and "e" in times:
+        extra = result["step_ms"]["d"]["median"] - result["step_ms"]["e"]["median"]
+        moved = S*Cn*(n + m)*(2 + 4)  # each pass reads one format and writes the other
+        result["conversion_passes"] = dict(extra_ms=extra, bytes=moved, gb_per_s=(moved/(extra*1e-3)/1e9 if extra > 0 else None))
+    print(json.dumps(result))
+
+
+if __name__ == "__main__":
+    main()
