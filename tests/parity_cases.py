@@ -377,12 +377,77 @@ def case_vocn_writer_forms(lib, monkeypatch, channel_counts=(3, 8), n=12000, ext
                 assert np.array_equal(outs[0], o), (geometry, C, float(np.abs(outs[0] - o).max()))
 
 
-def case_feed_fusion_equals_separate(lib, monkeypatch, channel_counts=(2, 3), geometry=None, n=9000, formants=False, bases_given=False):
+def feed_scan_setup(b):
+    """Pitch map with a tonality limit on every stream; formant compensation with the base frequency estimated on stream 0 (the
+    raw estimate and kFeedFreq run) and given on stream 1; stream 2 has the map alone."""
+    b.setTransposeSemitones(4, 8000/48000)
+    b.setFormantFactor(1.2, True, stream=0)
+    b.setFormantFactor(1.2, True, stream=1)
+    b.setFormantBase(200/48000, stream=1)
+
+
+# The smallest shapes that reach each form of the feed kernels: name -> (geometry, hops' worth of input, the SERIAL form's own
+# rel-RMS response to an input perturbed by PERTURBATION -- measured, see case_feed_scan_close_to_serial)
+FEED_SCAN_SHAPES = {
+    "160 bands": (dict(block=300, interval=75, split=False), 6, 4.6e-6),       # threads 160..255 own no bin (cnt == 0)
+    "256 bands": (dict(block=512, interval=128, split=False), 6, 3.5e-4),      # one bin per thread, <16>
+    "5120 bands": (dict(block=10240, interval=2560, split=False), 6, 1.5e-3),  # 20 bins per thread: <24>, as the 96 kHz presets
+    "8192 bands": (dict(block=15360, interval=3840, split=False), 6, 2.7e-3),  # 32 bins per thread: the LDS form and the bisection
+}
+
+
+def feed_scan_shape(name):
+    """(geometry, input samples, bound) of one of FEED_SCAN_SHAPES"""
+    geometry, hops, own = FEED_SCAN_SHAPES[name]
+    return geometry, hops*geometry["interval"] + geometry["block"]//4, SELF_FACTOR*own
+
+
+def case_feed_scan_close_to_serial(lib, monkeypatch, geometry, streams, n, bound, setup=feed_scan_setup, channels=2, measure_self=False):
+    """The feed recurrences (smoothing, peaks, map, formant envelope) run in scan form; SMST_FEED_SERIAL=1 evaluates them
+    bin by bin in the reference's order.  Only the carries entering a chunk round differently: the outputs of all `streams`
+    streams together (sine, chirp, noise, ...: none is left out) agree within `bound` relative RMS.
+
+    The bounds of FEED_SCAN_SHAPES are SELF_FACTOR times the serial form's own response to an input perturbed by PERTURBATION
+    (`measure_self`: that figure is measured and returned too), over the same 3 streams and length.  Measured on the CPU stand-in
+    before the forms came to share their steps -- scan against serial | serial against serial of the perturbed input; all streams,
+    then sine / chirp / noise alone:
+       160 bands  0        (0, 0, 0)                | 4.61e-6 (8.1e-7, 1.5e-6, 1.4e-5)
+       256 bands  5.6e-9   (8.8e-9, 0, 0)           | 3.53e-4 (5.5e-4, 1.9e-6, 9.1e-6)
+      5120 bands  3.6e-8   (2.9e-8, 4.4e-8, 0)      | 1.55e-3 (2.2e-5, 8.9e-4, 4.5e-3)
+      8192 bands  9.3e-8   (1.2e-7, 8.0e-8, 0)      | 2.72e-3 (6.5e-6, 1.7e-4, 8.5e-3)
+    (the noise stream has the map alone: its peak lists come out the same in both forms, so its outputs are identical)."""
+    pkg = package()
+    sr = 48000
+    x = np.stack([synth_input(s, channels, n, sr) for s in range(streams)])
+    runs = [(False, x), (True, x)] + ([(True, np.stack([perturbed(v, 1 + s) for s, v in enumerate(x)]))] if measure_self else [])
+    outs = []
+    for serial, xin in runs:
+        if serial:
+            monkeypatch.setenv("SMST_FEED_SERIAL", "1")
+        else:
+            monkeypatch.delenv("SMST_FEED_SERIAL", raising=False)
+        b = pkg.StretchBatch(streams, channels, lib=lib, **geometry)
+        setup(b)
+        outs.append(np.array(b.process(xin, int(n*0.9)), copy=True))
+        b.close()
+    monkeypatch.delenv("SMST_FEED_SERIAL", raising=False)
+    assert np.abs(outs[1]).max() > 0.05
+    figures = dict(scan_vs_serial=rel_rms(outs[0], outs[1]), per_stream=[rel_rms(outs[0][s], outs[1][s]) for s in range(streams)])
+    if measure_self:
+        figures.update(serial_self=rel_rms(outs[2], outs[1]), serial_self_per_stream=[rel_rms(outs[2][s], outs[1][s]) for s in range(streams)])
+    print(geometry, figures)
+    assert figures["scan_vs_serial"] < bound, (geometry, figures, bound)
+    return figures
+
+
+def case_feed_fusion_equals_separate(lib, monkeypatch, channel_counts=(2, 3), geometry=None, n=9000, formants=False, bases_given=False, one_pass=True):
     """Pass A folded into the feed kernel (tiles with a pitch map and no formant processing) against the separate kPredictA
     (SMST_NO_FEED_FUSION=1): the same arithmetic on the same operands, so bit-identical -- mapped and unmapped streams side
     by side, two calls.  `formants`: tiles with formant processing fold pass A into the envelope kernel (the ratios stay in LDS);
     `bases_given`: every formant stream has a base frequency, so the whole feed stage is ONE kernel (kFeedScanA<.., FUSE_FORM>, round 6) --
-    compared with the two-pass form (SMST_NO_FEED_FUSION=2) and the separate kernels (=1); the launch counter proves which ran."""
+    compared with the two-pass form (SMST_NO_FEED_FUSION=2) and the separate kernels (=1); the launch counter proves which ran.
+    `one_pass=False`: a plan beyond the register-resident forms (more than 24 bins per thread), which has no one-pass form: the
+    counter must not grow in any mode."""
     pkg = package()
     geometry = geometry or dict(block=512, interval=128, split=False)
     for C in channel_counts:
@@ -407,7 +472,7 @@ def case_feed_fusion_equals_separate(lib, monkeypatch, channel_counts=(2, 3), ge
             y2 = np.array(b.process(xs[:, :, n//3:], int((n - n//3)*0.9)), copy=True)
             b.close()
             grew = pkg.launch_count("feed_one_pass", lib) - before
-            assert (grew > 0) == (bases_given and mode is None), (mode, grew)
+            assert (grew > 0) == (one_pass and bases_given and mode is None), (mode, grew)
             outs.append(np.concatenate([y1, y2], axis=2))
         monkeypatch.delenv("SMST_NO_FEED_FUSION", raising=False)
         assert np.abs(outs[0]).max() > 0.05

@@ -88,6 +88,21 @@ def test_feed_fusion_equals_separate(emu, monkeypatch):
     pc.case_feed_fusion_equals_separate(emu, monkeypatch)
     pc.case_feed_fusion_equals_separate(emu, monkeypatch, channel_counts=(2,), formants=True)
     pc.case_feed_fusion_equals_separate(emu, monkeypatch, channel_counts=(2, 3), formants=True, bases_given=True)  # the one-pass form (round 6)
+    # 20 bins per thread (kFeedScanA<24, true>, <24, false, true>, kFeedScanC<24, true>; every 96 kHz preset), three intervals
+    g24 = dict(block=10240, interval=2560, split=False)
+    pc.case_feed_fusion_equals_separate(emu, monkeypatch, channel_counts=(2,), geometry=g24, n=3*2560 + 2560)
+    pc.case_feed_fusion_equals_separate(emu, monkeypatch, channel_counts=(2,), geometry=g24, n=3*2560 + 2560, formants=True)
+    pc.case_feed_fusion_equals_separate(emu, monkeypatch, channel_counts=(2,), geometry=g24, n=3*2560 + 2560, formants=True, bases_given=True)
+    # 32 bins per thread: the LDS forms have no one-pass variant (the case asserts that the counter does not grow)
+    pc.case_feed_fusion_equals_separate(emu, monkeypatch, channel_counts=(2,), geometry=dict(block=15360, interval=3840, split=False), n=3*3840 + 3840, formants=True,
+                                        bases_given=True, one_pass=False)
+
+
+@pytest.mark.parametrize("shape", list(pc.FEED_SCAN_SHAPES))
+def test_feed_scan_close_to_serial(emu, monkeypatch, shape):
+    """Scan form against the bin-by-bin form (SMST_FEED_SERIAL=1) at the smallest shapes that reach each form of the feed kernels."""
+    geometry, n, bound = pc.feed_scan_shape(shape)
+    pc.case_feed_scan_close_to_serial(emu, monkeypatch, geometry, 3, n, bound)
 
 
 def test_single_hop_chunks(emu):

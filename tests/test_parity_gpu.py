@@ -251,23 +251,17 @@ def test_feed_scan_close_to_serial(hip, monkeypatch):
     """The feed recurrences (smoothing, peaks, map, formant envelope) run in scan form; SMST_FEED_SERIAL=1 evaluates them
     bin by bin in the reference's order.  Only the carries entering a chunk round differently: the outputs agree to the
     level a 1e-6 input perturbation moves them (measured 5e-8 .. 4e-6 relative RMS on 0.5 s)."""
-    import torch
-    pkg = package()
-    S, C, sr, n = 6, 2, 48000, 24000
-    x = torch.from_numpy(np.stack([synth_input(s, C, n, sr) for s in range(S)])).cuda()
-    outs = []
-    for serial in (False, True):
-        if serial:
-            monkeypatch.setenv("SMST_FEED_SERIAL", "1")
-        b = pkg.StretchBatch(S, C, preset="default", sample_rate=sr, lib=hip)
-        b.setTransposeSemitones(4, 8000/48000)
-        b.setFormantFactor(1.2, True)
-        y = b.process(x, int(n*0.9))
-        b.synchronize()
-        outs.append(y.clone())
-        b.close()
-    d = (outs[0] - outs[1]).pow(2).mean().sqrt()/outs[1].pow(2).mean().sqrt()
-    assert float(d) < 2e-4, float(d)
+    pc.case_feed_scan_close_to_serial(hip, monkeypatch, D48, 6, 24000, 2e-4,
+                                      setup=lambda b: (b.setTransposeSemitones(4, 8000/48000), b.setFormantFactor(1.2, True)))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("shape", list(pc.FEED_SCAN_SHAPES))
+def test_feed_scan_close_to_serial_shapes(hip, monkeypatch, shape):
+    """The same at the smallest shapes that reach each form of the feed kernels (threads without a bin, one bin per thread, the
+    <24> instantiations, the LDS form with the bisection): pitch map, formants with an estimated and with a given base."""
+    geometry, n, bound = pc.feed_scan_shape(shape)
+    pc.case_feed_scan_close_to_serial(hip, monkeypatch, geometry, 3, n, bound)
 
 
 @pytest.mark.gpu
@@ -527,6 +521,14 @@ def test_feed_fusion_equals_separate(hip, monkeypatch):
     pc.case_feed_fusion_equals_separate(hip, monkeypatch, channel_counts=(2,), geometry=dict(preset="default", sample_rate=48000.0), n=40000, formants=True)
     pc.case_feed_fusion_equals_separate(hip, monkeypatch, channel_counts=(1, 2, 8), formants=True, bases_given=True)  # every base frequency given: the feed stage is ONE kernel
     pc.case_feed_fusion_equals_separate(hip, monkeypatch, channel_counts=(2,), geometry=dict(preset="default", sample_rate=48000.0), n=40000, formants=True, bases_given=True)
+    # 20 bins per thread (kFeedScanA<24, true>, <24, false, true>, kFeedScanC<24, true>; every 96 kHz preset), three intervals
+    g24 = dict(block=10240, interval=2560, split=False)
+    pc.case_feed_fusion_equals_separate(hip, monkeypatch, channel_counts=(2,), geometry=g24, n=3*2560 + 2560)
+    pc.case_feed_fusion_equals_separate(hip, monkeypatch, channel_counts=(2,), geometry=g24, n=3*2560 + 2560, formants=True)
+    pc.case_feed_fusion_equals_separate(hip, monkeypatch, channel_counts=(2,), geometry=g24, n=3*2560 + 2560, formants=True, bases_given=True)
+    # 32 bins per thread: the LDS forms have no one-pass variant (the case asserts that the counter does not grow)
+    pc.case_feed_fusion_equals_separate(hip, monkeypatch, channel_counts=(2,), geometry=dict(block=15360, interval=3840, split=False), n=3*3840 + 3840, formants=True,
+                                        bases_given=True, one_pass=False)
 
 
 def test_gather_pass_shapes(hip, monkeypatch):
