@@ -244,15 +244,22 @@ int smst_batch_output_seek(smst_batch *b, const float *in, long long inStreamStr
 /* ---- interleaved PCM (EXTENSION: the reference's process() is templated on its buffers, so a caller there can hand it an adaptor over an
  * interleaved frame buffer; here the conversion is part of the call and runs on the GPU) ----
  * The four calls above with FRAME buffers: sample (s, i, c) at base[s*streamStride + i*frameStride + c], strides in ELEMENTS of the
- * format, frameStride >= channels; the pointers need the element's alignment only (2 bytes for int16), no stride need be a multiple of
- * 16 bytes.  `format` holds for the input and the output of a call; counts, rates and lengths are as in the planar calls (frames per
+ * format, frameStride >= channels; the pointers need the element's alignment only (2 bytes for int16, ONE byte for packed int24, whose
+ * strides count elements of 3 bytes), no stride need be a multiple of 16 bytes.  `format` holds for the input and the output of a call; counts, rates and lengths are as in the planar calls (frames per
  * stream; flush_pcm keeps the negative-count rule).
  *   SMST_PCM_S16  in: float(v)/32768 (exact).  out: q = roundf(v*32768), ties away from zero, clamped to [-32768, 32767], no dither --
  *                 the rule the CLI writes WAV files with.  NaN gives 0 (the CLI has no such case: a NaN there ends as -32768).
  *   SMST_PCM_F32  copied bit for bit.
+ *   SMST_PCM_S24  3 bytes per sample, little-endian two's complement, packed without padding (a WAV file's 24-bit data chunk).
+ *                 in: float(v)/8388608 (exact).  out: roundf(v*8388608), ties away from zero, clamped to [-8388608, 8388607]; NaN gives 0.
+ *   SMST_PCM_S32  in: the int32 converted to float32 (round to nearest even: the engine is fp32, codes above 2^24 lose their low bits)
+ *                 times 2^-31.  out: roundf(v*2^31) clamped to [-2^31, 2^31 - 1] -- a product at or above 2^31 gives 2147483647 --; NaN gives 0.
+ *   SMST_PCM_F16  IEEE binary16.  in: widened exactly.  out: round to nearest even, subnormal halves kept, magnitudes of 65520 and above
+ *                 +-inf, NaN stays NaN (numpy's float32 -> float16).
+ *   (3 and 7 are no formats.)
  * The engine still works on a planar fp32 image of the call, now the library's own: a conversion kernel in front of the call and one behind it.
  * SMST_MEM_HOST: each stream's frames are gathered into pinned memory (one memcpy per stream; a frameStride > channels is gathered frame by
- *   frame), cross PCIe as ONE copy per direction -- half the bytes of the planar call for int16 --, and the call returns with the output in place.
+ *   frame), cross PCIe as ONE copy per direction -- half the bytes of the planar call for int16 and float16, 3/4 for int24 --, and the call returns with the output in place.
  * SMST_MEM_DEVICE: the kernels read / write the caller's device pointers; the call is asynchronous exactly as smst_batch_process is.
  * Ordering contract: the input conversion runs on the batch's stream behind everything smst_batch_wait_for_stream has ordered it after,
  *   and every reader of the call's input -- the silence gate runs on a stream of its own -- is ordered behind it by the edge
@@ -262,6 +269,9 @@ int smst_batch_output_seek(smst_batch *b, const float *in, long long inStreamStr
  * SMST_ERR_INVALID with a message: an unknown format, frameStride < channels, a null buffer with a non-zero count. */
 #define SMST_PCM_S16 1 /* int16, full scale 32768 */
 #define SMST_PCM_F32 2 /* float32 */
+#define SMST_PCM_S24 4 /* packed 24-bit integer, full scale 8388608 */
+#define SMST_PCM_S32 5 /* int32, full scale 2^31 */
+#define SMST_PCM_F16 6 /* IEEE binary16 */
 int smst_batch_process_pcm(smst_batch *b, const void *in, long long inStreamStride, long long inFrameStride, const int *inSamples,
                            void *out, long long outStreamStride, long long outFrameStride, const int *outSamples,
                            int format, int memory);
@@ -278,6 +288,18 @@ int smst_batch_output_seek_pcm(smst_batch *b, const void *in, long long inStream
 int smst_debug_pcm_convert(int device, int dir, int format, int streams, int channels, const int *counts,
                            const void *src, long long srcStreamStride, long long srcInnerStride,
                            void *dst, long long dstStreamStride, long long dstInnerStride);
+/* Overs.  The output conversions of process_pcm and flush_pcm count, per stream, the elements they could not represent: clamped[s] = those
+ * whose code the clamp set (integer formats) or that became +-inf from a finite value (float16); nans[s] = those whose input was NaN (every
+ * format, float32 included).  The counters ([streams][2], 32 bits each, device memory allocated with the batch and part of
+ * smst_batch_workspace_bytes) are added to by the conversion kernel itself: the calls allocate and synchronise nothing for them. */
+/* overs of the _pcm output conversions (process_pcm, flush_pcm) since the last take, per stream; either pointer may be null.
+ * Synchronises the batch. */
+int smst_batch_take_pcm_overs(smst_batch *b, long long *clamped, long long *nans);
+/* smst_debug_pcm_convert for dir 1, also returning the counts the kernel made ([streams] each) */
+int smst_debug_pcm_convert_counted(int device, int format, int streams, int channels, const int *counts,
+                                   const void *src, long long srcStreamStride, long long srcInnerStride,
+                                   void *dst, long long dstStreamStride, long long dstInnerStride,
+                                   long long *clamped, long long *nans);
 int smst_batch_synchronize(smst_batch *b);
 /* raw hipStream_t the batch enqueues on (so callers can order their own device work against it) */
 void *smst_batch_hip_stream(smst_batch *b);
@@ -329,8 +351,9 @@ int smst_batch_debug_get_formants(smst_batch *b, int stream, float *ratio, float
  * (a.re, a.im, b.re, b.im, c.re, c.im, fraction), out = n x (a*b, a*conj(b), a*b + c, a + (b - a)*fraction) as 8 floats. */
 int smst_debug_complex_selftest(int device, const float *in, float *out, int n);
 /* launches, since the library was loaded, of one kernel variant: "vocoder_aligned", "vocoder_staged", "vocoder_gather",
- * "vocoder_n", "vocoder_one", "vocoder_across", "chain_unfused", "analyse_teams", "analyse_fast", "analyse_generic",
- * "synth_teams", "synth_fast", "synth_generic", "pcm_in", "pcm_out" (the conversion kernels of the _pcm calls) (-1: unknown name).  The "this form is bit-identical to that form" tests
+ * "vocoder_n", "vocoder_one", "vocoder_across", "vocoder_continuous", "chain_unfused", "analyse_teams", "analyse_fast", "analyse_generic",
+ * "synth_teams", "synth_fast", "synth_generic", "synth_emit", "emit_carried", "feed_one_pass", "pcm_in", "pcm_out" (the conversion kernels of the _pcm calls, whatever
+ * the format) (-1: unknown name).  The "this form is bit-identical to that form" tests
  * assert through it that both forms really ran. */
 long long smst_debug_launch_count(const char *name);
 

@@ -25,7 +25,9 @@ LIBRARY_PATH = os.environ.get("SMST_LIBRARY") or os.path.join(_HERE, "libsmst_hi
 CSRC_DIR = os.path.join(_HERE, "csrc")
 
 MEM_HOST, MEM_DEVICE = 0, 1
-PCM_S16, PCM_F32 = 1, 2  # frame formats of the *_pcm calls (include/smst.h)
+PCM_S16, PCM_F32, PCM_S24, PCM_S32, PCM_F16 = 1, 2, 4, 5, 6  # frame formats of the *_pcm calls (include/smst.h)
+_FRAME_DTYPES = {"int16": PCM_S16, "float32": PCM_F32, "int32": PCM_S32, "float16": PCM_F16}  # (packed int24 travels as uint8 [..., 3])
+_FRAME_DTYPE_OF = {PCM_S16: "int16", PCM_F32: "float32", PCM_S32: "int32", PCM_F16: "float16", PCM_S24: "uint8"}
 _fp = C.POINTER(C.c_float)
 _ip = C.POINTER(C.c_int)
 _dp = C.POINTER(C.c_double)
@@ -112,6 +114,8 @@ _SIGNATURES = {
     "smst_batch_flush_pcm": (C.c_int, [C.c_void_p, C.c_void_p, _ll, _ll, _ip, _fp, C.c_int, C.c_int]),
     "smst_batch_output_seek_pcm": (C.c_int, [C.c_void_p, C.c_void_p, _ll, _ll, _ip, C.c_int, C.c_int]),
     "smst_debug_pcm_convert": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _ip, C.c_void_p, _ll, _ll, C.c_void_p, _ll, _ll]),
+    "smst_debug_pcm_convert_counted": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _ip, C.c_void_p, _ll, _ll, C.c_void_p, _ll, _ll, C.POINTER(_ll), C.POINTER(_ll)]),
+    "smst_batch_take_pcm_overs": (C.c_int, [C.c_void_p, C.POINTER(_ll), C.POINTER(_ll)]),
     "smst_batch_synchronize": (C.c_int, [C.c_void_p]),
     "smst_batch_hip_stream": (C.c_void_p, [C.c_void_p]),
     "smst_batch_enable_profiling": (C.c_int, [C.c_void_p, C.c_int]),
@@ -405,22 +409,40 @@ class StretchBatch:
             self._order_after_torch(x)
         _check(self.lib, self.lib.smst_batch_output_seek(self.h, ptr, ss, cs, pin, mem))
 
-    # --- interleaved PCM frames (smst_batch_*_pcm): [S, n, C] of int16 or float32, the same dtype and layout back
+    # --- interleaved PCM frames (smst_batch_*_pcm): [S, n, C] of int16, int32, float16 or float32, or packed int24 as uint8 [S, n, C, 3];
+    # the same dtype and layout back
     def _describe_frames(self, x, what):
-        """-> (pointer, streamStride, frameStride, frames, format, memory, keepalive); strides in elements"""
-        if _is_torch(x):
-            if x.dim() != 3 or x.shape[0] != self.streams or x.shape[2] != self.channels:
-                raise StretchError("%s must be [S, n, C]" % what)
-            fmt = {"torch.int16": PCM_S16, "torch.float32": PCM_F32}.get(str(x.dtype))
-            if fmt is None or not x.is_cuda or x.stride(2) != 1:
-                raise StretchError("%s: need an int16 or float32 GPU tensor with contiguous channels" % what)
-            return C.c_void_p(x.data_ptr()), x.stride(0), x.stride(1), x.shape[1], fmt, MEM_DEVICE, x
-        a = np.asarray(x)
-        fmt = {"int16": PCM_S16, "float32": PCM_F32}.get(a.dtype.name)
+        """-> (pointer, streamStride, frameStride, frames, format, memory, keepalive); strides in elements.
+
+        Frames are [S, n, C] of int16, int32, float16 or float32, or -- packed 24-bit, SMST_PCM_S24 -- uint8 of shape [S, n, C, 3]: three
+        little-endian bytes per sample.  numpy arrays are host memory, torch GPU tensors device memory.  The channels of a frame (and the
+        bytes of a 24-bit sample) must be contiguous; the stream and frame strides are free -- whole elements, so multiples of 3 bytes
+        for packed int24, which needs no alignment beyond the byte."""
+        torch_x = _is_torch(x)
+        a = x if torch_x else np.asarray(x)
+        name = str(a.dtype).replace("torch.", "")
+        ndim = a.dim() if torch_x else a.ndim
+        s24 = name == "uint8" and ndim == 4 and a.shape[3] == 3
+        fmt = PCM_S24 if s24 else _FRAME_DTYPES.get(name)
         if fmt is None:
-            raise StretchError("%s: frames are int16 or float32" % what)
-        if a.ndim != 3 or a.shape[0] != self.streams or a.shape[2] != self.channels:
-            raise StretchError("%s must be [S, n, C]" % what)
+            raise StretchError("%s: frames are int16, int32, float16 or float32 [S, n, C], or uint8 [S, n, C, 3] (packed int24)" % what)
+        if ndim != (4 if s24 else 3) or a.shape[0] != self.streams or a.shape[2] != self.channels:
+            raise StretchError("%s must be [S, n, C]%s" % (what, " x 3 bytes" if s24 else ""))
+        if torch_x:
+            if not x.is_cuda or x.stride(ndim - 1) != 1 or (s24 and x.stride(2) != 3):
+                raise StretchError("%s: need a GPU tensor with contiguous channels" % what)
+            if s24 and (x.stride(0) % 3 or x.stride(1) % 3):
+                raise StretchError("%s: the stream and frame strides of packed int24 frames must be multiples of 3 bytes" % what)
+            unit = 3 if s24 else 1
+            return C.c_void_p(x.data_ptr()), x.stride(0)//unit, x.stride(1)//unit, x.shape[1], fmt, MEM_DEVICE, x
+        if s24:
+            if a.size and (a.strides[3] != 1 or a.strides[2] != 3):
+                a = np.ascontiguousarray(a)
+            if a.size and (a.strides[0] % 3 or a.strides[1] % 3 or a.strides[0] < 0 or a.strides[1] < 3*a.shape[2]):
+                raise StretchError("%s: the stream and frame strides of packed int24 frames must be multiples of 3 bytes" % what)
+            if a.size == 0:
+                return C.c_void_p(a.ctypes.data), a.shape[1]*a.shape[2], a.shape[2], a.shape[1], fmt, MEM_HOST, a
+            return C.c_void_p(a.ctypes.data), a.strides[0]//3, a.strides[1]//3, a.shape[1], fmt, MEM_HOST, a
         if a.size and (a.strides[2] != a.itemsize or a.strides[0] % a.itemsize or a.strides[1] % a.itemsize or a.strides[0] < 0 or a.strides[1] < a.itemsize*a.shape[2]):
             a = np.ascontiguousarray(a)
         if a.size == 0:  # (numpy gives an empty array zero strides)
@@ -428,15 +450,18 @@ class StretchBatch:
         return C.c_void_p(a.ctypes.data), a.strides[0]//a.itemsize, a.strides[1]//a.itemsize, a.shape[1], fmt, MEM_HOST, a
 
     def _new_frames(self, frames, fmt, like):
+        shape = (self.streams, frames, self.channels) + ((3,) if fmt == PCM_S24 else ())
         if like is not None and _is_torch(like):
             import torch
-            return torch.zeros((self.streams, frames, self.channels), dtype=torch.int16 if fmt == PCM_S16 else torch.float32, device=like.device)
-        return np.zeros((self.streams, frames, self.channels), np.int16 if fmt == PCM_S16 else np.float32)
+            return torch.zeros(shape, dtype=getattr(torch, _FRAME_DTYPE_OF[fmt]), device=like.device)
+        return np.zeros(shape, _FRAME_DTYPE_OF[fmt])
 
     def processFrames(self, x, out_samples, in_samples=None, out=None, ordered=True):
-        """process() on interleaved frames: x is [S, n, C] int16 (full scale 32768) or float32, numpy (host memory) or a torch GPU tensor;
-        the result has the same dtype and layout.  int16 output is round-to-nearest, ties away from zero, clamped, no dither; NaN -> 0
-        (include/smst.h).  ``ordered`` as in process()."""
+        """process() on interleaved frames: x is [S, n, C] int16 (full scale 32768), int32 (2^31), float16 or float32, or uint8
+        [S, n, C, 3] for packed int24 (8388608), numpy (host memory) or a torch GPU tensor (_describe_frames has the layout rules); the
+        result has the same dtype and shape convention.  Integer output is round-to-nearest, ties away from zero, clamped, no dither;
+        NaN -> 0.  int32 input above 2^24 is rounded to float32.  float16 output is round-to-nearest-even: subnormals kept, 65520 and
+        above +-inf, NaN stays NaN (include/smst.h).  What was clamped: takePcmOvers().  ``ordered`` as in process()."""
         S = self.streams
         ptr, ss, fs, n, fmt, mem, keep = self._describe_frames(x, "input")
         nin, pin = _int_array(n if in_samples is None else in_samples, S)
@@ -469,11 +494,12 @@ class StretchBatch:
         _check(self.lib, self.lib.smst_batch_seek_pcm(self.h, ptr, ss, fs, pin, r.ctypes.data_as(_dp), fmt, mem))
 
     def flushFrames(self, out_samples, rates=0.0, like=None, dtype=np.int16):
-        """flush() into [S, n, C] frames of ``dtype`` (int16 or float32); a negative count leaves that stream alone"""
+        """flush() into [S, n, C] frames of ``dtype`` (int16, int32, float16 or float32), or with dtype="s24" into uint8 [S, n, C, 3]
+        (packed int24); a negative count leaves that stream alone"""
         S = self.streams
-        fmt = {"int16": PCM_S16, "float32": PCM_F32}.get(np.dtype(dtype).name)
+        fmt = PCM_S24 if isinstance(dtype, str) and dtype.lower() == "s24" else _FRAME_DTYPES.get(np.dtype(dtype).name)
         if fmt is None:
-            raise StretchError("frames are int16 or float32")
+            raise StretchError("frames are int16, int32, float16, float32 or \"s24\"")
         nout, pout = _int_array(out_samples, S)
         r = np.ascontiguousarray(np.broadcast_to(np.asarray(rates, dtype=np.float32), (S,)))
         out = self._new_frames(max(int(nout.max()), 1), fmt, like)
@@ -490,6 +516,15 @@ class StretchBatch:
         if mem == MEM_DEVICE:
             self._order_after_torch(x)
         _check(self.lib, self.lib.smst_batch_output_seek_pcm(self.h, ptr, ss, fs, pin, fmt, mem))
+
+    def takePcmOvers(self):
+        """-> (clamped, nans), int64 [S]: per stream, the output elements of processFrames / flushFrames since the last take whose code
+        the clamp set (integer formats) or that became +-inf from a finite value (float16), and those whose input was NaN (every
+        format).  Synchronises the batch and clears the counters."""
+        clamped, nans = np.zeros(self.streams, np.int64), np.zeros(self.streams, np.int64)
+        _check(self.lib, self.lib.smst_batch_take_pcm_overs(self.h, clamped.ctypes.data_as(C.POINTER(_ll)), nans.ctypes.data_as(C.POINTER(_ll))))
+        self._inflight = []
+        return clamped, nans
 
     # --- test hooks
     def debug_state(self, stream, which):

@@ -32,6 +32,9 @@ struct smst_batch {
 	size_t dPcmInCap = 0, dPcmOutCap = 0, hPcmInCap = 0, hPcmOutCap = 0;
 	struct PcmCounts { int *host = nullptr, *dev = nullptr; hipEvent_t done = nullptr; bool used = false; } pcmCounts[2]; // [2*S]: input frames, output frames
 	int pcmCur = 0;
+	// overs of the output conversions ([S][2]: clamped, NaN): the kernels add to them, smst_batch_take_pcm_overs reads and clears them
+	unsigned *dPcmOvers = nullptr;
+	std::vector<unsigned> hPcmOvers;
 	~smst_batch() {
 		if (engine) hipSetDevice(engine->device());
 		if (dIn) hipFree(dIn);
@@ -40,6 +43,7 @@ struct smst_batch {
 		if (dPcmOut) hipFree(dPcmOut);
 		if (hPcmIn) hipHostFree(hPcmIn);
 		if (hPcmOut) hipHostFree(hPcmOut);
+		if (dPcmOvers) hipFree(dPcmOvers);
 		for (PcmCounts &c : pcmCounts) {
 			if (c.dev) hipFree(c.dev);
 			if (c.host) hipHostFree(c.host);
@@ -118,6 +122,8 @@ static void ensureStage(float *&ptr, size_t &cap, size_t need, int device, long 
 	cap = want;
 }
 
+static size_t pcmOversBytes(int streams) { return (size_t)2*streams*sizeof(unsigned); }
+
 extern "C" {
 
 const char *smst_last_error(void) { return g_lastError.c_str(); }
@@ -140,6 +146,9 @@ int smst_batch_create_ex(smst_batch **out, int streams, int channels, int block,
 	if (device < 0 || device >= n) throw smst::Error("device ordinal out of range");
 	std::unique_ptr<smst_batch> b(new smst_batch());
 	b->engine.reset(new Batch(streams, channels, block, interval, split != 0, device, seed, (flags & SMST_FLAG_HALF_STATE) != 0));
+	b->hPcmOvers.assign((size_t)2*streams, 0u);
+	if (hipMalloc(reinterpret_cast<void **>(&b->dPcmOvers), pcmOversBytes(streams)) != hipSuccess) throw smst::Error("hipMalloc (PCM overs) failed", true);
+	if (hipMemset(b->dPcmOvers, 0, pcmOversBytes(streams)) != hipSuccess) throw smst::Error("hipMemset (PCM overs) failed", true);
 	*out = b.release();
 	return SMST_OK;
 	SMST_CATCH
@@ -173,7 +182,7 @@ BATCH_Q(smst_batch_output_latency, b->engine->outputLatency())
 BATCH_Q(smst_batch_seek_length, b->engine->seekLength())
 BATCH_Q(smst_batch_half_state, b->engine->halfPrecisionState() ? 1 : 0)
 int smst_batch_output_seek_length(const smst_batch *b, float rate) { if (!b || !b->engine) return fail("null batch"); return b->engine->outputSeekLength(rate); }
-long long smst_batch_workspace_bytes(const smst_batch *b) { if (!b || !b->engine) return fail("null batch"); return (long long)b->engine->workspaceBytes(); }
+long long smst_batch_workspace_bytes(const smst_batch *b) { if (!b || !b->engine) return fail("null batch"); return (long long)(b->engine->workspaceBytes() + (b->dPcmOvers ? pcmOversBytes(b->engine->streams()) : 0)); }
 
 #define BATCH_CALL(body) if (!b || !b->engine) return fail("null batch"); SMST_TRY body; return SMST_OK; SMST_CATCH
 
@@ -343,10 +352,10 @@ int smst_batch_output_seek(smst_batch *b, const float *in, long long ss, long lo
 }
 
 // ---------------------------------------------------------------------------------------------------------
-// interleaved PCM: the four calls above with frame buffers of int16 / float32 (include/smst.h).  kPcmIn fills the planar image the engine
+// interleaved PCM: the four calls above with frame buffers of the SMST_PCM_* formats (include/smst.h).  kPcmIn fills the planar image the engine
 // reads, kPcmOut empties the one it wrote; both run on the engine's stream.
 // ---------------------------------------------------------------------------------------------------------
-static size_t pcmElemBytes(int format) { return format == SMST_PCM_S16 ? sizeof(int16_t) : sizeof(float); }
+static size_t pcmElemBytes(int format) { return format == SMST_PCM_S16 || format == SMST_PCM_F16 ? 2 : format == SMST_PCM_S24 ? 3 : 4; }
 static void ensurePcmBytes(unsigned char *&ptr, size_t &cap, size_t need, bool pinned, int device, long long &allocs) {
 	if (need <= cap) return;
 	++allocs;
@@ -368,7 +377,8 @@ static void checkPcmSide(const void *buf, long long frameStride, const int *n, i
 	}
 }
 static void checkPcmFormat(int format, int memory) {
-	if (format != SMST_PCM_S16 && format != SMST_PCM_F32) throw smst::Error("unknown PCM format (SMST_PCM_S16 or SMST_PCM_F32)");
+	if (format != SMST_PCM_S16 && format != SMST_PCM_F32 && format != SMST_PCM_S24 && format != SMST_PCM_S32 && format != SMST_PCM_F16)
+		throw smst::Error("unknown PCM format (SMST_PCM_S16, _F32, _S24, _S32 or _F16)");
 	if (memory != SMST_MEM_HOST && memory != SMST_MEM_DEVICE) throw smst::Error("unknown memory kind");
 }
 // the count tables of this call: the set the call before the previous one used (its conversion kernels must have run)
@@ -392,8 +402,8 @@ static void endPcmCall(smst_batch *b, smst_batch::PcmCounts &c) {
 	if (hipEventRecord(c.done, b->engine->stream()) != hipSuccess) throw smst::Error("hipEventRecord failed", true);
 	c.used = true;
 }
-// a stream's row in the library's own raw buffers: its frames densely, rows a multiple of 32 bytes apart
-static long long pcmRowElems(int maxFrames, int C) { return ((long long)maxFrames*C + 7)/8*8; }
+// a stream's row in the library's own raw buffers: its frames densely, rows a multiple of 16 bytes apart for every element size
+static long long pcmRowElems(int maxFrames, int C) { return ((long long)maxFrames*C + 15)/16*16; }
 
 // Raw frames -> the planar image b->dIn [S][C][maxLen] (returns maxLen), on the engine's stream and in front of every reader of the call's input
 static int pcmStageIn(smst_batch *b, smst_batch::PcmCounts &c, const void *in, long long ss, long long fs, const int *n, int format, int memory) {
@@ -455,13 +465,13 @@ static void pcmStageOut(smst_batch *b, smst_batch::PcmCounts &c, void *out, long
 	for (int s = 0; s < S; ++s) most = std::max(most, n[s]);
 	hipSetDevice(e.device());
 	if (memory == SMST_MEM_DEVICE) {
-		smst::launchPcmOut(format, b->dOut, (long long)C*maxLen, maxLen, out, ss, fs, c.dev + S, S, C, most, e.stream());
+		smst::launchPcmOut(format, b->dOut, (long long)C*maxLen, maxLen, out, ss, fs, c.dev + S, S, C, most, b->dPcmOvers, e.stream());
 		return;
 	}
 	if (most < 1) return;
 	const size_t esz = pcmElemBytes(format);
 	const long long row = pcmRowElems(most, C);
-	smst::launchPcmOut(format, b->dOut, (long long)C*maxLen, maxLen, b->dPcmOut, row, C, c.dev + S, S, C, most, e.stream());
+	smst::launchPcmOut(format, b->dOut, (long long)C*maxLen, maxLen, b->dPcmOut, row, C, c.dev + S, S, C, most, b->dPcmOvers, e.stream());
 	if (hipMemcpyAsync(b->hPcmOut, b->dPcmOut, (size_t)S*row*esz, hipMemcpyDeviceToHost, e.stream()) != hipSuccess) throw smst::Error("hipMemcpyAsync (D2H) failed", true);
 	if (hipStreamSynchronize(e.stream()) != hipSuccess) throw smst::Error("hipStreamSynchronize failed", true);
 	for (int s = 0; s < S; ++s) {
@@ -529,8 +539,9 @@ int smst_batch_output_seek_pcm(smst_batch *b, const void *in, long long ss, long
 		if (memory == SMST_MEM_HOST) e.synchronize();
 	})
 }
-int smst_debug_pcm_convert(int device, int dir, int format, int streams, int channels, const int *counts,
-                           const void *src, long long srcSS, long long srcInner, void *dst, long long dstSS, long long dstInner) {
+} // extern "C"
+static int pcmConvert(int device, int dir, int format, int streams, int channels, const int *counts,
+                      const void *src, long long srcSS, long long srcInner, void *dst, long long dstSS, long long dstInner, long long *clamped, long long *nans) {
 	SMST_TRY
 	checkPcmFormat(format, SMST_MEM_HOST);
 	if (dir != 0 && dir != 1) throw smst::Error("pcm convert: dir is 0 (PCM -> planar) or 1 (planar -> PCM)");
@@ -548,6 +559,9 @@ int smst_debug_pcm_convert(int device, int dir, int format, int streams, int cha
 	if (hipSetDevice(device) != hipSuccess) throw smst::Error("hipSetDevice failed", true);
 	unsigned char *dSrc = nullptr, *dDst = nullptr;
 	int *dCounts = nullptr;
+	unsigned *dOvers = nullptr;
+	std::vector<unsigned> overs((size_t)2*streams, 0u);
+	const bool counted = dir == 1 && (clamped || nans);
 	hipError_t err = hipMalloc(reinterpret_cast<void **>(&dSrc), srcBytes + 32);
 	if (err == hipSuccess) err = hipMalloc(reinterpret_cast<void **>(&dDst), dstBytes + 32);
 	if (err == hipSuccess) err = hipMalloc(reinterpret_cast<void **>(&dCounts), streams*sizeof(int));
@@ -556,19 +570,53 @@ int smst_debug_pcm_convert(int device, int dir, int format, int streams, int cha
 	if (err == hipSuccess && srcBytes) err = hipMemcpy(s0, src, srcBytes, hipMemcpyHostToDevice);
 	if (err == hipSuccess && dstBytes) err = hipMemcpy(d0, dst, dstBytes, hipMemcpyHostToDevice);
 	if (err == hipSuccess) err = hipMemcpy(dCounts, counts, streams*sizeof(int), hipMemcpyHostToDevice);
+	if (err == hipSuccess && counted) err = hipMalloc(reinterpret_cast<void **>(&dOvers), pcmOversBytes(streams));
+	if (err == hipSuccess && counted) err = hipMemcpy(dOvers, overs.data(), pcmOversBytes(streams), hipMemcpyHostToDevice);
 	if (err == hipSuccess) {
 		if (dir == 0) smst::launchPcmIn(format, s0, srcSS, srcInner, reinterpret_cast<float *>(d0), dstSS, dstInner, dCounts, streams, channels, most, nullptr);
-		else smst::launchPcmOut(format, reinterpret_cast<const float *>(s0), srcSS, srcInner, d0, dstSS, dstInner, dCounts, streams, channels, most, nullptr);
+		else smst::launchPcmOut(format, reinterpret_cast<const float *>(s0), srcSS, srcInner, d0, dstSS, dstInner, dCounts, streams, channels, most, dOvers, nullptr);
 		err = hipGetLastError();
 	}
 	if (err == hipSuccess) err = hipStreamSynchronize(nullptr);
 	if (err == hipSuccess && dstBytes) err = hipMemcpy(dst, d0, dstBytes, hipMemcpyDeviceToHost);
+	if (err == hipSuccess && counted) err = hipMemcpy(overs.data(), dOvers, pcmOversBytes(streams), hipMemcpyDeviceToHost);
 	if (dSrc) hipFree(dSrc);
 	if (dDst) hipFree(dDst);
 	if (dCounts) hipFree(dCounts);
+	if (dOvers) hipFree(dOvers);
 	if (err != hipSuccess) throw smst::Error(std::string("pcm convert: ") + hipGetErrorString(err), true);
+	for (int s = 0; s < streams; ++s) {
+		if (clamped) clamped[s] = overs[2*s];
+		if (nans) nans[s] = overs[2*s + 1];
+	}
 	return SMST_OK;
 	SMST_CATCH
+}
+extern "C" {
+int smst_debug_pcm_convert(int device, int dir, int format, int streams, int channels, const int *counts,
+                           const void *src, long long srcSS, long long srcInner, void *dst, long long dstSS, long long dstInner) {
+	return pcmConvert(device, dir, format, streams, channels, counts, src, srcSS, srcInner, dst, dstSS, dstInner, nullptr, nullptr);
+}
+int smst_debug_pcm_convert_counted(int device, int format, int streams, int channels, const int *counts,
+                                   const void *src, long long srcSS, long long srcInner, void *dst, long long dstSS, long long dstInner,
+                                   long long *clamped, long long *nans) {
+	if (!clamped || !nans) return fail("pcm convert: null count arrays");
+	return pcmConvert(device, 1, format, streams, channels, counts, src, srcSS, srcInner, dst, dstSS, dstInner, clamped, nans);
+}
+int smst_batch_take_pcm_overs(smst_batch *b, long long *clamped, long long *nans) {
+	BATCH_CALL({
+		Batch &e = *b->engine;
+		const int S = e.streams();
+		e.synchronize();
+		if (!b->dPcmOvers) throw smst::Error("this batch has no PCM over counters");
+		hipSetDevice(e.device());
+		if (hipMemcpy(b->hPcmOvers.data(), b->dPcmOvers, pcmOversBytes(S), hipMemcpyDeviceToHost) != hipSuccess) throw smst::Error("hipMemcpy (PCM overs) failed", true);
+		if (hipMemset(b->dPcmOvers, 0, pcmOversBytes(S)) != hipSuccess) throw smst::Error("hipMemset (PCM overs) failed", true);
+		for (int s = 0; s < S; ++s) {
+			if (clamped) clamped[s] = b->hPcmOvers[2*s];
+			if (nans) nans[s] = b->hPcmOvers[2*s + 1];
+		}
+	})
 }
 
 // ---------------------------------------------------------------------------------------------------------

@@ -204,12 +204,14 @@ void launchAddPreRoll(const DevBatch &d, const float *preRoll, int length, const
 void launchComplexSelfTest(const float *in, float *out, int n, hipStream_t st); // smst_complex.h against its documented formulas (test hook)
 void launchFlushTail(const DevBatch &d, const IoArgs &io, const int *tailOffset, const int *outOffset, hipStream_t st);
 void launchMoveStreams(const MoveArgs &a, hipStream_t st); // every segment of every pair in one launch
-// Interleaved PCM frames <-> the planar fp32 image (smst_pcm.h).  format: SMST_PCM_S16 / SMST_PCM_F32 of include/smst.h; strides in elements;
-// counts: [S] device, frames per stream; maxFrames: the largest of them (sizes the grid; nothing is launched for 0)
+// Interleaved PCM frames <-> the planar fp32 image (smst_pcm.h).  format: the SMST_PCM_* codes of include/smst.h; strides in elements (packed
+// int24: of 3 bytes); counts: [S] device, frames per stream; maxFrames: the largest of them (sizes the grid; nothing is launched for 0);
+// overs (may be null): [S][2] device counters that the output conversion adds its clamped / NaN elements to
 constexpr int kPcmTileFrames = 512; // frames one workgroup moves
+constexpr int kPcmS16 = 1, kPcmF32 = 2, kPcmS24 = 4, kPcmS32 = 5, kPcmF16 = 6;
 void launchPcmIn(int format, const void *in, long long inStreamStride, long long inFrameStride, float *out, long long outStreamStride, long long outChannelStride,
                  const int *counts, int S, int C, int maxFrames, hipStream_t st);
 void launchPcmOut(int format, const float *in, long long inStreamStride, long long inChannelStride, void *out, long long outStreamStride, long long outFrameStride,
-                  const int *counts, int S, int C, int maxFrames, hipStream_t st);
+                  const int *counts, int S, int C, int maxFrames, unsigned *overs, hipStream_t st);
 
 } // namespace smst

@@ -1,74 +1,179 @@
-// Interleaved PCM at the batch API's boundary (include/smst.h: smst_batch_*_pcm): frames of int16 or float32, channel-interleaved, to
-// and from the dense planar fp32 image [S][C][maxLen] that the engine consumes and emits.  Included by smst_state.hip only.
+// Interleaved PCM at the batch API's boundary (include/smst.h: smst_batch_*_pcm): frames of int16, packed int24, int32, float16 or
+// float32, channel-interleaved, to and from the dense planar fp32 image [S][C][maxLen] that the engine consumes and emits.  Included by
+// smst_state.hip only.
 //
 // Conversion.  int16 -> float: float(v)/32768 (exact).  float -> int16: q = roundf(v*32768) -- ties away from zero --, clamped to
 // [-32768, 32767], no dither: the rule tools/wav_io.h writes files with.  NaN gives 0; wav_io.h has no such case (its clamp turns a NaN
 // into -32768): a NaN here is a fault of the signal path, and silence is the one code that is not a full-scale click.
+// int24 (3 bytes, little-endian, packed) and int32: the same rule at full scale 2^23 and 2^31; an int32 above 2^24 is rounded to float32
+// (nearest even) on the way in, and the way out clamps the FLOAT before it becomes an integer (2^31 and above give 2147483647).
+// float16: widened exactly; narrowed round-to-nearest-even, subnormals kept, beyond 65520 to +-inf, NaN stays NaN.
 //
 // Shape.  A workgroup moves one tile of a stream's run -- kPcmTileFrames frames x C channels -- through LDS.  With frameStride == C the run
-// is contiguous: it is read / written as 16-byte accesses (8 int16 or 4 floats per lane).  The pointers are aligned to the element only,
-// so the run's first elements up to the first 16-byte boundary (tile 0) and its last ones behind the last whole 16 bytes (the last tile)
-// go one by one; the tiles in between begin and end ON 16-byte boundaries (tile t > 0 begins `head` elements behind t*tile, in the middle
-// of a frame if it has to), so narrow stores happen at a run's two ends only.  frameStride > C: every element goes by itself.
-// The planar side is rows of consecutive frames, one dword per lane.
+// is contiguous: it is read / written in GROUPS of G elements that fill W aligned 16-byte words (8 int16 / 4 floats in one word; 16 int24
+// in three: 3 is invertible mod 16, so whatever the base address one sample boundary in every 16 lies on a 16-byte boundary), W 16-byte
+// accesses per lane.  The pointers are aligned to the element only (int24: to the byte), so the run's first elements up to the first
+// group boundary (tile 0, at most G - 1) and its last ones behind the last whole group (the last tile) go one by one; the tiles in
+// between begin and end ON group boundaries (tile t > 0 begins `head` elements behind t*tile, in the middle of a frame if it has to: a
+// tile is a whole number of groups for every C), so narrow accesses happen at a run's two ends only.  frameStride > C: every element goes
+// by itself.  The planar side is rows of consecutive frames, one dword per lane.
 //
-// LDS image: element e of the tile (interleaved order) at dword e + e/32 (one pad dword per 32).  The 16-byte side touches it as V
-// ds_*_b32 per lane, lane stride V = 4 or 8 elements: lanes 4j..4j+3 (V = 8; 8j..8j+7 for V = 4) share a pad count and fill a residue
-// class of banks, the next group is shifted by one -- 32 lanes, 32 banks, for every C.  The row side has lane stride C: conflict-free
-// for C = 1, 2, 4, 8, 16 (the pad makes every 32/C-lane group start one bank further); for the other C one pad boundary inside the
-// 32 lanes' span can put two lanes on a bank -- 2-way at the worst (brute force over C = 1..16, every channel and lane group), which
-// a ds_write_b32 absorbs (kPcmOut) and which costs kPcmIn's ds_read_b32 one extra LDS cycle against ~100x that in memory time.
+// LDS image: element e of the tile (interleaved order) at dword e + e/32 (one pad dword per 32).  The group side touches it as G
+// ds_*_b32 per lane, lane stride G = 4, 8 or 16 elements: lanes 4j..4j+3 (G = 8; 8j..8j+7 for G = 4, 2j and 2j+1 for G = 16) share a pad
+// count and fill a residue class of banks, the next set is shifted by one -- 32 lanes, 32 banks, for every C.  The row side has lane
+// stride C: conflict-free for C = 1, 2, 4, 8, 16 (the pad makes every 32/C-lane group start one bank further); for the other C one pad
+// boundary inside the 32 lanes' span can put two lanes on a bank -- 2-way at the worst (brute force over C = 1..16, every channel and
+// lane group), which a ds_write_b32 absorbs (kPcmOut) and which costs kPcmIn's ds_read_b32 one extra LDS cycle against ~100x that in
+// memory time.
+//
+// Overs.  kPcmOut counts what the conversion could not represent: per lane one word, clamped (or, float16, turned +-inf from a finite
+// value) in its low half and NaN inputs in its high half -- a lane converts some 35 elements of a tile at the most --, summed over the
+// wavefront, and one atomicAdd per wavefront and non-zero counter into overs[2*s], overs[2*s + 1].
 #pragma once
 #include <cstdint>
+#include <stdexcept>
 
 namespace smst {
 
 typedef unsigned PcmWord4 __attribute__((vector_size(16), may_alias)); // one 16-byte access
+struct PcmS24 { unsigned char b[3]; };                                   // one packed sample, little-endian
+typedef _Float16 PcmF16;
+constexpr unsigned kPcmOverClamped = 1u, kPcmOverNan = 1u << 16;
 
+// Per format: a group of G elements is W 16-byte words; lead(address) = the elements in front of the first group boundary;
+// over(v) = what encode(v) adds to a lane's overs word.
 template <typename T> struct PcmFormat;
+template <typename T, int G> __device__ inline int pcmLeadAligned(uintptr_t address) { return (G - int((address/sizeof(T))%G))%G; }
 template <> struct PcmFormat<int16_t> {
-	static constexpr int V = 8; // elements per 16 bytes
+	static constexpr int G = 8, W = 1;
+	static __device__ inline int lead(uintptr_t a) { return pcmLeadAligned<int16_t, G>(a); }
 	static __device__ inline float decode(int16_t v) { return float(v)*(1.0f/32768.0f); }
 	static __device__ inline int16_t encode(float v) {
 		const float q = fminf(fmaxf(roundf(v*32768.0f), -32768.0f), 32767.0f);
 		return (v != v) ? int16_t(0) : int16_t(int(q));
 	}
-	static __device__ inline void unpack(const PcmWord4 w, float *x) {
+	static __device__ inline unsigned over(float v) {
+		const float r = roundf(v*32768.0f);
+		return (v != v) ? kPcmOverNan : (r > 32767.0f || r < -32768.0f) ? kPcmOverClamped : 0u;
+	}
+	static __device__ inline void unpack(const PcmWord4 *w, float *x) {
 		for (int k = 0; k < 4; ++k) {
-			x[2*k] = decode(int16_t(w[k] & 0xffffu));
-			x[2*k + 1] = decode(int16_t(w[k] >> 16));
+			x[2*k] = decode(int16_t(w[0][k] & 0xffffu));
+			x[2*k + 1] = decode(int16_t(w[0][k] >> 16));
 		}
 	}
-	static __device__ inline PcmWord4 pack(const float *x) {
-		PcmWord4 w;
-		for (int k = 0; k < 4; ++k) w[k] = unsigned(uint16_t(encode(x[2*k]))) | (unsigned(uint16_t(encode(x[2*k + 1]))) << 16);
-		return w;
+	static __device__ inline void pack(const float *x, PcmWord4 *w) {
+		for (int k = 0; k < 4; ++k) w[0][k] = unsigned(uint16_t(encode(x[2*k]))) | (unsigned(uint16_t(encode(x[2*k + 1]))) << 16);
 	}
 };
 template <> struct PcmFormat<float> {
-	static constexpr int V = 4;
+	static constexpr int G = 4, W = 1;
+	static __device__ inline int lead(uintptr_t a) { return pcmLeadAligned<float, G>(a); }
 	static __device__ inline float decode(float v) { return v; }
 	static __device__ inline float encode(float v) { return v; }
-	static __device__ inline void unpack(const PcmWord4 w, float *x) {
-		for (int k = 0; k < 4; ++k) x[k] = __int_as_float(int(w[k]));
+	static __device__ inline unsigned over(float v) { return (v != v) ? kPcmOverNan : 0u; }
+	static __device__ inline void unpack(const PcmWord4 *w, float *x) {
+		for (int k = 0; k < 4; ++k) x[k] = __int_as_float(int(w[0][k]));
 	}
-	static __device__ inline PcmWord4 pack(const float *x) {
-		PcmWord4 w;
-		for (int k = 0; k < 4; ++k) w[k] = unsigned(__float_as_int(x[k]));
-		return w;
+	static __device__ inline void pack(const float *x, PcmWord4 *w) {
+		for (int k = 0; k < 4; ++k) w[0][k] = unsigned(__float_as_int(x[k]));
+	}
+};
+template <> struct PcmFormat<int32_t> {
+	static constexpr int G = 4, W = 1;
+	static __device__ inline int lead(uintptr_t a) { return pcmLeadAligned<int32_t, G>(a); }
+	static __device__ inline float decode(int32_t v) { return float(v)*(1.0f/2147483648.0f); }
+	// the clamp acts on the float (2147483520 is the largest one below 2^31): no float outside int's range is ever converted
+	static __device__ inline int32_t encode(float v) {
+		const float r = roundf(v*2147483648.0f);
+		const int32_t q = int32_t(fminf(fmaxf(r, -2147483648.0f), 2147483520.0f));
+		return (v != v) ? 0 : (r >= 2147483648.0f ? 2147483647 : q);
+	}
+	static __device__ inline unsigned over(float v) {
+		const float r = roundf(v*2147483648.0f);
+		return (v != v) ? kPcmOverNan : (r >= 2147483648.0f || r < -2147483648.0f) ? kPcmOverClamped : 0u;
+	}
+	static __device__ inline void unpack(const PcmWord4 *w, float *x) {
+		for (int k = 0; k < 4; ++k) x[k] = decode(int32_t(w[0][k]));
+	}
+	static __device__ inline void pack(const float *x, PcmWord4 *w) {
+		for (int k = 0; k < 4; ++k) w[0][k] = unsigned(encode(x[k]));
+	}
+};
+template <> struct PcmFormat<PcmF16> {
+	static constexpr int G = 8, W = 1;
+	static __device__ inline int lead(uintptr_t a) { return pcmLeadAligned<PcmF16, G>(a); }
+	static __device__ inline float fromBits(unsigned bits) { const uint16_t b = uint16_t(bits); PcmF16 h; __builtin_memcpy(&h, &b, 2); return float(h); }
+	static __device__ inline unsigned toBits(float v) { const PcmF16 h = PcmF16(v); uint16_t b; __builtin_memcpy(&b, &h, 2); return b; }
+	static __device__ inline float decode(PcmF16 v) { return float(v); }
+	static __device__ inline PcmF16 encode(float v) { return PcmF16(v); }
+	// 65520 is the tie between 65504 and 2^16: to even, which is +-inf
+	static __device__ inline unsigned over(float v) {
+		const float a = fabsf(v);
+		return (v != v) ? kPcmOverNan : (a >= 65520.0f && a <= 3.402823466e38f) ? kPcmOverClamped : 0u;
+	}
+	static __device__ inline void unpack(const PcmWord4 *w, float *x) {
+		for (int k = 0; k < 4; ++k) {
+			x[2*k] = fromBits(w[0][k] & 0xffffu);
+			x[2*k + 1] = fromBits(w[0][k] >> 16);
+		}
+	}
+	static __device__ inline void pack(const float *x, PcmWord4 *w) {
+		for (int k = 0; k < 4; ++k) w[0][k] = toBits(x[2*k]) | (toBits(x[2*k + 1]) << 16);
+	}
+};
+template <> struct PcmFormat<PcmS24> {
+	static constexpr int G = 16, W = 3;
+	// the k < 16 with address + 3k = 0 mod 16: k = -address*11, as 3*11 = 1 mod 16
+	static __device__ inline int lead(uintptr_t a) { return int(((0 - a) & 15u)*11u & 15u); }
+	static __device__ inline float fromLow24(unsigned v) { return float(int(v << 8) >> 8)*(1.0f/8388608.0f); } // (bits 24..31 of v are ignored)
+	static __device__ inline unsigned code(float v) { // the 24 bits
+		const float q = fminf(fmaxf(roundf(v*8388608.0f), -8388608.0f), 8388607.0f);
+		return (v != v) ? 0u : (unsigned(int(q)) & 0xffffffu);
+	}
+	static __device__ inline float decode(PcmS24 v) { return fromLow24(unsigned(v.b[0]) | (unsigned(v.b[1]) << 8) | (unsigned(v.b[2]) << 16)); }
+	static __device__ inline PcmS24 encode(float v) {
+		const unsigned q = code(v);
+		PcmS24 r;
+		r.b[0] = (unsigned char)(q & 0xffu); r.b[1] = (unsigned char)((q >> 8) & 0xffu); r.b[2] = (unsigned char)(q >> 16);
+		return r;
+	}
+	static __device__ inline unsigned over(float v) {
+		const float r = roundf(v*8388608.0f);
+		return (v != v) ? kPcmOverNan : (r > 8388607.0f || r < -8388608.0f) ? kPcmOverClamped : 0u;
+	}
+	// four samples are three dwords: a = d0[0:23], b = d0[24:31] d1[0:15], c = d1[16:31] d2[0:7], d = d2[8:31]
+	static __device__ inline void unpack(const PcmWord4 *w, float *x) {
+		unsigned d[12];
+		for (int k = 0; k < 12; ++k) d[k] = w[k >> 2][k & 3];
+		for (int q = 0; q < 4; ++q) {
+			const unsigned d0 = d[3*q], d1 = d[3*q + 1], d2 = d[3*q + 2];
+			x[4*q] = fromLow24(d0);
+			x[4*q + 1] = fromLow24((d0 >> 24) | (d1 << 8));
+			x[4*q + 2] = fromLow24((d1 >> 16) | (d2 << 16));
+			x[4*q + 3] = fromLow24(d2 >> 8);
+		}
+	}
+	static __device__ inline void pack(const float *x, PcmWord4 *w) {
+		unsigned d[12];
+		for (int q = 0; q < 4; ++q) {
+			const unsigned a = code(x[4*q]), b = code(x[4*q + 1]), c = code(x[4*q + 2]), e = code(x[4*q + 3]);
+			d[3*q] = a | (b << 24);
+			d[3*q + 1] = (b >> 8) | (c << 16);
+			d[3*q + 2] = (c >> 16) | (e << 8);
+		}
+		for (int k = 0; k < 12; ++k) w[k >> 2][k & 3] = d[k];
 	}
 };
 
 __device__ inline int pcmSlot(int e) { return e + (e >> 5); }
-inline size_t pcmLdsBytes(int C) { const int most = kPcmTileFrames*C + 8; return size_t(most + most/32 + 1)*sizeof(float); } // (tile 0 is up to V - 1 elements longer)
+inline size_t pcmLdsBytes(int C) { const int most = kPcmTileFrames*C + 16; return size_t(most + most/32 + 1)*sizeof(float); } // (tile 0 is up to G - 1 = 15 elements longer)
 
 // The elements [e0, e0 + count) of a stream's run of `total` elements that tile `t` moves, and how many of them (tile 0 only) lie in
-// front of the first 16-byte boundary.  false: the tile lies behind the run.
+// front of the first group boundary.  false: the tile lies behind the run.
 template <typename T> __device__ inline bool pcmTileRun(const T *run, long long total, bool dense, int t, int C, long long &e0, int &count, int &head) {
-	constexpr int V = PcmFormat<T>::V;
-	const int tileElems = kPcmTileFrames*C; // a multiple of 16 bytes
-	const int misaligned = int((reinterpret_cast<uintptr_t>(run)/sizeof(T))%V);
-	const int lead = dense ? (V - misaligned)%V : 0;
+	const int tileElems = kPcmTileFrames*C; // whole groups: a multiple of 16 elements
+	const int lead = dense ? PcmFormat<T>::lead(reinterpret_cast<uintptr_t>(run)) : 0;
 	e0 = t ? (long long)t*tileElems + lead : 0;
 	if (e0 >= total) return false;
 	const long long e1 = (long long)(t + 1)*tileElems + lead;
@@ -82,7 +187,7 @@ template <typename T> __global__ __launch_bounds__(256) void kPcmIn(const T *__r
 		float *__restrict__ out, long long outStreamStride, long long outChannelStride, const int *__restrict__ counts, int C) {
 	extern __shared__ __attribute__((aligned(16))) unsigned char smemRaw[];
 	float *tile = reinterpret_cast<float *>(smemRaw);
-	constexpr int V = PcmFormat<T>::V;
+	constexpr int G = PcmFormat<T>::G, W = PcmFormat<T>::W;
 	const int s = blockIdx.y, tid = threadIdx.x;
 	const T *run = in + (size_t)s*inStreamStride;
 	const bool dense = inFrameStride == C;
@@ -92,14 +197,17 @@ template <typename T> __global__ __launch_bounds__(256) void kPcmIn(const T *__r
 	if (dense) {
 		const T *p = run + e0;
 		if (tid < head) tile[pcmSlot(tid)] = PcmFormat<T>::decode(p[tid]);
-		const int nVec = (count - head)/V;
-		for (int v = tid; v < nVec; v += 256) {
-			const int e = head + v*V;
-			float x[V];
-			PcmFormat<T>::unpack(*reinterpret_cast<const PcmWord4 *>(p + e), x);
-			for (int k = 0; k < V; ++k) tile[pcmSlot(e + k)] = x[k];
+		const int nGroups = (count - head)/G;
+		for (int g = tid; g < nGroups; g += 256) {
+			const int e = head + g*G;
+			const PcmWord4 *src = reinterpret_cast<const PcmWord4 *>(p + e);
+			PcmWord4 w[W];
+			for (int k = 0; k < W; ++k) w[k] = src[k];
+			float x[G];
+			PcmFormat<T>::unpack(w, x);
+			for (int k = 0; k < G; ++k) tile[pcmSlot(e + k)] = x[k];
 		}
-		const int done = head + nVec*V;
+		const int done = head + nGroups*G;
 		if (tid < count - done) tile[pcmSlot(done + tid)] = PcmFormat<T>::decode(p[done + tid]);
 	} else {
 		for (int i = tid; i < count; i += 256) {
@@ -120,12 +228,12 @@ template <typename T> __global__ __launch_bounds__(256) void kPcmIn(const T *__r
 	}
 }
 
-// planar fp32 -> interleaved frames: the reverse
+// planar fp32 -> interleaved frames: the reverse.  overs (may be null): [S][2] counters, see "Overs" above
 template <typename T> __global__ __launch_bounds__(256) void kPcmOut(const float *__restrict__ in, long long inStreamStride, long long inChannelStride,
-		T *__restrict__ out, long long outStreamStride, long long outFrameStride, const int *__restrict__ counts, int C) {
+		T *__restrict__ out, long long outStreamStride, long long outFrameStride, const int *__restrict__ counts, int C, unsigned *__restrict__ overs) {
 	extern __shared__ __attribute__((aligned(16))) unsigned char smemRaw[];
 	float *tile = reinterpret_cast<float *>(smemRaw);
-	constexpr int V = PcmFormat<T>::V;
+	constexpr int G = PcmFormat<T>::G, W = PcmFormat<T>::W;
 	const int s = blockIdx.y, tid = threadIdx.x;
 	T *run = out + (size_t)s*outStreamStride;
 	const bool dense = outFrameStride == C;
@@ -143,41 +251,77 @@ template <typename T> __global__ __launch_bounds__(256) void kPcmOut(const float
 		}
 	}
 	__syncthreads();
+	unsigned over = 0;
 	if (dense) {
 		T *p = run + e0;
-		if (tid < head) p[tid] = PcmFormat<T>::encode(tile[pcmSlot(tid)]);
-		const int nVec = (count - head)/V;
-		for (int v = tid; v < nVec; v += 256) {
-			const int e = head + v*V;
-			float x[V];
-			for (int k = 0; k < V; ++k) x[k] = tile[pcmSlot(e + k)];
-			*reinterpret_cast<PcmWord4 *>(p + e) = PcmFormat<T>::pack(x);
+		if (tid < head) { const float v = tile[pcmSlot(tid)]; p[tid] = PcmFormat<T>::encode(v); over += PcmFormat<T>::over(v); }
+		const int nGroups = (count - head)/G;
+		for (int g = tid; g < nGroups; g += 256) {
+			const int e = head + g*G;
+			float x[G];
+			for (int k = 0; k < G; ++k) { x[k] = tile[pcmSlot(e + k)]; over += PcmFormat<T>::over(x[k]); }
+			PcmWord4 w[W];
+			PcmFormat<T>::pack(x, w);
+			PcmWord4 *dst = reinterpret_cast<PcmWord4 *>(p + e);
+			for (int k = 0; k < W; ++k) dst[k] = w[k];
 		}
-		const int done = head + nVec*V;
-		if (tid < count - done) p[done + tid] = PcmFormat<T>::encode(tile[pcmSlot(done + tid)]);
+		const int done = head + nGroups*G;
+		if (tid < count - done) { const float v = tile[pcmSlot(done + tid)]; p[done + tid] = PcmFormat<T>::encode(v); over += PcmFormat<T>::over(v); }
 	} else {
 		for (int i = tid; i < count; i += 256) {
 			const long long e = e0 + i, f = e/C;
-			run[f*outFrameStride + (e - f*C)] = PcmFormat<T>::encode(tile[pcmSlot(i)]);
+			const float v = tile[pcmSlot(i)];
+			run[f*outFrameStride + (e - f*C)] = PcmFormat<T>::encode(v);
+			over += PcmFormat<T>::over(v);
+		}
+	}
+	// (every lane of the workgroup arrives here; the vote keeps the clean wavefront, which is nearly every one, to one instruction)
+	if (overs && __any(over != 0)) {
+		int sum = int(over);
+		for (int m = 32; m; m >>= 1) sum += __shfl(sum, (tid & 63) ^ m);
+		if ((tid & 63) == 0) {
+			int *words = reinterpret_cast<int *>(overs) + 2*s; // (the words wrap as unsigned ones do)
+			if (sum & 0xffff) atomicAdd(words, sum & 0xffff);
+			if (sum >> 16) atomicAdd(words + 1, sum >> 16);
 		}
 	}
 }
 
-// format: 1 = int16, 2 = float32 (SMST_PCM_S16 / SMST_PCM_F32; the C ABI has checked it).  maxFrames: the largest of the streams' counts.
+// format: SMST_PCM_* of include/smst.h (the C ABI has checked it).  maxFrames: the largest of the streams' counts.
+template <typename T> static void launchPcmInAs(dim3 grid, int C, hipStream_t st, const void *in, long long inStreamStride, long long inFrameStride, float *out, long long outStreamStride,
+		long long outChannelStride, const int *counts) {
+	hipLaunchKernelGGL(kPcmIn<T>, grid, dim3(256), pcmLdsBytes(C), st, static_cast<const T *>(in), inStreamStride, inFrameStride, out, outStreamStride, outChannelStride, counts, C);
+}
+template <typename T> static void launchPcmOutAs(dim3 grid, int C, hipStream_t st, const float *in, long long inStreamStride, long long inChannelStride, void *out, long long outStreamStride,
+		long long outFrameStride, const int *counts, unsigned *overs) {
+	hipLaunchKernelGGL(kPcmOut<T>, grid, dim3(256), pcmLdsBytes(C), st, in, inStreamStride, inChannelStride, static_cast<T *>(out), outStreamStride, outFrameStride, counts, C, overs);
+}
 void launchPcmIn(int format, const void *in, long long inStreamStride, long long inFrameStride, float *out, long long outStreamStride, long long outChannelStride,
                  const int *counts, int S, int C, int maxFrames, hipStream_t st) {
 	if (maxFrames < 1) return;
 	const dim3 grid(divUp(maxFrames, kPcmTileFrames), S);
-	if (format == 1) hipLaunchKernelGGL(kPcmIn<int16_t>, grid, dim3(256), pcmLdsBytes(C), st, static_cast<const int16_t *>(in), inStreamStride, inFrameStride, out, outStreamStride, outChannelStride, counts, C);
-	else hipLaunchKernelGGL(kPcmIn<float>, grid, dim3(256), pcmLdsBytes(C), st, static_cast<const float *>(in), inStreamStride, inFrameStride, out, outStreamStride, outChannelStride, counts, C);
+	switch (format) {
+	case kPcmS16: launchPcmInAs<int16_t>(grid, C, st, in, inStreamStride, inFrameStride, out, outStreamStride, outChannelStride, counts); break;
+	case kPcmF32: launchPcmInAs<float>(grid, C, st, in, inStreamStride, inFrameStride, out, outStreamStride, outChannelStride, counts); break;
+	case kPcmS24: launchPcmInAs<PcmS24>(grid, C, st, in, inStreamStride, inFrameStride, out, outStreamStride, outChannelStride, counts); break;
+	case kPcmS32: launchPcmInAs<int32_t>(grid, C, st, in, inStreamStride, inFrameStride, out, outStreamStride, outChannelStride, counts); break;
+	case kPcmF16: launchPcmInAs<PcmF16>(grid, C, st, in, inStreamStride, inFrameStride, out, outStreamStride, outChannelStride, counts); break;
+	default: throw std::invalid_argument("unknown PCM format");
+	}
 	countLaunch(LK_PCM_IN);
 }
 void launchPcmOut(int format, const float *in, long long inStreamStride, long long inChannelStride, void *out, long long outStreamStride, long long outFrameStride,
-                  const int *counts, int S, int C, int maxFrames, hipStream_t st) {
+                  const int *counts, int S, int C, int maxFrames, unsigned *overs, hipStream_t st) {
 	if (maxFrames < 1) return;
 	const dim3 grid(divUp(maxFrames, kPcmTileFrames), S);
-	if (format == 1) hipLaunchKernelGGL(kPcmOut<int16_t>, grid, dim3(256), pcmLdsBytes(C), st, in, inStreamStride, inChannelStride, static_cast<int16_t *>(out), outStreamStride, outFrameStride, counts, C);
-	else hipLaunchKernelGGL(kPcmOut<float>, grid, dim3(256), pcmLdsBytes(C), st, in, inStreamStride, inChannelStride, static_cast<float *>(out), outStreamStride, outFrameStride, counts, C);
+	switch (format) {
+	case kPcmS16: launchPcmOutAs<int16_t>(grid, C, st, in, inStreamStride, inChannelStride, out, outStreamStride, outFrameStride, counts, overs); break;
+	case kPcmF32: launchPcmOutAs<float>(grid, C, st, in, inStreamStride, inChannelStride, out, outStreamStride, outFrameStride, counts, overs); break;
+	case kPcmS24: launchPcmOutAs<PcmS24>(grid, C, st, in, inStreamStride, inChannelStride, out, outStreamStride, outFrameStride, counts, overs); break;
+	case kPcmS32: launchPcmOutAs<int32_t>(grid, C, st, in, inStreamStride, inChannelStride, out, outStreamStride, outFrameStride, counts, overs); break;
+	case kPcmF16: launchPcmOutAs<PcmF16>(grid, C, st, in, inStreamStride, inChannelStride, out, outStreamStride, outFrameStride, counts, overs); break;
+	default: throw std::invalid_argument("unknown PCM format");
+	}
 	countLaunch(LK_PCM_OUT);
 }
 

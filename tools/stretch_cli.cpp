@@ -4,8 +4,10 @@
 // implementation).
 //
 //   stretch_cli [--semitones=S] [--formant=S] [--formant-comp] [--formant-base=Hz] [--tonality=Hz] [--time=F]
-//               [--split-computation] [--device=N] in.wav out.wav [in2.wav out2.wav ...]
+//               [--split-computation] [--device=N] [--out-format=s16|s24|f32] in.wav out.wav [in2.wav out2.wav ...]
 //
+// --out-format (also "--out-format s24"): the samples of the files written -- 16-bit (the default, as the reference's CLI writes), 24-bit by the
+// library's rounding rule for SMST_PCM_S24, or float32.
 // Files given together must share sample rate and channel count (they form one batch); lengths may differ.
 #include <algorithm>
 #include <cmath>
@@ -28,6 +30,16 @@ static bool hasFlag(int argc, char **argv, const char *name) {
 	for (int i = 1; i < argc; ++i) if (flag == argv[i]) return true;
 	return false;
 }
+// --name=value or --name value; consumed[i] marks the arguments that are no file names
+static std::string flagText(int argc, char **argv, const char *name, const char *fallback, std::vector<bool> &consumed) {
+	const std::string flag = std::string("--") + name, prefix = flag + "=";
+	std::string value = fallback;
+	for (int i = 1; i < argc; ++i) {
+		if (!std::strncmp(argv[i], prefix.c_str(), prefix.size())) value = argv[i] + prefix.size();
+		else if (flag == argv[i] && i + 1 < argc) { value = argv[i + 1]; consumed[i + 1] = true; }
+	}
+	return value;
+}
 #define CHECK(call) do { if ((call) != SMST_OK) { std::fprintf(stderr, "%s: %s\n", #call, smst_last_error()); return 1; } } while (0)
 
 int main(int argc, char **argv) {
@@ -37,8 +49,14 @@ int main(int argc, char **argv) {
 	const double time = flagValue(argc, argv, "time", 1);
 	const bool formantComp = hasFlag(argc, argv, "formant-comp"), split = hasFlag(argc, argv, "split-computation");
 	const int device = int(flagValue(argc, argv, "device", 0));
+	std::vector<bool> consumed(argc, false);
+	const std::string outFormat = flagText(argc, argv, "out-format", "s16", consumed);
+	if (outFormat != "s16" && outFormat != "s24" && outFormat != "f32") {
+		std::fprintf(stderr, "--out-format is s16, s24 or f32\n");
+		return 2;
+	}
 	std::vector<std::string> files;
-	for (int i = 1; i < argc; ++i) if (std::strncmp(argv[i], "--", 2)) files.push_back(argv[i]);
+	for (int i = 1; i < argc; ++i) if (std::strncmp(argv[i], "--", 2) && !consumed[i]) files.push_back(argv[i]);
 	if (files.size() < 2 || files.size()%2) {
 		std::fprintf(stderr, "usage: %s [flags] in.wav out.wav [in2.wav out2.wav ...]\n", argv[0]);
 		return 2;
@@ -101,7 +119,8 @@ int main(int argc, char **argv) {
 		result.channels = inputs[s].channels;
 		result.samples.assign(C, std::vector<float>(outLen[s]));
 		for (int c = 0; c < C; ++c) std::copy(out.begin() + ((size_t)s*C + c)*maxOut, out.begin() + ((size_t)s*C + c)*maxOut + outLen[s], result.samples[c].begin());
-		if (!writeWav16(files[2*s + 1], result, error)) { std::fprintf(stderr, "%s\n", error.c_str()); return 1; }
+		const bool written = outFormat == "s24" ? writeWav24(files[2*s + 1], result, error) : outFormat == "f32" ? writeWavFloat32(files[2*s + 1], result, error) : writeWav16(files[2*s + 1], result, error);
+		if (!written) { std::fprintf(stderr, "%s\n", error.c_str()); return 1; }
 	}
 	smst_batch_destroy(batch);
 	return 0;

@@ -1,4 +1,4 @@
-// Minimal 16-bit PCM / 32-bit float WAV reader and writer for the command-line tool (the format either side of the
+// Minimal 16-bit / 24-bit PCM and 32-bit float WAV reader and writer for the command-line tool (the format either side of the
 // hot path: the reference CLI reads and writes 16-bit WAV, cmd/main.cpp:20-21,33-42,85).
 #pragma once
 #include <cmath>
@@ -75,6 +75,52 @@ inline bool writeWav16(const std::string &path, const WavData &wav, std::string 
 			float v = wav.samples[c][i]*32768.0f;
 			v = std::fmin(32767.0f, std::fmax(-32768.0f, std::round(v)));
 			put16(uint16_t(int16_t(v)));
+		}
+	}
+	std::fclose(f);
+	return true;
+}
+
+// The same file with 24-bit samples, by the library's rule for SMST_PCM_S24 (include/smst.h): roundf(v*8388608) -- ties away from zero --,
+// clamped to [-8388608, 8388607]; NaN gives 0.
+inline bool writeWav24(const std::string &path, const WavData &wav, std::string &error) {
+	FILE *f = std::fopen(path.c_str(), "wb");
+	if (!f) { error = "cannot create " + path; return false; }
+	const uint32_t frames = uint32_t(wav.length()), dataBytes = frames*wav.channels*3;
+	auto put32 = [&](uint32_t v) { unsigned char b[4] = {(unsigned char)v, (unsigned char)(v >> 8), (unsigned char)(v >> 16), (unsigned char)(v >> 24)}; std::fwrite(b, 1, 4, f); };
+	auto put16 = [&](uint16_t v) { unsigned char b[2] = {(unsigned char)v, (unsigned char)(v >> 8)}; std::fwrite(b, 1, 2, f); };
+	std::fwrite("RIFF", 1, 4, f); put32(36 + dataBytes + (dataBytes & 1)); std::fwrite("WAVEfmt ", 1, 8, f);
+	put32(16); put16(1); put16(uint16_t(wav.channels)); put32(wav.sampleRate); put32(wav.sampleRate*wav.channels*3); put16(uint16_t(wav.channels*3)); put16(24);
+	std::fwrite("data", 1, 4, f); put32(dataBytes);
+	for (uint32_t i = 0; i < frames; ++i) {
+		for (unsigned c = 0; c < wav.channels; ++c) {
+			const float x = wav.samples[c][i];
+			const float v = std::fmin(8388607.0f, std::fmax(-8388608.0f, std::round(x*8388608.0f)));
+			const uint32_t q = (x != x) ? 0u : uint32_t(int32_t(v));
+			unsigned char b[3] = {(unsigned char)q, (unsigned char)(q >> 8), (unsigned char)(q >> 16)};
+			std::fwrite(b, 1, 3, f);
+		}
+	}
+	if (dataBytes & 1) std::fputc(0, f); // (RIFF chunks are padded to an even length)
+	std::fclose(f);
+	return true;
+}
+
+// ... and with IEEE float32 samples (format tag 3), bit for bit
+inline bool writeWavFloat32(const std::string &path, const WavData &wav, std::string &error) {
+	FILE *f = std::fopen(path.c_str(), "wb");
+	if (!f) { error = "cannot create " + path; return false; }
+	const uint32_t frames = uint32_t(wav.length()), dataBytes = frames*wav.channels*4;
+	auto put32 = [&](uint32_t v) { unsigned char b[4] = {(unsigned char)v, (unsigned char)(v >> 8), (unsigned char)(v >> 16), (unsigned char)(v >> 24)}; std::fwrite(b, 1, 4, f); };
+	auto put16 = [&](uint16_t v) { unsigned char b[2] = {(unsigned char)v, (unsigned char)(v >> 8)}; std::fwrite(b, 1, 2, f); };
+	std::fwrite("RIFF", 1, 4, f); put32(36 + dataBytes); std::fwrite("WAVEfmt ", 1, 8, f);
+	put32(16); put16(3); put16(uint16_t(wav.channels)); put32(wav.sampleRate); put32(wav.sampleRate*wav.channels*4); put16(uint16_t(wav.channels*4)); put16(32);
+	std::fwrite("data", 1, 4, f); put32(dataBytes);
+	for (uint32_t i = 0; i < frames; ++i) {
+		for (unsigned c = 0; c < wav.channels; ++c) {
+			uint32_t w;
+			std::memcpy(&w, &wav.samples[c][i], 4);
+			put32(w);
 		}
 	}
 	std::fclose(f);
