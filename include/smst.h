@@ -241,6 +241,35 @@ int smst_batch_flush(smst_batch *b, float *out, long long outStreamStride, long 
                      const int *outSamples, const float *playbackRates, int memory);
 int smst_batch_output_seek(smst_batch *b, const float *in, long long inStreamStride, long long inChannelStride,
                            const int *inputLengths, int memory);
+/* ---- whole clips (EXTENSION: the reference has exact() per instance, signalsmith-stretch.h:468-491; here S clips of S lengths and S rates are ONE call) ----
+ * exact() of every stream: stream s is a fresh run of instance seed+s over its whole clip -- inSamples[s] input samples become exactly
+ * outSamples[s] output samples, rate_s = inSamples[s]/float(outSamples[s]) -- and, as exact() of an instance, starts from reset(): the
+ * stream's parameters and its random engine stay as earlier calls left them.  Per stream, in the reference's arithmetic (the one smst_exact uses):
+ *   seekLength = outputSeekLength(rate_s); inSamples[s] < seekLength: the stream is TOO SHORT -- its outSamples[s] output samples are written
+ *   as zeros (the PCM code of 0.0), status[s] = SMST_ERR_SHORT, and its state is untouched (the reference returns before outputSeek, :471-480);
+ *   else outputSeek(in[0, seekLength)), outputIndex = int(outSamples[s] - seekLength/rate_s), process(in[seekLength, inSamples[s]) -> out[0, outputIndex)),
+ *   flush(out[outputIndex, outSamples[s]), rate_s), and status[s] = SMST_OK.
+ * A NEGATIVE outSamples[s] leaves stream s out of the call altogether, as the flush rule does: state, output and status[s] untouched.
+ * SMST_ERR_INVALID with a message, before anything runs: outSamples[s] == 0 (the reference divides by it), a negative inSamples[s] on a
+ * participating stream, a null buffer with a non-zero count, an unknown memory kind.  The call returns SMST_OK when it ran: short streams are
+ * reported through `status` only.  status (may be null): [streams] host ints.  Everything written lies inside [0, outSamples[s]) of a
+ * participating stream.
+ * The engine runs ONE outputSeek, ONE main process and ONE flush whatever the spread of rates: two copy kernels (csrc/smst_clip.h) move each
+ * stream's segments between the caller's buffers and planar images of the library's own in which every stream's stage begins at one column
+ * (allocated by the first call, part of smst_batch_workspace_bytes; a second call of the same shapes allocates nothing).
+ * SMST_MEM_HOST: returns with the output in place.  SMST_MEM_DEVICE: the contract of the other device-memory calls -- smst_batch_wait_for_stream
+ * before, buffers alive and untouched until smst_batch_synchronize or a signalled stream has caught up; the copy kernels are ordered as the
+ * conversions of the _pcm calls are ("Ordering contract" below), and no host synchronisation is added to those outputSeek, seek and flush have.
+ * (They come earlier than in smst_batch_output_seek: resetting only the streams that take part uploads a mask, which waits for the batch's stream --
+ * and with it for the producer handed to smst_batch_wait_for_stream -- before the first stage is enqueued.)
+ * The _pcm form takes frames (formats, strides, alignment and overs as in the _pcm calls below; also SMST_ERR_INVALID: an unknown format,
+ * frameStride < channels); the zeros of a short stream count as no overs. */
+int smst_batch_exact(smst_batch *b, const float *in, long long inStreamStride, long long inChannelStride, const int *inSamples,
+                     float *out, long long outStreamStride, long long outChannelStride, const int *outSamples,
+                     int *status, int memory);
+int smst_batch_exact_pcm(smst_batch *b, const void *in, long long inStreamStride, long long inFrameStride, const int *inSamples,
+                         void *out, long long outStreamStride, long long outFrameStride, const int *outSamples,
+                         int *status, int format, int memory);
 /* ---- interleaved PCM (EXTENSION: the reference's process() is templated on its buffers, so a caller there can hand it an adaptor over an
  * interleaved frame buffer; here the conversion is part of the call and runs on the GPU) ----
  * The four calls above with FRAME buffers: sample (s, i, c) at base[s*streamStride + i*frameStride + c], strides in ELEMENTS of the
@@ -300,6 +329,17 @@ int smst_debug_pcm_convert_counted(int device, int format, int streams, int chan
                                    const void *src, long long srcStreamStride, long long srcInnerStride,
                                    void *dst, long long dstStreamStride, long long dstInnerStride,
                                    long long *clamped, long long *nans);
+/* test hook: the two copy kernels of the exact calls alone (csrc/smst_clip.h).  dir 0 = caller's buffer -> planar image, 1 = planar image ->
+ * caller's buffer; format: an SMST_PCM_* code (the caller's side is frames: stream stride, frame stride) or 0 (it is planar fp32 itself: stream
+ * stride, channel stride); the image side is always (stream stride, channel stride); strides in elements.  segments: [streams][2][4] host ints
+ * (source frame, destination frame, count, zeros): `count` frames from frame `source` of the stream's row(s) in src to frame `destination` in
+ * dst; zeros != 0 (dir 1): no source, the destination gets 0.0.  Host pointers; both buffers are staged whole -- as far as the segments reach --
+ * (what the kernel leaves alone in `dst` comes back as it was) into device buffers offset from a 16-byte boundary as the caller's pointers are.
+ * clamped / nans (either may be null): [streams], the overs the kernel counted (dir 1 into a frame format).  Synchronises before it returns. */
+int smst_debug_clip_copy(int device, int dir, int format, int streams, int channels, const int *segments,
+                         const void *src, long long srcStreamStride, long long srcInnerStride,
+                         void *dst, long long dstStreamStride, long long dstInnerStride,
+                         long long *clamped, long long *nans);
 int smst_batch_synchronize(smst_batch *b);
 /* raw hipStream_t the batch enqueues on (so callers can order their own device work against it) */
 void *smst_batch_hip_stream(smst_batch *b);
@@ -353,7 +393,7 @@ int smst_debug_complex_selftest(int device, const float *in, float *out, int n);
 /* launches, since the library was loaded, of one kernel variant: "vocoder_aligned", "vocoder_staged", "vocoder_gather",
  * "vocoder_n", "vocoder_one", "vocoder_across", "vocoder_continuous", "chain_unfused", "analyse_teams", "analyse_fast", "analyse_generic",
  * "synth_teams", "synth_fast", "synth_generic", "synth_emit", "emit_carried", "feed_one_pass", "pcm_in", "pcm_out" (the conversion kernels of the _pcm calls, whatever
- * the format) (-1: unknown name).  The "this form is bit-identical to that form" tests
+ * the format), "clip_in", "clip_out" (the copy kernels of the exact calls, planar or any format) (-1: unknown name).  The "this form is bit-identical to that form" tests
  * assert through it that both forms really ran. */
 long long smst_debug_launch_count(const char *name);
 

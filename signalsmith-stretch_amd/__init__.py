@@ -109,6 +109,9 @@ _SIGNATURES = {
     "smst_batch_process": (C.c_int, [C.c_void_p, C.c_void_p, _ll, _ll, _ip, C.c_void_p, _ll, _ll, _ip, C.c_int]),
     "smst_batch_flush": (C.c_int, [C.c_void_p, C.c_void_p, _ll, _ll, _ip, _fp, C.c_int]),
     "smst_batch_output_seek": (C.c_int, [C.c_void_p, C.c_void_p, _ll, _ll, _ip, C.c_int]),
+    "smst_batch_exact": (C.c_int, [C.c_void_p, C.c_void_p, _ll, _ll, _ip, C.c_void_p, _ll, _ll, _ip, _ip, C.c_int]),
+    "smst_batch_exact_pcm": (C.c_int, [C.c_void_p, C.c_void_p, _ll, _ll, _ip, C.c_void_p, _ll, _ll, _ip, _ip, C.c_int, C.c_int]),
+    "smst_debug_clip_copy": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _ip, C.c_void_p, _ll, _ll, C.c_void_p, _ll, _ll, C.POINTER(_ll), C.POINTER(_ll)]),
     "smst_batch_process_pcm": (C.c_int, [C.c_void_p, C.c_void_p, _ll, _ll, _ip, C.c_void_p, _ll, _ll, _ip, C.c_int, C.c_int]),
     "smst_batch_seek_pcm": (C.c_int, [C.c_void_p, C.c_void_p, _ll, _ll, _ip, _dp, C.c_int, C.c_int]),
     "smst_batch_flush_pcm": (C.c_int, [C.c_void_p, C.c_void_p, _ll, _ll, _ip, _fp, C.c_int, C.c_int]),
@@ -516,6 +519,61 @@ class StretchBatch:
         if mem == MEM_DEVICE:
             self._order_after_torch(x)
         _check(self.lib, self.lib.smst_batch_output_seek_pcm(self.h, ptr, ss, fs, pin, fmt, mem))
+
+    # --- whole clips (smst_batch_exact / smst_batch_exact_pcm): S clips of S lengths and S rates in one call
+    def _exact(self, frames, x, out_samples, in_samples, out, ordered):
+        S, Cn = self.streams, self.channels
+        if frames:
+            ptr, ss, inner, n, fmt, mem, keep = self._describe_frames(x, "input")
+        else:
+            ptr, ss, inner, n, mem, keep = self._describe(x, "input")
+            fmt = None
+        nin, pin = _int_array(n if in_samples is None else in_samples, S)
+        nout, pout = _int_array(out_samples, S)
+        max_out = max(int(nout.max()), 1)
+        if out is None:
+            if frames:
+                out = self._new_frames(max_out, fmt, x if mem == MEM_DEVICE else None)
+            elif mem == MEM_DEVICE:
+                import torch
+                out = torch.zeros((S, Cn, max_out), dtype=torch.float32, device=x.device)
+            else:
+                out = np.zeros((S, Cn, max_out), np.float32)
+        if frames:
+            optr, oss, oinner, on, ofmt, omem, okeep = self._describe_frames(out, "output")
+        else:
+            optr, oss, oinner, on, omem, okeep = self._describe(out, "output")
+            ofmt = None
+        if omem != mem or ofmt != fmt:
+            raise StretchError("input and output must have the same format and live in the same memory space")
+        if omem == MEM_HOST and okeep is not out:
+            raise StretchError("output: need an array the library can write in place")
+        if on < max_out or int(nin[nout >= 0].max(initial=0)) > n:
+            raise StretchError("buffer shorter than the requested sample count")
+        status = np.full(S, 1, np.int32)                        # (a stream that is left out keeps the 1)
+        if mem == MEM_DEVICE and ordered:
+            self._order_after_torch(x, out)
+        if frames:
+            rc = self.lib.smst_batch_exact_pcm(self.h, ptr, ss, inner, pin, optr, oss, oinner, pout, status.ctypes.data_as(_ip), fmt, mem)
+        else:
+            rc = self.lib.smst_batch_exact(self.h, ptr, ss, inner, pin, optr, oss, oinner, pout, status.ctypes.data_as(_ip), mem)
+        _check(self.lib, rc)
+        if mem == MEM_DEVICE and ordered:
+            import torch
+            _check(self.lib, self.lib.smst_batch_signal_stream(self.h, C.c_void_p(torch.cuda.current_stream(out.device).cuda_stream)))
+        return out, status == 0
+
+    def exact(self, x, out_samples, in_samples=None, out=None, ordered=True):
+        """exact() of every stream (signalsmith-stretch.h:468-491): stream s, a fresh run of instance seed+s, turns its whole clip
+        x[s, :, :in_samples[s]] into exactly out_samples[s] samples -- lengths and rates are each stream's own, one call for all.
+        -> (out [S, C, max(out_samples)], ok bool [S]); ok[s] is False for a stream whose clip is shorter than outputSeekLength(rate_s)
+        (its output is zeros, its state untouched) and for one left out of the call by a NEGATIVE out_samples[s] (nothing of it is
+        touched).  numpy arrays are host memory, torch GPU tensors device memory; ``ordered`` as in process()."""
+        return self._exact(False, x, out_samples, in_samples, out, ordered)
+
+    def exactFrames(self, x, out_samples, in_samples=None, out=None, ordered=True):
+        """exact() on interleaved frames ([S, n, C] of a frame dtype, or uint8 [S, n, C, 3]: processFrames has the rules) -> (out, ok)"""
+        return self._exact(True, x, out_samples, in_samples, out, ordered)
 
     def takePcmOvers(self):
         """-> (clamped, nans), int64 [S]: per stream, the output elements of processFrames / flushFrames since the last take whose code

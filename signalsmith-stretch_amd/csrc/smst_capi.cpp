@@ -405,6 +405,41 @@ static void endPcmCall(smst_batch *b, smst_batch::PcmCounts &c) {
 // a stream's row in the library's own raw buffers: its frames densely, rows a multiple of 16 bytes apart for every element size
 static long long pcmRowElems(int maxFrames, int C) { return ((long long)maxFrames*C + 15)/16*16; }
 
+// Host frames -> the library's raw device buffer b->dPcmIn (rows of pcmRowElems(most, C) elements, frames dense), one copy across PCIe on the engine's stream
+static void pcmRawIn(smst_batch *b, const void *in, long long ss, long long fs, const int *n, int most, int format) {
+	Batch &e = *b->engine;
+	const int S = e.streams(), C = e.channels();
+	const size_t esz = pcmElemBytes(format);
+	const long long row = pcmRowElems(most, C);
+	const size_t bytes = (size_t)S*row*esz;
+	ensurePcmBytes(b->hPcmIn, b->hPcmInCap, bytes, true, e.device(), b->stagingAllocs);
+	ensurePcmBytes(b->dPcmIn, b->dPcmInCap, bytes, false, e.device(), b->stagingAllocs);
+	for (int s = 0; s < S; ++s) {
+		if (n[s] <= 0) continue;
+		const unsigned char *src = static_cast<const unsigned char *>(in) + (size_t)s*ss*esz;
+		unsigned char *dst = b->hPcmIn + (size_t)s*row*esz;
+		if (fs == C) std::memcpy(dst, src, (size_t)n[s]*C*esz);
+		else for (int i = 0; i < n[s]; ++i) std::memcpy(dst + (size_t)i*C*esz, src + (size_t)i*fs*esz, (size_t)C*esz);
+	}
+	if (hipMemcpyAsync(b->dPcmIn, b->hPcmIn, bytes, hipMemcpyHostToDevice, e.stream()) != hipSuccess) throw smst::Error("hipMemcpyAsync (H2D) failed", true);
+}
+// ... and b->dPcmOut back into the caller's host frames: one copy, a synchronisation, one memcpy per stream (frame by frame where frameStride > C)
+static void pcmRawOut(smst_batch *b, void *out, long long ss, long long fs, const int *n, int most, int format) {
+	Batch &e = *b->engine;
+	const int S = e.streams(), C = e.channels();
+	const size_t esz = pcmElemBytes(format);
+	const long long row = pcmRowElems(most, C);
+	if (hipMemcpyAsync(b->hPcmOut, b->dPcmOut, (size_t)S*row*esz, hipMemcpyDeviceToHost, e.stream()) != hipSuccess) throw smst::Error("hipMemcpyAsync (D2H) failed", true);
+	if (hipStreamSynchronize(e.stream()) != hipSuccess) throw smst::Error("hipStreamSynchronize failed", true);
+	for (int s = 0; s < S; ++s) {
+		if (n[s] <= 0) continue;
+		const unsigned char *src = b->hPcmOut + (size_t)s*row*esz;
+		unsigned char *dst = static_cast<unsigned char *>(out) + (size_t)s*ss*esz;
+		if (fs == C) std::memcpy(dst, src, (size_t)n[s]*C*esz);
+		else for (int i = 0; i < n[s]; ++i) std::memcpy(dst + (size_t)i*fs*esz, src + (size_t)i*C*esz, (size_t)C*esz);
+	}
+}
+
 // Raw frames -> the planar image b->dIn [S][C][maxLen] (returns maxLen), on the engine's stream and in front of every reader of the call's input
 static int pcmStageIn(smst_batch *b, smst_batch::PcmCounts &c, const void *in, long long ss, long long fs, const int *n, int format, int memory) {
 	Batch &e = *b->engine;
@@ -418,20 +453,8 @@ static int pcmStageIn(smst_batch *b, smst_batch::PcmCounts &c, const void *in, l
 	const void *raw = in;
 	long long rawSS = ss, rawFS = fs;
 	if (memory == SMST_MEM_HOST && most > 0) {
-		const size_t esz = pcmElemBytes(format);
-		const long long row = pcmRowElems(most, C);
-		const size_t bytes = (size_t)S*row*esz;
-		ensurePcmBytes(b->hPcmIn, b->hPcmInCap, bytes, true, e.device(), b->stagingAllocs);
-		ensurePcmBytes(b->dPcmIn, b->dPcmInCap, bytes, false, e.device(), b->stagingAllocs);
-		for (int s = 0; s < S; ++s) {
-			if (n[s] <= 0) continue;
-			const unsigned char *src = static_cast<const unsigned char *>(in) + (size_t)s*ss*esz;
-			unsigned char *dst = b->hPcmIn + (size_t)s*row*esz;
-			if (fs == C) std::memcpy(dst, src, (size_t)n[s]*C*esz);
-			else for (int i = 0; i < n[s]; ++i) std::memcpy(dst + (size_t)i*C*esz, src + (size_t)i*fs*esz, (size_t)C*esz);
-		}
-		if (hipMemcpyAsync(b->dPcmIn, b->hPcmIn, bytes, hipMemcpyHostToDevice, e.stream()) != hipSuccess) throw smst::Error("hipMemcpyAsync (H2D) failed", true);
-		raw = b->dPcmIn; rawSS = row; rawFS = C;
+		pcmRawIn(b, in, ss, fs, n, most, format);
+		raw = b->dPcmIn; rawSS = pcmRowElems(most, C); rawFS = C;
 	}
 	smst::launchPcmIn(format, raw, rawSS, rawFS, b->dIn, (long long)C*maxLen, maxLen, c.dev, S, C, most, e.stream());
 	// the engine reads its input on more than one stream (the silence gate on its own): the edge a caller's producer stream gets
@@ -469,18 +492,8 @@ static void pcmStageOut(smst_batch *b, smst_batch::PcmCounts &c, void *out, long
 		return;
 	}
 	if (most < 1) return;
-	const size_t esz = pcmElemBytes(format);
-	const long long row = pcmRowElems(most, C);
-	smst::launchPcmOut(format, b->dOut, (long long)C*maxLen, maxLen, b->dPcmOut, row, C, c.dev + S, S, C, most, b->dPcmOvers, e.stream());
-	if (hipMemcpyAsync(b->hPcmOut, b->dPcmOut, (size_t)S*row*esz, hipMemcpyDeviceToHost, e.stream()) != hipSuccess) throw smst::Error("hipMemcpyAsync (D2H) failed", true);
-	if (hipStreamSynchronize(e.stream()) != hipSuccess) throw smst::Error("hipStreamSynchronize failed", true);
-	for (int s = 0; s < S; ++s) {
-		if (n[s] <= 0) continue;
-		const unsigned char *src = b->hPcmOut + (size_t)s*row*esz;
-		unsigned char *dst = static_cast<unsigned char *>(out) + (size_t)s*ss*esz;
-		if (fs == C) std::memcpy(dst, src, (size_t)n[s]*C*esz);
-		else for (int i = 0; i < n[s]; ++i) std::memcpy(dst + (size_t)i*fs*esz, src + (size_t)i*C*esz, (size_t)C*esz);
-	}
+	smst::launchPcmOut(format, b->dOut, (long long)C*maxLen, maxLen, b->dPcmOut, pcmRowElems(most, C), C, c.dev + S, S, C, most, b->dPcmOvers, e.stream());
+	pcmRawOut(b, out, ss, fs, n, most, format);
 }
 
 int smst_batch_process_pcm(smst_batch *b, const void *in, long long iss, long long ifs, const int *inSamples,
@@ -538,6 +551,86 @@ int smst_batch_output_seek_pcm(smst_batch *b, const void *in, long long ss, long
 		endPcmCall(b, c);
 		if (memory == SMST_MEM_HOST) e.synchronize();
 	})
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// whole clips: exact() of every stream (Batch::exact; the clip kernels of smst_clip.h move each stream's segments)
+// ---------------------------------------------------------------------------------------------------------
+// Refusals, before anything runs.  inner: the frame stride of a frame buffer, 0 for planar ones
+static void checkExactArgs(const Batch &e, const void *in, const int *inSamples, const void *out, const int *outSamples, long long inInner, long long outInner, bool frames, int memory) {
+	if (memory != SMST_MEM_HOST && memory != SMST_MEM_DEVICE) throw smst::Error("unknown memory kind");
+	if (!inSamples || !outSamples) throw smst::Error("null sample counts");
+	if (frames && (inInner < e.channels() || outInner < e.channels())) throw smst::Error("frame stride smaller than the channel count");
+	for (int s = 0; s < e.streams(); ++s) {
+		if (outSamples[s] < 0) continue; // left out of the call
+		if (outSamples[s] == 0) throw smst::Error("exact(): outSamples[" + std::to_string(s) + "] is 0 (the playback rate is inSamples/outSamples; a negative count leaves the stream out)");
+		if (inSamples[s] < 0) throw smst::Error("exact(): negative inSamples[" + std::to_string(s) + "]");
+		if (!out || (inSamples[s] > 0 && !in)) throw smst::Error("null buffer with a non-zero sample count");
+	}
+}
+// the counts of the streams that take part (a stream left out moves no sample in either direction); returns the largest
+static int exactCounts(const int *n, const int *outSamples, int S, std::vector<int> &counts) {
+	counts.assign(S, 0);
+	int most = 0;
+	for (int s = 0; s < S; ++s) if (outSamples[s] >= 0) { counts[s] = n[s]; most = std::max(most, n[s]); }
+	return most;
+}
+// Batch::exact's flags -> the status array of the call (a stream that was left out keeps its entry)
+static void runExact(Batch &e, const Batch::ClipIo &io, const int *inSamples, const int *outSamples, int *status) {
+	std::vector<unsigned char> tooShort(e.streams(), 0);
+	e.exact(io, inSamples, outSamples, tooShort.data());
+	if (status) for (int s = 0; s < e.streams(); ++s) if (outSamples[s] >= 0) status[s] = tooShort[s] ? SMST_ERR_SHORT : SMST_OK;
+}
+static const char *const kShortMessage = "exact(): input shorter than outputSeekLength";
+
+int smst_batch_exact(smst_batch *b, const float *in, long long iss, long long ics, const int *inSamples,
+                     float *out, long long oss, long long ocs, const int *outSamples, int *status, int memory) {
+	if (!b || !b->engine) return fail("null batch");
+	SMST_TRY
+	{
+		Batch &e = *b->engine;
+		checkExactArgs(e, in, inSamples, out, outSamples, 0, 0, false, memory);
+		if (memory == SMST_MEM_DEVICE) {
+			runExact(e, Batch::ClipIo{in, iss, ics, out, oss, ocs, 0, nullptr}, inSamples, outSamples, status);
+		} else {
+			const int S = e.streams(), C = e.channels();
+			std::vector<int> nIn, nOut;
+			exactCounts(inSamples, outSamples, S, nIn);
+			const int maxOut = std::max(exactCounts(outSamples, outSamples, S, nOut), 1);
+			int maxIn;
+			const float *dIn = stageIn(b, in, iss, ics, nIn.data(), maxIn);
+			ensureStage(b->dOut, b->outCap, (size_t)S*C*maxOut, e.device(), b->stagingAllocs);
+			runExact(e, Batch::ClipIo{dIn, (long long)C*maxIn, maxIn, b->dOut, (long long)C*maxOut, maxOut, 0, nullptr}, inSamples, outSamples, status);
+			unstageOut(b, out, oss, ocs, nOut.data(), maxOut);
+		}
+	}
+	return SMST_OK;
+	SMST_CATCH
+}
+int smst_batch_exact_pcm(smst_batch *b, const void *in, long long iss, long long ifs, const int *inSamples,
+                         void *out, long long oss, long long ofs, const int *outSamples, int *status, int format, int memory) {
+	if (!b || !b->engine) return fail("null batch");
+	SMST_TRY
+	{
+		Batch &e = *b->engine;
+		checkPcmFormat(format, memory);
+		checkExactArgs(e, in, inSamples, out, outSamples, ifs, ofs, true, memory);
+		if (memory == SMST_MEM_DEVICE) {
+			runExact(e, Batch::ClipIo{in, iss, ifs, out, oss, ofs, format, b->dPcmOvers}, inSamples, outSamples, status);
+		} else {
+			const int S = e.streams(), C = e.channels();
+			std::vector<int> nIn, nOut;
+			const int mostIn = std::max(exactCounts(inSamples, outSamples, S, nIn), 1), mostOut = std::max(exactCounts(outSamples, outSamples, S, nOut), 1);
+			const size_t outBytes = (size_t)S*pcmRowElems(mostOut, C)*pcmElemBytes(format);
+			ensurePcmBytes(b->hPcmOut, b->hPcmOutCap, outBytes, true, e.device(), b->stagingAllocs);
+			ensurePcmBytes(b->dPcmOut, b->dPcmOutCap, outBytes, false, e.device(), b->stagingAllocs);
+			pcmRawIn(b, in, iss, ifs, nIn.data(), mostIn, format);
+			runExact(e, Batch::ClipIo{b->dPcmIn, pcmRowElems(mostIn, C), C, b->dPcmOut, pcmRowElems(mostOut, C), C, format, b->dPcmOvers}, inSamples, outSamples, status);
+			pcmRawOut(b, out, oss, ofs, nOut.data(), mostOut, format);
+		}
+	}
+	return SMST_OK;
+	SMST_CATCH
 }
 } // extern "C"
 static int pcmConvert(int device, int dir, int format, int streams, int channels, const int *counts,
@@ -602,6 +695,67 @@ int smst_debug_pcm_convert_counted(int device, int format, int streams, int chan
                                    long long *clamped, long long *nans) {
 	if (!clamped || !nans) return fail("pcm convert: null count arrays");
 	return pcmConvert(device, 1, format, streams, channels, counts, src, srcSS, srcInner, dst, dstSS, dstInner, clamped, nans);
+}
+// the two clip kernels alone (smst_clip.h): see include/smst.h
+int smst_debug_clip_copy(int device, int dir, int format, int streams, int channels, const int *segments,
+                         const void *src, long long srcSS, long long srcInner, void *dst, long long dstSS, long long dstInner,
+                         long long *clamped, long long *nans) {
+	SMST_TRY
+	if (format != 0) checkPcmFormat(format, SMST_MEM_HOST);
+	if (dir != 0 && dir != 1) throw smst::Error("clip copy: dir is 0 (caller's buffer -> planar image) or 1 (planar image -> caller's buffer)");
+	if (streams < 1 || channels < 1 || channels > 16 || !segments || !src || !dst || srcSS < 0 || dstSS < 0 || srcInner < 0 || dstInner < 0) throw smst::Error("clip copy: bad arguments");
+	// frames either side spans from its base, and the largest count
+	int srcEnd = 0, dstEnd = 0, most = 0;
+	for (int k = 0; k < 2*streams; ++k) {
+		const int *g = segments + 4*k;
+		if (g[0] < 0 || g[1] < 0 || g[2] < 0) throw smst::Error("clip copy: negative segment offset or count");
+		if (g[2] == 0) continue;
+		if (!g[3]) srcEnd = std::max(srcEnd, g[0] + g[2]);
+		dstEnd = std::max(dstEnd, g[1] + g[2]);
+		most = std::max(most, g[2]);
+	}
+	// dir 0: src is the caller's side (frames of `format`, or planar for 0), dst the planar image; dir 1: the reverse
+	const bool srcFrames = dir == 0 && format != 0, dstFrames = dir == 1 && format != 0;
+	if ((srcFrames && srcInner < channels) || (dstFrames && dstInner < channels)) throw smst::Error("frame stride smaller than the channel count");
+	auto spanBytes = [&](bool frames, int end, long long ss, long long inner) -> size_t {
+		if (!end) return 0;
+		return frames ? size_t((streams - 1)*ss + (end - 1)*inner + channels)*pcmElemBytes(format) : size_t((streams - 1)*ss + (channels - 1)*inner + end)*sizeof(float);
+	};
+	const size_t srcBytes = spanBytes(srcFrames, srcEnd, srcSS, srcInner), dstBytes = spanBytes(dstFrames, dstEnd, dstSS, dstInner);
+	if (hipSetDevice(device) != hipSuccess) throw smst::Error("hipSetDevice failed", true);
+	struct DeviceBuffer { // freed when the function leaves, whichever way
+		void *p = nullptr;
+		~DeviceBuffer() { if (p) hipFree(p); }
+		void alloc(size_t bytes) { if (hipMalloc(&p, bytes) != hipSuccess) throw smst::Error("clip copy: hipMalloc failed", true); }
+	} dSrc, dDst, dSegs, dOvers;
+	auto hip = [](hipError_t err) { if (err != hipSuccess) throw smst::Error(std::string("clip copy: ") + hipGetErrorString(err), true); };
+	std::vector<unsigned> overs((size_t)2*streams, 0u);
+	const bool counted = dstFrames && (clamped || nans);
+	dSrc.alloc(srcBytes + 32);
+	dDst.alloc(dstBytes + 32);
+	dSegs.alloc((size_t)2*streams*sizeof(smst::ClipSeg));
+	// the device buffers sit as far behind a 16-byte boundary as the caller's do
+	unsigned char *s0 = static_cast<unsigned char *>(dSrc.p) + reinterpret_cast<uintptr_t>(src)%16, *d0 = static_cast<unsigned char *>(dDst.p) + reinterpret_cast<uintptr_t>(dst)%16;
+	if (srcBytes) hip(hipMemcpy(s0, src, srcBytes, hipMemcpyHostToDevice));
+	if (dstBytes) hip(hipMemcpy(d0, dst, dstBytes, hipMemcpyHostToDevice));
+	hip(hipMemcpy(dSegs.p, segments, (size_t)2*streams*sizeof(smst::ClipSeg), hipMemcpyHostToDevice));
+	if (counted) {
+		dOvers.alloc(pcmOversBytes(streams));
+		hip(hipMemcpy(dOvers.p, overs.data(), pcmOversBytes(streams), hipMemcpyHostToDevice));
+	}
+	const smst::ClipSeg *segs = static_cast<const smst::ClipSeg *>(dSegs.p);
+	if (dir == 0) smst::launchClipIn(format, s0, srcSS, srcInner, reinterpret_cast<float *>(d0), dstSS, dstInner, segs, streams, channels, most, nullptr);
+	else smst::launchClipOut(format, reinterpret_cast<const float *>(s0), srcSS, srcInner, d0, dstSS, dstInner, segs, streams, channels, most, static_cast<unsigned *>(dOvers.p), nullptr);
+	hip(hipGetLastError());
+	hip(hipStreamSynchronize(nullptr));
+	if (dstBytes) hip(hipMemcpy(dst, d0, dstBytes, hipMemcpyDeviceToHost));
+	if (counted) hip(hipMemcpy(overs.data(), dOvers.p, pcmOversBytes(streams), hipMemcpyDeviceToHost));
+	for (int s = 0; s < streams; ++s) {
+		if (clamped) clamped[s] = overs[2*s];
+		if (nans) nans[s] = overs[2*s + 1];
+	}
+	return SMST_OK;
+	SMST_CATCH
 }
 int smst_batch_take_pcm_overs(smst_batch *b, long long *clamped, long long *nans) {
 	BATCH_CALL({
@@ -1215,16 +1369,16 @@ int smst_exact(smst_stretch *h, const float *const *inputs, int inputSamples, fl
 	if (!engineOf(h)) return fail("unconfigured handle");
 	Batch &e = *engineOf(h);
 	const int C = e.channels();
-	float playbackRate = inputSamples/float(outputSamples);
-	int seekLength = e.outputSeekLength(playbackRate);
-	if (inputSamples < seekLength) {
+	const Batch::ExactLengths l = e.exactLengths(inputSamples, outputSamples); // (the lengths smst_batch_exact cuts every stream's clip by)
+	const float playbackRate = l.rate;
+	const int seekLength = l.seekLength, outputIndex = l.outputIndex;
+	if (l.tooShort) {
 		for (int c = 0; c < C; ++c) std::fill(outputs[c], outputs[c] + outputSamples, 0.0f);
-		g_lastError = "exact(): input shorter than outputSeekLength";
+		g_lastError = kShortMessage;
 		return SMST_ERR_SHORT;
 	}
 	int rc = smst_output_seek(h, inputs, seekLength);
 	if (rc != SMST_OK) return rc;
-	int outputIndex = int(outputSamples - seekLength/playbackRate);
 	std::vector<const float *> inOff(C);
 	std::vector<float *> outOff(C);
 	for (int c = 0; c < C; ++c) inOff[c] = inputs[c] + seekLength;

@@ -1,0 +1,143 @@
+// Whole clips of ragged lengths at the batch API's boundary (include/smst.h: smst_batch_exact, smst_batch_exact_pcm): the engine's kernels address
+// caller memory as base + s*streamStride + c*channelStride + i, the same offsets for every stream, while exact() of S clips of S rates
+// cuts every clip at places of its own (outputSeekLength(rate_s) in the input, outputIndex_s in the output).  So the engine runs on planar
+// fp32 images of its own in which every stream's stage begins at one column, and the two kernels here move the clips: per stream two
+// segments (ClipSeg, smst_device.h) of `count` frames from frame `src` of the source to frame `dst` of the destination.
+//   kClipIn<T>   the caller's frames of format T -> the input image            (pcmTileIn of smst_pcm.h on a run that begins at the segment)
+//   kClipOut<T>  the output image -> the caller's frames, overs counted        (pcmTileOut; a "zeros" segment has no source)
+//   kClipPlanar  planar fp32 -> planar fp32, either direction                  (the caller's buffer is planar itself)
+// Included by smst_state.hip only, behind smst_pcm.h: the conversion rule, the tiling of a run and the overs scheme are the ones defined there.
+//
+// Alignment.  A segment's offset moves the run's base address, so nothing is known about it beyond the element's alignment -- offsets that are
+// no multiple of 4 frames are the normal case.  The frame kernels derive the first 16-byte group boundary from the run's ADDRESS
+// (pcmTileRun), per segment.  kClipPlanar moves a row's run of floats through LDS: the tiles are cut on the DESTINATION's 16-byte
+// boundaries (tile t > 0 begins `lead` floats behind t*kClipTileFloats), so every store in between is one aligned 16-byte store; the source is
+// read as the aligned 16-byte words that cover the tile -- a word that reaches over the tile's edge but lies inside the run is read whole (a
+// neighbour's floats, read twice, never written), so on both sides narrow accesses happen at a run's two ends only.  The LDS image is
+// shifted so that the destination's groups are 16-byte aligned in LDS as well; the source side writes it dword by dword.
+#pragma once
+#include "smst_pcm.h"
+
+namespace smst {
+
+constexpr int kClipTileFloats = 2048; // floats of one row that one workgroup step of kClipPlanar moves
+inline size_t clipPlanarLdsBytes() { return size_t(kClipTileFloats + 16)*sizeof(float); }
+
+// frames of format T -> the planar image.  grid (tiles, S, 2 segments), 256 threads
+template <typename T> __global__ __launch_bounds__(256) void kClipIn(const T *__restrict__ in, long long inStreamStride, long long inFrameStride,
+		float *__restrict__ image, long long imageStreamStride, long long imageChannelStride, const ClipSeg *__restrict__ segs, int C) {
+	extern __shared__ __attribute__((aligned(16))) unsigned char smemRaw[];
+	const int s = blockIdx.y;
+	const ClipSeg g = segs[2*s + blockIdx.z];
+	if (g.count < 1 || g.zeros) return;
+	pcmTileIn<T>(in + (size_t)s*inStreamStride + (size_t)g.src*inFrameStride, inFrameStride, g.count, image + (size_t)s*imageStreamStride + g.dst, imageChannelStride,
+	             blockIdx.x, C, reinterpret_cast<float *>(smemRaw));
+}
+
+// the planar image -> frames of format T.  overs (may be null): [S][2] counters as kPcmOut's (a run of zeros adds nothing: 0.0 has a code in every format)
+template <typename T> __global__ __launch_bounds__(256) void kClipOut(const float *__restrict__ image, long long imageStreamStride, long long imageChannelStride,
+		T *__restrict__ out, long long outStreamStride, long long outFrameStride, const ClipSeg *__restrict__ segs, int C, unsigned *__restrict__ overs) {
+	extern __shared__ __attribute__((aligned(16))) unsigned char smemRaw[];
+	const int s = blockIdx.y;
+	const ClipSeg g = segs[2*s + blockIdx.z];
+	if (g.count < 1) return;
+	const float *src = g.zeros ? nullptr : image + (size_t)s*imageStreamStride + g.src;
+	unsigned over;
+	if (!pcmTileOut<T>(src, imageChannelStride, out + (size_t)s*outStreamStride + (size_t)g.dst*outFrameStride, outFrameStride, g.count, blockIdx.x, C, reinterpret_cast<float *>(smemRaw), over)) return;
+	pcmAddOvers(overs, s, over);
+}
+
+// Tile t of one row's run of `total` floats, src (null: zeros) -> dst, through `lds`.  Every lane of the workgroup calls it.
+__device__ inline void clipRowTile(const float *__restrict__ src, float *__restrict__ dst, int total, int t, float *lds) {
+	const int tid = threadIdx.x;
+	const int lead = int((0 - (reinterpret_cast<uintptr_t>(dst) >> 2)) & 3u); // floats in front of dst's first 16-byte boundary
+	const int e0 = t ? t*kClipTileFloats + lead : 0;
+	if (e0 >= total) return;
+	const int e1 = (t + 1)*kClipTileFloats + lead;
+	const int count = (e1 < total ? e1 : total) - e0;
+	const int head = t ? 0 : (lead < count ? lead : count);
+	const int shift = (4 - head) & 3; // element e0 + i of the run at lds[shift + i]: the destination's groups begin at multiples of 4
+	if (src) {
+		const int back = int((reinterpret_cast<uintptr_t>(src + e0) >> 2) & 3u); // floats between the 16-byte boundary at or in front of src + e0 and it
+		const int nWords = (back + count + 3)/4;
+		for (int w = tid; w < nWords; w += 256) {
+			const int a = e0 - back + 4*w;  // the word's first element in the run (negative / beyond the run only at the run's two ends)
+			const int i = shift - back + 4*w; // ... and in lds
+			if (a >= 0 && a + 4 <= total) {
+				const PcmWord4 v = *reinterpret_cast<const PcmWord4 *>(src + a);
+				for (int k = 0; k < 4; ++k) if (i + k >= 0) lds[i + k] = __int_as_float(int(v[k]));
+			} else {
+				for (int k = 0; k < 4; ++k) if (a + k >= 0 && a + k < total && i + k >= 0) lds[i + k] = src[a + k];
+			}
+		}
+		__syncthreads();
+	}
+	float *p = dst + e0;
+	if (tid < head) p[tid] = src ? lds[shift + tid] : 0.0f;
+	const int nGroups = (count - head)/4;
+	for (int g = tid; g < nGroups; g += 256) {
+		const int e = head + 4*g;
+		PcmWord4 v;
+		for (int k = 0; k < 4; ++k) v[k] = src ? unsigned(__float_as_int(lds[shift + e + k])) : 0u;
+		*reinterpret_cast<PcmWord4 *>(p + e) = v;
+	}
+	const int done = head + 4*nGroups;
+	if (tid < count - done) p[done + tid] = src ? lds[shift + done + tid] : 0.0f;
+	if (src) __syncthreads(); // (the next row's words go into the same image)
+}
+
+// planar fp32 -> planar fp32: src[s*srcStreamStride + c*srcChannelStride + seg.src + i] -> dst[s*dstStreamStride + c*dstChannelStride + seg.dst + i], i < seg.count.
+// grid (tiles, S, 2 segments), 256 threads; a workgroup takes its tile of every channel's row in turn
+__global__ __launch_bounds__(256) void kClipPlanar(const float *__restrict__ src, long long srcStreamStride, long long srcChannelStride,
+		float *__restrict__ dst, long long dstStreamStride, long long dstChannelStride, const ClipSeg *__restrict__ segs, int C) {
+	extern __shared__ __attribute__((aligned(16))) unsigned char smemRaw[];
+	const int s = blockIdx.y;
+	const ClipSeg g = segs[2*s + blockIdx.z];
+	if (g.count < 1) return;
+	for (int c = 0; c < C; ++c) {
+		const float *from = g.zeros ? nullptr : src + (size_t)s*srcStreamStride + (size_t)c*srcChannelStride + g.src;
+		clipRowTile(from, dst + (size_t)s*dstStreamStride + (size_t)c*dstChannelStride + g.dst, g.count, blockIdx.x, reinterpret_cast<float *>(smemRaw));
+	}
+}
+
+static void launchClipPlanar(const float *src, long long srcSS, long long srcCS, float *dst, long long dstSS, long long dstCS, const ClipSeg *segs, int S, int C, int maxCount, hipStream_t st) {
+	hipLaunchKernelGGL(kClipPlanar, dim3(divUp(maxCount, kClipTileFloats), S, 2), dim3(256), clipPlanarLdsBytes(), st, src, srcSS, srcCS, dst, dstSS, dstCS, segs, C);
+}
+template <typename T> static void launchClipInAs(dim3 grid, int C, hipStream_t st, const void *in, long long inSS, long long inFS, float *image, long long imageSS, long long imageCS, const ClipSeg *segs) {
+	hipLaunchKernelGGL(kClipIn<T>, grid, dim3(256), pcmLdsBytes(C), st, static_cast<const T *>(in), inSS, inFS, image, imageSS, imageCS, segs, C);
+}
+template <typename T> static void launchClipOutAs(dim3 grid, int C, hipStream_t st, const float *image, long long imageSS, long long imageCS, void *out, long long outSS, long long outFS,
+		const ClipSeg *segs, unsigned *overs) {
+	hipLaunchKernelGGL(kClipOut<T>, grid, dim3(256), pcmLdsBytes(C), st, image, imageSS, imageCS, static_cast<T *>(out), outSS, outFS, segs, C, overs);
+}
+void launchClipIn(int format, const void *in, long long inSS, long long inInner, float *image, long long imageSS, long long imageCS, const ClipSeg *segs, int S, int C, int maxCount, hipStream_t st) {
+	if (maxCount < 1) return;
+	const dim3 grid(divUp(maxCount, kPcmTileFrames), S, 2);
+	switch (format) {
+	case 0: launchClipPlanar(static_cast<const float *>(in), inSS, inInner, image, imageSS, imageCS, segs, S, C, maxCount, st); break;
+	case kPcmS16: launchClipInAs<int16_t>(grid, C, st, in, inSS, inInner, image, imageSS, imageCS, segs); break;
+	case kPcmF32: launchClipInAs<float>(grid, C, st, in, inSS, inInner, image, imageSS, imageCS, segs); break;
+	case kPcmS24: launchClipInAs<PcmS24>(grid, C, st, in, inSS, inInner, image, imageSS, imageCS, segs); break;
+	case kPcmS32: launchClipInAs<int32_t>(grid, C, st, in, inSS, inInner, image, imageSS, imageCS, segs); break;
+	case kPcmF16: launchClipInAs<PcmF16>(grid, C, st, in, inSS, inInner, image, imageSS, imageCS, segs); break;
+	default: throw std::invalid_argument("unknown PCM format");
+	}
+	countLaunch(LK_CLIP_IN);
+}
+void launchClipOut(int format, const float *image, long long imageSS, long long imageCS, void *out, long long outSS, long long outInner, const ClipSeg *segs, int S, int C, int maxCount,
+                   unsigned *overs, hipStream_t st) {
+	if (maxCount < 1) return;
+	const dim3 grid(divUp(maxCount, kPcmTileFrames), S, 2);
+	switch (format) {
+	case 0: launchClipPlanar(image, imageSS, imageCS, static_cast<float *>(out), outSS, outInner, segs, S, C, maxCount, st); break;
+	case kPcmS16: launchClipOutAs<int16_t>(grid, C, st, image, imageSS, imageCS, out, outSS, outInner, segs, overs); break;
+	case kPcmF32: launchClipOutAs<float>(grid, C, st, image, imageSS, imageCS, out, outSS, outInner, segs, overs); break;
+	case kPcmS24: launchClipOutAs<PcmS24>(grid, C, st, image, imageSS, imageCS, out, outSS, outInner, segs, overs); break;
+	case kPcmS32: launchClipOutAs<int32_t>(grid, C, st, image, imageSS, imageCS, out, outSS, outInner, segs, overs); break;
+	case kPcmF16: launchClipOutAs<PcmF16>(grid, C, st, image, imageSS, imageCS, out, outSS, outInner, segs, overs); break;
+	default: throw std::invalid_argument("unknown PCM format");
+	}
+	countLaunch(LK_CLIP_OUT);
+}
+
+} // namespace smst

@@ -161,7 +161,7 @@ __host__ __device__ inline bool analysisWindowInCall(int B, int M, int I, int in
 // form" tests assert through these that BOTH forms really ran.
 enum LaunchKind {
 	LK_VOC_ALIGNED, LK_VOC_STAGED, LK_VOC_GATHER, LK_VOC_N, LK_VOC_ONE, LK_VOC_ACROSS, LK_VOC_CONT, LK_CHAIN_UNFUSED,
-	LK_ANALYSE_TEAMS, LK_ANALYSE_FAST, LK_ANALYSE_GENERIC, LK_SYNTH_TEAMS, LK_SYNTH_FAST, LK_SYNTH_GENERIC, LK_SYNTH_EMIT, LK_EMIT_CARRIED, LK_FEED_ONE_PASS, LK_PCM_IN, LK_PCM_OUT, LK_COUNT
+	LK_ANALYSE_TEAMS, LK_ANALYSE_FAST, LK_ANALYSE_GENERIC, LK_SYNTH_TEAMS, LK_SYNTH_FAST, LK_SYNTH_GENERIC, LK_SYNTH_EMIT, LK_EMIT_CARRIED, LK_FEED_ONE_PASS, LK_PCM_IN, LK_PCM_OUT, LK_CLIP_IN, LK_CLIP_OUT, LK_COUNT
 };
 long long launchCount(const char *name); // -1: unknown name
 
@@ -213,5 +213,15 @@ void launchPcmIn(int format, const void *in, long long inStreamStride, long long
                  const int *counts, int S, int C, int maxFrames, hipStream_t st);
 void launchPcmOut(int format, const float *in, long long inStreamStride, long long inChannelStride, void *out, long long outStreamStride, long long outFrameStride,
                   const int *counts, int S, int C, int maxFrames, unsigned *overs, hipStream_t st);
+// Whole clips of ragged lengths (smst_clip.h; Batch::exact): each stream moves two segments of frames between the caller's buffer and a planar
+// fp32 image -- `count` frames from frame `src` of its row(s) on the source side to frame `dst` on the destination side; zeros != 0: no
+// source, the destination gets 0.0 (its code, in a frame format).  segs: [S][2] device.  format: an SMST_PCM_* code, or 0 for a caller's
+// buffer that is planar fp32 itself (inner stride = channel stride instead of frame stride; the copy is then plain in both directions).
+// maxCount: the largest count of any segment (sizes the grid; nothing is launched for 0).
+struct ClipSeg { int src, dst, count, zeros; };
+void launchClipIn(int format, const void *in, long long inStreamStride, long long inInnerStride, float *image, long long imageStreamStride, long long imageChannelStride,
+                  const ClipSeg *segs, int S, int C, int maxCount, hipStream_t st);
+void launchClipOut(int format, const float *image, long long imageStreamStride, long long imageChannelStride, void *out, long long outStreamStride, long long outInnerStride,
+                   const ClipSeg *segs, int S, int C, int maxCount, unsigned *overs, hipStream_t st);
 
 } // namespace smst

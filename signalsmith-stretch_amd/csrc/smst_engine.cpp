@@ -438,6 +438,8 @@ void Batch::releaseAll() {
 		callSets[i].done = callSets[i].tables = nullptr;
 		if (pendSets[i].done) hipEventDestroy(pendSets[i].done);
 		pendSets[i].done = nullptr;
+		if (clipSets[i].done) hipEventDestroy(clipSets[i].done);
+		clipSets[i].done = nullptr;
 	}
 	if (evStart) hipEventDestroy(evStart);
 	if (evOrder) hipEventDestroy(evOrder);
@@ -592,21 +594,27 @@ void Batch::reset() { // signalsmith-stretch.h:49-60
 	}
 }
 
-void Batch::resetStream(int s) { // reset() for one stream; kResetStreams writes both halves of the double buffers, so which half is current does not matter
+void Batch::resetStream(int s) { // reset() for one stream
 	if (s < 0 || s >= S) throw Error("stream index out of range");
+	std::vector<unsigned char> one(S, 0);
+	one[s] = 1;
+	resetStreamsMasked(one.data());
+}
+void Batch::resetStreamsMasked(const unsigned char *active) { // reset() for the masked streams; kResetStreams writes both halves of the double buffers, so which half is current does not matter
 	SMST_HIP(hipSetDevice(dev));
 	SMST_HIP(hipStreamSynchronize(st)); // (an earlier launch may still read the mask buffer)
-	SMST_HIP(hipMemsetAsync(d.stFreq + 2*(size_t)s, 0, 2*sizeof(float), st));
-	std::fill(resetBitsV.begin(), resetBitsV.end(), 0);
-	resetBitsV[s] = RESET_STFT | RESET_INPUT | RESET_PREV | RESET_OUTPUT;
+	for (int s = 0; s < S; ++s) resetBitsV[s] = active[s] ? (RESET_STFT | RESET_INPUT | RESET_PREV | RESET_OUTPUT | RESET_FREQ) : 0;
 	resetStreams(resetBitsV.data(), 0);
-	lastHop[s] = LastHop();
-	lastSteps[s] = 0;
-	lastStarts[s] = 0;
-	const unsigned seed = seedAfterDroppedBlock(s);
-	pend[s] = PendingBlock();
-	sched[s] = StreamSched();
-	sched[s].seed = seed;
+	for (int s = 0; s < S; ++s) {
+		if (!active[s]) continue;
+		lastHop[s] = LastHop();
+		lastSteps[s] = 0;
+		lastStarts[s] = 0;
+		const unsigned seed = seedAfterDroppedBlock(s);
+		pend[s] = PendingBlock();
+		sched[s] = StreamSched();
+		sched[s].seed = seed;
+	}
 }
 
 // ---- parameters ------------------------------------------------------------------------------------------
@@ -1652,19 +1660,21 @@ void Batch::flush(float *out, long long outSS, long long outCS, const int *outSa
 }
 
 // ---- outputSeek -------------------------------------------------------------------------------------------
-void Batch::outputSeek(const float *in, long long inSS, long long inCS, const int *inputLengths) {
+void Batch::outputSeek(const float *in, long long inSS, long long inCS, const int *inputLengths, const unsigned char *active) {
 	// signalsmith-stretch.h:173-204
-	reset();
+	if (active) resetStreamsMasked(active);
+	else reset();
 	const int outLat = outputLatency(), inLat = inputLatency();
-	std::vector<int> seekSamples(S), surplus(S), preOut(S, outLat);
-	std::vector<double> rates(S);
+	std::vector<int> seekSamples(S, 0), surplus(S, 0), preOut(S, outLat);
+	std::vector<double> rates(S, 1.0);
 	for (int s = 0; s < S; ++s) {
+		if (active && !active[s]) continue;
 		surplus[s] = std::max(inputLengths[s] - inLat, 0);
 		float playbackRate = surplus[s]/float(outLat);
 		seekSamples[s] = inputLengths[s] - surplus[s];
 		rates[s] = playbackRate;
 	}
-	seek(in, inSS, inCS, seekSamples.data(), rates.data());
+	seek(in, inSS, inCS, seekSamples.data(), rates.data(), active);
 	// pre-roll output into scratch [S][C][outLat]
 	const size_t need = (size_t)S*C*outLat;
 	if (need > scratchOutCapacity) {
@@ -1676,20 +1686,115 @@ void Batch::outputSeek(const float *in, long long inSS, long long inCS, const in
 	// otherwise run stream groups with equal offsets
 	std::vector<unsigned char> mask(S);
 	std::vector<int> done(S, 0);
+	for (int s = 0; s < S; ++s) if (active && !active[s]) done[s] = 1;
 	for (int s0 = 0; s0 < S; ++s0) {
 		if (done[s0]) continue;
 		std::fill(mask.begin(), mask.end(), 0);
 		for (int s = s0; s < S; ++s) if (!done[s] && seekSamples[s] == seekSamples[s0]) { mask[s] = 1; done[s] = 1; }
 		process(in + seekSamples[s0], inSS, inCS, surplus.data(), dScratchOut, (long long)C*outLat, outLat, preOut.data(), mask.data());
 	}
-	// "put the thing down, flip it and reverse it" (:198-203): negate, reverse, add into the output ring
+	// "put the thing down, flip it and reverse it" (:198-203): negate, reverse, add into the output ring (a stream that is masked out
+	// gets an offset behind its ring: nothing is added)
 	std::vector<int> off(S, 0);
-	for (int s = 0; s < S; ++s) off[s] = aheadOffset(s);
+	for (int s = 0; s < S; ++s) off[s] = (active && !active[s]) ? d.carryLen : aheadOffset(s);
 	SMST_HIP(hipMemcpyAsync(dAux0, off.data(), S*sizeof(int), hipMemcpyHostToDevice, st));
 	SMST_HIP(hipStreamSynchronize(st));
 	settleCarry();
 	launchAddPreRoll(d, dScratchOut, outLat, dAux0, st);
 	SMST_HIP(hipGetLastError());
+}
+
+// ---- exact ------------------------------------------------------------------------------------------------
+void Batch::growClipImage(float *&image, size_t &capacity, size_t need) {
+	if (need <= capacity) return;
+	if (image) { SMST_HIP(hipStreamSynchronize(st)); devFree(image); wsBytes -= capacity*sizeof(float); }
+	image = nullptr;
+	capacity = 0;
+	const size_t want = need + need/8 + 1024;
+	image = devAlloc<float>(want);
+	capacity = want;
+	wsBytes += want*sizeof(float);
+}
+
+void Batch::exact(const ClipIo &io, const int *inSamples, const int *outSamples, unsigned char *tooShort) {
+	// signalsmith-stretch.h:468-491, every participating stream at once.  A stream cuts its clip where its own rate says (exactLengths), the
+	// engine's kernels take one offset for all streams: so the stages run on planar images in which every stream's stage begins at one
+	// column -- input [0, seekLength_s) at column 0 and [seekLength_s, in_s) at column P; output [0, outputIndex_s) from column 0 and the
+	// flush [outputIndex_s, out_s) from column Q -- and kClipIn / kClipOut (smst_clip.h) move the segments.  A caller's buffer that is planar
+	// fp32 itself serves the two stages whose offset is 0 for every stream directly: outputSeek reads it, the main process writes it; only the
+	// input behind seekLength_s and the flush go through the images.
+	SMST_HIP(hipSetDevice(dev));
+	const bool direct = io.format == 0;
+	for (ClipSet &t : clipSets) { // (both sets with the first call: the second call allocates nothing)
+		if (t.host) continue;
+		t.host = pinnedAlloc<ClipSeg>((size_t)4*S);
+		t.dev = devAlloc<ClipSeg>((size_t)4*S);
+		wsBytes += (size_t)4*S*sizeof(ClipSeg);
+		SMST_HIP(hipEventCreateWithFlags(&t.done, hipEventDisableTiming));
+	}
+	clipCur ^= 1;
+	ClipSet &cs = clipSets[clipCur];
+	if (cs.used) SMST_HIP(hipEventSynchronize(cs.done)); // (the call before the previous one: its clip kernels must have read the tables)
+	cs.used = false;
+	std::vector<int> seekLen(S, 0), rest(S, 0), procOut(S, 0), flushN(S, 0);
+	std::vector<float> rates(S, 0.0f);
+	std::vector<unsigned char> run(S, 0);
+	int maxSeek = 0, maxRest = 0, maxProc = 0, maxFlush = 0, maxZeros = 0;
+	bool anyRun = false;
+	for (int s = 0; s < S; ++s) {
+		if (outSamples[s] < 0) continue;
+		ExactLengths l = exactLengths(inSamples[s], outSamples[s]);
+		if (l.tooShort) { maxZeros = std::max(maxZeros, outSamples[s]); continue; }
+		l.outputIndex = std::min(std::max(l.outputIndex, 0), outSamples[s]); // (seekLength/rate <= outSamples[s] but for its rounding: the two output parts stay inside the stream's count)
+		run[s] = 1;
+		anyRun = true;
+		rates[s] = l.rate;
+		seekLen[s] = l.seekLength; rest[s] = inSamples[s] - l.seekLength;
+		procOut[s] = l.outputIndex; flushN[s] = outSamples[s] - l.outputIndex;
+		maxSeek = std::max(maxSeek, seekLen[s]); maxRest = std::max(maxRest, rest[s]);
+		maxProc = std::max(maxProc, procOut[s]); maxFlush = std::max(maxFlush, flushN[s]);
+	}
+	// columns and row pitches: multiples of 4 floats, so that every row and both columns of an image begin on 16-byte boundaries
+	auto up4 = [](int n) { return (n + 3)/4*4; };
+	const int P = direct ? 0 : up4(maxSeek), Q = direct ? 0 : up4(maxProc);
+	const int pitchIn = std::max(up4(P + maxRest), 4), pitchOut = std::max(up4(Q + maxFlush), 4);
+	growClipImage(dClipIn, clipInCapacity, (size_t)S*C*pitchIn);
+	growClipImage(dClipOut, clipOutCapacity, (size_t)S*C*pitchOut);
+	ClipSeg *segIn = cs.host, *segOut = cs.host + (size_t)2*S;
+	for (int s = 0; s < S; ++s) {
+		const ClipSeg none{0, 0, 0, 0};
+		segIn[2*s] = segIn[2*s + 1] = segOut[2*s] = segOut[2*s + 1] = none;
+		if (run[s]) {
+			if (!direct) segIn[2*s] = ClipSeg{0, 0, seekLen[s], 0};
+			segIn[2*s + 1] = ClipSeg{seekLen[s], P, rest[s], 0};
+			if (!direct) segOut[2*s] = ClipSeg{0, 0, procOut[s], 0};
+			segOut[2*s + 1] = ClipSeg{Q, procOut[s], flushN[s], 0};
+		} else if (outSamples[s] > 0) {
+			segOut[2*s] = ClipSeg{0, 0, outSamples[s], 1}; // too short: zeros, and the stream's state stays as it is
+		}
+	}
+	SMST_HIP(hipMemcpyAsync(cs.dev, cs.host, (size_t)4*S*sizeof(ClipSeg), hipMemcpyHostToDevice, st));
+	const long long inImgSS = (long long)C*pitchIn, outImgSS = (long long)C*pitchOut;
+	launchClipIn(io.format, io.in, io.inStreamStride, io.inInnerStride, dClipIn, inImgSS, pitchIn, cs.dev, S, C, std::max(direct ? 0 : maxSeek, maxRest), st);
+	// the engine reads its input on more than one stream (the silence gate on its own): the edge a caller's producer stream gets
+	waitForStream(st);
+	if (anyRun) {
+		if (direct) {
+			outputSeek(static_cast<const float *>(io.in), io.inStreamStride, io.inInnerStride, seekLen.data(), run.data());
+			process(dClipIn, inImgSS, pitchIn, rest.data(), static_cast<float *>(io.out), io.outStreamStride, io.outInnerStride, procOut.data(), run.data());
+		} else {
+			outputSeek(dClipIn, inImgSS, pitchIn, seekLen.data(), run.data());
+			process(dClipIn + P, inImgSS, pitchIn, rest.data(), dClipOut, outImgSS, pitchOut, procOut.data(), run.data());
+		}
+		flush(dClipOut + Q, outImgSS, pitchOut, flushN.data(), rates.data(), run.data());
+	}
+	// behind the call's last emitting kernel (everything of a call is joined into `st`), in front of whatever synchronize() / signalStream() wait for
+	launchClipOut(io.format, dClipOut, outImgSS, pitchOut, io.out, io.outStreamStride, io.outInnerStride, cs.dev + (size_t)2*S, S, C,
+	              std::max(std::max(direct ? 0 : maxProc, maxFlush), maxZeros), io.overs, st);
+	SMST_HIP(hipEventRecord(cs.done, st));
+	cs.used = true;
+	SMST_HIP(hipGetLastError());
+	if (tooShort) for (int s = 0; s < S; ++s) if (outSamples[s] >= 0) tooShort[s] = run[s] ? 0 : 1; // (only once every stage has been issued)
 }
 
 // ---- copy -------------------------------------------------------------------------------------------------

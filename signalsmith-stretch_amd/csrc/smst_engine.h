@@ -1,6 +1,7 @@
 // Host-side engine: owns a batch of independent streams on one GPU, mirrors the reference's block scheduler
 // (signalsmith-stretch.h:280-319) per stream, and drives the gfx950 kernels tile by tile.
 #pragma once
+#include <algorithm>
 #include <cstddef>
 #include <cstdint>
 #include <string>
@@ -85,7 +86,26 @@ public:
 	          const double *playbackRates, const unsigned char *active = nullptr); // :140-165
 	void flush(float *out, long long outStreamStride, long long outChannelStride, const int *outSamples,
 	           const float *playbackRates, const unsigned char *active = nullptr); // :427-464
-	void outputSeek(const float *in, long long inStreamStride, long long inChannelStride, const int *inputLengths); // :173-204
+	void outputSeek(const float *in, long long inStreamStride, long long inChannelStride, const int *inputLengths,
+	                const unsigned char *active = nullptr); // :173-204; with a mask: only those streams are reset, sought and folded back
+	// exact() (:468-491): the lengths of its three stages for one clip -- outputSeek(in[0, seekLength)), process(in[seekLength, in) -> out[0, outputIndex)),
+	// flush(out[outputIndex, out), rate) -- in the reference's own arithmetic (:470-472, :483).  outputSamples > 0; tooShort: :471-480, nothing else is set.
+	struct ExactLengths { float rate; int seekLength, outputIndex; bool tooShort; };
+	ExactLengths exactLengths(int inputSamples, int outputSamples) const {
+		ExactLengths l{inputSamples/float(outputSamples), 0, 0, false};
+		l.seekLength = outputSeekLength(l.rate);
+		l.tooShort = inputSamples < l.seekLength;
+		if (!l.tooShort) l.outputIndex = int(outputSamples - l.seekLength/l.rate);
+		return l;
+	}
+	// exact() of every stream with outSamples[s] >= 0, each a whole clip of its own length and rate, in ONE outputSeek, ONE main process and ONE
+	// flush.  The caller's buffers (device memory) are planar fp32 (format 0: inner stride = channel stride) or frames of an SMST_PCM_* format
+	// (inner stride = frame stride); the stages run on the engine's own planar images, in which every stream's stage begins at one column
+	// (smst_clip.h).  A stream whose input is shorter than its outputSeekLength gets zeros and keeps its state (:471-480).  tooShort (host, may
+	// be null): 1 for such a stream, 0 for the others that take part, written once every stage has been issued; a stream left out keeps its entry.  overs (device, may be null): [S][2] counters of the frame conversion.
+	// Counts are checked by the caller: outSamples[s] != 0, inSamples[s] >= 0 where outSamples[s] > 0.
+	struct ClipIo { const void *in; long long inStreamStride, inInnerStride; void *out; long long outStreamStride, outInnerStride; int format; unsigned *overs; };
+	void exact(const ClipIo &io, const int *inSamples, const int *outSamples, unsigned char *tooShort);
 	void synchronize();
 
 	hipStream_t stream() const { return st; }
@@ -123,6 +143,7 @@ public:
 	void moveStreamsFrom(Batch &src, const int *srcStreams, const int *dstStreams, int n);
 	// reset() (:49-60) of ONE stream: its neighbours are not touched
 	void resetStream(int stream);
+	void resetStreamsMasked(const unsigned char *active); // ... of every stream with active[s] != 0
 
 	// test hooks: copy state rows to the host (which: 0 input, 1 prevInput, 2 output -> 2*C*M floats; 3 energy -> C*M)
 	void debugGetState(int stream, int which, float *dst);
@@ -255,6 +276,13 @@ private:
 	size_t zerosCapacity = 0;
 	float *dScratchOut = nullptr;
 	size_t scratchOutCapacity = 0;
+	// exact(): the planar images the stages run on ([S][C][pitch], grown on demand) and the segment tables of the two clip kernels, twice as the
+	// per-call tables are (a call returns before its last kernel has run)
+	float *dClipIn = nullptr, *dClipOut = nullptr;
+	size_t clipInCapacity = 0, clipOutCapacity = 0;
+	struct ClipSet { ClipSeg *host = nullptr, *dev = nullptr; hipEvent_t done = nullptr; bool used = false; } clipSets[2]; // [2][S][2]: input segments, output segments
+	int clipCur = 0;
+	void growClipImage(float *&image, size_t &capacity, size_t need);
 	StreamParams *dParams = nullptr;
 	float *dMapTable = nullptr;
 	std::vector<float> hostMapTable;

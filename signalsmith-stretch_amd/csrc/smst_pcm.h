@@ -182,18 +182,16 @@ template <typename T> __device__ inline bool pcmTileRun(const T *run, long long 
 	return true;
 }
 
-// interleaved frames -> planar fp32.  grid (tiles, S), 256 threads; in[s*inStreamStride + i*inFrameStride + c] -> out[s*outStreamStride + c*outChannelStride + i], i < counts[s]
-template <typename T> __global__ __launch_bounds__(256) void kPcmIn(const T *__restrict__ in, long long inStreamStride, long long inFrameStride,
-		float *__restrict__ out, long long outStreamStride, long long outChannelStride, const int *__restrict__ counts, int C) {
-	extern __shared__ __attribute__((aligned(16))) unsigned char smemRaw[];
-	float *tile = reinterpret_cast<float *>(smemRaw);
+// One tile of a run of frames -> the rows of a planar fp32 image.  run: the run's first frame; dst: the sample of channel 0 that frame goes to.
+// Every lane of the workgroup calls it (kPcmIn; kClipIn of smst_clip.h for a run that begins at a per-stream offset).
+template <typename T> __device__ inline void pcmTileIn(const T *__restrict__ run, long long inFrameStride, long long frames, float *__restrict__ out, long long outChannelStride,
+		int t, int C, float *tile) {
 	constexpr int G = PcmFormat<T>::G, W = PcmFormat<T>::W;
-	const int s = blockIdx.y, tid = threadIdx.x;
-	const T *run = in + (size_t)s*inStreamStride;
+	const int tid = threadIdx.x;
 	const bool dense = inFrameStride == C;
 	long long e0;
 	int count, head;
-	if (!pcmTileRun<T>(run, (long long)counts[s]*C, dense, blockIdx.x, C, e0, count, head)) return;
+	if (!pcmTileRun<T>(run, frames*C, dense, t, C, e0, count, head)) return;
 	if (dense) {
 		const T *p = run + e0;
 		if (tid < head) tile[pcmSlot(tid)] = PcmFormat<T>::decode(p[tid]);
@@ -218,7 +216,7 @@ template <typename T> __global__ __launch_bounds__(256) void kPcmIn(const T *__r
 	__syncthreads();
 	const long long f0 = e0/C; // (a tile may begin and end inside a frame: each element is moved by the tile that holds it)
 	const int nFrames = int((e0 + count - 1)/C - f0) + 1;
-	float *dst = out + (size_t)s*outStreamStride + f0;
+	float *dst = out + f0;
 	for (int c = 0; c < C; ++c) {
 		const int first = int(f0*C + c - e0);
 		for (int fl = tid; fl < nFrames; fl += 256) {
@@ -228,30 +226,28 @@ template <typename T> __global__ __launch_bounds__(256) void kPcmIn(const T *__r
 	}
 }
 
-// planar fp32 -> interleaved frames: the reverse.  overs (may be null): [S][2] counters, see "Overs" above
-template <typename T> __global__ __launch_bounds__(256) void kPcmOut(const float *__restrict__ in, long long inStreamStride, long long inChannelStride,
-		T *__restrict__ out, long long outStreamStride, long long outFrameStride, const int *__restrict__ counts, int C, unsigned *__restrict__ overs) {
-	extern __shared__ __attribute__((aligned(16))) unsigned char smemRaw[];
-	float *tile = reinterpret_cast<float *>(smemRaw);
+// The reverse: one tile of the rows of a planar fp32 image -> a run of frames.  in: the sample of channel 0 that goes to the run's first frame,
+// or null for a run of zeros (the code of 0.0).  false: the tile lies behind the run; else `over` has this lane's overs word (see "Overs").
+template <typename T> __device__ inline bool pcmTileOut(const float *__restrict__ in, long long inChannelStride, T *__restrict__ run, long long outFrameStride, long long frames,
+		int t, int C, float *tile, unsigned &over) {
 	constexpr int G = PcmFormat<T>::G, W = PcmFormat<T>::W;
-	const int s = blockIdx.y, tid = threadIdx.x;
-	T *run = out + (size_t)s*outStreamStride;
+	const int tid = threadIdx.x;
 	const bool dense = outFrameStride == C;
 	long long e0;
 	int count, head;
-	if (!pcmTileRun<T>(run, (long long)counts[s]*C, dense, blockIdx.x, C, e0, count, head)) return;
+	if (!pcmTileRun<T>(run, frames*C, dense, t, C, e0, count, head)) return false;
 	const long long f0 = e0/C;
 	const int nFrames = int((e0 + count - 1)/C - f0) + 1;
-	const float *src = in + (size_t)s*inStreamStride + f0;
+	const float *src = in ? in + f0 : nullptr;
 	for (int c = 0; c < C; ++c) {
 		const int first = int(f0*C + c - e0);
 		for (int fl = tid; fl < nFrames; fl += 256) {
 			const int i = first + fl*C;
-			if (i >= 0 && i < count) tile[pcmSlot(i)] = src[(size_t)c*inChannelStride + fl];
+			if (i >= 0 && i < count) tile[pcmSlot(i)] = src ? src[(size_t)c*inChannelStride + fl] : 0.0f;
 		}
 	}
 	__syncthreads();
-	unsigned over = 0;
+	over = 0;
 	if (dense) {
 		T *p = run + e0;
 		if (tid < head) { const float v = tile[pcmSlot(tid)]; p[tid] = PcmFormat<T>::encode(v); over += PcmFormat<T>::over(v); }
@@ -275,8 +271,13 @@ template <typename T> __global__ __launch_bounds__(256) void kPcmOut(const float
 			over += PcmFormat<T>::over(v);
 		}
 	}
-	// (every lane of the workgroup arrives here; the vote keeps the clean wavefront, which is nearly every one, to one instruction)
+	return true;
+}
+// the lanes' overs words into stream s's counters (every lane of the workgroup arrives here; the vote keeps the clean wavefront, which is
+// nearly every one, to one instruction)
+__device__ inline void pcmAddOvers(unsigned *__restrict__ overs, int s, unsigned over) {
 	if (overs && __any(over != 0)) {
+		const int tid = threadIdx.x;
 		int sum = int(over);
 		for (int m = 32; m; m >>= 1) sum += __shfl(sum, (tid & 63) ^ m);
 		if ((tid & 63) == 0) {
@@ -285,6 +286,24 @@ template <typename T> __global__ __launch_bounds__(256) void kPcmOut(const float
 			if (sum >> 16) atomicAdd(words + 1, sum >> 16);
 		}
 	}
+}
+
+// interleaved frames -> planar fp32.  grid (tiles, S), 256 threads; in[s*inStreamStride + i*inFrameStride + c] -> out[s*outStreamStride + c*outChannelStride + i], i < counts[s]
+template <typename T> __global__ __launch_bounds__(256) void kPcmIn(const T *__restrict__ in, long long inStreamStride, long long inFrameStride,
+		float *__restrict__ out, long long outStreamStride, long long outChannelStride, const int *__restrict__ counts, int C) {
+	extern __shared__ __attribute__((aligned(16))) unsigned char smemRaw[];
+	const int s = blockIdx.y;
+	pcmTileIn<T>(in + (size_t)s*inStreamStride, inFrameStride, counts[s], out + (size_t)s*outStreamStride, outChannelStride, blockIdx.x, C, reinterpret_cast<float *>(smemRaw));
+}
+
+// planar fp32 -> interleaved frames: the reverse.  overs (may be null): [S][2] counters, see "Overs" above
+template <typename T> __global__ __launch_bounds__(256) void kPcmOut(const float *__restrict__ in, long long inStreamStride, long long inChannelStride,
+		T *__restrict__ out, long long outStreamStride, long long outFrameStride, const int *__restrict__ counts, int C, unsigned *__restrict__ overs) {
+	extern __shared__ __attribute__((aligned(16))) unsigned char smemRaw[];
+	const int s = blockIdx.y;
+	unsigned over;
+	if (!pcmTileOut<T>(in + (size_t)s*inStreamStride, inChannelStride, out + (size_t)s*outStreamStride, outFrameStride, counts[s], blockIdx.x, C, reinterpret_cast<float *>(smemRaw), over)) return;
+	pcmAddOvers(overs, s, over);
 }
 
 // format: SMST_PCM_* of include/smst.h (the C ABI has checked it).  maxFrames: the largest of the streams' counts.

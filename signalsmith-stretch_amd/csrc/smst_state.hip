@@ -1,7 +1,8 @@
 // State that outlives a tile or a call (carry, history, reset, seek, flush, pre-roll, pass-through), the launch counters, the self-test of smst_complex.h,
-// and (smst_pcm.h) the interleaved-PCM converters of the batch API's boundary.
+// and (smst_pcm.h, smst_clip.h) the interleaved-PCM converters and the clip copies of the batch API's boundary.
 #include "smst_recurrence.h"
 #include "smst_pcm.h"
+#include "smst_clip.h"
 
 namespace smst {
 
@@ -84,7 +85,8 @@ __global__ __launch_bounds__(256) void kPassThrough(DevBatch d, IoArgs io, const
 
 // reset() / flush() / first silent block (signalsmith-stretch.h:49-60, :456-463, :244-251) for the selected streams in ONE
 // launch.  Per-stream bit mask (smst_types.h): RESET_STFT = stft.reset(0.1) (overlap-add sums and input history cleared, window products
-// re-seeded, both halves of the double buffers), RESET_INPUT / RESET_PREV / RESET_OUTPUT = clear Band.input / .prevInput / .output.
+// re-seeded, both halves of the double buffers), RESET_INPUT / RESET_PREV / RESET_OUTPUT = clear Band.input / .prevInput / .output,
+// RESET_FREQ = clear the pitch-estimate averages (a masked reset(): the unmasked one clears all of them with one memset).
 __global__ __launch_bounds__(256) void kResetStreams(DevBatch d, const int *__restrict__ flags, int allBits, const float *__restrict__ seedWp, const int *__restrict__ keep) {
 	const int sg = blockIdx.y;
 	const int bits = flags ? flags[sg] : allBits;
@@ -116,6 +118,7 @@ __global__ __launch_bounds__(256) void kResetStreams(DevBatch d, const int *__re
 		}
 		if (i == 0) d.histBase[0][sg] = d.histBase[1][sg] = 0;
 	}
+	if (i == 0 && (bits & RESET_FREQ)) d.stFreq[2*(size_t)sg] = d.stFreq[2*(size_t)sg + 1] = 0.0f;
 	if (i < M && (bits & (RESET_INPUT | RESET_PREV | RESET_OUTPUT))) {
 		const float2 zero = make_float2(0.f, 0.f);
 		for (int c = 0; c < C; ++c) {
@@ -248,7 +251,7 @@ void launchComplexSelfTest(const float *in, float *out, int n, hipStream_t st) {
 static std::atomic<long long> gLaunchCounts[LK_COUNT];
 static const char *const kLaunchNames[LK_COUNT] = {
 	"vocoder_aligned", "vocoder_staged", "vocoder_gather", "vocoder_n", "vocoder_one", "vocoder_across", "vocoder_continuous", "chain_unfused",
-	"analyse_teams", "analyse_fast", "analyse_generic", "synth_teams", "synth_fast", "synth_generic", "synth_emit", "emit_carried", "feed_one_pass", "pcm_in", "pcm_out"};
+	"analyse_teams", "analyse_fast", "analyse_generic", "synth_teams", "synth_fast", "synth_generic", "synth_emit", "emit_carried", "feed_one_pass", "pcm_in", "pcm_out", "clip_in", "clip_out"};
 void countLaunch(LaunchKind k) { gLaunchCounts[k].fetch_add(1, std::memory_order_relaxed); }
 long long launchCount(const char *name) {
 	for (int i = 0; i < LK_COUNT; ++i) if (name && std::strcmp(name, kLaunchNames[i]) == 0) return gLaunchCounts[i].load(std::memory_order_relaxed);

@@ -34,7 +34,7 @@ struct TileSummary {
 
 // kResetStreams' per-stream mask: stft.reset(0.1) (overlap-add sums and input history cleared, window products re-seeded, both halves of
 // the double buffers); clear Band.input / .prevInput / .output
-enum : int { RESET_STFT = 1, RESET_INPUT = 2, RESET_PREV = 4, RESET_OUTPUT = 8 };
+enum : int { RESET_STFT = 1, RESET_INPUT = 2, RESET_PREV = 4, RESET_OUTPUT = 8, RESET_FREQ = 16 }; // (RESET_FREQ: the pitch-estimate averages, stFreq)
 
 // Hop flags (reference: signalsmith-stretch.h:299-313)
 enum : unsigned {

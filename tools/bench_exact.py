@@ -1,0 +1,105 @@
+#!/usr/bin/env python3
+"""Whole clips in device memory: one smst_batch_exact call against the three-call sequence it replaces (smst_batch_output_seek,
+smst_batch_process, smst_batch_flush with the stage lengths computed by the caller), and the call with a different rate per stream, for
+which there is no three-call equivalent.  Prints one JSON line per mode: the median over --steps calls after --warmup, each call timed on
+the host from its first entry point to the return of smst_batch_synchronize.
+
+  python tools/bench_exact.py --mode three        # the yardstick (also runs on a build without smst_batch_exact: SMST_LIBRARY)
+  python tools/bench_exact.py --mode exact --check   # ... and compares the first call's output with the three-call sequence, bit for bit
+  python tools/bench_exact.py --mode ragged       # per-stream rates drawn from [0.5, 2.0)
+"""
+import argparse
+import ctypes as C
+import importlib
+import json
+import os
+import statistics
+import sys
+import time
+
+os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")  # (INTEGRATION.md "Hardware queues"; before the HIP runtime starts)
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+smst = importlib.import_module("signalsmith-stretch_amd")
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--mode", choices=["three", "exact", "ragged"], required=True)
+    ap.add_argument("--streams", type=int, default=256)
+    ap.add_argument("--channels", type=int, default=2)
+    ap.add_argument("--seconds", type=float, default=10.0)
+    ap.add_argument("--sample-rate", type=float, default=48000.0)
+    ap.add_argument("--stretch", type=float, default=1.5, help="uniform modes: output length / input length")
+    ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--check", action="store_true", help="mode exact: the first call's output equals the three-call sequence of a twin batch")
+    a = ap.parse_args()
+    assert torch.cuda.is_available(), "needs a GPU"
+    lib = smst.load_library()
+    S, Cn, n = a.streams, a.channels, int(a.seconds*a.sample_rate)
+    if a.mode == "ragged":
+        rates = np.random.default_rng(1).uniform(0.5, 2.0, S)
+        nout = np.maximum((n/rates).astype(np.int64), 1).astype(np.int32)
+    else:
+        nout = np.full(S, int(n*a.stretch), np.int32)
+    nin = np.full(S, n, np.int32)
+    g = torch.Generator(device="cuda").manual_seed(7)
+    t = torch.arange(n, device="cuda", dtype=torch.float32)/a.sample_rate
+    f = 110.0*2**(torch.arange(S*Cn, device="cuda", dtype=torch.float32).reshape(S, Cn, 1) % 37/12)
+    x = (0.4*torch.sin(2*np.pi*f*t) + 0.05*torch.rand((S, Cn, n), generator=g, device="cuda") - 0.025).contiguous()
+    most = int(nout.max())
+    out = torch.zeros((S, Cn, most), dtype=torch.float32, device="cuda")
+    torch.cuda.synchronize()
+    ip = lambda v: v.ctypes.data_as(C.POINTER(C.c_int))
+
+    def batch():
+        return smst.StretchBatch(S, Cn, preset="default", sample_rate=a.sample_rate, seed=0)
+
+    def three(b, y):
+        """exact() by hand, one rate for all streams: the stage lengths of signalsmith-stretch.h:468-491"""
+        rate = float(np.float32(n)/np.float32(nout[0]))
+        seek = b.outputSeekLength(rate)
+        index = int(np.float32(nout[0]) - np.float32(seek)/np.float32(rate))
+        ints = lambda v: np.full(S, v, np.int32)
+        k, r, m, tail = ints(seek), ints(n - seek), ints(index), ints(int(nout[0]) - index)
+        rates32 = np.full(S, rate, np.float32)
+        smst._check(lib, lib.smst_batch_output_seek(b.h, C.c_void_p(x.data_ptr()), Cn*n, n, ip(k), smst.MEM_DEVICE))
+        smst._check(lib, lib.smst_batch_process(b.h, C.c_void_p(x.data_ptr() + 4*seek), Cn*n, n, ip(r), C.c_void_p(y.data_ptr()), Cn*most, most, ip(m), smst.MEM_DEVICE))
+        smst._check(lib, lib.smst_batch_flush(b.h, C.c_void_p(y.data_ptr() + 4*index), Cn*most, most, ip(tail), rates32.ctypes.data_as(C.POINTER(C.c_float)), smst.MEM_DEVICE))
+
+    def exact(b, y):
+        status = np.zeros(S, np.int32)
+        smst._check(lib, lib.smst_batch_exact(b.h, C.c_void_p(x.data_ptr()), Cn*n, n, ip(nin), C.c_void_p(y.data_ptr()), Cn*most, most, ip(nout), ip(status), smst.MEM_DEVICE))
+        assert not status.any(), status
+
+    call = three if a.mode == "three" else exact
+    b = batch()
+    if a.check and a.mode == "exact":
+        twin, y2 = batch(), torch.zeros_like(out)
+        exact(b, out)
+        three(twin, y2)
+        b.synchronize()
+        twin.synchronize()
+        assert torch.equal(out, y2) and bool(out.abs().max() > 0), "exact differs from the three-call sequence"
+        twin.close()
+        del y2
+    times = []
+    for k in range(a.warmup + a.steps):
+        b.synchronize()
+        t0 = time.perf_counter()
+        call(b, out)
+        b.synchronize()
+        times.append((time.perf_counter() - t0)*1e3)
+    timed = times[a.warmup:]
+    print(json.dumps(dict(mode=a.mode, library=os.path.relpath(smst.LIBRARY_PATH), streams=S, channels=Cn, in_samples=n, out_samples=[int(nout.min()), int(nout.max())],
+                          median_ms=round(statistics.median(timed), 3), min_ms=round(min(timed), 3), max_ms=round(max(timed), 3), steps=a.steps, warmup=a.warmup,
+                          checked=bool(a.check and a.mode == "exact"), device=torch.cuda.get_device_name(0), hw_queues=os.environ["GPU_MAX_HW_QUEUES"])))
+    b.close()
+
+
+if __name__ == "__main__":
+    main()
