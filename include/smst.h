@@ -276,11 +276,13 @@ int smst_batch_exact_pcm(smst_batch *b, const void *in, long long inStreamStride
  * format, frameStride >= channels; the pointers need the element's alignment only (2 bytes for int16, ONE byte for packed int24, whose
  * strides count elements of 3 bytes), no stride need be a multiple of 16 bytes.  `format` holds for the input and the output of a call; counts, rates and lengths are as in the planar calls (frames per
  * stream; flush_pcm keeps the negative-count rule).
- *   SMST_PCM_S16  in: float(v)/32768 (exact).  out: q = roundf(v*32768), ties away from zero, clamped to [-32768, 32767], no dither --
- *                 the rule the CLI writes WAV files with.  NaN gives 0 (the CLI has no such case: a NaN there ends as -32768).
+ *   SMST_PCM_S16  in: float(v)/32768 (exact).  out: q = roundf(v*32768), ties away from zero, clamped to [-32768, 32767]; no dither by
+ *                 default -- the rule the CLI writes WAV files with --, TPDF dither as an option ("Dither" below).  NaN gives 0 (the CLI
+ *                 has no such case: a NaN there ends as -32768).
  *   SMST_PCM_F32  copied bit for bit.
  *   SMST_PCM_S24  3 bytes per sample, little-endian two's complement, packed without padding (a WAV file's 24-bit data chunk).
  *                 in: float(v)/8388608 (exact).  out: roundf(v*8388608), ties away from zero, clamped to [-8388608, 8388607]; NaN gives 0.
+ *                 Dither as for SMST_PCM_S16.
  *   SMST_PCM_S32  in: the int32 converted to float32 (round to nearest even: the engine is fp32, codes above 2^24 lose their low bits)
  *                 times 2^-31.  out: roundf(v*2^31) clamped to [-2^31, 2^31 - 1] -- a product at or above 2^31 gives 2147483647 --; NaN gives 0.
  *   SMST_PCM_F16  IEEE binary16.  in: widened exactly.  out: round to nearest even, subnormal halves kept, magnitudes of 65520 and above
@@ -310,6 +312,71 @@ int smst_batch_flush_pcm(smst_batch *b, void *out, long long outStreamStride, lo
                          const float *playbackRates, int format, int memory);
 int smst_batch_output_seek_pcm(smst_batch *b, const void *in, long long inStreamStride, long long inFrameStride, const int *inputLengths,
                                int format, int memory);
+/* ---- Dither (EXTENSION; opt-in: a batch that never turns it on launches the kernels, writes the bytes and counts the launches it did before) ----
+ * TPDF dither of the int16 and int24 output of the _pcm calls, from a counter-based, stateless noise source: the dither of an element is
+ * a function of the stream's seed, the channel and the frame index alone, so it can be restated bit for bit on the host
+ * (tests/dither_cases.py) and does not depend on how a stream's output is cut into calls.
+ *
+ * The dither signal.  All arithmetic is on unsigned 32-bit words, wrapping.
+ *
+ *   mix(x):  x ^= x>>16;  x *= 0x7feb352d;  x ^= x>>15;  x *= 0x846ca68b;  x ^= x>>16
+ *   D        = the stream's 64-bit dither seed, as an unsigned 64-bit value
+ *   h        = mix( mix(lo32(D) ^ 0x736d7374) ^ hi32(D) )              per stream (the host can precompute it)
+ *   key(c)   = mix( h + 0x9E3779B9*(c + 1) )                           per channel c
+ *   word(n,j)= mix( mix(key(c) ^ lo32(n)) + 0x85EBCA6B*(2*hi32(n) + j + 1) )
+ *              n = the 64-bit frame index, j = 0 or 1
+ *   u(n,j)   = float(word(n,j) >> 8) * 2^-24 - 0.5                     in [-0.5, 0.5), exact in fp32
+ *
+ * - SMST_DITHER_TPDF (1): d = u(n,0) + u(n,1).  It is white and triangular on (-1, 1) LSB.
+ * - SMST_DITHER_TPDF_HP (2): d = u(n,0) - u(n-1,0), with n-1 taken modulo 2^64.  It is the same triangle with lag-1 correlation -1/2, so
+ *   the noise power moves towards Nyquist.  It needs no carried state because u(n-1,0) is recomputed from the counter.
+ * - SMST_DITHER_NONE (0): today's rule.
+ *
+ * Both sums are exact in fp32.
+ *
+ * Quantisation rule
+ * - t = v*scale + d.  This is one fp32 rounding.  The product is a power-of-two scaling and exact, so the result is the same whether or
+ *   not the compiler fuses it into a multiply-add.
+ * - q = roundf(t), ties away from zero.
+ * - Clamp as today.
+ * - NaN gives 0 as today.
+ *
+ * Overs
+ * - An element counts as clamped iff roundf(t) lies outside the format's range.  That is, the dithered value was clamped.
+ * - nans counts as today.
+ *
+ * Formats
+ * - Dither applies to SMST_PCM_S16 and SMST_PCM_S24 only.
+ * - For S32, F16 and F32 the output is bit-identical to today whatever the mode.  fp32 has nothing below an int32 LSB, and float formats
+ *   are not quantised to a fixed step.
+ * - S24 near full scale has an fp32 ulp of 0.5 LSB.  The mirror reproduces this because it adds in float32.
+ *
+ * Known answers
+ * - mix(1) = 0x688990c0.  mix(0xffffffff) = 0x6768824a.
+ * - key: D = 0, c = 0: 0xd56e12bd;  D = 0, c = 1: 0x56302af1;  D = -7, c = 1: 0xdbfc9700;  D = 2^40+5, c = 15: 0xdbe9456e.
+ * - word(n,0) for D=0, c=0, n=0,1,2: 0x8ea83340 0xd3f7b664 0xa82e2bc5.  word(n,1) for the same: 0x73eac46c 0xdfcaa731 0x2ea8393e.
+ * - For D=0, c=0, n=0,1,2: d*2^24 = 168695, 11780701, -2697628 (TPDF) and -7219755, 4542339, -2869643 (HP).
+ * - For D=-7, c=1, n = 0, 2^32-1, 2^32, 2^64-1: d*2^24 = 7581456, 5086807, 515381, 7516847 (TPDF) and 1786397, -1939039, -6678722, -988138 (HP).
+ * - int16 codes of the constant v = 0.3/32768 for D=0, c=0, n=0..15:
+ *     TPDF: 0 1 0 0 1 0 0 0 0 0 -1 0 0 0 0 1        HP: 0 1 0 0 0 0 1 0 0 0 0 1 0 0 0 1
+ *
+ * Frame index n.  Every stream has a frame counter.  In smst_batch_process_pcm and smst_batch_flush_pcm, frame i of stream s in a call has
+ * n = counter_s + i, and after the call counter_s += max(outSamples[s], 0) -- for every stream whose mode is not NONE, whatever the call's
+ * format.  So a stream's dithered output does not depend on how it is cut into calls, and a flush continues the sequence.  Only
+ * smst_batch_set_pcm_dither resets the counter; smst_batch_reset does not.
+ * In smst_batch_exact_pcm n is the output frame's index within the clip, from 0: the counter is neither read nor advanced, so the same clip
+ * gives the same file.  The zeros of a too-short stream stay the code of 0.0, undithered, and count no overs; streams left out stay untouched.
+ * The per-stream entries (mode, h, lo32 and hi32 of the first n) ride in the per-call table the _pcm calls upload anyway (the exact call:
+ * the same table, uploaded beside its segments): no allocation and no host synchronisation is added to any call, the ordering contract is
+ * unchanged, and a steady-state dithered call leaves smst_batch_debug_allocation_events where it is.
+ * SMST_ERR_INVALID with a message: an unknown mode, a stream index out of range, a null batch. */
+#define SMST_DITHER_NONE 0
+#define SMST_DITHER_TPDF 1
+#define SMST_DITHER_TPDF_HP 2
+/* stream = -1: every stream, stream s getting seed + s (the batch's own seed rule); sets the stream's frame counter to 0 */
+int smst_batch_set_pcm_dither(smst_batch *b, int stream, int mode, long long seed);
+/* any pointer may be null; frames = the stream's frame counter */
+int smst_batch_pcm_dither(const smst_batch *b, int stream, int *mode, long long *seed, long long *frames);
 /* test hook: the two conversion kernels alone, ragged counts, arbitrary strides; dir 0 = PCM -> planar, 1 = planar -> PCM.  Host pointers: the
  * PCM side is (stream stride, frame stride), the planar side (stream stride, channel stride), in elements.  Both buffers are staged whole (what
  * the kernel leaves alone in `dst` comes back as it was) into device buffers offset from a 16-byte boundary as the caller's pointers are.
@@ -329,6 +396,14 @@ int smst_debug_pcm_convert_counted(int device, int format, int streams, int chan
                                    const void *src, long long srcStreamStride, long long srcInnerStride,
                                    void *dst, long long dstStreamStride, long long dstInnerStride,
                                    long long *clamped, long long *nans);
+/* test hook: the planar -> PCM kernel alone with per-stream dither ([streams] each: modes, seeds, the frame index of each stream's first
+ * frame), staged as smst_debug_pcm_convert_counted stages its buffers; clamped / nans: either may be null.  A launch in which a stream has a
+ * mode is the dithered kernel (int16 / int24; the other formats have none). */
+int smst_debug_pcm_convert_dithered(int device, int format, int streams, int channels, const int *counts,
+                                    const void *src, long long srcStreamStride, long long srcInnerStride,
+                                    void *dst, long long dstStreamStride, long long dstInnerStride,
+                                    const int *modes, const long long *seeds, const long long *firstFrames,
+                                    long long *clamped, long long *nans);
 /* test hook: the two copy kernels of the exact calls alone (csrc/smst_clip.h).  dir 0 = caller's buffer -> planar image, 1 = planar image ->
  * caller's buffer; format: an SMST_PCM_* code (the caller's side is frames: stream stride, frame stride) or 0 (it is planar fp32 itself: stream
  * stride, channel stride); the image side is always (stream stride, channel stride); strides in elements.  segments: [streams][2][4] host ints
@@ -393,7 +468,8 @@ int smst_debug_complex_selftest(int device, const float *in, float *out, int n);
 /* launches, since the library was loaded, of one kernel variant: "vocoder_aligned", "vocoder_staged", "vocoder_gather",
  * "vocoder_n", "vocoder_one", "vocoder_across", "vocoder_continuous", "chain_unfused", "analyse_teams", "analyse_fast", "analyse_generic",
  * "synth_teams", "synth_fast", "synth_generic", "synth_emit", "emit_carried", "feed_one_pass", "pcm_in", "pcm_out" (the conversion kernels of the _pcm calls, whatever
- * the format), "clip_in", "clip_out" (the copy kernels of the exact calls, planar or any format) (-1: unknown name).  The "this form is bit-identical to that form" tests
+ * the format), "clip_in", "clip_out" (the copy kernels of the exact calls, planar or any format), "pcm_out_dithered", "clip_out_dithered" (a launch in
+ * which at least one stream dithers into int16 or int24 counts here INSTEAD of "pcm_out" / "clip_out") (-1: unknown name).  The "this form is bit-identical to that form" tests
  * assert through it that both forms really ran. */
 long long smst_debug_launch_count(const char *name);
 

@@ -26,6 +26,7 @@ CSRC_DIR = os.path.join(_HERE, "csrc")
 
 MEM_HOST, MEM_DEVICE = 0, 1
 PCM_S16, PCM_F32, PCM_S24, PCM_S32, PCM_F16 = 1, 2, 4, 5, 6  # frame formats of the *_pcm calls (include/smst.h)
+DITHER_NONE, DITHER_TPDF, DITHER_TPDF_HP = 0, 1, 2           # dither of the int16 / int24 output (StretchBatch.setPcmDither)
 _FRAME_DTYPES = {"int16": PCM_S16, "float32": PCM_F32, "int32": PCM_S32, "float16": PCM_F16}  # (packed int24 travels as uint8 [..., 3])
 _FRAME_DTYPE_OF = {PCM_S16: "int16", PCM_F32: "float32", PCM_S32: "int32", PCM_F16: "float16", PCM_S24: "uint8"}
 _fp = C.POINTER(C.c_float)
@@ -119,6 +120,10 @@ _SIGNATURES = {
     "smst_debug_pcm_convert": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _ip, C.c_void_p, _ll, _ll, C.c_void_p, _ll, _ll]),
     "smst_debug_pcm_convert_counted": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _ip, C.c_void_p, _ll, _ll, C.c_void_p, _ll, _ll, C.POINTER(_ll), C.POINTER(_ll)]),
     "smst_batch_take_pcm_overs": (C.c_int, [C.c_void_p, C.POINTER(_ll), C.POINTER(_ll)]),
+    "smst_batch_set_pcm_dither": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _ll]),
+    "smst_batch_pcm_dither": (C.c_int, [C.c_void_p, C.c_int, _ip, C.POINTER(_ll), C.POINTER(_ll)]),
+    "smst_debug_pcm_convert_dithered": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _ip, C.c_void_p, _ll, _ll, C.c_void_p, _ll, _ll, _ip, C.POINTER(_ll), C.POINTER(_ll),
+                                                  C.POINTER(_ll), C.POINTER(_ll)]),
     "smst_batch_synchronize": (C.c_int, [C.c_void_p]),
     "smst_batch_hip_stream": (C.c_void_p, [C.c_void_p]),
     "smst_batch_enable_profiling": (C.c_int, [C.c_void_p, C.c_int]),
@@ -462,7 +467,8 @@ class StretchBatch:
     def processFrames(self, x, out_samples, in_samples=None, out=None, ordered=True):
         """process() on interleaved frames: x is [S, n, C] int16 (full scale 32768), int32 (2^31), float16 or float32, or uint8
         [S, n, C, 3] for packed int24 (8388608), numpy (host memory) or a torch GPU tensor (_describe_frames has the layout rules); the
-        result has the same dtype and shape convention.  Integer output is round-to-nearest, ties away from zero, clamped, no dither;
+        result has the same dtype and shape convention.  Integer output is round-to-nearest, ties away from zero, clamped, no dither
+        unless setPcmDither() turned it on (int16 / int24);
         NaN -> 0.  int32 input above 2^24 is rounded to float32.  float16 output is round-to-nearest-even: subnormals kept, 65520 and
         above +-inf, NaN stays NaN (include/smst.h).  What was clamped: takePcmOvers().  ``ordered`` as in process()."""
         S = self.streams
@@ -574,6 +580,18 @@ class StretchBatch:
     def exactFrames(self, x, out_samples, in_samples=None, out=None, ordered=True):
         """exact() on interleaved frames ([S, n, C] of a frame dtype, or uint8 [S, n, C, 3]: processFrames has the rules) -> (out, ok)"""
         return self._exact(True, x, out_samples, in_samples, out, ordered)
+
+    def setPcmDither(self, mode, seed=0, stream=-1):
+        """TPDF dither of the int16 / int24 output of processFrames, flushFrames and exactFrames (include/smst.h, "Dither"): DITHER_NONE,
+        DITHER_TPDF (white) or DITHER_TPDF_HP (lag-1 correlation -1/2).  stream = -1: every stream, stream s with seed + s.  The frame
+        counter of the stream(s) restarts at 0; the other formats are not affected."""
+        _check(self.lib, self.lib.smst_batch_set_pcm_dither(self.h, int(stream), int(mode), int(seed)))
+
+    def pcmDither(self, stream):
+        """-> (mode, seed, frames): the stream's dither mode, its seed and its frame counter"""
+        mode, seed, frames = C.c_int(0), _ll(0), _ll(0)
+        _check(self.lib, self.lib.smst_batch_pcm_dither(self.h, int(stream), C.byref(mode), C.byref(seed), C.byref(frames)))
+        return mode.value, seed.value, frames.value
 
     def takePcmOvers(self):
         """-> (clamped, nans), int64 [S]: per stream, the output elements of processFrames / flushFrames since the last take whose code

@@ -30,8 +30,13 @@ struct smst_batch {
 	// per-call tables do: a device-memory call returns before its kernels have run
 	unsigned char *dPcmIn = nullptr, *dPcmOut = nullptr, *hPcmIn = nullptr, *hPcmOut = nullptr;
 	size_t dPcmInCap = 0, dPcmOutCap = 0, hPcmInCap = 0, hPcmOutCap = 0;
-	struct PcmCounts { int *host = nullptr, *dev = nullptr; hipEvent_t done = nullptr; bool used = false; } pcmCounts[2]; // [2*S]: input frames, output frames
+	// ... and, behind the counts, the dither entries of the call's output conversion ([S] smst::PcmDither, uploaded with the output counts by a
+	// call that dithers)
+	struct PcmCounts { int *host = nullptr, *dev = nullptr; hipEvent_t done = nullptr; bool used = false, dithered = false; } pcmCounts[2]; // [2*S]: input frames, output frames; [S] dither entries
 	int pcmCur = 0;
+	// dither of the int16 / int24 output (smst_batch_set_pcm_dither): per stream the mode, the seed, its hash and the frame counter
+	struct PcmDitherState { int mode = SMST_DITHER_NONE; long long seed = 0; unsigned h = 0; unsigned long long frames = 0; };
+	std::vector<PcmDitherState> pcmDither;
 	// overs of the output conversions ([S][2]: clamped, NaN): the kernels add to them, smst_batch_take_pcm_overs reads and clears them
 	unsigned *dPcmOvers = nullptr;
 	std::vector<unsigned> hPcmOvers;
@@ -147,6 +152,7 @@ int smst_batch_create_ex(smst_batch **out, int streams, int channels, int block,
 	std::unique_ptr<smst_batch> b(new smst_batch());
 	b->engine.reset(new Batch(streams, channels, block, interval, split != 0, device, seed, (flags & SMST_FLAG_HALF_STATE) != 0));
 	b->hPcmOvers.assign((size_t)2*streams, 0u);
+	b->pcmDither.assign((size_t)streams, smst_batch::PcmDitherState());
 	if (hipMalloc(reinterpret_cast<void **>(&b->dPcmOvers), pcmOversBytes(streams)) != hipSuccess) throw smst::Error("hipMalloc (PCM overs) failed", true);
 	if (hipMemset(b->dPcmOvers, 0, pcmOversBytes(streams)) != hipSuccess) throw smst::Error("hipMemset (PCM overs) failed", true);
 	*out = b.release();
@@ -389,14 +395,38 @@ static smst_batch::PcmCounts &beginPcmCall(smst_batch *b) {
 	smst_batch::PcmCounts &c = b->pcmCounts[b->pcmCur];
 	if (!c.host) {
 		++b->stagingAllocs;
-		const size_t bytes = (size_t)2*e.streams()*sizeof(int);
+		const size_t bytes = (size_t)2*e.streams()*sizeof(int) + (size_t)e.streams()*sizeof(smst::PcmDither);
 		if (hipHostMalloc(reinterpret_cast<void **>(&c.host), bytes, hipHostMallocDefault) != hipSuccess) throw smst::Error("hipHostMalloc (PCM counts) failed", true);
 		if (hipMalloc(reinterpret_cast<void **>(&c.dev), bytes) != hipSuccess) throw smst::Error("hipMalloc (PCM counts) failed", true);
 		if (hipEventCreateWithFlags(&c.done, hipEventDisableTiming) != hipSuccess) throw smst::Error("hipEventCreate failed", true);
 	}
 	if (c.used && hipEventSynchronize(c.done) != hipSuccess) throw smst::Error("hipEventSynchronize failed", true);
 	c.used = false;
+	c.dithered = false;
 	return c;
+}
+// the dither entries of a call's table: on the host, and where the kernels read them
+static smst::PcmDither *pcmDitherHost(smst_batch *b, smst_batch::PcmCounts &c) { return reinterpret_cast<smst::PcmDither *>(c.host + 2*b->engine->streams()); }
+static const smst::PcmDither *pcmDitherDev(smst_batch *b, smst_batch::PcmCounts &c) { return c.dithered ? reinterpret_cast<const smst::PcmDither *>(c.dev + 2*b->engine->streams()) : nullptr; }
+// whether a call of this format dithers: a stream has a mode, and the format has a step to dither
+static bool pcmDithers(const smst_batch *b, int format) {
+	if (format != SMST_PCM_S16 && format != SMST_PCM_S24) return false;
+	for (const smst_batch::PcmDitherState &d : b->pcmDither) if (d.mode != SMST_DITHER_NONE) return true;
+	return false;
+}
+// ... if so the entries are filled: every stream's mode and hash, and its frame counter as the index of the call's first frame
+static bool pcmFillDither(smst_batch *b, smst_batch::PcmCounts &c, int format) {
+	if (!pcmDithers(b, format)) return false;
+	smst::PcmDither *t = pcmDitherHost(b, c);
+	for (size_t s = 0; s < b->pcmDither.size(); ++s) {
+		const smst_batch::PcmDitherState &d = b->pcmDither[s];
+		t[s] = smst::PcmDither{unsigned(d.mode), d.h, unsigned(d.frames), unsigned(d.frames >> 32)};
+	}
+	return true;
+}
+// after a call that emitted n[s] frames: the counters of the streams that have a mode move on, whatever the call's format
+static void pcmAdvanceDither(smst_batch *b, const int *n) {
+	for (size_t s = 0; s < b->pcmDither.size(); ++s) if (b->pcmDither[s].mode != SMST_DITHER_NONE && n[s] > 0) b->pcmDither[s].frames += (unsigned long long)n[s];
 }
 static void endPcmCall(smst_batch *b, smst_batch::PcmCounts &c) {
 	if (hipEventRecord(c.done, b->engine->stream()) != hipSuccess) throw smst::Error("hipEventRecord failed", true);
@@ -475,7 +505,9 @@ static int pcmPrepareOut(smst_batch *b, smst_batch::PcmCounts &c, const int *n, 
 		ensurePcmBytes(b->dPcmOut, b->dPcmOutCap, bytes, false, e.device(), b->stagingAllocs);
 	}
 	hipSetDevice(e.device());
-	if (hipMemcpyAsync(c.dev + S, c.host + S, S*sizeof(int), hipMemcpyHostToDevice, e.stream()) != hipSuccess) throw smst::Error("hipMemcpyAsync (H2D) failed", true);
+	c.dithered = pcmFillDither(b, c, format);
+	const size_t bytes = S*sizeof(int) + (c.dithered ? S*sizeof(smst::PcmDither) : 0); // (the entries lie behind the output counts: still one copy)
+	if (hipMemcpyAsync(c.dev + S, c.host + S, bytes, hipMemcpyHostToDevice, e.stream()) != hipSuccess) throw smst::Error("hipMemcpyAsync (H2D) failed", true);
 	return maxLen;
 }
 // The planar image b->dOut -> raw frames, behind the engine's last emitting kernel (everything of a call is joined into the engine's stream,
@@ -488,14 +520,40 @@ static void pcmStageOut(smst_batch *b, smst_batch::PcmCounts &c, void *out, long
 	for (int s = 0; s < S; ++s) most = std::max(most, n[s]);
 	hipSetDevice(e.device());
 	if (memory == SMST_MEM_DEVICE) {
-		smst::launchPcmOut(format, b->dOut, (long long)C*maxLen, maxLen, out, ss, fs, c.dev + S, S, C, most, b->dPcmOvers, e.stream());
+		smst::launchPcmOut(format, b->dOut, (long long)C*maxLen, maxLen, out, ss, fs, c.dev + S, S, C, most, b->dPcmOvers, e.stream(), pcmDitherDev(b, c));
+		pcmAdvanceDither(b, n);
 		return;
 	}
-	if (most < 1) return;
-	smst::launchPcmOut(format, b->dOut, (long long)C*maxLen, maxLen, b->dPcmOut, pcmRowElems(most, C), C, c.dev + S, S, C, most, b->dPcmOvers, e.stream());
-	pcmRawOut(b, out, ss, fs, n, most, format);
+	if (most >= 1) {
+		smst::launchPcmOut(format, b->dOut, (long long)C*maxLen, maxLen, b->dPcmOut, pcmRowElems(most, C), C, c.dev + S, S, C, most, b->dPcmOvers, e.stream(), pcmDitherDev(b, c));
+		pcmRawOut(b, out, ss, fs, n, most, format);
+	}
+	pcmAdvanceDither(b, n);
 }
 
+int smst_batch_set_pcm_dither(smst_batch *b, int stream, int mode, long long seed) {
+	BATCH_CALL({
+		const int S = b->engine->streams();
+		if (mode != SMST_DITHER_NONE && mode != SMST_DITHER_TPDF && mode != SMST_DITHER_TPDF_HP) throw smst::Error("unknown dither mode (SMST_DITHER_NONE, _TPDF or _TPDF_HP)");
+		if (stream < -1 || stream >= S) throw smst::Error("stream index out of range");
+		for (int s = stream < 0 ? 0 : stream; s < (stream < 0 ? S : stream + 1); ++s) {
+			smst_batch::PcmDitherState &d = b->pcmDither[s];
+			d.mode = mode;
+			d.seed = stream < 0 ? (long long)((unsigned long long)seed + (unsigned long long)s) : seed;
+			d.h = smst::pcmDitherHash(d.seed);
+			d.frames = 0;
+		}
+	})
+}
+int smst_batch_pcm_dither(const smst_batch *b, int stream, int *mode, long long *seed, long long *frames) {
+	if (!b || !b->engine) return fail("null batch");
+	if (stream < 0 || stream >= b->engine->streams()) return fail("stream index out of range");
+	const smst_batch::PcmDitherState &d = b->pcmDither[stream];
+	if (mode) *mode = d.mode;
+	if (seed) *seed = d.seed;
+	if (frames) *frames = (long long)d.frames;
+	return SMST_OK;
+}
 int smst_batch_process_pcm(smst_batch *b, const void *in, long long iss, long long ifs, const int *inSamples,
                            void *out, long long oss, long long ofs, const int *outSamples, int format, int memory) {
 	BATCH_CALL({
@@ -615,8 +673,17 @@ int smst_batch_exact_pcm(smst_batch *b, const void *in, long long iss, long long
 		Batch &e = *b->engine;
 		checkPcmFormat(format, memory);
 		checkExactArgs(e, in, inSamples, out, outSamples, ifs, ofs, true, memory);
+		// a dithered call: the streams' modes and hashes ride in the _pcm calls' table (the frame index is the place in the clip: the counters
+		// are neither read nor moved)
+		smst_batch::PcmCounts *table = pcmDithers(b, format) ? &beginPcmCall(b) : nullptr;
+		const smst::PcmDither *dither = nullptr;
+		if (table) {
+			table->dithered = pcmFillDither(b, *table, format);
+			if (hipMemcpyAsync(table->dev + 2*e.streams(), table->host + 2*e.streams(), e.streams()*sizeof(smst::PcmDither), hipMemcpyHostToDevice, e.stream()) != hipSuccess) throw smst::Error("hipMemcpyAsync (H2D) failed", true);
+			dither = pcmDitherDev(b, *table);
+		}
 		if (memory == SMST_MEM_DEVICE) {
-			runExact(e, Batch::ClipIo{in, iss, ifs, out, oss, ofs, format, b->dPcmOvers}, inSamples, outSamples, status);
+			runExact(e, Batch::ClipIo{in, iss, ifs, out, oss, ofs, format, b->dPcmOvers, dither}, inSamples, outSamples, status);
 		} else {
 			const int S = e.streams(), C = e.channels();
 			std::vector<int> nIn, nOut;
@@ -625,16 +692,18 @@ int smst_batch_exact_pcm(smst_batch *b, const void *in, long long iss, long long
 			ensurePcmBytes(b->hPcmOut, b->hPcmOutCap, outBytes, true, e.device(), b->stagingAllocs);
 			ensurePcmBytes(b->dPcmOut, b->dPcmOutCap, outBytes, false, e.device(), b->stagingAllocs);
 			pcmRawIn(b, in, iss, ifs, nIn.data(), mostIn, format);
-			runExact(e, Batch::ClipIo{b->dPcmIn, pcmRowElems(mostIn, C), C, b->dPcmOut, pcmRowElems(mostOut, C), C, format, b->dPcmOvers}, inSamples, outSamples, status);
+			runExact(e, Batch::ClipIo{b->dPcmIn, pcmRowElems(mostIn, C), C, b->dPcmOut, pcmRowElems(mostOut, C), C, format, b->dPcmOvers, dither}, inSamples, outSamples, status);
 			pcmRawOut(b, out, oss, ofs, nOut.data(), mostOut, format);
 		}
+		if (table) endPcmCall(b, *table);
 	}
 	return SMST_OK;
 	SMST_CATCH
 }
 } // extern "C"
 static int pcmConvert(int device, int dir, int format, int streams, int channels, const int *counts,
-                      const void *src, long long srcSS, long long srcInner, void *dst, long long dstSS, long long dstInner, long long *clamped, long long *nans) {
+                      const void *src, long long srcSS, long long srcInner, void *dst, long long dstSS, long long dstInner, long long *clamped, long long *nans,
+                      const int *modes = nullptr, const long long *seeds = nullptr, const long long *firstFrames = nullptr) {
 	SMST_TRY
 	checkPcmFormat(format, SMST_MEM_HOST);
 	if (dir != 0 && dir != 1) throw smst::Error("pcm convert: dir is 0 (PCM -> planar) or 1 (planar -> PCM)");
@@ -655,7 +724,22 @@ static int pcmConvert(int device, int dir, int format, int streams, int channels
 	unsigned *dOvers = nullptr;
 	std::vector<unsigned> overs((size_t)2*streams, 0u);
 	const bool counted = dir == 1 && (clamped || nans);
+	// the streams' dither entries (dir 1); a launch is a dithered one when a stream has a mode
+	std::vector<smst::PcmDither> dither;
+	smst::PcmDither *dDither = nullptr;
+	bool dithered = false;
+	if (modes) {
+		if (!seeds || !firstFrames) throw smst::Error("pcm convert: null seeds or first frames");
+		for (int s = 0; s < streams; ++s) {
+			if (modes[s] != SMST_DITHER_NONE && modes[s] != SMST_DITHER_TPDF && modes[s] != SMST_DITHER_TPDF_HP) throw smst::Error("unknown dither mode (SMST_DITHER_NONE, _TPDF or _TPDF_HP)");
+			const unsigned long long n = (unsigned long long)firstFrames[s];
+			dither.push_back(smst::PcmDither{unsigned(modes[s]), smst::pcmDitherHash(seeds[s]), unsigned(n), unsigned(n >> 32)});
+			dithered = dithered || modes[s] != SMST_DITHER_NONE;
+		}
+	}
 	hipError_t err = hipMalloc(reinterpret_cast<void **>(&dSrc), srcBytes + 32);
+	if (err == hipSuccess && dithered) err = hipMalloc(reinterpret_cast<void **>(&dDither), streams*sizeof(smst::PcmDither));
+	if (err == hipSuccess && dithered) err = hipMemcpy(dDither, dither.data(), streams*sizeof(smst::PcmDither), hipMemcpyHostToDevice);
 	if (err == hipSuccess) err = hipMalloc(reinterpret_cast<void **>(&dDst), dstBytes + 32);
 	if (err == hipSuccess) err = hipMalloc(reinterpret_cast<void **>(&dCounts), streams*sizeof(int));
 	// the device buffers sit as far behind a 16-byte boundary as the caller's do
@@ -667,7 +751,7 @@ static int pcmConvert(int device, int dir, int format, int streams, int channels
 	if (err == hipSuccess && counted) err = hipMemcpy(dOvers, overs.data(), pcmOversBytes(streams), hipMemcpyHostToDevice);
 	if (err == hipSuccess) {
 		if (dir == 0) smst::launchPcmIn(format, s0, srcSS, srcInner, reinterpret_cast<float *>(d0), dstSS, dstInner, dCounts, streams, channels, most, nullptr);
-		else smst::launchPcmOut(format, reinterpret_cast<const float *>(s0), srcSS, srcInner, d0, dstSS, dstInner, dCounts, streams, channels, most, dOvers, nullptr);
+		else smst::launchPcmOut(format, reinterpret_cast<const float *>(s0), srcSS, srcInner, d0, dstSS, dstInner, dCounts, streams, channels, most, dOvers, nullptr, dDither);
 		err = hipGetLastError();
 	}
 	if (err == hipSuccess) err = hipStreamSynchronize(nullptr);
@@ -677,6 +761,7 @@ static int pcmConvert(int device, int dir, int format, int streams, int channels
 	if (dDst) hipFree(dDst);
 	if (dCounts) hipFree(dCounts);
 	if (dOvers) hipFree(dOvers);
+	if (dDither) hipFree(dDither);
 	if (err != hipSuccess) throw smst::Error(std::string("pcm convert: ") + hipGetErrorString(err), true);
 	for (int s = 0; s < streams; ++s) {
 		if (clamped) clamped[s] = overs[2*s];
@@ -695,6 +780,12 @@ int smst_debug_pcm_convert_counted(int device, int format, int streams, int chan
                                    long long *clamped, long long *nans) {
 	if (!clamped || !nans) return fail("pcm convert: null count arrays");
 	return pcmConvert(device, 1, format, streams, channels, counts, src, srcSS, srcInner, dst, dstSS, dstInner, clamped, nans);
+}
+int smst_debug_pcm_convert_dithered(int device, int format, int streams, int channels, const int *counts,
+                                    const void *src, long long srcSS, long long srcInner, void *dst, long long dstSS, long long dstInner,
+                                    const int *modes, const long long *seeds, const long long *firstFrames, long long *clamped, long long *nans) {
+	if (!modes || !seeds || !firstFrames) return fail("pcm convert: null dither arrays");
+	return pcmConvert(device, 1, format, streams, channels, counts, src, srcSS, srcInner, dst, dstSS, dstInner, clamped, nans, modes, seeds, firstFrames);
 }
 // the two clip kernels alone (smst_clip.h): see include/smst.h
 int smst_debug_clip_copy(int device, int dir, int format, int streams, int channels, const int *segments,

@@ -46,6 +46,20 @@ template <typename T> __global__ __launch_bounds__(256) void kClipOut(const floa
 	if (!pcmTileOut<T>(src, imageChannelStride, out + (size_t)s*outStreamStride + (size_t)g.dst*outFrameStride, outFrameStride, g.count, blockIdx.x, C, reinterpret_cast<float *>(smemRaw), over)) return;
 	pcmAddOvers(overs, s, over);
 }
+// ... dithered (int16 / int24): the frame index of a segment's first frame is its place in the clip, g.dst -- dither[s] gives the stream's
+// mode and hash only --, so a clip's codes do not depend on where its two segments meet; a run of zeros stays the code of 0.0
+template <typename T> __global__ __launch_bounds__(256) void kClipOutDithered(const float *__restrict__ image, long long imageStreamStride, long long imageChannelStride,
+		T *__restrict__ out, long long outStreamStride, long long outFrameStride, const ClipSeg *__restrict__ segs, int C, unsigned *__restrict__ overs, const PcmDither *__restrict__ dither) {
+	extern __shared__ __attribute__((aligned(16))) unsigned char smemRaw[];
+	const int s = blockIdx.y;
+	const ClipSeg g = segs[2*s + blockIdx.z];
+	if (g.count < 1) return;
+	const float *src = g.zeros ? nullptr : image + (size_t)s*imageStreamStride + g.src;
+	const PcmDither dp{dither[s].mode, dither[s].h, unsigned(g.dst), 0u};
+	unsigned over;
+	if (!pcmTileOut<T, true>(src, imageChannelStride, out + (size_t)s*outStreamStride + (size_t)g.dst*outFrameStride, outFrameStride, g.count, blockIdx.x, C, reinterpret_cast<float *>(smemRaw), over, dp)) return;
+	pcmAddOvers(overs, s, over);
+}
 
 // Tile t of one row's run of `total` floats, src (null: zeros) -> dst, through `lds`.  Every lane of the workgroup calls it.
 __device__ inline void clipRowTile(const float *__restrict__ src, float *__restrict__ dst, int total, int t, float *lds) {
@@ -124,10 +138,20 @@ void launchClipIn(int format, const void *in, long long inSS, long long inInner,
 	}
 	countLaunch(LK_CLIP_IN);
 }
+template <typename T> static void launchClipOutDitheredAs(dim3 grid, int C, hipStream_t st, const float *image, long long imageSS, long long imageCS, void *out, long long outSS, long long outFS,
+		const ClipSeg *segs, unsigned *overs, const PcmDither *dither) {
+	hipLaunchKernelGGL(kClipOutDithered<T>, grid, dim3(256), pcmDitherLdsBytes(C), st, image, imageSS, imageCS, static_cast<T *>(out), outSS, outFS, segs, C, overs, dither);
+}
 void launchClipOut(int format, const float *image, long long imageSS, long long imageCS, void *out, long long outSS, long long outInner, const ClipSeg *segs, int S, int C, int maxCount,
-                   unsigned *overs, hipStream_t st) {
+                   unsigned *overs, hipStream_t st, const PcmDither *dither) {
 	if (maxCount < 1) return;
 	const dim3 grid(divUp(maxCount, kPcmTileFrames), S, 2);
+	if (dither && (format == kPcmS16 || format == kPcmS24)) {
+		if (format == kPcmS16) launchClipOutDitheredAs<int16_t>(grid, C, st, image, imageSS, imageCS, out, outSS, outInner, segs, overs, dither);
+		else launchClipOutDitheredAs<PcmS24>(grid, C, st, image, imageSS, imageCS, out, outSS, outInner, segs, overs, dither);
+		countLaunch(LK_CLIP_OUT_DITHERED);
+		return;
+	}
 	switch (format) {
 	case 0: launchClipPlanar(image, imageSS, imageCS, static_cast<float *>(out), outSS, outInner, segs, S, C, maxCount, st); break;
 	case kPcmS16: launchClipOutAs<int16_t>(grid, C, st, image, imageSS, imageCS, out, outSS, outInner, segs, overs); break;

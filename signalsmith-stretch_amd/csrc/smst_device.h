@@ -161,7 +161,7 @@ __host__ __device__ inline bool analysisWindowInCall(int B, int M, int I, int in
 // form" tests assert through these that BOTH forms really ran.
 enum LaunchKind {
 	LK_VOC_ALIGNED, LK_VOC_STAGED, LK_VOC_GATHER, LK_VOC_N, LK_VOC_ONE, LK_VOC_ACROSS, LK_VOC_CONT, LK_CHAIN_UNFUSED,
-	LK_ANALYSE_TEAMS, LK_ANALYSE_FAST, LK_ANALYSE_GENERIC, LK_SYNTH_TEAMS, LK_SYNTH_FAST, LK_SYNTH_GENERIC, LK_SYNTH_EMIT, LK_EMIT_CARRIED, LK_FEED_ONE_PASS, LK_PCM_IN, LK_PCM_OUT, LK_CLIP_IN, LK_CLIP_OUT, LK_COUNT
+	LK_ANALYSE_TEAMS, LK_ANALYSE_FAST, LK_ANALYSE_GENERIC, LK_SYNTH_TEAMS, LK_SYNTH_FAST, LK_SYNTH_GENERIC, LK_SYNTH_EMIT, LK_EMIT_CARRIED, LK_FEED_ONE_PASS, LK_PCM_IN, LK_PCM_OUT, LK_CLIP_IN, LK_CLIP_OUT, LK_PCM_OUT_DITHERED, LK_CLIP_OUT_DITHERED, LK_COUNT
 };
 long long launchCount(const char *name); // -1: unknown name
 
@@ -211,8 +211,19 @@ constexpr int kPcmTileFrames = 512; // frames one workgroup moves
 constexpr int kPcmS16 = 1, kPcmF32 = 2, kPcmS24 = 4, kPcmS32 = 5, kPcmF16 = 6;
 void launchPcmIn(int format, const void *in, long long inStreamStride, long long inFrameStride, float *out, long long outStreamStride, long long outChannelStride,
                  const int *counts, int S, int C, int maxFrames, hipStream_t st);
+// Dither of the int16 / int24 output conversions (include/smst.h, "Dither", has the definition; all of it is wrapping 32-bit arithmetic).
+// One entry per stream, device: the mode (0: none -- today's rule), the stream's hash h of its seed (pcmDitherHash, computed by the host) and
+// the frame index n of the run's first frame (kPcmOut; kClipOut takes its segment's destination frame instead).  dither == null, or a
+// format other than int16 / int24: the undithered kernels, as before.
+struct PcmDither { unsigned mode, h, nLo, nHi; };
+constexpr unsigned kPcmDitherTpdf = 1u, kPcmDitherHp = 2u;
+inline __host__ __device__ unsigned pcmMix(unsigned x) { x ^= x >> 16; x *= 0x7feb352du; x ^= x >> 15; x *= 0x846ca68bu; x ^= x >> 16; return x; }
+inline unsigned pcmDitherHash(long long seed) {
+	const unsigned long long d = (unsigned long long)seed;
+	return pcmMix(pcmMix(unsigned(d) ^ 0x736d7374u) ^ unsigned(d >> 32));
+}
 void launchPcmOut(int format, const float *in, long long inStreamStride, long long inChannelStride, void *out, long long outStreamStride, long long outFrameStride,
-                  const int *counts, int S, int C, int maxFrames, unsigned *overs, hipStream_t st);
+                  const int *counts, int S, int C, int maxFrames, unsigned *overs, hipStream_t st, const PcmDither *dither = nullptr);
 // Whole clips of ragged lengths (smst_clip.h; Batch::exact): each stream moves two segments of frames between the caller's buffer and a planar
 // fp32 image -- `count` frames from frame `src` of its row(s) on the source side to frame `dst` on the destination side; zeros != 0: no
 // source, the destination gets 0.0 (its code, in a frame format).  segs: [S][2] device.  format: an SMST_PCM_* code, or 0 for a caller's
@@ -222,6 +233,6 @@ struct ClipSeg { int src, dst, count, zeros; };
 void launchClipIn(int format, const void *in, long long inStreamStride, long long inInnerStride, float *image, long long imageStreamStride, long long imageChannelStride,
                   const ClipSeg *segs, int S, int C, int maxCount, hipStream_t st);
 void launchClipOut(int format, const float *image, long long imageStreamStride, long long imageChannelStride, void *out, long long outStreamStride, long long outInnerStride,
-                   const ClipSeg *segs, int S, int C, int maxCount, unsigned *overs, hipStream_t st);
+                   const ClipSeg *segs, int S, int C, int maxCount, unsigned *overs, hipStream_t st, const PcmDither *dither = nullptr);
 
 } // namespace smst

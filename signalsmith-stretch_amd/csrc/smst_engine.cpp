@@ -1790,7 +1790,7 @@ void Batch::exact(const ClipIo &io, const int *inSamples, const int *outSamples,
 	}
 	// behind the call's last emitting kernel (everything of a call is joined into `st`), in front of whatever synchronize() / signalStream() wait for
 	launchClipOut(io.format, dClipOut, outImgSS, pitchOut, io.out, io.outStreamStride, io.outInnerStride, cs.dev + (size_t)2*S, S, C,
-	              std::max(std::max(direct ? 0 : maxProc, maxFlush), maxZeros), io.overs, st);
+	              std::max(std::max(direct ? 0 : maxProc, maxFlush), maxZeros), io.overs, st, io.dither);
 	SMST_HIP(hipEventRecord(cs.done, st));
 	cs.used = true;
 	SMST_HIP(hipGetLastError());

@@ -3,7 +3,7 @@
 // smst_state.hip only.
 //
 // Conversion.  int16 -> float: float(v)/32768 (exact).  float -> int16: q = roundf(v*32768) -- ties away from zero --, clamped to
-// [-32768, 32767], no dither: the rule tools/wav_io.h writes files with.  NaN gives 0; wav_io.h has no such case (its clamp turns a NaN
+// [-32768, 32767], no dither unless a stream asks for it ("Dither" below): the rule tools/wav_io.h writes files with.  NaN gives 0; wav_io.h has no such case (its clamp turns a NaN
 // into -32768): a NaN here is a fault of the signal path, and silence is the one code that is not a full-scale click.
 // int24 (3 bytes, little-endian, packed) and int32: the same rule at full scale 2^23 and 2^31; an int32 above 2^24 is rounded to float32
 // (nearest even) on the way in, and the way out clamps the FLOAT before it becomes an integer (2^31 and above give 2147483647).
@@ -55,6 +55,20 @@ template <> struct PcmFormat<int16_t> {
 	static __device__ inline unsigned over(float v) {
 		const float r = roundf(v*32768.0f);
 		return (v != v) ? kPcmOverNan : (r > 32767.0f || r < -32768.0f) ? kPcmOverClamped : 0u;
+	}
+	// the dithered forms take t = v*kScale + d (NaN iff v is: d is finite)
+	static constexpr float kScale = 32768.0f;
+	static __device__ inline unsigned codeScaled(float t) {
+		const float q = fminf(fmaxf(roundf(t), -32768.0f), 32767.0f);
+		return (t != t) ? 0u : (unsigned(int(q)) & 0xffffu);
+	}
+	static __device__ inline int16_t encodeScaled(float t) { return int16_t(uint16_t(codeScaled(t))); }
+	static __device__ inline unsigned overScaled(float t) {
+		const float r = roundf(t);
+		return (t != t) ? kPcmOverNan : (r > 32767.0f || r < -32768.0f) ? kPcmOverClamped : 0u;
+	}
+	static __device__ inline void packScaled(const float *t, PcmWord4 *w) {
+		for (int k = 0; k < 4; ++k) w[0][k] = codeScaled(t[2*k]) | (codeScaled(t[2*k + 1]) << 16);
 	}
 	static __device__ inline void unpack(const PcmWord4 *w, float *x) {
 		for (int k = 0; k < 4; ++k) {
@@ -142,6 +156,22 @@ template <> struct PcmFormat<PcmS24> {
 		const float r = roundf(v*8388608.0f);
 		return (v != v) ? kPcmOverNan : (r > 8388607.0f || r < -8388608.0f) ? kPcmOverClamped : 0u;
 	}
+	// the dithered forms take t = v*kScale + d (NaN iff v is: d is finite)
+	static constexpr float kScale = 8388608.0f;
+	static __device__ inline unsigned codeScaled(float t) {
+		const float q = fminf(fmaxf(roundf(t), -8388608.0f), 8388607.0f);
+		return (t != t) ? 0u : (unsigned(int(q)) & 0xffffffu);
+	}
+	static __device__ inline PcmS24 encodeScaled(float t) {
+		const unsigned q = codeScaled(t);
+		PcmS24 r;
+		r.b[0] = (unsigned char)(q & 0xffu); r.b[1] = (unsigned char)((q >> 8) & 0xffu); r.b[2] = (unsigned char)(q >> 16);
+		return r;
+	}
+	static __device__ inline unsigned overScaled(float t) {
+		const float r = roundf(t);
+		return (t != t) ? kPcmOverNan : (r > 8388607.0f || r < -8388608.0f) ? kPcmOverClamped : 0u;
+	}
 	// four samples are three dwords: a = d0[0:23], b = d0[24:31] d1[0:15], c = d1[16:31] d2[0:7], d = d2[8:31]
 	static __device__ inline void unpack(const PcmWord4 *w, float *x) {
 		unsigned d[12];
@@ -164,10 +194,42 @@ template <> struct PcmFormat<PcmS24> {
 		}
 		for (int k = 0; k < 12; ++k) w[k >> 2][k & 3] = d[k];
 	}
+	static __device__ inline void packScaled(const float *t, PcmWord4 *w) {
+		unsigned d[12];
+		for (int q = 0; q < 4; ++q) {
+			const unsigned a = codeScaled(t[4*q]), b = codeScaled(t[4*q + 1]), c = codeScaled(t[4*q + 2]), e = codeScaled(t[4*q + 3]);
+			d[3*q] = a | (b << 24);
+			d[3*q + 1] = (b >> 8) | (c << 16);
+			d[3*q + 2] = (c >> 16) | (e << 8);
+		}
+		for (int k = 0; k < 12; ++k) w[k >> 2][k & 3] = d[k];
+	}
 };
 
 __device__ inline int pcmSlot(int e) { return e + (e >> 5); }
-inline size_t pcmLdsBytes(int C) { const int most = kPcmTileFrames*C + 16; return size_t(most + most/32 + 1)*sizeof(float); } // (tile 0 is up to G - 1 = 15 elements longer)
+inline __host__ __device__ int pcmLdsWords(int C) { const int most = kPcmTileFrames*C + 16; return most + most/32 + 1; } // (tile 0 is up to G - 1 = 15 elements longer)
+inline size_t pcmLdsBytes(int C) { return size_t(pcmLdsWords(C))*sizeof(float); }
+inline size_t pcmDitherLdsBytes(int C) { return pcmLdsBytes(C) + 16*sizeof(unsigned); } // behind the image: key(c) of the 16 channels at the most
+
+// Dither (include/smst.h, "Dither": the definition; PcmDither of smst_device.h: a stream's entry).  Element i of a tile is channel c of the
+// run's frame f -- from the tile's first element e0, wherever in a frame that lies --, and frame f of the run has the index n = first + f:
+// the dither of an element is a function of (h, c, n) alone, whichever of the three paths below stores it and whichever tile, call or
+// launch it falls into.  key(c) = pcmMix(h + 0x9E3779B9*(c + 1)) is computed once per workgroup, into LDS behind the tile image;
+// per element there remain mix(key ^ lo32(n)) -- shared by the two words of the white form -- and one mix per word.
+__device__ inline float pcmDitherUnit(unsigned word) { return float(word >> 8)*(1.0f/16777216.0f) - 0.5f; } // [-0.5, 0.5), exact
+__device__ inline float pcmDitherValue(unsigned mode, unsigned key, unsigned long long n) {
+	const unsigned hi = unsigned(n >> 32), a = pcmMix(key ^ unsigned(n)), step = 0x85EBCA6Bu*(2u*hi + 1u);
+	const float u0 = pcmDitherUnit(pcmMix(a + step));
+	if (mode == kPcmDitherTpdf) return u0 + pcmDitherUnit(pcmMix(a + step + 0x85EBCA6Bu));
+	const unsigned long long m = n - 1; // (modulo 2^64)
+	return u0 - pcmDitherUnit(pcmMix(pcmMix(key ^ unsigned(m)) + 0x85EBCA6Bu*(2u*unsigned(m >> 32) + 1u)));
+}
+// Where element i of a tile lies: frame `frame` behind the tile's first frame, channel c.  next(): the element behind it.
+struct PcmDitherPlace {
+	unsigned frame, c;
+	__device__ inline PcmDitherPlace(int lag, int i, int C) : frame(unsigned(lag + i)/unsigned(C)), c(unsigned(lag + i) - frame*unsigned(C)) {}
+	__device__ inline void next(int C) { if (++c == unsigned(C)) { c = 0; ++frame; } }
+};
 
 // The elements [e0, e0 + count) of a stream's run of `total` elements that tile `t` moves, and how many of them (tile 0 only) lie in
 // front of the first group boundary.  false: the tile lies behind the run.
@@ -228,8 +290,10 @@ template <typename T> __device__ inline void pcmTileIn(const T *__restrict__ run
 
 // The reverse: one tile of the rows of a planar fp32 image -> a run of frames.  in: the sample of channel 0 that goes to the run's first frame,
 // or null for a run of zeros (the code of 0.0).  false: the tile lies behind the run; else `over` has this lane's overs word (see "Overs").
-template <typename T> __device__ inline bool pcmTileOut(const float *__restrict__ in, long long inChannelStride, T *__restrict__ run, long long outFrameStride, long long frames,
-		int t, int C, float *tile, unsigned &over) {
+// Dith (int16 / int24): the run's elements are quantised as roundf(v*scale + d), d the dither of the stream's entry dp for the frame index
+// first + f (a run of zeros and a stream of mode 0 get d = 0: today's codes); an element counts as clamped when the DITHERED value was.
+template <typename T, bool Dith = false> __device__ inline bool pcmTileOut(const float *__restrict__ in, long long inChannelStride, T *__restrict__ run, long long outFrameStride, long long frames,
+		int t, int C, float *tile, unsigned &over, PcmDither dp = PcmDither{0u, 0u, 0u, 0u}) {
 	constexpr int G = PcmFormat<T>::G, W = PcmFormat<T>::W;
 	const int tid = threadIdx.x;
 	const bool dense = outFrameStride == C;
@@ -245,6 +309,45 @@ template <typename T> __device__ inline bool pcmTileOut(const float *__restrict_
 			const int i = first + fl*C;
 			if (i >= 0 && i < count) tile[pcmSlot(i)] = src ? src[(size_t)c*inChannelStride + fl] : 0.0f;
 		}
+	}
+	if constexpr (Dith) {
+		const unsigned mode = src ? dp.mode : 0u;
+		unsigned *keys = reinterpret_cast<unsigned *>(tile) + pcmLdsWords(C);
+		if (mode && tid < C) keys[tid] = pcmMix(dp.h + 0x9E3779B9u*unsigned(tid + 1));
+		__syncthreads();
+		over = 0;
+		const int lag = int(e0 - f0*C); // elements of the tile's first frame that lie in front of the tile
+		const unsigned long long n0 = (((unsigned long long)dp.nHi << 32) | dp.nLo) + (unsigned long long)f0;
+		constexpr float scale = PcmFormat<T>::kScale;
+		auto scaled = [&](int i, const PcmDitherPlace &at) { // element i of the tile, times the scale, plus its dither
+			const float v = tile[pcmSlot(i)];
+			return mode ? v*scale + pcmDitherValue(mode, keys[at.c], n0 + at.frame) : v*scale;
+		};
+		if (dense) {
+			T *p = run + e0;
+			if (tid < head) { const float q = scaled(tid, PcmDitherPlace(lag, tid, C)); p[tid] = PcmFormat<T>::encodeScaled(q); over += PcmFormat<T>::overScaled(q); }
+			const int nGroups = (count - head)/G;
+			for (int g = tid; g < nGroups; g += 256) {
+				const int e = head + g*G;
+				PcmDitherPlace at(lag, e, C);
+				float x[G];
+				for (int k = 0; k < G; ++k) { x[k] = scaled(e + k, at); over += PcmFormat<T>::overScaled(x[k]); at.next(C); }
+				PcmWord4 w[W];
+				PcmFormat<T>::packScaled(x, w);
+				PcmWord4 *dst = reinterpret_cast<PcmWord4 *>(p + e);
+				for (int k = 0; k < W; ++k) dst[k] = w[k];
+			}
+			const int done = head + nGroups*G;
+			if (tid < count - done) { const float q = scaled(done + tid, PcmDitherPlace(lag, done + tid, C)); p[done + tid] = PcmFormat<T>::encodeScaled(q); over += PcmFormat<T>::overScaled(q); }
+		} else {
+			for (int i = tid; i < count; i += 256) {
+				const PcmDitherPlace at(lag, i, C);
+				const float q = scaled(i, at);
+				run[(f0 + at.frame)*outFrameStride + at.c] = PcmFormat<T>::encodeScaled(q);
+				over += PcmFormat<T>::overScaled(q);
+			}
+		}
+		return true;
 	}
 	__syncthreads();
 	over = 0;
@@ -305,6 +408,15 @@ template <typename T> __global__ __launch_bounds__(256) void kPcmOut(const float
 	if (!pcmTileOut<T>(in + (size_t)s*inStreamStride, inChannelStride, out + (size_t)s*outStreamStride, outFrameStride, counts[s], blockIdx.x, C, reinterpret_cast<float *>(smemRaw), over)) return;
 	pcmAddOvers(overs, s, over);
 }
+// ... dithered (int16 / int24): dither[s] is stream s's entry, the index of the run's first frame in it
+template <typename T> __global__ __launch_bounds__(256) void kPcmOutDithered(const float *__restrict__ in, long long inStreamStride, long long inChannelStride,
+		T *__restrict__ out, long long outStreamStride, long long outFrameStride, const int *__restrict__ counts, int C, unsigned *__restrict__ overs, const PcmDither *__restrict__ dither) {
+	extern __shared__ __attribute__((aligned(16))) unsigned char smemRaw[];
+	const int s = blockIdx.y;
+	unsigned over;
+	if (!pcmTileOut<T, true>(in + (size_t)s*inStreamStride, inChannelStride, out + (size_t)s*outStreamStride, outFrameStride, counts[s], blockIdx.x, C, reinterpret_cast<float *>(smemRaw), over, dither[s])) return;
+	pcmAddOvers(overs, s, over);
+}
 
 // format: SMST_PCM_* of include/smst.h (the C ABI has checked it).  maxFrames: the largest of the streams' counts.
 template <typename T> static void launchPcmInAs(dim3 grid, int C, hipStream_t st, const void *in, long long inStreamStride, long long inFrameStride, float *out, long long outStreamStride,
@@ -329,10 +441,20 @@ void launchPcmIn(int format, const void *in, long long inStreamStride, long long
 	}
 	countLaunch(LK_PCM_IN);
 }
+template <typename T> static void launchPcmOutDitheredAs(dim3 grid, int C, hipStream_t st, const float *in, long long inStreamStride, long long inChannelStride, void *out, long long outStreamStride,
+		long long outFrameStride, const int *counts, unsigned *overs, const PcmDither *dither) {
+	hipLaunchKernelGGL(kPcmOutDithered<T>, grid, dim3(256), pcmDitherLdsBytes(C), st, in, inStreamStride, inChannelStride, static_cast<T *>(out), outStreamStride, outFrameStride, counts, C, overs, dither);
+}
 void launchPcmOut(int format, const float *in, long long inStreamStride, long long inChannelStride, void *out, long long outStreamStride, long long outFrameStride,
-                  const int *counts, int S, int C, int maxFrames, unsigned *overs, hipStream_t st) {
+                  const int *counts, int S, int C, int maxFrames, unsigned *overs, hipStream_t st, const PcmDither *dither) {
 	if (maxFrames < 1) return;
 	const dim3 grid(divUp(maxFrames, kPcmTileFrames), S);
+	if (dither && (format == kPcmS16 || format == kPcmS24)) {
+		if (format == kPcmS16) launchPcmOutDitheredAs<int16_t>(grid, C, st, in, inStreamStride, inChannelStride, out, outStreamStride, outFrameStride, counts, overs, dither);
+		else launchPcmOutDitheredAs<PcmS24>(grid, C, st, in, inStreamStride, inChannelStride, out, outStreamStride, outFrameStride, counts, overs, dither);
+		countLaunch(LK_PCM_OUT_DITHERED);
+		return;
+	}
 	switch (format) {
 	case kPcmS16: launchPcmOutAs<int16_t>(grid, C, st, in, inStreamStride, inChannelStride, out, outStreamStride, outFrameStride, counts, overs); break;
 	case kPcmF32: launchPcmOutAs<float>(grid, C, st, in, inStreamStride, inChannelStride, out, outStreamStride, outFrameStride, counts, overs); break;

@@ -9,6 +9,10 @@ that drift of the host or the device hits all of them alike:
   c  smst_batch_process_pcm, SMST_MEM_HOST, int16 frames
   d  smst_batch_process_pcm, SMST_MEM_DEVICE, int16 frames  (torch tensors, batch synchronised per step)
   e  smst_batch_process, SMST_MEM_DEVICE, planar float      (what d is compared with: d - e = the two conversion passes)
+  f  d with TPDF dither (setPcmDither), g  d with high-passed TPDF dither       (f - d, g - d = what the dither adds to a step)
+  h  smst_batch_process_pcm, SMST_MEM_DEVICE, packed int24 frames, i  h with TPDF dither, j  h with high-passed TPDF dither
+The dithered rows are not in the default set: --variants d,e,f,g,h,i,j.  The time of the output conversion KERNEL alone (kPcmOut /
+kPcmOutDithered per format) is read from a kernel trace of such a run.
 A step's time is the host clock around one call that ends synchronised.  Prints one JSON line."""
 import argparse
 import importlib
@@ -55,12 +59,29 @@ def main():
     if "c" in variants:
         b, out = pkg.StretchBatch(S, Cn, preset="default", sample_rate=sr), np.zeros((S, m, Cn), np.int16)
         runs["c"] = lambda b=b, out=out: b.processFrames(s16, m, out=out)
-    if "d" in variants or "e" in variants:
+    if any(k in variants for k in "defghij"):
         import torch
     if "d" in variants:
         b, x, out = pkg.StretchBatch(S, Cn, preset="default", sample_rate=sr), torch.from_numpy(s16).cuda(), torch.zeros((S, m, Cn), dtype=torch.int16, device="cuda")
         torch.cuda.synchronize()
         runs["d"] = lambda b=b, x=x, out=out: (b.processFrames(x, m, out=out, ordered=False), b.synchronize())
+    for k, mode in (("f", pkg.DITHER_TPDF), ("g", pkg.DITHER_TPDF_HP)):
+        if k in variants:
+            b, x, out = pkg.StretchBatch(S, Cn, preset="default", sample_rate=sr), torch.from_numpy(s16).cuda(), torch.zeros((S, m, Cn), dtype=torch.int16, device="cuda")
+            if mode != pkg.DITHER_NONE:
+                b.setPcmDither(mode, seed=1)
+            torch.cuda.synchronize()
+            runs[k] = lambda b=b, x=x, out=out: (b.processFrames(x, m, out=out, ordered=False), b.synchronize())
+    if any(k in variants for k in "hij"):
+        codes = np.clip(np.round(f32.astype(np.float64)*8388608.0), -8388608, 8388607).astype(np.int32)
+        s24 = np.stack([codes & 255, (codes >> 8) & 255, (codes >> 16) & 255], -1).astype(np.uint8)
+    for k, mode in (("h", pkg.DITHER_NONE), ("i", pkg.DITHER_TPDF), ("j", pkg.DITHER_TPDF_HP)):
+        if k in variants:
+            b, x, out = pkg.StretchBatch(S, Cn, preset="default", sample_rate=sr), torch.from_numpy(s24).cuda(), torch.zeros((S, m, Cn, 3), dtype=torch.uint8, device="cuda")
+            if mode != pkg.DITHER_NONE:
+                b.setPcmDither(mode, seed=1)
+            torch.cuda.synchronize()
+            runs[k] = lambda b=b, x=x, out=out: (b.processFrames(x, m, out=out, ordered=False), b.synchronize())
     if "e" in variants:
         b, x, out = pkg.StretchBatch(S, Cn, preset="default", sample_rate=sr), torch.from_numpy(planar).cuda(), torch.zeros((S, Cn, m), dtype=torch.float32, device="cuda")
         torch.cuda.synchronize()
@@ -81,6 +102,13 @@ def main():
         extra = result["step_ms"]["d"]["median"] - result["step_ms"]["e"]["median"]
         moved = S*Cn*(n + m)*(2 + 4)  # each pass reads one format and writes the other
         result["conversion_passes"] = dict(extra_ms=extra, bytes=moved, gb_per_s=(moved/(extra*1e-3)/1e9 if extra > 0 else None))
+    dither = {}
+    for k, base in (("f", "d"), ("g", "d"), ("i", "h"), ("j", "h")):
+        if k in times and base in times:
+            extra = result["step_ms"][k]["median"] - result["step_ms"][base]["median"]
+            dither[k] = dict(against=base, extra_ms=extra, share_of_step=extra/result["step_ms"][k]["median"])
+    if dither:
+        result["dither"] = dither
     print(json.dumps(result))
 
 

@@ -4,10 +4,16 @@
 // implementation).
 //
 //   stretch_cli [--semitones=S] [--formant=S] [--formant-comp] [--formant-base=Hz] [--tonality=Hz] [--time=F]
-//               [--split-computation] [--device=N] [--out-format=s16|s24|f32] in.wav out.wav [in2.wav out2.wav ...]
+//               [--split-computation] [--device=N] [--out-format=s16|s24|f32] [--dither=none|tpdf|tpdf-hp] [--dither-seed=N]
+//               in.wav out.wav [in2.wav out2.wav ...]
 //
 // --out-format (also "--out-format s24"): the samples of the files written -- 16-bit (the default, as the reference's CLI writes), 24-bit by the
 // library's rounding rule for SMST_PCM_S24, or float32.
+// --dither: TPDF dither of the 16-bit / 24-bit samples written (include/smst.h, "Dither"): white (tpdf) or with its power moved towards
+// Nyquist (tpdf-hp); none, the default, is the tool as it was.  --dither-seed=N (default 0): file k is stream k, hence seed N + k.  With
+// dither the main process and the flush run through smst_batch_process_pcm / smst_batch_flush_pcm, which quantise on the GPU -- the flush
+// goes on with the frame counter --, and the frames are written as they come back.  Those calls take their input in the output's format:
+// an input that format cannot hold exactly (24-bit or float input with --out-format=s16) is refused rather than rounded.
 // Files given together must share sample rate and channel count (they form one batch); lengths may differ.
 #include <algorithm>
 #include <cmath>
@@ -53,6 +59,17 @@ int main(int argc, char **argv) {
 	const std::string outFormat = flagText(argc, argv, "out-format", "s16", consumed);
 	if (outFormat != "s16" && outFormat != "s24" && outFormat != "f32") {
 		std::fprintf(stderr, "--out-format is s16, s24 or f32\n");
+		return 2;
+	}
+	const std::string ditherName = flagText(argc, argv, "dither", "none", consumed);
+	const int dither = ditherName == "none" ? SMST_DITHER_NONE : ditherName == "tpdf" ? SMST_DITHER_TPDF : ditherName == "tpdf-hp" ? SMST_DITHER_TPDF_HP : -1;
+	const long long ditherSeed = std::strtoll(flagText(argc, argv, "dither-seed", "0", consumed).c_str(), nullptr, 10);
+	if (dither < 0) {
+		std::fprintf(stderr, "--dither is none, tpdf or tpdf-hp\n");
+		return 2;
+	}
+	if (dither != SMST_DITHER_NONE && outFormat == "f32") {
+		std::fprintf(stderr, "--dither applies to --out-format s16 and s24: float32 samples are not quantised\n");
 		return 2;
 	}
 	std::vector<std::string> files;
@@ -105,6 +122,39 @@ int main(int argc, char **argv) {
 	const long long iss = (long long)C*maxIn, ics = maxIn, oss = (long long)C*maxOut, ocs = maxOut;
 
 	CHECK(smst_batch_output_seek(batch, in.data(), iss, ics, seekLens.data(), SMST_MEM_HOST));                                   // :58-59
+	if (dither != SMST_DITHER_NONE) {
+		// the process stage and the flush as frames of the output's format, dithered by the library: stream s has seed ditherSeed + s
+		const int format = outFormat == "s24" ? SMST_PCM_S24 : SMST_PCM_S16, bits = outFormat == "s24" ? 24 : 16;
+		const size_t esz = size_t(bits/8);
+		const float scale = bits == 24 ? 8388608.0f : 32768.0f;
+		CHECK(smst_batch_set_pcm_dither(batch, -1, dither, ditherSeed));
+		int maxProc = 1;
+		for (int s = 0; s < S; ++s) maxProc = std::max(maxProc, procIn[s]);
+		const int tailLen = std::max(interval, 1);
+		std::vector<unsigned char> inFrames((size_t)S*maxProc*C*esz, 0), outFrames((size_t)S*maxOut*C*esz, 0), tailFrames((size_t)S*tailLen*C*esz, 0);
+		for (int s = 0; s < S; ++s) for (int i = 0; i < procIn[s]; ++i) for (int c = 0; c < C; ++c) {
+			const float v = in[((size_t)s*C + c)*maxIn + seekLength + i];
+			const float q = std::fmin(scale - 1.0f, std::fmax(-scale, std::round(v*scale)));
+			if (!(q/scale == v)) {
+				std::fprintf(stderr, "%s: sample %d is no %d-bit value: --dither needs an input that --out-format holds exactly\n", files[2*s].c_str(), seekLength + i, bits);
+				return 1;
+			}
+			const uint32_t code = uint32_t(int32_t(q));
+			unsigned char *p = inFrames.data() + (((size_t)s*maxProc + i)*C + c)*esz;
+			for (size_t k = 0; k < esz; ++k) p[k] = (unsigned char)(code >> (8*k));
+		}
+		CHECK(smst_batch_process_pcm(batch, inFrames.data(), (long long)maxProc*C, C, procIn.data(), outFrames.data(), (long long)maxOut*C, C, outIndex.data(), format, SMST_MEM_HOST));
+		CHECK(smst_batch_flush_pcm(batch, tailFrames.data(), (long long)tailLen*C, C, tail.data(), nullptr, format, SMST_MEM_HOST));
+		for (int s = 0; s < S; ++s) {
+			std::copy(tailFrames.begin() + (size_t)s*tailLen*C*esz, tailFrames.begin() + ((size_t)s*tailLen + tail[s])*C*esz, outFrames.begin() + ((size_t)s*maxOut + outIndex[s])*C*esz);
+			if (!writeWavFrames(files[2*s + 1], inputs[s].sampleRate, inputs[s].channels, bits, outFrames.data() + (size_t)s*maxOut*C*esz, size_t(outLen[s]), error)) {
+				std::fprintf(stderr, "%s\n", error.c_str());
+				return 1;
+			}
+		}
+		smst_batch_destroy(batch);
+		return 0;
+	}
 	CHECK(smst_batch_process(batch, in.data() + seekLength, iss, ics, procIn.data(), out.data(), oss, ocs, outIndex.data(), SMST_MEM_HOST)); // :77-78
 	// flush writes at each stream's own output offset: stage through a second buffer and splice
 	std::vector<float> tails((size_t)S*C*std::max(interval, 1), 0.0f);
