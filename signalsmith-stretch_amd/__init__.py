@@ -348,75 +348,6 @@ class StretchBatch:
         a = np.ascontiguousarray(a)
         return C.c_void_p(a.ctypes.data), a.shape[1]*a.shape[2], a.shape[2], a.shape[2], MEM_HOST, a
 
-    def process(self, x, out_samples, in_samples=None, out=None, ordered=True):
-        """process(inputs, inputSamples, outputs, outputSamples) for every stream (signalsmith-stretch.h:210).
-
-        Device tensors: with ``ordered`` (default) the call is ordered after torch's current stream (the producer of ``x``) and
-        torch's current stream is ordered after it (consumers of the result) -- by events, without a host synchronisation.
-        That makes consecutive calls wait for each other through torch's stream.  A caller whose inputs are already
-        complete and who synchronises the batch itself before touching the outputs (``bench.py``) passes
-        ``ordered=False`` and keeps the overlap of call n+1's host scheduling with call n's kernels."""
-        S, Cn = self.streams, self.channels
-        ptr, ss, cs, n, mem, keep = self._describe(x, "input")
-        nin, pin = _int_array(n if in_samples is None else in_samples, S)
-        nout, pout = _int_array(out_samples, S)
-        max_out = max(int(nout.max()), 1)
-        if out is None:
-            if mem == MEM_DEVICE:
-                import torch
-                out = torch.zeros((S, Cn, max_out), dtype=torch.float32, device=x.device)
-            else:
-                out = np.zeros((S, Cn, max_out), np.float32)
-        optr, oss, ocs, on, omem, okeep = self._describe(out, "output")
-        if omem != mem:
-            raise StretchError("input and output must live in the same memory space")
-        if on < max_out or int(nin.max()) > n:
-            raise StretchError("buffer shorter than the requested sample count")
-        if mem == MEM_DEVICE and ordered:
-            self._order_after_torch(x, out)
-        # (ordered=False: the caller's contract -- inputs complete, outputs untouched and both tensors ALIVE until it synchronises the batch -- so
-        # nothing is tracked here.  Until round 6 the tensors were still put on the in-flight list, whose every 17th entry synchronises the batch:
-        # one pipeline drain per 16 calls, 2.4 ms of the bench's 17th step -- bench.py's per-step periods showed it, roofline.step_ms.in_order)
-        _check(self.lib, self.lib.smst_batch_process(self.h, ptr, ss, cs, pin, optr, oss, ocs, pout, mem))
-        if mem == MEM_DEVICE and ordered:  # torch ops on `out` issued from here on are ordered after our kernels (no host sync either)
-            import torch
-            _check(self.lib, self.lib.smst_batch_signal_stream(self.h, C.c_void_p(torch.cuda.current_stream(out.device).cuda_stream)))
-        return out
-
-    def seek(self, x, rates, in_samples=None):
-        S = self.streams
-        ptr, ss, cs, n, mem, keep = self._describe(x, "input")
-        nin, pin = _int_array(n if in_samples is None else in_samples, S)
-        r = np.ascontiguousarray(np.broadcast_to(np.asarray(rates, dtype=np.float64), (S,)))
-        if mem == MEM_DEVICE:
-            self._order_after_torch(x)
-        _check(self.lib, self.lib.smst_batch_seek(self.h, ptr, ss, cs, pin, r.ctypes.data_as(_dp), mem))
-
-    def flush(self, out_samples, rates=0.0, like=None):
-        """flush() of every stream with a non-negative count; a negative count leaves that stream alone (include/smst.h)"""
-        S, Cn = self.streams, self.channels
-        nout, pout = _int_array(out_samples, S)
-        r = np.ascontiguousarray(np.broadcast_to(np.asarray(rates, dtype=np.float32), (S,)))
-        max_out = max(int(nout.max()), 1)
-        if like is not None and _is_torch(like):
-            import torch
-            out = torch.zeros((S, Cn, max_out), dtype=torch.float32, device=like.device)
-        else:
-            out = np.zeros((S, Cn, max_out), np.float32)
-        optr, oss, ocs, on, omem, okeep = self._describe(out, "output")
-        _check(self.lib, self.lib.smst_batch_flush(self.h, optr, oss, ocs, pout, r.ctypes.data_as(_fp), omem))
-        if omem == MEM_DEVICE:
-            self.synchronize()
-        return out
-
-    def outputSeek(self, x, input_lengths=None):
-        S = self.streams
-        ptr, ss, cs, n, mem, keep = self._describe(x, "input")
-        nin, pin = _int_array(n if input_lengths is None else input_lengths, S)
-        if mem == MEM_DEVICE:
-            self._order_after_torch(x)
-        _check(self.lib, self.lib.smst_batch_output_seek(self.h, ptr, ss, cs, pin, mem))
-
     # --- interleaved PCM frames (smst_batch_*_pcm): [S, n, C] of int16, int32, float16 or float32, or packed int24 as uint8 [S, n, C, 3];
     # the same dtype and layout back
     def _describe_frames(self, x, what):
@@ -464,6 +395,102 @@ class StretchBatch:
             return torch.zeros(shape, dtype=getattr(torch, _FRAME_DTYPE_OF[fmt]), device=like.device)
         return np.zeros(shape, _FRAME_DTYPE_OF[fmt])
 
+    # --- the calls: each on planar buffers (frames False, format None) or on frames -- the same body, _describe against _describe_frames and
+    # smst_batch_<name> against smst_batch_<name>_pcm
+    def _describe_any(self, frames, x, what):
+        """-> (pointer, streamStride, channelStride | frameStride, length, format | None, memory, keepalive)"""
+        if frames:
+            return self._describe_frames(x, what)
+        ptr, ss, cs, n, mem, keep = self._describe(x, what)
+        return ptr, ss, cs, n, None, mem, keep
+
+    def _new_out(self, n, fmt, like):
+        """zeros for n samples per stream: frames of format fmt, planar float32 [S, C, n] for None; a torch tensor beside ``like`` if that is one"""
+        if fmt is not None:
+            return self._new_frames(n, fmt, like)
+        if like is not None and _is_torch(like):
+            import torch
+            return torch.zeros((self.streams, self.channels, n), dtype=torch.float32, device=like.device)
+        return np.zeros((self.streams, self.channels, n), np.float32)
+
+    def _batch_call(self, name, fmt, mem, *args):
+        fn = getattr(self.lib, "smst_batch_" + name + ("" if fmt is None else "_pcm"))
+        _check(self.lib, fn(self.h, *args, mem) if fmt is None else fn(self.h, *args, fmt, mem))
+
+    def _signal_torch(self, out):
+        """torch ops on ``out`` issued from here on are ordered after our kernels (no host sync either)"""
+        import torch
+        _check(self.lib, self.lib.smst_batch_signal_stream(self.h, C.c_void_p(torch.cuda.current_stream(out.device).cuda_stream)))
+
+    def _process(self, frames, x, out_samples, in_samples, out, ordered):
+        S = self.streams
+        ptr, ss, inner, n, fmt, mem, keep = self._describe_any(frames, x, "input")
+        nin, pin = _int_array(n if in_samples is None else in_samples, S)
+        nout, pout = _int_array(out_samples, S)
+        max_out = max(int(nout.max()), 1)
+        if out is None:
+            out = self._new_out(max_out, fmt, x if mem == MEM_DEVICE else None)
+        optr, oss, oinner, on, ofmt, omem, okeep = self._describe_any(frames, out, "output")
+        if frames:
+            if omem != mem or ofmt != fmt:
+                raise StretchError("input and output must have the same format and live in the same memory space")
+            if omem == MEM_HOST and okeep is not out:
+                raise StretchError("output: need an array the library can write in place")
+        elif omem != mem:
+            raise StretchError("input and output must live in the same memory space")
+        if on < max_out or int(nin.max()) > n:
+            raise StretchError("buffer shorter than the requested sample count")
+        if mem == MEM_DEVICE and ordered:
+            self._order_after_torch(x, out)
+        # (ordered=False: the caller's contract -- inputs complete, outputs untouched and both tensors ALIVE until it synchronises the batch -- so
+        # nothing is tracked here.  Until round 6 the tensors were still put on the in-flight list, whose every 17th entry synchronises the batch:
+        # one pipeline drain per 16 calls, 2.4 ms of the bench's 17th step -- bench.py's per-step periods showed it, roofline.step_ms.in_order)
+        self._batch_call("process", fmt, mem, ptr, ss, inner, pin, optr, oss, oinner, pout)
+        if mem == MEM_DEVICE and ordered:
+            self._signal_torch(out)
+        return out
+
+    def _seek(self, name, frames, x, counts, *rates):
+        """seek (rates: the double array) and outputSeek (none)"""
+        ptr, ss, inner, n, fmt, mem, keep = self._describe_any(frames, x, "input")
+        nin, pin = _int_array(n if counts is None else counts, self.streams)
+        if mem == MEM_DEVICE:
+            self._order_after_torch(x)
+        self._batch_call(name, fmt, mem, ptr, ss, inner, pin, *rates)
+
+    def _rates(self, rates, dtype, pointer):
+        """one rate per stream (a scalar: the same for all) -> the pointer (which keeps the array alive)"""
+        return np.ascontiguousarray(np.broadcast_to(np.asarray(rates, dtype=dtype), (self.streams,))).ctypes.data_as(pointer)
+
+    def _flush(self, fmt, out_samples, rates, like):
+        nout, pout = _int_array(out_samples, self.streams)
+        out = self._new_out(max(int(nout.max()), 1), fmt, like)
+        optr, oss, oinner, on, ofmt, omem, okeep = self._describe_any(fmt is not None, out, "output")
+        self._batch_call("flush", fmt, omem, optr, oss, oinner, pout, self._rates(rates, np.float32, _fp))
+        if omem == MEM_DEVICE:
+            self.synchronize()
+        return out
+
+    def process(self, x, out_samples, in_samples=None, out=None, ordered=True):
+        """process(inputs, inputSamples, outputs, outputSamples) for every stream (signalsmith-stretch.h:210).
+
+        Device tensors: with ``ordered`` (default) the call is ordered after torch's current stream (the producer of ``x``) and
+        torch's current stream is ordered after it (consumers of the result) -- by events, without a host synchronisation.
+        That makes consecutive calls wait for each other through torch's stream.  A caller whose inputs are already
+        complete and who synchronises the batch itself before touching the outputs (``bench.py``) passes
+        ``ordered=False`` and keeps the overlap of call n+1's host scheduling with call n's kernels."""
+        return self._process(False, x, out_samples, in_samples, out, ordered)
+
+    def seek(self, x, rates, in_samples=None):
+        self._seek("seek", False, x, in_samples, self._rates(rates, np.float64, _dp))
+
+    def flush(self, out_samples, rates=0.0, like=None):
+        """flush() of every stream with a non-negative count; a negative count leaves that stream alone (include/smst.h)"""
+        return self._flush(None, out_samples, rates, like)
+
+    def outputSeek(self, x, input_lengths=None):
+        self._seek("output_seek", False, x, input_lengths)
+
     def processFrames(self, x, out_samples, in_samples=None, out=None, ordered=True):
         """process() on interleaved frames: x is [S, n, C] int16 (full scale 32768), int32 (2^31), float16 or float32, or uint8
         [S, n, C, 3] for packed int24 (8388608), numpy (host memory) or a torch GPU tensor (_describe_frames has the layout rules); the
@@ -471,85 +498,32 @@ class StretchBatch:
         unless setPcmDither() turned it on (int16 / int24);
         NaN -> 0.  int32 input above 2^24 is rounded to float32.  float16 output is round-to-nearest-even: subnormals kept, 65520 and
         above +-inf, NaN stays NaN (include/smst.h).  What was clamped: takePcmOvers().  ``ordered`` as in process()."""
-        S = self.streams
-        ptr, ss, fs, n, fmt, mem, keep = self._describe_frames(x, "input")
-        nin, pin = _int_array(n if in_samples is None else in_samples, S)
-        nout, pout = _int_array(out_samples, S)
-        max_out = max(int(nout.max()), 1)
-        if out is None:
-            out = self._new_frames(max_out, fmt, x if mem == MEM_DEVICE else None)
-        optr, oss, ofs, on, ofmt, omem, okeep = self._describe_frames(out, "output")
-        if omem != mem or ofmt != fmt:
-            raise StretchError("input and output must have the same format and live in the same memory space")
-        if omem == MEM_HOST and okeep is not out:
-            raise StretchError("output: need an array the library can write in place")
-        if on < max_out or int(nin.max()) > n:
-            raise StretchError("buffer shorter than the requested sample count")
-        if mem == MEM_DEVICE and ordered:
-            self._order_after_torch(x, out)
-        _check(self.lib, self.lib.smst_batch_process_pcm(self.h, ptr, ss, fs, pin, optr, oss, ofs, pout, fmt, mem))
-        if mem == MEM_DEVICE and ordered:
-            import torch
-            _check(self.lib, self.lib.smst_batch_signal_stream(self.h, C.c_void_p(torch.cuda.current_stream(out.device).cuda_stream)))
-        return out
+        return self._process(True, x, out_samples, in_samples, out, ordered)
 
     def seekFrames(self, x, rates, in_samples=None):
-        S = self.streams
-        ptr, ss, fs, n, fmt, mem, keep = self._describe_frames(x, "input")
-        nin, pin = _int_array(n if in_samples is None else in_samples, S)
-        r = np.ascontiguousarray(np.broadcast_to(np.asarray(rates, dtype=np.float64), (S,)))
-        if mem == MEM_DEVICE:
-            self._order_after_torch(x)
-        _check(self.lib, self.lib.smst_batch_seek_pcm(self.h, ptr, ss, fs, pin, r.ctypes.data_as(_dp), fmt, mem))
+        self._seek("seek", True, x, in_samples, self._rates(rates, np.float64, _dp))
 
     def flushFrames(self, out_samples, rates=0.0, like=None, dtype=np.int16):
         """flush() into [S, n, C] frames of ``dtype`` (int16, int32, float16 or float32), or with dtype="s24" into uint8 [S, n, C, 3]
         (packed int24); a negative count leaves that stream alone"""
-        S = self.streams
         fmt = PCM_S24 if isinstance(dtype, str) and dtype.lower() == "s24" else _FRAME_DTYPES.get(np.dtype(dtype).name)
         if fmt is None:
             raise StretchError("frames are int16, int32, float16, float32 or \"s24\"")
-        nout, pout = _int_array(out_samples, S)
-        r = np.ascontiguousarray(np.broadcast_to(np.asarray(rates, dtype=np.float32), (S,)))
-        out = self._new_frames(max(int(nout.max()), 1), fmt, like)
-        optr, oss, ofs, on, ofmt, omem, okeep = self._describe_frames(out, "output")
-        _check(self.lib, self.lib.smst_batch_flush_pcm(self.h, optr, oss, ofs, pout, r.ctypes.data_as(_fp), fmt, omem))
-        if omem == MEM_DEVICE:
-            self.synchronize()
-        return out
+        return self._flush(fmt, out_samples, rates, like)
 
     def outputSeekFrames(self, x, input_lengths=None):
-        S = self.streams
-        ptr, ss, fs, n, fmt, mem, keep = self._describe_frames(x, "input")
-        nin, pin = _int_array(n if input_lengths is None else input_lengths, S)
-        if mem == MEM_DEVICE:
-            self._order_after_torch(x)
-        _check(self.lib, self.lib.smst_batch_output_seek_pcm(self.h, ptr, ss, fs, pin, fmt, mem))
+        self._seek("output_seek", True, x, input_lengths)
 
     # --- whole clips (smst_batch_exact / smst_batch_exact_pcm): S clips of S lengths and S rates in one call
     def _exact(self, frames, x, out_samples, in_samples, out, ordered):
-        S, Cn = self.streams, self.channels
-        if frames:
-            ptr, ss, inner, n, fmt, mem, keep = self._describe_frames(x, "input")
-        else:
-            ptr, ss, inner, n, mem, keep = self._describe(x, "input")
-            fmt = None
+        S = self.streams
+        ptr, ss, inner, n, fmt, mem, keep = self._describe_any(frames, x, "input")
         nin, pin = _int_array(n if in_samples is None else in_samples, S)
         nout, pout = _int_array(out_samples, S)
         max_out = max(int(nout.max()), 1)
         if out is None:
-            if frames:
-                out = self._new_frames(max_out, fmt, x if mem == MEM_DEVICE else None)
-            elif mem == MEM_DEVICE:
-                import torch
-                out = torch.zeros((S, Cn, max_out), dtype=torch.float32, device=x.device)
-            else:
-                out = np.zeros((S, Cn, max_out), np.float32)
-        if frames:
-            optr, oss, oinner, on, ofmt, omem, okeep = self._describe_frames(out, "output")
-        else:
-            optr, oss, oinner, on, omem, okeep = self._describe(out, "output")
-            ofmt = None
+            out = self._new_out(max_out, fmt, x if mem == MEM_DEVICE else None)
+        optr, oss, oinner, on, ofmt, omem, okeep = self._describe_any(frames, out, "output")
         if omem != mem or ofmt != fmt:
             raise StretchError("input and output must have the same format and live in the same memory space")
         if omem == MEM_HOST and okeep is not out:
@@ -559,14 +533,9 @@ class StretchBatch:
         status = np.full(S, 1, np.int32)                        # (a stream that is left out keeps the 1)
         if mem == MEM_DEVICE and ordered:
             self._order_after_torch(x, out)
-        if frames:
-            rc = self.lib.smst_batch_exact_pcm(self.h, ptr, ss, inner, pin, optr, oss, oinner, pout, status.ctypes.data_as(_ip), fmt, mem)
-        else:
-            rc = self.lib.smst_batch_exact(self.h, ptr, ss, inner, pin, optr, oss, oinner, pout, status.ctypes.data_as(_ip), mem)
-        _check(self.lib, rc)
+        self._batch_call("exact", fmt, mem, ptr, ss, inner, pin, optr, oss, oinner, pout, status.ctypes.data_as(_ip))
         if mem == MEM_DEVICE and ordered:
-            import torch
-            _check(self.lib, self.lib.smst_batch_signal_stream(self.h, C.c_void_p(torch.cuda.current_stream(out.device).cuda_stream)))
+            self._signal_torch(out)
         return out, status == 0
 
     def exact(self, x, out_samples, in_samples=None, out=None, ordered=True):

@@ -19,42 +19,70 @@ using smst::Batch;
 
 static thread_local std::string g_lastError;
 
+// Memory a handle (or one call of a debug hook) owns: `cap` elements of T in device memory or in pinned host memory, released in the
+// destructor.  The owner selects the device first (hipSetDevice) wherever it frees or allocates.
+template <typename T, bool Pinned, size_t Slack = 0> struct Buffer {
+	T *p = nullptr;
+	size_t cap = 0;
+	Buffer() {}
+	Buffer(const Buffer &) = delete;
+	Buffer &operator=(const Buffer &) = delete;
+	~Buffer() { release(); }
+	operator T *() const { return p; }
+	void release() {
+		if (p) { if (Pinned) hipHostFree(p); else hipFree(p); }
+		p = nullptr;
+		cap = 0;
+	}
+	// exactly n elements, the contents undefined; what: the buffer's name in the error
+	void allocate(size_t n, const char *what) {
+		release();
+		const hipError_t err = Pinned ? hipHostMalloc(reinterpret_cast<void **>(&p), n*sizeof(T), hipHostMallocDefault) : hipMalloc(reinterpret_cast<void **>(&p), n*sizeof(T));
+		if (err != hipSuccess) throw smst::Error(std::string(Pinned ? "hipHostMalloc (" : "hipMalloc (") + what + ") failed", true);
+		cap = n;
+	}
+	// at least `need` elements (the contents are not kept); a growth is one event of `allocs` and takes need/8 + Slack elements more
+	void ensure(size_t need, int device, long long &allocs, const char *what) {
+		if (need <= cap) return;
+		++allocs;
+		hipSetDevice(device);
+		allocate(need + need/8 + Slack, what);
+	}
+};
+// the two growth formulas: float staging need + need/8 + 1024 elements, raw PCM frames need + need/8 + 4096 bytes
+typedef Buffer<float, false, 1024> DeviceFloats;
+typedef Buffer<float, true, 1024> PinnedFloats;
+typedef Buffer<unsigned char, false, 4096> DeviceBytes;
+typedef Buffer<unsigned char, true, 4096> PinnedBytes;
+
 struct smst_batch {
 	std::unique_ptr<Batch> engine;
 	// host staging (SMST_MEM_HOST)
-	float *dIn = nullptr, *dOut = nullptr;
-	size_t inCap = 0, outCap = 0;
+	DeviceFloats dIn, dOut;
 	long long stagingAllocs = 0;
 	// interleaved PCM (smst_batch_*_pcm): the raw frames as they cross PCIe, one device and one pinned host buffer per direction (bytes); the
 	// planar image the engine works on is dIn / dOut above.  The per-stream frame counts of the conversion kernels exist twice, as the engine's
 	// per-call tables do: a device-memory call returns before its kernels have run
-	unsigned char *dPcmIn = nullptr, *dPcmOut = nullptr, *hPcmIn = nullptr, *hPcmOut = nullptr;
-	size_t dPcmInCap = 0, dPcmOutCap = 0, hPcmInCap = 0, hPcmOutCap = 0;
+	DeviceBytes dPcmIn, dPcmOut;
+	PinnedBytes hPcmIn, hPcmOut;
 	// ... and, behind the counts, the dither entries of the call's output conversion ([S] smst::PcmDither, uploaded with the output counts by a
-	// call that dithers)
-	struct PcmCounts { int *host = nullptr, *dev = nullptr; hipEvent_t done = nullptr; bool used = false, dithered = false; } pcmCounts[2]; // [2*S]: input frames, output frames; [S] dither entries
+	// call that dithers: pcmUploadDither)
+	struct PcmCounts { // [2*S]: input frames, output frames; [S] dither entries
+		Buffer<int, true> host;
+		Buffer<int, false> dev;
+		hipEvent_t done = nullptr;
+		bool used = false;
+		const smst::PcmDither *dither = nullptr; // the call's entries in `dev`; null: the call does not dither
+		~PcmCounts() { if (done) hipEventDestroy(done); }
+	} pcmCounts[2];
 	int pcmCur = 0;
 	// dither of the int16 / int24 output (smst_batch_set_pcm_dither): per stream the mode, the seed, its hash and the frame counter
 	struct PcmDitherState { int mode = SMST_DITHER_NONE; long long seed = 0; unsigned h = 0; unsigned long long frames = 0; };
 	std::vector<PcmDitherState> pcmDither;
 	// overs of the output conversions ([S][2]: clamped, NaN): the kernels add to them, smst_batch_take_pcm_overs reads and clears them
-	unsigned *dPcmOvers = nullptr;
+	Buffer<unsigned, false> dPcmOvers;
 	std::vector<unsigned> hPcmOvers;
-	~smst_batch() {
-		if (engine) hipSetDevice(engine->device());
-		if (dIn) hipFree(dIn);
-		if (dOut) hipFree(dOut);
-		if (dPcmIn) hipFree(dPcmIn);
-		if (dPcmOut) hipFree(dPcmOut);
-		if (hPcmIn) hipHostFree(hPcmIn);
-		if (hPcmOut) hipHostFree(hPcmOut);
-		if (dPcmOvers) hipFree(dPcmOvers);
-		for (PcmCounts &c : pcmCounts) {
-			if (c.dev) hipFree(c.dev);
-			if (c.host) hipHostFree(c.host);
-			if (c.done) hipEventDestroy(c.done);
-		}
-	}
+	~smst_batch() { if (engine) hipSetDevice(engine->device()); } // (the buffers above go behind it, the engine last)
 };
 
 struct smst_stretch {
@@ -90,12 +118,7 @@ struct PoolGroup {
 	// per-run scratch, sized with the engine (nothing is allocated in a steady-state run)
 	std::vector<int> nIn, nOut;
 	std::vector<unsigned char> active;
-	float *hIn = nullptr, *hOut = nullptr; // pinned staging: the members' planes gathered as [slot][channel][longest count]
-	size_t hInCap = 0, hOutCap = 0;
-	~PoolGroup() {
-		if (hIn) hipHostFree(hIn);
-		if (hOut) hipHostFree(hOut);
-	}
+	PinnedFloats hIn, hOut; // pinned staging: the members' planes gathered as [slot][channel][longest count]
 };
 struct smst_pool {
 	int device = 0;
@@ -115,17 +138,30 @@ static int fail(const char *msg) {
 	return SMST_ERR_INVALID;
 }
 
-static void ensureStage(float *&ptr, size_t &cap, size_t need, int device, long long &allocs) {
-	if (need <= cap) return;
-	++allocs;
-	hipSetDevice(device);
-	if (ptr) hipFree(ptr);
-	ptr = nullptr;
-	cap = 0;
-	size_t want = need + need/8 + 1024;
-	if (hipMalloc(reinterpret_cast<void **>(&ptr), want*sizeof(float)) != hipSuccess) throw smst::Error("hipMalloc (staging) failed", true);
-	cap = want;
+// the planar staging image of one direction, [rows][len] floats
+static void ensureStage(smst_batch *b, DeviceFloats &image, size_t need) { image.ensure(need, b->engine->device(), b->stagingAllocs, "staging"); }
+// A call's counts as the staging side takes them: used[s] = n[s], 0 for a stream that moves nothing (a negative count; takesPart[s] < 0) ->
+// the largest, and the row length of a dense image [S][C][len], which is at least 1
+struct Counts { int most, len; };
+static Counts countsOf(const int *n, int S, int *used = nullptr, const int *takesPart = nullptr) {
+	int most = 0;
+	for (int s = 0; s < S; ++s) {
+		const int k = (takesPart && takesPart[s] < 0) ? 0 : std::max(n[s], 0);
+		if (used) used[s] = k;
+		most = std::max(most, k);
+	}
+	return Counts{most, std::max(most, 1)};
 }
+// flush(): a NEGATIVE count leaves that stream out of the call (flush() of an instance also resets it, :456-463: a count of 0 would do that)
+struct FlushCounts {
+	std::vector<int> counts;
+	std::vector<unsigned char> active;
+	bool all = true;
+	FlushCounts(const int *n, int S) : counts(n, n + S), active(S, 1) {
+		for (int s = 0; s < S; ++s) if (counts[s] < 0) { active[s] = 0; counts[s] = 0; all = false; }
+	}
+	const unsigned char *mask() const { return all ? nullptr : active.data(); }
+};
 
 static size_t pcmOversBytes(int streams) { return (size_t)2*streams*sizeof(unsigned); }
 
@@ -153,7 +189,7 @@ int smst_batch_create_ex(smst_batch **out, int streams, int channels, int block,
 	b->engine.reset(new Batch(streams, channels, block, interval, split != 0, device, seed, (flags & SMST_FLAG_HALF_STATE) != 0));
 	b->hPcmOvers.assign((size_t)2*streams, 0u);
 	b->pcmDither.assign((size_t)streams, smst_batch::PcmDitherState());
-	if (hipMalloc(reinterpret_cast<void **>(&b->dPcmOvers), pcmOversBytes(streams)) != hipSuccess) throw smst::Error("hipMalloc (PCM overs) failed", true);
+	b->dPcmOvers.allocate((size_t)2*streams, "PCM overs");
 	if (hipMemset(b->dPcmOvers, 0, pcmOversBytes(streams)) != hipSuccess) throw smst::Error("hipMemset (PCM overs) failed", true);
 	*out = b.release();
 	return SMST_OK;
@@ -190,7 +226,7 @@ BATCH_Q(smst_batch_half_state, b->engine->halfPrecisionState() ? 1 : 0)
 int smst_batch_output_seek_length(const smst_batch *b, float rate) { if (!b || !b->engine) return fail("null batch"); return b->engine->outputSeekLength(rate); }
 long long smst_batch_workspace_bytes(const smst_batch *b) { if (!b || !b->engine) return fail("null batch"); return (long long)(b->engine->workspaceBytes() + (b->dPcmOvers ? pcmOversBytes(b->engine->streams()) : 0)); }
 
-#define BATCH_CALL(body) if (!b || !b->engine) return fail("null batch"); SMST_TRY body; return SMST_OK; SMST_CATCH
+#define BATCH_CALL(...) if (!b || !b->engine) return fail("null batch"); SMST_TRY __VA_ARGS__; return SMST_OK; SMST_CATCH
 
 int smst_batch_reset(smst_batch *b) { BATCH_CALL(b->engine->reset()) }
 int smst_batch_set_transpose_factor(smst_batch *b, int s, float m, float t) { BATCH_CALL(b->engine->setTransposeFactor(s, m, t)) }
@@ -259,10 +295,8 @@ int smst_batch_debug_get_map(smst_batch *b, int stream, float *dst) {
 static const float *stageIn(smst_batch *b, const float *in, long long ss, long long cs, const int *n, int &maxLen) {
 	Batch &e = *b->engine;
 	const int S = e.streams(), C = e.channels();
-	maxLen = 0;
-	for (int s = 0; s < S; ++s) maxLen = std::max(maxLen, n[s]);
-	if (maxLen == 0) maxLen = 1;
-	ensureStage(b->dIn, b->inCap, (size_t)S*C*maxLen, e.device(), b->stagingAllocs);
+	maxLen = countsOf(n, S).len;
+	ensureStage(b, b->dIn, (size_t)S*C*maxLen);
 	hipSetDevice(e.device());
 	for (int s = 0; s < S; ++s) {
 		for (int c = 0; c < C; ++c) {
@@ -286,11 +320,6 @@ static void unstageOut(smst_batch *b, float *out, long long ss, long long cs, co
 		}
 	}
 	if (hipStreamSynchronize(e.stream()) != hipSuccess) throw smst::Error("hipStreamSynchronize failed", true);
-}
-static int maxOf(const int *n, int S) {
-	int m = 0;
-	for (int s = 0; s < S; ++s) m = std::max(m, n[s]);
-	return std::max(m, 1);
 }
 
 int smst_batch_seek(smst_batch *b, const float *in, long long ss, long long cs, const int *inSamples, const double *rates, int memory) {
@@ -316,8 +345,8 @@ int smst_batch_process(smst_batch *b, const float *in, long long iss, long long 
 			Batch &e = *b->engine;
 			int maxIn;
 			const float *dIn = stageIn(b, in, iss, ics, inSamples, maxIn);
-			const int maxOut = maxOf(outSamples, e.streams());
-			ensureStage(b->dOut, b->outCap, (size_t)e.streams()*e.channels()*maxOut, e.device(), b->stagingAllocs);
+			const int maxOut = countsOf(outSamples, e.streams()).len;
+			ensureStage(b, b->dOut, (size_t)e.streams()*e.channels()*maxOut);
 			e.process(dIn, (long long)e.channels()*maxIn, maxIn, inSamples, b->dOut, (long long)e.channels()*maxOut, maxOut, outSamples);
 			unstageOut(b, out, oss, ocs, outSamples, maxOut);
 		}
@@ -327,19 +356,14 @@ int smst_batch_flush(smst_batch *b, float *out, long long oss, long long ocs, co
 	BATCH_CALL({
 		if (!outSamples) throw smst::Error("null sample counts");
 		Batch &e = *b->engine;
-		// a NEGATIVE count leaves that stream out of the flush (flush() of an instance also resets it, :456-463: a count of 0 would do that)
-		std::vector<unsigned char> active(e.streams(), 1);
-		std::vector<int> counts(outSamples, outSamples + e.streams());
-		bool all = true;
-		for (int s = 0; s < e.streams(); ++s) if (counts[s] < 0) { active[s] = 0; counts[s] = 0; all = false; }
-		const unsigned char *mask = all ? nullptr : active.data();
+		const FlushCounts f(outSamples, e.streams());
 		if (memory == SMST_MEM_DEVICE) {
-			e.flush(out, oss, ocs, counts.data(), rates, mask);
+			e.flush(out, oss, ocs, f.counts.data(), rates, f.mask());
 		} else {
-			const int maxOut = maxOf(counts.data(), e.streams());
-			ensureStage(b->dOut, b->outCap, (size_t)e.streams()*e.channels()*maxOut, e.device(), b->stagingAllocs);
-			e.flush(b->dOut, (long long)e.channels()*maxOut, maxOut, counts.data(), rates, mask);
-			unstageOut(b, out, oss, ocs, counts.data(), maxOut);
+			const int maxOut = countsOf(f.counts.data(), e.streams()).len;
+			ensureStage(b, b->dOut, (size_t)e.streams()*e.channels()*maxOut);
+			e.flush(b->dOut, (long long)e.channels()*maxOut, maxOut, f.counts.data(), rates, f.mask());
+			unstageOut(b, out, oss, ocs, f.counts.data(), maxOut);
 		}
 	})
 }
@@ -362,17 +386,10 @@ int smst_batch_output_seek(smst_batch *b, const float *in, long long ss, long lo
 // reads, kPcmOut empties the one it wrote; both run on the engine's stream.
 // ---------------------------------------------------------------------------------------------------------
 static size_t pcmElemBytes(int format) { return format == SMST_PCM_S16 || format == SMST_PCM_F16 ? 2 : format == SMST_PCM_S24 ? 3 : 4; }
-static void ensurePcmBytes(unsigned char *&ptr, size_t &cap, size_t need, bool pinned, int device, long long &allocs) {
-	if (need <= cap) return;
-	++allocs;
-	hipSetDevice(device);
-	if (ptr) { if (pinned) hipHostFree(ptr); else hipFree(ptr); }
-	ptr = nullptr;
-	cap = 0;
-	const size_t want = need + need/8 + 4096;
-	const hipError_t err = pinned ? hipHostMalloc(reinterpret_cast<void **>(&ptr), want, hipHostMallocDefault) : hipMalloc(reinterpret_cast<void **>(&ptr), want);
-	if (err != hipSuccess) throw smst::Error(pinned ? "hipHostMalloc (PCM staging) failed" : "hipMalloc (PCM staging) failed", true);
-	cap = want;
+// the raw frames of one direction: the pinned host buffer, then the device buffer
+static void ensurePcmBytes(smst_batch *b, PinnedBytes &host, DeviceBytes &dev, size_t bytes) {
+	host.ensure(bytes, b->engine->device(), b->stagingAllocs, "PCM staging");
+	dev.ensure(bytes, b->engine->device(), b->stagingAllocs, "PCM staging");
 }
 static void checkPcmSide(const void *buf, long long frameStride, const int *n, int S, int C, bool negativeSkips) {
 	if (!n) throw smst::Error("null sample counts");
@@ -395,34 +412,39 @@ static smst_batch::PcmCounts &beginPcmCall(smst_batch *b) {
 	smst_batch::PcmCounts &c = b->pcmCounts[b->pcmCur];
 	if (!c.host) {
 		++b->stagingAllocs;
-		const size_t bytes = (size_t)2*e.streams()*sizeof(int) + (size_t)e.streams()*sizeof(smst::PcmDither);
-		if (hipHostMalloc(reinterpret_cast<void **>(&c.host), bytes, hipHostMallocDefault) != hipSuccess) throw smst::Error("hipHostMalloc (PCM counts) failed", true);
-		if (hipMalloc(reinterpret_cast<void **>(&c.dev), bytes) != hipSuccess) throw smst::Error("hipMalloc (PCM counts) failed", true);
+		const size_t ints = (size_t)2*e.streams() + (size_t)e.streams()*(sizeof(smst::PcmDither)/sizeof(int));
+		c.host.allocate(ints, "PCM counts");
+		c.dev.allocate(ints, "PCM counts");
 		if (hipEventCreateWithFlags(&c.done, hipEventDisableTiming) != hipSuccess) throw smst::Error("hipEventCreate failed", true);
 	}
 	if (c.used && hipEventSynchronize(c.done) != hipSuccess) throw smst::Error("hipEventSynchronize failed", true);
 	c.used = false;
-	c.dithered = false;
+	c.dither = nullptr;
 	return c;
 }
-// the dither entries of a call's table: on the host, and where the kernels read them
-static smst::PcmDither *pcmDitherHost(smst_batch *b, smst_batch::PcmCounts &c) { return reinterpret_cast<smst::PcmDither *>(c.host + 2*b->engine->streams()); }
-static const smst::PcmDither *pcmDitherDev(smst_batch *b, smst_batch::PcmCounts &c) { return c.dithered ? reinterpret_cast<const smst::PcmDither *>(c.dev + 2*b->engine->streams()) : nullptr; }
 // whether a call of this format dithers: a stream has a mode, and the format has a step to dither
 static bool pcmDithers(const smst_batch *b, int format) {
 	if (format != SMST_PCM_S16 && format != SMST_PCM_S24) return false;
 	for (const smst_batch::PcmDitherState &d : b->pcmDither) if (d.mode != SMST_DITHER_NONE) return true;
 	return false;
 }
-// ... if so the entries are filled: every stream's mode and hash, and its frame counter as the index of the call's first frame
-static bool pcmFillDither(smst_batch *b, smst_batch::PcmCounts &c, int format) {
-	if (!pcmDithers(b, format)) return false;
-	smst::PcmDither *t = pcmDitherHost(b, c);
-	for (size_t s = 0; s < b->pcmDither.size(); ++s) {
-		const smst_batch::PcmDitherState &d = b->pcmDither[s];
-		t[s] = smst::PcmDither{unsigned(d.mode), d.h, unsigned(d.frames), unsigned(d.frames >> 32)};
+// ... if so the call's entries are filled -- every stream's mode and hash, and its frame counter as the index of the call's first frame --
+// and uploaded, with the S output counts in front of them where the call has some (still one copy); c.dither is where the kernels read
+// them.  The only place that knows that the entries lie behind the 2*S counts.
+static void pcmUploadDither(smst_batch *b, smst_batch::PcmCounts &c, int format, bool withOutCounts) {
+	Batch &e = *b->engine;
+	const size_t S = size_t(e.streams()), first = withOutCounts ? S : 2*S;
+	const bool dithered = pcmDithers(b, format);
+	if (dithered) {
+		smst::PcmDither *t = reinterpret_cast<smst::PcmDither *>(c.host + 2*S);
+		for (size_t s = 0; s < S; ++s) {
+			const smst_batch::PcmDitherState &d = b->pcmDither[s];
+			t[s] = smst::PcmDither{unsigned(d.mode), d.h, unsigned(d.frames), unsigned(d.frames >> 32)};
+		}
+		c.dither = reinterpret_cast<const smst::PcmDither *>(c.dev + 2*S);
 	}
-	return true;
+	const size_t bytes = (2*S - first)*sizeof(int) + (dithered ? S*sizeof(smst::PcmDither) : 0);
+	if (hipMemcpyAsync(c.dev + first, c.host + first, bytes, hipMemcpyHostToDevice, e.stream()) != hipSuccess) throw smst::Error("hipMemcpyAsync (H2D) failed", true);
 }
 // after a call that emitted n[s] frames: the counters of the streams that have a mode move on, whatever the call's format
 static void pcmAdvanceDither(smst_batch *b, const int *n) {
@@ -442,8 +464,7 @@ static void pcmRawIn(smst_batch *b, const void *in, long long ss, long long fs, 
 	const size_t esz = pcmElemBytes(format);
 	const long long row = pcmRowElems(most, C);
 	const size_t bytes = (size_t)S*row*esz;
-	ensurePcmBytes(b->hPcmIn, b->hPcmInCap, bytes, true, e.device(), b->stagingAllocs);
-	ensurePcmBytes(b->dPcmIn, b->dPcmInCap, bytes, false, e.device(), b->stagingAllocs);
+	ensurePcmBytes(b, b->hPcmIn, b->dPcmIn, bytes);
 	for (int s = 0; s < S; ++s) {
 		if (n[s] <= 0) continue;
 		const unsigned char *src = static_cast<const unsigned char *>(in) + (size_t)s*ss*esz;
@@ -474,10 +495,9 @@ static void pcmRawOut(smst_batch *b, void *out, long long ss, long long fs, cons
 static int pcmStageIn(smst_batch *b, smst_batch::PcmCounts &c, const void *in, long long ss, long long fs, const int *n, int format, int memory) {
 	Batch &e = *b->engine;
 	const int S = e.streams(), C = e.channels();
-	int most = 0;
-	for (int s = 0; s < S; ++s) { c.host[s] = n[s]; most = std::max(most, n[s]); }
-	const int maxLen = std::max(most, 1);
-	ensureStage(b->dIn, b->inCap, (size_t)S*C*maxLen, e.device(), b->stagingAllocs);
+	const Counts k = countsOf(n, S, c.host);
+	const int most = k.most, maxLen = k.len;
+	ensureStage(b, b->dIn, (size_t)S*C*maxLen);
 	hipSetDevice(e.device());
 	if (hipMemcpyAsync(c.dev, c.host, S*sizeof(int), hipMemcpyHostToDevice, e.stream()) != hipSuccess) throw smst::Error("hipMemcpyAsync (H2D) failed", true);
 	const void *raw = in;
@@ -495,20 +515,12 @@ static int pcmStageIn(smst_batch *b, smst_batch::PcmCounts &c, const void *in, l
 static int pcmPrepareOut(smst_batch *b, smst_batch::PcmCounts &c, const int *n, int format, int memory) {
 	Batch &e = *b->engine;
 	const int S = e.streams(), C = e.channels();
-	int most = 0;
-	for (int s = 0; s < S; ++s) { c.host[S + s] = std::max(n[s], 0); most = std::max(most, n[s]); }
-	const int maxLen = std::max(most, 1);
-	ensureStage(b->dOut, b->outCap, (size_t)S*C*maxLen, e.device(), b->stagingAllocs);
-	if (memory == SMST_MEM_HOST && most > 0) {
-		const size_t bytes = (size_t)S*pcmRowElems(most, C)*pcmElemBytes(format);
-		ensurePcmBytes(b->hPcmOut, b->hPcmOutCap, bytes, true, e.device(), b->stagingAllocs);
-		ensurePcmBytes(b->dPcmOut, b->dPcmOutCap, bytes, false, e.device(), b->stagingAllocs);
-	}
+	const Counts k = countsOf(n, S, c.host + S);
+	ensureStage(b, b->dOut, (size_t)S*C*k.len);
+	if (memory == SMST_MEM_HOST && k.most > 0) ensurePcmBytes(b, b->hPcmOut, b->dPcmOut, (size_t)S*pcmRowElems(k.most, C)*pcmElemBytes(format));
 	hipSetDevice(e.device());
-	c.dithered = pcmFillDither(b, c, format);
-	const size_t bytes = S*sizeof(int) + (c.dithered ? S*sizeof(smst::PcmDither) : 0); // (the entries lie behind the output counts: still one copy)
-	if (hipMemcpyAsync(c.dev + S, c.host + S, bytes, hipMemcpyHostToDevice, e.stream()) != hipSuccess) throw smst::Error("hipMemcpyAsync (H2D) failed", true);
-	return maxLen;
+	pcmUploadDither(b, c, format, true);
+	return k.len;
 }
 // The planar image b->dOut -> raw frames, behind the engine's last emitting kernel (everything of a call is joined into the engine's stream,
 // which is what smst_batch_synchronize and smst_batch_signal_stream wait on).  Host memory: the call returns with the frames in place.
@@ -516,16 +528,15 @@ static void pcmStageOut(smst_batch *b, smst_batch::PcmCounts &c, void *out, long
 	Batch &e = *b->engine;
 	const int S = e.streams(), C = e.channels();
 	const int *n = c.host + S;
-	int most = 0;
-	for (int s = 0; s < S; ++s) most = std::max(most, n[s]);
+	const int most = countsOf(n, S).most;
 	hipSetDevice(e.device());
 	if (memory == SMST_MEM_DEVICE) {
-		smst::launchPcmOut(format, b->dOut, (long long)C*maxLen, maxLen, out, ss, fs, c.dev + S, S, C, most, b->dPcmOvers, e.stream(), pcmDitherDev(b, c));
+		smst::launchPcmOut(format, b->dOut, (long long)C*maxLen, maxLen, out, ss, fs, c.dev + S, S, C, most, b->dPcmOvers, e.stream(), c.dither);
 		pcmAdvanceDither(b, n);
 		return;
 	}
 	if (most >= 1) {
-		smst::launchPcmOut(format, b->dOut, (long long)C*maxLen, maxLen, b->dPcmOut, pcmRowElems(most, C), C, c.dev + S, S, C, most, b->dPcmOvers, e.stream(), pcmDitherDev(b, c));
+		smst::launchPcmOut(format, b->dOut, (long long)C*maxLen, maxLen, b->dPcmOut, pcmRowElems(most, C), C, c.dev + S, S, C, most, b->dPcmOvers, e.stream(), c.dither);
 		pcmRawOut(b, out, ss, fs, n, most, format);
 	}
 	pcmAdvanceDither(b, n);
@@ -586,14 +597,10 @@ int smst_batch_flush_pcm(smst_batch *b, void *out, long long oss, long long ofs,
 		Batch &e = *b->engine;
 		checkPcmFormat(format, memory);
 		checkPcmSide(out, ofs, outSamples, e.streams(), e.channels(), true);
-		// a NEGATIVE count leaves that stream out of the flush, as in smst_batch_flush
-		std::vector<unsigned char> active(e.streams(), 1);
-		std::vector<int> counts(outSamples, outSamples + e.streams());
-		bool all = true;
-		for (int s = 0; s < e.streams(); ++s) if (counts[s] < 0) { active[s] = 0; counts[s] = 0; all = false; }
+		const FlushCounts f(outSamples, e.streams());
 		smst_batch::PcmCounts &c = beginPcmCall(b);
-		const int maxOut = pcmPrepareOut(b, c, counts.data(), format, memory);
-		e.flush(b->dOut, (long long)e.channels()*maxOut, maxOut, counts.data(), rates, all ? nullptr : active.data());
+		const int maxOut = pcmPrepareOut(b, c, f.counts.data(), format, memory);
+		e.flush(b->dOut, (long long)e.channels()*maxOut, maxOut, f.counts.data(), rates, f.mask());
 		pcmStageOut(b, c, out, oss, ofs, maxOut, format, memory);
 		endPcmCall(b, c);
 	})
@@ -626,12 +633,10 @@ static void checkExactArgs(const Batch &e, const void *in, const int *inSamples,
 		if (!out || (inSamples[s] > 0 && !in)) throw smst::Error("null buffer with a non-zero sample count");
 	}
 }
-// the counts of the streams that take part (a stream left out moves no sample in either direction); returns the largest
+// the counts of the streams that take part (a stream left out moves no sample in either direction); returns the row length of their image
 static int exactCounts(const int *n, const int *outSamples, int S, std::vector<int> &counts) {
 	counts.assign(S, 0);
-	int most = 0;
-	for (int s = 0; s < S; ++s) if (outSamples[s] >= 0) { counts[s] = n[s]; most = std::max(most, n[s]); }
-	return most;
+	return countsOf(n, S, counts.data(), outSamples).len;
 }
 // Batch::exact's flags -> the status array of the call (a stream that was left out keeps its entry)
 static void runExact(Batch &e, const Batch::ClipIo &io, const int *inSamples, const int *outSamples, int *status) {
@@ -643,9 +648,7 @@ static const char *const kShortMessage = "exact(): input shorter than outputSeek
 
 int smst_batch_exact(smst_batch *b, const float *in, long long iss, long long ics, const int *inSamples,
                      float *out, long long oss, long long ocs, const int *outSamples, int *status, int memory) {
-	if (!b || !b->engine) return fail("null batch");
-	SMST_TRY
-	{
+	BATCH_CALL({
 		Batch &e = *b->engine;
 		checkExactArgs(e, in, inSamples, out, outSamples, 0, 0, false, memory);
 		if (memory == SMST_MEM_DEVICE) {
@@ -654,53 +657,75 @@ int smst_batch_exact(smst_batch *b, const float *in, long long iss, long long ic
 			const int S = e.streams(), C = e.channels();
 			std::vector<int> nIn, nOut;
 			exactCounts(inSamples, outSamples, S, nIn);
-			const int maxOut = std::max(exactCounts(outSamples, outSamples, S, nOut), 1);
+			const int maxOut = exactCounts(outSamples, outSamples, S, nOut);
 			int maxIn;
 			const float *dIn = stageIn(b, in, iss, ics, nIn.data(), maxIn);
-			ensureStage(b->dOut, b->outCap, (size_t)S*C*maxOut, e.device(), b->stagingAllocs);
+			ensureStage(b, b->dOut, (size_t)S*C*maxOut);
 			runExact(e, Batch::ClipIo{dIn, (long long)C*maxIn, maxIn, b->dOut, (long long)C*maxOut, maxOut, 0, nullptr}, inSamples, outSamples, status);
 			unstageOut(b, out, oss, ocs, nOut.data(), maxOut);
 		}
-	}
-	return SMST_OK;
-	SMST_CATCH
+	})
 }
 int smst_batch_exact_pcm(smst_batch *b, const void *in, long long iss, long long ifs, const int *inSamples,
                          void *out, long long oss, long long ofs, const int *outSamples, int *status, int format, int memory) {
-	if (!b || !b->engine) return fail("null batch");
-	SMST_TRY
-	{
+	BATCH_CALL({
 		Batch &e = *b->engine;
 		checkPcmFormat(format, memory);
 		checkExactArgs(e, in, inSamples, out, outSamples, ifs, ofs, true, memory);
 		// a dithered call: the streams' modes and hashes ride in the _pcm calls' table (the frame index is the place in the clip: the counters
 		// are neither read nor moved)
 		smst_batch::PcmCounts *table = pcmDithers(b, format) ? &beginPcmCall(b) : nullptr;
-		const smst::PcmDither *dither = nullptr;
-		if (table) {
-			table->dithered = pcmFillDither(b, *table, format);
-			if (hipMemcpyAsync(table->dev + 2*e.streams(), table->host + 2*e.streams(), e.streams()*sizeof(smst::PcmDither), hipMemcpyHostToDevice, e.stream()) != hipSuccess) throw smst::Error("hipMemcpyAsync (H2D) failed", true);
-			dither = pcmDitherDev(b, *table);
-		}
+		if (table) pcmUploadDither(b, *table, format, false);
+		const smst::PcmDither *dither = table ? table->dither : nullptr;
 		if (memory == SMST_MEM_DEVICE) {
 			runExact(e, Batch::ClipIo{in, iss, ifs, out, oss, ofs, format, b->dPcmOvers, dither}, inSamples, outSamples, status);
 		} else {
 			const int S = e.streams(), C = e.channels();
 			std::vector<int> nIn, nOut;
-			const int mostIn = std::max(exactCounts(inSamples, outSamples, S, nIn), 1), mostOut = std::max(exactCounts(outSamples, outSamples, S, nOut), 1);
-			const size_t outBytes = (size_t)S*pcmRowElems(mostOut, C)*pcmElemBytes(format);
-			ensurePcmBytes(b->hPcmOut, b->hPcmOutCap, outBytes, true, e.device(), b->stagingAllocs);
-			ensurePcmBytes(b->dPcmOut, b->dPcmOutCap, outBytes, false, e.device(), b->stagingAllocs);
+			const int mostIn = exactCounts(inSamples, outSamples, S, nIn), mostOut = exactCounts(outSamples, outSamples, S, nOut);
+			ensurePcmBytes(b, b->hPcmOut, b->dPcmOut, (size_t)S*pcmRowElems(mostOut, C)*pcmElemBytes(format));
 			pcmRawIn(b, in, iss, ifs, nIn.data(), mostIn, format);
 			runExact(e, Batch::ClipIo{b->dPcmIn, pcmRowElems(mostIn, C), C, b->dPcmOut, pcmRowElems(mostOut, C), C, format, b->dPcmOvers, dither}, inSamples, outSamples, status);
 			pcmRawOut(b, out, oss, ofs, nOut.data(), mostOut, format);
 		}
 		if (table) endPcmCall(b, *table);
-	}
-	return SMST_OK;
-	SMST_CATCH
+	})
 }
 } // extern "C"
+// What the two debug converters are: the launch of one conversion kernel on device copies of the caller's buffers, which sit as far behind a
+// 16-byte boundary as the caller's own do; the launch's table (the counts, or the segments) and, uploaded in front of everything, `first`
+// (the dither entries; 0 bytes: none); the overs zeroed and, `counted`, read back.  launch(src, dst, table, first, overs) runs on the null
+// stream.  name: the hook's, in front of a HIP error.
+template <typename Launch> static void debugConvert(const std::string &name, int streams, const void *src, size_t srcBytes, void *dst, size_t dstBytes, const void *table, size_t tableBytes,
+		const void *first, size_t firstBytes, bool counted, long long *clamped, long long *nans, Launch launch) {
+	auto hip = [&](hipError_t err) { if (err != hipSuccess) throw smst::Error(name + ": " + hipGetErrorString(err), true); };
+	Buffer<unsigned char, false> dSrc, dDst, dTable, dFirst, dOvers; // freed when the function leaves, whichever way
+	std::vector<unsigned> overs((size_t)2*streams, 0u);
+	dSrc.allocate(srcBytes + 32, name.c_str());
+	if (firstBytes) {
+		dFirst.allocate(firstBytes, name.c_str());
+		hip(hipMemcpy(dFirst, first, firstBytes, hipMemcpyHostToDevice));
+	}
+	dDst.allocate(dstBytes + 32, name.c_str());
+	dTable.allocate(tableBytes, name.c_str());
+	unsigned char *s0 = dSrc + reinterpret_cast<uintptr_t>(src)%16, *d0 = dDst + reinterpret_cast<uintptr_t>(dst)%16;
+	if (srcBytes) hip(hipMemcpy(s0, src, srcBytes, hipMemcpyHostToDevice));
+	if (dstBytes) hip(hipMemcpy(d0, dst, dstBytes, hipMemcpyHostToDevice));
+	hip(hipMemcpy(dTable, table, tableBytes, hipMemcpyHostToDevice));
+	if (counted) {
+		dOvers.allocate(pcmOversBytes(streams), name.c_str());
+		hip(hipMemcpy(dOvers, overs.data(), pcmOversBytes(streams), hipMemcpyHostToDevice));
+	}
+	launch(s0, d0, dTable.p, dFirst.p, reinterpret_cast<unsigned *>(dOvers.p));
+	hip(hipGetLastError());
+	hip(hipStreamSynchronize(nullptr));
+	if (dstBytes) hip(hipMemcpy(dst, d0, dstBytes, hipMemcpyDeviceToHost));
+	if (counted) hip(hipMemcpy(overs.data(), dOvers, pcmOversBytes(streams), hipMemcpyDeviceToHost));
+	for (int s = 0; s < streams; ++s) {
+		if (clamped) clamped[s] = overs[2*s];
+		if (nans) nans[s] = overs[2*s + 1];
+	}
+}
 static int pcmConvert(int device, int dir, int format, int streams, int channels, const int *counts,
                       const void *src, long long srcSS, long long srcInner, void *dst, long long dstSS, long long dstInner, long long *clamped, long long *nans,
                       const int *modes = nullptr, const long long *seeds = nullptr, const long long *firstFrames = nullptr) {
@@ -708,8 +733,8 @@ static int pcmConvert(int device, int dir, int format, int streams, int channels
 	checkPcmFormat(format, SMST_MEM_HOST);
 	if (dir != 0 && dir != 1) throw smst::Error("pcm convert: dir is 0 (PCM -> planar) or 1 (planar -> PCM)");
 	if (streams < 1 || channels < 1 || channels > 16 || !counts || !src || !dst || srcSS < 0 || dstSS < 0 || srcInner < 0 || dstInner < 0) throw smst::Error("pcm convert: bad arguments");
-	int most = 0;
-	for (int s = 0; s < streams; ++s) { if (counts[s] < 0) throw smst::Error("negative sample count"); most = std::max(most, counts[s]); }
+	for (int s = 0; s < streams; ++s) if (counts[s] < 0) throw smst::Error("negative sample count");
+	const int most = countsOf(counts, streams).most;
 	const long long pcmFS = dir == 0 ? srcInner : dstInner;
 	if (pcmFS < channels) throw smst::Error("frame stride smaller than the channel count");
 	const size_t esz = pcmElemBytes(format);
@@ -719,14 +744,8 @@ static int pcmConvert(int device, int dir, int format, int streams, int channels
 	const size_t plBytes = most ? size_t((streams - 1)*plSS + (channels - 1)*plCS + most)*sizeof(float) : 0;
 	const size_t srcBytes = dir == 0 ? pcmBytes : plBytes, dstBytes = dir == 0 ? plBytes : pcmBytes;
 	if (hipSetDevice(device) != hipSuccess) throw smst::Error("hipSetDevice failed", true);
-	unsigned char *dSrc = nullptr, *dDst = nullptr;
-	int *dCounts = nullptr;
-	unsigned *dOvers = nullptr;
-	std::vector<unsigned> overs((size_t)2*streams, 0u);
-	const bool counted = dir == 1 && (clamped || nans);
 	// the streams' dither entries (dir 1); a launch is a dithered one when a stream has a mode
 	std::vector<smst::PcmDither> dither;
-	smst::PcmDither *dDither = nullptr;
 	bool dithered = false;
 	if (modes) {
 		if (!seeds || !firstFrames) throw smst::Error("pcm convert: null seeds or first frames");
@@ -737,36 +756,12 @@ static int pcmConvert(int device, int dir, int format, int streams, int channels
 			dithered = dithered || modes[s] != SMST_DITHER_NONE;
 		}
 	}
-	hipError_t err = hipMalloc(reinterpret_cast<void **>(&dSrc), srcBytes + 32);
-	if (err == hipSuccess && dithered) err = hipMalloc(reinterpret_cast<void **>(&dDither), streams*sizeof(smst::PcmDither));
-	if (err == hipSuccess && dithered) err = hipMemcpy(dDither, dither.data(), streams*sizeof(smst::PcmDither), hipMemcpyHostToDevice);
-	if (err == hipSuccess) err = hipMalloc(reinterpret_cast<void **>(&dDst), dstBytes + 32);
-	if (err == hipSuccess) err = hipMalloc(reinterpret_cast<void **>(&dCounts), streams*sizeof(int));
-	// the device buffers sit as far behind a 16-byte boundary as the caller's do
-	unsigned char *s0 = dSrc + reinterpret_cast<uintptr_t>(src)%16, *d0 = dDst + reinterpret_cast<uintptr_t>(dst)%16;
-	if (err == hipSuccess && srcBytes) err = hipMemcpy(s0, src, srcBytes, hipMemcpyHostToDevice);
-	if (err == hipSuccess && dstBytes) err = hipMemcpy(d0, dst, dstBytes, hipMemcpyHostToDevice);
-	if (err == hipSuccess) err = hipMemcpy(dCounts, counts, streams*sizeof(int), hipMemcpyHostToDevice);
-	if (err == hipSuccess && counted) err = hipMalloc(reinterpret_cast<void **>(&dOvers), pcmOversBytes(streams));
-	if (err == hipSuccess && counted) err = hipMemcpy(dOvers, overs.data(), pcmOversBytes(streams), hipMemcpyHostToDevice);
-	if (err == hipSuccess) {
-		if (dir == 0) smst::launchPcmIn(format, s0, srcSS, srcInner, reinterpret_cast<float *>(d0), dstSS, dstInner, dCounts, streams, channels, most, nullptr);
-		else smst::launchPcmOut(format, reinterpret_cast<const float *>(s0), srcSS, srcInner, d0, dstSS, dstInner, dCounts, streams, channels, most, dOvers, nullptr, dDither);
-		err = hipGetLastError();
-	}
-	if (err == hipSuccess) err = hipStreamSynchronize(nullptr);
-	if (err == hipSuccess && dstBytes) err = hipMemcpy(dst, d0, dstBytes, hipMemcpyDeviceToHost);
-	if (err == hipSuccess && counted) err = hipMemcpy(overs.data(), dOvers, pcmOversBytes(streams), hipMemcpyDeviceToHost);
-	if (dSrc) hipFree(dSrc);
-	if (dDst) hipFree(dDst);
-	if (dCounts) hipFree(dCounts);
-	if (dOvers) hipFree(dOvers);
-	if (dDither) hipFree(dDither);
-	if (err != hipSuccess) throw smst::Error(std::string("pcm convert: ") + hipGetErrorString(err), true);
-	for (int s = 0; s < streams; ++s) {
-		if (clamped) clamped[s] = overs[2*s];
-		if (nans) nans[s] = overs[2*s + 1];
-	}
+	debugConvert("pcm convert", streams, src, srcBytes, dst, dstBytes, counts, streams*sizeof(int), dither.data(), dithered ? streams*sizeof(smst::PcmDither) : 0,
+	             dir == 1 && (clamped || nans), clamped, nans, [&](unsigned char *s0, unsigned char *d0, const unsigned char *dCounts, const unsigned char *dDither, unsigned *dOvers) {
+		const int *n = reinterpret_cast<const int *>(dCounts);
+		if (dir == 0) smst::launchPcmIn(format, s0, srcSS, srcInner, reinterpret_cast<float *>(d0), dstSS, dstInner, n, streams, channels, most, nullptr);
+		else smst::launchPcmOut(format, reinterpret_cast<const float *>(s0), srcSS, srcInner, d0, dstSS, dstInner, n, streams, channels, most, dOvers, nullptr, reinterpret_cast<const smst::PcmDither *>(dDither));
+	});
 	return SMST_OK;
 	SMST_CATCH
 }
@@ -814,37 +809,12 @@ int smst_debug_clip_copy(int device, int dir, int format, int streams, int chann
 	};
 	const size_t srcBytes = spanBytes(srcFrames, srcEnd, srcSS, srcInner), dstBytes = spanBytes(dstFrames, dstEnd, dstSS, dstInner);
 	if (hipSetDevice(device) != hipSuccess) throw smst::Error("hipSetDevice failed", true);
-	struct DeviceBuffer { // freed when the function leaves, whichever way
-		void *p = nullptr;
-		~DeviceBuffer() { if (p) hipFree(p); }
-		void alloc(size_t bytes) { if (hipMalloc(&p, bytes) != hipSuccess) throw smst::Error("clip copy: hipMalloc failed", true); }
-	} dSrc, dDst, dSegs, dOvers;
-	auto hip = [](hipError_t err) { if (err != hipSuccess) throw smst::Error(std::string("clip copy: ") + hipGetErrorString(err), true); };
-	std::vector<unsigned> overs((size_t)2*streams, 0u);
-	const bool counted = dstFrames && (clamped || nans);
-	dSrc.alloc(srcBytes + 32);
-	dDst.alloc(dstBytes + 32);
-	dSegs.alloc((size_t)2*streams*sizeof(smst::ClipSeg));
-	// the device buffers sit as far behind a 16-byte boundary as the caller's do
-	unsigned char *s0 = static_cast<unsigned char *>(dSrc.p) + reinterpret_cast<uintptr_t>(src)%16, *d0 = static_cast<unsigned char *>(dDst.p) + reinterpret_cast<uintptr_t>(dst)%16;
-	if (srcBytes) hip(hipMemcpy(s0, src, srcBytes, hipMemcpyHostToDevice));
-	if (dstBytes) hip(hipMemcpy(d0, dst, dstBytes, hipMemcpyHostToDevice));
-	hip(hipMemcpy(dSegs.p, segments, (size_t)2*streams*sizeof(smst::ClipSeg), hipMemcpyHostToDevice));
-	if (counted) {
-		dOvers.alloc(pcmOversBytes(streams));
-		hip(hipMemcpy(dOvers.p, overs.data(), pcmOversBytes(streams), hipMemcpyHostToDevice));
-	}
-	const smst::ClipSeg *segs = static_cast<const smst::ClipSeg *>(dSegs.p);
-	if (dir == 0) smst::launchClipIn(format, s0, srcSS, srcInner, reinterpret_cast<float *>(d0), dstSS, dstInner, segs, streams, channels, most, nullptr);
-	else smst::launchClipOut(format, reinterpret_cast<const float *>(s0), srcSS, srcInner, d0, dstSS, dstInner, segs, streams, channels, most, static_cast<unsigned *>(dOvers.p), nullptr);
-	hip(hipGetLastError());
-	hip(hipStreamSynchronize(nullptr));
-	if (dstBytes) hip(hipMemcpy(dst, d0, dstBytes, hipMemcpyDeviceToHost));
-	if (counted) hip(hipMemcpy(overs.data(), dOvers.p, pcmOversBytes(streams), hipMemcpyDeviceToHost));
-	for (int s = 0; s < streams; ++s) {
-		if (clamped) clamped[s] = overs[2*s];
-		if (nans) nans[s] = overs[2*s + 1];
-	}
+	debugConvert("clip copy", streams, src, srcBytes, dst, dstBytes, segments, (size_t)2*streams*sizeof(smst::ClipSeg), nullptr, 0, dstFrames && (clamped || nans), clamped, nans,
+	             [&](unsigned char *s0, unsigned char *d0, const unsigned char *dSegs, const unsigned char *, unsigned *dOvers) {
+		const smst::ClipSeg *segs = reinterpret_cast<const smst::ClipSeg *>(dSegs);
+		if (dir == 0) smst::launchClipIn(format, s0, srcSS, srcInner, reinterpret_cast<float *>(d0), dstSS, dstInner, segs, streams, channels, most, nullptr);
+		else smst::launchClipOut(format, reinterpret_cast<const float *>(s0), srcSS, srcInner, d0, dstSS, dstInner, segs, streams, channels, most, dOvers, nullptr);
+	});
 	return SMST_OK;
 	SMST_CATCH
 }
@@ -930,18 +900,6 @@ static Batch *engineOf(const smst_stretch *h) {
 	return h->batch ? h->batch->engine.get() : nullptr;
 }
 static int slotOf(const smst_stretch *h) { return h->group ? h->slot : 0; }
-
-static void ensurePinned(float *&ptr, size_t &cap, size_t need, int device, long long &allocs) {
-	if (need <= cap) return;
-	++allocs;
-	hipSetDevice(device);
-	if (ptr) hipHostFree(ptr);
-	ptr = nullptr;
-	cap = 0;
-	const size_t want = need + need/8 + 1024;
-	if (hipHostMalloc(reinterpret_cast<void **>(&ptr), want*sizeof(float), hipHostMallocDefault) != hipSuccess) throw smst::Error("hipHostMalloc (pool staging) failed", true);
-	cap = want;
-}
 
 static const int kPoolFirstSlots = 4;
 
@@ -1058,19 +1016,19 @@ static bool runGroup(smst_pool *p, PoolGroup &g, smst_stretch *only) {
 	try {
 		hipSetDevice(e.device());
 		// gather -> one copy to the device
-		ensurePinned(g.hIn, g.hInCap, rows*maxIn, e.device(), p->allocEvents);
+		g.hIn.ensure(rows*maxIn, e.device(), p->allocEvents, "pool staging");
 		for (int s = 0; s < S; ++s) {
 			if (!g.active[s] || g.nIn[s] <= 0) continue;
 			const smst_stretch *m = g.slots[s];
 			for (int c = 0; c < C; ++c) std::copy(m->reqIn[c], m->reqIn[c] + g.nIn[s], g.hIn + row(s, c)*maxIn);
 		}
-		ensureStage(b->dIn, b->inCap, rows*maxIn, e.device(), b->stagingAllocs);
-		ensureStage(b->dOut, b->outCap, rows*maxOut, e.device(), b->stagingAllocs);
+		ensureStage(b, b->dIn, rows*maxIn);
+		ensureStage(b, b->dOut, rows*maxOut);
 		if (hipMemcpyAsync(b->dIn, g.hIn, rows*maxIn*sizeof(float), hipMemcpyHostToDevice, e.stream()) != hipSuccess) throw smst::Error("hipMemcpyAsync (H2D) failed", true);
 		if (hipStreamSynchronize(e.stream()) != hipSuccess) throw smst::Error("hipStreamSynchronize failed", true); // (the silence gate reads the input on another stream)
 		e.process(b->dIn, only ? 0 : (long long)C*maxIn, maxIn, g.nIn.data(), b->dOut, only ? 0 : (long long)C*maxOut, maxOut, g.nOut.data(), all ? nullptr : g.active.data());
 		// one copy back -> scatter
-		ensurePinned(g.hOut, g.hOutCap, rows*maxOut, e.device(), p->allocEvents);
+		g.hOut.ensure(rows*maxOut, e.device(), p->allocEvents, "pool staging");
 		if (hipMemcpyAsync(g.hOut, b->dOut, rows*maxOut*sizeof(float), hipMemcpyDeviceToHost, e.stream()) != hipSuccess) throw smst::Error("hipMemcpyAsync (D2H) failed", true);
 		if (hipStreamSynchronize(e.stream()) != hipSuccess) throw smst::Error("hipStreamSynchronize failed", true);
 		for (int s = 0; s < S; ++s) {
@@ -1337,7 +1295,7 @@ static int memberSeek(smst_stretch *h, const float *const *inputs, int n, double
 	std::vector<double> rates(S, 1.0);
 	std::vector<unsigned char> mask(S, 0);
 	counts[h->slot] = n; rates[h->slot] = rate; mask[h->slot] = 1;
-	ensureStage(b->dIn, b->inCap, (size_t)C*len, e.device(), b->stagingAllocs);
+	ensureStage(b, b->dIn, (size_t)C*len);
 	hipSetDevice(e.device());
 	if (hipMemcpy(b->dIn, in.data(), (size_t)C*len*sizeof(float), hipMemcpyHostToDevice) != hipSuccess) throw smst::Error("hipMemcpy (H2D) failed", true);
 	e.seek(b->dIn, 0, len, counts.data(), rates.data(), mask.data());
@@ -1355,7 +1313,7 @@ static int memberFlush(smst_stretch *h, float *const *outputs, int n, float rate
 	std::vector<float> rates(S, 0.0f);
 	std::vector<unsigned char> mask(S, 0);
 	counts[h->slot] = n; rates[h->slot] = rate; mask[h->slot] = 1;
-	ensureStage(b->dOut, b->outCap, (size_t)C*len, e.device(), b->stagingAllocs);
+	ensureStage(b, b->dOut, (size_t)C*len);
 	e.flush(b->dOut, 0, len, counts.data(), rates.data(), mask.data());
 	e.synchronize();
 	std::vector<float> out((size_t)C*len);

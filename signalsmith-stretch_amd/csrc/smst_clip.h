@@ -4,7 +4,7 @@
 // fp32 images of its own in which every stream's stage begins at one column, and the two kernels here move the clips: per stream two
 // segments (ClipSeg, smst_device.h) of `count` frames from frame `src` of the source to frame `dst` of the destination.
 //   kClipIn<T>   the caller's frames of format T -> the input image            (pcmTileIn of smst_pcm.h on a run that begins at the segment)
-//   kClipOut<T>  the output image -> the caller's frames, overs counted        (pcmTileOut; a "zeros" segment has no source)
+//   kClipOut<T, Dith>  the output image -> the caller's frames, overs counted  (pcmTileOut; a "zeros" segment has no source; Dith: dithered)
 //   kClipPlanar  planar fp32 -> planar fp32, either direction                  (the caller's buffer is planar itself)
 // Included by smst_state.hip only, behind smst_pcm.h: the conversion rule, the tiling of a run and the overs scheme are the ones defined there.
 //
@@ -34,30 +34,20 @@ template <typename T> __global__ __launch_bounds__(256) void kClipIn(const T *__
 	             blockIdx.x, C, reinterpret_cast<float *>(smemRaw));
 }
 
-// the planar image -> frames of format T.  overs (may be null): [S][2] counters as kPcmOut's (a run of zeros adds nothing: 0.0 has a code in every format)
-template <typename T> __global__ __launch_bounds__(256) void kClipOut(const float *__restrict__ image, long long imageStreamStride, long long imageChannelStride,
-		T *__restrict__ out, long long outStreamStride, long long outFrameStride, const ClipSeg *__restrict__ segs, int C, unsigned *__restrict__ overs) {
-	extern __shared__ __attribute__((aligned(16))) unsigned char smemRaw[];
-	const int s = blockIdx.y;
-	const ClipSeg g = segs[2*s + blockIdx.z];
-	if (g.count < 1) return;
-	const float *src = g.zeros ? nullptr : image + (size_t)s*imageStreamStride + g.src;
-	unsigned over;
-	if (!pcmTileOut<T>(src, imageChannelStride, out + (size_t)s*outStreamStride + (size_t)g.dst*outFrameStride, outFrameStride, g.count, blockIdx.x, C, reinterpret_cast<float *>(smemRaw), over)) return;
-	pcmAddOvers(overs, s, over);
-}
-// ... dithered (int16 / int24): the frame index of a segment's first frame is its place in the clip, g.dst -- dither[s] gives the stream's
-// mode and hash only --, so a clip's codes do not depend on where its two segments meet; a run of zeros stays the code of 0.0
-template <typename T> __global__ __launch_bounds__(256) void kClipOutDithered(const float *__restrict__ image, long long imageStreamStride, long long imageChannelStride,
+// the planar image -> frames of format T.  overs (may be null): [S][2] counters as kPcmOut's (a run of zeros adds nothing: 0.0 has a code in every format).
+// Dith (int16 / int24): the frame index of a segment's first frame is its place in the clip, g.dst -- dither[s] gives the stream's mode and
+// hash only --, so a clip's codes do not depend on where its two segments meet; a run of zeros stays the code of 0.0
+template <typename T, bool Dith> __global__ __launch_bounds__(256) void kClipOut(const float *__restrict__ image, long long imageStreamStride, long long imageChannelStride,
 		T *__restrict__ out, long long outStreamStride, long long outFrameStride, const ClipSeg *__restrict__ segs, int C, unsigned *__restrict__ overs, const PcmDither *__restrict__ dither) {
 	extern __shared__ __attribute__((aligned(16))) unsigned char smemRaw[];
 	const int s = blockIdx.y;
 	const ClipSeg g = segs[2*s + blockIdx.z];
 	if (g.count < 1) return;
 	const float *src = g.zeros ? nullptr : image + (size_t)s*imageStreamStride + g.src;
-	const PcmDither dp{dither[s].mode, dither[s].h, unsigned(g.dst), 0u};
+	PcmDither dp{0u, 0u, 0u, 0u};
+	if constexpr (Dith) dp = PcmDither{dither[s].mode, dither[s].h, unsigned(g.dst), 0u};
 	unsigned over;
-	if (!pcmTileOut<T, true>(src, imageChannelStride, out + (size_t)s*outStreamStride + (size_t)g.dst*outFrameStride, outFrameStride, g.count, blockIdx.x, C, reinterpret_cast<float *>(smemRaw), over, dp)) return;
+	if (!pcmTileOut<T, Dith>(src, imageChannelStride, out + (size_t)s*outStreamStride + (size_t)g.dst*outFrameStride, outFrameStride, g.count, blockIdx.x, C, reinterpret_cast<float *>(smemRaw), over, dp)) return;
 	pcmAddOvers(overs, s, over);
 }
 
@@ -86,17 +76,13 @@ __device__ inline void clipRowTile(const float *__restrict__ src, float *__restr
 		}
 		__syncthreads();
 	}
-	float *p = dst + e0;
-	if (tid < head) p[tid] = src ? lds[shift + tid] : 0.0f;
-	const int nGroups = (count - head)/4;
-	for (int g = tid; g < nGroups; g += 256) {
-		const int e = head + 4*g;
-		PcmWord4 v;
-		for (int k = 0; k < 4; ++k) v[k] = src ? unsigned(__float_as_int(lds[shift + e + k])) : 0u;
-		*reinterpret_cast<PcmWord4 *>(p + e) = v;
-	}
-	const int done = head + 4*nGroups;
-	if (tid < count - done) p[done + tid] = src ? lds[shift + done + tid] : 0.0f;
+	pcmWalk(dst, 1, e0, count, head, 1, // (one channel, dense: dst's groups of 4 floats)
+		[&](float &x, int i, const PcmPlace &) { x = src ? lds[shift + i] : 0.0f; },
+		[&](float *p, int i, const PcmPlace &) {
+			PcmWord4 v;
+			for (int k = 0; k < 4; ++k) v[k] = src ? unsigned(__float_as_int(lds[shift + i + k])) : 0u;
+			*reinterpret_cast<PcmWord4 *>(p) = v;
+		});
 	if (src) __syncthreads(); // (the next row's words go into the same image)
 }
 
@@ -114,54 +100,36 @@ __global__ __launch_bounds__(256) void kClipPlanar(const float *__restrict__ src
 	}
 }
 
+// format 0: the caller's buffer is planar fp32 itself (kClipPlanar, either direction); else pcmDispatch of smst_pcm.h
 static void launchClipPlanar(const float *src, long long srcSS, long long srcCS, float *dst, long long dstSS, long long dstCS, const ClipSeg *segs, int S, int C, int maxCount, hipStream_t st) {
 	hipLaunchKernelGGL(kClipPlanar, dim3(divUp(maxCount, kClipTileFloats), S, 2), dim3(256), clipPlanarLdsBytes(), st, src, srcSS, srcCS, dst, dstSS, dstCS, segs, C);
-}
-template <typename T> static void launchClipInAs(dim3 grid, int C, hipStream_t st, const void *in, long long inSS, long long inFS, float *image, long long imageSS, long long imageCS, const ClipSeg *segs) {
-	hipLaunchKernelGGL(kClipIn<T>, grid, dim3(256), pcmLdsBytes(C), st, static_cast<const T *>(in), inSS, inFS, image, imageSS, imageCS, segs, C);
-}
-template <typename T> static void launchClipOutAs(dim3 grid, int C, hipStream_t st, const float *image, long long imageSS, long long imageCS, void *out, long long outSS, long long outFS,
-		const ClipSeg *segs, unsigned *overs) {
-	hipLaunchKernelGGL(kClipOut<T>, grid, dim3(256), pcmLdsBytes(C), st, image, imageSS, imageCS, static_cast<T *>(out), outSS, outFS, segs, C, overs);
 }
 void launchClipIn(int format, const void *in, long long inSS, long long inInner, float *image, long long imageSS, long long imageCS, const ClipSeg *segs, int S, int C, int maxCount, hipStream_t st) {
 	if (maxCount < 1) return;
 	const dim3 grid(divUp(maxCount, kPcmTileFrames), S, 2);
-	switch (format) {
-	case 0: launchClipPlanar(static_cast<const float *>(in), inSS, inInner, image, imageSS, imageCS, segs, S, C, maxCount, st); break;
-	case kPcmS16: launchClipInAs<int16_t>(grid, C, st, in, inSS, inInner, image, imageSS, imageCS, segs); break;
-	case kPcmF32: launchClipInAs<float>(grid, C, st, in, inSS, inInner, image, imageSS, imageCS, segs); break;
-	case kPcmS24: launchClipInAs<PcmS24>(grid, C, st, in, inSS, inInner, image, imageSS, imageCS, segs); break;
-	case kPcmS32: launchClipInAs<int32_t>(grid, C, st, in, inSS, inInner, image, imageSS, imageCS, segs); break;
-	case kPcmF16: launchClipInAs<PcmF16>(grid, C, st, in, inSS, inInner, image, imageSS, imageCS, segs); break;
-	default: throw std::invalid_argument("unknown PCM format");
-	}
+	if (format == 0) launchClipPlanar(static_cast<const float *>(in), inSS, inInner, image, imageSS, imageCS, segs, S, C, maxCount, st);
+	else pcmDispatch(format, false, [&](auto tag, auto) {
+		typedef typename decltype(tag)::type T;
+		hipLaunchKernelGGL(kClipIn<T>, grid, dim3(256), pcmLdsBytes(C), st, static_cast<const T *>(in), inSS, inInner, image, imageSS, imageCS, segs, C);
+	});
 	countLaunch(LK_CLIP_IN);
-}
-template <typename T> static void launchClipOutDitheredAs(dim3 grid, int C, hipStream_t st, const float *image, long long imageSS, long long imageCS, void *out, long long outSS, long long outFS,
-		const ClipSeg *segs, unsigned *overs, const PcmDither *dither) {
-	hipLaunchKernelGGL(kClipOutDithered<T>, grid, dim3(256), pcmDitherLdsBytes(C), st, image, imageSS, imageCS, static_cast<T *>(out), outSS, outFS, segs, C, overs, dither);
 }
 void launchClipOut(int format, const float *image, long long imageSS, long long imageCS, void *out, long long outSS, long long outInner, const ClipSeg *segs, int S, int C, int maxCount,
                    unsigned *overs, hipStream_t st, const PcmDither *dither) {
 	if (maxCount < 1) return;
 	const dim3 grid(divUp(maxCount, kPcmTileFrames), S, 2);
-	if (dither && (format == kPcmS16 || format == kPcmS24)) {
-		if (format == kPcmS16) launchClipOutDitheredAs<int16_t>(grid, C, st, image, imageSS, imageCS, out, outSS, outInner, segs, overs, dither);
-		else launchClipOutDitheredAs<PcmS24>(grid, C, st, image, imageSS, imageCS, out, outSS, outInner, segs, overs, dither);
-		countLaunch(LK_CLIP_OUT_DITHERED);
+	if (format == 0) {
+		launchClipPlanar(image, imageSS, imageCS, static_cast<float *>(out), outSS, outInner, segs, S, C, maxCount, st);
+		countLaunch(LK_CLIP_OUT);
 		return;
 	}
-	switch (format) {
-	case 0: launchClipPlanar(image, imageSS, imageCS, static_cast<float *>(out), outSS, outInner, segs, S, C, maxCount, st); break;
-	case kPcmS16: launchClipOutAs<int16_t>(grid, C, st, image, imageSS, imageCS, out, outSS, outInner, segs, overs); break;
-	case kPcmF32: launchClipOutAs<float>(grid, C, st, image, imageSS, imageCS, out, outSS, outInner, segs, overs); break;
-	case kPcmS24: launchClipOutAs<PcmS24>(grid, C, st, image, imageSS, imageCS, out, outSS, outInner, segs, overs); break;
-	case kPcmS32: launchClipOutAs<int32_t>(grid, C, st, image, imageSS, imageCS, out, outSS, outInner, segs, overs); break;
-	case kPcmF16: launchClipOutAs<PcmF16>(grid, C, st, image, imageSS, imageCS, out, outSS, outInner, segs, overs); break;
-	default: throw std::invalid_argument("unknown PCM format");
-	}
-	countLaunch(LK_CLIP_OUT);
+	pcmDispatch(format, dither != nullptr, [&](auto tag, auto dithered) {
+		typedef typename decltype(tag)::type T;
+		constexpr bool Dith = decltype(dithered)::value;
+		hipLaunchKernelGGL((kClipOut<T, Dith>), grid, dim3(256), Dith ? pcmDitherLdsBytes(C) : pcmLdsBytes(C), st, image, imageSS, imageCS, static_cast<T *>(out), outSS, outInner, segs, C,
+		                   overs, dither);
+		countLaunch(Dith ? LK_CLIP_OUT_DITHERED : LK_CLIP_OUT);
+	});
 }
 
 } // namespace smst

@@ -32,6 +32,7 @@
 #pragma once
 #include <cstdint>
 #include <stdexcept>
+#include <type_traits>
 
 namespace smst {
 
@@ -40,35 +41,26 @@ struct PcmS24 { unsigned char b[3]; };                                   // one 
 typedef _Float16 PcmF16;
 constexpr unsigned kPcmOverClamped = 1u, kPcmOverNan = 1u << 16;
 
-// Per format: a group of G elements is W 16-byte words; lead(address) = the elements in front of the first group boundary;
-// over(v) = what encode(v) adds to a lane's overs word.
+// Per format: a group of G elements is W 16-byte words; lead(address) = the elements in front of the first group boundary.  The way out is
+// one quantiser: t = scaled(v) is the value that is rounded (v*kScale for the integer formats, v itself for the float ones; a dithered
+// element is v*kScale + d instead, NaN iff v is: d is finite), encode(t) its code, over(t) what encode(t) adds to a lane's overs word,
+// pack(t, w) the codes of a group.
 template <typename T> struct PcmFormat;
 template <typename T, int G> __device__ inline int pcmLeadAligned(uintptr_t address) { return (G - int((address/sizeof(T))%G))%G; }
 template <> struct PcmFormat<int16_t> {
 	static constexpr int G = 8, W = 1;
+	static constexpr float kScale = 32768.0f;
 	static __device__ inline int lead(uintptr_t a) { return pcmLeadAligned<int16_t, G>(a); }
 	static __device__ inline float decode(int16_t v) { return float(v)*(1.0f/32768.0f); }
-	static __device__ inline int16_t encode(float v) {
-		const float q = fminf(fmaxf(roundf(v*32768.0f), -32768.0f), 32767.0f);
-		return (v != v) ? int16_t(0) : int16_t(int(q));
-	}
-	static __device__ inline unsigned over(float v) {
-		const float r = roundf(v*32768.0f);
-		return (v != v) ? kPcmOverNan : (r > 32767.0f || r < -32768.0f) ? kPcmOverClamped : 0u;
-	}
-	// the dithered forms take t = v*kScale + d (NaN iff v is: d is finite)
-	static constexpr float kScale = 32768.0f;
-	static __device__ inline unsigned codeScaled(float t) {
+	static __device__ inline float scaled(float v) { return v*kScale; }
+	static __device__ inline unsigned code(float t) { // the 16 bits
 		const float q = fminf(fmaxf(roundf(t), -32768.0f), 32767.0f);
 		return (t != t) ? 0u : (unsigned(int(q)) & 0xffffu);
 	}
-	static __device__ inline int16_t encodeScaled(float t) { return int16_t(uint16_t(codeScaled(t))); }
-	static __device__ inline unsigned overScaled(float t) {
+	static __device__ inline int16_t encode(float t) { return int16_t(uint16_t(code(t))); }
+	static __device__ inline unsigned over(float t) {
 		const float r = roundf(t);
 		return (t != t) ? kPcmOverNan : (r > 32767.0f || r < -32768.0f) ? kPcmOverClamped : 0u;
-	}
-	static __device__ inline void packScaled(const float *t, PcmWord4 *w) {
-		for (int k = 0; k < 4; ++k) w[0][k] = codeScaled(t[2*k]) | (codeScaled(t[2*k + 1]) << 16);
 	}
 	static __device__ inline void unpack(const PcmWord4 *w, float *x) {
 		for (int k = 0; k < 4; ++k) {
@@ -76,42 +68,45 @@ template <> struct PcmFormat<int16_t> {
 			x[2*k + 1] = decode(int16_t(w[0][k] >> 16));
 		}
 	}
-	static __device__ inline void pack(const float *x, PcmWord4 *w) {
-		for (int k = 0; k < 4; ++k) w[0][k] = unsigned(uint16_t(encode(x[2*k]))) | (unsigned(uint16_t(encode(x[2*k + 1]))) << 16);
+	static __device__ inline void pack(const float *t, PcmWord4 *w) {
+		for (int k = 0; k < 4; ++k) w[0][k] = code(t[2*k]) | (code(t[2*k + 1]) << 16);
 	}
 };
 template <> struct PcmFormat<float> {
 	static constexpr int G = 4, W = 1;
 	static __device__ inline int lead(uintptr_t a) { return pcmLeadAligned<float, G>(a); }
 	static __device__ inline float decode(float v) { return v; }
-	static __device__ inline float encode(float v) { return v; }
-	static __device__ inline unsigned over(float v) { return (v != v) ? kPcmOverNan : 0u; }
+	static __device__ inline float scaled(float v) { return v; }
+	static __device__ inline float encode(float t) { return t; }
+	static __device__ inline unsigned over(float t) { return (t != t) ? kPcmOverNan : 0u; }
 	static __device__ inline void unpack(const PcmWord4 *w, float *x) {
 		for (int k = 0; k < 4; ++k) x[k] = __int_as_float(int(w[0][k]));
 	}
-	static __device__ inline void pack(const float *x, PcmWord4 *w) {
-		for (int k = 0; k < 4; ++k) w[0][k] = unsigned(__float_as_int(x[k]));
+	static __device__ inline void pack(const float *t, PcmWord4 *w) {
+		for (int k = 0; k < 4; ++k) w[0][k] = unsigned(__float_as_int(t[k]));
 	}
 };
 template <> struct PcmFormat<int32_t> {
 	static constexpr int G = 4, W = 1;
+	static constexpr float kScale = 2147483648.0f;
 	static __device__ inline int lead(uintptr_t a) { return pcmLeadAligned<int32_t, G>(a); }
 	static __device__ inline float decode(int32_t v) { return float(v)*(1.0f/2147483648.0f); }
+	static __device__ inline float scaled(float v) { return v*kScale; }
 	// the clamp acts on the float (2147483520 is the largest one below 2^31): no float outside int's range is ever converted
-	static __device__ inline int32_t encode(float v) {
-		const float r = roundf(v*2147483648.0f);
+	static __device__ inline int32_t encode(float t) {
+		const float r = roundf(t);
 		const int32_t q = int32_t(fminf(fmaxf(r, -2147483648.0f), 2147483520.0f));
-		return (v != v) ? 0 : (r >= 2147483648.0f ? 2147483647 : q);
+		return (t != t) ? 0 : (r >= 2147483648.0f ? 2147483647 : q);
 	}
-	static __device__ inline unsigned over(float v) {
-		const float r = roundf(v*2147483648.0f);
-		return (v != v) ? kPcmOverNan : (r >= 2147483648.0f || r < -2147483648.0f) ? kPcmOverClamped : 0u;
+	static __device__ inline unsigned over(float t) {
+		const float r = roundf(t);
+		return (t != t) ? kPcmOverNan : (r >= 2147483648.0f || r < -2147483648.0f) ? kPcmOverClamped : 0u;
 	}
 	static __device__ inline void unpack(const PcmWord4 *w, float *x) {
 		for (int k = 0; k < 4; ++k) x[k] = decode(int32_t(w[0][k]));
 	}
-	static __device__ inline void pack(const float *x, PcmWord4 *w) {
-		for (int k = 0; k < 4; ++k) w[0][k] = unsigned(encode(x[k]));
+	static __device__ inline void pack(const float *t, PcmWord4 *w) {
+		for (int k = 0; k < 4; ++k) w[0][k] = unsigned(encode(t[k]));
 	}
 };
 template <> struct PcmFormat<PcmF16> {
@@ -120,11 +115,12 @@ template <> struct PcmFormat<PcmF16> {
 	static __device__ inline float fromBits(unsigned bits) { const uint16_t b = uint16_t(bits); PcmF16 h; __builtin_memcpy(&h, &b, 2); return float(h); }
 	static __device__ inline unsigned toBits(float v) { const PcmF16 h = PcmF16(v); uint16_t b; __builtin_memcpy(&b, &h, 2); return b; }
 	static __device__ inline float decode(PcmF16 v) { return float(v); }
-	static __device__ inline PcmF16 encode(float v) { return PcmF16(v); }
+	static __device__ inline float scaled(float v) { return v; }
+	static __device__ inline PcmF16 encode(float t) { return PcmF16(t); }
 	// 65520 is the tie between 65504 and 2^16: to even, which is +-inf
-	static __device__ inline unsigned over(float v) {
-		const float a = fabsf(v);
-		return (v != v) ? kPcmOverNan : (a >= 65520.0f && a <= 3.402823466e38f) ? kPcmOverClamped : 0u;
+	static __device__ inline unsigned over(float t) {
+		const float a = fabsf(t);
+		return (t != t) ? kPcmOverNan : (a >= 65520.0f && a <= 3.402823466e38f) ? kPcmOverClamped : 0u;
 	}
 	static __device__ inline void unpack(const PcmWord4 *w, float *x) {
 		for (int k = 0; k < 4; ++k) {
@@ -132,43 +128,29 @@ template <> struct PcmFormat<PcmF16> {
 			x[2*k + 1] = fromBits(w[0][k] >> 16);
 		}
 	}
-	static __device__ inline void pack(const float *x, PcmWord4 *w) {
-		for (int k = 0; k < 4; ++k) w[0][k] = toBits(x[2*k]) | (toBits(x[2*k + 1]) << 16);
+	static __device__ inline void pack(const float *t, PcmWord4 *w) {
+		for (int k = 0; k < 4; ++k) w[0][k] = toBits(t[2*k]) | (toBits(t[2*k + 1]) << 16);
 	}
 };
 template <> struct PcmFormat<PcmS24> {
 	static constexpr int G = 16, W = 3;
+	static constexpr float kScale = 8388608.0f;
 	// the k < 16 with address + 3k = 0 mod 16: k = -address*11, as 3*11 = 1 mod 16
 	static __device__ inline int lead(uintptr_t a) { return int(((0 - a) & 15u)*11u & 15u); }
 	static __device__ inline float fromLow24(unsigned v) { return float(int(v << 8) >> 8)*(1.0f/8388608.0f); } // (bits 24..31 of v are ignored)
-	static __device__ inline unsigned code(float v) { // the 24 bits
-		const float q = fminf(fmaxf(roundf(v*8388608.0f), -8388608.0f), 8388607.0f);
-		return (v != v) ? 0u : (unsigned(int(q)) & 0xffffffu);
-	}
 	static __device__ inline float decode(PcmS24 v) { return fromLow24(unsigned(v.b[0]) | (unsigned(v.b[1]) << 8) | (unsigned(v.b[2]) << 16)); }
-	static __device__ inline PcmS24 encode(float v) {
-		const unsigned q = code(v);
-		PcmS24 r;
-		r.b[0] = (unsigned char)(q & 0xffu); r.b[1] = (unsigned char)((q >> 8) & 0xffu); r.b[2] = (unsigned char)(q >> 16);
-		return r;
-	}
-	static __device__ inline unsigned over(float v) {
-		const float r = roundf(v*8388608.0f);
-		return (v != v) ? kPcmOverNan : (r > 8388607.0f || r < -8388608.0f) ? kPcmOverClamped : 0u;
-	}
-	// the dithered forms take t = v*kScale + d (NaN iff v is: d is finite)
-	static constexpr float kScale = 8388608.0f;
-	static __device__ inline unsigned codeScaled(float t) {
+	static __device__ inline float scaled(float v) { return v*kScale; }
+	static __device__ inline unsigned code(float t) { // the 24 bits
 		const float q = fminf(fmaxf(roundf(t), -8388608.0f), 8388607.0f);
 		return (t != t) ? 0u : (unsigned(int(q)) & 0xffffffu);
 	}
-	static __device__ inline PcmS24 encodeScaled(float t) {
-		const unsigned q = codeScaled(t);
+	static __device__ inline PcmS24 encode(float t) {
+		const unsigned q = code(t);
 		PcmS24 r;
 		r.b[0] = (unsigned char)(q & 0xffu); r.b[1] = (unsigned char)((q >> 8) & 0xffu); r.b[2] = (unsigned char)(q >> 16);
 		return r;
 	}
-	static __device__ inline unsigned overScaled(float t) {
+	static __device__ inline unsigned over(float t) {
 		const float r = roundf(t);
 		return (t != t) ? kPcmOverNan : (r > 8388607.0f || r < -8388608.0f) ? kPcmOverClamped : 0u;
 	}
@@ -184,20 +166,10 @@ template <> struct PcmFormat<PcmS24> {
 			x[4*q + 3] = fromLow24(d2 >> 8);
 		}
 	}
-	static __device__ inline void pack(const float *x, PcmWord4 *w) {
+	static __device__ inline void pack(const float *t, PcmWord4 *w) {
 		unsigned d[12];
 		for (int q = 0; q < 4; ++q) {
-			const unsigned a = code(x[4*q]), b = code(x[4*q + 1]), c = code(x[4*q + 2]), e = code(x[4*q + 3]);
-			d[3*q] = a | (b << 24);
-			d[3*q + 1] = (b >> 8) | (c << 16);
-			d[3*q + 2] = (c >> 16) | (e << 8);
-		}
-		for (int k = 0; k < 12; ++k) w[k >> 2][k & 3] = d[k];
-	}
-	static __device__ inline void packScaled(const float *t, PcmWord4 *w) {
-		unsigned d[12];
-		for (int q = 0; q < 4; ++q) {
-			const unsigned a = codeScaled(t[4*q]), b = codeScaled(t[4*q + 1]), c = codeScaled(t[4*q + 2]), e = codeScaled(t[4*q + 3]);
+			const unsigned a = code(t[4*q]), b = code(t[4*q + 1]), c = code(t[4*q + 2]), e = code(t[4*q + 3]);
 			d[3*q] = a | (b << 24);
 			d[3*q + 1] = (b >> 8) | (c << 16);
 			d[3*q + 2] = (c >> 16) | (e << 8);
@@ -225,9 +197,9 @@ __device__ inline float pcmDitherValue(unsigned mode, unsigned key, unsigned lon
 	return u0 - pcmDitherUnit(pcmMix(pcmMix(key ^ unsigned(m)) + 0x85EBCA6Bu*(2u*unsigned(m >> 32) + 1u)));
 }
 // Where element i of a tile lies: frame `frame` behind the tile's first frame, channel c.  next(): the element behind it.
-struct PcmDitherPlace {
+struct PcmPlace {
 	unsigned frame, c;
-	__device__ inline PcmDitherPlace(int lag, int i, int C) : frame(unsigned(lag + i)/unsigned(C)), c(unsigned(lag + i) - frame*unsigned(C)) {}
+	__device__ inline PcmPlace(int lag, int i, int C) : frame(unsigned(lag + i)/unsigned(C)), c(unsigned(lag + i) - frame*unsigned(C)) {}
 	__device__ inline void next(int C) { if (++c == unsigned(C)) { c = 0; ++frame; } }
 };
 
@@ -244,39 +216,52 @@ template <typename T> __device__ inline bool pcmTileRun(const T *run, long long 
 	return true;
 }
 
+// The walk over those elements, in either direction (T may be const): with frameStride == C the `head` elements one by one, the whole groups
+// of G, the elements behind the last group one by one; else every element by itself.  element(x, i, at): x is element i of the tile, at its
+// PcmPlace; group(p, i, at): p points at the W aligned 16-byte words of the G elements from i on.  Every lane of the workgroup calls it.
+template <typename T, typename Element, typename Group> __device__ inline void pcmWalk(T *run, long long frameStride, long long e0, int count, int head, int C, Element element, Group group) {
+	constexpr int G = PcmFormat<typename std::remove_const<T>::type>::G;
+	const int tid = threadIdx.x;
+	const long long f0 = e0/C; // (a tile may begin and end inside a frame)
+	const int lag = int(e0 - f0*C); // elements of the tile's first frame that lie in front of the tile
+	if (frameStride == C) {
+		T *p = run + e0;
+		if (tid < head) element(p[tid], tid, PcmPlace(lag, tid, C));
+		const int nGroups = (count - head)/G;
+		for (int g = tid; g < nGroups; g += 256) {
+			const int e = head + g*G;
+			group(p + e, e, PcmPlace(lag, e, C));
+		}
+		const int done = head + nGroups*G;
+		if (tid < count - done) element(p[done + tid], done + tid, PcmPlace(lag, done + tid, C));
+	} else {
+		for (int i = tid; i < count; i += 256) {
+			const PcmPlace at(lag, i, C);
+			element(run[(f0 + at.frame)*frameStride + at.c], i, at);
+		}
+	}
+}
+
 // One tile of a run of frames -> the rows of a planar fp32 image.  run: the run's first frame; dst: the sample of channel 0 that frame goes to.
 // Every lane of the workgroup calls it (kPcmIn; kClipIn of smst_clip.h for a run that begins at a per-stream offset).
 template <typename T> __device__ inline void pcmTileIn(const T *__restrict__ run, long long inFrameStride, long long frames, float *__restrict__ out, long long outChannelStride,
 		int t, int C, float *tile) {
-	constexpr int G = PcmFormat<T>::G, W = PcmFormat<T>::W;
+	typedef PcmFormat<T> F;
 	const int tid = threadIdx.x;
-	const bool dense = inFrameStride == C;
 	long long e0;
 	int count, head;
-	if (!pcmTileRun<T>(run, frames*C, dense, t, C, e0, count, head)) return;
-	if (dense) {
-		const T *p = run + e0;
-		if (tid < head) tile[pcmSlot(tid)] = PcmFormat<T>::decode(p[tid]);
-		const int nGroups = (count - head)/G;
-		for (int g = tid; g < nGroups; g += 256) {
-			const int e = head + g*G;
-			const PcmWord4 *src = reinterpret_cast<const PcmWord4 *>(p + e);
-			PcmWord4 w[W];
-			for (int k = 0; k < W; ++k) w[k] = src[k];
-			float x[G];
-			PcmFormat<T>::unpack(w, x);
-			for (int k = 0; k < G; ++k) tile[pcmSlot(e + k)] = x[k];
-		}
-		const int done = head + nGroups*G;
-		if (tid < count - done) tile[pcmSlot(done + tid)] = PcmFormat<T>::decode(p[done + tid]);
-	} else {
-		for (int i = tid; i < count; i += 256) {
-			const long long e = e0 + i, f = e/C;
-			tile[pcmSlot(i)] = PcmFormat<T>::decode(run[f*inFrameStride + (e - f*C)]);
-		}
-	}
+	if (!pcmTileRun<T>(run, frames*C, inFrameStride == C, t, C, e0, count, head)) return;
+	pcmWalk(run, inFrameStride, e0, count, head, C,
+		[&](const T &x, int i, const PcmPlace &) { tile[pcmSlot(i)] = F::decode(x); },
+		[&](const T *p, int i, const PcmPlace &) {
+			PcmWord4 w[F::W];
+			for (int k = 0; k < F::W; ++k) w[k] = reinterpret_cast<const PcmWord4 *>(p)[k];
+			float x[F::G];
+			F::unpack(w, x);
+			for (int k = 0; k < F::G; ++k) tile[pcmSlot(i + k)] = x[k];
+		});
 	__syncthreads();
-	const long long f0 = e0/C; // (a tile may begin and end inside a frame: each element is moved by the tile that holds it)
+	const long long f0 = e0/C; // (each element is moved by the tile that holds it)
 	const int nFrames = int((e0 + count - 1)/C - f0) + 1;
 	float *dst = out + f0;
 	for (int c = 0; c < C; ++c) {
@@ -290,16 +275,16 @@ template <typename T> __device__ inline void pcmTileIn(const T *__restrict__ run
 
 // The reverse: one tile of the rows of a planar fp32 image -> a run of frames.  in: the sample of channel 0 that goes to the run's first frame,
 // or null for a run of zeros (the code of 0.0).  false: the tile lies behind the run; else `over` has this lane's overs word (see "Overs").
-// Dith (int16 / int24): the run's elements are quantised as roundf(v*scale + d), d the dither of the stream's entry dp for the frame index
-// first + f (a run of zeros and a stream of mode 0 get d = 0: today's codes); an element counts as clamped when the DITHERED value was.
-template <typename T, bool Dith = false> __device__ inline bool pcmTileOut(const float *__restrict__ in, long long inChannelStride, T *__restrict__ run, long long outFrameStride, long long frames,
-		int t, int C, float *tile, unsigned &over, PcmDither dp = PcmDither{0u, 0u, 0u, 0u}) {
-	constexpr int G = PcmFormat<T>::G, W = PcmFormat<T>::W;
+// Dith (int16 / int24) decides how an element's rounded value is formed -- v*scale + d, d the dither of the stream's entry dp for the frame
+// index first + f (a run of zeros and a stream of mode 0 get d = 0: the undithered codes), so that an element counts as clamped when the
+// DITHERED value was -- and that the 16 key words behind the image are filled; nothing else.
+template <typename T, bool Dith> __device__ inline bool pcmTileOut(const float *__restrict__ in, long long inChannelStride, T *__restrict__ run, long long outFrameStride, long long frames,
+		int t, int C, float *tile, unsigned &over, PcmDither dp) {
+	typedef PcmFormat<T> F;
 	const int tid = threadIdx.x;
-	const bool dense = outFrameStride == C;
 	long long e0;
 	int count, head;
-	if (!pcmTileRun<T>(run, frames*C, dense, t, C, e0, count, head)) return false;
+	if (!pcmTileRun<T>(run, frames*C, outFrameStride == C, t, C, e0, count, head)) return false;
 	const long long f0 = e0/C;
 	const int nFrames = int((e0 + count - 1)/C - f0) + 1;
 	const float *src = in ? in + f0 : nullptr;
@@ -310,70 +295,26 @@ template <typename T, bool Dith = false> __device__ inline bool pcmTileOut(const
 			if (i >= 0 && i < count) tile[pcmSlot(i)] = src ? src[(size_t)c*inChannelStride + fl] : 0.0f;
 		}
 	}
-	if constexpr (Dith) {
-		const unsigned mode = src ? dp.mode : 0u;
-		unsigned *keys = reinterpret_cast<unsigned *>(tile) + pcmLdsWords(C);
-		if (mode && tid < C) keys[tid] = pcmMix(dp.h + 0x9E3779B9u*unsigned(tid + 1));
-		__syncthreads();
-		over = 0;
-		const int lag = int(e0 - f0*C); // elements of the tile's first frame that lie in front of the tile
-		const unsigned long long n0 = (((unsigned long long)dp.nHi << 32) | dp.nLo) + (unsigned long long)f0;
-		constexpr float scale = PcmFormat<T>::kScale;
-		auto scaled = [&](int i, const PcmDitherPlace &at) { // element i of the tile, times the scale, plus its dither
-			const float v = tile[pcmSlot(i)];
-			return mode ? v*scale + pcmDitherValue(mode, keys[at.c], n0 + at.frame) : v*scale;
-		};
-		if (dense) {
-			T *p = run + e0;
-			if (tid < head) { const float q = scaled(tid, PcmDitherPlace(lag, tid, C)); p[tid] = PcmFormat<T>::encodeScaled(q); over += PcmFormat<T>::overScaled(q); }
-			const int nGroups = (count - head)/G;
-			for (int g = tid; g < nGroups; g += 256) {
-				const int e = head + g*G;
-				PcmDitherPlace at(lag, e, C);
-				float x[G];
-				for (int k = 0; k < G; ++k) { x[k] = scaled(e + k, at); over += PcmFormat<T>::overScaled(x[k]); at.next(C); }
-				PcmWord4 w[W];
-				PcmFormat<T>::packScaled(x, w);
-				PcmWord4 *dst = reinterpret_cast<PcmWord4 *>(p + e);
-				for (int k = 0; k < W; ++k) dst[k] = w[k];
-			}
-			const int done = head + nGroups*G;
-			if (tid < count - done) { const float q = scaled(done + tid, PcmDitherPlace(lag, done + tid, C)); p[done + tid] = PcmFormat<T>::encodeScaled(q); over += PcmFormat<T>::overScaled(q); }
-		} else {
-			for (int i = tid; i < count; i += 256) {
-				const PcmDitherPlace at(lag, i, C);
-				const float q = scaled(i, at);
-				run[(f0 + at.frame)*outFrameStride + at.c] = PcmFormat<T>::encodeScaled(q);
-				over += PcmFormat<T>::overScaled(q);
-			}
-		}
-		return true;
-	}
+	const unsigned mode = Dith && src ? dp.mode : 0u;
+	unsigned *keys = reinterpret_cast<unsigned *>(tile) + pcmLdsWords(C);
+	if (mode && tid < C) keys[tid] = pcmMix(dp.h + 0x9E3779B9u*unsigned(tid + 1));
 	__syncthreads();
 	over = 0;
-	if (dense) {
-		T *p = run + e0;
-		if (tid < head) { const float v = tile[pcmSlot(tid)]; p[tid] = PcmFormat<T>::encode(v); over += PcmFormat<T>::over(v); }
-		const int nGroups = (count - head)/G;
-		for (int g = tid; g < nGroups; g += 256) {
-			const int e = head + g*G;
-			float x[G];
-			for (int k = 0; k < G; ++k) { x[k] = tile[pcmSlot(e + k)]; over += PcmFormat<T>::over(x[k]); }
-			PcmWord4 w[W];
-			PcmFormat<T>::pack(x, w);
-			PcmWord4 *dst = reinterpret_cast<PcmWord4 *>(p + e);
-			for (int k = 0; k < W; ++k) dst[k] = w[k];
-		}
-		const int done = head + nGroups*G;
-		if (tid < count - done) { const float v = tile[pcmSlot(done + tid)]; p[done + tid] = PcmFormat<T>::encode(v); over += PcmFormat<T>::over(v); }
-	} else {
-		for (int i = tid; i < count; i += 256) {
-			const long long e = e0 + i, f = e/C;
-			const float v = tile[pcmSlot(i)];
-			run[f*outFrameStride + (e - f*C)] = PcmFormat<T>::encode(v);
-			over += PcmFormat<T>::over(v);
-		}
-	}
+	const unsigned long long n0 = (((unsigned long long)dp.nHi << 32) | dp.nLo) + (unsigned long long)f0;
+	auto rounded = [&](int i, const PcmPlace &at) { // element i of the tile as the quantiser takes it
+		const float v = tile[pcmSlot(i)];
+		if constexpr (Dith) return mode ? v*F::kScale + pcmDitherValue(mode, keys[at.c], n0 + at.frame) : v*F::kScale;
+		else return F::scaled(v);
+	};
+	pcmWalk(run, outFrameStride, e0, count, head, C,
+		[&](T &x, int i, const PcmPlace &at) { const float q = rounded(i, at); x = F::encode(q); over += F::over(q); },
+		[&](T *p, int i, PcmPlace at) {
+			float x[F::G];
+			for (int k = 0; k < F::G; ++k) { x[k] = rounded(i + k, at); over += F::over(x[k]); at.next(C); }
+			PcmWord4 w[F::W];
+			F::pack(x, w);
+			for (int k = 0; k < F::W; ++k) reinterpret_cast<PcmWord4 *>(p)[k] = w[k];
+		});
 	return true;
 }
 // the lanes' overs words into stream s's counters (every lane of the workgroup arrives here; the vote keeps the clean wavefront, which is
@@ -399,71 +340,59 @@ template <typename T> __global__ __launch_bounds__(256) void kPcmIn(const T *__r
 	pcmTileIn<T>(in + (size_t)s*inStreamStride, inFrameStride, counts[s], out + (size_t)s*outStreamStride, outChannelStride, blockIdx.x, C, reinterpret_cast<float *>(smemRaw));
 }
 
-// planar fp32 -> interleaved frames: the reverse.  overs (may be null): [S][2] counters, see "Overs" above
-template <typename T> __global__ __launch_bounds__(256) void kPcmOut(const float *__restrict__ in, long long inStreamStride, long long inChannelStride,
-		T *__restrict__ out, long long outStreamStride, long long outFrameStride, const int *__restrict__ counts, int C, unsigned *__restrict__ overs) {
-	extern __shared__ __attribute__((aligned(16))) unsigned char smemRaw[];
-	const int s = blockIdx.y;
-	unsigned over;
-	if (!pcmTileOut<T>(in + (size_t)s*inStreamStride, inChannelStride, out + (size_t)s*outStreamStride, outFrameStride, counts[s], blockIdx.x, C, reinterpret_cast<float *>(smemRaw), over)) return;
-	pcmAddOvers(overs, s, over);
-}
-// ... dithered (int16 / int24): dither[s] is stream s's entry, the index of the run's first frame in it
-template <typename T> __global__ __launch_bounds__(256) void kPcmOutDithered(const float *__restrict__ in, long long inStreamStride, long long inChannelStride,
+// planar fp32 -> interleaved frames: the reverse.  overs (may be null): [S][2] counters, see "Overs" above.  Dith (int16 / int24): dither[s] is
+// stream s's entry, the index of the run's first frame in it; else dither is not read
+template <typename T, bool Dith> __global__ __launch_bounds__(256) void kPcmOut(const float *__restrict__ in, long long inStreamStride, long long inChannelStride,
 		T *__restrict__ out, long long outStreamStride, long long outFrameStride, const int *__restrict__ counts, int C, unsigned *__restrict__ overs, const PcmDither *__restrict__ dither) {
 	extern __shared__ __attribute__((aligned(16))) unsigned char smemRaw[];
 	const int s = blockIdx.y;
+	PcmDither dp{0u, 0u, 0u, 0u};
+	if constexpr (Dith) dp = dither[s];
 	unsigned over;
-	if (!pcmTileOut<T, true>(in + (size_t)s*inStreamStride, inChannelStride, out + (size_t)s*outStreamStride, outFrameStride, counts[s], blockIdx.x, C, reinterpret_cast<float *>(smemRaw), over, dither[s])) return;
+	if (!pcmTileOut<T, Dith>(in + (size_t)s*inStreamStride, inChannelStride, out + (size_t)s*outStreamStride, outFrameStride, counts[s], blockIdx.x, C, reinterpret_cast<float *>(smemRaw), over, dp)) return;
 	pcmAddOvers(overs, s, over);
 }
 
-// format: SMST_PCM_* of include/smst.h (the C ABI has checked it).  maxFrames: the largest of the streams' counts.
-template <typename T> static void launchPcmInAs(dim3 grid, int C, hipStream_t st, const void *in, long long inStreamStride, long long inFrameStride, float *out, long long outStreamStride,
-		long long outChannelStride, const int *counts) {
-	hipLaunchKernelGGL(kPcmIn<T>, grid, dim3(256), pcmLdsBytes(C), st, static_cast<const T *>(in), inStreamStride, inFrameStride, out, outStreamStride, outChannelStride, counts, C);
+// A runtime format (SMST_PCM_* of include/smst.h; the C ABI has checked it) -> its element type: f(PcmTag<T>(), dithered), `dithered` a
+// std::true_type where the caller has dither entries AND the format has a step to dither (int16 / int24), else a std::false_type
+template <typename T> struct PcmTag { typedef T type; };
+template <typename T, typename F> static void pcmDispatchDithered(bool dither, F &f) {
+	if (dither) f(PcmTag<T>(), std::true_type());
+	else f(PcmTag<T>(), std::false_type());
 }
-template <typename T> static void launchPcmOutAs(dim3 grid, int C, hipStream_t st, const float *in, long long inStreamStride, long long inChannelStride, void *out, long long outStreamStride,
-		long long outFrameStride, const int *counts, unsigned *overs) {
-	hipLaunchKernelGGL(kPcmOut<T>, grid, dim3(256), pcmLdsBytes(C), st, in, inStreamStride, inChannelStride, static_cast<T *>(out), outStreamStride, outFrameStride, counts, C, overs);
+template <typename F> static void pcmDispatch(int format, bool dither, F f) {
+	switch (format) {
+	case kPcmS16: pcmDispatchDithered<int16_t>(dither, f); break;
+	case kPcmS24: pcmDispatchDithered<PcmS24>(dither, f); break;
+	case kPcmF32: f(PcmTag<float>(), std::false_type()); break;
+	case kPcmS32: f(PcmTag<int32_t>(), std::false_type()); break;
+	case kPcmF16: f(PcmTag<PcmF16>(), std::false_type()); break;
+	default: throw std::invalid_argument("unknown PCM format");
+	}
 }
+
+// maxFrames: the largest of the streams' counts
 void launchPcmIn(int format, const void *in, long long inStreamStride, long long inFrameStride, float *out, long long outStreamStride, long long outChannelStride,
                  const int *counts, int S, int C, int maxFrames, hipStream_t st) {
 	if (maxFrames < 1) return;
 	const dim3 grid(divUp(maxFrames, kPcmTileFrames), S);
-	switch (format) {
-	case kPcmS16: launchPcmInAs<int16_t>(grid, C, st, in, inStreamStride, inFrameStride, out, outStreamStride, outChannelStride, counts); break;
-	case kPcmF32: launchPcmInAs<float>(grid, C, st, in, inStreamStride, inFrameStride, out, outStreamStride, outChannelStride, counts); break;
-	case kPcmS24: launchPcmInAs<PcmS24>(grid, C, st, in, inStreamStride, inFrameStride, out, outStreamStride, outChannelStride, counts); break;
-	case kPcmS32: launchPcmInAs<int32_t>(grid, C, st, in, inStreamStride, inFrameStride, out, outStreamStride, outChannelStride, counts); break;
-	case kPcmF16: launchPcmInAs<PcmF16>(grid, C, st, in, inStreamStride, inFrameStride, out, outStreamStride, outChannelStride, counts); break;
-	default: throw std::invalid_argument("unknown PCM format");
-	}
+	pcmDispatch(format, false, [&](auto tag, auto) {
+		typedef typename decltype(tag)::type T;
+		hipLaunchKernelGGL(kPcmIn<T>, grid, dim3(256), pcmLdsBytes(C), st, static_cast<const T *>(in), inStreamStride, inFrameStride, out, outStreamStride, outChannelStride, counts, C);
+	});
 	countLaunch(LK_PCM_IN);
-}
-template <typename T> static void launchPcmOutDitheredAs(dim3 grid, int C, hipStream_t st, const float *in, long long inStreamStride, long long inChannelStride, void *out, long long outStreamStride,
-		long long outFrameStride, const int *counts, unsigned *overs, const PcmDither *dither) {
-	hipLaunchKernelGGL(kPcmOutDithered<T>, grid, dim3(256), pcmDitherLdsBytes(C), st, in, inStreamStride, inChannelStride, static_cast<T *>(out), outStreamStride, outFrameStride, counts, C, overs, dither);
 }
 void launchPcmOut(int format, const float *in, long long inStreamStride, long long inChannelStride, void *out, long long outStreamStride, long long outFrameStride,
                   const int *counts, int S, int C, int maxFrames, unsigned *overs, hipStream_t st, const PcmDither *dither) {
 	if (maxFrames < 1) return;
 	const dim3 grid(divUp(maxFrames, kPcmTileFrames), S);
-	if (dither && (format == kPcmS16 || format == kPcmS24)) {
-		if (format == kPcmS16) launchPcmOutDitheredAs<int16_t>(grid, C, st, in, inStreamStride, inChannelStride, out, outStreamStride, outFrameStride, counts, overs, dither);
-		else launchPcmOutDitheredAs<PcmS24>(grid, C, st, in, inStreamStride, inChannelStride, out, outStreamStride, outFrameStride, counts, overs, dither);
-		countLaunch(LK_PCM_OUT_DITHERED);
-		return;
-	}
-	switch (format) {
-	case kPcmS16: launchPcmOutAs<int16_t>(grid, C, st, in, inStreamStride, inChannelStride, out, outStreamStride, outFrameStride, counts, overs); break;
-	case kPcmF32: launchPcmOutAs<float>(grid, C, st, in, inStreamStride, inChannelStride, out, outStreamStride, outFrameStride, counts, overs); break;
-	case kPcmS24: launchPcmOutAs<PcmS24>(grid, C, st, in, inStreamStride, inChannelStride, out, outStreamStride, outFrameStride, counts, overs); break;
-	case kPcmS32: launchPcmOutAs<int32_t>(grid, C, st, in, inStreamStride, inChannelStride, out, outStreamStride, outFrameStride, counts, overs); break;
-	case kPcmF16: launchPcmOutAs<PcmF16>(grid, C, st, in, inStreamStride, inChannelStride, out, outStreamStride, outFrameStride, counts, overs); break;
-	default: throw std::invalid_argument("unknown PCM format");
-	}
-	countLaunch(LK_PCM_OUT);
+	pcmDispatch(format, dither != nullptr, [&](auto tag, auto dithered) {
+		typedef typename decltype(tag)::type T;
+		constexpr bool Dith = decltype(dithered)::value;
+		hipLaunchKernelGGL((kPcmOut<T, Dith>), grid, dim3(256), Dith ? pcmDitherLdsBytes(C) : pcmLdsBytes(C), st, in, inStreamStride, inChannelStride, static_cast<T *>(out), outStreamStride,
+		                   outFrameStride, counts, C, overs, dither);
+		countLaunch(Dith ? LK_PCM_OUT_DITHERED : LK_PCM_OUT);
+	});
 }
 
 } // namespace smst

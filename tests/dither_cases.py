@@ -436,10 +436,12 @@ CLIPS = dict(inputs=[3000, 4000, 200, 6250, 5000], outputs=[7500, 5000, 300, -1,
 CLIP_MODES, CLIP_SEED = (TPDF, HP, TPDF, HP, HP), 21
 
 
-def check_clips(lib, fmt, to_memory=lambda a: a, to_host=lambda a: np.array(a, copy=True)):
+def check_clips(lib, fmt, to_memory=lambda a: a, to_host=lambda a: np.array(a, copy=True), wide=False):
     """exactFrames with dither = the mirror of exact's planar output with n from 0 per clip; the short clip is zero codes with ok False, the
     left-out clip's buffer is untouched, the counters stand, clip_out_dithered is counted; a second call obeys the same rule (and gives
-    the same bytes where the engine gives the same samples)"""
+    the same bytes where the engine gives the same samples).  wide: `out` is the [S, n, C] view into frames of C + 1 channels -- the
+    kernel's element-by-element store in device memory, the frame-by-frame copy behind it in host memory -- and the pad element of every
+    frame stays as it was"""
     import exact_cases as ec
     pkg = package()
     nin, nout, short, left = CLIPS["inputs"], CLIPS["outputs"], CLIPS["short"], CLIPS["left_out"]
@@ -456,9 +458,11 @@ def check_clips(lib, fmt, to_memory=lambda a: a, to_host=lambda a: np.array(a, c
         want = np.array(want, copy=True)
         out = np.full(frames.shape[:1] + (most,) + frames.shape[2:], 0x5A, frames.dtype)
         before = (pkg.launch_count("clip_out", lib), pkg.launch_count("clip_out_dithered", lib))
-        dev_out = to_memory(out)
+        store = to_memory(np.full(out.shape[:2] + (Cn + 1,) + out.shape[3:], 0x5A, out.dtype) if wide else out)
+        dev_out = store[:, :, :Cn] if wide else store
         got, ok_f = f.exactFrames(to_memory(frames), nout, in_samples=nin, out=dev_out)
         got = to_host(got)
+        assert got.shape == out.shape and (to_host(store)[:, :, Cn:] == 0x5A).all()
         after = (pkg.launch_count("clip_out", lib), pkg.launch_count("clip_out_dithered", lib))
         assert (after[0] - before[0], after[1] - before[1]) == (0, 1)
         assert ok_p.tolist() == ok_f.tolist() == [s not in (short, left) for s in range(S)]

@@ -63,6 +63,11 @@ def test_whole_clips(emu, fmt):
     dc.check_clips(emu, fmt)
 
 
+@pytest.mark.parametrize("fmt", dc.DITHERED_FORMATS)
+def test_whole_clips_wide_output(emu, fmt):
+    dc.check_clips(emu, fmt, wide=True)
+
+
 def test_refusals(emu):
     dc.check_refusals(emu)
 

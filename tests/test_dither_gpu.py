@@ -81,6 +81,16 @@ def test_whole_clips_device_memory(hip):
     dc.check_clips(hip, fc.S24, **_device_memory())
 
 
+@pytest.mark.parametrize("fmt", dc.DITHERED_FORMATS)
+def test_whole_clips_wide_output_host_memory(hip, fmt):
+    dc.check_clips(hip, fmt, wide=True)
+
+
+@pytest.mark.parametrize("fmt", dc.DITHERED_FORMATS)
+def test_whole_clips_wide_output_device_memory(hip, fmt):
+    dc.check_clips(hip, fmt, wide=True, **_device_memory())
+
+
 def test_refusals(hip):
     dc.check_refusals(hip)
 

@@ -11,8 +11,8 @@ that drift of the host or the device hits all of them alike:
   e  smst_batch_process, SMST_MEM_DEVICE, planar float      (what d is compared with: d - e = the two conversion passes)
   f  d with TPDF dither (setPcmDither), g  d with high-passed TPDF dither       (f - d, g - d = what the dither adds to a step)
   h  smst_batch_process_pcm, SMST_MEM_DEVICE, packed int24 frames, i  h with TPDF dither, j  h with high-passed TPDF dither
-The dithered rows are not in the default set: --variants d,e,f,g,h,i,j.  The time of the output conversion KERNEL alone (kPcmOut /
-kPcmOutDithered per format) is read from a kernel trace of such a run.
+The dithered rows are not in the default set: --variants d,e,f,g,h,i,j.  The time of the output conversion KERNEL alone (kPcmOut<T, false> /
+kPcmOut<T, true> per format) is read from a kernel trace of such a run.
 A step's time is the host clock around one call that ends synchronised.  Prints one JSON line."""
 import argparse
 import importlib
