@@ -633,55 +633,87 @@ __global__ __launch_bounds__(256) void kEmitProducts(DevBatch d, int sBase, int 
 // its window products (kEmitProducts) and stored; the ring moves on by one interval.  The previous frame's additions run while the
 // next frame's spectrum is on its way in.  Two teams per workgroup (the ring takes NI*SLOTS registers on top of the transform's), one
 // workgroup per CU.  Same operations in the same order on the same values as kSynthTeams + kEmit: bit-identical output and carry
-// (test_synth_emit_equals_two_kernels).
-template <int R3, int QN, int SLOTS, bool SPLIT>
+// (test_synth_emit_equals_two_kernels; at the edges of a tile, every instantiation: test_synth_emit_hoploop).
+// The hop loop carries only what every hop needs.  GI, GB: the interval and the block where the launcher knows them (launchSynthEmit; 0: read
+// from the batch) -- thread t owns r = t + 256*slot, so with the interval a constant every slot below I/256 needs no predicate, one partial
+// slot tests t alone, and `a*I + r < B` is decided per (a, slot) but for one partial slot at most.  What only the edges of a tile need --
+// the samples in front of the first hop, a stream without hops, the call's last interval (which may end behind ed.nHi), SPLIT's trailing
+// interval, the carry write, the fp16 form of the carry -- sits in front of the loop and behind it, and the scalars it takes (SynthEmitEdge)
+// are formed again behind the loop instead of living through it.
+// Why an interval emitted INSIDE the loop is final as a whole: interval q is emitted while hop q + 1 <= cnt - 1 is transformed; the hops of a
+// tile lie I samples apart, so the interval ends where hop q + 1 begins, and a hop begins inside its call (scheduleStream: outPos < nOut;
+// split computation: its whole interval does) and not behind the tile's nHi (the next tile's first hop, or the call's end).
+struct SynthEmitEdge {
+	EmitDesc ed;
+	float *out;           // the (stream, channel)'s output row
+	size_t carryRow;      // the new carry's row
+	size_t carried;       // the old carry's first entry
+	const float *wpOld;   // the old carry's window products
+};
+__device__ __forceinline__ SynthEmitEdge synthEmitEdge(const DevBatch &d, const IoArgs &io, int sg, int c, int tileIndex) {
+	SynthEmitEdge e;
+	e.ed = d.emit[(size_t)sg*d.emitStride + tileIndex];
+	const int carryFrom = d.carryBase[d.carryCur][sg];
+	e.carryRow = carrySumRow(d, sg, c);
+	e.carried = e.carryRow + carryFrom;
+	e.wpOld = d.carryWp[d.carryCur] + carryWpRow(d, sg) + carryFrom;
+	e.out = io.out + (size_t)sg*io.outStreamStride + (size_t)c*io.outChannelStride;
+	return e;
+}
+// output sample n of the call: final, or part of what the next tile starts from
+__device__ __forceinline__ void synthEmitPlace(const DevBatch &d, const SynthEmitEdge &e, int n, float sum, float wp) {
+	if (n < e.ed.nHi) e.out[n] = sum/wp;
+	else if (n - e.ed.nHi < d.carryLen) storeCarrySum(d, d.carryCur ^ 1, e.carryRow + (n - e.ed.nHi), sum);
+}
+template <int R3, int QN, int SLOTS, bool SPLIT, int GI, int GB>
 __global__ __launch_bounds__(512) void kSynthEmitTeams(DevBatch d, IoArgs io, int sBase, int tileIndex, int nStreams) {
 	constexpr int TEAMS = 2, MA = 16*R3, H = 256*R3, N = 2*H, NI = QN + 1, DQ = SPLIT ? 1 : 0;
+	static_assert(GI == 0 || (GI <= 256*SLOTS && GI > 256*(SLOTS - 1) && QN*GI >= GB && GB <= N), "the geometry this instantiation is for");
 	extern __shared__ __attribute__((aligned(16))) unsigned char smemRaw[];
-	const int B = d.B, I = d.I, CL = d.carryLen;
+	const int B = GI ? GB : d.B, I = GI ? GI : d.I;
 	TeamWorkgroup<R3, TEAMS> wg(smemRaw, d, d.synTab); // table: (e^{-i pi m/N}, the two window samples of output m)
 	const TeamSync sync = wg.sync();
 	const int team = wg.team, t = wg.t;
 	float2 *lds = wg.lds;
 	float *ex = reinterpret_cast<float *>(lds); // the frame, B floats, in the transform buffer
+	// position r = t + 256*slot of an interval exists / frame sample a*I + r exists: decided at compile time wherever GI, GB and t < 256 decide it
+	auto inInterval = [&](int slot) { return 256*slot + t < I; };
+	auto inFrame = [&](int a, int slot) { return 256*slot + t < I && a*I + 256*slot + t < B; };
 	float steady[SLOTS]; // the window products under a sample that only this tile's frames cover: oldest frame first, as the ring sums them
 #pragma unroll
 	for (int slot = 0; slot < SLOTS; ++slot) {
-		const int r = 256*slot + t;
 		steady[slot] = 1e-30f;
 #pragma unroll
 		for (int a = QN - 1; a >= 0; --a) {
-			if (r < I && a*I + r < B) steady[slot] += d.wprod[a*I + r];
+			if (inFrame(a, slot)) steady[slot] += d.wprod[a*I + 256*slot + t];
 		}
 		keepUnconditional(steady[slot]);
 	}
-	const int items = nStreams*d.C;
+	const int C = d.C, items = nStreams*C;
+	const unsigned hopPitch = (unsigned)C*(unsigned)d.Mp; // from one hop's row of OUT to the next, in elements (rowOf)
 	for (int item = blockIdx.x*TEAMS + team; item < items; item += gridDim.x*TEAMS) {
-		const int s = item/d.C, c = item - s*d.C, sg = sBase + s;
-		const EmitDesc ed = d.emit[(size_t)sg*d.emitStride + tileIndex];
-		const int cnt = ed.hopCount, span = ed.nHi - ed.nLo;
-		const int carryFrom = d.carryBase[d.carryCur][sg];
-		const size_t carryRow = carrySumRow(d, sg, c), carried = carryRow + carryFrom; // the new carry's row, the old carry's first entry
-		const float *wpOld = d.carryWp[d.carryCur] + carryWpRow(d, sg) + carryFrom;
-		const float *wpHead = d.wpHead + (size_t)sg*d.wpHeadLen; // (kEmitProducts; it also writes the new carry's products)
-		float *out = io.out + (size_t)sg*io.outStreamStride + (size_t)c*io.outChannelStride;
-		auto place = [&](int n, float sum, float wp) { // output sample n of the call: final, or part of what the next tile starts from
-			if (n < ed.nHi) out[n] = sum/wp;
-			else if (n - ed.nHi < CL) storeCarrySum(d, d.carryCur ^ 1, carryRow + (n - ed.nHi), sum);
-		};
-		if (cnt == 0) { // nothing synthesised for this stream in this tile: the carried sums are emitted / move up
-			for (int i = t; i < span + CL; i += 256) place(ed.nLo + i, carriedSumAt(d, carried, i), carriedProductAt(d, wpOld, i));
-			continue;
-		}
-		const int off = ed.firstHopPos - ed.nLo; // samples in front of the tile's first hop (the first tile of a call only)
-		for (int i = t; i < off; i += 256) place(ed.nLo + i, carriedSumAt(d, carried, i), carriedProductAt(d, wpOld, i));
+		const int s = item/C, c = item - s*C, sg = sBase + s;
+		int cnt, off, firstHopPos;
 		float acc[NI][SLOTS];
+		{
+			const SynthEmitEdge e = synthEmitEdge(d, io, sg, c, tileIndex);
+			const int CL = d.carryLen;
+			cnt = e.ed.hopCount;
+			if (cnt == 0) { // nothing synthesised for this stream in this tile: the carried sums are emitted / move up
+				const int span = e.ed.nHi - e.ed.nLo;
+				for (int i = t; i < span + CL; i += 256) synthEmitPlace(d, e, e.ed.nLo + i, carriedSumAt(d, e.carried, i), carriedProductAt(d, e.wpOld, i));
+				continue;
+			}
+			firstHopPos = e.ed.firstHopPos;
+			off = firstHopPos - e.ed.nLo; // samples in front of the tile's first hop (the first tile of a call only)
+			for (int i = t; i < off; i += 256) synthEmitPlace(d, e, e.ed.nLo + i, carriedSumAt(d, e.carried, i), carriedProductAt(d, e.wpOld, i));
 #pragma unroll
-		for (int u = 0; u < NI; ++u) {
+			for (int u = 0; u < NI; ++u) {
 #pragma unroll
-			for (int slot = 0; slot < SLOTS; ++slot) {
-				const int r = 256*slot + t, i = off + u*I + r;
-				acc[u][slot] = r < I ? carriedSumAt(d, carried, i) : 0.0f;
+				for (int slot = 0; slot < SLOTS; ++slot) {
+					const int i = off + u*I + 256*slot + t;
+					acc[u][slot] = inInterval(slot) ? carriedSumAt(d, e.carried, i) : 0.0f;
+				}
 			}
 		}
 		// (waited for HERE: a register that is still "being loaded" when the hop loop is entered makes the compiler wait for ALL loads at
@@ -691,62 +723,35 @@ __global__ __launch_bounds__(512) void kSynthEmitTeams(DevBatch d, IoArgs io, in
 #pragma unroll
 			for (int slot = 0; slot < SLOTS; ++slot) keepUnconditional(acc[u][slot]);
 		}
+		// what the loop addresses: one base per item, 32-bit offsets per hop
+		const float2 *spectra = d.OUT + rowOf(d, s, 0, c);            // hop q: + q*hopPitch
+		float *outHops = io.out + (size_t)sg*io.outStreamStride + (size_t)c*io.outChannelStride + firstHopPos; // interval q: + q*I
+		const float *wpHead = d.wpHead + (size_t)sg*d.wpHeadLen + off; // (kEmitProducts; it also writes the new carry's products) interval q: + q*I
 		// frame q - 1 is added to the ring while frame q's spectrum is on its way in, and its finished interval leaves after frame
 		// q's first-stage writes (no store between a load and its use: vmcnt counts both)
 		auto overlapAdd = [&]() {
 			float e[QN][SLOTS]; // all reads in flight together, no branch around any of them
 			int tt = t;
-			keepUnconditional(tt); // (the 24 addresses are formed here, per hop: held across the loop they cost the registers the next spectrum needs)
+			keepUnconditional(tt); // (the addresses are formed here, per hop: held across the loop they cost the registers the next spectrum needs)
 #pragma unroll
 			for (int a = 0; a < QN; ++a) {
 #pragma unroll
 				for (int slot = 0; slot < SLOTS; ++slot) {
-					const int r = 256*slot + tt, i = a*I + r;
-					e[a][slot] = ex[r < I && i < B ? i : 0];
+					if (GI && (256*slot >= GI || a*GI + 256*slot >= GB)) continue; // no lane has this sample
+					e[a][slot] = ex[inFrame(a, slot) ? a*I + 256*slot + tt : 0];
 				}
 			}
 #pragma unroll
 			for (int a = 0; a < QN; ++a) {
 #pragma unroll
 				for (int slot = 0; slot < SLOTS; ++slot) {
-					const int r = 256*slot + t, i = a*I + r;
+					if (GI && (256*slot >= GI || a*GI + 256*slot >= GB)) continue;
 					keepUnconditional(e[a][slot]);
-					acc[a + DQ][slot] = (r < I && i < B) ? acc[a + DQ][slot] + e[a][slot] : acc[a + DQ][slot];
+					acc[a + DQ][slot] = inFrame(a, slot) ? acc[a + DQ][slot] + e[a][slot] : acc[a + DQ][slot];
 				}
 			}
 		};
-		auto emitInterval = [&](int q) {
-			const int n0 = ed.firstHopPos + q*I;
-			float wp[SLOTS];
-#pragma unroll
-			for (int slot = 0; slot < SLOTS; ++slot) wp[slot] = steady[slot];
-			if (q < NI) { // the carried sums may reach into this interval (loads of the kernel's own here too: see `next`)
-				Async4 head[SLOTS];
-#pragma unroll
-				for (int slot = 0; slot < SLOTS; ++slot) {
-					const int r = 256*slot + t;
-					asyncLoad4(head[slot], wpHead + (r < I ? off + q*I + r : 0));
-				}
-				asyncWait<0>();
-#pragma unroll
-				for (int slot = 0; slot < SLOTS; ++slot) {
-					asyncArrived(head[slot]);
-					if (256*slot + t < I) wp[slot] = asyncValue(head[slot]);
-				}
-			}
-			if (n0 + I <= ed.nHi) { // (all but a call's last hop)
-#pragma unroll
-				for (int slot = 0; slot < SLOTS; ++slot) {
-					const int r = 256*slot + t;
-					if (r < I) out[n0 + r] = acc[0][slot]/wp[slot];
-				}
-			} else {
-#pragma unroll
-				for (int slot = 0; slot < SLOTS; ++slot) {
-					const int r = 256*slot + t;
-					if (r < I) place(n0 + r, acc[0][slot], wp[slot]);
-				}
-			}
+		auto moveRing = [&]() {
 #pragma unroll
 			for (int u = 0; u + 1 < NI; ++u) {
 #pragma unroll
@@ -755,6 +760,34 @@ __global__ __launch_bounds__(512) void kSynthEmitTeams(DevBatch d, IoArgs io, in
 #pragma unroll
 			for (int slot = 0; slot < SLOTS; ++slot) acc[NI - 1][slot] = 0.0f;
 		};
+		// the window products under interval q: the steady pattern, but in the first NI intervals the carried products may reach into them
+		// (loads of the kernel's own here too: see `next`)
+		auto productsOf = [&](int q, float (&wp)[SLOTS]) {
+#pragma unroll
+			for (int slot = 0; slot < SLOTS; ++slot) wp[slot] = steady[slot];
+			if (q < NI) {
+				Async4 head[SLOTS];
+				const float *from = wpHead + q*I;
+#pragma unroll
+				for (int slot = 0; slot < SLOTS; ++slot) asyncLoad4(head[slot], from + (inInterval(slot) ? 256*slot + t : 0));
+				asyncWait<0>();
+#pragma unroll
+				for (int slot = 0; slot < SLOTS; ++slot) {
+					asyncArrived(head[slot]);
+					if (inInterval(slot)) wp[slot] = asyncValue(head[slot]);
+				}
+			}
+		};
+		auto emitFinal = [&](int q) { // an interval in front of the tile's last: final as a whole (see above)
+			float wp[SLOTS];
+			productsOf(q, wp);
+			float *to = outHops + q*I;
+#pragma unroll
+			for (int slot = 0; slot < SLOTS; ++slot) {
+				if (inInterval(slot)) to[256*slot + t] = acc[0][slot]/wp[slot];
+			}
+			moveRing();
+		};
 		// frame q + 1's spectrum is requested as soon as frame q's first stage has taken its own out of the registers
 		// (loads the kernel waits for itself, smst_async.h: a compiler-tracked load whose value crosses the loop's back-edge makes the
 		// compiler wait for EVERYTHING at the next barrier's counter update, i.e. right behind the request)
@@ -762,7 +795,7 @@ __global__ __launch_bounds__(512) void kSynthEmitTeams(DevBatch d, IoArgs io, in
 #pragma unroll
 		for (int k = 0; k < 16; ++k) asyncClear(next[k]);
 		auto request = [&](int q) {
-			const float2 *X = d.OUT + rowOf(d, s, q, c);
+			const float2 *X = spectra + (unsigned)q*hopPitch;
 			if (t < MA) {
 #pragma unroll
 				for (int k = 0; k < 16; ++k) asyncLoad8(next[k], X + halfBinIndex(t + MA*k, H, N)); // one load at a selected address (see loadHalfBin) ...
@@ -785,7 +818,7 @@ __global__ __launch_bounds__(512) void kSynthEmitTeams(DevBatch d, IoArgs io, in
 					sync(); // the previous frame has been read (or the previous item's last one), before this transform's first-stage writes
 				},
 				[&]() {
-					if (q > 0) emitInterval(q - 1);
+					if (q > 0) emitFinal(q - 1);
 					request(q + 1 < cnt ? q + 1 : q);
 				},
 				[&](float2 v, int j) { if (2*j >= H) v.y = -v.y; return v; }); // ... conjugated once it is there
@@ -794,18 +827,32 @@ __global__ __launch_bounds__(512) void kSynthEmitTeams(DevBatch d, IoArgs io, in
 		}
 		overlapAdd();
 		sync();
-		emitInterval(cnt - 1);
+		// the edge behind the loop: the item's scalars again, from values the compiler cannot trace back through the loop
+		int sgE = sg, cE = c;
+		keepUnconditional(sgE);
+		keepUnconditional(cE);
+		const SynthEmitEdge e = synthEmitEdge(d, io, __builtin_amdgcn_readfirstlane(sgE), __builtin_amdgcn_readfirstlane(cE), tileIndex);
+		auto emitEdge = [&](int q) { // an interval that may end behind ed.nHi: sample by sample
+			float wp[SLOTS];
+			productsOf(q, wp);
+			const int n0 = firstHopPos + q*I;
+#pragma unroll
+			for (int slot = 0; slot < SLOTS; ++slot) {
+				if (inInterval(slot)) synthEmitPlace(d, e, n0 + 256*slot + t, acc[0][slot], wp[slot]);
+			}
+			moveRing();
+		};
+		emitEdge(cnt - 1);
 		// split computation: only blocks whose interval is complete are in the tile (the one in flight runs with a later call), so a call's
 		// last tile may end up to an interval behind its last hop's interval: those samples leave like any other interval
-		const bool trailing = SPLIT && ed.firstHopPos + cnt*I < ed.nHi;
-		if (trailing) emitInterval(cnt);
-		const int n0 = ed.firstHopPos + (cnt + (trailing ? 1 : 0))*I; // what the ring still holds: the start of the next tile's sums
+		const bool trailing = SPLIT && firstHopPos + cnt*I < e.ed.nHi;
+		if (trailing) emitEdge(cnt);
+		const int n0 = firstHopPos + (cnt + (trailing ? 1 : 0))*I; // what the ring still holds: the start of the next tile's sums
 #pragma unroll
 		for (int u = 0; u < NI; ++u) {
 #pragma unroll
 			for (int slot = 0; slot < SLOTS; ++slot) {
-				const int r = 256*slot + t;
-				if (r < I) place(n0 + u*I + r, acc[u][slot], 1.0f); // (all of it behind the call's last final sample)
+				if (inInterval(slot)) synthEmitPlace(d, e, n0 + u*I + 256*slot + t, acc[u][slot], 1.0f); // (all of it behind the call's last final sample)
 			}
 		}
 	}
@@ -1129,12 +1176,23 @@ bool synthEmitApplies(const DevBatch &d, int nStreams, int tileHops) {
 void launchEmitProducts(const DevBatch &d, int sBase, int nStreams, int tileIndex, hipStream_t st) {
 	hipLaunchKernelGGL(kEmitProducts, dim3(divUp(d.wpHeadLen + d.carryLen, 256), nStreams), dim3(256), 0, st, d, sBase, tileIndex);
 }
+// kSynthEmitTeams with the interval and the block as constants (and as many slots as the interval takes): presetDefault and presetCheaper at
+// 48 and 44.1 kHz.  Every other geometry that synthEmitApplies() accepts takes the instantiation that reads them from the batch.
+template <int GI, int GB> struct SynthEmitGeometry { static constexpr int interval = GI, block = GB, slots = (GI + 255)/256; };
+template <int R3, typename F>
+static void withSynthEmitGeometry(const DevBatch &d, F f) { // f(geometry, slots)
+	using Slots = std::integral_constant<int, synthEmitSlots(R3)>;
+	auto is = [&](auto g) { return d.I == g.interval && d.B == g.block && (f(g, std::integral_constant<int, g.slots>()), true); };
+	if constexpr (R3 == 12) { if (is(SynthEmitGeometry<1440, 5760>()) || is(SynthEmitGeometry<1323, 5292>())) return; }
+	if constexpr (R3 == 10) { if (is(SynthEmitGeometry<1920, 4800>()) || is(SynthEmitGeometry<1764, 4410>())) return; }
+	f(SynthEmitGeometry<0, 0>(), Slots());
+}
 void launchSynthEmit(const DevBatch &d, const IoArgs &io, int sBase, int nStreams, int tileIndex, hipStream_t st) {
 	const int items = nStreams*d.C;
 	const int wgs = std::min(divUp(items, 2), d.teamsGrid); // two teams each
-	withTeamR3(d.M, [&](auto r3) { withFlag(d.delta != 0, [&](auto split) {
-		hipLaunchKernelGGL((kSynthEmitTeams<r3.value, synthEmitQN(r3.value), synthEmitSlots(r3.value), split.value>), dim3(wgs), dim3(512), teamLdsBytes(d.M, 2), st, d, io, sBase, tileIndex, nStreams);
-	}); });
+	withTeamR3(d.M, [&](auto r3) { withFlag(d.delta != 0, [&](auto split) { withSynthEmitGeometry<r3.value>(d, [&](auto g, auto slots) {
+		hipLaunchKernelGGL((kSynthEmitTeams<r3.value, synthEmitQN(r3.value), slots.value, split.value, g.interval, g.block>), dim3(wgs), dim3(512), teamLdsBytes(d.M, 2), st, d, io, sBase, tileIndex, nStreams);
+	}); }); });
 	countLaunch(LK_SYNTH_EMIT);
 }
 void launchEmit(const DevBatch &d, const IoArgs &io, int sBase, int nStreams, int tileIndex, int maxSpan, hipStream_t st) {
