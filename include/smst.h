@@ -377,6 +377,76 @@ int smst_batch_output_seek_pcm(smst_batch *b, const void *in, long long inStream
 int smst_batch_set_pcm_dither(smst_batch *b, int stream, int mode, long long seed);
 /* any pointer may be null; frames = the stream's frame counter */
 int smst_batch_pcm_dither(const smst_batch *b, int stream, int *mode, long long *seed, long long *frames);
+/* ---- Level (EXTENSION; opt-in: a batch that never calls smst_batch_set_pcm_level launches the kernels, writes the bytes and counts the launches it did before) ----
+ * Per-stream output gain and peak meters in the output conversion of the _pcm calls and, for whole clips (smst_batch_exact_pcm), a gain
+ * derived from the clip's own peak.  A batch uses the levelled kernels from its first smst_batch_set_pcm_level on; a stream that was never
+ * set has the gain 1, and v*1 is v.
+ *
+ * Arithmetic.  Every step is one correctly rounded fp32 operation, so it can be restated bit for bit on the host (tests/level_cases.py).
+ * - w = v*g: one fp32 multiply of its own, never fused into what follows.
+ * - Then the rule of the format runs on w: t = w*scale (+ d), roundf, clamp, NaN gives 0.  The float formats (F32, F16) write w.
+ * - Overs count as before, on t.  Dither is unchanged and comes after the gain.
+ *
+ * Peak.  The largest |v| BEFORE the gain, over the frames a call writes for the stream and over all channels.  NaNs are skipped, +-inf
+ * counts as inf.  Peaks are compared as the unsigned bit patterns of |v| -- an integer maximum: order-independent, bit-reproducible.
+ *
+ * Modes
+ * - SMST_LEVEL_FIXED (0): g = gain.  Any finite gain: 0 mutes, a negative one inverts.
+ * - SMST_LEVEL_PROTECT (1), whole clips only: q = ceiling/peak, g = gain <= q ? gain : q -- the gain, lowered where the clip would exceed the ceiling.
+ * - SMST_LEVEL_NORMALISE (2), whole clips only: g = ceiling/peak (the gain is not used).
+ *   peak is that of the stream's whole output clip [0, outSamples[s]), q the correctly rounded fp32 quotient; peak 0 or not finite: g = gain.
+ *   The peak is measured (one pass over the library's own planar image of the output) and the gain formed on the device: no host
+ *   synchronisation is added to the call.  A peak so small that the quotient overflows gives g = inf, as the arithmetic says.
+ *
+ * Which calls.  smst_batch_process_pcm and smst_batch_flush_pcm apply the gain of FIXED streams and meter them; if a stream that takes part
+ * (process: every stream; flush: those with a non-negative count) has a whole-clip mode they return SMST_ERR_INVALID before anything runs --
+ * a whole-clip gain in a streaming call would be a silent lie.  smst_batch_exact_pcm serves all three modes.  The too-short and left-out
+ * streams of an exact call stay as they are: undithered zeros or untouched, peak and gain unchanged.  Out of scope: the planar calls and the
+ * planar smst_batch_exact are neither levelled nor metered; loudness (LUFS) and true-peak metering; separate input and output formats in one call.
+ *
+ * Clip-free ceilings.  fl(peak*fl(ceiling/peak)) may exceed the ceiling by an fp32 rounding or two, so a ceiling of exactly full scale can
+ * clamp.  No element is clamped (smst_batch_take_pcm_overs gives 0) when ceiling*scale is at most
+ *
+ *     format   no dither      TPDF / TPDF_HP
+ *     S16      32767          32766
+ *     S24      8388606        8388605
+ *     S32      2^31 - 256     (S32 is not dithered)
+ *
+ * and the next code up (S32: the next float32, 2^31 - 128) does clamp for some peak.  Found by pushing sampled peaks through a float32
+ * mirror, which tests/level_cases.py repeats; the float formats have no ceiling to respect.
+ *
+ * The per-stream entries (mode, gain, ceiling) ride in the per-call table beside the dither entries; the meters ([3][streams] words:
+ * peaks, applied gains, the clip peaks of the newest exact call) are device memory allocated with the batch and part of
+ * smst_batch_workspace_bytes.  No allocation and no host synchronisation is added to any call, the ordering contract is unchanged, and a
+ * steady-state levelled call leaves smst_batch_debug_allocation_events where it is.
+ * SMST_ERR_INVALID with a message: an unknown mode, a stream index out of range, a null batch, a gain that is not finite, a gain <= 0 in
+ * PROTECT, a ceiling that is not finite or <= 0 in the two whole-clip modes. */
+#define SMST_LEVEL_FIXED     0 /* g = gain */
+#define SMST_LEVEL_PROTECT   1 /* whole clips only: q = ceiling/peak; g = gain <= q ? gain : q */
+#define SMST_LEVEL_NORMALISE 2 /* whole clips only: g = ceiling/peak */
+/* stream = -1: every stream.  ceiling is checked in the two whole-clip modes only */
+int smst_batch_set_pcm_level(smst_batch *b, int stream, int mode, float gain, float ceiling);
+/* any pointer may be null */
+int smst_batch_pcm_level(const smst_batch *b, int stream, int *mode, float *gain, float *ceiling);
+/* per stream, since the last take: peaks[s] = the largest |v| the levelled output conversions met BEFORE the gain (0 if none); gains[s] = the
+ * gain the newest levelled conversion of stream s applied (1 before any).  Either may be null.  Synchronises the batch; resets the peaks,
+ * not the gains. */
+int smst_batch_take_pcm_peaks(smst_batch *b, float *peaks, float *gains);
+/* test hook: smst_debug_pcm_convert_dithered through the levelled kernel, with per-stream fixed gains ([streams]); peaks ([streams], may be
+ * null): the peaks it metered */
+int smst_debug_pcm_convert_levelled(int device, int format, int streams, int channels, const int *counts,
+                                    const void *src, long long srcStreamStride, long long srcInnerStride,
+                                    void *dst, long long dstStreamStride, long long dstInnerStride,
+                                    const int *modes, const long long *seeds, const long long *firstFrames, const float *gains,
+                                    long long *clamped, long long *nans, float *peaks);
+/* test hook: smst_debug_clip_copy for dir 1 into a frame format through the peak pass and the levelled copy kernel, with per-stream level
+ * entries (levelModes, gains, ceilings) and dither entries (ditherModes, seeds; the frame index is the place in the clip) ([streams] each);
+ * peaks / applied ([streams], either may be null): the peaks it metered and the gains it applied (1 for a stream that moved no sample) */
+int smst_debug_clip_copy_levelled(int device, int format, int streams, int channels, const int *segments,
+                                  const void *src, long long srcStreamStride, long long srcInnerStride,
+                                  void *dst, long long dstStreamStride, long long dstInnerStride,
+                                  const int *levelModes, const float *gains, const float *ceilings, const int *ditherModes, const long long *seeds,
+                                  long long *clamped, long long *nans, float *peaks, float *applied);
 /* test hook: the two conversion kernels alone, ragged counts, arbitrary strides; dir 0 = PCM -> planar, 1 = planar -> PCM.  Host pointers: the
  * PCM side is (stream stride, frame stride), the planar side (stream stride, channel stride), in elements.  Both buffers are staged whole (what
  * the kernel leaves alone in `dst` comes back as it was) into device buffers offset from a 16-byte boundary as the caller's pointers are.

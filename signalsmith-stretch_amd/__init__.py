@@ -27,6 +27,7 @@ CSRC_DIR = os.path.join(_HERE, "csrc")
 MEM_HOST, MEM_DEVICE = 0, 1
 PCM_S16, PCM_F32, PCM_S24, PCM_S32, PCM_F16 = 1, 2, 4, 5, 6  # frame formats of the *_pcm calls (include/smst.h)
 DITHER_NONE, DITHER_TPDF, DITHER_TPDF_HP = 0, 1, 2           # dither of the int16 / int24 output (StretchBatch.setPcmDither)
+LEVEL_FIXED, LEVEL_PROTECT, LEVEL_NORMALISE = 0, 1, 2        # level of the frame output (StretchBatch.set_pcm_level)
 _FRAME_DTYPES = {"int16": PCM_S16, "float32": PCM_F32, "int32": PCM_S32, "float16": PCM_F16}  # (packed int24 travels as uint8 [..., 3])
 _FRAME_DTYPE_OF = {PCM_S16: "int16", PCM_F32: "float32", PCM_S32: "int32", PCM_F16: "float16", PCM_S24: "uint8"}
 _fp = C.POINTER(C.c_float)
@@ -124,6 +125,13 @@ _SIGNATURES = {
     "smst_batch_pcm_dither": (C.c_int, [C.c_void_p, C.c_int, _ip, C.POINTER(_ll), C.POINTER(_ll)]),
     "smst_debug_pcm_convert_dithered": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _ip, C.c_void_p, _ll, _ll, C.c_void_p, _ll, _ll, _ip, C.POINTER(_ll), C.POINTER(_ll),
                                                   C.POINTER(_ll), C.POINTER(_ll)]),
+    "smst_batch_set_pcm_level": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_float]),
+    "smst_batch_pcm_level": (C.c_int, [C.c_void_p, C.c_int, _ip, _fp, _fp]),
+    "smst_batch_take_pcm_peaks": (C.c_int, [C.c_void_p, _fp, _fp]),
+    "smst_debug_pcm_convert_levelled": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _ip, C.c_void_p, _ll, _ll, C.c_void_p, _ll, _ll, _ip, C.POINTER(_ll), C.POINTER(_ll),
+                                                  _fp, C.POINTER(_ll), C.POINTER(_ll), _fp]),
+    "smst_debug_clip_copy_levelled": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _ip, C.c_void_p, _ll, _ll, C.c_void_p, _ll, _ll, _ip, _fp, _fp, _ip, C.POINTER(_ll),
+                                                C.POINTER(_ll), C.POINTER(_ll), _fp, _fp]),
     "smst_batch_synchronize": (C.c_int, [C.c_void_p]),
     "smst_batch_hip_stream": (C.c_void_p, [C.c_void_p]),
     "smst_batch_enable_profiling": (C.c_int, [C.c_void_p, C.c_int]),
@@ -231,6 +239,40 @@ def complex_selftest(values, device=0, lib=None):
     out = np.zeros((v.shape[0], 8), np.float32)
     _check(lib, lib.smst_debug_complex_selftest(device, v.ctypes.data_as(_fp), out.ctypes.data_as(_fp), v.shape[0]))
     return out
+
+
+def _level_arrays(n, *columns):
+    """per-stream columns of the levelled debug hooks -> contiguous arrays (int32 / float32 / int64 by the column's kind) and their pointers"""
+    kinds = {"i": (np.int32, _ip), "f": (np.float32, _fp), "l": (np.int64, C.POINTER(_ll))}
+    arrays = [np.ascontiguousarray(np.broadcast_to(np.asarray(v, kinds[k][0]), (n,))) for k, v in columns]
+    return arrays, [a.ctypes.data_as(kinds[k][1]) for a, (k, _) in zip(arrays, columns)]
+
+
+def debug_pcm_convert_levelled(fmt, counts, channels, src, src_ss, src_cs, dst, dst_ss, dst_fs, modes, seeds, firsts, gains, device=0, lib=None):
+    """smst_debug_pcm_convert_levelled on numpy buffers (src planar float32, dst the frames' bytes or elements; strides in elements)
+    -> (clamped, nans int64 [S], peaks float32 [S])"""
+    lib = lib if lib is not None else load_library()
+    S = len(counts)
+    keep, (pc, pm, ps, pf, pg) = _level_arrays(S, ("i", counts), ("i", modes), ("l", seeds), ("l", firsts), ("f", gains))
+    clamped, nans, peaks = np.full(S, -1, np.int64), np.full(S, -1, np.int64), np.full(S, -1, np.float32)
+    _check(lib, lib.smst_debug_pcm_convert_levelled(device, fmt, S, channels, pc, C.c_void_p(src.ctypes.data), src_ss, src_cs, C.c_void_p(dst.ctypes.data), dst_ss, dst_fs,
+                                                    pm, ps, pf, pg, clamped.ctypes.data_as(C.POINTER(_ll)), nans.ctypes.data_as(C.POINTER(_ll)), peaks.ctypes.data_as(_fp)))
+    return clamped, nans, peaks
+
+
+def debug_clip_copy_levelled(fmt, segments, channels, src, src_ss, src_cs, dst, dst_ss, dst_fs, level_modes, gains, ceilings, dither_modes, seeds, device=0, lib=None):
+    """smst_debug_clip_copy_levelled on numpy buffers (src the planar float32 image, dst the frames; segments int [S, 2, 4])
+    -> (clamped, nans int64 [S], peaks, applied float32 [S])"""
+    lib = lib if lib is not None else load_library()
+    seg = np.ascontiguousarray(segments, np.int32)
+    S = seg.shape[0]
+    keep, (pl, pg, pc, pd, ps) = _level_arrays(S, ("i", level_modes), ("f", gains), ("f", ceilings), ("i", dither_modes), ("l", seeds))
+    clamped, nans = np.full(S, -1, np.int64), np.full(S, -1, np.int64)
+    peaks, applied = np.full(S, -1, np.float32), np.full(S, -1, np.float32)
+    _check(lib, lib.smst_debug_clip_copy_levelled(device, fmt, S, channels, seg.ctypes.data_as(_ip), C.c_void_p(src.ctypes.data), src_ss, src_cs, C.c_void_p(dst.ctypes.data), dst_ss, dst_fs,
+                                                  pl, pg, pc, pd, ps, clamped.ctypes.data_as(C.POINTER(_ll)), nans.ctypes.data_as(C.POINTER(_ll)),
+                                                  peaks.ctypes.data_as(_fp), applied.ctypes.data_as(_fp)))
+    return clamped, nans, peaks, applied
 
 
 def launch_count(name, lib=None):
@@ -570,6 +612,26 @@ class StretchBatch:
         _check(self.lib, self.lib.smst_batch_take_pcm_overs(self.h, clamped.ctypes.data_as(C.POINTER(_ll)), nans.ctypes.data_as(C.POINTER(_ll))))
         self._inflight = []
         return clamped, nans
+
+    def set_pcm_level(self, mode, gain=1.0, ceiling=1.0, stream=-1):
+        """Level of the frame output (include/smst.h, "Level"): LEVEL_FIXED (w = v*gain in processFrames, flushFrames and exactFrames) or, for
+        exactFrames only, LEVEL_PROTECT (the gain, lowered to ceiling/peak where the clip would exceed the ceiling) and LEVEL_NORMALISE
+        (ceiling/peak), peak being the clip's own.  stream = -1: every stream.  The batch uses the levelled kernels from the first call on."""
+        _check(self.lib, self.lib.smst_batch_set_pcm_level(self.h, int(stream), int(mode), float(gain), float(ceiling)))
+
+    def pcm_level(self, stream):
+        """-> (mode, gain, ceiling) of the stream"""
+        mode, gain, ceiling = C.c_int(0), C.c_float(0), C.c_float(0)
+        _check(self.lib, self.lib.smst_batch_pcm_level(self.h, int(stream), C.byref(mode), C.byref(gain), C.byref(ceiling)))
+        return mode.value, gain.value, ceiling.value
+
+    def take_pcm_peaks(self):
+        """-> (peaks, gains), float32 [S]: per stream, the largest |v| the levelled frame conversions met before the gain since the last take
+        (NaN skipped; 0 if none) and the gain the newest one applied (1 before any).  Synchronises the batch and clears the peaks."""
+        peaks, gains = np.zeros(self.streams, np.float32), np.zeros(self.streams, np.float32)
+        _check(self.lib, self.lib.smst_batch_take_pcm_peaks(self.h, peaks.ctypes.data_as(_fp), gains.ctypes.data_as(_fp)))
+        self._inflight = []
+        return peaks, gains
 
     # --- test hooks
     def debug_state(self, stream, which):

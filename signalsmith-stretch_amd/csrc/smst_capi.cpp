@@ -67,12 +67,13 @@ struct smst_batch {
 	PinnedBytes hPcmIn, hPcmOut;
 	// ... and, behind the counts, the dither entries of the call's output conversion ([S] smst::PcmDither, uploaded with the output counts by a
 	// call that dithers: pcmUploadDither)
-	struct PcmCounts { // [2*S]: input frames, output frames; [S] dither entries
+	struct PcmCounts { // [2*S]: input frames, output frames; [S] dither entries; [S] level entries
 		Buffer<int, true> host;
 		Buffer<int, false> dev;
 		hipEvent_t done = nullptr;
 		bool used = false;
 		const smst::PcmDither *dither = nullptr; // the call's entries in `dev`; null: the call does not dither
+		smst::PcmLevelIo level;                  // ... and its level entries, behind them, with the batch's meters; table null: the call is not levelled
 		~PcmCounts() { if (done) hipEventDestroy(done); }
 	} pcmCounts[2];
 	int pcmCur = 0;
@@ -82,6 +83,14 @@ struct smst_batch {
 	// overs of the output conversions ([S][2]: clamped, NaN): the kernels add to them, smst_batch_take_pcm_overs reads and clears them
 	Buffer<unsigned, false> dPcmOvers;
 	std::vector<unsigned> hPcmOvers;
+	// level of the output conversions (smst_batch_set_pcm_level): per stream the mode, the gain and the ceiling; the batch is a levelled one from
+	// the first set on.  Device: [3][S] words -- the peaks since the last take (float bits), the gains the newest conversions applied, and
+	// the clip peaks of the newest exact call (kClipPeak's; stream-ordered, so one set serves calls in flight)
+	struct PcmLevelState { int mode = SMST_LEVEL_FIXED; float gain = 1.0f, ceiling = 1.0f; };
+	std::vector<PcmLevelState> pcmLevel;
+	bool pcmLevelled = false;
+	Buffer<int, false> dPcmLevel;
+	std::vector<int> hPcmLevel;
 	~smst_batch() { if (engine) hipSetDevice(engine->device()); } // (the buffers above go behind it, the engine last)
 };
 
@@ -164,6 +173,18 @@ struct FlushCounts {
 };
 
 static size_t pcmOversBytes(int streams) { return (size_t)2*streams*sizeof(unsigned); }
+static size_t pcmLevelBytes(int streams) { return (size_t)3*streams*sizeof(int); }
+// the meters as a batch begins with them: no peak, gain 1, no clip peak
+static void pcmLevelStart(std::vector<int> &words, int streams) {
+	const float one = 1.0f;
+	words.assign((size_t)3*streams, 0);
+	for (int s = 0; s < streams; ++s) std::memcpy(&words[(size_t)streams + s], &one, sizeof one);
+}
+static smst::PcmLevelIo pcmLevelIo(const smst::PcmLevel *table, int *words, int streams) {
+	smst::PcmLevelIo io;
+	io.table = table; io.peaks = words; io.applied = reinterpret_cast<float *>(words + streams); io.clipPeak = words + 2*(size_t)streams;
+	return io;
+}
 
 extern "C" {
 
@@ -191,6 +212,10 @@ int smst_batch_create_ex(smst_batch **out, int streams, int channels, int block,
 	b->pcmDither.assign((size_t)streams, smst_batch::PcmDitherState());
 	b->dPcmOvers.allocate((size_t)2*streams, "PCM overs");
 	if (hipMemset(b->dPcmOvers, 0, pcmOversBytes(streams)) != hipSuccess) throw smst::Error("hipMemset (PCM overs) failed", true);
+	b->pcmLevel.assign((size_t)streams, smst_batch::PcmLevelState());
+	pcmLevelStart(b->hPcmLevel, streams);
+	b->dPcmLevel.allocate((size_t)3*streams, "PCM level");
+	if (hipMemcpy(b->dPcmLevel, b->hPcmLevel.data(), pcmLevelBytes(streams), hipMemcpyHostToDevice) != hipSuccess) throw smst::Error("hipMemcpy (PCM level) failed", true);
 	*out = b.release();
 	return SMST_OK;
 	SMST_CATCH
@@ -224,7 +249,7 @@ BATCH_Q(smst_batch_output_latency, b->engine->outputLatency())
 BATCH_Q(smst_batch_seek_length, b->engine->seekLength())
 BATCH_Q(smst_batch_half_state, b->engine->halfPrecisionState() ? 1 : 0)
 int smst_batch_output_seek_length(const smst_batch *b, float rate) { if (!b || !b->engine) return fail("null batch"); return b->engine->outputSeekLength(rate); }
-long long smst_batch_workspace_bytes(const smst_batch *b) { if (!b || !b->engine) return fail("null batch"); return (long long)(b->engine->workspaceBytes() + (b->dPcmOvers ? pcmOversBytes(b->engine->streams()) : 0)); }
+long long smst_batch_workspace_bytes(const smst_batch *b) { if (!b || !b->engine) return fail("null batch"); return (long long)(b->engine->workspaceBytes() + (b->dPcmOvers ? pcmOversBytes(b->engine->streams()) : 0) + (b->dPcmLevel ? pcmLevelBytes(b->engine->streams()) : 0)); }
 
 #define BATCH_CALL(...) if (!b || !b->engine) return fail("null batch"); SMST_TRY __VA_ARGS__; return SMST_OK; SMST_CATCH
 
@@ -412,7 +437,7 @@ static smst_batch::PcmCounts &beginPcmCall(smst_batch *b) {
 	smst_batch::PcmCounts &c = b->pcmCounts[b->pcmCur];
 	if (!c.host) {
 		++b->stagingAllocs;
-		const size_t ints = (size_t)2*e.streams() + (size_t)e.streams()*(sizeof(smst::PcmDither)/sizeof(int));
+		const size_t ints = (size_t)2*e.streams() + (size_t)e.streams()*((sizeof(smst::PcmDither) + sizeof(smst::PcmLevel))/sizeof(int));
 		c.host.allocate(ints, "PCM counts");
 		c.dev.allocate(ints, "PCM counts");
 		if (hipEventCreateWithFlags(&c.done, hipEventDisableTiming) != hipSuccess) throw smst::Error("hipEventCreate failed", true);
@@ -420,6 +445,7 @@ static smst_batch::PcmCounts &beginPcmCall(smst_batch *b) {
 	if (c.used && hipEventSynchronize(c.done) != hipSuccess) throw smst::Error("hipEventSynchronize failed", true);
 	c.used = false;
 	c.dither = nullptr;
+	c.level = smst::PcmLevelIo();
 	return c;
 }
 // whether a call of this format dithers: a stream has a mode, and the format has a step to dither
@@ -430,20 +456,26 @@ static bool pcmDithers(const smst_batch *b, int format) {
 }
 // ... if so the call's entries are filled -- every stream's mode and hash, and its frame counter as the index of the call's first frame --
 // and uploaded, with the S output counts in front of them where the call has some (still one copy); c.dither is where the kernels read
-// them.  The only place that knows that the entries lie behind the 2*S counts.
+// them.  A levelled batch's calls carry the streams' level entries behind the dither entries (which then travel whether the call dithers or
+// not: still one copy); c.level has them and the batch's meters.  The only place that knows that the entries lie behind the 2*S counts.
 static void pcmUploadDither(smst_batch *b, smst_batch::PcmCounts &c, int format, bool withOutCounts) {
 	Batch &e = *b->engine;
 	const size_t S = size_t(e.streams()), first = withOutCounts ? S : 2*S;
-	const bool dithered = pcmDithers(b, format);
-	if (dithered) {
+	const bool dithered = pcmDithers(b, format), levelled = b->pcmLevelled;
+	if (levelled) {
+		smst::PcmLevel *t = reinterpret_cast<smst::PcmLevel *>(reinterpret_cast<smst::PcmDither *>(c.host + 2*S) + S);
+		for (size_t s = 0; s < S; ++s) t[s] = smst::PcmLevel{unsigned(b->pcmLevel[s].mode), b->pcmLevel[s].gain, b->pcmLevel[s].ceiling, 0u};
+		c.level = pcmLevelIo(reinterpret_cast<const smst::PcmLevel *>(reinterpret_cast<const smst::PcmDither *>(c.dev + 2*S) + S), b->dPcmLevel, int(S));
+	}
+	if (dithered || levelled) {
 		smst::PcmDither *t = reinterpret_cast<smst::PcmDither *>(c.host + 2*S);
 		for (size_t s = 0; s < S; ++s) {
 			const smst_batch::PcmDitherState &d = b->pcmDither[s];
 			t[s] = smst::PcmDither{unsigned(d.mode), d.h, unsigned(d.frames), unsigned(d.frames >> 32)};
 		}
-		c.dither = reinterpret_cast<const smst::PcmDither *>(c.dev + 2*S);
+		if (dithered) c.dither = reinterpret_cast<const smst::PcmDither *>(c.dev + 2*S);
 	}
-	const size_t bytes = (2*S - first)*sizeof(int) + (dithered ? S*sizeof(smst::PcmDither) : 0);
+	const size_t bytes = (2*S - first)*sizeof(int) + (levelled ? S*(sizeof(smst::PcmDither) + sizeof(smst::PcmLevel)) : dithered ? S*sizeof(smst::PcmDither) : 0);
 	if (hipMemcpyAsync(c.dev + first, c.host + first, bytes, hipMemcpyHostToDevice, e.stream()) != hipSuccess) throw smst::Error("hipMemcpyAsync (H2D) failed", true);
 }
 // after a call that emitted n[s] frames: the counters of the streams that have a mode move on, whatever the call's format
@@ -531,12 +563,12 @@ static void pcmStageOut(smst_batch *b, smst_batch::PcmCounts &c, void *out, long
 	const int most = countsOf(n, S).most;
 	hipSetDevice(e.device());
 	if (memory == SMST_MEM_DEVICE) {
-		smst::launchPcmOut(format, b->dOut, (long long)C*maxLen, maxLen, out, ss, fs, c.dev + S, S, C, most, b->dPcmOvers, e.stream(), c.dither);
+		smst::launchPcmOut(format, b->dOut, (long long)C*maxLen, maxLen, out, ss, fs, c.dev + S, S, C, most, b->dPcmOvers, e.stream(), c.dither, c.level);
 		pcmAdvanceDither(b, n);
 		return;
 	}
 	if (most >= 1) {
-		smst::launchPcmOut(format, b->dOut, (long long)C*maxLen, maxLen, b->dPcmOut, pcmRowElems(most, C), C, c.dev + S, S, C, most, b->dPcmOvers, e.stream(), c.dither);
+		smst::launchPcmOut(format, b->dOut, (long long)C*maxLen, maxLen, b->dPcmOut, pcmRowElems(most, C), C, c.dev + S, S, C, most, b->dPcmOvers, e.stream(), c.dither, c.level);
 		pcmRawOut(b, out, ss, fs, n, most, format);
 	}
 	pcmAdvanceDither(b, n);
@@ -565,6 +597,37 @@ int smst_batch_pcm_dither(const smst_batch *b, int stream, int *mode, long long 
 	if (frames) *frames = (long long)d.frames;
 	return SMST_OK;
 }
+static void checkPcmLevel(int mode, float gain, float ceiling) {
+	if (mode != SMST_LEVEL_FIXED && mode != SMST_LEVEL_PROTECT && mode != SMST_LEVEL_NORMALISE) throw smst::Error("unknown level mode (SMST_LEVEL_FIXED, _PROTECT or _NORMALISE)");
+	if (!std::isfinite(gain)) throw smst::Error("level: the gain is not finite");
+	if (mode == SMST_LEVEL_PROTECT && !(gain > 0)) throw smst::Error("level: SMST_LEVEL_PROTECT needs a gain above 0");
+	if (mode != SMST_LEVEL_FIXED && !(std::isfinite(ceiling) && ceiling > 0)) throw smst::Error("level: the whole-clip modes need a finite ceiling above 0");
+}
+int smst_batch_set_pcm_level(smst_batch *b, int stream, int mode, float gain, float ceiling) {
+	BATCH_CALL({
+		const int S = b->engine->streams();
+		checkPcmLevel(mode, gain, ceiling);
+		if (stream < -1 || stream >= S) throw smst::Error("stream index out of range");
+		for (int s = stream < 0 ? 0 : stream; s < (stream < 0 ? S : stream + 1); ++s) b->pcmLevel[s] = smst_batch::PcmLevelState{mode, gain, ceiling};
+		b->pcmLevelled = true;
+	})
+}
+int smst_batch_pcm_level(const smst_batch *b, int stream, int *mode, float *gain, float *ceiling) {
+	if (!b || !b->engine) return fail("null batch");
+	if (stream < 0 || stream >= b->engine->streams()) return fail("stream index out of range");
+	const smst_batch::PcmLevelState &l = b->pcmLevel[stream];
+	if (mode) *mode = l.mode;
+	if (gain) *gain = l.gain;
+	if (ceiling) *ceiling = l.ceiling;
+	return SMST_OK;
+}
+// a streaming call knows no clip: refused, before anything runs, where a stream that takes part (active null: every one) has a whole-clip mode
+static void refuseWholeClipLevel(const smst_batch *b, const unsigned char *active) {
+	if (!b->pcmLevelled) return;
+	for (size_t s = 0; s < b->pcmLevel.size(); ++s)
+		if ((!active || active[s]) && b->pcmLevel[s].mode != SMST_LEVEL_FIXED)
+			throw smst::Error("stream " + std::to_string(s) + " has a whole-clip level mode (SMST_LEVEL_PROTECT / _NORMALISE): smst_batch_exact_pcm only");
+}
 int smst_batch_process_pcm(smst_batch *b, const void *in, long long iss, long long ifs, const int *inSamples,
                            void *out, long long oss, long long ofs, const int *outSamples, int format, int memory) {
 	BATCH_CALL({
@@ -572,6 +635,7 @@ int smst_batch_process_pcm(smst_batch *b, const void *in, long long iss, long lo
 		checkPcmFormat(format, memory);
 		checkPcmSide(in, ifs, inSamples, e.streams(), e.channels(), false);
 		checkPcmSide(out, ofs, outSamples, e.streams(), e.channels(), false);
+		refuseWholeClipLevel(b, nullptr);
 		smst_batch::PcmCounts &c = beginPcmCall(b);
 		const int maxIn = pcmStageIn(b, c, in, iss, ifs, inSamples, format, memory);
 		const int maxOut = pcmPrepareOut(b, c, outSamples, format, memory);
@@ -598,6 +662,7 @@ int smst_batch_flush_pcm(smst_batch *b, void *out, long long oss, long long ofs,
 		checkPcmFormat(format, memory);
 		checkPcmSide(out, ofs, outSamples, e.streams(), e.channels(), true);
 		const FlushCounts f(outSamples, e.streams());
+		refuseWholeClipLevel(b, f.active.data());
 		smst_batch::PcmCounts &c = beginPcmCall(b);
 		const int maxOut = pcmPrepareOut(b, c, f.counts.data(), format, memory);
 		e.flush(b->dOut, (long long)e.channels()*maxOut, maxOut, f.counts.data(), rates, f.mask());
@@ -674,18 +739,22 @@ int smst_batch_exact_pcm(smst_batch *b, const void *in, long long iss, long long
 		checkExactArgs(e, in, inSamples, out, outSamples, ifs, ofs, true, memory);
 		// a dithered call: the streams' modes and hashes ride in the _pcm calls' table (the frame index is the place in the clip: the counters
 		// are neither read nor moved)
-		smst_batch::PcmCounts *table = pcmDithers(b, format) ? &beginPcmCall(b) : nullptr;
+		smst_batch::PcmCounts *table = pcmDithers(b, format) || b->pcmLevelled ? &beginPcmCall(b) : nullptr;
 		if (table) pcmUploadDither(b, *table, format, false);
 		const smst::PcmDither *dither = table ? table->dither : nullptr;
+		// a levelled call: the entries ride there too; the streams whose gain comes from their clip's peak decide whether kClipPeak runs
+		const smst::PcmLevelIo level = table ? table->level : smst::PcmLevelIo();
+		std::vector<unsigned char> wholeClip;
+		if (level.table) for (const smst_batch::PcmLevelState &l : b->pcmLevel) wholeClip.push_back(l.mode != SMST_LEVEL_FIXED);
 		if (memory == SMST_MEM_DEVICE) {
-			runExact(e, Batch::ClipIo{in, iss, ifs, out, oss, ofs, format, b->dPcmOvers, dither}, inSamples, outSamples, status);
+			runExact(e, Batch::ClipIo{in, iss, ifs, out, oss, ofs, format, b->dPcmOvers, dither, level, wholeClip.data()}, inSamples, outSamples, status);
 		} else {
 			const int S = e.streams(), C = e.channels();
 			std::vector<int> nIn, nOut;
 			const int mostIn = exactCounts(inSamples, outSamples, S, nIn), mostOut = exactCounts(outSamples, outSamples, S, nOut);
 			ensurePcmBytes(b, b->hPcmOut, b->dPcmOut, (size_t)S*pcmRowElems(mostOut, C)*pcmElemBytes(format));
 			pcmRawIn(b, in, iss, ifs, nIn.data(), mostIn, format);
-			runExact(e, Batch::ClipIo{b->dPcmIn, pcmRowElems(mostIn, C), C, b->dPcmOut, pcmRowElems(mostOut, C), C, format, b->dPcmOvers, dither}, inSamples, outSamples, status);
+			runExact(e, Batch::ClipIo{b->dPcmIn, pcmRowElems(mostIn, C), C, b->dPcmOut, pcmRowElems(mostOut, C), C, format, b->dPcmOvers, dither, level, wholeClip.data()}, inSamples, outSamples, status);
 			pcmRawOut(b, out, oss, ofs, nOut.data(), mostOut, format);
 		}
 		if (table) endPcmCall(b, *table);
@@ -694,10 +763,10 @@ int smst_batch_exact_pcm(smst_batch *b, const void *in, long long iss, long long
 } // extern "C"
 // What the two debug converters are: the launch of one conversion kernel on device copies of the caller's buffers, which sit as far behind a
 // 16-byte boundary as the caller's own do; the launch's table (the counts, or the segments) and, uploaded in front of everything, `first`
-// (the dither entries; 0 bytes: none); the overs zeroed and, `counted`, read back.  launch(src, dst, table, first, overs) runs on the null
-// stream.  name: the hook's, in front of a HIP error.
+// (the dither entries, a levelled hook's DebugLevel block behind them; 0 bytes: none; firstBack, may be null: where it is read back to); the
+// overs zeroed and, `counted`, read back.  launch(src, dst, table, first, overs) runs on the null stream.  name: the hook's, in front of a HIP error.
 template <typename Launch> static void debugConvert(const std::string &name, int streams, const void *src, size_t srcBytes, void *dst, size_t dstBytes, const void *table, size_t tableBytes,
-		const void *first, size_t firstBytes, bool counted, long long *clamped, long long *nans, Launch launch) {
+		const void *first, size_t firstBytes, bool counted, long long *clamped, long long *nans, Launch launch, void *firstBack = nullptr) {
 	auto hip = [&](hipError_t err) { if (err != hipSuccess) throw smst::Error(name + ": " + hipGetErrorString(err), true); };
 	Buffer<unsigned char, false> dSrc, dDst, dTable, dFirst, dOvers; // freed when the function leaves, whichever way
 	std::vector<unsigned> overs((size_t)2*streams, 0u);
@@ -721,14 +790,44 @@ template <typename Launch> static void debugConvert(const std::string &name, int
 	hip(hipStreamSynchronize(nullptr));
 	if (dstBytes) hip(hipMemcpy(dst, d0, dstBytes, hipMemcpyDeviceToHost));
 	if (counted) hip(hipMemcpy(overs.data(), dOvers, pcmOversBytes(streams), hipMemcpyDeviceToHost));
+	if (firstBack && firstBytes) hip(hipMemcpy(firstBack, dFirst, firstBytes, hipMemcpyDeviceToHost));
 	for (int s = 0; s < streams; ++s) {
 		if (clamped) clamped[s] = overs[2*s];
 		if (nans) nans[s] = overs[2*s + 1];
 	}
 }
+// A levelled hook's `first` block: [S] dither entries (always present, mode 0 where the hook has none), [S] level entries, the [3][S] meter
+// words of a fresh batch.  io(base): the launch's PcmLevelIo where the block lies at `base`; results(): the peaks and the applied gains
+struct DebugLevel {
+	int S;
+	std::vector<unsigned char> block;
+	DebugLevel(int streams, const std::vector<smst::PcmDither> &dither, const int *modes, const float *gains, const float *ceilings) : S(streams) {
+		std::vector<smst::PcmLevel> level;
+		for (int s = 0; s < S; ++s) {
+			const int mode = modes ? modes[s] : SMST_LEVEL_FIXED;
+			checkPcmLevel(mode, gains[s], ceilings ? ceilings[s] : 1.0f);
+			level.push_back(smst::PcmLevel{unsigned(mode), gains[s], ceilings ? ceilings[s] : 1.0f, 0u});
+		}
+		std::vector<int> words;
+		pcmLevelStart(words, S);
+		block.resize((size_t)S*(sizeof(smst::PcmDither) + sizeof(smst::PcmLevel)) + pcmLevelBytes(S));
+		std::memcpy(block.data(), dither.data(), S*sizeof(smst::PcmDither));
+		std::memcpy(block.data() + S*sizeof(smst::PcmDither), level.data(), S*sizeof(smst::PcmLevel));
+		std::memcpy(block.data() + S*(sizeof(smst::PcmDither) + sizeof(smst::PcmLevel)), words.data(), pcmLevelBytes(S));
+	}
+	smst::PcmLevelIo io(const unsigned char *base) const {
+		unsigned char *words = const_cast<unsigned char *>(base) + S*(sizeof(smst::PcmDither) + sizeof(smst::PcmLevel));
+		return pcmLevelIo(reinterpret_cast<const smst::PcmLevel *>(base + S*sizeof(smst::PcmDither)), reinterpret_cast<int *>(words), S);
+	}
+	void results(float *peaks, float *applied) const {
+		const unsigned char *words = block.data() + S*(sizeof(smst::PcmDither) + sizeof(smst::PcmLevel));
+		if (peaks) std::memcpy(peaks, words, S*sizeof(float));
+		if (applied) std::memcpy(applied, words + S*sizeof(float), S*sizeof(float));
+	}
+};
 static int pcmConvert(int device, int dir, int format, int streams, int channels, const int *counts,
                       const void *src, long long srcSS, long long srcInner, void *dst, long long dstSS, long long dstInner, long long *clamped, long long *nans,
-                      const int *modes = nullptr, const long long *seeds = nullptr, const long long *firstFrames = nullptr) {
+                      const int *modes = nullptr, const long long *seeds = nullptr, const long long *firstFrames = nullptr, const float *gains = nullptr, float *peaks = nullptr) {
 	SMST_TRY
 	checkPcmFormat(format, SMST_MEM_HOST);
 	if (dir != 0 && dir != 1) throw smst::Error("pcm convert: dir is 0 (PCM -> planar) or 1 (planar -> PCM)");
@@ -756,6 +855,16 @@ static int pcmConvert(int device, int dir, int format, int streams, int channels
 			dithered = dithered || modes[s] != SMST_DITHER_NONE;
 		}
 	}
+	if (gains) { // the levelled kernel: fixed gains, the meters of a fresh batch
+		DebugLevel level(streams, dither, nullptr, gains, nullptr);
+		debugConvert("pcm convert", streams, src, srcBytes, dst, dstBytes, counts, streams*sizeof(int), level.block.data(), level.block.size(), clamped || nans, clamped, nans,
+		             [&](unsigned char *s0, unsigned char *d0, const unsigned char *dCounts, const unsigned char *dFirst, unsigned *dOvers) {
+			smst::launchPcmOut(format, reinterpret_cast<const float *>(s0), srcSS, srcInner, d0, dstSS, dstInner, reinterpret_cast<const int *>(dCounts), streams, channels, most, dOvers, nullptr,
+			                   dithered ? reinterpret_cast<const smst::PcmDither *>(dFirst) : nullptr, level.io(dFirst));
+		}, level.block.data());
+		level.results(peaks, nullptr);
+		return SMST_OK;
+	}
 	debugConvert("pcm convert", streams, src, srcBytes, dst, dstBytes, counts, streams*sizeof(int), dither.data(), dithered ? streams*sizeof(smst::PcmDither) : 0,
 	             dir == 1 && (clamped || nans), clamped, nans, [&](unsigned char *s0, unsigned char *d0, const unsigned char *dCounts, const unsigned char *dDither, unsigned *dOvers) {
 		const int *n = reinterpret_cast<const int *>(dCounts);
@@ -782,10 +891,18 @@ int smst_debug_pcm_convert_dithered(int device, int format, int streams, int cha
 	if (!modes || !seeds || !firstFrames) return fail("pcm convert: null dither arrays");
 	return pcmConvert(device, 1, format, streams, channels, counts, src, srcSS, srcInner, dst, dstSS, dstInner, clamped, nans, modes, seeds, firstFrames);
 }
-// the two clip kernels alone (smst_clip.h): see include/smst.h
-int smst_debug_clip_copy(int device, int dir, int format, int streams, int channels, const int *segments,
-                         const void *src, long long srcSS, long long srcInner, void *dst, long long dstSS, long long dstInner,
-                         long long *clamped, long long *nans) {
+int smst_debug_pcm_convert_levelled(int device, int format, int streams, int channels, const int *counts,
+                                    const void *src, long long srcSS, long long srcInner, void *dst, long long dstSS, long long dstInner,
+                                    const int *modes, const long long *seeds, const long long *firstFrames, const float *gains, long long *clamped, long long *nans, float *peaks) {
+	if (!modes || !seeds || !firstFrames || !gains) return fail("pcm convert: null dither or gain arrays");
+	return pcmConvert(device, 1, format, streams, channels, counts, src, srcSS, srcInner, dst, dstSS, dstInner, clamped, nans, modes, seeds, firstFrames, gains, peaks);
+}
+} // extern "C"
+// the clip kernels alone (smst_clip.h): see include/smst.h.  levelModes set: kClipPeak and the levelled kClipOut, into a frame format
+static int clipCopy(int device, int dir, int format, int streams, int channels, const int *segments,
+                    const void *src, long long srcSS, long long srcInner, void *dst, long long dstSS, long long dstInner, long long *clamped, long long *nans,
+                    const int *levelModes = nullptr, const float *gains = nullptr, const float *ceilings = nullptr, const int *ditherModes = nullptr, const long long *seeds = nullptr,
+                    float *peaks = nullptr, float *applied = nullptr) {
 	SMST_TRY
 	if (format != 0) checkPcmFormat(format, SMST_MEM_HOST);
 	if (dir != 0 && dir != 1) throw smst::Error("clip copy: dir is 0 (caller's buffer -> planar image) or 1 (planar image -> caller's buffer)");
@@ -809,6 +926,27 @@ int smst_debug_clip_copy(int device, int dir, int format, int streams, int chann
 	};
 	const size_t srcBytes = spanBytes(srcFrames, srcEnd, srcSS, srcInner), dstBytes = spanBytes(dstFrames, dstEnd, dstSS, dstInner);
 	if (hipSetDevice(device) != hipSuccess) throw smst::Error("hipSetDevice failed", true);
+	if (levelModes) {
+		std::vector<smst::PcmDither> dither;
+		bool dithered = false;
+		for (int s = 0; s < streams; ++s) {
+			if (ditherModes[s] != SMST_DITHER_NONE && ditherModes[s] != SMST_DITHER_TPDF && ditherModes[s] != SMST_DITHER_TPDF_HP) throw smst::Error("unknown dither mode (SMST_DITHER_NONE, _TPDF or _TPDF_HP)");
+			dither.push_back(smst::PcmDither{unsigned(ditherModes[s]), smst::pcmDitherHash(seeds[s]), 0u, 0u});
+			dithered = dithered || ditherModes[s] != SMST_DITHER_NONE;
+		}
+		dithered = dithered && (format == SMST_PCM_S16 || format == SMST_PCM_S24);
+		DebugLevel level(streams, dither, levelModes, gains, ceilings);
+		debugConvert("clip copy", streams, src, srcBytes, dst, dstBytes, segments, (size_t)2*streams*sizeof(smst::ClipSeg), level.block.data(), level.block.size(), clamped || nans, clamped, nans,
+		             [&](unsigned char *s0, unsigned char *d0, const unsigned char *dSegs, const unsigned char *dFirst, unsigned *dOvers) {
+			const smst::ClipSeg *segs = reinterpret_cast<const smst::ClipSeg *>(dSegs);
+			const smst::PcmLevelIo io = level.io(dFirst);
+			smst::launchClipPeak(reinterpret_cast<const float *>(s0), srcSS, srcInner, segs, streams, channels, most, io.clipPeak, nullptr);
+			smst::launchClipOut(format, reinterpret_cast<const float *>(s0), srcSS, srcInner, d0, dstSS, dstInner, segs, streams, channels, most, dOvers, nullptr,
+			                    dithered ? reinterpret_cast<const smst::PcmDither *>(dFirst) : nullptr, io);
+		}, level.block.data());
+		level.results(peaks, applied);
+		return SMST_OK;
+	}
 	debugConvert("clip copy", streams, src, srcBytes, dst, dstBytes, segments, (size_t)2*streams*sizeof(smst::ClipSeg), nullptr, 0, dstFrames && (clamped || nans), clamped, nans,
 	             [&](unsigned char *s0, unsigned char *d0, const unsigned char *dSegs, const unsigned char *, unsigned *dOvers) {
 		const smst::ClipSeg *segs = reinterpret_cast<const smst::ClipSeg *>(dSegs);
@@ -817,6 +955,20 @@ int smst_debug_clip_copy(int device, int dir, int format, int streams, int chann
 	});
 	return SMST_OK;
 	SMST_CATCH
+}
+extern "C" {
+int smst_debug_clip_copy(int device, int dir, int format, int streams, int channels, const int *segments,
+                         const void *src, long long srcSS, long long srcInner, void *dst, long long dstSS, long long dstInner,
+                         long long *clamped, long long *nans) {
+	return clipCopy(device, dir, format, streams, channels, segments, src, srcSS, srcInner, dst, dstSS, dstInner, clamped, nans);
+}
+int smst_debug_clip_copy_levelled(int device, int format, int streams, int channels, const int *segments,
+                                  const void *src, long long srcSS, long long srcInner, void *dst, long long dstSS, long long dstInner,
+                                  const int *levelModes, const float *gains, const float *ceilings, const int *ditherModes, const long long *seeds,
+                                  long long *clamped, long long *nans, float *peaks, float *applied) {
+	if (format == 0) return fail("clip copy: the levelled form writes frames of an SMST_PCM_* format");
+	if (!levelModes || !gains || !ceilings || !ditherModes || !seeds) return fail("clip copy: null level or dither arrays");
+	return clipCopy(device, 1, format, streams, channels, segments, src, srcSS, srcInner, dst, dstSS, dstInner, clamped, nans, levelModes, gains, ceilings, ditherModes, seeds, peaks, applied);
 }
 int smst_batch_take_pcm_overs(smst_batch *b, long long *clamped, long long *nans) {
 	BATCH_CALL({
@@ -831,6 +983,20 @@ int smst_batch_take_pcm_overs(smst_batch *b, long long *clamped, long long *nans
 			if (clamped) clamped[s] = b->hPcmOvers[2*s];
 			if (nans) nans[s] = b->hPcmOvers[2*s + 1];
 		}
+	})
+}
+
+int smst_batch_take_pcm_peaks(smst_batch *b, float *peaks, float *gains) {
+	BATCH_CALL({
+		Batch &e = *b->engine;
+		const size_t S = size_t(e.streams());
+		e.synchronize();
+		if (!b->dPcmLevel) throw smst::Error("this batch has no PCM level meters");
+		hipSetDevice(e.device());
+		if (hipMemcpy(b->hPcmLevel.data(), b->dPcmLevel, 2*S*sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) throw smst::Error("hipMemcpy (PCM level) failed", true);
+		if (hipMemset(b->dPcmLevel, 0, S*sizeof(int)) != hipSuccess) throw smst::Error("hipMemset (PCM level) failed", true);
+		if (peaks) std::memcpy(peaks, b->hPcmLevel.data(), S*sizeof(float));
+		if (gains) std::memcpy(gains, b->hPcmLevel.data() + S, S*sizeof(float));
 	})
 }
 

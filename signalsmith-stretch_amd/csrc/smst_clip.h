@@ -4,7 +4,9 @@
 // fp32 images of its own in which every stream's stage begins at one column, and the two kernels here move the clips: per stream two
 // segments (ClipSeg, smst_device.h) of `count` frames from frame `src` of the source to frame `dst` of the destination.
 //   kClipIn<T>   the caller's frames of format T -> the input image            (pcmTileIn of smst_pcm.h on a run that begins at the segment)
-//   kClipOut<T, Dith>  the output image -> the caller's frames, overs counted  (pcmTileOut; a "zeros" segment has no source; Dith: dithered)
+//   kClipOut<T, Dith, Level>  the output image -> the caller's frames, overs counted  (pcmTileOut; a "zeros" segment has no source; Dith: dithered;
+//                Level: every stream's gain applied -- a whole-clip gain formed from the clip's peak --, its peak metered)
+//   kClipPeak    the output image -> the peak of every stream's clip           (in front of a kClipOut that forms a whole-clip gain)
 //   kClipPlanar  planar fp32 -> planar fp32, either direction                  (the caller's buffer is planar itself)
 // Included by smst_state.hip only, behind smst_pcm.h: the conversion rule, the tiling of a run and the overs scheme are the ones defined there.
 //
@@ -36,9 +38,18 @@ template <typename T> __global__ __launch_bounds__(256) void kClipIn(const T *__
 
 // the planar image -> frames of format T.  overs (may be null): [S][2] counters as kPcmOut's (a run of zeros adds nothing: 0.0 has a code in every format).
 // Dith (int16 / int24): the frame index of a segment's first frame is its place in the clip, g.dst -- dither[s] gives the stream's mode and
-// hash only --, so a clip's codes do not depend on where its two segments meet; a run of zeros stays the code of 0.0
-template <typename T, bool Dith> __global__ __launch_bounds__(256) void kClipOut(const float *__restrict__ image, long long imageStreamStride, long long imageChannelStride,
-		T *__restrict__ out, long long outStreamStride, long long outFrameStride, const ClipSeg *__restrict__ segs, int C, unsigned *__restrict__ overs, const PcmDither *__restrict__ dither) {
+// hash only --, so a clip's codes do not depend on where its two segments meet; a run of zeros stays the code of 0.0.
+// Level: every workgroup forms its stream's gain by the same few correctly rounded fp32 operations (clipGain), so all of a clip's workgroups
+// agree on it without another launch; the workgroup of the first tile of the stream's first segment that has a source reports it in
+// level.applied[s]; a run of zeros is not levelled, metered or reported
+__device__ inline float clipGain(const PcmLevel &l, int peakBits) {
+	if (l.mode == kPcmLevelFixed || peakBits <= 0 || peakBits >= 0x7f800000) return l.gain; // (no peak, or none to divide by: the plain gain)
+	const float q = l.ceiling/__int_as_float(peakBits);
+	return (l.mode == kPcmLevelNormalise || !(l.gain <= q)) ? q : l.gain;
+}
+template <typename T, bool Dith, bool Level> __global__ __launch_bounds__(256) void kClipOut(const float *__restrict__ image, long long imageStreamStride, long long imageChannelStride,
+		T *__restrict__ out, long long outStreamStride, long long outFrameStride, const ClipSeg *__restrict__ segs, int C, unsigned *__restrict__ overs, const PcmDither *__restrict__ dither,
+		PcmLevelIo level) {
 	extern __shared__ __attribute__((aligned(16))) unsigned char smemRaw[];
 	const int s = blockIdx.y;
 	const ClipSeg g = segs[2*s + blockIdx.z];
@@ -47,8 +58,59 @@ template <typename T, bool Dith> __global__ __launch_bounds__(256) void kClipOut
 	PcmDither dp{0u, 0u, 0u, 0u};
 	if constexpr (Dith) dp = PcmDither{dither[s].mode, dither[s].h, unsigned(g.dst), 0u};
 	unsigned over;
-	if (!pcmTileOut<T, Dith>(src, imageChannelStride, out + (size_t)s*outStreamStride + (size_t)g.dst*outFrameStride, outFrameStride, g.count, blockIdx.x, C, reinterpret_cast<float *>(smemRaw), over, dp)) return;
+	if constexpr (Level) {
+		const PcmLevel l = level.table[s];
+		const float gain = clipGain(l, l.mode == kPcmLevelFixed ? 0 : level.clipPeak[s]);
+		unsigned peak;
+		if (!pcmTileOut<T, Dith, true>(src, imageChannelStride, out + (size_t)s*outStreamStride + (size_t)g.dst*outFrameStride, outFrameStride, g.count, blockIdx.x, C, reinterpret_cast<float *>(smemRaw), over, dp, gain, &peak)) return;
+		if (src) {
+			const ClipSeg first = segs[2*s];
+			const bool reports = blockIdx.z == 0 || first.count < 1 || first.zeros; // (segment 1 reports where segment 0 has no source)
+			if (reports && blockIdx.x == 0 && threadIdx.x == 0) level.applied[s] = gain;
+			pcmMaxPeak(level.peaks, s, peak);
+		}
+	} else {
+		if (!pcmTileOut<T, Dith>(src, imageChannelStride, out + (size_t)s*outStreamStride + (size_t)g.dst*outFrameStride, outFrameStride, g.count, blockIdx.x, C, reinterpret_cast<float *>(smemRaw), over, dp)) return;
+	}
 	pcmAddOvers(overs, s, over);
+}
+
+// The peak of every stream's clip: the largest pcmPeakBits of the image's samples that the stream's segments cover, into clipPeak[s].
+// grid (tiles of kClipTileFloats frames, S, 2 segments), 256 threads; a workgroup takes its tile of every channel's row in turn, as the
+// aligned 16-byte words inside the tile and, element by element, what lies in front of the first and behind the last of them (nothing
+// outside the tile is read); lane maximum -> wavefront -> workgroup through LDS -> one atomicMax where the tile holds anything above 0
+__global__ __launch_bounds__(256) void kClipPeak(const float *__restrict__ image, long long imageStreamStride, long long imageChannelStride, const ClipSeg *__restrict__ segs, int C,
+		int *__restrict__ clipPeak) {
+	extern __shared__ __attribute__((aligned(16))) unsigned char smemRaw[];
+	int *waveMost = reinterpret_cast<int *>(smemRaw); // [4]
+	const int s = blockIdx.y, tid = threadIdx.x;
+	const ClipSeg g = segs[2*s + blockIdx.z];
+	const int e0 = blockIdx.x*kClipTileFloats;
+	if (g.count < 1 || g.zeros || e0 >= g.count) return;
+	const int e1 = min(e0 + kClipTileFloats, g.count);
+	unsigned most = 0u;
+	for (int c = 0; c < C; ++c) {
+		const float *row = image + (size_t)s*imageStreamStride + (size_t)c*imageChannelStride + g.src;
+		const int back = int((reinterpret_cast<uintptr_t>(row + e0) >> 2) & 3u); // floats between the 16-byte boundary at or in front of row + e0 and it
+		const int nWords = (back + e1 - e0 + 3)/4;
+		for (int w = tid; w < nWords; w += 256) {
+			const int a = e0 - back + 4*w; // the word's first element in the run
+			if (a >= e0 && a + 4 <= e1) {
+				const PcmWord4 v = *reinterpret_cast<const PcmWord4 *>(row + a);
+				for (int k = 0; k < 4; ++k) most = max(most, pcmPeakBits(__int_as_float(int(v[k]))));
+			} else {
+				for (int k = 0; k < 4; ++k) if (a + k >= e0 && a + k < e1) most = max(most, pcmPeakBits(row[a + k]));
+			}
+		}
+	}
+	int m = int(most);
+	for (int k = 32; k; k >>= 1) m = max(m, __shfl(m, (tid & 63) ^ k));
+	if ((tid & 63) == 0) waveMost[tid >> 6] = m;
+	__syncthreads();
+	if (tid == 0) {
+		m = max(max(waveMost[0], waveMost[1]), max(waveMost[2], waveMost[3]));
+		if (m > 0) atomicMax(clipPeak + s, m);
+	}
 }
 
 // Tile t of one row's run of `total` floats, src (null: zeros) -> dst, through `lds`.  Every lane of the workgroup calls it.
@@ -115,7 +177,7 @@ void launchClipIn(int format, const void *in, long long inSS, long long inInner,
 	countLaunch(LK_CLIP_IN);
 }
 void launchClipOut(int format, const float *image, long long imageSS, long long imageCS, void *out, long long outSS, long long outInner, const ClipSeg *segs, int S, int C, int maxCount,
-                   unsigned *overs, hipStream_t st, const PcmDither *dither) {
+                   unsigned *overs, hipStream_t st, const PcmDither *dither, const PcmLevelIo &level) {
 	if (maxCount < 1) return;
 	const dim3 grid(divUp(maxCount, kPcmTileFrames), S, 2);
 	if (format == 0) {
@@ -126,10 +188,20 @@ void launchClipOut(int format, const float *image, long long imageSS, long long 
 	pcmDispatch(format, dither != nullptr, [&](auto tag, auto dithered) {
 		typedef typename decltype(tag)::type T;
 		constexpr bool Dith = decltype(dithered)::value;
-		hipLaunchKernelGGL((kClipOut<T, Dith>), grid, dim3(256), Dith ? pcmDitherLdsBytes(C) : pcmLdsBytes(C), st, image, imageSS, imageCS, static_cast<T *>(out), outSS, outInner, segs, C,
-		                   overs, dither);
-		countLaunch(Dith ? LK_CLIP_OUT_DITHERED : LK_CLIP_OUT);
+		const size_t lds = Dith ? pcmDitherLdsBytes(C) : pcmLdsBytes(C);
+		if (level.table) {
+			hipLaunchKernelGGL((kClipOut<T, Dith, true>), grid, dim3(256), lds, st, image, imageSS, imageCS, static_cast<T *>(out), outSS, outInner, segs, C, overs, dither, level);
+			countLaunch(LK_CLIP_OUT_LEVELLED);
+		} else {
+			hipLaunchKernelGGL((kClipOut<T, Dith, false>), grid, dim3(256), lds, st, image, imageSS, imageCS, static_cast<T *>(out), outSS, outInner, segs, C, overs, dither, level);
+			countLaunch(Dith ? LK_CLIP_OUT_DITHERED : LK_CLIP_OUT);
+		}
 	});
+}
+void launchClipPeak(const float *image, long long imageSS, long long imageCS, const ClipSeg *segs, int S, int C, int maxCount, int *clipPeak, hipStream_t st) {
+	if (maxCount < 1) return;
+	hipLaunchKernelGGL(kClipPeak, dim3(divUp(maxCount, kClipTileFloats), S, 2), dim3(256), 4*sizeof(int), st, image, imageSS, imageCS, segs, C, clipPeak);
+	countLaunch(LK_CLIP_PEAK);
 }
 
 } // namespace smst

@@ -161,7 +161,7 @@ __host__ __device__ inline bool analysisWindowInCall(int B, int M, int I, int in
 // form" tests assert through these that BOTH forms really ran.
 enum LaunchKind {
 	LK_VOC_ALIGNED, LK_VOC_STAGED, LK_VOC_GATHER, LK_VOC_N, LK_VOC_ONE, LK_VOC_ACROSS, LK_VOC_CONT, LK_CHAIN_UNFUSED,
-	LK_ANALYSE_TEAMS, LK_ANALYSE_FAST, LK_ANALYSE_GENERIC, LK_SYNTH_TEAMS, LK_SYNTH_FAST, LK_SYNTH_GENERIC, LK_SYNTH_EMIT, LK_EMIT_CARRIED, LK_FEED_ONE_PASS, LK_PCM_IN, LK_PCM_OUT, LK_CLIP_IN, LK_CLIP_OUT, LK_PCM_OUT_DITHERED, LK_CLIP_OUT_DITHERED, LK_COUNT
+	LK_ANALYSE_TEAMS, LK_ANALYSE_FAST, LK_ANALYSE_GENERIC, LK_SYNTH_TEAMS, LK_SYNTH_FAST, LK_SYNTH_GENERIC, LK_SYNTH_EMIT, LK_EMIT_CARRIED, LK_FEED_ONE_PASS, LK_PCM_IN, LK_PCM_OUT, LK_CLIP_IN, LK_CLIP_OUT, LK_PCM_OUT_DITHERED, LK_CLIP_OUT_DITHERED, LK_PCM_OUT_LEVELLED, LK_CLIP_OUT_LEVELLED, LK_CLIP_PEAK, LK_COUNT
 };
 long long launchCount(const char *name); // -1: unknown name
 
@@ -222,8 +222,16 @@ inline unsigned pcmDitherHash(long long seed) {
 	const unsigned long long d = (unsigned long long)seed;
 	return pcmMix(pcmMix(unsigned(d) ^ 0x736d7374u) ^ unsigned(d >> 32));
 }
+// Level of the output conversions (include/smst.h, "Level", has the definition).  One entry per stream, device: the mode (kPcmLevel*), the
+// gain and -- the two whole-clip modes -- the ceiling.  A launch is a levelled one when `table` is set: every element is w = v*g before the
+// rule above runs on w, peaks[s] (the bits of a non-negative float, which order as ints) takes the largest |v| the launch met in stream s,
+// NaN skipped, and applied[s] the gain g it used.  kPcmOut knows the fixed gain only; kClipOut derives a whole-clip gain from clipPeak[s],
+// the peak of the stream's clip that kClipPeak left there.  table == null: the unlevelled kernels, as before; nothing else is read.
+struct PcmLevel { unsigned mode; float gain, ceiling; unsigned pad; };
+constexpr unsigned kPcmLevelFixed = 0u, kPcmLevelProtect = 1u, kPcmLevelNormalise = 2u;
+struct PcmLevelIo { const PcmLevel *table = nullptr; int *peaks = nullptr; float *applied = nullptr; int *clipPeak = nullptr; };
 void launchPcmOut(int format, const float *in, long long inStreamStride, long long inChannelStride, void *out, long long outStreamStride, long long outFrameStride,
-                  const int *counts, int S, int C, int maxFrames, unsigned *overs, hipStream_t st, const PcmDither *dither = nullptr);
+                  const int *counts, int S, int C, int maxFrames, unsigned *overs, hipStream_t st, const PcmDither *dither = nullptr, const PcmLevelIo &level = PcmLevelIo());
 // Whole clips of ragged lengths (smst_clip.h; Batch::exact): each stream moves two segments of frames between the caller's buffer and a planar
 // fp32 image -- `count` frames from frame `src` of its row(s) on the source side to frame `dst` on the destination side; zeros != 0: no
 // source, the destination gets 0.0 (its code, in a frame format).  segs: [S][2] device.  format: an SMST_PCM_* code, or 0 for a caller's
@@ -233,6 +241,9 @@ struct ClipSeg { int src, dst, count, zeros; };
 void launchClipIn(int format, const void *in, long long inStreamStride, long long inInnerStride, float *image, long long imageStreamStride, long long imageChannelStride,
                   const ClipSeg *segs, int S, int C, int maxCount, hipStream_t st);
 void launchClipOut(int format, const float *image, long long imageStreamStride, long long imageChannelStride, void *out, long long outStreamStride, long long outInnerStride,
-                   const ClipSeg *segs, int S, int C, int maxCount, unsigned *overs, hipStream_t st, const PcmDither *dither = nullptr);
+                   const ClipSeg *segs, int S, int C, int maxCount, unsigned *overs, hipStream_t st, const PcmDither *dither = nullptr, const PcmLevelIo &level = PcmLevelIo());
+// The peak of every stream's clip -- the largest |v| of the image's samples that the segments cover, NaN skipped -- maxed into clipPeak[s]
+// (the caller zeroes the words in front of it): the pass of a levelled clip call in which a stream has a whole-clip mode
+void launchClipPeak(const float *image, long long imageStreamStride, long long imageChannelStride, const ClipSeg *segs, int S, int C, int maxCount, int *clipPeak, hipStream_t st);
 
 } // namespace smst

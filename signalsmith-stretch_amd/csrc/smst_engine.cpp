@@ -1789,8 +1789,14 @@ void Batch::exact(const ClipIo &io, const int *inSamples, const int *outSamples,
 		flush(dClipOut + Q, outImgSS, pitchOut, flushN.data(), rates.data(), run.data());
 	}
 	// behind the call's last emitting kernel (everything of a call is joined into `st`), in front of whatever synchronize() / signalStream() wait for
+	bool wholeClip = false;
+	if (io.level.table && io.wholeClip) for (int s = 0; s < S; ++s) wholeClip = wholeClip || (run[s] && io.wholeClip[s]);
+	if (wholeClip) { // the clips' peaks, from the finished image: what kClipOut forms those streams' gains from
+		SMST_HIP(hipMemsetAsync(io.level.clipPeak, 0, (size_t)S*sizeof(int), st));
+		launchClipPeak(dClipOut, outImgSS, pitchOut, cs.dev + (size_t)2*S, S, C, std::max(maxProc, maxFlush), io.level.clipPeak, st);
+	}
 	launchClipOut(io.format, dClipOut, outImgSS, pitchOut, io.out, io.outStreamStride, io.outInnerStride, cs.dev + (size_t)2*S, S, C,
-	              std::max(std::max(direct ? 0 : maxProc, maxFlush), maxZeros), io.overs, st, io.dither);
+	              std::max(std::max(direct ? 0 : maxProc, maxFlush), maxZeros), io.overs, st, io.dither, io.level);
 	SMST_HIP(hipEventRecord(cs.done, st));
 	cs.used = true;
 	SMST_HIP(hipGetLastError());

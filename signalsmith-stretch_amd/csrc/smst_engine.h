@@ -104,7 +104,8 @@ public:
 	// (smst_clip.h).  A stream whose input is shorter than its outputSeekLength gets zeros and keeps its state (:471-480).  tooShort (host, may
 	// be null): 1 for such a stream, 0 for the others that take part, written once every stage has been issued; a stream left out keeps its entry.  overs (device, may be null): [S][2] counters of the frame conversion.
 	// Counts are checked by the caller: outSamples[s] != 0, inSamples[s] >= 0 where outSamples[s] > 0.
-	struct ClipIo { const void *in; long long inStreamStride, inInnerStride; void *out; long long outStreamStride, outInnerStride; int format; unsigned *overs; const PcmDither *dither = nullptr; }; // dither: [S] device, or null (smst_device.h)
+	struct ClipIo { const void *in; long long inStreamStride, inInnerStride; void *out; long long outStreamStride, outInnerStride; int format; unsigned *overs; const PcmDither *dither = nullptr; // dither: [S] device, or null (smst_device.h)
+		PcmLevelIo level; const unsigned char *wholeClip = nullptr; }; // level.table set: a levelled call (frame formats); wholeClip (host, [S]): which streams' gains come from their clip's peak -- if one of them runs, kClipPeak does
 	void exact(const ClipIo &io, const int *inSamples, const int *outSamples, unsigned char *tooShort);
 	void synchronize();
 

@@ -29,6 +29,10 @@
 // Overs.  kPcmOut counts what the conversion could not represent: per lane one word, clamped (or, float16, turned +-inf from a finite
 // value) in its low half and NaN inputs in its high half -- a lane converts some 35 elements of a tile at the most --, summed over the
 // wavefront, and one atomicAdd per wavefront and non-zero counter into overs[2*s], overs[2*s + 1].
+//
+// Level.  The levelled forms of kPcmOut / kClipOut (a third template flag; PcmLevelIo of smst_device.h) multiply every element by its stream's
+// gain in front of the rule above and keep, beside the overs word, one running maximum of |v| per lane -- the bits of the float, compared as
+// integers: order-independent, so bit-reproducible --, maxed over the wavefront and, where it exceeds the stored one, into peaks[s].
 #pragma once
 #include <cstdint>
 #include <stdexcept>
@@ -273,13 +277,32 @@ template <typename T> __device__ inline void pcmTileIn(const T *__restrict__ run
 	}
 }
 
+// What an element adds to a peak meter: the bits of |v| -- non-negative floats order as their bit patterns do, +inf above every finite one --,
+// 0 for a NaN
+__device__ inline unsigned pcmPeakBits(float v) {
+	const unsigned a = unsigned(__float_as_int(v)) & 0x7fffffffu;
+	return a > 0x7f800000u ? 0u : a;
+}
+// the lanes' peaks into stream s's word (every lane of the workgroup arrives here): one vote, and a wavefront that holds nothing above the
+// stored peak -- nearly every one, once a loud tile has been met -- issues no atomic at all, another one a single atomicMax
+__device__ inline void pcmMaxPeak(int *__restrict__ peaks, int s, unsigned peak) {
+	if (__any(int(peak) > peaks[s])) {
+		const int tid = threadIdx.x;
+		int most = int(peak);
+		for (int m = 32; m; m >>= 1) most = max(most, __shfl(most, (tid & 63) ^ m));
+		if ((tid & 63) == 0) atomicMax(peaks + s, most);
+	}
+}
+
 // The reverse: one tile of the rows of a planar fp32 image -> a run of frames.  in: the sample of channel 0 that goes to the run's first frame,
 // or null for a run of zeros (the code of 0.0).  false: the tile lies behind the run; else `over` has this lane's overs word (see "Overs").
 // Dith (int16 / int24) decides how an element's rounded value is formed -- v*scale + d, d the dither of the stream's entry dp for the frame
 // index first + f (a run of zeros and a stream of mode 0 get d = 0: the undithered codes), so that an element counts as clamped when the
 // DITHERED value was -- and that the 16 key words behind the image are filled; nothing else.
-template <typename T, bool Dith> __device__ inline bool pcmTileOut(const float *__restrict__ in, long long inChannelStride, T *__restrict__ run, long long outFrameStride, long long frames,
-		int t, int C, float *tile, unsigned &over, PcmDither dp) {
+// Level ("Level" of include/smst.h): the quantiser takes w = v*g -- one fp32 multiply of its own -- in place of v, and `peak` has the largest
+// |v| of this lane's elements as its bits, NaN skipped; a run of zeros is not multiplied (0*inf would be a NaN).  Nothing else.
+template <typename T, bool Dith, bool Level = false> __device__ inline bool pcmTileOut(const float *__restrict__ in, long long inChannelStride, T *__restrict__ run, long long outFrameStride, long long frames,
+		int t, int C, float *tile, unsigned &over, PcmDither dp, float gain = 1.0f, unsigned *peak = nullptr) {
 	typedef PcmFormat<T> F;
 	const int tid = threadIdx.x;
 	long long e0;
@@ -301,8 +324,19 @@ template <typename T, bool Dith> __device__ inline bool pcmTileOut(const float *
 	__syncthreads();
 	over = 0;
 	const unsigned long long n0 = (((unsigned long long)dp.nHi << 32) | dp.nLo) + (unsigned long long)f0;
+	const float g = src ? gain : 1.0f;
+	unsigned most = 0u;
 	auto rounded = [&](int i, const PcmPlace &at) { // element i of the tile as the quantiser takes it
-		const float v = tile[pcmSlot(i)];
+		float v = tile[pcmSlot(i)];
+		if constexpr (Level) {
+			most = max(most, pcmPeakBits(v));
+			v = __fmul_rn(v, g);
+#if defined(__HIP_DEVICE_COMPILE__)
+			// float16 writes the fp32 product narrowed: two roundings.  Left alone, the compiler folds the multiply into the conversion
+			// (v_fma_mixlo_f16, which rounds the exact product once); an empty statement that "reads and writes" w keeps it a value of its own
+			if constexpr (std::is_same<T, PcmF16>::value) asm("" : "+v"(v));
+#endif
+		}
 		if constexpr (Dith) return mode ? v*F::kScale + pcmDitherValue(mode, keys[at.c], n0 + at.frame) : v*F::kScale;
 		else return F::scaled(v);
 	};
@@ -315,6 +349,7 @@ template <typename T, bool Dith> __device__ inline bool pcmTileOut(const float *
 			F::pack(x, w);
 			for (int k = 0; k < F::W; ++k) reinterpret_cast<PcmWord4 *>(p)[k] = w[k];
 		});
+	if constexpr (Level) *peak = most;
 	return true;
 }
 // the lanes' overs words into stream s's counters (every lane of the workgroup arrives here; the vote keeps the clean wavefront, which is
@@ -341,15 +376,25 @@ template <typename T> __global__ __launch_bounds__(256) void kPcmIn(const T *__r
 }
 
 // planar fp32 -> interleaved frames: the reverse.  overs (may be null): [S][2] counters, see "Overs" above.  Dith (int16 / int24): dither[s] is
-// stream s's entry, the index of the run's first frame in it; else dither is not read
-template <typename T, bool Dith> __global__ __launch_bounds__(256) void kPcmOut(const float *__restrict__ in, long long inStreamStride, long long inChannelStride,
-		T *__restrict__ out, long long outStreamStride, long long outFrameStride, const int *__restrict__ counts, int C, unsigned *__restrict__ overs, const PcmDither *__restrict__ dither) {
+// stream s's entry, the index of the run's first frame in it; else dither is not read.  Level: the stream's fixed gain of level.table[s] (the
+// host refuses a whole-clip mode here) is applied and reported -- by the workgroup of the run's first tile --, its peak metered; else level is not read
+template <typename T, bool Dith, bool Level> __global__ __launch_bounds__(256) void kPcmOut(const float *__restrict__ in, long long inStreamStride, long long inChannelStride,
+		T *__restrict__ out, long long outStreamStride, long long outFrameStride, const int *__restrict__ counts, int C, unsigned *__restrict__ overs, const PcmDither *__restrict__ dither,
+		PcmLevelIo level) {
 	extern __shared__ __attribute__((aligned(16))) unsigned char smemRaw[];
 	const int s = blockIdx.y;
 	PcmDither dp{0u, 0u, 0u, 0u};
 	if constexpr (Dith) dp = dither[s];
 	unsigned over;
-	if (!pcmTileOut<T, Dith>(in + (size_t)s*inStreamStride, inChannelStride, out + (size_t)s*outStreamStride, outFrameStride, counts[s], blockIdx.x, C, reinterpret_cast<float *>(smemRaw), over, dp)) return;
+	if constexpr (Level) {
+		const float g = level.table[s].gain;
+		unsigned peak;
+		if (!pcmTileOut<T, Dith, true>(in + (size_t)s*inStreamStride, inChannelStride, out + (size_t)s*outStreamStride, outFrameStride, counts[s], blockIdx.x, C, reinterpret_cast<float *>(smemRaw), over, dp, g, &peak)) return;
+		if (blockIdx.x == 0 && threadIdx.x == 0) level.applied[s] = g;
+		pcmMaxPeak(level.peaks, s, peak);
+	} else {
+		if (!pcmTileOut<T, Dith>(in + (size_t)s*inStreamStride, inChannelStride, out + (size_t)s*outStreamStride, outFrameStride, counts[s], blockIdx.x, C, reinterpret_cast<float *>(smemRaw), over, dp)) return;
+	}
 	pcmAddOvers(overs, s, over);
 }
 
@@ -383,15 +428,20 @@ void launchPcmIn(int format, const void *in, long long inStreamStride, long long
 	countLaunch(LK_PCM_IN);
 }
 void launchPcmOut(int format, const float *in, long long inStreamStride, long long inChannelStride, void *out, long long outStreamStride, long long outFrameStride,
-                  const int *counts, int S, int C, int maxFrames, unsigned *overs, hipStream_t st, const PcmDither *dither) {
+                  const int *counts, int S, int C, int maxFrames, unsigned *overs, hipStream_t st, const PcmDither *dither, const PcmLevelIo &level) {
 	if (maxFrames < 1) return;
 	const dim3 grid(divUp(maxFrames, kPcmTileFrames), S);
 	pcmDispatch(format, dither != nullptr, [&](auto tag, auto dithered) {
 		typedef typename decltype(tag)::type T;
 		constexpr bool Dith = decltype(dithered)::value;
-		hipLaunchKernelGGL((kPcmOut<T, Dith>), grid, dim3(256), Dith ? pcmDitherLdsBytes(C) : pcmLdsBytes(C), st, in, inStreamStride, inChannelStride, static_cast<T *>(out), outStreamStride,
-		                   outFrameStride, counts, C, overs, dither);
-		countLaunch(Dith ? LK_PCM_OUT_DITHERED : LK_PCM_OUT);
+		const size_t lds = Dith ? pcmDitherLdsBytes(C) : pcmLdsBytes(C);
+		if (level.table) {
+			hipLaunchKernelGGL((kPcmOut<T, Dith, true>), grid, dim3(256), lds, st, in, inStreamStride, inChannelStride, static_cast<T *>(out), outStreamStride, outFrameStride, counts, C, overs, dither, level);
+			countLaunch(LK_PCM_OUT_LEVELLED);
+		} else {
+			hipLaunchKernelGGL((kPcmOut<T, Dith, false>), grid, dim3(256), lds, st, in, inStreamStride, inChannelStride, static_cast<T *>(out), outStreamStride, outFrameStride, counts, C, overs, dither, level);
+			countLaunch(Dith ? LK_PCM_OUT_DITHERED : LK_PCM_OUT);
+		}
 	});
 }
 

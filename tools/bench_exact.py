@@ -7,6 +7,9 @@ the host from its first entry point to the return of smst_batch_synchronize.
   python tools/bench_exact.py --mode three        # the yardstick (also runs on a build without smst_batch_exact: SMST_LIBRARY)
   python tools/bench_exact.py --mode exact --check   # ... and compares the first call's output with the three-call sequence, bit for bit
   python tools/bench_exact.py --mode ragged       # per-stream rates drawn from [0.5, 2.0)
+  python tools/bench_exact.py --mode pcm          # smst_batch_exact_pcm on int16 frames (also on a build without the level calls: SMST_LIBRARY)
+  python tools/bench_exact.py --mode level        # pcm, fixed (a gain of 0.5 on every stream) and protect (ceiling 32766/32768) alternating step by
+                                                  # step, a batch each: fixed - pcm = the levelled copy kernel, protect - fixed = the peak pass
 """
 import argparse
 import ctypes as C
@@ -28,7 +31,7 @@ smst = importlib.import_module("signalsmith-stretch_amd")
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--mode", choices=["three", "exact", "ragged"], required=True)
+    ap.add_argument("--mode", choices=["three", "exact", "ragged", "pcm", "fixed", "protect", "level"], required=True)
     ap.add_argument("--streams", type=int, default=256)
     ap.add_argument("--channels", type=int, default=2)
     ap.add_argument("--seconds", type=float, default=10.0)
@@ -76,6 +79,8 @@ def main():
         smst._check(lib, lib.smst_batch_exact(b.h, C.c_void_p(x.data_ptr()), Cn*n, n, ip(nin), C.c_void_p(y.data_ptr()), Cn*most, most, ip(nout), ip(status), smst.MEM_DEVICE))
         assert not status.any(), status
 
+    if a.mode in ("pcm", "fixed", "protect", "level"):
+        return frames_modes(a, lib, x, nin, nout, batch)
     call = three if a.mode == "three" else exact
     b = batch()
     if a.check and a.mode == "exact":
@@ -99,6 +104,51 @@ def main():
                           median_ms=round(statistics.median(timed), 3), min_ms=round(min(timed), 3), max_ms=round(max(timed), 3), steps=a.steps, warmup=a.warmup,
                           checked=bool(a.check and a.mode == "exact"), device=torch.cuda.get_device_name(0), hw_queues=os.environ["GPU_MAX_HW_QUEUES"])))
     b.close()
+
+
+def frames_modes(a, lib, x, nin, nout, batch):
+    """smst_batch_exact_pcm on int16 frames in device memory: unlevelled, with a fixed gain, with PROTECT; `level` runs the three in turn within
+    every step, each on a batch of its own"""
+    S, Cn, n, most = a.streams, a.channels, x.shape[2], int(nout.max())
+    frames = (x.transpose(1, 2)*32768.0).round().clamp(-32768, 32767).to(torch.int16).contiguous()
+    out = torch.zeros((S, most, Cn), dtype=torch.int16, device="cuda")
+    torch.cuda.synchronize()
+    ip = lambda v: v.ctypes.data_as(C.POINTER(C.c_int))
+    runs = {}
+    for name in (("pcm", "fixed", "protect") if a.mode == "level" else (a.mode,)):
+        b = batch()
+        if name == "fixed":
+            b.set_pcm_level(smst.LEVEL_FIXED, 0.5)
+        if name == "protect":
+            b.set_pcm_level(smst.LEVEL_PROTECT, 1.0, 32766.0/32768.0)
+        runs[name] = b
+
+    def call(b):
+        status = np.zeros(S, np.int32)
+        smst._check(lib, lib.smst_batch_exact_pcm(b.h, C.c_void_p(frames.data_ptr()), n*Cn, Cn, ip(nin), C.c_void_p(out.data_ptr()), most*Cn, Cn, ip(nout), ip(status), smst.PCM_S16, smst.MEM_DEVICE))
+        assert not status.any(), status
+    times = {name: [] for name in runs}
+    for k in range(a.warmup + a.steps):
+        for name, b in runs.items():
+            b.synchronize()
+            t0 = time.perf_counter()
+            call(b)
+            b.synchronize()
+            if k >= a.warmup:
+                times[name].append((time.perf_counter() - t0)*1e3)
+    result = dict(mode=a.mode, library=os.path.relpath(smst.LIBRARY_PATH), streams=S, channels=Cn, in_samples=n, out_samples=[int(nout.min()), int(nout.max())], steps=a.steps,
+                  warmup=a.warmup, device=torch.cuda.get_device_name(0), hw_queues=os.environ["GPU_MAX_HW_QUEUES"], step_ms={})
+    for name, v in times.items():
+        result["step_ms"][name] = dict(median=round(statistics.median(v), 3), min=round(min(v), 3), max=round(max(v), 3))
+    if a.mode == "level":
+        med = lambda name: result["step_ms"][name]["median"]
+        result["level"] = dict(fixed_minus_pcm_ms=round(med("fixed") - med("pcm"), 3), protect_minus_fixed_ms=round(med("protect") - med("fixed"), 3),
+                               peak_pass_bytes=int(S)*Cn*int(nout.sum()//S)*4)
+        peaks, gains = runs["protect"].take_pcm_peaks()
+        result["level"]["protect_gain_range"] = [float(gains.min()), float(gains.max())]
+    print(json.dumps(result))
+    for b in runs.values():
+        b.close()
 
 
 if __name__ == "__main__":

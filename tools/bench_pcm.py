@@ -11,7 +11,8 @@ that drift of the host or the device hits all of them alike:
   e  smst_batch_process, SMST_MEM_DEVICE, planar float      (what d is compared with: d - e = the two conversion passes)
   f  d with TPDF dither (setPcmDither), g  d with high-passed TPDF dither       (f - d, g - d = what the dither adds to a step)
   h  smst_batch_process_pcm, SMST_MEM_DEVICE, packed int24 frames, i  h with TPDF dither, j  h with high-passed TPDF dither
-The dithered rows are not in the default set: --variants d,e,f,g,h,i,j.  The time of the output conversion KERNEL alone (kPcmOut<T, false> /
+  k  d with a fixed gain of 0.5 on every stream (set_pcm_level): the levelled kernel   (k - d = what the gain and the peak meter add to a step)
+The dithered and levelled rows are not in the default set: --variants d,e,f,g,h,i,j,k.  The time of the output conversion KERNEL alone (kPcmOut<T, false> /
 kPcmOut<T, true> per format) is read from a kernel trace of such a run.
 A step's time is the host clock around one call that ends synchronised.  Prints one JSON line."""
 import argparse
@@ -59,7 +60,7 @@ def main():
     if "c" in variants:
         b, out = pkg.StretchBatch(S, Cn, preset="default", sample_rate=sr), np.zeros((S, m, Cn), np.int16)
         runs["c"] = lambda b=b, out=out: b.processFrames(s16, m, out=out)
-    if any(k in variants for k in "defghij"):
+    if any(k in variants for k in "defghijk"):
         import torch
     if "d" in variants:
         b, x, out = pkg.StretchBatch(S, Cn, preset="default", sample_rate=sr), torch.from_numpy(s16).cuda(), torch.zeros((S, m, Cn), dtype=torch.int16, device="cuda")
@@ -72,6 +73,11 @@ def main():
                 b.setPcmDither(mode, seed=1)
             torch.cuda.synchronize()
             runs[k] = lambda b=b, x=x, out=out: (b.processFrames(x, m, out=out, ordered=False), b.synchronize())
+    if "k" in variants:
+        b, x, out = pkg.StretchBatch(S, Cn, preset="default", sample_rate=sr), torch.from_numpy(s16).cuda(), torch.zeros((S, m, Cn), dtype=torch.int16, device="cuda")
+        b.set_pcm_level(pkg.LEVEL_FIXED, 0.5)
+        torch.cuda.synchronize()
+        runs["k"] = lambda b=b, x=x, out=out: (b.processFrames(x, m, out=out, ordered=False), b.synchronize())
     if any(k in variants for k in "hij"):
         codes = np.clip(np.round(f32.astype(np.float64)*8388608.0), -8388608, 8388607).astype(np.int32)
         s24 = np.stack([codes & 255, (codes >> 8) & 255, (codes >> 16) & 255], -1).astype(np.uint8)
@@ -109,6 +115,9 @@ def main():
             dither[k] = dict(against=base, extra_ms=extra, share_of_step=extra/result["step_ms"][k]["median"])
     if dither:
         result["dither"] = dither
+    if "k" in times and "d" in times:
+        extra = result["step_ms"]["k"]["median"] - result["step_ms"]["d"]["median"]
+        result["level"] = dict(k=dict(against="d", extra_ms=extra, share_of_step=extra/result["step_ms"]["k"]["median"]))
     print(json.dumps(result))
 
 

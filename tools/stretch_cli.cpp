@@ -5,6 +5,7 @@
 //
 //   stretch_cli [--semitones=S] [--formant=S] [--formant-comp] [--formant-base=Hz] [--tonality=Hz] [--time=F]
 //               [--split-computation] [--device=N] [--out-format=s16|s24|f32] [--dither=none|tpdf|tpdf-hp] [--dither-seed=N]
+//               [--exact] [--gain=dB] [--protect=dBFS | --normalize=dBFS]
 //               in.wav out.wav [in2.wav out2.wav ...]
 //
 // --out-format (also "--out-format s24"): the samples of the files written -- 16-bit (the default, as the reference's CLI writes), 24-bit by the
@@ -14,6 +15,13 @@
 // dither the main process and the flush run through smst_batch_process_pcm / smst_batch_flush_pcm, which quantise on the GPU -- the flush
 // goes on with the frame counter --, and the frames are written as they come back.  Those calls take their input in the output's format:
 // an input that format cannot hold exactly (24-bit or float input with --out-format=s16) is refused rather than rounded.
+// --exact: every file is rendered by smst_batch_exact_pcm -- the reference's exact(): its seams instead of the three stages of cmd/main.cpp --
+// on frames of the output's format, with the same refusal of an input that format cannot hold.
+// --gain=dB: a fixed output gain (include/smst.h, "Level"), in either flow; in the default one it sends the process stage and the flush
+// through the _pcm calls, as --dither does.  --protect=dBFS and --normalize=dBFS (one of them; both imply --exact): the gain comes from the
+// rendered clip's own peak -- lowered (from --gain, or 0 dB) only where the clip would exceed the ceiling, or set so that the peak meets
+// it.  INTEGRATION.md says which ceiling keeps an integer format free of clamped samples.  dB -> linear: float(pow(10, dB/20)).  With any
+// of the three, one line per file: "level: <file> peak=<%.9g> gain=<%.9g> overs=<clamped samples>" -- the peak before the gain.
 // Files given together must share sample rate and channel count (they form one batch); lengths may differ.
 #include <algorithm>
 #include <cmath>
@@ -31,6 +39,12 @@ static double flagValue(int argc, char **argv, const char *name, double fallback
 	for (int i = 1; i < argc; ++i) if (!std::strncmp(argv[i], prefix.c_str(), prefix.size())) return std::atof(argv[i] + prefix.size());
 	return fallback;
 }
+static bool hasValue(int argc, char **argv, const char *name) {
+	const std::string prefix = std::string("--") + name + "=";
+	for (int i = 1; i < argc; ++i) if (!std::strncmp(argv[i], prefix.c_str(), prefix.size())) return true;
+	return false;
+}
+static float fromDecibels(double dB) { return float(std::pow(10.0, dB/20.0)); }
 static bool hasFlag(int argc, char **argv, const char *name) {
 	const std::string flag = std::string("--") + name;
 	for (int i = 1; i < argc; ++i) if (flag == argv[i]) return true;
@@ -72,6 +86,13 @@ int main(int argc, char **argv) {
 		std::fprintf(stderr, "--dither applies to --out-format s16 and s24: float32 samples are not quantised\n");
 		return 2;
 	}
+	const bool hasGain = hasValue(argc, argv, "gain"), protect = hasValue(argc, argv, "protect"), normalize = hasValue(argc, argv, "normalize");
+	if (protect && normalize) {
+		std::fprintf(stderr, "--protect and --normalize exclude each other\n");
+		return 2;
+	}
+	const bool exact = hasFlag(argc, argv, "exact") || protect || normalize, levelled = hasGain || protect || normalize;
+	const float gain = fromDecibels(flagValue(argc, argv, "gain", 0)), ceiling = fromDecibels(flagValue(argc, argv, protect ? "protect" : "normalize", 0));
 	std::vector<std::string> files;
 	for (int i = 1; i < argc; ++i) if (std::strncmp(argv[i], "--", 2) && !consumed[i]) files.push_back(argv[i]);
 	if (files.size() < 2 || files.size()%2) {
@@ -121,33 +142,61 @@ int main(int argc, char **argv) {
 		std::copy(inputs[s].samples[c].begin(), inputs[s].samples[c].end(), in.begin() + ((size_t)s*C + c)*maxIn);
 	const long long iss = (long long)C*maxIn, ics = maxIn, oss = (long long)C*maxOut, ocs = maxOut;
 
-	CHECK(smst_batch_output_seek(batch, in.data(), iss, ics, seekLens.data(), SMST_MEM_HOST));                                   // :58-59
-	if (dither != SMST_DITHER_NONE) {
-		// the process stage and the flush as frames of the output's format, dithered by the library: stream s has seed ditherSeed + s
-		const int format = outFormat == "s24" ? SMST_PCM_S24 : SMST_PCM_S16, bits = outFormat == "s24" ? 24 : 16;
+	if (!exact) CHECK(smst_batch_output_seek(batch, in.data(), iss, ics, seekLens.data(), SMST_MEM_HOST));                        // :58-59
+	if (dither != SMST_DITHER_NONE || levelled || exact) {
+		// frames of the output's format, quantised (dithered: stream s has seed ditherSeed + s; levelled) by the library
+		const int format = outFormat == "s24" ? SMST_PCM_S24 : outFormat == "f32" ? SMST_PCM_F32 : SMST_PCM_S16, bits = outFormat == "s24" ? 24 : outFormat == "f32" ? 32 : 16;
 		const size_t esz = size_t(bits/8);
 		const float scale = bits == 24 ? 8388608.0f : 32768.0f;
-		CHECK(smst_batch_set_pcm_dither(batch, -1, dither, ditherSeed));
-		int maxProc = 1;
-		for (int s = 0; s < S; ++s) maxProc = std::max(maxProc, procIn[s]);
-		const int tailLen = std::max(interval, 1);
-		std::vector<unsigned char> inFrames((size_t)S*maxProc*C*esz, 0), outFrames((size_t)S*maxOut*C*esz, 0), tailFrames((size_t)S*tailLen*C*esz, 0);
-		for (int s = 0; s < S; ++s) for (int i = 0; i < procIn[s]; ++i) for (int c = 0; c < C; ++c) {
-			const float v = in[((size_t)s*C + c)*maxIn + seekLength + i];
-			const float q = std::fmin(scale - 1.0f, std::fmax(-scale, std::round(v*scale)));
-			if (!(q/scale == v)) {
-				std::fprintf(stderr, "%s: sample %d is no %d-bit value: --dither needs an input that --out-format holds exactly\n", files[2*s].c_str(), seekLength + i, bits);
+		if (dither != SMST_DITHER_NONE) CHECK(smst_batch_set_pcm_dither(batch, -1, dither, ditherSeed));
+		if (levelled) CHECK(smst_batch_set_pcm_level(batch, -1, protect ? SMST_LEVEL_PROTECT : normalize ? SMST_LEVEL_NORMALISE : SMST_LEVEL_FIXED, gain, ceiling));
+		// `count` samples of file s from sample `first` on as frames at `frames`; false: one of them is no value of the format
+		auto toFrames = [&](int s, int first, int count, unsigned char *frames) {
+			for (int i = 0; i < count; ++i) for (int c = 0; c < C; ++c) {
+				const float v = in[((size_t)s*C + c)*maxIn + first + i];
+				unsigned char *p = frames + ((size_t)i*C + c)*esz;
+				if (format == SMST_PCM_F32) { std::memcpy(p, &v, 4); continue; }
+				const float q = std::fmin(scale - 1.0f, std::fmax(-scale, std::round(v*scale)));
+				if (!(q/scale == v)) {
+					std::fprintf(stderr, "%s: sample %d is no %d-bit value: frames need an input that --out-format holds exactly\n", files[2*s].c_str(), first + i, bits);
+					return false;
+				}
+				const uint32_t code = uint32_t(int32_t(q));
+				for (size_t k = 0; k < esz; ++k) p[k] = (unsigned char)(code >> (8*k));
+			}
+			return true;
+		};
+		std::vector<unsigned char> outFrames((size_t)S*maxOut*C*esz, 0);
+		if (exact) {
+			std::vector<int> inLen(S), status(S, SMST_OK);
+			for (int s = 0; s < S; ++s) inLen[s] = int(inputs[s].length());
+			std::vector<unsigned char> inFrames((size_t)S*maxIn*C*esz, 0);
+			for (int s = 0; s < S; ++s) if (!toFrames(s, 0, inLen[s], inFrames.data() + (size_t)s*maxIn*C*esz)) return 1;
+			CHECK(smst_batch_exact_pcm(batch, inFrames.data(), (long long)maxIn*C, C, inLen.data(), outFrames.data(), (long long)maxOut*C, C, outLen.data(), status.data(), format, SMST_MEM_HOST));
+			for (int s = 0; s < S; ++s) if (status[s] != SMST_OK) {
+				std::fprintf(stderr, "%s: too short for --exact at this rate\n", files[2*s].c_str());
 				return 1;
 			}
-			const uint32_t code = uint32_t(int32_t(q));
-			unsigned char *p = inFrames.data() + (((size_t)s*maxProc + i)*C + c)*esz;
-			for (size_t k = 0; k < esz; ++k) p[k] = (unsigned char)(code >> (8*k));
+		} else {
+			int maxProc = 1;
+			for (int s = 0; s < S; ++s) maxProc = std::max(maxProc, procIn[s]);
+			const int tailLen = std::max(interval, 1);
+			std::vector<unsigned char> inFrames((size_t)S*maxProc*C*esz, 0), tailFrames((size_t)S*tailLen*C*esz, 0);
+			for (int s = 0; s < S; ++s) if (!toFrames(s, seekLength, procIn[s], inFrames.data() + (size_t)s*maxProc*C*esz)) return 1;
+			CHECK(smst_batch_process_pcm(batch, inFrames.data(), (long long)maxProc*C, C, procIn.data(), outFrames.data(), (long long)maxOut*C, C, outIndex.data(), format, SMST_MEM_HOST));
+			CHECK(smst_batch_flush_pcm(batch, tailFrames.data(), (long long)tailLen*C, C, tail.data(), nullptr, format, SMST_MEM_HOST));
+			for (int s = 0; s < S; ++s)
+				std::copy(tailFrames.begin() + (size_t)s*tailLen*C*esz, tailFrames.begin() + ((size_t)s*tailLen + tail[s])*C*esz, outFrames.begin() + ((size_t)s*maxOut + outIndex[s])*C*esz);
 		}
-		CHECK(smst_batch_process_pcm(batch, inFrames.data(), (long long)maxProc*C, C, procIn.data(), outFrames.data(), (long long)maxOut*C, C, outIndex.data(), format, SMST_MEM_HOST));
-		CHECK(smst_batch_flush_pcm(batch, tailFrames.data(), (long long)tailLen*C, C, tail.data(), nullptr, format, SMST_MEM_HOST));
+		if (levelled) {
+			std::vector<long long> clamped(S, 0);
+			std::vector<float> peaks(S, 0.0f), gains(S, 1.0f);
+			CHECK(smst_batch_take_pcm_overs(batch, clamped.data(), nullptr));
+			CHECK(smst_batch_take_pcm_peaks(batch, peaks.data(), gains.data()));
+			for (int s = 0; s < S; ++s) std::printf("level: %s peak=%.9g gain=%.9g overs=%lld\n", files[2*s + 1].c_str(), peaks[s], gains[s], clamped[s]);
+		}
 		for (int s = 0; s < S; ++s) {
-			std::copy(tailFrames.begin() + (size_t)s*tailLen*C*esz, tailFrames.begin() + ((size_t)s*tailLen + tail[s])*C*esz, outFrames.begin() + ((size_t)s*maxOut + outIndex[s])*C*esz);
-			if (!writeWavFrames(files[2*s + 1], inputs[s].sampleRate, inputs[s].channels, bits, outFrames.data() + (size_t)s*maxOut*C*esz, size_t(outLen[s]), error)) {
+			if (!writeWavFrames(files[2*s + 1], inputs[s].sampleRate, inputs[s].channels, bits, outFrames.data() + (size_t)s*maxOut*C*esz, size_t(outLen[s]), error, format == SMST_PCM_F32)) {
 				std::fprintf(stderr, "%s\n", error.c_str());
 				return 1;
 			}

@@ -106,15 +106,16 @@ inline bool writeWav24(const std::string &path, const WavData &wav, std::string 
 	return true;
 }
 
-// Frames that are PCM already -- `bits` = 16 or 24, little-endian, channel-interleaved, as the library's _pcm calls write them -- as the data chunk
-inline bool writeWavFrames(const std::string &path, unsigned sampleRate, unsigned channels, unsigned bits, const unsigned char *data, size_t frames, std::string &error) {
+// Frames that are PCM already -- `bits` = 16 or 24, little-endian, channel-interleaved, as the library's _pcm calls write them -- as the data chunk;
+// floatSamples: `bits` = 32, IEEE float32 (format tag 3)
+inline bool writeWavFrames(const std::string &path, unsigned sampleRate, unsigned channels, unsigned bits, const unsigned char *data, size_t frames, std::string &error, bool floatSamples = false) {
 	FILE *f = std::fopen(path.c_str(), "wb");
 	if (!f) { error = "cannot create " + path; return false; }
 	const uint32_t frameBytes = channels*(bits/8), dataBytes = uint32_t(frames)*frameBytes;
 	auto put32 = [&](uint32_t v) { unsigned char b[4] = {(unsigned char)v, (unsigned char)(v >> 8), (unsigned char)(v >> 16), (unsigned char)(v >> 24)}; std::fwrite(b, 1, 4, f); };
 	auto put16 = [&](uint16_t v) { unsigned char b[2] = {(unsigned char)v, (unsigned char)(v >> 8)}; std::fwrite(b, 1, 2, f); };
 	std::fwrite("RIFF", 1, 4, f); put32(36 + dataBytes + (dataBytes & 1)); std::fwrite("WAVEfmt ", 1, 8, f);
-	put32(16); put16(1); put16(uint16_t(channels)); put32(sampleRate); put32(sampleRate*frameBytes); put16(uint16_t(frameBytes)); put16(uint16_t(bits));
+	put32(16); put16(floatSamples ? 3 : 1); put16(uint16_t(channels)); put32(sampleRate); put32(sampleRate*frameBytes); put16(uint16_t(frameBytes)); put16(uint16_t(bits));
 	std::fwrite("data", 1, 4, f); put32(dataBytes);
 	const bool ok = std::fwrite(data, 1, dataBytes, f) == dataBytes;
 	if (dataBytes & 1) std::fputc(0, f); // (RIFF chunks are padded to an even length)
