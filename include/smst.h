@@ -535,6 +535,10 @@ int smst_batch_debug_get_formants(smst_batch *b, int stream, float *ratio, float
 /* the kernels' packed complex helpers (csrc/smst_complex.h, gfx950 inline assembly) evaluated on the device: in = n x
  * (a.re, a.im, b.re, b.im, c.re, c.im, fraction), out = n x (a*b, a*conj(b), a*b + c, a + (b - a)*fraction) as 8 floats. */
 int smst_debug_complex_selftest(int device, const float *in, float *out, int n);
+/* the FFT kernels' complex helpers (csrc/smst_fft_complex.h) likewise: in = n x (a.re, a.im, b.re, b.im), out = n x (a*b, a*conj(b) as the
+ * inverse transform's twiddle product rounds it, a*conj(b) as the windowed store rounds it, a + i*b, a - i*b, a + b, a - b, conj(a) from the
+ * conjugating store, conj(a) from the conjugating load, a through both with the condition false) as 20 floats. */
+int smst_debug_fft_complex_selftest(int device, const float *in, float *out, int n);
 /* launches, since the library was loaded, of one kernel variant: "vocoder_aligned", "vocoder_staged", "vocoder_gather",
  * "vocoder_n", "vocoder_one", "vocoder_across", "vocoder_continuous", "chain_unfused", "analyse_teams", "analyse_fast", "analyse_generic",
  * "synth_teams", "synth_fast", "synth_generic", "synth_emit", "emit_carried", "feed_one_pass", "pcm_in", "pcm_out" (the conversion kernels of the _pcm calls, whatever

@@ -147,6 +147,7 @@ _SIGNATURES = {
     "smst_batch_wait_for_stream": (C.c_int, [C.c_void_p, C.c_void_p]),
     "smst_batch_signal_stream": (C.c_int, [C.c_void_p, C.c_void_p]),
     "smst_debug_complex_selftest": (C.c_int, [C.c_int, _fp, _fp, C.c_int]),
+    "smst_debug_fft_complex_selftest": (C.c_int, [C.c_int, _fp, _fp, C.c_int]),
     "smst_debug_launch_count": (_ll, [C.c_char_p]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
@@ -238,6 +239,16 @@ def complex_selftest(values, device=0, lib=None):
     v = np.ascontiguousarray(values, np.float32).reshape(-1, 7)
     out = np.zeros((v.shape[0], 8), np.float32)
     _check(lib, lib.smst_debug_complex_selftest(device, v.ctypes.data_as(_fp), out.ctypes.data_as(_fp), v.shape[0]))
+    return out
+
+
+def fft_complex_selftest(values, device=0, lib=None):
+    """values: [n, 4] float32 (a, b complex) -> [n, 20]: a*b, a*conj(b) (twiddle form), a*conj(b) (window form), a + i b, a - i b, a + b, a - b,
+    conj(a) (store), conj(a) (load), a -- from the FFT kernels' helpers (csrc/smst_fft_complex.h)."""
+    lib = lib if lib is not None else load_library()
+    v = np.ascontiguousarray(values, np.float32).reshape(-1, 4)
+    out = np.zeros((v.shape[0], 20), np.float32)
+    _check(lib, lib.smst_debug_fft_complex_selftest(device, v.ctypes.data_as(_fp), out.ctypes.data_as(_fp), v.shape[0]))
     return out
 
 

@@ -285,22 +285,25 @@ int smst_batch_debug_set_carry(smst_batch *b, int stream, const float *sums, con
 long long smst_batch_debug_allocation_events(const smst_batch *b) { if (!b || !b->engine) return fail("null batch"); return (long long)b->engine->allocationEvents() + b->stagingAllocs; }
 int smst_batch_wait_for_stream(smst_batch *b, void *hipStream) { BATCH_CALL(b->engine->waitForStream(static_cast<hipStream_t>(hipStream))) }
 int smst_batch_signal_stream(smst_batch *b, void *hipStream) { BATCH_CALL(b->engine->signalStream(static_cast<hipStream_t>(hipStream))) }
-int smst_debug_complex_selftest(int device, const float *in, float *out, int n) {
+// a helper self-test: n tuples of `inWidth` floats to the device, the kernel, n rows of `outWidth` floats back
+static int complexSelfTest(int device, const float *in, float *out, int n, int inWidth, int outWidth, void (*launch)(const float *, float *, int, hipStream_t)) {
 	SMST_TRY
 	if (n < 1 || !in || !out) throw smst::Error("complex self-test: bad arguments");
 	if (hipSetDevice(device) != hipSuccess) throw smst::Error("hipSetDevice failed", true);
 	float *dIn = nullptr, *dOut = nullptr;
-	if (hipMalloc(reinterpret_cast<void **>(&dIn), (size_t)n*7*sizeof(float)) != hipSuccess) throw smst::Error("hipMalloc failed", true);
-	if (hipMalloc(reinterpret_cast<void **>(&dOut), (size_t)n*8*sizeof(float)) != hipSuccess) { hipFree(dIn); throw smst::Error("hipMalloc failed", true); }
-	hipError_t e = hipMemcpy(dIn, in, (size_t)n*7*sizeof(float), hipMemcpyHostToDevice);
-	if (e == hipSuccess) { smst::launchComplexSelfTest(dIn, dOut, n, nullptr); e = hipGetLastError(); }
-	if (e == hipSuccess) e = hipMemcpy(out, dOut, (size_t)n*8*sizeof(float), hipMemcpyDeviceToHost);
+	if (hipMalloc(reinterpret_cast<void **>(&dIn), (size_t)n*inWidth*sizeof(float)) != hipSuccess) throw smst::Error("hipMalloc failed", true);
+	if (hipMalloc(reinterpret_cast<void **>(&dOut), (size_t)n*outWidth*sizeof(float)) != hipSuccess) { hipFree(dIn); throw smst::Error("hipMalloc failed", true); }
+	hipError_t e = hipMemcpy(dIn, in, (size_t)n*inWidth*sizeof(float), hipMemcpyHostToDevice);
+	if (e == hipSuccess) { launch(dIn, dOut, n, nullptr); e = hipGetLastError(); }
+	if (e == hipSuccess) e = hipMemcpy(out, dOut, (size_t)n*outWidth*sizeof(float), hipMemcpyDeviceToHost);
 	hipFree(dIn);
 	hipFree(dOut);
 	if (e != hipSuccess) throw smst::Error(std::string("complex self-test: ") + hipGetErrorString(e), true);
 	return 0;
 	SMST_CATCH
 }
+int smst_debug_complex_selftest(int device, const float *in, float *out, int n) { return complexSelfTest(device, in, out, n, 7, 8, smst::launchComplexSelfTest); }
+int smst_debug_fft_complex_selftest(int device, const float *in, float *out, int n) { return complexSelfTest(device, in, out, n, 4, 20, smst::launchFftComplexSelfTest); }
 long long smst_debug_launch_count(const char *name) { return smst::launchCount(name); }
 int smst_batch_debug_get_formants(smst_batch *b, int stream, float *ratio, float *envelope, float *freqEstimate) {
 	if (!b || !b->engine) return fail("null batch");

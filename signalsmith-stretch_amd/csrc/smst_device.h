@@ -202,6 +202,7 @@ void launchMaskOutRows(const DevBatch &d, int sBase, int nStreams, const int *sy
 void launchSeekHistory(const DevBatch &d, const IoArgs &io, const int *seekFlags, hipStream_t st);
 void launchAddPreRoll(const DevBatch &d, const float *preRoll, int length, const int *offsets, hipStream_t st);
 void launchComplexSelfTest(const float *in, float *out, int n, hipStream_t st); // smst_complex.h against its documented formulas (test hook)
+void launchFftComplexSelfTest(const float *in, float *out, int n, hipStream_t st); // smst_fft_complex.h likewise: [n][4] -> [n][20]
 void launchFlushTail(const DevBatch &d, const IoArgs &io, const int *tailOffset, const int *outOffset, hipStream_t st);
 void launchMoveStreams(const MoveArgs &a, hipStream_t st); // every segment of every pair in one launch
 // Interleaved PCM frames <-> the planar fp32 image (smst_pcm.h).  format: the SMST_PCM_* codes of include/smst.h; strides in elements (packed

@@ -10,52 +10,61 @@ namespace smst {
 // pass comes last, where all its twiddles are 1.  src/dst ping-pong; returns the buffer holding the result.
 // SIGN = -1: forward (e^{-i...}), +1: inverse (unnormalised).
 // ------------------------------------------------------------------------------------------------------
-template <int SIGN>
-__device__ __forceinline__ float2 twiddle(const float2 *__restrict__ tw, int idx) {
-	float2 w = tw[idx];
-	if (SIGN > 0) w.y = -w.y;
-	return w;
-}
+// Complex values are fc (smst_fft_complex.h): a register pair from load to store; conjugation, +-i and negation of an operand are folded into
+// the instruction that uses it.  The stage twiddles are stored for the forward transform: the inverse one conjugates them in the product.
+template <int SIGN> __device__ __forceinline__ fc mulTwiddle(fc v, fc w) { return fmul<(SIGN > 0)>(v, w); } // v * w (forward), v * conj(w) (inverse)
+template <int SIGN> __device__ __forceinline__ fc addJ(fc a, fc b) { return (SIGN < 0) ? fsubI(a, b) : faddI(a, b); } // a + j b, j = -i (forward), +i (inverse)
+template <int SIGN> __device__ __forceinline__ fc subJ(fc a, fc b) { return (SIGN < 0) ? faddI(a, b) : fsubI(a, b); } // a - j b
+template <int SIGN> __device__ __forceinline__ fc mulJ(fc a) { return (SIGN < 0) ? fmake(a.y, -a.x) : fmake(-a.y, a.x); } // j a (where no sum takes it)
 
 // the radix-4, -3 and -5 butterflies, in place, outputs in natural order (the generic ladder's and the register-blocked stages')
 template <int SIGN>
-__device__ __forceinline__ void dft4(float2 &a, float2 &b, float2 &c, float2 &d) {
-	float2 apc = cadd(a, c), amc = csub(a, c), bpd = cadd(b, d), bmd = csub(b, d);
-	float2 jb = (SIGN < 0) ? mulNegI(bmd) : mulI(bmd);
-	a = cadd(apc, bpd);
-	b = cadd(amc, jb);
-	c = csub(apc, bpd);
-	d = csub(amc, jb);
+__device__ __forceinline__ void dft4(fc &a, fc &b, fc &c, fc &d) {
+	const fc apc = fadd(a, c), amc = fsub(a, c), bpd = fadd(b, d), bmd = fsub(b, d);
+	a = fadd(apc, bpd);
+	b = addJ<SIGN>(amc, bmd);
+	c = fsub(apc, bpd);
+	d = subJ<SIGN>(amc, bmd);
+}
+// the same with j*c in the place of c (the w16^4 and w8^2 twiddles of the radix-16 and radix-8 butterflies: no instruction of their own)
+template <int SIGN>
+__device__ __forceinline__ void dft4J(fc &a, fc &b, fc &c, fc &d) {
+	const fc apc = addJ<SIGN>(a, c), amc = subJ<SIGN>(a, c), bpd = fadd(b, d), bmd = fsub(b, d);
+	a = fadd(apc, bpd);
+	b = addJ<SIGN>(amc, bmd);
+	c = fsub(apc, bpd);
+	d = subJ<SIGN>(amc, bmd);
 }
 template <int SIGN>
-__device__ __forceinline__ void dft3(float2 &a, float2 &b, float2 &c) {
+__device__ __forceinline__ void dft3(fc &a, fc &b, fc &c) {
 	const float s3 = 0.86602540378443864676f;
-	float2 bpc = cadd(b, c), bmc = csub(b, c);
-	float2 t = make_float2(a.x - 0.5f*bpc.x, a.y - 0.5f*bpc.y);
-	float2 u = cscale((SIGN < 0) ? mulNegI(bmc) : mulI(bmc), s3);
-	a = cadd(a, bpc);
-	b = cadd(t, u);
-	c = csub(t, u);
+	const fc bpc = fadd(b, c), bmc = fsub(b, c);
+	const fc t = fmake(a.x - 0.5f*bpc.x, a.y - 0.5f*bpc.y);
+	const fc jb = mulJ<SIGN>(bmc);
+	const fc u = fmake(jb.x*s3, jb.y*s3);
+	a = fadd(a, bpc);
+	b = fadd(t, u);
+	c = fsub(t, u);
 }
 template <int SIGN>
-__device__ __forceinline__ void dft5(float2 &a, float2 &b, float2 &c, float2 &d, float2 &e) {
+__device__ __forceinline__ void dft5(fc &a, fc &b, fc &c, fc &d, fc &e) {
 	const float c1 = 0.30901699437494742410f, c2 = -0.80901699437494742410f;
 	const float s1 = 0.95105651629515357212f, s2 = 0.58778525229247312917f;
-	float2 bpe = cadd(b, e), bme = csub(b, e), cpd = cadd(c, d), cmd = csub(c, d);
-	float2 t1 = make_float2(a.x + c1*bpe.x + c2*cpd.x, a.y + c1*bpe.y + c2*cpd.y);
-	float2 t2 = make_float2(a.x + c2*bpe.x + c1*cpd.x, a.y + c2*bpe.y + c1*cpd.y);
-	float2 u1 = make_float2(s1*bme.x + s2*cmd.x, s1*bme.y + s2*cmd.y);
-	float2 u2 = make_float2(s2*bme.x - s1*cmd.x, s2*bme.y - s1*cmd.y);
-	float2 ju1 = (SIGN < 0) ? mulNegI(u1) : mulI(u1);
-	float2 ju2 = (SIGN < 0) ? mulNegI(u2) : mulI(u2);
-	a = cadd(a, cadd(bpe, cpd));
-	b = cadd(t1, ju1);
-	c = cadd(t2, ju2);
-	d = csub(t2, ju2);
-	e = csub(t1, ju1);
+	const fc bpe = fadd(b, e), bme = fsub(b, e), cpd = fadd(c, d), cmd = fsub(c, d);
+	const fc t1 = fmake(a.x + c1*bpe.x + c2*cpd.x, a.y + c1*bpe.y + c2*cpd.y);
+	const fc t2 = fmake(a.x + c2*bpe.x + c1*cpd.x, a.y + c2*bpe.y + c1*cpd.y);
+	const fc u1 = fmake(s1*bme.x + s2*cmd.x, s1*bme.y + s2*cmd.y);
+	const fc u2 = fmake(s2*bme.x - s1*cmd.x, s2*bme.y - s1*cmd.y);
+	a = fadd(a, fadd(bpe, cpd));
+	b = addJ<SIGN>(t1, u1);
+	c = addJ<SIGN>(t2, u2);
+	d = subJ<SIGN>(t2, u2);
+	e = subJ<SIGN>(t1, u1);
 }
 template <int SIGN>
-__device__ float2 *fftLds(float2 *src, float2 *dst, const FftPlan &plan, const float2 *__restrict__ tw) {
+__device__ float2 *fftLds(float2 *src2, float2 *dst2, const FftPlan &plan, const float2 *__restrict__ tw2) {
+	fc *src = reinterpret_cast<fc *>(src2), *dst = reinterpret_cast<fc *>(dst2);
+	const fc *__restrict__ tw = reinterpret_cast<const fc *>(tw2);
 	const int H = plan.H;
 	int nCur = H;
 	int shift = 0; // s = 1 << shift while radices are powers of two
@@ -68,34 +77,34 @@ __device__ float2 *fftLds(float2 *src, float2 *dst, const FftPlan &plan, const f
 			const int s = 1 << shift;
 			for (int t = threadIdx.x; t < nb; t += blockDim.x) {
 				const int p = t >> shift, q0 = t & (s - 1);
-				const float2 *in = src + q0 + (p << shift);
+				const fc *in = src + q0 + (p << shift);
 				const int inStride = m << shift;
-				float2 *out = dst + q0 + ((4*p) << shift);
-				float2 a = in[0], b = in[inStride], c = in[2*inStride], e = in[3*inStride];
+				fc *out = dst + q0 + ((4*p) << shift);
+				fc a = in[0], b = in[inStride], c = in[2*inStride], e = in[3*inStride];
 				dft4<SIGN>(a, b, c, e);
 				const int ti = p*twScale;
 				out[0] = a;
-				out[s] = cmulPlain(b, twiddle<SIGN>(tw, ti));
-				out[2*s] = cmulPlain(c, twiddle<SIGN>(tw, 2*ti));
-				out[3*s] = cmulPlain(e, twiddle<SIGN>(tw, 3*ti));
+				out[s] = mulTwiddle<SIGN>(b, tw[ti]);
+				out[2*s] = mulTwiddle<SIGN>(c, tw[2*ti]);
+				out[3*s] = mulTwiddle<SIGN>(e, tw[3*ti]);
 			}
 			shift += 2;
 		} else if (r == 2) {
 			const int s = 1 << shift;
 			for (int t = threadIdx.x; t < nb; t += blockDim.x) {
 				const int p = t >> shift, q0 = t & (s - 1);
-				const float2 *in = src + q0 + (p << shift);
+				const fc *in = src + q0 + (p << shift);
 				const int inStride = m << shift;
-				float2 *out = dst + q0 + ((2*p) << shift);
-				float2 a = in[0], b = in[inStride];
-				out[0] = cadd(a, b);
-				out[s] = cmulPlain(csub(a, b), twiddle<SIGN>(tw, p*twScale));
+				fc *out = dst + q0 + ((2*p) << shift);
+				const fc a = in[0], b = in[inStride];
+				out[0] = fadd(a, b);
+				out[s] = mulTwiddle<SIGN>(fsub(a, b), tw[p*twScale]);
 			}
 			shift += 1;
 		} else if (r == 3) { // last pass: m == 1, p == 0, all twiddles are 1
 			const int s = nb;
 			for (int t = threadIdx.x; t < nb; t += blockDim.x) {
-				float2 a = src[t], b = src[t + s], c = src[t + 2*s];
+				fc a = src[t], b = src[t + s], c = src[t + 2*s];
 				dft3<SIGN>(a, b, c);
 				dst[t] = a;
 				dst[t + s] = b;
@@ -104,7 +113,7 @@ __device__ float2 *fftLds(float2 *src, float2 *dst, const FftPlan &plan, const f
 		} else { // r == 5, last pass
 			const int s = nb;
 			for (int t = threadIdx.x; t < nb; t += blockDim.x) {
-				float2 a = src[t], b = src[t + s], c = src[t + 2*s], e = src[t + 3*s], f = src[t + 4*s];
+				fc a = src[t], b = src[t + s], c = src[t + 2*s], e = src[t + 3*s], f = src[t + 4*s];
 				dft5<SIGN>(a, b, c, e, f);
 				dst[t] = a;
 				dst[t + s] = b;
@@ -114,10 +123,10 @@ __device__ float2 *fftLds(float2 *src, float2 *dst, const FftPlan &plan, const f
 			}
 		}
 		__syncthreads();
-		float2 *tmp = src; src = dst; dst = tmp;
+		fc *tmp = src; src = dst; dst = tmp;
 		nCur = m;
 	}
-	return src;
+	return reinterpret_cast<float2 *>(src);
 }
 
 // ------------------------------------------------------------------------------------------------------
@@ -129,13 +138,13 @@ __device__ float2 *fftLds(float2 *src, float2 *dst, const FftPlan &plan, const f
 // Twiddles come from per-stage tables laid out [n][p] (coalesced across the threads of a stage).
 // ------------------------------------------------------------------------------------------------------
 template <int SIGN>
-__device__ __forceinline__ float2 mulConst(float2 v, float re, float im) { // v * (re, SIGN<0 ? -im : +im)
+__device__ __forceinline__ fc mulConst(fc v, float re, float im) { // v * (re, SIGN<0 ? -im : +im)
 	const float s = (SIGN < 0) ? -im : im;
-	return make_float2(v.x*re - v.y*s, v.x*s + v.y*re);
+	return fmake(v.x*re - v.y*s, v.x*s + v.y*re);
 }
 // 16-point DFT in place; on return X[e + 4c] sits at v[c + 4e]
 template <int SIGN>
-__device__ __forceinline__ void dft16(float2 (&v)[16]) {
+__device__ __forceinline__ void dft16(fc (&v)[16]) {
 #pragma unroll
 	for (int i = 0; i < 4; ++i) dft4<SIGN>(v[i], v[i + 4], v[i + 8], v[i + 12]);
 	const float c1 = 0.92387953251128675613f, s1 = 0.38268343236508977173f, h = 0.70710678118654752440f;
@@ -144,38 +153,40 @@ __device__ __forceinline__ void dft16(float2 (&v)[16]) {
 	v[1 + 8] = mulConst<SIGN>(v[1 + 8], h, h);     // w^2
 	v[1 + 12] = mulConst<SIGN>(v[1 + 12], s1, c1); // w^3
 	v[2 + 4] = mulConst<SIGN>(v[2 + 4], h, h);     // w^2
-	v[2 + 8] = (SIGN < 0) ? mulNegI(v[2 + 8]) : mulI(v[2 + 8]); // w^4
+	// v[2 + 8] *= w^4 = j: taken by the butterfly that reads it (dft4J)
 	v[2 + 12] = mulConst<SIGN>(v[2 + 12], -h, h);  // w^6
 	v[3 + 4] = mulConst<SIGN>(v[3 + 4], s1, c1);   // w^3
 	v[3 + 8] = mulConst<SIGN>(v[3 + 8], -h, h);    // w^6
 	v[3 + 12] = mulConst<SIGN>(v[3 + 12], -c1, -s1); // w^9
 #pragma unroll
-	for (int e = 0; e < 4; ++e) dft4<SIGN>(v[4*e], v[4*e + 1], v[4*e + 2], v[4*e + 3]);
+	for (int e = 0; e < 4; ++e) {
+		if (e == 2) dft4J<SIGN>(v[4*e], v[4*e + 1], v[4*e + 2], v[4*e + 3]);
+		else dft4<SIGN>(v[4*e], v[4*e + 1], v[4*e + 2], v[4*e + 3]);
+	}
 }
 // RA-point DFT over v[base + stride*j], j < RA (RA = 2, 4 or 8), in place, outputs in natural order
 template <int SIGN, int RA, int N>
-__device__ __forceinline__ void dftPow2(float2 (&v)[N], int base, int stride) {
+__device__ __forceinline__ void dftPow2(fc (&v)[N], int base, int stride) {
 	if constexpr (RA == 2) {
-		const float2 a = v[base], b = v[base + stride];
-		v[base] = cadd(a, b);
-		v[base + stride] = csub(a, b);
+		const fc a = v[base], b = v[base + stride];
+		v[base] = fadd(a, b);
+		v[base + stride] = fsub(a, b);
 	} else if constexpr (RA == 4) {
 		dft4<SIGN>(v[base], v[base + stride], v[base + 2*stride], v[base + 3*stride]);
 	} else {
 		static_assert(RA == 8, "radix 2, 4 or 8");
 		// even / odd halves (each a natural-order 4-point DFT), then X[k] = E[k] + w8^k O[k], X[k+4] = E[k] - w8^k O[k]
-		float2 e0 = v[base], e1 = v[base + 2*stride], e2 = v[base + 4*stride], e3 = v[base + 6*stride];
-		float2 o0 = v[base + stride], o1 = v[base + 3*stride], o2 = v[base + 5*stride], o3 = v[base + 7*stride];
+		fc e0 = v[base], e1 = v[base + 2*stride], e2 = v[base + 4*stride], e3 = v[base + 6*stride];
+		fc o0 = v[base + stride], o1 = v[base + 3*stride], o2 = v[base + 5*stride], o3 = v[base + 7*stride];
 		dft4<SIGN>(e0, e1, e2, e3);
 		dft4<SIGN>(o0, o1, o2, o3);
 		const float h = 0.70710678118654752440f;
 		o1 = mulConst<SIGN>(o1, h, h);
-		o2 = (SIGN < 0) ? mulNegI(o2) : mulI(o2);
 		o3 = mulConst<SIGN>(o3, -h, h);
-		v[base] = cadd(e0, o0); v[base + 4*stride] = csub(e0, o0);
-		v[base + stride] = cadd(e1, o1); v[base + 5*stride] = csub(e1, o1);
-		v[base + 2*stride] = cadd(e2, o2); v[base + 6*stride] = csub(e2, o2);
-		v[base + 3*stride] = cadd(e3, o3); v[base + 7*stride] = csub(e3, o3);
+		v[base] = fadd(e0, o0); v[base + 4*stride] = fsub(e0, o0);
+		v[base + stride] = fadd(e1, o1); v[base + 5*stride] = fsub(e1, o1);
+		v[base + 2*stride] = addJ<SIGN>(e2, o2); v[base + 6*stride] = subJ<SIGN>(e2, o2); // w8^2 = j
+		v[base + 3*stride] = fadd(e3, o3); v[base + 7*stride] = fsub(e3, o3);
 	}
 }
 // R3-point DFT (R3 = RA*G: RA = 2, 4 or 8 and G = 3 or 5) in place; on return X[e + RA*c] sits at v[c + G*e]
@@ -185,7 +196,7 @@ template <int R3> struct LastStage {
 	static_assert(R3%G == 0 && (RA == 2 || RA == 4 || RA == 8), "last stage: {2,4,8} x {3,5} points");
 };
 template <int SIGN, int R3>
-__device__ __forceinline__ void dftLast(float2 (&v)[R3]) {
+__device__ __forceinline__ void dftLast(fc (&v)[R3]) {
 	constexpr int G = LastStage<R3>::G, RA = LastStage<R3>::RA;
 #pragma unroll
 	for (int i = 0; i < G; ++i) dftPow2<SIGN, RA>(v, i, G);
@@ -206,7 +217,7 @@ __device__ __forceinline__ void dftLast(float2 (&v)[R3]) {
 	}
 }
 
-// load(idx) -> float2 supplies the natural-order input, store(idx, value) receives the natural-order output.
+// load(idx) -> fc supplies the natural-order input, store(idx, value) receives the natural-order output (an fc).
 // lds: H + H/16 float2.  All threads of the block must call this (it synchronises).
 // prep(idx) -> any value: called for ALL outputs of a thread before the first store(idx, value, prepared), so whatever it
 // loads is in flight together (a load placed inside `store` is not moved above the preceding stores by the compiler).
@@ -216,7 +227,7 @@ __device__ __forceinline__ void dftLast(float2 (&v)[R3]) {
 // eight) and nine products of two of them: one extra rounding each.
 struct BlockSync { __device__ __forceinline__ void operator()() const { __syncthreads(); } };
 struct NoHook { __device__ __forceinline__ void operator()() const {} };
-struct NoArrival { __device__ __forceinline__ float2 operator()(float2 v, int) const { return v; } };
+struct NoArrival { __device__ __forceinline__ fc operator()(fc v, int) const { return v; } };
 // t / sync: a workgroup may hold several TEAMS of 256 threads, each transforming its own frame in its own `lds` at its own pace;
 // t is then the index within the team and sync() the team's barrier.  Hooks of kSynthEmitTeams: lastRead() is called once the last
 // stage's operands have left `lds` (a barrier there lets `store` write into the same buffer); requested() once the frame's loads have
@@ -224,11 +235,12 @@ struct NoArrival { __device__ __forceinline__ float2 operator()(float2 v, int) c
 // after the first stage's writes
 template <int SIGN, int R3, bool LEAN, int ROUNDS = 0, typename Load, typename Prep, typename Store, typename Sync = BlockSync, typename LastRead = NoHook,
           typename Requested = NoHook, typename FirstWritten = NoHook, typename Arrived = NoArrival>
-__device__ __forceinline__ void fftFast(float2 *lds, const float4 *__restrict__ twA, const float4 *__restrict__ twB, Load load, Prep prep, Store store,
+__device__ __forceinline__ void fftFast(float2 *lds2, const float4 *__restrict__ twA, const float4 *__restrict__ twB, Load load, Prep prep, Store store,
                                         const int t = threadIdx.x, Sync sync = Sync(), LastRead lastRead = LastRead(), Requested requested = Requested(),
                                         FirstWritten firstWritten = FirstWritten(), Arrived arrived = Arrived()) {
 	constexpr int MA = 16*R3;
-	float2 v[16];
+	fc *lds = reinterpret_cast<fc *>(lds2);
+	fc v[16];
 	// stage A: radix 16, stride 1
 	if (t < MA) {
 #pragma unroll
@@ -238,16 +250,15 @@ __device__ __forceinline__ void fftFast(float2 *lds, const float4 *__restrict__ 
 	if (t < MA) {
 #pragma unroll
 		for (int k = 0; k < 16; ++k) v[k] = arrived(v[k], t + MA*k); // (anything `load` did to its value would be waited for in front of requested())
-		float2 w[16]; // w[n] = w_H^(n t) (conjugated for the inverse transform)
+		fc w[16]; // w[n] = w_H^(n t) (the inverse transform conjugates it in the product: mulTwiddle)
 		if constexpr (LEAN) {
 			const float4 a = twA[t], b = twA[MA + t], c = twA[2*MA + t]; // (w1, w2) (w3, w4) (w8, w12)
-			const float sg = (SIGN > 0) ? -1.0f : 1.0f;
-			w[1] = make_float2(a.x, sg*a.y); w[2] = make_float2(a.z, sg*a.w); w[3] = make_float2(b.x, sg*b.y); w[4] = make_float2(b.z, sg*b.w);
-			w[8] = make_float2(c.x, sg*c.y); w[12] = make_float2(c.z, sg*c.w);
+			w[1] = fmake(a.x, a.y); w[2] = fmake(a.z, a.w); w[3] = fmake(b.x, b.y); w[4] = fmake(b.z, b.w);
+			w[8] = fmake(c.x, c.y); w[12] = fmake(c.z, c.w);
 #pragma unroll
 			for (int hi = 4; hi <= 12; hi += 4) {
 #pragma unroll
-				for (int lo = 1; lo < 4; ++lo) w[hi + lo] = cmulPlain(w[hi], w[lo]);
+				for (int lo = 1; lo < 4; ++lo) w[hi + lo] = fmul<false>(w[hi], w[lo]); // (conj(a)*conj(b) = conj(a*b) bit for bit: smst_fft_complex.h)
 			}
 		} else {
 			float4 wA[8]; // the 15 stage twiddles, two per 16-byte load, in flight during the butterflies
@@ -256,17 +267,14 @@ __device__ __forceinline__ void fftFast(float2 *lds, const float4 *__restrict__ 
 #pragma unroll
 			for (int n = 1; n < 16; ++n) {
 				const float4 pr = wA[(n - 1) >> 1];
-				w[n] = ((n - 1) & 1) ? make_float2(pr.z, pr.w) : make_float2(pr.x, pr.y);
-				if (SIGN > 0) w[n].y = -w[n].y;
+				w[n] = ((n - 1) & 1) ? fmake(pr.z, pr.w) : fmake(pr.x, pr.y);
 			}
 		}
 		dft16<SIGN>(v);
 #pragma unroll
 		for (int pos = 0; pos < 16; ++pos) {
 			const int n = (pos >> 2) + 4*(pos & 3);
-			float2 val = v[pos];
-			if (n > 0) val = cmulPlain(val, w[n]);
-			lds[17*t + n] = val; // padded index of 16 t + n
+			lds[17*t + n] = n > 0 ? mulTwiddle<SIGN>(v[pos], w[n]) : v[pos]; // padded index of 16 t + n
 		}
 	}
 	firstWritten();
@@ -286,12 +294,10 @@ __device__ __forceinline__ void fftFast(float2 *lds, const float4 *__restrict__ 
 #pragma unroll
 		for (int pos = 0; pos < 16; ++pos) {
 			const int n = (pos >> 2) + 4*(pos & 3);
-			float2 val = v[pos];
+			fc val = v[pos];
 			if (n > 0) {
 				const float4 pr = wB[(n - 1) >> 1];
-				float2 w = ((n - 1) & 1) ? make_float2(pr.z, pr.w) : make_float2(pr.x, pr.y);
-				if (SIGN > 0) w.y = -w.y;
-				val = cmulPlain(val, w);
+				val = mulTwiddle<SIGN>(val, ((n - 1) & 1) ? fmake(pr.z, pr.w) : fmake(pr.x, pr.y));
 			}
 			lds[q0 + 256*p + 16*n] = val;
 		}
@@ -300,7 +306,7 @@ __device__ __forceinline__ void fftFast(float2 *lds, const float4 *__restrict__ 
 	// stage C: radix R3, stride 256, no twiddles
 	if (t < 256) {
 		constexpr int G = LastStage<R3>::G, RA = LastStage<R3>::RA;
-		float2 u[R3];
+		fc u[R3];
 #pragma unroll
 		for (int k = 0; k < R3; ++k) u[k] = lds[t + 256*k];
 		lastRead();
@@ -345,17 +351,13 @@ __device__ __forceinline__ int halfBinIndex(int j, int H, int N) {
 	const int kk = 2*j;
 	return kk >= H ? N - 1 - kk : kk;
 }
-__device__ __forceinline__ float2 loadHalfBin(const float2 *X, int j, int H, int N) {
+__device__ __forceinline__ fc loadHalfBin(const float2 *X, int j, int H, int N) {
 	// one load at a selected address, conjugated afterwards: with a load in each arm of the conditional the
 	// compiler emitted 16 loads each followed by s_waitcnt vmcnt(0) -- sixteen memory round trips per FFT
-	float2 v = X[halfBinIndex(j, H, N)];
-	if (2*j >= H) v.y = -v.y;
-	return v;
+	return fconjLoad(X + halfBinIndex(j, H, N), 2*j >= H);
 }
-__device__ __forceinline__ void storeHalfBin(float2 *dst, int j, float2 u, int H, int N) {
-	const int kk = 2*j;
-	if (kk < H) dst[kk] = u;
-	else dst[N - 1 - kk] = cconj(u);
+__device__ __forceinline__ void storeHalfBin(float2 *dst, int j, fc u, int H, int N) {
+	fconjStore(dst + halfBinIndex(j, H, N), u, 2*j >= H);
 }
 
 // The windowed analysis element m = t + MA*slot from the full table w = (winA[m], winB[m]), where the window's halves change validity at
@@ -369,20 +371,20 @@ __device__ __forceinline__ float2 analysisElement(float4 w, const float *x0, con
 }
 // The lean tables' generated modulation e^{-i pi m/N} of element m = t + stride*k, where e^{-i pi stride/N} = e^{-i pi/per}: hb = halfTw[t] times one
 // of `per` constants (compile-time after unrolling).  Analysis: k = slot, per = 32; synthesis: k = j, per = 2*R3.
-__device__ __forceinline__ float2 leanModulation(float2 hb, int k, int per) {
+__device__ __forceinline__ fc leanModulation(float2 hb, int k, int per) {
 	const float ang = 3.14159265358979323846f*float(k)/float(per);
-	return cmulPlain(hb, make_float2(__builtin_cosf(ang), -__builtin_sinf(ang)));
+	return fmulExpr(fpack(hb), fmake(__builtin_cosf(ang), -__builtin_sinf(ang)));
 }
 // Synthesis output m of a frame into dst (the frame in memory, or kSynthEmitTeams' copy in LDS): u * e^{+i pi m/N} (tw = e^{-i pi m/N}), its real
 // part under the window at m + B/2, its imaginary part at m - H + B/2
-__device__ __forceinline__ void storeWindowed(float *dst, int m, float2 u, float2 tw, float wRe, float wIm, int B, int H) {
+__device__ __forceinline__ void storeWindowed(float *dst, int m, fc u, fc tw, float wRe, float wIm, int B, int H) {
 	const int halfB = B/2;
-	const float2 v = cmulcPlain(u, tw); // * e^{+i pi m / N}
+	const fc v = fmulc(u, tw); // * e^{+i pi m / N}
 	if (m < B - halfB) dst[m + halfB] = (2*v.x)*wRe;
 	if (m >= H - halfB) dst[m - H + halfB] = (2*v.y)*wIm;
 }
-__device__ __forceinline__ void storeWindowed(float *dst, int m, float2 u, float4 r, int B, int H) { // r: the output's synTab entry
-	storeWindowed(dst, m, u, make_float2(r.x, r.y), r.z, r.w, B, H);
+__device__ __forceinline__ void storeWindowed(float *dst, int m, fc u, float4 r, int B, int H) { // r: the output's synTab entry
+	storeWindowed(dst, m, u, fmake(r.x, r.y), r.z, r.w, B, H);
 }
 
 // (windowPad / analysisWindowInCall: smst_device.h -- the host scheduler evaluates the same condition)
@@ -405,7 +407,7 @@ __global__ __launch_bounds__(fastBlockThreads(R3)) __attribute__((amdgpu_waves_p
 	const float2 *__restrict__ winA = d.winA, *__restrict__ winB = d.winB;
 	float2 *dst = (which ? d.Xprev : d.Xcur) + rowOf(d, s, k, c);
 	auto prep = [](int, int) { return 0; };
-	auto store = [&](int j, float2 u, int, int) { storeHalfBin(dst, j, u, H, N); };
+	auto store = [&](int j, fc u, int, int) { storeHalfBin(dst, j, u, H, N); };
 	constexpr int MA = 16*R3;
 	const float4 *__restrict__ twA = LEAN ? d.twA6 : d.twA4;
 	// LEAN: the folded window (w_re, w_im)(m) * e^{-i pi m/N} as TWO floats per element and the modulation generated: element
@@ -425,9 +427,9 @@ __global__ __launch_bounds__(fastBlockThreads(R3)) __attribute__((amdgpu_waves_p
 					float2 z = make_float2(0.f, 0.f);
 					if (slot < 15) z.x = x0[m]*w.x;
 					if (slot > 0) z.y = x1[m]*w.y;
-					return cmulPlain(z, leanModulation(hb, slot, 32));
+					return fmul<false>(fpack(z), leanModulation(hb, slot, 32));
 				} else {
-					return analysisElement(win4[m], x0, x1, m, slot); // (winA, winB) in one 16-byte load
+					return fpack(analysisElement(win4[m], x0, x1, m, slot)); // (winA, winB) in one 16-byte load
 				}
 			}, prep, store);
 		return;
@@ -442,10 +444,10 @@ __global__ __launch_bounds__(fastBlockThreads(R3)) __attribute__((amdgpu_waves_p
 			if (m >= H - halfB) { int src = base + m - H + halfB; xi = (src >= 0) ? x[src] : hist[src]; }
 			if constexpr (LEAN) {
 				const float2 w = win2[m];
-				return cmulPlain(make_float2(xr*w.x, xi*w.y), leanModulation(hb, slot, 32));
+				return fmul<false>(fmake(xr*w.x, xi*w.y), leanModulation(hb, slot, 32));
 			} else {
 				const float2 a = winA[m], b = winB[m];
-				return make_float2(fmaf(xi, b.x, xr*a.x), fmaf(xi, b.y, xr*a.y));
+				return fmake(fmaf(xi, b.x, xr*a.x), fmaf(xi, b.y, xr*a.y));
 			}
 		}, prep, store);
 }
@@ -523,9 +525,9 @@ __global__ __launch_bounds__(256*TEAMS) void kAnalyseTeams(DevBatch d, IoArgs io
 		const float *x0 = x + base + halfB, *x1 = x + base - H + halfB;
 		float2 *dst = (which ? d.Xprev : d.Xcur) + rowOf(d, bc.s, bc.x, c);
 		fftFast<-1, R3, false>(wg.lds, wg.twA, wg.twB,
-			[&](int m, int slot) { return analysisElement(wg.table[tA + MA*slot], x0, x1, m, slot); },
+			[&](int m, int slot) { return fpack(analysisElement(wg.table[tA + MA*slot], x0, x1, m, slot)); },
 			[](int, int) { return 0; },
-			[&](int j, float2 u, int, int) { storeHalfBin(dst, j, u, H, N); }, t, sync);
+			[&](int j, fc u, int, int) { storeHalfBin(dst, j, u, H, N); }, t, sync);
 		sync(); // the last stage's LDS reads, before the next frame's first-stage writes
 	}
 }
@@ -548,7 +550,7 @@ __global__ __launch_bounds__(fastBlockThreads(R3)) void kSynthFast(DevBatch d, i
 		const float2 hb = d.halfTw[min((int)threadIdx.x, 255)];
 		fftFast<+1, R3, true>(lds, d.twA6, d.twB4, loadBin,
 			[&](int m, int) { return win2[m]; },
-			[&](int m, float2 u, float2 w, int j) { storeWindowed(frame, m, u, leanModulation(hb, j, 2*R3), w.x, w.y, B, H); });
+			[&](int m, fc u, float2 w, int j) { storeWindowed(frame, m, u, leanModulation(hb, j, 2*R3), w.x, w.y, B, H); });
 	} else {
 		const float4 *__restrict__ synTab = d.synTab;
 		fftFast<+1, R3, false>(lds, d.twA4, d.twB4, loadBin,
@@ -556,7 +558,7 @@ __global__ __launch_bounds__(fastBlockThreads(R3)) void kSynthFast(DevBatch d, i
 				// requested for all of a thread's outputs before the first store
 				return synTab[m];
 			},
-			[&](int m, float2 u, float4 r, int) { storeWindowed(frame, m, u, r, B, H); });
+			[&](int m, fc u, float4 r, int) { storeWindowed(frame, m, u, r, B, H); });
 	}
 }
 
@@ -580,7 +582,7 @@ __global__ __launch_bounds__(256*TEAMS) void kSynthTeams(DevBatch d, const HopDe
 		fftFast<+1, R3, false>(wg.lds, wg.twA, wg.twB,
 			[&](int j, int) { return loadHalfBin(X, j, H, N); },
 			[&](int m, int) { return wg.table[m]; },
-			[&](int m, float2 u, float4 r, int) { storeWindowed(frame, m, u, r, B, H); }, wg.t, sync);
+			[&](int m, fc u, float4 r, int) { storeWindowed(frame, m, u, r, B, H); }, wg.t, sync);
 		sync(); // the last stage's LDS reads, before the next frame's first-stage writes
 	}
 }
@@ -810,9 +812,9 @@ __global__ __launch_bounds__(512) void kSynthEmitTeams(DevBatch d, IoArgs io, in
 		landed();
 		for (int q = 0; q < cnt; ++q) {
 			fftFast<+1, R3, false, 2>(lds, wg.twA, wg.twB, // (two rounds of prepared outputs: the ring and the next spectrum need the registers)
-				[&](int, int k) { return asyncValue(next[k]); },
+				[&](int, int k) { return fpack(asyncValue(next[k])); },
 				[&](int m, int) { return wg.table[m]; },
-				[&](int m, float2 u, float4 r, int) { storeWindowed(ex, m, u, r, B, H); }, t, sync, sync,
+				[&](int m, fc u, float4 r, int) { storeWindowed(ex, m, u, r, B, H); }, t, sync, sync,
 				[&]() {
 					if (q > 0) overlapAdd();
 					sync(); // the previous frame has been read (or the previous item's last one), before this transform's first-stage writes
@@ -821,7 +823,7 @@ __global__ __launch_bounds__(512) void kSynthEmitTeams(DevBatch d, IoArgs io, in
 					if (q > 0) emitFinal(q - 1);
 					request(q + 1 < cnt ? q + 1 : q);
 				},
-				[&](float2 v, int j) { if (2*j >= H) v.y = -v.y; return v; }); // ... conjugated once it is there
+				[&](fc v, int j) { return fconjIf(v, 2*j >= H); }); // ... conjugated once it is there
 			sync(); // the frame is complete
 			landed();
 		}
@@ -933,7 +935,7 @@ __global__ __launch_bounds__(256) void kAnalyse(DevBatch d, IoArgs io, int sBase
 			float v = (src >= 0) ? x[src] : hist[d.histLen + src];
 			im = v*win[i];
 		}
-		bufA[m] = cmulPlain(make_float2(re, im), d.halfTw[m]);
+		bufA[m] = funpack(fmul<false>(fmake(re, im), fpack(d.halfTw[m])));
 	}
 	__syncthreads();
 	float2 *res = fftLds<-1>(bufA, bufB, d.plan, d.twH);
@@ -943,7 +945,7 @@ __global__ __launch_bounds__(256) void kAnalyse(DevBatch d, IoArgs io, int sBase
 		res = bufA;
 	}
 	const int N = d.N;
-	for (int j = threadIdx.x; j < H; j += blockDim.x) storeHalfBin(dst, j, res[j], H, N);
+	for (int j = threadIdx.x; j < H; j += blockDim.x) storeHalfBin(dst, j, fpack(res[j]), H, N);
 }
 
 // ------------------------------------------------------------------------------------------------------
@@ -962,14 +964,14 @@ __global__ __launch_bounds__(256) void kSynth(DevBatch d, int sBase, int hopBase
 	if (!(hd.flags & HOP_ACTIVE)) return;
 	const int B = d.B, H = d.M, N = d.N, halfB = B/2;
 	const float2 *X = d.OUT + rowOf(d, s, k, c);
-	for (int j = threadIdx.x; j < H; j += blockDim.x) bufA[j] = loadHalfBin(X, j, H, N);
+	for (int j = threadIdx.x; j < H; j += blockDim.x) bufA[j] = funpack(loadHalfBin(X, j, H, N));
 	__syncthreads();
 	float2 *res = fftLds<+1>(bufA, bufB, d.plan, d.twH);
 	float *frame = frameOf(d, s, k, c);
 	const float *__restrict__ win = d.window;
 	for (int m = threadIdx.x; m < H; m += blockDim.x) {
 		const float wRe = (m < B - halfB) ? win[m + halfB] : 0.0f, wIm = (m >= H - halfB) ? win[m - H + halfB] : 0.0f; // (the absent halves are not stored)
-		storeWindowed(frame, m, res[m], d.halfTw[m], wRe, wIm, B, H);
+		storeWindowed(frame, m, fpack(res[m]), fpack(d.halfTw[m]), wRe, wIm, B, H);
 	}
 }
 

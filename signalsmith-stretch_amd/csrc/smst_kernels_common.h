@@ -22,6 +22,7 @@
 #include <cstring>
 #include "smst_device.h"
 #include <smst_complex.h> // angle brackets: tests/emu shadows this header for the CPU stand-in
+#include <smst_fft_complex.h> // likewise
 #include <smst_async.h>   // likewise
 
 
@@ -44,21 +45,12 @@ namespace smst {
 // ------------------------------------------------------------------------------------------------------
 // cmul(a, b) = a*b, cmulc(a, b) = a*conj(b), cfma(a, b, c) = a*b + c, clerp(lo, hi, fr): smst_complex.h (two packed-f32 VALU
 // instructions each; reference _impl::mul<false/true>, :17-26)
-// The FFT kernels keep the plain C++ products: they are bound by their memory operations, not by VALU issue, and the opaque
-// assembly statements cost them the compiler's load / compute interleaving (kSynthFast 2.93 -> 3.42 ms per step with the packed
-// helpers, same box)
-__device__ __forceinline__ float2 cmulPlain(float2 a, float2 b) { return make_float2(a.x*b.x - a.y*b.y, a.x*b.y + a.y*b.x); }
-__device__ __forceinline__ float2 cmulcPlain(float2 a, float2 b) { return make_float2(b.x*a.x + b.y*a.y, b.x*a.y - b.y*a.x); }
+// The FFT kernels' own primitives, with the roundings their C++ products always had: smst_fft_complex.h
 // |a|^2 with three separate roundings, never a fused multiply-add: the compiler otherwise contracts this differently from
 // one call site to the next (mul+fma here, packed mul + add there), and the SAME energy is computed at several sites
 // (carried Prediction.energy in kCarryFeed vs the producers' on-the-fly value) that must agree bit for bit
 __device__ __forceinline__ float cnorm(float2 a) { return __fadd_rn(__fmul_rn(a.x, a.x), __fmul_rn(a.y, a.y)); } // :27-31
-__device__ __forceinline__ float2 cadd(float2 a, float2 b) { return make_float2(a.x + b.x, a.y + b.y); }
-__device__ __forceinline__ float2 csub(float2 a, float2 b) { return make_float2(a.x - b.x, a.y - b.y); }
 __device__ __forceinline__ float2 cscale(float2 a, float s) { return make_float2(a.x*s, a.y*s); }
-__device__ __forceinline__ float2 cconj(float2 a) { return make_float2(a.x, -a.y); }
-__device__ __forceinline__ float2 mulI(float2 a) { return make_float2(-a.y, a.x); }
-__device__ __forceinline__ float2 mulNegI(float2 a) { return make_float2(a.y, -a.x); }
 
 // ------------------------------------------------------------------------------------------------------
 // Carried per-stream state in fp32 or -- opt-in per batch (BASELINE config 5 "fp16 internal") -- in fp16: Band.output as

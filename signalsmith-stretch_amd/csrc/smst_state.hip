@@ -247,6 +247,28 @@ __global__ __launch_bounds__(64) void kComplexSelfTest(const float *__restrict__
 void launchComplexSelfTest(const float *in, float *out, int n, hipStream_t st) {
 	hipLaunchKernelGGL(kComplexSelfTest, dim3((n + 63)/64), dim3(64), 0, st, in, out, n);
 }
+// smst_fft_complex.h: (a, b) -> fmul<false>, fmul<true>, fmulc, faddI, fsubI, fadd, fsub of (a, b), then a through the conjugating store (condition
+// true), the conjugating load (true) and load + store (false) -- ten complex results per tuple
+__global__ __launch_bounds__(64) void kFftComplexSelfTest(const float *__restrict__ in, float *__restrict__ out, int n) {
+	const int i = blockIdx.x*blockDim.x + threadIdx.x;
+	if (i >= n) return;
+	const float2 *v = reinterpret_cast<const float2 *>(in + (size_t)4*i);
+	const fc a = fconjLoad(v, false), b = fpack(v[1]);
+	float2 *o = reinterpret_cast<float2 *>(out + (size_t)20*i);
+	o[0] = funpack(fmul<false>(a, b));
+	o[1] = funpack(fmul<true>(a, b));
+	o[2] = funpack(fmulc(a, b));
+	o[3] = funpack(faddI(a, b));
+	o[4] = funpack(fsubI(a, b));
+	o[5] = funpack(fadd(a, b));
+	o[6] = funpack(fsub(a, b));
+	fconjStore(o + 7, a, true);
+	o[8] = funpack(fconjLoad(v, true));
+	fconjStore(o + 9, a, false);
+}
+void launchFftComplexSelfTest(const float *in, float *out, int n, hipStream_t st) {
+	hipLaunchKernelGGL(kFftComplexSelfTest, dim3((n + 63)/64), dim3(64), 0, st, in, out, n);
+}
 
 static std::atomic<long long> gLaunchCounts[LK_COUNT];
 static const char *const kLaunchNames[LK_COUNT] = {
