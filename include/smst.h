@@ -540,7 +540,7 @@ int smst_debug_complex_selftest(int device, const float *in, float *out, int n);
  * conjugating store, conj(a) from the conjugating load, a through both with the condition false) as 20 floats. */
 int smst_debug_fft_complex_selftest(int device, const float *in, float *out, int n);
 /* launches, since the library was loaded, of one kernel variant: "vocoder_aligned", "vocoder_staged", "vocoder_gather",
- * "vocoder_n", "vocoder_one", "vocoder_across", "vocoder_continuous", "chain_unfused", "analyse_teams", "analyse_fast", "analyse_generic",
+ * "vocoder_n", "vocoder_one", "vocoder_across", "vocoder_continuous", "chain_unfused", "analyse_teams", "analyse_pairs" (the two-frames-per-pass form of the analysis teams: such a launch counts in both), "analyse_fast", "analyse_generic",
  * "synth_teams", "synth_fast", "synth_generic", "synth_emit", "emit_carried", "feed_one_pass", "pcm_in", "pcm_out" (the conversion kernels of the _pcm calls, whatever
  * the format), "clip_in", "clip_out" (the copy kernels of the exact calls, planar or any format), "pcm_out_dithered", "clip_out_dithered" (a launch in
  * which at least one stream dithers into int16 or int24 counts here INSTEAD of "pcm_out" / "clip_out") (-1: unknown name).  The "this form is bit-identical to that form" tests

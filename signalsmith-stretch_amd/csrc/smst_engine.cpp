@@ -191,6 +191,7 @@ void Batch::construct(const FftPlan &plan, long seed) {
 	d.fftLean = sw.fftLean ? 1 : 0;
 	d.feedSerial = sw.feedSerial;
 	d.fftTeams = sw.fftTeams;
+	d.analysePairs = sw.analysePairs;
 	d.synthEmit = sw.synthEmit;
 	{
 		int cus = 0;

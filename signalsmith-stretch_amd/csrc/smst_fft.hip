@@ -233,23 +233,49 @@ struct NoArrival { __device__ __forceinline__ fc operator()(fc v, int) const { r
 // stage's operands have left `lds` (a barrier there lets `store` write into the same buffer); requested() once the frame's loads have
 // been issued and before anything is written to `lds` (the previous frame's overlap-add runs under the loads' latency), firstWritten()
 // after the first stage's writes
-template <int SIGN, int R3, bool LEAN, int ROUNDS = 0, typename Load, typename Prep, typename Store, typename Sync = BlockSync, typename LastRead = NoHook,
-          typename Requested = NoHook, typename FirstWritten = NoHook, typename Arrived = NoArrival>
+// FRAMES = 2 (kAnalyseTeamPairs): two frames in lockstep -- every stage runs for both between the same two barriers, frame f in its own buffer
+// lds + f*(H + H/16), and every table value is read once and used for both.  The arithmetic of one frame is that of FRAMES = 1, the same helpers
+// in the same order; the two frames' butterflies are independent chains.  load(idx, k) then returns a FrameSet<2> (both frames' element idx),
+// arrived takes (value, idx, k, frame), prep and store take the frame as a last argument.
+// TwRegs = StageTwiddles: the first-stage twiddles of thread t in registers (loaded once by the caller: they depend on t alone); twA is then unused.
+template <int FRAMES> struct FrameSet { fc f[FRAMES]; };
+struct StageTwiddles { float4 w[8]; }; // twA4[i*MA + t], i < 8
+struct TwiddlesFromTable {};
+template <int SIGN, int R3, bool LEAN, int ROUNDS = 0, int FRAMES = 1, typename Load, typename Prep, typename Store, typename Sync = BlockSync, typename LastRead = NoHook,
+          typename Requested = NoHook, typename FirstWritten = NoHook, typename Arrived = NoArrival, typename TwRegs = TwiddlesFromTable>
 __device__ __forceinline__ void fftFast(float2 *lds2, const float4 *__restrict__ twA, const float4 *__restrict__ twB, Load load, Prep prep, Store store,
                                         const int t = threadIdx.x, Sync sync = Sync(), LastRead lastRead = LastRead(), Requested requested = Requested(),
-                                        FirstWritten firstWritten = FirstWritten(), Arrived arrived = Arrived()) {
-	constexpr int MA = 16*R3;
+                                        FirstWritten firstWritten = FirstWritten(), Arrived arrived = Arrived(), TwRegs twRegs = TwRegs()) {
+	static_assert(FRAMES == 1 || FRAMES == 2, "one frame, or two in lockstep");
+	constexpr int MA = 16*R3, BUF = 17*MA; // BUF: a frame's padded buffer, H + H/16
+	constexpr bool TW_REGS = std::is_same<TwRegs, StageTwiddles>::value;
+	static_assert(!(TW_REGS && LEAN), "the lean tables have no register form");
 	fc *lds = reinterpret_cast<fc *>(lds2);
-	fc v[16];
+	auto prepOf = [&](int j, int idx, int f) { if constexpr (FRAMES == 1) return prep(j, idx); else return prep(j, idx, f); };
+	auto storeOf = [&](int j, fc u, auto r, int idx, int f) { if constexpr (FRAMES == 1) store(j, u, r, idx); else store(j, u, r, idx, f); };
+	fc v[FRAMES][16];
 	// stage A: radix 16, stride 1
 	if (t < MA) {
 #pragma unroll
-		for (int k = 0; k < 16; ++k) v[k] = load(t + MA*k, k);
+		for (int k = 0; k < 16; ++k) {
+			if constexpr (FRAMES == 1) v[0][k] = load(t + MA*k, k);
+			else {
+				const FrameSet<FRAMES> both = load(t + MA*k, k);
+#pragma unroll
+				for (int f = 0; f < FRAMES; ++f) v[f][k] = both.f[f];
+			}
+		}
 	}
 	requested();
 	if (t < MA) {
 #pragma unroll
-		for (int k = 0; k < 16; ++k) v[k] = arrived(v[k], t + MA*k); // (anything `load` did to its value would be waited for in front of requested())
+		for (int f = 0; f < FRAMES; ++f) {
+#pragma unroll
+			for (int k = 0; k < 16; ++k) { // (anything `load` did to its value would be waited for in front of requested())
+				if constexpr (FRAMES == 1) v[f][k] = arrived(v[f][k], t + MA*k);
+				else v[f][k] = arrived(v[f][k], t + MA*k, k, f);
+			}
+		}
 		fc w[16]; // w[n] = w_H^(n t) (the inverse transform conjugates it in the product: mulTwiddle)
 		if constexpr (LEAN) {
 			const float4 a = twA[t], b = twA[MA + t], c = twA[2*MA + t]; // (w1, w2) (w3, w4) (w8, w12)
@@ -263,18 +289,25 @@ __device__ __forceinline__ void fftFast(float2 *lds2, const float4 *__restrict__
 		} else {
 			float4 wA[8]; // the 15 stage twiddles, two per 16-byte load, in flight during the butterflies
 #pragma unroll
-			for (int i = 0; i < 8; ++i) wA[i] = twA[i*MA + t];
+			for (int i = 0; i < 8; ++i) {
+				if constexpr (TW_REGS) wA[i] = twRegs.w[i];
+				else wA[i] = twA[i*MA + t];
+			}
 #pragma unroll
 			for (int n = 1; n < 16; ++n) {
 				const float4 pr = wA[(n - 1) >> 1];
 				w[n] = ((n - 1) & 1) ? fmake(pr.z, pr.w) : fmake(pr.x, pr.y);
 			}
 		}
-		dft16<SIGN>(v);
 #pragma unroll
-		for (int pos = 0; pos < 16; ++pos) {
-			const int n = (pos >> 2) + 4*(pos & 3);
-			lds[17*t + n] = n > 0 ? mulTwiddle<SIGN>(v[pos], w[n]) : v[pos]; // padded index of 16 t + n
+		for (int f = 0; f < FRAMES; ++f) dft16<SIGN>(v[f]);
+#pragma unroll
+		for (int f = 0; f < FRAMES; ++f) {
+#pragma unroll
+			for (int pos = 0; pos < 16; ++pos) {
+				const int n = (pos >> 2) + 4*(pos & 3);
+				lds[f*BUF + 17*t + n] = n > 0 ? mulTwiddle<SIGN>(v[f][pos], w[n]) : v[f][pos]; // padded index of 16 t + n
+			}
 		}
 	}
 	firstWritten();
@@ -283,54 +316,71 @@ __device__ __forceinline__ void fftFast(float2 *lds2, const float4 *__restrict__
 	const int p = t >> 4, q0 = t & 15;
 	if (t < MA) {
 #pragma unroll
-		for (int k = 0; k < 16; ++k) v[k] = lds[q0 + 17*(p + R3*k)];
+		for (int f = 0; f < FRAMES; ++f) {
+#pragma unroll
+			for (int k = 0; k < 16; ++k) v[f][k] = lds[f*BUF + q0 + 17*(p + R3*k)];
+		}
 	}
 	sync();
 	if (t < MA) {
 		float4 wB[8];
 #pragma unroll
 		for (int i = 0; i < 8; ++i) wB[i] = twB[i*R3 + p];
-		dft16<SIGN>(v);
 #pragma unroll
-		for (int pos = 0; pos < 16; ++pos) {
-			const int n = (pos >> 2) + 4*(pos & 3);
-			fc val = v[pos];
-			if (n > 0) {
-				const float4 pr = wB[(n - 1) >> 1];
-				val = mulTwiddle<SIGN>(val, ((n - 1) & 1) ? fmake(pr.z, pr.w) : fmake(pr.x, pr.y));
+		for (int f = 0; f < FRAMES; ++f) dft16<SIGN>(v[f]);
+#pragma unroll
+		for (int f = 0; f < FRAMES; ++f) {
+#pragma unroll
+			for (int pos = 0; pos < 16; ++pos) {
+				const int n = (pos >> 2) + 4*(pos & 3);
+				fc val = v[f][pos];
+				if (n > 0) {
+					const float4 pr = wB[(n - 1) >> 1];
+					val = mulTwiddle<SIGN>(val, ((n - 1) & 1) ? fmake(pr.z, pr.w) : fmake(pr.x, pr.y));
+				}
+				lds[f*BUF + q0 + 256*p + 16*n] = val;
 			}
-			lds[q0 + 256*p + 16*n] = val;
 		}
 	}
 	sync();
 	// stage C: radix R3, stride 256, no twiddles
 	if (t < 256) {
 		constexpr int G = LastStage<R3>::G, RA = LastStage<R3>::RA;
-		fc u[R3];
+		fc u[FRAMES][R3];
 #pragma unroll
-		for (int k = 0; k < R3; ++k) u[k] = lds[t + 256*k];
+		for (int f = 0; f < FRAMES; ++f) {
+#pragma unroll
+			for (int k = 0; k < R3; ++k) u[f][k] = lds[f*BUF + t + 256*k];
+		}
 		lastRead();
 		constexpr int CHUNK = ROUNDS ? R3/ROUNDS : (R3 <= 12 ? R3 : (R3 == 24 ? 6 : 5)); // outputs prepared ahead of their stores (R3 = 20 / 24: four rounds, or the registers cost a wave of occupancy; ROUNDS: the caller's choice)
-		decltype(prep(0, 0)) ready[CHUNK];
+		decltype(prepOf(0, 0, 0)) ready[FRAMES][CHUNK];
 #pragma unroll
-		for (int i = 0; i < CHUNK; ++i) { // the first round's loads fly during the butterflies
-			const int e = i/G, c = i - G*e;
-			ready[i] = prep(t + 256*(e + RA*c), e + RA*c);
+		for (int f = 0; f < FRAMES; ++f) {
+#pragma unroll
+			for (int i = 0; i < CHUNK; ++i) { // the first round's loads fly during the butterflies
+				const int e = i/G, c = i - G*e;
+				ready[f][i] = prepOf(t + 256*(e + RA*c), e + RA*c, f);
+			}
 		}
-		dftLast<SIGN, R3>(u);
 #pragma unroll
-		for (int p0 = 0; p0 < R3; p0 += CHUNK) {
-			if (p0 > 0) {
+		for (int f = 0; f < FRAMES; ++f) dftLast<SIGN, R3>(u[f]);
+#pragma unroll
+		for (int f = 0; f < FRAMES; ++f) {
+#pragma unroll
+			for (int p0 = 0; p0 < R3; p0 += CHUNK) {
+				if (p0 > 0) {
+#pragma unroll
+					for (int i = 0; i < CHUNK; ++i) {
+						const int pos = p0 + i, e = pos/G, c = pos - G*e;
+						if (pos < R3) ready[f][i] = prepOf(t + 256*(e + RA*c), e + RA*c, f);
+					}
+				}
 #pragma unroll
 				for (int i = 0; i < CHUNK; ++i) {
 					const int pos = p0 + i, e = pos/G, c = pos - G*e;
-					if (pos < R3) ready[i] = prep(t + 256*(e + RA*c), e + RA*c);
+					if (pos < R3) storeOf(t + 256*(e + RA*c), u[f][pos], ready[f][i], e + RA*c, f);
 				}
-			}
-#pragma unroll
-			for (int i = 0; i < CHUNK; ++i) {
-				const int pos = p0 + i, e = pos/G, c = pos - G*e;
-				if (pos < R3) store(t + 256*(e + RA*c), u[pos], ready[i], e + RA*c);
 			}
 		}
 	}
@@ -363,11 +413,19 @@ __device__ __forceinline__ void storeHalfBin(float2 *dst, int j, fc u, int H, in
 // The windowed analysis element m = t + MA*slot from the full table w = (winA[m], winB[m]), where the window's halves change validity at
 // element-slot boundaries (slot 0 has no imaginary part, slot 15 no real part): the same roundings as kAnalyseFast's general path,
 // round(xi*b + round(xr*a)), with the absent half an exact zero
-__device__ __forceinline__ float2 analysisElement(float4 w, const float *x0, const float *x1, int m, int slot) {
+__device__ __forceinline__ float2 analysisElement(float4 w, float xr, float xi, int slot) { // (an absent half is not read: its sample is no operand)
 	float2 r = make_float2(0.f, 0.f);
-	if (slot < 15) { const float xr = x0[m]; r = make_float2(xr*w.x, xr*w.y); }
-	if (slot > 0) { const float xi = x1[m]; r = make_float2(fmaf(xi, w.z, r.x), fmaf(xi, w.w, r.y)); }
+	if (slot < 15) r = make_float2(xr*w.x, xr*w.y);
+	if (slot > 0) r = make_float2(fmaf(xi, w.z, r.x), fmaf(xi, w.w, r.y));
 	return r;
+}
+// the element's two samples, fetched apart from their window entry (kAnalyseTeamPairs: all of a pass's samples are requested before the table is read)
+__device__ __forceinline__ float2 analysisSamples(const float *x0, const float *x1, int m, int slot) {
+	return make_float2(slot < 15 ? x0[m] : 0.f, slot > 0 ? x1[m] : 0.f);
+}
+__device__ __forceinline__ float2 analysisElement(float4 w, const float *x0, const float *x1, int m, int slot) {
+	const float2 x = analysisSamples(x0, x1, m, slot);
+	return analysisElement(w, x.x, x.y, slot);
 }
 // The lean tables' generated modulation e^{-i pi m/N} of element m = t + stride*k, where e^{-i pi stride/N} = e^{-i pi/per}: hb = halfTw[t] times one
 // of `per` constants (compile-time after unrolling).  Analysis: k = slot, per = 32; synthesis: k = j, per = 2*R3.
@@ -475,12 +533,14 @@ struct TeamSync { // LDS operations of a wave complete in order: a wave's counte
 // A team workgroup's prologue (every thread of the workgroup constructs one): its LDS is the 16-byte table of the kernel's elements
 // (`source`: d.win4 or d.synTab, [H]), the first- and second-stage twiddles ([8][MA], [8][R3]), a transform buffer per team and the teams'
 // barrier words -- teamLdsBytes() on the host.  The tables are copied and the words cleared once per workgroup.
-template <int R3, int TEAMS>
+// FRAMES = 2 (kAnalyseTeamPairs): two transform buffers per team, one behind the other, and no first-stage twiddles in LDS (the threads hold
+// theirs in registers: StageTwiddles) -- the table, [8][R3] second-stage twiddles, TEAMS x FRAMES buffers, the barrier words.
+template <int R3, int TEAMS, int FRAMES = 1>
 struct TeamWorkgroup {
 	static_assert(16*R3 <= 256, "a team is 256 threads");
 	static constexpr int MA = 16*R3, H = 256*R3;
 	float4 *table, *twA, *twB;
-	float2 *lds;         // this team's transform buffer, H + H/16
+	float2 *lds;         // this team's transform buffer(s), H + H/16 each
 	int team, t;         // the team, the thread within it
 	volatile int *word;  // the team's barrier word
 	int generation = 0;
@@ -489,11 +549,15 @@ struct TeamWorkgroup {
 		t = threadIdx.x & 255;
 		table = reinterpret_cast<float4 *>(smem);
 		twA = table + H;
-		twB = twA + 8*MA;
-		lds = reinterpret_cast<float2 *>(twB + 8*R3) + (size_t)team*(H + H/16);
-		volatile int *words = reinterpret_cast<volatile int *>(reinterpret_cast<float2 *>(twB + 8*R3) + (size_t)TEAMS*(H + H/16));
+		twB = twA + (FRAMES == 1 ? 8*MA : 0);
+		lds = reinterpret_cast<float2 *>(twB + 8*R3) + (size_t)team*FRAMES*(H + H/16);
+		volatile int *words = reinterpret_cast<volatile int *>(reinterpret_cast<float2 *>(twB + 8*R3) + (size_t)TEAMS*FRAMES*(H + H/16));
 		for (int i = threadIdx.x; i < H; i += blockDim.x) table[i] = source[i];
-		for (int i = threadIdx.x; i < 8*MA; i += blockDim.x) twA[i] = d.twA4[i];
+		if constexpr (FRAMES == 1) {
+			for (int i = threadIdx.x; i < 8*MA; i += blockDim.x) twA[i] = d.twA4[i];
+		} else {
+			twA = nullptr;
+		}
 		for (int i = threadIdx.x; i < 8*R3; i += blockDim.x) twB[i] = d.twB4[i];
 		if (threadIdx.x < 16) words[threadIdx.x] = 0;
 		__syncthreads();
@@ -529,6 +593,103 @@ __global__ __launch_bounds__(256*TEAMS) void kAnalyseTeams(DevBatch d, IoArgs io
 			[](int, int) { return 0; },
 			[&](int j, fc u, int, int) { storeHalfBin(dst, j, u, H, N); }, t, sync);
 		sync(); // the last stage's LDS reads, before the next frame's first-stage writes
+	}
+}
+
+// kAnalyseTeams, two frames per team pass (the default; SMST_ANALYSE_PAIRS=0: the single-frame teams above).  A frame of kAnalyseTeams is one
+// serial chain per team -- 30 loads, a radix-16 stage on 3 of its 4 waves, a barrier, another, a barrier, the last stage, 12 stores -- and three
+// such chains per SIMD left the vector ALUs idle two thirds of the time.  Here a workgroup is TWO teams, two waves per SIMD with 256 registers
+// each, and a team takes two frames through the transform in lockstep (fftFast<FRAMES = 2>): the two frames' butterflies are independent work
+// inside each wave, a pass has the four team barriers a single frame had, and every window entry and stage twiddle is read once for the two.
+// The first-stage twiddles depend on the thread alone and live in registers for the whole launch.
+// A pass is two consecutive positions of ONE stream's job order (xcdAwareCoord's: the hop fastest, then channel and window) -- hops x and
+// x + 1 of one (channel, window) but where a row of the order ends --, so both frames stay on the stream's XCD.  Each frame has its own
+// predicate, exactly kAnalyseTeams' (what this kernel leaves, kAnalyseFast's lateOnly pass takes): a pass with one wanted frame transforms
+// that frame alone, a pass with none is skipped.  inSamples: io.inSamples as a pointer the compiler may read through the scalar cache, like
+// hopTable -- a pass begins with three scalar loads issued together and then all of its sample loads.
+// Same table values, same operations in the same order on each frame: bit-identical to kAnalyseTeams and kAnalyseFast.
+template <int R3, bool EXACT>
+__global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) void kAnalyseTeamPairs(DevBatch d, IoArgs io, const HopDesc *__restrict__ hopTable, const int *__restrict__ inSamples, int sBase, int hopBase, int tileHops, int nStreams) {
+	extern __shared__ __attribute__((aligned(16))) unsigned char smemRaw[];
+	constexpr int TEAMS = 2, MA = 16*R3, H = 256*R3, N = 2*H;
+	const int B = EXACT ? 480*R3 : d.B, halfB = B/2; // EXACT: the geometry this kernel is launched for
+	const int jobs = tileHops*2*d.C;                 // of one stream
+	const int passes = (jobs + 1)/2, total = passes*nStreams;
+	static_assert((H + 8*R3)*sizeof(float4) + TEAMS*2*(H + H/16)*sizeof(float2) + 64 <= 160*1024, "the window, the second-stage twiddles, four transform buffers and the barrier words fit a CU's LDS (155,200 bytes at R3 = 12)");
+	TeamWorkgroup<R3, TEAMS, 2> wg(smemRaw, d, d.win4); // table: (winA, winB) of all elements
+	const TeamSync sync = wg.sync();
+	const int t = wg.t, tA = t < MA ? t : 0;
+	StageTwiddles twA;
+#pragma unroll
+	for (int i = 0; i < 8; ++i) twA.w[i] = d.twA4[i*MA + tA];
+	// Round i deals the passes [i*stride, (i + 1)*stride) to the teams, each team keeping its residue mod 8 (its XCD).  With a fixed place in
+	// every round a team would move on by stride/8 passes of a stream per round -- 64 on 256 CUs, two whole rows of a 64-hop tile, so it would
+	// meet the SAME window of the same or the other channel every time, and at stretch 1.0, where no hop re-analyses its previous window, one
+	// team of every workgroup would find all of its passes unwanted.  The teams' places therefore rotate by `turn` per round (a bijection of
+	// the round's passes onto the teams all the same), chosen so that a team moves on by an odd number of rows.
+	const int stride = gridDim.x*TEAMS, rowPasses = (tileHops + 1)/2;
+	const int turn = 8*((((rowPasses - stride/8)%(2*rowPasses)) + 2*rowPasses)%(2*rowPasses));
+	const int place = blockIdx.x + gridDim.x*wg.team;
+	for (int round = 0; round*stride < total; ++round) {
+		const int lin = round*stride + (place + round*turn)%stride;
+		if (lin >= total) continue; // (the last round)
+		const BlockCoord pc = xcdAwareCoord(lin, passes, 1, nStreams); // x: the pass of stream s
+		const int nIn = inSamples[sBase + pc.s];
+		HopDesc hd[2];
+		BlockCoord bc[2];
+		bool have[2];
+#pragma unroll
+		for (int f = 0; f < 2; ++f) {
+			const int job = 2*pc.x + f;
+			have[f] = job < jobs; // (an odd job count: the last pass has one frame)
+			const int j = have[f] ? job : 2*pc.x;
+			bc[f].y = j/tileHops;
+			bc[f].x = j - bc[f].y*tileHops;
+			bc[f].s = pc.s;
+			hd[f] = hopTable[(size_t)(sBase + pc.s)*d.hopStride + hopBase + bc[f].x];
+		}
+		const float *x0[2], *x1[2];
+		float2 *dst[2];
+		bool on[2];
+#pragma unroll
+		for (int f = 0; f < 2; ++f) {
+			const int c = bc[f].y >> 1, which = bc[f].y & 1;
+			// (no short cut between the conditions: both descriptors and the stream's length are requested before the first of them is looked at)
+			const bool wanted = hopWantsAnalysis(hd[f], which), inCall = analysisWindowInCall(B, H, d.I, hd[f].inputOffset, which, nIn);
+			on[f] = have[f] & wanted & inCall;
+			const int base = hd[f].inputOffset - (which ? d.I : 0) - B;
+			const float *x = io.in + (size_t)(sBase + pc.s)*io.inStreamStride + (size_t)c*io.inChannelStride;
+			x0[f] = x + base + halfB;
+			x1[f] = x + base - H + halfB;
+			dst[f] = (which ? d.Xprev : d.Xcur) + rowOf(d, pc.s, bc[f].x, c);
+		}
+		if (!on[0] && !on[1]) continue;
+		auto prep = [](int, int, int = 0) { return 0; };
+		if (on[0] && on[1]) {
+			float4 win[16]; // the window entries of the thread's elements: one read for the two frames
+			fftFast<-1, R3, false, 0, 2>(wg.lds, nullptr, wg.twB,
+				[&](int m, int slot) {
+					FrameSet<2> r;
+#pragma unroll
+					for (int f = 0; f < 2; ++f) r.f[f] = fpack(analysisSamples(x0[f], x1[f], m, slot));
+					return r;
+				},
+				prep, [&](int j, fc u, int, int, int f) { storeHalfBin(dst[f], j, u, H, N); }, t, sync, NoHook(),
+				[&]() { // all 60 samples are on their way: the table is read under their latency, and nothing below moves above this point
+#pragma unroll
+					for (int slot = 0; slot < 16; ++slot) win[slot] = wg.table[tA + MA*slot];
+					asm volatile("" ::: "memory");
+				},
+				NoHook(), [&](fc x, int, int slot, int) { return fpack(analysisElement(win[slot], x.x, x.y, slot)); }, twA);
+		} else {
+			const int f = on[0] ? 0 : 1; // the other slot does nothing
+			const float *xa = x0[f], *xb = x1[f];
+			float2 *dstOne = dst[f];
+			fftFast<-1, R3, false>(wg.lds, nullptr, wg.twB,
+				[&](int m, int slot) { return fpack(analysisElement(wg.table[tA + MA*slot], xa, xb, m, slot)); },
+				prep, [&](int j, fc u, int, int) { storeHalfBin(dstOne, j, u, H, N); }, t, sync, NoHook(), NoHook(), NoHook(), NoArrival(), twA);
+		}
+		sync(); // the last stage's LDS reads, before the next pass's first-stage writes
 	}
 }
 
@@ -1108,14 +1269,20 @@ static void withFlag(bool flag, F f) { // f(flag as a compile-time constant)
 	if (flag) f(std::true_type()); else f(std::false_type());
 }
 static size_t fastLdsBytes(int M) { return ((size_t)M + M/16)*sizeof(float2); } // fftFast's padded buffer
-static size_t teamLdsBytes(int M, int teams) { // TeamWorkgroup: element table, first- and second-stage twiddles, a buffer per team, barrier words
-	return ((size_t)M + M/2 + M/32)*sizeof(float4) + teams*fastLdsBytes(M) + 64;
+static size_t teamLdsBytes(int M, int teams, int frames = 1) { // TeamWorkgroup: element table, first- and second-stage twiddles, a buffer per team and frame, barrier words
+	const size_t twA = frames == 1 ? M/2 : 0; // (two frames per pass: the first-stage twiddles are in registers)
+	return ((size_t)M + twA + M/32)*sizeof(float4) + teams*frames*fastLdsBytes(M) + 64;
 }
 static bool fastApplies(const DevBatch &d) { return !d.noFastFft && isFastSize(d.M); }
 // (asks withTeamR3 itself, so a launcher that finds the teams to apply always has a team kernel to launch)
 static bool teamsAvailable(const DevBatch &d) { return fastApplies(d) && withTeamR3(d.M, [](auto) {}) && d.fftTeams && !d.fftLean; }
 // persistent teams pay a 76-KB table copy per workgroup: only where every team gets a few frames
 static bool teamsApply(const DevBatch &d, int jobs) { return teamsAvailable(d) && (d.fftTeams == 2 || jobs >= 6*d.teamsGrid); }
+// the analysis teams take two frames per pass (kAnalyseTeamPairs) wherever they apply: both geometries measured ahead of the single-frame form
+static bool analysePairsApply(const DevBatch &d) { return d.analysePairs != 0; }
+static int pairWorkgroups(const DevBatch &d, int passes) { // two teams each, otherwise as teamsWorkgroups
+	return std::max(8, std::min((passes + 1)/2/8*8, d.teamsGrid));
+}
 static int teamsWorkgroups(const DevBatch &d, int jobs) { // three teams each: one workgroup per CU, a multiple of 8 (one residue class of the job order per XCD)
 	return std::max(8, std::min((jobs + 2)/3/8*8, d.teamsGrid));
 }
@@ -1129,10 +1296,14 @@ void launchAnalyse(const DevBatch &d, const IoArgs &io, int sBase, int nStreams,
 	const bool teams = anyInCall && teamsApply(d, jobs);
 	if (teams) {
 		const WindowPad pad = windowPad(d.B, d.M);
+		const bool pairs = analysePairsApply(d);
+		const int passes = (tileHops*d.C*2 + 1)/2*nStreams;
 		withTeamR3(d.M, [&](auto r3) { withFlag(pad.lo == 0 && pad.hi == 0, [&](auto exact) {
-			hipLaunchKernelGGL((kAnalyseTeams<r3.value, 3, exact.value>), dim3(teamsWorkgroups(d, jobs)), dim3(768), teamLdsBytes(d.M, 3), st, d, io, d.hops, sBase, hopBase, tileHops, nStreams);
+			if (pairs) hipLaunchKernelGGL((kAnalyseTeamPairs<r3.value, exact.value>), dim3(pairWorkgroups(d, passes)), dim3(512), teamLdsBytes(d.M, 2, 2), st, d, io, d.hops, io.inSamples, sBase, hopBase, tileHops, nStreams);
+			else hipLaunchKernelGGL((kAnalyseTeams<r3.value, 3, exact.value>), dim3(teamsWorkgroups(d, jobs)), dim3(768), teamLdsBytes(d.M, 3), st, d, io, d.hops, sBase, hopBase, tileHops, nStreams);
 		}); });
-		countLaunch(LK_ANALYSE_TEAMS);
+		countLaunch(LK_ANALYSE_TEAMS); // (either form)
+		if (pairs) countLaunch(LK_ANALYSE_PAIRS);
 		if (!anyLate) return;
 	}
 	const int lateOnly = teams ? 1 : 0; // the frames whose windows reach into the carried history

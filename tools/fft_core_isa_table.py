@@ -8,12 +8,17 @@ between the two; the frame loop is the innermost such body that holds the transf
 and the edge loops hold none, a branch back inside the transform holds a part of it, the item loop around kSynthEmitTeams' hop loop contains it).  The kernels of one frame per workgroup (kAnalyseFast -- two
 copies of the transform, the usual case and the general one --, kSynthFast, kAnalyse, kSynth) are counted whole.
 
-usage: fft_core_isa_table.py [<label>=]<assembly> [[<label>=]<assembly of another build> ...]   -> one table per file on stdout"""
+kAnalyseTeamPairs' loop holds two copies of the transform: the pass of two frames in lockstep (two thirds of its packed instructions) and the
+pass with one wanted frame.
+
+usage: fft_core_isa_table.py [<label>=]<assembly> [[<label>=]<assembly of another build> ...]   -> one table per file on stdout
+       fft_core_isa_table.py --check-budgets <assembly>   -> exit status 1 unless the build keeps kAnalyseTeamPairs' budgets (csrc/Makefile runs this):
+       its four instantiations exist, none uses scratch, each is compiled for exactly two waves per SIMD"""
 import re
 import subprocess
 import sys
 
-KERNELS = ("kAnalyseTeams", "kSynthTeams", "kSynthEmitTeams", "kAnalyseFast", "kSynthFast", "kAnalyse", "kSynth")
+KERNELS = ("kAnalyseTeamPairs", "kAnalyseTeams", "kSynthTeams", "kSynthEmitTeams", "kAnalyseFast", "kSynthFast", "kAnalyse", "kSynth")
 PACKED = re.compile(r"v_pk_(mul|fma|add)_f32")
 SCALAR_F32 = re.compile(r"v_(mul|fma|fmac|add|sub|subrev|mac|mad)_f32")
 
@@ -102,7 +107,7 @@ def table(arg):
         if not short.startswith(KERNELS):
             continue
         ins, labels = instructions(lines)
-        span = frame_loop(ins, labels) if "Teams" in short else None
+        span = frame_loop(ins, labels) if "Team" in short else None
         ops = [op for _, op, _ in (ins[span[0]:span[1] + 1] if span else ins)]
         rows.append((short, "loop" if span else "whole", meta, classify(ops)))
     rows.sort()
@@ -114,6 +119,20 @@ def table(arg):
     print()
 
 
+def check_budgets(path):
+    funcs = functions(open(path).read())
+    names = demangle([f[0] for f in funcs])
+    pairs = [(names[m], meta) for m, _, meta in funcs if "kAnalyseTeamPairs<" in names[m]]
+    bad = ["%s: %s" % (n, meta) for n, meta in pairs if meta.get("ScratchSize") != 0 or meta.get("Occupancy") != 2 or meta.get("TotalNumVgprs", 999) > 256]
+    if len(pairs) != 4 or bad:
+        print("kAnalyseTeamPairs budgets (four instantiations, no scratch, two waves per SIMD, <= 256 registers): %d instantiation(s); %s" % (len(pairs), "; ".join(bad) or "none over budget"))
+        return 1
+    print("kAnalyseTeamPairs budgets: 4 instantiations, no scratch, two waves per SIMD, %s VGPRs" % " / ".join(str(meta["TotalNumVgprs"]) for _, meta in pairs))
+    return 0
+
+
 if __name__ == "__main__":
+    if sys.argv[1:2] == ["--check-budgets"]:
+        sys.exit(check_budgets(sys.argv[2]))
     for p in sys.argv[1:]:
         table(p)
