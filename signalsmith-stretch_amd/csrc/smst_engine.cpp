@@ -137,6 +137,19 @@ Batch::Batch(int streams, int channels, int block, int interval, bool splitCompu
 
 void Batch::construct(const FftPlan &plan, long seed) {
 	SMST_HIP(hipSetDevice(dev));
+	createStreamsAndEvents();
+	readSwitches(plan);
+	uploadConstantTables();
+	allocateCarriedState();
+	allocateCallTables();
+	initHostRows(seed);
+	allocateWorkspace();
+	allocateSplitTables();
+	SMST_HIP(hipDeviceSynchronize()); // the hipMemset calls above are ordered with the null stream only; the engine's streams are non-blocking
+	reset();
+}
+
+void Batch::createStreamsAndEvents() {
 	SMST_HIP(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
 	{ // the recurrence is latency-bound with few waves: give its stream the highest priority so its workgroups are
 	  // dispatched ahead of the bulk kernels' when they share the machine (raising the analysis stream as well makes
@@ -159,6 +172,9 @@ void Batch::construct(const FftPlan &plan, long seed) {
 		SMST_HIP(hipEventCreateWithFlags(&evOut[i], hipEventDisableTiming));
 		SMST_HIP(hipEventCreateWithFlags(&evSynth[i], hipEventDisableTiming));
 	}
+}
+
+void Batch::readSwitches(const FftPlan &plan) { // ... and the geometry, into `d`
 	// the cross-check switches: one struct, one table, read once (smst_switches.h)
 	const Switches sw = Switches::fromEnvironment();
 	overlap = sw.overlap; noFuse = sw.noFuse; noSingleHop = sw.noSingleHop; noAcross = sw.noAcross; carriedEmit = sw.carriedEmit != 0; checkLaunches = sw.checkLaunches; continuous = sw.continuous; contWriterWave = sw.contWriterWave;
@@ -198,8 +214,9 @@ void Batch::construct(const FftPlan &plan, long seed) {
 		SMST_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
 		d.teamsGrid = std::max(8, cus/8*8);
 	}
+}
 
-	// constant tables
+void Batch::uploadConstantTables() {
 	std::vector<float2> tw(M), half(M), rot(M);
 	for (int j = 0; j < M; ++j) {
 		double a = -2*M_PI*double(j)/double(M);
@@ -310,31 +327,62 @@ void Batch::construct(const FftPlan &plan, long seed) {
 	}
 	d.wprod = static_cast<float *>(upload(wprod.data(), B*sizeof(float)));
 
-	const size_t bandRows = (size_t)S*C*M;
-	d.stInput = devAlloc<float2>(bandRows);
-	d.stPrev = devAlloc<float2>(bandRows);
-	// carried state that the fp16 option narrows (the typed pointers then address half-sized allocations; every access goes
-	// through the accessors at the top of smst_kernels_common.h)
-	const size_t stateScale = halfState ? 2 : 1;
-	d.stOut = reinterpret_cast<float2 *>(devAlloc<unsigned char>(bandRows*sizeof(float2)/stateScale));
-	d.stEnergy = reinterpret_cast<float *>(devAlloc<unsigned char>(bandRows*sizeof(float)/stateScale + 16)); // (+16: PrevEnergy::at reads 8 bytes at an element)
-	SMST_HIP(hipMemset(d.stEnergy, 0, bandRows*sizeof(float)/stateScale + 16));
+}
+
+// The one list of the carried device arrays (CarriedArray, smst_engine.h).  The typed pointers of the narrowed arrays address half-sized
+// allocations; every access goes through the accessors at the top of smst_kernels_common.h.
+std::array<Batch::CarriedArray, Batch::kCarriedArrays> Batch::carriedArrays() {
+	const size_t band = (size_t)C*M, word = sizeof(float), stored = halfState ? sizeof(half_t) : sizeof(float);
+	auto at = [](auto *&p) { return reinterpret_cast<void **>(&p); };
+	auto single = [&](auto *&p, size_t rowBytes) { return CarriedArray{{at(p), nullptr}, nullptr, rowBytes, false, false, 0, false}; };
+	auto twice = [&](auto *(&p)[2], const int &cur, size_t rowBytes) { return CarriedArray{{at(p[0]), at(p[1])}, &cur, rowBytes, false, false, 0, false}; };
+	std::array<CarriedArray, kCarriedArrays> a{};
+	a[kStInput] = single(d.stInput, band*2*word);
+	a[kStPrev] = single(d.stPrev, band*2*word);
+	a[kStOut] = single(d.stOut, band*2*stored);
+	a[kStEnergy] = single(d.stEnergy, band*stored);
+	a[kStEnergy].slack = 16; // (PrevEnergy::at reads 8 bytes at an element)
+	a[kStEnergy].zeroed = true;
+	a[kHist] = single(d.hist, (size_t)C*d.histPitch*word);
+	a[kHistBase] = twice(d.histBase, d.histCur, sizeof(int));
+	a[kCarryBase] = twice(d.carryBase, d.carryCur, sizeof(int)); // (a row of the overlap-add carry moves with its carryBase entry: the window keeps its place in the row)
+	a[kHistBase].zeroed = a[kCarryBase].zeroed = true;
+	a[kCarrySum] = twice(d.carrySum, d.carryCur, (size_t)C*d.carryPitch*stored);
+	a[kCarryWp] = twice(d.carryWp, d.carryCur, (size_t)d.carryPitch*word);
+	a[kStFreq] = single(d.stFreq, 2*word);
+	// the block in flight: its spectra, Band.input and (re-analysed) Band.prevInput (PendingBlock, smst_engine.h)
+	a[kPendIn] = single(dPendIn, (size_t)C*d.Mp*2*word);
+	a[kPendPrev] = single(dPendPrev, (size_t)C*d.Mp*2*word);
+	a[kPendIn].splitOnly = a[kPendPrev].splitOnly = true;
+	a[kPendIn].zeroed = a[kPendPrev].zeroed = true;
+	a[kStOut].narrowed = a[kStEnergy].narrowed = a[kCarrySum].narrowed = halfState;
+	return a;
+}
+void Batch::allocateCarried(int first, int last) { // entries [first, last) of the list, double-buffered ones half by half
+	const auto list = carriedArrays();
+	for (int h = 0; h < 2; ++h)
+		for (int i = first; i < last; ++i) {
+			const CarriedArray &a = list[i];
+			if (h >= a.halves()) continue;
+			const size_t bytes = (size_t)S*a.rowBytes + a.slack;
+			*a.ptr[h] = devAlloc<unsigned char>(bytes);
+			if (a.zeroed) SMST_HIP(hipMemset(*a.ptr[h], 0, bytes));
+		}
+}
+
+void Batch::allocateCarriedState() {
 	d.histPitch = 2*d.histLen;
 	d.carryPitch = d.carryLen + 2*I;
-	d.hist = devAlloc<float>((size_t)S*C*d.histPitch);
+	allocateCarried(kStInput, kHistBase);
 	dZeroEmit = devAlloc<EmitDesc>(S); // (settleCarry)
 	SMST_HIP(hipMemset(dZeroEmit, 0, (size_t)S*sizeof(EmitDesc)));
-	for (int h = 0; h < 2; ++h) {
-		d.histBase[h] = devAlloc<int>((size_t)S);
-		SMST_HIP(hipMemset(d.histBase[h], 0, (size_t)S*sizeof(int)));
-		d.carrySum[h] = reinterpret_cast<float *>(devAlloc<unsigned char>((size_t)S*C*d.carryPitch*sizeof(float)/stateScale));
-		d.carryWp[h] = devAlloc<float>((size_t)S*d.carryPitch);
-		d.carryBase[h] = devAlloc<int>((size_t)S);
-		SMST_HIP(hipMemset(d.carryBase[h], 0, (size_t)S*sizeof(int)));
-	}
+	allocateCarried(kHistBase, kStFreq);
 	d.wpHeadLen = ((B + I - 1)/I + 2)*I;
 	d.wpHead = devAlloc<float>((size_t)S*d.wpHeadLen);
-	d.stFreq = devAlloc<float>((size_t)S*2);
+	allocateCarried(kStFreq, kPendIn);
+}
+
+void Batch::allocateCallTables() {
 	dParams = devAlloc<StreamParams>(S);
 	d.params = d.paramsPeaks = d.paramsForm0 = d.paramsForm2 = dParams;
 	dEnergy = devAlloc<float>((size_t)S*kEnergyParts);
@@ -367,7 +415,10 @@ void Batch::construct(const FftPlan &plan, long seed) {
 	dResetBits = devAlloc<int>(S);
 	dKeep = devAlloc<int>(S);
 	resetBitsV.assign(S, 0);
+	keepV.assign(S, 0);
+}
 
+void Batch::initHostRows(long seed) {
 	sched.assign(S, StreamSched());
 	lastHop.assign(S, LastHop());
 	// std::default_random_engine (libstdc++: minstd_rand0) of a reference instance constructed with seed + s (:39; smst_kernels_common.h: engineDraw)
@@ -381,41 +432,34 @@ void Batch::construct(const FftPlan &plan, long seed) {
 	p.formantMultiplier = 1; p.invFormantMultiplier = 1; p.formantBaseFreq = 0; p.formantCompensation = 0; p.hasCustomMap = 0;
 	params.assign(S, p);
 	paramsDirty = true;
-
-	allocateWorkspace();
 	pend.assign(S, PendingBlock());
 	lastSteps.assign(S, 0);
 	lastStarts.assign(S, 0);
 	histBase.assign(S, 0);
 	carryBase.assign(S, 0);
-	keepV.assign(S, 0);
-	if (split) { // the block in flight: its spectra, and the tables of the run that completes it (PendingBlock, smst_engine.h)
-		const size_t rows = (size_t)S*C*d.Mp;
-		dPendIn = devAlloc<float2>(rows);
-		dPendPrev = devAlloc<float2>(rows);
-		SMST_HIP(hipMemset(dPendIn, 0, rows*sizeof(float2)));
-		SMST_HIP(hipMemset(dPendPrev, 0, rows*sizeof(float2)));
-		const int nSub = (S + subS - 1)/subS;
-		for (int i = 0; i < 2; ++i) {
-			PendSet &ps = pendSets[i];
-			ps.hops = devAlloc<HopDesc>(S + kTileHops); ps.hHops = pinnedAlloc<HopDesc>(S); // (+ a tile's worth: the wavefront kernels cache a blind row of 64 descriptors per stream, hopStride 1)
-			SMST_HIP(hipMemset(ps.hops, 0, (size_t)(S + kTileHops)*sizeof(HopDesc)));
-			ps.emit = devAlloc<EmitDesc>(S); ps.hEmit = pinnedAlloc<EmitDesc>(S);
-			ps.tileInfo = devAlloc<int>((size_t)nSub*2*subS); ps.hTileInfo = pinnedAlloc<int>((size_t)nSub*2*subS);
-			ps.bits = devAlloc<int>(S); ps.hBits = pinnedAlloc<int>(S);
-			ps.synthChannels = devAlloc<int>(S); ps.hSynthChannels = pinnedAlloc<int>(S);
-			for (int j = 0; j < 3; ++j) { ps.prm[j] = devAlloc<StreamParams>(S); ps.hPrm[j] = pinnedAlloc<StreamParams>(S); }
-			SMST_HIP(hipEventCreateWithFlags(&ps.done, hipEventDisableTiming));
-			ps.used = false;
-		}
-		dZeroCounts = devAlloc<int>(S);
-		SMST_HIP(hipMemset(dZeroCounts, 0, S*sizeof(int)));
-		pendList.reserve(S);
-		pendTileHas.assign(nSub, TileSummary{});
-		pendMaxSpan.assign(nSub, 0);
+}
+
+void Batch::allocateSplitTables() { // the block in flight: its spectra, and the tables of the run that completes it
+	if (!split) return;
+	allocateCarried(kPendIn, kCarriedArrays);
+	const int nSub = (S + subS - 1)/subS;
+	for (int i = 0; i < 2; ++i) {
+		PendSet &ps = pendSets[i];
+		ps.hops = devAlloc<HopDesc>(S + kTileHops); ps.hHops = pinnedAlloc<HopDesc>(S); // (+ a tile's worth: the wavefront kernels cache a blind row of 64 descriptors per stream, hopStride 1)
+		SMST_HIP(hipMemset(ps.hops, 0, (size_t)(S + kTileHops)*sizeof(HopDesc)));
+		ps.emit = devAlloc<EmitDesc>(S); ps.hEmit = pinnedAlloc<EmitDesc>(S);
+		ps.tileInfo = devAlloc<int>((size_t)nSub*2*subS); ps.hTileInfo = pinnedAlloc<int>((size_t)nSub*2*subS);
+		ps.bits = devAlloc<int>(S); ps.hBits = pinnedAlloc<int>(S);
+		ps.synthChannels = devAlloc<int>(S); ps.hSynthChannels = pinnedAlloc<int>(S);
+		for (int j = 0; j < 3; ++j) { ps.prm[j] = devAlloc<StreamParams>(S); ps.hPrm[j] = pinnedAlloc<StreamParams>(S); }
+		SMST_HIP(hipEventCreateWithFlags(&ps.done, hipEventDisableTiming));
+		ps.used = false;
 	}
-	SMST_HIP(hipDeviceSynchronize()); // the hipMemset calls above are ordered with the null stream only; the engine's streams are non-blocking
-	reset();
+	dZeroCounts = devAlloc<int>(S);
+	SMST_HIP(hipMemset(dZeroCounts, 0, S*sizeof(int)));
+	pendList.reserve(S);
+	pendTileHas.assign(nSub, TileSummary{});
+	pendMaxSpan.assign(nSub, 0);
 }
 
 Batch::~Batch() { releaseAll(); }
@@ -580,19 +624,32 @@ void Batch::resetStreams(const int *bitsHost, int allBits, const int *keepHost) 
 
 void Batch::reset() { // signalsmith-stretch.h:49-60
 	SMST_HIP(hipSetDevice(dev));
-	SMST_HIP(hipMemsetAsync(d.stFreq, 0, (size_t)S*2*sizeof(float), st));
+	const CarriedArray freq = carriedArrays()[kStFreq];
+	SMST_HIP(hipMemsetAsync(freq.current(), 0, (size_t)S*freq.rowBytes, st));
 	resetStreams(nullptr, RESET_STFT | RESET_INPUT | RESET_PREV | RESET_OUTPUT);
-	for (auto &lh : lastHop) lh = LastHop();
-	std::fill(lastSteps.begin(), lastSteps.end(), 0);
-	std::fill(lastStarts.begin(), lastStarts.end(), 0);
 	d.histCur = 0;
 	d.carryCur = 0;
-	for (int s = 0; s < S; ++s) {
-		const unsigned seed = seedAfterDroppedBlock(s); // reset() leaves the reference's randomEngine alone; a block in flight is dropped with the draws it has made
-		pend[s] = PendingBlock(); // blockProcess = {}
-		sched[s] = StreamSched();
-		sched[s].seed = seed;
-	}
+	for (int s = 0; s < S; ++s) clearHostRow(s);
+}
+void Batch::clearHostRow(int s) { // (histBase / carryBase: resetStreams)
+	const unsigned seed = seedAfterDroppedBlock(s); // reset() leaves the reference's randomEngine alone; a block in flight is dropped with the draws it has made
+	pend[s] = PendingBlock(); // blockProcess = {}
+	sched[s] = StreamSched();
+	sched[s].seed = seed;
+	lastHop[s] = LastHop();
+	lastSteps[s] = 0;
+	lastStarts[s] = 0;
+}
+void Batch::takeHostRow(const Batch &o, int from, int to) {
+	sched[to] = o.sched[from];
+	params[to] = o.params[from];
+	pend[to] = o.pend[from];
+	lastSteps[to] = o.lastSteps[from]; // smst_block_steps of a clone = the original's newest block
+	lastStarts[to] = o.lastStarts[from];
+	histBase[to] = o.histBase[from];
+	carryBase[to] = o.carryBase[from];
+	lastHop[to] = LastHop();
+	paramsDirty = true;
 }
 
 void Batch::resetStream(int s) { // reset() for one stream
@@ -606,16 +663,7 @@ void Batch::resetStreamsMasked(const unsigned char *active) { // reset() for the
 	SMST_HIP(hipStreamSynchronize(st)); // (an earlier launch may still read the mask buffer)
 	for (int s = 0; s < S; ++s) resetBitsV[s] = active[s] ? (RESET_STFT | RESET_INPUT | RESET_PREV | RESET_OUTPUT | RESET_FREQ) : 0;
 	resetStreams(resetBitsV.data(), 0);
-	for (int s = 0; s < S; ++s) {
-		if (!active[s]) continue;
-		lastHop[s] = LastHop();
-		lastSteps[s] = 0;
-		lastStarts[s] = 0;
-		const unsigned seed = seedAfterDroppedBlock(s);
-		pend[s] = PendingBlock();
-		sched[s] = StreamSched();
-		sched[s].seed = seed;
-	}
+	for (int s = 0; s < S; ++s) if (active[s]) clearHostRow(s);
 }
 
 // ---- parameters ------------------------------------------------------------------------------------------
@@ -683,15 +731,8 @@ void Batch::setFreqMapTable(int stream, const float *table, int n) { // table fo
 	}
 	if (!anyCustom) d.mapTableLen = 0;
 	if (n > d.mapTableLen) {
-		std::vector<float> grown((size_t)S*kMapSlots*n, 0.0f);
-		for (size_t row = 0; row < (size_t)S*kMapSlots && d.mapTableLen > 0; ++row) // (rows that hold no table are zeros either way)
-			std::copy(hostMapTable.begin() + row*d.mapTableLen, hostMapTable.begin() + (row + 1)*d.mapTableLen, grown.begin() + row*n);
 		SMST_HIP(hipStreamSynchronize(st)); // kernels of earlier calls may still read the old array
-		if (dMapTable) devFree(dMapTable);
-		dMapTable = devAlloc<float>((size_t)S*kMapSlots*n);
-		hostMapTable.swap(grown);
-		d.mapTableLen = n;
-		d.mapTable = dMapTable;
+		growMapTable(n);
 	}
 	const int pitch = d.mapTableLen;
 	forStreams(S, stream, [&](int s) {
@@ -703,8 +744,23 @@ void Batch::setFreqMapTable(int stream, const float *table, int n) { // table fo
 		params[s].mapSlot = slot;
 	});
 	SMST_HIP(hipStreamSynchronize(st)); // kernels of earlier calls may still read the old table
-	SMST_HIP(hipMemcpy(dMapTable, hostMapTable.data(), hostMapTable.size()*sizeof(float), hipMemcpyHostToDevice));
+	uploadMapTable();
 	paramsDirty = true;
+}
+// hostMapTable is [S][kMapSlots][d.mapTableLen] throughout; the caller has synchronised `st` (the old array is freed)
+void Batch::growMapTable(int pitch) {
+	const size_t rows = (size_t)S*kMapSlots, have = (size_t)d.mapTableLen;
+	std::vector<float> grown(rows*pitch, 0.0f);
+	for (size_t row = 0; row < rows && have > 0; ++row) // (rows that hold no table are zeros either way)
+		std::copy(hostMapTable.begin() + row*have, hostMapTable.begin() + (row + 1)*have, grown.begin() + row*pitch);
+	if (dMapTable) devFree(dMapTable);
+	dMapTable = devAlloc<float>(grown.size());
+	hostMapTable.swap(grown);
+	d.mapTableLen = pitch;
+	d.mapTable = dMapTable;
+}
+void Batch::uploadMapTable() {
+	SMST_HIP(hipMemcpy(dMapTable, hostMapTable.data(), hostMapTable.size()*sizeof(float), hipMemcpyHostToDevice));
 }
 
 void Batch::checkLaunch(const char *what) {
@@ -1805,49 +1861,11 @@ void Batch::exact(const ClipIo &io, const int *inSamples, const int *outSamples,
 }
 
 // ---- copy -------------------------------------------------------------------------------------------------
-void Batch::copyStateFrom(Batch &o) {
-	if (o.S != S || o.C != C || o.B != B || o.I != I || o.split != split || o.halfState != halfState) throw Error("copyStateFrom: the two batches differ in geometry");
-	SMST_HIP(hipSetDevice(o.dev));
-	SMST_HIP(hipStreamSynchronize(o.st));
-	SMST_HIP(hipSetDevice(dev));
-	SMST_HIP(hipStreamSynchronize(st));
-	const size_t bandRows = (size_t)S*C*M, scale = halfState ? 2 : 1;
-	auto copy = [&](void *dst, const void *src, size_t bytes) { SMST_HIP(hipMemcpy(dst, src, bytes, hipMemcpyDefault)); };
-	copy(d.stInput, o.d.stInput, bandRows*sizeof(float2));
-	copy(d.stPrev, o.d.stPrev, bandRows*sizeof(float2));
-	copy(d.stOut, o.d.stOut, bandRows*sizeof(float2)/scale);
-	copy(d.stEnergy, o.d.stEnergy, bandRows*sizeof(float)/scale);
-	copy(d.hist, o.d.hist, (size_t)S*C*d.histPitch*sizeof(float));
-	histBase = o.histBase;
-	carryBase = o.carryBase;
-	for (int h = 0; h < 2; ++h) {
-		copy(d.histBase[h], o.d.histBase[h], (size_t)S*sizeof(int));
-		copy(d.carrySum[h], o.d.carrySum[h], (size_t)S*C*d.carryPitch*sizeof(float)/scale);
-		copy(d.carryWp[h], o.d.carryWp[h], (size_t)S*d.carryPitch*sizeof(float));
-		copy(d.carryBase[h], o.d.carryBase[h], (size_t)S*sizeof(int));
-	}
-	copy(d.stFreq, o.d.stFreq, (size_t)S*2*sizeof(float));
-	d.histCur = o.d.histCur;
-	d.carryCur = o.d.carryCur;
-	sched = o.sched;
-	params = o.params;
-	paramsDirty = true;
-	pend = o.pend;
-	lastSteps = o.lastSteps; // smst_block_steps of a clone = the original's newest block
-	lastStarts = o.lastStarts;
-	if (split) {
-		copy(dPendIn, o.dPendIn, (size_t)S*C*d.Mp*sizeof(float2));
-		copy(dPendPrev, o.dPendPrev, (size_t)S*C*d.Mp*sizeof(float2));
-	}
-	if (o.d.mapTableLen > 0) {
-		if (dMapTable) devFree(dMapTable);
-		dMapTable = devAlloc<float>((size_t)S*kMapSlots*o.d.mapTableLen);
-		hostMapTable = o.hostMapTable;
-		SMST_HIP(hipMemcpy(dMapTable, hostMapTable.data(), hostMapTable.size()*sizeof(float), hipMemcpyHostToDevice));
-		d.mapTableLen = o.d.mapTableLen;
-		d.mapTable = dMapTable;
-	}
-	for (auto &lh : lastHop) lh = LastHop();
+void Batch::copyStateFrom(Batch &o) { // every stream of a batch of the same shape (the move checks the rest of the geometry and the device)
+	if (o.S != S) throw Error("copyStateFrom: the two batches differ in geometry");
+	std::vector<int> all(S);
+	for (int s = 0; s < S; ++s) all[s] = s;
+	moveStreamsFrom(o, all.data(), all.data(), S);
 }
 
 void Batch::moveStreamsFrom(Batch &o, const int *from, const int *to, int n) {
@@ -1861,31 +1879,15 @@ void Batch::moveStreamsFrom(Batch &o, const int *from, const int *to, int n) {
 	SMST_HIP(hipSetDevice(dev));
 	SMST_HIP(hipStreamSynchronize(o.st));
 	SMST_HIP(hipStreamSynchronize(st));
-	// (a row of the overlap-add carry moves with its carryBase entry: the window keeps its place in the row)
 	MoveArgs a{};
-	auto seg = [&](const void *src, void *dst, size_t rowBytes, size_t srcPitch, size_t dstPitch) {
-		if (a.nSeg >= kMoveSegs) throw Error("moveStreamsFrom: too many state arrays");
-		MoveSeg &g = a.seg[a.nSeg++];
-		g.src = static_cast<const char *>(src); g.dst = static_cast<char *>(dst);
-		g.rowBytes = rowBytes; g.srcPitch = srcPitch; g.dstPitch = dstPitch;
-	};
-	auto rows = [&](const void *src, void *dst, size_t rowBytes) { seg(src, dst, rowBytes, rowBytes, rowBytes); };
-	const size_t band = (size_t)C*M, scale = halfState ? 2 : 1;
-	rows(o.d.stInput, d.stInput, band*sizeof(float2));
-	rows(o.d.stPrev, d.stPrev, band*sizeof(float2));
-	rows(o.d.stOut, d.stOut, band*sizeof(float2)/scale);
-	rows(o.d.stEnergy, d.stEnergy, band*sizeof(float)/scale);
-	rows(o.d.hist, d.hist, (size_t)C*d.histPitch*sizeof(float));
-	rows(o.d.stFreq, d.stFreq, 2*sizeof(float));
-	for (int h = 0; h < 2; ++h) { // the source's current half into both halves
-		rows(o.d.histBase[o.d.histCur], d.histBase[h], sizeof(int));
-		rows(o.d.carryBase[o.d.carryCur], d.carryBase[h], sizeof(int));
-		rows(o.d.carrySum[o.d.carryCur], d.carrySum[h], (size_t)C*d.carryPitch*sizeof(float)/scale);
-		rows(o.d.carryWp[o.d.carryCur], d.carryWp[h], (size_t)d.carryPitch*sizeof(float));
-	}
-	if (split) {
-		rows(o.dPendIn, dPendIn, (size_t)C*d.Mp*sizeof(float2));
-		rows(o.dPendPrev, dPendPrev, (size_t)C*d.Mp*sizeof(float2));
+	const auto theirs = o.carriedArrays(), mine = carriedArrays();
+	for (int i = 0; i < kCarriedArrays; ++i) {
+		if (mine[i].splitOnly && !split) continue;
+		for (int h = 0; h < mine[i].halves(); ++h) { // the source's current half into both halves
+			MoveSeg &g = a.seg[a.nSeg++];
+			g.src = theirs[i].current(); g.dst = static_cast<char *>(*mine[i].ptr[h]);
+			g.rowBytes = g.srcPitch = g.dstPitch = mine[i].rowBytes;
+		}
 	}
 	std::vector<int> pairs((size_t)2*n);
 	for (int p = 0; p < n; ++p) { pairs[2*p] = from[p]; pairs[2*p + 1] = to[p]; }
@@ -1900,41 +1902,19 @@ void Batch::moveStreamsFrom(Batch &o, const int *from, const int *to, int n) {
 	SMST_HIP(hipGetLastError());
 	SMST_HIP(hipStreamSynchronize(st));
 	devFree(dPairs);
-	// the host's side of the same rows
-	for (int p = 0; p < n; ++p) {
-		const int f = from[p], t = to[p];
-		sched[t] = o.sched[f];
-		params[t] = o.params[f];
-		pend[t] = o.pend[f];
-		lastSteps[t] = o.lastSteps[f];
-		lastStarts[t] = o.lastStarts[f];
-		histBase[t] = o.histBase[f];
-		carryBase[t] = o.carryBase[f];
-		lastHop[t] = LastHop();
-	}
-	paramsDirty = true;
+	for (int p = 0; p < n; ++p) takeHostRow(o, from[p], to[p]);
 	// the streams' own frequency-map tables, knot for knot: every row of the source's pitch fits the (possibly grown) pitch here
 	if (o.d.mapTableLen > 0) {
-		const int have = d.mapTableLen, need = std::max(have, o.d.mapTableLen);
-		if (need > have || hostMapTable.size() != (size_t)S*kMapSlots*need) {
-			std::vector<float> grown((size_t)S*kMapSlots*need, 0.0f);
-			for (size_t row = 0; row < (size_t)S*kMapSlots && have > 0 && hostMapTable.size() >= (size_t)S*kMapSlots*have; ++row)
-				std::copy(hostMapTable.begin() + row*have, hostMapTable.begin() + (row + 1)*have, grown.begin() + row*need);
-			if (dMapTable) devFree(dMapTable);
-			dMapTable = devAlloc<float>(grown.size());
-			hostMapTable.swap(grown);
-			d.mapTableLen = need;
-			d.mapTable = dMapTable;
-		}
-		const size_t op = (size_t)o.d.mapTableLen;
+		if (o.d.mapTableLen > d.mapTableLen) growMapTable(o.d.mapTableLen);
+		const size_t op = (size_t)o.d.mapTableLen, pitch = (size_t)d.mapTableLen;
 		for (int p = 0; p < n; ++p)
 			for (int slot = 0; slot < kMapSlots; ++slot) {
-				float *dstRow = hostMapTable.data() + ((size_t)to[p]*kMapSlots + slot)*need;
+				float *dstRow = hostMapTable.data() + ((size_t)to[p]*kMapSlots + slot)*pitch;
 				const float *srcRow = o.hostMapTable.data() + ((size_t)from[p]*kMapSlots + slot)*op;
 				std::copy(srcRow, srcRow + op, dstRow);
-				std::fill(dstRow + op, dstRow + need, 0.0f);
+				std::fill(dstRow + op, dstRow + pitch, 0.0f);
 			}
-		SMST_HIP(hipMemcpy(dMapTable, hostMapTable.data(), hostMapTable.size()*sizeof(float), hipMemcpyHostToDevice));
+		uploadMapTable();
 	}
 }
 
@@ -1942,11 +1922,12 @@ void Batch::inheritAcrossConfigure(Batch &o) {
 	if (o.S != S) throw Error("inheritAcrossConfigure: stream counts differ");
 	SMST_HIP(hipSetDevice(o.dev));
 	SMST_HIP(hipStreamSynchronize(o.st));
-	std::vector<float> freq((size_t)S*2);
-	SMST_HIP(hipMemcpy(freq.data(), o.d.stFreq, freq.size()*sizeof(float), hipMemcpyDeviceToHost));
+	const CarriedArray theirs = o.carriedArrays()[kStFreq], mine = carriedArrays()[kStFreq];
+	std::vector<char> freq((size_t)S*mine.rowBytes);
+	SMST_HIP(hipMemcpy(freq.data(), theirs.current(), freq.size(), hipMemcpyDeviceToHost));
 	SMST_HIP(hipSetDevice(dev));
 	SMST_HIP(hipStreamSynchronize(st));
-	SMST_HIP(hipMemcpy(d.stFreq, freq.data(), freq.size()*sizeof(float), hipMemcpyHostToDevice));
+	SMST_HIP(hipMemcpy(mine.current(), freq.data(), freq.size(), hipMemcpyHostToDevice));
 	for (int s = 0; s < S; ++s) {
 		const StreamSched &from = o.sched[s];
 		StreamSched &to = sched[s];
@@ -1963,58 +1944,45 @@ void Batch::inheritAcrossConfigure(Batch &o) {
 void Batch::debugGetState(int stream, int which, float *dst) {
 	SMST_HIP(hipSetDevice(dev));
 	SMST_HIP(hipStreamSynchronize(st));
-	const size_t off = (size_t)stream*C*M, n = (size_t)C*M;
-	if (halfState && (which == 2 || which == 3)) { // fp16 storage: widen on the host (energy is stored as its square root)
-		const size_t count = which == 2 ? 2*n : n;
-		std::vector<half_t> tmp(count);
-		const half_t *src = which == 2 ? reinterpret_cast<const half_t *>(d.stOut) + 2*off : reinterpret_cast<const half_t *>(d.stEnergy) + off;
-		SMST_HIP(hipMemcpy(tmp.data(), src, count*sizeof(half_t), hipMemcpyDeviceToHost));
-		for (size_t i = 0; i < count; ++i) { const float v = float(tmp[i]); dst[i] = which == 3 ? v*v : v; }
-		return;
-	}
-	if (which == 3) {
-		SMST_HIP(hipMemcpy(dst, d.stEnergy + off, n*sizeof(float), hipMemcpyDeviceToHost));
-		return;
-	}
-	const float2 *src = which == 0 ? d.stInput : (which == 1 ? d.stPrev : d.stOut);
-	SMST_HIP(hipMemcpy(dst, src + off, n*sizeof(float2), hipMemcpyDeviceToHost));
+	const StatePlane p = statePlane(stream, which);
+	debugCopy(false, p.row, dst, 1, p.values, p.values, p.narrowed, p.root);
 }
 void Batch::debugSetState(int stream, int which, const float *src) {
-	if (stream < 0 || stream >= S || which < 0 || which > 3) throw Error("debugSetState: bad stream / selector");
+	const StatePlane p = statePlane(stream, which);
 	SMST_HIP(hipSetDevice(dev));
 	SMST_HIP(hipStreamSynchronize(st));
-	const size_t off = (size_t)stream*C*M, n = (size_t)C*M;
-	if (halfState && (which == 2 || which == 3)) {
-		const size_t count = which == 2 ? 2*n : n;
-		std::vector<half_t> tmp(count);
-		for (size_t i = 0; i < count; ++i) tmp[i] = half_t(which == 3 ? std::sqrt(std::max(src[i], 0.0f)) : src[i]);
-		half_t *dst = which == 2 ? reinterpret_cast<half_t *>(d.stOut) + 2*off : reinterpret_cast<half_t *>(d.stEnergy) + off;
-		SMST_HIP(hipMemcpy(dst, tmp.data(), count*sizeof(half_t), hipMemcpyHostToDevice));
-		return;
-	}
-	if (which == 3) {
-		SMST_HIP(hipMemcpy(d.stEnergy + off, src, n*sizeof(float), hipMemcpyHostToDevice));
-		return;
-	}
-	float2 *dst = which == 0 ? d.stInput : (which == 1 ? d.stPrev : d.stOut);
-	SMST_HIP(hipMemcpy(dst + off, src, n*sizeof(float2), hipMemcpyHostToDevice));
+	debugCopy(true, p.row, const_cast<float *>(src), 1, p.values, p.values, p.narrowed, p.root);
 }
-void Batch::debugSetCarry(int stream, const float *sums, const float *products) {
-	if (stream < 0 || stream >= S) throw Error("debugSetCarry: bad stream");
+Batch::StatePlane Batch::statePlane(int stream, int which) { // 0 input, 1 prevInput, 2 output: 2*C*M floats; 3 energy: C*M, kept as its square root in fp16
+	static_assert(kStInput == 0 && kStPrev == 1 && kStOut == 2 && kStEnergy == 3, "the debug selectors are the list's first entries");
+	if (stream < 0 || stream >= S || which < 0 || which > 3) throw Error("debug state: bad stream / selector");
+	const CarriedArray a = carriedArrays()[which];
+	return StatePlane{a.current() + (size_t)stream*a.rowBytes, (size_t)C*M*(which == kStEnergy ? 1 : 2), a.narrowed, which == kStEnergy};
+}
+// fp16 storage widens / narrows on the host
+void Batch::debugCopy(bool set, void *device, float *host, size_t rows, size_t len, size_t devPitch, bool narrowed, bool root) {
+	const size_t width = narrowed ? sizeof(half_t) : sizeof(float);
+	std::vector<half_t> tmp(narrowed ? rows*len : 0);
+	if (narrowed && set) for (size_t i = 0; i < tmp.size(); ++i) tmp[i] = half_t(root ? std::sqrt(std::max(host[i], 0.0f)) : host[i]);
+	void *packed = narrowed ? static_cast<void *>(tmp.data()) : host;
+	if (rows == 1) SMST_HIP(hipMemcpy(set ? device : packed, set ? packed : device, len*width, set ? hipMemcpyHostToDevice : hipMemcpyDeviceToHost));
+	else if (set) SMST_HIP(hipMemcpy2D(device, devPitch*width, packed, len*width, len*width, rows, hipMemcpyHostToDevice));
+	else SMST_HIP(hipMemcpy2D(packed, len*width, device, devPitch*width, len*width, rows, hipMemcpyDeviceToHost));
+	if (narrowed && !set) for (size_t i = 0; i < tmp.size(); ++i) { const float v = float(tmp[i]); host[i] = root ? v*v : v; }
+}
+// [C] rows of B+I sums, carryPitch apart on the device, and one of products
+void Batch::debugSetCarry(int stream, const float *sums, const float *products) { debugCarry(true, stream, const_cast<float *>(sums), const_cast<float *>(products)); }
+void Batch::debugGetCarry(int stream, float *sums, float *products) { debugCarry(false, stream, sums, products); }
+void Batch::debugCarry(bool set, int stream, float *sums, float *products) {
+	if (stream < 0 || stream >= S) throw Error("debug carry: bad stream");
 	SMST_HIP(hipSetDevice(dev));
 	SMST_HIP(hipStreamSynchronize(st));
 	settleCarry();
 	SMST_HIP(hipStreamSynchronize(st));
-	// [C] rows of B+I values, carryPitch apart on the device
-	const size_t n = (size_t)C*d.carryLen, off = (size_t)stream*C*d.carryPitch, CL = d.carryLen, CP = d.carryPitch;
-	if (halfState) {
-		std::vector<half_t> tmp(n);
-		for (size_t i = 0; i < n; ++i) tmp[i] = half_t(sums[i]);
-		SMST_HIP(hipMemcpy2D(reinterpret_cast<half_t *>(d.carrySum[d.carryCur]) + off, CP*sizeof(half_t), tmp.data(), CL*sizeof(half_t), CL*sizeof(half_t), C, hipMemcpyHostToDevice));
-	} else {
-		SMST_HIP(hipMemcpy2D(d.carrySum[d.carryCur] + off, CP*sizeof(float), sums, CL*sizeof(float), CL*sizeof(float), C, hipMemcpyHostToDevice));
-	}
-	SMST_HIP(hipMemcpy(d.carryWp[d.carryCur] + (size_t)stream*CP, products, CL*sizeof(float), hipMemcpyHostToDevice));
+	const auto list = carriedArrays();
+	const CarriedArray &sum = list[kCarrySum], &wp = list[kCarryWp];
+	debugCopy(set, sum.current() + (size_t)stream*sum.rowBytes, sums, C, d.carryLen, d.carryPitch, sum.narrowed, false);
+	debugCopy(set, wp.current() + (size_t)stream*wp.rowBytes, products, 1, d.carryLen, d.carryPitch, false, false);
 }
 bool Batch::debugGetMap(int stream, float *dst) {
 	if (stream < 0 || stream >= S) throw Error("debugGetMap: bad stream");
@@ -2037,20 +2005,4 @@ bool Batch::debugGetFormants(int stream, float *ratio, float *envelope, float *f
 	SMST_HIP(hipMemcpy(freqEstimate, slots[lh.slot].freqEst + row, sizeof(float), hipMemcpyDeviceToHost));
 	return true;
 }
-void Batch::debugGetCarry(int stream, float *sums, float *products) {
-	SMST_HIP(hipSetDevice(dev));
-	SMST_HIP(hipStreamSynchronize(st));
-	settleCarry();
-	SMST_HIP(hipStreamSynchronize(st));
-	const size_t n = (size_t)C*d.carryLen, off = (size_t)stream*C*d.carryPitch, CL = d.carryLen, CP = d.carryPitch;
-	if (halfState) {
-		std::vector<half_t> tmp(n);
-		SMST_HIP(hipMemcpy2D(tmp.data(), CL*sizeof(half_t), reinterpret_cast<const half_t *>(d.carrySum[d.carryCur]) + off, CP*sizeof(half_t), CL*sizeof(half_t), C, hipMemcpyDeviceToHost));
-		for (size_t i = 0; i < n; ++i) sums[i] = float(tmp[i]);
-	} else {
-		SMST_HIP(hipMemcpy2D(sums, CL*sizeof(float), d.carrySum[d.carryCur] + off, CP*sizeof(float), CL*sizeof(float), C, hipMemcpyDeviceToHost));
-	}
-	SMST_HIP(hipMemcpy(products, d.carryWp[d.carryCur] + (size_t)stream*CP, CL*sizeof(float), hipMemcpyDeviceToHost));
-}
-
 } // namespace smst

@@ -2,6 +2,7 @@
 // (signalsmith-stretch.h:280-319) per stream, and drives the gfx950 kernels tile by tile.
 #pragma once
 #include <algorithm>
+#include <array>
 #include <cstddef>
 #include <cstdint>
 #include <string>
@@ -127,19 +128,18 @@ public:
 	int subBatchStreams() const { return subS; }
 	int lastBlockSteps(int stream) const { return (stream >= 0 && stream < S) ? lastSteps[stream] : 0; } // blockProcess.steps of the stream's newest block (:284-318)
 	int lastCallBlocks(int stream) const { return (stream >= 0 && stream < S) ? lastStarts[stream] : 0; } // blocks that began in the stream's most recent process() (:281)
-	// the object is copyable in the reference (a plain struct, signalsmith-stretch.h:34-35): same geometry required; every piece of
-	// carried state, the parameters and the scheduler state of `other` replace this batch's
+	// the object is copyable in the reference (a plain struct, signalsmith-stretch.h:34-35): same geometry, stream count and device required;
+	// the whole carried state of every stream of `other` replaces this batch's (moveStreamsFrom, stream s to stream s)
 	void copyStateFrom(Batch &other);
 	// What the reference's configure() (:71-94) leaves ALONE when an instance is configured again: the random engine (seeded in the
 	// constructor only, :38-39), prevInputOffset, didSeek / seekTimeFactor, the silence counter and the pitch-estimate averages
 	// (all reset by reset(), :49-60, not by configure).  `other` is the stream's previous batch (same stream count).
 	void inheritAcrossConfigure(Batch &other);
 	// One stream's whole carried state from a batch of the SAME geometry and device but any stream count (a pool's group takes a member
-	// in, lets one go, regrows): everything copyStateFrom carries, for the rows of the listed streams -- Band.input / .prevInput / .output,
-	// Prediction.energy, the input history, the overlap-add carry (the source's CURRENT half, into both halves here: which half is
-	// current belongs to a batch, not to a stream), the pitch-estimate averages, the spectra of a split-computation block in flight, the
-	// scheduler state with the random engine, the parameters and the stream's own frequency-map tables.  The device part is ONE launch
-	// (kMoveStreams) however many streams move.  Both batches are synchronised; the source rows are left as they are.
+	// in, lets one go, regrows), for the rows of the listed streams: every device array of carriedArrays() (of a double-buffered one the
+	// source's CURRENT half, into both halves here: which half is current belongs to a batch, not to a stream), the host row
+	// (takeHostRow) and the stream's own frequency-map tables.  The device part is ONE launch (kMoveStreams) however many streams move.
+	// Both batches are synchronised; the source rows are left as they are.
 	void moveStreamFrom(Batch &src, int srcStream, int dstStream) { moveStreamsFrom(src, &srcStream, &dstStream, 1); }
 	void moveStreamsFrom(Batch &src, const int *srcStreams, const int *dstStreams, int n);
 	// reset() (:49-60) of ONE stream: its neighbours are not touched
@@ -291,6 +291,43 @@ private:
 
 	template <typename T> T *devAlloc(size_t count);
 	void devFree(void *p);
+	// A stream's CARRIED state, the device half: every array that lets a stream continue from one call to the next, [S] rows each, named
+	// ONCE in carriedArrays().  Allocation, moveStreamsFrom (so copyStateFrom) and the debug hooks read that list: add an array there.
+	struct CarriedArray {
+		void **ptr[2];          // where the array's pointer lives in `d` / the batch; ptr[1] set: double-buffered, two arrays
+		const int *cur;         // ... and which half is current (d.histCur / d.carryCur)
+		size_t rowBytes;        // one stream's row; the fp16 narrowing (halfState) is folded in here and nowhere else
+		bool narrowed;          // ... for this array: its values are stored as half_t
+		bool splitOnly;         // exists only with split computation
+		size_t slack;           // allocation: bytes beyond the S rows
+		bool zeroed;            // allocation: cleared (the others are written by reset() before they are read)
+		int halves() const { return ptr[1] ? 2 : 1; }
+		char *current() const { return static_cast<char *>(*ptr[cur ? *cur : 0]); }
+	};
+	// (in the order construct() allocates them; the debug selectors 0..3 are the first four; [kHistBase, kStFreq) are the double-buffered
+	// ones, each of which takes two of kMoveStreams' segments; from kPendIn: split computation only)
+	enum { kStInput, kStPrev, kStOut, kStEnergy, kHist, kHistBase, kCarrySum, kCarryWp, kCarryBase, kStFreq, kPendIn, kPendPrev, kCarriedArrays };
+	static_assert(kCarriedArrays + (kStFreq - kHistBase) <= kMoveSegs, "moveStreamsFrom: too many state arrays for one kMoveStreams launch");
+	std::array<CarriedArray, kCarriedArrays> carriedArrays();
+	void allocateCarried(int first, int last);
+	// ... and the host half: sched, params, pend, lastSteps, lastStarts, histBase, carryBase, lastHop
+	void clearHostRow(int s);                             // reset() of one stream: the random engine stays (seedAfterDroppedBlock)
+	void takeHostRow(const Batch &o, int from, int to);   // moveStreamsFrom of one stream
+	void growMapTable(int pitch); // the frequency-map table to a longer row pitch: every row keeps its knots
+	void uploadMapTable();
+	// debug hooks: `rows` rows of `len` stored values, devPitch values apart on the device, to (set == false) or from packed floats on the host
+	void debugCopy(bool set, void *device, float *host, size_t rows, size_t len, size_t devPitch, bool narrowed, bool root);
+	void debugCarry(bool set, int stream, float *sums, float *products);
+	struct StatePlane { char *row; size_t values; bool narrowed, root; };
+	StatePlane statePlane(int stream, int which); // selector -> the stream's row, its length, stored in fp16?, stored as the square root?
+	// construct() in its order
+	void createStreamsAndEvents();
+	void readSwitches(const FftPlan &plan);
+	void uploadConstantTables();
+	void allocateCarriedState();
+	void allocateCallTables();
+	void initHostRows(long seed);
+	void allocateSplitTables();
 	void construct(const FftPlan &plan, long seed);
 	void uploadParams();
 	void allocateWorkspace();
