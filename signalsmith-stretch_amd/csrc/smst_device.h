@@ -26,6 +26,7 @@ struct DevBatch {
 	int fftLean;                  // SMST_FFT_TABLES=lean: register-blocked FFT kernels with the smaller tables (opt-in experiment, see smst_engine.cpp)
 	int noFastFft;                // SMST_NO_FAST_FFT: the generic radix-4/2/3/5 ladder even where a register-blocked FFT exists (cross-check)
 	int fftTeams;                 // analysis / synthesis by persistent workgroups of three free-running teams, tables in LDS (default; SMST_FFT_TEAMS=0: one frame per workgroup; =2: teams even for tiles with few frames per team -- tests)
+	int vocTwist;                 // tiles that qualify keep the previous-hop twist, formed by the analysis pass, in Xprev (default 1; SMST_VOC_TWIST=0: Band.prevInput, the twist per record -- the cross-check)
 	int analysePairs;             // the analysis teams take two frames per pass (kAnalyseTeamPairs; default 1; SMST_ANALYSE_PAIRS=0: kAnalyseTeams, one frame per pass -- the cross-check)
 	int teamsGrid;                // their grid: one workgroup per CU, a multiple of 8
 	int synthEmit;                // synthesis + overlap-add + emission in one kernel (kSynthEmitTeams) where it applies (default 1; SMST_SYNTH_EMIT=0: kSynthTeams + kEmit; =2: also for small tiles -- tests)
@@ -161,18 +162,22 @@ __host__ __device__ inline bool analysisWindowInCall(int B, int M, int I, int in
 // Which kernel variant a launcher chose, counted per process (test hook: smst_debug_launch_count).  "Bit-identical to the other
 // form" tests assert through these that BOTH forms really ran.
 enum LaunchKind {
-	LK_VOC_ALIGNED, LK_VOC_STAGED, LK_VOC_GATHER, LK_VOC_N, LK_VOC_ONE, LK_VOC_ACROSS, LK_VOC_CONT, LK_CHAIN_UNFUSED,
-	LK_ANALYSE_TEAMS, LK_ANALYSE_PAIRS, LK_ANALYSE_FAST, LK_ANALYSE_GENERIC, LK_SYNTH_TEAMS, LK_SYNTH_FAST, LK_SYNTH_GENERIC, LK_SYNTH_EMIT, LK_EMIT_CARRIED, LK_FEED_ONE_PASS, LK_PCM_IN, LK_PCM_OUT, LK_CLIP_IN, LK_CLIP_OUT, LK_PCM_OUT_DITHERED, LK_CLIP_OUT_DITHERED, LK_PCM_OUT_LEVELLED, LK_CLIP_OUT_LEVELLED, LK_CLIP_PEAK, LK_COUNT
+	LK_VOC_ALIGNED, LK_VOC_TWISTED, LK_VOC_STAGED, LK_VOC_GATHER, LK_VOC_N, LK_VOC_ONE, LK_VOC_ACROSS, LK_VOC_CONT, LK_CHAIN_UNFUSED,
+	LK_ANALYSE_TEAMS, LK_ANALYSE_PAIRS, LK_ANALYSE_TWIST, LK_TWIST_ROWS, LK_ANALYSE_FAST, LK_ANALYSE_GENERIC, LK_SYNTH_TEAMS, LK_SYNTH_FAST, LK_SYNTH_GENERIC, LK_SYNTH_EMIT, LK_EMIT_CARRIED, LK_FEED_ONE_PASS, LK_PCM_IN, LK_PCM_OUT, LK_CLIP_IN, LK_CLIP_OUT, LK_PCM_OUT_DITHERED, LK_CLIP_OUT_DITHERED, LK_PCM_OUT_LEVELLED, LK_CLIP_OUT_LEVELLED, LK_CLIP_PEAK, LK_COUNT
 };
 long long launchCount(const char *name); // -1: unknown name
 
 void launchEnergy(const DevBatch &d, const IoArgs &io, int sBase, int nStreams, int maxSamples, float *energyOut, hipStream_t st);
-void launchAnalyse(const DevBatch &d, const IoArgs &io, int sBase, int nStreams, int hopBase, int tileHops, bool anyInCall, bool anyLate, hipStream_t st);
+// twisted: the tile's Xprev rows take the finished previous-hop twists instead of Band.prevInput (analyseTwistApplies; lateHops: the tile's first hops,
+// those with a window that reaches into the history -- kTwistRows turns their rows)
+void launchAnalyse(const DevBatch &d, const IoArgs &io, int sBase, int nStreams, int hopBase, int tileHops, bool anyInCall, bool anyLate, hipStream_t st, bool twisted = false, int lateHops = 0);
+bool analyseTwistApplies(const DevBatch &d, int nStreams, int tileHops); // the pair teams take this tile (what a twisted tile's analysis is built on)
+bool vocoderAlignedApplies(const DevBatch &d);                           // a plain, bounded tile takes kVocoder ALIGNED
 bool launchFeed(const DevBatch &d, int sBase, int nStreams, int hopBase, int tileHops, bool anyFormants, bool anyEstimatedBase, hipStream_t st); // true: pass A done too
 void launchPredict(const DevBatch &d, int sBase, int nStreams, int hopBase, int tileHops, bool plain, bool passADone, hipStream_t st);
 void launchChain(const DevBatch &d, int sBase, int nStreams, int hopBase, hipStream_t st);
 void launchPredictFused(const DevBatch &d, int sBase, int nStreams, int hopBase, int tileHops, bool plain, bool passADone, hipStream_t st);
-void launchVocoder(const DevBatch &d, int sBase, int nStreams, int hopBase, bool plain, bool bounded, hipStream_t st); // bounded: no random time factors in the tile
+void launchVocoder(const DevBatch &d, int sBase, int nStreams, int hopBase, bool plain, bool bounded, bool twisted, hipStream_t st); // bounded: no random time factors in the tile; twisted: see launchAnalyse
 bool fusedSupported(const DevBatch &d);
 bool continuousSupported(const DevBatch &d); // the geometries of the line-aligned producers (mono / stereo, L <= 4, M a multiple of 16, fp32 state)
 int continuousPeriod(const DevBatch &d);     // blocks per tile of the continuous wavefront

@@ -208,6 +208,7 @@ void Batch::readSwitches(const FftPlan &plan) { // ... and the geometry, into `d
 	d.feedSerial = sw.feedSerial;
 	d.fftTeams = sw.fftTeams;
 	d.analysePairs = sw.analysePairs;
+	d.vocTwist = sw.vocTwist;
 	d.synthEmit = sw.synthEmit;
 	{
 		int cus = 0;
@@ -1096,6 +1097,11 @@ void Batch::runTilesRange(const TileRun &run, int tile0, int tile1, int carryFir
 			const int slot = q & 1;
 			const bool plain = th.plain();
 			const bool fused = fusedSupported(d) && !noFuse; // mono/stereo: records stay in LDS (kVocoder)
+			// A TWISTED tile: the rows of Xprev hold the finished previous-hop twists, formed once per bin by the analysis
+			// pass, instead of Band.prevInput.  Where kVocoder ALIGNED takes the tile (launchVocoder's conditions), every hop analyses both of
+			// its windows in this run and the pair teams apply; every other tile keeps Band.prevInput in Xprev.  SMST_VOC_TWIST=0: no tile.
+			const bool twisted = d.vocTwist && !continuous && !run.pendingRun && fused && !(tileHops == 1 && singleHop) && th.twistCapable() &&
+			                     vocoderAlignedApplies(d) && analyseTwistApplies(d, ns, tileHops);
 			const DevBatch dd = tileView(slots[slot], (carryFirst + t) & 1, run.dTileInfo + ((size_t)(sub*nTiles + t)*2)*subS);
 			if (!ts.serial && q - tile0 >= 2) { // this workspace was last used by tile q-2
 				SMST_HIP(hipStreamWaitEvent(ts.sF, evChain[slot], 0));
@@ -1104,7 +1110,7 @@ void Batch::runTilesRange(const TileRun &run, int tile0, int tile1, int carryFir
 			if (!ts.serial && fused && !plain && q - tile0 >= 1) SMST_HIP(hipStreamWaitEvent(ts.sF, evChain[slot ^ 1], 0)); // pass A reads the carried state
 			if (th.anyHop) {
 				if (th.preAnalysed) timed(timings.otherMs, [&] { launchPendingToTile(dd, sBase, ns, dPendIn, dPendPrev, ts.sF); }); // blocks that began in an earlier call: their spectra are waiting
-				if (th.newSpectrum) timed(timings.analyseMs, [&] { launchAnalyse(dd, io, sBase, ns, hopBase, tileHops, th.windowInCall, th.windowInHistory, ts.sF); if (profiling) ++timings.analyseLaunches; });
+				if (th.newSpectrum) timed(timings.analyseMs, [&] { launchAnalyse(dd, io, sBase, ns, hopBase, tileHops, th.windowInCall, th.windowInHistory, ts.sF, twisted, th.lateHops); if (profiling) ++timings.analyseLaunches; });
 				bool passADone = false;
 				if (!plain) timed(timings.feedMs, [&] { passADone = launchFeed(dd, sBase, ns, hopBase, tileHops, th.formants, th.estimatesBase, ts.sF); });
 				timed(timings.predictMs, [&] {
@@ -1131,7 +1137,7 @@ void Batch::runTilesRange(const TileRun &run, int tile0, int tile1, int carryFir
 					// kVocoder do not go through it, so such a tile takes the gathering form -- `bounded` false)
 					if (fused && tileHops == 1 && singleHop && !noAcross && acrossSupported(dd) && !th.startBin) launchVocoderAcross(dd, sBase, ns, hopBase, plain, ts.sC);
 					else if (fused && tileHops == 1 && singleHop) launchVocoderOne(dd, sBase, ns, hopBase, plain, ts.sC);
-					else if (fused) launchVocoder(dd, sBase, ns, hopBase, plain, !th.randomTimeFactor && !th.startBin, ts.sC);
+					else if (fused) launchVocoder(dd, sBase, ns, hopBase, plain, !th.randomTimeFactor && !th.startBin, twisted, ts.sC);
 					else launchChain(dd, sBase, ns, hopBase, ts.sC);
 				});
 				// synthesis needs the recurrence's rows only: the hand-over of the tile's last rows to the carried state (two copies at HBM rate --
@@ -1456,8 +1462,13 @@ void Batch::summariseStreamTiles(const CallPlan &c, int s) {
 			if ((f & HOP_NEW_SPECTRUM) && !(f & HOP_PREANALYSED)) {
 				lastNewLocal = h - h0; th.newSpectrum = true;
 				// analysis frames whose window lies in this call's input (taken by kAnalyseTeams) / reaches into the history
-				for (int which = 0; which < ((f & HOP_REANALYSE_PREV) ? 2 : 1); ++which) (analysisWindowInCall(d.B, d.M, d.I, list[h].inputOffset, which, nIn) ? th.windowInCall : th.windowInHistory) = true;
+				for (int which = 0; which < ((f & HOP_REANALYSE_PREV) ? 2 : 1); ++which) {
+					const bool inCall = analysisWindowInCall(d.B, d.M, d.I, list[h].inputOffset, which, nIn);
+					(inCall ? th.windowInCall : th.windowInHistory) = true;
+					if (!inCall) th.lateHops = std::max(th.lateHops, h - h0 + 1);
+				}
 			}
+			if (!(f & HOP_REANALYSE_PREV) || list[h].prevSrc != SRC_REANALYSED) th.plainPrev = true;
 			th.anyHop = true;
 			if (!(f & HOP_NEW_SPECTRUM)) th.reusedSpectrum = true; // (a hop that re-uses the spectrum before it: the continuous wavefront asks for a new one per hop)
 			if (f & HOP_MAPPED) th.mapped = true;

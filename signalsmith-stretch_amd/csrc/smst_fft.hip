@@ -608,13 +608,19 @@ __global__ __launch_bounds__(256*TEAMS) void kAnalyseTeams(DevBatch d, IoArgs io
 // that frame alone, a pass with none is skipped.  inSamples: io.inSamples as a pointer the compiler may read through the scalar cache, like
 // hopTable -- a pass begins with three scalar loads issued together and then all of its sample loads.
 // Same table values, same operations in the same order on each frame: bit-identical to kAnalyseTeams and kAnalyseFast.
-template <int R3, bool EXACT>
+// TWIST (a twisted tile, DESIGN.md section 4: every hop analyses both of its windows, launchAnalyse): a pass is the TWO WINDOWS of one (hop, channel)
+// -- frame 0 the current one, frame 1 the one an interval earlier -- so in the store step a thread holds the same bins of both, and what goes
+// to the Xprev row is not the earlier window's spectrum but the previous-hop twist of the bin, prevHopTwist(cur, prev, rot), formed from the
+// two values as they land in the rows (after the conjugation of the upper half).  The thread's bins never change: their twelve (R3)
+// rotation factors live in registers for the whole launch.  A pass with one window in the call's input stores that frame raw, as above;
+// kAnalyseFast takes the other one and kTwistRows turns the row afterwards.
+template <int R3, bool EXACT, bool TWIST>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) void kAnalyseTeamPairs(DevBatch d, IoArgs io, const HopDesc *__restrict__ hopTable, const int *__restrict__ inSamples, int sBase, int hopBase, int tileHops, int nStreams) {
 	extern __shared__ __attribute__((aligned(16))) unsigned char smemRaw[];
 	constexpr int TEAMS = 2, MA = 16*R3, H = 256*R3, N = 2*H;
 	const int B = EXACT ? 480*R3 : d.B, halfB = B/2; // EXACT: the geometry this kernel is launched for
 	const int jobs = tileHops*2*d.C;                 // of one stream
-	const int passes = (jobs + 1)/2, total = passes*nStreams;
+	const int passes = (jobs + 1)/2, total = passes*nStreams; // (TWIST: exactly tileHops*C passes of two frames)
 	static_assert((H + 8*R3)*sizeof(float4) + TEAMS*2*(H + H/16)*sizeof(float2) + 64 <= 160*1024, "the window, the second-stage twiddles, four transform buffers and the barrier words fit a CU's LDS (155,200 bytes at R3 = 12)");
 	TeamWorkgroup<R3, TEAMS, 2> wg(smemRaw, d, d.win4); // table: (winA, winB) of all elements
 	const TeamSync sync = wg.sync();
@@ -622,12 +628,17 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 	StageTwiddles twA;
 #pragma unroll
 	for (int i = 0; i < 8; ++i) twA.w[i] = d.twA4[i*MA + tA];
+	float2 rotOf[TWIST ? R3 : 1]; // TWIST: the hop rotation of the bins this thread stores (element t + 256*i of the last stage)
+	if constexpr (TWIST) {
+#pragma unroll
+		for (int i = 0; i < R3; ++i) rotOf[i] = d.rot[halfBinIndex(t + 256*i, H, N)];
+	}
 	// Round i deals the passes [i*stride, (i + 1)*stride) to the teams, each team keeping its residue mod 8 (its XCD).  With a fixed place in
 	// every round a team would move on by stride/8 passes of a stream per round -- 64 on 256 CUs, two whole rows of a 64-hop tile, so it would
 	// meet the SAME window of the same or the other channel every time, and at stretch 1.0, where no hop re-analyses its previous window, one
 	// team of every workgroup would find all of its passes unwanted.  The teams' places therefore rotate by `turn` per round (a bijection of
 	// the round's passes onto the teams all the same), chosen so that a team moves on by an odd number of rows.
-	const int stride = gridDim.x*TEAMS, rowPasses = (tileHops + 1)/2;
+	const int stride = gridDim.x*TEAMS, rowPasses = TWIST ? tileHops : (tileHops + 1)/2;
 	const int turn = 8*((((rowPasses - stride/8)%(2*rowPasses)) + 2*rowPasses)%(2*rowPasses));
 	const int place = blockIdx.x + gridDim.x*wg.team;
 	for (int round = 0; round*stride < total; ++round) {
@@ -643,8 +654,15 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 			const int job = 2*pc.x + f;
 			have[f] = job < jobs; // (an odd job count: the last pass has one frame)
 			const int j = have[f] ? job : 2*pc.x;
-			bc[f].y = j/tileHops;
-			bc[f].x = j - bc[f].y*tileHops;
+			if constexpr (TWIST) { // pass pc.x = (hop, channel), the hop fastest; frame f = window f
+				const int c = pc.x/tileHops;
+				have[f] = true;
+				bc[f].y = 2*c + f;
+				bc[f].x = pc.x - c*tileHops;
+			} else {
+				bc[f].y = j/tileHops;
+				bc[f].x = j - bc[f].y*tileHops;
+			}
 			bc[f].s = pc.s;
 			hd[f] = hopTable[(size_t)(sBase + pc.s)*d.hopStride + hopBase + bc[f].x];
 		}
@@ -667,6 +685,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 		auto prep = [](int, int, int = 0) { return 0; };
 		if (on[0] && on[1]) {
 			float4 win[16]; // the window entries of the thread's elements: one read for the two frames
+			[[maybe_unused]] fc landed[TWIST ? R3 : 1]; // TWIST: frame 0's values as they went into the Xcur row (frame 0 is stored first)
 			fftFast<-1, R3, false, 0, 2>(wg.lds, nullptr, wg.twB,
 				[&](int m, int slot) {
 					FrameSet<2> r;
@@ -674,7 +693,16 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 					for (int f = 0; f < 2; ++f) r.f[f] = fpack(analysisSamples(x0[f], x1[f], m, slot));
 					return r;
 				},
-				prep, [&](int j, fc u, int, int, int f) { storeHalfBin(dst[f], j, u, H, N); }, t, sync, NoHook(),
+				prep, [&](int j, fc u, int, int idx, int f) {
+					if constexpr (TWIST) {
+						const fc landedValue = fconjIf(u, 2*j >= H); // what storeHalfBin puts into the row
+						float2 *row = dst[f] + halfBinIndex(j, H, N);
+						if (f == 0) { landed[idx] = landedValue; *reinterpret_cast<fc *>(row) = landedValue; }
+						else *row = prevHopTwist(funpack(landed[idx]), funpack(landedValue), rotOf[idx]);
+					} else {
+						storeHalfBin(dst[f], j, u, H, N);
+					}
+				}, t, sync, NoHook(),
 				[&]() { // all 60 samples are on their way: the table is read under their latency, and nothing below moves above this point
 #pragma unroll
 					for (int slot = 0; slot < 16; ++slot) win[slot] = wg.table[tA + MA*slot];
@@ -691,6 +719,20 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 		}
 		sync(); // the last stage's LDS reads, before the next pass's first-stage writes
 	}
+}
+
+// A twisted tile's rows that the pair teams did not turn (a window of the hop reaches into the carried history: the first hops of a call;
+// kAnalyseFast has written both spectra raw): Xprev := prevHopTwist(Xcur, Xprev, rot) in place, the operation kAnalyseTeamPairs<TWIST> applies in its
+// store step.  Grid (the tile's first `lateHops` hops, channels, streams); teams: the pair kernel ran, and took the rows with both windows in the call.
+__global__ __launch_bounds__(256) void kTwistRows(DevBatch d, IoArgs io, int sBase, int hopBase, int teams) {
+	const int k = blockIdx.x, c = blockIdx.y, s = blockIdx.z;
+	const HopDesc hd = d.hops[(size_t)(sBase + s)*d.hopStride + hopBase + k];
+	if (!hopWantsAnalysis(hd, 1)) return;
+	const int nIn = io.inSamples[sBase + s];
+	if (teams && analysisWindowInCall(d.B, d.M, d.I, hd.inputOffset, 0, nIn) && analysisWindowInCall(d.B, d.M, d.I, hd.inputOffset, 1, nIn)) return;
+	const float2 *cur = d.Xcur + rowOf(d, s, k, c);
+	float2 *prev = d.Xprev + rowOf(d, s, k, c);
+	for (int b = threadIdx.x; b < d.M; b += blockDim.x) prev[b] = prevHopTwist(cur[b], prev[b], d.rot[b]);
 }
 
 template <int R3, bool LEAN>
@@ -1290,7 +1332,10 @@ static int teamsWorkgroups(const DevBatch &d, int jobs) { // three teams each: o
 constexpr int synthEmitQN(int R3) { return R3 == 10 ? 3 : 4; }
 constexpr int synthEmitSlots(int R3) { return R3 == 10 ? 8 : 6; }
 
-void launchAnalyse(const DevBatch &d, const IoArgs &io, int sBase, int nStreams, int hopBase, int tileHops, bool anyInCall, bool anyLate, hipStream_t st) {
+// what a twisted tile's analysis is built on: the pair teams take the tile (the frames they leave -- none in most tiles -- go through kTwistRows)
+bool analyseTwistApplies(const DevBatch &d, int nStreams, int tileHops) { return teamsApply(d, tileHops*d.C*2*nStreams) && analysePairsApply(d); }
+
+void launchAnalyse(const DevBatch &d, const IoArgs &io, int sBase, int nStreams, int hopBase, int tileHops, bool anyInCall, bool anyLate, hipStream_t st, bool twisted, int lateHops) {
 	const dim3 grid(tileHops, d.C*2, nStreams);
 	const int jobs = tileHops*d.C*2*nStreams;
 	const bool teams = anyInCall && teamsApply(d, jobs);
@@ -1299,22 +1344,30 @@ void launchAnalyse(const DevBatch &d, const IoArgs &io, int sBase, int nStreams,
 		const bool pairs = analysePairsApply(d);
 		const int passes = (tileHops*d.C*2 + 1)/2*nStreams;
 		withTeamR3(d.M, [&](auto r3) { withFlag(pad.lo == 0 && pad.hi == 0, [&](auto exact) {
-			if (pairs) hipLaunchKernelGGL((kAnalyseTeamPairs<r3.value, exact.value>), dim3(pairWorkgroups(d, passes)), dim3(512), teamLdsBytes(d.M, 2, 2), st, d, io, d.hops, io.inSamples, sBase, hopBase, tileHops, nStreams);
+			if (pairs && twisted) hipLaunchKernelGGL((kAnalyseTeamPairs<r3.value, exact.value, true>), dim3(pairWorkgroups(d, passes)), dim3(512), teamLdsBytes(d.M, 2, 2), st, d, io, d.hops, io.inSamples, sBase, hopBase, tileHops, nStreams);
+			else if (pairs) hipLaunchKernelGGL((kAnalyseTeamPairs<r3.value, exact.value, false>), dim3(pairWorkgroups(d, passes)), dim3(512), teamLdsBytes(d.M, 2, 2), st, d, io, d.hops, io.inSamples, sBase, hopBase, tileHops, nStreams);
 			else hipLaunchKernelGGL((kAnalyseTeams<r3.value, 3, exact.value>), dim3(teamsWorkgroups(d, jobs)), dim3(768), teamLdsBytes(d.M, 3), st, d, io, d.hops, sBase, hopBase, tileHops, nStreams);
 		}); });
 		countLaunch(LK_ANALYSE_TEAMS); // (either form)
 		if (pairs) countLaunch(LK_ANALYSE_PAIRS);
+		if (pairs && twisted) countLaunch(LK_ANALYSE_TWIST);
 		if (!anyLate) return;
 	}
+	auto twistRows = [&] { // behind the kernel that wrote the late frames, on the same stream
+		if (!twisted || lateHops <= 0) return;
+		hipLaunchKernelGGL(kTwistRows, dim3(std::min(lateHops, tileHops), d.C, nStreams), dim3(256), 0, st, d, io, sBase, hopBase, teams ? 1 : 0);
+		countLaunch(LK_TWIST_ROWS);
+	};
 	const int lateOnly = teams ? 1 : 0; // the frames whose windows reach into the carried history
 	countLaunch(fastApplies(d) ? LK_ANALYSE_FAST : LK_ANALYSE_GENERIC);
 	// every preset: presetCheaper at 44.1 / 48 kHz, presetDefault at 44.1 / 48 kHz, presetCheaper at 88.2 / 96 kHz, presetDefault at 88.2 / 96 kHz
 	if (!d.noFastFft && withFastR3(d.M, [&](auto r3) { withFlag(d.fftLean != 0, [&](auto lean) {
 			hipLaunchKernelGGL((kAnalyseFast<r3.value, lean.value>), grid, dim3(fastBlockThreads(r3.value)), fastLdsBytes(d.M), st, d, io, sBase, hopBase, lateOnly);
-		}); })) return;
+		}); })) { twistRows(); return; }
 	size_t lds = 2*(size_t)d.M*sizeof(float2);
 	if (fftNeedsScratch(d.M)) hipLaunchKernelGGL(kAnalyse<true>, grid, dim3(256), lds/2, st, d, io, sBase, hopBase);
 	else hipLaunchKernelGGL(kAnalyse<false>, grid, dim3(256), lds, st, d, io, sBase, hopBase);
+	twistRows();
 }
 void launchSynth(const DevBatch &d, int sBase, int nStreams, int hopBase, int tileHops, hipStream_t st) {
 	const dim3 grid(tileHops, d.C, nStreams);

@@ -51,6 +51,14 @@ namespace smst {
 // (carried Prediction.energy in kCarryFeed vs the producers' on-the-fly value) that must agree bit for bit
 __device__ __forceinline__ float cnorm(float2 a) { return __fadd_rn(__fmul_rn(a.x, a.x), __fmul_rn(a.y, a.y)); } // :27-31
 __device__ __forceinline__ float2 cscale(float2 a, float s) { return make_float2(a.x*s, a.y*s); }
+// The previous-hop twist of one bin (:744-800): rot * (in * conj(prev * rot)) with in = Band.input, prev = Band.prevInput, rot the hop rotation
+// of that bin (or (1, 0) where the hop has no new spectrum).  It depends on (hop, channel, bin) alone: a plain record forms it for its two
+// previous-hop bins (plainRecord), a TWISTED tile's analysis pass forms it once per bin and leaves it in the Xprev row (kAnalyseTeamPairs
+// TWIST, kTwistRows) -- the same three products in the same order, so the same bits
+__device__ __forceinline__ float2 prevHopTwist(float2 in, float2 prev, float2 rot) {
+	const float2 Q = cmul(prev, rot);
+	return cmul(rot, cmulc(in, Q));
+}
 
 // ------------------------------------------------------------------------------------------------------
 // Carried per-stream state in fp32 or -- opt-in per batch (BASELINE config 5 "fp16 internal") -- in fp16: Band.output as

@@ -233,7 +233,9 @@ __device__ __forceinline__ void vocoderProduceStaged(const DevBatch &d, int s, i
 // needs.  The 8-bin lag costs 63*3 more steps per tile (+5.6 %) and puts rows r and r+1 on complementary halves of the LDS
 // banks with no row padding.  The records are plainRecord's, as the staged producers' (AlignView says where the
 // operands lie).
-template <int CH, int L, int NB, bool FIRST>
+// TWISTED (a twisted tile: the rows of Xprev hold the finished previous-hop twist): the lines parked as prev() ARE the
+// records' TW -- no rotation factors are requested (two of the three small loads) and the record forms no Q and no products for them.
+template <int CH, int L, int NB, bool FIRST, bool TWISTED>
 __device__ __forceinline__ void vocoderProduceAligned(const DevBatch &d, int s, int sg, int nh, int it, int k, int totalBlocks,
                                                       float4 *recs, volatile int *sync, const HopDesc *hopsLds, float2 *sbuf, const CarriedOutput &stOut) {
 	// FIRST: the wave that owns rows 0..7 (it == 0): the hop above its first row is the carried state, its row 0 folds the carried
@@ -291,13 +293,15 @@ __device__ __forceinline__ void vocoderProduceAligned(const DevBatch &d, int s, 
 			asyncLoad16(v[i], lsrc[par][i] + 16*jc);
 		}
 	};
-	auto issueSmall = [&](int n) { // 3 requests (FIRST: 3 + 2*CH), every address clamped into its row: n may run past the tile's last block
+	auto issueSmall = [&](int n) { // 3 requests (TWISTED: 1; FIRST: + 2*CH), every address clamped into its row: n may run past the tile's last block
 		const int x0 = BS*(n - 8*it) + 2*xpiece, xcl = min(max(x0, 0), M - 2);
 		if (FIRST) asyncLoad8(xe, xenergy + xcl);
 		else asyncLoad16(xv, xsrc + xcl);
-		const int b = BS*(n - row) + st;
-		asyncLoad8(rotNext1, d.rot + min(max(b + 1, 0), M - 1));
-		asyncLoad8(rotNextL, d.rot + min(max(b + L, 0), M - 1));
+		[[maybe_unused]] const int b = BS*(n - row) + st;
+		if constexpr (!TWISTED) {
+			asyncLoad8(rotNext1, d.rot + min(max(b + 1, 0), M - 1));
+			asyncLoad8(rotNextL, d.rot + min(max(b + L, 0), M - 1));
+		}
 		if (FIRST) { // hop 0's previous-hop taps are the carried Band.output (FOLD0): lanes 0..7 = row 0 (no skew), steps 0..7
 			const int b0 = min(max(BS*n + st, 0), M - 1);
 #pragma unroll
@@ -319,8 +323,7 @@ __device__ __forceinline__ void vocoderProduceAligned(const DevBatch &d, int s, 
 #pragma unroll
 		for (int i = 0; i < G::LOADS; ++i) asyncArrived(v[i]);
 		if (FIRST) asyncArrived(xe); else asyncArrived(xv);
-		asyncArrived(rotNext1);
-		asyncArrived(rotNextL);
+		if constexpr (!TWISTED) { asyncArrived(rotNext1); asyncArrived(rotNextL); }
 		if (FIRST) {
 #pragma unroll
 			for (int c = 0; c < CH; ++c) { asyncArrived(carNext1[c]); asyncArrived(carNextL[c]); }
@@ -350,8 +353,7 @@ __device__ __forceinline__ void vocoderProduceAligned(const DevBatch &d, int s, 
 			else piece = asyncValue(xv);
 			*reinterpret_cast<float4 *>(xbuf + xc*16 + 2*xpiece) = (x0 >= 0 && x0 + 1 < M) ? piece : make_float4(0.f, 0.f, 0.f, 0.f);
 		}
-		rot1 = asyncValue(rotNext1);
-		rotL = asyncValue(rotNextL);
+		if constexpr (!TWISTED) { rot1 = asyncValue(rotNext1); rotL = asyncValue(rotNextL); }
 	};
 	const HopDesc hd = hopsLds[row < nh ? row : 0];
 	const bool rotate = hd.flags & HOP_NEW_SPECTRUM;
@@ -405,7 +407,7 @@ __device__ __forceinline__ void vocoderProduceAligned(const DevBatch &d, int s, 
 		for (int j = 0; j < NCH*4; ++j) f[j] = 0.0f;
 		if (row < nh && b >= 0 && b < M) {
 			const AlignView<CH, L> view(sbuf, xbuf, r, st, (n - row) & 1, !(row > 0), rot1, rotL); // above the tile's first hop: the carried energies
-			plainRecord<CH, L, FIRST>(view, b, M, tf, rotate, true, r == 0, car1, carL, f);
+			plainRecord<CH, L, FIRST, TWISTED>(view, b, M, tf, rotate, true, r == 0, car1, carL, f);
 		}
 		storeRecord<BS>(recs, slot, st, row, f);
 		asm volatile("" ::: "memory");
@@ -427,11 +429,13 @@ __device__ __forceinline__ void vocoderProduceAligned(const DevBatch &d, int s, 
 // values); at 4096 streams that is four chain waves per SIMD and 1.57 ms per hop quantum.  Same records (computeRecord with FOLD0), same
 // step (wavefrontBlock).
 // ALIGNED (with STAGED): the line-aligned producers and a wavefront lag of 8 bins (vocoderProduceAligned).
-template <int CH, bool PLAIN, int L, bool STAGED, bool ROTL = false, bool ACROSS = false, bool ALIGNED = false>
+// TWISTED (with ALIGNED): the tile's Xprev rows hold the finished previous-hop twists (the host decides it per tile: Batch::runTilesRange).
+template <int CH, bool PLAIN, int L, bool STAGED, bool ROTL = false, bool ACROSS = false, bool ALIGNED = false, bool TWISTED = false>
 __global__ __launch_bounds__(64*kVocWaves) __attribute__((amdgpu_waves_per_eu(4, 4))) void kVocoder(DevBatch d, int sBase, int hopBase, int acrossRows, int acrossStreams) {
 	static_assert(!STAGED || (PLAIN && L <= 5), "staged producers: identity map, bounded windows");
 	static_assert(!ALIGNED || (STAGED && L <= 4), "line-aligned producers: windows within the two lines around a row's bins");
 	static_assert(!ACROSS || !STAGED, "rows that are streams gather their operands");
+	static_assert(!TWISTED || ALIGNED, "only the line-aligned producers take the twist ready-made");
 	static_assert(!ROTL || (!PLAIN && !STAGED), "the LDS copy of the rotation table serves the gathering producers of mapped tiles");
 	constexpr int NF = 9 + 3*CH, NCH = (NF + 3)/4, BS = kVocBlockSteps, NB = STAGED ? kVocBlocksStaged : kVocBlocks;
 	constexpr int NP = STAGED ? kVocStagedProducers : kVocWaves - 2;
@@ -546,8 +550,8 @@ __global__ __launch_bounds__(64*kVocWaves) __attribute__((amdgpu_waves_per_eu(4,
 		if constexpr (ALIGNED) {
 			using G = AlignGeom<CH, L>;
 			float2 *sbuf = outRing + (size_t)OB*BS*CH*kVocOutPitch + (size_t)pIndex*G::PER_PRODUCER;
-			if (pIndex == 0) vocoderProduceAligned<CH, L, NB, true>(d, s, sg, nh, pIndex, k, totalBlocks, recs, sync, hopsLds, sbuf, stOut);
-			else vocoderProduceAligned<CH, L, NB, false>(d, s, sg, nh, pIndex, k, totalBlocks, recs, sync, hopsLds, sbuf, stOut);
+			if (pIndex == 0) vocoderProduceAligned<CH, L, NB, true, TWISTED>(d, s, sg, nh, pIndex, k, totalBlocks, recs, sync, hopsLds, sbuf, stOut);
+			else vocoderProduceAligned<CH, L, NB, false, TWISTED>(d, s, sg, nh, pIndex, k, totalBlocks, recs, sync, hopsLds, sbuf, stOut);
 			return;
 		} else if constexpr (STAGED) {
 			using G = StageGeom<CH, L>;
@@ -653,8 +657,13 @@ __global__ __launch_bounds__(64*kVocWaves) __attribute__((amdgpu_waves_per_eu(4,
 // host-side launchers
 // ------------------------------------------------------------------------------------------------------
 // ... and the fused producer/consumer recurrence
+// Whether a plain, bounded mono / stereo tile takes the line-aligned producers (fp16 state: the staged producers).  The host asks too: only such
+// a tile can be a twisted one (Batch::runTilesRange)
+bool vocoderAlignedApplies(const DevBatch &d) {
+	return d.C <= 2 && d.L >= 2 && d.L <= 4 && !d.noStage && !d.noAlign && d.M%16 == 0 && !d.halfState && (d.L == 4 || d.alignAll);
+}
 template <int CH, int L>
-static void launchVocoderTL(const DevBatch &d, int sBase, int nStreams, int hopBase, bool plain, bool bounded, hipStream_t st) {
+static void launchVocoderTL(const DevBatch &d, int sBase, int nStreams, int hopBase, bool plain, bool bounded, bool twisted, hipStream_t st) {
 	constexpr int NCH = (9 + 3*CH + 3)/4;
 	const size_t fixed = 64 + 128*sizeof(int) + 64*sizeof(HopDesc) + (size_t)kVocOutBlocks*kVocBlockSteps*CH*kVocOutPitch*sizeof(float2);
 	const size_t lds = (size_t)kVocBlocks*kVocBlockSteps*NCH*64*sizeof(float4) + fixed;
@@ -662,12 +671,14 @@ static void launchVocoderTL(const DevBatch &d, int sBase, int nStreams, int hopB
 	// (presetCheaper) the 8-bin lag costs 9 % more wavefront steps than lag 4 and the two forms tie (10.75 / 10.80 ms per step), so that
 	// geometry stays on the staged producers; SMST_ALIGN_ALL=1 takes the aligned form wherever it is valid (L <= 4), for the A/B.
 	if constexpr (L <= 4) {
-		if (plain && bounded && !d.noStage && !d.noAlign && d.M%16 == 0 && !d.halfState && (L == 4 || d.alignAll)) { // (fp16 state: the staged producers below)
+		if (plain && bounded && vocoderAlignedApplies(d)) {
 			using G = AlignGeom<CH, L>;
 			const size_t fixedA = 64 + 128*sizeof(int) + 64*sizeof(HopDesc) + (size_t)kVocOutBlocksAligned*kVocBlockSteps*CH*kVocOutPitch*sizeof(float2);
 			const size_t ldsAligned = (size_t)kVocBlocksStaged*kVocBlockSteps*NCH*64*sizeof(float4) + fixedA + (size_t)kVocStagedProducers*G::PER_PRODUCER*sizeof(float2);
-			hipLaunchKernelGGL((kVocoder<CH, true, L, true, false, false, true>), dim3(nStreams), dim3(64*kVocWaves), ldsAligned, st, d, sBase, hopBase, 0, 0);
-			countLaunch(LK_VOC_ALIGNED);
+			if (twisted) hipLaunchKernelGGL((kVocoder<CH, true, L, true, false, false, true, true>), dim3(nStreams), dim3(64*kVocWaves), ldsAligned, st, d, sBase, hopBase, 0, 0);
+			else hipLaunchKernelGGL((kVocoder<CH, true, L, true, false, false, true>), dim3(nStreams), dim3(64*kVocWaves), ldsAligned, st, d, sBase, hopBase, 0, 0);
+			countLaunch(LK_VOC_ALIGNED); // (either form)
+			if (twisted) countLaunch(LK_VOC_TWISTED);
 			return;
 		}
 	}
@@ -718,23 +729,23 @@ void launchVocoderAcross(const DevBatch &d, int sBase, int nStreams, int hopBase
 	else launchVocoderAcrossT<2>(d, sBase, nStreams, hopBase, plain, st);
 }
 template <int CH>
-static void launchVocoderT(const DevBatch &d, int sBase, int nStreams, int hopBase, bool plain, bool bounded, hipStream_t st) {
+static void launchVocoderT(const DevBatch &d, int sBase, int nStreams, int hopBase, bool plain, bool bounded, bool twisted, hipStream_t st) {
 	switch (d.L) { // longVerticalStep = round(fftSamples/interval): 4 (presetDefault @48k), 5 (@44.1k), 3 (presetCheaper)
-	case 3: launchVocoderTL<CH, 3>(d, sBase, nStreams, hopBase, plain, bounded, st); break;
-	case 4: launchVocoderTL<CH, 4>(d, sBase, nStreams, hopBase, plain, bounded, st); break;
-	case 5: launchVocoderTL<CH, 5>(d, sBase, nStreams, hopBase, plain, bounded, st); break;
-	case 2: launchVocoderTL<CH, 2>(d, sBase, nStreams, hopBase, plain, bounded, st); break;
-	case 6: launchVocoderTL<CH, 6>(d, sBase, nStreams, hopBase, plain, bounded, st); break;
-	default: launchVocoderTL<CH, 7>(d, sBase, nStreams, hopBase, plain, bounded, st); break; // only reached with L == 7 (see fusedSupported)
+	case 3: launchVocoderTL<CH, 3>(d, sBase, nStreams, hopBase, plain, bounded, twisted, st); break;
+	case 4: launchVocoderTL<CH, 4>(d, sBase, nStreams, hopBase, plain, bounded, twisted, st); break;
+	case 5: launchVocoderTL<CH, 5>(d, sBase, nStreams, hopBase, plain, bounded, twisted, st); break;
+	case 2: launchVocoderTL<CH, 2>(d, sBase, nStreams, hopBase, plain, bounded, twisted, st); break;
+	case 6: launchVocoderTL<CH, 6>(d, sBase, nStreams, hopBase, plain, bounded, twisted, st); break;
+	default: launchVocoderTL<CH, 7>(d, sBase, nStreams, hopBase, plain, bounded, twisted, st); break; // only reached with L == 7 (see fusedSupported)
 	}
 }
 bool fusedSupported(const DevBatch &d) {
 	return d.C <= kMaxFusedChannels && d.lag == d.L + 1 && d.L >= 2 && d.L <= (d.C <= 2 ? 7 : 5); // other geometries / more channels: kPredictB + kChain (records through HBM)
 }
-void launchVocoder(const DevBatch &d, int sBase, int nStreams, int hopBase, bool plain, bool bounded, hipStream_t st) {
+void launchVocoder(const DevBatch &d, int sBase, int nStreams, int hopBase, bool plain, bool bounded, bool twisted, hipStream_t st) {
 	switch (d.C) {
-	case 1: launchVocoderT<1>(d, sBase, nStreams, hopBase, plain, bounded, st); return;
-	case 2: launchVocoderT<2>(d, sBase, nStreams, hopBase, plain, bounded, st); return;
+	case 1: launchVocoderT<1>(d, sBase, nStreams, hopBase, plain, bounded, twisted, st); return;
+	case 2: launchVocoderT<2>(d, sBase, nStreams, hopBase, plain, bounded, twisted, st); return;
 	default: launchVocoderMany(d, sBase, nStreams, hopBase, plain, st); return; // 3-8 channels: kVocoderN
 	}
 }

@@ -41,8 +41,10 @@ __device__ __forceinline__ float2 fromLaneBelow(float2 v, float2 lane0) { // lan
 // FOLD (FOLD0, see computeRecord): the record of the tile's first hop carries  Cc := prevOut[b+1]*Cc + prevOut[b+L]*Dc, Dc := 0  with the
 // carried Band.output taps car1 / carL per channel; foldWave: this wave owns that row (uniform: the others skip the arithmetic),
 // foldLane: this lane's record is in it.
+// TWISTED (kVocoder ALIGNED on a twisted tile): prev(c, off) is not Band.prevInput but the finished twist of bin b + off
+// (prevHopTwist, formed by the analysis pass); rot() and `rotate` are then unused.
 // ------------------------------------------------------------------------------------------------------
-template <int CH, int L, bool FOLD, typename View, int NFLOATS>
+template <int CH, int L, bool FOLD, bool TWISTED = false, typename View, int NFLOATS>
 __device__ __forceinline__ void plainRecord(const View &v, int b, int M, float tf, bool rotate, bool foldWave, bool foldLane,
                                             const float2 (&car1)[CH], const float2 (&carL)[CH], float (&f)[NFLOATS]) {
 	auto lerpIN = [&](int c, LerpIndex li) { // li.lo is an absolute bin
@@ -65,10 +67,10 @@ __device__ __forceinline__ void plainRecord(const View &v, int b, int M, float t
 	float2 B = cmulc(Pm, lerpIN(mc, lerpIndex(fb - L*tf)));
 	auto twist = [&](int off, float stepMul) { // the coefficient of the previous hop's output at bin b + off
 		const int bc = min(b + off, M - 1);
-		const float2 rotB = rotate ? v.rot(off) : make_float2(1.f, 0.f);
-		const float2 Q = cmul(v.prev(mc, off), rotB);
 		const float2 Px = v.in(mc, off);
-		const float2 TW = cmul(rotB, cmulc(Px, Q));
+		float2 TW;
+		if constexpr (TWISTED) TW = v.prev(mc, off); // the analysis pass has formed it
+		else TW = prevHopTwist(Px, v.prev(mc, off), rotate ? v.rot(off) : make_float2(1.f, 0.f));
 		const float eNow = cnorm(Px);
 		const float2 up = v.above(mc, off);
 		const float ePrev = v.aboveIsEnergy() ? up.x : cnorm(up); // Prediction.energy of the previous hop

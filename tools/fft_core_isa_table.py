@@ -13,7 +13,7 @@ pass with one wanted frame.
 
 usage: fft_core_isa_table.py [<label>=]<assembly> [[<label>=]<assembly of another build> ...]   -> one table per file on stdout
        fft_core_isa_table.py --check-budgets <assembly>   -> exit status 1 unless the build keeps kAnalyseTeamPairs' budgets (csrc/Makefile runs this):
-       its four instantiations exist, none uses scratch, each is compiled for exactly two waves per SIMD"""
+       its eight instantiations exist, none uses scratch, each is compiled for exactly two waves per SIMD"""
 import re
 import subprocess
 import sys
@@ -124,10 +124,10 @@ def check_budgets(path):
     names = demangle([f[0] for f in funcs])
     pairs = [(names[m], meta) for m, _, meta in funcs if "kAnalyseTeamPairs<" in names[m]]
     bad = ["%s: %s" % (n, meta) for n, meta in pairs if meta.get("ScratchSize") != 0 or meta.get("Occupancy") != 2 or meta.get("TotalNumVgprs", 999) > 256]
-    if len(pairs) != 4 or bad:
-        print("kAnalyseTeamPairs budgets (four instantiations, no scratch, two waves per SIMD, <= 256 registers): %d instantiation(s); %s" % (len(pairs), "; ".join(bad) or "none over budget"))
+    if len(pairs) != 8 or bad:  # R3 = 10 / 12 x EXACT x TWIST (the twisted tiles' pass shape)
+        print("kAnalyseTeamPairs budgets (eight instantiations, no scratch, two waves per SIMD, <= 256 registers): %d instantiation(s); %s" % (len(pairs), "; ".join(bad) or "none over budget"))
         return 1
-    print("kAnalyseTeamPairs budgets: 4 instantiations, no scratch, two waves per SIMD, %s VGPRs" % " / ".join(str(meta["TotalNumVgprs"]) for _, meta in pairs))
+    print("kAnalyseTeamPairs budgets: 8 instantiations, no scratch, two waves per SIMD, %s VGPRs" % " / ".join(str(meta["TotalNumVgprs"]) for _, meta in pairs))
     return 0
 
 
