@@ -88,6 +88,9 @@ struct DevBatch {
 	float2 *fftScratch; // [subS][T][C][Mp]: second FFT buffer of the synthesis frames where two buffers do not fit LDS (fftNeedsScratch); null otherwise
 	const int *nHops;      // [subS] hops of this tile
 	const int *lastNewHop; // [subS] tile-local index of the last hop with a new spectrum, or -1
+	// (behind everything else: the fields above keep the places every other kernel reads them from)
+	int vocInterior;       // the line-aligned producers run the interior form of a block between a row's edges (default 1; SMST_VOC_INTERIOR=0: the general form in every block -- the cross-check)
+	int tileMaxHops;       // host only: the most hops a stream of this tile has (TileSummary::maxHops; the launchers' counters)
 };
 
 // The continuous wavefront of the fused mono / stereo recurrence (kVocoderCont, smst_vocoder_cont.hip): launch `tile` covers the global
@@ -162,7 +165,7 @@ __host__ __device__ inline bool analysisWindowInCall(int B, int M, int I, int in
 // Which kernel variant a launcher chose, counted per process (test hook: smst_debug_launch_count).  "Bit-identical to the other
 // form" tests assert through these that BOTH forms really ran.
 enum LaunchKind {
-	LK_VOC_ALIGNED, LK_VOC_TWISTED, LK_VOC_STAGED, LK_VOC_GATHER, LK_VOC_N, LK_VOC_ONE, LK_VOC_ACROSS, LK_VOC_CONT, LK_CHAIN_UNFUSED,
+	LK_VOC_ALIGNED, LK_VOC_TWISTED, LK_VOC_INTERIOR, LK_VOC_STAGED, LK_VOC_GATHER, LK_VOC_N, LK_VOC_ONE, LK_VOC_ACROSS, LK_VOC_CONT, LK_CHAIN_UNFUSED,
 	LK_ANALYSE_TEAMS, LK_ANALYSE_PAIRS, LK_ANALYSE_TWIST, LK_TWIST_ROWS, LK_ANALYSE_FAST, LK_ANALYSE_GENERIC, LK_SYNTH_TEAMS, LK_SYNTH_FAST, LK_SYNTH_GENERIC, LK_SYNTH_EMIT, LK_EMIT_CARRIED, LK_FEED_ONE_PASS, LK_PCM_IN, LK_PCM_OUT, LK_CLIP_IN, LK_CLIP_OUT, LK_PCM_OUT_DITHERED, LK_CLIP_OUT_DITHERED, LK_PCM_OUT_LEVELLED, LK_CLIP_OUT_LEVELLED, LK_CLIP_PEAK, LK_COUNT
 };
 long long launchCount(const char *name); // -1: unknown name

@@ -199,6 +199,7 @@ void Batch::readSwitches(const FftPlan &plan) { // ... and the geometry, into `d
 	d.vocWide = sw.vocWide;
 	d.vocNHalfLines = sw.vocNHalfLines;
 	d.noAlign = sw.noAlign;
+	d.vocInterior = sw.vocInterior;
 	d.alignAll = sw.alignAll;
 	d.noFastFft = sw.noFastFft;
 	// lean FFT tables (8-byte window entries + generated modulation, six stage twiddles instead of fifteen) are OPT-IN: they take 0.2 ms
@@ -1068,12 +1069,13 @@ template <typename F> void Batch::timedRecurrence(const TileStreams &ts, F &&lau
 	}
 }
 // The batch as the kernels of one tile see it: the tile's workspace, the half of the carry it writes, its rows of the tile-info table
-DevBatch Batch::tileView(const TileBuffers &w, int carryCur, const int *tileInfo) const {
+DevBatch Batch::tileView(const TileBuffers &w, int carryCur, const int *tileInfo, int maxHops) const {
 	DevBatch dd = d;
 	dd.Xcur = w.Xcur; dd.Xprev = w.Xprev; dd.PE = w.PE; dd.OUT = w.OUT; dd.REC = w.REC; dd.dump = w.dump;
 	dd.map = w.map; dd.ratio = w.ratio; dd.envelope = w.envelope; dd.energyT = w.energyT; dd.smoothT = w.smoothT; dd.peaksT = w.peaksT; dd.est = w.est; dd.freqEst = w.freqEst; dd.frames = w.frames; dd.fftScratch = w.fftScratch;
 	dd.carryCur = carryCur;
 	dd.nHops = tileInfo; dd.lastNewHop = tileInfo + subS;
+	dd.tileMaxHops = maxHops;
 	return dd;
 }
 
@@ -1102,7 +1104,7 @@ void Batch::runTilesRange(const TileRun &run, int tile0, int tile1, int carryFir
 			// its windows in this run and the pair teams apply; every other tile keeps Band.prevInput in Xprev.  SMST_VOC_TWIST=0: no tile.
 			const bool twisted = d.vocTwist && !continuous && !run.pendingRun && fused && !(tileHops == 1 && singleHop) && th.twistCapable() &&
 			                     vocoderAlignedApplies(d) && analyseTwistApplies(d, ns, tileHops);
-			const DevBatch dd = tileView(slots[slot], (carryFirst + t) & 1, run.dTileInfo + ((size_t)(sub*nTiles + t)*2)*subS);
+			const DevBatch dd = tileView(slots[slot], (carryFirst + t) & 1, run.dTileInfo + ((size_t)(sub*nTiles + t)*2)*subS, th.maxHops);
 			if (!ts.serial && q - tile0 >= 2) { // this workspace was last used by tile q-2
 				SMST_HIP(hipStreamWaitEvent(ts.sF, evChain[slot], 0));
 				SMST_HIP(hipStreamWaitEvent(ts.sF, evSynth[slot], 0));
@@ -1455,6 +1457,7 @@ void Batch::summariseStreamTiles(const CallPlan &c, int s) {
 		info[sl] = cnt;
 		int lastNewLocal = -1;
 		TileSummary &th = tileHasV[(size_t)sub*nTiles + t];
+		th.maxHops = std::max(th.maxHops, cnt);
 		for (int h = h0; h < h1; ++h) {
 			const unsigned f = list[h].flags;
 			if (f & HOP_PREANALYSED) th.preAnalysed = true;

@@ -233,7 +233,7 @@ private:
 	TileStreams forkTileStreams(const TileRun &run);
 	void joinTileStreams(const TileStreams &ts, int first, int passes, int depth);
 	template <typename F> void timedRecurrence(const TileStreams &ts, F &&launch);
-	DevBatch tileView(const TileBuffers &w, int carryCur, const int *tileInfo) const;
+	DevBatch tileView(const TileBuffers &w, int carryCur, const int *tileInfo, int maxHops = 0) const;
 	void runTilesRange(const TileRun &run, int tile0, int tile1, int carryFirst); // tile by tile
 	bool continuousApplies(const TileRun &run, int tile) const;
 	void runTilesContinuous(const TileRun &run, int tile0, int tile1, int carryFirst); // the recurrence as ONE wavefront through the tiles [tile0, tile1) (kVocoderCont)

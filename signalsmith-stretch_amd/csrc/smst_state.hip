@@ -272,7 +272,7 @@ void launchFftComplexSelfTest(const float *in, float *out, int n, hipStream_t st
 
 static std::atomic<long long> gLaunchCounts[LK_COUNT];
 static const char *const kLaunchNames[LK_COUNT] = {
-	"vocoder_aligned", "vocoder_twisted", "vocoder_staged", "vocoder_gather", "vocoder_n", "vocoder_one", "vocoder_across", "vocoder_continuous", "chain_unfused",
+	"vocoder_aligned", "vocoder_twisted", "vocoder_interior", "vocoder_staged", "vocoder_gather", "vocoder_n", "vocoder_one", "vocoder_across", "vocoder_continuous", "chain_unfused",
 	"analyse_teams", "analyse_pairs", "analyse_twist", "twist_rows", "analyse_fast", "analyse_generic", "synth_teams", "synth_fast", "synth_generic", "synth_emit", "emit_carried", "feed_one_pass", "pcm_in", "pcm_out", "clip_in", "clip_out", "pcm_out_dithered", "clip_out_dithered", "pcm_out_levelled", "clip_out_levelled", "clip_peak"};
 void countLaunch(LaunchKind k) { gLaunchCounts[k].fetch_add(1, std::memory_order_relaxed); }
 long long launchCount(const char *name) {

@@ -24,6 +24,8 @@
 //   SMST_FFT_TEAMS         1        0: one frame per workgroup; 2: persistent teams even for tiles with few frames per team (tests)
 //   SMST_ANALYSE_PAIRS     1        0: the analysis teams take one frame per pass, three teams per workgroup (kAnalyseTeams) instead of two frames per pass, two teams (kAnalyseTeamPairs)
 //   SMST_VOC_TWIST         1        0: no twisted tiles -- Xprev holds Band.prevInput everywhere and every plain record forms its two previous-hop twists itself
+//   SMST_VOC_INTERIOR      1        0: the line-aligned producers (kVocoder ALIGNED) run the general form of a block, with its edge handling, in every block instead of the
+//                                   interior form between a row's edges
 //   SMST_SYNTH_EMIT        1        0: kSynthTeams + kEmit; 2: kSynthEmitTeams also for small tiles (tests)
 //   SMST_CARRIED_EMIT      1        0: a call without hops emits through kEmit (which copies the carry) instead of kEmitCarried (cross-check: bit-identical)
 //   SMST_VOCN_WIDE         1        0: kVocoderN's producer passes 16 rows x 4 steps (the first form) instead of 8 rows x 8 steps
@@ -39,7 +41,7 @@ namespace smst {
 
 struct Switches {
 	bool overlap = true, noFuse = false, noSingleHop = false, noAcross = false, checkLaunches = false;
-	int noFeedFusion = 0, fftTeams = 1, analysePairs = 1, vocTwist = 1, synthEmit = 1, debugMode = 0, vocNWide = 1, vocWide = 1, vocNHalfLines = 2, carriedEmit = 1;
+	int noFeedFusion = 0, fftTeams = 1, analysePairs = 1, vocTwist = 1, vocInterior = 1, synthEmit = 1, debugMode = 0, vocNWide = 1, vocWide = 1, vocNHalfLines = 2, carriedEmit = 1;
 	bool noStage = false, noAlign = false, alignAll = false, noFastFft = false, fftLean = false, feedSerial = false, continuous = false;
 	int contWriterWave = 4;
 	double workspaceGiB = 0; // 0: automatic
@@ -69,6 +71,7 @@ struct Switches {
 		s.fftTeams = num("SMST_FFT_TEAMS", 1);
 		s.analysePairs = num("SMST_ANALYSE_PAIRS", 1);
 		s.vocTwist = num("SMST_VOC_TWIST", 1);
+		s.vocInterior = num("SMST_VOC_INTERIOR", 1);
 		s.synthEmit = num("SMST_SYNTH_EMIT", 1);
 		s.carriedEmit = num("SMST_CARRIED_EMIT", 1);
 		s.vocNWide = num("SMST_VOCN_WIDE", 1);

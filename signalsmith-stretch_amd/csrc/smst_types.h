@@ -28,6 +28,7 @@ struct TileSummary {
 	bool estimatesBase;    // a formant hop that estimates its base frequency (:929-966)
 	bool plainPrev;        // a hop whose previous input is not its own re-analysed window (no HOP_REANALYSE_PREV: prevSrc is a row of Xcur or the carried state)
 	int lateHops;          // the tile's first hops up to the last one with a window that reaches into the history (0: none)
+	int maxHops;           // the most hops a stream has in this tile
 	bool plain() const { return !(mapped || formants); }
 	// what the continuous wavefront (kVocoderCont) asks of a tile: plain, bounded, whole-line -- what launchVocoder sends to the aligned
 	// form -- with a new spectrum in every hop (the rows of a later tile then never read the carried feed-forward state)

@@ -286,31 +286,50 @@ __device__ __forceinline__ void vocoderProduceAligned(const DevBatch &d, int s, 
 	float2 rot1 = make_float2(1.f, 0.f), rotL = rot1;
 	// PAR = (n + 1) & 1: the rows with that parity take a new line in block n; m = n - row is odd
 	auto lineOf = [&](int n, int par, int i) { const int m = n - 8*it - lrow[par][i]; return m >= -1 ? (m + 1) >> 1 : -1; };
-	auto issueLines = [&](int n, int par, Async16 (&v)[G::LOADS]) {
+	// Where a block's requests go (linesAt / smallAt, and their interior forms below) and the requests themselves (requestLines / requestSmall):
+	// ONE load instruction per register and block whichever form found its address, so that no register with a load in flight is ever the
+	// result of two code paths that the compiler would have to reconcile with copies
+	struct Wanted { const float2 *line[G::LOADS]; const void *x; const float2 *rot1, *rotL, *car1[CH], *carL[CH]; };
+	auto linesAt = [&](int n, int par, Wanted &w) {
 #pragma unroll
 		for (int i = 0; i < G::LOADS; ++i) {
 			const int jc = min(max(lineOf(n, par, i), 0), lines - 1);
-			asyncLoad16(v[i], lsrc[par][i] + 16*jc);
+			w.line[i] = lsrc[par][i] + 16*jc;
 		}
 	};
-	auto issueSmall = [&](int n) { // 3 requests (TWISTED: 1; FIRST: + 2*CH), every address clamped into its row: n may run past the tile's last block
+	auto smallAt = [&](int n, Wanted &w) { // 3 requests (TWISTED: 1; FIRST: + 2*CH), every address clamped into its row: n may run past the tile's last block
 		const int x0 = BS*(n - 8*it) + 2*xpiece, xcl = min(max(x0, 0), M - 2);
-		if (FIRST) asyncLoad8(xe, xenergy + xcl);
-		else asyncLoad16(xv, xsrc + xcl);
+		if (FIRST) w.x = xenergy + xcl;
+		else w.x = xsrc + xcl;
 		[[maybe_unused]] const int b = BS*(n - row) + st;
 		if constexpr (!TWISTED) {
-			asyncLoad8(rotNext1, d.rot + min(max(b + 1, 0), M - 1));
-			asyncLoad8(rotNextL, d.rot + min(max(b + L, 0), M - 1));
+			w.rot1 = d.rot + min(max(b + 1, 0), M - 1);
+			w.rotL = d.rot + min(max(b + L, 0), M - 1);
 		}
 		if (FIRST) { // hop 0's previous-hop taps are the carried Band.output (FOLD0): lanes 0..7 = row 0 (no skew), steps 0..7
 			const int b0 = min(max(BS*n + st, 0), M - 1);
 #pragma unroll
 			for (int c = 0; c < CH; ++c) {
-				asyncLoad8(carNext1[c], carried + (size_t)c*M + min(b0 + 1, M - 1));
-				asyncLoad8(carNextL[c], carried + (size_t)c*M + min(b0 + L, M - 1));
+				w.car1[c] = carried + (size_t)c*M + min(b0 + 1, M - 1);
+				w.carL[c] = carried + (size_t)c*M + min(b0 + L, M - 1);
 			}
 		}
 	};
+	auto requestLines = [&](const Wanted &w, Async16 (&v)[G::LOADS]) {
+#pragma unroll
+		for (int i = 0; i < G::LOADS; ++i) asyncLoad16(v[i], w.line[i]);
+	};
+	auto requestSmall = [&](const Wanted &w) {
+		if (FIRST) asyncLoad8(xe, w.x);
+		else asyncLoad16(xv, w.x);
+		if constexpr (!TWISTED) { asyncLoad8(rotNext1, w.rot1); asyncLoad8(rotNextL, w.rotL); }
+		if (FIRST) {
+#pragma unroll
+			for (int c = 0; c < CH; ++c) { asyncLoad8(carNext1[c], w.car1[c]); asyncLoad8(carNextL[c], w.carL[c]); }
+		}
+	};
+	auto issueLines = [&](int n, int par, Async16 (&v)[G::LOADS]) { Wanted w; linesAt(n, par, w); requestLines(w, v); };
+	auto issueSmall = [&](int n) { Wanted w; smallAt(n, w); requestSmall(w); };
 	float2 car1[CH], carL[CH];
 #pragma unroll
 	for (int c = 0; c < CH; ++c) car1[c] = carL[c] = make_float2(0.f, 0.f);
@@ -355,6 +374,67 @@ __device__ __forceinline__ void vocoderProduceAligned(const DevBatch &d, int s, 
 		}
 		if constexpr (!TWISTED) { rot1 = asyncValue(rotNext1); rotL = asyncValue(rotNextL); }
 	};
+	// ---- The INTERIOR form of a block (SMST_VOC_INTERIOR, default on).  Everything above that clamps, selects a zero or masks lanes exists for
+	// the edges of a row; with mw = n - 8*it the block number counted from the wave's first row, and m = mw - r that of local row r (0..7), a
+	// block of a wave whose eight rows are all hops of the tile (8*it + 7 < nh) needs none of it when
+	//   records        b = 8m + st in [L, M-L-1] for every lane: 8(mw-7) >= L and 8mw + 7 <= M-L-1          <=>  8 <= mw <= M/8 - 2
+	//                  (then b > 0, b >= L, b < M-1, b < M-L hold, b + off <= M-1 is not clamped, and no lane is outside the tile)
+	//   park           the rows that take a line (m odd) have 0 <= (m+1)/2 <= M/16 - 1, i.e. -1 <= m <= M/8 - 3     <=>  6 <= mw <= M/8 - 3
+	//                  the row above: 0 <= x0, x0 + 1 < M with x0 = 8mw + 2*piece <= 8mw + 14                       <=>  mw <= M/8 - 2
+	//   line requests  (for block mw+2) the same with mw + 2                                                        <=>  4 <= mw <= M/8 - 5
+	//   small requests (for block mw+1) row above: 8(mw+1) + 14 <= M-2; rotation factors and carried taps:
+	//                  0 <= 8(mw+1-7) + 1 and 8(mw+1) + 7 + L <= M-1                                                 <=>  6 <= mw <= M/8 - 3
+	// (L <= 8, M a multiple of 16) -- together vocInteriorFirst <= mw <= vocInteriorLast(M) = M/8 - 5 (smst_vocoder_common.h): 372 of the 391
+	// blocks a wave is active in at M = 3072.  The loop below runs blocks in pairs that begin at even mw; a pair is interior when both are.
+	// Inside the range a request's position is its lane's constant plus a multiple of the block number: the address is the lane's pointer plus an
+	// unsigned byte offset whose varying part is formed on the scalar unit -- one subtraction and a 64-bit add where lineOf + clamp + shift + address
+	// build took ten instructions.  (Running pointers, one per request, save the subtraction and cost 14 registers that stay live through the general
+	// form too: the stereo kernels then spill.)
+	const bool wholeWave = d.vocInterior && 8*it + 7 < nh && kVocInteriorFirst + 1 <= vocInteriorLast(M);
+	auto atBytes = [](const auto *p, unsigned bytes) { return reinterpret_cast<decltype(p)>(reinterpret_cast<const char *>(p) + bytes); };
+	// lineOf(n, par, i) = (mw - par + 1)/2 - rr for the lane's rows r = 2*rr + par, rr = ((k + 64*i) >> 3)/(2*CH) = laneRR + i*(4/CH)
+	const unsigned laneRR = unsigned(k >> 3)/(2*CH);
+	auto linesAtI = [&](int n, int par, Wanted &w) { // linesAt(n, par, w), every line inside its row
+		const unsigned jw = unsigned((n - 8*it - par + 1) >> 1);
+#pragma unroll
+		for (int i = 0; i < G::LOADS; ++i) w.line[i] = atBytes(lsrc[par][i], 128u*(jw - unsigned(i*(4/CH))) - 128u*laneRR);
+	};
+	auto smallAtI = [&](int n, Wanted &w) { // smallAt(n, w), every address inside its row
+		const unsigned mw = unsigned(n - 8*it);
+		if (FIRST) w.x = atBytes(xenergy, 4u*BS*mw + 8u*unsigned(xpiece));
+		else w.x = atBytes(xsrc, 8u*BS*mw + 16u*unsigned(xpiece));
+		if constexpr (!TWISTED) { // bins b + 1, b + L with b = BS*(mw - r) + st
+			const unsigned lane = 8u*unsigned(st - BS*r); // (wraps; the sum does not)
+			w.rot1 = atBytes(d.rot, 8u*(BS*mw + 1) + lane);
+			w.rotL = atBytes(d.rot, 8u*(BS*mw + L) + lane);
+		}
+		if (FIRST) { // (it == 0: mw = n)
+#pragma unroll
+			for (int c = 0; c < CH; ++c) {
+				w.car1[c] = atBytes(carried + (size_t)c*M, 8u*(BS*mw + 1) + 8u*unsigned(st));
+				w.carL[c] = atBytes(carried + (size_t)c*M, 8u*(BS*mw + L) + 8u*unsigned(st));
+			}
+		}
+	};
+	auto parkI = [&](int par, Async16 (&v)[G::LOADS]) { // park() where every line and every piece lies inside its row
+		if (FIRST) {
+#pragma unroll
+			for (int c = 0; c < CH; ++c) { car1[c] = asyncValue(carNext1[c]); carL[c] = asyncValue(carNextL[c]); }
+		}
+#pragma unroll
+		for (int i = 0; i < G::LOADS; ++i) {
+			float4 *lower = reinterpret_cast<float4 *>(sbuf + llds[par][i]), *upper = reinterpret_cast<float4 *>(sbuf + llds[par][i] + 16);
+			*lower = *upper;
+			*upper = asyncValue(v[i]);
+		}
+		if (xlane) {
+			float4 piece;
+			if (FIRST) { const float2 e = asyncValue(xe); piece = make_float4(e.x, 0.f, e.y, 0.f); }
+			else piece = asyncValue(xv);
+			*reinterpret_cast<float4 *>(xbuf + xc*16 + 2*xpiece) = piece;
+		}
+		if constexpr (!TWISTED) { rot1 = asyncValue(rotNext1); rotL = asyncValue(rotNextL); }
+	};
 	const HopDesc hd = hopsLds[row < nh ? row : 0];
 	const bool rotate = hd.flags & HOP_NEW_SPECTRUM;
 	const float tf = hd.timeFactor;
@@ -393,31 +473,42 @@ __device__ __forceinline__ void vocoderProduceAligned(const DevBatch &d, int s, 
 		}
 		landed(vO);
 	}
-	auto step = [&](int n, int par, Async16 (&v)[G::LOADS], Async16 (&vNextBlock)[G::LOADS]) {
-		park(n, par, v);
+	// interior (wave-uniform): the block and the blocks its requests are for lie between the rows' edges
+	auto step = [&](int n, int par, Async16 (&v)[G::LOADS], Async16 (&vNextBlock)[G::LOADS], bool interior) {
+		Wanted w; // small loads of block n + 1, lines of block n + 2
+		if (interior) { parkI(par, v); smallAtI(n + 1, w); linesAtI(n + 2, par, w); }
+		else { park(n, par, v); smallAt(n + 1, w); linesAt(n + 2, par, w); }
 		waveSync();
-		issueSmall(n + 1);
-		issueLines(n + 2, par, v);
+		requestSmall(w);
+		requestLines(w, v);
 		const int slot = n%NB;
 		while (n - ldsPeek(&sync[NB]) >= NB) __builtin_amdgcn_s_sleep(2); // slot still being read
 		asm volatile("" ::: "memory");
 		const int b0 = BS*(n - row), b = b0 + st;
+		const AlignView<CH, L> view(sbuf, xbuf, r, st, (n - row) & 1, !(row > 0), rot1, rotL); // above the tile's first hop: the carried energies
 		float f[NCH*4];
+		if (interior) { // every lane has a record, and none at an edge of the spectrum
 #pragma unroll
-		for (int j = 0; j < NCH*4; ++j) f[j] = 0.0f;
-		if (row < nh && b >= 0 && b < M) {
-			const AlignView<CH, L> view(sbuf, xbuf, r, st, (n - row) & 1, !(row > 0), rot1, rotL); // above the tile's first hop: the carried energies
-			plainRecord<CH, L, FIRST, TWISTED>(view, b, M, tf, rotate, true, r == 0, car1, carL, f);
+			for (int j = NF; j < NCH*4; ++j) f[j] = 0.0f; // (the record's padding)
+			plainRecord<CH, L, FIRST, TWISTED, true>(view, b, M, tf, rotate, true, r == 0, car1, carL, f);
+			storeRecord<BS>(recs, slot, st, row, f);
+		} else {
+#pragma unroll
+			for (int j = 0; j < NCH*4; ++j) f[j] = 0.0f;
+			if (row < nh && b >= 0 && b < M) plainRecord<CH, L, FIRST, TWISTED>(view, b, M, tf, rotate, true, r == 0, car1, carL, f);
+			storeRecord<BS>(recs, slot, st, row, f);
 		}
-		storeRecord<BS>(recs, slot, st, row, f);
 		asm volatile("" ::: "memory");
 		if (k == 0) ldsCount(&sync[slot]);
 		waveSync(); // every lane has read its operands before the next block's lines are parked
 		landed(vNextBlock);
 	};
+	// one loop; a pair of blocks (the two parities keep their register sets) is interior when both blocks are
+	const int interiorFirst = 8*it + kVocInteriorFirst, interiorLast = 8*it + vocInteriorLast(M) - 1; // first blocks (even) of the interior pairs
 	for (int n = n0 + 1; n < totalBlocks; n += 2) {
-		step(n, 1, vO, vE);
-		step(n + 1, 0, vE, vO);
+		const bool interior = wholeWave && n >= interiorFirst && n <= interiorLast;
+		step(n, 1, vO, vE, interior);
+		step(n + 1, 0, vE, vO, interior);
 	}
 	asyncWait<0>(); // the requests that ran past the tile's last block: nothing of this wave stays in flight behind it
 }
@@ -662,6 +753,11 @@ __global__ __launch_bounds__(64*kVocWaves) __attribute__((amdgpu_waves_per_eu(4,
 bool vocoderAlignedApplies(const DevBatch &d) {
 	return d.C <= 2 && d.L >= 2 && d.L <= 4 && !d.noStage && !d.noAlign && d.M%16 == 0 && !d.halfState && (d.L == 4 || d.alignAll);
 }
+// Whether some wave of a launch of the aligned kernel runs interior blocks (vocoderProduceAligned): the form is enabled, a stream of the tile has
+// a whole producer wave of hops (rows 0..7), and the geometry leaves a pair of blocks between the edges
+static bool vocoderInteriorApplies(const DevBatch &d) {
+	return d.vocInterior && d.tileMaxHops >= 8 && kVocInteriorFirst + 1 <= vocInteriorLast(d.M);
+}
 template <int CH, int L>
 static void launchVocoderTL(const DevBatch &d, int sBase, int nStreams, int hopBase, bool plain, bool bounded, bool twisted, hipStream_t st) {
 	constexpr int NCH = (9 + 3*CH + 3)/4;
@@ -679,6 +775,7 @@ static void launchVocoderTL(const DevBatch &d, int sBase, int nStreams, int hopB
 			else hipLaunchKernelGGL((kVocoder<CH, true, L, true, false, false, true>), dim3(nStreams), dim3(64*kVocWaves), ldsAligned, st, d, sBase, hopBase, 0, 0);
 			countLaunch(LK_VOC_ALIGNED); // (either form)
 			if (twisted) countLaunch(LK_VOC_TWISTED);
+			if (vocoderInteriorApplies(d)) countLaunch(LK_VOC_INTERIOR);
 			return;
 		}
 	}

@@ -22,6 +22,11 @@ constexpr int kVocOutBlocksAligned = 3; // lag 8: a row's 16-bin line lies in ex
 // lane groups, and 2*CH*64 float2 is a multiple of the 32 banks (an 8-way conflict on every writer read with the first layout)
 constexpr int kVocOutPitch = 66;
 
+// The INTERIOR blocks of a line-aligned producer wave (vocoderProduceAligned has the derivation): blocks mw = n - 8*it, counted from the wave's first
+// row, in [kVocInteriorFirst, vocInteriorLast(M)].  The launcher evaluates the same rule for its counter.
+constexpr int kVocInteriorFirst = 8;
+__host__ __device__ inline int vocInteriorLast(int M) { return (M >> 3) - 5; }
+
 __device__ __forceinline__ float2 selectPair(bool pick, float2 a, float2 b) { return make_float2(pick ? a.x : b.x, pick ? a.y : b.y); }
 __device__ __forceinline__ float2 fromLaneBelow(float2 v, float2 lane0) { // lane k receives lane k-1's v; lane 0 keeps its `lane0`
 	// DPP wave_shr:1 without bound_ctrl: a lane with no source lane keeps the old value of the destination register
@@ -43,8 +48,10 @@ __device__ __forceinline__ float2 fromLaneBelow(float2 v, float2 lane0) { // lan
 // foldLane: this lane's record is in it.
 // TWISTED (kVocoder ALIGNED on a twisted tile): prev(c, off) is not Band.prevInput but the finished twist of bin b + off
 // (prevHopTwist, formed by the analysis pass); rot() and `rotate` are then unused.
+// INTERIOR (the line-aligned producers' interior blocks): the caller guarantees L <= b < M - L, so the clamp of b + off and the four zeroings at the
+// spectrum's edges cannot act and are left out; every floating-point operation and its order stay.
 // ------------------------------------------------------------------------------------------------------
-template <int CH, int L, bool FOLD, bool TWISTED = false, typename View, int NFLOATS>
+template <int CH, int L, bool FOLD, bool TWISTED = false, bool INTERIOR = false, typename View, int NFLOATS>
 __device__ __forceinline__ void plainRecord(const View &v, int b, int M, float tf, bool rotate, bool foldWave, bool foldLane,
                                             const float2 (&car1)[CH], const float2 (&carL)[CH], float (&f)[NFLOATS]) {
 	auto lerpIN = [&](int c, LerpIndex li) { // li.lo is an absolute bin
@@ -66,7 +73,7 @@ __device__ __forceinline__ void plainRecord(const View &v, int b, int M, float t
 	float2 A = cmulc(Pm, lerpIN(mc, lerpIndex(fb - tf)));
 	float2 B = cmulc(Pm, lerpIN(mc, lerpIndex(fb - L*tf)));
 	auto twist = [&](int off, float stepMul) { // the coefficient of the previous hop's output at bin b + off
-		const int bc = min(b + off, M - 1);
+		const int bc = INTERIOR ? b + off : min(b + off, M - 1);
 		const float2 Px = v.in(mc, off);
 		float2 TW;
 		if constexpr (TWISTED) TW = v.prev(mc, off); // the analysis pass has formed it
@@ -82,10 +89,12 @@ __device__ __forceinline__ void plainRecord(const View &v, int b, int M, float t
 	};
 	float2 Cc = twist(1, 1.0f), Dc = twist(L, float(L));
 	const float2 zero = make_float2(0.f, 0.f);
-	if (!(b > 0)) A = zero;
-	if (!(b >= L)) B = zero;
-	if (!(b < M - 1)) Cc = zero;
-	if (!(b < M - L)) Dc = zero;
+	if constexpr (!INTERIOR) {
+		if (!(b > 0)) A = zero;
+		if (!(b >= L)) B = zero;
+		if (!(b < M - 1)) Cc = zero;
+		if (!(b < M - L)) Dc = zero;
+	}
 	if constexpr (FOLD) {
 		if (foldWave) {
 			float2 c1 = car1[0], cL = carL[0];
