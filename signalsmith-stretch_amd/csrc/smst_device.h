@@ -90,7 +90,6 @@ struct DevBatch {
 	const int *lastNewHop; // [subS] tile-local index of the last hop with a new spectrum, or -1
 	// (behind everything else: the fields above keep the places every other kernel reads them from)
 	int vocInterior;       // the line-aligned producers run the interior form of a block between a row's edges (default 1; SMST_VOC_INTERIOR=0: the general form in every block -- the cross-check)
-	int tileMaxHops;       // host only: the most hops a stream of this tile has (TileSummary::maxHops; the launchers' counters)
 };
 
 // The continuous wavefront of the fused mono / stereo recurrence (kVocoderCont, smst_vocoder_cont.hip): launch `tile` covers the global
@@ -144,6 +143,10 @@ struct MoveArgs {
 __host__ __device__ inline bool fftNeedsScratch(int bands) { return (size_t)bands*16 > (size_t)150*1024; }
 // The register-blocked FFT's band counts, 256*R3 (smst_fft.hip)
 __host__ __device__ inline bool isFastSize(int bands) { return bands == 256*10 || bands == 256*12 || bands == 256*20 || bands == 256*24; }
+constexpr size_t kLdsBytesPerCU = 160*1024;
+// kChain's LDS (smst_vocoder_n.hip), one array of float2: a ring [C][ringSlots][64] of the last outputs per channel and lane, then the stage [C][128].
+// Its size depends on the geometry alone; a batch whose ring does not fit is refused when it is created (Batch::Batch).
+constexpr size_t chainLdsBytes(int channels, int ringSlots) { return ((size_t)channels*ringSlots*64 + (size_t)channels*128)*sizeof(float2); }
 constexpr int kMaxBands = 150*1024/8; // 19200 bins of LDS; the largest band count {1,2,3,4,5,6,8}*2^k reaches below it is 16384
 
 struct WindowPad { int lo, hi; };
@@ -171,24 +174,15 @@ enum LaunchKind {
 long long launchCount(const char *name); // -1: unknown name
 
 void launchEnergy(const DevBatch &d, const IoArgs &io, int sBase, int nStreams, int maxSamples, float *energyOut, hipStream_t st);
-// twisted: the tile's Xprev rows take the finished previous-hop twists instead of Band.prevInput (analyseTwistApplies; lateHops: the tile's first hops,
+// twisted: the tile's Xprev rows take the finished previous-hop twists instead of Band.prevInput (RecurrenceForm::twisted; lateHops: the tile's first hops,
 // those with a window that reaches into the history -- kTwistRows turns their rows)
 void launchAnalyse(const DevBatch &d, const IoArgs &io, int sBase, int nStreams, int hopBase, int tileHops, bool anyInCall, bool anyLate, hipStream_t st, bool twisted = false, int lateHops = 0);
 bool analyseTwistApplies(const DevBatch &d, int nStreams, int tileHops); // the pair teams take this tile (what a twisted tile's analysis is built on)
-bool vocoderAlignedApplies(const DevBatch &d);                           // a plain, bounded tile takes kVocoder ALIGNED
 bool launchFeed(const DevBatch &d, int sBase, int nStreams, int hopBase, int tileHops, bool anyFormants, bool anyEstimatedBase, hipStream_t st); // true: pass A done too
-void launchPredict(const DevBatch &d, int sBase, int nStreams, int hopBase, int tileHops, bool plain, bool passADone, hipStream_t st);
-void launchChain(const DevBatch &d, int sBase, int nStreams, int hopBase, hipStream_t st);
-void launchPredictFused(const DevBatch &d, int sBase, int nStreams, int hopBase, int tileHops, bool plain, bool passADone, hipStream_t st);
-void launchVocoder(const DevBatch &d, int sBase, int nStreams, int hopBase, bool plain, bool bounded, bool twisted, hipStream_t st); // bounded: no random time factors in the tile; twisted: see launchAnalyse
-bool fusedSupported(const DevBatch &d);
-bool continuousSupported(const DevBatch &d); // the geometries of the line-aligned producers (mono / stereo, L <= 4, M a multiple of 16, fp32 state)
+void launchPredict(const DevBatch &d, bool fused, int sBase, int nStreams, int hopBase, int tileHops, bool plain, bool passADone, hipStream_t st); // fused: RecurrenceForm::fused()
+// (the recurrence of a tile: recurrenceForm / launchRecurrence, smst_recurrence_form.h)
 int continuousPeriod(const DevBatch &d);     // blocks per tile of the continuous wavefront
 void launchVocoderContinuous(const DevBatch &d, const ContArgs &a, int sBase, int nStreams, hipStream_t st);
-bool singleHopSupported(const DevBatch &d);
-void launchVocoderOne(const DevBatch &d, int sBase, int nStreams, int hopBase, bool plain, hipStream_t st); // tiles in which no stream has more than one hop
-bool acrossSupported(const DevBatch &d);
-void launchVocoderAcross(const DevBatch &d, int sBase, int nStreams, int hopBase, bool plain, hipStream_t st); // the same tiles, mono / stereo: lanes of the recurrence wave = streams
 void launchSynth(const DevBatch &d, int sBase, int nStreams, int hopBase, int tileHops, hipStream_t st);
 void launchEmit(const DevBatch &d, const IoArgs &io, int sBase, int nStreams, int tileIndex, int maxSpan, hipStream_t st);
 void launchEmitCarried(const DevBatch &d, const IoArgs &io, hipStream_t st); // a call without hops, every stream (emit table row 0)

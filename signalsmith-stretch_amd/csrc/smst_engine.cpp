@@ -122,7 +122,7 @@ Batch::Batch(int streams, int channels, int block, int interval, bool splitCompu
 		if (ring > 64) throw Error("interval too small relative to the FFT size (vertical step too long)");
 		// kChain (9-16 channels, a vertical step the fused kernels do not take, or SMST_NO_FUSE -- so any channel count) keeps a ring of
 		// `ring` bins per channel and lane in LDS: up to 4 channels the vertical step may be 62, 5-9 channels 30, 10-16 channels 14
-		if (((size_t)C*ring*64 + (size_t)C*128)*sizeof(float2) > (size_t)160*1024)
+		if (chainLdsBytes(C, ring) > kLdsBytesPerCU)
 			throw Error("vertical step round(fftSamples/interval) = " + std::to_string(L) + " too long for " + std::to_string(C) +
 			            " channels: at most 62 for 1-4 channels, 30 for 5-9, 14 for 10-16 (the un-fused recurrence keeps a history ring per channel in LDS)");
 	}
@@ -177,7 +177,7 @@ void Batch::createStreamsAndEvents() {
 void Batch::readSwitches(const FftPlan &plan) { // ... and the geometry, into `d`
 	// the cross-check switches: one struct, one table, read once (smst_switches.h)
 	const Switches sw = Switches::fromEnvironment();
-	overlap = sw.overlap; noFuse = sw.noFuse; noSingleHop = sw.noSingleHop; noAcross = sw.noAcross; carriedEmit = sw.carriedEmit != 0; checkLaunches = sw.checkLaunches; continuous = sw.continuous; contWriterWave = sw.contWriterWave;
+	overlap = sw.overlap; formSwitches = FormSwitches{sw.noFuse, sw.noSingleHop, sw.noAcross, sw.continuous}; carriedEmit = sw.carriedEmit != 0; checkLaunches = sw.checkLaunches; contWriterWave = sw.contWriterWave;
 	workspaceGiB = sw.workspaceGiB;
 	subStreamsAsked = sw.subStreams;
 
@@ -521,7 +521,7 @@ void Batch::allocateWorkspace() {
 		}
 	}
 	if (workspaceGiB > 0) budgetGiB = std::max(0.0005, workspaceGiB); // SMST_WORKSPACE_GIB (smst_switches.h)
-	const bool needRecords = !fusedSupported(d) || noFuse; // the fused recurrence keeps its records in LDS
+	const bool needRecords = formReachable(d, formSwitches, RecurrenceKernel::CHAIN_UNFUSED); // the fused recurrence keeps its records in LDS
 	const size_t recChunks = (size_t(recordFloats(C)) + 3)/4;
 	d.recSteps = ((M + d.lag*(d.T - 1) + 63)/64)*64 + 8;
 	d.recPitch = int(recChunks*64 + 16);
@@ -570,7 +570,7 @@ void Batch::allocateWorkspace() {
 			// the spectra, the results and the frames of a PLAIN tile only, and only where that form can run at all (one sub-batch)
 			slots[2] = TileBuffers{};
 			dContSave = nullptr;
-			if (continuous && continuousSupported(d) && fusedSupported(d) && !noFuse && subS == S) {
+			if (formReachable(d, formSwitches, RecurrenceKernel::CONTINUOUS) && subS == S) {
 				TileBuffers &w = slots[2];
 				w.Xcur = devAlloc<float2>(rows);
 				w.Xprev = devAlloc<float2>(rows);
@@ -1069,13 +1069,12 @@ template <typename F> void Batch::timedRecurrence(const TileStreams &ts, F &&lau
 	}
 }
 // The batch as the kernels of one tile see it: the tile's workspace, the half of the carry it writes, its rows of the tile-info table
-DevBatch Batch::tileView(const TileBuffers &w, int carryCur, const int *tileInfo, int maxHops) const {
+DevBatch Batch::tileView(const TileBuffers &w, int carryCur, const int *tileInfo) const {
 	DevBatch dd = d;
 	dd.Xcur = w.Xcur; dd.Xprev = w.Xprev; dd.PE = w.PE; dd.OUT = w.OUT; dd.REC = w.REC; dd.dump = w.dump;
 	dd.map = w.map; dd.ratio = w.ratio; dd.envelope = w.envelope; dd.energyT = w.energyT; dd.smoothT = w.smoothT; dd.peaksT = w.peaksT; dd.est = w.est; dd.freqEst = w.freqEst; dd.frames = w.frames; dd.fftScratch = w.fftScratch;
 	dd.carryCur = carryCur;
 	dd.nHops = tileInfo; dd.lastNewHop = tileInfo + subS;
-	dd.tileMaxHops = maxHops;
 	return dd;
 }
 
@@ -1087,7 +1086,6 @@ void Batch::runTilesRange(const TileRun &run, int tile0, int tile1, int carryFir
 	// hundred waves, instruction-issue bound), `stSynth` synthesis + emission.  Two workspaces alternate, so the bulk
 	// kernels of the next tile fill the machine while the recurrence of the current one is in flight.
 	const TileStreams ts = forkTileStreams(run);
-	const bool singleHop = singleHopSupported(d) && !noSingleHop;
 	int q = tile0; // (the workspace of tile t of a single sub-batch is slots[t & 1] whatever segment it runs in: debugGetMap relies on it)
 	for (int sub = 0; sub < nSub; ++sub) {
 		const int sBase = sub*subS;
@@ -1098,13 +1096,11 @@ void Batch::runTilesRange(const TileRun &run, int tile0, int tile1, int carryFir
 			const int tileHops = std::min(T, std::max(1, maxHops - hopBase));
 			const int slot = q & 1;
 			const bool plain = th.plain();
-			const bool fused = fusedSupported(d) && !noFuse; // mono/stereo: records stay in LDS (kVocoder)
-			// A TWISTED tile: the rows of Xprev hold the finished previous-hop twists, formed once per bin by the analysis
-			// pass, instead of Band.prevInput.  Where kVocoder ALIGNED takes the tile (launchVocoder's conditions), every hop analyses both of
-			// its windows in this run and the pair teams apply; every other tile keeps Band.prevInput in Xprev.  SMST_VOC_TWIST=0: no tile.
-			const bool twisted = d.vocTwist && !continuous && !run.pendingRun && fused && !(tileHops == 1 && singleHop) && th.twistCapable() &&
-			                     vocoderAlignedApplies(d) && analyseTwistApplies(d, ns, tileHops);
-			const DevBatch dd = tileView(slots[slot], (carryFirst + t) & 1, run.dTileInfo + ((size_t)(sub*nTiles + t)*2)*subS, th.maxHops);
+			// which recurrence the tile takes: decided once, here (smst_recurrence_form.h).  fused: the records stay in LDS; twisted (DESIGN.md
+			// section 4): the rows of Xprev hold the finished previous-hop twists, formed once per bin by the analysis pass, instead of Band.prevInput
+			const RecurrenceForm form = recurrenceForm(d, th, tileHops, ns, run.pendingRun, formSwitches);
+			const bool fused = form.fused();
+			const DevBatch dd = tileView(slots[slot], (carryFirst + t) & 1, run.dTileInfo + ((size_t)(sub*nTiles + t)*2)*subS);
 			if (!ts.serial && q - tile0 >= 2) { // this workspace was last used by tile q-2
 				SMST_HIP(hipStreamWaitEvent(ts.sF, evChain[slot], 0));
 				SMST_HIP(hipStreamWaitEvent(ts.sF, evSynth[slot], 0));
@@ -1112,14 +1108,10 @@ void Batch::runTilesRange(const TileRun &run, int tile0, int tile1, int carryFir
 			if (!ts.serial && fused && !plain && q - tile0 >= 1) SMST_HIP(hipStreamWaitEvent(ts.sF, evChain[slot ^ 1], 0)); // pass A reads the carried state
 			if (th.anyHop) {
 				if (th.preAnalysed) timed(timings.otherMs, [&] { launchPendingToTile(dd, sBase, ns, dPendIn, dPendPrev, ts.sF); }); // blocks that began in an earlier call: their spectra are waiting
-				if (th.newSpectrum) timed(timings.analyseMs, [&] { launchAnalyse(dd, io, sBase, ns, hopBase, tileHops, th.windowInCall, th.windowInHistory, ts.sF, twisted, th.lateHops); if (profiling) ++timings.analyseLaunches; });
+				if (th.newSpectrum) timed(timings.analyseMs, [&] { launchAnalyse(dd, io, sBase, ns, hopBase, tileHops, th.windowInCall, th.windowInHistory, ts.sF, form.twisted, th.lateHops); if (profiling) ++timings.analyseLaunches; });
 				bool passADone = false;
 				if (!plain) timed(timings.feedMs, [&] { passADone = launchFeed(dd, sBase, ns, hopBase, tileHops, th.formants, th.estimatesBase, ts.sF); });
-				timed(timings.predictMs, [&] {
-					if (fused) launchPredictFused(dd, sBase, ns, hopBase, tileHops, plain, passADone, ts.sF);
-					else launchPredict(dd, sBase, ns, hopBase, tileHops, plain, passADone, ts.sF);
-					if (profiling) ++timings.predictLaunches;
-				});
+				timed(timings.predictMs, [&] { launchPredict(dd, fused, sBase, ns, hopBase, tileHops, plain, passADone, ts.sF); if (profiling) ++timings.predictLaunches; });
 				// the carried feed-forward state (Band.input/.prevInput, Prediction.energy) may only move on once every
 				// reader of the OLD state has run: in the fused path the producers inside kVocoder still read it
 				if (!fused) timed(timings.otherMs, [&] { launchCarryFeed(dd, sBase, ns, hopBase, th.formants, ts.sF); });
@@ -1133,15 +1125,7 @@ void Batch::runTilesRange(const TileRun &run, int tile0, int tile1, int carryFir
 			const bool emitted = th.anyHop && !th.preAnalysed && synthEmitApplies(dd, ns, tileHops); // (preAnalysed: a hop that began before the call's first sample -- kSynthTeams + kEmit place its frame)
 			const bool earlySynth = emitted || tileHops == 1;
 			if (th.anyHop) {
-				timedRecurrence(ts, [&] {
-					// (startBin: a block that a flush() interrupted inside its main prediction, HopDesc.startBin > 0.  Every form that forms its
-					// records through computeRecord honours it (all-zero records below the start bin); the staged / line-aligned producers of
-					// kVocoder do not go through it, so such a tile takes the gathering form -- `bounded` false)
-					if (fused && tileHops == 1 && singleHop && !noAcross && acrossSupported(dd) && !th.startBin) launchVocoderAcross(dd, sBase, ns, hopBase, plain, ts.sC);
-					else if (fused && tileHops == 1 && singleHop) launchVocoderOne(dd, sBase, ns, hopBase, plain, ts.sC);
-					else if (fused) launchVocoder(dd, sBase, ns, hopBase, plain, !th.randomTimeFactor && !th.startBin, twisted, ts.sC);
-					else launchChain(dd, sBase, ns, hopBase, ts.sC);
-				});
+				timedRecurrence(ts, [&] { launchRecurrence(dd, form, sBase, ns, hopBase, plain, ts.sC); });
 				// synthesis needs the recurrence's rows only: the hand-over of the tile's last rows to the carried state (two copies at HBM rate --
 				// 250 us of a 4096-stream hop quantum) runs beside it, behind the event synthesis waits for.  Where synthesis is a grid of
 				// per-frame workgroups and more recurrence launches follow (config 5) the hand-over goes first, as before: it is what the NEXT
@@ -1177,12 +1161,14 @@ void Batch::runTilesRange(const TileRun &run, int tile0, int tile1, int carryFir
 	joinTileStreams(ts, tile0, q - tile0, 2); // (passes, not tiles: q runs on through the sub-batches; tile0 may be odd)
 }
 
-// Whether a tile can be part of a continuous wavefront (kVocoderCont; runs of two or more such tiles are): the geometries of the
-// line-aligned producers, one sub-batch, and what the tile's hops need (TileSummary::continuousCapable).
+// Whether a tile can be part of a continuous wavefront (kVocoderCont; runs of two or more such tiles are): the third workspace exists (the
+// geometry and SMST_CONTINUOUS: allocateWorkspace), one sub-batch, what the tile's hops need (TileSummary::continuousCapable) -- and tile by
+// tile it would be an ALIGNED one.  Asked for a FULL tile: rows of a wavefront that does not drain are never a one-hop tile's, so a run's
+// last tile rides the wavefront even where it has one hop (tile by tile it would go to the single-hop kernels).
 bool Batch::continuousApplies(const TileRun &run, int t) const {
 	if (!slots[2].Xcur || run.pendingRun || run.carriedOnly || subS != S) return false;
-	if (!(d.L == 4 || d.alignAll)) return false; // (as launchVocoder chooses the aligned producers)
-	return run.tileHas[t].continuousCapable();
+	const TileSummary &th = run.tileHas[t];
+	return th.continuousCapable() && recurrenceForm(d, th, d.T, S, false, formSwitches).kernel == RecurrenceKernel::ALIGNED;
 }
 
 // The same pipeline as runTiles -- analysis of tile t+1, recurrence, synthesis + emission over three HIP streams -- with the recurrence as
@@ -1530,7 +1516,7 @@ void Batch::process(const float *in, long long inSS, long long inCS, const int *
 	// One row of T hop descriptors per stream and tile -- except in the real-time calling pattern, where no stream fires more than one hop per
 	// call: the single-hop kernels index hop 0 only, so a row is ONE descriptor (4096 streams: 131 KB to clear and upload per 128-frame
 	// quantum instead of 8.4 MB -- a third of the quantum's cost).  (The wavefront kernels load a row of 64 blindly: they keep the full rows.)
-	const bool compactHops = maxHops <= 1 && singleHopSupported(d) && !noSingleHop && fusedSupported(d) && !noFuse;
+	const bool compactHops = maxHops <= 1 && formReachable(d, formSwitches, RecurrenceKernel::ONE);
 	c.nTiles = nTiles;
 	c.hopStride = compactHops ? 1 : nTiles*T;
 	const int nSub = (S + subS - 1)/subS;

@@ -9,6 +9,7 @@
 #include <vector>
 #include <hip/hip_runtime.h>
 #include "smst_device.h"
+#include "smst_recurrence_form.h"
 
 namespace smst {
 
@@ -182,7 +183,8 @@ private:
 	int callCur = 0;
 	hipEvent_t evStart = nullptr, evFeed[3] = {nullptr, nullptr, nullptr}, evChain[3] = {nullptr, nullptr, nullptr}, evOut[3] = {nullptr, nullptr, nullptr}, evSynth[3] = {nullptr, nullptr, nullptr}; // (the third set: the continuous wavefront's tile pipeline is one stage deeper)
 	struct TileBuffers { float2 *Xcur, *Xprev, *OUT, *dump, *map, *peaksT; float4 *REC; PredEntry *PE; float *ratio, *envelope, *energyT, *smoothT, *est, *freqEst, *frames; float2 *fftScratch; } slots[3]{}; // [2]: only what a plain tile touches, only where the continuous wavefront applies (allocateWorkspace)
-	bool overlap = true, noFuse = false, noSingleHop = false, noAcross = false, carriedEmit = true, continuous = false; // (smst_switches.h)
+	bool overlap = true, carriedEmit = true; // (smst_switches.h)
+	FormSwitches formSwitches{};             // ... those that take part in the choice of a tile's recurrence (smst_recurrence_form.h)
 	int contWriterWave = 4;
 	float2 *dContSave = nullptr; // kVocoderCont: the recurrence wave's history between two launches, [S][8*C*64]
 	double workspaceGiB = 0;
@@ -233,7 +235,7 @@ private:
 	TileStreams forkTileStreams(const TileRun &run);
 	void joinTileStreams(const TileStreams &ts, int first, int passes, int depth);
 	template <typename F> void timedRecurrence(const TileStreams &ts, F &&launch);
-	DevBatch tileView(const TileBuffers &w, int carryCur, const int *tileInfo, int maxHops = 0) const;
+	DevBatch tileView(const TileBuffers &w, int carryCur, const int *tileInfo) const;
 	void runTilesRange(const TileRun &run, int tile0, int tile1, int carryFirst); // tile by tile
 	bool continuousApplies(const TileRun &run, int tile) const;
 	void runTilesContinuous(const TileRun &run, int tile0, int tile1, int carryFirst); // the recurrence as ONE wavefront through the tiles [tile0, tile1) (kVocoderCont)

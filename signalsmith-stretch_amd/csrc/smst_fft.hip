@@ -1302,14 +1302,10 @@ void launchEnergy(const DevBatch &d, const IoArgs &io, int sBase, int nStreams, 
 }
 // f(R3 = M/256 as a compile-time constant) where M/256 is one of R3S; false, and f not called, at any other size
 template <int... R3S, typename F>
-static bool withR3(int M, F f) { return ((M == 256*R3S && (f(std::integral_constant<int, R3S>()), true)) || ...); }
+static bool withR3(int M, F f) { return M%256 == 0 && withInt<R3S...>(M/256, f); }
 // The register-blocked kernels exist at four sizes (isFastSize), the team kernels at the two whose stages A and B fit a team's 256 threads
 template <typename F> static bool withFastR3(int M, F f) { return withR3<10, 12, 20, 24>(M, f); }
 template <typename F> static bool withTeamR3(int M, F f) { return withR3<10, 12>(M, f); }
-template <typename F>
-static void withFlag(bool flag, F f) { // f(flag as a compile-time constant)
-	if (flag) f(std::true_type()); else f(std::false_type());
-}
 static size_t fastLdsBytes(int M) { return ((size_t)M + M/16)*sizeof(float2); } // fftFast's padded buffer
 static size_t teamLdsBytes(int M, int teams, int frames = 1) { // TeamWorkgroup: element table, first- and second-stage twiddles, a buffer per team and frame, barrier words
 	const size_t twA = frames == 1 ? M/2 : 0; // (two frames per pass: the first-stage twiddles are in registers)

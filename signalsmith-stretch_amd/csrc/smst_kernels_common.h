@@ -20,6 +20,7 @@
 #include <hip/hip_runtime.h>
 #include <atomic>
 #include <cstring>
+#include <type_traits>
 #include "smst_device.h"
 #include <smst_complex.h> // angle brackets: tests/emu shadows this header for the CPU stand-in
 #include <smst_fft_complex.h> // likewise
@@ -163,7 +164,28 @@ __device__ __forceinline__ float engineDraw(const DevBatch &d, unsigned state, i
 // ------------------------------------------------------------------------------------------------------
 static inline int divUp(int a, int b) { return (a + b - 1)/b; }
 void countLaunch(LaunchKind k); // smst_state.hip
-// 3-8 channels: smst_vocoder_n.hip (launchVocoder in smst_vocoder.hip dispatches on the channel count)
+// A run-time value as a template argument: f(v as a std::integral_constant) where v is one of VALUES; false, and f not called, for any other value
+template <int... VALUES, typename F>
+static bool withInt(int v, F f) { return ((v == VALUES && (f(std::integral_constant<int, VALUES>()), true)) || ...); }
+// ... where v is one of LO .. HI; HI also stands for every other value (the geometry predicates of smst_vocoder.hip keep those away)
+template <int LO, int HI, typename F>
+static void withIntIn(int v, F f) {
+	if constexpr (LO == HI) f(std::integral_constant<int, HI>());
+	else if (v == LO) f(std::integral_constant<int, LO>());
+	else withIntIn<LO + 1, HI>(v, f);
+}
+template <typename F>
+static void withFlag(bool flag, F f) { // f(flag as a compile-time constant)
+	if (flag) f(std::true_type()); else f(std::false_type());
+}
+
+// A recurrence kernel's dynamic LDS is laid out ONCE, in a layout type beside the kernel (VocoderLds, ContLds, VocoderNLds, VocoderOneLds,
+// PredictBLds; kChain: chainLdsBytes, smst_device.h): it names the regions in order as byte offsets, the kernel takes its pointers from them
+// (smemRaw + Lds::region), the launcher its size -- nothing else knows either.  (An LDS access past what the launcher asked for is dropped
+// silently on the device; the CPU stand-in checks the bytes behind the request after every launch, tests/emu/hip_emu.cpp.)
+// the recurrence launchers of smst_vocoder_n.hip (3-8 channels, one-hop tiles, records through HBM), for launchRecurrence in smst_vocoder.hip
 void launchVocoderMany(const DevBatch &d, int sBase, int nStreams, int hopBase, bool plain, hipStream_t st);
+void launchVocoderOne(const DevBatch &d, int sBase, int nStreams, int hopBase, bool plain, hipStream_t st); // tiles in which no stream has more than one hop
+void launchChain(const DevBatch &d, int sBase, int nStreams, int hopBase, hipStream_t st);
 
 } // namespace smst

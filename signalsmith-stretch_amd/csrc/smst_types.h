@@ -28,12 +28,12 @@ struct TileSummary {
 	bool estimatesBase;    // a formant hop that estimates its base frequency (:929-966)
 	bool plainPrev;        // a hop whose previous input is not its own re-analysed window (no HOP_REANALYSE_PREV: prevSrc is a row of Xcur or the carried state)
 	int lateHops;          // the tile's first hops up to the last one with a window that reaches into the history (0: none)
-	int maxHops;           // the most hops a stream has in this tile
+	int maxHops;           // the most hops a stream has in this tile (RecurrenceForm::interior)
 	bool plain() const { return !(mapped || formants); }
-	// what the continuous wavefront (kVocoderCont) asks of a tile: plain, bounded, whole-line -- what launchVocoder sends to the aligned
+	// what the continuous wavefront (kVocoderCont) asks of a tile: plain, bounded, whole-line -- what recurrenceForm sends to the aligned
 	// form -- with a new spectrum in every hop (the rows of a later tile then never read the carried feed-forward state)
 	bool continuousCapable() const { return anyHop && plain() && !randomTimeFactor && !startBin && !preAnalysed && !reusedSpectrum; }
-	// what a TWISTED tile asks of its hops (the batch's side of the condition: Batch::runTilesRange): the same, and
+	// what a TWISTED tile asks of its hops (the batch's side of the condition: recurrenceForm): the same, and
 	// every hop analyses both of its windows in this run
 	bool twistCapable() const { return continuousCapable() && newSpectrum && !plainPrev; }
 };

@@ -1,5 +1,6 @@
 // K3 fused, mono / stereo: the bin recurrence and its record producers in one kernel (kVocoder; ACROSS form for single-hop tiles) and its launchers.
 #include "smst_vocoder_common.h"
+#include "smst_recurrence_form.h"
 
 namespace smst {
 
@@ -519,27 +520,53 @@ __device__ __forceinline__ void vocoderProduceAligned(const DevBatch &d, int s, 
 // output: no skew (lag 0), no DPP, M steps per launch.  kVocoderOne runs one chain per WAVE (64 lanes computing the same
 // values); at 4096 streams that is four chain waves per SIMD and 1.57 ms per hop quantum.  Same records (computeRecord with FOLD0), same
 // step (wavefrontBlock).
-// ALIGNED (with STAGED): the line-aligned producers and a wavefront lag of 8 bins (vocoderProduceAligned).
-// TWISTED (with ALIGNED): the tile's Xprev rows hold the finished previous-hop twists (the host decides it per tile: Batch::runTilesRange).
-template <int CH, bool PLAIN, int L, bool STAGED, bool ROTL = false, bool ACROSS = false, bool ALIGNED = false, bool TWISTED = false>
+//
+// The producers of a kVocoder instantiation; the enumerators are the valid combinations.  GATHER: computeRecord from HBM, ACROSS: the same with rows
+// that are streams -- _ROTL (mapped tiles): the hop rotation table in LDS beside the rings.  STAGED: per-row windows in LDS, lag L + 1
+// (vocoderProduceStaged).  ALIGNED: the line-aligned producers and a wavefront lag of 8 bins (vocoderProduceAligned) -- _TWISTED: the tile's Xprev rows
+// hold the finished previous-hop twists (the host decides it per tile: recurrenceForm).
+enum class VocProducers { GATHER, GATHER_ROTL, ACROSS, ACROSS_ROTL, STAGED, ALIGNED, ALIGNED_TWISTED };
+constexpr bool vocAligned(VocProducers p) { return p == VocProducers::ALIGNED || p == VocProducers::ALIGNED_TWISTED; }
+constexpr bool vocTwisted(VocProducers p) { return p == VocProducers::ALIGNED_TWISTED; }
+constexpr bool vocStaged(VocProducers p) { return p == VocProducers::STAGED || vocAligned(p); } // records from operands parked in LDS (plainRecord), eight producer waves
+constexpr bool vocAcross(VocProducers p) { return p == VocProducers::ACROSS || p == VocProducers::ACROSS_ROTL; }
+constexpr bool vocRotInLds(VocProducers p) { return p == VocProducers::GATHER_ROTL || p == VocProducers::ACROSS_ROTL; }
+
+// kVocoder's LDS, in order.  bytes(M): with the hop rotation table of M bins behind the rings (_ROTL; the staged kernels keep their windows there)
+template <int CH, int L, VocProducers P>
+struct VocoderLds {
+	static constexpr int NCH = (9 + 3*CH + 3)/4, NB = vocStaged(P) ? kVocBlocksStaged : kVocBlocks;
+	static constexpr int OB = vocAligned(P) ? kVocOutBlocksAligned : kVocOutBlocks; // result ring blocks
+	static constexpr size_t recs = 0;                                                                 // float4 [(slot*BS + st)*NCH + j][64 lanes]
+	static constexpr size_t sync = recs + (size_t)NB*kVocBlockSteps*NCH*64*sizeof(float4);            // int [16]: [0..NB) units produced per slot, [NB] blocks consumed, [NB+1] result blocks ready, [NB+2] result blocks written
+	static constexpr size_t rowClass = sync + 16*sizeof(int);                                         // int [2][64]: the writer's two classes of rows
+	static constexpr size_t hops = rowClass + 128*sizeof(int);                                        // HopDesc [64]: the tile's hop descriptors
+	static constexpr size_t outRing = hops + 64*sizeof(HopDesc);                                      // float2 [OB][BS][CH][kVocOutPitch]: results on their way to HBM
+	static constexpr size_t tail = outRing + (size_t)OB*kVocBlockSteps*CH*kVocOutPitch*sizeof(float2); // float2: [M] hop rotation table, or the producers' buffers [kVocStagedProducers][perProducer]
+	static constexpr size_t perProducer = vocAligned(P) ? AlignGeom<CH, L>::PER_PRODUCER : (vocStaged(P) ? StageGeom<CH, L>::ROWS*StageGeom<CH, L>::ROWLEN : 0);
+	static constexpr size_t fixedBytes = tail + kVocStagedProducers*perProducer*sizeof(float2);
+	static_assert(fixedBytes <= kLdsBytesPerCU, "the rings and the producers' buffers fit a CU's LDS");
+	static constexpr size_t bytes(int M = 0) { return fixedBytes + (size_t)M*sizeof(float2); }
+};
+
+template <int CH, bool PLAIN, int L, VocProducers P>
 __global__ __launch_bounds__(64*kVocWaves) __attribute__((amdgpu_waves_per_eu(4, 4))) void kVocoder(DevBatch d, int sBase, int hopBase, int acrossRows, int acrossStreams) {
+	constexpr bool STAGED = vocStaged(P), ROTL = vocRotInLds(P), ACROSS = vocAcross(P), ALIGNED = vocAligned(P), TWISTED = vocTwisted(P);
 	static_assert(!STAGED || (PLAIN && L <= 5), "staged producers: identity map, bounded windows");
-	static_assert(!ALIGNED || (STAGED && L <= 4), "line-aligned producers: windows within the two lines around a row's bins");
-	static_assert(!ACROSS || !STAGED, "rows that are streams gather their operands");
-	static_assert(!TWISTED || ALIGNED, "only the line-aligned producers take the twist ready-made");
-	static_assert(!ROTL || (!PLAIN && !STAGED), "the LDS copy of the rotation table serves the gathering producers of mapped tiles");
-	constexpr int NF = 9 + 3*CH, NCH = (NF + 3)/4, BS = kVocBlockSteps, NB = STAGED ? kVocBlocksStaged : kVocBlocks;
+	static_assert(!ALIGNED || L <= 4, "line-aligned producers: windows within the two lines around a row's bins");
+	static_assert(!ROTL || !PLAIN, "the LDS copy of the rotation table serves the gathering producers of mapped tiles");
+	using Lds = VocoderLds<CH, L, P>;
+	constexpr int NCH = Lds::NCH, BS = kVocBlockSteps, NB = Lds::NB;
 	constexpr int NP = STAGED ? kVocStagedProducers : kVocWaves - 2;
 	constexpr int lag = ACROSS ? 0 : (ALIGNED ? 8 : L + 1);
-	constexpr int OB = ALIGNED ? kVocOutBlocksAligned : kVocOutBlocks; // result ring blocks
+	constexpr int OB = Lds::OB;
 	static_assert(BS == 8 && L >= 1 && L <= 7 && lag <= 8, "history registers are indexed by step & 7");
 	extern __shared__ __attribute__((aligned(16))) unsigned char smemRaw[];
-	float4 *recs = reinterpret_cast<float4 *>(smemRaw);                 // [(slot*BS + st)*NCH + j][64 lanes]
-	volatile int *sync = reinterpret_cast<volatile int *>(recs + NB*BS*NCH*64); // [0..NB) units produced, [NB] blocks consumed
-	int *rowClass = const_cast<int *>(sync) + 16;                                  // [2][64]: the writer's two classes of rows
-	HopDesc *hopsLds = reinterpret_cast<HopDesc *>(rowClass + 128);                // the tile's 64 hop descriptors
-	float2 *outRing = reinterpret_cast<float2 *>(hopsLds + 64);                    // [OB][BS][CH][kVocOutPitch]: results on their way to HBM
-	// sync words: [0..NB) units produced per slot, [NB] blocks consumed, [NB+1] result blocks ready, [NB+2] result blocks written
+	float4 *recs = reinterpret_cast<float4 *>(smemRaw + Lds::recs);
+	volatile int *sync = reinterpret_cast<volatile int *>(smemRaw + Lds::sync);
+	int *rowClass = reinterpret_cast<int *>(smemRaw + Lds::rowClass);
+	HopDesc *hopsLds = reinterpret_cast<HopDesc *>(smemRaw + Lds::hops);
+	float2 *outRing = reinterpret_cast<float2 *>(smemRaw + Lds::outRing);
 
 	// rows of the workgroup: hops 0 .. nh-1 of stream s, or (ACROSS) hop 0 of streams s .. s+nh-1
 	const int s = ACROSS ? blockIdx.x*acrossRows : blockIdx.x, sg = sBase + s;
@@ -569,7 +596,7 @@ __global__ __launch_bounds__(64*kVocWaves) __attribute__((amdgpu_waves_per_eu(4,
 			hopsLds[threadIdx.x] = d.hops[(size_t)sg*d.hopStride + hopBase + threadIdx.x];
 		}
 	}
-	float2 *rotLds = outRing + (size_t)OB*BS*CH*kVocOutPitch; // [M] hop rotation table (ROTL; the staged kernels keep their windows here)
+	float2 *rotLds = reinterpret_cast<float2 *>(smemRaw + Lds::tail); // [M] hop rotation table (ROTL; the staged kernels keep their windows here)
 	if constexpr (ROTL) {
 		for (int i = threadIdx.x; i < M; i += blockDim.x) rotLds[i] = d.rot[i];
 	}
@@ -638,16 +665,11 @@ __global__ __launch_bounds__(64*kVocWaves) __attribute__((amdgpu_waves_per_eu(4,
 		// on the SIMD that holds only two producers (waves 3, 7): recurrence 0.97 -> 0.95 ms in place, step -0.12 ms
 		if (STAGED && ALIGNED && pIndex < NP) pIndex = (pIndex == 0) ? 2 : ((pIndex == 2) ? 0 : pIndex);
 		if (pIndex >= NP) return;
-		if constexpr (ALIGNED) {
-			using G = AlignGeom<CH, L>;
-			float2 *sbuf = outRing + (size_t)OB*BS*CH*kVocOutPitch + (size_t)pIndex*G::PER_PRODUCER;
-			if (pIndex == 0) vocoderProduceAligned<CH, L, NB, true, TWISTED>(d, s, sg, nh, pIndex, k, totalBlocks, recs, sync, hopsLds, sbuf, stOut);
+		if constexpr (STAGED) {
+			float2 *sbuf = reinterpret_cast<float2 *>(smemRaw + Lds::tail) + (size_t)pIndex*Lds::perProducer;
+			if constexpr (!ALIGNED) vocoderProduceStaged<CH, L, NB, NP>(d, s, sg, nh, pIndex, k, totalBlocks, recs, sync, hopsLds, sbuf, stOut);
+			else if (pIndex == 0) vocoderProduceAligned<CH, L, NB, true, TWISTED>(d, s, sg, nh, pIndex, k, totalBlocks, recs, sync, hopsLds, sbuf, stOut);
 			else vocoderProduceAligned<CH, L, NB, false, TWISTED>(d, s, sg, nh, pIndex, k, totalBlocks, recs, sync, hopsLds, sbuf, stOut);
-			return;
-		} else if constexpr (STAGED) {
-			using G = StageGeom<CH, L>;
-			float2 *sbuf = outRing + (size_t)OB*BS*CH*kVocOutPitch + (size_t)pIndex*G::ROWS*G::ROWLEN;
-			vocoderProduceStaged<CH, L, NB, NP>(d, s, sg, nh, pIndex, k, totalBlocks, recs, sync, hopsLds, sbuf, stOut);
 			return;
 		}
 		if (!ACROSS && d.vocWide) {
@@ -745,106 +767,107 @@ __global__ __launch_bounds__(64*kVocWaves) __attribute__((amdgpu_waves_per_eu(4,
 }
 
 // ------------------------------------------------------------------------------------------------------
-// host-side launchers
+// host side: which form a tile takes (smst_recurrence_form.h), and the one launcher of the recurrence
 // ------------------------------------------------------------------------------------------------------
-// ... and the fused producer/consumer recurrence
-// Whether a plain, bounded mono / stereo tile takes the line-aligned producers (fp16 state: the staged producers).  The host asks too: only such
-// a tile can be a twisted one (Batch::runTilesRange)
-bool vocoderAlignedApplies(const DevBatch &d) {
+// The geometries of the forms.  (Other geometries / more channels: kPredictB + kChain, records through HBM.)
+static bool fusedSupported(const DevBatch &d) { return d.C <= kMaxFusedChannels && d.lag == d.L + 1 && d.L >= 2 && d.L <= (d.C <= 2 ? 7 : 5); }
+// single-hop tiles (every stream fires at most one hop): kVocoderOne.  Same geometries as the fused 3-8 channel kernel.
+static bool singleHopSupported(const DevBatch &d) { return d.C <= kMaxFusedChannels && d.lag == d.L + 1 && d.L >= 2 && d.L <= 5; }
+static bool acrossSupported(const DevBatch &d) { return d.C <= 2 && d.lag == d.L + 1 && d.L >= 2 && d.L <= 5; }
+// Line-aligned producers where they were measured to pay: L = 4 (presetDefault at 48 / 96 kHz: step 14.9 -> 14.5 ms).  At L = 3 (presetCheaper)
+// the 8-bin lag costs 9 % more wavefront steps than lag 4 and the two forms tie (10.75 / 10.80 ms per step), so that geometry stays on the staged
+// producers; SMST_ALIGN_ALL=1 takes the aligned form wherever it is valid (L <= 4), for the A/B.  fp16 state: the staged producers.
+static bool vocoderAlignedApplies(const DevBatch &d) {
 	return d.C <= 2 && d.L >= 2 && d.L <= 4 && !d.noStage && !d.noAlign && d.M%16 == 0 && !d.halfState && (d.L == 4 || d.alignAll);
 }
-// Whether some wave of a launch of the aligned kernel runs interior blocks (vocoderProduceAligned): the form is enabled, a stream of the tile has
-// a whole producer wave of hops (rows 0..7), and the geometry leaves a pair of blocks between the edges
-static bool vocoderInteriorApplies(const DevBatch &d) {
-	return d.vocInterior && d.tileMaxHops >= 8 && kVocInteriorFirst + 1 <= vocInteriorLast(d.M);
+// the continuous wavefront: the geometries of the line-aligned producers (mono / stereo, L <= 4, M a multiple of 16, fp32 state)
+// (M >= 1024: a period of at least 128 blocks -- a launch then sees two tiles per row at most, and row 0 reads lane 63's rows long after they were stored)
+static bool continuousSupported(const DevBatch &d) {
+	return d.C <= 2 && d.L >= 2 && d.L <= 4 && d.lag == d.L + 1 && d.M%16 == 0 && d.M >= 1024 && !d.halfState && !d.noStage && !d.noAlign;
 }
-template <int CH, int L>
-static void launchVocoderTL(const DevBatch &d, int sBase, int nStreams, int hopBase, bool plain, bool bounded, bool twisted, hipStream_t st) {
-	constexpr int NCH = (9 + 3*CH + 3)/4;
-	const size_t fixed = 64 + 128*sizeof(int) + 64*sizeof(HopDesc) + (size_t)kVocOutBlocks*kVocBlockSteps*CH*kVocOutPitch*sizeof(float2);
-	const size_t lds = (size_t)kVocBlocks*kVocBlockSteps*NCH*64*sizeof(float4) + fixed;
-	// line-aligned producers where they were measured to pay: L = 4 (presetDefault at 48 / 96 kHz: step 14.9 -> 14.5 ms).  At L = 3
-	// (presetCheaper) the 8-bin lag costs 9 % more wavefront steps than lag 4 and the two forms tie (10.75 / 10.80 ms per step), so that
-	// geometry stays on the staged producers; SMST_ALIGN_ALL=1 takes the aligned form wherever it is valid (L <= 4), for the A/B.
-	if constexpr (L <= 4) {
-		if (plain && bounded && vocoderAlignedApplies(d)) {
-			using G = AlignGeom<CH, L>;
-			const size_t fixedA = 64 + 128*sizeof(int) + 64*sizeof(HopDesc) + (size_t)kVocOutBlocksAligned*kVocBlockSteps*CH*kVocOutPitch*sizeof(float2);
-			const size_t ldsAligned = (size_t)kVocBlocksStaged*kVocBlockSteps*NCH*64*sizeof(float4) + fixedA + (size_t)kVocStagedProducers*G::PER_PRODUCER*sizeof(float2);
-			if (twisted) hipLaunchKernelGGL((kVocoder<CH, true, L, true, false, false, true, true>), dim3(nStreams), dim3(64*kVocWaves), ldsAligned, st, d, sBase, hopBase, 0, 0);
-			else hipLaunchKernelGGL((kVocoder<CH, true, L, true, false, false, true>), dim3(nStreams), dim3(64*kVocWaves), ldsAligned, st, d, sBase, hopBase, 0, 0);
-			countLaunch(LK_VOC_ALIGNED); // (either form)
-			if (twisted) countLaunch(LK_VOC_TWISTED);
-			if (vocoderInteriorApplies(d)) countLaunch(LK_VOC_INTERIOR);
-			return;
-		}
+// mapped tiles, gathering producers: the hop rotation table beside the rings when the CU's 160 KB hold both (presetDefault: 3073 bins, 24 KB)
+static bool rotationTableFitsLds(const DevBatch &d) { // (L does not enter the gathering layout)
+	return (d.C == 1 ? VocoderLds<1, 2, VocProducers::GATHER_ROTL>::bytes(d.M) : VocoderLds<2, 2, VocProducers::GATHER_ROTL>::bytes(d.M)) <= kLdsBytesPerCU;
+}
+
+RecurrenceForm recurrenceForm(const DevBatch &d, const TileSummary &th, int tileHops, int nStreams, bool pendingRun, const FormSwitches &sw) {
+	using K = RecurrenceKernel;
+	RecurrenceForm f{K::CHAIN_UNFUSED, false, false, false};
+	if (!fusedSupported(d) || sw.noFuse) return f;
+	const bool plain = th.plain();
+	if (tileHops == 1 && singleHopSupported(d) && !sw.noSingleHop) {
+		// (startBin: a block that a flush() interrupted inside its main prediction, HopDesc.startBin > 0 -- not with rows that are streams)
+		f.kernel = (!sw.noAcross && acrossSupported(d) && !th.startBin) ? K::ACROSS : K::ONE;
+		f.rotInLds = f.kernel == K::ACROSS && !plain && rotationTableFitsLds(d);
+		return f;
 	}
-	if constexpr (L <= 5) {
-		if (plain && bounded && !d.noStage) {
-			using G = StageGeom<CH, L>;
-			const size_t ldsStaged = (size_t)kVocBlocksStaged*kVocBlockSteps*NCH*64*sizeof(float4) + fixed + (size_t)kVocStagedProducers*G::ROWS*G::ROWLEN*sizeof(float2);
-			hipLaunchKernelGGL((kVocoder<CH, true, L, true>), dim3(nStreams), dim3(64*kVocWaves), ldsStaged, st, d, sBase, hopBase, 0, 0);
-			countLaunch(LK_VOC_STAGED);
-			return;
-		}
+	if (d.C > 2) { f.kernel = K::MANY; return f; }
+	// bounded: no random time factors in the tile, and no start bin -- every form that forms its records through computeRecord honours it (all-zero
+	// records below the start bin); the staged / line-aligned producers do not go through it, so such a tile takes the gathering form
+	const bool bounded = plain && !th.randomTimeFactor && !th.startBin;
+	if (bounded && vocoderAlignedApplies(d)) {
+		f.kernel = K::ALIGNED;
+		// A TWISTED tile: every hop analyses both of its windows in this run and the pair teams apply.  Never in a run of blocks in
+		// flight; SMST_VOC_TWIST=0: no tile; SMST_CONTINUOUS: none either (the wavefront across tiles reads Band.prevInput)
+		f.twisted = d.vocTwist && !sw.continuous && !pendingRun && th.twistCapable() && analyseTwistApplies(d, nStreams, tileHops);
+		// some wave of the launch runs interior blocks (vocoderProduceAligned): the form is enabled, a stream of the tile has a whole producer wave of hops
+		// (rows 0..7), and the geometry leaves a pair of blocks between the edges
+		f.interior = d.vocInterior && th.maxHops >= 8 && kVocInteriorFirst + 1 <= vocInteriorLast(d.M);
+	} else if (bounded && d.L <= 5 && !d.noStage) f.kernel = K::STAGED;
+	else {
+		f.kernel = K::GATHER;
+		f.rotInLds = !plain && rotationTableFitsLds(d);
 	}
-	countLaunch(LK_VOC_GATHER);
-	if (plain) { hipLaunchKernelGGL((kVocoder<CH, true, L, false>), dim3(nStreams), dim3(64*kVocWaves), lds, st, d, sBase, hopBase, 0, 0); return; }
-	// mapped tiles: the hop rotation table beside the rings when the CU's 160 KB hold it (presetDefault: 3073 bins, 24 KB)
-	const size_t ldsRot = lds + (size_t)d.M*sizeof(float2);
-	if (ldsRot <= (size_t)160*1024) hipLaunchKernelGGL((kVocoder<CH, false, L, false, true>), dim3(nStreams), dim3(64*kVocWaves), ldsRot, st, d, sBase, hopBase, 0, 0);
-	else hipLaunchKernelGGL((kVocoder<CH, false, L, false>), dim3(nStreams), dim3(64*kVocWaves), lds, st, d, sBase, hopBase, 0, 0);
+	return f;
 }
-// single-hop tiles, mono / stereo: rows of the recurrence wave are streams (kVocoder ACROSS).  Rows per workgroup: enough to cover the
-// streams with one workgroup per CU (a multiple of 8: a producer pass is 8 rows x 8 steps), at most 64
-template <int CH, int L>
-static void launchVocoderAcrossL(const DevBatch &d, int sBase, int nStreams, int hopBase, bool plain, hipStream_t st) {
-	constexpr int NCH = (9 + 3*CH + 3)/4;
-	const size_t fixed = 64 + 128*sizeof(int) + 64*sizeof(HopDesc) + (size_t)kVocOutBlocks*kVocBlockSteps*CH*kVocOutPitch*sizeof(float2);
-	const size_t lds = (size_t)kVocBlocks*kVocBlockSteps*NCH*64*sizeof(float4) + fixed;
-	int rows = ((nStreams + 255)/256 + 7) & ~7;
-	rows = rows < 8 ? 8 : (rows > 64 ? 64 : rows);
-	const dim3 grid((nStreams + rows - 1)/rows);
-	if (plain) { hipLaunchKernelGGL((kVocoder<CH, true, L, false, false, true>), grid, dim3(64*kVocWaves), lds, st, d, sBase, hopBase, rows, nStreams); return; }
-	const size_t ldsRot = lds + (size_t)d.M*sizeof(float2);
-	if (ldsRot <= (size_t)160*1024) hipLaunchKernelGGL((kVocoder<CH, false, L, false, true, true>), grid, dim3(64*kVocWaves), ldsRot, st, d, sBase, hopBase, rows, nStreams);
-	else hipLaunchKernelGGL((kVocoder<CH, false, L, false, false, true>), grid, dim3(64*kVocWaves), lds, st, d, sBase, hopBase, rows, nStreams);
+bool formReachable(const DevBatch &d, const FormSwitches &sw, RecurrenceKernel kernel) {
+	const bool fused = fusedSupported(d) && !sw.noFuse;
+	if (kernel == RecurrenceKernel::CHAIN_UNFUSED) return !fused;
+	if (kernel == RecurrenceKernel::ONE) return fused && singleHopSupported(d) && !sw.noSingleHop;
+	return fused && sw.continuous && continuousSupported(d); // CONTINUOUS
 }
-template <int CH>
-static void launchVocoderAcrossT(const DevBatch &d, int sBase, int nStreams, int hopBase, bool plain, hipStream_t st) {
-	switch (d.L) {
-	case 2: launchVocoderAcrossL<CH, 2>(d, sBase, nStreams, hopBase, plain, st); break;
-	case 3: launchVocoderAcrossL<CH, 3>(d, sBase, nStreams, hopBase, plain, st); break;
-	case 4: launchVocoderAcrossL<CH, 4>(d, sBase, nStreams, hopBase, plain, st); break;
-	default: launchVocoderAcrossL<CH, 5>(d, sBase, nStreams, hopBase, plain, st); break;
+
+// kVocoder<CH, PLAIN, L, P>, one workgroup per stream -- or (ACROSS) per `rows` streams: enough to cover the streams with one workgroup per CU
+// (a multiple of 8: a producer pass is 8 rows x 8 steps), at most 64
+template <int CH, bool PLAIN, int L, VocProducers P>
+static void launchVocoderAs(const DevBatch &d, int sBase, int nStreams, int hopBase, hipStream_t st) {
+	const size_t lds = VocoderLds<CH, L, P>::bytes(vocRotInLds(P) ? d.M : 0);
+	if constexpr (vocAcross(P)) {
+		int rows = ((nStreams + 255)/256 + 7) & ~7;
+		rows = rows < 8 ? 8 : (rows > 64 ? 64 : rows);
+		hipLaunchKernelGGL((kVocoder<CH, PLAIN, L, P>), dim3((nStreams + rows - 1)/rows), dim3(64*kVocWaves), lds, st, d, sBase, hopBase, rows, nStreams);
+	} else {
+		hipLaunchKernelGGL((kVocoder<CH, PLAIN, L, P>), dim3(nStreams), dim3(64*kVocWaves), lds, st, d, sBase, hopBase, 0, 0);
 	}
 }
-bool acrossSupported(const DevBatch &d) { return d.C <= 2 && d.lag == d.L + 1 && d.L >= 2 && d.L <= 5; }
-void launchVocoderAcross(const DevBatch &d, int sBase, int nStreams, int hopBase, bool plain, hipStream_t st) {
-	countLaunch(LK_VOC_ACROSS);
-	if (d.C == 1) launchVocoderAcrossT<1>(d, sBase, nStreams, hopBase, plain, st);
-	else launchVocoderAcrossT<2>(d, sBase, nStreams, hopBase, plain, st);
+// the gathering forms: plain; mapped with the rotation table in LDS; mapped without
+template <int CH, int L, VocProducers P, VocProducers P_ROTL>
+static void launchVocoderGathering(const DevBatch &d, bool plain, bool rotInLds, int sBase, int nStreams, int hopBase, hipStream_t st) {
+	if (plain) launchVocoderAs<CH, true, L, P>(d, sBase, nStreams, hopBase, st);
+	else if (rotInLds) launchVocoderAs<CH, false, L, P_ROTL>(d, sBase, nStreams, hopBase, st);
+	else launchVocoderAs<CH, false, L, P>(d, sBase, nStreams, hopBase, st);
 }
-template <int CH>
-static void launchVocoderT(const DevBatch &d, int sBase, int nStreams, int hopBase, bool plain, bool bounded, bool twisted, hipStream_t st) {
-	switch (d.L) { // longVerticalStep = round(fftSamples/interval): 4 (presetDefault @48k), 5 (@44.1k), 3 (presetCheaper)
-	case 3: launchVocoderTL<CH, 3>(d, sBase, nStreams, hopBase, plain, bounded, twisted, st); break;
-	case 4: launchVocoderTL<CH, 4>(d, sBase, nStreams, hopBase, plain, bounded, twisted, st); break;
-	case 5: launchVocoderTL<CH, 5>(d, sBase, nStreams, hopBase, plain, bounded, twisted, st); break;
-	case 2: launchVocoderTL<CH, 2>(d, sBase, nStreams, hopBase, plain, bounded, twisted, st); break;
-	case 6: launchVocoderTL<CH, 6>(d, sBase, nStreams, hopBase, plain, bounded, twisted, st); break;
-	default: launchVocoderTL<CH, 7>(d, sBase, nStreams, hopBase, plain, bounded, twisted, st); break; // only reached with L == 7 (see fusedSupported)
-	}
-}
-bool fusedSupported(const DevBatch &d) {
-	return d.C <= kMaxFusedChannels && d.lag == d.L + 1 && d.L >= 2 && d.L <= (d.C <= 2 ? 7 : 5); // other geometries / more channels: kPredictB + kChain (records through HBM)
-}
-void launchVocoder(const DevBatch &d, int sBase, int nStreams, int hopBase, bool plain, bool bounded, bool twisted, hipStream_t st) {
-	switch (d.C) {
-	case 1: launchVocoderT<1>(d, sBase, nStreams, hopBase, plain, bounded, twisted, st); return;
-	case 2: launchVocoderT<2>(d, sBase, nStreams, hopBase, plain, bounded, twisted, st); return;
-	default: launchVocoderMany(d, sBase, nStreams, hopBase, plain, st); return; // 3-8 channels: kVocoderN
-	}
+
+void launchRecurrence(const DevBatch &d, const RecurrenceForm &form, int sBase, int nStreams, int hopBase, bool plain, hipStream_t st) {
+	using K = RecurrenceKernel;
+	using P = VocProducers;
+	static const LaunchKind counter[] = {LK_CHAIN_UNFUSED, LK_VOC_ONE, LK_VOC_ACROSS, LK_VOC_N, LK_VOC_GATHER, LK_VOC_STAGED, LK_VOC_ALIGNED}; // (RecurrenceKernel's order)
+	countLaunch(counter[int(form.kernel)]);
+	if (form.twisted) countLaunch(LK_VOC_TWISTED);
+	if (form.interior) countLaunch(LK_VOC_INTERIOR);
+	if (form.kernel == K::CHAIN_UNFUSED) return launchChain(d, sBase, nStreams, hopBase, st);
+	if (form.kernel == K::ONE) return launchVocoderOne(d, sBase, nStreams, hopBase, plain, st);
+	if (form.kernel == K::MANY) return launchVocoderMany(d, sBase, nStreams, hopBase, plain, st);
+	// mono / stereo; longVerticalStep = round(fftSamples/interval): 4 (presetDefault @48k), 5 (@44.1k), 3 (presetCheaper); ACROSS: 2..5, GATHER: 2..7
+	withIntIn<1, 2>(d.C, [&](auto ch) {
+		constexpr int CH = decltype(ch)::value;
+		if (form.kernel == K::ACROSS) withIntIn<2, 5>(d.L, [&](auto l) { launchVocoderGathering<CH, decltype(l)::value, P::ACROSS, P::ACROSS_ROTL>(d, plain, form.rotInLds, sBase, nStreams, hopBase, st); });
+		else if (form.kernel == K::GATHER) withIntIn<2, 7>(d.L, [&](auto l) { launchVocoderGathering<CH, decltype(l)::value, P::GATHER, P::GATHER_ROTL>(d, plain, form.rotInLds, sBase, nStreams, hopBase, st); });
+		else if (form.kernel == K::STAGED) withIntIn<2, 5>(d.L, [&](auto l) { launchVocoderAs<CH, true, decltype(l)::value, P::STAGED>(d, sBase, nStreams, hopBase, st); });
+		else withIntIn<2, 4>(d.L, [&](auto l) { withFlag(form.twisted, [&](auto tw) {
+			launchVocoderAs<CH, true, decltype(l)::value, decltype(tw)::value ? P::ALIGNED_TWISTED : P::ALIGNED>(d, sBase, nStreams, hopBase, st);
+		}); });
+	});
 }
 
 } // namespace smst

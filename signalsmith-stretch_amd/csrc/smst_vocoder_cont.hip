@@ -286,17 +286,30 @@ __device__ __forceinline__ void contProduce(const DevBatch &d, const ContArgs &a
 // SIMD w % 4) -- the gathering form's other six waves have no work here, and three waves per SIMD leave every wave 168 registers instead
 // of 128 (the first build of this kernel spilled 17 of them to scratch: the row cursors and hop bookkeeping of the continuous form).
 constexpr int kContWaves = 12;
+// kVocoderCont's LDS, in order
+template <int CH, int L>
+struct ContLds {
+	static constexpr int NCH = (9 + 3*CH + 3)/4;
+	static constexpr size_t recs = 0;                                                                                   // float4 [(slot*BS + st)*NCH + j][64 lanes]
+	static constexpr size_t sync = recs + (size_t)kVocBlocksStaged*kVocBlockSteps*NCH*64*sizeof(float4);                // int [16]: [0..NB) units produced per slot, [NB] blocks consumed, [NB+1] result blocks ready,
+	                                                                                                                    // [NB+2] result blocks written, [NB+3] blocks whose stores have completed -- absolute block numbers
+	static constexpr size_t rowInfo = sync + 16*sizeof(int);                                                            // RowInfo [tile parity][64]
+	static constexpr size_t outRing = rowInfo + 128*sizeof(RowInfo);                                                    // float2 [OB][BS][CH][kVocOutPitch]
+	static constexpr size_t lines = outRing + (size_t)kVocOutBlocksAligned*kVocBlockSteps*CH*kVocOutPitch*sizeof(float2); // float2 [kVocStagedProducers][PER_PRODUCER]: the producers' line buffers
+	static constexpr size_t bytes = lines + (size_t)kVocStagedProducers*AlignGeom<CH, L>::PER_PRODUCER*sizeof(float2);
+	static_assert(bytes <= kLdsBytesPerCU, "the rings and the line buffers fit a CU's LDS");
+};
 template <int CH, int L>
 __global__ __launch_bounds__(64*kContWaves) __attribute__((amdgpu_waves_per_eu(3, 3))) void kVocoderCont(DevBatch d, ContArgs a, int sBase) {
 	using G = AlignGeom<CH, L>;
 	constexpr int NF = 9 + 3*CH, NCH = (NF + 3)/4, BS = kVocBlockSteps, NB = kVocBlocksStaged, NP = kVocStagedProducers, OB = kVocOutBlocksAligned;
+	using Lds = ContLds<CH, L>;
 	extern __shared__ __attribute__((aligned(16))) unsigned char smemRaw[];
-	float4 *recs = reinterpret_cast<float4 *>(smemRaw);                            // [(slot*BS + st)*NCH + j][64 lanes]
-	volatile int *sync = reinterpret_cast<volatile int *>(recs + NB*BS*NCH*64);    // [0..NB) units produced per slot, [NB] blocks consumed, [NB+1] result blocks ready,
-	                                                                               // [NB+2] result blocks written, [NB+3] blocks whose stores have completed -- absolute block numbers
-	RowInfo *rowInfo = reinterpret_cast<RowInfo *>(const_cast<int *>(sync) + 16);  // [tile parity][64]
-	float2 *outRing = reinterpret_cast<float2 *>(rowInfo + 128);                   // [OB][BS][CH][kVocOutPitch]
-	float2 *lines = outRing + (size_t)OB*BS*CH*kVocOutPitch;                       // the producers' line buffers
+	float4 *recs = reinterpret_cast<float4 *>(smemRaw + Lds::recs);
+	volatile int *sync = reinterpret_cast<volatile int *>(smemRaw + Lds::sync);
+	RowInfo *rowInfo = reinterpret_cast<RowInfo *>(smemRaw + Lds::rowInfo);
+	float2 *outRing = reinterpret_cast<float2 *>(smemRaw + Lds::outRing);
+	float2 *lines = reinterpret_cast<float2 *>(smemRaw + Lds::lines);
 
 	const int s = blockIdx.x, sg = sBase + s;
 	const int M = d.M, P = a.period, ML = M >> 4;
@@ -437,32 +450,13 @@ __global__ __launch_bounds__(64*kContWaves) __attribute__((amdgpu_waves_per_eu(3
 // ------------------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------------------
-bool continuousSupported(const DevBatch &d) {
-	// (M >= 1024: a period of at least 128 blocks -- a launch then sees two tiles per row at most, and row 0 reads lane 63's rows long after they were stored)
-	return d.C <= 2 && d.L >= 2 && d.L <= 4 && d.lag == d.L + 1 && d.M%16 == 0 && d.M >= 1024 && !d.halfState && !d.noStage && !d.noAlign;
-}
 int continuousPeriod(const DevBatch &d) { return d.M/8 + 2; }
 
-template <int CH, int L>
-static void launchContL(const DevBatch &d, const ContArgs &a, int sBase, int nStreams, hipStream_t st) {
-	using G = AlignGeom<CH, L>;
-	constexpr int NCH = (9 + 3*CH + 3)/4;
-	const size_t lds = (size_t)kVocBlocksStaged*kVocBlockSteps*NCH*64*sizeof(float4) + 64 + 128*sizeof(RowInfo)
-	                   + (size_t)kVocOutBlocksAligned*kVocBlockSteps*CH*kVocOutPitch*sizeof(float2) + (size_t)kVocStagedProducers*G::PER_PRODUCER*sizeof(float2);
-	hipLaunchKernelGGL((kVocoderCont<CH, L>), dim3(nStreams), dim3(64*kContWaves), lds, st, d, a, sBase);
-}
-template <int CH>
-static void launchContT(const DevBatch &d, const ContArgs &a, int sBase, int nStreams, hipStream_t st) {
-	switch (d.L) {
-	case 2: launchContL<CH, 2>(d, a, sBase, nStreams, st); break;
-	case 3: launchContL<CH, 3>(d, a, sBase, nStreams, st); break;
-	default: launchContL<CH, 4>(d, a, sBase, nStreams, st); break;
-	}
-}
 void launchVocoderContinuous(const DevBatch &d, const ContArgs &a, int sBase, int nStreams, hipStream_t st) {
 	countLaunch(LK_VOC_CONT);
-	if (d.C == 1) launchContT<1>(d, a, sBase, nStreams, st);
-	else launchContT<2>(d, a, sBase, nStreams, st);
+	withIntIn<1, 2>(d.C, [&](auto ch) { withIntIn<2, 4>(d.L, [&](auto l) {
+		hipLaunchKernelGGL((kVocoderCont<ch.value, l.value>), dim3(nStreams), dim3(64*kContWaves), (ContLds<ch.value, l.value>::bytes), st, d, a, sBase);
+	}); });
 }
 
 } // namespace smst

@@ -39,11 +39,18 @@ __global__ __launch_bounds__(256) void kPredictA(DevBatch d, int sBase, int hopB
 // per row); the 512 records are transposed through LDS so that the stores to the skewed array are contiguous 1-KiB
 // rows (the scattered 16-byte stores of the first version ran at 1.3 TB/s and dominated the whole pipeline).
 // (Used for more than 2 channels; mono/stereo use the fused kVocoder below, which never writes records to HBM.)
+template <int CH>
+struct PredictBLds {
+	static constexpr int NCH = (recordFloats(CH) + 3)/4;
+	static constexpr size_t tile = 0; // float4 [(st*NCH + j)*65 + k]: 8 steps, 64 hops at a pitch of 65
+	static constexpr size_t bytes = tile + (size_t)8*NCH*65*sizeof(float4);
+	static_assert(bytes <= kLdsBytesPerCU, "the transposing tile fits a CU's LDS");
+};
 template <int CH, bool PLAIN>
 __global__ __launch_bounds__(256) void kPredictB(DevBatch d, int sBase, int hopBase) {
 	constexpr int NF = recordFloats(CH), NCH = (NF + 3)/4;
 	extern __shared__ __attribute__((aligned(16))) unsigned char smemRaw[];
-	float4 *tile = reinterpret_cast<float4 *>(smemRaw); // [(st*NCH + j)*65 + k]
+	float4 *tile = reinterpret_cast<float4 *>(smemRaw + PredictBLds<CH>::tile);
 	const int s = blockIdx.y, sg = sBase + s;
 	const int T0 = blockIdx.x*8;
 	const int M = d.M;
@@ -83,8 +90,9 @@ __global__ __launch_bounds__(64) void kChain(DevBatch d, int sBase, int hopBase)
 	constexpr int PD = 4; // prefetch depth (one wave per SIMD slot: the register file is not the limit)
 	extern __shared__ __attribute__((aligned(16))) unsigned char smemRaw[];
 	const int R = d.ringSlots, Rm = R - 1;
-	float2 *lds = reinterpret_cast<float2 *>(smemRaw); // ring [CH][R][64], then stage [CH][128]
-	const int stageBase = CH*R*64;                      // carried Band.output of the previous tile, 128-bin window
+	float2 *lds = reinterpret_cast<float2 *>(smemRaw); // ring [CH][R][64], then stage [CH][128] (chainLdsBytes, smst_device.h)
+	const int stageBase = CH*R*64;                      // carried Band.output of the previous tile, 128-bin window (spelled out: through a function
+	                                                    // shared with chainLdsBytes the compiler's code for kChain<2> came out five instructions longer)
 
 	const int s = blockIdx.x, sg = sBase + s, k = threadIdx.x;
 	const int nh = d.nHops[s];
@@ -192,6 +200,20 @@ __global__ __launch_bounds__(64) void kChain(DevBatch d, int sBase, int hopBase)
 // (vmcnt counts both on gfx9): 4.4 us per step for 8 channels.
 // ------------------------------------------------------------------------------------------------------
 constexpr int kVocNBlockSteps = 4, kVocNBlocks = 2, kVocNRing = 16;
+// kVocoderN's LDS, in order
+template <int CH>
+struct VocoderNLds {
+	static constexpr int NCH = (recordFloats(CH) + 3)/4;
+	static constexpr size_t recs = 0;                                                                   // float4 [(slot*BS + st)*NCH + j][64 lanes]
+	static constexpr size_t ring = recs + (size_t)kVocNBlocks*kVocNBlockSteps*NCH*64*sizeof(float4);    // float2 [CH][R bins][64 lanes]: Band.output of the last R bins of every hop
+	static constexpr size_t stage = ring + (size_t)CH*kVocNRing*64*sizeof(float2);                      // float2 [CH][128]: carried Band.output, 128-bin window
+	static constexpr size_t sync = stage + (size_t)CH*128*sizeof(float2);                               // int [16]: [0..NB) units produced, [NB] blocks consumed, [NB+1] result blocks ready, [NB+2] written
+	static constexpr size_t hops = sync + 16*sizeof(int);                                               // HopDesc [64]
+	static constexpr size_t rowClass = hops + 64*sizeof(HopDesc);                                       // int [4][64]: the writer's classes of rows (two for half lines, four for whole lines)
+	static constexpr size_t slabs = rowClass + 4*64*sizeof(int);                                        // float4 [6][16 rows][CH][2]: the whole-line writer's slabs (see the writer)
+	static constexpr size_t bytes = slabs + (size_t)6*16*CH*2*sizeof(float4);
+	static_assert(bytes <= kLdsBytesPerCU, "rings, stage and slabs fit a CU's LDS");
+};
 
 template <int CH, bool PLAIN, int L>
 __global__ __launch_bounds__(64*kVocWaves) __attribute__((amdgpu_waves_per_eu(4, 4))) void kVocoderN(DevBatch d, int sBase, int hopBase) {
@@ -200,13 +222,14 @@ __global__ __launch_bounds__(64*kVocWaves) __attribute__((amdgpu_waves_per_eu(4,
 	constexpr int lag = L + 1;
 	static_assert(CH >= 3 && CH <= kMaxFusedChannels && L >= 1 && L + BS < R, "ring depth: a slot is rewritten R bins later, the oldest tap is L bins back");
 	static_assert(NB == 2, "the wide producer passes fill both blocks of the ring");
+	using Lds = VocoderNLds<CH>;
 	extern __shared__ __attribute__((aligned(16))) unsigned char smemRaw[];
-	float4 *recs = reinterpret_cast<float4 *>(smemRaw);                  // [(slot*BS + st)*NCH + j][64 lanes]
-	float2 *ring = reinterpret_cast<float2 *>(recs + NB*BS*NCH*64);      // [CH][R bins][64 lanes]: Band.output of the last R bins of every hop
-	float2 *stage = ring + CH*R*64;                                      // [CH][128]: carried Band.output, 128-bin window
-	volatile int *sync = reinterpret_cast<volatile int *>(stage + CH*128); // [0..NB) units produced, [NB] blocks consumed, [NB+1] result blocks ready, [NB+2] written
-	HopDesc *hopsLds = reinterpret_cast<HopDesc *>(const_cast<int *>(sync) + 16);
-	int *rowClass = reinterpret_cast<int *>(hopsLds + 64);                 // [4][64]: the writer's classes of rows (two for half lines, four for whole lines), then its slabs
+	float4 *recs = reinterpret_cast<float4 *>(smemRaw + Lds::recs);
+	float2 *ring = reinterpret_cast<float2 *>(smemRaw + Lds::ring);
+	float2 *stage = reinterpret_cast<float2 *>(smemRaw + Lds::stage);
+	volatile int *sync = reinterpret_cast<volatile int *>(smemRaw + Lds::sync);
+	HopDesc *hopsLds = reinterpret_cast<HopDesc *>(smemRaw + Lds::hops);
+	int *rowClass = reinterpret_cast<int *>(smemRaw + Lds::rowClass);
 
 	const int s = blockIdx.x, sg = sBase + s;
 	const int nh = d.nHops[s];
@@ -239,7 +262,7 @@ __global__ __launch_bounds__(64*kVocWaves) __attribute__((amdgpu_waves_per_eu(4,
 				// is only 16 bins deep).  Six slabs of [16 rows][CH][4 bins] do: a line's first group waits three passes (three slabs in rotation),
 				// the second two (two), the third one -- and a pass reads the slabs it frees before it fills them (LDS operations of a wave
 				// execute in order).  24 KB at 8 channels, which the shorter records of round 6 left free.
-				float4 *slabs = reinterpret_cast<float4 *>(rowClass + 4*64);
+				float4 *slabs = reinterpret_cast<float4 *>(smemRaw + Lds::slabs);
 				constexpr int SL = 16*CH*2; // float4s per slab
 				{
 					int c0 = 0, c1 = 0, c2 = 0, c3 = 0; // (scalars: a counter array indexed by the class would live in scratch memory)
@@ -533,16 +556,29 @@ __global__ __launch_bounds__(64*kVocWaves) __attribute__((amdgpu_waves_per_eu(4,
 // Same records (computeRecord), same step (recurrenceOutputs) as kVocoder / kVocoderN.
 // ------------------------------------------------------------------------------------------------------
 constexpr int kVocOneBlock = 64;
+// kVocoderOne's LDS, in order
+template <int CH>
+struct VocoderOneLds {
+	static constexpr int NCH = (recordFloats(CH) + 3)/4;
+	static constexpr size_t recs = 0;                                                       // float4 [2 slots][step][NCH]
+	static constexpr size_t outRing = recs + (size_t)2*kVocOneBlock*NCH*sizeof(float4);     // float2 [2 blocks][CH][BS]: results on their way to HBM
+	static constexpr size_t stage = outRing + (size_t)2*CH*kVocOneBlock*sizeof(float2);     // float2 [CH][128]: carried Band.output, 128-bin window
+	static constexpr size_t sync = stage + (size_t)CH*128*sizeof(float2);                   // int [4]: [0] blocks produced, [1] blocks consumed (= result blocks ready)
+	static constexpr size_t hop = sync + 4*sizeof(int);                                     // HopDesc: the stream's one hop
+	static constexpr size_t bytes = hop + sizeof(HopDesc);
+	static_assert(bytes <= kLdsBytesPerCU, "two record blocks, results and stage fit a CU's LDS");
+};
 
 template <int CH, bool PLAIN, int L>
 __global__ __launch_bounds__(128) void kVocoderOne(DevBatch d, int sBase, int hopBase) {
 	constexpr int NF = recordFloats(CH), NCH = (NF + 3)/4, BS = kVocOneBlock, NB = 2;
+	using Lds = VocoderOneLds<CH>;
 	extern __shared__ __attribute__((aligned(16))) unsigned char smemRaw[];
-	float4 *recs = reinterpret_cast<float4 *>(smemRaw);                  // [slot][step][NCH]
-	float2 *outRing = reinterpret_cast<float2 *>(recs + NB*BS*NCH);      // [2 blocks][CH][BS]: results on their way to HBM
-	float2 *stage = outRing + 2*CH*BS;                                   // [CH][128]: carried Band.output, 128-bin window
-	volatile int *sync = reinterpret_cast<volatile int *>(stage + CH*128); // [0] blocks produced, [1] blocks consumed (= result blocks ready)
-	HopDesc *hopLds = reinterpret_cast<HopDesc *>(const_cast<int *>(sync) + 4);
+	float4 *recs = reinterpret_cast<float4 *>(smemRaw + Lds::recs);
+	float2 *outRing = reinterpret_cast<float2 *>(smemRaw + Lds::outRing);
+	float2 *stage = reinterpret_cast<float2 *>(smemRaw + Lds::stage);
+	volatile int *sync = reinterpret_cast<volatile int *>(smemRaw + Lds::sync);
+	HopDesc *hopLds = reinterpret_cast<HopDesc *>(smemRaw + Lds::hop);
 
 	const int s = blockIdx.x, sg = sBase + s;
 	if (d.nHops[s] == 0) return;
@@ -657,127 +693,34 @@ __global__ __launch_bounds__(128) void kVocoderOne(DevBatch d, int sBase, int ho
 }
 
 // ------------------------------------------------------------------------------------------------------
-// host-side launchers
+// host-side launchers (which of them a tile takes: recurrenceForm, smst_vocoder.hip)
 // ------------------------------------------------------------------------------------------------------
-template <int CH>
-static void launchPredictT(const DevBatch &d, int sBase, int nStreams, int hopBase, int tileHops, bool plain, bool passADone, hipStream_t st) {
-	const dim3 grid(divUp(d.M + d.lag*(d.T - 1), 8), nStreams);
-	const size_t lds = (size_t)8*((recordFloats(CH) + 3)/4)*65*sizeof(float4);
-	if (plain) {
-		hipLaunchKernelGGL((kPredictB<CH, true>), grid, dim3(256), lds, st, d, sBase, hopBase);
-	} else {
-		if (!passADone) hipLaunchKernelGGL(kPredictA, dim3(divUp(d.M, 256), tileHops, nStreams), dim3(256), 0, st, d, sBase, hopBase);
-		hipLaunchKernelGGL((kPredictB<CH, false>), grid, dim3(256), lds, st, d, sBase, hopBase);
-	}
-}
-// mono / stereo: pass A (only with a pitch map or formants) on the feed-forward stream ...
-void launchPredictFused(const DevBatch &d, int sBase, int nStreams, int hopBase, int tileHops, bool plain, bool passADone, hipStream_t st) {
+// pass A where the tile has a pitch map or formants and the feed kernels have not folded it in; then -- un-fused forms only (RecurrenceForm::fused:
+// the fused kernels' producers form the records) -- the records through HBM
+void launchPredict(const DevBatch &d, bool fused, int sBase, int nStreams, int hopBase, int tileHops, bool plain, bool passADone, hipStream_t st) {
 	if (!plain && !passADone) hipLaunchKernelGGL(kPredictA, dim3(divUp(d.M, 256), tileHops, nStreams), dim3(256), 0, st, d, sBase, hopBase);
-}
-template <int CH, int L>
-static void launchVocoderNL(const DevBatch &d, int sBase, int nStreams, int hopBase, bool plain, hipStream_t st) {
-	constexpr int NCH = (recordFloats(CH) + 3)/4;
-	const size_t lds = (size_t)kVocNBlocks*kVocNBlockSteps*NCH*64*sizeof(float4) + (size_t)CH*kVocNRing*64*sizeof(float2)
-	                   + (size_t)CH*128*sizeof(float2) + 64 + 64*sizeof(HopDesc) + 4*64*sizeof(int) + (size_t)6*16*CH*2*sizeof(float4);
-	if (plain) hipLaunchKernelGGL((kVocoderN<CH, true, L>), dim3(nStreams), dim3(64*kVocWaves), lds, st, d, sBase, hopBase);
-	else hipLaunchKernelGGL((kVocoderN<CH, false, L>), dim3(nStreams), dim3(64*kVocWaves), lds, st, d, sBase, hopBase);
-}
-template <int CH>
-static void launchVocoderN(const DevBatch &d, int sBase, int nStreams, int hopBase, bool plain, hipStream_t st) {
-	switch (d.L) { // longVerticalStep: 3 (presetCheaper), 4 / 5 (presetDefault at 48 / 44.1 kHz); fusedSupported(): 2 <= L <= 5 here
-	case 2: launchVocoderNL<CH, 2>(d, sBase, nStreams, hopBase, plain, st); break;
-	case 3: launchVocoderNL<CH, 3>(d, sBase, nStreams, hopBase, plain, st); break;
-	case 4: launchVocoderNL<CH, 4>(d, sBase, nStreams, hopBase, plain, st); break;
-	default: launchVocoderNL<CH, 5>(d, sBase, nStreams, hopBase, plain, st); break;
-	}
-}
-template <int CH, int L>
-static void launchVocoderOneL(const DevBatch &d, int sBase, int nStreams, int hopBase, bool plain, hipStream_t st) {
-	constexpr int NCH = (recordFloats(CH) + 3)/4;
-	const size_t lds = (size_t)2*kVocOneBlock*NCH*sizeof(float4) + (size_t)2*CH*kVocOneBlock*sizeof(float2) + (size_t)CH*128*sizeof(float2) + 16 + sizeof(HopDesc);
-	if (plain) hipLaunchKernelGGL((kVocoderOne<CH, true, L>), dim3(nStreams), dim3(128), lds, st, d, sBase, hopBase);
-	else hipLaunchKernelGGL((kVocoderOne<CH, false, L>), dim3(nStreams), dim3(128), lds, st, d, sBase, hopBase);
-}
-template <int CH>
-static void launchVocoderOneT(const DevBatch &d, int sBase, int nStreams, int hopBase, bool plain, hipStream_t st) {
-	switch (d.L) {
-	case 2: launchVocoderOneL<CH, 2>(d, sBase, nStreams, hopBase, plain, st); break;
-	case 3: launchVocoderOneL<CH, 3>(d, sBase, nStreams, hopBase, plain, st); break;
-	case 4: launchVocoderOneL<CH, 4>(d, sBase, nStreams, hopBase, plain, st); break;
-	default: launchVocoderOneL<CH, 5>(d, sBase, nStreams, hopBase, plain, st); break;
-	}
-}
-// single-hop tiles (every stream fires at most one hop): see kVocoderOne.  Same geometries as the fused 3-8 channel kernel.
-bool singleHopSupported(const DevBatch &d) { return d.C <= kMaxFusedChannels && d.lag == d.L + 1 && d.L >= 2 && d.L <= 5; }
-void launchVocoderOne(const DevBatch &d, int sBase, int nStreams, int hopBase, bool plain, hipStream_t st) {
-	countLaunch(LK_VOC_ONE);
-	switch (d.C) {
-	case 1: launchVocoderOneT<1>(d, sBase, nStreams, hopBase, plain, st); return;
-	case 2: launchVocoderOneT<2>(d, sBase, nStreams, hopBase, plain, st); return;
-	case 3: launchVocoderOneT<3>(d, sBase, nStreams, hopBase, plain, st); return;
-	case 4: launchVocoderOneT<4>(d, sBase, nStreams, hopBase, plain, st); return;
-	case 5: launchVocoderOneT<5>(d, sBase, nStreams, hopBase, plain, st); return;
-	case 6: launchVocoderOneT<6>(d, sBase, nStreams, hopBase, plain, st); return;
-	case 7: launchVocoderOneT<7>(d, sBase, nStreams, hopBase, plain, st); return;
-	default: launchVocoderOneT<8>(d, sBase, nStreams, hopBase, plain, st); return;
-	}
-}
-void launchPredict(const DevBatch &d, int sBase, int nStreams, int hopBase, int tileHops, bool plain, bool passADone, hipStream_t st) {
-	switch (d.C) {
-	case 1: launchPredictT<1>(d, sBase, nStreams, hopBase, tileHops, plain, passADone, st); break;
-	case 2: launchPredictT<2>(d, sBase, nStreams, hopBase, tileHops, plain, passADone, st); break;
-	case 3: launchPredictT<3>(d, sBase, nStreams, hopBase, tileHops, plain, passADone, st); break;
-	case 4: launchPredictT<4>(d, sBase, nStreams, hopBase, tileHops, plain, passADone, st); break;
-	case 5: launchPredictT<5>(d, sBase, nStreams, hopBase, tileHops, plain, passADone, st); break;
-	case 6: launchPredictT<6>(d, sBase, nStreams, hopBase, tileHops, plain, passADone, st); break;
-	case 7: launchPredictT<7>(d, sBase, nStreams, hopBase, tileHops, plain, passADone, st); break;
-	case 8: launchPredictT<8>(d, sBase, nStreams, hopBase, tileHops, plain, passADone, st); break;
-	case 9: launchPredictT<9>(d, sBase, nStreams, hopBase, tileHops, plain, passADone, st); break;
-	case 10: launchPredictT<10>(d, sBase, nStreams, hopBase, tileHops, plain, passADone, st); break;
-	case 11: launchPredictT<11>(d, sBase, nStreams, hopBase, tileHops, plain, passADone, st); break;
-	case 12: launchPredictT<12>(d, sBase, nStreams, hopBase, tileHops, plain, passADone, st); break;
-	case 13: launchPredictT<13>(d, sBase, nStreams, hopBase, tileHops, plain, passADone, st); break;
-	case 14: launchPredictT<14>(d, sBase, nStreams, hopBase, tileHops, plain, passADone, st); break;
-	case 15: launchPredictT<15>(d, sBase, nStreams, hopBase, tileHops, plain, passADone, st); break;
-	default: launchPredictT<16>(d, sBase, nStreams, hopBase, tileHops, plain, passADone, st); break;
-	}
-}
-template <int CH>
-static void launchChainT(const DevBatch &d, int sBase, int nStreams, int hopBase, hipStream_t st) {
-	size_t lds = ((size_t)CH*d.ringSlots*64 + (size_t)CH*128)*sizeof(float2);
-	hipLaunchKernelGGL(kChain<CH>, dim3(nStreams), dim3(64), lds, st, d, sBase, hopBase);
+	if (fused) return;
+	const dim3 grid(divUp(d.M + d.lag*(d.T - 1), 8), nStreams);
+	withIntIn<1, kMaxChannels>(d.C, [&](auto ch) { withFlag(plain, [&](auto isPlain) {
+		hipLaunchKernelGGL((kPredictB<ch.value, isPlain.value>), grid, dim3(256), PredictBLds<ch.value>::bytes, st, d, sBase, hopBase);
+	}); });
 }
 void launchChain(const DevBatch &d, int sBase, int nStreams, int hopBase, hipStream_t st) {
-	countLaunch(LK_CHAIN_UNFUSED);
-	switch (d.C) {
-	case 1: launchChainT<1>(d, sBase, nStreams, hopBase, st); break;
-	case 2: launchChainT<2>(d, sBase, nStreams, hopBase, st); break;
-	case 3: launchChainT<3>(d, sBase, nStreams, hopBase, st); break;
-	case 4: launchChainT<4>(d, sBase, nStreams, hopBase, st); break;
-	case 5: launchChainT<5>(d, sBase, nStreams, hopBase, st); break;
-	case 6: launchChainT<6>(d, sBase, nStreams, hopBase, st); break;
-	case 7: launchChainT<7>(d, sBase, nStreams, hopBase, st); break;
-	case 8: launchChainT<8>(d, sBase, nStreams, hopBase, st); break;
-	case 9: launchChainT<9>(d, sBase, nStreams, hopBase, st); break;
-	case 10: launchChainT<10>(d, sBase, nStreams, hopBase, st); break;
-	case 11: launchChainT<11>(d, sBase, nStreams, hopBase, st); break;
-	case 12: launchChainT<12>(d, sBase, nStreams, hopBase, st); break;
-	case 13: launchChainT<13>(d, sBase, nStreams, hopBase, st); break;
-	case 14: launchChainT<14>(d, sBase, nStreams, hopBase, st); break;
-	case 15: launchChainT<15>(d, sBase, nStreams, hopBase, st); break;
-	default: launchChainT<16>(d, sBase, nStreams, hopBase, st); break;
-	}
+	withIntIn<1, kMaxChannels>(d.C, [&](auto ch) {
+		hipLaunchKernelGGL(kChain<ch.value>, dim3(nStreams), dim3(64), chainLdsBytes(ch.value, d.ringSlots), st, d, sBase, hopBase);
+	});
 }
+// 3-8 channels, longVerticalStep 2..5: 3 (presetCheaper), 4 / 5 (presetDefault at 48 / 44.1 kHz)
 void launchVocoderMany(const DevBatch &d, int sBase, int nStreams, int hopBase, bool plain, hipStream_t st) {
-	countLaunch(LK_VOC_N);
-	switch (d.C) {
-	case 3: launchVocoderN<3>(d, sBase, nStreams, hopBase, plain, st); return;
-	case 4: launchVocoderN<4>(d, sBase, nStreams, hopBase, plain, st); return;
-	case 5: launchVocoderN<5>(d, sBase, nStreams, hopBase, plain, st); return;
-	case 6: launchVocoderN<6>(d, sBase, nStreams, hopBase, plain, st); return;
-	case 7: launchVocoderN<7>(d, sBase, nStreams, hopBase, plain, st); return;
-	default: launchVocoderN<8>(d, sBase, nStreams, hopBase, plain, st); return;
-	}
+	withIntIn<3, kMaxFusedChannels>(d.C, [&](auto ch) { withIntIn<2, 5>(d.L, [&](auto l) { withFlag(plain, [&](auto isPlain) {
+		hipLaunchKernelGGL((kVocoderN<ch.value, isPlain.value, l.value>), dim3(nStreams), dim3(64*kVocWaves), VocoderNLds<ch.value>::bytes, st, d, sBase, hopBase);
+	}); }); });
+}
+// single-hop tiles (every stream fires at most one hop): see kVocoderOne.  1-8 channels, the same vertical steps.
+void launchVocoderOne(const DevBatch &d, int sBase, int nStreams, int hopBase, bool plain, hipStream_t st) {
+	withIntIn<1, kMaxFusedChannels>(d.C, [&](auto ch) { withIntIn<2, 5>(d.L, [&](auto l) { withFlag(plain, [&](auto isPlain) {
+		hipLaunchKernelGGL((kVocoderOne<ch.value, isPlain.value, l.value>), dim3(nStreams), dim3(128), VocoderOneLds<ch.value>::bytes, st, d, sBase, hopBase);
+	}); }); });
 }
 
 } // namespace smst

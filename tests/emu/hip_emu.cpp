@@ -12,7 +12,9 @@
 #include <stdexcept>
 
 EmuIdx threadIdx, blockIdx, blockDim, gridDim;
-namespace smst { alignas(16) unsigned char smemRaw[160*1024]; }
+// (behind the CU's 160 KB: room for the guard that emuLaunch lays behind every request)
+constexpr size_t kLdsBytes = 160*1024, kLdsGuardBytes = 4096;
+namespace smst { alignas(16) unsigned char smemRaw[kLdsBytes + kLdsGuardBytes]; }
 
 // Context switches: a workgroup of 1024 fibers yields at every barrier, poll and s_sleep -- tens of millions of switches per test run.  glibc's
 // swapcontext() makes a signal-mask system call per switch (the CPU suite spent 4 min 54 s of 8 min 23 s in the kernel); the switch below saves
@@ -111,7 +113,11 @@ static long maxRounds() {
 }
 
 void emuLaunch(dim3 grid, dim3 block, size_t ldsBytes, const std::function<void()> &body, const char *name) {
-	if (ldsBytes > sizeof(smst::smemRaw)) throw std::runtime_error("emu: LDS request too large");
+	if (ldsBytes > kLdsBytes) throw std::runtime_error("emu: LDS request too large");
+	// On the device an LDS write past what the launcher asked for is dropped silently.  Here the bytes behind the request carry a pattern
+	// that must still stand after the launch: "the kernel writes nothing past what its launcher asked for", for every kernel of the library.
+	auto guardByte = [](size_t i) { return (unsigned char)(0xA5u ^ (i*37u)); };
+	for (size_t i = 0; i < kLdsGuardBytes; ++i) smst::smemRaw[ldsBytes + i] = guardByte(i);
 	const unsigned nThreads = block.x*block.y*block.z;
 	static std::vector<Fiber> fibers;
 	if (fibers.size() < nThreads) fibers.resize(nThreads);
@@ -144,6 +150,10 @@ void emuLaunch(dim3 grid, dim3 block, size_t ldsBytes, const std::function<void(
 				if (!f.done) anyAlive = true;
 			}
 		}
+	}
+	for (size_t i = 0; i < kLdsGuardBytes; ++i) {
+		if (smst::smemRaw[ldsBytes + i] != guardByte(i))
+			throw std::runtime_error(std::string("emu: kernel ") + name + " wrote LDS byte " + std::to_string(ldsBytes + i) + ", its launcher asked for " + std::to_string(ldsBytes));
 	}
 }
 
