@@ -70,13 +70,10 @@ struct smst_batch {
 	struct PcmCounts { // [2*S]: input frames, output frames; [S] dither entries; [S] level entries
 		Buffer<int, true> host;
 		Buffer<int, false> dev;
-		hipEvent_t done = nullptr;
-		bool used = false;
 		const smst::PcmDither *dither = nullptr; // the call's entries in `dev`; null: the call does not dither
 		smst::PcmLevelIo level;                  // ... and its level entries, behind them, with the batch's meters; table null: the call is not levelled
-		~PcmCounts() { if (done) hipEventDestroy(done); }
-	} pcmCounts[2];
-	int pcmCur = 0;
+	};
+	smst::TwoSets<PcmCounts> pcmCounts; // (smst_staging.h)
 	// dither of the int16 / int24 output (smst_batch_set_pcm_dither): per stream the mode, the seed, its hash and the frame counter
 	struct PcmDitherState { int mode = SMST_DITHER_NONE; long long seed = 0; unsigned h = 0; unsigned long long frames = 0; };
 	std::vector<PcmDitherState> pcmDither;
@@ -436,17 +433,16 @@ static void checkPcmFormat(int format, int memory) {
 static smst_batch::PcmCounts &beginPcmCall(smst_batch *b) {
 	Batch &e = *b->engine;
 	hipSetDevice(e.device());
-	b->pcmCur ^= 1;
-	smst_batch::PcmCounts &c = b->pcmCounts[b->pcmCur];
-	if (!c.host) {
+	b->pcmCounts.create();
+	smst_batch::PcmCounts &c = b->pcmCounts.begin();
+	if (!c.host) { // (both sets with the first call, as Batch::exact's segment tables: the second call allocates nothing)
 		++b->stagingAllocs;
 		const size_t ints = (size_t)2*e.streams() + (size_t)e.streams()*((sizeof(smst::PcmDither) + sizeof(smst::PcmLevel))/sizeof(int));
-		c.host.allocate(ints, "PCM counts");
-		c.dev.allocate(ints, "PCM counts");
-		if (hipEventCreateWithFlags(&c.done, hipEventDisableTiming) != hipSuccess) throw smst::Error("hipEventCreate failed", true);
+		for (smst_batch::PcmCounts &t : b->pcmCounts.sets) {
+			t.host.allocate(ints, "PCM counts");
+			t.dev.allocate(ints, "PCM counts");
+		}
 	}
-	if (c.used && hipEventSynchronize(c.done) != hipSuccess) throw smst::Error("hipEventSynchronize failed", true);
-	c.used = false;
 	c.dither = nullptr;
 	c.level = smst::PcmLevelIo();
 	return c;
@@ -485,10 +481,7 @@ static void pcmUploadDither(smst_batch *b, smst_batch::PcmCounts &c, int format,
 static void pcmAdvanceDither(smst_batch *b, const int *n) {
 	for (size_t s = 0; s < b->pcmDither.size(); ++s) if (b->pcmDither[s].mode != SMST_DITHER_NONE && n[s] > 0) b->pcmDither[s].frames += (unsigned long long)n[s];
 }
-static void endPcmCall(smst_batch *b, smst_batch::PcmCounts &c) {
-	if (hipEventRecord(c.done, b->engine->stream()) != hipSuccess) throw smst::Error("hipEventRecord failed", true);
-	c.used = true;
-}
+static void endPcmCall(smst_batch *b) { b->pcmCounts.end(b->engine->stream()); }
 // a stream's row in the library's own raw buffers: its frames densely, rows a multiple of 16 bytes apart for every element size
 static long long pcmRowElems(int maxFrames, int C) { return ((long long)maxFrames*C + 15)/16*16; }
 
@@ -644,7 +637,7 @@ int smst_batch_process_pcm(smst_batch *b, const void *in, long long iss, long lo
 		const int maxOut = pcmPrepareOut(b, c, outSamples, format, memory);
 		e.process(b->dIn, (long long)e.channels()*maxIn, maxIn, inSamples, b->dOut, (long long)e.channels()*maxOut, maxOut, outSamples);
 		pcmStageOut(b, c, out, oss, ofs, maxOut, format, memory);
-		endPcmCall(b, c);
+		endPcmCall(b);
 	})
 }
 int smst_batch_seek_pcm(smst_batch *b, const void *in, long long ss, long long fs, const int *inSamples, const double *rates, int format, int memory) {
@@ -655,7 +648,7 @@ int smst_batch_seek_pcm(smst_batch *b, const void *in, long long ss, long long f
 		smst_batch::PcmCounts &c = beginPcmCall(b);
 		const int maxLen = pcmStageIn(b, c, in, ss, fs, inSamples, format, memory);
 		e.seek(b->dIn, (long long)e.channels()*maxLen, maxLen, inSamples, rates);
-		endPcmCall(b, c);
+		endPcmCall(b);
 		if (memory == SMST_MEM_HOST) e.synchronize();
 	})
 }
@@ -670,7 +663,7 @@ int smst_batch_flush_pcm(smst_batch *b, void *out, long long oss, long long ofs,
 		const int maxOut = pcmPrepareOut(b, c, f.counts.data(), format, memory);
 		e.flush(b->dOut, (long long)e.channels()*maxOut, maxOut, f.counts.data(), rates, f.mask());
 		pcmStageOut(b, c, out, oss, ofs, maxOut, format, memory);
-		endPcmCall(b, c);
+		endPcmCall(b);
 	})
 }
 int smst_batch_output_seek_pcm(smst_batch *b, const void *in, long long ss, long long fs, const int *inputLengths, int format, int memory) {
@@ -681,7 +674,7 @@ int smst_batch_output_seek_pcm(smst_batch *b, const void *in, long long ss, long
 		smst_batch::PcmCounts &c = beginPcmCall(b);
 		const int maxLen = pcmStageIn(b, c, in, ss, fs, inputLengths, format, memory);
 		e.outputSeek(b->dIn, (long long)e.channels()*maxLen, maxLen, inputLengths);
-		endPcmCall(b, c);
+		endPcmCall(b);
 		if (memory == SMST_MEM_HOST) e.synchronize();
 	})
 }
@@ -760,7 +753,7 @@ int smst_batch_exact_pcm(smst_batch *b, const void *in, long long iss, long long
 			runExact(e, Batch::ClipIo{b->dPcmIn, pcmRowElems(mostIn, C), C, b->dPcmOut, pcmRowElems(mostOut, C), C, format, b->dPcmOvers, dither, level, wholeClip.data()}, inSamples, outSamples, status);
 			pcmRawOut(b, out, oss, ofs, nOut.data(), mostOut, format);
 		}
-		if (table) endPcmCall(b, *table);
+		if (table) endPcmCall(b);
 	})
 }
 } // extern "C"

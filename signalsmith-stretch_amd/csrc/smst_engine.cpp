@@ -13,6 +13,8 @@ namespace smst {
 
 #define SMST_HIP(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) throw Error(std::string(#expr) + ": " + hipGetErrorString(e_), true); } while (0)
 
+void throwDeviceError(const char *call, hipError_t e) { throw Error(std::string(call) + ": " + hipGetErrorString(e), true); }
+
 static constexpr float kNoiseFloor = 1e-15f;     // signalsmith-stretch.h:508
 static constexpr float kMaxCleanStretch = 2.0f;  // :509
 static constexpr unsigned long long kEngineModulus = 2147483647ull; // 2^31 - 1: the random engine is libstdc++'s minstd_rand0 (:616; smst_kernels_common.h: engineDraw)
@@ -160,10 +162,9 @@ void Batch::createStreamsAndEvents() {
 	}
 	SMST_HIP(hipStreamCreateWithFlags(&stSynth, hipStreamNonBlocking));
 	SMST_HIP(hipStreamCreateWithFlags(&stGate, hipStreamNonBlocking));
-	for (int i = 0; i < 2; ++i) {
-		SMST_HIP(hipEventCreateWithFlags(&callSets[i].done, hipEventDisableTiming));
-		SMST_HIP(hipEventCreateWithFlags(&callSets[i].tables, hipEventDisableTiming));
-	}
+	callSets.create();
+	stageSets.create();
+	for (CallSet &cs : callSets.sets) SMST_HIP(hipEventCreateWithFlags(&cs.tables, hipEventDisableTiming));
 	SMST_HIP(hipEventCreateWithFlags(&evStart, hipEventDisableTiming));
 	SMST_HIP(hipEventCreateWithFlags(&evOrder, hipEventDisableTiming));
 	for (int i = 0; i < 3; ++i) {
@@ -386,22 +387,28 @@ void Batch::allocateCarriedState() {
 
 void Batch::allocateCallTables() {
 	dParams = devAlloc<StreamParams>(S);
+	hParams = pinnedAlloc<StreamParams>(S);
 	d.params = d.paramsPeaks = d.paramsForm0 = d.paramsForm2 = dParams;
 	dEnergy = devAlloc<float>((size_t)S*kEnergyParts);
-	for (int i = 0; i < 2; ++i) {
-		callSets[i].inSamples = devAlloc<int>(S);
-		callSets[i].outSamples = devAlloc<int>(S);
-		callSets[i].flags = devAlloc<int>(S);
-		callSets[i].hInSamples = pinnedAlloc<int>(S);
-		callSets[i].hOutSamples = pinnedAlloc<int>(S);
-		callSets[i].hFlags = pinnedAlloc<int>(S);
-		callSets[i].hEnergy = pinnedAlloc<float>((size_t)S*kEnergyParts);
-		callSets[i].resetBits = devAlloc<int>(S);
-		callSets[i].hResetBits = pinnedAlloc<int>(S);
+	for (CallSet &cs : callSets.sets) {
+		cs.inSamples = devAlloc<int>(S);
+		cs.outSamples = devAlloc<int>(S);
+		cs.flags = devAlloc<int>(S);
+		cs.hInSamples = pinnedAlloc<int>(S);
+		cs.hOutSamples = pinnedAlloc<int>(S);
+		cs.hFlags = pinnedAlloc<int>(S);
+		cs.hEnergy = pinnedAlloc<float>((size_t)S*kEnergyParts);
+		cs.resetBits = devAlloc<int>(S);
+		cs.hResetBits = pinnedAlloc<int>(S);
 		if (split) {
-			callSets[i].pendHops = devAlloc<HopDesc>(S);
-			callSets[i].hPendHops = pinnedAlloc<HopDesc>(S);
+			cs.pendHops = devAlloc<HopDesc>(S);
+			cs.hPendHops = pinnedAlloc<HopDesc>(S);
 		}
+	}
+	for (StageSet &t : stageSets.sets) {
+		t.host = pinnedAlloc<int>((size_t)kStageColumns*S);
+		t.dev = devAlloc<int>((size_t)kStageColumns*S);
+		t.hEnergy = pinnedAlloc<float>((size_t)S*kEnergyParts);
 	}
 	dSeedWp = devAlloc<float>(d.carryLen);
 	SMST_HIP(hipMemcpy(dSeedWp, seedCarryWp.data(), d.carryLen*sizeof(float), hipMemcpyHostToDevice));
@@ -409,15 +416,14 @@ void Batch::allocateCallTables() {
 	hopCount.assign(S, 0);
 	leavesPendingV.assign(S, 0);
 	ridesV.assign(S, 0);
-	dInSamples = callSets[0].inSamples;
-	dOutSamples = callSets[0].outSamples;
-	dFlags = callSets[0].flags;
-	dAux0 = devAlloc<int>(S);
-	dAux1 = devAlloc<int>(S);
-	dResetBits = devAlloc<int>(S);
-	dKeep = devAlloc<int>(S);
-	resetBitsV.assign(S, 0);
-	keepV.assign(S, 0);
+	dInSamples = callSets.sets[0].inSamples;
+	dOutSamples = callSets.sets[0].outSamples;
+	dFlags = callSets.sets[0].flags;
+	for (std::vector<int> *v : {&flushV.blockOut, &flushV.blockIn, &flushV.synthChannels, &outputSeekV.seekSamples, &outputSeekV.surplus, &outputSeekV.preOut, &outputSeekV.done,
+	                            &exactV.seekLen, &exactV.rest, &exactV.procOut, &exactV.flushN}) v->assign(S, 0);
+	for (std::vector<unsigned char> *v : {&flushV.runBlock, &flushV.on, &outputSeekV.mask, &exactV.run}) v->assign(S, 0);
+	outputSeekV.rates.assign(S, 1.0);
+	exactV.rates.assign(S, 0.0f);
 }
 
 void Batch::initHostRows(long seed) {
@@ -445,8 +451,8 @@ void Batch::allocateSplitTables() { // the block in flight: its spectra, and the
 	if (!split) return;
 	allocateCarried(kPendIn, kCarriedArrays);
 	const int nSub = (S + subS - 1)/subS;
-	for (int i = 0; i < 2; ++i) {
-		PendSet &ps = pendSets[i];
+	pendSets.create();
+	for (PendSet &ps : pendSets.sets) {
 		ps.hops = devAlloc<HopDesc>(S + kTileHops); ps.hHops = pinnedAlloc<HopDesc>(S); // (+ a tile's worth: the wavefront kernels cache a blind row of 64 descriptors per stream, hopStride 1)
 		SMST_HIP(hipMemset(ps.hops, 0, (size_t)(S + kTileHops)*sizeof(HopDesc)));
 		ps.emit = devAlloc<EmitDesc>(S); ps.hEmit = pinnedAlloc<EmitDesc>(S);
@@ -454,8 +460,6 @@ void Batch::allocateSplitTables() { // the block in flight: its spectra, and the
 		ps.bits = devAlloc<int>(S); ps.hBits = pinnedAlloc<int>(S);
 		ps.synthChannels = devAlloc<int>(S); ps.hSynthChannels = pinnedAlloc<int>(S);
 		for (int j = 0; j < 3; ++j) { ps.prm[j] = devAlloc<StreamParams>(S); ps.hPrm[j] = pinnedAlloc<StreamParams>(S); }
-		SMST_HIP(hipEventCreateWithFlags(&ps.done, hipEventDisableTiming));
-		ps.used = false;
 	}
 	dZeroCounts = devAlloc<int>(S);
 	SMST_HIP(hipMemset(dZeroCounts, 0, S*sizeof(int)));
@@ -479,15 +483,6 @@ void Batch::releaseAll() {
 	allocations.clear();
 	for (void *p : pinned) hipHostFree(p);
 	pinned.clear();
-	for (int i = 0; i < 2; ++i) {
-		if (callSets[i].done) hipEventDestroy(callSets[i].done);
-		if (callSets[i].tables) hipEventDestroy(callSets[i].tables);
-		callSets[i].done = callSets[i].tables = nullptr;
-		if (pendSets[i].done) hipEventDestroy(pendSets[i].done);
-		pendSets[i].done = nullptr;
-		if (clipSets[i].done) hipEventDestroy(clipSets[i].done);
-		clipSets[i].done = nullptr;
-	}
 	if (evStart) hipEventDestroy(evStart);
 	if (evOrder) hipEventDestroy(evOrder);
 	evStart = evOrder = nullptr;
@@ -592,14 +587,12 @@ void Batch::allocateWorkspace() {
 
 void Batch::uploadParams() {
 	if (!paramsDirty) return;
-	SMST_HIP(hipMemcpyAsync(dParams, params.data(), S*sizeof(StreamParams), hipMemcpyHostToDevice, st));
+	std::copy(params.begin(), params.end(), hParams); // (pinned; the synchronise below makes it free to rewrite)
+	SMST_HIP(hipMemcpyAsync(dParams, hParams, S*sizeof(StreamParams), hipMemcpyHostToDevice, st));
 	SMST_HIP(hipStreamSynchronize(st));
 	paramsDirty = false;
 }
 
-// stft.reset(0.1) / Band clearing for a set of streams (bit masks, see kResetStreams): one upload + one launch, instead
-// of six API calls per stream.  `bitsHost` == nullptr: `allBits` for every stream.  Not on the steady-state path (reset,
-// flush, first silent block), so the small synchronous upload is fine.
 // The kernels outside the tile pipeline (flush tail, pre-roll, the reset that keeps the samples of a split interval, the debug accessors) index
 // the overlap-add carry from the front of its rows: a call without hops may have left the windows further in (kEmitCarried) -- one
 // emission of nothing moves them back.
@@ -616,19 +609,34 @@ void Batch::settleCarry() {
 	std::fill(carryBase.begin(), carryBase.end(), 0);
 }
 
-void Batch::resetStreams(const int *bitsHost, int allBits, const int *keepHost) {
-	if (keepHost) settleCarry();
-	if (bitsHost) SMST_HIP(hipMemcpy(dResetBits, bitsHost, S*sizeof(int), hipMemcpyHostToDevice));
-	if (keepHost) SMST_HIP(hipMemcpy(dKeep, keepHost, S*sizeof(int), hipMemcpyHostToDevice));
-	launchResetStreams(d, bitsHost ? dResetBits : nullptr, allBits, dSeedWp, st, keepHost ? dKeep : nullptr);
-	for (int s = 0; s < S; ++s) if ((bitsHost ? bitsHost[s] : allBits) & RESET_STFT) histBase[s] = carryBase[s] = 0; // (the host's copies of DevBatch::histBase / carryBase)
+void Batch::uploadStage(const StageSet &t, int columns) { // a stage's ONE upload: its columns are contiguous
+	SMST_HIP(hipMemcpyAsync(t.dev, t.host, (size_t)columns*S*sizeof(int), hipMemcpyHostToDevice, st));
+}
+
+// stft.reset(0.1) / Band clearing for the streams that pick(s) names (bit masks, see kResetStreams): one upload + one launch, instead of
+// six API calls per stream.  A stage set of its own turn: column 0 the masks, column 1 (keepAhead: flush() with split computation) how many
+// samples of the stashed ring each stream keeps -- what is left of its interval.
+template <typename Pick> void Batch::resetStreams(Pick pick, int bits, bool keepAhead) {
+	if (keepAhead) settleCarry();
+	StageSet &t = stageSets.begin();
+	int *mask = t.host, *keep = t.host + S;
+	for (int s = 0; s < S; ++s) {
+		mask[s] = pick(s) ? bits : 0;
+		keep[s] = (mask[s] && keepAhead) ? aheadOffset(s) : 0;
+		if (mask[s] & RESET_STFT) histBase[s] = carryBase[s] = 0; // (the host's copies of DevBatch::histBase / carryBase)
+	}
+	uploadStage(t, keepAhead ? 2 : 1);
+	launchResetStreams(d, t.dev, 0, dSeedWp, st, keepAhead ? t.dev + S : nullptr);
+	stageSets.end(st);
 }
 
 void Batch::reset() { // signalsmith-stretch.h:49-60
 	SMST_HIP(hipSetDevice(dev));
 	const CarriedArray freq = carriedArrays()[kStFreq];
 	SMST_HIP(hipMemsetAsync(freq.current(), 0, (size_t)S*freq.rowBytes, st));
-	resetStreams(nullptr, RESET_STFT | RESET_INPUT | RESET_PREV | RESET_OUTPUT);
+	launchResetStreams(d, nullptr, RESET_STFT | RESET_INPUT | RESET_PREV | RESET_OUTPUT, dSeedWp, st); // (every stream: no table)
+	std::fill(histBase.begin(), histBase.end(), 0);
+	std::fill(carryBase.begin(), carryBase.end(), 0);
 	d.histCur = 0;
 	d.carryCur = 0;
 	for (int s = 0; s < S; ++s) clearHostRow(s);
@@ -654,19 +662,17 @@ void Batch::takeHostRow(const Batch &o, int from, int to) {
 	paramsDirty = true;
 }
 
+template <typename Pick> void Batch::resetPicked(Pick pick) { // reset() for the picked streams; kResetStreams writes both halves of the double buffers, so which half is current does not matter
+	SMST_HIP(hipSetDevice(dev));
+	SMST_HIP(hipStreamSynchronize(st)); // (orders nothing that the masks need any more -- their set's event does; kept: EXPERIMENTS.md, "One per-call table set")
+	resetStreams(pick, RESET_STFT | RESET_INPUT | RESET_PREV | RESET_OUTPUT | RESET_FREQ);
+	for (int s = 0; s < S; ++s) if (pick(s)) clearHostRow(s);
+}
 void Batch::resetStream(int s) { // reset() for one stream
 	if (s < 0 || s >= S) throw Error("stream index out of range");
-	std::vector<unsigned char> one(S, 0);
-	one[s] = 1;
-	resetStreamsMasked(one.data());
+	resetPicked([s](int t) { return t == s; });
 }
-void Batch::resetStreamsMasked(const unsigned char *active) { // reset() for the masked streams; kResetStreams writes both halves of the double buffers, so which half is current does not matter
-	SMST_HIP(hipSetDevice(dev));
-	SMST_HIP(hipStreamSynchronize(st)); // (an earlier launch may still read the mask buffer)
-	for (int s = 0; s < S; ++s) resetBitsV[s] = active[s] ? (RESET_STFT | RESET_INPUT | RESET_PREV | RESET_OUTPUT | RESET_FREQ) : 0;
-	resetStreams(resetBitsV.data(), 0);
-	for (int s = 0; s < S; ++s) if (active[s]) clearHostRow(s);
-}
+void Batch::resetStreamsMasked(const unsigned char *active) { resetPicked([active](int s) { return active[s] != 0; }); }
 
 // ---- parameters ------------------------------------------------------------------------------------------
 template <typename F> static void forStreams(int S, int stream, F &&f) {
@@ -931,9 +937,7 @@ void Batch::noteLastHop(int s, int slot, int local, unsigned flags) { // where t
 void Batch::runPendingBlocks(const int *synthChannels) {
 	if (pendList.empty()) return;
 	uploadParams();
-	pendCur ^= 1;
-	PendSet &ps = pendSets[pendCur];
-	if (ps.used) SMST_HIP(hipEventSynchronize(ps.done));
+	PendSet &ps = pendSets.begin();
 	const int nSub = (S + subS - 1)/subS;
 	std::memset(ps.hHops, 0, S*sizeof(HopDesc));
 	std::memset(ps.hEmit, 0, S*sizeof(EmitDesc));
@@ -995,8 +999,7 @@ void Batch::runPendingBlocks(const int *synthChannels) {
 		SMST_HIP(hipMemcpyAsync(ps.bits, ps.hBits, S*sizeof(int), hipMemcpyHostToDevice, st));
 		launchResetStreams(d, ps.bits, 0, dSeedWp, st);
 	}
-	SMST_HIP(hipEventRecord(ps.done, st));
-	ps.used = true;
+	pendSets.end(st);
 	for (int s : pendList) {
 		if (pend[s].flags & HOP_RANDOM_TF) sched[s].seed = advanceOneHop(sched[s].seed); // its draws happen now
 		pend[s] = PendingBlock();
@@ -1330,7 +1333,7 @@ void Batch::growCallTables(const CallPlan &c) {
 	cs.retiredDevice.clear();
 	cs.retiredPinned.clear();
 	for (int which = 0; which < 2; ++which) {
-		CallSet &t = callSets[which ? callCur ^ 1 : callCur];
+		CallSet &t = which ? callSets.other() : cs;
 		growCallTable(t, which == 0, t.hops, t.hHops, t.hopsCap, c.needHops);
 		growCallTable(t, which == 0, t.emit, t.hEmit, t.emitCap, c.needEmit);
 		growCallTable(t, which == 0, t.tileInfo, t.hTileInfo, t.tileInfoCap, c.needInfo);
@@ -1481,9 +1484,7 @@ void Batch::process(const float *in, long long inSS, long long inCS, const int *
 	// everything up to the first tile launch runs on `stGate`, so the host-side scheduling of this call overlaps the
 	// kernels of the previous call that are still queued on `st`.  All staging is pinned and owned by the set, so the
 	// uploads are asynchronous and the ONLY host synchronisation of a call is the silence-gate readback.
-	callCur ^= 1;
-	CallSet &cs = callSets[callCur];
-	if (cs.used) { const auto t = std::chrono::steady_clock::now(); SMST_HIP(hipEventSynchronize(cs.done)); hostTimes.waitTablesMs += msSince(t); }
+	CallSet &cs = callSets.begin(&hostTimes.waitTablesMs);
 	dInSamples = cs.inSamples; dOutSamples = cs.outSamples; dFlags = cs.flags;
 	const int T = d.T;
 	int *nIn = cs.hInSamples, *nOut = cs.hOutSamples;
@@ -1577,8 +1578,7 @@ void Batch::process(const float *in, long long inSS, long long inCS, const int *
 		launchHistory(d, io, span, st);
 	});
 	d.histCur ^= 1;
-	SMST_HIP(hipEventRecord(cs.done, st));
-	cs.used = true;
+	callSets.end(st);
 	SMST_HIP(hipGetLastError());
 	hostTimes.callMs += msSince(hostT0);
 	++hostTimes.calls;
@@ -1587,15 +1587,11 @@ void Batch::process(const float *in, long long inSS, long long inCS, const int *
 // ---- seek -------------------------------------------------------------------------------------------------
 void Batch::seek(const float *in, long long inSS, long long inCS, const int *inSamples, const double *rates, const unsigned char *active) {
 	SMST_HIP(hipSetDevice(dev));
-	// pinned staging of its own ([S] sample counts, [S] flags, [S] history lengths, energy partials): one host
-	// synchronisation (the energy readback that decides about the silence counter, :159-162)
-	if (!hSeek) {
-		hSeek = pinnedAlloc<int>((size_t)3*S);
-		hSeekEnergy = pinnedAlloc<float>((size_t)S*kEnergyParts);
-	} else {
-		SMST_HIP(hipStreamSynchronize(st)); // an earlier seek's uploads may still be in flight
-	}
-	int *nIn = hSeek, *flags = hSeek + S, *histN = hSeek + 2*S;
+	// a stage set ([S] sample counts, [S] flags, [S] history lengths; the energy partials come back into it): one host synchronisation of its
+	// own (the energy readback that decides about the silence counter, :159-162)
+	SMST_HIP(hipStreamSynchronize(st)); // (no staging needs it any more -- the set's event guards that; kept: EXPERIMENTS.md, "One per-call table set")
+	StageSet &t = stageSets.begin();
+	int *nIn = t.host, *flags = t.host + S, *histN = t.host + 2*S;
 	for (int s = 0; s < S; ++s) {
 		const bool on = !active || active[s];
 		flags[s] = on ? 1 : 0;
@@ -1603,22 +1599,21 @@ void Batch::seek(const float *in, long long inSS, long long inCS, const int *inS
 		histN[s] = d.histLen;
 		if (nIn[s] < 0) throw Error("negative sample count");
 	}
-	SMST_HIP(hipMemcpyAsync(dInSamples, nIn, S*sizeof(int), hipMemcpyHostToDevice, st));
-	SMST_HIP(hipMemcpyAsync(dFlags, flags, S*sizeof(int), hipMemcpyHostToDevice, st));
-	SMST_HIP(hipMemcpyAsync(dAux0, histN, S*sizeof(int), hipMemcpyHostToDevice, st));
-	IoArgs io{in, nullptr, inSS, inCS, 0, 0, dInSamples, dOutSamples};
-	launchSeekHistory(d, io, dFlags, st);
+	uploadStage(t, 3);
+	IoArgs io{in, nullptr, inSS, inCS, 0, 0, t.dev, dOutSamples};
+	launchSeekHistory(d, io, t.dev + S, st);
 	d.histCur ^= 1;
 	// energy of the copied part only (:144-154) = energy over the new history (the zero padding adds nothing)
 	for (int s = 0; s < S; ++s) if (flags[s]) histBase[s] = 0;
-	IoArgs ioE{d.hist, nullptr, (long long)C*d.histPitch, (long long)d.histPitch, 0, 0, dAux0, dOutSamples}; // (the streams that seek: their windows are at the front of the rows now)
+	IoArgs ioE{d.hist, nullptr, (long long)C*d.histPitch, (long long)d.histPitch, 0, 0, t.dev + 2*S, dOutSamples}; // (the streams that seek: their windows are at the front of the rows now)
 	launchEnergy(d, ioE, 0, S, d.histLen, dEnergy, st);
-	SMST_HIP(hipMemcpyAsync(hSeekEnergy, dEnergy, (size_t)S*kEnergyParts*sizeof(float), hipMemcpyDeviceToHost, st));
+	SMST_HIP(hipMemcpyAsync(t.hEnergy, dEnergy, (size_t)S*kEnergyParts*sizeof(float), hipMemcpyDeviceToHost, st));
+	stageSets.end(st);
 	SMST_HIP(hipStreamSynchronize(st));
 	for (int s = 0; s < S; ++s) {
 		if (!flags[s]) continue;
 		float e = 0;
-		for (int p = 0; p < kEnergyParts; ++p) e += hSeekEnergy[(size_t)s*kEnergyParts + p];
+		for (int p = 0; p < kEnergyParts; ++p) e += t.hEnergy[(size_t)s*kEnergyParts + p];
 		StreamSched &sc = sched[s];
 		if (e >= kNoiseFloor) { // :159-162
 			sc.silenceCounter = 0;
@@ -1638,32 +1633,23 @@ int Batch::aheadOffset(int s) const {
 }
 void Batch::flush(float *out, long long outSS, long long outCS, const int *outSamples, const float *rates, const unsigned char *active) {
 	SMST_HIP(hipSetDevice(dev));
-	std::vector<int> blockOut(S, 0), blockIn(S, 0), tail(S, -1), tailOff(S, 0), outOff(S, 0);
-	std::vector<unsigned char> runBlock(S, 0), on(S, 0);
+	std::vector<int> &blockOut = flushV.blockOut, &blockIn = flushV.blockIn, &synthChannels = flushV.synthChannels; // (every entry is written below)
+	std::vector<unsigned char> &runBlock = flushV.runBlock, &on = flushV.on;
 	bool anyBlock = false;
 	int maxIn = 0;
 	for (int s = 0; s < S; ++s) {
-		if (active && !active[s]) continue;
-		on[s] = 1;
-		const int n = outSamples[s];
-		if (n < 0) throw Error("negative sample count");
-		const int outputBlock = std::max(0, n - I); // :439
-		const float rate = rates ? rates[s] : 0.0f;
-		if (outputBlock > 0) {
-			runBlock[s] = 1;
-			anyBlock = true;
-			blockOut[s] = outputBlock;
-			blockIn[s] = int(outputBlock*rate); // :440
-			maxIn = std::max(maxIn, blockIn[s]);
-		}
-		tail[s] = n - outputBlock;
-		outOff[s] = outputBlock;
+		on[s] = !(active && !active[s]);
+		if (on[s] && outSamples[s] < 0) throw Error("negative sample count");
+		const int outputBlock = on[s] ? std::max(0, outSamples[s] - I) : 0; // :439
+		runBlock[s] = outputBlock > 0;
+		anyBlock = anyBlock || runBlock[s];
+		blockOut[s] = outputBlock;
+		blockIn[s] = (runBlock[s] && rates) ? int(outputBlock*rates[s]) : 0; // :440
+		maxIn = std::max(maxIn, blockIn[s]);
+		synthChannels[s] = -1;
 	}
 	if (anyBlock) {
-		if ((size_t)maxIn + 1 > zerosCapacity) {
-			if (dZeros) { SMST_HIP(hipStreamSynchronize(st)); devFree(dZeros); }
-			zerosCapacity = (size_t)maxIn + 1 + 4096;
-			dZeros = devAlloc<float>(zerosCapacity);
+		if (growScratch(dZeros, zerosCapacity, (size_t)maxIn + 1, 4096, false)) {
 			// process() reads this on another stream (the silence gate runs on stGate): complete the fill before going on
 			SMST_HIP(hipMemsetAsync(dZeros, 0, zerosCapacity*sizeof(float), st));
 			SMST_HIP(hipStreamSynchronize(st));
@@ -1674,7 +1660,6 @@ void Batch::flush(float *out, long long outSS, long long outCS, const int *outSa
 	// interval; flush() reads the REAL ring, one interval ahead of the stashed one that process() emits from, then stft.reset(0.1) and
 	// prevInput = output = 0, :442-463 -- and the block's remaining steps run afterwards, on what the flush left.  Pinned step by step by
 	// tests/golden/split_events.)
-	std::vector<int> synthChannels;
 	pendList.clear();
 	for (int s = 0; s < S; ++s) {
 		if (!on[s] || !split || !pend[s].valid) continue;
@@ -1684,8 +1669,7 @@ void Batch::flush(float *out, long long outSS, long long outCS, const int *outSa
 		if (e > size_t(l.synth0)) {
 			// the spectrum is complete and e - synth0 channels have been synthesised into the ring (all of them: the block is finished): run
 			// the block now; the other channels' frames never come -- stft.reset() clears the spectrum they would be made from
-			if (synthChannels.empty()) synthChannels.assign(S, -1);
-			synthChannels[s] = (e >= size_t(l.steps)) ? -1 : int(e) - l.synth0;
+			synthChannels[s] =(e >= size_t(l.steps)) ? -1 : int(e) - l.synth0;
 			pendList.push_back(s);
 		} else if (e >= size_t(l.spectrum)) {
 			// output (and, after `.input -> .prevInput`, prevInput) were complete and are zeroed; what remains is a silent frame: its window product
@@ -1701,18 +1685,25 @@ void Batch::flush(float *out, long long outSS, long long outCS, const int *outSa
 		}
 	}
 	if (!pendList.empty()) runPendingBlocks(synthChannels.data());
-	for (int s = 0; s < S; ++s) if (on[s]) tailOff[s] = aheadOffset(s);
-	SMST_HIP(hipMemcpyAsync(dOutSamples, tail.data(), S*sizeof(int), hipMemcpyHostToDevice, st));
-	SMST_HIP(hipMemcpyAsync(dAux0, tailOff.data(), S*sizeof(int), hipMemcpyHostToDevice, st));
-	SMST_HIP(hipMemcpyAsync(dAux1, outOff.data(), S*sizeof(int), hipMemcpyHostToDevice, st));
-	SMST_HIP(hipStreamSynchronize(st));
-	IoArgs io{nullptr, out, 0, 0, outSS, outCS, dInSamples, dOutSamples};
+	// the stage's own set, now that process() and runPendingBlocks() are through with theirs: the tail's length (-1: the stream takes no
+	// part), where the real ring's read position is in the stashed one, where the tail goes in the stream's output
+	StageSet &t = stageSets.begin();
+	int *tail = t.host, *tailOff = t.host + S, *outOff = t.host + 2*S;
+	for (int s = 0; s < S; ++s) {
+		tail[s] = on[s] ? outSamples[s] - blockOut[s] : -1;
+		tailOff[s] = on[s] ? aheadOffset(s) : 0;
+		outOff[s] = blockOut[s];
+	}
+	uploadStage(t, 3);
+	SMST_HIP(hipStreamSynchronize(st)); // (the upload no longer needs it -- pinned, and the set's event guards it; kept: EXPERIMENTS.md, "One per-call table set")
+	IoArgs io{nullptr, out, 0, 0, outSS, outCS, dInSamples, t.dev};
 	settleCarry();
-	launchFlushTail(d, io, dAux0, dAux1, st);
+	launchFlushTail(d, io, t.dev + S, t.dev + 2*S, st);
+	stageSets.end(st);
 	// stft.reset(0.1) + zero prevInput/output (:456-463).  Split computation: the samples up to the end of the interval still come from
 	// the stashed ring (:407-415), which the reset does not touch -- the fresh ring begins behind them
-	for (int s = 0; s < S; ++s) { resetBitsV[s] = on[s] ? (RESET_STFT | RESET_PREV | RESET_OUTPUT) : 0; keepV[s] = on[s] ? tailOff[s] : 0; if (on[s]) lastHop[s] = LastHop(); }
-	resetStreams(resetBitsV.data(), 0, split ? keepV.data() : nullptr);
+	for (int s = 0; s < S; ++s) if (on[s]) lastHop[s] = LastHop();
+	resetStreams([&on](int s) { return on[s] != 0; }, RESET_STFT | RESET_PREV | RESET_OUTPUT, split);
 	SMST_HIP(hipGetLastError());
 }
 
@@ -1722,28 +1713,22 @@ void Batch::outputSeek(const float *in, long long inSS, long long inCS, const in
 	if (active) resetStreamsMasked(active);
 	else reset();
 	const int outLat = outputLatency(), inLat = inputLatency();
-	std::vector<int> seekSamples(S, 0), surplus(S, 0), preOut(S, outLat);
-	std::vector<double> rates(S, 1.0);
+	std::vector<int> &seekSamples = outputSeekV.seekSamples, &surplus = outputSeekV.surplus, &preOut = outputSeekV.preOut, &done = outputSeekV.done; // (every entry is written below)
+	std::vector<double> &rates = outputSeekV.rates;
+	std::vector<unsigned char> &mask = outputSeekV.mask;
 	for (int s = 0; s < S; ++s) {
-		if (active && !active[s]) continue;
-		surplus[s] = std::max(inputLengths[s] - inLat, 0);
+		const bool on = !(active && !active[s]);
+		surplus[s] = on ? std::max(inputLengths[s] - inLat, 0) : 0;
 		float playbackRate = surplus[s]/float(outLat);
-		seekSamples[s] = inputLengths[s] - surplus[s];
-		rates[s] = playbackRate;
+		seekSamples[s] = on ? inputLengths[s] - surplus[s] : 0;
+		rates[s] = on ? playbackRate : 1.0;
+		preOut[s] = outLat;
+		done[s] = !on; // (... of the pre-roll, below)
 	}
 	seek(in, inSS, inCS, seekSamples.data(), rates.data(), active);
-	// pre-roll output into scratch [S][C][outLat]
-	const size_t need = (size_t)S*C*outLat;
-	if (need > scratchOutCapacity) {
-		if (dScratchOut) { SMST_HIP(hipStreamSynchronize(st)); devFree(dScratchOut); }
-		scratchOutCapacity = need;
-		dScratchOut = devAlloc<float>(need);
-	}
+	growScratch(dScratchOut, scratchOutCapacity, (size_t)S*C*outLat, 0, false); // pre-roll output into scratch [S][C][outLat]
 	// offset input per stream: seekSamples differ per stream, so pass per-stream start through a shifted base when uniform,
 	// otherwise run stream groups with equal offsets
-	std::vector<unsigned char> mask(S);
-	std::vector<int> done(S, 0);
-	for (int s = 0; s < S; ++s) if (active && !active[s]) done[s] = 1;
 	for (int s0 = 0; s0 < S; ++s0) {
 		if (done[s0]) continue;
 		std::fill(mask.begin(), mask.end(), 0);
@@ -1752,25 +1737,26 @@ void Batch::outputSeek(const float *in, long long inSS, long long inCS, const in
 	}
 	// "put the thing down, flip it and reverse it" (:198-203): negate, reverse, add into the output ring (a stream that is masked out
 	// gets an offset behind its ring: nothing is added)
-	std::vector<int> off(S, 0);
-	for (int s = 0; s < S; ++s) off[s] = (active && !active[s]) ? d.carryLen : aheadOffset(s);
-	SMST_HIP(hipMemcpyAsync(dAux0, off.data(), S*sizeof(int), hipMemcpyHostToDevice, st));
-	SMST_HIP(hipStreamSynchronize(st));
+	StageSet &t = stageSets.begin();
+	for (int s = 0; s < S; ++s) t.host[s] = (active && !active[s]) ? d.carryLen : aheadOffset(s);
+	uploadStage(t, 1);
+	SMST_HIP(hipStreamSynchronize(st)); // (the upload no longer needs it -- pinned, and the set's event guards it; kept: EXPERIMENTS.md, "One per-call table set")
 	settleCarry();
-	launchAddPreRoll(d, dScratchOut, outLat, dAux0, st);
+	launchAddPreRoll(d, dScratchOut, outLat, t.dev, st);
+	stageSets.end(st);
 	SMST_HIP(hipGetLastError());
 }
 
 // ---- exact ------------------------------------------------------------------------------------------------
-void Batch::growClipImage(float *&image, size_t &capacity, size_t need) {
-	if (need <= capacity) return;
-	if (image) { SMST_HIP(hipStreamSynchronize(st)); devFree(image); wsBytes -= capacity*sizeof(float); }
-	image = nullptr;
+bool Batch::growScratch(float *&scratch, size_t &capacity, size_t need, size_t room, bool workspace) {
+	if (need <= capacity) return false;
+	if (scratch) { SMST_HIP(hipStreamSynchronize(st)); devFree(scratch); if (workspace) wsBytes -= capacity*sizeof(float); }
+	scratch = nullptr;
 	capacity = 0;
-	const size_t want = need + need/8 + 1024;
-	image = devAlloc<float>(want);
-	capacity = want;
-	wsBytes += want*sizeof(float);
+	scratch = devAlloc<float>(need + room);
+	capacity = need + room;
+	if (workspace) wsBytes += capacity*sizeof(float);
+	return true;
 }
 
 void Batch::exact(const ClipIo &io, const int *inSamples, const int *outSamples, unsigned char *tooShort) {
@@ -1782,23 +1768,22 @@ void Batch::exact(const ClipIo &io, const int *inSamples, const int *outSamples,
 	// input behind seekLength_s and the flush go through the images.
 	SMST_HIP(hipSetDevice(dev));
 	const bool direct = io.format == 0;
-	for (ClipSet &t : clipSets) { // (both sets with the first call: the second call allocates nothing)
+	for (ClipSet &t : clipSets.sets) { // (both sets with the first call: the second call allocates nothing)
 		if (t.host) continue;
 		t.host = pinnedAlloc<ClipSeg>((size_t)4*S);
 		t.dev = devAlloc<ClipSeg>((size_t)4*S);
 		wsBytes += (size_t)4*S*sizeof(ClipSeg);
-		SMST_HIP(hipEventCreateWithFlags(&t.done, hipEventDisableTiming));
 	}
-	clipCur ^= 1;
-	ClipSet &cs = clipSets[clipCur];
-	if (cs.used) SMST_HIP(hipEventSynchronize(cs.done)); // (the call before the previous one: its clip kernels must have read the tables)
-	cs.used = false;
-	std::vector<int> seekLen(S, 0), rest(S, 0), procOut(S, 0), flushN(S, 0);
-	std::vector<float> rates(S, 0.0f);
-	std::vector<unsigned char> run(S, 0);
+	clipSets.create();
+	ClipSet &cs = clipSets.begin(); // (the call before the previous one: its clip kernels must have read the tables)
+	std::vector<int> &seekLen = exactV.seekLen, &rest = exactV.rest, &procOut = exactV.procOut, &flushN = exactV.flushN;
+	std::vector<float> &rates = exactV.rates;
+	std::vector<unsigned char> &run = exactV.run;
 	int maxSeek = 0, maxRest = 0, maxProc = 0, maxFlush = 0, maxZeros = 0;
 	bool anyRun = false;
 	for (int s = 0; s < S; ++s) {
+		seekLen[s] = rest[s] = procOut[s] = flushN[s] = run[s] = 0;
+		rates[s] = 0.0f;
 		if (outSamples[s] < 0) continue;
 		ExactLengths l = exactLengths(inSamples[s], outSamples[s]);
 		if (l.tooShort) { maxZeros = std::max(maxZeros, outSamples[s]); continue; }
@@ -1815,8 +1800,9 @@ void Batch::exact(const ClipIo &io, const int *inSamples, const int *outSamples,
 	auto up4 = [](int n) { return (n + 3)/4*4; };
 	const int P = direct ? 0 : up4(maxSeek), Q = direct ? 0 : up4(maxProc);
 	const int pitchIn = std::max(up4(P + maxRest), 4), pitchOut = std::max(up4(Q + maxFlush), 4);
-	growClipImage(dClipIn, clipInCapacity, (size_t)S*C*pitchIn);
-	growClipImage(dClipOut, clipOutCapacity, (size_t)S*C*pitchOut);
+	const size_t needIn = (size_t)S*C*pitchIn, needOut = (size_t)S*C*pitchOut;
+	growScratch(dClipIn, clipInCapacity, needIn, needIn/8 + 1024, true);
+	growScratch(dClipOut, clipOutCapacity, needOut, needOut/8 + 1024, true);
 	ClipSeg *segIn = cs.host, *segOut = cs.host + (size_t)2*S;
 	for (int s = 0; s < S; ++s) {
 		const ClipSeg none{0, 0, 0, 0};
@@ -1854,8 +1840,7 @@ void Batch::exact(const ClipIo &io, const int *inSamples, const int *outSamples,
 	}
 	launchClipOut(io.format, dClipOut, outImgSS, pitchOut, io.out, io.outStreamStride, io.outInnerStride, cs.dev + (size_t)2*S, S, C,
 	              std::max(std::max(direct ? 0 : maxProc, maxFlush), maxZeros), io.overs, st, io.dither, io.level);
-	SMST_HIP(hipEventRecord(cs.done, st));
-	cs.used = true;
+	clipSets.end(st);
 	SMST_HIP(hipGetLastError());
 	if (tooShort) for (int s = 0; s < S; ++s) if (outSamples[s] >= 0) tooShort[s] = run[s] ? 0 : 1; // (only once every stage has been issued)
 }

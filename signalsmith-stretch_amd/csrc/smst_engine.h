@@ -10,6 +10,7 @@
 #include <hip/hip_runtime.h>
 #include "smst_device.h"
 #include "smst_recurrence_form.h"
+#include "smst_staging.h"
 
 namespace smst {
 
@@ -169,18 +170,26 @@ private:
 	hipStream_t stChain = nullptr;  // the bin recurrence (few waves, latency-bound): overlaps with the bulk kernels
 	hipStream_t stSynth = nullptr;  // synthesis + emission of the previous tile
 	hipStream_t stGate = nullptr;   // silence-gate reduction + table uploads of the NEXT call, while the previous call still runs
-	// Per-call device tables exist twice: a call fills one set on `stGate` while kernels of the previous call read the other
+	// Per-call device tables exist twice (smst_staging.h): a call fills one set on `stGate` while kernels of the previous call read the other
 	// ... and so does their PINNED host staging (h*): nothing pageable is handed to an async copy, so the only host
-	// synchronisation of a call is the silence-gate readback
+	// synchronisation of a call is the silence-gate readback.  That holds for every table of the engine: the sets below (callSets,
+	// pendSets, stageSets, clipSets) and the parameter rows (hParams) are all of its uploads on the calling paths.
 	struct CallSet {
 		int *inSamples, *outSamples, *flags, *tileInfo, *resetBits; HopDesc *hops; EmitDesc *emit;
 		int *hInSamples, *hOutSamples, *hFlags, *hTileInfo, *hResetBits; HopDesc *hHops; EmitDesc *hEmit; float *hEnergy;
 		HopDesc *pendHops = nullptr, *hPendHops = nullptr; // split computation: the block each stream leaves in flight at the end of the call ([S], analysis only)
 		size_t hopsCap, emitCap, tileInfoCap;
-		hipEvent_t done, tables; bool used;
+		hipEvent_t tables; // the uploads on `stGate`, for `st` to wait on
 		std::vector<void *> retiredDevice, retiredPinned; // outgrown tables that the previous call may still read
-	} callSets[2]{};
-	int callCur = 0;
+		~CallSet() { if (tables) hipEventDestroy(tables); }
+	};
+	TwoSets<CallSet> callSets;
+	// The whole-call stages (seek, flush, outputSeek's fold-back, resetStreams) hand the device per-stream COLUMNS of S ints: a stage takes a
+	// set, fills its first columns, uploads them in one copy on `st`, launches, and gives the set back.  hEnergy: seek()'s readback.
+	static constexpr int kStageColumns = 3;
+	struct StageSet { int *host, *dev; float *hEnergy; };
+	TwoSets<StageSet> stageSets;
+	void uploadStage(const StageSet &t, int columns);
 	hipEvent_t evStart = nullptr, evFeed[3] = {nullptr, nullptr, nullptr}, evChain[3] = {nullptr, nullptr, nullptr}, evOut[3] = {nullptr, nullptr, nullptr}, evSynth[3] = {nullptr, nullptr, nullptr}; // (the third set: the continuous wavefront's tile pipeline is one stage deeper)
 	struct TileBuffers { float2 *Xcur, *Xprev, *OUT, *dump, *map, *peaksT; float4 *REC; PredEntry *PE; float *ratio, *envelope, *energyT, *smoothT, *est, *freqEst, *frames; float2 *fftScratch; } slots[3]{}; // [2]: only what a plain tile touches, only where the continuous wavefront applies (allocateWorkspace)
 	bool overlap = true, carriedEmit = true; // (smst_switches.h)
@@ -194,6 +203,10 @@ private:
 	std::vector<int> hopFirst, hopCount, maxSpanV;
 	std::vector<TileSummary> tileHasV, pendTileHas; // [sub][tile] of a call, [sub] of a run of blocks in flight
 	std::vector<unsigned char> leavesPendingV, ridesV;
+	// ... and of the whole-call stages, [S] each: a stage's own, never shared (exact() hands its own down to outputSeek(), process() and flush())
+	struct FlushScratch { std::vector<int> blockOut, blockIn, synthChannels; std::vector<unsigned char> runBlock, on; } flushV;
+	struct OutputSeekScratch { std::vector<int> seekSamples, surplus, preOut, done; std::vector<double> rates; std::vector<unsigned char> mask; } outputSeekV;
+	struct ExactScratch { std::vector<int> seekLen, rest, procOut, flushN; std::vector<float> rates; std::vector<unsigned char> run; } exactV;
 	long allocEvents = 0; // device allocations + pinned allocations + host table growth since construction
 	size_t wsBytes = 0;
 	DevBatch d{};
@@ -212,15 +225,14 @@ private:
 	std::vector<int> histBase;  // the host's copy of DevBatch::histBase (where each stream's input-history window begins)
 	std::vector<PendingBlock> pend;
 	float2 *dPendIn = nullptr, *dPendPrev = nullptr; // its spectra, [S][C][Mp]: Band.input and (re-analysed) Band.prevInput
-	struct PendSet { // tables of one run of blocks in flight (double-buffered like CallSet: pinned staging, asynchronous uploads)
+	struct PendSet { // tables of one run of blocks in flight (twice, like CallSet: pinned staging, asynchronous uploads)
 		HopDesc *hops, *hHops; EmitDesc *emit, *hEmit; int *tileInfo, *hTileInfo, *bits, *hBits, *synthChannels, *hSynthChannels;
 		StreamParams *prm[3], *hPrm[3];
-		hipEvent_t done; bool used;
-	} pendSets[2]{};
-	int pendCur = 0;
+	};
+	TwoSets<PendSet> pendSets;
 	int *dZeroCounts = nullptr; // [S] zeros: the sample counts of a run that consumes and emits nothing
 	std::vector<int> pendList;  // streams of the run being prepared
-	std::vector<int> pendMaxSpan, keepV;
+	std::vector<int> pendMaxSpan;
 	StepLayout stepLayout(unsigned flags) const;
 	size_t stepsExecuted(size_t steps, size_t samplesIntoInterval) const;
 	void freezePendingParams(int s);   // before a setter changes params[s]
@@ -258,23 +270,20 @@ private:
 
 	std::vector<void *> allocations;
 	float *dEnergy = nullptr;
-	int *dInSamples = nullptr, *dOutSamples = nullptr, *dFlags = nullptr, *dAux0 = nullptr, *dAux1 = nullptr;
+	int *dInSamples = nullptr, *dOutSamples = nullptr, *dFlags = nullptr;
 	HopDesc *dHops = nullptr;
 	EmitDesc *dEmit = nullptr;
 	int *dTileInfo = nullptr;
-	int *hSeek = nullptr;          // pinned staging of seek()
-	float *hSeekEnergy = nullptr;
 	float *dSeedWp = nullptr; // reset(0.1) window-product seed, device copy
 	hipEvent_t evOrder = nullptr;
 	std::vector<void *> pinned;
 	template <typename T> T *pinnedAlloc(size_t count);
 	void pinnedFree(void *p);
 	void releaseAll();
-	void resetStreams(const int *bitsHost, int allBits, const int *keepHost = nullptr); // per-stream bit masks (kResetStreams) or null = allBits for all; keepHost: see launchResetStreams; synchronous upload (reset / flush)
+	template <typename Pick> void resetStreams(Pick pick, int bits, bool keepAhead = false); // kResetStreams with `bits` for the streams that pick(s) names; keepAhead: see launchResetStreams' keep
+	template <typename Pick> void resetPicked(Pick pick); // resetStream / resetStreamsMasked
 	bool checkLaunches = false; // SMST_CHECK_LAUNCHES=1: hipGetLastError() after every launch group of process(), not only at its end
 	void checkLaunch(const char *what);
-	int *dResetBits = nullptr, *dKeep = nullptr;
-	std::vector<int> resetBitsV;
 	float *dZeros = nullptr;
 	size_t zerosCapacity = 0;
 	float *dScratchOut = nullptr;
@@ -283,10 +292,11 @@ private:
 	// per-call tables are (a call returns before its last kernel has run)
 	float *dClipIn = nullptr, *dClipOut = nullptr;
 	size_t clipInCapacity = 0, clipOutCapacity = 0;
-	struct ClipSet { ClipSeg *host = nullptr, *dev = nullptr; hipEvent_t done = nullptr; bool used = false; } clipSets[2]; // [2][S][2]: input segments, output segments
-	int clipCur = 0;
-	void growClipImage(float *&image, size_t &capacity, size_t need);
-	StreamParams *dParams = nullptr;
+	struct ClipSet { ClipSeg *host, *dev; }; // [2][S][2]: input segments, output segments
+	TwoSets<ClipSet> clipSets;
+	// a device scratch that holds `need` floats, allocated with `room` more; true: it was replaced (the old one freed behind a synchronise).  workspace: counted in workspaceBytes()
+	bool growScratch(float *&scratch, size_t &capacity, size_t need, size_t room, bool workspace);
+	StreamParams *dParams = nullptr, *hParams = nullptr; // (hParams: pinned staging of uploadParams())
 	float *dMapTable = nullptr;
 	std::vector<float> hostMapTable;
 	std::vector<float> seedCarryWp;

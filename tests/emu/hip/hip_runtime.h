@@ -144,6 +144,8 @@ static inline hipError_t hipEventElapsedTime(float *ms, hipEvent_t, hipEvent_t) 
 // the synchronous hipMemcpy / hipMemset (null stream) run at once; hipFree / hipHostFree synchronise the device.
 // hipMemcpyAsync reads / writes device and hipHostMalloc memory when the copy runs; a pageable source is staged at enqueue
 // (HIP may do either: the copy from pageable memory below is the one choice that cannot hide a missing edge on the device side).
+// What it CAN hide is a too-early rewrite of such a source by the host: such copies are counted (smst_emu_pageable_async_copies), and the
+// engine's calling paths make none (csrc/smst_staging.h).
 hipError_t hipStreamCreateWithFlags(hipStream_t *s, unsigned flags);
 hipError_t hipStreamCreateWithPriority(hipStream_t *s, unsigned flags, int priority);
 hipError_t hipStreamDestroy(hipStream_t s);

@@ -241,6 +241,7 @@ Schedule overrideMode = EAGER;
 std::string envSeen;
 Schedule envMode = EAGER;
 std::map<uintptr_t, size_t> deviceRanges, pinnedRanges;
+long long pageableAsyncCopies = 0; // hipMemcpyAsync calls on a stream whose source is neither device nor hipHostMalloc memory, under every schedule
 
 bool parseSchedule(const char *spec, Schedule &mode, uint64_t &seed, bool &seeded) {
 	const std::string v = spec ? spec : "";
@@ -421,6 +422,7 @@ hipError_t hipMemcpyAsync(void *d, const void *s, size_t n, hipMemcpyKind, hipSt
 	// Device and pinned memory are read and written when the copy runs.  A pageable source is staged at enqueue (HIP may copy it
 	// through a staging buffer at once); a pageable destination is written when the copy runs, so the host must still wait for it.
 	const bool late = inRange(deviceRanges, s) || (rules.pinnedAtExecution && inRange(pinnedRanges, s));
+	if (!inRange(deviceRanges, s) && !inRange(pinnedRanges, s)) ++pageableAsyncCopies; // (the model cannot see a too-early rewrite of such a source)
 	if (late || stream->mode == EAGER) emuEnqueue(stream, "copy", [d, s, n]() { std::memcpy(d, s, n); });
 	else {
 		std::vector<unsigned char> staged(static_cast<const unsigned char *>(s), static_cast<const unsigned char *>(s) + n);
@@ -507,6 +509,8 @@ void smst_emu_enqueue_tick(void *s, int *slot) {
 	static int ticks = 0;
 	emuEnqueue(static_cast<hipStream_t>(s), "tick", [slot]() { *slot = ++ticks; });
 }
+// async copies from pageable memory since the library was loaded: the engine's calling paths make none (csrc/smst_staging.h)
+long long smst_emu_pageable_async_copies() { return pageableAsyncCopies; }
 // operations queued on all live streams and not run yet
 long long smst_emu_queued() {
 	long long n = 0;

@@ -42,6 +42,7 @@ def model(emu):
         "smst_emu_unregister_device": (None, [C.c_void_p]),
         "smst_emu_enqueue_tick": (None, [C.c_void_p, C.c_void_p]),
         "smst_emu_queued": (C.c_longlong, []),
+        "smst_emu_pageable_async_copies": (C.c_longlong, []),
     }
     for name, (res, args) in hooks.items():
         f = getattr(emu, name)
@@ -499,3 +500,118 @@ def test_device_memory_caller_streams(hooks, monkeypatch, continuous):
     if continuous:
         monkeypatch.setenv("SMST_CONTINUOUS", "1")
     _check_schedules(hooks, lambda lib: _device_memory(lib, continuous))
+
+
+# ---- the whole-call stages: seek, flush, outputSeek, the resets under them, exact() ---------------------------------------------------------
+
+class _DeviceCalls:
+    """whole_call_cases' calls through the C ABI on SMST_MEM_DEVICE buffers with the caller's own producer and consumer streams, as
+    _device_memory: an input goes up from pinned memory on the producer, the batch waits for it; an output is read on the consumer, ordered
+    after the batch by smst_batch_signal_stream, never after smst_batch_synchronize.  Every buffer is a fresh one and lives to close()."""
+
+    def __init__(self, lib, batch):
+        self.lib, self.b, self.pkg = lib, batch, package()
+        self.prod, self.cons = lib.smst_emu_stream_create(), lib.smst_emu_stream_create()
+        self.device, self.pinned = [], []
+
+    def _ints(self, v):
+        a = np.ascontiguousarray(v, np.int32)
+        return a, a.ctypes.data_as(C.POINTER(C.c_int))
+
+    def _new(self, shape, dtype, fill):
+        d = np.full(shape, fill, dtype)
+        self.lib.smst_emu_register_device(_ptr(d), d.nbytes)
+        self.device.append(d)
+        return d
+
+    def _up(self, x):
+        p = self.lib.smst_emu_host_malloc(x.nbytes)
+        self.pinned.append(p)
+        C.memmove(p, x.ctypes.data, x.nbytes)
+        d = self._new(x.shape, x.dtype, 0)
+        self.lib.smst_emu_memcpy_async(_ptr(d), C.c_void_p(p), d.nbytes, self.prod)
+        assert self.lib.smst_batch_wait_for_stream(self.b.h, self.prod) == 0
+        return d
+
+    def _ok(self, rc):
+        assert rc == 0, self.lib.smst_last_error()
+
+    def seek(self, x, counts, rates):
+        d, (_, n), r = self._up(x), self._ints(counts), np.ascontiguousarray(rates, np.float64)
+        self._ok(self.lib.smst_batch_seek(self.b.h, _ptr(d), x.shape[1]*x.shape[2], x.shape[2], n, r.ctypes.data_as(C.POINTER(C.c_double)), self.pkg.MEM_DEVICE))
+
+    def process(self, x, nin, nout):
+        d, (_, pin), (_, pout), m = self._up(x), self._ints(nin), self._ints(nout), max(max(nout), 1)
+        y = self._new((x.shape[0], x.shape[1], m), np.float32, np.nan)
+        self._ok(self.lib.smst_batch_process(self.b.h, _ptr(d), x.shape[1]*x.shape[2], x.shape[2], pin, _ptr(y), x.shape[1]*m, m, pout, self.pkg.MEM_DEVICE))
+        return y
+
+    def flush(self, counts, rates):
+        (_, n), r, m = self._ints(counts), np.ascontiguousarray(rates, np.float32), max(max(counts), 1)
+        y = self._new((self.b.streams, self.b.channels, m), np.float32, np.nan)
+        self._ok(self.lib.smst_batch_flush(self.b.h, _ptr(y), self.b.channels*m, m, n, r.ctypes.data_as(C.POINTER(C.c_float)), self.pkg.MEM_DEVICE))
+        return y
+
+    def output_seek(self, x, lengths):
+        d, (_, n) = self._up(x), self._ints(lengths)
+        self._ok(self.lib.smst_batch_output_seek(self.b.h, _ptr(d), x.shape[1]*x.shape[2], x.shape[2], n, self.pkg.MEM_DEVICE))
+
+    def exact(self, x, nin, nout, frames):
+        d, (_, pin), (_, pout), m = self._up(x), self._ints(nin), self._ints(nout), max(nout)
+        status, Cn = np.full(self.b.streams, 1, np.int32), self.b.channels
+        if frames:
+            n, y = x.shape[1], self._new((x.shape[0], m, Cn), np.int16, 0x5A5A)
+            self._ok(self.lib.smst_batch_exact_pcm(self.b.h, _ptr(d), n*Cn, Cn, pin, _ptr(y), m*Cn, Cn, pout, status.ctypes.data_as(C.POINTER(C.c_int)),
+                                                   self.pkg.PCM_S16, self.pkg.MEM_DEVICE))
+        else:
+            n, y = x.shape[2], self._new((x.shape[0], Cn, m), np.float32, np.nan)
+            self._ok(self.lib.smst_batch_exact(self.b.h, _ptr(d), Cn*n, n, pin, _ptr(y), Cn*m, m, pout, status.ctypes.data_as(C.POINTER(C.c_int)), self.pkg.MEM_DEVICE))
+        return y, status == 0
+
+    def host(self, d):
+        y = np.zeros_like(d)
+        assert self.lib.smst_batch_signal_stream(self.b.h, self.cons) == 0
+        self.lib.smst_emu_memcpy_async(_ptr(y), _ptr(d), d.nbytes, self.cons)
+        self.lib.smst_emu_stream_synchronize(self.cons)
+        return y
+
+    def close(self):
+        self.lib.smst_emu_device_synchronize()
+        for d in self.device:
+            self.lib.smst_emu_unregister_device(_ptr(d))
+        for p in self.pinned:
+            self.lib.smst_emu_host_free(C.c_void_p(p))
+        self.lib.smst_emu_stream_destroy(self.prod)
+        self.lib.smst_emu_stream_destroy(self.cons)
+
+
+def _whole_call(lib, split, rounds=1):
+    """-> (the digests of whole_call_cases.SEQUENCE on device memory, async copies from pageable memory it made)"""
+    import whole_call_cases as wc
+    b = wc.new_batch(lib, split)
+    calls = _DeviceCalls(lib, b)
+    before = lib.smst_emu_pageable_async_copies()
+    digests = wc.run_sequence(b, calls, rounds=rounds)
+    pageable = lib.smst_emu_pageable_async_copies() - before
+    calls.close()
+    b.close()
+    return digests, pageable
+
+
+@pytest.mark.parametrize("name", ["plain", "split"])
+def test_whole_call_stages(hooks, name):
+    """Bit-identical under every schedule -- the stages' tables are pinned, so a set rewritten before its upload ran would show -- and equal
+    to what the parent commit gave on host memory."""
+    import json
+    import whole_call_cases as wc
+    digests, _ = _check_schedules(hooks, lambda lib: _whole_call(lib, wc.SCENARIOS[name]))
+    assert digests == json.load(open(wc.GOLDEN["emu"]))["scenarios"][name]
+
+
+@pytest.mark.parametrize("name", ["plain", "split"])
+def test_no_pageable_async_copy_on_the_calling_paths(hooks, name):
+    """csrc/smst_engine.h: "nothing pageable is handed to an async copy" -- over the whole-call sequence on device memory, setters between
+    the calls included, and a second round of it (every set has been used before), the stand-in counts no such copy."""
+    import whole_call_cases as wc
+    _schedule(hooks, "eager")
+    assert _whole_call(hooks, wc.SCENARIOS[name], rounds=2)[1] == 0
