@@ -402,7 +402,7 @@ int smst_batch_pcm_dither(const smst_batch *b, int stream, int *mode, long long 
  * (process: every stream; flush: those with a non-negative count) has a whole-clip mode they return SMST_ERR_INVALID before anything runs --
  * a whole-clip gain in a streaming call would be a silent lie.  smst_batch_exact_pcm serves all three modes.  The too-short and left-out
  * streams of an exact call stay as they are: undithered zeros or untouched, peak and gain unchanged.  Out of scope: the planar calls and the
- * planar smst_batch_exact are neither levelled nor metered; loudness (LUFS) and true-peak metering; separate input and output formats in one call.
+ * planar smst_batch_exact are neither levelled nor metered; true-peak metering; separate input and output formats in one call.
  *
  * Clip-free ceilings.  fl(peak*fl(ceiling/peak)) may exceed the ceiling by an fp32 rounding or two, so a ceiling of exactly full scale can
  * clamp.  No element is clamped (smst_batch_take_pcm_overs gives 0) when ceiling*scale is at most
@@ -420,14 +420,73 @@ int smst_batch_pcm_dither(const smst_batch *b, int stream, int *mode, long long 
  * smst_batch_workspace_bytes.  No allocation and no host synchronisation is added to any call, the ordering contract is unchanged, and a
  * steady-state levelled call leaves smst_batch_debug_allocation_events where it is.
  * SMST_ERR_INVALID with a message: an unknown mode, a stream index out of range, a null batch, a gain that is not finite, a gain <= 0 in
- * PROTECT, a ceiling that is not finite or <= 0 in the two whole-clip modes. */
+ * PROTECT, a ceiling that is not finite or <= 0 in the two whole-clip modes.
+ *
+ * Loudness.  SMST_LEVEL_LOUDNESS (3) is a third whole-clip mode, set by smst_batch_set_pcm_loudness (not by smst_batch_set_pcm_level): the
+ * clip is brought to a target T in LUFS.  smst_batch_exact_pcm only; process_pcm and flush_pcm refuse it as they refuse the other two.
+ * fs is the stream's loudness sample rate -- the rate of the OUTPUT clip; a parameter of the level setting, not of the engine's geometry.
+ *
+ * Measurement.  ITU-R BS.1770-4 integrated loudness of the stream's output clip [0, outSamples[s]), before any gain, on the library's own
+ * planar image of the output.  Everything up to the final gain is float64.
+ * - K-weighting: two biquads in series, coefficients computed by the host in double from fs, zero state at the clip's first sample.
+ *     shelf      f0 = 1681.974450955533, G = 3.999843853973347 dB, Q = 0.7071752369554196
+ *                K = tan(pi*f0/fs), Vh = 10^(G/20), Vb = Vh^0.4996667741545416, a0 = 1 + K/Q + K*K
+ *                b = [(Vh + Vb*K/Q + K*K)/a0, 2*(K*K - Vh)/a0, (Vh - Vb*K/Q + K*K)/a0],  a = [1, 2*(K*K - 1)/a0, (1 - K/Q + K*K)/a0]
+ *     high-pass  f0 = 38.13547087602444, Q = 0.5003270373238773, K = tan(pi*f0/fs), d = 1 + K/Q + K*K
+ *                b = [1, -2, 1],  a = [1, 2*(K*K - 1)/d, (1 - K/Q + K*K)/d]
+ *   Known answer: at fs = 48000 these are the standard's table -- shelf b 1.53512485958697, -2.69169618940638, 1.19839281085285; shelf a
+ *   -1.69065929318241, 0.73248077421585; high-pass a -1.99004745483398, 0.99007225036621.
+ * - Blocks: h = round(fs/10) samples; block i covers [i*h, i*h + 4h) of the N = outSamples[s] samples; nb = (N - 4h)/h + 1 (integer
+ *   division) for N >= 4h, else 0.  z_i = sum_c w_c * (sum of y_c^2 over block i) / (4h), y_c the weighted channel c; the channel weights
+ *   w_c are per batch and 1 unless set (a 5.1 caller sets 1.41 on the surrounds and 0 on the LFE).
+ * - Gates, in the power domain (no logarithm is taken on the device): absolute, z_i > 10^((-70 + 0.691)/10); relative, z_i > 0.1 * the
+ *   mean of the z that passed the absolute gate.  Z = the mean of the z that pass both.  The host reports L = -0.691 + 10*log10(Z).
+ *   A block that holds a NaN passes no gate; a NaN poisons the filter state, so every block from the NaN's on is such a block.
+ * - Loudness is undefined when nb = 0, when no block passes, or when Z is not finite or not positive (a clip of silence; one with a NaN
+ *   in its first 100 ms).
+ *
+ * Gain.  gL = float32(sqrt(P/Z)), P = 10^((T + 0.691)/10) computed by the host in double; the division and the square root are float64
+ * operations, followed by one rounding to fp32.  gL = 1 where loudness is undefined.  q = ceiling/peak exactly as PROTECT forms it from
+ * the clip's peak; peak 0, a peak that is not finite or a ceiling of +inf: no limit.  g = gL <= q ? gL : q.  From there the levelled
+ * conversion runs unchanged: w = v*g, the format's rule, dither after the gain.  A stream that is too short or left out stays as it is.
+ *
+ * How.  Four passes over the image on the device, behind the peak pass and in front of the conversion; every sum has one fixed order and
+ * no floating-point atomic is used, so a call's result is bit-reproducible whatever the scheduling (csrc/smst_loudness.h).
+ * The sample rate must give h >= SMST_LOUDNESS_CHUNK samples (fs >= 2555).  The per-stream entries and the channel weights ride in the
+ * per-call table beside the level entries; the passes' scratch and the meters grow with the first call that measures, as the images do, and
+ * count in smst_batch_workspace_bytes: a second call of the same shapes allocates nothing, no host synchronisation is added, and the
+ * ordering contract of the device-memory call is unchanged.  A batch without a stream in this mode launches none of the passes.
+ * Out of scope: momentary and short-term loudness, loudness range, true-peak metering, measuring in the streaming or the planar calls.
+ * SMST_ERR_INVALID with a message: a target that is not finite; a sample rate that is not finite, <= 0 or gives h < SMST_LOUDNESS_CHUNK; a
+ * ceiling <= 0 or NaN (+inf is allowed); a weight that is negative or not finite; a stream index out of range; a null batch. */
 #define SMST_LEVEL_FIXED     0 /* g = gain */
 #define SMST_LEVEL_PROTECT   1 /* whole clips only: q = ceiling/peak; g = gain <= q ? gain : q */
 #define SMST_LEVEL_NORMALISE 2 /* whole clips only: g = ceiling/peak */
+#define SMST_LEVEL_LOUDNESS  3 /* whole clips only: gL = sqrt(P/Z); g = gL <= q ? gL : q (smst_batch_set_pcm_loudness) */
+#define SMST_LOUDNESS_CHUNK 256 /* frames of a clip that one lane of the loudness passes filters (kLoudChunk) */
 /* stream = -1: every stream.  ceiling is checked in the two whole-clip modes only */
 int smst_batch_set_pcm_level(smst_batch *b, int stream, int mode, float gain, float ceiling);
 /* any pointer may be null */
 int smst_batch_pcm_level(const smst_batch *b, int stream, int *mode, float *gain, float *ceiling);
+/* stream = -1: every stream.  Sets the stream's mode to SMST_LEVEL_LOUDNESS (smst_batch_pcm_level then reports mode 3, gain 1 and the
+ * ceiling); smst_batch_set_pcm_level takes it out of the mode again */
+int smst_batch_set_pcm_loudness(smst_batch *b, int stream, double targetLufs, float ceiling, double sampleRate);
+/* of a stream in SMST_LEVEL_LOUDNESS (another one: SMST_ERR_INVALID); either pointer may be null */
+int smst_batch_pcm_loudness(const smst_batch *b, int stream, double *target, double *sampleRate);
+/* weights: [channels], or null for 1 on every channel */
+int smst_batch_set_pcm_loudness_weights(smst_batch *b, const float *weights);
+/* per stream, of the newest smst_batch_exact_pcm that measured: lufs[s] = L (-inf where loudness was undefined or the stream was not
+ * measured), blocks[s] = the blocks that passed the absolute gate, gated[s] = those that passed both.  Any pointer may be null.
+ * Synchronises the batch.  smst_batch_take_pcm_peaks reports the gain g that was applied. */
+int smst_batch_take_pcm_loudness(smst_batch *b, double *lufs, int *blocks, int *gated);
+/* test hook: the four loudness passes alone on a planar fp32 image (host pointer, strides in floats) with a segment table as
+ * smst_debug_clip_copy's ([streams][2][4]: a clip is segment 0 then segment 1 of its rows), per-stream sample rates ([streams]) and channel
+ * weights ([channels], null: 1) -> per stream Z, the two block counts, gL for the target, and the block powers z_i
+ * (blockPowers[s*maxBlocks + i], the first min(nb, maxBlocks) of them).  Any output pointer may be null. */
+int smst_debug_clip_loudness(int device, int streams, int channels, const int *segments,
+                             const float *image, long long imageStreamStride, long long imageChannelStride,
+                             const double *sampleRates, const float *weights, double targetLufs,
+                             double *Z, int *blocks, int *gated, float *gains, double *blockPowers, int maxBlocks);
 /* per stream, since the last take: peaks[s] = the largest |v| the levelled output conversions met BEFORE the gain (0 if none); gains[s] = the
  * gain the newest levelled conversion of stream s applied (1 before any).  Either may be null.  Synchronises the batch; resets the peaks,
  * not the gains. */

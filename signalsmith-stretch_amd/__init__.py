@@ -28,6 +28,8 @@ MEM_HOST, MEM_DEVICE = 0, 1
 PCM_S16, PCM_F32, PCM_S24, PCM_S32, PCM_F16 = 1, 2, 4, 5, 6  # frame formats of the *_pcm calls (include/smst.h)
 DITHER_NONE, DITHER_TPDF, DITHER_TPDF_HP = 0, 1, 2           # dither of the int16 / int24 output (StretchBatch.setPcmDither)
 LEVEL_FIXED, LEVEL_PROTECT, LEVEL_NORMALISE = 0, 1, 2        # level of the frame output (StretchBatch.set_pcm_level)
+LEVEL_LOUDNESS = 3                                           # ... to a LUFS target (StretchBatch.set_pcm_loudness)
+LOUDNESS_CHUNK = 256                                         # frames one lane of the loudness passes filters (SMST_LOUDNESS_CHUNK)
 _FRAME_DTYPES = {"int16": PCM_S16, "float32": PCM_F32, "int32": PCM_S32, "float16": PCM_F16}  # (packed int24 travels as uint8 [..., 3])
 _FRAME_DTYPE_OF = {PCM_S16: "int16", PCM_F32: "float32", PCM_S32: "int32", PCM_F16: "float16", PCM_S24: "uint8"}
 _fp = C.POINTER(C.c_float)
@@ -132,6 +134,11 @@ _SIGNATURES = {
                                                   _fp, C.POINTER(_ll), C.POINTER(_ll), _fp]),
     "smst_debug_clip_copy_levelled": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _ip, C.c_void_p, _ll, _ll, C.c_void_p, _ll, _ll, _ip, _fp, _fp, _ip, C.POINTER(_ll),
                                                 C.POINTER(_ll), C.POINTER(_ll), _fp, _fp]),
+    "smst_batch_set_pcm_loudness": (C.c_int, [C.c_void_p, C.c_int, C.c_double, C.c_float, C.c_double]),
+    "smst_batch_pcm_loudness": (C.c_int, [C.c_void_p, C.c_int, _dp, _dp]),
+    "smst_batch_set_pcm_loudness_weights": (C.c_int, [C.c_void_p, _fp]),
+    "smst_batch_take_pcm_loudness": (C.c_int, [C.c_void_p, _dp, _ip, _ip]),
+    "smst_debug_clip_loudness": (C.c_int, [C.c_int, C.c_int, C.c_int, _ip, C.c_void_p, _ll, _ll, _dp, _fp, C.c_double, _dp, _ip, _ip, _fp, _dp, C.c_int]),
     "smst_batch_synchronize": (C.c_int, [C.c_void_p]),
     "smst_batch_hip_stream": (C.c_void_p, [C.c_void_p]),
     "smst_batch_enable_profiling": (C.c_int, [C.c_void_p, C.c_int]),
@@ -284,6 +291,23 @@ def debug_clip_copy_levelled(fmt, segments, channels, src, src_ss, src_cs, dst, 
                                                   pl, pg, pc, pd, ps, clamped.ctypes.data_as(C.POINTER(_ll)), nans.ctypes.data_as(C.POINTER(_ll)),
                                                   peaks.ctypes.data_as(_fp), applied.ctypes.data_as(_fp)))
     return clamped, nans, peaks, applied
+
+
+def debug_clip_loudness(segments, channels, image, image_ss, image_cs, sample_rates, weights=None, target=-23.0, max_blocks=0, device=0, lib=None):
+    """smst_debug_clip_loudness on a numpy image (planar float32; segments int [S, 2, 4]; strides in floats)
+    -> (Z float64 [S], blocks, gated int32 [S], gains float32 [S], block powers float64 [S, max_blocks], NaN behind a stream's last block)"""
+    lib = lib if lib is not None else load_library()
+    seg = np.ascontiguousarray(segments, np.int32)
+    S = seg.shape[0]
+    rates = np.ascontiguousarray(np.broadcast_to(np.asarray(sample_rates, np.float64), (S,)))
+    w = None if weights is None else np.ascontiguousarray(weights, np.float32)
+    assert w is None or w.shape == (channels,)
+    Z, blocks, gated, gains = np.full(S, -1.0), np.full(S, -1, np.int32), np.full(S, -1, np.int32), np.full(S, -1, np.float32)
+    powers = np.full((S, max(max_blocks, 1)), np.nan)
+    _check(lib, lib.smst_debug_clip_loudness(device, S, channels, seg.ctypes.data_as(_ip), C.c_void_p(image.ctypes.data), image_ss, image_cs, rates.ctypes.data_as(_dp),
+                                             None if w is None else w.ctypes.data_as(_fp), float(target), Z.ctypes.data_as(_dp), blocks.ctypes.data_as(_ip),
+                                             gated.ctypes.data_as(_ip), gains.ctypes.data_as(_fp), powers.ctypes.data_as(_dp), max_blocks))
+    return Z, blocks, gated, gains, powers[:, :max_blocks]
 
 
 def launch_count(name, lib=None):
@@ -643,6 +667,36 @@ class StretchBatch:
         _check(self.lib, self.lib.smst_batch_take_pcm_peaks(self.h, peaks.ctypes.data_as(_fp), gains.ctypes.data_as(_fp)))
         self._inflight = []
         return peaks, gains
+
+    def set_pcm_loudness(self, target_lufs, ceiling=float("inf"), sample_rate=48000.0, stream=-1):
+        """LEVEL_LOUDNESS (include/smst.h, "Loudness"), exactFrames only: the clip's ITU-R BS.1770-4 integrated loudness is measured on the
+        device at ``sample_rate`` -- the rate of the OUTPUT clip -- and the clip brought to ``target_lufs``, the gain lowered to ceiling/peak
+        where the clip would exceed the ceiling (inf: no limit).  stream = -1: every stream."""
+        _check(self.lib, self.lib.smst_batch_set_pcm_loudness(self.h, int(stream), float(target_lufs), float(ceiling), float(sample_rate)))
+
+    def pcm_loudness(self, stream):
+        """-> (target, sample_rate) of a stream in LEVEL_LOUDNESS"""
+        target, rate = C.c_double(0), C.c_double(0)
+        _check(self.lib, self.lib.smst_batch_pcm_loudness(self.h, int(stream), C.byref(target), C.byref(rate)))
+        return target.value, rate.value
+
+    def set_pcm_loudness_weights(self, weights=None):
+        """the channel weights of the loudness measurement, [C] (None: 1 on every channel)"""
+        if weights is None:
+            _check(self.lib, self.lib.smst_batch_set_pcm_loudness_weights(self.h, None))
+            return
+        w = np.ascontiguousarray(weights, np.float32)
+        if w.shape != (self.channels,):
+            raise StretchError("one weight per channel")
+        _check(self.lib, self.lib.smst_batch_set_pcm_loudness_weights(self.h, w.ctypes.data_as(_fp)))
+
+    def take_pcm_loudness(self):
+        """-> (lufs float64 [S], blocks, gated int32 [S]) of the newest exactFrames that measured: the loudness (-inf where it was undefined or
+        the stream was not measured), the blocks that passed the absolute gate and those that passed both.  Synchronises the batch."""
+        lufs, blocks, gated = np.zeros(self.streams), np.zeros(self.streams, np.int32), np.zeros(self.streams, np.int32)
+        _check(self.lib, self.lib.smst_batch_take_pcm_loudness(self.h, lufs.ctypes.data_as(_dp), blocks.ctypes.data_as(_ip), gated.ctypes.data_as(_ip)))
+        self._inflight = []
+        return lufs, blocks, gated
 
     # --- test hooks
     def debug_state(self, stream, which):

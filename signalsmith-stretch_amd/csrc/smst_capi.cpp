@@ -67,11 +67,13 @@ struct smst_batch {
 	PinnedBytes hPcmIn, hPcmOut;
 	// ... and, behind the counts, the dither entries of the call's output conversion ([S] smst::PcmDither, uploaded with the output counts by a
 	// call that dithers: pcmUploadDither)
-	struct PcmCounts { // [2*S]: input frames, output frames; [S] dither entries; [S] level entries
+	struct PcmCounts { // [2*S]: input frames, output frames; [S] dither entries; [S] level entries; [S] loudness entries; [kMaxChannels] channel weights
 		Buffer<int, true> host;
 		Buffer<int, false> dev;
 		const smst::PcmDither *dither = nullptr; // the call's entries in `dev`; null: the call does not dither
 		smst::PcmLevelIo level;                  // ... and its level entries, behind them, with the batch's meters; table null: the call is not levelled
+		const smst::LoudEntry *loud = nullptr;   // ... and its loudness entries and channel weights, behind those; null: no stream is in the loudness mode
+		const float *loudWeights = nullptr;
 	};
 	smst::TwoSets<PcmCounts> pcmCounts; // (smst_staging.h)
 	// dither of the int16 / int24 output (smst_batch_set_pcm_dither): per stream the mode, the seed, its hash and the frame counter
@@ -86,6 +88,11 @@ struct smst_batch {
 	struct PcmLevelState { int mode = SMST_LEVEL_FIXED; float gain = 1.0f, ceiling = 1.0f; };
 	std::vector<PcmLevelState> pcmLevel;
 	bool pcmLevelled = false;
+	// ... and, for a stream in SMST_LEVEL_LOUDNESS (smst_batch_set_pcm_loudness), the target, the sample rate and the table entry made of them
+	// (h == 0: another mode); the channel weights of the batch
+	struct PcmLoudState { double target = 0, sampleRate = 0; smst::LoudEntry entry{}; };
+	std::vector<PcmLoudState> pcmLoud;
+	std::vector<float> pcmLoudWeights;
 	Buffer<int, false> dPcmLevel;
 	std::vector<int> hPcmLevel;
 	~smst_batch() { if (engine) hipSetDevice(engine->device()); } // (the buffers above go behind it, the engine last)
@@ -210,6 +217,8 @@ int smst_batch_create_ex(smst_batch **out, int streams, int channels, int block,
 	b->dPcmOvers.allocate((size_t)2*streams, "PCM overs");
 	if (hipMemset(b->dPcmOvers, 0, pcmOversBytes(streams)) != hipSuccess) throw smst::Error("hipMemset (PCM overs) failed", true);
 	b->pcmLevel.assign((size_t)streams, smst_batch::PcmLevelState());
+	b->pcmLoud.assign((size_t)streams, smst_batch::PcmLoudState());
+	b->pcmLoudWeights.assign((size_t)channels, 1.0f);
 	pcmLevelStart(b->hPcmLevel, streams);
 	b->dPcmLevel.allocate((size_t)3*streams, "PCM level");
 	if (hipMemcpy(b->dPcmLevel, b->hPcmLevel.data(), pcmLevelBytes(streams), hipMemcpyHostToDevice) != hipSuccess) throw smst::Error("hipMemcpy (PCM level) failed", true);
@@ -437,7 +446,7 @@ static smst_batch::PcmCounts &beginPcmCall(smst_batch *b) {
 	smst_batch::PcmCounts &c = b->pcmCounts.begin();
 	if (!c.host) { // (both sets with the first call, as Batch::exact's segment tables: the second call allocates nothing)
 		++b->stagingAllocs;
-		const size_t ints = (size_t)2*e.streams() + (size_t)e.streams()*((sizeof(smst::PcmDither) + sizeof(smst::PcmLevel))/sizeof(int));
+		const size_t ints = (size_t)2*e.streams() + (size_t)e.streams()*((sizeof(smst::PcmDither) + sizeof(smst::PcmLevel) + sizeof(smst::LoudEntry))/sizeof(int)) + smst::kMaxChannels;
 		for (smst_batch::PcmCounts &t : b->pcmCounts.sets) {
 			t.host.allocate(ints, "PCM counts");
 			t.dev.allocate(ints, "PCM counts");
@@ -445,6 +454,8 @@ static smst_batch::PcmCounts &beginPcmCall(smst_batch *b) {
 	}
 	c.dither = nullptr;
 	c.level = smst::PcmLevelIo();
+	c.loud = nullptr;
+	c.loudWeights = nullptr;
 	return c;
 }
 // whether a call of this format dithers: a stream has a mode, and the format has a step to dither
@@ -456,11 +467,23 @@ static bool pcmDithers(const smst_batch *b, int format) {
 // ... if so the call's entries are filled -- every stream's mode and hash, and its frame counter as the index of the call's first frame --
 // and uploaded, with the S output counts in front of them where the call has some (still one copy); c.dither is where the kernels read
 // them.  A levelled batch's calls carry the streams' level entries behind the dither entries (which then travel whether the call dithers or
-// not: still one copy); c.level has them and the batch's meters.  The only place that knows that the entries lie behind the 2*S counts.
+// not: still one copy); c.level has them and the batch's meters.  Where a stream is in the loudness mode the streams' loudness entries and
+// the channel weights travel behind the level entries (still one copy); c.loud and c.loudWeights have them.  The only place that knows
+// that the entries lie behind the 2*S counts.
 static void pcmUploadDither(smst_batch *b, smst_batch::PcmCounts &c, int format, bool withOutCounts) {
 	Batch &e = *b->engine;
 	const size_t S = size_t(e.streams()), first = withOutCounts ? S : 2*S;
 	const bool dithered = pcmDithers(b, format), levelled = b->pcmLevelled;
+	bool loud = false;
+	if (levelled) for (const smst_batch::PcmLevelState &l : b->pcmLevel) loud = loud || l.mode == SMST_LEVEL_LOUDNESS;
+	if (loud) { // (S*(16 + 16) bytes behind the 2*S counts: 8-byte aligned, as the entries' doubles need)
+		smst::LoudEntry *t = reinterpret_cast<smst::LoudEntry *>(reinterpret_cast<smst::PcmLevel *>(reinterpret_cast<smst::PcmDither *>(c.host + 2*S) + S) + S);
+		for (size_t s = 0; s < S; ++s) t[s] = b->pcmLevel[s].mode == SMST_LEVEL_LOUDNESS ? b->pcmLoud[s].entry : smst::LoudEntry{};
+		float *w = reinterpret_cast<float *>(t + S);
+		for (int k = 0; k < smst::kMaxChannels; ++k) w[k] = k < e.channels() ? b->pcmLoudWeights[k] : 0.0f;
+		c.loud = reinterpret_cast<const smst::LoudEntry *>(reinterpret_cast<const smst::PcmLevel *>(reinterpret_cast<const smst::PcmDither *>(c.dev + 2*S) + S) + S);
+		c.loudWeights = reinterpret_cast<const float *>(c.loud + S);
+	}
 	if (levelled) {
 		smst::PcmLevel *t = reinterpret_cast<smst::PcmLevel *>(reinterpret_cast<smst::PcmDither *>(c.host + 2*S) + S);
 		for (size_t s = 0; s < S; ++s) t[s] = smst::PcmLevel{unsigned(b->pcmLevel[s].mode), b->pcmLevel[s].gain, b->pcmLevel[s].ceiling, 0u};
@@ -474,7 +497,8 @@ static void pcmUploadDither(smst_batch *b, smst_batch::PcmCounts &c, int format,
 		}
 		if (dithered) c.dither = reinterpret_cast<const smst::PcmDither *>(c.dev + 2*S);
 	}
-	const size_t bytes = (2*S - first)*sizeof(int) + (levelled ? S*(sizeof(smst::PcmDither) + sizeof(smst::PcmLevel)) : dithered ? S*sizeof(smst::PcmDither) : 0);
+	const size_t bytes = (2*S - first)*sizeof(int) + (levelled ? S*(sizeof(smst::PcmDither) + sizeof(smst::PcmLevel)) : dithered ? S*sizeof(smst::PcmDither) : 0)
+	                     + (loud ? S*sizeof(smst::LoudEntry) + smst::kMaxChannels*sizeof(float) : 0);
 	if (hipMemcpyAsync(c.dev + first, c.host + first, bytes, hipMemcpyHostToDevice, e.stream()) != hipSuccess) throw smst::Error("hipMemcpyAsync (H2D) failed", true);
 }
 // after a call that emitted n[s] frames: the counters of the streams that have a mode move on, whatever the call's format
@@ -594,7 +618,7 @@ int smst_batch_pcm_dither(const smst_batch *b, int stream, int *mode, long long 
 	return SMST_OK;
 }
 static void checkPcmLevel(int mode, float gain, float ceiling) {
-	if (mode != SMST_LEVEL_FIXED && mode != SMST_LEVEL_PROTECT && mode != SMST_LEVEL_NORMALISE) throw smst::Error("unknown level mode (SMST_LEVEL_FIXED, _PROTECT or _NORMALISE)");
+	if (mode != SMST_LEVEL_FIXED && mode != SMST_LEVEL_PROTECT && mode != SMST_LEVEL_NORMALISE) throw smst::Error("unknown level mode (SMST_LEVEL_FIXED, _PROTECT or _NORMALISE; smst_batch_set_pcm_loudness sets _LOUDNESS)");
 	if (!std::isfinite(gain)) throw smst::Error("level: the gain is not finite");
 	if (mode == SMST_LEVEL_PROTECT && !(gain > 0)) throw smst::Error("level: SMST_LEVEL_PROTECT needs a gain above 0");
 	if (mode != SMST_LEVEL_FIXED && !(std::isfinite(ceiling) && ceiling > 0)) throw smst::Error("level: the whole-clip modes need a finite ceiling above 0");
@@ -617,12 +641,61 @@ int smst_batch_pcm_level(const smst_batch *b, int stream, int *mode, float *gain
 	if (ceiling) *ceiling = l.ceiling;
 	return SMST_OK;
 }
+int smst_batch_set_pcm_loudness(smst_batch *b, int stream, double targetLufs, float ceiling, double sampleRate) {
+	BATCH_CALL({
+		const int S = b->engine->streams();
+		if (!std::isfinite(targetLufs)) throw smst::Error("loudness: the target is not finite");
+		if (!(ceiling > 0)) throw smst::Error("loudness: the ceiling is not above 0 (+inf: no limit)");
+		if (!(std::isfinite(sampleRate) && sampleRate > 0)) throw smst::Error("loudness: the sample rate is not finite or not above 0");
+		smst_batch::PcmLoudState l;
+		l.target = targetLufs; l.sampleRate = sampleRate;
+		if (!smst::loudEntryOf(sampleRate, targetLufs, l.entry)) throw smst::Error("loudness: the sample rate gives a 100-ms step of fewer than " + std::to_string(smst::kLoudChunk) + " samples (or is beyond 1e9)");
+		if (stream < -1 || stream >= S) throw smst::Error("stream index out of range");
+		for (int s = stream < 0 ? 0 : stream; s < (stream < 0 ? S : stream + 1); ++s) {
+			b->pcmLevel[s] = smst_batch::PcmLevelState{SMST_LEVEL_LOUDNESS, 1.0f, ceiling};
+			b->pcmLoud[s] = l;
+		}
+		b->pcmLevelled = true;
+	})
+}
+int smst_batch_pcm_loudness(const smst_batch *b, int stream, double *target, double *sampleRate) {
+	if (!b || !b->engine) return fail("null batch");
+	if (stream < 0 || stream >= b->engine->streams()) return fail("stream index out of range");
+	if (b->pcmLevel[stream].mode != SMST_LEVEL_LOUDNESS) return fail("the stream is not in SMST_LEVEL_LOUDNESS");
+	if (target) *target = b->pcmLoud[stream].target;
+	if (sampleRate) *sampleRate = b->pcmLoud[stream].sampleRate;
+	return SMST_OK;
+}
+int smst_batch_set_pcm_loudness_weights(smst_batch *b, const float *weights) {
+	BATCH_CALL({
+		const int C = b->engine->channels();
+		for (int c = 0; weights && c < C; ++c) if (!(std::isfinite(weights[c]) && weights[c] >= 0)) throw smst::Error("loudness: a channel weight is negative or not finite");
+		for (int c = 0; c < C; ++c) b->pcmLoudWeights[c] = weights ? weights[c] : 1.0f;
+	})
+}
+// Z and the count of gated blocks -> LUFS; -inf where loudness is undefined
+static double loudnessLufs(double Z, int gated) { return (gated > 0 && Z > 0 && std::isfinite(Z)) ? -0.691 + 10*std::log10(Z) : -INFINITY; }
+int smst_batch_take_pcm_loudness(smst_batch *b, double *lufs, int *blocks, int *gated) {
+	BATCH_CALL({
+		Batch &e = *b->engine;
+		const int S = e.streams();
+		e.synchronize();
+		std::vector<double> Z((size_t)S, 0.0);
+		std::vector<int> counts((size_t)2*S, 0);
+		e.readLoudness(Z.data(), counts.data()); // (false: no call has measured yet -- nothing is defined)
+		for (int s = 0; s < S; ++s) {
+			if (lufs) lufs[s] = loudnessLufs(Z[s], counts[2*s + 1]);
+			if (blocks) blocks[s] = counts[2*s];
+			if (gated) gated[s] = counts[2*s + 1];
+		}
+	})
+}
 // a streaming call knows no clip: refused, before anything runs, where a stream that takes part (active null: every one) has a whole-clip mode
 static void refuseWholeClipLevel(const smst_batch *b, const unsigned char *active) {
 	if (!b->pcmLevelled) return;
 	for (size_t s = 0; s < b->pcmLevel.size(); ++s)
 		if ((!active || active[s]) && b->pcmLevel[s].mode != SMST_LEVEL_FIXED)
-			throw smst::Error("stream " + std::to_string(s) + " has a whole-clip level mode (SMST_LEVEL_PROTECT / _NORMALISE): smst_batch_exact_pcm only");
+			throw smst::Error("stream " + std::to_string(s) + " has a whole-clip level mode (SMST_LEVEL_PROTECT / _NORMALISE / _LOUDNESS): smst_batch_exact_pcm only");
 }
 int smst_batch_process_pcm(smst_batch *b, const void *in, long long iss, long long ifs, const int *inSamples,
                            void *out, long long oss, long long ofs, const int *outSamples, int format, int memory) {
@@ -742,15 +815,20 @@ int smst_batch_exact_pcm(smst_batch *b, const void *in, long long iss, long long
 		const smst::PcmLevelIo level = table ? table->level : smst::PcmLevelIo();
 		std::vector<unsigned char> wholeClip;
 		if (level.table) for (const smst_batch::PcmLevelState &l : b->pcmLevel) wholeClip.push_back(l.mode != SMST_LEVEL_FIXED);
+		// ... and those in the loudness mode whether the four passes do: their entries and the channel weights ride there as well
+		std::vector<int> loudHop;
+		if (table && table->loud) for (size_t s = 0; s < b->pcmLevel.size(); ++s) loudHop.push_back(b->pcmLevel[s].mode == SMST_LEVEL_LOUDNESS ? b->pcmLoud[s].entry.h : 0);
+		const smst::LoudEntry *loud = loudHop.empty() ? nullptr : table->loud;
+		const float *loudWeights = loudHop.empty() ? nullptr : table->loudWeights;
 		if (memory == SMST_MEM_DEVICE) {
-			runExact(e, Batch::ClipIo{in, iss, ifs, out, oss, ofs, format, b->dPcmOvers, dither, level, wholeClip.data()}, inSamples, outSamples, status);
+			runExact(e, Batch::ClipIo{in, iss, ifs, out, oss, ofs, format, b->dPcmOvers, dither, level, wholeClip.data(), loud, loudWeights, loudHop.data()}, inSamples, outSamples, status);
 		} else {
 			const int S = e.streams(), C = e.channels();
 			std::vector<int> nIn, nOut;
 			const int mostIn = exactCounts(inSamples, outSamples, S, nIn), mostOut = exactCounts(outSamples, outSamples, S, nOut);
 			ensurePcmBytes(b, b->hPcmOut, b->dPcmOut, (size_t)S*pcmRowElems(mostOut, C)*pcmElemBytes(format));
 			pcmRawIn(b, in, iss, ifs, nIn.data(), mostIn, format);
-			runExact(e, Batch::ClipIo{b->dPcmIn, pcmRowElems(mostIn, C), C, b->dPcmOut, pcmRowElems(mostOut, C), C, format, b->dPcmOvers, dither, level, wholeClip.data()}, inSamples, outSamples, status);
+			runExact(e, Batch::ClipIo{b->dPcmIn, pcmRowElems(mostIn, C), C, b->dPcmOut, pcmRowElems(mostOut, C), C, format, b->dPcmOvers, dither, level, wholeClip.data(), loud, loudWeights, loudHop.data()}, inSamples, outSamples, status);
 			pcmRawOut(b, out, oss, ofs, nOut.data(), mostOut, format);
 		}
 		if (table) endPcmCall(b);
@@ -965,6 +1043,61 @@ int smst_debug_clip_copy_levelled(int device, int format, int streams, int chann
 	if (format == 0) return fail("clip copy: the levelled form writes frames of an SMST_PCM_* format");
 	if (!levelModes || !gains || !ceilings || !ditherModes || !seeds) return fail("clip copy: null level or dither arrays");
 	return clipCopy(device, 1, format, streams, channels, segments, src, srcSS, srcInner, dst, dstSS, dstInner, clamped, nans, levelModes, gains, ceilings, ditherModes, seeds, peaks, applied);
+}
+int smst_debug_clip_loudness(int device, int streams, int channels, const int *segments, const float *image, long long imageSS, long long imageCS,
+                             const double *sampleRates, const float *weights, double targetLufs, double *Z, int *blocks, int *gated, float *gains, double *blockPowers, int maxBlocks) {
+	SMST_TRY
+	if (streams < 1 || channels < 1 || channels > smst::kMaxChannels || !segments || !image || imageSS < 0 || imageCS < 0 || !sampleRates || maxBlocks < 0) throw smst::Error("clip loudness: bad arguments");
+	auto hip = [&](hipError_t err) { if (err != hipSuccess) throw smst::Error(std::string("clip loudness: ") + hipGetErrorString(err), true); };
+	std::vector<smst::LoudEntry> entries((size_t)streams);
+	int end = 0, most = 0, maxSub = 1;
+	for (int s = 0; s < streams; ++s) {
+		const int *g = segments + 8*s;
+		if (g[0] < 0 || g[2] < 0 || g[4] < 0 || g[6] < 0) throw smst::Error("clip loudness: negative segment offset or count");
+		if ((long long)g[2] + g[6] > 0x7fffffff) throw smst::Error("clip loudness: the clip is too long");
+		if (!smst::loudEntryOf(sampleRates[s], targetLufs, entries[s])) throw smst::Error("clip loudness: bad sample rate");
+		for (int k = 0; k < 2; ++k) if (g[4*k + 2] > 0 && !g[4*k + 3]) end = std::max(end, g[4*k] + g[4*k + 2]);
+		most = std::max(most, g[2] + g[6]);
+		maxSub = std::max(maxSub, (g[2] + g[6])/entries[s].h + 1);
+	}
+	std::vector<float> w((size_t)smst::kMaxChannels, 0.0f);
+	for (int c = 0; c < channels; ++c) {
+		w[c] = weights ? weights[c] : 1.0f;
+		if (!(std::isfinite(w[c]) && w[c] >= 0)) throw smst::Error("loudness: a channel weight is negative or not finite");
+	}
+	hip(hipSetDevice(device));
+	const size_t imageBytes = end ? size_t((streams - 1)*imageSS + (channels - 1)*imageCS + end)*sizeof(float) : 0;
+	const int maxChunks = std::max((most + smst::kLoudChunk - 1)/smst::kLoudChunk, 1);
+	Buffer<unsigned char, false> dImage, dSegs, dEntries, dWeights;
+	Buffer<double, false> dScratch;
+	dImage.allocate(imageBytes + 32, "clip loudness");
+	dSegs.allocate((size_t)2*streams*sizeof(smst::ClipSeg), "clip loudness");
+	dEntries.allocate(entries.size()*sizeof(smst::LoudEntry), "clip loudness");
+	dWeights.allocate(w.size()*sizeof(float), "clip loudness");
+	dScratch.allocate(smst::loudScratchDoubles(streams, channels, maxChunks, maxSub), "clip loudness");
+	unsigned char *i0 = dImage + reinterpret_cast<uintptr_t>(image)%16; // (as far behind a 16-byte boundary as the caller's image)
+	if (imageBytes) hip(hipMemcpy(i0, image, imageBytes, hipMemcpyHostToDevice));
+	hip(hipMemcpy(dSegs, segments, (size_t)2*streams*sizeof(smst::ClipSeg), hipMemcpyHostToDevice));
+	hip(hipMemcpy(dEntries, entries.data(), entries.size()*sizeof(smst::LoudEntry), hipMemcpyHostToDevice));
+	hip(hipMemcpy(dWeights, w.data(), w.size()*sizeof(float), hipMemcpyHostToDevice));
+	const smst::LoudScratch at = smst::loudScratchAt(dScratch, streams, channels, maxChunks, maxSub);
+	smst::launchClipLoudness(reinterpret_cast<const float *>(i0), imageSS, imageCS, reinterpret_cast<const smst::ClipSeg *>(dSegs.p), streams, channels,
+	                         reinterpret_cast<const smst::LoudEntry *>(dEntries.p), reinterpret_cast<const float *>(dWeights.p), at, nullptr);
+	hip(hipGetLastError());
+	hip(hipStreamSynchronize(nullptr));
+	std::vector<int> counts((size_t)2*streams);
+	hip(hipMemcpy(counts.data(), at.counts, counts.size()*sizeof(int), hipMemcpyDeviceToHost));
+	if (Z) hip(hipMemcpy(Z, at.Z, (size_t)streams*sizeof(double), hipMemcpyDeviceToHost));
+	if (gains) hip(hipMemcpy(gains, at.gain, (size_t)streams*sizeof(float), hipMemcpyDeviceToHost));
+	for (int s = 0; s < streams; ++s) {
+		if (blocks) blocks[s] = counts[2*s];
+		if (gated) gated[s] = counts[2*s + 1];
+		const int *g = segments + 8*s;
+		const int N = (g[3] || g[7]) ? 0 : g[2] + g[6], h = entries[s].h, nb = N >= 4*h ? (N - 4*h)/h + 1 : 0;
+		if (blockPowers && std::min(nb, maxBlocks) > 0) hip(hipMemcpy(blockPowers + (size_t)s*maxBlocks, at.z + (size_t)s*maxSub, (size_t)std::min(nb, maxBlocks)*sizeof(double), hipMemcpyDeviceToHost));
+	}
+	return SMST_OK;
+	SMST_CATCH
 }
 int smst_batch_take_pcm_overs(smst_batch *b, long long *clamped, long long *nans) {
 	BATCH_CALL({

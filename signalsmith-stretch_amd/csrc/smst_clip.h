@@ -42,10 +42,12 @@ template <typename T> __global__ __launch_bounds__(256) void kClipIn(const T *__
 // Level: every workgroup forms its stream's gain by the same few correctly rounded fp32 operations (clipGain), so all of a clip's workgroups
 // agree on it without another launch; the workgroup of the first tile of the stream's first segment that has a source reports it in
 // level.applied[s]; a run of zeros is not levelled, metered or reported
-__device__ inline float clipGain(const PcmLevel &l, int peakBits) {
-	if (l.mode == kPcmLevelFixed || peakBits <= 0 || peakBits >= 0x7f800000) return l.gain; // (no peak, or none to divide by: the plain gain)
+// loudGain: gL of a stream in the loudness mode (kLoudGate's, smst_loudness.h), which takes the place of the entry's gain
+__device__ inline float clipGain(const PcmLevel &l, int peakBits, float loudGain) {
+	const float gain = l.mode == kPcmLevelLoudness ? loudGain : l.gain;
+	if (l.mode == kPcmLevelFixed || peakBits <= 0 || peakBits >= 0x7f800000) return gain; // (no peak, or none to divide by: the plain gain)
 	const float q = l.ceiling/__int_as_float(peakBits);
-	return (l.mode == kPcmLevelNormalise || !(l.gain <= q)) ? q : l.gain;
+	return (l.mode == kPcmLevelNormalise || !(gain <= q)) ? q : gain;
 }
 template <typename T, bool Dith, bool Level> __global__ __launch_bounds__(256) void kClipOut(const float *__restrict__ image, long long imageStreamStride, long long imageChannelStride,
 		T *__restrict__ out, long long outStreamStride, long long outFrameStride, const ClipSeg *__restrict__ segs, int C, unsigned *__restrict__ overs, const PcmDither *__restrict__ dither,
@@ -60,7 +62,7 @@ template <typename T, bool Dith, bool Level> __global__ __launch_bounds__(256) v
 	unsigned over;
 	if constexpr (Level) {
 		const PcmLevel l = level.table[s];
-		const float gain = clipGain(l, l.mode == kPcmLevelFixed ? 0 : level.clipPeak[s]);
+		const float gain = clipGain(l, l.mode == kPcmLevelFixed ? 0 : level.clipPeak[s], l.mode == kPcmLevelLoudness && level.loudGain ? level.loudGain[s] : 1.0f);
 		unsigned peak;
 		if (!pcmTileOut<T, Dith, true>(src, imageChannelStride, out + (size_t)s*outStreamStride + (size_t)g.dst*outFrameStride, outFrameStride, g.count, blockIdx.x, C, reinterpret_cast<float *>(smemRaw), over, dp, gain, &peak)) return;
 		if (src) {

@@ -169,7 +169,7 @@ __host__ __device__ inline bool analysisWindowInCall(int B, int M, int I, int in
 // form" tests assert through these that BOTH forms really ran.
 enum LaunchKind {
 	LK_VOC_ALIGNED, LK_VOC_TWISTED, LK_VOC_INTERIOR, LK_VOC_STAGED, LK_VOC_GATHER, LK_VOC_N, LK_VOC_ONE, LK_VOC_ACROSS, LK_VOC_CONT, LK_CHAIN_UNFUSED,
-	LK_ANALYSE_TEAMS, LK_ANALYSE_PAIRS, LK_ANALYSE_TWIST, LK_TWIST_ROWS, LK_ANALYSE_FAST, LK_ANALYSE_GENERIC, LK_SYNTH_TEAMS, LK_SYNTH_FAST, LK_SYNTH_GENERIC, LK_SYNTH_EMIT, LK_EMIT_CARRIED, LK_FEED_ONE_PASS, LK_PCM_IN, LK_PCM_OUT, LK_CLIP_IN, LK_CLIP_OUT, LK_PCM_OUT_DITHERED, LK_CLIP_OUT_DITHERED, LK_PCM_OUT_LEVELLED, LK_CLIP_OUT_LEVELLED, LK_CLIP_PEAK, LK_COUNT
+	LK_ANALYSE_TEAMS, LK_ANALYSE_PAIRS, LK_ANALYSE_TWIST, LK_TWIST_ROWS, LK_ANALYSE_FAST, LK_ANALYSE_GENERIC, LK_SYNTH_TEAMS, LK_SYNTH_FAST, LK_SYNTH_GENERIC, LK_SYNTH_EMIT, LK_EMIT_CARRIED, LK_FEED_ONE_PASS, LK_PCM_IN, LK_PCM_OUT, LK_CLIP_IN, LK_CLIP_OUT, LK_PCM_OUT_DITHERED, LK_CLIP_OUT_DITHERED, LK_PCM_OUT_LEVELLED, LK_CLIP_OUT_LEVELLED, LK_CLIP_PEAK, LK_CLIP_LOUDNESS, LK_COUNT
 };
 long long launchCount(const char *name); // -1: unknown name
 
@@ -232,8 +232,9 @@ inline unsigned pcmDitherHash(long long seed) {
 // NaN skipped, and applied[s] the gain g it used.  kPcmOut knows the fixed gain only; kClipOut derives a whole-clip gain from clipPeak[s],
 // the peak of the stream's clip that kClipPeak left there.  table == null: the unlevelled kernels, as before; nothing else is read.
 struct PcmLevel { unsigned mode; float gain, ceiling; unsigned pad; };
-constexpr unsigned kPcmLevelFixed = 0u, kPcmLevelProtect = 1u, kPcmLevelNormalise = 2u;
-struct PcmLevelIo { const PcmLevel *table = nullptr; int *peaks = nullptr; float *applied = nullptr; int *clipPeak = nullptr; };
+// kClipOut takes the loudness mode's gain gL from loudGain[s], which kLoudGate (smst_loudness.h) left there, and limits it by ceiling/peak.
+constexpr unsigned kPcmLevelFixed = 0u, kPcmLevelProtect = 1u, kPcmLevelNormalise = 2u, kPcmLevelLoudness = 3u;
+struct PcmLevelIo { const PcmLevel *table = nullptr; int *peaks = nullptr; float *applied = nullptr; int *clipPeak = nullptr; const float *loudGain = nullptr; };
 void launchPcmOut(int format, const float *in, long long inStreamStride, long long inChannelStride, void *out, long long outStreamStride, long long outFrameStride,
                   const int *counts, int S, int C, int maxFrames, unsigned *overs, hipStream_t st, const PcmDither *dither = nullptr, const PcmLevelIo &level = PcmLevelIo());
 // Whole clips of ragged lengths (smst_clip.h; Batch::exact): each stream moves two segments of frames between the caller's buffer and a planar
@@ -249,5 +250,34 @@ void launchClipOut(int format, const float *image, long long imageStreamStride, 
 // The peak of every stream's clip -- the largest |v| of the image's samples that the segments cover, NaN skipped -- maxed into clipPeak[s]
 // (the caller zeroes the words in front of it): the pass of a levelled clip call in which a stream has a whole-clip mode
 void launchClipPeak(const float *image, long long imageStreamStride, long long imageChannelStride, const ClipSeg *segs, int S, int C, int maxCount, int *clipPeak, hipStream_t st);
+// Integrated loudness of every stream's clip (include/smst.h, "Loudness", has the definition; smst_loudness.h the kernels).  One entry per
+// stream, device: the two biquads' coefficients, the cascade's transition matrix to the power of the chunk length, the target power P, the
+// absolute gate and the hop h of the 100-ms sub-blocks; h == 0: the stream is not measured.  All of it float64, computed by the host
+// (loudEntryOf; false: the sample rate gives h < kLoudChunk).
+constexpr int kLoudChunk = 256; // frames of a channel's clip, in clip order, that one lane filters
+struct LoudCoef { double b0, b1, b2, a1, a2, d1, d2; }; // shelf: b0 b1 b2 / 1 a1 a2; high-pass: 1 -2 1 / 1 d1 d2
+struct LoudEntry { LoudCoef k; double Ac[16], P, gate; int h, pad; };
+bool loudEntryOf(double sampleRate, double targetLufs, LoudEntry &e);
+// The passes' scratch, all float64 but the meters' last two: per stream the meters -- Z, the two block counts, gL --, per (stream, channel,
+// chunk) the chunk's end state (then its incoming state) and its two partial sums, per (stream, channel) the sub-block sums, per stream the
+// block powers.  maxChunks / maxSub: of the longest measured clip (loudScratchAt lays out `base`, which holds loudScratchDoubles)
+struct LoudScratch { double *Z; int *counts; float *gain; double *ends, *partials, *sub, *z; int maxChunks, maxSub; };
+inline size_t loudScratchDoubles(int S, int C, int maxChunks, int maxSub) { return (size_t)2*S + (S + 1)/2 + (size_t)S*C*maxChunks*6 + (size_t)S*C*maxSub + (size_t)S*maxSub; }
+inline LoudScratch loudScratchAt(double *base, int S, int C, int maxChunks, int maxSub) {
+	LoudScratch w;
+	double *p = base;
+	w.Z = p; p += S;
+	w.counts = reinterpret_cast<int *>(p); p += S;
+	w.gain = reinterpret_cast<float *>(p); p += (S + 1)/2;
+	w.ends = p; p += (size_t)S*C*maxChunks*4;
+	w.partials = p; p += (size_t)S*C*maxChunks*2;
+	w.sub = p; p += (size_t)S*C*maxSub;
+	w.z = p;
+	w.maxChunks = maxChunks; w.maxSub = maxSub;
+	return w;
+}
+// the four passes, on `st`: every stream's meters are written (a stream that is not measured: Z 0, no blocks, gL 1)
+void launchClipLoudness(const float *image, long long imageStreamStride, long long imageChannelStride, const ClipSeg *segs, int S, int C,
+                        const LoudEntry *loud, const float *weights, const LoudScratch &w, hipStream_t st);
 
 } // namespace smst

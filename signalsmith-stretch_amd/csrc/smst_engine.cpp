@@ -1838,11 +1838,35 @@ void Batch::exact(const ClipIo &io, const int *inSamples, const int *outSamples,
 		SMST_HIP(hipMemsetAsync(io.level.clipPeak, 0, (size_t)S*sizeof(int), st));
 		launchClipPeak(dClipOut, outImgSS, pitchOut, cs.dev + (size_t)2*S, S, C, std::max(maxProc, maxFlush), io.level.clipPeak, st);
 	}
+	PcmLevelIo level = io.level;
+	int loudMost = 0, loudSub = 0;
+	if (wholeClip && io.loudHop) for (int s = 0; s < S; ++s) if (run[s] && io.loudHop[s] > 0) {
+		loudMost = std::max(loudMost, outSamples[s]);
+		loudSub = std::max(loudSub, outSamples[s]/io.loudHop[s] + 1);
+	}
+	if (loudMost > 0) { // the clips' loudness, from the same image: the meters hold what kClipOut forms those streams' gains from
+		const int maxChunks = (loudMost + kLoudChunk - 1)/kLoudChunk;
+		const size_t doubles = loudScratchDoubles(S, C, maxChunks, loudSub);
+		growScratch(dLoud, loudCapacity, 2*doubles, doubles/4 + 1024, true);
+		const LoudScratch w = loudScratchAt(reinterpret_cast<double *>(dLoud), S, C, maxChunks, loudSub);
+		launchClipLoudness(dClipOut, outImgSS, pitchOut, cs.dev + (size_t)2*S, S, C, io.loud, io.loudWeights, w, st);
+		level.loudGain = w.gain;
+	}
 	launchClipOut(io.format, dClipOut, outImgSS, pitchOut, io.out, io.outStreamStride, io.outInnerStride, cs.dev + (size_t)2*S, S, C,
-	              std::max(std::max(direct ? 0 : maxProc, maxFlush), maxZeros), io.overs, st, io.dither, io.level);
+	              std::max(std::max(direct ? 0 : maxProc, maxFlush), maxZeros), io.overs, st, io.dither, level);
 	clipSets.end(st);
 	SMST_HIP(hipGetLastError());
 	if (tooShort) for (int s = 0; s < S; ++s) if (outSamples[s] >= 0) tooShort[s] = run[s] ? 0 : 1; // (only once every stage has been issued)
+}
+
+bool Batch::readLoudness(double *Z, int *counts) {
+	if (!dLoud) return false;
+	SMST_HIP(hipSetDevice(dev));
+	SMST_HIP(hipStreamSynchronize(st));
+	const LoudScratch w = loudScratchAt(reinterpret_cast<double *>(dLoud), S, C, 0, 0); // (the meters lie in front, whatever the call's shapes)
+	SMST_HIP(hipMemcpy(Z, w.Z, (size_t)S*sizeof(double), hipMemcpyDeviceToHost));
+	SMST_HIP(hipMemcpy(counts, w.counts, (size_t)2*S*sizeof(int), hipMemcpyDeviceToHost));
+	return true;
 }
 
 // ---- copy -------------------------------------------------------------------------------------------------

@@ -108,7 +108,12 @@ public:
 	// be null): 1 for such a stream, 0 for the others that take part, written once every stage has been issued; a stream left out keeps its entry.  overs (device, may be null): [S][2] counters of the frame conversion.
 	// Counts are checked by the caller: outSamples[s] != 0, inSamples[s] >= 0 where outSamples[s] > 0.
 	struct ClipIo { const void *in; long long inStreamStride, inInnerStride; void *out; long long outStreamStride, outInnerStride; int format; unsigned *overs; const PcmDither *dither = nullptr; // dither: [S] device, or null (smst_device.h)
-		PcmLevelIo level; const unsigned char *wholeClip = nullptr; }; // level.table set: a levelled call (frame formats); wholeClip (host, [S]): which streams' gains come from their clip's peak -- if one of them runs, kClipPeak does
+		PcmLevelIo level; const unsigned char *wholeClip = nullptr; // level.table set: a levelled call (frame formats); wholeClip (host, [S]): which streams' gains come from their clip's peak -- if one of them runs, kClipPeak does
+		// loudness (smst_loudness.h): loud ([S] device) and loudWeights ([C] device) ride in the caller's per-call table; loudHop (host, [S]): h of the
+		// streams in the loudness mode, 0 for the others -- if one of them runs, the four passes do, and kClipOut finds the gains in the engine's meters
+		const LoudEntry *loud = nullptr; const float *loudWeights = nullptr; const int *loudHop = nullptr; };
+	// the loudness meters of the newest exact call that measured, [S] and [S][2] (blocks past the absolute gate, past both); false: none has.  Synchronises
+	bool readLoudness(double *Z, int *counts);
 	void exact(const ClipIo &io, const int *inSamples, const int *outSamples, unsigned char *tooShort);
 	void synchronize();
 
@@ -292,6 +297,8 @@ private:
 	// per-call tables are (a call returns before its last kernel has run)
 	float *dClipIn = nullptr, *dClipOut = nullptr;
 	size_t clipInCapacity = 0, clipOutCapacity = 0;
+	float *dLoud = nullptr; // the loudness passes' scratch (LoudScratch: float64, the meters in front), grown on demand as the images are
+	size_t loudCapacity = 0;
 	struct ClipSet { ClipSeg *host, *dev; }; // [2][S][2]: input segments, output segments
 	TwoSets<ClipSet> clipSets;
 	// a device scratch that holds `need` floats, allocated with `room` more; true: it was replaced (the old one freed behind a synchronise).  workspace: counted in workspaceBytes()

@@ -10,6 +10,8 @@ the host from its first entry point to the return of smst_batch_synchronize.
   python tools/bench_exact.py --mode pcm          # smst_batch_exact_pcm on int16 frames (also on a build without the level calls: SMST_LIBRARY)
   python tools/bench_exact.py --mode level        # pcm, fixed (a gain of 0.5 on every stream) and protect (ceiling 32766/32768) alternating step by
                                                   # step, a batch each: fixed - pcm = the levelled copy kernel, protect - fixed = the peak pass
+  python tools/bench_exact.py --mode normalise --loudness   # NORMALISE and LOUDNESS (-23 LUFS at --sample-rate) alternating: loudness - normalise =
+                                                  # the four loudness passes (mode normalise alone also runs on a build without them: SMST_LIBRARY)
 """
 import argparse
 import ctypes as C
@@ -31,7 +33,8 @@ smst = importlib.import_module("signalsmith-stretch_amd")
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--mode", choices=["three", "exact", "ragged", "pcm", "fixed", "protect", "level"], required=True)
+    ap.add_argument("--mode", choices=["three", "exact", "ragged", "pcm", "fixed", "protect", "level", "normalise"], required=True)
+    ap.add_argument("--loudness", action="store_true", help="frame modes: a batch in LEVEL_LOUDNESS (-23 LUFS, ceiling 32766/32768) beside the mode's own")
     ap.add_argument("--streams", type=int, default=256)
     ap.add_argument("--channels", type=int, default=2)
     ap.add_argument("--seconds", type=float, default=10.0)
@@ -79,7 +82,7 @@ def main():
         smst._check(lib, lib.smst_batch_exact(b.h, C.c_void_p(x.data_ptr()), Cn*n, n, ip(nin), C.c_void_p(y.data_ptr()), Cn*most, most, ip(nout), ip(status), smst.MEM_DEVICE))
         assert not status.any(), status
 
-    if a.mode in ("pcm", "fixed", "protect", "level"):
+    if a.mode in ("pcm", "fixed", "protect", "level", "normalise"):
         return frames_modes(a, lib, x, nin, nout, batch)
     call = three if a.mode == "three" else exact
     b = batch()
@@ -115,12 +118,16 @@ def frames_modes(a, lib, x, nin, nout, batch):
     torch.cuda.synchronize()
     ip = lambda v: v.ctypes.data_as(C.POINTER(C.c_int))
     runs = {}
-    for name in (("pcm", "fixed", "protect") if a.mode == "level" else (a.mode,)):
+    for name in (("pcm", "fixed", "protect") if a.mode == "level" else (a.mode,)) + (("loudness",) if a.loudness else ()):
         b = batch()
         if name == "fixed":
             b.set_pcm_level(smst.LEVEL_FIXED, 0.5)
         if name == "protect":
             b.set_pcm_level(smst.LEVEL_PROTECT, 1.0, 32766.0/32768.0)
+        if name == "normalise":
+            b.set_pcm_level(smst.LEVEL_NORMALISE, 1.0, 32766.0/32768.0)
+        if name == "loudness":
+            b.set_pcm_loudness(-23.0, 32766.0/32768.0, a.sample_rate)
         runs[name] = b
 
     def call(b):
@@ -146,6 +153,12 @@ def frames_modes(a, lib, x, nin, nout, batch):
                                peak_pass_bytes=int(S)*Cn*int(nout.sum()//S)*4)
         peaks, gains = runs["protect"].take_pcm_peaks()
         result["level"]["protect_gain_range"] = [float(gains.min()), float(gains.max())]
+    if a.loudness:
+        lufs, blocks, gated = runs["loudness"].take_pcm_loudness()
+        result["loudness"] = dict(lufs_range=[float(lufs.min()), float(lufs.max())], gated_blocks=[int(gated.min()), int(gated.max())],
+                                  image_bytes=int(S)*Cn*int(nout.sum()//S)*4)
+        if a.mode in result["step_ms"]:
+            result["loudness"]["minus_%s_ms" % a.mode] = round(result["step_ms"]["loudness"]["median"] - result["step_ms"][a.mode]["median"], 3)
     print(json.dumps(result))
     for b in runs.values():
         b.close()

@@ -5,7 +5,7 @@
 //
 //   stretch_cli [--semitones=S] [--formant=S] [--formant-comp] [--formant-base=Hz] [--tonality=Hz] [--time=F]
 //               [--split-computation] [--device=N] [--out-format=s16|s24|f32] [--dither=none|tpdf|tpdf-hp] [--dither-seed=N]
-//               [--exact] [--gain=dB] [--protect=dBFS | --normalize=dBFS]
+//               [--exact] [--gain=dB] [--protect=dBFS | --normalize=dBFS] [--loudness=LUFS]
 //               in.wav out.wav [in2.wav out2.wav ...]
 //
 // --out-format (also "--out-format s24"): the samples of the files written -- 16-bit (the default, as the reference's CLI writes), 24-bit by the
@@ -22,6 +22,10 @@
 // rendered clip's own peak -- lowered (from --gain, or 0 dB) only where the clip would exceed the ceiling, or set so that the peak meets
 // it.  INTEGRATION.md says which ceiling keeps an integer format free of clamped samples.  dB -> linear: float(pow(10, dB/20)).  With any
 // of the three, one line per file: "level: <file> peak=<%.9g> gain=<%.9g> overs=<clamped samples>" -- the peak before the gain.
+// --loudness=LUFS (implies --exact; not with --normalize): every rendered clip is brought to that integrated loudness (ITU-R BS.1770-4,
+// measured on the GPU at the files' sample rate; include/smst.h, "Loudness"), with --protect=dBFS as the ceiling that limits the gain
+// (none without it; --gain is not used).  The line then reads "level: <file> loudness=<%.4f> peak=... gain=... overs=...": the measured
+// loudness in LUFS before the gain, -inf for a clip that has none (shorter than 400 ms, silent).
 // Files given together must share sample rate and channel count (they form one batch); lengths may differ.
 #include <algorithm>
 #include <cmath>
@@ -91,7 +95,12 @@ int main(int argc, char **argv) {
 		std::fprintf(stderr, "--protect and --normalize exclude each other\n");
 		return 2;
 	}
-	const bool exact = hasFlag(argc, argv, "exact") || protect || normalize, levelled = hasGain || protect || normalize;
+	const bool loudness = hasValue(argc, argv, "loudness");
+	if (loudness && normalize) {
+		std::fprintf(stderr, "--loudness and --normalize exclude each other\n");
+		return 2;
+	}
+	const bool exact = hasFlag(argc, argv, "exact") || protect || normalize || loudness, levelled = hasGain || protect || normalize || loudness;
 	const float gain = fromDecibels(flagValue(argc, argv, "gain", 0)), ceiling = fromDecibels(flagValue(argc, argv, protect ? "protect" : "normalize", 0));
 	std::vector<std::string> files;
 	for (int i = 1; i < argc; ++i) if (std::strncmp(argv[i], "--", 2) && !consumed[i]) files.push_back(argv[i]);
@@ -149,7 +158,8 @@ int main(int argc, char **argv) {
 		const size_t esz = size_t(bits/8);
 		const float scale = bits == 24 ? 8388608.0f : 32768.0f;
 		if (dither != SMST_DITHER_NONE) CHECK(smst_batch_set_pcm_dither(batch, -1, dither, ditherSeed));
-		if (levelled) CHECK(smst_batch_set_pcm_level(batch, -1, protect ? SMST_LEVEL_PROTECT : normalize ? SMST_LEVEL_NORMALISE : SMST_LEVEL_FIXED, gain, ceiling));
+		if (loudness) CHECK(smst_batch_set_pcm_loudness(batch, -1, flagValue(argc, argv, "loudness", 0), protect ? ceiling : INFINITY, double(inputs[0].sampleRate)));
+		else if (levelled) CHECK(smst_batch_set_pcm_level(batch, -1, protect ? SMST_LEVEL_PROTECT : normalize ? SMST_LEVEL_NORMALISE : SMST_LEVEL_FIXED, gain, ceiling));
 		// `count` samples of file s from sample `first` on as frames at `frames`; false: one of them is no value of the format
 		auto toFrames = [&](int s, int first, int count, unsigned char *frames) {
 			for (int i = 0; i < count; ++i) for (int c = 0; c < C; ++c) {
@@ -193,7 +203,13 @@ int main(int argc, char **argv) {
 			std::vector<float> peaks(S, 0.0f), gains(S, 1.0f);
 			CHECK(smst_batch_take_pcm_overs(batch, clamped.data(), nullptr));
 			CHECK(smst_batch_take_pcm_peaks(batch, peaks.data(), gains.data()));
-			for (int s = 0; s < S; ++s) std::printf("level: %s peak=%.9g gain=%.9g overs=%lld\n", files[2*s + 1].c_str(), peaks[s], gains[s], clamped[s]);
+			std::vector<double> lufs(S, 0.0);
+			if (loudness) CHECK(smst_batch_take_pcm_loudness(batch, lufs.data(), nullptr, nullptr));
+			for (int s = 0; s < S; ++s) {
+				std::printf("level: %s ", files[2*s + 1].c_str());
+				if (loudness) std::printf("loudness=%.4f ", lufs[s]);
+				std::printf("peak=%.9g gain=%.9g overs=%lld\n", peaks[s], gains[s], clamped[s]);
+			}
 		}
 		for (int s = 0; s < S; ++s) {
 			if (!writeWavFrames(files[2*s + 1], inputs[s].sampleRate, inputs[s].channels, bits, outFrames.data() + (size_t)s*maxOut*C*esz, size_t(outLen[s]), error, format == SMST_PCM_F32)) {
