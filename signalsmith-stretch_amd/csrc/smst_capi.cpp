@@ -55,46 +55,184 @@ typedef Buffer<float, true, 1024> PinnedFloats;
 typedef Buffer<unsigned char, false, 4096> DeviceBytes;
 typedef Buffer<unsigned char, true, 4096> PinnedBytes;
 
+static size_t pcmOversBytes(int streams) { return (size_t)2*streams*sizeof(unsigned); }
+static void checkDitherMode(int mode) {
+	if (mode != SMST_DITHER_NONE && mode != SMST_DITHER_TPDF && mode != SMST_DITHER_TPDF_HP) throw smst::Error("unknown dither mode (SMST_DITHER_NONE, _TPDF or _TPDF_HP)");
+}
+static void checkPcmLevel(int mode, float gain, float ceiling) {
+	if (mode != SMST_LEVEL_FIXED && mode != SMST_LEVEL_PROTECT && mode != SMST_LEVEL_NORMALISE) throw smst::Error("unknown level mode (SMST_LEVEL_FIXED, _PROTECT or _NORMALISE; smst_batch_set_pcm_loudness sets _LOUDNESS)");
+	if (!std::isfinite(gain)) throw smst::Error("level: the gain is not finite");
+	if (mode == SMST_LEVEL_PROTECT && !(gain > 0)) throw smst::Error("level: SMST_LEVEL_PROTECT needs a gain above 0");
+	if (mode != SMST_LEVEL_FIXED && !(std::isfinite(ceiling) && ceiling > 0)) throw smst::Error("level: the whole-clip modes need a finite ceiling above 0");
+}
+
+// The output side of a batch's frame-format calls: what the setters set per stream, and what the conversion kernels count and meter.  A call's
+// share of it travels in the call's table (smst_pcm_tables.h): fill() writes it there.  The owner has selected the device wherever HIP is called.
+struct PcmOutState {
+	int S = 0, C = 0;
+	// dither of the int16 / int24 output (smst_batch_set_pcm_dither): the mode, the seed, its hash and the frame counter
+	struct Dither { int mode = SMST_DITHER_NONE; long long seed = 0; unsigned h = 0; unsigned long long frames = 0; };
+	// level (smst_batch_set_pcm_level): the mode, the gain and the ceiling; the batch is a levelled one from the first set on
+	struct Level { int mode = SMST_LEVEL_FIXED; float gain = 1.0f, ceiling = 1.0f; };
+	// ... and, for a stream in SMST_LEVEL_LOUDNESS (smst_batch_set_pcm_loudness), the target, the sample rate and the table entry made of them
+	struct Loud { double target = 0, sampleRate = 0; smst::LoudEntry entry{}; };
+	std::vector<Dither> dither;
+	std::vector<Level> level;
+	std::vector<Loud> loud;
+	std::vector<float> loudWeights; // [C], the batch's
+	bool levelled = false;
+	// overs ([S][2]: clamped, NaN): the kernels add to them, takeOvers() reads and clears them; the meter words (smst::PcmMeters)
+	Buffer<unsigned, false> dOvers;
+	Buffer<int, false> dMeters;
+	std::vector<unsigned> hOvers;
+	std::vector<int> hMeters;
+	std::vector<unsigned char> wholeClip; // clipModes()' arrays
+	std::vector<int> loudHop;
+
+	void create(int streams, int channels) {
+		S = streams; C = channels;
+		const smst::PcmMeters meters(S);
+		dither.assign((size_t)S, Dither());
+		level.assign((size_t)S, Level());
+		loud.assign((size_t)S, Loud());
+		loudWeights.assign((size_t)C, 1.0f);
+		wholeClip.assign((size_t)S, 0);
+		loudHop.assign((size_t)S, 0);
+		hOvers.assign((size_t)2*S, 0u);
+		dOvers.allocate((size_t)2*S, "PCM overs");
+		if (hipMemset(dOvers, 0, pcmOversBytes(S)) != hipSuccess) throw smst::Error("hipMemset (PCM overs) failed", true);
+		hMeters.resize(meters.words());
+		meters.start(hMeters.data());
+		dMeters.allocate(meters.words(), "PCM level");
+		if (hipMemcpy(dMeters, hMeters.data(), meters.bytes(), hipMemcpyHostToDevice) != hipSuccess) throw smst::Error("hipMemcpy (PCM level) failed", true);
+	}
+	size_t workspaceBytes() const { return (dOvers ? pcmOversBytes(S) : 0) + (dMeters ? smst::PcmMeters(S).bytes() : 0); }
+
+	// f(s) for the streams that `stream` names: -1 is every one
+	template <typename F> void forStreams(int stream, F f) {
+		if (stream < -1 || stream >= S) throw smst::Error("stream index out of range");
+		for (int s = stream < 0 ? 0 : stream; s < (stream < 0 ? S : stream + 1); ++s) f(s);
+	}
+	void setDither(int stream, int mode, long long seed) {
+		checkDitherMode(mode);
+		forStreams(stream, [&](int s) {
+			Dither &d = dither[s];
+			d.mode = mode;
+			d.seed = stream < 0 ? (long long)((unsigned long long)seed + (unsigned long long)s) : seed;
+			d.h = smst::pcmDitherHash(d.seed);
+			d.frames = 0;
+		});
+	}
+	void setLevel(int stream, int mode, float gain, float ceiling) {
+		checkPcmLevel(mode, gain, ceiling);
+		forStreams(stream, [&](int s) { level[s] = Level{mode, gain, ceiling}; });
+		levelled = true;
+	}
+	void setLoudness(int stream, double targetLufs, float ceiling, double sampleRate) {
+		if (!std::isfinite(targetLufs)) throw smst::Error("loudness: the target is not finite");
+		if (!(ceiling > 0)) throw smst::Error("loudness: the ceiling is not above 0 (+inf: no limit)");
+		if (!(std::isfinite(sampleRate) && sampleRate > 0)) throw smst::Error("loudness: the sample rate is not finite or not above 0");
+		Loud l;
+		l.target = targetLufs; l.sampleRate = sampleRate;
+		if (!smst::loudEntryOf(sampleRate, targetLufs, l.entry)) throw smst::Error("loudness: the sample rate gives a 100-ms step of fewer than " + std::to_string(smst::kLoudChunk) + " samples (or is beyond 1e9)");
+		forStreams(stream, [&](int s) {
+			level[s] = Level{SMST_LEVEL_LOUDNESS, 1.0f, ceiling};
+			loud[s] = l;
+		});
+		levelled = true;
+	}
+	void setLoudnessWeights(const float *weights) {
+		for (int c = 0; weights && c < C; ++c) if (!(std::isfinite(weights[c]) && weights[c] >= 0)) throw smst::Error("loudness: a channel weight is negative or not finite");
+		for (int c = 0; c < C; ++c) loudWeights[c] = weights ? weights[c] : 1.0f;
+	}
+
+	// whether a call of this format dithers: a stream has a mode, and the format has a step to dither
+	bool dithers(int format) const {
+		if (format != SMST_PCM_S16 && format != SMST_PCM_S24) return false;
+		for (const Dither &d : dither) if (d.mode != SMST_DITHER_NONE) return true;
+		return false;
+	}
+	bool anyLoudness() const {
+		if (levelled) for (const Level &l : level) if (l.mode == SMST_LEVEL_LOUDNESS) return true;
+		return false;
+	}
+	// A call's sections into its table's pinned copy `host` -> where the kernels find them in the device twin `dev`.  A call that dithers has
+	// every stream's mode and hash, and its frame counter as the index of the call's first frame; a levelled batch's calls the streams' level
+	// entries too (the dither entries then travel whether the call dithers or not) and, where a stream is in the loudness mode, the loudness
+	// entries and the channel weights
+	smst::PcmOutCall fill(void *host, void *dev, const smst::PcmTableLayout &at, int format) const {
+		smst::PcmOutCall call;
+		const bool dithered = dithers(format);
+		call.overs = dOvers;
+		if (anyLoudness()) {
+			for (int s = 0; s < S; ++s) at.loud(host)[s] = level[s].mode == SMST_LEVEL_LOUDNESS ? loud[s].entry : smst::LoudEntry{};
+			for (int k = 0; k < smst::kMaxChannels; ++k) at.weights(host)[k] = k < C ? loudWeights[k] : 0.0f;
+			call.loud = at.loud(dev);
+			call.loudWeights = at.weights(dev);
+		}
+		if (levelled) {
+			for (int s = 0; s < S; ++s) at.level(host)[s] = smst::PcmLevel{unsigned(level[s].mode), level[s].gain, level[s].ceiling, 0u};
+			call.level = smst::PcmMeters(S).io(at.level(dev), dMeters);
+		}
+		if (dithered || levelled) {
+			for (int s = 0; s < S; ++s) at.dither(host)[s] = smst::PcmDither{unsigned(dither[s].mode), dither[s].h, unsigned(dither[s].frames), unsigned(dither[s].frames >> 32)};
+			if (dithered) call.dither = at.dither(dev);
+		}
+		return call;
+	}
+	// What exact() needs on the host beside a call's view: which streams' gains come from their clip's peak (they decide whether kClipPeak
+	// runs), and h of those in the loudness mode (whether the four passes do).  Null as the view's members are
+	void clipModes(const smst::PcmOutCall &call, Batch::ClipIo &io) {
+		for (int s = 0; s < S; ++s) {
+			wholeClip[s] = level[s].mode != SMST_LEVEL_FIXED;
+			loudHop[s] = level[s].mode == SMST_LEVEL_LOUDNESS ? loud[s].entry.h : 0;
+		}
+		io.pcm = call;
+		io.wholeClip = call.level.table ? wholeClip.data() : nullptr;
+		io.loudHop = call.loud ? loudHop.data() : nullptr;
+	}
+	// after a call that emitted n[s] frames: the counters of the streams that have a mode move on, whatever the call's format
+	void advance(const int *n) {
+		for (int s = 0; s < S; ++s) if (dither[s].mode != SMST_DITHER_NONE && n[s] > 0) dither[s].frames += (unsigned long long)n[s];
+	}
+	// the takes: behind a synchronisation of the batch
+	void takeOvers(long long *clamped, long long *nans) {
+		if (!dOvers) throw smst::Error("this batch has no PCM over counters");
+		if (hipMemcpy(hOvers.data(), dOvers, pcmOversBytes(S), hipMemcpyDeviceToHost) != hipSuccess) throw smst::Error("hipMemcpy (PCM overs) failed", true);
+		if (hipMemset(dOvers, 0, pcmOversBytes(S)) != hipSuccess) throw smst::Error("hipMemset (PCM overs) failed", true);
+		for (int s = 0; s < S; ++s) {
+			if (clamped) clamped[s] = hOvers[2*s];
+			if (nans) nans[s] = hOvers[2*s + 1];
+		}
+	}
+	void takePeaks(float *peaks, float *gains) {
+		const smst::PcmMeters meters(S);
+		if (!dMeters) throw smst::Error("this batch has no PCM level meters");
+		if (hipMemcpy(hMeters.data(), dMeters, meters.takeBytes(), hipMemcpyDeviceToHost) != hipSuccess) throw smst::Error("hipMemcpy (PCM level) failed", true);
+		if (hipMemset(dMeters, 0, meters.clearBytes()) != hipSuccess) throw smst::Error("hipMemset (PCM level) failed", true);
+		meters.taken(hMeters.data(), peaks, gains);
+	}
+};
+
 struct smst_batch {
 	std::unique_ptr<Batch> engine;
 	// host staging (SMST_MEM_HOST)
 	DeviceFloats dIn, dOut;
 	long long stagingAllocs = 0;
 	// interleaved PCM (smst_batch_*_pcm): the raw frames as they cross PCIe, one device and one pinned host buffer per direction (bytes); the
-	// planar image the engine works on is dIn / dOut above.  The per-stream frame counts of the conversion kernels exist twice, as the engine's
-	// per-call tables do: a device-memory call returns before its kernels have run
+	// planar image the engine works on is dIn / dOut above
 	DeviceBytes dPcmIn, dPcmOut;
 	PinnedBytes hPcmIn, hPcmOut;
-	// ... and, behind the counts, the dither entries of the call's output conversion ([S] smst::PcmDither, uploaded with the output counts by a
-	// call that dithers: pcmUploadDither)
-	struct PcmCounts { // [2*S]: input frames, output frames; [S] dither entries; [S] level entries; [S] loudness entries; [kMaxChannels] channel weights
-		Buffer<int, true> host;
-		Buffer<int, false> dev;
-		const smst::PcmDither *dither = nullptr; // the call's entries in `dev`; null: the call does not dither
-		smst::PcmLevelIo level;                  // ... and its level entries, behind them, with the batch's meters; table null: the call is not levelled
-		const smst::LoudEntry *loud = nullptr;   // ... and its loudness entries and channel weights, behind those; null: no stream is in the loudness mode
-		const float *loudWeights = nullptr;
+	// The per-call table of the conversion kernels (smst::PcmTableLayout: the streams' frame counts, then the output side's entries) exists
+	// twice, as the engine's per-call tables do: a device-memory call returns before its kernels have run.  out: where the call's output
+	// conversion finds its entries in `dev` (PcmOutState::fill)
+	struct PcmTable {
+		Buffer<unsigned char, true> host;
+		Buffer<unsigned char, false> dev;
+		smst::PcmOutCall out;
 	};
-	smst::TwoSets<PcmCounts> pcmCounts; // (smst_staging.h)
-	// dither of the int16 / int24 output (smst_batch_set_pcm_dither): per stream the mode, the seed, its hash and the frame counter
-	struct PcmDitherState { int mode = SMST_DITHER_NONE; long long seed = 0; unsigned h = 0; unsigned long long frames = 0; };
-	std::vector<PcmDitherState> pcmDither;
-	// overs of the output conversions ([S][2]: clamped, NaN): the kernels add to them, smst_batch_take_pcm_overs reads and clears them
-	Buffer<unsigned, false> dPcmOvers;
-	std::vector<unsigned> hPcmOvers;
-	// level of the output conversions (smst_batch_set_pcm_level): per stream the mode, the gain and the ceiling; the batch is a levelled one from
-	// the first set on.  Device: [3][S] words -- the peaks since the last take (float bits), the gains the newest conversions applied, and
-	// the clip peaks of the newest exact call (kClipPeak's; stream-ordered, so one set serves calls in flight)
-	struct PcmLevelState { int mode = SMST_LEVEL_FIXED; float gain = 1.0f, ceiling = 1.0f; };
-	std::vector<PcmLevelState> pcmLevel;
-	bool pcmLevelled = false;
-	// ... and, for a stream in SMST_LEVEL_LOUDNESS (smst_batch_set_pcm_loudness), the target, the sample rate and the table entry made of them
-	// (h == 0: another mode); the channel weights of the batch
-	struct PcmLoudState { double target = 0, sampleRate = 0; smst::LoudEntry entry{}; };
-	std::vector<PcmLoudState> pcmLoud;
-	std::vector<float> pcmLoudWeights;
-	Buffer<int, false> dPcmLevel;
-	std::vector<int> hPcmLevel;
+	smst::TwoSets<PcmTable> pcmTables; // (smst_staging.h)
+	PcmOutState pcmOut;
 	~smst_batch() { if (engine) hipSetDevice(engine->device()); } // (the buffers above go behind it, the engine last)
 };
 
@@ -176,20 +314,6 @@ struct FlushCounts {
 	const unsigned char *mask() const { return all ? nullptr : active.data(); }
 };
 
-static size_t pcmOversBytes(int streams) { return (size_t)2*streams*sizeof(unsigned); }
-static size_t pcmLevelBytes(int streams) { return (size_t)3*streams*sizeof(int); }
-// the meters as a batch begins with them: no peak, gain 1, no clip peak
-static void pcmLevelStart(std::vector<int> &words, int streams) {
-	const float one = 1.0f;
-	words.assign((size_t)3*streams, 0);
-	for (int s = 0; s < streams; ++s) std::memcpy(&words[(size_t)streams + s], &one, sizeof one);
-}
-static smst::PcmLevelIo pcmLevelIo(const smst::PcmLevel *table, int *words, int streams) {
-	smst::PcmLevelIo io;
-	io.table = table; io.peaks = words; io.applied = reinterpret_cast<float *>(words + streams); io.clipPeak = words + 2*(size_t)streams;
-	return io;
-}
-
 extern "C" {
 
 const char *smst_last_error(void) { return g_lastError.c_str(); }
@@ -212,16 +336,7 @@ int smst_batch_create_ex(smst_batch **out, int streams, int channels, int block,
 	if (device < 0 || device >= n) throw smst::Error("device ordinal out of range");
 	std::unique_ptr<smst_batch> b(new smst_batch());
 	b->engine.reset(new Batch(streams, channels, block, interval, split != 0, device, seed, (flags & SMST_FLAG_HALF_STATE) != 0));
-	b->hPcmOvers.assign((size_t)2*streams, 0u);
-	b->pcmDither.assign((size_t)streams, smst_batch::PcmDitherState());
-	b->dPcmOvers.allocate((size_t)2*streams, "PCM overs");
-	if (hipMemset(b->dPcmOvers, 0, pcmOversBytes(streams)) != hipSuccess) throw smst::Error("hipMemset (PCM overs) failed", true);
-	b->pcmLevel.assign((size_t)streams, smst_batch::PcmLevelState());
-	b->pcmLoud.assign((size_t)streams, smst_batch::PcmLoudState());
-	b->pcmLoudWeights.assign((size_t)channels, 1.0f);
-	pcmLevelStart(b->hPcmLevel, streams);
-	b->dPcmLevel.allocate((size_t)3*streams, "PCM level");
-	if (hipMemcpy(b->dPcmLevel, b->hPcmLevel.data(), pcmLevelBytes(streams), hipMemcpyHostToDevice) != hipSuccess) throw smst::Error("hipMemcpy (PCM level) failed", true);
+	b->pcmOut.create(streams, channels);
 	*out = b.release();
 	return SMST_OK;
 	SMST_CATCH
@@ -236,10 +351,7 @@ int smst_batch_create_preset_ex(smst_batch **out, int streams, int channels, int
 	return fail("unknown preset");
 }
 int smst_batch_create_preset(smst_batch **out, int streams, int channels, int preset, float sampleRate, int split, int device, long seed) {
-	// signalsmith-stretch.h:63-68 (float products truncated to int by configure's int parameters)
-	if (preset == 0) return smst_batch_create(out, streams, channels, int(sampleRate*0.12), int(sampleRate*0.03), split < 0 ? 0 : split, device, seed);
-	if (preset == 1) return smst_batch_create(out, streams, channels, int(sampleRate*0.1), int(sampleRate*0.04), split < 0 ? 1 : split, device, seed);
-	return fail("unknown preset");
+	return smst_batch_create_preset_ex(out, streams, channels, preset, sampleRate, split, device, seed, 0u);
 }
 void smst_batch_destroy(smst_batch *b) { delete b; }
 
@@ -255,7 +367,7 @@ BATCH_Q(smst_batch_output_latency, b->engine->outputLatency())
 BATCH_Q(smst_batch_seek_length, b->engine->seekLength())
 BATCH_Q(smst_batch_half_state, b->engine->halfPrecisionState() ? 1 : 0)
 int smst_batch_output_seek_length(const smst_batch *b, float rate) { if (!b || !b->engine) return fail("null batch"); return b->engine->outputSeekLength(rate); }
-long long smst_batch_workspace_bytes(const smst_batch *b) { if (!b || !b->engine) return fail("null batch"); return (long long)(b->engine->workspaceBytes() + (b->dPcmOvers ? pcmOversBytes(b->engine->streams()) : 0) + (b->dPcmLevel ? pcmLevelBytes(b->engine->streams()) : 0)); }
+long long smst_batch_workspace_bytes(const smst_batch *b) { if (!b || !b->engine) return fail("null batch"); return (long long)(b->engine->workspaceBytes() + b->pcmOut.workspaceBytes()); }
 
 #define BATCH_CALL(...) if (!b || !b->engine) return fail("null batch"); SMST_TRY __VA_ARGS__; return SMST_OK; SMST_CATCH
 
@@ -438,74 +550,32 @@ static void checkPcmFormat(int format, int memory) {
 		throw smst::Error("unknown PCM format (SMST_PCM_S16, _F32, _S24, _S32 or _F16)");
 	if (memory != SMST_MEM_HOST && memory != SMST_MEM_DEVICE) throw smst::Error("unknown memory kind");
 }
-// the count tables of this call: the set the call before the previous one used (its conversion kernels must have run)
-static smst_batch::PcmCounts &beginPcmCall(smst_batch *b) {
+// the table of this call: the set the call before the previous one used (its conversion kernels must have run)
+static smst_batch::PcmTable &beginPcmCall(smst_batch *b) {
 	Batch &e = *b->engine;
 	hipSetDevice(e.device());
-	b->pcmCounts.create();
-	smst_batch::PcmCounts &c = b->pcmCounts.begin();
+	b->pcmTables.create();
+	smst_batch::PcmTable &c = b->pcmTables.begin();
 	if (!c.host) { // (both sets with the first call, as Batch::exact's segment tables: the second call allocates nothing)
 		++b->stagingAllocs;
-		const size_t ints = (size_t)2*e.streams() + (size_t)e.streams()*((sizeof(smst::PcmDither) + sizeof(smst::PcmLevel) + sizeof(smst::LoudEntry))/sizeof(int)) + smst::kMaxChannels;
-		for (smst_batch::PcmCounts &t : b->pcmCounts.sets) {
-			t.host.allocate(ints, "PCM counts");
-			t.dev.allocate(ints, "PCM counts");
+		for (smst_batch::PcmTable &t : b->pcmTables.sets) {
+			t.host.allocate(smst::PcmTableLayout(e.streams()).bytes(), "PCM counts");
+			t.dev.allocate(smst::PcmTableLayout(e.streams()).bytes(), "PCM counts");
 		}
 	}
-	c.dither = nullptr;
-	c.level = smst::PcmLevelIo();
-	c.loud = nullptr;
-	c.loudWeights = nullptr;
+	c.out = smst::PcmOutCall();
 	return c;
 }
-// whether a call of this format dithers: a stream has a mode, and the format has a step to dither
-static bool pcmDithers(const smst_batch *b, int format) {
-	if (format != SMST_PCM_S16 && format != SMST_PCM_S24) return false;
-	for (const smst_batch::PcmDitherState &d : b->pcmDither) if (d.mode != SMST_DITHER_NONE) return true;
-	return false;
-}
-// ... if so the call's entries are filled -- every stream's mode and hash, and its frame counter as the index of the call's first frame --
-// and uploaded, with the S output counts in front of them where the call has some (still one copy); c.dither is where the kernels read
-// them.  A levelled batch's calls carry the streams' level entries behind the dither entries (which then travel whether the call dithers or
-// not: still one copy); c.level has them and the batch's meters.  Where a stream is in the loudness mode the streams' loudness entries and
-// the channel weights travel behind the level entries (still one copy); c.loud and c.loudWeights have them.  The only place that knows
-// that the entries lie behind the 2*S counts.
-static void pcmUploadDither(smst_batch *b, smst_batch::PcmCounts &c, int format, bool withOutCounts) {
+// The output side's sections of the call's table, from the batch's state, and their upload -- with the S output counts in front of them where
+// the call has some -- in one copy; c.out is where the kernels read them
+static void pcmUploadOutTable(smst_batch *b, smst_batch::PcmTable &c, int format, bool withOutCounts) {
 	Batch &e = *b->engine;
-	const size_t S = size_t(e.streams()), first = withOutCounts ? S : 2*S;
-	const bool dithered = pcmDithers(b, format), levelled = b->pcmLevelled;
-	bool loud = false;
-	if (levelled) for (const smst_batch::PcmLevelState &l : b->pcmLevel) loud = loud || l.mode == SMST_LEVEL_LOUDNESS;
-	if (loud) { // (S*(16 + 16) bytes behind the 2*S counts: 8-byte aligned, as the entries' doubles need)
-		smst::LoudEntry *t = reinterpret_cast<smst::LoudEntry *>(reinterpret_cast<smst::PcmLevel *>(reinterpret_cast<smst::PcmDither *>(c.host + 2*S) + S) + S);
-		for (size_t s = 0; s < S; ++s) t[s] = b->pcmLevel[s].mode == SMST_LEVEL_LOUDNESS ? b->pcmLoud[s].entry : smst::LoudEntry{};
-		float *w = reinterpret_cast<float *>(t + S);
-		for (int k = 0; k < smst::kMaxChannels; ++k) w[k] = k < e.channels() ? b->pcmLoudWeights[k] : 0.0f;
-		c.loud = reinterpret_cast<const smst::LoudEntry *>(reinterpret_cast<const smst::PcmLevel *>(reinterpret_cast<const smst::PcmDither *>(c.dev + 2*S) + S) + S);
-		c.loudWeights = reinterpret_cast<const float *>(c.loud + S);
-	}
-	if (levelled) {
-		smst::PcmLevel *t = reinterpret_cast<smst::PcmLevel *>(reinterpret_cast<smst::PcmDither *>(c.host + 2*S) + S);
-		for (size_t s = 0; s < S; ++s) t[s] = smst::PcmLevel{unsigned(b->pcmLevel[s].mode), b->pcmLevel[s].gain, b->pcmLevel[s].ceiling, 0u};
-		c.level = pcmLevelIo(reinterpret_cast<const smst::PcmLevel *>(reinterpret_cast<const smst::PcmDither *>(c.dev + 2*S) + S), b->dPcmLevel, int(S));
-	}
-	if (dithered || levelled) {
-		smst::PcmDither *t = reinterpret_cast<smst::PcmDither *>(c.host + 2*S);
-		for (size_t s = 0; s < S; ++s) {
-			const smst_batch::PcmDitherState &d = b->pcmDither[s];
-			t[s] = smst::PcmDither{unsigned(d.mode), d.h, unsigned(d.frames), unsigned(d.frames >> 32)};
-		}
-		if (dithered) c.dither = reinterpret_cast<const smst::PcmDither *>(c.dev + 2*S);
-	}
-	const size_t bytes = (2*S - first)*sizeof(int) + (levelled ? S*(sizeof(smst::PcmDither) + sizeof(smst::PcmLevel)) : dithered ? S*sizeof(smst::PcmDither) : 0)
-	                     + (loud ? S*sizeof(smst::LoudEntry) + smst::kMaxChannels*sizeof(float) : 0);
-	if (hipMemcpyAsync(c.dev + first, c.host + first, bytes, hipMemcpyHostToDevice, e.stream()) != hipSuccess) throw smst::Error("hipMemcpyAsync (H2D) failed", true);
+	const smst::PcmTableLayout at(e.streams());
+	c.out = b->pcmOut.fill(c.host, c.dev, at, format);
+	const smst::PcmTableLayout::Range r = at.upload(withOutCounts, c.out.dither != nullptr, c.out.level.table != nullptr, c.out.loud != nullptr);
+	if (hipMemcpyAsync(c.dev + r.offset, c.host + r.offset, r.bytes, hipMemcpyHostToDevice, e.stream()) != hipSuccess) throw smst::Error("hipMemcpyAsync (H2D) failed", true);
 }
-// after a call that emitted n[s] frames: the counters of the streams that have a mode move on, whatever the call's format
-static void pcmAdvanceDither(smst_batch *b, const int *n) {
-	for (size_t s = 0; s < b->pcmDither.size(); ++s) if (b->pcmDither[s].mode != SMST_DITHER_NONE && n[s] > 0) b->pcmDither[s].frames += (unsigned long long)n[s];
-}
-static void endPcmCall(smst_batch *b) { b->pcmCounts.end(b->engine->stream()); }
+static void endPcmCall(smst_batch *b) { b->pcmTables.end(b->engine->stream()); }
 // a stream's row in the library's own raw buffers: its frames densely, rows a multiple of 16 bytes apart for every element size
 static long long pcmRowElems(int maxFrames, int C) { return ((long long)maxFrames*C + 15)/16*16; }
 
@@ -544,135 +614,88 @@ static void pcmRawOut(smst_batch *b, void *out, long long ss, long long fs, cons
 }
 
 // Raw frames -> the planar image b->dIn [S][C][maxLen] (returns maxLen), on the engine's stream and in front of every reader of the call's input
-static int pcmStageIn(smst_batch *b, smst_batch::PcmCounts &c, const void *in, long long ss, long long fs, const int *n, int format, int memory) {
+static int pcmStageIn(smst_batch *b, smst_batch::PcmTable &c, const void *in, long long ss, long long fs, const int *n, int format, int memory) {
 	Batch &e = *b->engine;
 	const int S = e.streams(), C = e.channels();
-	const Counts k = countsOf(n, S, c.host);
+	const smst::PcmTableLayout at(S);
+	const Counts k = countsOf(n, S, at.inCounts(c.host));
 	const int most = k.most, maxLen = k.len;
 	ensureStage(b, b->dIn, (size_t)S*C*maxLen);
 	hipSetDevice(e.device());
-	if (hipMemcpyAsync(c.dev, c.host, S*sizeof(int), hipMemcpyHostToDevice, e.stream()) != hipSuccess) throw smst::Error("hipMemcpyAsync (H2D) failed", true);
+	if (hipMemcpyAsync(at.inCounts(c.dev), at.inCounts(c.host), S*sizeof(int), hipMemcpyHostToDevice, e.stream()) != hipSuccess) throw smst::Error("hipMemcpyAsync (H2D) failed", true);
 	const void *raw = in;
 	long long rawSS = ss, rawFS = fs;
 	if (memory == SMST_MEM_HOST && most > 0) {
 		pcmRawIn(b, in, ss, fs, n, most, format);
 		raw = b->dPcmIn; rawSS = pcmRowElems(most, C); rawFS = C;
 	}
-	smst::launchPcmIn(format, raw, rawSS, rawFS, b->dIn, (long long)C*maxLen, maxLen, c.dev, S, C, most, e.stream());
+	smst::launchPcmIn(format, raw, rawSS, rawFS, b->dIn, (long long)C*maxLen, maxLen, at.inCounts(c.dev), S, C, most, e.stream());
 	// the engine reads its input on more than one stream (the silence gate on its own): the edge a caller's producer stream gets
 	e.waitForStream(e.stream());
 	return maxLen;
 }
 // the output side's buffers, before the engine is called (a growth frees, which synchronises the device): returns maxLen of b->dOut [S][C][maxLen]
-static int pcmPrepareOut(smst_batch *b, smst_batch::PcmCounts &c, const int *n, int format, int memory) {
+static int pcmPrepareOut(smst_batch *b, smst_batch::PcmTable &c, const int *n, int format, int memory) {
 	Batch &e = *b->engine;
 	const int S = e.streams(), C = e.channels();
-	const Counts k = countsOf(n, S, c.host + S);
+	const Counts k = countsOf(n, S, smst::PcmTableLayout(S).outCounts(c.host));
 	ensureStage(b, b->dOut, (size_t)S*C*k.len);
 	if (memory == SMST_MEM_HOST && k.most > 0) ensurePcmBytes(b, b->hPcmOut, b->dPcmOut, (size_t)S*pcmRowElems(k.most, C)*pcmElemBytes(format));
 	hipSetDevice(e.device());
-	pcmUploadDither(b, c, format, true);
+	pcmUploadOutTable(b, c, format, true);
 	return k.len;
 }
 // The planar image b->dOut -> raw frames, behind the engine's last emitting kernel (everything of a call is joined into the engine's stream,
 // which is what smst_batch_synchronize and smst_batch_signal_stream wait on).  Host memory: the call returns with the frames in place.
-static void pcmStageOut(smst_batch *b, smst_batch::PcmCounts &c, void *out, long long ss, long long fs, int maxLen, int format, int memory) {
+static void pcmStageOut(smst_batch *b, smst_batch::PcmTable &c, void *out, long long ss, long long fs, int maxLen, int format, int memory) {
 	Batch &e = *b->engine;
 	const int S = e.streams(), C = e.channels();
-	const int *n = c.host + S;
+	const smst::PcmTableLayout at(S);
+	const int *n = at.outCounts(c.host);
 	const int most = countsOf(n, S).most;
 	hipSetDevice(e.device());
 	if (memory == SMST_MEM_DEVICE) {
-		smst::launchPcmOut(format, b->dOut, (long long)C*maxLen, maxLen, out, ss, fs, c.dev + S, S, C, most, b->dPcmOvers, e.stream(), c.dither, c.level);
-		pcmAdvanceDither(b, n);
+		smst::launchPcmOut(format, b->dOut, (long long)C*maxLen, maxLen, out, ss, fs, at.outCounts(c.dev), S, C, most, c.out.overs, e.stream(), c.out.dither, c.out.level);
+		b->pcmOut.advance(n);
 		return;
 	}
 	if (most >= 1) {
-		smst::launchPcmOut(format, b->dOut, (long long)C*maxLen, maxLen, b->dPcmOut, pcmRowElems(most, C), C, c.dev + S, S, C, most, b->dPcmOvers, e.stream(), c.dither, c.level);
+		smst::launchPcmOut(format, b->dOut, (long long)C*maxLen, maxLen, b->dPcmOut, pcmRowElems(most, C), C, at.outCounts(c.dev), S, C, most, c.out.overs, e.stream(), c.out.dither, c.out.level);
 		pcmRawOut(b, out, ss, fs, n, most, format);
 	}
-	pcmAdvanceDither(b, n);
+	b->pcmOut.advance(n);
 }
 
-int smst_batch_set_pcm_dither(smst_batch *b, int stream, int mode, long long seed) {
-	BATCH_CALL({
-		const int S = b->engine->streams();
-		if (mode != SMST_DITHER_NONE && mode != SMST_DITHER_TPDF && mode != SMST_DITHER_TPDF_HP) throw smst::Error("unknown dither mode (SMST_DITHER_NONE, _TPDF or _TPDF_HP)");
-		if (stream < -1 || stream >= S) throw smst::Error("stream index out of range");
-		for (int s = stream < 0 ? 0 : stream; s < (stream < 0 ? S : stream + 1); ++s) {
-			smst_batch::PcmDitherState &d = b->pcmDither[s];
-			d.mode = mode;
-			d.seed = stream < 0 ? (long long)((unsigned long long)seed + (unsigned long long)s) : seed;
-			d.h = smst::pcmDitherHash(d.seed);
-			d.frames = 0;
-		}
-	})
-}
+int smst_batch_set_pcm_dither(smst_batch *b, int stream, int mode, long long seed) { BATCH_CALL(b->pcmOut.setDither(stream, mode, seed)) }
 int smst_batch_pcm_dither(const smst_batch *b, int stream, int *mode, long long *seed, long long *frames) {
 	if (!b || !b->engine) return fail("null batch");
 	if (stream < 0 || stream >= b->engine->streams()) return fail("stream index out of range");
-	const smst_batch::PcmDitherState &d = b->pcmDither[stream];
+	const PcmOutState::Dither &d = b->pcmOut.dither[stream];
 	if (mode) *mode = d.mode;
 	if (seed) *seed = d.seed;
 	if (frames) *frames = (long long)d.frames;
 	return SMST_OK;
 }
-static void checkPcmLevel(int mode, float gain, float ceiling) {
-	if (mode != SMST_LEVEL_FIXED && mode != SMST_LEVEL_PROTECT && mode != SMST_LEVEL_NORMALISE) throw smst::Error("unknown level mode (SMST_LEVEL_FIXED, _PROTECT or _NORMALISE; smst_batch_set_pcm_loudness sets _LOUDNESS)");
-	if (!std::isfinite(gain)) throw smst::Error("level: the gain is not finite");
-	if (mode == SMST_LEVEL_PROTECT && !(gain > 0)) throw smst::Error("level: SMST_LEVEL_PROTECT needs a gain above 0");
-	if (mode != SMST_LEVEL_FIXED && !(std::isfinite(ceiling) && ceiling > 0)) throw smst::Error("level: the whole-clip modes need a finite ceiling above 0");
-}
-int smst_batch_set_pcm_level(smst_batch *b, int stream, int mode, float gain, float ceiling) {
-	BATCH_CALL({
-		const int S = b->engine->streams();
-		checkPcmLevel(mode, gain, ceiling);
-		if (stream < -1 || stream >= S) throw smst::Error("stream index out of range");
-		for (int s = stream < 0 ? 0 : stream; s < (stream < 0 ? S : stream + 1); ++s) b->pcmLevel[s] = smst_batch::PcmLevelState{mode, gain, ceiling};
-		b->pcmLevelled = true;
-	})
-}
+int smst_batch_set_pcm_level(smst_batch *b, int stream, int mode, float gain, float ceiling) { BATCH_CALL(b->pcmOut.setLevel(stream, mode, gain, ceiling)) }
 int smst_batch_pcm_level(const smst_batch *b, int stream, int *mode, float *gain, float *ceiling) {
 	if (!b || !b->engine) return fail("null batch");
 	if (stream < 0 || stream >= b->engine->streams()) return fail("stream index out of range");
-	const smst_batch::PcmLevelState &l = b->pcmLevel[stream];
+	const PcmOutState::Level &l = b->pcmOut.level[stream];
 	if (mode) *mode = l.mode;
 	if (gain) *gain = l.gain;
 	if (ceiling) *ceiling = l.ceiling;
 	return SMST_OK;
 }
-int smst_batch_set_pcm_loudness(smst_batch *b, int stream, double targetLufs, float ceiling, double sampleRate) {
-	BATCH_CALL({
-		const int S = b->engine->streams();
-		if (!std::isfinite(targetLufs)) throw smst::Error("loudness: the target is not finite");
-		if (!(ceiling > 0)) throw smst::Error("loudness: the ceiling is not above 0 (+inf: no limit)");
-		if (!(std::isfinite(sampleRate) && sampleRate > 0)) throw smst::Error("loudness: the sample rate is not finite or not above 0");
-		smst_batch::PcmLoudState l;
-		l.target = targetLufs; l.sampleRate = sampleRate;
-		if (!smst::loudEntryOf(sampleRate, targetLufs, l.entry)) throw smst::Error("loudness: the sample rate gives a 100-ms step of fewer than " + std::to_string(smst::kLoudChunk) + " samples (or is beyond 1e9)");
-		if (stream < -1 || stream >= S) throw smst::Error("stream index out of range");
-		for (int s = stream < 0 ? 0 : stream; s < (stream < 0 ? S : stream + 1); ++s) {
-			b->pcmLevel[s] = smst_batch::PcmLevelState{SMST_LEVEL_LOUDNESS, 1.0f, ceiling};
-			b->pcmLoud[s] = l;
-		}
-		b->pcmLevelled = true;
-	})
-}
+int smst_batch_set_pcm_loudness(smst_batch *b, int stream, double targetLufs, float ceiling, double sampleRate) { BATCH_CALL(b->pcmOut.setLoudness(stream, targetLufs, ceiling, sampleRate)) }
 int smst_batch_pcm_loudness(const smst_batch *b, int stream, double *target, double *sampleRate) {
 	if (!b || !b->engine) return fail("null batch");
 	if (stream < 0 || stream >= b->engine->streams()) return fail("stream index out of range");
-	if (b->pcmLevel[stream].mode != SMST_LEVEL_LOUDNESS) return fail("the stream is not in SMST_LEVEL_LOUDNESS");
-	if (target) *target = b->pcmLoud[stream].target;
-	if (sampleRate) *sampleRate = b->pcmLoud[stream].sampleRate;
+	if (b->pcmOut.level[stream].mode != SMST_LEVEL_LOUDNESS) return fail("the stream is not in SMST_LEVEL_LOUDNESS");
+	if (target) *target = b->pcmOut.loud[stream].target;
+	if (sampleRate) *sampleRate = b->pcmOut.loud[stream].sampleRate;
 	return SMST_OK;
 }
-int smst_batch_set_pcm_loudness_weights(smst_batch *b, const float *weights) {
-	BATCH_CALL({
-		const int C = b->engine->channels();
-		for (int c = 0; weights && c < C; ++c) if (!(std::isfinite(weights[c]) && weights[c] >= 0)) throw smst::Error("loudness: a channel weight is negative or not finite");
-		for (int c = 0; c < C; ++c) b->pcmLoudWeights[c] = weights ? weights[c] : 1.0f;
-	})
-}
+int smst_batch_set_pcm_loudness_weights(smst_batch *b, const float *weights) { BATCH_CALL(b->pcmOut.setLoudnessWeights(weights)) }
 // Z and the count of gated blocks -> LUFS; -inf where loudness is undefined
 static double loudnessLufs(double Z, int gated) { return (gated > 0 && Z > 0 && std::isfinite(Z)) ? -0.691 + 10*std::log10(Z) : -INFINITY; }
 int smst_batch_take_pcm_loudness(smst_batch *b, double *lufs, int *blocks, int *gated) {
@@ -692,9 +715,9 @@ int smst_batch_take_pcm_loudness(smst_batch *b, double *lufs, int *blocks, int *
 }
 // a streaming call knows no clip: refused, before anything runs, where a stream that takes part (active null: every one) has a whole-clip mode
 static void refuseWholeClipLevel(const smst_batch *b, const unsigned char *active) {
-	if (!b->pcmLevelled) return;
-	for (size_t s = 0; s < b->pcmLevel.size(); ++s)
-		if ((!active || active[s]) && b->pcmLevel[s].mode != SMST_LEVEL_FIXED)
+	if (!b->pcmOut.levelled) return;
+	for (size_t s = 0; s < b->pcmOut.level.size(); ++s)
+		if ((!active || active[s]) && b->pcmOut.level[s].mode != SMST_LEVEL_FIXED)
 			throw smst::Error("stream " + std::to_string(s) + " has a whole-clip level mode (SMST_LEVEL_PROTECT / _NORMALISE / _LOUDNESS): smst_batch_exact_pcm only");
 }
 int smst_batch_process_pcm(smst_batch *b, const void *in, long long iss, long long ifs, const int *inSamples,
@@ -705,7 +728,7 @@ int smst_batch_process_pcm(smst_batch *b, const void *in, long long iss, long lo
 		checkPcmSide(in, ifs, inSamples, e.streams(), e.channels(), false);
 		checkPcmSide(out, ofs, outSamples, e.streams(), e.channels(), false);
 		refuseWholeClipLevel(b, nullptr);
-		smst_batch::PcmCounts &c = beginPcmCall(b);
+		smst_batch::PcmTable &c = beginPcmCall(b);
 		const int maxIn = pcmStageIn(b, c, in, iss, ifs, inSamples, format, memory);
 		const int maxOut = pcmPrepareOut(b, c, outSamples, format, memory);
 		e.process(b->dIn, (long long)e.channels()*maxIn, maxIn, inSamples, b->dOut, (long long)e.channels()*maxOut, maxOut, outSamples);
@@ -718,7 +741,7 @@ int smst_batch_seek_pcm(smst_batch *b, const void *in, long long ss, long long f
 		Batch &e = *b->engine;
 		checkPcmFormat(format, memory);
 		checkPcmSide(in, fs, inSamples, e.streams(), e.channels(), false);
-		smst_batch::PcmCounts &c = beginPcmCall(b);
+		smst_batch::PcmTable &c = beginPcmCall(b);
 		const int maxLen = pcmStageIn(b, c, in, ss, fs, inSamples, format, memory);
 		e.seek(b->dIn, (long long)e.channels()*maxLen, maxLen, inSamples, rates);
 		endPcmCall(b);
@@ -732,7 +755,7 @@ int smst_batch_flush_pcm(smst_batch *b, void *out, long long oss, long long ofs,
 		checkPcmSide(out, ofs, outSamples, e.streams(), e.channels(), true);
 		const FlushCounts f(outSamples, e.streams());
 		refuseWholeClipLevel(b, f.active.data());
-		smst_batch::PcmCounts &c = beginPcmCall(b);
+		smst_batch::PcmTable &c = beginPcmCall(b);
 		const int maxOut = pcmPrepareOut(b, c, f.counts.data(), format, memory);
 		e.flush(b->dOut, (long long)e.channels()*maxOut, maxOut, f.counts.data(), rates, f.mask());
 		pcmStageOut(b, c, out, oss, ofs, maxOut, format, memory);
@@ -744,7 +767,7 @@ int smst_batch_output_seek_pcm(smst_batch *b, const void *in, long long ss, long
 		Batch &e = *b->engine;
 		checkPcmFormat(format, memory);
 		checkPcmSide(in, fs, inputLengths, e.streams(), e.channels(), false);
-		smst_batch::PcmCounts &c = beginPcmCall(b);
+		smst_batch::PcmTable &c = beginPcmCall(b);
 		const int maxLen = pcmStageIn(b, c, in, ss, fs, inputLengths, format, memory);
 		e.outputSeek(b->dIn, (long long)e.channels()*maxLen, maxLen, inputLengths);
 		endPcmCall(b);
@@ -786,7 +809,7 @@ int smst_batch_exact(smst_batch *b, const float *in, long long iss, long long ic
 		Batch &e = *b->engine;
 		checkExactArgs(e, in, inSamples, out, outSamples, 0, 0, false, memory);
 		if (memory == SMST_MEM_DEVICE) {
-			runExact(e, Batch::ClipIo{in, iss, ics, out, oss, ocs, 0, nullptr}, inSamples, outSamples, status);
+			runExact(e, Batch::ClipIo{in, iss, ics, out, oss, ocs, 0}, inSamples, outSamples, status);
 		} else {
 			const int S = e.streams(), C = e.channels();
 			std::vector<int> nIn, nOut;
@@ -795,7 +818,7 @@ int smst_batch_exact(smst_batch *b, const float *in, long long iss, long long ic
 			int maxIn;
 			const float *dIn = stageIn(b, in, iss, ics, nIn.data(), maxIn);
 			ensureStage(b, b->dOut, (size_t)S*C*maxOut);
-			runExact(e, Batch::ClipIo{dIn, (long long)C*maxIn, maxIn, b->dOut, (long long)C*maxOut, maxOut, 0, nullptr}, inSamples, outSamples, status);
+			runExact(e, Batch::ClipIo{dIn, (long long)C*maxIn, maxIn, b->dOut, (long long)C*maxOut, maxOut, 0}, inSamples, outSamples, status);
 			unstageOut(b, out, oss, ocs, nOut.data(), maxOut);
 		}
 	})
@@ -807,28 +830,24 @@ int smst_batch_exact_pcm(smst_batch *b, const void *in, long long iss, long long
 		checkPcmFormat(format, memory);
 		checkExactArgs(e, in, inSamples, out, outSamples, ifs, ofs, true, memory);
 		// a dithered call: the streams' modes and hashes ride in the _pcm calls' table (the frame index is the place in the clip: the counters
-		// are neither read nor moved)
-		smst_batch::PcmCounts *table = pcmDithers(b, format) || b->pcmLevelled ? &beginPcmCall(b) : nullptr;
-		if (table) pcmUploadDither(b, *table, format, false);
-		const smst::PcmDither *dither = table ? table->dither : nullptr;
-		// a levelled call: the entries ride there too; the streams whose gain comes from their clip's peak decide whether kClipPeak runs
-		const smst::PcmLevelIo level = table ? table->level : smst::PcmLevelIo();
-		std::vector<unsigned char> wholeClip;
-		if (level.table) for (const smst_batch::PcmLevelState &l : b->pcmLevel) wholeClip.push_back(l.mode != SMST_LEVEL_FIXED);
-		// ... and those in the loudness mode whether the four passes do: their entries and the channel weights ride there as well
-		std::vector<int> loudHop;
-		if (table && table->loud) for (size_t s = 0; s < b->pcmLevel.size(); ++s) loudHop.push_back(b->pcmLevel[s].mode == SMST_LEVEL_LOUDNESS ? b->pcmLoud[s].entry.h : 0);
-		const smst::LoudEntry *loud = loudHop.empty() ? nullptr : table->loud;
-		const float *loudWeights = loudHop.empty() ? nullptr : table->loudWeights;
+		// are neither read nor moved); a levelled call: the level entries ride there too, and the loudness entries and the channel weights
+		smst_batch::PcmTable *table = b->pcmOut.dithers(format) || b->pcmOut.levelled ? &beginPcmCall(b) : nullptr;
+		if (table) pcmUploadOutTable(b, *table, format, false);
+		smst::PcmOutCall plain;
+		plain.overs = b->pcmOut.dOvers;
+		Batch::ClipIo io{in, iss, ifs, out, oss, ofs, format};
+		b->pcmOut.clipModes(table ? table->out : plain, io);
 		if (memory == SMST_MEM_DEVICE) {
-			runExact(e, Batch::ClipIo{in, iss, ifs, out, oss, ofs, format, b->dPcmOvers, dither, level, wholeClip.data(), loud, loudWeights, loudHop.data()}, inSamples, outSamples, status);
+			runExact(e, io, inSamples, outSamples, status);
 		} else {
 			const int S = e.streams(), C = e.channels();
 			std::vector<int> nIn, nOut;
 			const int mostIn = exactCounts(inSamples, outSamples, S, nIn), mostOut = exactCounts(outSamples, outSamples, S, nOut);
 			ensurePcmBytes(b, b->hPcmOut, b->dPcmOut, (size_t)S*pcmRowElems(mostOut, C)*pcmElemBytes(format));
 			pcmRawIn(b, in, iss, ifs, nIn.data(), mostIn, format);
-			runExact(e, Batch::ClipIo{b->dPcmIn, pcmRowElems(mostIn, C), C, b->dPcmOut, pcmRowElems(mostOut, C), C, format, b->dPcmOvers, dither, level, wholeClip.data(), loud, loudWeights, loudHop.data()}, inSamples, outSamples, status);
+			io.in = b->dPcmIn; io.inStreamStride = pcmRowElems(mostIn, C); io.inInnerStride = C;
+			io.out = b->dPcmOut; io.outStreamStride = pcmRowElems(mostOut, C); io.outInnerStride = C;
+			runExact(e, io, inSamples, outSamples, status);
 			pcmRawOut(b, out, oss, ofs, nOut.data(), mostOut, format);
 		}
 		if (table) endPcmCall(b);
@@ -870,34 +889,22 @@ template <typename Launch> static void debugConvert(const std::string &name, int
 		if (nans) nans[s] = overs[2*s + 1];
 	}
 }
-// A levelled hook's `first` block: [S] dither entries (always present, mode 0 where the hook has none), [S] level entries, the [3][S] meter
-// words of a fresh batch.  io(base): the launch's PcmLevelIo where the block lies at `base`; results(): the peaks and the applied gains
+// A levelled hook's `first` block (smst::PcmDebugBlock): the dither entries (always present, mode 0 where the hook has none), the level
+// entries, the meter words of a fresh batch.  io(base): the launch's PcmLevelIo where the block lies at `base`; results(): the peaks and the applied gains
 struct DebugLevel {
-	int S;
+	smst::PcmDebugBlock at;
 	std::vector<unsigned char> block;
-	DebugLevel(int streams, const std::vector<smst::PcmDither> &dither, const int *modes, const float *gains, const float *ceilings) : S(streams) {
-		std::vector<smst::PcmLevel> level;
-		for (int s = 0; s < S; ++s) {
+	DebugLevel(int streams, const std::vector<smst::PcmDither> &dither, const int *modes, const float *gains, const float *ceilings) : at(streams), block(at.bytes()) {
+		for (int s = 0; s < streams; ++s) {
 			const int mode = modes ? modes[s] : SMST_LEVEL_FIXED;
 			checkPcmLevel(mode, gains[s], ceilings ? ceilings[s] : 1.0f);
-			level.push_back(smst::PcmLevel{unsigned(mode), gains[s], ceilings ? ceilings[s] : 1.0f, 0u});
+			at.dither(block.data())[s] = dither[s];
+			at.level(block.data())[s] = smst::PcmLevel{unsigned(mode), gains[s], ceilings ? ceilings[s] : 1.0f, 0u};
 		}
-		std::vector<int> words;
-		pcmLevelStart(words, S);
-		block.resize((size_t)S*(sizeof(smst::PcmDither) + sizeof(smst::PcmLevel)) + pcmLevelBytes(S));
-		std::memcpy(block.data(), dither.data(), S*sizeof(smst::PcmDither));
-		std::memcpy(block.data() + S*sizeof(smst::PcmDither), level.data(), S*sizeof(smst::PcmLevel));
-		std::memcpy(block.data() + S*(sizeof(smst::PcmDither) + sizeof(smst::PcmLevel)), words.data(), pcmLevelBytes(S));
+		at.meters.start(at.words(block.data()));
 	}
-	smst::PcmLevelIo io(const unsigned char *base) const {
-		unsigned char *words = const_cast<unsigned char *>(base) + S*(sizeof(smst::PcmDither) + sizeof(smst::PcmLevel));
-		return pcmLevelIo(reinterpret_cast<const smst::PcmLevel *>(base + S*sizeof(smst::PcmDither)), reinterpret_cast<int *>(words), S);
-	}
-	void results(float *peaks, float *applied) const {
-		const unsigned char *words = block.data() + S*(sizeof(smst::PcmDither) + sizeof(smst::PcmLevel));
-		if (peaks) std::memcpy(peaks, words, S*sizeof(float));
-		if (applied) std::memcpy(applied, words + S*sizeof(float), S*sizeof(float));
-	}
+	smst::PcmLevelIo io(unsigned char *base) const { return at.meters.io(at.level(base), at.words(base)); }
+	void results(float *peaks, float *applied) { at.meters.taken(at.words(block.data()), peaks, applied); }
 };
 static int pcmConvert(int device, int dir, int format, int streams, int channels, const int *counts,
                       const void *src, long long srcSS, long long srcInner, void *dst, long long dstSS, long long dstInner, long long *clamped, long long *nans,
@@ -923,7 +930,7 @@ static int pcmConvert(int device, int dir, int format, int streams, int channels
 	if (modes) {
 		if (!seeds || !firstFrames) throw smst::Error("pcm convert: null seeds or first frames");
 		for (int s = 0; s < streams; ++s) {
-			if (modes[s] != SMST_DITHER_NONE && modes[s] != SMST_DITHER_TPDF && modes[s] != SMST_DITHER_TPDF_HP) throw smst::Error("unknown dither mode (SMST_DITHER_NONE, _TPDF or _TPDF_HP)");
+			checkDitherMode(modes[s]);
 			const unsigned long long n = (unsigned long long)firstFrames[s];
 			dither.push_back(smst::PcmDither{unsigned(modes[s]), smst::pcmDitherHash(seeds[s]), unsigned(n), unsigned(n >> 32)});
 			dithered = dithered || modes[s] != SMST_DITHER_NONE;
@@ -932,18 +939,18 @@ static int pcmConvert(int device, int dir, int format, int streams, int channels
 	if (gains) { // the levelled kernel: fixed gains, the meters of a fresh batch
 		DebugLevel level(streams, dither, nullptr, gains, nullptr);
 		debugConvert("pcm convert", streams, src, srcBytes, dst, dstBytes, counts, streams*sizeof(int), level.block.data(), level.block.size(), clamped || nans, clamped, nans,
-		             [&](unsigned char *s0, unsigned char *d0, const unsigned char *dCounts, const unsigned char *dFirst, unsigned *dOvers) {
+		             [&](unsigned char *s0, unsigned char *d0, const unsigned char *dCounts, unsigned char *dFirst, unsigned *dOvers) {
 			smst::launchPcmOut(format, reinterpret_cast<const float *>(s0), srcSS, srcInner, d0, dstSS, dstInner, reinterpret_cast<const int *>(dCounts), streams, channels, most, dOvers, nullptr,
-			                   dithered ? reinterpret_cast<const smst::PcmDither *>(dFirst) : nullptr, level.io(dFirst));
+			                   dithered ? level.at.dither(dFirst) : nullptr, level.io(dFirst));
 		}, level.block.data());
 		level.results(peaks, nullptr);
 		return SMST_OK;
 	}
 	debugConvert("pcm convert", streams, src, srcBytes, dst, dstBytes, counts, streams*sizeof(int), dither.data(), dithered ? streams*sizeof(smst::PcmDither) : 0,
-	             dir == 1 && (clamped || nans), clamped, nans, [&](unsigned char *s0, unsigned char *d0, const unsigned char *dCounts, const unsigned char *dDither, unsigned *dOvers) {
+	             dir == 1 && (clamped || nans), clamped, nans, [&](unsigned char *s0, unsigned char *d0, const unsigned char *dCounts, unsigned char *dDither, unsigned *dOvers) {
 		const int *n = reinterpret_cast<const int *>(dCounts);
 		if (dir == 0) smst::launchPcmIn(format, s0, srcSS, srcInner, reinterpret_cast<float *>(d0), dstSS, dstInner, n, streams, channels, most, nullptr);
-		else smst::launchPcmOut(format, reinterpret_cast<const float *>(s0), srcSS, srcInner, d0, dstSS, dstInner, n, streams, channels, most, dOvers, nullptr, reinterpret_cast<const smst::PcmDither *>(dDither));
+		else smst::launchPcmOut(format, reinterpret_cast<const float *>(s0), srcSS, srcInner, d0, dstSS, dstInner, n, streams, channels, most, dOvers, nullptr, smst::PcmDebugBlock(streams).dither(dDither));
 	});
 	return SMST_OK;
 	SMST_CATCH
@@ -1004,19 +1011,19 @@ static int clipCopy(int device, int dir, int format, int streams, int channels, 
 		std::vector<smst::PcmDither> dither;
 		bool dithered = false;
 		for (int s = 0; s < streams; ++s) {
-			if (ditherModes[s] != SMST_DITHER_NONE && ditherModes[s] != SMST_DITHER_TPDF && ditherModes[s] != SMST_DITHER_TPDF_HP) throw smst::Error("unknown dither mode (SMST_DITHER_NONE, _TPDF or _TPDF_HP)");
+			checkDitherMode(ditherModes[s]);
 			dither.push_back(smst::PcmDither{unsigned(ditherModes[s]), smst::pcmDitherHash(seeds[s]), 0u, 0u});
 			dithered = dithered || ditherModes[s] != SMST_DITHER_NONE;
 		}
 		dithered = dithered && (format == SMST_PCM_S16 || format == SMST_PCM_S24);
 		DebugLevel level(streams, dither, levelModes, gains, ceilings);
 		debugConvert("clip copy", streams, src, srcBytes, dst, dstBytes, segments, (size_t)2*streams*sizeof(smst::ClipSeg), level.block.data(), level.block.size(), clamped || nans, clamped, nans,
-		             [&](unsigned char *s0, unsigned char *d0, const unsigned char *dSegs, const unsigned char *dFirst, unsigned *dOvers) {
+		             [&](unsigned char *s0, unsigned char *d0, const unsigned char *dSegs, unsigned char *dFirst, unsigned *dOvers) {
 			const smst::ClipSeg *segs = reinterpret_cast<const smst::ClipSeg *>(dSegs);
 			const smst::PcmLevelIo io = level.io(dFirst);
 			smst::launchClipPeak(reinterpret_cast<const float *>(s0), srcSS, srcInner, segs, streams, channels, most, io.clipPeak, nullptr);
 			smst::launchClipOut(format, reinterpret_cast<const float *>(s0), srcSS, srcInner, d0, dstSS, dstInner, segs, streams, channels, most, dOvers, nullptr,
-			                    dithered ? reinterpret_cast<const smst::PcmDither *>(dFirst) : nullptr, io);
+			                    dithered ? level.at.dither(dFirst) : nullptr, io);
 		}, level.block.data());
 		level.results(peaks, applied);
 		return SMST_OK;
@@ -1101,31 +1108,16 @@ int smst_debug_clip_loudness(int device, int streams, int channels, const int *s
 }
 int smst_batch_take_pcm_overs(smst_batch *b, long long *clamped, long long *nans) {
 	BATCH_CALL({
-		Batch &e = *b->engine;
-		const int S = e.streams();
-		e.synchronize();
-		if (!b->dPcmOvers) throw smst::Error("this batch has no PCM over counters");
-		hipSetDevice(e.device());
-		if (hipMemcpy(b->hPcmOvers.data(), b->dPcmOvers, pcmOversBytes(S), hipMemcpyDeviceToHost) != hipSuccess) throw smst::Error("hipMemcpy (PCM overs) failed", true);
-		if (hipMemset(b->dPcmOvers, 0, pcmOversBytes(S)) != hipSuccess) throw smst::Error("hipMemset (PCM overs) failed", true);
-		for (int s = 0; s < S; ++s) {
-			if (clamped) clamped[s] = b->hPcmOvers[2*s];
-			if (nans) nans[s] = b->hPcmOvers[2*s + 1];
-		}
+		b->engine->synchronize();
+		hipSetDevice(b->engine->device());
+		b->pcmOut.takeOvers(clamped, nans);
 	})
 }
-
 int smst_batch_take_pcm_peaks(smst_batch *b, float *peaks, float *gains) {
 	BATCH_CALL({
-		Batch &e = *b->engine;
-		const size_t S = size_t(e.streams());
-		e.synchronize();
-		if (!b->dPcmLevel) throw smst::Error("this batch has no PCM level meters");
-		hipSetDevice(e.device());
-		if (hipMemcpy(b->hPcmLevel.data(), b->dPcmLevel, 2*S*sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) throw smst::Error("hipMemcpy (PCM level) failed", true);
-		if (hipMemset(b->dPcmLevel, 0, S*sizeof(int)) != hipSuccess) throw smst::Error("hipMemset (PCM level) failed", true);
-		if (peaks) std::memcpy(peaks, b->hPcmLevel.data(), S*sizeof(float));
-		if (gains) std::memcpy(gains, b->hPcmLevel.data() + S, S*sizeof(float));
+		b->engine->synchronize();
+		hipSetDevice(b->engine->device());
+		b->pcmOut.takePeaks(peaks, gains);
 	})
 }
 

@@ -1833,12 +1833,12 @@ void Batch::exact(const ClipIo &io, const int *inSamples, const int *outSamples,
 	}
 	// behind the call's last emitting kernel (everything of a call is joined into `st`), in front of whatever synchronize() / signalStream() wait for
 	bool wholeClip = false;
-	if (io.level.table && io.wholeClip) for (int s = 0; s < S; ++s) wholeClip = wholeClip || (run[s] && io.wholeClip[s]);
+	if (io.pcm.level.table && io.wholeClip) for (int s = 0; s < S; ++s) wholeClip = wholeClip || (run[s] && io.wholeClip[s]);
 	if (wholeClip) { // the clips' peaks, from the finished image: what kClipOut forms those streams' gains from
-		SMST_HIP(hipMemsetAsync(io.level.clipPeak, 0, (size_t)S*sizeof(int), st));
-		launchClipPeak(dClipOut, outImgSS, pitchOut, cs.dev + (size_t)2*S, S, C, std::max(maxProc, maxFlush), io.level.clipPeak, st);
+		SMST_HIP(hipMemsetAsync(io.pcm.level.clipPeak, 0, (size_t)S*sizeof(int), st));
+		launchClipPeak(dClipOut, outImgSS, pitchOut, cs.dev + (size_t)2*S, S, C, std::max(maxProc, maxFlush), io.pcm.level.clipPeak, st);
 	}
-	PcmLevelIo level = io.level;
+	PcmLevelIo level = io.pcm.level;
 	int loudMost = 0, loudSub = 0;
 	if (wholeClip && io.loudHop) for (int s = 0; s < S; ++s) if (run[s] && io.loudHop[s] > 0) {
 		loudMost = std::max(loudMost, outSamples[s]);
@@ -1849,11 +1849,11 @@ void Batch::exact(const ClipIo &io, const int *inSamples, const int *outSamples,
 		const size_t doubles = loudScratchDoubles(S, C, maxChunks, loudSub);
 		growScratch(dLoud, loudCapacity, 2*doubles, doubles/4 + 1024, true);
 		const LoudScratch w = loudScratchAt(reinterpret_cast<double *>(dLoud), S, C, maxChunks, loudSub);
-		launchClipLoudness(dClipOut, outImgSS, pitchOut, cs.dev + (size_t)2*S, S, C, io.loud, io.loudWeights, w, st);
+		launchClipLoudness(dClipOut, outImgSS, pitchOut, cs.dev + (size_t)2*S, S, C, io.pcm.loud, io.pcm.loudWeights, w, st);
 		level.loudGain = w.gain;
 	}
 	launchClipOut(io.format, dClipOut, outImgSS, pitchOut, io.out, io.outStreamStride, io.outInnerStride, cs.dev + (size_t)2*S, S, C,
-	              std::max(std::max(direct ? 0 : maxProc, maxFlush), maxZeros), io.overs, st, io.dither, level);
+	              std::max(std::max(direct ? 0 : maxProc, maxFlush), maxZeros), io.pcm.overs, st, io.pcm.dither, level);
 	clipSets.end(st);
 	SMST_HIP(hipGetLastError());
 	if (tooShort) for (int s = 0; s < S; ++s) if (outSamples[s] >= 0) tooShort[s] = run[s] ? 0 : 1; // (only once every stage has been issued)

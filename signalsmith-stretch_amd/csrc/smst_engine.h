@@ -11,6 +11,7 @@
 #include "smst_device.h"
 #include "smst_recurrence_form.h"
 #include "smst_staging.h"
+#include "smst_pcm_tables.h"
 
 namespace smst {
 
@@ -107,11 +108,12 @@ public:
 	// (smst_clip.h).  A stream whose input is shorter than its outputSeekLength gets zeros and keeps its state (:471-480).  tooShort (host, may
 	// be null): 1 for such a stream, 0 for the others that take part, written once every stage has been issued; a stream left out keeps its entry.  overs (device, may be null): [S][2] counters of the frame conversion.
 	// Counts are checked by the caller: outSamples[s] != 0, inSamples[s] >= 0 where outSamples[s] > 0.
-	struct ClipIo { const void *in; long long inStreamStride, inInnerStride; void *out; long long outStreamStride, outInnerStride; int format; unsigned *overs; const PcmDither *dither = nullptr; // dither: [S] device, or null (smst_device.h)
-		PcmLevelIo level; const unsigned char *wholeClip = nullptr; // level.table set: a levelled call (frame formats); wholeClip (host, [S]): which streams' gains come from their clip's peak -- if one of them runs, kClipPeak does
-		// loudness (smst_loudness.h): loud ([S] device) and loudWeights ([C] device) ride in the caller's per-call table; loudHop (host, [S]): h of the
-		// streams in the loudness mode, 0 for the others -- if one of them runs, the four passes do, and kClipOut finds the gains in the engine's meters
-		const LoudEntry *loud = nullptr; const float *loudWeights = nullptr; const int *loudHop = nullptr; };
+	// pcm (frame formats; smst_pcm_tables.h): the device side of the output conversion, which rides in the caller's per-call table.  wholeClip
+	// (host, [S]; null where the call is not levelled): which streams' gains come from their clip's peak -- if one of them runs, kClipPeak
+	// does.  loudHop (host, [S]; null where no stream is in the loudness mode): h of the streams in that mode, 0 for the others -- if one of
+	// them runs, the four passes of smst_loudness.h do, and kClipOut finds the gains in the engine's meters
+	struct ClipIo { const void *in; long long inStreamStride, inInnerStride; void *out; long long outStreamStride, outInnerStride; int format;
+		PcmOutCall pcm; const unsigned char *wholeClip = nullptr; const int *loudHop = nullptr; };
 	// the loudness meters of the newest exact call that measured, [S] and [S][2] (blocks past the absolute gate, past both); false: none has.  Synchronises
 	bool readLoudness(double *Z, int *counts);
 	void exact(const ClipIo &io, const int *inSamples, const int *outSamples, unsigned char *tooShort);

@@ -615,3 +615,54 @@ def test_no_pageable_async_copy_on_the_calling_paths(hooks, name):
     import whole_call_cases as wc
     _schedule(hooks, "eager")
     assert _whole_call(hooks, wc.SCENARIOS[name], rounds=2)[1] == 0
+
+
+# ---- the _pcm calls' per-call table: every combination of its sections, on device memory -------------------------------------------------
+
+class _DevicePcmCalls(_DeviceCalls):
+    """pcm_tables_cases' frame calls through the C ABI on SMST_MEM_DEVICE buffers; frames are [S, n, C] (packed int24: [S, n, C, 3] bytes)"""
+
+    def _format(self, a):
+        return self.pkg.PCM_S24 if a.dtype == np.uint8 else {"int16": self.pkg.PCM_S16, "float32": self.pkg.PCM_F32}[a.dtype.name]
+
+    def _out(self, like, m):
+        return self._new((like.shape[0], m) + like.shape[2:], like.dtype, 0x5A if like.dtype == np.uint8 else 0x5A5A if like.dtype == np.int16 else np.nan)
+
+    def process(self, x, nin, nout):
+        d, (_, pin), (_, pout), m, Cn = self._up(x), self._ints(nin), self._ints(nout), max(max(nout), 1), self.b.channels
+        y = self._out(x, m)
+        self._ok(self.lib.smst_batch_process_pcm(self.b.h, _ptr(d), x.shape[1]*Cn, Cn, pin, _ptr(y), m*Cn, Cn, pout, self._format(x), self.pkg.MEM_DEVICE))
+        return y
+
+    def flush(self, counts, rates, fmt):
+        (_, n), r, m, Cn = self._ints(counts), np.ascontiguousarray(rates, np.float32), max(max(counts), 1), self.b.channels
+        like = {"s16": np.zeros((self.b.streams, 0, Cn), np.int16), "s24": np.zeros((self.b.streams, 0, Cn, 3), np.uint8), "f32": np.zeros((self.b.streams, 0, Cn), np.float32)}[fmt]
+        y = self._out(like, m)
+        self._ok(self.lib.smst_batch_flush_pcm(self.b.h, _ptr(y), m*Cn, Cn, n, r.ctypes.data_as(C.POINTER(C.c_float)), self._format(y), self.pkg.MEM_DEVICE))
+        return y
+
+    def exact(self, x, nin, nout):
+        d, (_, pin), (_, pout), m, Cn = self._up(x), self._ints(nin), self._ints(nout), max(nout), self.b.channels
+        status, y = np.full(self.b.streams, 1, np.int32), self._out(x, m)
+        self._ok(self.lib.smst_batch_exact_pcm(self.b.h, _ptr(d), x.shape[1]*Cn, Cn, pin, _ptr(y), m*Cn, Cn, pout, status.ctypes.data_as(C.POINTER(C.c_int)),
+                                               self._format(x), self.pkg.MEM_DEVICE))
+        return y, status == 0
+
+
+@pytest.mark.parametrize("spec", ("eager",) + SCHEDULES)
+def test_pcm_tables_stages(hooks, spec):
+    """pcm_tables_cases' sequence on device memory under each schedule: equal to what the parent commit gave on host memory -- the table sets
+    are pinned and rotate, so one rewritten before its upload ran would show -- and no async copy from pageable memory."""
+    import json
+    import pcm_tables_cases as pt
+    _schedule(hooks, spec)
+    b = pt.new_batch(hooks)
+    calls = _DevicePcmCalls(hooks, b)
+    before = hooks.smst_emu_pageable_async_copies()
+    digests = pt.run_sequence(b, calls)
+    pageable = hooks.smst_emu_pageable_async_copies() - before
+    calls.close()
+    b.close()
+    want = json.load(open(pt.GOLDEN["emu"]))["memory"]["host"]
+    assert [k for k in sorted(want) if digests.get(k) != want[k]] == [] and sorted(digests) == sorted(want)
+    assert pageable == 0
