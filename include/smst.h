@@ -402,7 +402,8 @@ int smst_batch_pcm_dither(const smst_batch *b, int stream, int *mode, long long 
  * (process: every stream; flush: those with a non-negative count) has a whole-clip mode they return SMST_ERR_INVALID before anything runs --
  * a whole-clip gain in a streaming call would be a silent lie.  smst_batch_exact_pcm serves all three modes.  The too-short and left-out
  * streams of an exact call stay as they are: undithered zeros or untouched, peak and gain unchanged.  Out of scope: the planar calls and the
- * planar smst_batch_exact are neither levelled nor metered; true-peak metering; separate input and output formats in one call.
+ * planar smst_batch_exact are neither levelled nor metered; separate input and output formats in one call.  (The peak above is the SAMPLE
+ * peak; "True peak" below has the inter-sample meter and what it does to the ceilings.)
  *
  * Clip-free ceilings.  fl(peak*fl(ceiling/peak)) may exceed the ceiling by an fp32 rounding or two, so a ceiling of exactly full scale can
  * clamp.  No element is clamped (smst_batch_take_pcm_overs gives 0) when ceiling*scale is at most
@@ -456,7 +457,7 @@ int smst_batch_pcm_dither(const smst_batch *b, int stream, int *mode, long long 
  * per-call table beside the level entries; the passes' scratch and the meters grow with the first call that measures, as the images do, and
  * count in smst_batch_workspace_bytes: a second call of the same shapes allocates nothing, no host synchronisation is added, and the
  * ordering contract of the device-memory call is unchanged.  A batch without a stream in this mode launches none of the passes.
- * Out of scope: momentary and short-term loudness, loudness range, true-peak metering, measuring in the streaming or the planar calls.
+ * Out of scope: momentary and short-term loudness, loudness range, measuring in the streaming or the planar calls.
  * SMST_ERR_INVALID with a message: a target that is not finite; a sample rate that is not finite, <= 0 or gives h < SMST_LOUDNESS_CHUNK; a
  * ceiling <= 0 or NaN (+inf is allowed); a weight that is negative or not finite; a stream index out of range; a null batch. */
 #define SMST_LEVEL_FIXED     0 /* g = gain */
@@ -487,6 +488,69 @@ int smst_debug_clip_loudness(int device, int streams, int channels, const int *s
                              const float *image, long long imageStreamStride, long long imageChannelStride,
                              const double *sampleRates, const float *weights, double targetLufs,
                              double *Z, int *blocks, int *gated, float *gains, double *blockPowers, int maxBlocks);
+/* ---- True peak (EXTENSION; opt-in: a batch that never calls smst_batch_set_pcm_true_peak launches the kernels, writes the bytes and counts the launches it did before) ----
+ * Every ceiling above is a sample-peak ceiling; a delivery specification (EBU R 128, ATSC A/85) states a maximum TRUE peak, the peak of the
+ * waveform between the samples as well.  A stream with the true-peak flag has the true peak of its whole output clip measured in
+ * smst_batch_exact_pcm, and its whole-clip modes then form their quotient from it: the ceilings of PROTECT, NORMALISE and LOUDNESS are dBTP.
+ *
+ * The interpolator oversamples 4x.  The fractional phases are p = 1, 2, 3 (phase 0 is the sample itself); each has 12 taps, j = 0 ... 11:
+ *     t = (j - 5) - p/4
+ *     h = sinc(t) * 0.5*(1 + cos(pi*t/6))      sinc(t) = sin(pi*t)/(pi*t): a Hann window of half-width 6, |t| < 6 for every tap
+ *     c[p][j] = float32(h / sum_j h)           computed by the host in double; each phase normalised to unit DC gain; one rounding
+ *   Known answers: c[2] = -9.85122286e-04, 1.03496173e-02, -3.36731486e-02, 8.00664872e-02, -1.80965975e-01, 6.25208139e-01, then
+ *   mirrored; c[1][5] = 8.96035254e-01, c[1][6] = 2.88544923e-01; c[3][j] = c[1][11 - j].
+ *   The filter is defined by this formula, not by the 48-coefficient table of ITU-R BS.1770-4 Annex 2 (DESIGN.md states the deviation).
+ *   Per-phase gain is at most 1.0118 (+0.10 dB, near 0.67 Nyquist); above 0.8 Nyquist the meter under-reads, as one of 12 taps per phase
+ *   does.  A Hann-faded tone whose samples straddle its crests reads 0.99528 at fs/4 (sample peak 0.70711), 0.99930 at fs/8, 0.97687 at 3fs/8.
+ *
+ * Arithmetic.  Float64 up to the final comparison:
+ *     y_p(n) = sum_{j = 0 ... 11} double(c[p][j]) * double(x(n + j - 5))
+ *   accumulated from 0.0 in the order j = 0 ... 11, for n = 0 ... N - 1 in clip order, N = outSamples[s]; x outside [0, N) is 0.  A product
+ *   of two float32 values is exact in float64, so the sum is the same with or without fused multiply-adds, and a float64 mirror that adds
+ *   in the same order reproduces it bit for bit (tests/true_peak_cases.py).
+ * - True peak of a stream: the maximum over channels, n and phases of the bit pattern of float32(|v|) -- v the sample x(n) itself and
+ *   the three y_p(n), each rounded once to float32.  An integer maximum, as the sample peak is.  NaNs are skipped (a window that holds a
+ *   NaN gives NaN), +-inf counts as inf.  The true peak is therefore >= the sample peak by construction.
+ *
+ * The flag is a setting of its own beside the stream's level mode: smst_batch_set_pcm_level and smst_batch_set_pcm_loudness leave it as it
+ * is.  The first call with on != 0 makes the batch a levelled one, as the first smst_batch_set_pcm_level does.  In smst_batch_exact_pcm, for
+ * a stream that runs:
+ * - the true peak is measured (one more pass over the library's own planar image of the output, on the device);
+ * - PROTECT, NORMALISE and LOUDNESS form q = ceiling/peak from the TRUE peak instead of the sample peak; everything else stays: the same
+ *   correctly rounded fp32 division, the same rule for a peak of 0 or one that is not finite, the same rule for a ceiling of +inf;
+ * - a FIXED stream is metered only;
+ * - streams without the flag, in the same call, produce the bytes, meters and gains they produce without it.
+ * The "Clip-free ceilings" table keeps holding with the flag on: the true peak is >= the sample peak, so the gain can only be lower.
+ * smst_batch_take_pcm_peaks still reports the SAMPLE peak and the applied gain.
+ *
+ * Which calls.  smst_batch_process_pcm and smst_batch_flush_pcm return SMST_ERR_INVALID, before anything runs, if a stream that takes part
+ * has the flag -- the rule and the reason of the whole-clip modes: a meter across calls would need 11 frames of carried history per channel.
+ *
+ * How.  One kernel (csrc/smst_true_peak.h) behind the call's last emitting kernel and in front of the conversion.  The flag rides
+ * in the fourth word of the stream's level entry; the taps travel as a kernel argument.  The true-peak words ([streams] ints) are device
+ * memory that grows with the first call that measures and counts in smst_batch_workspace_bytes: a second call of the same shapes allocates
+ * nothing, no host synchronisation is added, and the ordering contract of the device-memory call is unchanged.  The maximum is one of
+ * integers and no floating-point atomic is used: a call's result is bit-reproducible whatever the scheduling.
+ * Out of scope: true-peak metering in the streaming and the planar calls; a limiter; an oversampling factor that depends on the rate (4x at
+ * every rate); momentary and short-term loudness, loudness range.
+ * SMST_ERR_INVALID with a message: a stream index out of range, a null batch. */
+#define SMST_TRUE_PEAK_TILE 1024 /* frames of a channel's clip that one workgroup of the true-peak pass measures (kTruePeakTile) */
+/* stream = -1: every stream */
+int smst_batch_set_pcm_true_peak(smst_batch *b, int stream, int on);
+/* on may be null */
+int smst_batch_pcm_true_peak(const smst_batch *b, int stream, int *on);
+/* per stream, of the newest smst_batch_exact_pcm that measured: truePeaks[s] = the true peak of the stream's clip BEFORE the gain; 0 for a
+ * stream that call did not measure (flag off, too short, left out) and before any call has measured.  Synchronises the batch; resets nothing. */
+int smst_batch_take_pcm_true_peaks(smst_batch *b, float *truePeaks);
+/* test hook: the true-peak pass alone on a planar fp32 image (host pointer, strides in floats) with a segment table as smst_debug_clip_copy's
+ * ([streams][2][4]: a clip is segment 0 then segment 1 of its rows) -> per stream the true peak and, from kClipPeak on the same image, the
+ * sample peak.  flags ([streams], null: every stream): the streams that have the flag; another one reports a true peak of 0.  Either output
+ * pointer may be null. */
+int smst_debug_clip_true_peak(int device, int streams, int channels, const int *segments,
+                              const float *image, long long imageStreamStride, long long imageChannelStride,
+                              float *truePeaks, float *samplePeaks, const int *flags);
+/* test hook: the library's tap table c[p][j], phase-major: out[12*(p - 1) + j], p = 1, 2, 3 */
+int smst_debug_true_peak_taps(float *out);
 /* per stream, since the last take: peaks[s] = the largest |v| the levelled output conversions met BEFORE the gain (0 if none); gains[s] = the
  * gain the newest levelled conversion of stream s applied (1 before any).  Either may be null.  Synchronises the batch; resets the peaks,
  * not the gains. */

@@ -30,6 +30,7 @@ DITHER_NONE, DITHER_TPDF, DITHER_TPDF_HP = 0, 1, 2           # dither of the int
 LEVEL_FIXED, LEVEL_PROTECT, LEVEL_NORMALISE = 0, 1, 2        # level of the frame output (StretchBatch.set_pcm_level)
 LEVEL_LOUDNESS = 3                                           # ... to a LUFS target (StretchBatch.set_pcm_loudness)
 LOUDNESS_CHUNK = 256                                         # frames one lane of the loudness passes filters (SMST_LOUDNESS_CHUNK)
+TRUE_PEAK_TILE = 1024                                        # frames one workgroup of the true-peak pass measures (SMST_TRUE_PEAK_TILE)
 _FRAME_DTYPES = {"int16": PCM_S16, "float32": PCM_F32, "int32": PCM_S32, "float16": PCM_F16}  # (packed int24 travels as uint8 [..., 3])
 _FRAME_DTYPE_OF = {PCM_S16: "int16", PCM_F32: "float32", PCM_S32: "int32", PCM_F16: "float16", PCM_S24: "uint8"}
 _fp = C.POINTER(C.c_float)
@@ -139,6 +140,11 @@ _SIGNATURES = {
     "smst_batch_set_pcm_loudness_weights": (C.c_int, [C.c_void_p, _fp]),
     "smst_batch_take_pcm_loudness": (C.c_int, [C.c_void_p, _dp, _ip, _ip]),
     "smst_debug_clip_loudness": (C.c_int, [C.c_int, C.c_int, C.c_int, _ip, C.c_void_p, _ll, _ll, _dp, _fp, C.c_double, _dp, _ip, _ip, _fp, _dp, C.c_int]),
+    "smst_batch_set_pcm_true_peak": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
+    "smst_batch_pcm_true_peak": (C.c_int, [C.c_void_p, C.c_int, _ip]),
+    "smst_batch_take_pcm_true_peaks": (C.c_int, [C.c_void_p, _fp]),
+    "smst_debug_clip_true_peak": (C.c_int, [C.c_int, C.c_int, C.c_int, _ip, C.c_void_p, _ll, _ll, _fp, _fp, _ip]),
+    "smst_debug_true_peak_taps": (C.c_int, [_fp]),
     "smst_batch_synchronize": (C.c_int, [C.c_void_p]),
     "smst_batch_hip_stream": (C.c_void_p, [C.c_void_p]),
     "smst_batch_enable_profiling": (C.c_int, [C.c_void_p, C.c_int]),
@@ -308,6 +314,28 @@ def debug_clip_loudness(segments, channels, image, image_ss, image_cs, sample_ra
                                              None if w is None else w.ctypes.data_as(_fp), float(target), Z.ctypes.data_as(_dp), blocks.ctypes.data_as(_ip),
                                              gated.ctypes.data_as(_ip), gains.ctypes.data_as(_fp), powers.ctypes.data_as(_dp), max_blocks))
     return Z, blocks, gated, gains, powers[:, :max_blocks]
+
+
+def debug_clip_true_peak(segments, channels, image, image_ss, image_cs, flags=None, device=0, lib=None):
+    """smst_debug_clip_true_peak on a numpy image (planar float32; segments int [S, 2, 4]; strides in floats; flags: [S], None: every stream)
+    -> (true peaks, sample peaks), float32 [S]"""
+    lib = lib if lib is not None else load_library()
+    seg = np.ascontiguousarray(segments, np.int32)
+    S = seg.shape[0]
+    on = None if flags is None else np.ascontiguousarray(flags, np.int32)
+    assert on is None or on.shape == (S,)
+    true_peaks, sample_peaks = np.full(S, -1, np.float32), np.full(S, -1, np.float32)
+    _check(lib, lib.smst_debug_clip_true_peak(device, S, channels, seg.ctypes.data_as(_ip), C.c_void_p(image.ctypes.data), image_ss, image_cs,
+                                              true_peaks.ctypes.data_as(_fp), sample_peaks.ctypes.data_as(_fp), None if on is None else on.ctypes.data_as(_ip)))
+    return true_peaks, sample_peaks
+
+
+def debug_true_peak_taps(lib=None):
+    """smst_debug_true_peak_taps -> float32 [3, 12]: the library's taps of the phases 1, 2, 3"""
+    lib = lib if lib is not None else load_library()
+    taps = np.zeros((3, 12), np.float32)
+    _check(lib, lib.smst_debug_true_peak_taps(taps.ctypes.data_as(_fp)))
+    return taps
 
 
 def launch_count(name, lib=None):
@@ -697,6 +725,27 @@ class StretchBatch:
         _check(self.lib, self.lib.smst_batch_take_pcm_loudness(self.h, lufs.ctypes.data_as(_dp), blocks.ctypes.data_as(_ip), gated.ctypes.data_as(_ip)))
         self._inflight = []
         return lufs, blocks, gated
+
+    def set_pcm_true_peak(self, on=True, stream=-1):
+        """The true-peak flag (include/smst.h, "True peak"), exactFrames only: the clip's true peak -- a 4x interpolation between the samples,
+        and the samples themselves -- is measured on the device, and the stream's whole-clip modes (LEVEL_PROTECT, LEVEL_NORMALISE,
+        LEVEL_LOUDNESS) form ceiling/peak from it: their ceilings are then true-peak ceilings.  A LEVEL_FIXED stream is metered only.
+        stream = -1: every stream.  set_pcm_level and set_pcm_loudness leave the flag as it is."""
+        _check(self.lib, self.lib.smst_batch_set_pcm_true_peak(self.h, int(stream), 1 if on else 0))
+
+    def pcm_true_peak(self, stream):
+        """-> whether the stream has the true-peak flag"""
+        on = C.c_int(0)
+        _check(self.lib, self.lib.smst_batch_pcm_true_peak(self.h, int(stream), C.byref(on)))
+        return bool(on.value)
+
+    def take_pcm_true_peaks(self):
+        """-> float32 [S]: the true peaks, before the gain, of the newest exactFrames that measured (0 for a stream it did not measure).
+        Synchronises the batch; resets nothing."""
+        peaks = np.zeros(self.streams, np.float32)
+        _check(self.lib, self.lib.smst_batch_take_pcm_true_peaks(self.h, peaks.ctypes.data_as(_fp)))
+        self._inflight = []
+        return peaks
 
     # --- test hooks
     def debug_state(self, stream, which):

@@ -80,6 +80,9 @@ struct PcmOutState {
 	std::vector<Level> level;
 	std::vector<Loud> loud;
 	std::vector<float> loudWeights; // [C], the batch's
+	// the true-peak flag (smst_batch_set_pcm_true_peak): a setting of its own beside the stream's mode, which the two setters above leave as
+	// it is; the first stream that gets it makes the batch a levelled one
+	std::vector<unsigned char> truePeak;
 	bool levelled = false;
 	// overs ([S][2]: clamped, NaN): the kernels add to them, takeOvers() reads and clears them; the meter words (smst::PcmMeters)
 	Buffer<unsigned, false> dOvers;
@@ -96,6 +99,7 @@ struct PcmOutState {
 		level.assign((size_t)S, Level());
 		loud.assign((size_t)S, Loud());
 		loudWeights.assign((size_t)C, 1.0f);
+		truePeak.assign((size_t)S, 0);
 		wholeClip.assign((size_t)S, 0);
 		loudHop.assign((size_t)S, 0);
 		hOvers.assign((size_t)2*S, 0u);
@@ -141,6 +145,14 @@ struct PcmOutState {
 		});
 		levelled = true;
 	}
+	void setTruePeak(int stream, int on) {
+		forStreams(stream, [&](int s) { truePeak[s] = on ? 1 : 0; });
+		if (on) levelled = true;
+	}
+	bool anyTruePeak() const {
+		if (levelled) for (unsigned char on : truePeak) if (on) return true;
+		return false;
+	}
 	void setLoudnessWeights(const float *weights) {
 		for (int c = 0; weights && c < C; ++c) if (!(std::isfinite(weights[c]) && weights[c] >= 0)) throw smst::Error("loudness: a channel weight is negative or not finite");
 		for (int c = 0; c < C; ++c) loudWeights[c] = weights ? weights[c] : 1.0f;
@@ -171,7 +183,7 @@ struct PcmOutState {
 			call.loudWeights = at.weights(dev);
 		}
 		if (levelled) {
-			for (int s = 0; s < S; ++s) at.level(host)[s] = smst::PcmLevel{unsigned(level[s].mode), level[s].gain, level[s].ceiling, 0u};
+			for (int s = 0; s < S; ++s) at.level(host)[s] = smst::PcmLevel{unsigned(level[s].mode), level[s].gain, level[s].ceiling, unsigned(truePeak[s])};
 			call.level = smst::PcmMeters(S).io(at.level(dev), dMeters);
 		}
 		if (dithered || levelled) {
@@ -181,7 +193,8 @@ struct PcmOutState {
 		return call;
 	}
 	// What exact() needs on the host beside a call's view: which streams' gains come from their clip's peak (they decide whether kClipPeak
-	// runs), and h of those in the loudness mode (whether the four passes do).  Null as the view's members are
+	// runs), h of those in the loudness mode (whether the four passes do), and the true-peak flags (whether kClipTruePeak does).  Null as the
+	// view's members are
 	void clipModes(const smst::PcmOutCall &call, Batch::ClipIo &io) {
 		for (int s = 0; s < S; ++s) {
 			wholeClip[s] = level[s].mode != SMST_LEVEL_FIXED;
@@ -190,6 +203,7 @@ struct PcmOutState {
 		io.pcm = call;
 		io.wholeClip = call.level.table ? wholeClip.data() : nullptr;
 		io.loudHop = call.loud ? loudHop.data() : nullptr;
+		io.truePeak = call.level.table && anyTruePeak() ? truePeak.data() : nullptr;
 	}
 	// after a call that emitted n[s] frames: the counters of the streams that have a mode move on, whatever the call's format
 	void advance(const int *n) {
@@ -696,6 +710,22 @@ int smst_batch_pcm_loudness(const smst_batch *b, int stream, double *target, dou
 	return SMST_OK;
 }
 int smst_batch_set_pcm_loudness_weights(smst_batch *b, const float *weights) { BATCH_CALL(b->pcmOut.setLoudnessWeights(weights)) }
+int smst_batch_set_pcm_true_peak(smst_batch *b, int stream, int on) { BATCH_CALL(b->pcmOut.setTruePeak(stream, on)) }
+int smst_batch_pcm_true_peak(const smst_batch *b, int stream, int *on) {
+	if (!b || !b->engine) return fail("null batch");
+	if (stream < 0 || stream >= b->engine->streams()) return fail("stream index out of range");
+	if (on) *on = b->pcmOut.truePeak[stream];
+	return SMST_OK;
+}
+int smst_batch_take_pcm_true_peaks(smst_batch *b, float *truePeaks) {
+	BATCH_CALL({
+		Batch &e = *b->engine;
+		e.synchronize();
+		std::vector<float> peaks((size_t)e.streams(), 0.0f);
+		e.readTruePeaks(peaks.data()); // (false: no call has measured yet -- 0 for every stream)
+		if (truePeaks) std::copy(peaks.begin(), peaks.end(), truePeaks);
+	})
+}
 // Z and the count of gated blocks -> LUFS; -inf where loudness is undefined
 static double loudnessLufs(double Z, int gated) { return (gated > 0 && Z > 0 && std::isfinite(Z)) ? -0.691 + 10*std::log10(Z) : -INFINITY; }
 int smst_batch_take_pcm_loudness(smst_batch *b, double *lufs, int *blocks, int *gated) {
@@ -714,11 +744,15 @@ int smst_batch_take_pcm_loudness(smst_batch *b, double *lufs, int *blocks, int *
 	})
 }
 // a streaming call knows no clip: refused, before anything runs, where a stream that takes part (active null: every one) has a whole-clip mode
+// or the true-peak flag (a meter across calls would need 11 frames of carried history per channel)
 static void refuseWholeClipLevel(const smst_batch *b, const unsigned char *active) {
 	if (!b->pcmOut.levelled) return;
 	for (size_t s = 0; s < b->pcmOut.level.size(); ++s)
 		if ((!active || active[s]) && b->pcmOut.level[s].mode != SMST_LEVEL_FIXED)
 			throw smst::Error("stream " + std::to_string(s) + " has a whole-clip level mode (SMST_LEVEL_PROTECT / _NORMALISE / _LOUDNESS): smst_batch_exact_pcm only");
+	for (size_t s = 0; s < b->pcmOut.truePeak.size(); ++s)
+		if ((!active || active[s]) && b->pcmOut.truePeak[s])
+			throw smst::Error("stream " + std::to_string(s) + " has the true-peak flag (smst_batch_set_pcm_true_peak): smst_batch_exact_pcm only");
 }
 int smst_batch_process_pcm(smst_batch *b, const void *in, long long iss, long long ifs, const int *inSamples,
                            void *out, long long oss, long long ofs, const int *outSamples, int format, int memory) {
@@ -1105,6 +1139,51 @@ int smst_debug_clip_loudness(int device, int streams, int channels, const int *s
 	}
 	return SMST_OK;
 	SMST_CATCH
+}
+// the true-peak pass alone, and kClipPeak beside it: see include/smst.h
+int smst_debug_clip_true_peak(int device, int streams, int channels, const int *segments, const float *image, long long imageSS, long long imageCS,
+                              float *truePeaks, float *samplePeaks, const int *flags) {
+	SMST_TRY
+	if (streams < 1 || channels < 1 || channels > smst::kMaxChannels || !segments || !image || imageSS < 0 || imageCS < 0) throw smst::Error("clip true peak: bad arguments");
+	auto hip = [&](hipError_t err) { if (err != hipSuccess) throw smst::Error(std::string("clip true peak: ") + hipGetErrorString(err), true); };
+	std::vector<smst::PcmLevel> level((size_t)streams);
+	int end = 0, most = 0, mostSegment = 0;
+	for (int s = 0; s < streams; ++s) {
+		const int *g = segments + 8*s;
+		if (g[0] < 0 || g[2] < 0 || g[4] < 0 || g[6] < 0) throw smst::Error("clip true peak: negative segment offset or count");
+		if ((long long)g[2] + g[6] > 0x7fffffff) throw smst::Error("clip true peak: the clip is too long");
+		for (int k = 0; k < 2; ++k) if (g[4*k + 2] > 0 && !g[4*k + 3]) end = std::max(end, g[4*k] + g[4*k + 2]);
+		most = std::max(most, g[2] + g[6]);
+		mostSegment = std::max(mostSegment, std::max(g[2], g[6]));
+		level[s] = smst::PcmLevel{smst::kPcmLevelFixed, 1.0f, 1.0f, (!flags || flags[s]) ? 1u : 0u};
+	}
+	hip(hipSetDevice(device));
+	const size_t imageBytes = end ? size_t((streams - 1)*imageSS + (channels - 1)*imageCS + end)*sizeof(float) : 0;
+	Buffer<unsigned char, false> dImage, dSegs, dLevel;
+	Buffer<int, false> dWords; // [2][streams]: true peaks, sample peaks
+	dImage.allocate(imageBytes + 32, "clip true peak");
+	dSegs.allocate((size_t)2*streams*sizeof(smst::ClipSeg), "clip true peak");
+	dLevel.allocate(level.size()*sizeof(smst::PcmLevel), "clip true peak");
+	dWords.allocate((size_t)2*streams, "clip true peak");
+	unsigned char *i0 = dImage + reinterpret_cast<uintptr_t>(image)%16; // (as far behind a 16-byte boundary as the caller's image)
+	if (imageBytes) hip(hipMemcpy(i0, image, imageBytes, hipMemcpyHostToDevice));
+	hip(hipMemcpy(dSegs, segments, (size_t)2*streams*sizeof(smst::ClipSeg), hipMemcpyHostToDevice));
+	hip(hipMemcpy(dLevel, level.data(), level.size()*sizeof(smst::PcmLevel), hipMemcpyHostToDevice));
+	hip(hipMemset(dWords, 0, (size_t)2*streams*sizeof(int)));
+	const smst::ClipSeg *segs = reinterpret_cast<const smst::ClipSeg *>(dSegs.p);
+	smst::launchClipTruePeak(reinterpret_cast<const float *>(i0), imageSS, imageCS, segs, streams, channels, most, reinterpret_cast<const smst::PcmLevel *>(dLevel.p), dWords, nullptr);
+	smst::launchClipPeak(reinterpret_cast<const float *>(i0), imageSS, imageCS, segs, streams, channels, mostSegment, dWords + streams, nullptr);
+	hip(hipGetLastError());
+	hip(hipStreamSynchronize(nullptr));
+	if (truePeaks) hip(hipMemcpy(truePeaks, dWords, (size_t)streams*sizeof(float), hipMemcpyDeviceToHost));
+	if (samplePeaks) hip(hipMemcpy(samplePeaks, dWords + streams, (size_t)streams*sizeof(float), hipMemcpyDeviceToHost));
+	return SMST_OK;
+	SMST_CATCH
+}
+int smst_debug_true_peak_taps(float *out) {
+	if (!out) return fail("true peak taps: null pointer");
+	std::memcpy(out, smst::truePeakTable().c, sizeof(smst::TruePeakTable));
+	return SMST_OK;
 }
 int smst_batch_take_pcm_overs(smst_batch *b, long long *clamped, long long *nans) {
 	BATCH_CALL({

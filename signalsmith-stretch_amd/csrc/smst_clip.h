@@ -62,7 +62,8 @@ template <typename T, bool Dith, bool Level> __global__ __launch_bounds__(256) v
 	unsigned over;
 	if constexpr (Level) {
 		const PcmLevel l = level.table[s];
-		const float gain = clipGain(l, l.mode == kPcmLevelFixed ? 0 : level.clipPeak[s], l.mode == kPcmLevelLoudness && level.loudGain ? level.loudGain[s] : 1.0f);
+		const int *clipPeak = l.truePeak && level.truePeak ? level.truePeak : level.clipPeak; // (a flagged stream: its true peak, kClipTruePeak's)
+		const float gain = clipGain(l, l.mode == kPcmLevelFixed ? 0 : clipPeak[s], l.mode == kPcmLevelLoudness && level.loudGain ? level.loudGain[s] : 1.0f);
 		unsigned peak;
 		if (!pcmTileOut<T, Dith, true>(src, imageChannelStride, out + (size_t)s*outStreamStride + (size_t)g.dst*outFrameStride, outFrameStride, g.count, blockIdx.x, C, reinterpret_cast<float *>(smemRaw), over, dp, gain, &peak)) return;
 		if (src) {

@@ -169,7 +169,7 @@ __host__ __device__ inline bool analysisWindowInCall(int B, int M, int I, int in
 // form" tests assert through these that BOTH forms really ran.
 enum LaunchKind {
 	LK_VOC_ALIGNED, LK_VOC_TWISTED, LK_VOC_INTERIOR, LK_VOC_STAGED, LK_VOC_GATHER, LK_VOC_N, LK_VOC_ONE, LK_VOC_ACROSS, LK_VOC_CONT, LK_CHAIN_UNFUSED,
-	LK_ANALYSE_TEAMS, LK_ANALYSE_PAIRS, LK_ANALYSE_TWIST, LK_TWIST_ROWS, LK_ANALYSE_FAST, LK_ANALYSE_GENERIC, LK_SYNTH_TEAMS, LK_SYNTH_FAST, LK_SYNTH_GENERIC, LK_SYNTH_EMIT, LK_EMIT_CARRIED, LK_FEED_ONE_PASS, LK_PCM_IN, LK_PCM_OUT, LK_CLIP_IN, LK_CLIP_OUT, LK_PCM_OUT_DITHERED, LK_CLIP_OUT_DITHERED, LK_PCM_OUT_LEVELLED, LK_CLIP_OUT_LEVELLED, LK_CLIP_PEAK, LK_CLIP_LOUDNESS, LK_COUNT
+	LK_ANALYSE_TEAMS, LK_ANALYSE_PAIRS, LK_ANALYSE_TWIST, LK_TWIST_ROWS, LK_ANALYSE_FAST, LK_ANALYSE_GENERIC, LK_SYNTH_TEAMS, LK_SYNTH_FAST, LK_SYNTH_GENERIC, LK_SYNTH_EMIT, LK_EMIT_CARRIED, LK_FEED_ONE_PASS, LK_PCM_IN, LK_PCM_OUT, LK_CLIP_IN, LK_CLIP_OUT, LK_PCM_OUT_DITHERED, LK_CLIP_OUT_DITHERED, LK_PCM_OUT_LEVELLED, LK_CLIP_OUT_LEVELLED, LK_CLIP_PEAK, LK_CLIP_LOUDNESS, LK_CLIP_TRUE_PEAK, LK_COUNT
 };
 long long launchCount(const char *name); // -1: unknown name
 
@@ -231,10 +231,13 @@ inline unsigned pcmDitherHash(long long seed) {
 // rule above runs on w, peaks[s] (the bits of a non-negative float, which order as ints) takes the largest |v| the launch met in stream s,
 // NaN skipped, and applied[s] the gain g it used.  kPcmOut knows the fixed gain only; kClipOut derives a whole-clip gain from clipPeak[s],
 // the peak of the stream's clip that kClipPeak left there.  table == null: the unlevelled kernels, as before; nothing else is read.
-struct PcmLevel { unsigned mode; float gain, ceiling; unsigned pad; };
+// truePeak != 0: the stream's true-peak flag (include/smst.h, "True peak") -- kClipTruePeak measures the stream, and kClipOut forms its
+// whole-clip gain from truePeak[s] of the PcmLevelIo, which that pass left there, in the place of clipPeak[s]
+struct PcmLevel { unsigned mode; float gain, ceiling; unsigned truePeak; };
 // kClipOut takes the loudness mode's gain gL from loudGain[s], which kLoudGate (smst_loudness.h) left there, and limits it by ceiling/peak.
 constexpr unsigned kPcmLevelFixed = 0u, kPcmLevelProtect = 1u, kPcmLevelNormalise = 2u, kPcmLevelLoudness = 3u;
-struct PcmLevelIo { const PcmLevel *table = nullptr; int *peaks = nullptr; float *applied = nullptr; int *clipPeak = nullptr; const float *loudGain = nullptr; };
+struct PcmLevelIo { const PcmLevel *table = nullptr; int *peaks = nullptr; float *applied = nullptr; int *clipPeak = nullptr; const float *loudGain = nullptr;
+	const int *truePeak = nullptr; }; // (null: no stream of the call was measured -- every stream's gain comes from its clip peak)
 void launchPcmOut(int format, const float *in, long long inStreamStride, long long inChannelStride, void *out, long long outStreamStride, long long outFrameStride,
                   const int *counts, int S, int C, int maxFrames, unsigned *overs, hipStream_t st, const PcmDither *dither = nullptr, const PcmLevelIo &level = PcmLevelIo());
 // Whole clips of ragged lengths (smst_clip.h; Batch::exact): each stream moves two segments of frames between the caller's buffer and a planar
@@ -279,5 +282,15 @@ inline LoudScratch loudScratchAt(double *base, int S, int C, int maxChunks, int 
 // the four passes, on `st`: every stream's meters are written (a stream that is not measured: Z 0, no blocks, gL 1)
 void launchClipLoudness(const float *image, long long imageStreamStride, long long imageChannelStride, const ClipSeg *segs, int S, int C,
                         const LoudEntry *loud, const float *weights, const LoudScratch &w, hipStream_t st);
+// True peak of every flagged stream's clip (include/smst.h, "True peak", has the definition; smst_true_peak.h the kernel): a 4x polyphase
+// interpolation in float64 of every channel, in clip order across the join of the two segments, maxed with the samples themselves into
+// truePeak[s] as float bits (the caller zeroes the words in front of it).  level: the call's level entries, whose fourth word is the flag.
+// maxFrames: the longest measured clip (sizes the grid; nothing is launched for 0).  The taps travel by value, as a kernel argument
+constexpr int kTruePeakTile = 1024;                                        // frames of a channel's clip, in clip order, that one workgroup measures
+constexpr int kTruePeakTaps = 12, kTruePeakLead = 5, kTruePeakTrail = 6;   // tap j of a frame weighs the sample j - 5 frames from it
+struct TruePeakTable { float c[3][kTruePeakTaps]; };                       // phase p = 1, 2, 3 at [p - 1]
+const TruePeakTable &truePeakTable();
+void launchClipTruePeak(const float *image, long long imageStreamStride, long long imageChannelStride, const ClipSeg *segs, int S, int C, int maxFrames,
+                        const PcmLevel *level, int *truePeak, hipStream_t st);
 
 } // namespace smst

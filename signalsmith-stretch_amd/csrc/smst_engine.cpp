@@ -1852,6 +1852,15 @@ void Batch::exact(const ClipIo &io, const int *inSamples, const int *outSamples,
 		launchClipLoudness(dClipOut, outImgSS, pitchOut, cs.dev + (size_t)2*S, S, C, io.pcm.loud, io.pcm.loudWeights, w, st);
 		level.loudGain = w.gain;
 	}
+	int truePeakMost = 0;
+	if (io.pcm.level.table && io.truePeak) for (int s = 0; s < S; ++s) if (run[s] && io.truePeak[s]) truePeakMost = std::max(truePeakMost, outSamples[s]);
+	if (truePeakMost > 0) { // the flagged clips' true peaks, from the same image: what kClipOut forms those streams' whole-clip gains from
+		growScratch(dTruePeak, truePeakCapacity, (size_t)S, 0, true);
+		int *words = reinterpret_cast<int *>(dTruePeak);
+		SMST_HIP(hipMemsetAsync(words, 0, (size_t)S*sizeof(int), st));
+		launchClipTruePeak(dClipOut, outImgSS, pitchOut, cs.dev + (size_t)2*S, S, C, truePeakMost, io.pcm.level.table, words, st);
+		level.truePeak = words;
+	}
 	launchClipOut(io.format, dClipOut, outImgSS, pitchOut, io.out, io.outStreamStride, io.outInnerStride, cs.dev + (size_t)2*S, S, C,
 	              std::max(std::max(direct ? 0 : maxProc, maxFlush), maxZeros), io.pcm.overs, st, io.pcm.dither, level);
 	clipSets.end(st);
@@ -1866,6 +1875,14 @@ bool Batch::readLoudness(double *Z, int *counts) {
 	const LoudScratch w = loudScratchAt(reinterpret_cast<double *>(dLoud), S, C, 0, 0); // (the meters lie in front, whatever the call's shapes)
 	SMST_HIP(hipMemcpy(Z, w.Z, (size_t)S*sizeof(double), hipMemcpyDeviceToHost));
 	SMST_HIP(hipMemcpy(counts, w.counts, (size_t)2*S*sizeof(int), hipMemcpyDeviceToHost));
+	return true;
+}
+
+bool Batch::readTruePeaks(float *truePeaks) {
+	if (!dTruePeak) return false;
+	SMST_HIP(hipSetDevice(dev));
+	SMST_HIP(hipStreamSynchronize(st));
+	SMST_HIP(hipMemcpy(truePeaks, dTruePeak, (size_t)S*sizeof(float), hipMemcpyDeviceToHost));
 	return true;
 }
 

@@ -111,9 +111,13 @@ public:
 	// pcm (frame formats; smst_pcm_tables.h): the device side of the output conversion, which rides in the caller's per-call table.  wholeClip
 	// (host, [S]; null where the call is not levelled): which streams' gains come from their clip's peak -- if one of them runs, kClipPeak
 	// does.  loudHop (host, [S]; null where no stream is in the loudness mode): h of the streams in that mode, 0 for the others -- if one of
-	// them runs, the four passes of smst_loudness.h do, and kClipOut finds the gains in the engine's meters
+	// them runs, the four passes of smst_loudness.h do, and kClipOut finds the gains in the engine's meters.  truePeak (host, [S]; null where
+	// no stream has the true-peak flag): the streams that have it -- if one of them runs, kClipTruePeak (smst_true_peak.h) does, and kClipOut
+	// forms those streams' whole-clip gains from the words it leaves in the engine's memory
 	struct ClipIo { const void *in; long long inStreamStride, inInnerStride; void *out; long long outStreamStride, outInnerStride; int format;
-		PcmOutCall pcm; const unsigned char *wholeClip = nullptr; const int *loudHop = nullptr; };
+		PcmOutCall pcm; const unsigned char *wholeClip = nullptr; const int *loudHop = nullptr; const unsigned char *truePeak = nullptr; };
+	// the true peaks of the newest exact call that measured, [S] (0: a stream it did not measure); false: none has.  Synchronises
+	bool readTruePeaks(float *truePeaks);
 	// the loudness meters of the newest exact call that measured, [S] and [S][2] (blocks past the absolute gate, past both); false: none has.  Synchronises
 	bool readLoudness(double *Z, int *counts);
 	void exact(const ClipIo &io, const int *inSamples, const int *outSamples, unsigned char *tooShort);
@@ -301,6 +305,8 @@ private:
 	size_t clipInCapacity = 0, clipOutCapacity = 0;
 	float *dLoud = nullptr; // the loudness passes' scratch (LoudScratch: float64, the meters in front), grown on demand as the images are
 	size_t loudCapacity = 0;
+	float *dTruePeak = nullptr; // the true-peak words of the newest exact call that measured ([S] float bits), allocated by the first one
+	size_t truePeakCapacity = 0;
 	struct ClipSet { ClipSeg *host, *dev; }; // [2][S][2]: input segments, output segments
 	TwoSets<ClipSet> clipSets;
 	// a device scratch that holds `need` floats, allocated with `room` more; true: it was replaced (the old one freed behind a synchronise).  workspace: counted in workspaceBytes()

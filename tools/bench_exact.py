@@ -12,6 +12,8 @@ the host from its first entry point to the return of smst_batch_synchronize.
                                                   # step, a batch each: fixed - pcm = the levelled copy kernel, protect - fixed = the peak pass
   python tools/bench_exact.py --mode normalise --loudness   # NORMALISE and LOUDNESS (-23 LUFS at --sample-rate) alternating: loudness - normalise =
                                                   # the four loudness passes (mode normalise alone also runs on a build without them: SMST_LIBRARY)
+  python tools/bench_exact.py --mode normalise --true-peak  # NORMALISE without and with the true-peak flag alternating: true_peak - normalise =
+                                                  # the true-peak pass
 """
 import argparse
 import ctypes as C
@@ -35,6 +37,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--mode", choices=["three", "exact", "ragged", "pcm", "fixed", "protect", "level", "normalise"], required=True)
     ap.add_argument("--loudness", action="store_true", help="frame modes: a batch in LEVEL_LOUDNESS (-23 LUFS, ceiling 32766/32768) beside the mode's own")
+    ap.add_argument("--true-peak", action="store_true", help="frame modes: a batch with the mode's own level setting and the true-peak flag on every stream beside the mode's own")
     ap.add_argument("--streams", type=int, default=256)
     ap.add_argument("--channels", type=int, default=2)
     ap.add_argument("--seconds", type=float, default=10.0)
@@ -118,8 +121,12 @@ def frames_modes(a, lib, x, nin, nout, batch):
     torch.cuda.synchronize()
     ip = lambda v: v.ctypes.data_as(C.POINTER(C.c_int))
     runs = {}
-    for name in (("pcm", "fixed", "protect") if a.mode == "level" else (a.mode,)) + (("loudness",) if a.loudness else ()):
+    assert not (a.true_peak and a.mode == "level"), "--true-peak goes with one mode"
+    for key in (("pcm", "fixed", "protect") if a.mode == "level" else (a.mode,)) + (("loudness",) if a.loudness else ()) + (("true_peak",) if a.true_peak else ()):
         b = batch()
+        name = a.mode if key == "true_peak" else key
+        if key == "true_peak":
+            b.set_pcm_true_peak(True)
         if name == "fixed":
             b.set_pcm_level(smst.LEVEL_FIXED, 0.5)
         if name == "protect":
@@ -128,7 +135,7 @@ def frames_modes(a, lib, x, nin, nout, batch):
             b.set_pcm_level(smst.LEVEL_NORMALISE, 1.0, 32766.0/32768.0)
         if name == "loudness":
             b.set_pcm_loudness(-23.0, 32766.0/32768.0, a.sample_rate)
-        runs[name] = b
+        runs[key] = b
 
     def call(b):
         status = np.zeros(S, np.int32)
@@ -159,6 +166,13 @@ def frames_modes(a, lib, x, nin, nout, batch):
                                   image_bytes=int(S)*Cn*int(nout.sum()//S)*4)
         if a.mode in result["step_ms"]:
             result["loudness"]["minus_%s_ms" % a.mode] = round(result["step_ms"]["loudness"]["median"] - result["step_ms"][a.mode]["median"], 3)
+    if a.true_peak:
+        tp = runs["true_peak"].take_pcm_true_peaks()
+        peaks, gains = runs["true_peak"].take_pcm_peaks()
+        result["true_peak"] = dict(true_peak_range=[float(tp.min()), float(tp.max())], sample_peak_range=[float(peaks.min()), float(peaks.max())],
+                                   gain_range=[float(gains.min()), float(gains.max())], image_bytes=int(S)*Cn*int(nout.sum()//S)*4,
+                                   launches=smst.launch_count("clip_true_peak", lib))
+        result["true_peak"]["minus_%s_ms" % a.mode] = round(result["step_ms"]["true_peak"]["median"] - result["step_ms"][a.mode]["median"], 3)
     print(json.dumps(result))
     for b in runs.values():
         b.close()

@@ -5,7 +5,7 @@
 //
 //   stretch_cli [--semitones=S] [--formant=S] [--formant-comp] [--formant-base=Hz] [--tonality=Hz] [--time=F]
 //               [--split-computation] [--device=N] [--out-format=s16|s24|f32] [--dither=none|tpdf|tpdf-hp] [--dither-seed=N]
-//               [--exact] [--gain=dB] [--protect=dBFS | --normalize=dBFS] [--loudness=LUFS]
+//               [--exact] [--gain=dB] [--protect=dBFS | --normalize=dBFS] [--loudness=LUFS] [--true-peak]
 //               in.wav out.wav [in2.wav out2.wav ...]
 //
 // --out-format (also "--out-format s24"): the samples of the files written -- 16-bit (the default, as the reference's CLI writes), 24-bit by the
@@ -26,6 +26,10 @@
 // measured on the GPU at the files' sample rate; include/smst.h, "Loudness"), with --protect=dBFS as the ceiling that limits the gain
 // (none without it; --gain is not used).  The line then reads "level: <file> loudness=<%.4f> peak=... gain=... overs=...": the measured
 // loudness in LUFS before the gain, -inf for a clip that has none (shorter than 400 ms, silent).
+// --true-peak (needs the exact flow: --exact, or one of --protect / --normalize / --loudness, which imply it): every rendered clip's true
+// peak is measured on the GPU (a 4x interpolation between the samples; include/smst.h, "True peak") and the ceilings of --protect,
+// --normalize and --loudness are dBTP: the gain comes from the true peak instead of the sample peak.  Alone it only meters.  The line of a
+// file then ends in " true-peak=<%.4f>": the true peak before the gain, in dBTP (-inf for silence).
 // Files given together must share sample rate and channel count (they form one batch); lengths may differ.
 #include <algorithm>
 #include <cmath>
@@ -100,7 +104,12 @@ int main(int argc, char **argv) {
 		std::fprintf(stderr, "--loudness and --normalize exclude each other\n");
 		return 2;
 	}
-	const bool exact = hasFlag(argc, argv, "exact") || protect || normalize || loudness, levelled = hasGain || protect || normalize || loudness;
+	const bool truePeak = hasFlag(argc, argv, "true-peak");
+	const bool exact = hasFlag(argc, argv, "exact") || protect || normalize || loudness, levelled = hasGain || protect || normalize || loudness || truePeak;
+	if (truePeak && !exact) {
+		std::fprintf(stderr, "--true-peak needs --exact (or --protect, --normalize or --loudness, which imply it): whole clips only\n");
+		return 2;
+	}
 	const float gain = fromDecibels(flagValue(argc, argv, "gain", 0)), ceiling = fromDecibels(flagValue(argc, argv, protect ? "protect" : "normalize", 0));
 	std::vector<std::string> files;
 	for (int i = 1; i < argc; ++i) if (std::strncmp(argv[i], "--", 2) && !consumed[i]) files.push_back(argv[i]);
@@ -160,6 +169,7 @@ int main(int argc, char **argv) {
 		if (dither != SMST_DITHER_NONE) CHECK(smst_batch_set_pcm_dither(batch, -1, dither, ditherSeed));
 		if (loudness) CHECK(smst_batch_set_pcm_loudness(batch, -1, flagValue(argc, argv, "loudness", 0), protect ? ceiling : INFINITY, double(inputs[0].sampleRate)));
 		else if (levelled) CHECK(smst_batch_set_pcm_level(batch, -1, protect ? SMST_LEVEL_PROTECT : normalize ? SMST_LEVEL_NORMALISE : SMST_LEVEL_FIXED, gain, ceiling));
+		if (truePeak) CHECK(smst_batch_set_pcm_true_peak(batch, -1, 1));
 		// `count` samples of file s from sample `first` on as frames at `frames`; false: one of them is no value of the format
 		auto toFrames = [&](int s, int first, int count, unsigned char *frames) {
 			for (int i = 0; i < count; ++i) for (int c = 0; c < C; ++c) {
@@ -205,10 +215,14 @@ int main(int argc, char **argv) {
 			CHECK(smst_batch_take_pcm_peaks(batch, peaks.data(), gains.data()));
 			std::vector<double> lufs(S, 0.0);
 			if (loudness) CHECK(smst_batch_take_pcm_loudness(batch, lufs.data(), nullptr, nullptr));
+			std::vector<float> truePeaks(S, 0.0f);
+			if (truePeak) CHECK(smst_batch_take_pcm_true_peaks(batch, truePeaks.data()));
 			for (int s = 0; s < S; ++s) {
 				std::printf("level: %s ", files[2*s + 1].c_str());
 				if (loudness) std::printf("loudness=%.4f ", lufs[s]);
-				std::printf("peak=%.9g gain=%.9g overs=%lld\n", peaks[s], gains[s], clamped[s]);
+				std::printf("peak=%.9g gain=%.9g overs=%lld", peaks[s], gains[s], clamped[s]);
+				if (truePeak) std::printf(" true-peak=%.4f", 20.0*std::log10(double(truePeaks[s])));
+				std::printf("\n");
 			}
 		}
 		for (int s = 0; s < S; ++s) {
