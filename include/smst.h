@@ -403,7 +403,8 @@ int smst_batch_pcm_dither(const smst_batch *b, int stream, int *mode, long long 
  * a whole-clip gain in a streaming call would be a silent lie.  smst_batch_exact_pcm serves all three modes.  The too-short and left-out
  * streams of an exact call stay as they are: undithered zeros or untouched, peak and gain unchanged.  Out of scope: the planar calls and the
  * planar smst_batch_exact are neither levelled nor metered; separate input and output formats in one call.  (The peak above is the SAMPLE
- * peak; "True peak" below has the inter-sample meter and what it does to the ceilings.)
+ * peak; "True peak" below has the inter-sample meter and what it does to the ceilings, "Limiter" the stage that meets a ceiling frame by
+ * frame instead of lowering the whole clip's gain.)
  *
  * Clip-free ceilings.  fl(peak*fl(ceiling/peak)) may exceed the ceiling by an fp32 rounding or two, so a ceiling of exactly full scale can
  * clamp.  No element is clamped (smst_batch_take_pcm_overs gives 0) when ceiling*scale is at most
@@ -531,7 +532,7 @@ int smst_debug_clip_loudness(int device, int streams, int channels, const int *s
  * memory that grows with the first call that measures and counts in smst_batch_workspace_bytes: a second call of the same shapes allocates
  * nothing, no host synchronisation is added, and the ordering contract of the device-memory call is unchanged.  The maximum is one of
  * integers and no floating-point atomic is used: a call's result is bit-reproducible whatever the scheduling.
- * Out of scope: true-peak metering in the streaming and the planar calls; a limiter; an oversampling factor that depends on the rate (4x at
+ * Out of scope: true-peak metering in the streaming and the planar calls; an oversampling factor that depends on the rate (4x at
  * every rate); momentary and short-term loudness, loudness range.
  * SMST_ERR_INVALID with a message: a stream index out of range, a null batch. */
 #define SMST_TRUE_PEAK_TILE 1024 /* frames of a channel's clip that one workgroup of the true-peak pass measures (kTruePeakTile) */
@@ -551,6 +552,83 @@ int smst_debug_clip_true_peak(int device, int streams, int channels, const int *
                               float *truePeaks, float *samplePeaks, const int *flags);
 /* test hook: the library's tap table c[p][j], phase-major: out[12*(p - 1) + j], p = 1, 2, 3 */
 int smst_debug_true_peak_taps(float *out);
+/* ---- Limiter (EXTENSION; opt-in: a batch that never calls smst_batch_set_pcm_limiter launches the kernels, writes the bytes and counts the launches it did before) ----
+ * A ceiling above can only lower the gain of the WHOLE clip (g = gL <= q ? gL : q): a clip with one loud transient comes out quieter than the
+ * LUFS target its caller asked for.  A stream with the limiter flag keeps its whole-clip gain and has the frames that would exceed the
+ * ceiling brought down to it by a lookahead limiter, in smst_batch_exact_pcm only.  Within a stream the channels are linked: one gain curve
+ * r(n).  The curve is non-recursive -- a function of the frames within 2H of n --, so it is bit-reproducible whatever the scheduling.
+ *
+ * The flag is a setting of its own beside the stream's level mode, as the true-peak flag is; the batch has one lookahead of H frames,
+ * 1 <= H <= SMST_LIMITER_MAX_LOOKAHEAD.  The limiter acts on PROTECT and LOUDNESS streams.  FIXED has no ceiling and NORMALISE meets its
+ * ceiling by construction: there the flag is inert -- r is identically 1, the call writes the bytes and launches the kernels it does without
+ * the flag.  For a limited stream of N = outSamples[s] frames, x_c(n) the samples of channel c in clip order:
+ * 1. g, the whole-clip gain WITHOUT the quotient q: PROTECT g = gain; LOUDNESS g = gL (1 where loudness is undefined).
+ *    smst_batch_take_pcm_peaks reports this g.
+ * 2. Detector: m(n) = the maximum over the channels of the bit pattern of |x_c(n)|; with the stream's true-peak flag also of
+ *    float32(|y_p,c(n)|), p = 1, 2, 3 -- "True peak"'s own phases of frame n, in its float64 arithmetic, each rounded once.  NaNs are skipped.
+ * 3. Need: w = m(n)*g, one fp32 multiply (|v*g| of the loudest channel: the multiply the conversion makes).  need(n) = ceiling/w, the
+ *    correctly rounded fp32 quotient, where w is finite and w > ceiling; else need(n) = 1 (w not finite, a ceiling of +inf, a g that is not
+ *    finite or not above 0: "no limit", as q has it).  Outside [0, N) need is 1.
+ * 4. Hold: hold(i) = the minimum of need(j) over |j - i| <= H, for i in [-H, N + H).
+ * 5. Smooth: win[k] = float32(h_k / sum h), h_k = 0.5*(1 + cos(pi*k/(H + 1))), k = -H ... H, computed by the host in double, one rounding.
+ *    y(n) = sum_{k = -H ... H} double(win[k]) * double(hold(n + k)), in float64, from 0.0, in that order.  The products are exact, so a
+ *    fused multiply-add changes nothing (the true-peak argument).
+ * 6. Gain: r(n) = 1.0f exactly where every hold(n + k), |k| <= H, is 1 (no need below 1 within 2H frames); else r(n) = min(float32(y(n)),
+ *    need(n)).  So r(n) <= need(n) for every frame whatever the rounding of the window, and a clip that never exceeds its ceiling gets the
+ *    bytes it gets with the limiter off.
+ * 7. Apply: w = v*g as in "Level", then u = w*r(n), one more fp32 multiply of its own (never fused), then the format's rule on u, dither
+ *    behind it.  Overs and the sample-peak meter stay as they are.
+ * The too-short and left-out streams of a call stay as they are.  smst_batch_process_pcm and smst_batch_flush_pcm return SMST_ERR_INVALID,
+ * before anything runs, if a stream that takes part has the flag: the rule and the reason of the whole-clip modes.
+ *   Known answers (float32 bit patterns).  Window, H = 1: 3e800000 3f000000 3e800000.  H = 2: 3daaaaab 3e800000 3eaaaaab 3e800000 3daaaaab.
+ *   H = 72: win[-72] = 36d4ca98, win[-71] = 37d4b160, win[0] = 3c607038.
+ *   Mono, 13 frames, x(6) = 1, else 0; g = 1, ceiling 0.5, H = 2, no true peak: r = 3f800000 3f800000 3f755556 3f555556 3f2aaaab 3f0aaaab
+ *   3f000000 3f0aaaab 3f2aaaab 3f555556 3f755556 3f800000 3f800000.  5 frames, x(0) = 1, the same settings: r = 3f000000 3f0aaaab 3f2aaaab
+ *   3f555556 3f755556 -- the clip's edge counts as need 1.  12 frames, x(5) = x(6) = 1, g = 1, ceiling 1, H = 1, true-peak flag on:
+ *   need(5) = 3f4cbb59 (1/1.2504163: the inter-sample crest belongs to frame 5), r(3 ... 7) = 3f732ed6 3f598c83 3f4cbb59 3f598c83 3f732ed6,
+ *   1 elsewhere.
+ *
+ * What it guarantees.  The SAMPLE peak of u is at most the ceiling, up to the fp32 roundings of ceiling/w and w*r: fl(w*fl(ceiling/w)) is the
+ * function of "Clip-free ceilings" above with w in the place of the peak, and r < need only lowers it -- the same search on the limiter's
+ * mirror (tests/limiter_cases.py, CPU) gives the same table: no element is clamped when ceiling*scale is at most 32767 / 32766 (int16
+ * without / with dither), 8388606 / 8388605 (int24), 2^31 - 256 (int32).
+ * The TRUE peak of the limited output is not bounded exactly, with or without the true-peak flag: the interpolator does not commute with a
+ * gain that varies from frame to frame.  It is a measured property (the true-peak mirror on the limiter mirror's float32 output; white noise,
+ * AM tones and sparse spikes driven 12 dB over the ceiling, true-peak flag on): the worst true peak exceeds the ceiling by 2.4e-6 at
+ * H = 72, 2.5e-5 at H = 36, 3.4e-3 (0.03 dB) at H = 8 and 17 % (1.4 dB) at H = 1 (EXPERIMENTS.md, "Limiter").  A short lookahead weakens a dBTP promise: the window must be long against the
+ * 12 taps of the interpolator.
+ *
+ * How.  Two kernels (csrc/smst_limiter.h) behind the peak, loudness and true-peak passes and in front of the conversion, whose
+ * limited variant reads r at the frame's clip position.  The flag is bit 1 of the fourth word of the stream's level entry (bit 0: true
+ * peak); H travels as a kernel argument; the window is device memory, uploaded by the setters below, never in a call.  need, r ([streams]
+ * [longest limited clip] floats each) and the meter words grow with the first call that limits and count in smst_batch_workspace_bytes: a
+ * second call of the same shapes allocates nothing, no host synchronisation is added, and the ordering contract of the device-memory call is
+ * unchanged.  The meters are integers: no floating-point atomic.
+ * Out of scope: a streaming limiter, release shaping other than the symmetric window, a lookahead per stream, oversampled gain application.
+ * SMST_ERR_INVALID with a message: a lookahead outside [1, SMST_LIMITER_MAX_LOOKAHEAD], a stream index out of range, a null batch. */
+#define SMST_LIMITER_MAX_LOOKAHEAD 1024
+#define SMST_LIMITER_DEFAULT_LOOKAHEAD 72 /* 1.5 ms at 48 kHz */
+#define SMST_LIMITER_TILE 1024 /* frames of a clip that one workgroup of either pass takes (kLimitTile) */
+/* stream = -1: every stream.  The first call with on != 0 makes the batch a levelled one and puts the window into device memory */
+int smst_batch_set_pcm_limiter(smst_batch *b, int stream, int on);
+/* on may be null */
+int smst_batch_pcm_limiter(const smst_batch *b, int stream, int *on);
+/* the batch's lookahead H in frames; synchronises the batch where the window is on the device already */
+int smst_batch_set_pcm_limiter_lookahead(smst_batch *b, int frames);
+int smst_batch_pcm_limiter_lookahead(const smst_batch *b, int *frames);
+/* per stream, of the newest smst_batch_exact_pcm that limited: minGain[s] = the lowest r(n), limitedFrames[s] = the frames with r(n) < 1;
+ * 1 and 0 for a stream that call did not limit and before any call has limited.  Either may be null.  Synchronises the batch; resets nothing. */
+int smst_batch_take_pcm_limiter(smst_batch *b, float *minGain, long long *limitedFrames);
+/* test hook: the limiter's two passes alone on a planar fp32 image (host pointer, strides in floats) with a segment table as
+ * smst_debug_clip_true_peak's.  Per stream: g = gains[s] (the PROTECT form), ceilings[s], flags[s] with bit 0 true peak and bit 1 limiter.
+ * need and r: [streams][maxFrames], indexed [s*maxFrames + n], 1 where nothing is limited (maxFrames >= every clip's length); minGain,
+ * limitedFrames: [streams], as smst_batch_take_pcm_limiter.  Every output pointer may be null. */
+int smst_debug_clip_limit(int device, int streams, int channels, const int *segments,
+                          const float *image, long long imageStreamStride, long long imageChannelStride,
+                          const float *gains, const float *ceilings, const int *flags, int lookahead,
+                          float *need, float *r, int maxFrames, float *minGain, long long *limitedFrames);
+/* test hook: the library's window, out[k + lookahead] = win[k], k = -lookahead ... lookahead */
+int smst_debug_limiter_window(int lookahead, float *out);
 /* per stream, since the last take: peaks[s] = the largest |v| the levelled output conversions met BEFORE the gain (0 if none); gains[s] = the
  * gain the newest levelled conversion of stream s applied (1 before any).  Either may be null.  Synchronises the batch; resets the peaks,
  * not the gains. */

@@ -31,6 +31,7 @@ LEVEL_FIXED, LEVEL_PROTECT, LEVEL_NORMALISE = 0, 1, 2        # level of the fram
 LEVEL_LOUDNESS = 3                                           # ... to a LUFS target (StretchBatch.set_pcm_loudness)
 LOUDNESS_CHUNK = 256                                         # frames one lane of the loudness passes filters (SMST_LOUDNESS_CHUNK)
 TRUE_PEAK_TILE = 1024                                        # frames one workgroup of the true-peak pass measures (SMST_TRUE_PEAK_TILE)
+LIMITER_TILE, LIMITER_MAX_LOOKAHEAD, LIMITER_DEFAULT_LOOKAHEAD = 1024, 1024, 72  # frames one workgroup of the limiter's passes takes; the lookahead's bound and default (SMST_LIMITER_*)
 _FRAME_DTYPES = {"int16": PCM_S16, "float32": PCM_F32, "int32": PCM_S32, "float16": PCM_F16}  # (packed int24 travels as uint8 [..., 3])
 _FRAME_DTYPE_OF = {PCM_S16: "int16", PCM_F32: "float32", PCM_S32: "int32", PCM_F16: "float16", PCM_S24: "uint8"}
 _fp = C.POINTER(C.c_float)
@@ -145,6 +146,13 @@ _SIGNATURES = {
     "smst_batch_take_pcm_true_peaks": (C.c_int, [C.c_void_p, _fp]),
     "smst_debug_clip_true_peak": (C.c_int, [C.c_int, C.c_int, C.c_int, _ip, C.c_void_p, _ll, _ll, _fp, _fp, _ip]),
     "smst_debug_true_peak_taps": (C.c_int, [_fp]),
+    "smst_batch_set_pcm_limiter": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
+    "smst_batch_pcm_limiter": (C.c_int, [C.c_void_p, C.c_int, _ip]),
+    "smst_batch_set_pcm_limiter_lookahead": (C.c_int, [C.c_void_p, C.c_int]),
+    "smst_batch_pcm_limiter_lookahead": (C.c_int, [C.c_void_p, _ip]),
+    "smst_batch_take_pcm_limiter": (C.c_int, [C.c_void_p, _fp, C.POINTER(_ll)]),
+    "smst_debug_clip_limit": (C.c_int, [C.c_int, C.c_int, C.c_int, _ip, C.c_void_p, _ll, _ll, _fp, _fp, _ip, C.c_int, _fp, _fp, C.c_int, _fp, C.POINTER(_ll)]),
+    "smst_debug_limiter_window": (C.c_int, [C.c_int, _fp]),
     "smst_batch_synchronize": (C.c_int, [C.c_void_p]),
     "smst_batch_hip_stream": (C.c_void_p, [C.c_void_p]),
     "smst_batch_enable_profiling": (C.c_int, [C.c_void_p, C.c_int]),
@@ -336,6 +344,31 @@ def debug_true_peak_taps(lib=None):
     taps = np.zeros((3, 12), np.float32)
     _check(lib, lib.smst_debug_true_peak_taps(taps.ctypes.data_as(_fp)))
     return taps
+
+
+def debug_clip_limit(segments, channels, image, image_ss, image_cs, gains, ceilings, flags, lookahead, max_frames, device=0, lib=None):
+    """smst_debug_clip_limit on a numpy image (planar float32; segments int [S, 2, 4]; strides in floats; gains, ceilings, flags: [S], flags
+    with bit 0 true peak and bit 1 limiter) -> (need, r: float32 [S, max_frames]; min gain: float32 [S]; limited frames: int64 [S])"""
+    lib = lib if lib is not None else load_library()
+    seg = np.ascontiguousarray(segments, np.int32)
+    S = seg.shape[0]
+    g, c, f = np.ascontiguousarray(gains, np.float32), np.ascontiguousarray(ceilings, np.float32), np.ascontiguousarray(flags, np.int32)
+    assert g.shape == c.shape == f.shape == (S,)
+    need, r = np.full((S, max_frames), -1, np.float32), np.full((S, max_frames), -1, np.float32)
+    low, frames = np.full(S, -1, np.float32), np.full(S, -1, np.int64)
+    _check(lib, lib.smst_debug_clip_limit(device, S, channels, seg.ctypes.data_as(_ip), C.c_void_p(image.ctypes.data), image_ss, image_cs,
+                                          g.ctypes.data_as(_fp), c.ctypes.data_as(_fp), f.ctypes.data_as(_ip), int(lookahead),
+                                          need.ctypes.data_as(_fp), r.ctypes.data_as(_fp), int(max_frames), low.ctypes.data_as(_fp),
+                                          frames.ctypes.data_as(C.POINTER(_ll))))
+    return need, r, low, frames
+
+
+def debug_limiter_window(lookahead, lib=None):
+    """smst_debug_limiter_window -> float32 [2*lookahead + 1]: the library's smoothing window"""
+    lib = lib if lib is not None else load_library()
+    win = np.zeros(2*int(lookahead) + 1, np.float32)
+    _check(lib, lib.smst_debug_limiter_window(int(lookahead), win.ctypes.data_as(_fp)))
+    return win
 
 
 def launch_count(name, lib=None):
@@ -746,6 +779,36 @@ class StretchBatch:
         _check(self.lib, self.lib.smst_batch_take_pcm_true_peaks(self.h, peaks.ctypes.data_as(_fp)))
         self._inflight = []
         return peaks
+
+    def set_pcm_limiter(self, on=True, stream=-1):
+        """The limiter flag (include/smst.h, "Limiter"), exactFrames only: a stream in LEVEL_PROTECT or LEVEL_LOUDNESS keeps its whole-clip
+        gain -- the clip reaches its LUFS target -- and a lookahead limiter, on the device, brings the frames that would exceed the ceiling
+        down to it (with the true-peak flag: the frames whose inter-sample values would).  Inert in the other two modes.  stream = -1: every
+        stream.  set_pcm_level and set_pcm_loudness leave the flag as it is."""
+        _check(self.lib, self.lib.smst_batch_set_pcm_limiter(self.h, int(stream), 1 if on else 0))
+
+    def pcm_limiter(self, stream):
+        """-> whether the stream has the limiter flag"""
+        on = C.c_int(0)
+        _check(self.lib, self.lib.smst_batch_pcm_limiter(self.h, int(stream), C.byref(on)))
+        return bool(on.value)
+
+    def set_pcm_limiter_lookahead(self, frames):
+        """The batch's lookahead in frames, 1 ... LIMITER_MAX_LOOKAHEAD (default 72: 1.5 ms at 48 kHz)"""
+        _check(self.lib, self.lib.smst_batch_set_pcm_limiter_lookahead(self.h, int(frames)))
+
+    def pcm_limiter_lookahead(self):
+        frames = C.c_int(0)
+        _check(self.lib, self.lib.smst_batch_pcm_limiter_lookahead(self.h, C.byref(frames)))
+        return frames.value
+
+    def take_pcm_limiter(self):
+        """-> (float32 [S]: the lowest r, int64 [S]: the frames with r < 1) of the newest exactFrames that limited; 1 and 0 for a stream it
+        did not limit.  Synchronises the batch; resets nothing."""
+        low, frames = np.ones(self.streams, np.float32), np.zeros(self.streams, np.int64)
+        _check(self.lib, self.lib.smst_batch_take_pcm_limiter(self.h, low.ctypes.data_as(_fp), frames.ctypes.data_as(C.POINTER(_ll))))
+        self._inflight = []
+        return low, frames
 
     # --- test hooks
     def debug_state(self, stream, which):

@@ -83,13 +83,15 @@ struct PcmOutState {
 	// the true-peak flag (smst_batch_set_pcm_true_peak): a setting of its own beside the stream's mode, which the two setters above leave as
 	// it is; the first stream that gets it makes the batch a levelled one
 	std::vector<unsigned char> truePeak;
+	// the limiter flag (smst_batch_set_pcm_limiter): likewise; it acts in SMST_LEVEL_PROTECT and _LOUDNESS only (smst::pcmLimited)
+	std::vector<unsigned char> limiter;
 	bool levelled = false;
 	// overs ([S][2]: clamped, NaN): the kernels add to them, takeOvers() reads and clears them; the meter words (smst::PcmMeters)
 	Buffer<unsigned, false> dOvers;
 	Buffer<int, false> dMeters;
 	std::vector<unsigned> hOvers;
 	std::vector<int> hMeters;
-	std::vector<unsigned char> wholeClip; // clipModes()' arrays
+	std::vector<unsigned char> wholeClip, limited; // clipModes()' arrays
 	std::vector<int> loudHop;
 
 	void create(int streams, int channels) {
@@ -100,7 +102,9 @@ struct PcmOutState {
 		loud.assign((size_t)S, Loud());
 		loudWeights.assign((size_t)C, 1.0f);
 		truePeak.assign((size_t)S, 0);
+		limiter.assign((size_t)S, 0);
 		wholeClip.assign((size_t)S, 0);
+		limited.assign((size_t)S, 0);
 		loudHop.assign((size_t)S, 0);
 		hOvers.assign((size_t)2*S, 0u);
 		dOvers.allocate((size_t)2*S, "PCM overs");
@@ -153,6 +157,11 @@ struct PcmOutState {
 		if (levelled) for (unsigned char on : truePeak) if (on) return true;
 		return false;
 	}
+	void setLimiter(int stream, int on) {
+		forStreams(stream, [&](int s) { limiter[s] = on ? 1 : 0; });
+		if (on) levelled = true;
+	}
+	unsigned flags(int s) const { return (truePeak[s] ? smst::kPcmFlagTruePeak : 0u) | (limiter[s] ? smst::kPcmFlagLimiter : 0u); }
 	void setLoudnessWeights(const float *weights) {
 		for (int c = 0; weights && c < C; ++c) if (!(std::isfinite(weights[c]) && weights[c] >= 0)) throw smst::Error("loudness: a channel weight is negative or not finite");
 		for (int c = 0; c < C; ++c) loudWeights[c] = weights ? weights[c] : 1.0f;
@@ -183,7 +192,7 @@ struct PcmOutState {
 			call.loudWeights = at.weights(dev);
 		}
 		if (levelled) {
-			for (int s = 0; s < S; ++s) at.level(host)[s] = smst::PcmLevel{unsigned(level[s].mode), level[s].gain, level[s].ceiling, unsigned(truePeak[s])};
+			for (int s = 0; s < S; ++s) at.level(host)[s] = smst::PcmLevel{unsigned(level[s].mode), level[s].gain, level[s].ceiling, flags(s)};
 			call.level = smst::PcmMeters(S).io(at.level(dev), dMeters);
 		}
 		if (dithered || levelled) {
@@ -193,10 +202,13 @@ struct PcmOutState {
 		return call;
 	}
 	// What exact() needs on the host beside a call's view: which streams' gains come from their clip's peak (they decide whether kClipPeak
-	// runs), h of those in the loudness mode (whether the four passes do), and the true-peak flags (whether kClipTruePeak does).  Null as the
-	// view's members are
+	// runs), h of those in the loudness mode (whether the four passes do), the true-peak flags (whether kClipTruePeak does) and the streams
+	// that are limited (whether the limiter's two passes do).  Null as the view's members are
 	void clipModes(const smst::PcmOutCall &call, Batch::ClipIo &io) {
+		bool anyLimited = false;
 		for (int s = 0; s < S; ++s) {
+			limited[s] = levelled && smst::pcmLimited(smst::PcmLevel{unsigned(level[s].mode), level[s].gain, level[s].ceiling, flags(s)});
+			anyLimited = anyLimited || limited[s];
 			wholeClip[s] = level[s].mode != SMST_LEVEL_FIXED;
 			loudHop[s] = level[s].mode == SMST_LEVEL_LOUDNESS ? loud[s].entry.h : 0;
 		}
@@ -204,6 +216,7 @@ struct PcmOutState {
 		io.wholeClip = call.level.table ? wholeClip.data() : nullptr;
 		io.loudHop = call.loud ? loudHop.data() : nullptr;
 		io.truePeak = call.level.table && anyTruePeak() ? truePeak.data() : nullptr;
+		io.limiter = call.level.table && anyLimited ? limited.data() : nullptr;
 	}
 	// after a call that emitted n[s] frames: the counters of the streams that have a mode move on, whatever the call's format
 	void advance(const int *n) {
@@ -726,6 +739,35 @@ int smst_batch_take_pcm_true_peaks(smst_batch *b, float *truePeaks) {
 		if (truePeaks) std::copy(peaks.begin(), peaks.end(), truePeaks);
 	})
 }
+int smst_batch_set_pcm_limiter(smst_batch *b, int stream, int on) {
+	BATCH_CALL({
+		b->pcmOut.setLimiter(stream, on);
+		if (on) b->engine->prepareLimiter(); // (the window goes to the device here, not in a call)
+	})
+}
+int smst_batch_pcm_limiter(const smst_batch *b, int stream, int *on) {
+	if (!b || !b->engine) return fail("null batch");
+	if (stream < 0 || stream >= b->engine->streams()) return fail("stream index out of range");
+	if (on) *on = b->pcmOut.limiter[stream];
+	return SMST_OK;
+}
+int smst_batch_set_pcm_limiter_lookahead(smst_batch *b, int frames) { BATCH_CALL(b->engine->setLimiterLookahead(frames)) }
+int smst_batch_pcm_limiter_lookahead(const smst_batch *b, int *frames) {
+	if (!b || !b->engine) return fail("null batch");
+	if (frames) *frames = b->engine->limiterLookahead();
+	return SMST_OK;
+}
+int smst_batch_take_pcm_limiter(smst_batch *b, float *minGain, long long *limitedFrames) {
+	BATCH_CALL({
+		Batch &e = *b->engine;
+		e.synchronize();
+		std::vector<float> gains((size_t)e.streams(), 1.0f);
+		std::vector<long long> frames((size_t)e.streams(), 0);
+		e.readLimiter(gains.data(), frames.data()); // (false: no call has limited yet -- 1 and 0 for every stream)
+		if (minGain) std::copy(gains.begin(), gains.end(), minGain);
+		if (limitedFrames) std::copy(frames.begin(), frames.end(), limitedFrames);
+	})
+}
 // Z and the count of gated blocks -> LUFS; -inf where loudness is undefined
 static double loudnessLufs(double Z, int gated) { return (gated > 0 && Z > 0 && std::isfinite(Z)) ? -0.691 + 10*std::log10(Z) : -INFINITY; }
 int smst_batch_take_pcm_loudness(smst_batch *b, double *lufs, int *blocks, int *gated) {
@@ -753,6 +795,9 @@ static void refuseWholeClipLevel(const smst_batch *b, const unsigned char *activ
 	for (size_t s = 0; s < b->pcmOut.truePeak.size(); ++s)
 		if ((!active || active[s]) && b->pcmOut.truePeak[s])
 			throw smst::Error("stream " + std::to_string(s) + " has the true-peak flag (smst_batch_set_pcm_true_peak): smst_batch_exact_pcm only");
+	for (size_t s = 0; s < b->pcmOut.limiter.size(); ++s)
+		if ((!active || active[s]) && b->pcmOut.limiter[s])
+			throw smst::Error("stream " + std::to_string(s) + " has the limiter flag (smst_batch_set_pcm_limiter): smst_batch_exact_pcm only");
 }
 int smst_batch_process_pcm(smst_batch *b, const void *in, long long iss, long long ifs, const int *inSamples,
                            void *out, long long oss, long long ofs, const int *outSamples, int format, int memory) {
@@ -1155,7 +1200,7 @@ int smst_debug_clip_true_peak(int device, int streams, int channels, const int *
 		for (int k = 0; k < 2; ++k) if (g[4*k + 2] > 0 && !g[4*k + 3]) end = std::max(end, g[4*k] + g[4*k + 2]);
 		most = std::max(most, g[2] + g[6]);
 		mostSegment = std::max(mostSegment, std::max(g[2], g[6]));
-		level[s] = smst::PcmLevel{smst::kPcmLevelFixed, 1.0f, 1.0f, (!flags || flags[s]) ? 1u : 0u};
+		level[s] = smst::PcmLevel{smst::kPcmLevelFixed, 1.0f, 1.0f, (!flags || flags[s]) ? smst::kPcmFlagTruePeak : 0u};
 	}
 	hip(hipSetDevice(device));
 	const size_t imageBytes = end ? size_t((streams - 1)*imageSS + (channels - 1)*imageCS + end)*sizeof(float) : 0;
@@ -1179,6 +1224,72 @@ int smst_debug_clip_true_peak(int device, int streams, int channels, const int *
 	if (samplePeaks) hip(hipMemcpy(samplePeaks, dWords + streams, (size_t)streams*sizeof(float), hipMemcpyDeviceToHost));
 	return SMST_OK;
 	SMST_CATCH
+}
+// the limiter's two passes alone: see include/smst.h
+int smst_debug_clip_limit(int device, int streams, int channels, const int *segments, const float *image, long long imageSS, long long imageCS,
+                          const float *gains, const float *ceilings, const int *flags, int lookahead, float *need, float *r, int maxFrames,
+                          float *minGain, long long *limitedFrames) {
+	SMST_TRY
+	if (streams < 1 || channels < 1 || channels > smst::kMaxChannels || !segments || !image || imageSS < 0 || imageCS < 0 || !gains || !ceilings || !flags || maxFrames < 0)
+		throw smst::Error("clip limit: bad arguments");
+	if (lookahead < 1 || lookahead > smst::kLimitMaxLookahead) throw smst::Error("clip limit: the lookahead is outside 1 ... " + std::to_string(smst::kLimitMaxLookahead) + " frames");
+	auto hip = [&](hipError_t err) { if (err != hipSuccess) throw smst::Error(std::string("clip limit: ") + hipGetErrorString(err), true); };
+	std::vector<smst::PcmLevel> level((size_t)streams);
+	int end = 0, most = 0;
+	for (int s = 0; s < streams; ++s) {
+		const int *g = segments + 8*s;
+		if (g[0] < 0 || g[2] < 0 || g[4] < 0 || g[6] < 0) throw smst::Error("clip limit: negative segment offset or count");
+		if ((long long)g[2] + g[6] > maxFrames) throw smst::Error("clip limit: a clip is longer than maxFrames");
+		if (!(ceilings[s] > 0)) throw smst::Error("clip limit: a ceiling is not above 0");
+		for (int k = 0; k < 2; ++k) if (g[4*k + 2] > 0 && !g[4*k + 3]) end = std::max(end, g[4*k] + g[4*k + 2]);
+		level[s] = smst::PcmLevel{smst::kPcmLevelProtect, gains[s], ceilings[s], unsigned(flags[s]) & (smst::kPcmFlagTruePeak | smst::kPcmFlagLimiter)};
+		if (smst::pcmLimited(level[s]) && !g[3] && !g[7]) most = std::max(most, g[2] + g[6]);
+	}
+	hip(hipSetDevice(device));
+	const size_t imageBytes = end ? size_t((streams - 1)*imageSS + (channels - 1)*imageCS + end)*sizeof(float) : 0;
+	const size_t pitch = size_t(std::max(maxFrames, 1) + 3)/4*4, rows = (size_t)streams*pitch;
+	Buffer<unsigned char, false> dImage, dSegs, dLevel;
+	Buffer<float, false> dRows, dWin; // [2][streams][pitch]: need, r -- 1.0 where the passes write nothing
+	Buffer<int, false> dMeters;       // [2][streams]
+	dImage.allocate(imageBytes + 32, "clip limit");
+	dSegs.allocate((size_t)2*streams*sizeof(smst::ClipSeg), "clip limit");
+	dLevel.allocate(level.size()*sizeof(smst::PcmLevel), "clip limit");
+	dRows.allocate(2*rows, "clip limit");
+	dWin.allocate((size_t)2*lookahead + 1, "clip limit");
+	dMeters.allocate((size_t)2*streams, "clip limit");
+	unsigned char *i0 = dImage + reinterpret_cast<uintptr_t>(image)%16; // (as far behind a 16-byte boundary as the caller's image)
+	if (imageBytes) hip(hipMemcpy(i0, image, imageBytes, hipMemcpyHostToDevice));
+	hip(hipMemcpy(dSegs, segments, (size_t)2*streams*sizeof(smst::ClipSeg), hipMemcpyHostToDevice));
+	hip(hipMemcpy(dLevel, level.data(), level.size()*sizeof(smst::PcmLevel), hipMemcpyHostToDevice));
+	std::vector<float> ones(2*rows, 1.0f), win((size_t)2*lookahead + 1);
+	smst::limitWindow(lookahead, win.data());
+	hip(hipMemcpy(dRows, ones.data(), ones.size()*sizeof(float), hipMemcpyHostToDevice));
+	hip(hipMemcpy(dWin, win.data(), win.size()*sizeof(float), hipMemcpyHostToDevice));
+	hip(hipMemset(dMeters, 0, (size_t)2*streams*sizeof(int)));
+	smst::PcmLevelIo io;
+	io.table = reinterpret_cast<const smst::PcmLevel *>(dLevel.p);
+	smst::launchClipLimit(reinterpret_cast<const float *>(i0), imageSS, imageCS, reinterpret_cast<const smst::ClipSeg *>(dSegs.p), streams, channels, most, io, lookahead, dWin,
+	                      dRows, dRows + rows, (long long)pitch, dMeters, nullptr);
+	hip(hipGetLastError());
+	hip(hipStreamSynchronize(nullptr));
+	hip(hipMemcpy(ones.data(), dRows, ones.size()*sizeof(float), hipMemcpyDeviceToHost));
+	std::vector<int> words((size_t)2*streams);
+	hip(hipMemcpy(words.data(), dMeters, words.size()*sizeof(int), hipMemcpyDeviceToHost));
+	for (int s = 0; s < streams; ++s) {
+		if (need) std::copy(ones.begin() + (size_t)s*pitch, ones.begin() + (size_t)s*pitch + maxFrames, need + (size_t)s*maxFrames);
+		if (r) std::copy(ones.begin() + rows + (size_t)s*pitch, ones.begin() + rows + (size_t)s*pitch + maxFrames, r + (size_t)s*maxFrames);
+		const int bits = 0x3f800000 - words[s];
+		if (minGain) std::memcpy(minGain + s, &bits, sizeof(float));
+		if (limitedFrames) limitedFrames[s] = words[(size_t)streams + s];
+	}
+	return SMST_OK;
+	SMST_CATCH
+}
+int smst_debug_limiter_window(int lookahead, float *out) {
+	if (!out) return fail("limiter window: null pointer");
+	if (lookahead < 1 || lookahead > smst::kLimitMaxLookahead) return fail("limiter window: the lookahead is outside 1 ... 1024 frames");
+	smst::limitWindow(lookahead, out);
+	return SMST_OK;
 }
 int smst_debug_true_peak_taps(float *out) {
 	if (!out) return fail("true peak taps: null pointer");

@@ -5,7 +5,8 @@
 // segments (ClipSeg, smst_device.h) of `count` frames from frame `src` of the source to frame `dst` of the destination.
 //   kClipIn<T>   the caller's frames of format T -> the input image            (pcmTileIn of smst_pcm.h on a run that begins at the segment)
 //   kClipOut<T, Dith, Level>  the output image -> the caller's frames, overs counted  (pcmTileOut; a "zeros" segment has no source; Dith: dithered;
-//                Level: every stream's gain applied -- a whole-clip gain formed from the clip's peak --, its peak metered)
+//                Level: every stream's gain applied -- a whole-clip gain formed from the clip's peak --, its peak metered; a fourth flag,
+//                Limit: a limited stream's frames multiplied by the gain curve of smst_limiter.h as well)
 //   kClipPeak    the output image -> the peak of every stream's clip           (in front of a kClipOut that forms a whole-clip gain)
 //   kClipPlanar  planar fp32 -> planar fp32, either direction                  (the caller's buffer is planar itself)
 // Included by smst_state.hip only, behind smst_pcm.h: the conversion rule, the tiling of a run and the overs scheme are the ones defined there.
@@ -43,13 +44,16 @@ template <typename T> __global__ __launch_bounds__(256) void kClipIn(const T *__
 // agree on it without another launch; the workgroup of the first tile of the stream's first segment that has a source reports it in
 // level.applied[s]; a run of zeros is not levelled, metered or reported
 // loudGain: gL of a stream in the loudness mode (kLoudGate's, smst_loudness.h), which takes the place of the entry's gain
-__device__ inline float clipGain(const PcmLevel &l, int peakBits, float loudGain) {
+// limited: the stream goes through the limiter (smst_limiter.h), which meets the ceiling frame by frame -- the form without the quotient
+__device__ inline float clipGain(const PcmLevel &l, int peakBits, float loudGain, bool limited = false) {
 	const float gain = l.mode == kPcmLevelLoudness ? loudGain : l.gain;
-	if (l.mode == kPcmLevelFixed || peakBits <= 0 || peakBits >= 0x7f800000) return gain; // (no peak, or none to divide by: the plain gain)
+	if (limited || l.mode == kPcmLevelFixed || peakBits <= 0 || peakBits >= 0x7f800000) return gain; // (no peak, or none to divide by: the plain gain)
 	const float q = l.ceiling/__int_as_float(peakBits);
 	return (l.mode == kPcmLevelNormalise || !(gain <= q)) ? q : gain;
 }
-template <typename T, bool Dith, bool Level> __global__ __launch_bounds__(256) void kClipOut(const float *__restrict__ image, long long imageStreamStride, long long imageChannelStride,
+// Limit (a levelled launch in which a stream is limited): such a stream's gain is the limited form's and every frame is multiplied by
+// level.limit[s*limitPitch + its clip position] as well -- the segment's dst is the position of its first frame; the other streams as Level
+template <typename T, bool Dith, bool Level, bool Limit = false> __global__ __launch_bounds__(256) void kClipOut(const float *__restrict__ image, long long imageStreamStride, long long imageChannelStride,
 		T *__restrict__ out, long long outStreamStride, long long outFrameStride, const ClipSeg *__restrict__ segs, int C, unsigned *__restrict__ overs, const PcmDither *__restrict__ dither,
 		PcmLevelIo level) {
 	extern __shared__ __attribute__((aligned(16))) unsigned char smemRaw[];
@@ -62,10 +66,12 @@ template <typename T, bool Dith, bool Level> __global__ __launch_bounds__(256) v
 	unsigned over;
 	if constexpr (Level) {
 		const PcmLevel l = level.table[s];
-		const int *clipPeak = l.truePeak && level.truePeak ? level.truePeak : level.clipPeak; // (a flagged stream: its true peak, kClipTruePeak's)
-		const float gain = clipGain(l, l.mode == kPcmLevelFixed ? 0 : clipPeak[s], l.mode == kPcmLevelLoudness && level.loudGain ? level.loudGain[s] : 1.0f);
+		const int *clipPeak = (l.flags & kPcmFlagTruePeak) && level.truePeak ? level.truePeak : level.clipPeak; // (a flagged stream: its true peak, kClipTruePeak's)
+		const bool limited = Limit && level.limit && pcmLimited(l);
+		const float gain = clipGain(l, l.mode == kPcmLevelFixed ? 0 : clipPeak[s], l.mode == kPcmLevelLoudness && level.loudGain ? level.loudGain[s] : 1.0f, limited);
+		const float *r = limited ? level.limit + (size_t)s*level.limitPitch + g.dst : nullptr;
 		unsigned peak;
-		if (!pcmTileOut<T, Dith, true>(src, imageChannelStride, out + (size_t)s*outStreamStride + (size_t)g.dst*outFrameStride, outFrameStride, g.count, blockIdx.x, C, reinterpret_cast<float *>(smemRaw), over, dp, gain, &peak)) return;
+		if (!pcmTileOut<T, Dith, true, Limit>(src, imageChannelStride, out + (size_t)s*outStreamStride + (size_t)g.dst*outFrameStride, outFrameStride, g.count, blockIdx.x, C, reinterpret_cast<float *>(smemRaw), over, dp, gain, &peak, r)) return;
 		if (src) {
 			const ClipSeg first = segs[2*s];
 			const bool reports = blockIdx.z == 0 || first.count < 1 || first.zeros; // (segment 1 reports where segment 0 has no source)
@@ -192,7 +198,10 @@ void launchClipOut(int format, const float *image, long long imageSS, long long 
 		typedef typename decltype(tag)::type T;
 		constexpr bool Dith = decltype(dithered)::value;
 		const size_t lds = Dith ? pcmDitherLdsBytes(C) : pcmLdsBytes(C);
-		if (level.table) {
+		if (level.table && level.limit) {
+			hipLaunchKernelGGL((kClipOut<T, Dith, true, true>), grid, dim3(256), lds, st, image, imageSS, imageCS, static_cast<T *>(out), outSS, outInner, segs, C, overs, dither, level);
+			countLaunch(LK_CLIP_OUT_LIMITED);
+		} else if (level.table) {
 			hipLaunchKernelGGL((kClipOut<T, Dith, true>), grid, dim3(256), lds, st, image, imageSS, imageCS, static_cast<T *>(out), outSS, outInner, segs, C, overs, dither, level);
 			countLaunch(LK_CLIP_OUT_LEVELLED);
 		} else {

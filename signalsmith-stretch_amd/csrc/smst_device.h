@@ -169,7 +169,7 @@ __host__ __device__ inline bool analysisWindowInCall(int B, int M, int I, int in
 // form" tests assert through these that BOTH forms really ran.
 enum LaunchKind {
 	LK_VOC_ALIGNED, LK_VOC_TWISTED, LK_VOC_INTERIOR, LK_VOC_STAGED, LK_VOC_GATHER, LK_VOC_N, LK_VOC_ONE, LK_VOC_ACROSS, LK_VOC_CONT, LK_CHAIN_UNFUSED,
-	LK_ANALYSE_TEAMS, LK_ANALYSE_PAIRS, LK_ANALYSE_TWIST, LK_TWIST_ROWS, LK_ANALYSE_FAST, LK_ANALYSE_GENERIC, LK_SYNTH_TEAMS, LK_SYNTH_FAST, LK_SYNTH_GENERIC, LK_SYNTH_EMIT, LK_EMIT_CARRIED, LK_FEED_ONE_PASS, LK_PCM_IN, LK_PCM_OUT, LK_CLIP_IN, LK_CLIP_OUT, LK_PCM_OUT_DITHERED, LK_CLIP_OUT_DITHERED, LK_PCM_OUT_LEVELLED, LK_CLIP_OUT_LEVELLED, LK_CLIP_PEAK, LK_CLIP_LOUDNESS, LK_CLIP_TRUE_PEAK, LK_COUNT
+	LK_ANALYSE_TEAMS, LK_ANALYSE_PAIRS, LK_ANALYSE_TWIST, LK_TWIST_ROWS, LK_ANALYSE_FAST, LK_ANALYSE_GENERIC, LK_SYNTH_TEAMS, LK_SYNTH_FAST, LK_SYNTH_GENERIC, LK_SYNTH_EMIT, LK_EMIT_CARRIED, LK_FEED_ONE_PASS, LK_PCM_IN, LK_PCM_OUT, LK_CLIP_IN, LK_CLIP_OUT, LK_PCM_OUT_DITHERED, LK_CLIP_OUT_DITHERED, LK_PCM_OUT_LEVELLED, LK_CLIP_OUT_LEVELLED, LK_CLIP_PEAK, LK_CLIP_LOUDNESS, LK_CLIP_TRUE_PEAK, LK_CLIP_LIMIT_NEED, LK_CLIP_LIMIT_GAIN, LK_CLIP_OUT_LIMITED, LK_COUNT
 };
 long long launchCount(const char *name); // -1: unknown name
 
@@ -231,13 +231,18 @@ inline unsigned pcmDitherHash(long long seed) {
 // rule above runs on w, peaks[s] (the bits of a non-negative float, which order as ints) takes the largest |v| the launch met in stream s,
 // NaN skipped, and applied[s] the gain g it used.  kPcmOut knows the fixed gain only; kClipOut derives a whole-clip gain from clipPeak[s],
 // the peak of the stream's clip that kClipPeak left there.  table == null: the unlevelled kernels, as before; nothing else is read.
-// truePeak != 0: the stream's true-peak flag (include/smst.h, "True peak") -- kClipTruePeak measures the stream, and kClipOut forms its
-// whole-clip gain from truePeak[s] of the PcmLevelIo, which that pass left there, in the place of clipPeak[s]
-struct PcmLevel { unsigned mode; float gain, ceiling; unsigned truePeak; };
+// flags, a bit set.  kPcmFlagTruePeak: the stream's true-peak flag (include/smst.h, "True peak") -- kClipTruePeak measures the stream, and
+// kClipOut forms its whole-clip gain from truePeak[s] of the PcmLevelIo, which that pass left there, in the place of clipPeak[s].
+// kPcmFlagLimiter: the stream's limiter flag (include/smst.h, "Limiter"), which acts in the PROTECT and LOUDNESS modes only (pcmLimited):
+// the whole-clip gain is formed without the ceiling's quotient, and kClipOut multiplies every frame by its r of PcmLevelIo::limit as well
+struct PcmLevel { unsigned mode; float gain, ceiling; unsigned flags; };
+constexpr unsigned kPcmFlagTruePeak = 1u, kPcmFlagLimiter = 2u;
 // kClipOut takes the loudness mode's gain gL from loudGain[s], which kLoudGate (smst_loudness.h) left there, and limits it by ceiling/peak.
 constexpr unsigned kPcmLevelFixed = 0u, kPcmLevelProtect = 1u, kPcmLevelNormalise = 2u, kPcmLevelLoudness = 3u;
 struct PcmLevelIo { const PcmLevel *table = nullptr; int *peaks = nullptr; float *applied = nullptr; int *clipPeak = nullptr; const float *loudGain = nullptr;
-	const int *truePeak = nullptr; }; // (null: no stream of the call was measured -- every stream's gain comes from its clip peak)
+	const int *truePeak = nullptr;   // (null: no stream of the call was measured -- every stream's gain comes from its clip peak)
+	const float *limit = nullptr; long long limitPitch = 0; }; // r of the limited streams, [S][limitPitch] in clip order (null: no stream of the call is limited)
+inline __host__ __device__ bool pcmLimited(const PcmLevel &l) { return (l.flags & kPcmFlagLimiter) && (l.mode == kPcmLevelProtect || l.mode == kPcmLevelLoudness); }
 void launchPcmOut(int format, const float *in, long long inStreamStride, long long inChannelStride, void *out, long long outStreamStride, long long outFrameStride,
                   const int *counts, int S, int C, int maxFrames, unsigned *overs, hipStream_t st, const PcmDither *dither = nullptr, const PcmLevelIo &level = PcmLevelIo());
 // Whole clips of ragged lengths (smst_clip.h; Batch::exact): each stream moves two segments of frames between the caller's buffer and a planar
@@ -292,5 +297,17 @@ struct TruePeakTable { float c[3][kTruePeakTaps]; };                       // ph
 const TruePeakTable &truePeakTable();
 void launchClipTruePeak(const float *image, long long imageStreamStride, long long imageChannelStride, const ClipSeg *segs, int S, int C, int maxFrames,
                         const PcmLevel *level, int *truePeak, hipStream_t st);
+// Lookahead limiter of whole clips (include/smst.h, "Limiter", has the definition; smst_limiter.h the kernels), for the streams that
+// pcmLimited() names.  Two passes on `st`, over the image and the segments of the passes above:
+//   need   per frame, in clip order: all channels folded into need(n) = ceiling/(m(n)*g) where that is below 1   -> need[s*pitch + n]
+//   gain   hold (the minimum of need over 2H + 1 frames), smoothed by the window of 2H + 1 floats, min'ed with need -> r[s*pitch + n],
+//          and the stream's two meter words: meters[s] = max of bits(1.0f) - bits(r), meters[S + s] = frames with r < 1 (zeroed by the caller)
+// level: the call's view (table, and loudGain where a stream is in the loudness mode).  maxFrames: the longest limited clip, <= pitch (sizes
+// the grids; nothing is launched for 0).  H: the lookahead in frames, 1 ... kLimitMaxLookahead; window: device, limitWindow()'s floats
+constexpr int kLimitTile = kTruePeakTile;       // frames of a clip, in clip order, that one workgroup of either pass takes
+constexpr int kLimitMaxLookahead = 1024, kLimitDefaultLookahead = 72;
+void limitWindow(int H, float *win);            // win[k + H] = float32(h_k/sum h), k = -H ... H: in double, one rounding
+void launchClipLimit(const float *image, long long imageStreamStride, long long imageChannelStride, const ClipSeg *segs, int S, int C, int maxFrames,
+                     const PcmLevelIo &level, int H, const float *window, float *need, float *r, long long pitch, int *meters, hipStream_t st);
 
 } // namespace smst

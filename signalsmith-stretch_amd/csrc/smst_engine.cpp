@@ -1861,6 +1861,21 @@ void Batch::exact(const ClipIo &io, const int *inSamples, const int *outSamples,
 		launchClipTruePeak(dClipOut, outImgSS, pitchOut, cs.dev + (size_t)2*S, S, C, truePeakMost, io.pcm.level.table, words, st);
 		level.truePeak = words;
 	}
+	int limitMost = 0;
+	if (io.pcm.level.table && io.limiter && !direct) for (int s = 0; s < S; ++s) if (run[s] && io.limiter[s]) limitMost = std::max(limitMost, outSamples[s]);
+	if (limitMost > 0) { // the limited clips' gain curves, from the same image: what kClipOut multiplies those streams' frames by
+		if (!dLimitWin) throw Error("exact: a limited stream, but the limiter's window has not been prepared");
+		const size_t head = (size_t)(2*S + 3)/4*4; // (the meters; need and r begin on 16-byte boundaries)
+		const long long pitch = up4(limitMost);
+		const size_t rows = (size_t)S*(size_t)pitch;
+		growScratch(dLimit, limitCapacity, head + 2*rows, rows/4 + 1024, true);
+		int *meters = reinterpret_cast<int *>(dLimit);
+		float *need = dLimit + head, *r = need + rows;
+		SMST_HIP(hipMemsetAsync(meters, 0, (size_t)2*S*sizeof(int), st));
+		launchClipLimit(dClipOut, outImgSS, pitchOut, cs.dev + (size_t)2*S, S, C, limitMost, level, limitH, dLimitWin, need, r, pitch, meters, st);
+		level.limit = r;
+		level.limitPitch = pitch;
+	}
 	launchClipOut(io.format, dClipOut, outImgSS, pitchOut, io.out, io.outStreamStride, io.outInnerStride, cs.dev + (size_t)2*S, S, C,
 	              std::max(std::max(direct ? 0 : maxProc, maxFlush), maxZeros), io.pcm.overs, st, io.pcm.dither, level);
 	clipSets.end(st);
@@ -1883,6 +1898,38 @@ bool Batch::readTruePeaks(float *truePeaks) {
 	SMST_HIP(hipSetDevice(dev));
 	SMST_HIP(hipStreamSynchronize(st));
 	SMST_HIP(hipMemcpy(truePeaks, dTruePeak, (size_t)S*sizeof(float), hipMemcpyDeviceToHost));
+	return true;
+}
+
+void Batch::setLimiterLookahead(int frames) {
+	if (frames < 1 || frames > kLimitMaxLookahead) throw Error("limiter: the lookahead is outside 1 ... " + std::to_string(kLimitMaxLookahead) + " frames");
+	limitH = frames;
+	if (dLimitWin) prepareLimiter();
+}
+
+void Batch::prepareLimiter() {
+	SMST_HIP(hipSetDevice(dev));
+	if (!dLimitWin) {
+		dLimitWin = devAlloc<float>((size_t)2*kLimitMaxLookahead + 1);
+		wsBytes += ((size_t)2*kLimitMaxLookahead + 1)*sizeof(float);
+	}
+	std::vector<float> win((size_t)2*limitH + 1);
+	limitWindow(limitH, win.data());
+	SMST_HIP(hipStreamSynchronize(st)); // (a call in flight reads the window it was issued with)
+	SMST_HIP(hipMemcpy(dLimitWin, win.data(), win.size()*sizeof(float), hipMemcpyHostToDevice));
+}
+
+bool Batch::readLimiter(float *minGain, long long *limitedFrames) {
+	if (!dLimit) return false;
+	SMST_HIP(hipSetDevice(dev));
+	SMST_HIP(hipStreamSynchronize(st));
+	std::vector<int> words((size_t)2*S);
+	SMST_HIP(hipMemcpy(words.data(), dLimit, words.size()*sizeof(int), hipMemcpyDeviceToHost));
+	for (int s = 0; s < S; ++s) {
+		const int bits = 0x3f800000 - words[s];
+		std::memcpy(minGain + s, &bits, sizeof(float));
+		limitedFrames[s] = words[(size_t)S + s];
+	}
 	return true;
 }
 

@@ -115,7 +115,17 @@ public:
 	// no stream has the true-peak flag): the streams that have it -- if one of them runs, kClipTruePeak (smst_true_peak.h) does, and kClipOut
 	// forms those streams' whole-clip gains from the words it leaves in the engine's memory
 	struct ClipIo { const void *in; long long inStreamStride, inInnerStride; void *out; long long outStreamStride, outInnerStride; int format;
-		PcmOutCall pcm; const unsigned char *wholeClip = nullptr; const int *loudHop = nullptr; const unsigned char *truePeak = nullptr; };
+		PcmOutCall pcm; const unsigned char *wholeClip = nullptr; const int *loudHop = nullptr; const unsigned char *truePeak = nullptr;
+		const unsigned char *limiter = nullptr; }; // (host, [S]; null where no stream is limited: the streams whose level entry pcmLimited() names -- if one
+		                                           // of them runs, the two passes of smst_limiter.h do, and kClipOut takes their r from the engine's scratch)
+	// The limiter's lookahead H in frames (include/smst.h, "Limiter"), 1 ... kLimitMaxLookahead, the batch's one.  prepareLimiter() puts the
+	// window of the current H into device memory (the first call allocates it); setLimiterLookahead() does so again where it is there already.
+	// Neither runs in an exact call.  readLimiter: the meters of the newest exact call that limited, [S] each (1 and 0: a stream it did not
+	// limit); false: none has.  Synchronises
+	void setLimiterLookahead(int frames);
+	int limiterLookahead() const { return limitH; }
+	void prepareLimiter();
+	bool readLimiter(float *minGain, long long *limitedFrames);
 	// the true peaks of the newest exact call that measured, [S] (0: a stream it did not measure); false: none has.  Synchronises
 	bool readTruePeaks(float *truePeaks);
 	// the loudness meters of the newest exact call that measured, [S] and [S][2] (blocks past the absolute gate, past both); false: none has.  Synchronises
@@ -307,6 +317,11 @@ private:
 	size_t loudCapacity = 0;
 	float *dTruePeak = nullptr; // the true-peak words of the newest exact call that measured ([S] float bits), allocated by the first one
 	size_t truePeakCapacity = 0;
+	// the limiter: the meters of the newest exact call that limited ([2][S] ints) in front of need and r ([S][pitch] floats each), grown on
+	// demand as the images are; the window of 2*kLimitMaxLookahead + 1 floats, allocated by the first prepareLimiter()
+	float *dLimit = nullptr, *dLimitWin = nullptr;
+	size_t limitCapacity = 0;
+	int limitH = kLimitDefaultLookahead;
 	struct ClipSet { ClipSeg *host, *dev; }; // [2][S][2]: input segments, output segments
 	TwoSets<ClipSet> clipSets;
 	// a device scratch that holds `need` floats, allocated with `room` more; true: it was replaced (the old one freed behind a synchronise).  workspace: counted in workspaceBytes()

@@ -301,8 +301,10 @@ __device__ inline void pcmMaxPeak(int *__restrict__ peaks, int s, unsigned peak)
 // DITHERED value was -- and that the 16 key words behind the image are filled; nothing else.
 // Level ("Level" of include/smst.h): the quantiser takes w = v*g -- one fp32 multiply of its own -- in place of v, and `peak` has the largest
 // |v| of this lane's elements as its bits, NaN skipped; a run of zeros is not multiplied (0*inf would be a NaN).  Nothing else.
-template <typename T, bool Dith, bool Level = false> __device__ inline bool pcmTileOut(const float *__restrict__ in, long long inChannelStride, T *__restrict__ run, long long outFrameStride, long long frames,
-		int t, int C, float *tile, unsigned &over, PcmDither dp, float gain = 1.0f, unsigned *peak = nullptr) {
+// Limit ("Limiter" of include/smst.h; the levelled form only): where `limit` is set -- r of the run's first frame, one float per frame --
+// the quantiser takes u = w*r, one more fp32 multiply of its own; a stream whose `limit` is null gets the levelled form's bytes.
+template <typename T, bool Dith, bool Level = false, bool Limit = false> __device__ inline bool pcmTileOut(const float *__restrict__ in, long long inChannelStride, T *__restrict__ run, long long outFrameStride, long long frames,
+		int t, int C, float *tile, unsigned &over, PcmDither dp, float gain = 1.0f, unsigned *peak = nullptr, const float *__restrict__ limit = nullptr) {
 	typedef PcmFormat<T> F;
 	const int tid = threadIdx.x;
 	long long e0;
@@ -336,6 +338,12 @@ template <typename T, bool Dith, bool Level = false> __device__ inline bool pcmT
 			// (v_fma_mixlo_f16, which rounds the exact product once); an empty statement that "reads and writes" w keeps it a value of its own
 			if constexpr (std::is_same<T, PcmF16>::value) asm("" : "+v"(v));
 #endif
+			if constexpr (Limit) if (limit && src) {
+				v = __fmul_rn(v, limit[f0 + at.frame]);
+#if defined(__HIP_DEVICE_COMPILE__)
+				if constexpr (std::is_same<T, PcmF16>::value) asm("" : "+v"(v));
+#endif
+			}
 		}
 		if constexpr (Dith) return mode ? v*F::kScale + pcmDitherValue(mode, keys[at.c], n0 + at.frame) : v*F::kScale;
 		else return F::scaled(v);

@@ -31,46 +31,44 @@ static_assert(kTruePeakTile%(256*kTruePeakRun) == 0 && kTruePeakLds%4 == 0, "a t
 static_assert(kTruePeakLead + kTruePeakTrail + 1 == kTruePeakTaps, "the taps of a frame reach 5 frames back and 6 ahead");
 inline size_t truePeakLdsBytes() { return size_t(kTruePeakLds)*sizeof(float) + 4*sizeof(int); }
 
-// The largest bit pattern among the first `valid` of the F frames whose window begins at `at`: frame i is at[i + 5], its taps reach at[i ... i + 11]
-template <int F> __device__ inline unsigned truePeakFrames(const float *at, int valid, const TruePeakTable &taps) {
+// Per frame, the largest bit pattern of the sample and its three phases: m[i] of the F frames whose window begins at `at` -- frame i is
+// at[i + 5], its taps reach at[i ... i + 11].  (The per-frame form: the limiter's detector, smst_limiter.h, keeps every frame's word.)
+template <int F> __device__ inline void truePeakFrameBits(const float *at, const TruePeakTable &taps, unsigned (&m)[F]) {
 	double w[F + kTruePeakHalo];
 #pragma unroll
 	for (int i = 0; i < F + kTruePeakHalo; ++i) w[i] = double(at[i]);
-	unsigned most = 0u;
 #pragma unroll
-	for (int i = 0; i < F; ++i) { // (unrolled: w[] stays in registers.  A frame behind the clip's end is formed from the image's zeros and dropped)
-		unsigned m = pcmPeakBits(at[i + kTruePeakLead]);
+	for (int i = 0; i < F; ++i) { // (unrolled: w[] stays in registers)
+		unsigned most = pcmPeakBits(at[i + kTruePeakLead]);
 #pragma unroll
 		for (int p = 0; p < 3; ++p) {
 			double y = 0.0;
 #pragma unroll
 			for (int j = 0; j < kTruePeakTaps; ++j) y += double(taps.c[p][j])*w[i + j];
-			m = max(m, pcmPeakBits(float(y)));
+			most = max(most, pcmPeakBits(float(y)));
 		}
-		if (i < valid) most = max(most, m);
+		m[i] = most;
 	}
+}
+// The largest of them among the first `valid` frames (a frame behind the clip's end is formed from the image's zeros and dropped)
+template <int F> __device__ inline unsigned truePeakFrames(const float *at, int valid, const TruePeakTable &taps) {
+	unsigned m[F], most = 0u;
+	truePeakFrameBits<F>(at, taps, m);
+#pragma unroll
+	for (int i = 0; i < F; ++i) if (i < valid) most = max(most, m[i]);
 	return most;
 }
 
-// grid (tiles of kTruePeakTile frames in clip order, C, S), 256 threads.  level[s].truePeak == 0, a run of zeros, nothing to measure: returns at once
-__global__ __launch_bounds__(256) void kClipTruePeak(const float *__restrict__ image, long long imageStreamStride, long long imageChannelStride, const ClipSeg *__restrict__ segs,
-		const PcmLevel *__restrict__ level, TruePeakTable taps, int *__restrict__ truePeak) {
-	extern __shared__ __attribute__((aligned(16))) unsigned char smemRaw[];
-	float *lds = reinterpret_cast<float *>(smemRaw);       // [kTruePeakLds]
-	int *waveMost = reinterpret_cast<int *>(lds + kTruePeakLds); // [4]
-	const int s = blockIdx.z, c = blockIdx.y, tid = threadIdx.x;
-	if (!level[s].truePeak) return;
-	const ClipSeg g0 = segs[2*s], g1 = segs[2*s + 1];
-	if (g0.zeros || g1.zeros) return;
+// The LDS image of the tile that begins at position t0 of a clip of N = n0 + n1 frames, of the channel whose row of the image is `row`:
+// position t0 - 5 + i at lds[i], i < kTruePeakLds, 0.0 outside [0, N).  Every lane of the workgroup calls it; the caller synchronises.
+__device__ inline void truePeakStage(const float *__restrict__ row, const ClipSeg &g0, const ClipSeg &g1, int t0, float *lds) {
+	const int tid = threadIdx.x;
 	const int n0 = max(g0.count, 0), n1 = max(g1.count, 0), N = n0 + n1;
-	if ((long long)blockIdx.x*kTruePeakTile >= N) return;
-	const int t0 = int(blockIdx.x)*kTruePeakTile;
 	// [a, b): the clip's positions that the image holds, [i0, i1) their places in it; the rest of it is 0.0
 	const int a = max(t0 - kTruePeakLead, 0), b = N - t0 > kTruePeakTile + kTruePeakTrail ? t0 + kTruePeakTile + kTruePeakTrail : N;
 	const int i0 = a - t0 + kTruePeakLead, i1 = b - t0 + kTruePeakLead;
 	for (int i = tid; i < kTruePeakLds; i += 256) if (i < i0 || i >= i1) lds[i] = 0.0f;
 	// the two runs: [a, endA) of segment 0, [startB, b) of segment 1
-	const float *row = image + (size_t)s*imageStreamStride + (size_t)c*imageChannelStride;
 	const int endA = min(b, n0), nA = max(endA - a, 0), startB = max(a, n0), nB = max(b - startB, 0), q = startB - n0;
 	const float *runA = row + (size_t)g0.src + a, *runB = row + (size_t)g1.src + q;
 	const int wordsA = loudWordsOf(runA, nA), wordsB = loudWordsOf(runB, nB);
@@ -78,6 +76,22 @@ __global__ __launch_bounds__(256) void kClipTruePeak(const float *__restrict__ i
 		if (word < wordsA) loudStageWord(runA, nA, word, -a, n0 - a, lds + i0);
 		else loudStageWord(runB, nB, word - wordsA, -q, n1 - q, lds + (startB - t0 + kTruePeakLead));
 	}
+}
+
+// grid (tiles of kTruePeakTile frames in clip order, C, S), 256 threads.  The flag of level[s] off, a run of zeros, nothing to measure: returns at once
+__global__ __launch_bounds__(256) void kClipTruePeak(const float *__restrict__ image, long long imageStreamStride, long long imageChannelStride, const ClipSeg *__restrict__ segs,
+		const PcmLevel *__restrict__ level, TruePeakTable taps, int *__restrict__ truePeak) {
+	extern __shared__ __attribute__((aligned(16))) unsigned char smemRaw[];
+	float *lds = reinterpret_cast<float *>(smemRaw);       // [kTruePeakLds]
+	int *waveMost = reinterpret_cast<int *>(lds + kTruePeakLds); // [4]
+	const int s = blockIdx.z, c = blockIdx.y, tid = threadIdx.x;
+	if (!(level[s].flags & kPcmFlagTruePeak)) return;
+	const ClipSeg g0 = segs[2*s], g1 = segs[2*s + 1];
+	if (g0.zeros || g1.zeros) return;
+	const int N = max(g0.count, 0) + max(g1.count, 0);
+	if ((long long)blockIdx.x*kTruePeakTile >= N) return;
+	const int t0 = int(blockIdx.x)*kTruePeakTile;
+	truePeakStage(image + (size_t)s*imageStreamStride + (size_t)c*imageChannelStride, g0, g1, t0, lds);
 	__syncthreads();
 	const int frames = min(N - t0, kTruePeakTile);
 	unsigned most = 0u;

@@ -14,6 +14,8 @@ the host from its first entry point to the return of smst_batch_synchronize.
                                                   # the four loudness passes (mode normalise alone also runs on a build without them: SMST_LIBRARY)
   python tools/bench_exact.py --mode normalise --true-peak  # NORMALISE without and with the true-peak flag alternating: true_peak - normalise =
                                                   # the true-peak pass
+  python tools/bench_exact.py --mode protect --limit        # PROTECT (at --limit-gain, so that the ceiling bites) without and with the limiter flag
+                                                  # alternating: limit - protect = the limiter's two passes and the limited copy's extra read
 """
 import argparse
 import ctypes as C
@@ -38,6 +40,9 @@ def main():
     ap.add_argument("--mode", choices=["three", "exact", "ragged", "pcm", "fixed", "protect", "level", "normalise"], required=True)
     ap.add_argument("--loudness", action="store_true", help="frame modes: a batch in LEVEL_LOUDNESS (-23 LUFS, ceiling 32766/32768) beside the mode's own")
     ap.add_argument("--true-peak", action="store_true", help="frame modes: a batch with the mode's own level setting and the true-peak flag on every stream beside the mode's own")
+    ap.add_argument("--limit", action="store_true", help="frame modes protect / normalise: a batch with the mode's own level setting and the limiter flag on every stream beside the mode's own")
+    ap.add_argument("--limit-gain", type=float, default=4.0, help="--limit: the PROTECT gain of both batches (+12 dB: most tiles hold frames over the ceiling)")
+    ap.add_argument("--limit-lookahead", type=int, default=72, help="--limit: the lookahead in frames")
     ap.add_argument("--streams", type=int, default=256)
     ap.add_argument("--channels", type=int, default=2)
     ap.add_argument("--seconds", type=float, default=10.0)
@@ -122,15 +127,19 @@ def frames_modes(a, lib, x, nin, nout, batch):
     ip = lambda v: v.ctypes.data_as(C.POINTER(C.c_int))
     runs = {}
     assert not (a.true_peak and a.mode == "level"), "--true-peak goes with one mode"
-    for key in (("pcm", "fixed", "protect") if a.mode == "level" else (a.mode,)) + (("loudness",) if a.loudness else ()) + (("true_peak",) if a.true_peak else ()):
+    assert not (a.limit and a.mode not in ("protect", "normalise")), "--limit goes with --mode protect (or normalise, where the flag is inert)"
+    for key in (("pcm", "fixed", "protect") if a.mode == "level" else (a.mode,)) + (("loudness",) if a.loudness else ()) + (("true_peak",) if a.true_peak else ()) + (("limit",) if a.limit else ()):
         b = batch()
-        name = a.mode if key == "true_peak" else key
+        name = a.mode if key in ("true_peak", "limit") else key
         if key == "true_peak":
             b.set_pcm_true_peak(True)
+        if key == "limit":
+            b.set_pcm_limiter_lookahead(a.limit_lookahead)
+            b.set_pcm_limiter(True)
         if name == "fixed":
             b.set_pcm_level(smst.LEVEL_FIXED, 0.5)
         if name == "protect":
-            b.set_pcm_level(smst.LEVEL_PROTECT, 1.0, 32766.0/32768.0)
+            b.set_pcm_level(smst.LEVEL_PROTECT, a.limit_gain if a.limit else 1.0, 32766.0/32768.0)
         if name == "normalise":
             b.set_pcm_level(smst.LEVEL_NORMALISE, 1.0, 32766.0/32768.0)
         if name == "loudness":
@@ -173,6 +182,13 @@ def frames_modes(a, lib, x, nin, nout, batch):
                                    gain_range=[float(gains.min()), float(gains.max())], image_bytes=int(S)*Cn*int(nout.sum()//S)*4,
                                    launches=smst.launch_count("clip_true_peak", lib))
         result["true_peak"]["minus_%s_ms" % a.mode] = round(result["step_ms"]["true_peak"]["median"] - result["step_ms"][a.mode]["median"], 3)
+    if a.limit:
+        low, count = runs["limit"].take_pcm_limiter()
+        peaks, gains = runs["limit"].take_pcm_peaks()
+        result["limit"] = dict(lookahead=a.limit_lookahead, min_gain_range=[float(low.min()), float(low.max())], limited_frames=[int(count.min()), int(count.max())],
+                               gain_range=[float(gains.min()), float(gains.max())], image_bytes=int(S)*Cn*int(nout.sum()//S)*4,
+                               launches=[smst.launch_count(k, lib) for k in ("clip_limit_need", "clip_limit_gain", "clip_out_limited")])
+        result["limit"]["minus_%s_ms" % a.mode] = round(result["step_ms"]["limit"]["median"] - result["step_ms"][a.mode]["median"], 3)
     print(json.dumps(result))
     for b in runs.values():
         b.close()

@@ -6,6 +6,7 @@
 //   stretch_cli [--semitones=S] [--formant=S] [--formant-comp] [--formant-base=Hz] [--tonality=Hz] [--time=F]
 //               [--split-computation] [--device=N] [--out-format=s16|s24|f32] [--dither=none|tpdf|tpdf-hp] [--dither-seed=N]
 //               [--exact] [--gain=dB] [--protect=dBFS | --normalize=dBFS] [--loudness=LUFS] [--true-peak]
+//               [--limit] [--limit-lookahead=ms]
 //               in.wav out.wav [in2.wav out2.wav ...]
 //
 // --out-format (also "--out-format s24"): the samples of the files written -- 16-bit (the default, as the reference's CLI writes), 24-bit by the
@@ -30,6 +31,12 @@
 // peak is measured on the GPU (a 4x interpolation between the samples; include/smst.h, "True peak") and the ceilings of --protect,
 // --normalize and --loudness are dBTP: the gain comes from the true peak instead of the sample peak.  Alone it only meters.  The line of a
 // file then ends in " true-peak=<%.4f>": the true peak before the gain, in dBTP (-inf for silence).
+// --limit (needs --protect or --loudness; refused with --normalize, which meets its ceiling by construction): the --protect ceiling no
+// longer lowers the gain of the whole file -- the file keeps --gain, or reaches its --loudness target -- and a lookahead limiter on the GPU
+// (include/smst.h, "Limiter") brings down the frames that would exceed it; with --true-peak, the frames whose inter-sample values would.
+// --limit-lookahead=ms (default 1.5) is converted to frames with the batch's sample rate; a short lookahead weakens a dBTP ceiling.  The
+// line of a file then ends in " limit=<%.4f> limited=<frames>": the deepest gain reduction in dB (0 where nothing was limited) and the
+// number of frames that were reduced.
 // Files given together must share sample rate and channel count (they form one batch); lengths may differ.
 #include <algorithm>
 #include <cmath>
@@ -110,6 +117,16 @@ int main(int argc, char **argv) {
 		std::fprintf(stderr, "--true-peak needs --exact (or --protect, --normalize or --loudness, which imply it): whole clips only\n");
 		return 2;
 	}
+	const bool limit = hasFlag(argc, argv, "limit");
+	if (limit && normalize) {
+		std::fprintf(stderr, "--limit and --normalize exclude each other: a normalised file meets its ceiling by construction\n");
+		return 2;
+	}
+	if (limit && !protect && !loudness) {
+		std::fprintf(stderr, "--limit needs --protect=dBFS (its ceiling) or --loudness=LUFS\n");
+		return 2;
+	}
+	const double limitLookaheadMs = flagValue(argc, argv, "limit-lookahead", 1.5);
 	const float gain = fromDecibels(flagValue(argc, argv, "gain", 0)), ceiling = fromDecibels(flagValue(argc, argv, protect ? "protect" : "normalize", 0));
 	std::vector<std::string> files;
 	for (int i = 1; i < argc; ++i) if (std::strncmp(argv[i], "--", 2) && !consumed[i]) files.push_back(argv[i]);
@@ -170,6 +187,10 @@ int main(int argc, char **argv) {
 		if (loudness) CHECK(smst_batch_set_pcm_loudness(batch, -1, flagValue(argc, argv, "loudness", 0), protect ? ceiling : INFINITY, double(inputs[0].sampleRate)));
 		else if (levelled) CHECK(smst_batch_set_pcm_level(batch, -1, protect ? SMST_LEVEL_PROTECT : normalize ? SMST_LEVEL_NORMALISE : SMST_LEVEL_FIXED, gain, ceiling));
 		if (truePeak) CHECK(smst_batch_set_pcm_true_peak(batch, -1, 1));
+		if (limit) {
+			CHECK(smst_batch_set_pcm_limiter_lookahead(batch, int(std::lround(limitLookaheadMs*1e-3*double(inputs[0].sampleRate)))));
+			CHECK(smst_batch_set_pcm_limiter(batch, -1, 1));
+		}
 		// `count` samples of file s from sample `first` on as frames at `frames`; false: one of them is no value of the format
 		auto toFrames = [&](int s, int first, int count, unsigned char *frames) {
 			for (int i = 0; i < count; ++i) for (int c = 0; c < C; ++c) {
@@ -217,11 +238,15 @@ int main(int argc, char **argv) {
 			if (loudness) CHECK(smst_batch_take_pcm_loudness(batch, lufs.data(), nullptr, nullptr));
 			std::vector<float> truePeaks(S, 0.0f);
 			if (truePeak) CHECK(smst_batch_take_pcm_true_peaks(batch, truePeaks.data()));
+			std::vector<float> minGains(S, 1.0f);
+			std::vector<long long> limitedFrames(S, 0);
+			if (limit) CHECK(smst_batch_take_pcm_limiter(batch, minGains.data(), limitedFrames.data()));
 			for (int s = 0; s < S; ++s) {
 				std::printf("level: %s ", files[2*s + 1].c_str());
 				if (loudness) std::printf("loudness=%.4f ", lufs[s]);
 				std::printf("peak=%.9g gain=%.9g overs=%lld", peaks[s], gains[s], clamped[s]);
 				if (truePeak) std::printf(" true-peak=%.4f", 20.0*std::log10(double(truePeaks[s])));
+				if (limit) std::printf(" limit=%.4f limited=%lld", 20.0*std::log10(double(minGains[s])), limitedFrames[s]);
 				std::printf("\n");
 			}
 		}
