@@ -458,7 +458,7 @@ int smst_batch_pcm_dither(const smst_batch *b, int stream, int *mode, long long 
  * per-call table beside the level entries; the passes' scratch and the meters grow with the first call that measures, as the images do, and
  * count in smst_batch_workspace_bytes: a second call of the same shapes allocates nothing, no host synchronisation is added, and the
  * ordering contract of the device-memory call is unchanged.  A batch without a stream in this mode launches none of the passes.
- * Out of scope: momentary and short-term loudness, loudness range, measuring in the streaming or the planar calls.
+ * Out of scope: measuring in the streaming or the planar calls (momentary and short-term loudness and loudness range: "Loudness range").
  * SMST_ERR_INVALID with a message: a target that is not finite; a sample rate that is not finite, <= 0 or gives h < SMST_LOUDNESS_CHUNK; a
  * ceiling <= 0 or NaN (+inf is allowed); a weight that is negative or not finite; a stream index out of range; a null batch. */
 #define SMST_LEVEL_FIXED     0 /* g = gain */
@@ -533,7 +533,7 @@ int smst_debug_clip_loudness(int device, int streams, int channels, const int *s
  * nothing, no host synchronisation is added, and the ordering contract of the device-memory call is unchanged.  The maximum is one of
  * integers and no floating-point atomic is used: a call's result is bit-reproducible whatever the scheduling.
  * Out of scope: true-peak metering in the streaming and the planar calls; an oversampling factor that depends on the rate (4x at
- * every rate); momentary and short-term loudness, loudness range.
+ * every rate).
  * SMST_ERR_INVALID with a message: a stream index out of range, a null batch. */
 #define SMST_TRUE_PEAK_TILE 1024 /* frames of a channel's clip that one workgroup of the true-peak pass measures (kTruePeakTile) */
 /* stream = -1: every stream */
@@ -629,6 +629,84 @@ int smst_debug_clip_limit(int device, int streams, int channels, const int *segm
                           float *need, float *r, int maxFrames, float *minGain, long long *limitedFrames);
 /* test hook: the library's window, out[k + lookahead] = win[k], k = -lookahead ... lookahead */
 int smst_debug_limiter_window(int lookahead, float *out);
+/* ---- Loudness range (EXTENSION; opt-in: a batch that never calls smst_batch_set_pcm_loudness_range or _caps launches the kernels, writes the bytes and counts the launches it did before) ----
+ * A delivery to EBU R 128 reports the loudness range (LRA, EBU Tech 3342) and the maximum momentary and short-term loudness (EBU Tech
+ * 3341) of a clip, and R 128 s1 bounds the maximum short-term loudness of short-form content.  A stream with the meter flag has all three
+ * measured in smst_batch_exact_pcm, from the sums that the loudness passes form; a cap on either maximum lowers the gain of a stream in
+ * SMST_LEVEL_LOUDNESS.
+ *
+ * Definition.  All arithmetic is float64, on the device; logarithms are taken only by the host, when it reports.  "Loudness" supplies,
+ * unchanged: fs and h = round(fs/10); the channel weights w_c; the sub-block sums sub_c[j] = the sum of y_c^2 over [j*h, (j + 1)*h), j <
+ * nSub, where nSub = N/h (integer division) for N >= 4h and 0 otherwise; the block powers z_i, i < nb; the absolute gate G = 10^((-70 +
+ * 0.691)/10).
+ * - Maximum momentary power M: the largest z_i that is not NaN, ungated; 0 when nb = 0; +inf counts.
+ * - Short-term powers: ns = nSub - 29 for nSub >= 30, else 0.  For each channel q_c = sub_c[i] + ... + sub_c[i + 29], summed from 0.0 in
+ *   ascending j; st_i = (sum over c, in channel order, of double(w_c)*q_c)/(30*h).
+ * - Maximum short-term power ST: the largest st_i that is not NaN; 0 when ns = 0.
+ * - Loudness range: absolute gate st_i > G; relative gate st_i > 0.01 * (the mean of the st that passed the absolute gate, its sum taken in
+ *   block order).  n = the number that pass both (a NaN passes neither), v[0..n) those values in ascending order, kLo = ((n - 1)*10 +
+ *   50)/100 and kHi = ((n - 1)*95 + 50)/100 by integer division: the nearest rank of the 10th and the 95th percentile.  The device reports
+ *   lo = v[kLo], hi = v[kHi], n and ns; the host reports LRA = 10*log10(hi/lo) in LU, 0 when n = 0.
+ *   The hop of 100 ms is this library's choice (Tech 3342 asks for at most 1 s); Tech 3342 itself interpolates no percentile either.
+ * Known answers (a float64 restatement of the above, tests/loudness_range_cases.py): a stereo 1-kHz sine in consecutive parts of 20 s, at fs
+ * = 8000 and at fs = 48000 alike --
+ *     -20, -30 dBFS                     LRA 10.0000 LU   n 371   ns 371
+ *     -20, -15                               5.0000         371      371
+ *     -40, -20                              20.0000         371      371
+ *     -50, -35, -20, -35, -50               15.0000         627      971
+ *   (Tech 3342's own conformance signals; its tolerance is +-1 LU).  The maxima of the first read -19.9804 LUFS at 8 kHz and -19.9933 LUFS
+ *   at 48 kHz, momentary and short-term alike.
+ *
+ * The meter flag is a setting of its own beside the stream's level mode, as the true-peak flag is; the first call with on != 0 makes the
+ * batch a levelled one.  In smst_batch_exact_pcm a flagged stream that runs has the four loudness passes run on its output clip WHATEVER its
+ * level mode, and the range stage behind them.  fs: a stream in SMST_LEVEL_LOUDNESS uses that mode's rate; any other stream the rate given
+ * with the meter flag, which is checked by the rule of smst_batch_set_pcm_loudness (h >= SMST_LOUDNESS_CHUNK).  A flagged stream that is not
+ * in the loudness mode gets exactly the gain its mode gives it without the flag, and smst_batch_take_pcm_loudness reports its integrated
+ * loudness and counts too.  Streams without the flag, in the same call, produce the bytes, meters and gains they produce without it.
+ *
+ * Caps (R 128 s1).  Tm, Ts in LUFS, +inf: none.  A cap acts on SMST_LEVEL_LOUDNESS streams only, where a finite cap implies the meter;
+ * elsewhere it is inert, as the limiter flag is in FIXED.  The host forms Pm = 10^((Tm + 0.691)/10) in double, Ps likewise.  The device forms
+ * gm = float32(sqrt(Pm/M)) where the cap is finite and M is finite and above 0 -- division and square root in float64, one rounding --, gs
+ * from Ps and ST in the same way, otherwise no cap, and gL' = min(gL, gm, gs), written over gL.  Everything that reads gL reads gL': the
+ * quotient with the ceiling, the limiter's need and the conversion.  smst_batch_take_pcm_peaks reports the applied gain as before.  A stream
+ * without a finite cap keeps the bits of gL.
+ *
+ * Which calls.  smst_batch_process_pcm and smst_batch_flush_pcm return SMST_ERR_INVALID, before anything runs, if a stream that takes part
+ * has the meter flag or a finite cap: the rule of the whole-clip modes, for the same reason.
+ *
+ * How.  One kernel (csrc/smst_loudness_range.h), one workgroup per stream, behind the four loudness passes and in front of the
+ * true-peak and limiter passes, launched only in a call in which a metered stream runs (launch count "clip_loudness_range"; "clip_loudness"
+ * keeps counting the four passes alone).  The maxima are integer maxima; the two order statistics come from a radix select over the 64-bit
+ * patterns of the gated values -- eight passes of 8 bits, integer histograms, both ranks in the same passes -- which is exact for every n and
+ * reads the values where they lie, so no clip is too long for it.  No floating-point atomic is used: a call's result is bit-reproducible
+ * whatever the scheduling.  The flag and the two cap powers ride in the stream's loudness entry, which now travels when any stream is
+ * measured.  The short-term powers and the meter words grow with the first call that meters and count in smst_batch_workspace_bytes: a
+ * second call of the same shapes allocates nothing, no host synchronisation is added, and the ordering contract of the device-memory call
+ * is unchanged.
+ * Out of scope: metering in the streaming or the planar calls; the time at which a maximum occurs; percentiles other than 10 and 95.
+ * SMST_ERR_INVALID with a message: with on != 0, a sample rate that smst_batch_set_pcm_loudness would refuse; a cap that is NaN or -inf; a
+ * stream index out of range; a null batch. */
+#define SMST_LOUDNESS_RANGE_TILE 256 /* short-term powers that the range stage's workgroup takes at a time (kLoudRangeThreads) */
+/* stream = -1: every stream.  sampleRate is read with on != 0 only */
+int smst_batch_set_pcm_loudness_range(smst_batch *b, int stream, int on, double sampleRate);
+/* the flag, and the rate last given with it (0: none yet); either pointer may be null */
+int smst_batch_pcm_loudness_range(const smst_batch *b, int stream, int *on, double *sampleRate);
+/* stream = -1: every stream; +inf: no cap */
+int smst_batch_set_pcm_loudness_caps(smst_batch *b, int stream, double maxMomentaryLufs, double maxShortTermLufs);
+int smst_batch_pcm_loudness_caps(const smst_batch *b, int stream, double *maxMomentaryLufs, double *maxShortTermLufs);
+/* per stream, of the newest smst_batch_exact_pcm that metered: the two maxima in LUFS (-inf where the power is 0), range[s] = LRA in LU,
+ * low[s] and high[s] = lo and hi in LUFS (-inf where n = 0), shortBlocks[s] = ns, rangeBlocks[s] = n; a stream that call did not meter, and
+ * every stream before any call has metered: -inf, 0 and no blocks.  Any pointer may be null.  Synchronises the batch; resets nothing. */
+int smst_batch_take_pcm_loudness_range(smst_batch *b, double *momentaryMax, double *shortTermMax, double *range,
+                                       double *low, double *high, int *shortBlocks, int *rangeBlocks);
+/* test hook: the four loudness passes and the range stage on a planar fp32 image; arguments as smst_debug_clip_loudness's, every stream
+ * metered.  capsLufs: [streams][2] (momentary, short-term; +inf: none), null: none.  M, ST, lo and hi are reported as POWERS, gains[s] is
+ * gL' of "Caps", shortPowers[s*maxBlocks + i] the first min(ns, maxBlocks) short-term powers.  Any output pointer may be null. */
+int smst_debug_clip_loudness_range(int device, int streams, int channels, const int *segments,
+                                   const float *image, long long imageStreamStride, long long imageChannelStride,
+                                   const double *sampleRates, const float *weights, double targetLufs, const double *capsLufs,
+                                   double *momentaryMax, double *shortTermMax, double *low, double *high, int *shortBlocks, int *rangeBlocks,
+                                   float *gains, double *shortPowers, int maxBlocks);
 /* per stream, since the last take: peaks[s] = the largest |v| the levelled output conversions met BEFORE the gain (0 if none); gains[s] = the
  * gain the newest levelled conversion of stream s applied (1 before any).  Either may be null.  Synchronises the batch; resets the peaks,
  * not the gains. */

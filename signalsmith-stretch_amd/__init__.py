@@ -29,6 +29,7 @@ PCM_S16, PCM_F32, PCM_S24, PCM_S32, PCM_F16 = 1, 2, 4, 5, 6  # frame formats of 
 DITHER_NONE, DITHER_TPDF, DITHER_TPDF_HP = 0, 1, 2           # dither of the int16 / int24 output (StretchBatch.setPcmDither)
 LEVEL_FIXED, LEVEL_PROTECT, LEVEL_NORMALISE = 0, 1, 2        # level of the frame output (StretchBatch.set_pcm_level)
 LEVEL_LOUDNESS = 3                                           # ... to a LUFS target (StretchBatch.set_pcm_loudness)
+LOUDNESS_RANGE_TILE = 256                                    # short-term powers the range stage's workgroup takes at a time (SMST_LOUDNESS_RANGE_TILE)
 LOUDNESS_CHUNK = 256                                         # frames one lane of the loudness passes filters (SMST_LOUDNESS_CHUNK)
 TRUE_PEAK_TILE = 1024                                        # frames one workgroup of the true-peak pass measures (SMST_TRUE_PEAK_TILE)
 LIMITER_TILE, LIMITER_MAX_LOOKAHEAD, LIMITER_DEFAULT_LOOKAHEAD = 1024, 1024, 72  # frames one workgroup of the limiter's passes takes; the lookahead's bound and default (SMST_LIMITER_*)
@@ -153,6 +154,12 @@ _SIGNATURES = {
     "smst_batch_take_pcm_limiter": (C.c_int, [C.c_void_p, _fp, C.POINTER(_ll)]),
     "smst_debug_clip_limit": (C.c_int, [C.c_int, C.c_int, C.c_int, _ip, C.c_void_p, _ll, _ll, _fp, _fp, _ip, C.c_int, _fp, _fp, C.c_int, _fp, C.POINTER(_ll)]),
     "smst_debug_limiter_window": (C.c_int, [C.c_int, _fp]),
+    "smst_batch_set_pcm_loudness_range": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_double]),
+    "smst_batch_pcm_loudness_range": (C.c_int, [C.c_void_p, C.c_int, _ip, _dp]),
+    "smst_batch_set_pcm_loudness_caps": (C.c_int, [C.c_void_p, C.c_int, C.c_double, C.c_double]),
+    "smst_batch_pcm_loudness_caps": (C.c_int, [C.c_void_p, C.c_int, _dp, _dp]),
+    "smst_batch_take_pcm_loudness_range": (C.c_int, [C.c_void_p, _dp, _dp, _dp, _dp, _dp, _ip, _ip]),
+    "smst_debug_clip_loudness_range": (C.c_int, [C.c_int, C.c_int, C.c_int, _ip, C.c_void_p, _ll, _ll, _dp, _fp, C.c_double, _dp, _dp, _dp, _dp, _dp, _ip, _ip, _fp, _dp, C.c_int]),
     "smst_batch_synchronize": (C.c_int, [C.c_void_p]),
     "smst_batch_hip_stream": (C.c_void_p, [C.c_void_p]),
     "smst_batch_enable_profiling": (C.c_int, [C.c_void_p, C.c_int]),
@@ -322,6 +329,28 @@ def debug_clip_loudness(segments, channels, image, image_ss, image_cs, sample_ra
                                              None if w is None else w.ctypes.data_as(_fp), float(target), Z.ctypes.data_as(_dp), blocks.ctypes.data_as(_ip),
                                              gated.ctypes.data_as(_ip), gains.ctypes.data_as(_fp), powers.ctypes.data_as(_dp), max_blocks))
     return Z, blocks, gated, gains, powers[:, :max_blocks]
+
+
+def debug_clip_loudness_range(segments, channels, image, image_ss, image_cs, sample_rates, weights=None, target=-23.0, caps=None, max_blocks=0, device=0, lib=None):
+    """smst_debug_clip_loudness_range on a numpy image (as debug_clip_loudness; caps: [S, 2] in LUFS -- momentary, short-term; inf: none --, None:
+    none) -> (M, ST, lo, hi: powers, float64 [S]; ns, n: int32 [S]; gains float32 [S]; short-term powers float64 [S, max_blocks], NaN behind
+    a stream's last one)"""
+    lib = lib if lib is not None else load_library()
+    seg = np.ascontiguousarray(segments, np.int32)
+    S = seg.shape[0]
+    rates = np.ascontiguousarray(np.broadcast_to(np.asarray(sample_rates, np.float64), (S,)))
+    w = None if weights is None else np.ascontiguousarray(weights, np.float32)
+    assert w is None or w.shape == (channels,)
+    k = None if caps is None else np.ascontiguousarray(caps, np.float64)
+    assert k is None or k.shape == (S, 2)
+    M, ST, lo, hi = (np.full(S, -1.0) for _ in range(4))
+    ns, n, gains = np.full(S, -1, np.int32), np.full(S, -1, np.int32), np.full(S, -1, np.float32)
+    powers = np.full((S, max(max_blocks, 1)), np.nan)
+    _check(lib, lib.smst_debug_clip_loudness_range(device, S, channels, seg.ctypes.data_as(_ip), C.c_void_p(image.ctypes.data), image_ss, image_cs, rates.ctypes.data_as(_dp),
+                                                   None if w is None else w.ctypes.data_as(_fp), float(target), None if k is None else k.ctypes.data_as(_dp),
+                                                   M.ctypes.data_as(_dp), ST.ctypes.data_as(_dp), lo.ctypes.data_as(_dp), hi.ctypes.data_as(_dp), ns.ctypes.data_as(_ip),
+                                                   n.ctypes.data_as(_ip), gains.ctypes.data_as(_fp), powers.ctypes.data_as(_dp), max_blocks))
+    return M, ST, lo, hi, ns, n, gains, powers[:, :max_blocks]
 
 
 def debug_clip_true_peak(segments, channels, image, image_ss, image_cs, flags=None, device=0, lib=None):
@@ -750,6 +779,40 @@ class StretchBatch:
         if w.shape != (self.channels,):
             raise StretchError("one weight per channel")
         _check(self.lib, self.lib.smst_batch_set_pcm_loudness_weights(self.h, w.ctypes.data_as(_fp)))
+
+    def set_pcm_loudness_range(self, on=True, sample_rate=48000.0, stream=-1):
+        """The meter flag (include/smst.h, "Loudness range"), exactFrames only: the stream's maximum momentary and short-term loudness and its
+        loudness range (EBU Tech 3341 / 3342) are measured on the device, whatever its level mode.  sample_rate is the OUTPUT clip's rate, used
+        where the stream is not in LEVEL_LOUDNESS (which has a rate of its own).  stream = -1: every stream."""
+        _check(self.lib, self.lib.smst_batch_set_pcm_loudness_range(self.h, int(stream), 1 if on else 0, float(sample_rate)))
+
+    def pcm_loudness_range(self, stream):
+        """-> (on, sample_rate) of a stream's meter flag"""
+        on, rate = C.c_int(), C.c_double()
+        _check(self.lib, self.lib.smst_batch_pcm_loudness_range(self.h, int(stream), C.byref(on), C.byref(rate)))
+        return bool(on.value), rate.value
+
+    def set_pcm_loudness_caps(self, max_momentary=float("inf"), max_short_term=float("inf"), stream=-1):
+        """Caps in LUFS on the maximum momentary and short-term loudness of a LEVEL_LOUDNESS stream's clip (EBU R 128 s1): the gain is the
+        lowest of the target's and the caps'.  inf: none.  A finite cap implies the meter; outside LEVEL_LOUDNESS a cap is inert."""
+        _check(self.lib, self.lib.smst_batch_set_pcm_loudness_caps(self.h, int(stream), float(max_momentary), float(max_short_term)))
+
+    def pcm_loudness_caps(self, stream):
+        """-> (max_momentary, max_short_term) in LUFS, inf: none"""
+        m, t = C.c_double(), C.c_double()
+        _check(self.lib, self.lib.smst_batch_pcm_loudness_caps(self.h, int(stream), C.byref(m), C.byref(t)))
+        return m.value, t.value
+
+    def take_pcm_loudness_range(self):
+        """-> (momentary_max, short_term_max in LUFS, range in LU, low, high in LUFS: float64 [S]; short_blocks, range_blocks: int32 [S]) of the
+        newest exactFrames that metered (-inf, 0 and no blocks where the stream was not metered).  Synchronises; resets nothing."""
+        S = self.streams
+        m, t, lra, lo, hi = (np.zeros(S, np.float64) for _ in range(5))
+        ns, n = np.zeros(S, np.int32), np.zeros(S, np.int32)
+        _check(self.lib, self.lib.smst_batch_take_pcm_loudness_range(self.h, m.ctypes.data_as(_dp), t.ctypes.data_as(_dp), lra.ctypes.data_as(_dp), lo.ctypes.data_as(_dp),
+                                                                     hi.ctypes.data_as(_dp), ns.ctypes.data_as(_ip), n.ctypes.data_as(_ip)))
+        self._inflight = []
+        return m, t, lra, lo, hi, ns, n
 
     def take_pcm_loudness(self):
         """-> (lufs float64 [S], blocks, gated int32 [S]) of the newest exactFrames that measured: the loudness (-inf where it was undefined or

@@ -85,13 +85,17 @@ struct PcmOutState {
 	std::vector<unsigned char> truePeak;
 	// the limiter flag (smst_batch_set_pcm_limiter): likewise; it acts in SMST_LEVEL_PROTECT and _LOUDNESS only (smst::pcmLimited)
 	std::vector<unsigned char> limiter;
+	// the meter flag (smst_batch_set_pcm_loudness_range): likewise, with the rate -- and the entry made of it -- that a stream outside
+	// SMST_LEVEL_LOUDNESS is measured at; the caps on the two maxima (smst_batch_set_pcm_loudness_caps) in LUFS, +inf: none
+	struct Meter { unsigned char on = 0; double sampleRate = 0; smst::LoudEntry entry{}; double capMomentary = INFINITY, capShortTerm = INFINITY; };
+	std::vector<Meter> meter;
 	bool levelled = false;
 	// overs ([S][2]: clamped, NaN): the kernels add to them, takeOvers() reads and clears them; the meter words (smst::PcmMeters)
 	Buffer<unsigned, false> dOvers;
 	Buffer<int, false> dMeters;
 	std::vector<unsigned> hOvers;
 	std::vector<int> hMeters;
-	std::vector<unsigned char> wholeClip, limited; // clipModes()' arrays
+	std::vector<unsigned char> wholeClip, limited, metered; // clipModes()' arrays
 	std::vector<int> loudHop;
 
 	void create(int streams, int channels) {
@@ -103,6 +107,8 @@ struct PcmOutState {
 		loudWeights.assign((size_t)C, 1.0f);
 		truePeak.assign((size_t)S, 0);
 		limiter.assign((size_t)S, 0);
+		meter.assign((size_t)S, Meter());
+		metered.assign((size_t)S, 0);
 		wholeClip.assign((size_t)S, 0);
 		limited.assign((size_t)S, 0);
 		loudHop.assign((size_t)S, 0);
@@ -161,6 +167,39 @@ struct PcmOutState {
 		forStreams(stream, [&](int s) { limiter[s] = on ? 1 : 0; });
 		if (on) levelled = true;
 	}
+	void setLoudnessRange(int stream, int on, double sampleRate) {
+		Meter m;
+		if (on) {
+			if (!(std::isfinite(sampleRate) && sampleRate > 0)) throw smst::Error("loudness range: the sample rate is not finite or not above 0");
+			if (!smst::loudEntryOf(sampleRate, 0.0, m.entry)) throw smst::Error("loudness range: the sample rate gives a 100-ms step of fewer than " + std::to_string(smst::kLoudChunk) + " samples (or is beyond 1e9)");
+		}
+		forStreams(stream, [&](int s) {
+			meter[s].on = on ? 1 : 0;
+			if (on) { meter[s].sampleRate = sampleRate; meter[s].entry = m.entry; }
+		});
+		if (on) levelled = true;
+	}
+	void setLoudnessCaps(int stream, double maxMomentaryLufs, double maxShortTermLufs) {
+		for (double cap : {maxMomentaryLufs, maxShortTermLufs}) if (std::isnan(cap) || cap == -INFINITY) throw smst::Error("loudness caps: a cap is NaN or -inf (+inf: none)");
+		forStreams(stream, [&](int s) { meter[s].capMomentary = maxMomentaryLufs; meter[s].capShortTerm = maxShortTermLufs; });
+		if (std::isfinite(maxMomentaryLufs) || std::isfinite(maxShortTermLufs)) levelled = true;
+	}
+	bool capped(int s) const { return std::isfinite(meter[s].capMomentary) || std::isfinite(meter[s].capShortTerm); }
+	// The loudness entry a call's table carries for the stream.  A stream in SMST_LEVEL_LOUDNESS is measured at its mode's rate, metered where it
+	// has the flag or a finite cap, and capped; another one is measured at the meter flag's rate where it has the flag -- a cap is inert there
+	smst::LoudEntry loudEntry(int s) const {
+		static const auto power = [](double lufs) { return std::isfinite(lufs) ? std::pow(10.0, (lufs + 0.691)/10) : double(INFINITY); };
+		if (level[s].mode == SMST_LEVEL_LOUDNESS) {
+			smst::LoudEntry e = loud[s].entry;
+			e.meter = meter[s].on || capped(s);
+			e.Pm = power(meter[s].capMomentary); e.Ps = power(meter[s].capShortTerm);
+			return e;
+		}
+		if (!meter[s].on) return smst::LoudEntry{};
+		smst::LoudEntry e = meter[s].entry;
+		e.meter = 1;
+		return e;
+	}
 	unsigned flags(int s) const { return (truePeak[s] ? smst::kPcmFlagTruePeak : 0u) | (limiter[s] ? smst::kPcmFlagLimiter : 0u); }
 	void setLoudnessWeights(const float *weights) {
 		for (int c = 0; weights && c < C; ++c) if (!(std::isfinite(weights[c]) && weights[c] >= 0)) throw smst::Error("loudness: a channel weight is negative or not finite");
@@ -175,18 +214,19 @@ struct PcmOutState {
 	}
 	bool anyLoudness() const {
 		if (levelled) for (const Level &l : level) if (l.mode == SMST_LEVEL_LOUDNESS) return true;
+		if (levelled) for (const Meter &m : meter) if (m.on) return true; // (measured whatever its mode)
 		return false;
 	}
 	// A call's sections into its table's pinned copy `host` -> where the kernels find them in the device twin `dev`.  A call that dithers has
 	// every stream's mode and hash, and its frame counter as the index of the call's first frame; a levelled batch's calls the streams' level
-	// entries too (the dither entries then travel whether the call dithers or not) and, where a stream is in the loudness mode, the loudness
+	// entries too (the dither entries then travel whether the call dithers or not) and, where a stream is measured (loudEntry), the loudness
 	// entries and the channel weights
 	smst::PcmOutCall fill(void *host, void *dev, const smst::PcmTableLayout &at, int format) const {
 		smst::PcmOutCall call;
 		const bool dithered = dithers(format);
 		call.overs = dOvers;
 		if (anyLoudness()) {
-			for (int s = 0; s < S; ++s) at.loud(host)[s] = level[s].mode == SMST_LEVEL_LOUDNESS ? loud[s].entry : smst::LoudEntry{};
+			for (int s = 0; s < S; ++s) at.loud(host)[s] = loudEntry(s);
 			for (int k = 0; k < smst::kMaxChannels; ++k) at.weights(host)[k] = k < C ? loudWeights[k] : 0.0f;
 			call.loud = at.loud(dev);
 			call.loudWeights = at.weights(dev);
@@ -202,19 +242,23 @@ struct PcmOutState {
 		return call;
 	}
 	// What exact() needs on the host beside a call's view: which streams' gains come from their clip's peak (they decide whether kClipPeak
-	// runs), h of those in the loudness mode (whether the four passes do), the true-peak flags (whether kClipTruePeak does) and the streams
+	// runs), h of the measured ones (whether the four passes do) and which of them are metered (whether kLoudRange does), the true-peak flags (whether kClipTruePeak does) and the streams
 	// that are limited (whether the limiter's two passes do).  Null as the view's members are
 	void clipModes(const smst::PcmOutCall &call, Batch::ClipIo &io) {
-		bool anyLimited = false;
+		bool anyLimited = false, anyMetered = false;
 		for (int s = 0; s < S; ++s) {
 			limited[s] = levelled && smst::pcmLimited(smst::PcmLevel{unsigned(level[s].mode), level[s].gain, level[s].ceiling, flags(s)});
 			anyLimited = anyLimited || limited[s];
 			wholeClip[s] = level[s].mode != SMST_LEVEL_FIXED;
-			loudHop[s] = level[s].mode == SMST_LEVEL_LOUDNESS ? loud[s].entry.h : 0;
+			const smst::LoudEntry e = loudEntry(s);
+			loudHop[s] = e.h;
+			metered[s] = e.h > 0 && e.meter;
+			anyMetered = anyMetered || metered[s];
 		}
 		io.pcm = call;
 		io.wholeClip = call.level.table ? wholeClip.data() : nullptr;
 		io.loudHop = call.loud ? loudHop.data() : nullptr;
+		io.loudMeter = call.loud && anyMetered ? metered.data() : nullptr;
 		io.truePeak = call.level.table && anyTruePeak() ? truePeak.data() : nullptr;
 		io.limiter = call.level.table && anyLimited ? limited.data() : nullptr;
 	}
@@ -785,6 +829,45 @@ int smst_batch_take_pcm_loudness(smst_batch *b, double *lufs, int *blocks, int *
 		}
 	})
 }
+int smst_batch_set_pcm_loudness_range(smst_batch *b, int stream, int on, double sampleRate) { BATCH_CALL(b->pcmOut.setLoudnessRange(stream, on, sampleRate)) }
+int smst_batch_pcm_loudness_range(const smst_batch *b, int stream, int *on, double *sampleRate) {
+	if (!b || !b->engine) return fail("null batch");
+	if (stream < 0 || stream >= b->engine->streams()) return fail("stream index out of range");
+	if (on) *on = b->pcmOut.meter[stream].on;
+	if (sampleRate) *sampleRate = b->pcmOut.meter[stream].sampleRate;
+	return SMST_OK;
+}
+int smst_batch_set_pcm_loudness_caps(smst_batch *b, int stream, double maxMomentaryLufs, double maxShortTermLufs) { BATCH_CALL(b->pcmOut.setLoudnessCaps(stream, maxMomentaryLufs, maxShortTermLufs)) }
+int smst_batch_pcm_loudness_caps(const smst_batch *b, int stream, double *maxMomentaryLufs, double *maxShortTermLufs) {
+	if (!b || !b->engine) return fail("null batch");
+	if (stream < 0 || stream >= b->engine->streams()) return fail("stream index out of range");
+	if (maxMomentaryLufs) *maxMomentaryLufs = b->pcmOut.meter[stream].capMomentary;
+	if (maxShortTermLufs) *maxShortTermLufs = b->pcmOut.meter[stream].capShortTerm;
+	return SMST_OK;
+}
+// a power -> LUFS, -inf where it is 0; lo and hi of n gated values -> the range in LU
+static double powerLufs(double P) { return P > 0 ? -0.691 + 10*std::log10(P) : -INFINITY; }
+static double rangeLu(double lo, double hi, int n) { return n > 0 && lo > 0 ? 10*std::log10(hi/lo) : 0.0; }
+int smst_batch_take_pcm_loudness_range(smst_batch *b, double *momentaryMax, double *shortTermMax, double *range, double *low, double *high, int *shortBlocks, int *rangeBlocks) {
+	BATCH_CALL({
+		Batch &e = *b->engine;
+		const int S = e.streams();
+		e.synchronize();
+		std::vector<double> m((size_t)4*S, 0.0);
+		std::vector<int> counts((size_t)2*S, 0);
+		e.readLoudnessRange(m.data(), counts.data()); // (false: no call has metered yet -- nothing is defined)
+		for (int s = 0; s < S; ++s) {
+			const int n = counts[2*s + 1];
+			if (momentaryMax) momentaryMax[s] = powerLufs(m[4*s]);
+			if (shortTermMax) shortTermMax[s] = powerLufs(m[4*s + 1]);
+			if (range) range[s] = rangeLu(m[4*s + 2], m[4*s + 3], n);
+			if (low) low[s] = n > 0 ? powerLufs(m[4*s + 2]) : -INFINITY;
+			if (high) high[s] = n > 0 ? powerLufs(m[4*s + 3]) : -INFINITY;
+			if (shortBlocks) shortBlocks[s] = counts[2*s];
+			if (rangeBlocks) rangeBlocks[s] = n;
+		}
+	})
+}
 // a streaming call knows no clip: refused, before anything runs, where a stream that takes part (active null: every one) has a whole-clip mode
 // or the true-peak flag (a meter across calls would need 11 frames of carried history per channel)
 static void refuseWholeClipLevel(const smst_batch *b, const unsigned char *active) {
@@ -798,6 +881,9 @@ static void refuseWholeClipLevel(const smst_batch *b, const unsigned char *activ
 	for (size_t s = 0; s < b->pcmOut.limiter.size(); ++s)
 		if ((!active || active[s]) && b->pcmOut.limiter[s])
 			throw smst::Error("stream " + std::to_string(s) + " has the limiter flag (smst_batch_set_pcm_limiter): smst_batch_exact_pcm only");
+	for (size_t s = 0; s < b->pcmOut.meter.size(); ++s)
+		if ((!active || active[s]) && (b->pcmOut.meter[s].on || b->pcmOut.capped(int(s))))
+			throw smst::Error("stream " + std::to_string(s) + " has the loudness-range meter flag or a loudness cap (smst_batch_set_pcm_loudness_range / _caps), which measure a whole clip: smst_batch_exact_pcm only");
 }
 int smst_batch_process_pcm(smst_batch *b, const void *in, long long iss, long long ifs, const int *inSamples,
                            void *out, long long oss, long long ofs, const int *outSamples, int format, int memory) {
@@ -1130,8 +1216,12 @@ int smst_debug_clip_copy_levelled(int device, int format, int streams, int chann
 	if (!levelModes || !gains || !ceilings || !ditherModes || !seeds) return fail("clip copy: null level or dither arrays");
 	return clipCopy(device, 1, format, streams, channels, segments, src, srcSS, srcInner, dst, dstSS, dstInner, clamped, nans, levelModes, gains, ceilings, ditherModes, seeds, peaks, applied);
 }
-int smst_debug_clip_loudness(int device, int streams, int channels, const int *segments, const float *image, long long imageSS, long long imageCS,
-                             const double *sampleRates, const float *weights, double targetLufs, double *Z, int *blocks, int *gated, float *gains, double *blockPowers, int maxBlocks) {
+} // extern "C"
+// the four passes on a caller's image and, range != null, kLoudRange behind them with every stream metered
+struct DebugRange { const double *capsLufs; double *momentaryMax, *shortTermMax, *low, *high; int *shortBlocks, *rangeBlocks; double *shortPowers; };
+static int debugClipLoudness(int device, int streams, int channels, const int *segments, const float *image, long long imageSS, long long imageCS,
+                             const double *sampleRates, const float *weights, double targetLufs, double *Z, int *blocks, int *gated, float *gains, double *blockPowers, int maxBlocks,
+                             const DebugRange *range) {
 	SMST_TRY
 	if (streams < 1 || channels < 1 || channels > smst::kMaxChannels || !segments || !image || imageSS < 0 || imageCS < 0 || !sampleRates || maxBlocks < 0) throw smst::Error("clip loudness: bad arguments");
 	auto hip = [&](hipError_t err) { if (err != hipSuccess) throw smst::Error(std::string("clip loudness: ") + hipGetErrorString(err), true); };
@@ -1142,6 +1232,14 @@ int smst_debug_clip_loudness(int device, int streams, int channels, const int *s
 		if (g[0] < 0 || g[2] < 0 || g[4] < 0 || g[6] < 0) throw smst::Error("clip loudness: negative segment offset or count");
 		if ((long long)g[2] + g[6] > 0x7fffffff) throw smst::Error("clip loudness: the clip is too long");
 		if (!smst::loudEntryOf(sampleRates[s], targetLufs, entries[s])) throw smst::Error("clip loudness: bad sample rate");
+		if (range) {
+			entries[s].meter = 1;
+			for (int k = 0; range->capsLufs && k < 2; ++k) {
+				const double cap = range->capsLufs[2*s + k];
+				if (std::isnan(cap) || cap == -INFINITY) throw smst::Error("clip loudness: a cap is NaN or -inf");
+				(k ? entries[s].Ps : entries[s].Pm) = std::isfinite(cap) ? std::pow(10.0, (cap + 0.691)/10) : double(INFINITY);
+			}
+		}
 		for (int k = 0; k < 2; ++k) if (g[4*k + 2] > 0 && !g[4*k + 3]) end = std::max(end, g[4*k] + g[4*k + 2]);
 		most = std::max(most, g[2] + g[6]);
 		maxSub = std::max(maxSub, (g[2] + g[6])/entries[s].h + 1);
@@ -1155,12 +1253,13 @@ int smst_debug_clip_loudness(int device, int streams, int channels, const int *s
 	const size_t imageBytes = end ? size_t((streams - 1)*imageSS + (channels - 1)*imageCS + end)*sizeof(float) : 0;
 	const int maxChunks = std::max((most + smst::kLoudChunk - 1)/smst::kLoudChunk, 1);
 	Buffer<unsigned char, false> dImage, dSegs, dEntries, dWeights;
-	Buffer<double, false> dScratch;
+	Buffer<double, false> dScratch, dRange;
 	dImage.allocate(imageBytes + 32, "clip loudness");
 	dSegs.allocate((size_t)2*streams*sizeof(smst::ClipSeg), "clip loudness");
 	dEntries.allocate(entries.size()*sizeof(smst::LoudEntry), "clip loudness");
 	dWeights.allocate(w.size()*sizeof(float), "clip loudness");
 	dScratch.allocate(smst::loudScratchDoubles(streams, channels, maxChunks, maxSub), "clip loudness");
+	if (range) dRange.allocate(smst::loudRangeDoubles(streams, maxSub), "clip loudness");
 	unsigned char *i0 = dImage + reinterpret_cast<uintptr_t>(image)%16; // (as far behind a 16-byte boundary as the caller's image)
 	if (imageBytes) hip(hipMemcpy(i0, image, imageBytes, hipMemcpyHostToDevice));
 	hip(hipMemcpy(dSegs, segments, (size_t)2*streams*sizeof(smst::ClipSeg), hipMemcpyHostToDevice));
@@ -1169,8 +1268,27 @@ int smst_debug_clip_loudness(int device, int streams, int channels, const int *s
 	const smst::LoudScratch at = smst::loudScratchAt(dScratch, streams, channels, maxChunks, maxSub);
 	smst::launchClipLoudness(reinterpret_cast<const float *>(i0), imageSS, imageCS, reinterpret_cast<const smst::ClipSeg *>(dSegs.p), streams, channels,
 	                         reinterpret_cast<const smst::LoudEntry *>(dEntries.p), reinterpret_cast<const float *>(dWeights.p), at, nullptr);
+	const smst::LoudRangeScratch rangeAt = range ? smst::loudRangeAt(dRange, streams, maxSub) : smst::LoudRangeScratch{};
+	if (range) smst::launchClipLoudnessRange(reinterpret_cast<const smst::ClipSeg *>(dSegs.p), streams, channels, reinterpret_cast<const smst::LoudEntry *>(dEntries.p),
+	                                         reinterpret_cast<const float *>(dWeights.p), at, rangeAt, nullptr);
 	hip(hipGetLastError());
 	hip(hipStreamSynchronize(nullptr));
+	if (range) {
+		std::vector<double> m((size_t)4*streams);
+		std::vector<int> k((size_t)2*streams);
+		hip(hipMemcpy(m.data(), rangeAt.meters, m.size()*sizeof(double), hipMemcpyDeviceToHost));
+		hip(hipMemcpy(k.data(), rangeAt.counts, k.size()*sizeof(int), hipMemcpyDeviceToHost));
+		for (int s = 0; s < streams; ++s) {
+			if (range->momentaryMax) range->momentaryMax[s] = m[4*s];
+			if (range->shortTermMax) range->shortTermMax[s] = m[4*s + 1];
+			if (range->low) range->low[s] = m[4*s + 2];
+			if (range->high) range->high[s] = m[4*s + 3];
+			if (range->shortBlocks) range->shortBlocks[s] = k[2*s];
+			if (range->rangeBlocks) range->rangeBlocks[s] = k[2*s + 1];
+			const int ns = std::min(k[2*s], maxBlocks);
+			if (range->shortPowers && ns > 0) hip(hipMemcpy(range->shortPowers + (size_t)s*maxBlocks, rangeAt.st + (size_t)s*maxSub, (size_t)ns*sizeof(double), hipMemcpyDeviceToHost));
+		}
+	}
 	std::vector<int> counts((size_t)2*streams);
 	hip(hipMemcpy(counts.data(), at.counts, counts.size()*sizeof(int), hipMemcpyDeviceToHost));
 	if (Z) hip(hipMemcpy(Z, at.Z, (size_t)streams*sizeof(double), hipMemcpyDeviceToHost));
@@ -1184,6 +1302,18 @@ int smst_debug_clip_loudness(int device, int streams, int channels, const int *s
 	}
 	return SMST_OK;
 	SMST_CATCH
+}
+extern "C" {
+int smst_debug_clip_loudness(int device, int streams, int channels, const int *segments, const float *image, long long imageSS, long long imageCS,
+                             const double *sampleRates, const float *weights, double targetLufs, double *Z, int *blocks, int *gated, float *gains, double *blockPowers, int maxBlocks) {
+	return debugClipLoudness(device, streams, channels, segments, image, imageSS, imageCS, sampleRates, weights, targetLufs, Z, blocks, gated, gains, blockPowers, maxBlocks, nullptr);
+}
+int smst_debug_clip_loudness_range(int device, int streams, int channels, const int *segments, const float *image, long long imageSS, long long imageCS,
+                                   const double *sampleRates, const float *weights, double targetLufs, const double *capsLufs,
+                                   double *momentaryMax, double *shortTermMax, double *low, double *high, int *shortBlocks, int *rangeBlocks,
+                                   float *gains, double *shortPowers, int maxBlocks) {
+	const DebugRange range{capsLufs, momentaryMax, shortTermMax, low, high, shortBlocks, rangeBlocks, shortPowers};
+	return debugClipLoudness(device, streams, channels, segments, image, imageSS, imageCS, sampleRates, weights, targetLufs, nullptr, nullptr, nullptr, gains, nullptr, maxBlocks, &range);
 }
 // the true-peak pass alone, and kClipPeak beside it: see include/smst.h
 int smst_debug_clip_true_peak(int device, int streams, int channels, const int *segments, const float *image, long long imageSS, long long imageCS,

@@ -169,7 +169,7 @@ __host__ __device__ inline bool analysisWindowInCall(int B, int M, int I, int in
 // form" tests assert through these that BOTH forms really ran.
 enum LaunchKind {
 	LK_VOC_ALIGNED, LK_VOC_TWISTED, LK_VOC_INTERIOR, LK_VOC_STAGED, LK_VOC_GATHER, LK_VOC_N, LK_VOC_ONE, LK_VOC_ACROSS, LK_VOC_CONT, LK_CHAIN_UNFUSED,
-	LK_ANALYSE_TEAMS, LK_ANALYSE_PAIRS, LK_ANALYSE_TWIST, LK_TWIST_ROWS, LK_ANALYSE_FAST, LK_ANALYSE_GENERIC, LK_SYNTH_TEAMS, LK_SYNTH_FAST, LK_SYNTH_GENERIC, LK_SYNTH_EMIT, LK_EMIT_CARRIED, LK_FEED_ONE_PASS, LK_PCM_IN, LK_PCM_OUT, LK_CLIP_IN, LK_CLIP_OUT, LK_PCM_OUT_DITHERED, LK_CLIP_OUT_DITHERED, LK_PCM_OUT_LEVELLED, LK_CLIP_OUT_LEVELLED, LK_CLIP_PEAK, LK_CLIP_LOUDNESS, LK_CLIP_TRUE_PEAK, LK_CLIP_LIMIT_NEED, LK_CLIP_LIMIT_GAIN, LK_CLIP_OUT_LIMITED, LK_COUNT
+	LK_ANALYSE_TEAMS, LK_ANALYSE_PAIRS, LK_ANALYSE_TWIST, LK_TWIST_ROWS, LK_ANALYSE_FAST, LK_ANALYSE_GENERIC, LK_SYNTH_TEAMS, LK_SYNTH_FAST, LK_SYNTH_GENERIC, LK_SYNTH_EMIT, LK_EMIT_CARRIED, LK_FEED_ONE_PASS, LK_PCM_IN, LK_PCM_OUT, LK_CLIP_IN, LK_CLIP_OUT, LK_PCM_OUT_DITHERED, LK_CLIP_OUT_DITHERED, LK_PCM_OUT_LEVELLED, LK_CLIP_OUT_LEVELLED, LK_CLIP_PEAK, LK_CLIP_LOUDNESS, LK_CLIP_TRUE_PEAK, LK_CLIP_LIMIT_NEED, LK_CLIP_LIMIT_GAIN, LK_CLIP_OUT_LIMITED, LK_CLIP_LOUDNESS_RANGE, LK_COUNT
 };
 long long launchCount(const char *name); // -1: unknown name
 
@@ -264,8 +264,9 @@ void launchClipPeak(const float *image, long long imageStreamStride, long long i
 // (loudEntryOf; false: the sample rate gives h < kLoudChunk).
 constexpr int kLoudChunk = 256; // frames of a channel's clip, in clip order, that one lane filters
 struct LoudCoef { double b0, b1, b2, a1, a2, d1, d2; }; // shelf: b0 b1 b2 / 1 a1 a2; high-pass: 1 -2 1 / 1 d1 d2
-struct LoudEntry { LoudCoef k; double Ac[16], P, gate; int h, pad; };
-bool loudEntryOf(double sampleRate, double targetLufs, LoudEntry &e);
+// meter != 0: kLoudRange (smst_loudness_range.h) measures the stream too; Pm, Ps: the powers of its momentary and short-term caps (+inf: none)
+struct LoudEntry { LoudCoef k; double Ac[16], P, gate; int h, meter; double Pm, Ps; };
+bool loudEntryOf(double sampleRate, double targetLufs, LoudEntry &e); // (meter 0, no caps)
 // The passes' scratch, all float64 but the meters' last two: per stream the meters -- Z, the two block counts, gL --, per (stream, channel,
 // chunk) the chunk's end state (then its incoming state) and its two partial sums, per (stream, channel) the sub-block sums, per stream the
 // block powers.  maxChunks / maxSub: of the longest measured clip (loudScratchAt lays out `base`, which holds loudScratchDoubles)
@@ -287,6 +288,21 @@ inline LoudScratch loudScratchAt(double *base, int S, int C, int maxChunks, int 
 // the four passes, on `st`: every stream's meters are written (a stream that is not measured: Z 0, no blocks, gL 1)
 void launchClipLoudness(const float *image, long long imageStreamStride, long long imageChannelStride, const ClipSeg *segs, int S, int C,
                         const LoudEntry *loud, const float *weights, const LoudScratch &w, hipStream_t st);
+// Loudness range and the two maxima of every metered stream's clip (include/smst.h, "Loudness range", has the definition;
+// smst_loudness_range.h the kernel), from the sub-block sums and the block powers that the four passes left in `w`.  Per stream the meters --
+// M, ST, lo, hi as powers, then ns and n -- and the short-term powers st[s*maxSt + i]; a stream that is not metered: zeros.  Where a cap of
+// the stream's entry is finite, w.gain[s] is lowered to min(gL, gm, gs) in place.  maxSt >= ns of every metered stream
+struct LoudRangeScratch { double *meters; int *counts; double *st; int maxSt; };
+inline size_t loudRangeDoubles(int S, int maxSt) { return (size_t)5*S + (size_t)S*maxSt; }
+inline LoudRangeScratch loudRangeAt(double *base, int S, int maxSt) {
+	LoudRangeScratch r;
+	r.meters = base;
+	r.counts = reinterpret_cast<int *>(base + (size_t)4*S);
+	r.st = base + (size_t)5*S;
+	r.maxSt = maxSt;
+	return r;
+}
+void launchClipLoudnessRange(const ClipSeg *segs, int S, int C, const LoudEntry *loud, const float *weights, const LoudScratch &w, const LoudRangeScratch &r, hipStream_t st);
 // True peak of every flagged stream's clip (include/smst.h, "True peak", has the definition; smst_true_peak.h the kernel): a 4x polyphase
 // interpolation in float64 of every channel, in clip order across the join of the two segments, maxed with the samples themselves into
 // truePeak[s] as float bits (the caller zeroes the words in front of it).  level: the call's level entries, whose fourth word is the flag.

@@ -1840,7 +1840,7 @@ void Batch::exact(const ClipIo &io, const int *inSamples, const int *outSamples,
 	}
 	PcmLevelIo level = io.pcm.level;
 	int loudMost = 0, loudSub = 0;
-	if (wholeClip && io.loudHop) for (int s = 0; s < S; ++s) if (run[s] && io.loudHop[s] > 0) {
+	if (io.pcm.level.table && io.loudHop) for (int s = 0; s < S; ++s) if (run[s] && io.loudHop[s] > 0) { // (a stream in the loudness mode, or a metered one of any mode)
 		loudMost = std::max(loudMost, outSamples[s]);
 		loudSub = std::max(loudSub, outSamples[s]/io.loudHop[s] + 1);
 	}
@@ -1851,6 +1851,13 @@ void Batch::exact(const ClipIo &io, const int *inSamples, const int *outSamples,
 		const LoudScratch w = loudScratchAt(reinterpret_cast<double *>(dLoud), S, C, maxChunks, loudSub);
 		launchClipLoudness(dClipOut, outImgSS, pitchOut, cs.dev + (size_t)2*S, S, C, io.pcm.loud, io.pcm.loudWeights, w, st);
 		level.loudGain = w.gain;
+		bool metered = false;
+		if (io.loudMeter) for (int s = 0; s < S; ++s) metered = metered || (run[s] && io.loudMeter[s] && io.loudHop[s] > 0);
+		if (metered) { // the range and the two maxima, from what the passes left; a capped stream's gain is lowered where kLoudGate wrote it
+			const size_t more = loudRangeDoubles(S, loudSub);
+			growScratch(dLoudRange, loudRangeCapacity, 2*more, more/4 + 1024, true);
+			launchClipLoudnessRange(cs.dev + (size_t)2*S, S, C, io.pcm.loud, io.pcm.loudWeights, w, loudRangeAt(reinterpret_cast<double *>(dLoudRange), S, loudSub), st);
+		}
 	}
 	int truePeakMost = 0;
 	if (io.pcm.level.table && io.truePeak) for (int s = 0; s < S; ++s) if (run[s] && io.truePeak[s]) truePeakMost = std::max(truePeakMost, outSamples[s]);
@@ -1890,6 +1897,16 @@ bool Batch::readLoudness(double *Z, int *counts) {
 	const LoudScratch w = loudScratchAt(reinterpret_cast<double *>(dLoud), S, C, 0, 0); // (the meters lie in front, whatever the call's shapes)
 	SMST_HIP(hipMemcpy(Z, w.Z, (size_t)S*sizeof(double), hipMemcpyDeviceToHost));
 	SMST_HIP(hipMemcpy(counts, w.counts, (size_t)2*S*sizeof(int), hipMemcpyDeviceToHost));
+	return true;
+}
+
+bool Batch::readLoudnessRange(double *meters, int *counts) {
+	if (!dLoudRange) return false;
+	SMST_HIP(hipSetDevice(dev));
+	SMST_HIP(hipStreamSynchronize(st));
+	const LoudRangeScratch r = loudRangeAt(reinterpret_cast<double *>(dLoudRange), S, 0); // (the meters lie in front, whatever the call's shapes)
+	SMST_HIP(hipMemcpy(meters, r.meters, (size_t)4*S*sizeof(double), hipMemcpyDeviceToHost));
+	SMST_HIP(hipMemcpy(counts, r.counts, (size_t)2*S*sizeof(int), hipMemcpyDeviceToHost));
 	return true;
 }
 

@@ -110,12 +110,14 @@ public:
 	// Counts are checked by the caller: outSamples[s] != 0, inSamples[s] >= 0 where outSamples[s] > 0.
 	// pcm (frame formats; smst_pcm_tables.h): the device side of the output conversion, which rides in the caller's per-call table.  wholeClip
 	// (host, [S]; null where the call is not levelled): which streams' gains come from their clip's peak -- if one of them runs, kClipPeak
-	// does.  loudHop (host, [S]; null where no stream is in the loudness mode): h of the streams in that mode, 0 for the others -- if one of
+	// does.  loudHop (host, [S]; null where no stream is measured): h of the streams in the loudness mode and of the metered ones, 0 for the others -- if one of
 	// them runs, the four passes of smst_loudness.h do, and kClipOut finds the gains in the engine's meters.  truePeak (host, [S]; null where
 	// no stream has the true-peak flag): the streams that have it -- if one of them runs, kClipTruePeak (smst_true_peak.h) does, and kClipOut
 	// forms those streams' whole-clip gains from the words it leaves in the engine's memory
 	struct ClipIo { const void *in; long long inStreamStride, inInnerStride; void *out; long long outStreamStride, outInnerStride; int format;
 		PcmOutCall pcm; const unsigned char *wholeClip = nullptr; const int *loudHop = nullptr; const unsigned char *truePeak = nullptr;
+		const unsigned char *loudMeter = nullptr;  // (host, [S]; null where no stream is metered: the streams whose loudness entry has the meter flag -- loudHop has their
+		                                           // h whatever their mode, and if one of them runs, kLoudRange (smst_loudness_range.h) does behind the four passes)
 		const unsigned char *limiter = nullptr; }; // (host, [S]; null where no stream is limited: the streams whose level entry pcmLimited() names -- if one
 		                                           // of them runs, the two passes of smst_limiter.h do, and kClipOut takes their r from the engine's scratch)
 	// The limiter's lookahead H in frames (include/smst.h, "Limiter"), 1 ... kLimitMaxLookahead, the batch's one.  prepareLimiter() puts the
@@ -130,6 +132,8 @@ public:
 	bool readTruePeaks(float *truePeaks);
 	// the loudness meters of the newest exact call that measured, [S] and [S][2] (blocks past the absolute gate, past both); false: none has.  Synchronises
 	bool readLoudness(double *Z, int *counts);
+	// the range meters of the newest exact call that metered, [S][4] (M, ST, lo, hi: powers) and [S][2] (ns, n); false: none has.  Synchronises
+	bool readLoudnessRange(double *meters, int *counts);
 	void exact(const ClipIo &io, const int *inSamples, const int *outSamples, unsigned char *tooShort);
 	void synchronize();
 
@@ -315,6 +319,8 @@ private:
 	size_t clipInCapacity = 0, clipOutCapacity = 0;
 	float *dLoud = nullptr; // the loudness passes' scratch (LoudScratch: float64, the meters in front), grown on demand as the images are
 	size_t loudCapacity = 0;
+	float *dLoudRange = nullptr; // kLoudRange's scratch (LoudRangeScratch: float64, the meters in front of the short-term powers), grown by the calls that meter
+	size_t loudRangeCapacity = 0;
 	float *dTruePeak = nullptr; // the true-peak words of the newest exact call that measured ([S] float bits), allocated by the first one
 	size_t truePeakCapacity = 0;
 	// the limiter: the meters of the newest exact call that limited ([2][S] ints) in front of need and r ([S][pitch] floats each), grown on

@@ -221,6 +221,7 @@ bool loudEntryOf(double sampleRate, double targetLufs, LoudEntry &e) {
 	e.P = std::pow(10.0, (targetLufs + 0.691)/10);
 	e.gate = std::pow(10.0, (-70 + 0.691)/10);
 	e.h = int(hop);
+	e.Pm = e.Ps = __builtin_inf();
 	return true;
 }
 

@@ -5,7 +5,7 @@
 //                    outCounts  [S] int            frames each stream emits
 //                    dither     [S] PcmDither      mode, hash, index of the call's first frame
 //                    level      [S] PcmLevel       mode, gain, ceiling
-//                    loud       [S] LoudEntry      filter, gate and target of a stream in the loudness mode (h == 0: another mode)
+//                    loud       [S] LoudEntry      filter, gate, target, meter flag and caps of a measured stream (h == 0: not measured)
 //                    weights    [kMaxChannels] float
 //                  What a call's output side needs is a run of neighbouring sections: ONE copy (upload()).
 // PcmMeters        the batch's [3][S] meter words, device: the peaks since the last take (float bits), the gains the newest conversions
@@ -19,7 +19,7 @@
 
 namespace smst {
 
-// null members: not in this call (dither: the call does not dither; level.table: not a levelled batch; loud: no stream in the loudness mode)
+// null members: not in this call (dither: the call does not dither; level.table: not a levelled batch; loud: no stream is measured -- none in the loudness mode, none with the meter flag)
 struct PcmOutCall {
 	unsigned *overs = nullptr; // [S][2] counters: clamped, NaN
 	const PcmDither *dither = nullptr;
@@ -51,7 +51,7 @@ struct PcmTableLayout {
 	float *weights(void *base) const { return pcmTableAt<float>(base, weights()); }
 	// The bytes the output side of a call uploads: from the output counts where they ride along, else from the dither entries, to the end of
 	// the last section the call reads.  A levelled batch's calls carry the dither entries in front of the level entries whether they dither
-	// or not; only a levelled batch has a stream in the loudness mode
+	// or not; only a levelled batch has a measured stream
 	struct Range { size_t offset, bytes; };
 	Range upload(bool withOutCounts, bool dithered, bool levelled, bool loudness) const {
 		const size_t first = withOutCounts ? outCounts() : dither();

@@ -16,6 +16,8 @@ the host from its first entry point to the return of smst_batch_synchronize.
                                                   # the true-peak pass
   python tools/bench_exact.py --mode protect --limit        # PROTECT (at --limit-gain, so that the ceiling bites) without and with the limiter flag
                                                   # alternating: limit - protect = the limiter's two passes and the limited copy's extra read
+  python tools/bench_exact.py --mode normalise --loudness --loudness-range   # ... and LOUDNESS with the meter flag: loudness_range - loudness =
+                                                  # the range stage (kLoudRange) behind the four passes
 """
 import argparse
 import ctypes as C
@@ -41,6 +43,7 @@ def main():
     ap.add_argument("--loudness", action="store_true", help="frame modes: a batch in LEVEL_LOUDNESS (-23 LUFS, ceiling 32766/32768) beside the mode's own")
     ap.add_argument("--true-peak", action="store_true", help="frame modes: a batch with the mode's own level setting and the true-peak flag on every stream beside the mode's own")
     ap.add_argument("--limit", action="store_true", help="frame modes protect / normalise: a batch with the mode's own level setting and the limiter flag on every stream beside the mode's own")
+    ap.add_argument("--loudness-range", action="store_true", help="frame modes: a batch in LEVEL_LOUDNESS with the loudness-range meter flag on every stream beside the mode's own")
     ap.add_argument("--limit-gain", type=float, default=4.0, help="--limit: the PROTECT gain of both batches (+12 dB: most tiles hold frames over the ceiling)")
     ap.add_argument("--limit-lookahead", type=int, default=72, help="--limit: the lookahead in frames")
     ap.add_argument("--streams", type=int, default=256)
@@ -128,7 +131,7 @@ def frames_modes(a, lib, x, nin, nout, batch):
     runs = {}
     assert not (a.true_peak and a.mode == "level"), "--true-peak goes with one mode"
     assert not (a.limit and a.mode not in ("protect", "normalise")), "--limit goes with --mode protect (or normalise, where the flag is inert)"
-    for key in (("pcm", "fixed", "protect") if a.mode == "level" else (a.mode,)) + (("loudness",) if a.loudness else ()) + (("true_peak",) if a.true_peak else ()) + (("limit",) if a.limit else ()):
+    for key in (("pcm", "fixed", "protect") if a.mode == "level" else (a.mode,)) + (("loudness",) if a.loudness else ()) + (("true_peak",) if a.true_peak else ()) + (("limit",) if a.limit else ()) + (("loudness_range",) if a.loudness_range else ()):
         b = batch()
         name = a.mode if key in ("true_peak", "limit") else key
         if key == "true_peak":
@@ -142,8 +145,10 @@ def frames_modes(a, lib, x, nin, nout, batch):
             b.set_pcm_level(smst.LEVEL_PROTECT, a.limit_gain if a.limit else 1.0, 32766.0/32768.0)
         if name == "normalise":
             b.set_pcm_level(smst.LEVEL_NORMALISE, 1.0, 32766.0/32768.0)
-        if name == "loudness":
+        if name in ("loudness", "loudness_range"):
             b.set_pcm_loudness(-23.0, 32766.0/32768.0, a.sample_rate)
+        if name == "loudness_range":
+            b.set_pcm_loudness_range(True, a.sample_rate)
         runs[key] = b
 
     def call(b):
@@ -189,6 +194,14 @@ def frames_modes(a, lib, x, nin, nout, batch):
                                gain_range=[float(gains.min()), float(gains.max())], image_bytes=int(S)*Cn*int(nout.sum()//S)*4,
                                launches=[smst.launch_count(k, lib) for k in ("clip_limit_need", "clip_limit_gain", "clip_out_limited")])
         result["limit"]["minus_%s_ms" % a.mode] = round(result["step_ms"]["limit"]["median"] - result["step_ms"][a.mode]["median"], 3)
+    if a.loudness_range:
+        mmax, smax, lra, low, high, ns, ng = runs["loudness_range"].take_pcm_loudness_range()
+        result["loudness_range"] = dict(short_term_max_range=[float(smax.min()), float(smax.max())], lra_range=[float(lra.min()), float(lra.max())],
+                                        short_blocks=[int(ns.min()), int(ns.max())], range_blocks=[int(ng.min()), int(ng.max())],
+                                        launches=smst.launch_count("clip_loudness_range", lib))
+        for other in ("loudness", a.mode):
+            if other in result["step_ms"]:
+                result["loudness_range"]["minus_%s_ms" % other] = round(result["step_ms"]["loudness_range"]["median"] - result["step_ms"][other]["median"], 3)
     print(json.dumps(result))
     for b in runs.values():
         b.close()

@@ -6,7 +6,7 @@
 //   stretch_cli [--semitones=S] [--formant=S] [--formant-comp] [--formant-base=Hz] [--tonality=Hz] [--time=F]
 //               [--split-computation] [--device=N] [--out-format=s16|s24|f32] [--dither=none|tpdf|tpdf-hp] [--dither-seed=N]
 //               [--exact] [--gain=dB] [--protect=dBFS | --normalize=dBFS] [--loudness=LUFS] [--true-peak]
-//               [--limit] [--limit-lookahead=ms]
+//               [--limit] [--limit-lookahead=ms] [--loudness-range] [--max-short-term=LUFS] [--max-momentary=LUFS]
 //               in.wav out.wav [in2.wav out2.wav ...]
 //
 // --out-format (also "--out-format s24"): the samples of the files written -- 16-bit (the default, as the reference's CLI writes), 24-bit by the
@@ -37,6 +37,12 @@
 // --limit-lookahead=ms (default 1.5) is converted to frames with the batch's sample rate; a short lookahead weakens a dBTP ceiling.  The
 // line of a file then ends in " limit=<%.4f> limited=<frames>": the deepest gain reduction in dB (0 where nothing was limited) and the
 // number of frames that were reduced.
+// --loudness-range (needs the exact flow, as --true-peak does): every rendered clip's maximum momentary loudness, maximum short-term
+// loudness and loudness range (EBU Tech 3341 / 3342; include/smst.h, "Loudness range") are measured on the GPU at the files' sample rate,
+// before the gain, and printed: "range: <file> momentary-max=<%.4f> short-term-max=<%.4f> lra=<%.4f>", the maxima in LUFS (-inf for
+// silence and for a clip too short to have one), the range in LU.  Alone it only meters.
+// --max-short-term=LUFS and --max-momentary=LUFS (they need --loudness): caps on the two maxima of the file as written (EBU R 128 s1) --
+// the gain is the lowest of the target's and the caps'.
 // Files given together must share sample rate and channel count (they form one batch); lengths may differ.
 #include <algorithm>
 #include <cmath>
@@ -126,6 +132,15 @@ int main(int argc, char **argv) {
 		std::fprintf(stderr, "--limit needs --protect=dBFS (its ceiling) or --loudness=LUFS\n");
 		return 2;
 	}
+	const bool loudnessRange = hasFlag(argc, argv, "loudness-range"), capShortTerm = hasValue(argc, argv, "max-short-term"), capMomentary = hasValue(argc, argv, "max-momentary");
+	if (loudnessRange && !exact) {
+		std::fprintf(stderr, "--loudness-range needs --exact (or --protect, --normalize or --loudness, which imply it): whole clips only\n");
+		return 2;
+	}
+	if ((capShortTerm || capMomentary) && !loudness) {
+		std::fprintf(stderr, "--max-short-term and --max-momentary need --loudness=LUFS: they cap the gain that reaches its target\n");
+		return 2;
+	}
 	const double limitLookaheadMs = flagValue(argc, argv, "limit-lookahead", 1.5);
 	const float gain = fromDecibels(flagValue(argc, argv, "gain", 0)), ceiling = fromDecibels(flagValue(argc, argv, protect ? "protect" : "normalize", 0));
 	std::vector<std::string> files;
@@ -191,6 +206,8 @@ int main(int argc, char **argv) {
 			CHECK(smst_batch_set_pcm_limiter_lookahead(batch, int(std::lround(limitLookaheadMs*1e-3*double(inputs[0].sampleRate)))));
 			CHECK(smst_batch_set_pcm_limiter(batch, -1, 1));
 		}
+		if (loudnessRange) CHECK(smst_batch_set_pcm_loudness_range(batch, -1, 1, double(inputs[0].sampleRate)));
+		if (capShortTerm || capMomentary) CHECK(smst_batch_set_pcm_loudness_caps(batch, -1, flagValue(argc, argv, "max-momentary", INFINITY), flagValue(argc, argv, "max-short-term", INFINITY)));
 		// `count` samples of file s from sample `first` on as frames at `frames`; false: one of them is no value of the format
 		auto toFrames = [&](int s, int first, int count, unsigned char *frames) {
 			for (int i = 0; i < count; ++i) for (int c = 0; c < C; ++c) {
@@ -249,6 +266,11 @@ int main(int argc, char **argv) {
 				if (limit) std::printf(" limit=%.4f limited=%lld", 20.0*std::log10(double(minGains[s])), limitedFrames[s]);
 				std::printf("\n");
 			}
+		}
+		if (loudnessRange) {
+			std::vector<double> momentary(S, 0.0), shortTerm(S, 0.0), range(S, 0.0);
+			CHECK(smst_batch_take_pcm_loudness_range(batch, momentary.data(), shortTerm.data(), range.data(), nullptr, nullptr, nullptr, nullptr));
+			for (int s = 0; s < S; ++s) std::printf("range: %s momentary-max=%.4f short-term-max=%.4f lra=%.4f\n", files[2*s + 1].c_str(), momentary[s], shortTerm[s], range[s]);
 		}
 		for (int s = 0; s < S; ++s) {
 			if (!writeWavFrames(files[2*s + 1], inputs[s].sampleRate, inputs[s].channels, bits, outFrames.data() + (size_t)s*maxOut*C*esz, size_t(outLen[s]), error, format == SMST_PCM_F32)) {
