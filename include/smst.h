@@ -707,6 +707,73 @@ int smst_debug_clip_loudness_range(int device, int streams, int channels, const 
                                    const double *sampleRates, const float *weights, double targetLufs, const double *capsLufs,
                                    double *momentaryMax, double *shortTermMax, double *low, double *high, int *shortBlocks, int *rangeBlocks,
                                    float *gains, double *shortPowers, int maxBlocks);
+/* ---- Resample (EXTENSION; opt-in: a batch that never calls smst_batch_set_pcm_resample launches the kernels, writes the bytes and counts the launches it did before) ----
+ * A sample-rate converter in front of the engine, in smst_batch_exact_pcm: a stream may carry a rational ratio L/M = up/down, the batch's
+ * rate over its clips' rate, and its frames are resampled on the device to the batch's rate.  Everything behind that point -- outputSeek,
+ * process, flush, peak, loudness, true peak, limiter, conversion -- runs unchanged.  A caller who makes the batch's rate the delivery rate
+ * gets "any rate in, one rate out".  The reference has no sample-rate notion beyond its presets.
+ *
+ * Ratio.  L and M are integers, 1 <= L, M <= SMST_RESAMPLE_MAX_TERM once the library has reduced them by their gcd; 2*M <= 9*L and 2*L <= 9*M
+ * (at most 4.5 either way: 192 kHz -> 44.1 kHz is 147/640).  1/1 means "not resampled".  At most SMST_RESAMPLE_MAX_RATIOS distinct reduced
+ * ratios other than 1/1 are live in a batch at a time; a ratio that no stream uses any more frees its slot.
+ *
+ * Lengths.  N = inSamples[s] frames at the clip's rate become Nr = ceil(N*L/M) = (N*L + M - 1)/M frames (64-bit integers; Nr must fit an
+ * int).  Resampled frame n sits at input position n*M/L: i = (n*M)/L, p = (n*M) mod L, both in 64-bit integers.  Frame 0 sits on input
+ * frame 0: the filter is symmetric, there is no delay.  For a resampled stream smst_batch_exact_pcm behaves exactly as if the caller had
+ * handed it those Nr frames: exactLengths(Nr, outSamples[s]), rate_s = Nr/float(outSamples[s]), SMST_ERR_SHORT in status where Nr is
+ * below the seek length.
+ *
+ * Filter: Kaiser-windowed sinc, computed by the host in double, once per ratio.  r = min(1, L/M), rho = 0.98*r, W = 32/r, H = ceil(W),
+ * T = 2*H taps (64 upwards, 70 for 147/160, 128 for 1/2, 280 for 147/640).  For phase p in [0, L) and tap j in [0, T):
+ * t = (j - (H - 1)) - p/L;  h = rho*sinc(rho*t)*I0(10*sqrt(1 - (t/W)^2))/I0(10) for |t| < W, else 0, sinc(x) = sin(pi*x)/(pi*x);
+ * c[p][j] = float32(h / sum_j h): each phase normalised to unit DC gain, one rounding.  The filter is DEFINED by this formula, as the
+ * true-peak interpolator is.  Known answers (to within one float32 ulp; bit patterns of float32):
+ *   2/1:     c[0][30..32] = 3ca2f978 3f7ae0ea 3ca2f978 (0.97999442 at the centre); c[1][31] = c[1][32] = 3f22b49c (0.63556838)
+ *   160/147: T = 64; c[0][31] = 3f7ae0ea; c[80][31] = c[80][32] = 3f22b49c; c[159][0] = -3.198598506e-06
+ *   147/160: T = 70; c[1][34] = 3f667b0e (0.90031517), c[1][35] = 3dd53ebb; c[0][0] = 8.022285328e-06
+ *   T for 1/1, 2/1, 1/2, 3/2, 2/3, 160/147, 147/160, 147/640, 640/147: 64, 64, 128, 64, 96, 64, 70, 280, 64
+ * What it does (on the float32 table; 160/147, 147/160, 1/2): the passband holds within -0.053 ... +0.0001 dB up to 0.907 of the lower
+ * Nyquist (20 kHz for 44.1 kHz material); everything at or above 1.093 of it -- what would alias or image into that band -- is at -100.6 dB
+ * or below; in between the filter rolls off, through -11.6 dB at Nyquist.
+ *
+ * Arithmetic: float64, then one rounding.  y(n) = sum_{j=0...T-1} double(c[p][j])*double(x(i + j - (H - 1))), the sum from 0.0 in the order
+ * j = 0 ... T-1, x outside [0, N) = 0; the resampled frame is float32(y(n)).  A product of two float32 values is exact in float64, so an FMA
+ * changes nothing and a mirror that adds in the same order reproduces the device bit for bit.  x is the planar fp32 value that the
+ * format's input rule gives (float(v)/32768 for int16).  Known answers, float32 bit patterns:
+ *   3/2, 5 frames, x(2) = 1, Nr = 8: bca067e3 be4717b5 3ed8327b 3f7ae0ea 3ed8327b be4717b5 bca067e3 3dddb185
+ *   2/3, 7 frames, x(3) = 1, Nr = 5: bc55dff0 3c594cd8 3f2740ad 3c594cd8 bc55dff0
+ *   160/147, 200 frames of 1.0: Nr = 218, the frames 40 ... 169 deviate from 1 by at most 6.0e-8
+ *
+ * Which calls.  smst_batch_exact_pcm serves resampled streams, in host and device memory and in every format.  smst_batch_exact (planar)
+ * and smst_batch_process_pcm, _seek_pcm and _output_seek_pcm return SMST_ERR_INVALID, before anything runs, if a stream that takes part has a
+ * ratio other than 1/1: skipping the stage silently would be a lie.  smst_batch_flush_pcm has no input and is unaffected.  The too-short and
+ * left-out streams of a call stay as they are.
+ * Out of scope: resampling the output; resampling in the streaming or the planar calls; irrational or time-varying ratios; a quality
+ * setting; a fused PCM-to-resampled kernel without the raw image.
+ * SMST_ERR_INVALID with a message that names the limit: a term outside [1, SMST_RESAMPLE_MAX_TERM]; a ratio beyond 4.5 either way; a ninth
+ * distinct ratio; a stream index out of range; a null batch; in a call, an Nr that does not fit an int. */
+#define SMST_RESAMPLE_MAX_TERM 640
+#define SMST_RESAMPLE_MAX_RATIOS 8
+#define SMST_RESAMPLE_TILE 1024
+/* stream = -1: every stream.  1/1 turns the stage off.  The first call with another ratio builds that ratio's table and puts it into device
+ * memory: tables are never uploaded in a call */
+int smst_batch_set_pcm_resample(smst_batch *b, int stream, int up, int down);
+/* the stream's reduced ratio (1/1: none); either pointer may be null */
+int smst_batch_pcm_resample(const smst_batch *b, int stream, int *up, int *down);
+/* Nr of a clip of inSamples frames of the stream (inSamples itself at 1/1), or a negative code: what a caller derives outSamples from */
+long long smst_batch_resampled_length(const smst_batch *b, int stream, long long inSamples);
+/* the reduced ratio toRate/fromRate of two integer-valued rates; SMST_ERR_INVALID with a message where a rate is not a positive integer or
+ * the ratio misses a limit above.  Either pointer may be null */
+int smst_resample_ratio(double fromRate, double toRate, int *up, int *down);
+/* test hook: the library's table of a ratio, out [L][T] phase-major (L, T of the REDUCED ratio; out may be null), *taps = T */
+int smst_debug_resample_taps(int up, int down, float *out, int *taps);
+/* test hook: the resample kernel alone, planar fp32 to planar fp32.  counts: [streams] N; ratios: [streams][2] up, down (1/1: the stream's
+ * rows of `out` are left alone); image: each stream's clip from column 0 of its rows; segments: [streams][2][4] as smst_debug_clip_copy's,
+ * the DESTINATION of the stream's Nr frames (dst and count of the two segments; the counts add up to Nr).  Host pointers, staged whole as
+ * far behind a 16-byte boundary as the caller's; what the kernel leaves alone in `out` comes back as it was */
+int smst_debug_clip_resample(int device, int streams, int channels, const int *counts, const int *ratios,
+                             const float *image, long long imageStreamStride, long long imageChannelStride,
+                             const int *segments, float *out, long long outStreamStride, long long outChannelStride);
 /* per stream, since the last take: peaks[s] = the largest |v| the levelled output conversions met BEFORE the gain (0 if none); gains[s] = the
  * gain the newest levelled conversion of stream s applied (1 before any).  Either may be null.  Synchronises the batch; resets the peaks,
  * not the gains. */

@@ -10,6 +10,7 @@ The directory name contains a hyphen (it follows the reference project's name), 
     import importlib; smst = importlib.import_module("signalsmith-stretch_amd")
 """
 import ctypes as C
+import math
 import os
 
 import numpy as np
@@ -29,7 +30,8 @@ PCM_S16, PCM_F32, PCM_S24, PCM_S32, PCM_F16 = 1, 2, 4, 5, 6  # frame formats of 
 DITHER_NONE, DITHER_TPDF, DITHER_TPDF_HP = 0, 1, 2           # dither of the int16 / int24 output (StretchBatch.setPcmDither)
 LEVEL_FIXED, LEVEL_PROTECT, LEVEL_NORMALISE = 0, 1, 2        # level of the frame output (StretchBatch.set_pcm_level)
 LEVEL_LOUDNESS = 3                                           # ... to a LUFS target (StretchBatch.set_pcm_loudness)
-LOUDNESS_RANGE_TILE = 256                                    # short-term powers the range stage's workgroup takes at a time (SMST_LOUDNESS_RANGE_TILE)
+RESAMPLE_MAX_TERM, RESAMPLE_MAX_RATIOS, RESAMPLE_TILE = 640, 8, 1024   # the limits of a resample ratio, and the frames a workgroup forms (SMST_RESAMPLE_*)
+LOUDNESS_RANGE_TILE = 256                                   # short-term powers the range stage's workgroup takes at a time (SMST_LOUDNESS_RANGE_TILE)
 LOUDNESS_CHUNK = 256                                         # frames one lane of the loudness passes filters (SMST_LOUDNESS_CHUNK)
 TRUE_PEAK_TILE = 1024                                        # frames one workgroup of the true-peak pass measures (SMST_TRUE_PEAK_TILE)
 LIMITER_TILE, LIMITER_MAX_LOOKAHEAD, LIMITER_DEFAULT_LOOKAHEAD = 1024, 1024, 72  # frames one workgroup of the limiter's passes takes; the lookahead's bound and default (SMST_LIMITER_*)
@@ -160,6 +162,12 @@ _SIGNATURES = {
     "smst_batch_pcm_loudness_caps": (C.c_int, [C.c_void_p, C.c_int, _dp, _dp]),
     "smst_batch_take_pcm_loudness_range": (C.c_int, [C.c_void_p, _dp, _dp, _dp, _dp, _dp, _ip, _ip]),
     "smst_debug_clip_loudness_range": (C.c_int, [C.c_int, C.c_int, C.c_int, _ip, C.c_void_p, _ll, _ll, _dp, _fp, C.c_double, _dp, _dp, _dp, _dp, _dp, _ip, _ip, _fp, _dp, C.c_int]),
+    "smst_batch_set_pcm_resample": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
+    "smst_batch_pcm_resample": (C.c_int, [C.c_void_p, C.c_int, _ip, _ip]),
+    "smst_batch_resampled_length": (_ll, [C.c_void_p, C.c_int, _ll]),
+    "smst_resample_ratio": (C.c_int, [C.c_double, C.c_double, _ip, _ip]),
+    "smst_debug_resample_taps": (C.c_int, [C.c_int, C.c_int, _fp, _ip]),
+    "smst_debug_clip_resample": (C.c_int, [C.c_int, C.c_int, C.c_int, _ip, _ip, C.c_void_p, _ll, _ll, _ip, C.c_void_p, _ll, _ll]),
     "smst_batch_synchronize": (C.c_int, [C.c_void_p]),
     "smst_batch_hip_stream": (C.c_void_p, [C.c_void_p]),
     "smst_batch_enable_profiling": (C.c_int, [C.c_void_p, C.c_int]),
@@ -398,6 +406,40 @@ def debug_limiter_window(lookahead, lib=None):
     win = np.zeros(2*int(lookahead) + 1, np.float32)
     _check(lib, lib.smst_debug_limiter_window(int(lookahead), win.ctypes.data_as(_fp)))
     return win
+
+
+def resample_ratio(from_rate, to_rate, lib=None):
+    """smst_resample_ratio -> (up, down): the reduced ratio to_rate/from_rate of two integer-valued sample rates"""
+    lib = lib if lib is not None else load_library()
+    up, down = C.c_int(0), C.c_int(0)
+    _check(lib, lib.smst_resample_ratio(float(from_rate), float(to_rate), C.byref(up), C.byref(down)))
+    return up.value, down.value
+
+
+def debug_resample_taps(up, down, lib=None):
+    """smst_debug_resample_taps -> float32 [L, T]: the library's table of the (reduced) ratio up/down, phase-major"""
+    lib = lib if lib is not None else load_library()
+    g = math.gcd(int(up), int(down)) if int(up) > 0 and int(down) > 0 else 1
+    taps = C.c_int(0)
+    _check(lib, lib.smst_debug_resample_taps(int(up), int(down), None, C.byref(taps)))
+    table = np.zeros((int(up)//g, taps.value), np.float32)
+    _check(lib, lib.smst_debug_resample_taps(int(up), int(down), table.ctypes.data_as(_fp), C.byref(taps)))
+    return table
+
+
+def debug_clip_resample(counts, ratios, channels, image, image_ss, image_cs, segments, out, out_ss, out_cs, device=0, lib=None):
+    """smst_debug_clip_resample on numpy buffers (planar float32, 1-d views whose first element is the first stream's first row; strides in
+    floats; counts int [S]; ratios int [S, 2]; segments int [S, 2, 4], the destination).  ``out`` is written in place and returned."""
+    lib = lib if lib is not None else load_library()
+    n, r, seg = np.ascontiguousarray(counts, np.int32), np.ascontiguousarray(ratios, np.int32), np.ascontiguousarray(segments, np.int32)
+    S = n.shape[0]
+    assert r.shape == (S, 2) and seg.shape == (S, 2, 4)
+    assert image.dtype == np.float32 and out.dtype == np.float32 and image.ndim == 1 and out.ndim == 1 and image.strides[0] == 4 and out.strides[0] == 4
+    assert image.size >= (S - 1)*image_ss + (channels - 1)*image_cs + int(n.max(initial=0))
+    assert out.size >= (S - 1)*out_ss + (channels - 1)*out_cs + int((seg[:, :, 1] + seg[:, :, 2]).max(initial=0))
+    _check(lib, lib.smst_debug_clip_resample(device, S, channels, n.ctypes.data_as(_ip), r.ctypes.data_as(_ip), C.c_void_p(image.ctypes.data), image_ss, image_cs,
+                                             seg.ctypes.data_as(_ip), C.c_void_p(out.ctypes.data), out_ss, out_cs))
+    return out
 
 
 def launch_count(name, lib=None):
@@ -874,6 +916,24 @@ class StretchBatch:
         return low, frames
 
     # --- test hooks
+    def set_pcm_resample(self, up, down, stream=-1):
+        """Resample in front of exactFrames (include/smst.h, "Resample"): the stream's clips are at down/up of the batch's rate and are
+        resampled on the device, by the ratio up/down, before the engine sees them.  1/1 turns it off; stream = -1: every stream."""
+        _check(self.lib, self.lib.smst_batch_set_pcm_resample(self.h, int(stream), int(up), int(down)))
+
+    def pcm_resample(self, stream):
+        """-> (up, down), the stream's reduced ratio; (1, 1): not resampled"""
+        up, down = C.c_int(0), C.c_int(0)
+        _check(self.lib, self.lib.smst_batch_pcm_resample(self.h, int(stream), C.byref(up), C.byref(down)))
+        return up.value, down.value
+
+    def resampled_length(self, stream, in_samples):
+        """-> Nr = ceil(in_samples*up/down) of the stream's ratio: the clip's length at the batch's rate, what out_samples derives from"""
+        n = int(self.lib.smst_batch_resampled_length(self.h, int(stream), int(in_samples)))
+        if n < 0:
+            _check(self.lib, n)
+        return n
+
     def debug_state(self, stream, which):
         Cn, M = self.channels, self.bands()
         if which == 3:

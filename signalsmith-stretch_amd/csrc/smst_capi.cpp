@@ -885,6 +885,7 @@ static void refuseWholeClipLevel(const smst_batch *b, const unsigned char *activ
 		if ((!active || active[s]) && (b->pcmOut.meter[s].on || b->pcmOut.capped(int(s))))
 			throw smst::Error("stream " + std::to_string(s) + " has the loudness-range meter flag or a loudness cap (smst_batch_set_pcm_loudness_range / _caps), which measure a whole clip: smst_batch_exact_pcm only");
 }
+static void refuseResampled(const Batch &e, const int *takesPart, const char *call); // (below, with the whole-clip calls)
 int smst_batch_process_pcm(smst_batch *b, const void *in, long long iss, long long ifs, const int *inSamples,
                            void *out, long long oss, long long ofs, const int *outSamples, int format, int memory) {
 	BATCH_CALL({
@@ -893,6 +894,7 @@ int smst_batch_process_pcm(smst_batch *b, const void *in, long long iss, long lo
 		checkPcmSide(in, ifs, inSamples, e.streams(), e.channels(), false);
 		checkPcmSide(out, ofs, outSamples, e.streams(), e.channels(), false);
 		refuseWholeClipLevel(b, nullptr);
+		refuseResampled(e, nullptr, "smst_batch_process_pcm");
 		smst_batch::PcmTable &c = beginPcmCall(b);
 		const int maxIn = pcmStageIn(b, c, in, iss, ifs, inSamples, format, memory);
 		const int maxOut = pcmPrepareOut(b, c, outSamples, format, memory);
@@ -906,6 +908,7 @@ int smst_batch_seek_pcm(smst_batch *b, const void *in, long long ss, long long f
 		Batch &e = *b->engine;
 		checkPcmFormat(format, memory);
 		checkPcmSide(in, fs, inSamples, e.streams(), e.channels(), false);
+		refuseResampled(e, nullptr, "smst_batch_seek_pcm");
 		smst_batch::PcmTable &c = beginPcmCall(b);
 		const int maxLen = pcmStageIn(b, c, in, ss, fs, inSamples, format, memory);
 		e.seek(b->dIn, (long long)e.channels()*maxLen, maxLen, inSamples, rates);
@@ -932,6 +935,7 @@ int smst_batch_output_seek_pcm(smst_batch *b, const void *in, long long ss, long
 		Batch &e = *b->engine;
 		checkPcmFormat(format, memory);
 		checkPcmSide(in, fs, inputLengths, e.streams(), e.channels(), false);
+		refuseResampled(e, nullptr, "smst_batch_output_seek_pcm");
 		smst_batch::PcmTable &c = beginPcmCall(b);
 		const int maxLen = pcmStageIn(b, c, in, ss, fs, inputLengths, format, memory);
 		e.outputSeek(b->dIn, (long long)e.channels()*maxLen, maxLen, inputLengths);
@@ -967,12 +971,30 @@ static void runExact(Batch &e, const Batch::ClipIo &io, const int *inSamples, co
 	if (status) for (int s = 0; s < e.streams(); ++s) if (outSamples[s] >= 0) status[s] = tooShort[s] ? SMST_ERR_SHORT : SMST_OK;
 }
 static const char *const kShortMessage = "exact(): input shorter than outputSeekLength";
+// Resample (include/smst.h): only smst_batch_exact_pcm serves a stream's ratio.  Every other call with input refuses, before anything runs, where
+// a stream that takes part (takesPart null: every one; else the streams with a count >= 0) has one -- skipping the stage would be a silent lie
+static void refuseResampled(const Batch &e, const int *takesPart, const char *call) {
+	for (int s = 0; s < e.streams(); ++s)
+		if ((!takesPart || takesPart[s] >= 0) && e.resampled(s))
+			throw smst::Error(std::string(call) + ": stream " + std::to_string(s) + " has a resample ratio other than 1/1 (smst_batch_set_pcm_resample): smst_batch_exact_pcm only");
+}
+// ... and that call refuses a clip whose length at the batch's rate does not fit an int
+static long long resampledLengthChecked(const Batch &e, int s, long long inSamples) {
+	if (inSamples > (1LL << 40)) throw smst::Error("resample: stream " + std::to_string(s) + ": " + std::to_string(inSamples) + " frames resample to more than 2147483647 (the length at the batch's rate must fit an int)");
+	const long long nr = e.resampledLengthOf(s, inSamples);
+	if (nr > 0x7fffffffLL) throw smst::Error("resample: stream " + std::to_string(s) + ": " + std::to_string(inSamples) + " frames resample to " + std::to_string(nr) + ", more than 2147483647 (the length at the batch's rate must fit an int)");
+	return nr;
+}
+static void checkResampledLengths(const Batch &e, const int *inSamples, const int *outSamples) {
+	for (int s = 0; s < e.streams(); ++s) if (outSamples[s] >= 0 && e.resampled(s)) resampledLengthChecked(e, s, inSamples[s]);
+}
 
 int smst_batch_exact(smst_batch *b, const float *in, long long iss, long long ics, const int *inSamples,
                      float *out, long long oss, long long ocs, const int *outSamples, int *status, int memory) {
 	BATCH_CALL({
 		Batch &e = *b->engine;
 		checkExactArgs(e, in, inSamples, out, outSamples, 0, 0, false, memory);
+		refuseResampled(e, outSamples, "smst_batch_exact");
 		if (memory == SMST_MEM_DEVICE) {
 			runExact(e, Batch::ClipIo{in, iss, ics, out, oss, ocs, 0}, inSamples, outSamples, status);
 		} else {
@@ -994,6 +1016,7 @@ int smst_batch_exact_pcm(smst_batch *b, const void *in, long long iss, long long
 		Batch &e = *b->engine;
 		checkPcmFormat(format, memory);
 		checkExactArgs(e, in, inSamples, out, outSamples, ifs, ofs, true, memory);
+		checkResampledLengths(e, inSamples, outSamples);
 		// a dithered call: the streams' modes and hashes ride in the _pcm calls' table (the frame index is the place in the clip: the counters
 		// are neither read nor moved); a levelled call: the level entries ride there too, and the loudness entries and the channel weights
 		smst_batch::PcmTable *table = b->pcmOut.dithers(format) || b->pcmOut.levelled ? &beginPcmCall(b) : nullptr;
@@ -1002,6 +1025,7 @@ int smst_batch_exact_pcm(smst_batch *b, const void *in, long long iss, long long
 		plain.overs = b->pcmOut.dOvers;
 		Batch::ClipIo io{in, iss, ifs, out, oss, ofs, format};
 		b->pcmOut.clipModes(table ? table->out : plain, io);
+		io.resample = true; // (checkResampledLengths above: every Nr fits an int)
 		if (memory == SMST_MEM_DEVICE) {
 			runExact(e, io, inSamples, outSamples, status);
 		} else {
@@ -1017,6 +1041,41 @@ int smst_batch_exact_pcm(smst_batch *b, const void *in, long long iss, long long
 		}
 		if (table) endPcmCall(b);
 	})
+}
+// Resample (include/smst.h): the streams' ratios live in the engine, beside the tables they select
+int smst_batch_set_pcm_resample(smst_batch *b, int stream, int up, int down) { BATCH_CALL(b->engine->setResample(stream, up, down)) }
+int smst_batch_pcm_resample(const smst_batch *b, int stream, int *up, int *down) {
+	BATCH_CALL({
+		int l = 1, m = 1;
+		b->engine->resampleOf(stream, l, m);
+		if (up) *up = l;
+		if (down) *down = m;
+	})
+}
+long long smst_batch_resampled_length(const smst_batch *b, int stream, long long inSamples) {
+	if (!b || !b->engine) return fail("null batch");
+	SMST_TRY
+	if (stream < 0 || stream >= b->engine->streams()) throw smst::Error("stream index out of range");
+	if (inSamples < 0) throw smst::Error("resample: negative sample count");
+	return resampledLengthChecked(*b->engine, stream, inSamples);
+	SMST_CATCH
+}
+int smst_resample_ratio(double fromRate, double toRate, int *up, int *down) {
+	SMST_TRY
+	for (double rate : {fromRate, toRate})
+		if (!(std::isfinite(rate) && rate >= 1 && rate <= 1e9 && rate == std::floor(rate))) throw smst::Error("resample: a sample rate is not a positive integer (at most 1e9)");
+	long long a = (long long)toRate, c = (long long)fromRate, x = a, y = c;
+	while (y) { const long long r = x%y; x = y; y = r; }
+	a /= x; c /= x;
+	if (a > smst::kResampleMaxTerm || c > smst::kResampleMaxTerm)
+		throw smst::Error("resample: " + std::to_string((long long)fromRate) + " -> " + std::to_string((long long)toRate) + " Hz reduces to " + std::to_string(a) + "/" + std::to_string(c) +
+		                  ", a term above " + std::to_string(smst::kResampleMaxTerm) + " (SMST_RESAMPLE_MAX_TERM)");
+	int l = int(a), m = int(c);
+	smst::resampleReduce(l, m);
+	if (up) *up = l;
+	if (down) *down = m;
+	return SMST_OK;
+	SMST_CATCH
 }
 } // extern "C"
 // What the two debug converters are: the launch of one conversion kernel on device copies of the caller's buffers, which sit as far behind a
@@ -1425,6 +1484,71 @@ int smst_debug_true_peak_taps(float *out) {
 	if (!out) return fail("true peak taps: null pointer");
 	std::memcpy(out, smst::truePeakTable().c, sizeof(smst::TruePeakTable));
 	return SMST_OK;
+}
+int smst_debug_resample_taps(int up, int down, float *out, int *taps) {
+	SMST_TRY
+	smst::resampleReduce(up, down);
+	const smst::ResampleShape g = smst::resampleShapeOf(up, down);
+	if (taps) *taps = g.T;
+	if (out) {
+		std::vector<float> table((size_t)g.L*g.pitch);
+		smst::resampleTaps(g, table.data());
+		for (int p = 0; p < g.L; ++p) std::copy(table.begin() + (size_t)p*g.pitch, table.begin() + (size_t)p*g.pitch + g.T, out + (size_t)p*g.T);
+	}
+	return SMST_OK;
+	SMST_CATCH
+}
+// the resample kernel alone: see include/smst.h
+int smst_debug_clip_resample(int device, int streams, int channels, const int *counts, const int *ratios, const float *image, long long imageSS, long long imageCS,
+                             const int *segments, float *out, long long outSS, long long outCS) {
+	SMST_TRY
+	if (streams < 1 || channels < 1 || channels > smst::kMaxChannels || !counts || !ratios || !image || !segments || !out || imageSS < 0 || imageCS < 0 || outSS < 0 || outCS < 0)
+		throw smst::Error("clip resample: bad arguments");
+	auto hip = [&](hipError_t err) { if (err != hipSuccess) throw smst::Error(std::string("clip resample: ") + hipGetErrorString(err), true); };
+	hip(hipSetDevice(device));
+	std::vector<smst::ResampleEntry> entries((size_t)streams, smst::ResampleEntry{nullptr, 0, 0, 0, 0, 0, 0, 0, 0});
+	std::vector<Buffer<float, false>> tables((size_t)streams); // (one per resampled stream: a hook's streams do not share them)
+	int endIn = 0, endOut = 0, most = 0, maxSpanPitch = 4;
+	for (int s = 0; s < streams; ++s) {
+		const int *g = segments + 8*s;
+		int up = ratios[2*s], down = ratios[2*s + 1];
+		smst::resampleReduce(up, down);
+		if (counts[s] < 0) throw smst::Error("clip resample: negative sample count");
+		if (up == 1 && down == 1) continue; // not resampled: its rows of `out` are left alone
+		const long long nr = smst::resampledLength(counts[s], up, down);
+		if (nr > 0x7fffffffLL) throw smst::Error("clip resample: the resampled clip is too long");
+		if (g[1] < 0 || g[2] < 0 || g[5] < 0 || g[6] < 0 || (long long)g[2] + g[6] != nr) throw smst::Error("clip resample: the two segments' counts do not add up to the resampled length");
+		const smst::ResampleShape shape = smst::resampleShapeOf(up, down);
+		std::vector<float> table((size_t)shape.L*shape.pitch);
+		smst::resampleTaps(shape, table.data());
+		tables[s].allocate(table.size(), "clip resample");
+		hip(hipMemcpy(tables[s], table.data(), table.size()*sizeof(float), hipMemcpyHostToDevice));
+		entries[s] = smst::ResampleEntry{tables[s].p, counts[s], int(nr), shape.L, shape.M, shape.H, shape.T, shape.pitch, 0};
+		endIn = std::max(endIn, counts[s]);
+		for (int k = 0; k < 2; ++k) if (g[4*k + 2] > 0) endOut = std::max(endOut, g[4*k + 1] + g[4*k + 2]);
+		most = std::max(most, int(nr));
+		maxSpanPitch = std::max(maxSpanPitch, smst::resampleSpanPitch(shape.L, shape.M, shape.T));
+	}
+	// host pointers are staged whole: every stream's rows, as far behind a 16-byte boundary as the caller's
+	const size_t imageBytes = endIn ? size_t((streams - 1)*imageSS + (channels - 1)*imageCS + endIn)*sizeof(float) : 0;
+	const size_t outBytes = endOut ? size_t((streams - 1)*outSS + (channels - 1)*outCS + endOut)*sizeof(float) : 0;
+	Buffer<unsigned char, false> dImage, dOut, dSegs, dEntries;
+	dImage.allocate(imageBytes + 32, "clip resample");
+	dOut.allocate(outBytes + 32, "clip resample");
+	dSegs.allocate((size_t)2*streams*sizeof(smst::ClipSeg), "clip resample");
+	dEntries.allocate(entries.size()*sizeof(smst::ResampleEntry), "clip resample");
+	unsigned char *i0 = dImage + reinterpret_cast<uintptr_t>(image)%16, *o0 = dOut + reinterpret_cast<uintptr_t>(out)%16;
+	if (imageBytes) hip(hipMemcpy(i0, image, imageBytes, hipMemcpyHostToDevice));
+	if (outBytes) hip(hipMemcpy(o0, out, outBytes, hipMemcpyHostToDevice));
+	hip(hipMemcpy(dSegs, segments, (size_t)2*streams*sizeof(smst::ClipSeg), hipMemcpyHostToDevice));
+	hip(hipMemcpy(dEntries, entries.data(), entries.size()*sizeof(smst::ResampleEntry), hipMemcpyHostToDevice));
+	smst::launchClipResample(reinterpret_cast<const float *>(i0), imageSS, imageCS, reinterpret_cast<float *>(o0), outSS, outCS, reinterpret_cast<const smst::ClipSeg *>(dSegs.p),
+	                         reinterpret_cast<const smst::ResampleEntry *>(dEntries.p), streams, channels, most, maxSpanPitch, nullptr);
+	hip(hipGetLastError());
+	hip(hipStreamSynchronize(nullptr));
+	if (outBytes) hip(hipMemcpy(out, o0, outBytes, hipMemcpyDeviceToHost));
+	return SMST_OK;
+	SMST_CATCH
 }
 int smst_batch_take_pcm_overs(smst_batch *b, long long *clamped, long long *nans) {
 	BATCH_CALL({

@@ -169,7 +169,7 @@ __host__ __device__ inline bool analysisWindowInCall(int B, int M, int I, int in
 // form" tests assert through these that BOTH forms really ran.
 enum LaunchKind {
 	LK_VOC_ALIGNED, LK_VOC_TWISTED, LK_VOC_INTERIOR, LK_VOC_STAGED, LK_VOC_GATHER, LK_VOC_N, LK_VOC_ONE, LK_VOC_ACROSS, LK_VOC_CONT, LK_CHAIN_UNFUSED,
-	LK_ANALYSE_TEAMS, LK_ANALYSE_PAIRS, LK_ANALYSE_TWIST, LK_TWIST_ROWS, LK_ANALYSE_FAST, LK_ANALYSE_GENERIC, LK_SYNTH_TEAMS, LK_SYNTH_FAST, LK_SYNTH_GENERIC, LK_SYNTH_EMIT, LK_EMIT_CARRIED, LK_FEED_ONE_PASS, LK_PCM_IN, LK_PCM_OUT, LK_CLIP_IN, LK_CLIP_OUT, LK_PCM_OUT_DITHERED, LK_CLIP_OUT_DITHERED, LK_PCM_OUT_LEVELLED, LK_CLIP_OUT_LEVELLED, LK_CLIP_PEAK, LK_CLIP_LOUDNESS, LK_CLIP_TRUE_PEAK, LK_CLIP_LIMIT_NEED, LK_CLIP_LIMIT_GAIN, LK_CLIP_OUT_LIMITED, LK_CLIP_LOUDNESS_RANGE, LK_COUNT
+	LK_ANALYSE_TEAMS, LK_ANALYSE_PAIRS, LK_ANALYSE_TWIST, LK_TWIST_ROWS, LK_ANALYSE_FAST, LK_ANALYSE_GENERIC, LK_SYNTH_TEAMS, LK_SYNTH_FAST, LK_SYNTH_GENERIC, LK_SYNTH_EMIT, LK_EMIT_CARRIED, LK_FEED_ONE_PASS, LK_PCM_IN, LK_PCM_OUT, LK_CLIP_IN, LK_CLIP_OUT, LK_PCM_OUT_DITHERED, LK_CLIP_OUT_DITHERED, LK_PCM_OUT_LEVELLED, LK_CLIP_OUT_LEVELLED, LK_CLIP_PEAK, LK_CLIP_LOUDNESS, LK_CLIP_TRUE_PEAK, LK_CLIP_LIMIT_NEED, LK_CLIP_LIMIT_GAIN, LK_CLIP_OUT_LIMITED, LK_CLIP_LOUDNESS_RANGE, LK_CLIP_RESAMPLE, LK_COUNT
 };
 long long launchCount(const char *name); // -1: unknown name
 
@@ -325,5 +325,37 @@ constexpr int kLimitMaxLookahead = 1024, kLimitDefaultLookahead = 72;
 void limitWindow(int H, float *win);            // win[k + H] = float32(h_k/sum h), k = -H ... H: in double, one rounding
 void launchClipLimit(const float *image, long long imageStreamStride, long long imageChannelStride, const ClipSeg *segs, int S, int C, int maxFrames,
                      const PcmLevelIo &level, int H, const float *window, float *need, float *r, long long pitch, int *meters, hipStream_t st);
+// Sample-rate conversion of whole clips in front of the engine (include/smst.h, "Resample", has the definition; smst_resample.h the kernel).
+// A ratio L/M, reduced, the batch's rate over the clip's: N frames become Nr = ceil(N*L/M), frame n at input position n*M/L, formed by the T = 2H
+// taps of its phase's row of a Kaiser-windowed sinc in float64, rounded once.  ResampleShape: what a ratio fixes -- H, T and the pitch of a
+// row of its table ([L][pitch] floats, T rounded up to a multiple of 4, the padding 0.0); resampleTaps fills such a table (host, in double).
+// ResampleEntry: one per stream, device -- L == 0: the stream is not resampled, the kernel leaves its rows alone.
+// The kernel reads a raw image in which each resampled stream's clip lies from column 0 of its rows and writes resampled frame n where the
+// stream's two segments put it (their counts add up to Nr; src is not read).  maxFrames: the largest Nr (sizes the grid; nothing is
+// launched for 0); maxSpanPitch: the largest resampleSpanPitch of the launch's entries (sizes the LDS)
+constexpr int kResampleTile = 1024;                      // resampled frames of a stream that one workgroup forms
+constexpr int kResampleMaxTerm = 640, kResampleMaxRatios = 8;
+constexpr int kResampleLdsFloats = 15360;                // 60 KB: the most a launch asks for
+struct ResampleShape { int L, M, H, T, pitch; };
+inline ResampleShape resampleShapeOf(int L, int M) { // (reduced, within the limits)
+	ResampleShape g{L, M, 32, 64, 64};
+	if (M > L) g.H = (32*M + L - 1)/L;
+	g.T = 2*g.H;
+	g.pitch = (g.T + 3)/4*4;
+	return g;
+}
+struct ResampleEntry { const float *taps; int N, Nr, L, M, H, T, pitch, pad; };
+// floats of one channel's LDS image of a tile: the span, at most ceil((kResampleTile - 1)*M/L) + T, in whole 16-byte words
+inline __host__ __device__ int resampleSpanPitch(int L, int M, int T) { return (((kResampleTile - 1)*M + L - 1)/L + T + 3)/4*4; }
+// ... and of a launch: up to 4 channels side by side where they fit the most a launch asks for, at least one
+inline int resampleLdsFloats(int C, int maxSpanPitch) {
+	int group = C < 4 ? C : 4;
+	while (group > 1 && group*maxSpanPitch > kResampleLdsFloats) --group;
+	return group*maxSpanPitch;
+}
+inline long long resampledLength(long long N, int L, int M) { return (N*L + M - 1)/M; }
+void resampleTaps(const ResampleShape &g, float *out);
+void launchClipResample(const float *raw, long long rawStreamStride, long long rawChannelStride, float *image, long long imageStreamStride, long long imageChannelStride,
+                        const ClipSeg *segs, const ResampleEntry *entries, int S, int C, int maxFrames, int maxSpanPitch, hipStream_t st);
 
 } // namespace smst

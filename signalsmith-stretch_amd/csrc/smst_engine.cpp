@@ -420,7 +420,8 @@ void Batch::allocateCallTables() {
 	dOutSamples = callSets.sets[0].outSamples;
 	dFlags = callSets.sets[0].flags;
 	for (std::vector<int> *v : {&flushV.blockOut, &flushV.blockIn, &flushV.synthChannels, &outputSeekV.seekSamples, &outputSeekV.surplus, &outputSeekV.preOut, &outputSeekV.done,
-	                            &exactV.seekLen, &exactV.rest, &exactV.procOut, &exactV.flushN}) v->assign(S, 0);
+	                            &exactV.seekLen, &exactV.rest, &exactV.procOut, &exactV.flushN, &exactV.frames}) v->assign(S, 0);
+	resampleSlot.assign(S, -1);
 	for (std::vector<unsigned char> *v : {&flushV.runBlock, &flushV.on, &outputSeekV.mask, &exactV.run}) v->assign(S, 0);
 	outputSeekV.rates.assign(S, 1.0);
 	exactV.rates.assign(S, 0.0f);
@@ -1776,22 +1777,28 @@ void Batch::exact(const ClipIo &io, const int *inSamples, const int *outSamples,
 	}
 	clipSets.create();
 	ClipSet &cs = clipSets.begin(); // (the call before the previous one: its clip kernels must have read the tables)
-	std::vector<int> &seekLen = exactV.seekLen, &rest = exactV.rest, &procOut = exactV.procOut, &flushN = exactV.flushN;
+	std::vector<int> &seekLen = exactV.seekLen, &rest = exactV.rest, &procOut = exactV.procOut, &flushN = exactV.flushN, &frames = exactV.frames;
 	std::vector<float> &rates = exactV.rates;
 	std::vector<unsigned char> &run = exactV.run;
 	int maxSeek = 0, maxRest = 0, maxProc = 0, maxFlush = 0, maxZeros = 0;
+	int maxRaw = 0, maxResampled = 0, maxPlainSeek = 0, maxPlainRest = 0; // the resampled streams that run: their longest clip, before and behind; the others' longest segments
 	bool anyRun = false;
 	for (int s = 0; s < S; ++s) {
 		seekLen[s] = rest[s] = procOut[s] = flushN[s] = run[s] = 0;
 		rates[s] = 0.0f;
+		frames[s] = 0;
 		if (outSamples[s] < 0) continue;
-		ExactLengths l = exactLengths(inSamples[s], outSamples[s]);
+		// (a resampled stream behaves exactly as if the caller had handed over its Nr frames; the caller has checked that Nr fits an int)
+		frames[s] = io.resample && resampled(s) ? int(resampledLengthOf(s, inSamples[s])) : inSamples[s];
+		ExactLengths l = exactLengths(frames[s], outSamples[s]);
 		if (l.tooShort) { maxZeros = std::max(maxZeros, outSamples[s]); continue; }
 		l.outputIndex = std::min(std::max(l.outputIndex, 0), outSamples[s]); // (seekLength/rate <= outSamples[s] but for its rounding: the two output parts stay inside the stream's count)
 		run[s] = 1;
 		anyRun = true;
 		rates[s] = l.rate;
-		seekLen[s] = l.seekLength; rest[s] = inSamples[s] - l.seekLength;
+		seekLen[s] = l.seekLength; rest[s] = frames[s] - l.seekLength;
+		if (io.resample && resampled(s)) { maxRaw = std::max(maxRaw, inSamples[s]); maxResampled = std::max(maxResampled, frames[s]); }
+		else { maxPlainSeek = std::max(maxPlainSeek, seekLen[s]); maxPlainRest = std::max(maxPlainRest, rest[s]); }
 		procOut[s] = l.outputIndex; flushN[s] = outSamples[s] - l.outputIndex;
 		maxSeek = std::max(maxSeek, seekLen[s]); maxRest = std::max(maxRest, rest[s]);
 		maxProc = std::max(maxProc, procOut[s]); maxFlush = std::max(maxFlush, flushN[s]);
@@ -1816,9 +1823,48 @@ void Batch::exact(const ClipIo &io, const int *inSamples, const int *outSamples,
 			segOut[2*s] = ClipSeg{0, 0, outSamples[s], 1}; // too short: zeros, and the stream's state stays as it is
 		}
 	}
-	SMST_HIP(hipMemcpyAsync(cs.dev, cs.host, (size_t)4*S*sizeof(ClipSeg), hipMemcpyHostToDevice, st));
 	const long long inImgSS = (long long)C*pitchIn, outImgSS = (long long)C*pitchOut;
-	launchClipIn(io.format, io.in, io.inStreamStride, io.inInnerStride, dClipIn, inImgSS, pitchIn, cs.dev, S, C, std::max(direct ? 0 : maxSeek, maxRest), st);
+	if (maxResampled > 0) {
+		// The resampled streams: kClipIn moves their whole clips into the raw image -- a second segment table, one whole-clip segment per
+		// stream -- and leaves them out of the input image, which kClipResample fills where the call's two input segments put their frames
+		if (direct) throw Error("exact: a resampled stream in a planar call");
+		const ResampleTableLayout at(S);
+		for (ClipSet &t : clipSets.sets) { // (both sets with the first such call)
+			if (t.resHost) continue;
+			t.resHost = pinnedAlloc<unsigned char>(at.bytes());
+			t.resDev = devAlloc<unsigned char>(at.bytes());
+			wsBytes += at.bytes();
+		}
+		const int pitchRaw = up4(maxRaw);
+		const size_t needRaw = (size_t)S*C*pitchRaw;
+		growScratch(dClipRaw, clipRawCapacity, needRaw, needRaw/8 + 1024, true);
+		int maxSpanPitch = 4;
+		for (int s = 0; s < S; ++s) {
+			const ClipSeg none{0, 0, 0, 0};
+			ResampleEntry e{nullptr, 0, 0, 0, 0, 0, 0, 0, 0};
+			at.rawSegs(cs.resHost)[2*s] = at.rawSegs(cs.resHost)[2*s + 1] = at.dstSegs(cs.resHost)[2*s] = at.dstSegs(cs.resHost)[2*s + 1] = none;
+			if (run[s] && resampled(s)) {
+				const ResampleSlot &slot = resampleSlots[resampleSlot[s]];
+				const ResampleShape &g = slot.shape;
+				e = ResampleEntry{slot.taps, inSamples[s], frames[s], g.L, g.M, g.H, g.T, g.pitch, 0};
+				maxSpanPitch = std::max(maxSpanPitch, resampleSpanPitch(g.L, g.M, g.T));
+				at.rawSegs(cs.resHost)[2*s] = ClipSeg{0, 0, inSamples[s], 0};
+				at.dstSegs(cs.resHost)[2*s] = segIn[2*s];
+				at.dstSegs(cs.resHost)[2*s + 1] = segIn[2*s + 1];
+				segIn[2*s] = segIn[2*s + 1] = none;
+			}
+			at.entries(cs.resHost)[s] = e;
+		}
+		SMST_HIP(hipMemcpyAsync(cs.dev, cs.host, (size_t)4*S*sizeof(ClipSeg), hipMemcpyHostToDevice, st));
+		SMST_HIP(hipMemcpyAsync(cs.resDev, cs.resHost, at.bytes(), hipMemcpyHostToDevice, st));
+		const long long rawSS = (long long)C*pitchRaw;
+		launchClipIn(io.format, io.in, io.inStreamStride, io.inInnerStride, dClipRaw, rawSS, pitchRaw, at.rawSegs(cs.resDev), S, C, maxRaw, st);
+		launchClipIn(io.format, io.in, io.inStreamStride, io.inInnerStride, dClipIn, inImgSS, pitchIn, cs.dev, S, C, std::max(maxPlainSeek, maxPlainRest), st);
+		launchClipResample(dClipRaw, rawSS, pitchRaw, dClipIn, inImgSS, pitchIn, at.dstSegs(cs.resDev), at.entries(cs.resDev), S, C, maxResampled, maxSpanPitch, st);
+	} else {
+		SMST_HIP(hipMemcpyAsync(cs.dev, cs.host, (size_t)4*S*sizeof(ClipSeg), hipMemcpyHostToDevice, st));
+		launchClipIn(io.format, io.in, io.inStreamStride, io.inInnerStride, dClipIn, inImgSS, pitchIn, cs.dev, S, C, std::max(direct ? 0 : maxSeek, maxRest), st);
+	}
 	// the engine reads its input on more than one stream (the silence gate on its own): the edge a caller's producer stream gets
 	waitForStream(st);
 	if (anyRun) {
@@ -1934,6 +1980,76 @@ void Batch::prepareLimiter() {
 	limitWindow(limitH, win.data());
 	SMST_HIP(hipStreamSynchronize(st)); // (a call in flight reads the window it was issued with)
 	SMST_HIP(hipMemcpy(dLimitWin, win.data(), win.size()*sizeof(float), hipMemcpyHostToDevice));
+}
+
+// the reduced ratio, checked against the limits of include/smst.h, "Resample" (also smst_resample_ratio's check)
+void resampleReduce(int &up, int &down) {
+	const std::string limit = std::to_string(kResampleMaxTerm);
+	if (up < 1 || down < 1) throw Error("resample: the ratio " + std::to_string(up) + "/" + std::to_string(down) + " has a term below 1 (both are 1 ... " + limit + ")");
+	int a = up, b = down;
+	while (b) { const int r = a%b; a = b; b = r; }
+	up /= a; down /= a;
+	if (up > kResampleMaxTerm || down > kResampleMaxTerm)
+		throw Error("resample: the reduced ratio " + std::to_string(up) + "/" + std::to_string(down) + " has a term above " + limit + " (SMST_RESAMPLE_MAX_TERM)");
+	if (2LL*down > 9LL*up)
+		throw Error("resample: the ratio " + std::to_string(up) + "/" + std::to_string(down) + " downsamples by more than 4.5 (2*down <= 9*up)");
+	if (2LL*up > 9LL*down)
+		throw Error("resample: the ratio " + std::to_string(up) + "/" + std::to_string(down) + " upsamples by more than 4.5 (2*up <= 9*down)");
+}
+
+void Batch::setResample(int stream, int up, int down) {
+	if (stream < -1 || stream >= S) throw Error("stream index out of range");
+	resampleReduce(up, down);
+	SMST_HIP(hipSetDevice(dev));
+	const bool none = up == 1 && down == 1;
+	const int first = stream < 0 ? 0 : stream, last = stream < 0 ? S : stream + 1;
+	// the slot the ratio has or takes, once the streams named have dropped theirs: refused, before anything changes, where there would be a ninth
+	int target = -1;
+	if (!none) {
+		int users[kResampleMaxRatios];
+		for (int k = 0; k < kResampleMaxRatios; ++k) users[k] = resampleSlots[k].users;
+		for (int s = first; s < last; ++s) if (resampleSlot[s] >= 0) --users[resampleSlot[s]];
+		for (int k = 0; k < kResampleMaxRatios && target < 0; ++k) if (resampleSlots[k].taps && resampleSlots[k].shape.L == up && resampleSlots[k].shape.M == down) target = k;
+		for (int k = 0; k < kResampleMaxRatios && target < 0; ++k) if (users[k] == 0) target = k;
+		if (target < 0) throw Error("resample: " + std::to_string(up) + "/" + std::to_string(down) + " would be distinct ratio number " + std::to_string(kResampleMaxRatios + 1) +
+		                            " of the batch, at most " + std::to_string(kResampleMaxRatios) + " are live at a time (SMST_RESAMPLE_MAX_RATIOS)");
+	}
+	for (int s = first; s < last; ++s) if (resampleSlot[s] >= 0) { --resampleSlots[resampleSlot[s]].users; resampleSlot[s] = -1; }
+	bool synced = false;
+	for (int k = 0; k < kResampleMaxRatios; ++k) { // a ratio that no stream has any more frees its slot (but the one that is about to be taken again)
+		ResampleSlot &slot = resampleSlots[k];
+		if (!slot.taps || slot.users > 0 || (k == target && slot.shape.L == up && slot.shape.M == down)) continue;
+		if (!synced) SMST_HIP(hipStreamSynchronize(st)); // (a call in flight reads the table it was issued with)
+		synced = true;
+		wsBytes -= (size_t)slot.shape.L*slot.shape.pitch*sizeof(float);
+		devFree(slot.taps);
+		slot = ResampleSlot();
+	}
+	if (none) return;
+	ResampleSlot &slot = resampleSlots[target];
+	if (!slot.taps) { // the first stream with this ratio: the table, built in double and put into device memory here, not in a call
+		const ResampleShape g = resampleShapeOf(up, down);
+		std::vector<float> taps((size_t)g.L*g.pitch);
+		resampleTaps(g, taps.data());
+		slot.taps = devAlloc<float>(taps.size());
+		slot.shape = g;
+		wsBytes += taps.size()*sizeof(float);
+		SMST_HIP(hipMemcpy(slot.taps, taps.data(), taps.size()*sizeof(float), hipMemcpyHostToDevice));
+	}
+	for (int s = first; s < last; ++s) { resampleSlot[s] = target; ++slot.users; }
+}
+
+void Batch::resampleOf(int stream, int &up, int &down) const {
+	if (stream < 0 || stream >= S) throw Error("stream index out of range");
+	up = down = 1;
+	if (resampleSlot[stream] >= 0) { up = resampleSlots[resampleSlot[stream]].shape.L; down = resampleSlots[resampleSlot[stream]].shape.M; }
+}
+
+long long Batch::resampledLengthOf(int stream, long long inSamples) const {
+	if (stream < 0 || stream >= S) throw Error("stream index out of range");
+	if (resampleSlot[stream] < 0 || inSamples < 0) return inSamples;
+	const ResampleShape &g = resampleSlots[resampleSlot[stream]].shape;
+	return resampledLength(inSamples, g.L, g.M);
 }
 
 bool Batch::readLimiter(float *minGain, long long *limitedFrames) {

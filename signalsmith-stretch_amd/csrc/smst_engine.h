@@ -118,8 +118,17 @@ public:
 		PcmOutCall pcm; const unsigned char *wholeClip = nullptr; const int *loudHop = nullptr; const unsigned char *truePeak = nullptr;
 		const unsigned char *loudMeter = nullptr;  // (host, [S]; null where no stream is metered: the streams whose loudness entry has the meter flag -- loudHop has their
 		                                           // h whatever their mode, and if one of them runs, kLoudRange (smst_loudness_range.h) does behind the four passes)
-		const unsigned char *limiter = nullptr; }; // (host, [S]; null where no stream is limited: the streams whose level entry pcmLimited() names -- if one
+		const unsigned char *limiter = nullptr;    // (host, [S]; null where no stream is limited: the streams whose level entry pcmLimited() names -- if one
 		                                           // of them runs, the two passes of smst_limiter.h do, and kClipOut takes their r from the engine's scratch)
+		bool resample = false; };                  // (the call serves the streams' ratios, a frame format only: inSamples[s] of a stream that has one counts frames at the
+		                                           // clip's rate, and kClipResample (smst_resample.h) forms its Nr frames in front of the stages; false: the caller has refused them)
+	// Resample (include/smst.h, "Resample"): a stream's ratio up/down, the batch's rate over its clips' rate; 1/1: none.  setResample reduces
+	// and checks the ratio (Error with the limit in its message) and, for the first stream that takes a ratio, builds the ratio's table and puts
+	// it into device memory -- never in a call; a ratio that no stream has any more frees its table.  stream -1: every stream
+	void setResample(int stream, int up, int down);
+	bool resampled(int stream) const { return resampleSlot[stream] >= 0; }
+	void resampleOf(int stream, int &up, int &down) const;
+	long long resampledLengthOf(int stream, long long inSamples) const; // Nr of a clip of the stream (inSamples itself where it has no ratio)
 	// The limiter's lookahead H in frames (include/smst.h, "Limiter"), 1 ... kLimitMaxLookahead, the batch's one.  prepareLimiter() puts the
 	// window of the current H into device memory (the first call allocates it); setLimiterLookahead() does so again where it is there already.
 	// Neither runs in an exact call.  readLimiter: the meters of the newest exact call that limited, [S] each (1 and 0: a stream it did not
@@ -231,7 +240,7 @@ private:
 	// ... and of the whole-call stages, [S] each: a stage's own, never shared (exact() hands its own down to outputSeek(), process() and flush())
 	struct FlushScratch { std::vector<int> blockOut, blockIn, synthChannels; std::vector<unsigned char> runBlock, on; } flushV;
 	struct OutputSeekScratch { std::vector<int> seekSamples, surplus, preOut, done; std::vector<double> rates; std::vector<unsigned char> mask; } outputSeekV;
-	struct ExactScratch { std::vector<int> seekLen, rest, procOut, flushN; std::vector<float> rates; std::vector<unsigned char> run; } exactV;
+	struct ExactScratch { std::vector<int> seekLen, rest, procOut, flushN, frames; std::vector<float> rates; std::vector<unsigned char> run; } exactV; // (frames: a clip's length at the batch's rate)
 	long allocEvents = 0; // device allocations + pinned allocations + host table growth since construction
 	size_t wsBytes = 0;
 	DevBatch d{};
@@ -328,8 +337,16 @@ private:
 	float *dLimit = nullptr, *dLimitWin = nullptr;
 	size_t limitCapacity = 0;
 	int limitH = kLimitDefaultLookahead;
-	struct ClipSet { ClipSeg *host, *dev; }; // [2][S][2]: input segments, output segments
+	// resHost / resDev: the table of a call with a resampled stream (ResampleTableLayout), allocated by the first such call
+	struct ClipSet { ClipSeg *host, *dev; unsigned char *resHost, *resDev; }; // [2][S][2]: input segments, output segments
 	TwoSets<ClipSet> clipSets;
+	// Resample: the raw image of the resampled streams' clips ([S][C][pitch], grown on demand as the images are); the ratios' tables, each
+	// [L][pitch] floats in device memory from the first stream that takes the ratio to the last that drops it; every stream's slot (-1: none)
+	float *dClipRaw = nullptr;
+	size_t clipRawCapacity = 0;
+	struct ResampleSlot { ResampleShape shape{0, 0, 0, 0, 0}; float *taps = nullptr; int users = 0; };
+	ResampleSlot resampleSlots[kResampleMaxRatios];
+	std::vector<int> resampleSlot;
 	// a device scratch that holds `need` floats, allocated with `room` more; true: it was replaced (the old one freed behind a synchronise).  workspace: counted in workspaceBytes()
 	bool growScratch(float *&scratch, size_t &capacity, size_t need, size_t room, bool workspace);
 	StreamParams *dParams = nullptr, *hParams = nullptr; // (hParams: pinned staging of uploadParams())
@@ -389,5 +406,8 @@ struct Error : std::exception {
 	explicit Error(std::string m, bool deviceError = false) : msg(std::move(m)), device(deviceError) {}
 	const char *what() const noexcept override { return msg.c_str(); }
 };
+
+// up/down reduced by their gcd, then checked against the limits of include/smst.h, "Resample"; Error, the limit in its message, where one is missed
+void resampleReduce(int &up, int &down);
 
 } // namespace smst

@@ -12,6 +12,7 @@
 //                  applied, the clip peaks of the newest exact call (kClipPeak's; stream-ordered, so one set serves calls in flight)
 // PcmDebugBlock    what a levelled debug hook uploads in front of its launch: the table's dither and level sections, then the meter words
 // PcmOutCall       where one call's output conversion finds all of that on the device
+// ResampleTableLayout  the table a whole-clip call with a resampled stream adds on the input side (the engine's; two sets as the above)
 #pragma once
 #include "smst_device.h"
 #include <cstddef>
@@ -65,6 +66,24 @@ static_assert(sizeof(PcmDither) == 16 && sizeof(PcmLevel) == 16, "the table's en
 static_assert(alignof(PcmDither) <= sizeof(int) && alignof(PcmLevel) <= sizeof(int) && alignof(float) <= sizeof(int), "counts in front of entries of 4-byte members");
 static_assert(alignof(LoudEntry) <= 16 && (2*sizeof(int) + sizeof(PcmDither) + sizeof(PcmLevel)) % alignof(LoudEntry) == 0, "the loudness entries' doubles are 8-byte aligned");
 static_assert(sizeof(LoudEntry) % alignof(float) == 0 && sizeof(LoudEntry) % sizeof(int) == 0, "the channel weights are aligned, and the table is whole ints");
+
+// ResampleTableLayout: what a whole-clip call with a resampled stream adds (include/smst.h, "Resample"), a table of its own beside the one
+// above -- pinned host staging with a device twin, as that one, and uploaded in ONE copy.  Three sections of a batch of S streams, in order:
+//   rawSegs  [S][2] ClipSeg        kClipIn's segments into the raw image: a resampled stream's whole clip, N frames from frame 0 to column 0
+//   dstSegs  [S][2] ClipSeg        where kClipResample puts the stream's Nr frames in the input image: the call's two input segments
+//   entries  [S]    ResampleEntry  N, Nr, the reduced ratio, its shape and where its table lies in device memory (L == 0: not resampled)
+struct ResampleTableLayout {
+	size_t S;
+	explicit ResampleTableLayout(int streams) : S(size_t(streams)) {}
+	size_t rawSegs() const { return 0; }
+	size_t dstSegs() const { return rawSegs() + 2*S*sizeof(ClipSeg); }
+	size_t entries() const { return dstSegs() + 2*S*sizeof(ClipSeg); }
+	size_t bytes() const { return entries() + S*sizeof(ResampleEntry); }
+	ClipSeg *rawSegs(void *base) const { return pcmTableAt<ClipSeg>(base, rawSegs()); }
+	ClipSeg *dstSegs(void *base) const { return pcmTableAt<ClipSeg>(base, dstSegs()); }
+	ResampleEntry *entries(void *base) const { return pcmTableAt<ResampleEntry>(base, entries()); }
+};
+static_assert(sizeof(ClipSeg) == 16 && alignof(ResampleEntry) <= 16, "the entries begin on a 16-byte boundary where the table does");
 
 struct PcmMeters {
 	size_t S;

@@ -16,6 +16,9 @@ the host from its first entry point to the return of smst_batch_synchronize.
                                                   # the true-peak pass
   python tools/bench_exact.py --mode protect --limit        # PROTECT (at --limit-gain, so that the ceiling bites) without and with the limiter flag
                                                   # alternating: limit - protect = the limiter's two passes and the limited copy's extra read
+  python tools/bench_exact.py --mode pcm --resample=160/147   # pcm without and with that resample ratio on every stream alternating, the resampled
+                                                  # batch's clips as long as resample to the plain batch's input length: resample - pcm = the raw
+                                                  # image's copy and kClipResample
   python tools/bench_exact.py --mode normalise --loudness --loudness-range   # ... and LOUDNESS with the meter flag: loudness_range - loudness =
                                                   # the range stage (kLoudRange) behind the four passes
 """
@@ -44,6 +47,8 @@ def main():
     ap.add_argument("--true-peak", action="store_true", help="frame modes: a batch with the mode's own level setting and the true-peak flag on every stream beside the mode's own")
     ap.add_argument("--limit", action="store_true", help="frame modes protect / normalise: a batch with the mode's own level setting and the limiter flag on every stream beside the mode's own")
     ap.add_argument("--loudness-range", action="store_true", help="frame modes: a batch in LEVEL_LOUDNESS with the loudness-range meter flag on every stream beside the mode's own")
+    ap.add_argument("--resample", default=None, metavar="UP/DOWN", help="frame modes: a batch whose streams all carry this resample ratio, fed clips that resample to the "
+                    "mode's own input length, beside the mode's own")
     ap.add_argument("--limit-gain", type=float, default=4.0, help="--limit: the PROTECT gain of both batches (+12 dB: most tiles hold frames over the ceiling)")
     ap.add_argument("--limit-lookahead", type=int, default=72, help="--limit: the lookahead in frames")
     ap.add_argument("--streams", type=int, default=256)
@@ -131,9 +136,25 @@ def frames_modes(a, lib, x, nin, nout, batch):
     runs = {}
     assert not (a.true_peak and a.mode == "level"), "--true-peak goes with one mode"
     assert not (a.limit and a.mode not in ("protect", "normalise")), "--limit goes with --mode protect (or normalise, where the flag is inert)"
-    for key in (("pcm", "fixed", "protect") if a.mode == "level" else (a.mode,)) + (("loudness",) if a.loudness else ()) + (("true_peak",) if a.true_peak else ()) + (("limit",) if a.limit else ()) + (("loudness_range",) if a.loudness_range else ()):
+    assert not (a.resample and a.mode == "level"), "--resample goes with one mode"
+    inputs = {}
+    for key in (("pcm", "fixed", "protect") if a.mode == "level" else (a.mode,)) + (("loudness",) if a.loudness else ()) + (("true_peak",) if a.true_peak else ()) + (("limit",) if a.limit else ()) + (("loudness_range",) if a.loudness_range else ()) + (("resample",) if a.resample else ()):
         b = batch()
-        name = a.mode if key in ("true_peak", "limit") else key
+        name = a.mode if key in ("true_peak", "limit", "resample") else key
+        if key == "resample":
+            up, down = (int(v) for v in a.resample.split("/"))
+            b.set_pcm_resample(up, down)
+            up, down = b.pcm_resample(0)
+            src = (n*down)//up                                                     # the shortest clip whose Nr is the plain batch's input length
+            while b.resampled_length(0, src) < n:
+                src += 1
+            assert b.resampled_length(0, src) == n, (src, b.resampled_length(0, src), n)
+            ts = torch.arange(src, device="cuda", dtype=torch.float32)*(up/(down*a.sample_rate))   # the same tones, at the clips' rate
+            f = 110.0*2**(torch.arange(S*Cn, device="cuda", dtype=torch.float32).reshape(S, 1, Cn) % 37/12)
+            g = torch.Generator(device="cuda").manual_seed(8)
+            xs = 0.4*torch.sin(2*np.pi*f*ts.reshape(1, src, 1)) + 0.05*torch.rand((S, src, Cn), generator=g, device="cuda") - 0.025
+            inputs[key] = ((xs*32768.0).round().clamp(-32768, 32767).to(torch.int16).contiguous(), np.full(S, src, np.int32))
+            del xs
         if key == "true_peak":
             b.set_pcm_true_peak(True)
         if key == "limit":
@@ -151,16 +172,19 @@ def frames_modes(a, lib, x, nin, nout, batch):
             b.set_pcm_loudness_range(True, a.sample_rate)
         runs[key] = b
 
-    def call(b):
+    torch.cuda.synchronize()
+
+    def call(b, key):
         status = np.zeros(S, np.int32)
-        smst._check(lib, lib.smst_batch_exact_pcm(b.h, C.c_void_p(frames.data_ptr()), n*Cn, Cn, ip(nin), C.c_void_p(out.data_ptr()), most*Cn, Cn, ip(nout), ip(status), smst.PCM_S16, smst.MEM_DEVICE))
+        fr, counts = inputs.get(key, (frames, nin))
+        smst._check(lib, lib.smst_batch_exact_pcm(b.h, C.c_void_p(fr.data_ptr()), fr.shape[1]*Cn, Cn, ip(counts), C.c_void_p(out.data_ptr()), most*Cn, Cn, ip(nout), ip(status), smst.PCM_S16, smst.MEM_DEVICE))
         assert not status.any(), status
     times = {name: [] for name in runs}
     for k in range(a.warmup + a.steps):
         for name, b in runs.items():
             b.synchronize()
             t0 = time.perf_counter()
-            call(b)
+            call(b, name)
             b.synchronize()
             if k >= a.warmup:
                 times[name].append((time.perf_counter() - t0)*1e3)
@@ -194,6 +218,11 @@ def frames_modes(a, lib, x, nin, nout, batch):
                                gain_range=[float(gains.min()), float(gains.max())], image_bytes=int(S)*Cn*int(nout.sum()//S)*4,
                                launches=[smst.launch_count(k, lib) for k in ("clip_limit_need", "clip_limit_gain", "clip_out_limited")])
         result["limit"]["minus_%s_ms" % a.mode] = round(result["step_ms"]["limit"]["median"] - result["step_ms"][a.mode]["median"], 3)
+    if a.resample:
+        up, down = runs["resample"].pcm_resample(0)
+        result["resample"] = dict(ratio="%d/%d" % (up, down), in_samples=int(inputs["resample"][1][0]), resampled=n, launches=smst.launch_count("clip_resample", lib),
+                                  raw_image_bytes=int(S)*Cn*int(inputs["resample"][1][0])*4, input_image_bytes=int(S)*Cn*n*4)
+        result["resample"]["minus_%s_ms" % a.mode] = round(result["step_ms"]["resample"]["median"] - result["step_ms"][a.mode]["median"], 3)
     if a.loudness_range:
         mmax, smax, lra, low, high, ns, ng = runs["loudness_range"].take_pcm_loudness_range()
         result["loudness_range"] = dict(short_term_max_range=[float(smax.min()), float(smax.max())], lra_range=[float(lra.min()), float(lra.max())],

@@ -6,7 +6,7 @@
 //   stretch_cli [--semitones=S] [--formant=S] [--formant-comp] [--formant-base=Hz] [--tonality=Hz] [--time=F]
 //               [--split-computation] [--device=N] [--out-format=s16|s24|f32] [--dither=none|tpdf|tpdf-hp] [--dither-seed=N]
 //               [--exact] [--gain=dB] [--protect=dBFS | --normalize=dBFS] [--loudness=LUFS] [--true-peak]
-//               [--limit] [--limit-lookahead=ms] [--loudness-range] [--max-short-term=LUFS] [--max-momentary=LUFS]
+//               [--limit] [--limit-lookahead=ms] [--loudness-range] [--max-short-term=LUFS] [--max-momentary=LUFS] [--rate=HZ]
 //               in.wav out.wav [in2.wav out2.wav ...]
 //
 // --out-format (also "--out-format s24"): the samples of the files written -- 16-bit (the default, as the reference's CLI writes), 24-bit by the
@@ -43,7 +43,12 @@
 // silence and for a clip too short to have one), the range in LU.  Alone it only meters.
 // --max-short-term=LUFS and --max-momentary=LUFS (they need --loudness): caps on the two maxima of the file as written (EBU R 128 s1) --
 // the gain is the lowest of the target's and the caps'.
-// Files given together must share sample rate and channel count (they form one batch); lengths may differ.
+// --rate=HZ (needs --exact, or a flag that implies it): the batch is created, and the files are written, at HZ; an input file of another
+// integer rate is resampled on the GPU on its way in (include/smst.h, "Resample"; the ratio comes from smst_resample_ratio), so files of
+// different rates form one batch.  A file's output length is round(Nr*time), today's rule on its length at HZ.  One line per file:
+// "resample: <file> <its rate> Hz -> <HZ> Hz ratio=<up>/<down>".
+// Files given together must share sample rate and channel count (they form one batch); lengths may differ.  With --rate only the channel
+// count must be shared.
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -141,6 +146,12 @@ int main(int argc, char **argv) {
 		std::fprintf(stderr, "--max-short-term and --max-momentary need --loudness=LUFS: they cap the gain that reaches its target\n");
 		return 2;
 	}
+	const bool resample = hasValue(argc, argv, "rate");
+	const double rate = flagValue(argc, argv, "rate", 0);
+	if (resample && !exact) {
+		std::fprintf(stderr, "--rate needs --exact (or --protect, --normalize or --loudness, which imply it): whole clips only\n");
+		return 2;
+	}
 	const double limitLookaheadMs = flagValue(argc, argv, "limit-lookahead", 1.5);
 	const float gain = fromDecibels(flagValue(argc, argv, "gain", 0)), ceiling = fromDecibels(flagValue(argc, argv, protect ? "protect" : "normalize", 0));
 	std::vector<std::string> files;
@@ -154,20 +165,27 @@ int main(int argc, char **argv) {
 	std::string error;
 	for (int s = 0; s < S; ++s) {
 		if (!readWav(files[2*s], inputs[s], error)) { std::fprintf(stderr, "%s\n", error.c_str()); return 1; }
-		if (inputs[s].sampleRate != inputs[0].sampleRate || inputs[s].channels != inputs[0].channels) {
+		if ((!resample && inputs[s].sampleRate != inputs[0].sampleRate) || inputs[s].channels != inputs[0].channels) {
 			std::fprintf(stderr, "all files of a batch must share sample rate and channel count\n");
 			return 1;
 		}
 		std::printf("%s -> %s\n", files[2*s].c_str(), files[2*s + 1].c_str());
 	}
 	const int C = int(inputs[0].channels);
-	const float sr = float(inputs[0].sampleRate);
+	const double batchRate = resample ? rate : double(inputs[0].sampleRate); // the rate of the batch and of the files written
+	const float sr = float(batchRate);
 
 	smst_batch *batch = nullptr;
 	CHECK(smst_batch_create_preset(&batch, S, C, 0, sr, split ? 1 : 0, device, 0)); // presetDefault, cmd/main.cpp:45
 	CHECK(smst_batch_set_transpose_semitones(batch, -1, float(semitones), float(tonality/sr)));  // :46
 	CHECK(smst_batch_set_formant_semitones(batch, -1, float(formants), formantComp));             // :47
 	CHECK(smst_batch_set_formant_base(batch, -1, float(formantBase/sr)));                         // :48
+	if (resample) for (int s = 0; s < S; ++s) { // the files' ratios: HZ over each file's own rate
+		int up = 1, down = 1;
+		CHECK(smst_resample_ratio(double(inputs[s].sampleRate), rate, &up, &down));
+		CHECK(smst_batch_set_pcm_resample(batch, s, up, down));
+		std::printf("resample: %s %d Hz -> %.0f Hz ratio=%d/%d\n", files[2*s].c_str(), int(inputs[s].sampleRate), rate, up, down);
+	}
 	const int inLat = smst_batch_input_latency(batch), outLat = smst_batch_output_latency(batch), interval = smst_batch_interval_samples(batch);
 
 	// per-stream lengths of the three stages, exactly as cmd/main.cpp:55-82 computes them
@@ -176,7 +194,9 @@ int main(int argc, char **argv) {
 	int maxIn = 0, maxOut = 0;
 	for (int s = 0; s < S; ++s) {
 		const int n = int(inputs[s].length());
-		outLen[s] = int(std::round(n*time));
+		long long atRate = n; // the file's length at the batch's rate
+		if (resample && (atRate = smst_batch_resampled_length(batch, s, n)) < 0) { std::fprintf(stderr, "%s: %s\n", files[2*s].c_str(), smst_last_error()); return 1; }
+		outLen[s] = int(std::round(atRate*time));
 		outIndex[s] = std::max(0, outLen[s] - interval);
 		const int outputPos = outIndex[s] + outLat;
 		const int inputPos = int(std::round(outputPos/time));
@@ -199,14 +219,14 @@ int main(int argc, char **argv) {
 		const size_t esz = size_t(bits/8);
 		const float scale = bits == 24 ? 8388608.0f : 32768.0f;
 		if (dither != SMST_DITHER_NONE) CHECK(smst_batch_set_pcm_dither(batch, -1, dither, ditherSeed));
-		if (loudness) CHECK(smst_batch_set_pcm_loudness(batch, -1, flagValue(argc, argv, "loudness", 0), protect ? ceiling : INFINITY, double(inputs[0].sampleRate)));
+		if (loudness) CHECK(smst_batch_set_pcm_loudness(batch, -1, flagValue(argc, argv, "loudness", 0), protect ? ceiling : INFINITY, batchRate));
 		else if (levelled) CHECK(smst_batch_set_pcm_level(batch, -1, protect ? SMST_LEVEL_PROTECT : normalize ? SMST_LEVEL_NORMALISE : SMST_LEVEL_FIXED, gain, ceiling));
 		if (truePeak) CHECK(smst_batch_set_pcm_true_peak(batch, -1, 1));
 		if (limit) {
-			CHECK(smst_batch_set_pcm_limiter_lookahead(batch, int(std::lround(limitLookaheadMs*1e-3*double(inputs[0].sampleRate)))));
+			CHECK(smst_batch_set_pcm_limiter_lookahead(batch, int(std::lround(limitLookaheadMs*1e-3*batchRate))));
 			CHECK(smst_batch_set_pcm_limiter(batch, -1, 1));
 		}
-		if (loudnessRange) CHECK(smst_batch_set_pcm_loudness_range(batch, -1, 1, double(inputs[0].sampleRate)));
+		if (loudnessRange) CHECK(smst_batch_set_pcm_loudness_range(batch, -1, 1, batchRate));
 		if (capShortTerm || capMomentary) CHECK(smst_batch_set_pcm_loudness_caps(batch, -1, flagValue(argc, argv, "max-momentary", INFINITY), flagValue(argc, argv, "max-short-term", INFINITY)));
 		// `count` samples of file s from sample `first` on as frames at `frames`; false: one of them is no value of the format
 		auto toFrames = [&](int s, int first, int count, unsigned char *frames) {
@@ -273,7 +293,7 @@ int main(int argc, char **argv) {
 			for (int s = 0; s < S; ++s) std::printf("range: %s momentary-max=%.4f short-term-max=%.4f lra=%.4f\n", files[2*s + 1].c_str(), momentary[s], shortTerm[s], range[s]);
 		}
 		for (int s = 0; s < S; ++s) {
-			if (!writeWavFrames(files[2*s + 1], inputs[s].sampleRate, inputs[s].channels, bits, outFrames.data() + (size_t)s*maxOut*C*esz, size_t(outLen[s]), error, format == SMST_PCM_F32)) {
+			if (!writeWavFrames(files[2*s + 1], resample ? unsigned(rate) : inputs[s].sampleRate, inputs[s].channels, bits, outFrames.data() + (size_t)s*maxOut*C*esz, size_t(outLen[s]), error, format == SMST_PCM_F32)) {
 				std::fprintf(stderr, "%s\n", error.c_str());
 				return 1;
 			}
