@@ -99,7 +99,10 @@ __device__ __forceinline__ float2 rotAt(const float2 *rot, int M, int idx, bool 
 //   14,15  F  = P_o * sqrt(E_o) / sqrt(|P_o|^2 + 1e-15)  in that weak case, else 0   (the fallback to the input, :598-601)
 // and the recurrence wave computes  out_o = out_m T' + F : one complex multiply-add instead of two multiplies, a norm, a
 // compare, a reciprocal square root and four selects ON THE SERIAL PATH -- 77 of the 563 clock cycles a step took (cycle
-// trace, tools/probes/voc_trace.py).  The norm is E_m |T|^2 instead of |out_m T|^2: equal up to rounding (1e-7 relative).
+// trace, tools/probes/voc_trace.py).  The norm is E_m |T|^2 instead of |out_m T|^2: equal up to rounding -- measured in float32 on the checker's
+// operands, the two norms differ by 4.8e-7 relative at the most and the locked output's magnitude by 2.7e-7; with the 1-ulp rcp / rsq / sqrt
+// on top, every bin of every form's plain tiles stays within 4.3e-7 (condition-normalised, MI355X) of the float64 evaluation at tf = 1, where
+// the reference's own float32 arithmetic reaches 1.9e-7 (tests/recurrence_residual_cases.py; EXPERIMENTS.md "Recurrence against a float64 mirror").
 template <int CH, int NFLOATS>
 __device__ __forceinline__ void recordChannelFields(float (&f)[NFLOATS], const float2 (&p)[CH], const float (&e)[CH], int mc, float2 PmN = float2{0.f, 0.f}, float eMN = 0.0f) {
 	if constexpr (CH == 2) {
