@@ -604,7 +604,8 @@ int smst_debug_true_peak_taps(float *out);
  * [longest limited clip] floats each) and the meter words grow with the first call that limits and count in smst_batch_workspace_bytes: a
  * second call of the same shapes allocates nothing, no host synchronisation is added, and the ordering contract of the device-memory call is
  * unchanged.  The meters are integers: no floating-point atomic.
- * Out of scope: a streaming limiter, release shaping other than the symmetric window, a lookahead per stream, oversampled gain application.
+ * Out of scope: release shaping other than the symmetric window, a lookahead per stream, oversampled gain application.  (The streaming calls
+ * have a limiter of their own, a setting beside this flag: "Stream limiter" below.)
  * SMST_ERR_INVALID with a message: a lookahead outside [1, SMST_LIMITER_MAX_LOOKAHEAD], a stream index out of range, a null batch. */
 #define SMST_LIMITER_MAX_LOOKAHEAD 1024
 #define SMST_LIMITER_DEFAULT_LOOKAHEAD 72 /* 1.5 ms at 48 kHz */
@@ -613,7 +614,7 @@ int smst_debug_true_peak_taps(float *out);
 int smst_batch_set_pcm_limiter(smst_batch *b, int stream, int on);
 /* on may be null */
 int smst_batch_pcm_limiter(const smst_batch *b, int stream, int *on);
-/* the batch's lookahead H in frames; synchronises the batch where the window is on the device already */
+/* the batch's lookahead H in frames; synchronises the batch where the window is on the device already, and clears the lines of "Stream limiter" */
 int smst_batch_set_pcm_limiter_lookahead(smst_batch *b, int frames);
 int smst_batch_pcm_limiter_lookahead(const smst_batch *b, int *frames);
 /* per stream, of the newest smst_batch_exact_pcm that limited: minGain[s] = the lowest r(n), limitedFrames[s] = the frames with r(n) < 1;
@@ -629,6 +630,82 @@ int smst_debug_clip_limit(int device, int streams, int channels, const int *segm
                           float *need, float *r, int maxFrames, float *minGain, long long *limitedFrames);
 /* test hook: the library's window, out[k + lookahead] = win[k], k = -lookahead ... lookahead */
 int smst_debug_limiter_window(int lookahead, float *out);
+/* ---- Stream limiter (EXTENSION; opt-in: a batch that never calls smst_batch_set_pcm_stream_limiter launches the kernels, writes the bytes and counts the launches it did before) ----
+ * The limiter above knows a whole clip.  A real-time caller who applies a gain to an int16 or int24 bus through smst_batch_process_pcm could
+ * only let the conversion clamp and count the overs.  The curve of "Limiter" is non-recursive -- r(n) is a function of need over the 4H + 1
+ * frames around n --, so it has an exact streaming form: with the output 2H frames late and need of the last 4H frames carried per stream,
+ * a stream cut into calls in any way gets, bit for bit, the clip limiter's output.
+ *
+ * It is a per-stream setting of its own, on/off and a ceiling, NOT the flag above: that flag stays refused in the streaming calls.  The
+ * batch's one lookahead H serves both limiters (smst_batch_set_pcm_limiter_lookahead).  The setting acts on streams in SMST_LEVEL_FIXED with
+ * g = the stream's fixed gain (a stream that was never given a level: g = 1); a stream in a whole-clip mode is refused by the streaming calls
+ * as ever, with the setting on as well.
+ *
+ * Definition.  Let v(n), n = 0, 1, 2 ..., be the frames the engine has emitted for the stream through smst_batch_process_pcm and
+ * smst_batch_flush_pcm since the stream's line was last cleared.  The T frames the stream has been handed so far are the first T frames of
+ * "Limiter"'s steps 2 to 7 applied to the clip [2H frames of +0.0, v(0), v(1), ... v(T - 1)], where g is the fixed gain, the detector works
+ * without true-peak phases, need uses |g| -- an inverting stream is limited too; fabsf is exact, so limitNeed(m, fabsf(g), ceiling) is the
+ * one definition of the step --, the ceiling is the stream limiter's own and the window is the one the batch already has.  The result does
+ * not depend on how T is cut into calls, and the clip's right edge never enters: frame i < T depends on need up to i + 2H < T + 2H.
+ *   Latency.  The output is the engine's, 2H frames late; smst_batch_pcm_stream_limiter_latency reports 2H.
+ *   Leading frames.  The first 2H frames are the zeros in front of the stream, treated as any frame: multiplied (w = 0*g, u = w*r -- with
+ *   a negative gain a float format shows -0.0), dithered with the stream's running frame counter, metered.  A loud v(0) pulls r below 1 on
+ *   them, and they count as limited frames.
+ *   Flush.  The line is not the engine's: a flush does not empty it.  To end a stream, its flush is asked for 2H frames more -- the
+ *   reference's flush writes zeros behind its tail --, or the stream is flushed again.
+ *   Meters.  The sample-peak meter and the overs stay as they are; the peak is over the |v| of the frames a call WRITES, the delayed ones.
+ *   Counters.  Dither is applied behind the limiter; its frame counter advances as ever.
+ *   Unflagged streams.  In the same call a stream without the setting is not delayed and gets the bytes it gets without this section; a
+ *   batch may mix both.  A stream with no frame in a call, or left out of a flush, keeps its line.
+ * The line is cleared (need <- 1, frames <- +0.0) by smst_batch_set_pcm_stream_limiter for the stream, on or off -- turning it off drops the
+ * 2H frames inside --, by smst_batch_set_pcm_limiter_lookahead for every stream, and by smst_batch_reset.  smst_batch_set_pcm_level does NOT
+ * clear it: a gain change acts on the frames whose need is formed from then on, and on every frame written from then on.
+ *   Meters of its own.  minGain[s] = the lowest r written for the stream, limitedFrames[s] = the frames written with r < 1, both
+ *   accumulated over the calls since the last take, which clears them as the peaks' take does.  On the device they are integer words
+ *   (atomicMax, atomicAdd: no floating-point atomic); the count wraps as an unsigned 32-bit word does, the overs' rule.
+ *   Known answers (float32 bit patterns).  H = 2, mono, g = 1, ceiling 0.5, 17 frames with v(6) = 1 and the rest 0, cut as 5, 1, 7, 4:
+ *   r of the frames written = 3f800000 x6, 3f755556 3f555556 3f2aaaab 3f0aaaab 3f000000 3f0aaaab 3f2aaaab 3f555556 3f755556, 3f800000 x2;
+ *   the float32 output is 3f000000 at frame 10 and 0 elsewhere; minGain 3f000000, limitedFrames 9.  H = 2, mono, g = -1, ceiling 0.5,
+ *   9 frames with v(0) = 1, cut as 3, 6: r = 3f755556 3f555556 3f2aaaab 3f0aaaab 3f000000 3f0aaaab 3f2aaaab 3f555556 3f755556; the output
+ *   is 80000000 x4, bf000000, 80000000 x4; limitedFrames 9.
+ *
+ * What it guarantees: what the clip limiter guarantees.  The SAMPLE peak of u is at most the ceiling, up to the roundings tabulated under
+ * "Clip-free ceilings"; the TRUE peak is not bounded -- "Limiter" quotes the measured overshoots per H.
+ *
+ * How.  Per stream, in device memory and counted in smst_batch_workspace_bytes: need of the last 4H frames, the last 2H frames of every
+ * channel (v, before the gain) and the meter words, allocated by the first setter call with on != 0 -- which makes the batch a levelled one
+ * and puts the window on the device --, never in a call.  The lines exist twice: every kernel of a call reads one set and writes the other,
+ * and everything is ordered by the batch's stream, so one pair serves calls in flight.  Three kernels (csrc/smst_stream_limiter.h):
+ * need of the call's frames behind the carried ones; the curve, by the clip limiter's own steps 4 to 6 (one device function for both); and
+ * a limited conversion -- a kernel of its own -- whose loader takes frame i from the line (i < 2H) or from the call's image at i - 2H.  The
+ * work rows ([streams][4H + longest limited call] and [streams][longest limited call] floats) grow with the first call that needs them; a
+ * steady-state call allocates nothing and no host synchronisation is added.  The setting is bit 2 of the fourth word of the stream's level
+ * entry, the ceiling rides in the word a FIXED entry does not use; smst_batch_pcm_level keeps reporting the level's own ceiling.
+ * Out of scope: a true-peak detector (its 12 taps would add latency of their own), a lookahead per stream, the planar calls,
+ * smst_batch_exact_pcm, release shaping, stretch_cli (a whole-file tool, which has --limit).
+ * SMST_ERR_INVALID with a message, before anything runs: a stream index out of range, a null batch, a ceiling that is NaN or <= 0 (+inf is
+ * allowed: no limit); smst_batch_exact_pcm with a participating stream that has the setting on (the whole-clip form is
+ * smst_batch_set_pcm_limiter). */
+/* stream = -1: every stream.  Clears the line of the stream(s).  The first call with on != 0 makes the batch a levelled one, puts the window
+ * into device memory and allocates the lines */
+int smst_batch_set_pcm_stream_limiter(smst_batch *b, int stream, int on, float ceiling);
+/* on and ceiling may be null */
+int smst_batch_pcm_stream_limiter(const smst_batch *b, int stream, int *on, float *ceiling);
+/* 2H: the frames by which a limited stream's output is late */
+int smst_batch_pcm_stream_limiter_latency(const smst_batch *b, int *frames);
+/* per stream, over the calls since the last take: minGain[s] = the lowest r written, limitedFrames[s] = the frames written with r < 1; 1 and
+ * 0 where nothing was limited.  Either may be null.  Synchronises the batch and clears the meters. */
+int smst_batch_take_pcm_stream_limiter(smst_batch *b, float *minGain, long long *limitedFrames);
+/* test hook: `calls` output conversions in sequence on one device stream, with the carried lines, on a planar fp32 image (host pointer,
+ * strides in floats) that holds each stream's frames in order.  counts: [calls][streams], negative = the stream takes no part in that call.
+ * gains, ceilings, flags: [streams]; flags: 1 = setting on.  r: [streams][maxFrames] as written (delayed; 1 for a stream without the setting
+ * and behind the frames written); frames: interleaved float32 [streams][maxFrames][channels], the F32 output (+0.0 behind the frames
+ * written).  maxFrames >= the sum of every stream's counts.  minGain, limitedFrames: [streams], the meters of all the calls.  Any output
+ * pointer may be null. */
+int smst_debug_pcm_stream_limit(int device, int streams, int channels, int calls, const int *counts,
+                                const float *image, long long imageStreamStride, long long imageChannelStride,
+                                const float *gains, const float *ceilings, const int *flags, int lookahead,
+                                float *r, float *frames, int maxFrames, float *minGain, long long *limitedFrames);
 /* ---- Loudness range (EXTENSION; opt-in: a batch that never calls smst_batch_set_pcm_loudness_range or _caps launches the kernels, writes the bytes and counts the launches it did before) ----
  * A delivery to EBU R 128 reports the loudness range (LRA, EBU Tech 3342) and the maximum momentary and short-term loudness (EBU Tech
  * 3341) of a clip, and R 128 s1 bounds the maximum short-term loudness of short-form content.  A stream with the meter flag has all three

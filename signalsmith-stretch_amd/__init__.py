@@ -156,6 +156,11 @@ _SIGNATURES = {
     "smst_batch_take_pcm_limiter": (C.c_int, [C.c_void_p, _fp, C.POINTER(_ll)]),
     "smst_debug_clip_limit": (C.c_int, [C.c_int, C.c_int, C.c_int, _ip, C.c_void_p, _ll, _ll, _fp, _fp, _ip, C.c_int, _fp, _fp, C.c_int, _fp, C.POINTER(_ll)]),
     "smst_debug_limiter_window": (C.c_int, [C.c_int, _fp]),
+    "smst_batch_set_pcm_stream_limiter": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_float]),
+    "smst_batch_pcm_stream_limiter": (C.c_int, [C.c_void_p, C.c_int, _ip, _fp]),
+    "smst_batch_pcm_stream_limiter_latency": (C.c_int, [C.c_void_p, _ip]),
+    "smst_batch_take_pcm_stream_limiter": (C.c_int, [C.c_void_p, _fp, C.POINTER(_ll)]),
+    "smst_debug_pcm_stream_limit": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _ip, C.c_void_p, _ll, _ll, _fp, _fp, _ip, C.c_int, _fp, _fp, C.c_int, _fp, C.POINTER(_ll)]),
     "smst_batch_set_pcm_loudness_range": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_double]),
     "smst_batch_pcm_loudness_range": (C.c_int, [C.c_void_p, C.c_int, _ip, _dp]),
     "smst_batch_set_pcm_loudness_caps": (C.c_int, [C.c_void_p, C.c_int, C.c_double, C.c_double]),
@@ -406,6 +411,24 @@ def debug_limiter_window(lookahead, lib=None):
     win = np.zeros(2*int(lookahead) + 1, np.float32)
     _check(lib, lib.smst_debug_limiter_window(int(lookahead), win.ctypes.data_as(_fp)))
     return win
+
+
+def debug_pcm_stream_limit(counts, channels, image, image_ss, image_cs, gains, ceilings, flags, lookahead, max_frames, device=0, lib=None):
+    """smst_debug_pcm_stream_limit on a numpy image (planar float32 that holds each stream's frames in order; strides in floats; counts int
+    [calls, S], negative: the stream takes no part in that call; gains, ceilings, flags: [S], flags 1 = the setting on) -> (r: float32
+    [S, max_frames] as written; frames: float32 [S, max_frames, channels], the F32 output; min gain: float32 [S]; limited frames: int64 [S])"""
+    lib = lib if lib is not None else load_library()
+    g, c, f = np.ascontiguousarray(gains, np.float32), np.ascontiguousarray(ceilings, np.float32), np.ascontiguousarray(flags, np.int32)
+    S = g.shape[0]
+    n = np.ascontiguousarray(counts, np.int32).reshape(-1, S)
+    assert g.shape == c.shape == f.shape == (S,)
+    r, frames = np.full((S, max_frames), -1, np.float32), np.full((S, max_frames, channels), -1, np.float32)
+    low, limited = np.full(S, -1, np.float32), np.full(S, -1, np.int64)
+    _check(lib, lib.smst_debug_pcm_stream_limit(device, S, channels, n.shape[0], n.ctypes.data_as(_ip), C.c_void_p(image.ctypes.data), image_ss, image_cs,
+                                                g.ctypes.data_as(_fp), c.ctypes.data_as(_fp), f.ctypes.data_as(_ip), int(lookahead),
+                                                r.ctypes.data_as(_fp), frames.ctypes.data_as(_fp), int(max_frames), low.ctypes.data_as(_fp),
+                                                limited.ctypes.data_as(C.POINTER(_ll))))
+    return r, frames, low, limited
 
 
 def resample_ratio(from_rate, to_rate, lib=None):
@@ -912,6 +935,32 @@ class StretchBatch:
         did not limit.  Synchronises the batch; resets nothing."""
         low, frames = np.ones(self.streams, np.float32), np.zeros(self.streams, np.int64)
         _check(self.lib, self.lib.smst_batch_take_pcm_limiter(self.h, low.ctypes.data_as(_fp), frames.ctypes.data_as(C.POINTER(_ll))))
+        self._inflight = []
+        return low, frames
+
+    def set_pcm_stream_limiter(self, on=True, ceiling=1.0, stream=-1):
+        """The stream limiter (include/smst.h, "Stream limiter"), processFrames and flushFrames only: a LEVEL_FIXED stream's output comes
+        2*lookahead frames late and is brought down to ``ceiling`` (inf: no limit) by the clip limiter's curve, whatever the cuts between
+        calls.  A setting of its own beside set_pcm_limiter's flag.  Clears the stream's line; stream = -1: every stream."""
+        _check(self.lib, self.lib.smst_batch_set_pcm_stream_limiter(self.h, int(stream), 1 if on else 0, float(ceiling)))
+
+    def pcm_stream_limiter(self, stream):
+        """-> (on, ceiling) of the stream's setting"""
+        on, ceiling = C.c_int(0), C.c_float(0)
+        _check(self.lib, self.lib.smst_batch_pcm_stream_limiter(self.h, int(stream), C.byref(on), C.byref(ceiling)))
+        return bool(on.value), ceiling.value
+
+    def pcm_stream_limiter_latency(self):
+        """-> 2*lookahead: the frames by which a limited stream's output is late"""
+        frames = C.c_int(0)
+        _check(self.lib, self.lib.smst_batch_pcm_stream_limiter_latency(self.h, C.byref(frames)))
+        return frames.value
+
+    def take_pcm_stream_limiter(self):
+        """-> (float32 [S]: the lowest r written, int64 [S]: the frames written with r < 1) over the calls since the last take; 1 and 0 where
+        nothing was limited.  Synchronises the batch and clears the meters."""
+        low, frames = np.ones(self.streams, np.float32), np.zeros(self.streams, np.int64)
+        _check(self.lib, self.lib.smst_batch_take_pcm_stream_limiter(self.h, low.ctypes.data_as(_fp), frames.ctypes.data_as(C.POINTER(_ll))))
         self._inflight = []
         return low, frames
 

@@ -89,6 +89,17 @@ struct PcmOutState {
 	// SMST_LEVEL_LOUDNESS is measured at; the caps on the two maxima (smst_batch_set_pcm_loudness_caps) in LUFS, +inf: none
 	struct Meter { unsigned char on = 0; double sampleRate = 0; smst::LoudEntry entry{}; double capMomentary = INFINITY, capShortTerm = INFINITY; };
 	std::vector<Meter> meter;
+	// the stream limiter (smst_batch_set_pcm_stream_limiter; include/smst.h, "Stream limiter"): the setting and its ceiling, and which of the
+	// stream's two carried lines the next call reads.  The lines -- both sets in one buffer, sized for the lookahead they were allocated at --
+	// and the two meter words per stream exist from the first setter call with `on`; the need and r rows of a call grow on demand, as the
+	// images do.  streamLimitView: where the kernels find all of that (smst::PcmStreamLimit)
+	struct StreamLimit { unsigned char on = 0, set = 0; float ceiling = 1.0f; };
+	std::vector<StreamLimit> streamLimit;
+	DeviceFloats dLimitLines, dLimitRows;
+	Buffer<int, false> dLimitMeters;
+	int limitLinesH = 0;
+	smst::PcmStreamLimit streamLimitView;
+	std::vector<int> hLimitMeters;
 	bool levelled = false;
 	// overs ([S][2]: clamped, NaN): the kernels add to them, takeOvers() reads and clears them; the meter words (smst::PcmMeters)
 	Buffer<unsigned, false> dOvers;
@@ -108,6 +119,7 @@ struct PcmOutState {
 		truePeak.assign((size_t)S, 0);
 		limiter.assign((size_t)S, 0);
 		meter.assign((size_t)S, Meter());
+		streamLimit.assign((size_t)S, StreamLimit());
 		metered.assign((size_t)S, 0);
 		wholeClip.assign((size_t)S, 0);
 		limited.assign((size_t)S, 0);
@@ -120,7 +132,9 @@ struct PcmOutState {
 		dMeters.allocate(meters.words(), "PCM level");
 		if (hipMemcpy(dMeters, hMeters.data(), meters.bytes(), hipMemcpyHostToDevice) != hipSuccess) throw smst::Error("hipMemcpy (PCM level) failed", true);
 	}
-	size_t workspaceBytes() const { return (dOvers ? pcmOversBytes(S) : 0) + (dMeters ? smst::PcmMeters(S).bytes() : 0); }
+	size_t workspaceBytes() const {
+		return (dOvers ? pcmOversBytes(S) : 0) + (dMeters ? smst::PcmMeters(S).bytes() : 0) + (dLimitLines.cap + dLimitRows.cap)*sizeof(float) + dLimitMeters.cap*sizeof(int);
+	}
 
 	// f(s) for the streams that `stream` names: -1 is every one
 	template <typename F> void forStreams(int stream, F f) {
@@ -167,6 +181,88 @@ struct PcmOutState {
 		forStreams(stream, [&](int s) { limiter[s] = on ? 1 : 0; });
 		if (on) levelled = true;
 	}
+	// The stream limiter's lines for the engine's lookahead H, every one cleared: allocated where they are missing or were made for another H
+	// (the caller has synchronised the batch then: a call in flight reads the lines it was issued with)
+	void prepareStreamLimitLines(Batch &e) {
+		const int H = e.limiterLookahead();
+		if (!dLimitLines || limitLinesH != H) {
+			const size_t set = smst::pcmStreamLimitSetFloats(S, C, H);
+			dLimitLines.allocate(2*set, "stream limiter lines");
+			limitLinesH = H;
+			for (int k = 0; k < 2; ++k) {
+				streamLimitView.need[k] = dLimitLines + k*set;
+				streamLimitView.frames[k] = dLimitLines + k*set + (size_t)S*4*H;
+			}
+			streamLimitView.H = H;
+			dLimitRows.release(); // (their pitch depends on H: the next limited call grows them)
+		}
+		if (!dLimitMeters) {
+			dLimitMeters.allocate((size_t)2*S, "stream limiter meters");
+			hLimitMeters.assign((size_t)2*S, 0);
+			if (hipMemsetAsync(dLimitMeters, 0, (size_t)2*S*sizeof(int), e.stream()) != hipSuccess) throw smst::Error("hipMemsetAsync (stream limiter meters) failed", true);
+		}
+		streamLimitView.meters = dLimitMeters;
+		streamLimitView.window = e.limiterWindow();
+		clearStreamLimitLines(e, -1);
+	}
+	// need <- 1, frames <- +0.0 for the stream (-1: every one), in the batch's stream order
+	void clearStreamLimitLines(Batch &e, int stream) {
+		if (!dLimitLines) return;
+		if (hipSetDevice(e.device()) != hipSuccess) throw smst::Error("hipSetDevice failed", true);
+		smst::launchPcmLimitClear(streamLimitView, S, C, stream, e.stream());
+		for (int s = stream < 0 ? 0 : stream; s < (stream < 0 ? S : stream + 1); ++s) streamLimit[s].set = 0;
+	}
+	void setStreamLimiter(Batch &e, int stream, int on, float ceiling) {
+		if (!(ceiling > 0)) throw smst::Error("stream limiter: the ceiling is NaN or not above 0 (+inf: no limit)");
+		forStreams(stream, [](int) {}); // (refused before anything is allocated)
+		if (on) {
+			if (hipSetDevice(e.device()) != hipSuccess) throw smst::Error("hipSetDevice failed", true);
+			if (!e.limiterWindow()) e.prepareLimiter(); // (the window goes to the device here, not in a call)
+			if (!dLimitLines) prepareStreamLimitLines(e);
+			levelled = true;
+		}
+		forStreams(stream, [&](int s) { streamLimit[s].on = on ? 1 : 0; streamLimit[s].ceiling = ceiling; });
+		clearStreamLimitLines(e, stream);
+	}
+	bool anyStreamLimit() const {
+		if (levelled) for (const StreamLimit &l : streamLimit) if (l.on) return true;
+		return false;
+	}
+	// the largest count of a stream that a streaming call of these counts limits: the setting, a FIXED level and frames
+	int mostStreamLimited(const int *n) const {
+		int most = 0;
+		if (anyStreamLimit()) for (int s = 0; s < S; ++s) if (streamLimit[s].on && level[s].mode == SMST_LEVEL_FIXED) most = std::max(most, n[s]);
+		return most;
+	}
+	// the rows of a call whose longest limited count is `most`, before the engine is called (a growth frees, which synchronises the device)
+	void ensureStreamLimitRows(Batch &e, int most, long long &allocs) {
+		const long long lead = (long long)4*limitLinesH, pitch = ((long long)most + 3)/4*4;
+		dLimitRows.ensure((size_t)S*size_t(lead + 2*pitch), e.device(), allocs, "stream limiter rows");
+		// laid out for the capacity, so that a buffer that has served a longer call serves this one with the pitches of that one
+		const long long per = (long long)(dLimitRows.cap/(size_t)S);
+		streamLimitView.rPitch = (per - lead)/2/4*4;
+		streamLimitView.needPitch = lead + streamLimitView.rPitch;
+		streamLimitView.needRow = dLimitRows;
+		streamLimitView.rRow = dLimitRows + (size_t)S*size_t(streamLimitView.needPitch);
+	}
+	// after a call that limited: the streams that took part read the other set next time
+	void advanceStreamLimit(const int *n) {
+		for (int s = 0; s < S; ++s) if (streamLimit[s].on && level[s].mode == SMST_LEVEL_FIXED && n[s] > 0) streamLimit[s].set ^= 1;
+	}
+	void takeStreamLimiter(float *minGain, long long *limitedFrames) {
+		for (int s = 0; s < S; ++s) {
+			if (minGain) minGain[s] = 1.0f;
+			if (limitedFrames) limitedFrames[s] = 0;
+		}
+		if (!dLimitMeters) return; // (the setting was never on: nothing has limited)
+		if (hipMemcpy(hLimitMeters.data(), dLimitMeters, (size_t)2*S*sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) throw smst::Error("hipMemcpy (stream limiter meters) failed", true);
+		if (hipMemset(dLimitMeters, 0, (size_t)2*S*sizeof(int)) != hipSuccess) throw smst::Error("hipMemset (stream limiter meters) failed", true);
+		for (int s = 0; s < S; ++s) {
+			const int bits = 0x3f800000 - hLimitMeters[s];
+			if (minGain) std::memcpy(minGain + s, &bits, sizeof(float));
+			if (limitedFrames) limitedFrames[s] = (long long)(unsigned)hLimitMeters[(size_t)S + s]; // (the count wraps as an unsigned 32-bit word does)
+		}
+	}
 	void setLoudnessRange(int stream, int on, double sampleRate) {
 		Meter m;
 		if (on) {
@@ -201,6 +297,13 @@ struct PcmOutState {
 		return e;
 	}
 	unsigned flags(int s) const { return (truePeak[s] ? smst::kPcmFlagTruePeak : 0u) | (limiter[s] ? smst::kPcmFlagLimiter : 0u); }
+	// a call's level entry: a FIXED stream with the stream limiter's setting carries that limiter's ceiling in the word its mode does not use,
+	// the setting in bit 2 of the flags and the set of lines the call reads in bit 3
+	smst::PcmLevel levelEntry(int s) const {
+		const bool limit = streamLimit[s].on && level[s].mode == SMST_LEVEL_FIXED;
+		return smst::PcmLevel{unsigned(level[s].mode), level[s].gain, limit ? streamLimit[s].ceiling : level[s].ceiling,
+		                      flags(s) | (limit ? smst::kPcmFlagStreamLimiter | (streamLimit[s].set ? smst::kPcmFlagStreamLimitSet : 0u) : 0u)};
+	}
 	void setLoudnessWeights(const float *weights) {
 		for (int c = 0; weights && c < C; ++c) if (!(std::isfinite(weights[c]) && weights[c] >= 0)) throw smst::Error("loudness: a channel weight is negative or not finite");
 		for (int c = 0; c < C; ++c) loudWeights[c] = weights ? weights[c] : 1.0f;
@@ -232,7 +335,7 @@ struct PcmOutState {
 			call.loudWeights = at.weights(dev);
 		}
 		if (levelled) {
-			for (int s = 0; s < S; ++s) at.level(host)[s] = smst::PcmLevel{unsigned(level[s].mode), level[s].gain, level[s].ceiling, flags(s)};
+			for (int s = 0; s < S; ++s) at.level(host)[s] = levelEntry(s);
 			call.level = smst::PcmMeters(S).io(at.level(dev), dMeters);
 		}
 		if (dithered || levelled) {
@@ -301,6 +404,7 @@ struct smst_batch {
 		Buffer<unsigned char, true> host;
 		Buffer<unsigned char, false> dev;
 		smst::PcmOutCall out;
+		int mostLimited = 0; // the largest count of a stream that the call's output limits ("Stream limiter"); 0: the call launches what it did without the setting
 	};
 	smst::TwoSets<PcmTable> pcmTables; // (smst_staging.h)
 	PcmOutState pcmOut;
@@ -442,7 +546,12 @@ long long smst_batch_workspace_bytes(const smst_batch *b) { if (!b || !b->engine
 
 #define BATCH_CALL(...) if (!b || !b->engine) return fail("null batch"); SMST_TRY __VA_ARGS__; return SMST_OK; SMST_CATCH
 
-int smst_batch_reset(smst_batch *b) { BATCH_CALL(b->engine->reset()) }
+int smst_batch_reset(smst_batch *b) {
+	BATCH_CALL({
+		b->engine->reset();
+		b->pcmOut.clearStreamLimitLines(*b->engine, -1); // (the stream limiter's lines begin again, in stream order behind the calls in flight)
+	})
+}
 int smst_batch_set_transpose_factor(smst_batch *b, int s, float m, float t) { BATCH_CALL(b->engine->setTransposeFactor(s, m, t)) }
 int smst_batch_set_transpose_semitones(smst_batch *b, int s, float st, float t) { BATCH_CALL(b->engine->setTransposeSemitones(s, st, t)) }
 int smst_batch_set_formant_factor(smst_batch *b, int s, float m, int c) { BATCH_CALL(b->engine->setFormantFactor(s, m, c != 0)) }
@@ -635,6 +744,7 @@ static smst_batch::PcmTable &beginPcmCall(smst_batch *b) {
 		}
 	}
 	c.out = smst::PcmOutCall();
+	c.mostLimited = 0;
 	return c;
 }
 // The output side's sections of the call's table, from the batch's state, and their upload -- with the S output counts in front of them where
@@ -713,6 +823,8 @@ static int pcmPrepareOut(smst_batch *b, smst_batch::PcmTable &c, const int *n, i
 	ensureStage(b, b->dOut, (size_t)S*C*k.len);
 	if (memory == SMST_MEM_HOST && k.most > 0) ensurePcmBytes(b, b->hPcmOut, b->dPcmOut, (size_t)S*pcmRowElems(k.most, C)*pcmElemBytes(format));
 	hipSetDevice(e.device());
+	c.mostLimited = b->pcmOut.mostStreamLimited(smst::PcmTableLayout(S).outCounts(c.host));
+	if (c.mostLimited > 0) b->pcmOut.ensureStreamLimitRows(e, c.mostLimited, b->stagingAllocs);
 	pcmUploadOutTable(b, c, format, true);
 	return k.len;
 }
@@ -725,13 +837,23 @@ static void pcmStageOut(smst_batch *b, smst_batch::PcmTable &c, void *out, long 
 	const int *n = at.outCounts(c.host);
 	const int most = countsOf(n, S).most;
 	hipSetDevice(e.device());
+	// a call that limits a stream: the two passes and the limited conversion (a kernel of its own) in the place of the levelled one
+	auto convert = [&](void *raw, long long rawSS, long long rawFS) {
+		if (c.mostLimited > 0) {
+			smst::launchPcmOutLimited(format, b->dOut, (long long)C*maxLen, maxLen, raw, rawSS, rawFS, at.outCounts(c.dev), S, C, most, c.mostLimited, c.out.overs, e.stream(), c.out.dither, c.out.level,
+			                          b->pcmOut.streamLimitView);
+			b->pcmOut.advanceStreamLimit(n);
+		} else {
+			smst::launchPcmOut(format, b->dOut, (long long)C*maxLen, maxLen, raw, rawSS, rawFS, at.outCounts(c.dev), S, C, most, c.out.overs, e.stream(), c.out.dither, c.out.level);
+		}
+	};
 	if (memory == SMST_MEM_DEVICE) {
-		smst::launchPcmOut(format, b->dOut, (long long)C*maxLen, maxLen, out, ss, fs, at.outCounts(c.dev), S, C, most, c.out.overs, e.stream(), c.out.dither, c.out.level);
+		convert(out, ss, fs);
 		b->pcmOut.advance(n);
 		return;
 	}
 	if (most >= 1) {
-		smst::launchPcmOut(format, b->dOut, (long long)C*maxLen, maxLen, b->dPcmOut, pcmRowElems(most, C), C, at.outCounts(c.dev), S, C, most, c.out.overs, e.stream(), c.out.dither, c.out.level);
+		convert(b->dPcmOut, pcmRowElems(most, C), C);
 		pcmRawOut(b, out, ss, fs, n, most, format);
 	}
 	b->pcmOut.advance(n);
@@ -795,7 +917,33 @@ int smst_batch_pcm_limiter(const smst_batch *b, int stream, int *on) {
 	if (on) *on = b->pcmOut.limiter[stream];
 	return SMST_OK;
 }
-int smst_batch_set_pcm_limiter_lookahead(smst_batch *b, int frames) { BATCH_CALL(b->engine->setLimiterLookahead(frames)) }
+int smst_batch_set_pcm_limiter_lookahead(smst_batch *b, int frames) {
+	BATCH_CALL({
+		b->engine->setLimiterLookahead(frames); // (synchronises where the window is on the device: the stream limiter's lines are then idle)
+		if (b->pcmOut.dLimitLines) b->pcmOut.prepareStreamLimitLines(*b->engine);
+	})
+}
+// Stream limiter (include/smst.h): the setting lives beside the level entries, the lines and rows in the batch's PCM output state
+int smst_batch_set_pcm_stream_limiter(smst_batch *b, int stream, int on, float ceiling) { BATCH_CALL(b->pcmOut.setStreamLimiter(*b->engine, stream, on, ceiling)) }
+int smst_batch_pcm_stream_limiter(const smst_batch *b, int stream, int *on, float *ceiling) {
+	if (!b || !b->engine) return fail("null batch");
+	if (stream < 0 || stream >= b->engine->streams()) return fail("stream index out of range");
+	if (on) *on = b->pcmOut.streamLimit[stream].on;
+	if (ceiling) *ceiling = b->pcmOut.streamLimit[stream].ceiling;
+	return SMST_OK;
+}
+int smst_batch_pcm_stream_limiter_latency(const smst_batch *b, int *frames) {
+	if (!b || !b->engine) return fail("null batch");
+	if (frames) *frames = 2*b->engine->limiterLookahead();
+	return SMST_OK;
+}
+int smst_batch_take_pcm_stream_limiter(smst_batch *b, float *minGain, long long *limitedFrames) {
+	BATCH_CALL({
+		b->engine->synchronize();
+		hipSetDevice(b->engine->device());
+		b->pcmOut.takeStreamLimiter(minGain, limitedFrames);
+	})
+}
 int smst_batch_pcm_limiter_lookahead(const smst_batch *b, int *frames) {
 	if (!b || !b->engine) return fail("null batch");
 	if (frames) *frames = b->engine->limiterLookahead();
@@ -1016,6 +1164,10 @@ int smst_batch_exact_pcm(smst_batch *b, const void *in, long long iss, long long
 		Batch &e = *b->engine;
 		checkPcmFormat(format, memory);
 		checkExactArgs(e, in, inSamples, out, outSamples, ifs, ofs, true, memory);
+		for (int s = 0; s < e.streams(); ++s)
+			if (outSamples[s] >= 0 && b->pcmOut.streamLimit[s].on)
+				throw smst::Error("stream " + std::to_string(s) + " has the stream limiter's setting (smst_batch_set_pcm_stream_limiter), which acts in smst_batch_process_pcm and smst_batch_flush_pcm: "
+				                  "the whole-clip form is smst_batch_set_pcm_limiter");
 		checkResampledLengths(e, inSamples, outSamples);
 		// a dithered call: the streams' modes and hashes ride in the _pcm calls' table (the frame index is the place in the clip: the counters
 		// are neither read nor moved); a levelled call: the level entries ride there too, and the loudness entries and the channel weights
@@ -1479,6 +1631,100 @@ int smst_debug_limiter_window(int lookahead, float *out) {
 	if (lookahead < 1 || lookahead > smst::kLimitMaxLookahead) return fail("limiter window: the lookahead is outside 1 ... 1024 frames");
 	smst::limitWindow(lookahead, out);
 	return SMST_OK;
+}
+// the stream limiter's output conversions, call after call with the carried lines: see include/smst.h
+int smst_debug_pcm_stream_limit(int device, int streams, int channels, int calls, const int *counts, const float *image, long long imageSS, long long imageCS,
+                                const float *gains, const float *ceilings, const int *flags, int lookahead, float *r, float *frames, int maxFrames,
+                                float *minGain, long long *limitedFrames) {
+	SMST_TRY
+	if (streams < 1 || channels < 1 || channels > smst::kMaxChannels || calls < 0 || (calls && !counts) || !image || imageSS < 0 || imageCS < 0 || !gains || !ceilings || !flags || maxFrames < 0)
+		throw smst::Error("stream limit: bad arguments");
+	if (lookahead < 1 || lookahead > smst::kLimitMaxLookahead) throw smst::Error("stream limit: the lookahead is outside 1 ... " + std::to_string(smst::kLimitMaxLookahead) + " frames");
+	auto hip = [&](hipError_t err) { if (err != hipSuccess) throw smst::Error(std::string("stream limit: ") + hipGetErrorString(err), true); };
+	const int S = streams, Cn = channels, H = lookahead;
+	int longest = 0;
+	for (int s = 0; s < S; ++s) {
+		long long total = 0;
+		for (int k = 0; k < calls; ++k) { const int n = std::max(counts[(size_t)k*S + s], 0); total += n; longest = std::max(longest, n); }
+		if (total > maxFrames) throw smst::Error("stream limit: a stream's calls add up to more than maxFrames");
+		if (!(ceilings[s] > 0)) throw smst::Error("stream limit: a ceiling is NaN or not above 0");
+		if (!std::isfinite(gains[s])) throw smst::Error("stream limit: a gain is not finite");
+	}
+	hip(hipSetDevice(device));
+	const size_t len = size_t(std::max(longest, 1)), pitch = (len + 3)/4*4, set = smst::pcmStreamLimitSetFloats(S, Cn, H);
+	const smst::PcmTableLayout at(S);
+	const smst::PcmMeters meters(S);
+	Buffer<unsigned char, false> dTable;
+	Buffer<float, false> dImage, dOut, dLines, dRows, dWin;
+	Buffer<int, false> dWords, dLimitMeters;
+	dTable.allocate(at.bytes(), "stream limit");
+	dImage.allocate((size_t)S*Cn*len, "stream limit");
+	dOut.allocate((size_t)S*len*Cn, "stream limit");
+	dLines.allocate(2*set, "stream limit");
+	dRows.allocate((size_t)S*(4*H + 2*pitch), "stream limit");
+	dWin.allocate((size_t)2*H + 1, "stream limit");
+	dWords.allocate(meters.words(), "stream limit");
+	dLimitMeters.allocate((size_t)2*S, "stream limit");
+	std::vector<float> win((size_t)2*H + 1), hImage((size_t)S*Cn*len), hOut((size_t)S*len*Cn), hR((size_t)S*pitch);
+	std::vector<int> words(meters.words());
+	std::vector<unsigned char> table(at.bytes());
+	smst::limitWindow(H, win.data());
+	meters.start(words.data());
+	hip(hipMemcpy(dWin, win.data(), win.size()*sizeof(float), hipMemcpyHostToDevice));
+	hip(hipMemcpy(dWords, words.data(), meters.bytes(), hipMemcpyHostToDevice));
+	hip(hipMemset(dLimitMeters, 0, (size_t)2*S*sizeof(int)));
+	smst::PcmStreamLimit lim;
+	for (int k = 0; k < 2; ++k) { lim.need[k] = dLines + k*set; lim.frames[k] = dLines + k*set + (size_t)S*4*H; }
+	lim.meters = dLimitMeters;
+	lim.needRow = dRows; lim.needPitch = (long long)(4*H + pitch);
+	lim.rRow = dRows + (size_t)S*(4*H + pitch); lim.rPitch = (long long)pitch;
+	lim.window = dWin; lim.H = H;
+	smst::launchPcmLimitClear(lim, S, Cn, -1, nullptr);
+	if (r) std::fill(r, r + (size_t)S*maxFrames, 1.0f);
+	if (frames) std::fill(frames, frames + (size_t)S*maxFrames*Cn, 0.0f);
+	std::vector<long long> done((size_t)S, 0);
+	std::vector<unsigned char> whichSet((size_t)S, 0);
+	const smst::PcmLevelIo io = meters.io(at.level(dTable.p), dWords);
+	for (int k = 0; k < calls; ++k) {
+		int most = 0, mostLimited = 0;
+		for (int s = 0; s < S; ++s) {
+			const int n = std::max(counts[(size_t)k*S + s], 0);
+			const bool on = (flags[s] & 1) != 0;
+			at.outCounts(table.data())[s] = n;
+			at.level(table.data())[s] = smst::PcmLevel{smst::kPcmLevelFixed, gains[s], on ? ceilings[s] : 1.0f,
+			                                           on ? smst::kPcmFlagStreamLimiter | (whichSet[s] ? smst::kPcmFlagStreamLimitSet : 0u) : 0u};
+			most = std::max(most, n);
+			if (on) mostLimited = std::max(mostLimited, n);
+			for (int c = 0; c < Cn; ++c) std::copy(image + s*imageSS + c*imageCS + done[s], image + s*imageSS + c*imageCS + done[s] + n, hImage.begin() + ((size_t)s*Cn + c)*len);
+		}
+		if (most < 1) continue;
+		hip(hipMemcpy(dImage, hImage.data(), hImage.size()*sizeof(float), hipMemcpyHostToDevice));
+		hip(hipMemcpy(dTable, table.data(), table.size(), hipMemcpyHostToDevice));
+		if (mostLimited > 0) smst::launchPcmOutLimited(SMST_PCM_F32, dImage, (long long)(Cn*len), (long long)len, dOut, (long long)(len*Cn), Cn, at.outCounts(dTable.p), S, Cn, most, mostLimited, nullptr, nullptr, nullptr, io, lim);
+		else smst::launchPcmOut(SMST_PCM_F32, dImage, (long long)(Cn*len), (long long)len, dOut, (long long)(len*Cn), Cn, at.outCounts(dTable.p), S, Cn, most, nullptr, nullptr, nullptr, io);
+		hip(hipGetLastError());
+		hip(hipStreamSynchronize(nullptr));
+		hip(hipMemcpy(hOut.data(), dOut, hOut.size()*sizeof(float), hipMemcpyDeviceToHost));
+		if (mostLimited > 0) hip(hipMemcpy(hR.data(), lim.rRow, hR.size()*sizeof(float), hipMemcpyDeviceToHost));
+		for (int s = 0; s < S; ++s) {
+			const int n = at.outCounts(table.data())[s];
+			const bool on = (flags[s] & 1) != 0;
+			if (frames) std::copy(hOut.begin() + (size_t)s*len*Cn, hOut.begin() + ((size_t)s*len + n)*Cn, frames + ((size_t)s*maxFrames + done[s])*Cn);
+			if (r && on) std::copy(hR.begin() + (size_t)s*pitch, hR.begin() + (size_t)s*pitch + n, r + (size_t)s*maxFrames + done[s]);
+			if (on && n > 0) whichSet[s] ^= 1;
+			done[s] += n;
+		}
+	}
+	hip(hipStreamSynchronize(nullptr));
+	std::vector<int> limitWords((size_t)2*S);
+	hip(hipMemcpy(limitWords.data(), dLimitMeters, limitWords.size()*sizeof(int), hipMemcpyDeviceToHost));
+	for (int s = 0; s < S; ++s) {
+		const int bits = 0x3f800000 - limitWords[s];
+		if (minGain) std::memcpy(minGain + s, &bits, sizeof(float));
+		if (limitedFrames) limitedFrames[s] = (long long)(unsigned)limitWords[(size_t)S + s];
+	}
+	return SMST_OK;
+	SMST_CATCH
 }
 int smst_debug_true_peak_taps(float *out) {
 	if (!out) return fail("true peak taps: null pointer");

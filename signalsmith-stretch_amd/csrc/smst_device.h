@@ -169,7 +169,7 @@ __host__ __device__ inline bool analysisWindowInCall(int B, int M, int I, int in
 // form" tests assert through these that BOTH forms really ran.
 enum LaunchKind {
 	LK_VOC_ALIGNED, LK_VOC_TWISTED, LK_VOC_INTERIOR, LK_VOC_STAGED, LK_VOC_GATHER, LK_VOC_N, LK_VOC_ONE, LK_VOC_ACROSS, LK_VOC_CONT, LK_CHAIN_UNFUSED,
-	LK_ANALYSE_TEAMS, LK_ANALYSE_PAIRS, LK_ANALYSE_TWIST, LK_TWIST_ROWS, LK_ANALYSE_FAST, LK_ANALYSE_GENERIC, LK_SYNTH_TEAMS, LK_SYNTH_FAST, LK_SYNTH_GENERIC, LK_SYNTH_EMIT, LK_EMIT_CARRIED, LK_FEED_ONE_PASS, LK_PCM_IN, LK_PCM_OUT, LK_CLIP_IN, LK_CLIP_OUT, LK_PCM_OUT_DITHERED, LK_CLIP_OUT_DITHERED, LK_PCM_OUT_LEVELLED, LK_CLIP_OUT_LEVELLED, LK_CLIP_PEAK, LK_CLIP_LOUDNESS, LK_CLIP_TRUE_PEAK, LK_CLIP_LIMIT_NEED, LK_CLIP_LIMIT_GAIN, LK_CLIP_OUT_LIMITED, LK_CLIP_LOUDNESS_RANGE, LK_CLIP_RESAMPLE, LK_COUNT
+	LK_ANALYSE_TEAMS, LK_ANALYSE_PAIRS, LK_ANALYSE_TWIST, LK_TWIST_ROWS, LK_ANALYSE_FAST, LK_ANALYSE_GENERIC, LK_SYNTH_TEAMS, LK_SYNTH_FAST, LK_SYNTH_GENERIC, LK_SYNTH_EMIT, LK_EMIT_CARRIED, LK_FEED_ONE_PASS, LK_PCM_IN, LK_PCM_OUT, LK_CLIP_IN, LK_CLIP_OUT, LK_PCM_OUT_DITHERED, LK_CLIP_OUT_DITHERED, LK_PCM_OUT_LEVELLED, LK_CLIP_OUT_LEVELLED, LK_CLIP_PEAK, LK_CLIP_LOUDNESS, LK_CLIP_TRUE_PEAK, LK_CLIP_LIMIT_NEED, LK_CLIP_LIMIT_GAIN, LK_CLIP_OUT_LIMITED, LK_CLIP_LOUDNESS_RANGE, LK_CLIP_RESAMPLE, LK_PCM_LIMIT_FEED, LK_PCM_LIMIT_GAIN, LK_PCM_OUT_LIMITED, LK_COUNT
 };
 long long launchCount(const char *name); // -1: unknown name
 
@@ -237,6 +237,10 @@ inline unsigned pcmDitherHash(long long seed) {
 // the whole-clip gain is formed without the ceiling's quotient, and kClipOut multiplies every frame by its r of PcmLevelIo::limit as well
 struct PcmLevel { unsigned mode; float gain, ceiling; unsigned flags; };
 constexpr unsigned kPcmFlagTruePeak = 1u, kPcmFlagLimiter = 2u;
+// kPcmFlagStreamLimiter: the stream limiter's setting (include/smst.h, "Stream limiter"), which acts in the streaming calls on a FIXED stream;
+// the entry's ceiling word -- a FIXED entry has no use for it otherwise -- then holds the stream limiter's ceiling.  kPcmFlagStreamLimitSet:
+// which of the stream's two carried lines the call reads (it writes the other one)
+constexpr unsigned kPcmFlagStreamLimiter = 4u, kPcmFlagStreamLimitSet = 8u;
 // kClipOut takes the loudness mode's gain gL from loudGain[s], which kLoudGate (smst_loudness.h) left there, and limits it by ceiling/peak.
 constexpr unsigned kPcmLevelFixed = 0u, kPcmLevelProtect = 1u, kPcmLevelNormalise = 2u, kPcmLevelLoudness = 3u;
 struct PcmLevelIo { const PcmLevel *table = nullptr; int *peaks = nullptr; float *applied = nullptr; int *clipPeak = nullptr; const float *loudGain = nullptr;
@@ -325,6 +329,30 @@ constexpr int kLimitMaxLookahead = 1024, kLimitDefaultLookahead = 72;
 void limitWindow(int H, float *win);            // win[k + H] = float32(h_k/sum h), k = -H ... H: in double, one rounding
 void launchClipLimit(const float *image, long long imageStreamStride, long long imageChannelStride, const ClipSeg *segs, int S, int C, int maxFrames,
                      const PcmLevelIo &level, int H, const float *window, float *need, float *r, long long pitch, int *meters, hipStream_t st);
+// The limiter's streaming form (include/smst.h, "Stream limiter", has the definition; smst_stream_limiter.h the kernels), for the streams whose
+// level entry has kPcmFlagStreamLimiter: the output of smst_batch_process_pcm / _flush_pcm 2H frames late, limited by the curve of the clip
+// [2H zeros, every frame emitted so far].  What a batch carries, device: per stream two LINES -- need of the last 4H frames, [S][4H], and the
+// last 2H frames of every channel before the gain, [S][C][2H] --, of which a call reads the one its entry's kPcmFlagStreamLimitSet names and
+// writes the other, and the two meter words of kClipLimitGain, [2][S], which accumulate until they are taken.  What a call works in: the
+// need row [S][needPitch >= 4H + longest limited count] and the r row [S][rPitch >= that count], stream-ordered scratch as the images are
+struct PcmStreamLimit {
+	float *need[2] = {nullptr, nullptr};
+	float *frames[2] = {nullptr, nullptr};
+	int *meters = nullptr;
+	float *needRow = nullptr, *rRow = nullptr;
+	long long needPitch = 0, rPitch = 0;
+	const float *window = nullptr; // limitWindow(H)'s floats, device
+	int H = 0;
+};
+inline size_t pcmStreamLimitSetFloats(int S, int C, int H) { return (size_t)S*4*H + (size_t)S*C*2*H; } // one set of lines: need, then the frames
+// need <- 1, frames <- +0.0 in both sets of `stream` (-1: of every stream), on `st`
+void launchPcmLimitClear(const PcmStreamLimit &lim, int S, int C, int stream, hipStream_t st);
+// launchPcmOut's levelled form for a call in which a limited stream has frames (maxLimited >= 1: the largest count of such a stream): the two
+// passes, then the conversion -- a kernel of its own -- that takes a limited stream's frame i from its line (i < 2H) or from the image at
+// i - 2H and multiplies it by r as well; a stream without the setting gets the levelled form's bytes.  Three launches on `st`
+void launchPcmOutLimited(int format, const float *in, long long inStreamStride, long long inChannelStride, void *out, long long outStreamStride, long long outFrameStride,
+                         const int *counts, int S, int C, int maxFrames, int maxLimited, unsigned *overs, hipStream_t st, const PcmDither *dither, const PcmLevelIo &level,
+                         const PcmStreamLimit &lim);
 // Sample-rate conversion of whole clips in front of the engine (include/smst.h, "Resample", has the definition; smst_resample.h the kernel).
 // A ratio L/M, reduced, the batch's rate over the clip's: N frames become Nr = ceil(N*L/M), frame n at input position n*M/L, formed by the T = 2H
 // taps of its phase's row of a Kaiser-windowed sinc in float64, rounded once.  ResampleShape: what a ratio fixes -- H, T and the pitch of a

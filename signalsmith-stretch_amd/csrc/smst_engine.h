@@ -136,6 +136,7 @@ public:
 	void setLimiterLookahead(int frames);
 	int limiterLookahead() const { return limitH; }
 	void prepareLimiter();
+	const float *limiterWindow() const { return dLimitWin; } // (device; null before the first prepareLimiter(): the stream limiter of the C ABI reads it too)
 	bool readLimiter(float *minGain, long long *limitedFrames);
 	// the true peaks of the newest exact call that measured, [S] (0: a stream it did not measure); false: none has.  Synchronises
 	bool readTruePeaks(float *truePeaks);

@@ -9,7 +9,7 @@
 // truePeakFrameBits, the true-peak kernel's own sums), and behind the last channel forms need from the maximum, the stream's gain in its
 // limited form (clipGain) and the ceiling: one fp32 multiply, one comparison, one correctly rounded division.
 //
-// kClipLimitGain.  A workgroup stages its tile's need with 2H frames on either side (1.0 outside the clip) into LDS; a tile in which all of
+// kClipLimitGain (its body is limitGainTile, which the streaming form shares).  A workgroup stages its tile's need with 2H frames on either side (1.0 outside the clip) into LDS; a tile in which all of
 // that is 1.0 writes r = 1.0f and ends -- the definition's idle rule makes this exact.  Else the windowed minimum by doubling: M_1 = need,
 // M_2k[i] = min(M_k[i], M_k[i + k]) between two LDS arrays while 2k <= 2H + 1, then hold[i] = min(M_k[i], M_k[i + 2H + 1 - k]) -- two
 // overlapping spans of k frames that cover the 2H + 1; the minimum is exact and associative, so the scheme does not show in the result.
@@ -74,28 +74,23 @@ __global__ __launch_bounds__(256) void kClipLimitNeed(const float *__restrict__ 
 	for (int i = 0; i < kLimitRun; ++i) if (f + i < frames) row[f + i] = limitNeed(m[i], g, l.ceiling);
 }
 
-// grid (tiles of kLimitTile frames in clip order, S), 256 threads, limitGainLdsBytes(H) of LDS.  win: [2H + 1]; meters: [2][S]
-__global__ __launch_bounds__(256) void kClipLimitGain(const ClipSeg *__restrict__ segs, const PcmLevel *__restrict__ table, int S, const float *__restrict__ need, float *__restrict__ r,
-		long long pitch, const float *__restrict__ win, int H, int *__restrict__ meters) {
-	extern __shared__ __attribute__((aligned(16))) unsigned char smemRaw[];
-	const int s = blockIdx.y, tid = threadIdx.x, span = kLimitTile + 4*H, W = 2*H + 1;
-	float *cur = reinterpret_cast<float *>(smemRaw), *nxt = cur + span; // [span] each
-	int *words = reinterpret_cast<int *>(nxt + span);                   // [0]: the tile is active; [1 ... 4], [5 ... 8]: the wavefronts' meters
-	if (!pcmLimited(table[s])) return;
-	const ClipSeg g0 = segs[2*s], g1 = segs[2*s + 1];
-	if (g0.zeros || g1.zeros) return;
-	const int N = max(g0.count, 0) + max(g1.count, 0);
-	if ((long long)blockIdx.x*kLimitTile >= N) return;
-	const int t0 = int(blockIdx.x)*kLimitTile, frames = min(N - t0, kLimitTile);
-	const float *row = need + (size_t)s*pitch;
-	float *out = r + (size_t)s*pitch + t0;
+// Steps 4 to 6 of the definition for one tile, the one definition of kClipLimitGain and of the streaming form (kPcmLimitGain,
+// smst_stream_limiter.h): r of the `frames` frames from t0 on -> out[0 ... frames), and the stream's two meter words.  need(j) = row[j] for
+// lo <= j < hi and 1 outside; the tile's own frames lie inside.  Every lane of the workgroup calls it, with limitGainLdsBytes(H) of LDS at
+// smemRaw.  Staging, the idle rule, the doubling minimum, the float64 sum in order, min(float(y), need) and the meter reduction; the loops run
+// over the frames the tile has plus 4H.  win: [2H + 1]; meters: [2][S]
+__device__ inline void limitGainTile(unsigned char *smemRaw, const float *__restrict__ row, long long lo, long long hi, int t0, int frames, float *__restrict__ out,
+		const float *__restrict__ win, int H, int *__restrict__ meters, int s, int S) {
+	const int tid = threadIdx.x, span = frames + 4*H, W = 2*H + 1;
+	float *cur = reinterpret_cast<float *>(smemRaw), *nxt = cur + (kLimitTile + 4*H); // [limitSpan(H)] each
+	int *words = reinterpret_cast<int *>(nxt + (kLimitTile + 4*H));                   // [0]: the tile is active; [1 ... 4], [5 ... 8]: the wavefronts' meters
 	if (tid == 0) words[0] = 0;
 	__syncthreads();
-	// need(t0 - 2H + i) at cur[i]; outside the clip it is 1
+	// need(t0 - 2H + i) at cur[i]; outside [lo, hi) it is 1
 	bool active = false;
 	for (int i = tid; i < span; i += 256) {
 		const long long j = (long long)t0 - 2*H + i;
-		const float v = (j >= 0 && j < N) ? row[j] : 1.0f;
+		const float v = (j >= lo && j < hi) ? row[j] : 1.0f;
 		cur[i] = v;
 		active = active || v != 1.0f;
 	}
@@ -112,8 +107,8 @@ __global__ __launch_bounds__(256) void kClipLimitGain(const ClipSeg *__restrict_
 		__syncthreads();
 		float *t = cur; cur = nxt; nxt = t;
 	}
-	// hold(t0 - H + i) at nxt[i], i < kLimitTile + 2H: the 2H + 1 frames from t0 - 2H + i on, as two spans of len
-	for (int i = tid; i < kLimitTile + 2*H; i += 256) nxt[i] = fminf(cur[i], cur[i + W - len]);
+	// hold(t0 - H + i) at nxt[i], i < frames + 2H: the 2H + 1 frames from t0 - 2H + i on, as two spans of len
+	for (int i = tid; i < frames + 2*H; i += 256) nxt[i] = fminf(cur[i], cur[i + W - len]);
 	__syncthreads();
 	const float *hold = nxt;
 	unsigned deepest = 0u;
@@ -127,7 +122,7 @@ __global__ __launch_bounds__(256) void kClipLimitGain(const ClipSeg *__restrict_
 			lowest = fminf(lowest, v);
 			y += double(win[k])*double(v);
 		}
-		const float rr = lowest == 1.0f ? 1.0f : fminf(float(y), row[t0 + f]);
+		const float rr = lowest == 1.0f ? 1.0f : fminf(float(y), row[(long long)t0 + f]);
 		out[f] = rr;
 		deepest = max(deepest, 0x3f800000u - unsigned(__float_as_int(rr))); // (0 < r <= 1: need is, and r <= need)
 		limited += rr < 1.0f ? 1 : 0;
@@ -142,6 +137,20 @@ __global__ __launch_bounds__(256) void kClipLimitGain(const ClipSeg *__restrict_
 		if (most > 0) atomicMax(meters + s, most);
 		if (count > 0) atomicAdd(meters + S + s, count);
 	}
+}
+
+// grid (tiles of kLimitTile frames in clip order, S), 256 threads, limitGainLdsBytes(H) of LDS.  win: [2H + 1]; meters: [2][S]
+__global__ __launch_bounds__(256) void kClipLimitGain(const ClipSeg *__restrict__ segs, const PcmLevel *__restrict__ table, int S, const float *__restrict__ need, float *__restrict__ r,
+		long long pitch, const float *__restrict__ win, int H, int *__restrict__ meters) {
+	extern __shared__ __attribute__((aligned(16))) unsigned char smemRaw[];
+	const int s = blockIdx.y;
+	if (!pcmLimited(table[s])) return;
+	const ClipSeg g0 = segs[2*s], g1 = segs[2*s + 1];
+	if (g0.zeros || g1.zeros) return;
+	const int N = max(g0.count, 0) + max(g1.count, 0);
+	if ((long long)blockIdx.x*kLimitTile >= N) return;
+	const int t0 = int(blockIdx.x)*kLimitTile, frames = min(N - t0, kLimitTile);
+	limitGainTile(smemRaw, need + (size_t)s*pitch, 0, N, t0, frames, r + (size_t)s*pitch + t0, win, H, meters, s, S);
 }
 
 void limitWindow(int H, float *win) {
