@@ -825,8 +825,8 @@ int smst_debug_clip_loudness_range(int device, int streams, int channels, const 
  * and smst_batch_process_pcm, _seek_pcm and _output_seek_pcm return SMST_ERR_INVALID, before anything runs, if a stream that takes part has a
  * ratio other than 1/1: skipping the stage silently would be a lie.  smst_batch_flush_pcm has no input and is unaffected.  The too-short and
  * left-out streams of a call stay as they are.
- * Out of scope: resampling the output; resampling in the streaming or the planar calls; irrational or time-varying ratios; a quality
- * setting; a fused PCM-to-resampled kernel without the raw image.
+ * Out of scope: resampling the output; resampling in the planar calls (the streaming frame calls have a setting of their own: "Stream
+ * resample" below); irrational or time-varying ratios; a quality setting; a fused PCM-to-resampled kernel without the raw image.
  * SMST_ERR_INVALID with a message that names the limit: a term outside [1, SMST_RESAMPLE_MAX_TERM]; a ratio beyond 4.5 either way; a ninth
  * distinct ratio; a stream index out of range; a null batch; in a call, an Nr that does not fit an int. */
 #define SMST_RESAMPLE_MAX_TERM 640
@@ -851,6 +851,70 @@ int smst_debug_resample_taps(int up, int down, float *out, int *taps);
 int smst_debug_clip_resample(int device, int streams, int channels, const int *counts, const int *ratios,
                              const float *image, long long imageStreamStride, long long imageChannelStride,
                              const int *segments, float *out, long long outStreamStride, long long outChannelStride);
+/* ---- Stream resample (EXTENSION; opt-in: a batch that never calls smst_batch_set_pcm_stream_resample launches the kernels, writes the bytes and counts the launches it did before) ----
+ * The converter above knows a whole clip.  A live 44.1 kHz source in a 48 kHz batch had to be resampled on the CPU before every
+ * smst_batch_process_pcm.  The converter is a non-recursive FIR, so it has an exact streaming form: with the last T - 1 input frames carried
+ * per stream and the output H input frames late, a stream cut into calls in any way hands the engine, bit for bit, the frames that the clip
+ * converter makes of the same material.
+ *
+ * It is a per-stream setting of its own, a reduced ratio L/M with the shape H, T = 2H and the limits, table and arithmetic of "Resample", NOT
+ * the whole-clip ratio: that one stays refused in the streaming calls.  A stream may carry both; each call family reads its own.
+ *
+ * Definition.  Let x(0), x(1), ... be the frames handed for the stream through smst_batch_process_pcm / smst_batch_seek_pcm since its line
+ * was last cleared, fed their number, and R(q) = ceil(max(q, 0)*L/M) in 64-bit integers.  After fed frames the engine has been handed, in
+ * order, the first made = R(fed - H) frames of "Resample" applied to the clip [x(0) ... x(fed - 1)]: frame n sits at i = (n*M)/L,
+ * p = (n*M) mod L and is float32(sum_j double(c[p][j])*double(x(i + j - (H - 1)))), j ascending from 0.0, x of a negative index = +0.0.
+ * Frame n is produced once i + H <= fed - 1, so the clip's right edge never enters and the result does not depend on the cuts.
+ *   Frames per call.  A call that hands n frames gives the engine k = R(fed + n - H) - R(fed - H) frames; k may be 0.  The call then
+ *   behaves exactly as if the caller had handed those k planar frames to smst_batch_process / _seek: the engine's rate is k/outSamples, the
+ *   silence gate and everything behind it see the k frames.  k moves by +-1 from call to call where n*L/M is no integer, and the first
+ *   calls are short by the latency; a caller who wants a fixed k asks smst_batch_pcm_stream_resample_need for the n that gives it.
+ *   Known answers.  160/147, calls of 441 frames: k = 446, 480, 480, 480.  147/160 (H = 35), calls of 128: k = 86, 118, 117, 118.  3/2,
+ *   37 frames with x(2) = 1, cut 3, 2, 32: k = 0, 0, 8, and the 8 frames are "Resample"'s known answer bca067e3 be4717b5 3ed8327b 3f7ae0ea
+ *   3ed8327b be4717b5 bca067e3 3dddb185.
+ *   Latency.  H frames at the stream's own rate: 32 for an upsampling ratio, ceil(32*M/L) otherwise (smst_batch_pcm_stream_resample_latency).
+ *   Ending a stream.  The caller hands H frames of zeros: the engine has then been handed exactly the Nr = ceil(N*L/M) frames of the clip form.
+ *   The line holds the last T - 1 planar fp32 frames of every channel; fed and made are 64-bit host counters.  No device readback and no host
+ *   synchronisation is added.  It is cleared (frames <- +0.0, fed = made = 0) by the setter for the stream, by smst_batch_reset, and by
+ *   smst_batch_seek_pcm for the streams that take part, BEFORE their frames go in: a seek is a jump in the source.  A stream with no frame
+ *   in a call keeps its line.
+ *   Mixing.  A stream without the setting gets, in the same call, the bytes it gets in a batch without any.
+ *   Ratio tables.  The setting shares the batch's ratio tables and its SMST_RESAMPLE_MAX_RATIOS slots with the whole-clip setting: a slot is
+ *   live while either setting of any stream uses it.
+ *
+ * How.  In a call where a stream of the batch has the setting, the frame conversion runs once per destination that has frames -- the plain
+ * streams into the engine's input image as ever, the others into a raw planar image -- and one kernel (csrc/smst_stream_resample.h;
+ * DESIGN.md) forms the k frames of each such stream into the engine's image, staging every tile's input span from the line and the raw
+ * image, by the clip converter's own tap sum (one device function for both); the workgroup behind a stream's last tile writes its new
+ * line.  The lines exist twice, a call reads one set and writes the other, and everything is ordered by the batch's stream.  Lines and call
+ * tables live in device memory, allocated by the first setter call with a ratio other than 1/1, never in a call, and counted in
+ * smst_batch_workspace_bytes; the raw image grows with the first call that needs it; a steady-state call allocates nothing.
+ * Out of scope: resampling the output; the planar calls; smst_batch_output_seek_pcm; stretch_cli (a whole-file tool, which has --rate);
+ * time-varying ratios.
+ * SMST_ERR_INVALID with a message, before anything runs: the limits of "Resample"; a stream index out of range; a null batch;
+ * smst_batch_output_seek_pcm and smst_batch_exact_pcm with a participating stream that has the setting (smst_batch_exact_pcm has
+ * smst_batch_set_pcm_resample); a k or a count that does not fit an int. */
+/* stream = -1: every stream.  1/1 turns the setting off.  Clears the line of the stream(s).  The first call with another ratio allocates the
+ * lines and the call tables, and builds the ratio's table where the batch does not have it yet */
+int smst_batch_set_pcm_stream_resample(smst_batch *b, int stream, int up, int down);
+/* the stream's reduced ratio (1/1: none); either pointer may be null */
+int smst_batch_pcm_stream_resample(const smst_batch *b, int stream, int *up, int *down);
+/* H of the stream's ratio, the frames at the stream's own rate by which its input is late; 0 without the setting */
+int smst_batch_pcm_stream_resample_latency(const smst_batch *b, int stream, int *frames);
+/* k of the stream's next call if it hands inSamples frames (inSamples itself without the setting), or a negative code.  fresh != 0: as after
+ * a clear -- what the call behind a seek or a reset gives */
+long long smst_batch_pcm_stream_resample_frames(const smst_batch *b, int stream, long long inSamples, int fresh);
+/* the smallest n whose call gives the engine k >= frames, frames >= 1: max(0, ((made + frames - 1)*M)/L + H + 1 - fed) (frames itself
+ * without the setting), or a negative code */
+long long smst_batch_pcm_stream_resample_need(const smst_batch *b, int stream, long long frames, int fresh);
+/* test hook: `calls` launches of the stream-resample kernel in sequence, with the carried lines, planar fp32 to planar fp32 (host pointers,
+ * strides in floats, staged whole as far behind a 16-byte boundary as the caller's).  counts: [calls][streams], negative = the stream takes
+ * no part in that call; ratios: [streams][2] up, down (1/1: the stream's rows of `out` are left alone); fed0: [streams] or null -- the line
+ * starts as zeros at that position (fed = fed0, made = R(fed0 - H)); image: each stream's frames in order from column 0 of its rows; out:
+ * each stream's frames as made, in order from column 0, at most maxFrames of them; made: [streams], the frames written (may be null) */
+int smst_debug_pcm_stream_resample(int device, int streams, int channels, int calls, const int *counts, const int *ratios, const long long *fed0,
+                                   const float *image, long long imageStreamStride, long long imageChannelStride,
+                                   float *out, long long outStreamStride, long long outChannelStride, int maxFrames, long long *made);
 /* per stream, since the last take: peaks[s] = the largest |v| the levelled output conversions met BEFORE the gain (0 if none); gains[s] = the
  * gain the newest levelled conversion of stream s applied (1 before any).  Either may be null.  Synchronises the batch; resets the peaks,
  * not the gains. */

@@ -173,6 +173,12 @@ _SIGNATURES = {
     "smst_resample_ratio": (C.c_int, [C.c_double, C.c_double, _ip, _ip]),
     "smst_debug_resample_taps": (C.c_int, [C.c_int, C.c_int, _fp, _ip]),
     "smst_debug_clip_resample": (C.c_int, [C.c_int, C.c_int, C.c_int, _ip, _ip, C.c_void_p, _ll, _ll, _ip, C.c_void_p, _ll, _ll]),
+    "smst_batch_set_pcm_stream_resample": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
+    "smst_batch_pcm_stream_resample": (C.c_int, [C.c_void_p, C.c_int, _ip, _ip]),
+    "smst_batch_pcm_stream_resample_latency": (C.c_int, [C.c_void_p, C.c_int, _ip]),
+    "smst_batch_pcm_stream_resample_frames": (_ll, [C.c_void_p, C.c_int, _ll, C.c_int]),
+    "smst_batch_pcm_stream_resample_need": (_ll, [C.c_void_p, C.c_int, _ll, C.c_int]),
+    "smst_debug_pcm_stream_resample": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _ip, _ip, C.POINTER(_ll), C.c_void_p, _ll, _ll, C.c_void_p, _ll, _ll, C.c_int, C.POINTER(_ll)]),
     "smst_batch_synchronize": (C.c_int, [C.c_void_p]),
     "smst_batch_hip_stream": (C.c_void_p, [C.c_void_p]),
     "smst_batch_enable_profiling": (C.c_int, [C.c_void_p, C.c_int]),
@@ -448,6 +454,22 @@ def debug_resample_taps(up, down, lib=None):
     table = np.zeros((int(up)//g, taps.value), np.float32)
     _check(lib, lib.smst_debug_resample_taps(int(up), int(down), table.ctypes.data_as(_fp), C.byref(taps)))
     return table
+
+
+def debug_pcm_stream_resample(counts, ratios, channels, image, image_ss, image_cs, out, out_ss, out_cs, max_frames, fed0=None, device=0, lib=None):
+    """smst_debug_pcm_stream_resample on numpy buffers (planar float32, 1-d views whose first element is the first stream's first row; strides
+    in floats).  counts: int [calls, S], negative = no part; ratios: [S] of (up, down); fed0: [S] int64 or None.  ``out`` is written in
+    place -> made, int64 [S]: the frames written per stream"""
+    lib = lib or load_library()
+    n = np.ascontiguousarray(np.asarray(counts, np.int32))
+    calls, S = n.shape
+    r = np.ascontiguousarray(np.asarray(ratios, np.int32).reshape(S, 2))
+    start = None if fed0 is None else np.ascontiguousarray(np.asarray(fed0, np.int64).reshape(S))
+    made = np.zeros(S, np.int64)
+    _check(lib, lib.smst_debug_pcm_stream_resample(device, S, channels, calls, n.ctypes.data_as(_ip), r.ctypes.data_as(_ip),
+                                                   None if start is None else start.ctypes.data_as(C.POINTER(_ll)), C.c_void_p(image.ctypes.data), image_ss, image_cs,
+                                                   C.c_void_p(out.ctypes.data), out_ss, out_cs, int(max_frames), made.ctypes.data_as(C.POINTER(_ll))))
+    return made
 
 
 def debug_clip_resample(counts, ratios, channels, image, image_ss, image_cs, segments, out, out_ss, out_cs, device=0, lib=None):
@@ -969,6 +991,38 @@ class StretchBatch:
         """Resample in front of exactFrames (include/smst.h, "Resample"): the stream's clips are at down/up of the batch's rate and are
         resampled on the device, by the ratio up/down, before the engine sees them.  1/1 turns it off; stream = -1: every stream."""
         _check(self.lib, self.lib.smst_batch_set_pcm_resample(self.h, int(stream), int(up), int(down)))
+
+    def set_pcm_stream_resample(self, up, down, stream=-1):
+        """Resample in front of processFrames / seekFrames (include/smst.h, "Stream resample"): the stream's frames are at down/up of the
+        batch's rate and are resampled on the device, by the ratio up/down, with the last T - 1 frames carried from call to call; the engine
+        gets them H frames late.  1/1 turns it off; stream = -1: every stream.  Clears the stream's line."""
+        _check(self.lib, self.lib.smst_batch_set_pcm_stream_resample(self.h, int(stream), int(up), int(down)))
+
+    def pcm_stream_resample(self, stream):
+        """-> (up, down), the stream's reduced streaming ratio; (1, 1): none"""
+        up, down = C.c_int(0), C.c_int(0)
+        _check(self.lib, self.lib.smst_batch_pcm_stream_resample(self.h, int(stream), C.byref(up), C.byref(down)))
+        return up.value, down.value
+
+    def stream_resample_latency(self, stream):
+        """-> H, the frames at the stream's own rate by which its input is late (0 without the setting)"""
+        frames = C.c_int(0)
+        _check(self.lib, self.lib.smst_batch_pcm_stream_resample_latency(self.h, int(stream), C.byref(frames)))
+        return frames.value
+
+    def stream_resample_frames(self, stream, in_samples, fresh=False):
+        """-> k, the frames the engine gets from the stream's next call if it hands in_samples frames (fresh: as after a clear)"""
+        k = int(self.lib.smst_batch_pcm_stream_resample_frames(self.h, int(stream), int(in_samples), 1 if fresh else 0))
+        if k < 0:
+            _check(self.lib, k)
+        return k
+
+    def stream_resample_need(self, stream, frames, fresh=False):
+        """-> the smallest n whose call gives the engine at least ``frames`` frames of the stream (fresh: as after a clear)"""
+        n = int(self.lib.smst_batch_pcm_stream_resample_need(self.h, int(stream), int(frames), 1 if fresh else 0))
+        if n < 0:
+            _check(self.lib, n)
+        return n
 
     def pcm_resample(self, stream):
         """-> (up, down), the stream's reduced ratio; (1, 1): not resampled"""

@@ -388,6 +388,39 @@ struct PcmOutState {
 	}
 };
 
+// The input side of a batch's frame-format streaming calls where a stream has the setting of include/smst.h, "Stream resample": per stream the
+// two 64-bit counters, which set of its two carried lines the next call reads and whether the line counts as cleared; the lines (both sets in
+// one buffer), allocated by the first setter call with a ratio other than 1/1, and the raw image, which grows on demand as the images do.  The
+// ratios, their tables and their slots are the engine's (Batch::setResample, streaming).  The owner has selected the device wherever HIP is called.
+struct PcmStreamResampleState {
+	struct Stream { long long fed = 0, made = 0; unsigned char set = 0, fresh = 1; };
+	std::vector<Stream> stream;
+	std::vector<int> counts; // the frames the engine gets from each stream in the newest call
+	Buffer<float, false> dLines;
+	DeviceFloats dRaw;
+	size_t tableBytes = 0;   // of the call tables' device twins (both sets)
+	void create(int S) { stream.assign((size_t)S, Stream()); counts.assign((size_t)S, 0); }
+	size_t workspaceBytes() const { return (dLines.cap + dRaw.cap)*sizeof(float) + tableBytes; }
+	// frames <- +0.0, fed = made = 0 for the stream (-1: every one): the next call reads zeros in the place of the line
+	void clear(int stream_) {
+		for (size_t s = stream_ < 0 ? 0 : size_t(stream_); s < (stream_ < 0 ? stream.size() : size_t(stream_) + 1); ++s) { stream[s].fed = stream[s].made = 0; stream[s].fresh = 1; }
+	}
+	static bool any(const Batch &e) {
+		for (int s = 0; s < e.streams(); ++s) if (e.streamResampled(s)) return true;
+		return false;
+	}
+	// k of a call that hands the stream n frames (fresh: as after a clear); Error where it does not fit an int
+	long long framesOf(const Batch &e, int s, long long n, bool fresh) const {
+		if (!e.streamResampled(s)) return n;
+		const smst::ResampleShape &g = e.streamResampleShape(s);
+		const long long fed = fresh ? 0 : stream[s].fed;
+		if (n > (1LL << 40) || fed > (1LL << 62) - n) throw smst::Error("stream resample: stream " + std::to_string(s) + ": " + std::to_string(n) + " frames give the engine more than 2147483647 (k must fit an int)");
+		const long long k = smst::streamResampleDue(fed + n - g.H, g.L, g.M) - smst::streamResampleDue(fed - g.H, g.L, g.M);
+		if (k > 0x7fffffffLL) throw smst::Error("stream resample: stream " + std::to_string(s) + ": " + std::to_string(n) + " frames give the engine " + std::to_string(k) + ", more than 2147483647 (k must fit an int)");
+		return k;
+	}
+};
+
 struct smst_batch {
 	std::unique_ptr<Batch> engine;
 	// host staging (SMST_MEM_HOST)
@@ -404,10 +437,13 @@ struct smst_batch {
 		Buffer<unsigned char, true> host;
 		Buffer<unsigned char, false> dev;
 		smst::PcmOutCall out;
+		Buffer<unsigned char, true> resHost; // the input side's table of a call with a stream-resampled stream (smst::StreamResampleTableLayout),
+		Buffer<unsigned char, false> resDev; // allocated -- both sets -- by the first setter call with a ratio other than 1/1
 		int mostLimited = 0; // the largest count of a stream that the call's output limits ("Stream limiter"); 0: the call launches what it did without the setting
 	};
 	smst::TwoSets<PcmTable> pcmTables; // (smst_staging.h)
 	PcmOutState pcmOut;
+	PcmStreamResampleState pcmIn;
 	~smst_batch() { if (engine) hipSetDevice(engine->device()); } // (the buffers above go behind it, the engine last)
 };
 
@@ -512,6 +548,7 @@ int smst_batch_create_ex(smst_batch **out, int streams, int channels, int block,
 	std::unique_ptr<smst_batch> b(new smst_batch());
 	b->engine.reset(new Batch(streams, channels, block, interval, split != 0, device, seed, (flags & SMST_FLAG_HALF_STATE) != 0));
 	b->pcmOut.create(streams, channels);
+	b->pcmIn.create(streams);
 	*out = b.release();
 	return SMST_OK;
 	SMST_CATCH
@@ -542,7 +579,7 @@ BATCH_Q(smst_batch_output_latency, b->engine->outputLatency())
 BATCH_Q(smst_batch_seek_length, b->engine->seekLength())
 BATCH_Q(smst_batch_half_state, b->engine->halfPrecisionState() ? 1 : 0)
 int smst_batch_output_seek_length(const smst_batch *b, float rate) { if (!b || !b->engine) return fail("null batch"); return b->engine->outputSeekLength(rate); }
-long long smst_batch_workspace_bytes(const smst_batch *b) { if (!b || !b->engine) return fail("null batch"); return (long long)(b->engine->workspaceBytes() + b->pcmOut.workspaceBytes()); }
+long long smst_batch_workspace_bytes(const smst_batch *b) { if (!b || !b->engine) return fail("null batch"); return (long long)(b->engine->workspaceBytes() + b->pcmOut.workspaceBytes() + b->pcmIn.workspaceBytes()); }
 
 #define BATCH_CALL(...) if (!b || !b->engine) return fail("null batch"); SMST_TRY __VA_ARGS__; return SMST_OK; SMST_CATCH
 
@@ -550,6 +587,7 @@ int smst_batch_reset(smst_batch *b) {
 	BATCH_CALL({
 		b->engine->reset();
 		b->pcmOut.clearStreamLimitLines(*b->engine, -1); // (the stream limiter's lines begin again, in stream order behind the calls in flight)
+		b->pcmIn.clear(-1);                              // (... and the stream resampler's)
 	})
 }
 int smst_batch_set_transpose_factor(smst_batch *b, int s, float m, float t) { BATCH_CALL(b->engine->setTransposeFactor(s, m, t)) }
@@ -795,8 +833,73 @@ static void pcmRawOut(smst_batch *b, void *out, long long ss, long long fs, cons
 }
 
 // Raw frames -> the planar image b->dIn [S][C][maxLen] (returns maxLen), on the engine's stream and in front of every reader of the call's input
-static int pcmStageIn(smst_batch *b, smst_batch::PcmTable &c, const void *in, long long ss, long long fs, const int *n, int format, int memory) {
+// A streaming call in which a stream has the stream-resample setting (include/smst.h, "Stream resample"): kPcmIn runs once per destination
+// image that has frames -- the plain streams into b->dIn as ever, the streams with the setting into the raw image --, and kPcmStreamResample
+// forms those streams' k frames into b->dIn from their lines and the raw image.  b->pcmIn.counts: what the engine gets.  clearLines: a seek --
+// the lines of the streams that take part are cleared before their frames go in.  Every refusal comes before anything changes
+static int pcmStageInResampled(smst_batch *b, smst_batch::PcmTable &c, const void *in, long long ss, long long fs, const int *n, int format, int memory, bool clearLines) {
 	Batch &e = *b->engine;
+	PcmStreamResampleState &r = b->pcmIn;
+	const int S = e.streams(), C = e.channels();
+	const smst::StreamResampleTableLayout at(S);
+	int most = 0, mostPlain = 0, mostRaw = 0, mostK = 0, maxLen = 1;
+	for (int s = 0; s < S; ++s) {
+		const int frames = std::max(n[s], 0);
+		most = std::max(most, frames);
+		if (e.streamResampled(s)) {
+			r.counts[s] = int(r.framesOf(e, s, frames, clearLines || r.stream[s].fresh));
+			mostRaw = std::max(mostRaw, frames);
+			mostK = std::max(mostK, r.counts[s]);
+		} else {
+			r.counts[s] = n[s];
+			mostPlain = std::max(mostPlain, frames);
+		}
+		maxLen = std::max(maxLen, r.counts[s]);
+	}
+	const int rawLen = std::max(mostRaw, 1), tileFrames = smst::streamResampleTileFrames(mostK);
+	ensureStage(b, b->dIn, (size_t)S*C*maxLen);
+	ensureStage(b, r.dRaw, (size_t)S*C*rawLen);
+	hipSetDevice(e.device());
+	int maxSpanPitch = 4;
+	for (int s = 0; s < S; ++s) {
+		const int frames = std::max(n[s], 0);
+		smst::StreamResampleEntry entry{nullptr, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+		const bool on = e.streamResampled(s);
+		if (on) {
+			PcmStreamResampleState::Stream &st = r.stream[s];
+			if (clearLines && n[s] >= 0) { st.fed = st.made = 0; st.fresh = 1; }
+			const smst::ResampleShape &g = e.streamResampleShape(s);
+			entry = smst::StreamResampleEntry{e.streamResampleTaps(s), st.fed, st.made, 0, 0, frames, r.counts[s], g.L, g.M, g.H, g.T, g.pitch, st.set, st.fresh, 0};
+			maxSpanPitch = std::max(maxSpanPitch, smst::resampleSpanPitchOf(g.L, g.M, g.T, tileFrames));
+			if (frames > 0) { st.fed += frames; st.made += r.counts[s]; st.set ^= 1; st.fresh = 0; } // (a stream with no frame keeps its line)
+		}
+		at.plainCounts(c.resHost)[s] = on ? 0 : frames;
+		at.rawCounts(c.resHost)[s] = on ? frames : 0;
+		at.entries(c.resHost)[s] = entry;
+	}
+	if (hipMemcpyAsync(c.resDev, c.resHost, at.bytes(), hipMemcpyHostToDevice, e.stream()) != hipSuccess) throw smst::Error("hipMemcpyAsync (H2D) failed", true);
+	const void *raw = in;
+	long long rawSS = ss, rawFS = fs;
+	if (memory == SMST_MEM_HOST && most > 0) {
+		pcmRawIn(b, in, ss, fs, n, most, format);
+		raw = b->dPcmIn; rawSS = pcmRowElems(most, C); rawFS = C;
+	}
+	smst::launchPcmIn(format, raw, rawSS, rawFS, b->dIn, (long long)C*maxLen, maxLen, at.plainCounts(c.resDev), S, C, mostPlain, e.stream());
+	smst::launchPcmIn(format, raw, rawSS, rawFS, r.dRaw, (long long)C*rawLen, rawLen, at.rawCounts(c.resDev), S, C, mostRaw, e.stream());
+	if (mostRaw > 0)
+		smst::launchPcmStreamResample(r.dRaw, (long long)C*rawLen, rawLen, b->dIn, (long long)C*maxLen, maxLen, r.dLines, (long long)(r.dLines.cap/2), at.entries(c.resDev), S, C, mostK, maxSpanPitch, e.stream());
+	e.waitForStream(e.stream());
+	return maxLen;
+}
+// engineCounts (null: the call serves no stream-resample setting): the frames the engine gets from each stream -- n itself, or the k of "Stream resample"
+static int pcmStageIn(smst_batch *b, smst_batch::PcmTable &c, const void *in, long long ss, long long fs, const int *n, int format, int memory, const int **engineCounts = nullptr, bool clearLines = false) {
+	Batch &e = *b->engine;
+	if (engineCounts) *engineCounts = n;
+	if (engineCounts && PcmStreamResampleState::any(e)) {
+		const int maxLen = pcmStageInResampled(b, c, in, ss, fs, n, format, memory, clearLines);
+		*engineCounts = b->pcmIn.counts.data();
+		return maxLen;
+	}
 	const int S = e.streams(), C = e.channels();
 	const smst::PcmTableLayout at(S);
 	const Counts k = countsOf(n, S, at.inCounts(c.host));
@@ -1034,6 +1137,7 @@ static void refuseWholeClipLevel(const smst_batch *b, const unsigned char *activ
 			throw smst::Error("stream " + std::to_string(s) + " has the loudness-range meter flag or a loudness cap (smst_batch_set_pcm_loudness_range / _caps), which measure a whole clip: smst_batch_exact_pcm only");
 }
 static void refuseResampled(const Batch &e, const int *takesPart, const char *call); // (below, with the whole-clip calls)
+static void refuseStreamResampled(const Batch &e, const int *takesPart, const char *call);
 int smst_batch_process_pcm(smst_batch *b, const void *in, long long iss, long long ifs, const int *inSamples,
                            void *out, long long oss, long long ofs, const int *outSamples, int format, int memory) {
 	BATCH_CALL({
@@ -1044,9 +1148,10 @@ int smst_batch_process_pcm(smst_batch *b, const void *in, long long iss, long lo
 		refuseWholeClipLevel(b, nullptr);
 		refuseResampled(e, nullptr, "smst_batch_process_pcm");
 		smst_batch::PcmTable &c = beginPcmCall(b);
-		const int maxIn = pcmStageIn(b, c, in, iss, ifs, inSamples, format, memory);
+		const int *fed = inSamples; // (a stream with the stream-resample setting: its k)
+		const int maxIn = pcmStageIn(b, c, in, iss, ifs, inSamples, format, memory, &fed);
 		const int maxOut = pcmPrepareOut(b, c, outSamples, format, memory);
-		e.process(b->dIn, (long long)e.channels()*maxIn, maxIn, inSamples, b->dOut, (long long)e.channels()*maxOut, maxOut, outSamples);
+		e.process(b->dIn, (long long)e.channels()*maxIn, maxIn, fed, b->dOut, (long long)e.channels()*maxOut, maxOut, outSamples);
 		pcmStageOut(b, c, out, oss, ofs, maxOut, format, memory);
 		endPcmCall(b);
 	})
@@ -1058,8 +1163,9 @@ int smst_batch_seek_pcm(smst_batch *b, const void *in, long long ss, long long f
 		checkPcmSide(in, fs, inSamples, e.streams(), e.channels(), false);
 		refuseResampled(e, nullptr, "smst_batch_seek_pcm");
 		smst_batch::PcmTable &c = beginPcmCall(b);
-		const int maxLen = pcmStageIn(b, c, in, ss, fs, inSamples, format, memory);
-		e.seek(b->dIn, (long long)e.channels()*maxLen, maxLen, inSamples, rates);
+		const int *fed = inSamples;
+		const int maxLen = pcmStageIn(b, c, in, ss, fs, inSamples, format, memory, &fed, true);
+		e.seek(b->dIn, (long long)e.channels()*maxLen, maxLen, fed, rates);
 		endPcmCall(b);
 		if (memory == SMST_MEM_HOST) e.synchronize();
 	})
@@ -1084,6 +1190,7 @@ int smst_batch_output_seek_pcm(smst_batch *b, const void *in, long long ss, long
 		checkPcmFormat(format, memory);
 		checkPcmSide(in, fs, inputLengths, e.streams(), e.channels(), false);
 		refuseResampled(e, nullptr, "smst_batch_output_seek_pcm");
+		refuseStreamResampled(e, nullptr, "smst_batch_output_seek_pcm");
 		smst_batch::PcmTable &c = beginPcmCall(b);
 		const int maxLen = pcmStageIn(b, c, in, ss, fs, inputLengths, format, memory);
 		e.outputSeek(b->dIn, (long long)e.channels()*maxLen, maxLen, inputLengths);
@@ -1125,6 +1232,13 @@ static void refuseResampled(const Batch &e, const int *takesPart, const char *ca
 	for (int s = 0; s < e.streams(); ++s)
 		if ((!takesPart || takesPart[s] >= 0) && e.resampled(s))
 			throw smst::Error(std::string(call) + ": stream " + std::to_string(s) + " has a resample ratio other than 1/1 (smst_batch_set_pcm_resample): smst_batch_exact_pcm only");
+}
+// Stream resample (include/smst.h): that setting is served by smst_batch_process_pcm and _seek_pcm only
+static void refuseStreamResampled(const Batch &e, const int *takesPart, const char *call) {
+	for (int s = 0; s < e.streams(); ++s)
+		if ((!takesPart || takesPart[s] >= 0) && e.streamResampled(s))
+			throw smst::Error(std::string(call) + ": stream " + std::to_string(s) + " has the stream-resample setting (smst_batch_set_pcm_stream_resample), which acts in smst_batch_process_pcm and "
+			                  "smst_batch_seek_pcm only" + (std::strcmp(call, "smst_batch_exact_pcm") == 0 ? ": the whole-clip form is smst_batch_set_pcm_resample" : ""));
 }
 // ... and that call refuses a clip whose length at the batch's rate does not fit an int
 static long long resampledLengthChecked(const Batch &e, int s, long long inSamples) {
@@ -1168,6 +1282,7 @@ int smst_batch_exact_pcm(smst_batch *b, const void *in, long long iss, long long
 			if (outSamples[s] >= 0 && b->pcmOut.streamLimit[s].on)
 				throw smst::Error("stream " + std::to_string(s) + " has the stream limiter's setting (smst_batch_set_pcm_stream_limiter), which acts in smst_batch_process_pcm and smst_batch_flush_pcm: "
 				                  "the whole-clip form is smst_batch_set_pcm_limiter");
+		refuseStreamResampled(e, outSamples, "smst_batch_exact_pcm");
 		checkResampledLengths(e, inSamples, outSamples);
 		// a dithered call: the streams' modes and hashes ride in the _pcm calls' table (the frame index is the place in the clip: the counters
 		// are neither read nor moved); a levelled call: the level entries ride there too, and the loudness entries and the channel weights
@@ -1210,6 +1325,64 @@ long long smst_batch_resampled_length(const smst_batch *b, int stream, long long
 	if (stream < 0 || stream >= b->engine->streams()) throw smst::Error("stream index out of range");
 	if (inSamples < 0) throw smst::Error("resample: negative sample count");
 	return resampledLengthChecked(*b->engine, stream, inSamples);
+	SMST_CATCH
+}
+// Stream resample (include/smst.h): the ratios live in the engine beside the whole-clip ones, whose tables and slots they share; the lines,
+// the counters and the call tables here.  Everything is allocated by the setter, never in a call
+int smst_batch_set_pcm_stream_resample(smst_batch *b, int stream, int up, int down) {
+	BATCH_CALL({
+		Batch &e = *b->engine;
+		e.setResample(stream, up, down, true); // (every refusal, before anything changes)
+		hipSetDevice(e.device());
+		if (PcmStreamResampleState::any(e) && !b->pcmIn.dLines) {
+			const size_t set = (size_t)e.streams()*e.channels()*smst::kStreamResampleLine;
+			++b->stagingAllocs;
+			b->pcmIn.dLines.allocate(2*set, "stream resample lines");
+			if (hipMemsetAsync(b->pcmIn.dLines, 0, 2*set*sizeof(float), e.stream()) != hipSuccess) throw smst::Error("hipMemsetAsync (stream resample lines) failed", true);
+			b->pcmTables.create();
+			const size_t bytes = smst::StreamResampleTableLayout(e.streams()).bytes();
+			for (smst_batch::PcmTable &t : b->pcmTables.sets) {
+				t.resHost.allocate(bytes, "stream resample table");
+				t.resDev.allocate(bytes, "stream resample table");
+			}
+			b->pcmIn.tableBytes = 2*bytes;
+		}
+		b->pcmIn.clear(stream);
+	})
+}
+int smst_batch_pcm_stream_resample(const smst_batch *b, int stream, int *up, int *down) {
+	BATCH_CALL({
+		int l = 1, m = 1;
+		b->engine->streamResampleOf(stream, l, m);
+		if (up) *up = l;
+		if (down) *down = m;
+	})
+}
+int smst_batch_pcm_stream_resample_latency(const smst_batch *b, int stream, int *frames) {
+	BATCH_CALL({
+		if (stream < 0 || stream >= b->engine->streams()) throw smst::Error("stream index out of range");
+		if (frames) *frames = b->engine->streamResampled(stream) ? b->engine->streamResampleShape(stream).H : 0;
+	})
+}
+long long smst_batch_pcm_stream_resample_frames(const smst_batch *b, int stream, long long inSamples, int fresh) {
+	if (!b || !b->engine) return fail("null batch");
+	SMST_TRY
+	if (stream < 0 || stream >= b->engine->streams()) throw smst::Error("stream index out of range");
+	if (inSamples < 0) throw smst::Error("stream resample: negative sample count");
+	return b->pcmIn.framesOf(*b->engine, stream, inSamples, fresh != 0 || b->pcmIn.stream[stream].fresh);
+	SMST_CATCH
+}
+long long smst_batch_pcm_stream_resample_need(const smst_batch *b, int stream, long long frames, int fresh) {
+	if (!b || !b->engine) return fail("null batch");
+	SMST_TRY
+	const Batch &e = *b->engine;
+	if (stream < 0 || stream >= e.streams()) throw smst::Error("stream index out of range");
+	if (frames < 1 || frames > 0x7fffffffLL) throw smst::Error("stream resample: the frame count is below 1 or does not fit an int (1 ... 2147483647)");
+	if (!e.streamResampled(stream)) return frames;
+	const smst::ResampleShape &g = e.streamResampleShape(stream);
+	const PcmStreamResampleState::Stream &st = b->pcmIn.stream[stream];
+	const long long fed = fresh ? 0 : st.fed, made = fresh ? 0 : st.made;
+	return std::max(0LL, ((made + frames - 1)*g.M)/g.L + g.H + 1 - fed);
 	SMST_CATCH
 }
 int smst_resample_ratio(double fromRate, double toRate, int *up, int *down) {
@@ -1793,6 +1966,79 @@ int smst_debug_clip_resample(int device, int streams, int channels, const int *c
 	hip(hipGetLastError());
 	hip(hipStreamSynchronize(nullptr));
 	if (outBytes) hip(hipMemcpy(out, o0, outBytes, hipMemcpyDeviceToHost));
+	return SMST_OK;
+	SMST_CATCH
+}
+// the stream-resample kernel alone, call after call: see include/smst.h
+int smst_debug_pcm_stream_resample(int device, int streams, int channels, int calls, const int *counts, const int *ratios, const long long *fed0,
+                                   const float *image, long long imageSS, long long imageCS, float *out, long long outSS, long long outCS, int maxFrames, long long *made) {
+	SMST_TRY
+	if (streams < 1 || channels < 1 || channels > smst::kMaxChannels || calls < 0 || (calls > 0 && !counts) || !ratios || !image || !out || maxFrames < 0 || imageSS < 0 || imageCS < 0 || outSS < 0 || outCS < 0)
+		throw smst::Error("stream resample: bad arguments");
+	auto hip = [&](hipError_t err) { if (err != hipSuccess) throw smst::Error(std::string("stream resample: ") + hipGetErrorString(err), true); };
+	hip(hipSetDevice(device));
+	struct Stream { smst::ResampleShape g{0, 0, 0, 0, 0}; long long fed = 0, made = 0, at = 0, written = 0; int set = 0, fresh = 1; };
+	std::vector<Stream> st((size_t)streams);
+	std::vector<Buffer<float, false>> tables((size_t)streams); // (one per resampled stream: a hook's streams do not share them)
+	long long endIn = 0;
+	for (int s = 0; s < streams; ++s) {
+		int up = ratios[2*s], down = ratios[2*s + 1];
+		smst::resampleReduce(up, down);
+		long long total = 0;
+		for (int k = 0; k < calls; ++k) total += std::max(counts[(size_t)k*streams + s], 0);
+		if (total > 0x7fffffffLL) throw smst::Error("stream resample: a stream's counts add up to more than 2147483647");
+		if (up == 1 && down == 1) continue; // no setting: its rows of `out` are left alone
+		endIn = std::max(endIn, total);
+		st[s].g = smst::resampleShapeOf(up, down);
+		if (fed0) {
+			if (fed0[s] < 0 || fed0[s] > (1LL << 48)) throw smst::Error("stream resample: a starting position is negative or above 2^48");
+			st[s].fed = fed0[s];
+			st[s].made = smst::streamResampleDue(fed0[s] - st[s].g.H, up, down);
+		}
+		std::vector<float> table((size_t)st[s].g.L*st[s].g.pitch);
+		smst::resampleTaps(st[s].g, table.data());
+		tables[s].allocate(table.size(), "stream resample");
+		hip(hipMemcpy(tables[s], table.data(), table.size()*sizeof(float), hipMemcpyHostToDevice));
+	}
+	// host pointers are staged whole: every stream's rows, as far behind a 16-byte boundary as the caller's
+	const size_t imageBytes = endIn ? size_t((streams - 1)*imageSS + (channels - 1)*imageCS + endIn)*sizeof(float) : 0;
+	const size_t outBytes = maxFrames ? size_t((streams - 1)*outSS + (channels - 1)*outCS + maxFrames)*sizeof(float) : 0;
+	const size_t lineSet = (size_t)streams*channels*smst::kStreamResampleLine;
+	Buffer<unsigned char, false> dImage, dOut, dEntries;
+	Buffer<float, false> dLines;
+	dImage.allocate(imageBytes + 32, "stream resample");
+	dOut.allocate(outBytes + 32, "stream resample");
+	dEntries.allocate((size_t)streams*sizeof(smst::StreamResampleEntry), "stream resample");
+	dLines.allocate(2*lineSet, "stream resample");
+	unsigned char *i0 = dImage + reinterpret_cast<uintptr_t>(image)%16, *o0 = dOut + reinterpret_cast<uintptr_t>(out)%16;
+	if (imageBytes) hip(hipMemcpy(i0, image, imageBytes, hipMemcpyHostToDevice));
+	if (outBytes) hip(hipMemcpy(o0, out, outBytes, hipMemcpyHostToDevice));
+	hip(hipMemset(dLines, 0, 2*lineSet*sizeof(float)));
+	std::vector<smst::StreamResampleEntry> entries((size_t)streams);
+	for (int call = 0; call < calls; ++call) {
+		int mostK = 0, mostN = 0;
+		for (int s = 0; s < streams; ++s) {
+			const int n = counts[(size_t)call*streams + s];
+			entries[s] = smst::StreamResampleEntry{nullptr, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+			Stream &t = st[s];
+			if (t.g.L < 1 || n < 1) continue; // no setting, no part, or no frame: the line stays
+			const long long k = smst::streamResampleDue(t.fed + n - t.g.H, t.g.L, t.g.M) - t.made;
+			if (t.written + k > maxFrames) throw smst::Error("stream resample: maxFrames is smaller than the frames a stream makes");
+			entries[s] = smst::StreamResampleEntry{tables[s].p, t.fed, t.made, t.at, t.written, n, int(k), t.g.L, t.g.M, t.g.H, t.g.T, t.g.pitch, t.set, t.fresh, 0};
+			t.fed += n; t.made += k; t.at += n; t.written += k; t.set ^= 1; t.fresh = 0;
+			mostK = std::max(mostK, int(k)); mostN = std::max(mostN, n);
+		}
+		if (mostN < 1) continue;
+		int maxSpanPitch = 4;
+		for (int s = 0; s < streams; ++s) if (entries[s].L > 0) maxSpanPitch = std::max(maxSpanPitch, smst::resampleSpanPitchOf(entries[s].L, entries[s].M, entries[s].T, smst::streamResampleTileFrames(mostK)));
+		hip(hipMemcpy(dEntries, entries.data(), entries.size()*sizeof(smst::StreamResampleEntry), hipMemcpyHostToDevice));
+		smst::launchPcmStreamResample(reinterpret_cast<const float *>(i0), imageSS, imageCS, reinterpret_cast<float *>(o0), outSS, outCS, dLines, (long long)lineSet,
+		                              reinterpret_cast<const smst::StreamResampleEntry *>(dEntries.p), streams, channels, mostK, maxSpanPitch, nullptr);
+		hip(hipGetLastError());
+		hip(hipStreamSynchronize(nullptr));
+	}
+	if (outBytes) hip(hipMemcpy(out, o0, outBytes, hipMemcpyDeviceToHost));
+	if (made) for (int s = 0; s < streams; ++s) made[s] = st[s].written;
 	return SMST_OK;
 	SMST_CATCH
 }

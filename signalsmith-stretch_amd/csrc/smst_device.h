@@ -169,7 +169,7 @@ __host__ __device__ inline bool analysisWindowInCall(int B, int M, int I, int in
 // form" tests assert through these that BOTH forms really ran.
 enum LaunchKind {
 	LK_VOC_ALIGNED, LK_VOC_TWISTED, LK_VOC_INTERIOR, LK_VOC_STAGED, LK_VOC_GATHER, LK_VOC_N, LK_VOC_ONE, LK_VOC_ACROSS, LK_VOC_CONT, LK_CHAIN_UNFUSED,
-	LK_ANALYSE_TEAMS, LK_ANALYSE_PAIRS, LK_ANALYSE_TWIST, LK_TWIST_ROWS, LK_ANALYSE_FAST, LK_ANALYSE_GENERIC, LK_SYNTH_TEAMS, LK_SYNTH_FAST, LK_SYNTH_GENERIC, LK_SYNTH_EMIT, LK_EMIT_CARRIED, LK_FEED_ONE_PASS, LK_PCM_IN, LK_PCM_OUT, LK_CLIP_IN, LK_CLIP_OUT, LK_PCM_OUT_DITHERED, LK_CLIP_OUT_DITHERED, LK_PCM_OUT_LEVELLED, LK_CLIP_OUT_LEVELLED, LK_CLIP_PEAK, LK_CLIP_LOUDNESS, LK_CLIP_TRUE_PEAK, LK_CLIP_LIMIT_NEED, LK_CLIP_LIMIT_GAIN, LK_CLIP_OUT_LIMITED, LK_CLIP_LOUDNESS_RANGE, LK_CLIP_RESAMPLE, LK_PCM_LIMIT_FEED, LK_PCM_LIMIT_GAIN, LK_PCM_OUT_LIMITED, LK_COUNT
+	LK_ANALYSE_TEAMS, LK_ANALYSE_PAIRS, LK_ANALYSE_TWIST, LK_TWIST_ROWS, LK_ANALYSE_FAST, LK_ANALYSE_GENERIC, LK_SYNTH_TEAMS, LK_SYNTH_FAST, LK_SYNTH_GENERIC, LK_SYNTH_EMIT, LK_EMIT_CARRIED, LK_FEED_ONE_PASS, LK_PCM_IN, LK_PCM_OUT, LK_CLIP_IN, LK_CLIP_OUT, LK_PCM_OUT_DITHERED, LK_CLIP_OUT_DITHERED, LK_PCM_OUT_LEVELLED, LK_CLIP_OUT_LEVELLED, LK_CLIP_PEAK, LK_CLIP_LOUDNESS, LK_CLIP_TRUE_PEAK, LK_CLIP_LIMIT_NEED, LK_CLIP_LIMIT_GAIN, LK_CLIP_OUT_LIMITED, LK_CLIP_LOUDNESS_RANGE, LK_CLIP_RESAMPLE, LK_PCM_LIMIT_FEED, LK_PCM_LIMIT_GAIN, LK_PCM_OUT_LIMITED, LK_PCM_STREAM_RESAMPLE, LK_COUNT
 };
 long long launchCount(const char *name); // -1: unknown name
 
@@ -385,5 +385,22 @@ inline long long resampledLength(long long N, int L, int M) { return (N*L + M - 
 void resampleTaps(const ResampleShape &g, float *out);
 void launchClipResample(const float *raw, long long rawStreamStride, long long rawChannelStride, float *image, long long imageStreamStride, long long imageChannelStride,
                         const ClipSeg *segs, const ResampleEntry *entries, int S, int C, int maxFrames, int maxSpanPitch, hipStream_t st);
+
+// The converter's streaming form (include/smst.h, "Stream resample", has the definition; smst_stream_resample.h the kernel): a stream with the
+// setting has been handed `fed` raw frames since its line was last cleared, and the engine the first made = streamResampleDue(fed - H) frames
+// of "Resample" applied to them; a call that hands n frames completes k = streamResampleDue(fed + n - H) - made more.  What a batch carries,
+// device: per stream and channel the last T - 1 raw frames in a row of kStreamResampleLine floats, two sets [2][S][C][kStreamResampleLine],
+// of which a call reads the one its entry names and writes the other.  StreamResampleEntry: one per stream, device -- L == 0: the stream has
+// no setting, n < 1: it has no frame in the call; either way the kernel leaves its rows and its line alone.  fresh != 0: the line counts as
+// +0.0 (it was cleared); rawAt / outAt: the column of the call's first raw frame in the raw image and of its first frame in the engine's
+// image.  maxFrames: the largest k (sizes the grid; a launch with 0 still writes the lines); maxSpanPitch: the largest
+// resampleSpanPitchOf(..., streamResampleTileFrames(maxFrames)) of the launch's entries (sizes the LDS)
+constexpr int kStreamResampleLine = 288;                 // floats of a channel's line: T - 1 <= 287 (T = 288 at 2/9)
+struct StreamResampleEntry { const float *taps; long long fed, made, rawAt, outAt; int n, k, L, M, H, T, pitch, set, fresh, pad; };
+inline __host__ __device__ int resampleSpanPitchOf(int L, int M, int T, int frames) { return (((frames - 1)*M + L - 1)/L + T + 3)/4*4; }
+inline int streamResampleTileFrames(int maxFrames) { return maxFrames < 1 ? 1 : maxFrames < kResampleTile ? maxFrames : kResampleTile; }
+inline long long streamResampleDue(long long q, int L, int M) { return q <= 0 ? 0 : (q*L + M - 1)/M; } // R(q) = ceil(max(q, 0)*L/M)
+void launchPcmStreamResample(const float *raw, long long rawStreamStride, long long rawChannelStride, float *image, long long imageStreamStride, long long imageChannelStride,
+                             float *lines, long long lineSetStride, const StreamResampleEntry *entries, int S, int C, int maxFrames, int maxSpanPitch, hipStream_t st);
 
 } // namespace smst

@@ -422,6 +422,7 @@ void Batch::allocateCallTables() {
 	for (std::vector<int> *v : {&flushV.blockOut, &flushV.blockIn, &flushV.synthChannels, &outputSeekV.seekSamples, &outputSeekV.surplus, &outputSeekV.preOut, &outputSeekV.done,
 	                            &exactV.seekLen, &exactV.rest, &exactV.procOut, &exactV.flushN, &exactV.frames}) v->assign(S, 0);
 	resampleSlot.assign(S, -1);
+	streamResampleSlot.assign(S, -1);
 	for (std::vector<unsigned char> *v : {&flushV.runBlock, &flushV.on, &outputSeekV.mask, &exactV.run}) v->assign(S, 0);
 	outputSeekV.rates.assign(S, 1.0);
 	exactV.rates.assign(S, 0.0f);
@@ -1997,9 +1998,10 @@ void resampleReduce(int &up, int &down) {
 		throw Error("resample: the ratio " + std::to_string(up) + "/" + std::to_string(down) + " upsamples by more than 4.5 (2*up <= 9*down)");
 }
 
-void Batch::setResample(int stream, int up, int down) {
+void Batch::setResample(int stream, int up, int down, bool streaming) {
 	if (stream < -1 || stream >= S) throw Error("stream index out of range");
 	resampleReduce(up, down);
+	std::vector<int> &mine = streaming ? streamResampleSlot : resampleSlot; // (a slot's users are the streams of BOTH settings)
 	SMST_HIP(hipSetDevice(dev));
 	const bool none = up == 1 && down == 1;
 	const int first = stream < 0 ? 0 : stream, last = stream < 0 ? S : stream + 1;
@@ -2008,13 +2010,13 @@ void Batch::setResample(int stream, int up, int down) {
 	if (!none) {
 		int users[kResampleMaxRatios];
 		for (int k = 0; k < kResampleMaxRatios; ++k) users[k] = resampleSlots[k].users;
-		for (int s = first; s < last; ++s) if (resampleSlot[s] >= 0) --users[resampleSlot[s]];
+		for (int s = first; s < last; ++s) if (mine[s] >= 0) --users[mine[s]];
 		for (int k = 0; k < kResampleMaxRatios && target < 0; ++k) if (resampleSlots[k].taps && resampleSlots[k].shape.L == up && resampleSlots[k].shape.M == down) target = k;
 		for (int k = 0; k < kResampleMaxRatios && target < 0; ++k) if (users[k] == 0) target = k;
 		if (target < 0) throw Error("resample: " + std::to_string(up) + "/" + std::to_string(down) + " would be distinct ratio number " + std::to_string(kResampleMaxRatios + 1) +
 		                            " of the batch, at most " + std::to_string(kResampleMaxRatios) + " are live at a time (SMST_RESAMPLE_MAX_RATIOS)");
 	}
-	for (int s = first; s < last; ++s) if (resampleSlot[s] >= 0) { --resampleSlots[resampleSlot[s]].users; resampleSlot[s] = -1; }
+	for (int s = first; s < last; ++s) if (mine[s] >= 0) { --resampleSlots[mine[s]].users; mine[s] = -1; }
 	bool synced = false;
 	for (int k = 0; k < kResampleMaxRatios; ++k) { // a ratio that no stream has any more frees its slot (but the one that is about to be taken again)
 		ResampleSlot &slot = resampleSlots[k];
@@ -2036,13 +2038,19 @@ void Batch::setResample(int stream, int up, int down) {
 		wsBytes += taps.size()*sizeof(float);
 		SMST_HIP(hipMemcpy(slot.taps, taps.data(), taps.size()*sizeof(float), hipMemcpyHostToDevice));
 	}
-	for (int s = first; s < last; ++s) { resampleSlot[s] = target; ++slot.users; }
+	for (int s = first; s < last; ++s) { mine[s] = target; ++slot.users; }
 }
 
 void Batch::resampleOf(int stream, int &up, int &down) const {
 	if (stream < 0 || stream >= S) throw Error("stream index out of range");
 	up = down = 1;
 	if (resampleSlot[stream] >= 0) { up = resampleSlots[resampleSlot[stream]].shape.L; down = resampleSlots[resampleSlot[stream]].shape.M; }
+}
+
+void Batch::streamResampleOf(int stream, int &up, int &down) const {
+	if (stream < 0 || stream >= S) throw Error("stream index out of range");
+	up = down = 1;
+	if (streamResampleSlot[stream] >= 0) { up = resampleSlots[streamResampleSlot[stream]].shape.L; down = resampleSlots[streamResampleSlot[stream]].shape.M; }
 }
 
 long long Batch::resampledLengthOf(int stream, long long inSamples) const {

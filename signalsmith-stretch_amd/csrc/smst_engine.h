@@ -125,8 +125,15 @@ public:
 	// Resample (include/smst.h, "Resample"): a stream's ratio up/down, the batch's rate over its clips' rate; 1/1: none.  setResample reduces
 	// and checks the ratio (Error with the limit in its message) and, for the first stream that takes a ratio, builds the ratio's table and puts
 	// it into device memory -- never in a call; a ratio that no stream has any more frees its table.  stream -1: every stream
-	void setResample(int stream, int up, int down);
+	// streaming: the stream's OTHER setting, the one the streaming calls read (include/smst.h, "Stream resample") -- a ratio of its own per
+	// stream, which shares the tables and their kResampleMaxRatios slots: a slot is live while either setting of any stream uses it
+	void setResample(int stream, int up, int down, bool streaming = false);
 	bool resampled(int stream) const { return resampleSlot[stream] >= 0; }
+	bool streamResampled(int stream) const { return streamResampleSlot[stream] >= 0; }
+	void streamResampleOf(int stream, int &up, int &down) const;
+	// shape and table (device) of a stream that has the streaming setting
+	const ResampleShape &streamResampleShape(int stream) const { return resampleSlots[streamResampleSlot[stream]].shape; }
+	const float *streamResampleTaps(int stream) const { return resampleSlots[streamResampleSlot[stream]].taps; }
 	void resampleOf(int stream, int &up, int &down) const;
 	long long resampledLengthOf(int stream, long long inSamples) const; // Nr of a clip of the stream (inSamples itself where it has no ratio)
 	// The limiter's lookahead H in frames (include/smst.h, "Limiter"), 1 ... kLimitMaxLookahead, the batch's one.  prepareLimiter() puts the
@@ -347,7 +354,7 @@ private:
 	size_t clipRawCapacity = 0;
 	struct ResampleSlot { ResampleShape shape{0, 0, 0, 0, 0}; float *taps = nullptr; int users = 0; };
 	ResampleSlot resampleSlots[kResampleMaxRatios];
-	std::vector<int> resampleSlot;
+	std::vector<int> resampleSlot, streamResampleSlot; // per stream, the slot of its whole-clip and of its streaming ratio (-1: none)
 	// a device scratch that holds `need` floats, allocated with `room` more; true: it was replaced (the old one freed behind a synchronise).  workspace: counted in workspaceBytes()
 	bool growScratch(float *&scratch, size_t &capacity, size_t need, size_t room, bool workspace);
 	StreamParams *dParams = nullptr, *hParams = nullptr; // (hParams: pinned staging of uploadParams())

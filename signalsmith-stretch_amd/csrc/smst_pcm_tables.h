@@ -13,6 +13,7 @@
 // PcmDebugBlock    what a levelled debug hook uploads in front of its launch: the table's dither and level sections, then the meter words
 // PcmOutCall       where one call's output conversion finds all of that on the device
 // ResampleTableLayout  the table a whole-clip call with a resampled stream adds on the input side (the engine's; two sets as the above)
+// StreamResampleTableLayout  the table a streaming call adds on the input side where a stream has the stream-resample setting
 #pragma once
 #include "smst_device.h"
 #include <cstddef>
@@ -84,6 +85,25 @@ struct ResampleTableLayout {
 	ResampleEntry *entries(void *base) const { return pcmTableAt<ResampleEntry>(base, entries()); }
 };
 static_assert(sizeof(ClipSeg) == 16 && alignof(ResampleEntry) <= 16, "the entries begin on a 16-byte boundary where the table does");
+
+// StreamResampleTableLayout: what a streaming call adds on the input side where a stream of the batch has the setting of include/smst.h,
+// "Stream resample" -- a table of its own beside the two above, pinned host staging with a device twin, uploaded in ONE copy.  Three sections
+// of a batch of S streams, in order:
+//   plainCounts  [S] int                  kPcmIn's counts into the engine's input image: the call's frames of a stream without the setting, 0 for one with it
+//   rawCounts    [S] int                  kPcmIn's counts into the raw image: the call's frames of a stream with the setting, 0 for one without
+//   entries      [S] StreamResampleEntry  taps, shape, n, k, fed, made and the set of lines the call reads (L == 0: no setting)
+struct StreamResampleTableLayout {
+	size_t S;
+	explicit StreamResampleTableLayout(int streams) : S(size_t(streams)) {}
+	size_t plainCounts() const { return 0; }
+	size_t rawCounts() const { return plainCounts() + S*sizeof(int); }
+	size_t entries() const { return rawCounts() + S*sizeof(int); }
+	size_t bytes() const { return entries() + S*sizeof(StreamResampleEntry); }
+	int *plainCounts(void *base) const { return pcmTableAt<int>(base, plainCounts()); }
+	int *rawCounts(void *base) const { return pcmTableAt<int>(base, rawCounts()); }
+	StreamResampleEntry *entries(void *base) const { return pcmTableAt<StreamResampleEntry>(base, entries()); }
+};
+static_assert(alignof(StreamResampleEntry) <= 2*sizeof(int) && sizeof(StreamResampleEntry)%8 == 0, "the entries' 64-bit members are aligned behind two runs of S ints");
 
 struct PcmMeters {
 	size_t S;

@@ -58,6 +58,29 @@ void resampleTaps(const ResampleShape &g, float *out) {
 	}
 }
 
+// One resampled frame of the `chans` channels of a group: y[k] = sum_j double(coef[j])*double(x[k*pitch + j]), j = 0 ... T - 1 from 0.0 -- the
+// frame's T taps lie at x[0 ... T) of each channel's LDS image, `pitch` floats apart; coef: the phase's row of the table, 16-byte aligned.
+// The one definition of the tap sum: kClipResample and kPcmStreamResample (smst_stream_resample.h) both call it
+__device__ __forceinline__ void resampleFrameSum(const float *__restrict__ coef, const float *x, int pitch, int T, int chans, double (&y)[kResampleGroup]) {
+#pragma unroll
+	for (int k = 0; k < kResampleGroup; ++k) y[k] = 0.0;
+	const int whole = T & ~3;
+	for (int j = 0; j < whole; j += 4) {
+		const PcmWord4 v = *reinterpret_cast<const PcmWord4 *>(coef + j);
+#pragma unroll
+		for (int i = 0; i < 4; ++i) {
+			const double w = double(__int_as_float(int(v[i])));
+#pragma unroll
+			for (int k = 0; k < kResampleGroup; ++k) if (k < chans) y[k] += w*double(x[k*pitch + j + i]);
+		}
+	}
+	for (int j = whole; j < T; ++j) { // (T is even: two taps where it is no multiple of 4)
+		const double w = double(coef[j]);
+#pragma unroll
+		for (int k = 0; k < kResampleGroup; ++k) if (k < chans) y[k] += w*double(x[k*pitch + j]);
+	}
+}
+
 // grid (tiles of kResampleTile resampled frames, S), 256 threads.  A stream without a ratio (L == 0), a tile behind the stream's Nr: returns at once
 __global__ __launch_bounds__(256) void kClipResample(const float *__restrict__ raw, long long rawStreamStride, long long rawChannelStride,
 		float *__restrict__ image, long long imageStreamStride, long long imageChannelStride, const ClipSeg *__restrict__ segs, const ResampleEntry *__restrict__ entries, int C, int ldsFloats) {
@@ -96,23 +119,7 @@ __global__ __launch_bounds__(256) void kClipResample(const float *__restrict__ r
 			const float *coef = e.taps + (size_t)p*e.pitch;
 			const float *x = lds + at0;
 			double y[kResampleGroup];
-#pragma unroll
-			for (int k = 0; k < kResampleGroup; ++k) y[k] = 0.0;
-			const int whole = e.T & ~3;
-			for (int j = 0; j < whole; j += 4) {
-				const PcmWord4 v = *reinterpret_cast<const PcmWord4 *>(coef + j);
-#pragma unroll
-				for (int i = 0; i < 4; ++i) {
-					const double w = double(__int_as_float(int(v[i])));
-#pragma unroll
-					for (int k = 0; k < kResampleGroup; ++k) if (k < chans) y[k] += w*double(x[k*pitch + j + i]);
-				}
-			}
-			for (int j = whole; j < e.T; ++j) { // (T is even: two taps where it is no multiple of 4)
-				const double w = double(coef[j]);
-#pragma unroll
-				for (int k = 0; k < kResampleGroup; ++k) if (k < chans) y[k] += w*double(x[k*pitch + j]);
-			}
+			resampleFrameSum(coef, x, pitch, e.T, chans, y);
 			const long long nf = n0 + f;
 			const size_t col = nf < split ? (size_t)g0.dst + (size_t)nf : (size_t)g1.dst + (size_t)(nf - split);
 #pragma unroll
