@@ -458,7 +458,8 @@ int smst_batch_pcm_dither(const smst_batch *b, int stream, int *mode, long long 
  * per-call table beside the level entries; the passes' scratch and the meters grow with the first call that measures, as the images do, and
  * count in smst_batch_workspace_bytes: a second call of the same shapes allocates nothing, no host synchronisation is added, and the
  * ordering contract of the device-memory call is unchanged.  A batch without a stream in this mode launches none of the passes.
- * Out of scope: measuring in the streaming or the planar calls (momentary and short-term loudness and loudness range: "Loudness range").
+ * Out of scope: measuring in the planar calls (momentary and short-term loudness and loudness range: "Loudness range"; the streaming frame
+ * calls have a meter of their own: "Stream meter").
  * SMST_ERR_INVALID with a message: a target that is not finite; a sample rate that is not finite, <= 0 or gives h < SMST_LOUDNESS_CHUNK; a
  * ceiling <= 0 or NaN (+inf is allowed); a weight that is negative or not finite; a stream index out of range; a null batch. */
 #define SMST_LEVEL_FIXED     0 /* g = gain */
@@ -526,13 +527,14 @@ int smst_debug_clip_loudness(int device, int streams, int channels, const int *s
  *
  * Which calls.  smst_batch_process_pcm and smst_batch_flush_pcm return SMST_ERR_INVALID, before anything runs, if a stream that takes part
  * has the flag -- the rule and the reason of the whole-clip modes: a meter across calls would need 11 frames of carried history per channel.
+ * (That meter exists as a setting of its own, with exactly that history: "Stream meter".)
  *
  * How.  One kernel (csrc/smst_true_peak.h) behind the call's last emitting kernel and in front of the conversion.  The flag rides
  * in the fourth word of the stream's level entry; the taps travel as a kernel argument.  The true-peak words ([streams] ints) are device
  * memory that grows with the first call that measures and counts in smst_batch_workspace_bytes: a second call of the same shapes allocates
  * nothing, no host synchronisation is added, and the ordering contract of the device-memory call is unchanged.  The maximum is one of
  * integers and no floating-point atomic is used: a call's result is bit-reproducible whatever the scheduling.
- * Out of scope: true-peak metering in the streaming and the planar calls; an oversampling factor that depends on the rate (4x at
+ * Out of scope: true-peak metering in the planar calls (the streaming frame calls: "Stream meter"); an oversampling factor that depends on the rate (4x at
  * every rate).
  * SMST_ERR_INVALID with a message: a stream index out of range, a null batch. */
 #define SMST_TRUE_PEAK_TILE 1024 /* frames of a channel's clip that one workgroup of the true-peak pass measures (kTruePeakTile) */
@@ -749,7 +751,8 @@ int smst_debug_pcm_stream_limit(int device, int streams, int channels, int calls
  * without a finite cap keeps the bits of gL.
  *
  * Which calls.  smst_batch_process_pcm and smst_batch_flush_pcm return SMST_ERR_INVALID, before anything runs, if a stream that takes part
- * has the meter flag or a finite cap: the rule of the whole-clip modes, for the same reason.
+ * has the meter flag or a finite cap: the rule of the whole-clip modes, for the same reason.  (The streaming form is a setting of its own:
+ * "Stream meter".)
  *
  * How.  One kernel (csrc/smst_loudness_range.h), one workgroup per stream, behind the four loudness passes and in front of the
  * true-peak and limiter passes, launched only in a call in which a metered stream runs (launch count "clip_loudness_range"; "clip_loudness"
@@ -760,7 +763,7 @@ int smst_debug_pcm_stream_limit(int device, int streams, int channels, int calls
  * measured.  The short-term powers and the meter words grow with the first call that meters and count in smst_batch_workspace_bytes: a
  * second call of the same shapes allocates nothing, no host synchronisation is added, and the ordering contract of the device-memory call
  * is unchanged.
- * Out of scope: metering in the streaming or the planar calls; the time at which a maximum occurs; percentiles other than 10 and 95.
+ * Out of scope: metering in the planar calls (the streaming frame calls: "Stream meter"); the time at which a maximum occurs; percentiles other than 10 and 95.
  * SMST_ERR_INVALID with a message: with on != 0, a sample rate that smst_batch_set_pcm_loudness would refuse; a cap that is NaN or -inf; a
  * stream index out of range; a null batch. */
 #define SMST_LOUDNESS_RANGE_TILE 256 /* short-term powers that the range stage's workgroup takes at a time (kLoudRangeThreads) */
@@ -915,6 +918,92 @@ long long smst_batch_pcm_stream_resample_need(const smst_batch *b, int stream, l
 int smst_debug_pcm_stream_resample(int device, int streams, int channels, int calls, const int *counts, const int *ratios, const long long *fed0,
                                    const float *image, long long imageStreamStride, long long imageChannelStride,
                                    float *out, long long outStreamStride, long long outChannelStride, int maxFrames, long long *made);
+/* ---- Stream meter (EXTENSION; opt-in: a batch that never calls smst_batch_set_pcm_stream_meter launches the kernels, writes the bytes and counts the launches it did before) ----
+ * The meters above ("Loudness", "True peak", "Loudness range") know a whole clip.  A live bus could be stretched, resampled, levelled and
+ * limited on the device, but to learn its loudness the caller had to copy the output back and meter it on the host.  Each meter has an exact
+ * streaming form: a small carried state per stream, and a definition that makes the readings equal to the clip meters' bit for bit, however
+ * the stream is cut into calls.
+ *
+ * It is a per-stream setting of its own beside the whole-clip flags, which stay refused in the streaming calls.  With it on, every frame that
+ * smst_batch_process_pcm and smst_batch_flush_pcm write for the stream is measured on the device, behind the call's last emitting kernel:
+ * no host synchronisation in the call, no allocation in the call, no floating-point atomic.  The caller asks for the readings at any time.
+ *
+ * Definition.  Let v(n), n = 0 ... T - 1, be the frames the engine has emitted for the stream through smst_batch_process_pcm /
+ * smst_batch_flush_pcm since the meter was last cleared -- BEFORE the gain, as every other meter of the library measures, and at emission, not
+ * where a stream limiter delays them.  Let h = round(fs/10) and Tm = min(T, maxSubBlocks*h).  After any call the readings are, bit for bit,
+ * what smst_debug_clip_loudness_range (the four loudness passes and the range stage) and smst_debug_clip_true_peak report of the clip
+ * v[0, Tm) with the same fs and the batch's channel weights.  Nothing else defines the result: not how T was cut into calls, not which
+ * update form ran.
+ *   K-weighting.  The clip meter enters chunk k + 1 of SMST_LOUDNESS_CHUNK = 256 frames with A^256 x_in[k] + ends[k], ends[k] the state chunk
+ *   k reaches from ZERO state.  The stream meter keeps that chunk grid, anchored at n = 0, and carries per (stream, channel), all float64,
+ *   for the chunk in progress: x_in, the state run from x_in, the state run from zero, and the two partial sums e0, e1.
+ *   Sub-block sums.  The clip meter adds a sub-block's partials from 0.0 in chunk order, so the running sum of the sub-block in progress is
+ *   carried too.  Sub-block j closes when position (j + 1)*h is reached, which may fall inside a chunk whose e0 is by then complete.
+ *   One source form.  The filter step, the accumulation e += y*y and the chunk carry are one source expression each, shared with the clip
+ *   passes (the library is built with -ffp-contract=on: the source form decides the fusing).
+ *   History.  The relative gates and the percentiles need every block of the programme: per metered stream the device keeps the closed
+ *   sub-block sums sub[c][j], j < maxSubBlocks, appended by the update and never rewritten.  A reading runs the clip meter's own stages on
+ *   them -- sub-block sums -> block powers -> the two gates, then the range stage --, so everything behind the sums is identical by construction.
+ *   True peak.  The clip definition has zeros beyond the clip's end, so the windows of n >= T - 6 change when more frames arrive.  The
+ *   update folds only COMPLETE windows (n <= Tm - 7) into the running word, every sample |x(n)| at once, and carries the last 11 frames of
+ *   every channel.  A reading computes the six edge windows against zeros from the carried frames and reports max(running, edge) without
+ *   folding the edge in: a later reading may be LOWER.  The running word starts at 0, the carried frames at +0.0 (the clip's "x outside
+ *   [0, N) is 0").
+ *   Capacity.  maxSubBlocks is given with the setting and sizes the history: 100-ms sub-blocks, `channels` doubles each.  A full meter
+ *   freezes -- it refuses no call --, true peak at the same frame, so one Tm describes all readings.  The batch's histories are allocated by
+ *   the first setter call with on != 0, for its maxSubBlocks; a later call may ask for at most that many.
+ *   NaN and inf behave as in the clip meters: a NaN poisons the filter from there on and is skipped by the peak.
+ *   Which calls.  smst_batch_process_pcm and smst_batch_flush_pcm meter the frames they write for a stream with the setting.  A stream with no
+ *   frame in a call, or left out of a flush, keeps its state.  The seek calls emit nothing and meter nothing.
+ *   Clearing.  By the setter (for that stream) and by smst_batch_reset; not by a level, limiter or weights change.
+ *   smst_batch_set_pcm_loudness_weights while a meter holds frames is refused: the clip equivalence has one weight set.
+ *   Mixing.  The meter changes NO output byte of any stream; an unflagged stream's bytes and meters are what they are without it.
+ *   A reading describes v before the gain: a FIXED gain g adds 20*log10|g| LU to every loudness.
+ *
+ * How.  Behind the output conversion of a call in which a metered stream has frames, kPcmStreamMeterPeak (one lane per new frame: the sample
+ * and the window that the frame completes, integer maxima) and the update run on the batch's stream (csrc/smst_stream_meter.h).
+ * The update has two forms, which give the same bits; the host chooses by the call's longest metered count (SMST_STREAM_METER_SCAN_FRAMES).
+ * The short-call form, kPcmStreamMeter: one lane per (stream, channel), its row staged through LDS in tiles, continues the chunk in progress
+ * and appends the sub-block sums that close.  The chunk-scan form: the clip meter's three passes with a start position and the carried state
+ * -- a zero-state pass over the call's chunks whose first chunk resumes the carried zero-state run, the carry chain from the carried x_in,
+ * an energy pass whose last chunk, if incomplete, leaves the carried state -- and a pass that closes the sub-block sums in chunk order; its
+ * scratch grows with the first call that needs it, as the images do.  One set of carried state serves calls in flight: a lane updates the
+ * state of its own (stream, channel) only, the kernels in front of it only read what is carried, and everything is ordered by the batch's
+ * stream.  A take runs the gate stage, the range stage and one small kernel for the true-peak edge on the histories.
+ * The equality covers the sign of a NaN: where both operands of a product or a sum can be NaN -- the chunk carry and the sub-block sums at a
+ * rate below 3364 Hz, where the K-weighting shelf is unstable and A^256 is not finite -- the operand order is written down, one device
+ * function for the clip passes and both update forms.
+ * Out of scope: metering the signal behind the gain or the stream limiter; the planar calls; stretch_cli (a whole-file tool, which has the
+ * clip meters); a sliding "last N minutes" integrated window; a per-stream weight set; a histogram-gated approximate meter with unbounded
+ * programme length.
+ * SMST_ERR_INVALID with a message: a null batch; a stream index out of range; with on != 0 a rate that smst_batch_set_pcm_loudness would
+ * refuse, maxSubBlocks < 1, maxSubBlocks*h >= 2^31 or maxSubBlocks above what the histories were allocated for; smst_batch_exact_pcm with a
+ * participating stream that has the setting (the whole-clip flags are the clip form). */
+/* stream = -1: every stream.  Clears the stream's meter (T = 0), on or off.  sampleRate by the rule of smst_batch_set_pcm_loudness
+ * (h >= SMST_LOUDNESS_CHUNK); maxSubBlocks >= 1, read with on != 0 only.  The first call with on != 0 allocates the carried state and the
+ * histories (counted in smst_batch_workspace_bytes) -- never a streaming call */
+int smst_batch_set_pcm_stream_meter(smst_batch *b, int stream, int on, double sampleRate, int maxSubBlocks);
+int smst_batch_pcm_stream_meter(const smst_batch *b, int stream, int *on, double *sampleRate, int *maxSubBlocks);
+/* host counters, no synchronisation: frames emitted for the stream since the clear (T) and frames metered (Tm) */
+int smst_batch_pcm_stream_meter_frames(const smst_batch *b, int stream, long long *frames, long long *metered);
+/* per stream, of v[0, Tm): integrated loudness and its two block counts; the NEWEST momentary and short-term loudness (z of block nb - 1,
+ * st of block ns - 1; -inf where there is none); their maxima; LRA, low, high, ns, n; the true peak and the sample peak.  Values and
+ * conventions as smst_batch_take_pcm_loudness / _loudness_range / _true_peaks report them.  Any pointer may be null.  Synchronises the
+ * batch; resets nothing: metering goes on */
+int smst_batch_take_pcm_stream_meter(smst_batch *b, double *lufs, int *blocks, int *gated, double *momentary, double *shortTerm,
+                                     double *momentaryMax, double *shortTermMax, double *range, double *low, double *high,
+                                     int *shortBlocks, int *rangeBlocks, float *truePeaks, float *samplePeaks);
+/* test hook: `calls` meter updates in sequence on one device stream over a planar fp32 image that holds each stream's frames in order
+ * (counts: [calls][streams], negative = takes no part), a reading after every call k with readAfter[k] != 0 (null: after the last only).
+ * Readings are POWERS, as smst_debug_clip_loudness_range reports them, reading-major: Z[r*streams + s] ...; blockPowers / shortPowers of the
+ * LAST reading only ([streams][maxBlocks]).  flags: [streams], 0 = the stream is not metered (null: every one is).  form: 0 = the library's
+ * own choice per call, 1 = force the short-call form, 2 = force the chunk-scan form */
+int smst_debug_pcm_stream_meter(int device, int streams, int channels, int calls, const int *counts, const int *readAfter, int form,
+                                const float *image, long long imageStreamStride, long long imageChannelStride,
+                                const double *sampleRates, const float *weights, const int *flags, int maxSubBlocks,
+                                double *Z, int *blocks, int *gated, double *momentaryMax, double *shortTermMax, double *low, double *high,
+                                int *shortBlocks, int *rangeBlocks, float *truePeaks, float *samplePeaks, long long *metered,
+                                double *blockPowers, double *shortPowers, int maxBlocks);
 /* per stream, since the last take: peaks[s] = the largest |v| the levelled output conversions met BEFORE the gain (0 if none); gains[s] = the
  * gain the newest levelled conversion of stream s applied (1 before any).  Either may be null.  Synchronises the batch; resets the peaks,
  * not the gains. */

@@ -179,6 +179,12 @@ _SIGNATURES = {
     "smst_batch_pcm_stream_resample_frames": (_ll, [C.c_void_p, C.c_int, _ll, C.c_int]),
     "smst_batch_pcm_stream_resample_need": (_ll, [C.c_void_p, C.c_int, _ll, C.c_int]),
     "smst_debug_pcm_stream_resample": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _ip, _ip, C.POINTER(_ll), C.c_void_p, _ll, _ll, C.c_void_p, _ll, _ll, C.c_int, C.POINTER(_ll)]),
+    "smst_batch_set_pcm_stream_meter": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_int]),
+    "smst_batch_pcm_stream_meter": (C.c_int, [C.c_void_p, C.c_int, _ip, _dp, _ip]),
+    "smst_batch_pcm_stream_meter_frames": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(_ll), C.POINTER(_ll)]),
+    "smst_batch_take_pcm_stream_meter": (C.c_int, [C.c_void_p, _dp, _ip, _ip, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _ip, _ip, _fp, _fp]),
+    "smst_debug_pcm_stream_meter": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _ip, _ip, C.c_int, C.c_void_p, _ll, _ll, _dp, _fp, _ip, C.c_int,
+                                              _dp, _ip, _ip, _dp, _dp, _dp, _dp, _ip, _ip, _fp, _fp, C.POINTER(_ll), _dp, _dp, C.c_int]),
     "smst_batch_synchronize": (C.c_int, [C.c_void_p]),
     "smst_batch_hip_stream": (C.c_void_p, [C.c_void_p]),
     "smst_batch_enable_profiling": (C.c_int, [C.c_void_p, C.c_int]),
@@ -435,6 +441,40 @@ def debug_pcm_stream_limit(counts, channels, image, image_ss, image_cs, gains, c
                                                 r.ctypes.data_as(_fp), frames.ctypes.data_as(_fp), int(max_frames), low.ctypes.data_as(_fp),
                                                 limited.ctypes.data_as(C.POINTER(_ll))))
     return r, frames, low, limited
+
+
+def debug_pcm_stream_meter(counts, channels, image, image_ss, image_cs, sample_rates, max_sub_blocks, weights=None, flags=None, read_after=None, form=0,
+                           max_blocks=0, device=0, lib=None):
+    """smst_debug_pcm_stream_meter on a numpy image (planar float32 that holds each stream's frames in order; strides in floats; counts int
+    [calls, S], negative: the stream takes no part in that call; read_after: [calls] or None -- a reading after the last call only)
+    -> a dict of arrays, reading-major [R, S]: Z, M, ST, lo, hi (powers, float64), blocks, gated, ns, n (int32), true_peaks, sample_peaks
+    (float32), metered (int64); block_powers, short_powers: float64 [S, max_blocks] of the LAST reading, NaN behind a stream's last one"""
+    lib = lib if lib is not None else load_library()
+    rates = np.ascontiguousarray(np.asarray(sample_rates, np.float64).reshape(-1))
+    S = rates.shape[0]
+    n = np.ascontiguousarray(counts, np.int32).reshape(-1, S)
+    calls = n.shape[0]
+    after = None if read_after is None else np.ascontiguousarray(read_after, np.int32)
+    assert after is None or after.shape == (calls,)
+    R = 1 if after is None else int(np.count_nonzero(after))
+    w = None if weights is None else np.ascontiguousarray(weights, np.float32)
+    assert w is None or w.shape == (channels,)
+    on = None if flags is None else np.ascontiguousarray(flags, np.int32)
+    assert on is None or on.shape == (S,)
+    f64 = {k: np.full((max(R, 1), S), -1.0) for k in ("Z", "M", "ST", "lo", "hi")}
+    i32 = {k: np.full((max(R, 1), S), -1, np.int32) for k in ("blocks", "gated", "ns", "n")}
+    f32 = {k: np.full((max(R, 1), S), -1, np.float32) for k in ("true_peaks", "sample_peaks")}
+    metered = np.full((max(R, 1), S), -1, np.int64)
+    block_powers, short_powers = np.full((S, max(max_blocks, 1)), np.nan), np.full((S, max(max_blocks, 1)), np.nan)
+    d, i, f = (lambda a: a.ctypes.data_as(_dp)), (lambda a: a.ctypes.data_as(_ip)), (lambda a: a.ctypes.data_as(_fp))
+    _check(lib, lib.smst_debug_pcm_stream_meter(device, S, channels, calls, i(n), None if after is None else i(after), int(form), C.c_void_p(image.ctypes.data), image_ss, image_cs,
+                                                d(rates), None if w is None else f(w), None if on is None else i(on), int(max_sub_blocks),
+                                                d(f64["Z"]), i(i32["blocks"]), i(i32["gated"]), d(f64["M"]), d(f64["ST"]), d(f64["lo"]), d(f64["hi"]), i(i32["ns"]), i(i32["n"]),
+                                                f(f32["true_peaks"]), f(f32["sample_peaks"]), metered.ctypes.data_as(C.POINTER(_ll)), d(block_powers), d(short_powers), int(max_blocks)))
+    out = dict(f64, **i32, **f32)
+    out = {k: v[:R] for k, v in out.items()}
+    out.update(metered=metered[:R], block_powers=block_powers[:, :max_blocks], short_powers=short_powers[:, :max_blocks])
+    return out
 
 
 def resample_ratio(from_rate, to_rate, lib=None):
@@ -985,6 +1025,39 @@ class StretchBatch:
         _check(self.lib, self.lib.smst_batch_take_pcm_stream_limiter(self.h, low.ctypes.data_as(_fp), frames.ctypes.data_as(C.POINTER(_ll))))
         self._inflight = []
         return low, frames
+
+    def set_pcm_stream_meter(self, on=True, sample_rate=48000.0, max_sub_blocks=36000, stream=-1):
+        """The stream meter (include/smst.h, "Stream meter"), processFrames and flushFrames only: every frame written for the stream is
+        measured on the device -- R 128 loudness, loudness range, true peak --, before the gain, with readings equal to the clip meters'
+        of the frames so far, whatever the cuts between calls.  ``max_sub_blocks`` 100-ms sub-blocks size the history (an hour: 36000); a
+        full meter freezes.  Clears the stream's meter; stream = -1: every stream."""
+        _check(self.lib, self.lib.smst_batch_set_pcm_stream_meter(self.h, int(stream), 1 if on else 0, float(sample_rate), int(max_sub_blocks)))
+
+    def pcm_stream_meter(self, stream):
+        """-> (on, sample_rate, max_sub_blocks) of the stream's setting"""
+        on, rate, blocks = C.c_int(0), C.c_double(0), C.c_int(0)
+        _check(self.lib, self.lib.smst_batch_pcm_stream_meter(self.h, int(stream), C.byref(on), C.byref(rate), C.byref(blocks)))
+        return bool(on.value), rate.value, blocks.value
+
+    def pcm_stream_meter_frames(self, stream):
+        """-> (frames emitted for the stream since its meter was cleared, frames metered): host counters, no synchronisation"""
+        frames, metered = _ll(0), _ll(0)
+        _check(self.lib, self.lib.smst_batch_pcm_stream_meter_frames(self.h, int(stream), C.byref(frames), C.byref(metered)))
+        return frames.value, metered.value
+
+    def take_pcm_stream_meter(self):
+        """-> a dict of arrays [S] over the frames metered so far: lufs, momentary, short_term, momentary_max, short_term_max, low, high (LUFS,
+        float64; -inf where undefined), range (LU), blocks, gated, short_blocks, range_blocks (int32), true_peaks, sample_peaks (float32,
+        before the gain).  Synchronises the batch; resets nothing: metering goes on."""
+        S = self.streams
+        f64 = {k: np.zeros(S, np.float64) for k in ("lufs", "momentary", "short_term", "momentary_max", "short_term_max", "range", "low", "high")}
+        i32 = {k: np.zeros(S, np.int32) for k in ("blocks", "gated", "short_blocks", "range_blocks")}
+        f32 = {k: np.zeros(S, np.float32) for k in ("true_peaks", "sample_peaks")}
+        d, i, f = (lambda k: f64[k].ctypes.data_as(_dp)), (lambda k: i32[k].ctypes.data_as(_ip)), (lambda k: f32[k].ctypes.data_as(_fp))
+        _check(self.lib, self.lib.smst_batch_take_pcm_stream_meter(self.h, d("lufs"), i("blocks"), i("gated"), d("momentary"), d("short_term"), d("momentary_max"), d("short_term_max"),
+                                                                   d("range"), d("low"), d("high"), i("short_blocks"), i("range_blocks"), f("true_peaks"), f("sample_peaks")))
+        self._inflight = []
+        return dict(f64, **i32, **f32)
 
     # --- test hooks
     def set_pcm_resample(self, up, down, stream=-1):

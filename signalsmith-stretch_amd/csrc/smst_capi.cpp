@@ -100,6 +100,21 @@ struct PcmOutState {
 	int limitLinesH = 0;
 	smst::PcmStreamLimit streamLimitView;
 	std::vector<int> hLimitMeters;
+	// the stream meter (smst_batch_set_pcm_stream_meter; include/smst.h, "Stream meter"): the setting, the entry made of its rate, the frames
+	// emitted for the stream since the clear (T) and the most that are metered (cap = maxSubBlocks*h).  The device side -- configurations,
+	// carried state, histories of meterPitch sub-blocks per channel, a reading's scratch and tables -- exists from the first setter call with
+	// `on`.  streamMeterView: where the kernels find it (smst::PcmStreamMeter)
+	struct StreamMeter { unsigned char on = 0; double sampleRate = 0; int maxSub = 0; long long frames = 0, cap = 0; smst::LoudEntry entry{}; };
+	std::vector<StreamMeter> streamMeter;
+	Buffer<smst::StreamMeterConfig, false> dMeterConfig;
+	Buffer<double, false> dMeterState, dMeterSub, dMeterRead;
+	Buffer<double, false, 1024> dMeterScan;    // the chunk-scan form's scratch: grows on demand, as the images do
+	Buffer<float, false> dMeterFrames;
+	Buffer<int, false> dMeterWords;
+	Buffer<unsigned char, false> dMeterTables; // a reading's: [2S] ClipSeg, [S] LoudEntry, [kMaxChannels] weights
+	int meterPitch = 0;
+	const double *meterReadZ = nullptr, *meterReadSt = nullptr;
+	smst::PcmStreamMeter streamMeterView;
 	bool levelled = false;
 	// overs ([S][2]: clamped, NaN): the kernels add to them, takeOvers() reads and clears them; the meter words (smst::PcmMeters)
 	Buffer<unsigned, false> dOvers;
@@ -120,6 +135,7 @@ struct PcmOutState {
 		limiter.assign((size_t)S, 0);
 		meter.assign((size_t)S, Meter());
 		streamLimit.assign((size_t)S, StreamLimit());
+		streamMeter.assign((size_t)S, StreamMeter());
 		metered.assign((size_t)S, 0);
 		wholeClip.assign((size_t)S, 0);
 		limited.assign((size_t)S, 0);
@@ -133,7 +149,9 @@ struct PcmOutState {
 		if (hipMemcpy(dMeters, hMeters.data(), meters.bytes(), hipMemcpyHostToDevice) != hipSuccess) throw smst::Error("hipMemcpy (PCM level) failed", true);
 	}
 	size_t workspaceBytes() const {
-		return (dOvers ? pcmOversBytes(S) : 0) + (dMeters ? smst::PcmMeters(S).bytes() : 0) + (dLimitLines.cap + dLimitRows.cap)*sizeof(float) + dLimitMeters.cap*sizeof(int);
+		return (dOvers ? pcmOversBytes(S) : 0) + (dMeters ? smst::PcmMeters(S).bytes() : 0) + (dLimitLines.cap + dLimitRows.cap)*sizeof(float) + dLimitMeters.cap*sizeof(int) +
+		       dMeterConfig.cap*sizeof(smst::StreamMeterConfig) + (dMeterState.cap + dMeterSub.cap + dMeterRead.cap + dMeterScan.cap)*sizeof(double) + dMeterFrames.cap*sizeof(float) +
+		       dMeterWords.cap*sizeof(int) + dMeterTables.cap;
 	}
 
 	// f(s) for the streams that `stream` names: -1 is every one
@@ -263,6 +281,130 @@ struct PcmOutState {
 			if (limitedFrames) limitedFrames[s] = (long long)(unsigned)hLimitMeters[(size_t)S + s]; // (the count wraps as an unsigned 32-bit word does)
 		}
 	}
+	// Stream meter.  The doubles of a reading's scratch: the gate stage's meters and block powers, the range stage's, the reading's words
+	static size_t meterReadDoubles(int S, int pitch) { return (size_t)2*S + (S + 1)/2 + (size_t)S*pitch + smst::loudRangeDoubles(S, pitch) + (size_t)3*S; }
+	static size_t meterTableBytes(int S) { return (size_t)2*S*sizeof(smst::ClipSeg) + (size_t)S*sizeof(smst::LoudEntry) + smst::kMaxChannels*sizeof(float); }
+	static smst::StreamMeterConfig meterConfig(const StreamMeter &m) {
+		smst::StreamMeterConfig cfg{};
+		cfg.k = m.entry.k;
+		for (int i = 0; i < 16; ++i) cfg.Ac[i] = m.entry.Ac[i];
+		cfg.h = m.entry.h; cfg.on = m.on; cfg.cap = int(m.cap);
+		return cfg;
+	}
+	void setStreamMeter(int device, hipStream_t st, int stream, int on, double sampleRate, int maxSubBlocks, long long &allocs) {
+		forStreams(stream, [](int) {}); // (refused before anything is allocated)
+		StreamMeter m;
+		if (on) {
+			if (!(std::isfinite(sampleRate) && sampleRate > 0)) throw smst::Error("stream meter: the sample rate is not finite or not above 0");
+			if (!smst::loudEntryOf(sampleRate, 0.0, m.entry)) throw smst::Error("stream meter: the sample rate gives a 100-ms step of fewer than " + std::to_string(smst::kLoudChunk) + " samples (or is beyond 1e9)");
+			if (maxSubBlocks < 1) throw smst::Error("stream meter: maxSubBlocks is below 1");
+			if ((long long)maxSubBlocks*m.entry.h >= (1LL << 31)) throw smst::Error("stream meter: maxSubBlocks 100-ms sub-blocks are 2^31 frames or more at this rate");
+			if (dMeterState && maxSubBlocks > meterPitch)
+				throw smst::Error("stream meter: maxSubBlocks is above " + std::to_string(meterPitch) + ", what the batch's histories were allocated for by the first call with the setting on");
+			m.on = 1; m.sampleRate = sampleRate; m.maxSub = maxSubBlocks; m.cap = (long long)maxSubBlocks*m.entry.h;
+			m.entry.meter = 1;
+		}
+		if (hipSetDevice(device) != hipSuccess) throw smst::Error("hipSetDevice failed", true);
+		if (on && !dMeterState) {
+			++allocs;
+			meterPitch = maxSubBlocks;
+			dMeterConfig.allocate((size_t)S, "stream meter configurations");
+			dMeterState.allocate((size_t)S*C*smst::kStreamMeterDoubles, "stream meter state");
+			dMeterFrames.allocate((size_t)S*C*smst::kStreamMeterLine, "stream meter frames");
+			dMeterWords.allocate((size_t)2*S, "stream meter words");
+			dMeterSub.allocate((size_t)S*C*meterPitch, "stream meter histories");
+			dMeterRead.allocate(meterReadDoubles(S, meterPitch), "stream meter reading");
+			dMeterTables.allocate(meterTableBytes(S), "stream meter tables");
+			streamMeterView.config = dMeterConfig; streamMeterView.state = dMeterState; streamMeterView.frames = dMeterFrames;
+			streamMeterView.words = dMeterWords; streamMeterView.sub = dMeterSub; streamMeterView.maxSub = meterPitch;
+			const smst::StreamMeterConfig off{};
+			smst::launchPcmStreamMeterClear(streamMeterView, S, C, -1, &off, st);
+		}
+		forStreams(stream, [&](int s) { streamMeter[s] = m; });
+		if (dMeterState) {
+			const smst::StreamMeterConfig cfg = meterConfig(m);
+			smst::launchPcmStreamMeterClear(streamMeterView, S, C, stream, &cfg, st);
+		}
+	}
+	// nothing metered, the settings kept, for the stream (-1: every one), in the batch's stream order
+	void clearStreamMeter(int device, hipStream_t st, int stream) {
+		for (int s = stream < 0 ? 0 : stream; s < (stream < 0 ? S : stream + 1); ++s) streamMeter[s].frames = 0;
+		if (!dMeterState) return;
+		if (hipSetDevice(device) != hipSuccess) throw smst::Error("hipSetDevice failed", true);
+		smst::launchPcmStreamMeterClear(streamMeterView, S, C, stream, nullptr, st);
+	}
+	bool streamMeterHolds() const {
+		for (const StreamMeter &m : streamMeter) if (m.frames > 0) return true;
+		return false;
+	}
+	// the largest count of a stream that a streaming call of these counts meters (a full meter takes none of them)
+	int mostStreamMetered(const int *n) const {
+		int most = 0;
+		if (dMeterState) for (int s = 0; s < S; ++s) if (streamMeter[s].on && streamMeter[s].frames < streamMeter[s].cap) most = std::max(most, n[s]);
+		return most;
+	}
+	// the chunk-scan form's scratch for a call whose longest metered count is `most`, before the engine is called (a growth frees, which
+	// synchronises the device)
+	void ensureStreamMeterScan(int device, int most, int form, long long &allocs) {
+		if (most < 1 || !smst::streamMeterScans(most, form)) return;
+		const int chunks = smst::streamMeterChunksOf(most);
+		dMeterScan.ensure(smst::streamMeterScanDoubles(S, C, chunks), device, allocs, "stream meter scan");
+		streamMeterView.scan = dMeterScan;
+		streamMeterView.maxChunks = int((dMeterScan.cap/((size_t)S*C) - 4)/6); // (laid out for the capacity: a buffer that has served a longer call serves this one)
+	}
+	// a call's update behind its output conversion, and the host's count of what the streams were handed
+	// (dStarts, form: the test hook's -- where each stream's frames begin in its rows, and the update form forced)
+	void meterStream(hipStream_t st, const float *image, long long imageSS, long long imageCS, const int *n, const int *dCounts, const int *dStarts = nullptr, int form = 0) {
+		const int most = mostStreamMetered(n);
+		if (most > 0) smst::launchPcmStreamMeter(image, imageSS, imageCS, dCounts, dStarts, S, C, most, streamMeterView, form, st);
+		for (int s = 0; s < S; ++s) if (streamMeter[s].on && n[s] > 0) streamMeter[s].frames += n[s];
+	}
+	struct MeterReading { std::vector<double> Z, range, newest; std::vector<int> counts, rangeCounts, peaks; };
+	// a reading, behind a synchronisation of the batch (false: the setting was never on -- nothing is defined)
+	const double *readBlockPowers(int s) const { return meterReadZ + (size_t)s*meterPitch; }  // (of the newest reading, device)
+	const double *readShortPowers(int s) const { return meterReadSt + (size_t)s*meterPitch; }
+	bool readStreamMeter(hipStream_t st, MeterReading &r) {
+		r.Z.assign((size_t)S, 0.0); r.range.assign((size_t)4*S, 0.0); r.newest.assign((size_t)2*S, 0.0);
+		r.counts.assign((size_t)2*S, 0); r.rangeCounts.assign((size_t)2*S, 0); r.peaks.assign((size_t)2*S, 0);
+		if (!dMeterState) return false;
+		auto hip = [&](hipError_t err) { if (err != hipSuccess) throw smst::Error(std::string("stream meter reading: ") + hipGetErrorString(err), true); };
+		std::vector<unsigned char> tables(meterTableBytes(S));
+		smst::ClipSeg *segs = reinterpret_cast<smst::ClipSeg *>(tables.data());
+		smst::LoudEntry *entries = reinterpret_cast<smst::LoudEntry *>(segs + 2*S);
+		float *weights = reinterpret_cast<float *>(entries + S);
+		for (int s = 0; s < S; ++s) {
+			const StreamMeter &m = streamMeter[s];
+			segs[2*s] = smst::ClipSeg{0, 0, int(std::min(m.frames, m.cap)), 0};
+			segs[2*s + 1] = smst::ClipSeg{0, 0, 0, 0};
+			entries[s] = m.on ? m.entry : smst::LoudEntry{};
+		}
+		for (int k = 0; k < smst::kMaxChannels; ++k) weights[k] = k < C ? loudWeights[k] : 0.0f;
+		hip(hipMemcpy(dMeterTables, tables.data(), tables.size(), hipMemcpyHostToDevice));
+		const smst::ClipSeg *dSegs = reinterpret_cast<const smst::ClipSeg *>(dMeterTables.p);
+		const smst::LoudEntry *dEntries = reinterpret_cast<const smst::LoudEntry *>(dSegs + 2*S);
+		const float *dWeights = reinterpret_cast<const float *>(dEntries + S);
+		smst::LoudScratch w{};
+		double *p = dMeterRead;
+		w.Z = p; p += S;
+		w.counts = reinterpret_cast<int *>(p); p += S;
+		w.gain = reinterpret_cast<float *>(p); p += (S + 1)/2;
+		w.z = p; p += (size_t)S*meterPitch;
+		w.sub = dMeterSub; w.maxSub = meterPitch; w.maxChunks = 0;
+		const smst::LoudRangeScratch range = smst::loudRangeAt(p, S, meterPitch);
+		p += smst::loudRangeDoubles(S, meterPitch);
+		const smst::StreamMeterReading out{reinterpret_cast<int *>(p), p + S};
+		meterReadZ = w.z; meterReadSt = range.st;
+		smst::launchPcmStreamMeterRead(dSegs, dEntries, dWeights, S, C, streamMeterView, w, range, out, st);
+		hip(hipGetLastError());
+		hip(hipStreamSynchronize(st));
+		hip(hipMemcpy(r.Z.data(), w.Z, (size_t)S*sizeof(double), hipMemcpyDeviceToHost));
+		hip(hipMemcpy(r.counts.data(), w.counts, (size_t)2*S*sizeof(int), hipMemcpyDeviceToHost));
+		hip(hipMemcpy(r.range.data(), range.meters, (size_t)4*S*sizeof(double), hipMemcpyDeviceToHost));
+		hip(hipMemcpy(r.rangeCounts.data(), range.counts, (size_t)2*S*sizeof(int), hipMemcpyDeviceToHost));
+		hip(hipMemcpy(r.peaks.data(), out.peaks, (size_t)2*S*sizeof(int), hipMemcpyDeviceToHost));
+		hip(hipMemcpy(r.newest.data(), out.newest, (size_t)2*S*sizeof(double), hipMemcpyDeviceToHost));
+		return true;
+	}
 	void setLoudnessRange(int stream, int on, double sampleRate) {
 		Meter m;
 		if (on) {
@@ -306,6 +448,7 @@ struct PcmOutState {
 	}
 	void setLoudnessWeights(const float *weights) {
 		for (int c = 0; weights && c < C; ++c) if (!(std::isfinite(weights[c]) && weights[c] >= 0)) throw smst::Error("loudness: a channel weight is negative or not finite");
+		if (streamMeterHolds()) throw smst::Error("loudness: a stream meter holds frames that were metered under the present weights (smst_batch_set_pcm_stream_meter clears it)");
 		for (int c = 0; c < C; ++c) loudWeights[c] = weights ? weights[c] : 1.0f;
 	}
 
@@ -588,6 +731,7 @@ int smst_batch_reset(smst_batch *b) {
 		b->engine->reset();
 		b->pcmOut.clearStreamLimitLines(*b->engine, -1); // (the stream limiter's lines begin again, in stream order behind the calls in flight)
 		b->pcmIn.clear(-1);                              // (... and the stream resampler's)
+		b->pcmOut.clearStreamMeter(b->engine->device(), b->engine->stream(), -1);     // (... and the stream meter's)
 	})
 }
 int smst_batch_set_transpose_factor(smst_batch *b, int s, float m, float t) { BATCH_CALL(b->engine->setTransposeFactor(s, m, t)) }
@@ -926,6 +1070,7 @@ static int pcmPrepareOut(smst_batch *b, smst_batch::PcmTable &c, const int *n, i
 	ensureStage(b, b->dOut, (size_t)S*C*k.len);
 	if (memory == SMST_MEM_HOST && k.most > 0) ensurePcmBytes(b, b->hPcmOut, b->dPcmOut, (size_t)S*pcmRowElems(k.most, C)*pcmElemBytes(format));
 	hipSetDevice(e.device());
+	b->pcmOut.ensureStreamMeterScan(e.device(), b->pcmOut.mostStreamMetered(smst::PcmTableLayout(S).outCounts(c.host)), 0, b->stagingAllocs);
 	c.mostLimited = b->pcmOut.mostStreamLimited(smst::PcmTableLayout(S).outCounts(c.host));
 	if (c.mostLimited > 0) b->pcmOut.ensureStreamLimitRows(e, c.mostLimited, b->stagingAllocs);
 	pcmUploadOutTable(b, c, format, true);
@@ -952,13 +1097,12 @@ static void pcmStageOut(smst_batch *b, smst_batch::PcmTable &c, void *out, long 
 	};
 	if (memory == SMST_MEM_DEVICE) {
 		convert(out, ss, fs);
-		b->pcmOut.advance(n);
-		return;
-	}
-	if (most >= 1) {
+	} else if (most >= 1) {
 		convert(b->dPcmOut, pcmRowElems(most, C), C);
 		pcmRawOut(b, out, ss, fs, n, most, format);
 	}
+	// the stream meter: behind the call's last emitting kernel (and behind a host call's copy back: the call does not wait for it)
+	b->pcmOut.meterStream(e.stream(), b->dOut, (long long)C*maxLen, maxLen, n, at.outCounts(c.dev));
 	b->pcmOut.advance(n);
 }
 
@@ -1045,6 +1189,59 @@ int smst_batch_take_pcm_stream_limiter(smst_batch *b, float *minGain, long long 
 		b->engine->synchronize();
 		hipSetDevice(b->engine->device());
 		b->pcmOut.takeStreamLimiter(minGain, limitedFrames);
+	})
+}
+// Stream meter (include/smst.h): the setting, the counters and the device side live in the batch's PCM output state
+int smst_batch_set_pcm_stream_meter(smst_batch *b, int stream, int on, double sampleRate, int maxSubBlocks) {
+	BATCH_CALL(b->pcmOut.setStreamMeter(b->engine->device(), b->engine->stream(), stream, on, sampleRate, maxSubBlocks, b->stagingAllocs))
+}
+int smst_batch_pcm_stream_meter(const smst_batch *b, int stream, int *on, double *sampleRate, int *maxSubBlocks) {
+	if (!b || !b->engine) return fail("null batch");
+	if (stream < 0 || stream >= b->engine->streams()) return fail("stream index out of range");
+	const PcmOutState::StreamMeter &m = b->pcmOut.streamMeter[stream];
+	if (on) *on = m.on;
+	if (sampleRate) *sampleRate = m.sampleRate;
+	if (maxSubBlocks) *maxSubBlocks = m.maxSub;
+	return SMST_OK;
+}
+int smst_batch_pcm_stream_meter_frames(const smst_batch *b, int stream, long long *frames, long long *metered) {
+	if (!b || !b->engine) return fail("null batch");
+	if (stream < 0 || stream >= b->engine->streams()) return fail("stream index out of range");
+	const PcmOutState::StreamMeter &m = b->pcmOut.streamMeter[stream];
+	if (frames) *frames = m.frames;
+	if (metered) *metered = std::min(m.frames, m.cap);
+	return SMST_OK;
+}
+static double loudnessLufs(double Z, int gated);
+static double powerLufs(double P);
+static double rangeLu(double lo, double hi, int n);
+int smst_batch_take_pcm_stream_meter(smst_batch *b, double *lufs, int *blocks, int *gated, double *momentary, double *shortTerm,
+                                     double *momentaryMax, double *shortTermMax, double *range, double *low, double *high,
+                                     int *shortBlocks, int *rangeBlocks, float *truePeaks, float *samplePeaks) {
+	BATCH_CALL({
+		Batch &e = *b->engine;
+		const int S = e.streams();
+		e.synchronize();
+		PcmOutState::MeterReading r;
+		hipSetDevice(e.device());
+		b->pcmOut.readStreamMeter(e.stream(), r); // (false: the setting was never on -- nothing is defined)
+		for (int s = 0; s < S; ++s) {
+			const int n = r.rangeCounts[2*s + 1];
+			if (lufs) lufs[s] = loudnessLufs(r.Z[s], r.counts[2*s + 1]);
+			if (blocks) blocks[s] = r.counts[2*s];
+			if (gated) gated[s] = r.counts[2*s + 1];
+			if (momentary) momentary[s] = powerLufs(r.newest[2*s]);
+			if (shortTerm) shortTerm[s] = powerLufs(r.newest[2*s + 1]);
+			if (momentaryMax) momentaryMax[s] = powerLufs(r.range[4*s]);
+			if (shortTermMax) shortTermMax[s] = powerLufs(r.range[4*s + 1]);
+			if (range) range[s] = rangeLu(r.range[4*s + 2], r.range[4*s + 3], n);
+			if (low) low[s] = n > 0 ? powerLufs(r.range[4*s + 2]) : -INFINITY;
+			if (high) high[s] = n > 0 ? powerLufs(r.range[4*s + 3]) : -INFINITY;
+			if (shortBlocks) shortBlocks[s] = r.rangeCounts[2*s];
+			if (rangeBlocks) rangeBlocks[s] = n;
+			if (truePeaks) std::memcpy(truePeaks + s, &r.peaks[s], sizeof(float));
+			if (samplePeaks) std::memcpy(samplePeaks + s, &r.peaks[(size_t)S + s], sizeof(float));
+		}
 	})
 }
 int smst_batch_pcm_limiter_lookahead(const smst_batch *b, int *frames) {
@@ -1282,6 +1479,10 @@ int smst_batch_exact_pcm(smst_batch *b, const void *in, long long iss, long long
 			if (outSamples[s] >= 0 && b->pcmOut.streamLimit[s].on)
 				throw smst::Error("stream " + std::to_string(s) + " has the stream limiter's setting (smst_batch_set_pcm_stream_limiter), which acts in smst_batch_process_pcm and smst_batch_flush_pcm: "
 				                  "the whole-clip form is smst_batch_set_pcm_limiter");
+		for (int s = 0; s < e.streams(); ++s)
+			if (outSamples[s] >= 0 && b->pcmOut.streamMeter[s].on)
+				throw smst::Error("stream " + std::to_string(s) + " has the stream meter's setting (smst_batch_set_pcm_stream_meter), which acts in smst_batch_process_pcm and smst_batch_flush_pcm: "
+				                  "the whole-clip forms are smst_batch_set_pcm_loudness_range and smst_batch_set_pcm_true_peak");
 		refuseStreamResampled(e, outSamples, "smst_batch_exact_pcm");
 		checkResampledLengths(e, inSamples, outSamples);
 		// a dithered call: the streams' modes and hashes ride in the _pcm calls' table (the frame index is the place in the clip: the counters
@@ -1736,6 +1937,84 @@ int smst_debug_clip_true_peak(int device, int streams, int channels, const int *
 	hip(hipStreamSynchronize(nullptr));
 	if (truePeaks) hip(hipMemcpy(truePeaks, dWords, (size_t)streams*sizeof(float), hipMemcpyDeviceToHost));
 	if (samplePeaks) hip(hipMemcpy(samplePeaks, dWords + streams, (size_t)streams*sizeof(float), hipMemcpyDeviceToHost));
+	return SMST_OK;
+	SMST_CATCH
+}
+// the stream meter's updates and readings alone, on a state of the hook's own: see include/smst.h
+int smst_debug_pcm_stream_meter(int device, int streams, int channels, int calls, const int *counts, const int *readAfter, int form,
+                                const float *image, long long imageSS, long long imageCS,
+                                const double *sampleRates, const float *weights, const int *flags, int maxSubBlocks,
+                                double *Z, int *blocks, int *gated, double *momentaryMax, double *shortTermMax, double *low, double *high,
+                                int *shortBlocks, int *rangeBlocks, float *truePeaks, float *samplePeaks, long long *metered,
+                                double *blockPowers, double *shortPowers, int maxBlocks) {
+	SMST_TRY
+	const int S = streams, Cn = channels;
+	if (S < 1 || Cn < 1 || Cn > smst::kMaxChannels || calls < 1 || !counts || !image || imageSS < 0 || imageCS < 0 || !sampleRates || maxBlocks < 0) throw smst::Error("stream meter: bad arguments");
+	if (form < 0 || form > 2) throw smst::Error("stream meter: unknown form (0: the library's choice, 1: the short-call form, 2: the chunk-scan form)");
+	if (maxSubBlocks < 1) throw smst::Error("stream meter: maxSubBlocks is below 1");
+	auto hip = [&](hipError_t err) { if (err != hipSuccess) throw smst::Error(std::string("stream meter: ") + hipGetErrorString(err), true); };
+	PcmOutState state; // (the batch's own host side: settings, counters, a reading)
+	state.S = S; state.C = Cn;
+	state.streamMeter.assign((size_t)S, PcmOutState::StreamMeter());
+	state.loudWeights.assign((size_t)Cn, 1.0f);
+	for (int c = 0; c < Cn; ++c) {
+		if (weights) state.loudWeights[c] = weights[c];
+		if (!(std::isfinite(state.loudWeights[c]) && state.loudWeights[c] >= 0)) throw smst::Error("loudness: a channel weight is negative or not finite");
+	}
+	std::vector<int> starts((size_t)calls*S, 0);
+	std::vector<long long> total((size_t)S, 0);
+	for (int k = 0; k < calls; ++k)
+		for (int s = 0; s < S; ++s) {
+			if (total[s] > 0x7fffffffLL) throw smst::Error("stream meter: a stream's frames do not fit an int");
+			starts[(size_t)k*S + s] = int(total[s]);
+			total[s] += std::max(counts[(size_t)k*S + s], 0);
+		}
+	long long end = 0;
+	for (int s = 0; s < S; ++s) end = std::max(end, total[s]);
+	hip(hipSetDevice(device));
+	const size_t imageBytes = end ? size_t((S - 1)*imageSS + (Cn - 1)*imageCS + end)*sizeof(float) : 0;
+	Buffer<unsigned char, false> dImage;
+	Buffer<int, false> dCounts;
+	dImage.allocate(imageBytes + 32, "stream meter");
+	dCounts.allocate((size_t)2*calls*S, "stream meter");
+	unsigned char *i0 = dImage + reinterpret_cast<uintptr_t>(image)%16; // (as far behind a 16-byte boundary as the caller's image)
+	if (imageBytes) hip(hipMemcpy(i0, image, imageBytes, hipMemcpyHostToDevice));
+	hip(hipMemcpy(dCounts, counts, (size_t)calls*S*sizeof(int), hipMemcpyHostToDevice));
+	hip(hipMemcpy(dCounts + (size_t)calls*S, starts.data(), (size_t)calls*S*sizeof(int), hipMemcpyHostToDevice));
+	long long allocs = 0;
+	for (int s = 0; s < S; ++s) state.setStreamMeter(device, nullptr, s, (!flags || flags[s]) ? 1 : 0, sampleRates[s], maxSubBlocks, allocs);
+	int reading = 0;
+	for (int k = 0; k < calls; ++k) {
+		state.ensureStreamMeterScan(device, state.mostStreamMetered(counts + (size_t)k*S), form, allocs);
+		state.meterStream(nullptr, reinterpret_cast<const float *>(i0), imageSS, imageCS, counts + (size_t)k*S, dCounts + (size_t)k*S, dCounts + (size_t)(calls + k)*S, form);
+		if (readAfter ? readAfter[k] == 0 : k + 1 < calls) continue;
+		PcmOutState::MeterReading r;
+		hip(hipStreamSynchronize(nullptr));
+		state.readStreamMeter(nullptr, r);
+		const bool last = k + 1 == calls;
+		for (int s = 0; s < S; ++s) {
+			const size_t at = (size_t)reading*S + s;
+			const PcmOutState::StreamMeter &m = state.streamMeter[s];
+			if (Z) Z[at] = r.Z[s];
+			if (blocks) blocks[at] = r.counts[2*s];
+			if (gated) gated[at] = r.counts[2*s + 1];
+			if (momentaryMax) momentaryMax[at] = r.range[4*s];
+			if (shortTermMax) shortTermMax[at] = r.range[4*s + 1];
+			if (low) low[at] = r.range[4*s + 2];
+			if (high) high[at] = r.range[4*s + 3];
+			if (shortBlocks) shortBlocks[at] = r.rangeCounts[2*s];
+			if (rangeBlocks) rangeBlocks[at] = r.rangeCounts[2*s + 1];
+			if (truePeaks) std::memcpy(truePeaks + at, &r.peaks[s], sizeof(float));
+			if (samplePeaks) std::memcpy(samplePeaks + at, &r.peaks[(size_t)S + s], sizeof(float));
+			if (metered) metered[at] = std::min(m.frames, m.cap);
+			if (!last || !m.on) continue;
+			const long long Tm = std::min(m.frames, m.cap);
+			const int h = m.entry.h, nSub = Tm/4 >= h ? int(Tm/h) : 0, nb = std::min(nSub ? nSub - 3 : 0, maxBlocks), ns = std::min(nSub >= 30 ? nSub - 29 : 0, maxBlocks);
+			if (blockPowers && nb > 0) hip(hipMemcpy(blockPowers + (size_t)s*maxBlocks, state.readBlockPowers(s), (size_t)nb*sizeof(double), hipMemcpyDeviceToHost));
+			if (shortPowers && ns > 0) hip(hipMemcpy(shortPowers + (size_t)s*maxBlocks, state.readShortPowers(s), (size_t)ns*sizeof(double), hipMemcpyDeviceToHost));
+		}
+		++reading;
+	}
 	return SMST_OK;
 	SMST_CATCH
 }

@@ -169,7 +169,7 @@ __host__ __device__ inline bool analysisWindowInCall(int B, int M, int I, int in
 // form" tests assert through these that BOTH forms really ran.
 enum LaunchKind {
 	LK_VOC_ALIGNED, LK_VOC_TWISTED, LK_VOC_INTERIOR, LK_VOC_STAGED, LK_VOC_GATHER, LK_VOC_N, LK_VOC_ONE, LK_VOC_ACROSS, LK_VOC_CONT, LK_CHAIN_UNFUSED,
-	LK_ANALYSE_TEAMS, LK_ANALYSE_PAIRS, LK_ANALYSE_TWIST, LK_TWIST_ROWS, LK_ANALYSE_FAST, LK_ANALYSE_GENERIC, LK_SYNTH_TEAMS, LK_SYNTH_FAST, LK_SYNTH_GENERIC, LK_SYNTH_EMIT, LK_EMIT_CARRIED, LK_FEED_ONE_PASS, LK_PCM_IN, LK_PCM_OUT, LK_CLIP_IN, LK_CLIP_OUT, LK_PCM_OUT_DITHERED, LK_CLIP_OUT_DITHERED, LK_PCM_OUT_LEVELLED, LK_CLIP_OUT_LEVELLED, LK_CLIP_PEAK, LK_CLIP_LOUDNESS, LK_CLIP_TRUE_PEAK, LK_CLIP_LIMIT_NEED, LK_CLIP_LIMIT_GAIN, LK_CLIP_OUT_LIMITED, LK_CLIP_LOUDNESS_RANGE, LK_CLIP_RESAMPLE, LK_PCM_LIMIT_FEED, LK_PCM_LIMIT_GAIN, LK_PCM_OUT_LIMITED, LK_PCM_STREAM_RESAMPLE, LK_COUNT
+	LK_ANALYSE_TEAMS, LK_ANALYSE_PAIRS, LK_ANALYSE_TWIST, LK_TWIST_ROWS, LK_ANALYSE_FAST, LK_ANALYSE_GENERIC, LK_SYNTH_TEAMS, LK_SYNTH_FAST, LK_SYNTH_GENERIC, LK_SYNTH_EMIT, LK_EMIT_CARRIED, LK_FEED_ONE_PASS, LK_PCM_IN, LK_PCM_OUT, LK_CLIP_IN, LK_CLIP_OUT, LK_PCM_OUT_DITHERED, LK_CLIP_OUT_DITHERED, LK_PCM_OUT_LEVELLED, LK_CLIP_OUT_LEVELLED, LK_CLIP_PEAK, LK_CLIP_LOUDNESS, LK_CLIP_TRUE_PEAK, LK_CLIP_LIMIT_NEED, LK_CLIP_LIMIT_GAIN, LK_CLIP_OUT_LIMITED, LK_CLIP_LOUDNESS_RANGE, LK_CLIP_RESAMPLE, LK_PCM_LIMIT_FEED, LK_PCM_LIMIT_GAIN, LK_PCM_OUT_LIMITED, LK_PCM_STREAM_RESAMPLE, LK_PCM_STREAM_METER, LK_PCM_STREAM_METER_READ, LK_PCM_STREAM_METER_SCAN, LK_COUNT
 };
 long long launchCount(const char *name); // -1: unknown name
 
@@ -402,5 +402,49 @@ inline int streamResampleTileFrames(int maxFrames) { return maxFrames < 1 ? 1 : 
 inline long long streamResampleDue(long long q, int L, int M) { return q <= 0 ? 0 : (q*L + M - 1)/M; } // R(q) = ceil(max(q, 0)*L/M)
 void launchPcmStreamResample(const float *raw, long long rawStreamStride, long long rawChannelStride, float *image, long long imageStreamStride, long long imageChannelStride,
                              float *lines, long long lineSetStride, const StreamResampleEntry *entries, int S, int C, int maxFrames, int maxSpanPitch, hipStream_t st);
+
+// The R 128 meters' streaming form (include/smst.h, "Stream meter", has the definition; smst_stream_meter.h the kernels), for the streams whose
+// configuration has `on`: every frame that smst_batch_process_pcm / _flush_pcm write for the stream, up to cap = maxSubBlocks*h of them, is
+// measured behind the output conversion.  What a batch carries, device, ONE set ordered by the batch's stream: per stream its configuration
+// (written by the setter's clear kernel, so a call in flight keeps the one it was issued under), per (stream, channel) kStreamMeterDoubles
+// doubles -- x_in at [0], the state run from it at [4], the state run from zero at [8], e0, e1, the running sub-block sum, and the frames
+// metered so far (Tm, a whole number) at [kStreamMeterAt] -- and the last kStreamMeterLine frames, per stream the running true-peak and
+// sample-peak words, [2][S], and the closed sub-block sums sub[(s*C + c)*maxSub + j] in LoudScratch::sub's layout, appended and never rewritten
+constexpr int kStreamMeterDoubles = 16, kStreamMeterAt = 15;
+constexpr int kStreamMeterLine = kTruePeakLead + kTruePeakTrail; // 11 frames: what the taps of the next frames reach back to
+struct StreamMeterConfig { LoudCoef k; double Ac[16]; int h, on, cap, pad; };
+struct PcmStreamMeter {
+	StreamMeterConfig *config = nullptr;
+	double *state = nullptr;
+	float *frames = nullptr;
+	int *words = nullptr;
+	double *sub = nullptr;
+	int maxSub = 0;
+	double *scan = nullptr; // the chunk-scan form's scratch of a call, stream-ordered as the images are: streamMeterScanDoubles(S, C, maxChunks)
+	int maxChunks = 0;
+};
+// The update's two forms give the same bits.  The short-call form serves a call by one lane per (stream, channel), whatever its length; the
+// chunk-scan form spreads a call's chunks over lanes in three passes and pays four launches for it.  A call whose longest metered count
+// reaches kStreamMeterScanFrames takes the chunk-scan form (EXPERIMENTS.md, "Stream meter", has the measurement)
+#ifndef SMST_STREAM_METER_SCAN_FRAMES
+#define SMST_STREAM_METER_SCAN_FRAMES 2048
+#endif
+constexpr int kStreamMeterScanFrames = SMST_STREAM_METER_SCAN_FRAMES;
+inline bool streamMeterScans(int maxFrames, int form) { return form == 2 || (form == 0 && maxFrames >= kStreamMeterScanFrames); }
+inline int streamMeterChunksOf(int maxFrames) { return maxFrames/kLoudChunk + 2; } // the chunks that maxFrames frames touch, from any position
+inline size_t streamMeterScanDoubles(int S, int C, int maxChunks) { return (size_t)S*C*((size_t)maxChunks*6 + 4); }
+// a reading's words beside the clip stages' scratch: peaks [2][S] (true peak, sample peak, float bits), newest [S][2] (z[nb - 1], st[ns - 1])
+struct StreamMeterReading { int *peaks; double *newest; };
+// the stream's (-1: every stream's) meter cleared -- nothing metered -- and, cfg != null, its configuration set; on `st`
+void launchPcmStreamMeterClear(const PcmStreamMeter &m, int S, int C, int stream, const StreamMeterConfig *cfg, hipStream_t st);
+// a call's update: counts [S] device, the frames written for each stream, which lie from column starts[s] (null: 0) of its rows of the image;
+// maxFrames: the largest count of a metered stream (nothing is launched for 0).  form: 0 -- the launcher chooses by maxFrames --, 1 the
+// short-call form, 2 the chunk-scan form; both give the same bits.  On `st`
+void launchPcmStreamMeter(const float *image, long long imageStreamStride, long long imageChannelStride, const int *counts, const int *starts, int S, int C, int maxFrames,
+                          const PcmStreamMeter &m, int form, hipStream_t st);
+// a reading: kLoudGate from its second stage on and kLoudRange over the histories (w.sub = m.sub, w.maxSub = m.maxSub; segs: one segment of
+// count Tm per stream; loud: h == 0 where the stream is not metered), then the true-peak edge and the newest powers.  Three launches on `st`
+void launchPcmStreamMeterRead(const ClipSeg *segs, const LoudEntry *loud, const float *weights, int S, int C, const PcmStreamMeter &m, const LoudScratch &w, const LoudRangeScratch &r,
+                              const StreamMeterReading &out, hipStream_t st);
 
 } // namespace smst

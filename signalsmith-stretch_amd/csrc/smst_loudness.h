@@ -43,6 +43,40 @@ __device__ inline double loudStep(const LoudCoef &k, LoudState &x, double u) {
 	x.s4 = y1 - k.d2*y;
 	return y;
 }
+// ... and its square into the partial sum it belongs to.  One source form for every pass and for the stream meter (smst_stream_meter.h): the
+// library is built with -ffp-contract=on, so the form decides the fusing
+__device__ inline void loudEnergyStep(const LoudCoef &k, LoudState &x, double u, double &e) {
+	const double y = loudStep(k, x, u);
+	e += y*y;
+}
+// x_in of the next chunk: next = A^chunk x + end, end the state the chunk reaches from zero state (likewise one source form).
+// Here and in loudSumStep both operands of an operation can be NaN -- A^chunk itself is not finite where the shelf is unstable --, and the
+// hardware's result then has the sign of the operand that comes first.  The compiler orders the operands of a product or a sum as it
+// likes, kernel by kernel, so on the device the order is written down: a product, three fused multiply-adds and a sum -- what
+// -ffp-contract=on makes of the expression -- in the order kLoudCarry was compiled to before the step became a function: the state in front
+// of the matrix element in the product, the matrix element in front in the multiply-adds, the products in front of `end`
+__device__ inline void loudCarryStep(const double *A, const double *x, const double *end, double *next) {
+#if defined(__HIP_DEVICE_COMPILE__)
+	for (int i = 0; i < 4; ++i) {
+		double t;
+		asm("v_mul_f64 %0, %1, %2" : "=v"(t) : "v"(x[0]), "v"(A[4*i]));
+		asm("v_fma_f64 %0, %1, %2, %0" : "+v"(t) : "v"(A[4*i + 1]), "v"(x[1]));
+		asm("v_fma_f64 %0, %1, %2, %0" : "+v"(t) : "v"(A[4*i + 2]), "v"(x[2]));
+		asm("v_fma_f64 %0, %1, %2, %0" : "+v"(t) : "v"(A[4*i + 3]), "v"(x[3]));
+		asm("v_add_f64 %0, %1, %2" : "=v"(next[i]) : "v"(t), "v"(end[i]));
+	}
+#else
+	for (int i = 0; i < 4; ++i) next[i] = A[4*i]*x[0] + A[4*i + 1]*x[1] + A[4*i + 2]*x[2] + A[4*i + 3]*x[3] + end[i];
+#endif
+}
+// one addend of a sub-block's sum, the sum in front: kLoudGate's first stage, and the stream meter's running sum
+__device__ inline void loudSumStep(double &sum, double part) {
+#if defined(__HIP_DEVICE_COMPILE__)
+	asm("v_add_f64 %0, %0, %1" : "+v"(sum) : "v"(part));
+#else
+	sum += part;
+#endif
+}
 
 // Word `word` of the aligned 16-byte words that cover run[0, n): its floats inside the run go to dst[their index].  [lo, hi): the indices
 // around run[0] that the segment owns (lo <= 0, n <= hi); a word inside them is read whole, another one element by element
@@ -97,8 +131,8 @@ template <bool Energy> __global__ __launch_bounds__(256) void kLoudChunks(const 
 		const float *mine = rows + lane*kLoudPitch;
 		if constexpr (Energy) {
 			const int first = int(min(max(split - q0, 0ll), (long long)n));        // samples of the tile in the chunk's first sub-block
-			for (int i = 0; i < first; ++i) { const double y = loudStep(coef, x, double(mine[i])); e0 += y*y; }
-			for (int i = first; i < n; ++i) { const double y = loudStep(coef, x, double(mine[i])); e1 += y*y; }
+			for (int i = 0; i < first; ++i) loudEnergyStep(coef, x, double(mine[i]), e0);
+			for (int i = first; i < n; ++i) loudEnergyStep(coef, x, double(mine[i]), e1);
 		} else {
 			for (int i = 0; i < n; ++i) loudStep(coef, x, double(mine[i]));
 		}
@@ -135,17 +169,16 @@ __global__ __launch_bounds__(64) void kLoudCarry(const ClipSeg *__restrict__ seg
 		for (int u = 0; u < kLoudCarryAhead && k0 + u < nChunks; ++u) {
 			double *at = p + (size_t)4*(k0 + u);
 			double next[4];
-			for (int i = 0; i < 4; ++i) {
-				at[i] = x[i];
-				next[i] = A[4*i]*x[0] + A[4*i + 1]*x[1] + A[4*i + 2]*x[2] + A[4*i + 3]*x[3] + cur[u][i];
-			}
+			for (int i = 0; i < 4; ++i) at[i] = x[i];
+			loudCarryStep(A, x, cur[u], next);
 			for (int i = 0; i < 4; ++i) x[i] = next[i];
 		}
 	}
 }
 
-// grid (S), 256 threads; LDS: 256 doubles.  Writes every stream's meters: one that is not measured (h == 0, a run of zeros, nothing) has no block
-__global__ __launch_bounds__(256) void kLoudGate(const ClipSeg *__restrict__ segs, const LoudEntry *__restrict__ loud, const float *__restrict__ weights, int C, LoudScratch w) {
+// grid (S), 256 threads; LDS: 256 doubles.  Writes every stream's meters: one that is not measured (h == 0, a run of zeros, nothing) has no block.
+// FromPartials false: the sub-block sums are in w.sub already (the stream meter's histories, smst_stream_meter.h) -- the first stage is left out
+template <bool FromPartials> __global__ __launch_bounds__(256) void kLoudGate(const ClipSeg *__restrict__ segs, const LoudEntry *__restrict__ loud, const float *__restrict__ weights, int C, LoudScratch w) {
 	extern __shared__ __attribute__((aligned(16))) unsigned char smemRaw[];
 	double *tile = reinterpret_cast<double *>(smemRaw); // [256]
 	const int s = blockIdx.x, tid = threadIdx.x;
@@ -154,12 +187,12 @@ __global__ __launch_bounds__(256) void kLoudGate(const ClipSeg *__restrict__ seg
 	const int N = (h == 0 || g0.zeros || g1.zeros) ? 0 : max(g0.count, 0) + max(g1.count, 0);
 	const int nb = (h > 0 && N/4 >= h) ? (N - 4*h)/h + 1 : 0, nSub = nb ? nb + 3 : 0; // (block i: sub-blocks i ... i + 3)
 	double *sub = w.sub + (size_t)s*C*w.maxSub, *z = w.z + (size_t)s*w.maxSub;
-	for (int idx = tid; idx < C*nSub; idx += 256) {
+	if constexpr (FromPartials) for (int idx = tid; idx < C*nSub; idx += 256) {
 		const int c = idx/nSub, j = idx%nSub;
 		const int k0 = int((long long)j*h/kLoudChunk), k1 = int(((long long)(j + 1)*h - 1)/kLoudChunk);
 		const double *part = w.partials + ((size_t)s*C + c)*w.maxChunks*2;
 		double sum = 0.0;
-		for (int k = k0; k <= k1; ++k) sum += part[2*(size_t)k + ((long long)k*kLoudChunk/h == j ? 0 : 1)];
+		for (int k = k0; k <= k1; ++k) loudSumStep(sum, part[2*(size_t)k + ((long long)k*kLoudChunk/h == j ? 0 : 1)]);
 		sub[(size_t)c*w.maxSub + j] = sum;
 	}
 	__syncthreads();
@@ -230,7 +263,7 @@ void launchClipLoudness(const float *image, long long imageSS, long long imageCS
 	hipLaunchKernelGGL(kLoudChunks<false>, grid, dim3(256), loudLdsBytes(), st, image, imageSS, imageCS, segs, loud, w);
 	hipLaunchKernelGGL(kLoudCarry, dim3(divUp(S*C, 64)), dim3(64), 0, st, segs, loud, S, C, w);
 	hipLaunchKernelGGL(kLoudChunks<true>, grid, dim3(256), loudLdsBytes(), st, image, imageSS, imageCS, segs, loud, w);
-	hipLaunchKernelGGL(kLoudGate, dim3(S), dim3(256), 256*sizeof(double), st, segs, loud, weights, C, w);
+	hipLaunchKernelGGL(kLoudGate<true>, dim3(S), dim3(256), 256*sizeof(double), st, segs, loud, weights, C, w);
 	countLaunch(LK_CLIP_LOUDNESS);
 }
 
