@@ -791,7 +791,7 @@ int smst_debug_clip_loudness_range(int device, int streams, int channels, const 
  * A sample-rate converter in front of the engine, in smst_batch_exact_pcm: a stream may carry a rational ratio L/M = up/down, the batch's
  * rate over its clips' rate, and its frames are resampled on the device to the batch's rate.  Everything behind that point -- outputSeek,
  * process, flush, peak, loudness, true peak, limiter, conversion -- runs unchanged.  A caller who makes the batch's rate the delivery rate
- * gets "any rate in, one rate out".  The reference has no sample-rate notion beyond its presets.
+ * gets "any rate in, one rate out"; "Output resample" below delivers each clip at a rate of its own.  The reference has no sample-rate notion beyond its presets.
  *
  * Ratio.  L and M are integers, 1 <= L, M <= SMST_RESAMPLE_MAX_TERM once the library has reduced them by their gcd; 2*M <= 9*L and 2*L <= 9*M
  * (at most 4.5 either way: 192 kHz -> 44.1 kHz is 147/640).  1/1 means "not resampled".  At most SMST_RESAMPLE_MAX_RATIOS distinct reduced
@@ -828,7 +828,7 @@ int smst_debug_clip_loudness_range(int device, int streams, int channels, const 
  * and smst_batch_process_pcm, _seek_pcm and _output_seek_pcm return SMST_ERR_INVALID, before anything runs, if a stream that takes part has a
  * ratio other than 1/1: skipping the stage silently would be a lie.  smst_batch_flush_pcm has no input and is unaffected.  The too-short and
  * left-out streams of a call stay as they are.
- * Out of scope: resampling the output; resampling in the planar calls (the streaming frame calls have a setting of their own: "Stream
+ * Out of scope: resampling the output in the streaming calls ("Output resample" below is the whole-clip form); resampling in the planar calls (the streaming frame calls have a setting of their own: "Stream
  * resample" below); irrational or time-varying ratios; a quality setting; a fused PCM-to-resampled kernel without the raw image.
  * SMST_ERR_INVALID with a message that names the limit: a term outside [1, SMST_RESAMPLE_MAX_TERM]; a ratio beyond 4.5 either way; a ninth
  * distinct ratio; a stream index out of range; a null batch; in a call, an Nr that does not fit an int. */
@@ -854,6 +854,68 @@ int smst_debug_resample_taps(int up, int down, float *out, int *taps);
 int smst_debug_clip_resample(int device, int streams, int channels, const int *counts, const int *ratios,
                              const float *image, long long imageStreamStride, long long imageChannelStride,
                              const int *segments, float *out, long long outStreamStride, long long outChannelStride);
+/* ---- Output resample (EXTENSION; opt-in: a batch that never calls smst_batch_set_pcm_out_resample launches the kernels, writes the bytes and counts the launches it did before) ----
+ * "Resample" brings clips of any rate to the batch's rate, and every result came back at that one rate: a caller who handed in a 44.1 kHz file
+ * and wanted one back resampled the result on the CPU -- behind the loudness, true-peak, limiter and dither stages, whose figures then no
+ * longer described the delivered file.  This is the converter behind the engine, in smst_batch_exact_pcm: a stream may carry a second
+ * rational ratio L/M = up/down, the DELIVERY rate over the batch's rate, and the frames the engine rendered are resampled on the device
+ * between the engine's output and the level stages.  The reference has no sample-rate notion beyond its presets.
+ *
+ * Ratio.  Per stream, reduced by the library, with the limits of "Resample": 1 <= L, M <= SMST_RESAMPLE_MAX_TERM, at most 4.5 either way;
+ * 1/1 turns the stage off.  The tables are the batch's existing ratio tables -- the same formula, the same float32 table -- and the
+ * SMST_RESAMPLE_MAX_RATIOS slots are shared with the two input settings: a slot is live while any of the three settings of any stream
+ * uses it.  A setter call with a ratio the batch already has allocates nothing; tables are never uploaded in a call.
+ *
+ * Lengths.  outSamples[s] stays what the caller receives: Nd delivered frames at the delivery rate.  The engine renders
+ * E = floor((Nd - 1)*M/L) + 1 frames at the batch's rate (64-bit integers; E must fit an int): the smallest count for which the centre
+ * i = (n*M)/L of every delivered frame n < Nd lies inside [0, E).  For such a stream smst_batch_exact_pcm behaves towards the engine
+ * exactly as if the caller had asked for E frames: exactLengths(frames_s, E), rate_s = frames_s/float(E), where frames_s is already Nr for
+ * a stream that also has the input setting; SMST_ERR_SHORT in status as ever.  The caller's buffers hold Nd frames: nothing of the call's
+ * interface is sized by E (smst_batch_pcm_out_render_length reports it).
+ *
+ * Delivered frames.  Let r(0 ... E-1) be the rendered clip: the frames [0, outputIndex) of the main process followed by the flush.
+ * Delivered frame n sits at i = (n*M)/L, p = (n*M) mod L and is float32(sum_j double(c[p][j])*double(r(i + j - (H - 1)))), j ascending
+ * from 0.0, r outside [0, E) = +0.0: "Resample"'s arithmetic word for word, by the same device function.  Frames n >= Nd are not formed,
+ * although ceil(E*L/M) may exceed Nd; the right edge of the filter meets zeros at E, not the frames a longer render would have held.
+ * Known answers (those of "Resample"):
+ *   3/2: Nd = 8 gives E = 5; r(2) = 1: bca067e3 be4717b5 3ed8327b 3f7ae0ea 3ed8327b be4717b5 bca067e3 3dddb185
+ *   2/3: Nd = 5 gives E = 7; r(3) = 1: bc55dff0 3c594cd8 3f2740ad 3c594cd8 bc55dff0
+ *   147/160: Nd = 441 gives E = 479 (440*160/147 = 478.9...; the 480 of "Resample"'s ceil(441*160/147) is not needed).  160/147: Nd = 480 gives E = 441.
+ *
+ * Everything behind the converter runs on the delivered frames: the clip peak, BS.1770 loudness and loudness range, true peak, the limiter,
+ * gain, dither (whose frame index is the delivered frame's), conversion, overs and peaks.  The caller gives the DELIVERY rate as the
+ * sampleRate of smst_batch_set_pcm_loudness / _loudness_range.  The limiter's lookahead stays one batch-wide count, and for such a stream
+ * it counts delivered frames.  A too-short stream gets Nd zeros, as ever; a left-out stream (negative count) is untouched.
+ *
+ * Which calls.  smst_batch_exact_pcm serves the setting, in host and device memory and in every format, and it may be combined with
+ * smst_batch_set_pcm_resample on the same stream (a 44.1 kHz file through a 48 kHz batch and back).  smst_batch_exact (planar),
+ * smst_batch_process_pcm and smst_batch_flush_pcm return SMST_ERR_INVALID with a message, before anything runs, if a stream that takes part
+ * has an output ratio other than 1/1.  smst_batch_seek_pcm and smst_batch_output_seek_pcm write no output and are unaffected.
+ *
+ * How.  The engine's output image gets a third column behind the flush's; one kernel (csrc/smst_resample_out.h) reads each such
+ * stream's two-piece rendered clip and writes its delivered frames there, and the level stages and the conversion find them as one
+ * segment.  Streams at 1/1 keep their two segments, and their bytes, in the same call.  The call's table of rendered segments and entries
+ * exists twice, is allocated by the first such call and counted in smst_batch_workspace_bytes; a steady-state call allocates nothing and
+ * adds no host synchronisation.
+ * Out of scope: the streaming calls (a carried line behind the engine, in front of the stream limiter and meter); the planar calls;
+ * irrational or time-varying ratios; a quality setting.
+ * SMST_ERR_INVALID with a message that names the limit: the limits of "Resample", the ninth distinct ratio across the three settings
+ * included; a stream index out of range; a null batch; in a call, an E that does not fit an int. */
+/* stream = -1: every stream.  1/1 turns the stage off.  The first call with a ratio the batch does not have builds that ratio's table and
+ * puts it into device memory: tables are never uploaded in a call */
+int smst_batch_set_pcm_out_resample(smst_batch *b, int stream, int up, int down);
+/* the stream's reduced output ratio (1/1: none); either pointer may be null */
+int smst_batch_pcm_out_resample(const smst_batch *b, int stream, int *up, int *down);
+/* E of outSamples delivered frames of the stream (outSamples itself at 1/1), or a negative code */
+long long smst_batch_pcm_out_render_length(const smst_batch *b, int stream, long long outSamples);
+/* test hook: the output-resample kernel alone, planar fp32 to planar fp32, as smst_debug_clip_resample (host pointers, staged whole as far
+ * behind a 16-byte boundary as the caller's; a stream at 1/1 is left alone, and so is everything in `out` outside the destination runs).
+ * counts: [streams] Nd; ratios: [streams][2] up, down; srcSegments: [streams][2][4] as smst_debug_clip_copy's, where the E rendered frames
+ * lie in `image` (src and count: segment 0 holds the frames [0, k) at its column, segment 1 the frames [k, E) at its own; the counts add up
+ * to E); dstSegments: [streams][2][4], the DESTINATION of the Nd delivered frames (dst and count; the counts add up to Nd) */
+int smst_debug_clip_resample_out(int device, int streams, int channels, const int *counts, const int *ratios,
+                                 const float *image, long long imageStreamStride, long long imageChannelStride, const int *srcSegments,
+                                 const int *dstSegments, float *out, long long outStreamStride, long long outChannelStride);
 /* ---- Stream resample (EXTENSION; opt-in: a batch that never calls smst_batch_set_pcm_stream_resample launches the kernels, writes the bytes and counts the launches it did before) ----
  * The converter above knows a whole clip.  A live 44.1 kHz source in a 48 kHz batch had to be resampled on the CPU before every
  * smst_batch_process_pcm.  The converter is a non-recursive FIR, so it has an exact streaming form: with the last T - 1 input frames carried
@@ -892,7 +954,7 @@ int smst_debug_clip_resample(int device, int streams, int channels, const int *c
  * line.  The lines exist twice, a call reads one set and writes the other, and everything is ordered by the batch's stream.  Lines and call
  * tables live in device memory, allocated by the first setter call with a ratio other than 1/1, never in a call, and counted in
  * smst_batch_workspace_bytes; the raw image grows with the first call that needs it; a steady-state call allocates nothing.
- * Out of scope: resampling the output; the planar calls; smst_batch_output_seek_pcm; stretch_cli (a whole-file tool, which has --rate);
+ * Out of scope: resampling the output in the streaming calls; the planar calls; smst_batch_output_seek_pcm; stretch_cli (a whole-file tool, which has --rate);
  * time-varying ratios.
  * SMST_ERR_INVALID with a message, before anything runs: the limits of "Resample"; a stream index out of range; a null batch;
  * smst_batch_output_seek_pcm and smst_batch_exact_pcm with a participating stream that has the setting (smst_batch_exact_pcm has

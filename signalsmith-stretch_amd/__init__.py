@@ -173,6 +173,10 @@ _SIGNATURES = {
     "smst_resample_ratio": (C.c_int, [C.c_double, C.c_double, _ip, _ip]),
     "smst_debug_resample_taps": (C.c_int, [C.c_int, C.c_int, _fp, _ip]),
     "smst_debug_clip_resample": (C.c_int, [C.c_int, C.c_int, C.c_int, _ip, _ip, C.c_void_p, _ll, _ll, _ip, C.c_void_p, _ll, _ll]),
+    "smst_batch_set_pcm_out_resample": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
+    "smst_batch_pcm_out_resample": (C.c_int, [C.c_void_p, C.c_int, _ip, _ip]),
+    "smst_batch_pcm_out_render_length": (_ll, [C.c_void_p, C.c_int, _ll]),
+    "smst_debug_clip_resample_out": (C.c_int, [C.c_int, C.c_int, C.c_int, _ip, _ip, C.c_void_p, _ll, _ll, _ip, _ip, C.c_void_p, _ll, _ll]),
     "smst_batch_set_pcm_stream_resample": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
     "smst_batch_pcm_stream_resample": (C.c_int, [C.c_void_p, C.c_int, _ip, _ip]),
     "smst_batch_pcm_stream_resample_latency": (C.c_int, [C.c_void_p, C.c_int, _ip]),
@@ -524,6 +528,23 @@ def debug_clip_resample(counts, ratios, channels, image, image_ss, image_cs, seg
     assert out.size >= (S - 1)*out_ss + (channels - 1)*out_cs + int((seg[:, :, 1] + seg[:, :, 2]).max(initial=0))
     _check(lib, lib.smst_debug_clip_resample(device, S, channels, n.ctypes.data_as(_ip), r.ctypes.data_as(_ip), C.c_void_p(image.ctypes.data), image_ss, image_cs,
                                              seg.ctypes.data_as(_ip), C.c_void_p(out.ctypes.data), out_ss, out_cs))
+    return out
+
+
+def debug_clip_resample_out(counts, ratios, channels, image, image_ss, image_cs, src_segments, dst_segments, out, out_ss, out_cs, device=0, lib=None):
+    """smst_debug_clip_resample_out on numpy buffers (planar float32, 1-d views whose first element is the first stream's first row; strides
+    in floats; counts int [S], the delivered frames Nd; ratios int [S, 2]; src_segments int [S, 2, 4], where the E rendered frames lie in
+    ``image``; dst_segments int [S, 2, 4], the destination).  ``out`` is written in place and returned."""
+    lib = lib if lib is not None else load_library()
+    n, r = np.ascontiguousarray(counts, np.int32), np.ascontiguousarray(ratios, np.int32)
+    src, dst = np.ascontiguousarray(src_segments, np.int32), np.ascontiguousarray(dst_segments, np.int32)
+    S = n.shape[0]
+    assert r.shape == (S, 2) and src.shape == (S, 2, 4) and dst.shape == (S, 2, 4)
+    assert image.dtype == np.float32 and out.dtype == np.float32 and image.ndim == 1 and out.ndim == 1 and image.strides[0] == 4 and out.strides[0] == 4
+    assert image.size >= (S - 1)*image_ss + (channels - 1)*image_cs + int((src[:, :, 0] + src[:, :, 2]).max(initial=0))
+    assert out.size >= (S - 1)*out_ss + (channels - 1)*out_cs + int((dst[:, :, 1] + dst[:, :, 2]).max(initial=0))
+    _check(lib, lib.smst_debug_clip_resample_out(device, S, channels, n.ctypes.data_as(_ip), r.ctypes.data_as(_ip), C.c_void_p(image.ctypes.data), image_ss, image_cs,
+                                                 src.ctypes.data_as(_ip), dst.ctypes.data_as(_ip), C.c_void_p(out.ctypes.data), out_ss, out_cs))
     return out
 
 
@@ -1106,6 +1127,25 @@ class StretchBatch:
     def resampled_length(self, stream, in_samples):
         """-> Nr = ceil(in_samples*up/down) of the stream's ratio: the clip's length at the batch's rate, what out_samples derives from"""
         n = int(self.lib.smst_batch_resampled_length(self.h, int(stream), int(in_samples)))
+        if n < 0:
+            _check(self.lib, n)
+        return n
+
+    def set_pcm_out_resample(self, up, down, stream=-1):
+        """Resample behind the engine in exactFrames (include/smst.h, "Output resample"): the stream's clips are delivered at up/down of the
+        batch's rate -- out_samples counts delivered frames, and the level stages, dither and conversion run on them.  1/1 turns it off;
+        stream = -1: every stream."""
+        _check(self.lib, self.lib.smst_batch_set_pcm_out_resample(self.h, int(stream), int(up), int(down)))
+
+    def pcm_out_resample(self, stream):
+        """-> (up, down), the stream's reduced output ratio; (1, 1): delivered at the batch's rate"""
+        up, down = C.c_int(0), C.c_int(0)
+        _check(self.lib, self.lib.smst_batch_pcm_out_resample(self.h, int(stream), C.byref(up), C.byref(down)))
+        return up.value, down.value
+
+    def out_render_length(self, stream, out_samples):
+        """-> E = (out_samples - 1)*down//up + 1 of the stream's output ratio: the frames the engine renders for out_samples delivered ones"""
+        n = int(self.lib.smst_batch_pcm_out_render_length(self.h, int(stream), int(out_samples)))
         if n < 0:
             _check(self.lib, n)
         return n

@@ -1335,6 +1335,7 @@ static void refuseWholeClipLevel(const smst_batch *b, const unsigned char *activ
 }
 static void refuseResampled(const Batch &e, const int *takesPart, const char *call); // (below, with the whole-clip calls)
 static void refuseStreamResampled(const Batch &e, const int *takesPart, const char *call);
+static void refuseOutResampled(const Batch &e, const int *takesPart, const char *call);
 int smst_batch_process_pcm(smst_batch *b, const void *in, long long iss, long long ifs, const int *inSamples,
                            void *out, long long oss, long long ofs, const int *outSamples, int format, int memory) {
 	BATCH_CALL({
@@ -1344,6 +1345,7 @@ int smst_batch_process_pcm(smst_batch *b, const void *in, long long iss, long lo
 		checkPcmSide(out, ofs, outSamples, e.streams(), e.channels(), false);
 		refuseWholeClipLevel(b, nullptr);
 		refuseResampled(e, nullptr, "smst_batch_process_pcm");
+		refuseOutResampled(e, nullptr, "smst_batch_process_pcm");
 		smst_batch::PcmTable &c = beginPcmCall(b);
 		const int *fed = inSamples; // (a stream with the stream-resample setting: its k)
 		const int maxIn = pcmStageIn(b, c, in, iss, ifs, inSamples, format, memory, &fed);
@@ -1374,6 +1376,7 @@ int smst_batch_flush_pcm(smst_batch *b, void *out, long long oss, long long ofs,
 		checkPcmSide(out, ofs, outSamples, e.streams(), e.channels(), true);
 		const FlushCounts f(outSamples, e.streams());
 		refuseWholeClipLevel(b, f.active.data());
+		refuseOutResampled(e, outSamples, "smst_batch_flush_pcm");
 		smst_batch::PcmTable &c = beginPcmCall(b);
 		const int maxOut = pcmPrepareOut(b, c, f.counts.data(), format, memory);
 		e.flush(b->dOut, (long long)e.channels()*maxOut, maxOut, f.counts.data(), rates, f.mask());
@@ -1437,6 +1440,21 @@ static void refuseStreamResampled(const Batch &e, const int *takesPart, const ch
 			throw smst::Error(std::string(call) + ": stream " + std::to_string(s) + " has the stream-resample setting (smst_batch_set_pcm_stream_resample), which acts in smst_batch_process_pcm and "
 			                  "smst_batch_seek_pcm only" + (std::strcmp(call, "smst_batch_exact_pcm") == 0 ? ": the whole-clip form is smst_batch_set_pcm_resample" : ""));
 }
+// Output resample (include/smst.h): only smst_batch_exact_pcm serves a stream's output ratio.  The other calls that write output refuse where a
+// stream that takes part has one
+static void refuseOutResampled(const Batch &e, const int *takesPart, const char *call) {
+	for (int s = 0; s < e.streams(); ++s)
+		if ((!takesPart || takesPart[s] >= 0) && e.outResampled(s))
+			throw smst::Error(std::string(call) + ": stream " + std::to_string(s) + " has an output resample ratio other than 1/1 (smst_batch_set_pcm_out_resample): smst_batch_exact_pcm only");
+}
+// E of a stream's Nd delivered frames, which must fit an int (2*M <= 9*L: E < 4.5*Nd + 1, so a count below 2^40 cannot overflow 64 bits)
+static long long outRenderLengthChecked(const Batch &e, int s, long long outSamples) {
+	const std::string what = "out resample: stream " + std::to_string(s) + ": " + std::to_string(outSamples) + " delivered frames";
+	if (outSamples > (1LL << 40)) throw smst::Error(what + " need more than 2147483647 rendered frames (the length at the batch's rate must fit an int)");
+	const long long E = e.outRenderLengthOf(s, outSamples);
+	if (E > 0x7fffffffLL) throw smst::Error(what + " need " + std::to_string(E) + " rendered frames, more than 2147483647 (the length at the batch's rate must fit an int)");
+	return E;
+}
 // ... and that call refuses a clip whose length at the batch's rate does not fit an int
 static long long resampledLengthChecked(const Batch &e, int s, long long inSamples) {
 	if (inSamples > (1LL << 40)) throw smst::Error("resample: stream " + std::to_string(s) + ": " + std::to_string(inSamples) + " frames resample to more than 2147483647 (the length at the batch's rate must fit an int)");
@@ -1446,6 +1464,7 @@ static long long resampledLengthChecked(const Batch &e, int s, long long inSampl
 }
 static void checkResampledLengths(const Batch &e, const int *inSamples, const int *outSamples) {
 	for (int s = 0; s < e.streams(); ++s) if (outSamples[s] >= 0 && e.resampled(s)) resampledLengthChecked(e, s, inSamples[s]);
+	for (int s = 0; s < e.streams(); ++s) if (outSamples[s] >= 0 && e.outResampled(s)) outRenderLengthChecked(e, s, outSamples[s]);
 }
 
 int smst_batch_exact(smst_batch *b, const float *in, long long iss, long long ics, const int *inSamples,
@@ -1454,6 +1473,7 @@ int smst_batch_exact(smst_batch *b, const float *in, long long iss, long long ic
 		Batch &e = *b->engine;
 		checkExactArgs(e, in, inSamples, out, outSamples, 0, 0, false, memory);
 		refuseResampled(e, outSamples, "smst_batch_exact");
+		refuseOutResampled(e, outSamples, "smst_batch_exact");
 		if (memory == SMST_MEM_DEVICE) {
 			runExact(e, Batch::ClipIo{in, iss, ics, out, oss, ocs, 0}, inSamples, outSamples, status);
 		} else {
@@ -1494,6 +1514,7 @@ int smst_batch_exact_pcm(smst_batch *b, const void *in, long long iss, long long
 		Batch::ClipIo io{in, iss, ifs, out, oss, ofs, format};
 		b->pcmOut.clipModes(table ? table->out : plain, io);
 		io.resample = true; // (checkResampledLengths above: every Nr fits an int)
+		io.outResample = true; // (... and every E)
 		if (memory == SMST_MEM_DEVICE) {
 			runExact(e, io, inSamples, outSamples, status);
 		} else {
@@ -1528,12 +1549,30 @@ long long smst_batch_resampled_length(const smst_batch *b, int stream, long long
 	return resampledLengthChecked(*b->engine, stream, inSamples);
 	SMST_CATCH
 }
+// Output resample (include/smst.h): the ratios live in the engine beside the input side's, whose tables and slots they share
+int smst_batch_set_pcm_out_resample(smst_batch *b, int stream, int up, int down) { BATCH_CALL(b->engine->setResample(stream, up, down, Batch::kResampleOut)) }
+int smst_batch_pcm_out_resample(const smst_batch *b, int stream, int *up, int *down) {
+	BATCH_CALL({
+		int l = 1, m = 1;
+		b->engine->outResampleOf(stream, l, m);
+		if (up) *up = l;
+		if (down) *down = m;
+	})
+}
+long long smst_batch_pcm_out_render_length(const smst_batch *b, int stream, long long outSamples) {
+	if (!b || !b->engine) return fail("null batch");
+	SMST_TRY
+	if (stream < 0 || stream >= b->engine->streams()) throw smst::Error("stream index out of range");
+	if (outSamples < 0) throw smst::Error("out resample: negative sample count");
+	return outRenderLengthChecked(*b->engine, stream, outSamples);
+	SMST_CATCH
+}
 // Stream resample (include/smst.h): the ratios live in the engine beside the whole-clip ones, whose tables and slots they share; the lines,
 // the counters and the call tables here.  Everything is allocated by the setter, never in a call
 int smst_batch_set_pcm_stream_resample(smst_batch *b, int stream, int up, int down) {
 	BATCH_CALL({
 		Batch &e = *b->engine;
-		e.setResample(stream, up, down, true); // (every refusal, before anything changes)
+		e.setResample(stream, up, down, Batch::kResampleStream); // (every refusal, before anything changes)
 		hipSetDevice(e.device());
 		if (PcmStreamResampleState::any(e) && !b->pcmIn.dLines) {
 			const size_t set = (size_t)e.streams()*e.channels()*smst::kStreamResampleLine;
@@ -2242,6 +2281,61 @@ int smst_debug_clip_resample(int device, int streams, int channels, const int *c
 	hip(hipMemcpy(dEntries, entries.data(), entries.size()*sizeof(smst::ResampleEntry), hipMemcpyHostToDevice));
 	smst::launchClipResample(reinterpret_cast<const float *>(i0), imageSS, imageCS, reinterpret_cast<float *>(o0), outSS, outCS, reinterpret_cast<const smst::ClipSeg *>(dSegs.p),
 	                         reinterpret_cast<const smst::ResampleEntry *>(dEntries.p), streams, channels, most, maxSpanPitch, nullptr);
+	hip(hipGetLastError());
+	hip(hipStreamSynchronize(nullptr));
+	if (outBytes) hip(hipMemcpy(out, o0, outBytes, hipMemcpyDeviceToHost));
+	return SMST_OK;
+	SMST_CATCH
+}
+// the output-resample kernel alone: see include/smst.h
+int smst_debug_clip_resample_out(int device, int streams, int channels, const int *counts, const int *ratios, const float *image, long long imageSS, long long imageCS,
+                                 const int *srcSegments, const int *dstSegments, float *out, long long outSS, long long outCS) {
+	SMST_TRY
+	if (streams < 1 || channels < 1 || channels > smst::kMaxChannels || !counts || !ratios || !image || !srcSegments || !dstSegments || !out || imageSS < 0 || imageCS < 0 || outSS < 0 || outCS < 0)
+		throw smst::Error("clip resample out: bad arguments");
+	auto hip = [&](hipError_t err) { if (err != hipSuccess) throw smst::Error(std::string("clip resample out: ") + hipGetErrorString(err), true); };
+	hip(hipSetDevice(device));
+	std::vector<smst::ResampleOutEntry> entries((size_t)streams, smst::ResampleOutEntry{nullptr, 0, 0, 0, 0, 0, 0, 0, 0});
+	std::vector<Buffer<float, false>> tables((size_t)streams); // (one per resampled stream: a hook's streams do not share them)
+	int endIn = 0, endOut = 0, most = 0, maxSpanPitch = 4;
+	for (int s = 0; s < streams; ++s) {
+		const int *r = srcSegments + 8*s, *g = dstSegments + 8*s;
+		int up = ratios[2*s], down = ratios[2*s + 1];
+		smst::resampleReduce(up, down);
+		if (counts[s] < 0) throw smst::Error("clip resample out: negative sample count");
+		if (up == 1 && down == 1) continue; // not resampled: its rows of `out` are left alone
+		const long long E = smst::resampleRenderLength(counts[s], up, down);
+		if (E > 0x7fffffffLL) throw smst::Error("clip resample out: the rendered clip is too long");
+		if (r[0] < 0 || r[2] < 0 || r[4] < 0 || r[6] < 0 || (long long)r[2] + r[6] != E) throw smst::Error("clip resample out: the two source segments' counts do not add up to the rendered length");
+		if (g[1] < 0 || g[2] < 0 || g[5] < 0 || g[6] < 0 || (long long)g[2] + g[6] != counts[s]) throw smst::Error("clip resample out: the two destination segments' counts do not add up to the delivered length");
+		const smst::ResampleShape shape = smst::resampleShapeOf(up, down);
+		std::vector<float> table((size_t)shape.L*shape.pitch);
+		smst::resampleTaps(shape, table.data());
+		tables[s].allocate(table.size(), "clip resample out");
+		hip(hipMemcpy(tables[s], table.data(), table.size()*sizeof(float), hipMemcpyHostToDevice));
+		entries[s] = smst::ResampleOutEntry{tables[s].p, int(E), counts[s], shape.L, shape.M, shape.H, shape.T, shape.pitch, 0};
+		for (int k = 0; k < 2; ++k) if (r[4*k + 2] > 0) endIn = std::max(endIn, r[4*k] + r[4*k + 2]);
+		for (int k = 0; k < 2; ++k) if (g[4*k + 2] > 0) endOut = std::max(endOut, g[4*k + 1] + g[4*k + 2]);
+		most = std::max(most, counts[s]);
+		maxSpanPitch = std::max(maxSpanPitch, smst::resampleSpanPitch(shape.L, shape.M, shape.T));
+	}
+	// host pointers are staged whole: every stream's rows, as far behind a 16-byte boundary as the caller's
+	const size_t imageBytes = endIn ? size_t((streams - 1)*imageSS + (channels - 1)*imageCS + endIn)*sizeof(float) : 0;
+	const size_t outBytes = endOut ? size_t((streams - 1)*outSS + (channels - 1)*outCS + endOut)*sizeof(float) : 0;
+	Buffer<unsigned char, false> dImage, dOut, dSrc, dDst, dEntries;
+	dImage.allocate(imageBytes + 32, "clip resample out");
+	dOut.allocate(outBytes + 32, "clip resample out");
+	dSrc.allocate((size_t)2*streams*sizeof(smst::ClipSeg), "clip resample out");
+	dDst.allocate((size_t)2*streams*sizeof(smst::ClipSeg), "clip resample out");
+	dEntries.allocate(entries.size()*sizeof(smst::ResampleOutEntry), "clip resample out");
+	unsigned char *i0 = dImage + reinterpret_cast<uintptr_t>(image)%16, *o0 = dOut + reinterpret_cast<uintptr_t>(out)%16;
+	if (imageBytes) hip(hipMemcpy(i0, image, imageBytes, hipMemcpyHostToDevice));
+	if (outBytes) hip(hipMemcpy(o0, out, outBytes, hipMemcpyHostToDevice));
+	hip(hipMemcpy(dSrc, srcSegments, (size_t)2*streams*sizeof(smst::ClipSeg), hipMemcpyHostToDevice));
+	hip(hipMemcpy(dDst, dstSegments, (size_t)2*streams*sizeof(smst::ClipSeg), hipMemcpyHostToDevice));
+	hip(hipMemcpy(dEntries, entries.data(), entries.size()*sizeof(smst::ResampleOutEntry), hipMemcpyHostToDevice));
+	smst::launchClipResampleOut(reinterpret_cast<const float *>(i0), imageSS, imageCS, reinterpret_cast<float *>(o0), outSS, outCS, reinterpret_cast<const smst::ClipSeg *>(dSrc.p),
+	                            reinterpret_cast<const smst::ClipSeg *>(dDst.p), reinterpret_cast<const smst::ResampleOutEntry *>(dEntries.p), streams, channels, most, maxSpanPitch, nullptr);
 	hip(hipGetLastError());
 	hip(hipStreamSynchronize(nullptr));
 	if (outBytes) hip(hipMemcpy(out, o0, outBytes, hipMemcpyDeviceToHost));

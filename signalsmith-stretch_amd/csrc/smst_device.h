@@ -169,7 +169,7 @@ __host__ __device__ inline bool analysisWindowInCall(int B, int M, int I, int in
 // form" tests assert through these that BOTH forms really ran.
 enum LaunchKind {
 	LK_VOC_ALIGNED, LK_VOC_TWISTED, LK_VOC_INTERIOR, LK_VOC_STAGED, LK_VOC_GATHER, LK_VOC_N, LK_VOC_ONE, LK_VOC_ACROSS, LK_VOC_CONT, LK_CHAIN_UNFUSED,
-	LK_ANALYSE_TEAMS, LK_ANALYSE_PAIRS, LK_ANALYSE_TWIST, LK_TWIST_ROWS, LK_ANALYSE_FAST, LK_ANALYSE_GENERIC, LK_SYNTH_TEAMS, LK_SYNTH_FAST, LK_SYNTH_GENERIC, LK_SYNTH_EMIT, LK_EMIT_CARRIED, LK_FEED_ONE_PASS, LK_PCM_IN, LK_PCM_OUT, LK_CLIP_IN, LK_CLIP_OUT, LK_PCM_OUT_DITHERED, LK_CLIP_OUT_DITHERED, LK_PCM_OUT_LEVELLED, LK_CLIP_OUT_LEVELLED, LK_CLIP_PEAK, LK_CLIP_LOUDNESS, LK_CLIP_TRUE_PEAK, LK_CLIP_LIMIT_NEED, LK_CLIP_LIMIT_GAIN, LK_CLIP_OUT_LIMITED, LK_CLIP_LOUDNESS_RANGE, LK_CLIP_RESAMPLE, LK_PCM_LIMIT_FEED, LK_PCM_LIMIT_GAIN, LK_PCM_OUT_LIMITED, LK_PCM_STREAM_RESAMPLE, LK_PCM_STREAM_METER, LK_PCM_STREAM_METER_READ, LK_PCM_STREAM_METER_SCAN, LK_COUNT
+	LK_ANALYSE_TEAMS, LK_ANALYSE_PAIRS, LK_ANALYSE_TWIST, LK_TWIST_ROWS, LK_ANALYSE_FAST, LK_ANALYSE_GENERIC, LK_SYNTH_TEAMS, LK_SYNTH_FAST, LK_SYNTH_GENERIC, LK_SYNTH_EMIT, LK_EMIT_CARRIED, LK_FEED_ONE_PASS, LK_PCM_IN, LK_PCM_OUT, LK_CLIP_IN, LK_CLIP_OUT, LK_PCM_OUT_DITHERED, LK_CLIP_OUT_DITHERED, LK_PCM_OUT_LEVELLED, LK_CLIP_OUT_LEVELLED, LK_CLIP_PEAK, LK_CLIP_LOUDNESS, LK_CLIP_TRUE_PEAK, LK_CLIP_LIMIT_NEED, LK_CLIP_LIMIT_GAIN, LK_CLIP_OUT_LIMITED, LK_CLIP_LOUDNESS_RANGE, LK_CLIP_RESAMPLE, LK_PCM_LIMIT_FEED, LK_PCM_LIMIT_GAIN, LK_PCM_OUT_LIMITED, LK_PCM_STREAM_RESAMPLE, LK_PCM_STREAM_METER, LK_PCM_STREAM_METER_READ, LK_PCM_STREAM_METER_SCAN, LK_CLIP_RESAMPLE_OUT, LK_COUNT
 };
 long long launchCount(const char *name); // -1: unknown name
 
@@ -385,6 +385,17 @@ inline long long resampledLength(long long N, int L, int M) { return (N*L + M - 
 void resampleTaps(const ResampleShape &g, float *out);
 void launchClipResample(const float *raw, long long rawStreamStride, long long rawChannelStride, float *image, long long imageStreamStride, long long imageChannelStride,
                         const ClipSeg *segs, const ResampleEntry *entries, int S, int C, int maxFrames, int maxSpanPitch, hipStream_t st);
+
+// The converter BEHIND the engine (include/smst.h, "Output resample", has the definition; smst_resample_out.h the kernel): a stream's ratio L/M is
+// the delivery rate over the batch's; for Nd delivered frames the engine renders E = resampleRenderLength(Nd) frames, the smallest count that
+// holds the centre (n*M)/L of every delivered frame.  ResampleOutEntry: one per stream, device -- L == 0: no ratio, the kernel leaves the
+// stream's rows alone.  The kernel reads the E rendered frames where srcSegs puts them (src and count of the two segments: frames [0, k) and
+// [k, E); dst is not read) and writes delivered frame n where dstSegs puts it (dst and count; the counts add up to Nd; src is not read).
+// maxFrames: the largest Nd; maxSpanPitch: the largest resampleSpanPitch of the launch's entries
+struct ResampleOutEntry { const float *taps; int E, Nd, L, M, H, T, pitch, pad; };
+inline long long resampleRenderLength(long long Nd, int L, int M) { return Nd < 1 ? 0 : ((Nd - 1)*M)/L + 1; }
+void launchClipResampleOut(const float *image, long long imageStreamStride, long long imageChannelStride, float *out, long long outStreamStride, long long outChannelStride,
+                           const ClipSeg *srcSegs, const ClipSeg *dstSegs, const ResampleOutEntry *entries, int S, int C, int maxFrames, int maxSpanPitch, hipStream_t st);
 
 // The converter's streaming form (include/smst.h, "Stream resample", has the definition; smst_stream_resample.h the kernel): a stream with the
 // setting has been handed `fed` raw frames since its line was last cleared, and the engine the first made = streamResampleDue(fed - H) frames

@@ -420,9 +420,10 @@ void Batch::allocateCallTables() {
 	dOutSamples = callSets.sets[0].outSamples;
 	dFlags = callSets.sets[0].flags;
 	for (std::vector<int> *v : {&flushV.blockOut, &flushV.blockIn, &flushV.synthChannels, &outputSeekV.seekSamples, &outputSeekV.surplus, &outputSeekV.preOut, &outputSeekV.done,
-	                            &exactV.seekLen, &exactV.rest, &exactV.procOut, &exactV.flushN, &exactV.frames}) v->assign(S, 0);
+	                            &exactV.seekLen, &exactV.rest, &exactV.procOut, &exactV.flushN, &exactV.frames, &exactV.render}) v->assign(S, 0);
 	resampleSlot.assign(S, -1);
 	streamResampleSlot.assign(S, -1);
+	outResampleSlot.assign(S, -1);
 	for (std::vector<unsigned char> *v : {&flushV.runBlock, &flushV.on, &outputSeekV.mask, &exactV.run}) v->assign(S, 0);
 	outputSeekV.rates.assign(S, 1.0);
 	exactV.rates.assign(S, 0.0f);
@@ -1778,36 +1779,43 @@ void Batch::exact(const ClipIo &io, const int *inSamples, const int *outSamples,
 	}
 	clipSets.create();
 	ClipSet &cs = clipSets.begin(); // (the call before the previous one: its clip kernels must have read the tables)
-	std::vector<int> &seekLen = exactV.seekLen, &rest = exactV.rest, &procOut = exactV.procOut, &flushN = exactV.flushN, &frames = exactV.frames;
+	std::vector<int> &seekLen = exactV.seekLen, &rest = exactV.rest, &procOut = exactV.procOut, &flushN = exactV.flushN, &frames = exactV.frames, &render = exactV.render;
 	std::vector<float> &rates = exactV.rates;
 	std::vector<unsigned char> &run = exactV.run;
 	int maxSeek = 0, maxRest = 0, maxProc = 0, maxFlush = 0, maxZeros = 0;
 	int maxRaw = 0, maxResampled = 0, maxPlainSeek = 0, maxPlainRest = 0; // the resampled streams that run: their longest clip, before and behind; the others' longest segments
+	int maxDelivered = 0; // the out-resampled streams that run: their longest delivered clip
 	bool anyRun = false;
 	for (int s = 0; s < S; ++s) {
 		seekLen[s] = rest[s] = procOut[s] = flushN[s] = run[s] = 0;
 		rates[s] = 0.0f;
-		frames[s] = 0;
+		frames[s] = render[s] = 0;
 		if (outSamples[s] < 0) continue;
 		// (a resampled stream behaves exactly as if the caller had handed over its Nr frames; the caller has checked that Nr fits an int)
 		frames[s] = io.resample && resampled(s) ? int(resampledLengthOf(s, inSamples[s])) : inSamples[s];
-		ExactLengths l = exactLengths(frames[s], outSamples[s]);
+		// (an out-resampled stream behaves towards the engine exactly as if the caller had asked for its E frames; the caller has checked that E fits an int)
+		const bool outRes = io.outResample && outResampled(s);
+		render[s] = outRes ? int(outRenderLengthOf(s, outSamples[s])) : outSamples[s];
+		ExactLengths l = exactLengths(frames[s], render[s]);
 		if (l.tooShort) { maxZeros = std::max(maxZeros, outSamples[s]); continue; }
-		l.outputIndex = std::min(std::max(l.outputIndex, 0), outSamples[s]); // (seekLength/rate <= outSamples[s] but for its rounding: the two output parts stay inside the stream's count)
+		l.outputIndex = std::min(std::max(l.outputIndex, 0), render[s]); // (seekLength/rate <= render[s] but for its rounding: the two output parts stay inside the stream's count)
 		run[s] = 1;
 		anyRun = true;
 		rates[s] = l.rate;
 		seekLen[s] = l.seekLength; rest[s] = frames[s] - l.seekLength;
 		if (io.resample && resampled(s)) { maxRaw = std::max(maxRaw, inSamples[s]); maxResampled = std::max(maxResampled, frames[s]); }
 		else { maxPlainSeek = std::max(maxPlainSeek, seekLen[s]); maxPlainRest = std::max(maxPlainRest, rest[s]); }
-		procOut[s] = l.outputIndex; flushN[s] = outSamples[s] - l.outputIndex;
+		procOut[s] = l.outputIndex; flushN[s] = render[s] - l.outputIndex;
+		if (outRes) maxDelivered = std::max(maxDelivered, outSamples[s]);
 		maxSeek = std::max(maxSeek, seekLen[s]); maxRest = std::max(maxRest, rest[s]);
 		maxProc = std::max(maxProc, procOut[s]); maxFlush = std::max(maxFlush, flushN[s]);
 	}
 	// columns and row pitches: multiples of 4 floats, so that every row and both columns of an image begin on 16-byte boundaries
 	auto up4 = [](int n) { return (n + 3)/4*4; };
 	const int P = direct ? 0 : up4(maxSeek), Q = direct ? 0 : up4(maxProc);
-	const int pitchIn = std::max(up4(P + maxRest), 4), pitchOut = std::max(up4(Q + maxFlush), 4);
+	// (a call with an out-resampled stream: a third column R of the output image, where kClipResampleOut puts those streams' delivered frames)
+	const int R = up4(Q + maxFlush);
+	const int pitchIn = std::max(up4(P + maxRest), 4), pitchOut = std::max(maxDelivered > 0 ? up4(R + maxDelivered) : R, 4);
 	const size_t needIn = (size_t)S*C*pitchIn, needOut = (size_t)S*C*pitchOut;
 	growScratch(dClipIn, clipInCapacity, needIn, needIn/8 + 1024, true);
 	growScratch(dClipOut, clipOutCapacity, needOut, needOut/8 + 1024, true);
@@ -1820,11 +1828,44 @@ void Batch::exact(const ClipIo &io, const int *inSamples, const int *outSamples,
 			segIn[2*s + 1] = ClipSeg{seekLen[s], P, rest[s], 0};
 			if (!direct) segOut[2*s] = ClipSeg{0, 0, procOut[s], 0};
 			segOut[2*s + 1] = ClipSeg{Q, procOut[s], flushN[s], 0};
+			if (io.outResample && outResampled(s)) { // what the level stages and kClipOut read: the delivered frames, one segment from column R
+				segOut[2*s] = ClipSeg{R, 0, outSamples[s], 0};
+				segOut[2*s + 1] = none;
+			}
 		} else if (outSamples[s] > 0) {
 			segOut[2*s] = ClipSeg{0, 0, outSamples[s], 1}; // too short: zeros, and the stream's state stays as it is
 		}
 	}
 	const long long inImgSS = (long long)C*pitchIn, outImgSS = (long long)C*pitchOut;
+	int maxOutSpanPitch = 4;
+	const ResampleOutTableLayout outAt(S);
+	if (maxDelivered > 0) {
+		// The out-resampled streams: where their rendered frames lie (the two segments every other stream hands to kClipOut), where their
+		// delivered frames go, and their entries, in a table of its own
+		if (direct) throw Error("exact: an out-resampled stream in a planar call");
+		for (ClipSet &t : clipSets.sets) { // (both sets with the first such call)
+			if (t.outHost) continue;
+			t.outHost = pinnedAlloc<unsigned char>(outAt.bytes());
+			t.outDev = devAlloc<unsigned char>(outAt.bytes());
+			wsBytes += outAt.bytes();
+		}
+		for (int s = 0; s < S; ++s) {
+			const ClipSeg none{0, 0, 0, 0};
+			ResampleOutEntry e{nullptr, 0, 0, 0, 0, 0, 0, 0, 0};
+			outAt.srcSegs(cs.outHost)[2*s] = outAt.srcSegs(cs.outHost)[2*s + 1] = outAt.dstSegs(cs.outHost)[2*s] = outAt.dstSegs(cs.outHost)[2*s + 1] = none;
+			if (run[s] && outResampled(s)) {
+				const ResampleSlot &slot = resampleSlots[outResampleSlot[s]];
+				const ResampleShape &g = slot.shape;
+				e = ResampleOutEntry{slot.taps, render[s], outSamples[s], g.L, g.M, g.H, g.T, g.pitch, 0};
+				maxOutSpanPitch = std::max(maxOutSpanPitch, resampleSpanPitch(g.L, g.M, g.T));
+				outAt.srcSegs(cs.outHost)[2*s] = ClipSeg{0, 0, procOut[s], 0};
+				outAt.srcSegs(cs.outHost)[2*s + 1] = ClipSeg{Q, procOut[s], flushN[s], 0};
+				outAt.dstSegs(cs.outHost)[2*s] = ClipSeg{0, R, outSamples[s], 0};
+			}
+			outAt.entries(cs.outHost)[s] = e;
+		}
+		SMST_HIP(hipMemcpyAsync(cs.outDev, cs.outHost, outAt.bytes(), hipMemcpyHostToDevice, st));
+	}
 	if (maxResampled > 0) {
 		// The resampled streams: kClipIn moves their whole clips into the raw image -- a second segment table, one whole-clip segment per
 		// stream -- and leaves them out of the input image, which kClipResample fills where the call's two input segments put their frames
@@ -1877,13 +1918,17 @@ void Batch::exact(const ClipIo &io, const int *inSamples, const int *outSamples,
 			process(dClipIn + P, inImgSS, pitchIn, rest.data(), dClipOut, outImgSS, pitchOut, procOut.data(), run.data());
 		}
 		flush(dClipOut + Q, outImgSS, pitchOut, flushN.data(), rates.data(), run.data());
+		// the delivered frames of the out-resampled streams, from the finished two-piece image into its third column: in front of every level stage
+		if (maxDelivered > 0)
+			launchClipResampleOut(dClipOut, outImgSS, pitchOut, dClipOut, outImgSS, pitchOut, outAt.srcSegs(cs.outDev), outAt.dstSegs(cs.outDev), outAt.entries(cs.outDev), S, C,
+			                      maxDelivered, maxOutSpanPitch, st);
 	}
 	// behind the call's last emitting kernel (everything of a call is joined into `st`), in front of whatever synchronize() / signalStream() wait for
 	bool wholeClip = false;
 	if (io.pcm.level.table && io.wholeClip) for (int s = 0; s < S; ++s) wholeClip = wholeClip || (run[s] && io.wholeClip[s]);
 	if (wholeClip) { // the clips' peaks, from the finished image: what kClipOut forms those streams' gains from
 		SMST_HIP(hipMemsetAsync(io.pcm.level.clipPeak, 0, (size_t)S*sizeof(int), st));
-		launchClipPeak(dClipOut, outImgSS, pitchOut, cs.dev + (size_t)2*S, S, C, std::max(maxProc, maxFlush), io.pcm.level.clipPeak, st);
+		launchClipPeak(dClipOut, outImgSS, pitchOut, cs.dev + (size_t)2*S, S, C, std::max(std::max(maxProc, maxFlush), maxDelivered), io.pcm.level.clipPeak, st);
 	}
 	PcmLevelIo level = io.pcm.level;
 	int loudMost = 0, loudSub = 0;
@@ -1931,7 +1976,7 @@ void Batch::exact(const ClipIo &io, const int *inSamples, const int *outSamples,
 		level.limitPitch = pitch;
 	}
 	launchClipOut(io.format, dClipOut, outImgSS, pitchOut, io.out, io.outStreamStride, io.outInnerStride, cs.dev + (size_t)2*S, S, C,
-	              std::max(std::max(direct ? 0 : maxProc, maxFlush), maxZeros), io.pcm.overs, st, io.pcm.dither, level);
+	              std::max(std::max(std::max(direct ? 0 : maxProc, maxFlush), maxZeros), maxDelivered), io.pcm.overs, st, io.pcm.dither, level);
 	clipSets.end(st);
 	SMST_HIP(hipGetLastError());
 	if (tooShort) for (int s = 0; s < S; ++s) if (outSamples[s] >= 0) tooShort[s] = run[s] ? 0 : 1; // (only once every stage has been issued)
@@ -1998,10 +2043,10 @@ void resampleReduce(int &up, int &down) {
 		throw Error("resample: the ratio " + std::to_string(up) + "/" + std::to_string(down) + " upsamples by more than 4.5 (2*up <= 9*down)");
 }
 
-void Batch::setResample(int stream, int up, int down, bool streaming) {
+void Batch::setResample(int stream, int up, int down, int setting) {
 	if (stream < -1 || stream >= S) throw Error("stream index out of range");
 	resampleReduce(up, down);
-	std::vector<int> &mine = streaming ? streamResampleSlot : resampleSlot; // (a slot's users are the streams of BOTH settings)
+	std::vector<int> &mine = setting == kResampleStream ? streamResampleSlot : setting == kResampleOut ? outResampleSlot : resampleSlot; // (a slot's users are the streams of ALL three settings)
 	SMST_HIP(hipSetDevice(dev));
 	const bool none = up == 1 && down == 1;
 	const int first = stream < 0 ? 0 : stream, last = stream < 0 ? S : stream + 1;
@@ -2051,6 +2096,19 @@ void Batch::streamResampleOf(int stream, int &up, int &down) const {
 	if (stream < 0 || stream >= S) throw Error("stream index out of range");
 	up = down = 1;
 	if (streamResampleSlot[stream] >= 0) { up = resampleSlots[streamResampleSlot[stream]].shape.L; down = resampleSlots[streamResampleSlot[stream]].shape.M; }
+}
+
+void Batch::outResampleOf(int stream, int &up, int &down) const {
+	if (stream < 0 || stream >= S) throw Error("stream index out of range");
+	up = down = 1;
+	if (outResampleSlot[stream] >= 0) { up = resampleSlots[outResampleSlot[stream]].shape.L; down = resampleSlots[outResampleSlot[stream]].shape.M; }
+}
+
+long long Batch::outRenderLengthOf(int stream, long long outSamples) const {
+	if (stream < 0 || stream >= S) throw Error("stream index out of range");
+	if (outResampleSlot[stream] < 0 || outSamples < 0) return outSamples;
+	const ResampleShape &g = resampleSlots[outResampleSlot[stream]].shape;
+	return resampleRenderLength(outSamples, g.L, g.M);
 }
 
 long long Batch::resampledLengthOf(int stream, long long inSamples) const {

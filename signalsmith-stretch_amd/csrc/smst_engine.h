@@ -120,14 +120,23 @@ public:
 		                                           // h whatever their mode, and if one of them runs, kLoudRange (smst_loudness_range.h) does behind the four passes)
 		const unsigned char *limiter = nullptr;    // (host, [S]; null where no stream is limited: the streams whose level entry pcmLimited() names -- if one
 		                                           // of them runs, the two passes of smst_limiter.h do, and kClipOut takes their r from the engine's scratch)
+		bool outResample = false;                  // (the call serves the streams' OUTPUT ratios, a frame format only: outSamples[s] of a stream that has one counts delivered
+		                                           // frames, the engine renders outRenderLengthOf(s, outSamples[s]), and kClipResampleOut (smst_resample_out.h) forms the delivered
+		                                           // frames in front of the level stages; false: the caller has refused them)
 		bool resample = false; };                  // (the call serves the streams' ratios, a frame format only: inSamples[s] of a stream that has one counts frames at the
 		                                           // clip's rate, and kClipResample (smst_resample.h) forms its Nr frames in front of the stages; false: the caller has refused them)
 	// Resample (include/smst.h, "Resample"): a stream's ratio up/down, the batch's rate over its clips' rate; 1/1: none.  setResample reduces
 	// and checks the ratio (Error with the limit in its message) and, for the first stream that takes a ratio, builds the ratio's table and puts
 	// it into device memory -- never in a call; a ratio that no stream has any more frees its table.  stream -1: every stream
 	// streaming: the stream's OTHER setting, the one the streaming calls read (include/smst.h, "Stream resample") -- a ratio of its own per
-	// stream, which shares the tables and their kResampleMaxRatios slots: a slot is live while either setting of any stream uses it
-	void setResample(int stream, int up, int down, bool streaming = false);
+	// stream, which shares the tables and their kResampleMaxRatios slots: a slot is live while any setting of any stream uses it
+	// output: the stream's THIRD setting (include/smst.h, "Output resample"), the delivery rate over the batch's rate, which exact() serves
+	// behind the engine; it shares the tables and the slots as well
+	enum ResampleSetting { kResampleClip = 0, kResampleStream = 1, kResampleOut = 2 };
+	void setResample(int stream, int up, int down, int setting = kResampleClip);
+	bool outResampled(int stream) const { return outResampleSlot[stream] >= 0; }
+	void outResampleOf(int stream, int &up, int &down) const;
+	long long outRenderLengthOf(int stream, long long outSamples) const; // E of outSamples delivered frames of the stream (outSamples itself where it has no output ratio)
 	bool resampled(int stream) const { return resampleSlot[stream] >= 0; }
 	bool streamResampled(int stream) const { return streamResampleSlot[stream] >= 0; }
 	void streamResampleOf(int stream, int &up, int &down) const;
@@ -248,7 +257,7 @@ private:
 	// ... and of the whole-call stages, [S] each: a stage's own, never shared (exact() hands its own down to outputSeek(), process() and flush())
 	struct FlushScratch { std::vector<int> blockOut, blockIn, synthChannels; std::vector<unsigned char> runBlock, on; } flushV;
 	struct OutputSeekScratch { std::vector<int> seekSamples, surplus, preOut, done; std::vector<double> rates; std::vector<unsigned char> mask; } outputSeekV;
-	struct ExactScratch { std::vector<int> seekLen, rest, procOut, flushN, frames; std::vector<float> rates; std::vector<unsigned char> run; } exactV; // (frames: a clip's length at the batch's rate)
+	struct ExactScratch { std::vector<int> seekLen, rest, procOut, flushN, frames, render; std::vector<float> rates; std::vector<unsigned char> run; } exactV; // (frames: a clip's length at the batch's rate; render: the frames the engine renders, E of an out-resampled stream)
 	long allocEvents = 0; // device allocations + pinned allocations + host table growth since construction
 	size_t wsBytes = 0;
 	DevBatch d{};
@@ -346,7 +355,8 @@ private:
 	size_t limitCapacity = 0;
 	int limitH = kLimitDefaultLookahead;
 	// resHost / resDev: the table of a call with a resampled stream (ResampleTableLayout), allocated by the first such call
-	struct ClipSet { ClipSeg *host, *dev; unsigned char *resHost, *resDev; }; // [2][S][2]: input segments, output segments
+	// outHost / outDev: the table of a call with an out-resampled stream (ResampleOutTableLayout), allocated by the first such call
+	struct ClipSet { ClipSeg *host, *dev; unsigned char *resHost, *resDev, *outHost, *outDev; }; // [2][S][2]: input segments, output segments
 	TwoSets<ClipSet> clipSets;
 	// Resample: the raw image of the resampled streams' clips ([S][C][pitch], grown on demand as the images are); the ratios' tables, each
 	// [L][pitch] floats in device memory from the first stream that takes the ratio to the last that drops it; every stream's slot (-1: none)
@@ -354,7 +364,7 @@ private:
 	size_t clipRawCapacity = 0;
 	struct ResampleSlot { ResampleShape shape{0, 0, 0, 0, 0}; float *taps = nullptr; int users = 0; };
 	ResampleSlot resampleSlots[kResampleMaxRatios];
-	std::vector<int> resampleSlot, streamResampleSlot; // per stream, the slot of its whole-clip and of its streaming ratio (-1: none)
+	std::vector<int> resampleSlot, streamResampleSlot, outResampleSlot; // per stream, the slot of its whole-clip, of its streaming and of its output ratio (-1: none)
 	// a device scratch that holds `need` floats, allocated with `room` more; true: it was replaced (the old one freed behind a synchronise).  workspace: counted in workspaceBytes()
 	bool growScratch(float *&scratch, size_t &capacity, size_t need, size_t room, bool workspace);
 	StreamParams *dParams = nullptr, *hParams = nullptr; // (hParams: pinned staging of uploadParams())

@@ -14,6 +14,7 @@
 // PcmOutCall       where one call's output conversion finds all of that on the device
 // ResampleTableLayout  the table a whole-clip call with a resampled stream adds on the input side (the engine's; two sets as the above)
 // StreamResampleTableLayout  the table a streaming call adds on the input side where a stream has the stream-resample setting
+// ResampleOutTableLayout  the table a whole-clip call with an out-resampled stream adds on the output side (the engine's; two sets)
 #pragma once
 #include "smst_device.h"
 #include <cstddef>
@@ -104,6 +105,24 @@ struct StreamResampleTableLayout {
 	StreamResampleEntry *entries(void *base) const { return pcmTableAt<StreamResampleEntry>(base, entries()); }
 };
 static_assert(alignof(StreamResampleEntry) <= 2*sizeof(int) && sizeof(StreamResampleEntry)%8 == 0, "the entries' 64-bit members are aligned behind two runs of S ints");
+
+// ResampleOutTableLayout: what a whole-clip call with an out-resampled stream adds (include/smst.h, "Output resample"), a table of its own --
+// pinned host staging with a device twin, uploaded in ONE copy.  Three sections of a batch of S streams, in order:
+//   srcSegs  [S][2] ClipSeg           where the stream's E rendered frames lie in the output image: the main process's frames, then the flush's
+//   dstSegs  [S][2] ClipSeg           where kClipResampleOut puts the stream's Nd delivered frames in the same image: one segment, at the third column
+//   entries  [S]    ResampleOutEntry  E, Nd, the reduced ratio, its shape and where its table lies in device memory (L == 0: no ratio)
+struct ResampleOutTableLayout {
+	size_t S;
+	explicit ResampleOutTableLayout(int streams) : S(size_t(streams)) {}
+	size_t srcSegs() const { return 0; }
+	size_t dstSegs() const { return srcSegs() + 2*S*sizeof(ClipSeg); }
+	size_t entries() const { return dstSegs() + 2*S*sizeof(ClipSeg); }
+	size_t bytes() const { return entries() + S*sizeof(ResampleOutEntry); }
+	ClipSeg *srcSegs(void *base) const { return pcmTableAt<ClipSeg>(base, srcSegs()); }
+	ClipSeg *dstSegs(void *base) const { return pcmTableAt<ClipSeg>(base, dstSegs()); }
+	ResampleOutEntry *entries(void *base) const { return pcmTableAt<ResampleOutEntry>(base, entries()); }
+};
+static_assert(alignof(ResampleOutEntry) <= 16, "the entries begin on a 16-byte boundary where the table does");
 
 struct PcmMeters {
 	size_t S;

@@ -7,6 +7,7 @@
 //               [--split-computation] [--device=N] [--out-format=s16|s24|f32] [--dither=none|tpdf|tpdf-hp] [--dither-seed=N]
 //               [--exact] [--gain=dB] [--protect=dBFS | --normalize=dBFS] [--loudness=LUFS] [--true-peak]
 //               [--limit] [--limit-lookahead=ms] [--loudness-range] [--max-short-term=LUFS] [--max-momentary=LUFS] [--rate=HZ]
+//               [--out-rate=source|HZ]
 //               in.wav out.wav [in2.wav out2.wav ...]
 //
 // --out-format (also "--out-format s24"): the samples of the files written -- 16-bit (the default, as the reference's CLI writes), 24-bit by the
@@ -47,6 +48,12 @@
 // integer rate is resampled on the GPU on its way in (include/smst.h, "Resample"; the ratio comes from smst_resample_ratio), so files of
 // different rates form one batch.  A file's output length is round(Nr*time), today's rule on its length at HZ.  One line per file:
 // "resample: <file> <its rate> Hz -> <HZ> Hz ratio=<up>/<down>".
+// --out-rate=source|HZ (needs --rate): every file is written at its own input rate (source) or at HZ instead of the batch's rate -- the
+// rendered clip is resampled on the GPU behind the engine (include/smst.h, "Output resample"; the ratio comes from
+// smst_resample_ratio(batch rate, delivery rate)), in front of the loudness, true-peak, limiter and dither stages, which therefore see the
+// samples that are written: --loudness and --loudness-range measure at each file's delivery rate.  A file's output length is
+// round(N*time*delivery rate/its own rate), from its own length N.  --limit-lookahead stays one count of frames for the batch, converted
+// at the batch's rate.  One more line per file: "out-resample: <file> <batch rate> Hz -> <rate> Hz ratio=<up>/<down>".
 // Files given together must share sample rate and channel count (they form one batch); lengths may differ.  With --rate only the channel
 // count must be shared.
 #include <algorithm>
@@ -152,6 +159,16 @@ int main(int argc, char **argv) {
 		std::fprintf(stderr, "--rate needs --exact (or --protect, --normalize or --loudness, which imply it): whole clips only\n");
 		return 2;
 	}
+	const std::string outRateText = flagText(argc, argv, "out-rate", "", consumed);
+	const bool outResample = !outRateText.empty(), outRateSource = outRateText == "source";
+	if (outResample && !resample) {
+		std::fprintf(stderr, "--out-rate needs --rate=HZ: it delivers each file at a rate other than the batch's\n");
+		return 2;
+	}
+	if (outResample && !outRateSource && !(std::atof(outRateText.c_str()) >= 1)) {
+		std::fprintf(stderr, "--out-rate is source or a sample rate in Hz\n");
+		return 2;
+	}
 	const double limitLookaheadMs = flagValue(argc, argv, "limit-lookahead", 1.5);
 	const float gain = fromDecibels(flagValue(argc, argv, "gain", 0)), ceiling = fromDecibels(flagValue(argc, argv, protect ? "protect" : "normalize", 0));
 	std::vector<std::string> files;
@@ -186,6 +203,14 @@ int main(int argc, char **argv) {
 		CHECK(smst_batch_set_pcm_resample(batch, s, up, down));
 		std::printf("resample: %s %d Hz -> %.0f Hz ratio=%d/%d\n", files[2*s].c_str(), int(inputs[s].sampleRate), rate, up, down);
 	}
+	std::vector<double> deliveryRate(S, batchRate); // the rate each file is written at
+	if (outResample) for (int s = 0; s < S; ++s) { // the files' output ratios: each file's delivery rate over HZ
+		deliveryRate[s] = outRateSource ? double(inputs[s].sampleRate) : std::atof(outRateText.c_str());
+		int up = 1, down = 1;
+		CHECK(smst_resample_ratio(batchRate, deliveryRate[s], &up, &down));
+		CHECK(smst_batch_set_pcm_out_resample(batch, s, up, down));
+		std::printf("out-resample: %s %.0f Hz -> %.0f Hz ratio=%d/%d\n", files[2*s].c_str(), batchRate, deliveryRate[s], up, down);
+	}
 	const int inLat = smst_batch_input_latency(batch), outLat = smst_batch_output_latency(batch), interval = smst_batch_interval_samples(batch);
 
 	// per-stream lengths of the three stages, exactly as cmd/main.cpp:55-82 computes them
@@ -196,7 +221,7 @@ int main(int argc, char **argv) {
 		const int n = int(inputs[s].length());
 		long long atRate = n; // the file's length at the batch's rate
 		if (resample && (atRate = smst_batch_resampled_length(batch, s, n)) < 0) { std::fprintf(stderr, "%s: %s\n", files[2*s].c_str(), smst_last_error()); return 1; }
-		outLen[s] = int(std::round(atRate*time));
+		outLen[s] = outResample ? int(std::round(n*time*deliveryRate[s]/double(inputs[s].sampleRate))) : int(std::round(atRate*time));
 		outIndex[s] = std::max(0, outLen[s] - interval);
 		const int outputPos = outIndex[s] + outLat;
 		const int inputPos = int(std::round(outputPos/time));
@@ -219,14 +244,16 @@ int main(int argc, char **argv) {
 		const size_t esz = size_t(bits/8);
 		const float scale = bits == 24 ? 8388608.0f : 32768.0f;
 		if (dither != SMST_DITHER_NONE) CHECK(smst_batch_set_pcm_dither(batch, -1, dither, ditherSeed));
-		if (loudness) CHECK(smst_batch_set_pcm_loudness(batch, -1, flagValue(argc, argv, "loudness", 0), protect ? ceiling : INFINITY, batchRate));
+		if (loudness && outResample) { for (int s = 0; s < S; ++s) CHECK(smst_batch_set_pcm_loudness(batch, s, flagValue(argc, argv, "loudness", 0), protect ? ceiling : INFINITY, deliveryRate[s])); }
+		else if (loudness) CHECK(smst_batch_set_pcm_loudness(batch, -1, flagValue(argc, argv, "loudness", 0), protect ? ceiling : INFINITY, batchRate));
 		else if (levelled) CHECK(smst_batch_set_pcm_level(batch, -1, protect ? SMST_LEVEL_PROTECT : normalize ? SMST_LEVEL_NORMALISE : SMST_LEVEL_FIXED, gain, ceiling));
 		if (truePeak) CHECK(smst_batch_set_pcm_true_peak(batch, -1, 1));
 		if (limit) {
 			CHECK(smst_batch_set_pcm_limiter_lookahead(batch, int(std::lround(limitLookaheadMs*1e-3*batchRate))));
 			CHECK(smst_batch_set_pcm_limiter(batch, -1, 1));
 		}
-		if (loudnessRange) CHECK(smst_batch_set_pcm_loudness_range(batch, -1, 1, batchRate));
+		if (loudnessRange && outResample) { for (int s = 0; s < S; ++s) CHECK(smst_batch_set_pcm_loudness_range(batch, s, 1, deliveryRate[s])); }
+		else if (loudnessRange) CHECK(smst_batch_set_pcm_loudness_range(batch, -1, 1, batchRate));
 		if (capShortTerm || capMomentary) CHECK(smst_batch_set_pcm_loudness_caps(batch, -1, flagValue(argc, argv, "max-momentary", INFINITY), flagValue(argc, argv, "max-short-term", INFINITY)));
 		// `count` samples of file s from sample `first` on as frames at `frames`; false: one of them is no value of the format
 		auto toFrames = [&](int s, int first, int count, unsigned char *frames) {
@@ -293,7 +320,7 @@ int main(int argc, char **argv) {
 			for (int s = 0; s < S; ++s) std::printf("range: %s momentary-max=%.4f short-term-max=%.4f lra=%.4f\n", files[2*s + 1].c_str(), momentary[s], shortTerm[s], range[s]);
 		}
 		for (int s = 0; s < S; ++s) {
-			if (!writeWavFrames(files[2*s + 1], resample ? unsigned(rate) : inputs[s].sampleRate, inputs[s].channels, bits, outFrames.data() + (size_t)s*maxOut*C*esz, size_t(outLen[s]), error, format == SMST_PCM_F32)) {
+			if (!writeWavFrames(files[2*s + 1], resample ? unsigned(deliveryRate[s]) : inputs[s].sampleRate, inputs[s].channels, bits, outFrames.data() + (size_t)s*maxOut*C*esz, size_t(outLen[s]), error, format == SMST_PCM_F32)) {
 				std::fprintf(stderr, "%s\n", error.c_str());
 				return 1;
 			}
