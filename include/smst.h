@@ -828,8 +828,8 @@ int smst_debug_clip_loudness_range(int device, int streams, int channels, const 
  * and smst_batch_process_pcm, _seek_pcm and _output_seek_pcm return SMST_ERR_INVALID, before anything runs, if a stream that takes part has a
  * ratio other than 1/1: skipping the stage silently would be a lie.  smst_batch_flush_pcm has no input and is unaffected.  The too-short and
  * left-out streams of a call stay as they are.
- * Out of scope: resampling the output in the streaming calls ("Output resample" below is the whole-clip form); resampling in the planar calls (the streaming frame calls have a setting of their own: "Stream
- * resample" below); irrational or time-varying ratios; a quality setting; a fused PCM-to-resampled kernel without the raw image.
+ * Out of scope: resampling in the planar calls (the streaming frame calls have a setting of their own: "Stream resample" below; resampling
+ * the output: "Output resample" below is the whole-clip form, "Stream output resample" the streaming one); irrational or time-varying ratios; a quality setting; a fused PCM-to-resampled kernel without the raw image.
  * SMST_ERR_INVALID with a message that names the limit: a term outside [1, SMST_RESAMPLE_MAX_TERM]; a ratio beyond 4.5 either way; a ninth
  * distinct ratio; a stream index out of range; a null batch; in a call, an Nr that does not fit an int. */
 #define SMST_RESAMPLE_MAX_TERM 640
@@ -863,7 +863,7 @@ int smst_debug_clip_resample(int device, int streams, int channels, const int *c
  *
  * Ratio.  Per stream, reduced by the library, with the limits of "Resample": 1 <= L, M <= SMST_RESAMPLE_MAX_TERM, at most 4.5 either way;
  * 1/1 turns the stage off.  The tables are the batch's existing ratio tables -- the same formula, the same float32 table -- and the
- * SMST_RESAMPLE_MAX_RATIOS slots are shared with the two input settings: a slot is live while any of the three settings of any stream
+ * SMST_RESAMPLE_MAX_RATIOS slots are shared with the other resample settings: a slot is live while any of the four settings of any stream
  * uses it.  A setter call with a ratio the batch already has allocates nothing; tables are never uploaded in a call.
  *
  * Lengths.  outSamples[s] stays what the caller receives: Nd delivered frames at the delivery rate.  The engine renders
@@ -897,9 +897,9 @@ int smst_debug_clip_resample(int device, int streams, int channels, const int *c
  * segment.  Streams at 1/1 keep their two segments, and their bytes, in the same call.  The call's table of rendered segments and entries
  * exists twice, is allocated by the first such call and counted in smst_batch_workspace_bytes; a steady-state call allocates nothing and
  * adds no host synchronisation.
- * Out of scope: the streaming calls (a carried line behind the engine, in front of the stream limiter and meter); the planar calls;
+ * Out of scope: the planar calls (the streaming frame calls have a setting of their own: "Stream output resample" below);
  * irrational or time-varying ratios; a quality setting.
- * SMST_ERR_INVALID with a message that names the limit: the limits of "Resample", the ninth distinct ratio across the three settings
+ * SMST_ERR_INVALID with a message that names the limit: the limits of "Resample", the ninth distinct ratio across the four settings
  * included; a stream index out of range; a null batch; in a call, an E that does not fit an int. */
 /* stream = -1: every stream.  1/1 turns the stage off.  The first call with a ratio the batch does not have builds that ratio's table and
  * puts it into device memory: tables are never uploaded in a call */
@@ -945,7 +945,7 @@ int smst_debug_clip_resample_out(int device, int streams, int channels, const in
  *   in a call keeps its line.
  *   Mixing.  A stream without the setting gets, in the same call, the bytes it gets in a batch without any.
  *   Ratio tables.  The setting shares the batch's ratio tables and its SMST_RESAMPLE_MAX_RATIOS slots with the whole-clip setting: a slot is
- *   live while either setting of any stream uses it.
+ *   live while any of the four resample settings of any stream uses it.
  *
  * How.  In a call where a stream of the batch has the setting, the frame conversion runs once per destination that has frames -- the plain
  * streams into the engine's input image as ever, the others into a raw planar image -- and one kernel (csrc/smst_stream_resample.h;
@@ -954,7 +954,7 @@ int smst_debug_clip_resample_out(int device, int streams, int channels, const in
  * line.  The lines exist twice, a call reads one set and writes the other, and everything is ordered by the batch's stream.  Lines and call
  * tables live in device memory, allocated by the first setter call with a ratio other than 1/1, never in a call, and counted in
  * smst_batch_workspace_bytes; the raw image grows with the first call that needs it; a steady-state call allocates nothing.
- * Out of scope: resampling the output in the streaming calls; the planar calls; smst_batch_output_seek_pcm; stretch_cli (a whole-file tool, which has --rate);
+ * Out of scope: the planar calls (resampling the output in the streaming calls: "Stream output resample" below); smst_batch_output_seek_pcm; stretch_cli (a whole-file tool, which has --rate);
  * time-varying ratios.
  * SMST_ERR_INVALID with a message, before anything runs: the limits of "Resample"; a stream index out of range; a null batch;
  * smst_batch_output_seek_pcm and smst_batch_exact_pcm with a participating stream that has the setting (smst_batch_exact_pcm has
@@ -980,6 +980,83 @@ long long smst_batch_pcm_stream_resample_need(const smst_batch *b, int stream, l
 int smst_debug_pcm_stream_resample(int device, int streams, int channels, int calls, const int *counts, const int *ratios, const long long *fed0,
                                    const float *image, long long imageStreamStride, long long imageChannelStride,
                                    float *out, long long outStreamStride, long long outChannelStride, int maxFrames, long long *made);
+/* ---- Stream output resample (EXTENSION; opt-in: a batch that never calls smst_batch_set_pcm_stream_out_resample launches the kernels, writes the bytes and counts the launches it did before) ----
+ * "Output resample" delivers whole clips at their own rate; "Stream resample" takes a live stream at its own rate.  A live stream could not
+ * be DELIVERED at its own rate: a 44.1 kHz device fed from a 48 kHz batch copied every quantum back and resampled it on the CPU, behind the
+ * stream limiter, the stream meter, the gain, the dither and the overs counter, which then described frames that were not the ones
+ * delivered.  The converter is a non-recursive FIR, so it has an exact streaming form behind the engine as it has in front of it.
+ *
+ * It is a per-stream setting of its own beside the whole-clip output ratio (smst_batch_set_pcm_out_resample), which stays refused in the
+ * streaming calls.  The ratio L/M = up/down is the DELIVERY rate over the batch's rate, reduced by the library, with the limits, the table,
+ * the shape (H, T = 2H) and the arithmetic of "Resample"; it is one more user of the batch's SMST_RESAMPLE_MAX_RATIOS shared table slots: a
+ * slot is live while any of the four settings of any stream uses it.  The setting makes smst_batch_process_pcm and smst_batch_flush_pcm
+ * deliver the stream's frames at the delivery rate.
+ *
+ * Definition.  Let r(0), r(1), ... be the frames the engine has emitted for the stream through smst_batch_process_pcm / _flush_pcm since its
+ * line was last cleared, and `delivered` the number of frames the caller has received since then, a 64-bit host counter.  All integers
+ * below are 64-bit.
+ *   Lengths.  outSamples[s] stays what the caller receives: Nd frames at the delivery rate.  The engine renders
+ *   E = ceil((delivered + Nd)*M/L) - ceil(delivered*M/L) frames; E may be 0 and must fit an int.  E depends on nothing but `delivered` and
+ *   Nd: it has no burst and no term in H.  Towards the engine the call behaves exactly as if the caller had asked for E frames: the
+ *   engine's rate is fed/E, and a call with E = 0 is what smst_batch_process with a zero output count is.  In a flush the engine's flush
+ *   gets E; its `rates` stay relative to frames at the batch's rate.  Nothing in the call's interface is sized by E
+ *   (smst_batch_pcm_stream_out_resample_render reports it).
+ *   Latency.  Dl = ceil(H*L/M) delivered frames (smst_batch_pcm_stream_out_resample_latency): 64 at 2/1, 32 at 1/2, 48 at 3/2, 32 at 2/3,
+ *   35 at 160/147, 33 at 147/160, 33 at 147/640, 140 at 640/147.  Delivered frame n < Dl is +0.0.  Delivered frame n >= Dl is frame
+ *   m = n - Dl of "Resample" applied to r: i = (m*M)/L, p = (m*M) mod L, and the value is
+ *   float32(sum_j double(c[p][j])*double(r(i + j - (H - 1)))), j ascending from 0.0, r of a negative index = +0.0.  Because Dl*M/L >= H,
+ *   every such frame has i + H <= ceil((n + 1)*M/L) - 1: the right edge of what has been rendered never enters, and the result does not
+ *   depend on how the stream is cut into calls (csrc/smst_stream_resample_out.h has the proof).
+ *   Known answers.  147/160, calls of 128 delivered frames: E = 140, 139, 139, 140.  160/147, calls of 480: E = 441 every call.  3/2,
+ *   calls of 16: E = 11, 11, 10.  3/2, mono, r(2) = 1 and 0 elsewhere, calls of 20, 28, 8: E = 14, 18, 6; the delivered frames 0 ... 47 are
+ *   +0.0 and the frames 48 ... 55 are "Resample"'s known answer bca067e3 be4717b5 3ed8327b 3f7ae0ea 3ed8327b be4717b5 bca067e3 3dddb185.
+ *   2/3, r(3) = 1: the delivered frames 32 ... 36 are bc55dff0 3c594cd8 3f2740ad 3c594cd8 bc55dff0.
+ *   Ending a stream.  The caller asks its flush for Dl frames more: the engine's flush emits zeros beyond its tail, so the last frames are
+ *   the clip form's.
+ *   The line.  Per stream and channel, the last rendered frames that a later call can still reach.  The next call's first frame reaches
+ *   back to ((delivered - Dl)*M)/L - (H - 1), at most T + ceil(M/L) frames below ceil(delivered*M/L): 293 at 2/9.  It is cleared
+ *   (frames <- +0.0, delivered = 0) by the setter for the stream and by smst_batch_reset.  It is NOT cleared by smst_batch_seek_pcm or
+ *   smst_batch_output_seek_pcm -- they emit nothing, and the output timeline goes on -- nor by a flush.  A stream with no frame in a call
+ *   keeps its line.
+ *   Everything behind the converter runs on the delivered frames: the stream limiter (whose latency adds to Dl), the stream meter (its
+ *   v(n) are the delivered frames, the Dl zeros included; the caller gives it the DELIVERY rate), gain, dither (whose frame index is the
+ *   delivered frame's), conversion, overs and peaks.
+ *   The setting may be combined with smst_batch_set_pcm_stream_resample on the same stream: 44.1 kHz in, a 48 kHz batch, 44.1 kHz out.
+ *   Mixing.  A stream without the setting gets, in the same call, the bytes it gets in a batch without any.
+ *
+ * How.  The engine renders every stream's frames into its output image as ever -- E of them for a stream with the setting; the image's rows
+ * hold max(E, Nd) frames.  One kernel (csrc/smst_stream_resample_out.h) forms the Nd delivered frames of each such stream into
+ * a second image, staging every tile's span from the stream's line and the frames just rendered, by the clip converter's own tap sum (one
+ * device function for all four converters); the workgroup behind a stream's last tile writes its new line.  A small second kernel copies
+ * the delivered frames back over those streams' rows of the engine's image, and the stream limiter, the stream meter and the conversion
+ * read that one image as they did; plain streams are never touched.  The lines exist twice, a call reads one set and writes the other, and
+ * everything is ordered by the batch's stream.  Lines and call tables live in device memory, allocated by the first setter call with a ratio
+ * other than 1/1, never in a call, and counted in smst_batch_workspace_bytes; the second image grows with the first call that needs it; a
+ * steady-state call allocates nothing, and no host synchronisation and no device readback is added.
+ * Out of scope: the planar calls (they neither serve nor refuse the setting, as with "Stream resample"); stretch_cli (a whole-file tool,
+ * which has --out-rate); time-varying or irrational ratios; a quality setting.
+ * SMST_ERR_INVALID with a message, before anything runs: the limits of "Resample", the ninth distinct ratio across all four settings
+ * included; a stream index out of range; a null batch; an E that does not fit an int; smst_batch_exact_pcm with a participating stream that
+ * has the setting (it has smst_batch_set_pcm_out_resample). */
+/* stream = -1: every stream.  1/1 turns the setting off.  Clears the line of the stream(s).  The first call with another ratio allocates the
+ * lines and the call tables, and builds the ratio's table where the batch does not have it yet */
+int smst_batch_set_pcm_stream_out_resample(smst_batch *b, int stream, int up, int down);
+/* the stream's reduced ratio (1/1: none); either pointer may be null */
+int smst_batch_pcm_stream_out_resample(const smst_batch *b, int stream, int *up, int *down);
+/* Dl of the stream's ratio, the delivered frames by which its output is late; 0 without the setting */
+int smst_batch_pcm_stream_out_resample_latency(const smst_batch *b, int stream, int *frames);
+/* E of the stream's next call if it delivers outSamples frames (outSamples itself without the setting), or a negative code.  fresh != 0: as
+ * after a clear -- what the call behind a reset gives */
+long long smst_batch_pcm_stream_out_resample_render(const smst_batch *b, int stream, long long outSamples, int fresh);
+/* test hook: `calls` launches of the stream-output-resample kernel in sequence, with the carried lines, planar fp32 to planar fp32 (host
+ * pointers, strides in floats, staged whole as far behind a 16-byte boundary as the caller's).  counts: [calls][streams] Nd, negative = the
+ * stream takes no part in that call; ratios: [streams][2] up, down (1/1: the stream's rows of `out` are left alone); delivered0: [streams]
+ * or null -- the line starts as zeros at that position (delivered = delivered0); image: each stream's rendered frames in order from column
+ * 0 of its rows; out: each stream's delivered frames, in order from column 0, at most maxFrames of them; rendered: [streams], the frames
+ * of `image` consumed (may be null) */
+int smst_debug_pcm_stream_resample_out(int device, int streams, int channels, int calls, const int *counts, const int *ratios, const long long *delivered0,
+                                       const float *image, long long imageStreamStride, long long imageChannelStride,
+                                       float *out, long long outStreamStride, long long outChannelStride, int maxFrames, long long *rendered);
 /* ---- Stream meter (EXTENSION; opt-in: a batch that never calls smst_batch_set_pcm_stream_meter launches the kernels, writes the bytes and counts the launches it did before) ----
  * The meters above ("Loudness", "True peak", "Loudness range") know a whole clip.  A live bus could be stretched, resampled, levelled and
  * limited on the device, but to learn its loudness the caller had to copy the output back and meter it on the host.  Each meter has an exact

@@ -189,6 +189,11 @@ _SIGNATURES = {
     "smst_batch_take_pcm_stream_meter": (C.c_int, [C.c_void_p, _dp, _ip, _ip, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _ip, _ip, _fp, _fp]),
     "smst_debug_pcm_stream_meter": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _ip, _ip, C.c_int, C.c_void_p, _ll, _ll, _dp, _fp, _ip, C.c_int,
                                               _dp, _ip, _ip, _dp, _dp, _dp, _dp, _ip, _ip, _fp, _fp, C.POINTER(_ll), _dp, _dp, C.c_int]),
+    "smst_batch_set_pcm_stream_out_resample": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
+    "smst_batch_pcm_stream_out_resample": (C.c_int, [C.c_void_p, C.c_int, _ip, _ip]),
+    "smst_batch_pcm_stream_out_resample_latency": (C.c_int, [C.c_void_p, C.c_int, _ip]),
+    "smst_batch_pcm_stream_out_resample_render": (_ll, [C.c_void_p, C.c_int, _ll, C.c_int]),
+    "smst_debug_pcm_stream_resample_out": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _ip, _ip, C.POINTER(_ll), C.c_void_p, _ll, _ll, C.c_void_p, _ll, _ll, C.c_int, C.POINTER(_ll)]),
     "smst_batch_synchronize": (C.c_int, [C.c_void_p]),
     "smst_batch_hip_stream": (C.c_void_p, [C.c_void_p]),
     "smst_batch_enable_profiling": (C.c_int, [C.c_void_p, C.c_int]),
@@ -514,6 +519,22 @@ def debug_pcm_stream_resample(counts, ratios, channels, image, image_ss, image_c
                                                    None if start is None else start.ctypes.data_as(C.POINTER(_ll)), C.c_void_p(image.ctypes.data), image_ss, image_cs,
                                                    C.c_void_p(out.ctypes.data), out_ss, out_cs, int(max_frames), made.ctypes.data_as(C.POINTER(_ll))))
     return made
+
+
+def debug_pcm_stream_resample_out(counts, ratios, channels, image, image_ss, image_cs, out, out_ss, out_cs, max_frames, delivered0=None, device=0, lib=None):
+    """smst_debug_pcm_stream_resample_out on numpy buffers (planar float32, 1-d views whose first element is the first stream's first row;
+    strides in floats).  counts: int [calls, S] delivered frames, negative = no part; ratios: [S] of (up, down); delivered0: [S] int64 or
+    None.  ``out`` is written in place -> rendered, int64 [S]: the frames of ``image`` consumed per stream"""
+    lib = lib or load_library()
+    n = np.ascontiguousarray(np.asarray(counts, np.int32))
+    calls, S = n.shape
+    r = np.ascontiguousarray(np.asarray(ratios, np.int32).reshape(S, 2))
+    start = None if delivered0 is None else np.ascontiguousarray(np.asarray(delivered0, np.int64).reshape(S))
+    rendered = np.zeros(S, np.int64)
+    _check(lib, lib.smst_debug_pcm_stream_resample_out(device, S, channels, calls, n.ctypes.data_as(_ip), r.ctypes.data_as(_ip),
+                                                       None if start is None else start.ctypes.data_as(C.POINTER(_ll)), C.c_void_p(image.ctypes.data), image_ss, image_cs,
+                                                       C.c_void_p(out.ctypes.data), out_ss, out_cs, int(max_frames), rendered.ctypes.data_as(C.POINTER(_ll))))
+    return rendered
 
 
 def debug_clip_resample(counts, ratios, channels, image, image_ss, image_cs, segments, out, out_ss, out_cs, device=0, lib=None):
@@ -1117,6 +1138,32 @@ class StretchBatch:
         if n < 0:
             _check(self.lib, n)
         return n
+
+    def set_pcm_stream_out_resample(self, up, down, stream=-1):
+        """Resample behind processFrames / flushFrames (include/smst.h, "Stream output resample"): the stream's frames are delivered at
+        up/down of the batch's rate, resampled on the device in front of the stream limiter, the stream meter, gain and dither, with the
+        last rendered frames carried from call to call; they come ceil(H*up/down) delivered frames late.  1/1 turns it off; stream = -1:
+        every stream.  Clears the stream's line."""
+        _check(self.lib, self.lib.smst_batch_set_pcm_stream_out_resample(self.h, int(stream), int(up), int(down)))
+
+    def pcm_stream_out_resample(self, stream):
+        """-> (up, down), the stream's reduced streaming output ratio; (1, 1): none"""
+        up, down = C.c_int(0), C.c_int(0)
+        _check(self.lib, self.lib.smst_batch_pcm_stream_out_resample(self.h, int(stream), C.byref(up), C.byref(down)))
+        return up.value, down.value
+
+    def stream_out_resample_latency(self, stream):
+        """-> Dl, the delivered frames by which the stream's output is late (0 without the setting)"""
+        frames = C.c_int(0)
+        _check(self.lib, self.lib.smst_batch_pcm_stream_out_resample_latency(self.h, int(stream), C.byref(frames)))
+        return frames.value
+
+    def stream_out_resample_render(self, stream, out_samples, fresh=False):
+        """-> E, the frames the engine renders in the stream's next call if it delivers out_samples frames (fresh: as after a clear)"""
+        E = int(self.lib.smst_batch_pcm_stream_out_resample_render(self.h, int(stream), int(out_samples), 1 if fresh else 0))
+        if E < 0:
+            _check(self.lib, E)
+        return E
 
     def pcm_resample(self, stream):
         """-> (up, down), the stream's reduced ratio; (1, 1): not resampled"""

@@ -564,6 +564,50 @@ struct PcmStreamResampleState {
 	}
 };
 
+// The output side of a batch's frame-format streaming calls where a stream has the setting of include/smst.h, "Stream output resample": per
+// stream the 64-bit count of frames delivered since the clear, which set of its two carried lines the next call reads and whether the line
+// counts as cleared; the lines (both sets in one buffer), allocated by the first setter call with a ratio other than 1/1, and the image of
+// the delivered frames, which grows on demand as the images do.  The ratios, their tables and their slots are the engine's
+// (Batch::setResample, kResampleStreamOut).  The owner has selected the device wherever HIP is called.
+struct PcmStreamResampleOutState {
+	struct Stream { long long delivered = 0; unsigned char set = 0, fresh = 1; };
+	std::vector<Stream> stream;
+	std::vector<int> render; // the frames the engine renders for each stream in the newest call: its E, or the call's own count
+	Buffer<float, false> dLines;
+	DeviceFloats dDelivered;
+	size_t tableBytes = 0;   // of the call tables' device twins (both sets)
+	void create(int S) { stream.assign((size_t)S, Stream()); render.assign((size_t)S, 0); }
+	size_t workspaceBytes() const { return (dLines.cap + dDelivered.cap)*sizeof(float) + tableBytes; }
+	// frames <- +0.0, delivered = 0 for the stream (-1: every one): the next call reads zeros in the place of the line
+	void clear(int stream_) {
+		for (size_t s = stream_ < 0 ? 0 : size_t(stream_); s < (stream_ < 0 ? stream.size() : size_t(stream_) + 1); ++s) { stream[s].delivered = 0; stream[s].fresh = 1; }
+	}
+	static bool any(const Batch &e) {
+		for (int s = 0; s < e.streams(); ++s) if (e.streamOutResampled(s)) return true;
+		return false;
+	}
+	// E of a call that delivers Nd frames to the stream (fresh: as after a clear); Error where it does not fit an int
+	// (2*M <= 9*L: E < 4.5*Nd + 1, and delivered*M stays below 2^62)
+	long long renderOf(const Batch &e, int s, long long Nd, bool fresh) const {
+		if (!e.streamOutResampled(s)) return Nd;
+		const smst::ResampleShape &g = e.streamOutResampleShape(s);
+		const long long delivered = fresh ? 0 : stream[s].delivered;
+		const std::string what = "stream out resample: stream " + std::to_string(s) + ": " + std::to_string(Nd) + " delivered frames";
+		if (Nd > (1LL << 40)) throw smst::Error(what + " need more than 2147483647 rendered frames (E must fit an int)");
+		if (delivered > (1LL << 52) - Nd) throw smst::Error(what + " take the stream beyond 2^52 delivered frames (smst_batch_set_pcm_stream_out_resample clears the count)");
+		const long long E = smst::streamResampleOutDue(delivered + Nd, g.L, g.M) - smst::streamResampleOutDue(delivered, g.L, g.M);
+		if (E > 0x7fffffffLL) throw smst::Error(what + " need " + std::to_string(E) + " rendered frames, more than 2147483647 (E must fit an int)");
+		return E;
+	}
+	// render[s] of a call whose streams are delivered n[s] frames (a negative count: no part, the count itself) -> whether a stream of the
+	// batch has the setting.  Every refusal of the output side, before anything has changed
+	bool prepare(const Batch &e, const int *n) {
+		if (!any(e)) return false;
+		for (int s = 0; s < e.streams(); ++s) render[s] = n[s] < 0 ? n[s] : int(renderOf(e, s, n[s], stream[s].fresh != 0));
+		return true;
+	}
+};
+
 struct smst_batch {
 	std::unique_ptr<Batch> engine;
 	// host staging (SMST_MEM_HOST)
@@ -582,11 +626,15 @@ struct smst_batch {
 		smst::PcmOutCall out;
 		Buffer<unsigned char, true> resHost; // the input side's table of a call with a stream-resampled stream (smst::StreamResampleTableLayout),
 		Buffer<unsigned char, false> resDev; // allocated -- both sets -- by the first setter call with a ratio other than 1/1
+		Buffer<unsigned char, true> outResHost; // the output side's table of a call with a stream-out-resampled stream (smst::StreamResampleOutTableLayout),
+		Buffer<unsigned char, false> outResDev; // allocated -- both sets -- by the first setter call with a ratio other than 1/1
 		int mostLimited = 0; // the largest count of a stream that the call's output limits ("Stream limiter"); 0: the call launches what it did without the setting
+		int mostDelivered = 0, deliveredLen = 1, outSpanPitch = 4; // "Stream output resample": the largest Nd of a stream with the setting (0: as mostLimited), the row length of the delivered image, what sizes the LDS
 	};
 	smst::TwoSets<PcmTable> pcmTables; // (smst_staging.h)
 	PcmOutState pcmOut;
 	PcmStreamResampleState pcmIn;
+	PcmStreamResampleOutState pcmOutRes;
 	~smst_batch() { if (engine) hipSetDevice(engine->device()); } // (the buffers above go behind it, the engine last)
 };
 
@@ -692,6 +740,7 @@ int smst_batch_create_ex(smst_batch **out, int streams, int channels, int block,
 	b->engine.reset(new Batch(streams, channels, block, interval, split != 0, device, seed, (flags & SMST_FLAG_HALF_STATE) != 0));
 	b->pcmOut.create(streams, channels);
 	b->pcmIn.create(streams);
+	b->pcmOutRes.create(streams);
 	*out = b.release();
 	return SMST_OK;
 	SMST_CATCH
@@ -722,7 +771,7 @@ BATCH_Q(smst_batch_output_latency, b->engine->outputLatency())
 BATCH_Q(smst_batch_seek_length, b->engine->seekLength())
 BATCH_Q(smst_batch_half_state, b->engine->halfPrecisionState() ? 1 : 0)
 int smst_batch_output_seek_length(const smst_batch *b, float rate) { if (!b || !b->engine) return fail("null batch"); return b->engine->outputSeekLength(rate); }
-long long smst_batch_workspace_bytes(const smst_batch *b) { if (!b || !b->engine) return fail("null batch"); return (long long)(b->engine->workspaceBytes() + b->pcmOut.workspaceBytes() + b->pcmIn.workspaceBytes()); }
+long long smst_batch_workspace_bytes(const smst_batch *b) { if (!b || !b->engine) return fail("null batch"); return (long long)(b->engine->workspaceBytes() + b->pcmOut.workspaceBytes() + b->pcmIn.workspaceBytes() + b->pcmOutRes.workspaceBytes()); }
 
 #define BATCH_CALL(...) if (!b || !b->engine) return fail("null batch"); SMST_TRY __VA_ARGS__; return SMST_OK; SMST_CATCH
 
@@ -731,6 +780,7 @@ int smst_batch_reset(smst_batch *b) {
 		b->engine->reset();
 		b->pcmOut.clearStreamLimitLines(*b->engine, -1); // (the stream limiter's lines begin again, in stream order behind the calls in flight)
 		b->pcmIn.clear(-1);                              // (... and the stream resampler's)
+		b->pcmOutRes.clear(-1);                          // (... and the stream output resampler's)
 		b->pcmOut.clearStreamMeter(b->engine->device(), b->engine->stream(), -1);     // (... and the stream meter's)
 	})
 }
@@ -927,6 +977,7 @@ static smst_batch::PcmTable &beginPcmCall(smst_batch *b) {
 	}
 	c.out = smst::PcmOutCall();
 	c.mostLimited = 0;
+	c.mostDelivered = 0;
 	return c;
 }
 // The output side's sections of the call's table, from the batch's state, and their upload -- with the S output counts in front of them where
@@ -1063,10 +1114,45 @@ static int pcmStageIn(smst_batch *b, smst_batch::PcmTable &c, const void *in, lo
 	return maxLen;
 }
 // the output side's buffers, before the engine is called (a growth frees, which synchronises the device): returns maxLen of b->dOut [S][C][maxLen]
-static int pcmPrepareOut(smst_batch *b, smst_batch::PcmTable &c, const int *n, int format, int memory) {
+// A streaming call in which a stream of the batch has the stream-output-resample setting (include/smst.h, "Stream output resample"): n[s]
+// counts delivered frames, render[s] (PcmStreamResampleOutState::prepare) is what the engine renders.  The call's entries -- uploaded in one
+// copy --, the image of the delivered frames, and the streams' counters, which move on here.  Returns the row length b->dOut needs: it holds
+// a stream's E rendered frames first and its Nd delivered frames then
+static int pcmPrepareOutResampled(smst_batch *b, smst_batch::PcmTable &c, const int *n, const int *render, int len) {
+	Batch &e = *b->engine;
+	PcmStreamResampleOutState &r = b->pcmOutRes;
+	const int S = e.streams(), C = e.channels();
+	const smst::StreamResampleOutTableLayout at(S);
+	int most = 0;
+	for (int s = 0; s < S; ++s) {
+		len = std::max(len, render[s]);
+		if (e.streamOutResampled(s)) most = std::max(most, n[s]);
+	}
+	const int tileFrames = smst::streamResampleTileFrames(most);
+	c.mostDelivered = most; c.deliveredLen = std::max(most, 1); c.outSpanPitch = 4;
+	if (most > 0) ensureStage(b, r.dDelivered, (size_t)S*C*c.deliveredLen);
+	hipSetDevice(e.device());
+	for (int s = 0; s < S; ++s) {
+		smst::StreamResampleOutEntry entry{nullptr, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+		if (e.streamOutResampled(s)) {
+			PcmStreamResampleOutState::Stream &st = r.stream[s];
+			const smst::ResampleShape &g = e.streamOutResampleShape(s);
+			entry = smst::StreamResampleOutEntry{e.streamOutResampleTaps(s), st.delivered, smst::streamResampleOutDue(st.delivered, g.L, g.M), 0, 0, std::max(n[s], 0), std::max(render[s], 0),
+			                                     smst::streamResampleOutLatency(g.L, g.M, g.H), g.L, g.M, g.H, g.T, g.pitch, st.set, st.fresh};
+			c.outSpanPitch = std::max(c.outSpanPitch, smst::resampleSpanPitchOf(g.L, g.M, g.T, tileFrames));
+			if (n[s] > 0) { st.delivered += n[s]; st.set ^= 1; st.fresh = 0; } // (a stream with no frame keeps its line)
+		}
+		at.entries(c.outResHost)[s] = entry;
+	}
+	if (hipMemcpyAsync(c.outResDev, c.outResHost, at.bytes(), hipMemcpyHostToDevice, e.stream()) != hipSuccess) throw smst::Error("hipMemcpyAsync (H2D) failed", true);
+	return len;
+}
+// render (null: no stream of the batch has the stream-output-resample setting): the frames the engine renders for each stream
+static int pcmPrepareOut(smst_batch *b, smst_batch::PcmTable &c, const int *n, int format, int memory, const int *render = nullptr) {
 	Batch &e = *b->engine;
 	const int S = e.streams(), C = e.channels();
-	const Counts k = countsOf(n, S, smst::PcmTableLayout(S).outCounts(c.host));
+	Counts k = countsOf(n, S, smst::PcmTableLayout(S).outCounts(c.host));
+	if (render) k.len = pcmPrepareOutResampled(b, c, smst::PcmTableLayout(S).outCounts(c.host), render, k.len);
 	ensureStage(b, b->dOut, (size_t)S*C*k.len);
 	if (memory == SMST_MEM_HOST && k.most > 0) ensurePcmBytes(b, b->hPcmOut, b->dPcmOut, (size_t)S*pcmRowElems(k.most, C)*pcmElemBytes(format));
 	hipSetDevice(e.device());
@@ -1085,6 +1171,15 @@ static void pcmStageOut(smst_batch *b, smst_batch::PcmTable &c, void *out, long 
 	const int *n = at.outCounts(c.host);
 	const int most = countsOf(n, S).most;
 	hipSetDevice(e.device());
+	// a call that delivers frames to a stream with the stream-output-resample setting: those streams' delivered frames, formed from their lines
+	// and the frames the engine has just rendered, take the place of the rendered ones in b->dOut, in front of every stage below
+	if (c.mostDelivered > 0) {
+		PcmStreamResampleOutState &r = b->pcmOutRes;
+		const smst::StreamResampleOutEntry *entries = smst::StreamResampleOutTableLayout(S).entries(c.outResDev);
+		smst::launchPcmStreamResampleOut(b->dOut, (long long)C*maxLen, maxLen, r.dDelivered, (long long)C*c.deliveredLen, c.deliveredLen, r.dLines, (long long)(r.dLines.cap/2), entries, S, C,
+		                                 c.mostDelivered, c.outSpanPitch, e.stream());
+		smst::launchPcmStreamResampleOutCopy(r.dDelivered, (long long)C*c.deliveredLen, c.deliveredLen, b->dOut, (long long)C*maxLen, maxLen, entries, S, C, c.mostDelivered, e.stream());
+	}
 	// a call that limits a stream: the two passes and the limited conversion (a kernel of its own) in the place of the levelled one
 	auto convert = [&](void *raw, long long rawSS, long long rawFS) {
 		if (c.mostLimited > 0) {
@@ -1346,11 +1441,12 @@ int smst_batch_process_pcm(smst_batch *b, const void *in, long long iss, long lo
 		refuseWholeClipLevel(b, nullptr);
 		refuseResampled(e, nullptr, "smst_batch_process_pcm");
 		refuseOutResampled(e, nullptr, "smst_batch_process_pcm");
+		const int *render = b->pcmOutRes.prepare(e, outSamples) ? b->pcmOutRes.render.data() : nullptr; // (a stream with the stream-output-resample setting: its E)
 		smst_batch::PcmTable &c = beginPcmCall(b);
 		const int *fed = inSamples; // (a stream with the stream-resample setting: its k)
 		const int maxIn = pcmStageIn(b, c, in, iss, ifs, inSamples, format, memory, &fed);
-		const int maxOut = pcmPrepareOut(b, c, outSamples, format, memory);
-		e.process(b->dIn, (long long)e.channels()*maxIn, maxIn, fed, b->dOut, (long long)e.channels()*maxOut, maxOut, outSamples);
+		const int maxOut = pcmPrepareOut(b, c, outSamples, format, memory, render);
+		e.process(b->dIn, (long long)e.channels()*maxIn, maxIn, fed, b->dOut, (long long)e.channels()*maxOut, maxOut, render ? render : outSamples);
 		pcmStageOut(b, c, out, oss, ofs, maxOut, format, memory);
 		endPcmCall(b);
 	})
@@ -1377,9 +1473,10 @@ int smst_batch_flush_pcm(smst_batch *b, void *out, long long oss, long long ofs,
 		const FlushCounts f(outSamples, e.streams());
 		refuseWholeClipLevel(b, f.active.data());
 		refuseOutResampled(e, outSamples, "smst_batch_flush_pcm");
+		const int *render = b->pcmOutRes.prepare(e, f.counts.data()) ? b->pcmOutRes.render.data() : nullptr; // (a stream left out has no frame: E = 0, its line is kept)
 		smst_batch::PcmTable &c = beginPcmCall(b);
-		const int maxOut = pcmPrepareOut(b, c, f.counts.data(), format, memory);
-		e.flush(b->dOut, (long long)e.channels()*maxOut, maxOut, f.counts.data(), rates, f.mask());
+		const int maxOut = pcmPrepareOut(b, c, f.counts.data(), format, memory, render);
+		e.flush(b->dOut, (long long)e.channels()*maxOut, maxOut, render ? render : f.counts.data(), rates, f.mask());
 		pcmStageOut(b, c, out, oss, ofs, maxOut, format, memory);
 		endPcmCall(b);
 	})
@@ -1504,6 +1601,10 @@ int smst_batch_exact_pcm(smst_batch *b, const void *in, long long iss, long long
 				throw smst::Error("stream " + std::to_string(s) + " has the stream meter's setting (smst_batch_set_pcm_stream_meter), which acts in smst_batch_process_pcm and smst_batch_flush_pcm: "
 				                  "the whole-clip forms are smst_batch_set_pcm_loudness_range and smst_batch_set_pcm_true_peak");
 		refuseStreamResampled(e, outSamples, "smst_batch_exact_pcm");
+		for (int s = 0; s < e.streams(); ++s)
+			if (outSamples[s] >= 0 && e.streamOutResampled(s))
+				throw smst::Error("smst_batch_exact_pcm: stream " + std::to_string(s) + " has the stream-output-resample setting (smst_batch_set_pcm_stream_out_resample), which acts in "
+				                  "smst_batch_process_pcm and smst_batch_flush_pcm only: the whole-clip form is smst_batch_set_pcm_out_resample");
 		checkResampledLengths(e, inSamples, outSamples);
 		// a dithered call: the streams' modes and hashes ride in the _pcm calls' table (the frame index is the place in the clip: the counters
 		// are neither read nor moved); a levelled call: the level entries ride there too, and the loudness entries and the channel weights
@@ -1623,6 +1724,53 @@ long long smst_batch_pcm_stream_resample_need(const smst_batch *b, int stream, l
 	const PcmStreamResampleState::Stream &st = b->pcmIn.stream[stream];
 	const long long fed = fresh ? 0 : st.fed, made = fresh ? 0 : st.made;
 	return std::max(0LL, ((made + frames - 1)*g.M)/g.L + g.H + 1 - fed);
+	SMST_CATCH
+}
+// Stream output resample (include/smst.h): the ratios live in the engine beside the three others, whose tables and slots they share; the
+// lines, the counters and the call tables here.  Everything but the image of the delivered frames is allocated by the setter, never in a call
+int smst_batch_set_pcm_stream_out_resample(smst_batch *b, int stream, int up, int down) {
+	BATCH_CALL({
+		Batch &e = *b->engine;
+		e.setResample(stream, up, down, Batch::kResampleStreamOut); // (every refusal, before anything changes)
+		hipSetDevice(e.device());
+		if (PcmStreamResampleOutState::any(e) && !b->pcmOutRes.dLines) {
+			const size_t set = (size_t)e.streams()*e.channels()*smst::kStreamResampleOutLine;
+			++b->stagingAllocs;
+			b->pcmOutRes.dLines.allocate(2*set, "stream out resample lines");
+			if (hipMemsetAsync(b->pcmOutRes.dLines, 0, 2*set*sizeof(float), e.stream()) != hipSuccess) throw smst::Error("hipMemsetAsync (stream out resample lines) failed", true);
+			b->pcmTables.create();
+			const size_t bytes = smst::StreamResampleOutTableLayout(e.streams()).bytes();
+			for (smst_batch::PcmTable &t : b->pcmTables.sets) {
+				t.outResHost.allocate(bytes, "stream out resample table");
+				t.outResDev.allocate(bytes, "stream out resample table");
+			}
+			b->pcmOutRes.tableBytes = 2*bytes;
+		}
+		b->pcmOutRes.clear(stream);
+	})
+}
+int smst_batch_pcm_stream_out_resample(const smst_batch *b, int stream, int *up, int *down) {
+	BATCH_CALL({
+		int l = 1, m = 1;
+		b->engine->streamOutResampleOf(stream, l, m);
+		if (up) *up = l;
+		if (down) *down = m;
+	})
+}
+int smst_batch_pcm_stream_out_resample_latency(const smst_batch *b, int stream, int *frames) {
+	BATCH_CALL({
+		const Batch &e = *b->engine;
+		if (stream < 0 || stream >= e.streams()) throw smst::Error("stream index out of range");
+		if (frames) *frames = 0;
+		if (frames && e.streamOutResampled(stream)) { const smst::ResampleShape &g = e.streamOutResampleShape(stream); *frames = smst::streamResampleOutLatency(g.L, g.M, g.H); }
+	})
+}
+long long smst_batch_pcm_stream_out_resample_render(const smst_batch *b, int stream, long long outSamples, int fresh) {
+	if (!b || !b->engine) return fail("null batch");
+	SMST_TRY
+	if (stream < 0 || stream >= b->engine->streams()) throw smst::Error("stream index out of range");
+	if (outSamples < 0) throw smst::Error("stream out resample: negative sample count");
+	return b->pcmOutRes.renderOf(*b->engine, stream, outSamples, fresh != 0 || b->pcmOutRes.stream[stream].fresh);
 	SMST_CATCH
 }
 int smst_resample_ratio(double fromRate, double toRate, int *up, int *down) {
@@ -2412,6 +2560,81 @@ int smst_debug_pcm_stream_resample(int device, int streams, int channels, int ca
 	}
 	if (outBytes) hip(hipMemcpy(out, o0, outBytes, hipMemcpyDeviceToHost));
 	if (made) for (int s = 0; s < streams; ++s) made[s] = st[s].written;
+	return SMST_OK;
+	SMST_CATCH
+}
+// the stream-output-resample kernel alone, call after call: see include/smst.h
+int smst_debug_pcm_stream_resample_out(int device, int streams, int channels, int calls, const int *counts, const int *ratios, const long long *delivered0,
+                                       const float *image, long long imageSS, long long imageCS, float *out, long long outSS, long long outCS, int maxFrames, long long *rendered) {
+	SMST_TRY
+	if (streams < 1 || channels < 1 || channels > smst::kMaxChannels || calls < 0 || (calls > 0 && !counts) || !ratios || !image || !out || maxFrames < 0 || imageSS < 0 || imageCS < 0 || outSS < 0 || outCS < 0)
+		throw smst::Error("stream out resample: bad arguments");
+	auto hip = [&](hipError_t err) { if (err != hipSuccess) throw smst::Error(std::string("stream out resample: ") + hipGetErrorString(err), true); };
+	hip(hipSetDevice(device));
+	struct Stream { smst::ResampleShape g{0, 0, 0, 0, 0}; long long delivered = 0, at = 0, written = 0, endIn = 0; int Dl = 0, set = 0, fresh = 1; };
+	std::vector<Stream> st((size_t)streams);
+	std::vector<Buffer<float, false>> tables((size_t)streams); // (one per resampled stream: a hook's streams do not share them)
+	long long endIn = 0;
+	for (int s = 0; s < streams; ++s) {
+		int up = ratios[2*s], down = ratios[2*s + 1];
+		smst::resampleReduce(up, down);
+		if (up == 1 && down == 1) continue; // no setting: its rows of `out` are left alone
+		Stream &t = st[s];
+		t.g = smst::resampleShapeOf(up, down);
+		t.Dl = smst::streamResampleOutLatency(up, down, t.g.H);
+		if (delivered0) {
+			if (delivered0[s] < 0 || delivered0[s] > (1LL << 48)) throw smst::Error("stream out resample: a starting position is negative or above 2^48");
+			t.delivered = delivered0[s];
+		}
+		long long total = 0;
+		for (int k = 0; k < calls; ++k) total += std::max(counts[(size_t)k*streams + s], 0);
+		if (total > maxFrames) throw smst::Error("stream out resample: maxFrames is smaller than the frames a stream is delivered");
+		t.endIn = smst::streamResampleOutDue(t.delivered + total, up, down) - smst::streamResampleOutDue(t.delivered, up, down); // the rendered frames the calls consume
+		if (t.endIn > 0x7fffffffLL) throw smst::Error("stream out resample: a stream's rendered frames add up to more than 2147483647");
+		endIn = std::max(endIn, t.endIn);
+		std::vector<float> table((size_t)t.g.L*t.g.pitch);
+		smst::resampleTaps(t.g, table.data());
+		tables[s].allocate(table.size(), "stream out resample");
+		hip(hipMemcpy(tables[s], table.data(), table.size()*sizeof(float), hipMemcpyHostToDevice));
+	}
+	// host pointers are staged whole: every stream's rows, as far behind a 16-byte boundary as the caller's
+	const size_t imageBytes = endIn ? size_t((streams - 1)*imageSS + (channels - 1)*imageCS + endIn)*sizeof(float) : 0;
+	const size_t outBytes = maxFrames ? size_t((streams - 1)*outSS + (channels - 1)*outCS + maxFrames)*sizeof(float) : 0;
+	const size_t lineSet = (size_t)streams*channels*smst::kStreamResampleOutLine;
+	Buffer<unsigned char, false> dImage, dOut, dEntries;
+	Buffer<float, false> dLines;
+	dImage.allocate(imageBytes + 32, "stream out resample");
+	dOut.allocate(outBytes + 32, "stream out resample");
+	dEntries.allocate((size_t)streams*sizeof(smst::StreamResampleOutEntry), "stream out resample");
+	dLines.allocate(2*lineSet, "stream out resample");
+	unsigned char *i0 = dImage + reinterpret_cast<uintptr_t>(image)%16, *o0 = dOut + reinterpret_cast<uintptr_t>(out)%16;
+	if (imageBytes) hip(hipMemcpy(i0, image, imageBytes, hipMemcpyHostToDevice));
+	if (outBytes) hip(hipMemcpy(o0, out, outBytes, hipMemcpyHostToDevice));
+	hip(hipMemset(dLines, 0, 2*lineSet*sizeof(float)));
+	std::vector<smst::StreamResampleOutEntry> entries((size_t)streams);
+	for (int call = 0; call < calls; ++call) {
+		int mostNd = 0;
+		for (int s = 0; s < streams; ++s) {
+			const int n = counts[(size_t)call*streams + s];
+			entries[s] = smst::StreamResampleOutEntry{nullptr, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+			Stream &t = st[s];
+			if (t.g.L < 1 || n < 1) continue; // no setting, no part, or no frame: the line stays
+			const long long from = smst::streamResampleOutDue(t.delivered, t.g.L, t.g.M), E = smst::streamResampleOutDue(t.delivered + n, t.g.L, t.g.M) - from;
+			entries[s] = smst::StreamResampleOutEntry{tables[s].p, t.delivered, from, t.at, t.written, n, int(E), t.Dl, t.g.L, t.g.M, t.g.H, t.g.T, t.g.pitch, t.set, t.fresh};
+			t.delivered += n; t.at += E; t.written += n; t.set ^= 1; t.fresh = 0;
+			mostNd = std::max(mostNd, n);
+		}
+		if (mostNd < 1) continue;
+		int maxSpanPitch = 4;
+		for (int s = 0; s < streams; ++s) if (entries[s].L > 0) maxSpanPitch = std::max(maxSpanPitch, smst::resampleSpanPitchOf(entries[s].L, entries[s].M, entries[s].T, smst::streamResampleTileFrames(mostNd)));
+		hip(hipMemcpy(dEntries, entries.data(), entries.size()*sizeof(smst::StreamResampleOutEntry), hipMemcpyHostToDevice));
+		smst::launchPcmStreamResampleOut(reinterpret_cast<const float *>(i0), imageSS, imageCS, reinterpret_cast<float *>(o0), outSS, outCS, dLines, (long long)lineSet,
+		                                 reinterpret_cast<const smst::StreamResampleOutEntry *>(dEntries.p), streams, channels, mostNd, maxSpanPitch, nullptr);
+		hip(hipGetLastError());
+		hip(hipStreamSynchronize(nullptr));
+	}
+	if (outBytes) hip(hipMemcpy(out, o0, outBytes, hipMemcpyDeviceToHost));
+	if (rendered) for (int s = 0; s < streams; ++s) rendered[s] = st[s].at;
 	return SMST_OK;
 	SMST_CATCH
 }

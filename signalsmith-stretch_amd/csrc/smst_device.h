@@ -169,7 +169,7 @@ __host__ __device__ inline bool analysisWindowInCall(int B, int M, int I, int in
 // form" tests assert through these that BOTH forms really ran.
 enum LaunchKind {
 	LK_VOC_ALIGNED, LK_VOC_TWISTED, LK_VOC_INTERIOR, LK_VOC_STAGED, LK_VOC_GATHER, LK_VOC_N, LK_VOC_ONE, LK_VOC_ACROSS, LK_VOC_CONT, LK_CHAIN_UNFUSED,
-	LK_ANALYSE_TEAMS, LK_ANALYSE_PAIRS, LK_ANALYSE_TWIST, LK_TWIST_ROWS, LK_ANALYSE_FAST, LK_ANALYSE_GENERIC, LK_SYNTH_TEAMS, LK_SYNTH_FAST, LK_SYNTH_GENERIC, LK_SYNTH_EMIT, LK_EMIT_CARRIED, LK_FEED_ONE_PASS, LK_PCM_IN, LK_PCM_OUT, LK_CLIP_IN, LK_CLIP_OUT, LK_PCM_OUT_DITHERED, LK_CLIP_OUT_DITHERED, LK_PCM_OUT_LEVELLED, LK_CLIP_OUT_LEVELLED, LK_CLIP_PEAK, LK_CLIP_LOUDNESS, LK_CLIP_TRUE_PEAK, LK_CLIP_LIMIT_NEED, LK_CLIP_LIMIT_GAIN, LK_CLIP_OUT_LIMITED, LK_CLIP_LOUDNESS_RANGE, LK_CLIP_RESAMPLE, LK_PCM_LIMIT_FEED, LK_PCM_LIMIT_GAIN, LK_PCM_OUT_LIMITED, LK_PCM_STREAM_RESAMPLE, LK_PCM_STREAM_METER, LK_PCM_STREAM_METER_READ, LK_PCM_STREAM_METER_SCAN, LK_CLIP_RESAMPLE_OUT, LK_COUNT
+	LK_ANALYSE_TEAMS, LK_ANALYSE_PAIRS, LK_ANALYSE_TWIST, LK_TWIST_ROWS, LK_ANALYSE_FAST, LK_ANALYSE_GENERIC, LK_SYNTH_TEAMS, LK_SYNTH_FAST, LK_SYNTH_GENERIC, LK_SYNTH_EMIT, LK_EMIT_CARRIED, LK_FEED_ONE_PASS, LK_PCM_IN, LK_PCM_OUT, LK_CLIP_IN, LK_CLIP_OUT, LK_PCM_OUT_DITHERED, LK_CLIP_OUT_DITHERED, LK_PCM_OUT_LEVELLED, LK_CLIP_OUT_LEVELLED, LK_CLIP_PEAK, LK_CLIP_LOUDNESS, LK_CLIP_TRUE_PEAK, LK_CLIP_LIMIT_NEED, LK_CLIP_LIMIT_GAIN, LK_CLIP_OUT_LIMITED, LK_CLIP_LOUDNESS_RANGE, LK_CLIP_RESAMPLE, LK_PCM_LIMIT_FEED, LK_PCM_LIMIT_GAIN, LK_PCM_OUT_LIMITED, LK_PCM_STREAM_RESAMPLE, LK_PCM_STREAM_METER, LK_PCM_STREAM_METER_READ, LK_PCM_STREAM_METER_SCAN, LK_CLIP_RESAMPLE_OUT, LK_PCM_STREAM_RESAMPLE_OUT, LK_PCM_STREAM_RESAMPLE_OUT_COPY, LK_COUNT
 };
 long long launchCount(const char *name); // -1: unknown name
 
@@ -413,6 +413,34 @@ inline int streamResampleTileFrames(int maxFrames) { return maxFrames < 1 ? 1 : 
 inline long long streamResampleDue(long long q, int L, int M) { return q <= 0 ? 0 : (q*L + M - 1)/M; } // R(q) = ceil(max(q, 0)*L/M)
 void launchPcmStreamResample(const float *raw, long long rawStreamStride, long long rawChannelStride, float *image, long long imageStreamStride, long long imageChannelStride,
                              float *lines, long long lineSetStride, const StreamResampleEntry *entries, int S, int C, int maxFrames, int maxSpanPitch, hipStream_t st);
+
+// The converter's streaming form BEHIND the engine (include/smst.h, "Stream output resample", has the definition; smst_stream_resample_out.h
+// the kernels): a stream with the setting has received `delivered` frames at the delivery rate since its line was last cleared, and the engine
+// has rendered rendered = streamResampleOutDue(delivered) frames for it; a call that delivers Nd frames renders
+// E = streamResampleOutDue(delivered + Nd) - rendered more.  Delivered frame n < Dl = streamResampleOutLatency is +0.0, frame n >= Dl is
+// frame n - Dl of "Resample" applied to the rendered frames.  What a batch carries, device: per stream and channel the last
+// kStreamResampleOutLine rendered frames, r(rendered - kStreamResampleOutLine + j) at [j], two sets [2][S][C][kStreamResampleOutLine], of
+// which a call reads the one its entry names and writes the other.
+// The line's length: the call's first frame n = delivered >= Dl sits at i = ((delivered - Dl)*M)/L and reaches back to i - (H - 1).  With
+// a = delivered*M/L and b = (delivered - Dl)*M/L, a - b = Dl*M/L < (H*L/M + 1)*M/L = H + M/L, and ceil(a) - floor(b) < a - b + 2, a whole
+// number, so ceil(a) - floor(b) <= H + ceil(M/L) + 1: the reach rendered - (i - (H - 1)) is at most T + ceil(M/L).  M/L <= 4.5 gives
+// H <= 144, T <= 288, ceil(M/L) <= 5: 293 frames at 2/9, which kStreamResampleLine (288) does not hold.
+// StreamResampleOutEntry: one per stream, device -- L == 0: the stream has no setting, Nd < 1: it has no frame in the call; either way the
+// kernels leave its rows and its line alone.  fresh != 0: the line counts as +0.0 (it was cleared); imageAt / outAt: the column of the
+// call's first rendered frame in the engine's output image and of its first delivered frame in the image the kernel writes.
+// maxFrames: the largest Nd (sizes the grid); maxSpanPitch: the largest resampleSpanPitchOf(..., streamResampleTileFrames(maxFrames)) of the
+// launch's entries (sizes the LDS)
+constexpr int kStreamResampleOutLine = 296;              // floats of a channel's line: T + ceil(M/L) <= 293, in whole 16-byte words
+static_assert(kStreamResampleOutLine >= 2*((32*9 + 1)/2) + (9 + 1)/2 && kStreamResampleOutLine%4 == 0, "the line holds T + ceil(M/L) frames at 2/9, the longest");
+struct StreamResampleOutEntry { const float *taps; long long delivered, rendered, imageAt, outAt; int Nd, E, Dl, L, M, H, T, pitch, set, fresh; };
+inline long long streamResampleOutDue(long long delivered, int L, int M) { return (delivered*M + L - 1)/L; } // ceil(delivered*M/L), delivered >= 0
+inline int streamResampleOutLatency(int L, int M, int H) { return int(((long long)H*L + M - 1)/M); }       // Dl = ceil(H*L/M)
+void launchPcmStreamResampleOut(const float *image, long long imageStreamStride, long long imageChannelStride, float *out, long long outStreamStride, long long outChannelStride,
+                                float *lines, long long lineSetStride, const StreamResampleOutEntry *entries, int S, int C, int maxFrames, int maxSpanPitch, hipStream_t st);
+// ... and the delivered frames of the streams that have the setting from `from`, column outAt of their rows, over the rendered ones in
+// `image`, from column imageAt: the output stages then read ONE image, as they did.  Streams without the setting are not touched
+void launchPcmStreamResampleOutCopy(const float *from, long long fromStreamStride, long long fromChannelStride, float *image, long long imageStreamStride, long long imageChannelStride,
+                                    const StreamResampleOutEntry *entries, int S, int C, int maxFrames, hipStream_t st);
 
 // The R 128 meters' streaming form (include/smst.h, "Stream meter", has the definition; smst_stream_meter.h the kernels), for the streams whose
 // configuration has `on`: every frame that smst_batch_process_pcm / _flush_pcm write for the stream, up to cap = maxSubBlocks*h of them, is

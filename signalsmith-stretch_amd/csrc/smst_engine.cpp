@@ -424,6 +424,7 @@ void Batch::allocateCallTables() {
 	resampleSlot.assign(S, -1);
 	streamResampleSlot.assign(S, -1);
 	outResampleSlot.assign(S, -1);
+	streamOutResampleSlot.assign(S, -1);
 	for (std::vector<unsigned char> *v : {&flushV.runBlock, &flushV.on, &outputSeekV.mask, &exactV.run}) v->assign(S, 0);
 	outputSeekV.rates.assign(S, 1.0);
 	exactV.rates.assign(S, 0.0f);
@@ -2046,7 +2047,7 @@ void resampleReduce(int &up, int &down) {
 void Batch::setResample(int stream, int up, int down, int setting) {
 	if (stream < -1 || stream >= S) throw Error("stream index out of range");
 	resampleReduce(up, down);
-	std::vector<int> &mine = setting == kResampleStream ? streamResampleSlot : setting == kResampleOut ? outResampleSlot : resampleSlot; // (a slot's users are the streams of ALL three settings)
+	std::vector<int> &mine = setting == kResampleStream ? streamResampleSlot : setting == kResampleOut ? outResampleSlot : setting == kResampleStreamOut ? streamOutResampleSlot : resampleSlot; // (a slot's users are the streams of ALL four settings)
 	SMST_HIP(hipSetDevice(dev));
 	const bool none = up == 1 && down == 1;
 	const int first = stream < 0 ? 0 : stream, last = stream < 0 ? S : stream + 1;
@@ -2096,6 +2097,12 @@ void Batch::streamResampleOf(int stream, int &up, int &down) const {
 	if (stream < 0 || stream >= S) throw Error("stream index out of range");
 	up = down = 1;
 	if (streamResampleSlot[stream] >= 0) { up = resampleSlots[streamResampleSlot[stream]].shape.L; down = resampleSlots[streamResampleSlot[stream]].shape.M; }
+}
+
+void Batch::streamOutResampleOf(int stream, int &up, int &down) const {
+	if (stream < 0 || stream >= S) throw Error("stream index out of range");
+	up = down = 1;
+	if (streamOutResampleSlot[stream] >= 0) { up = resampleSlots[streamOutResampleSlot[stream]].shape.L; down = resampleSlots[streamOutResampleSlot[stream]].shape.M; }
 }
 
 void Batch::outResampleOf(int stream, int &up, int &down) const {

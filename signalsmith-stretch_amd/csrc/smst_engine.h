@@ -132,7 +132,9 @@ public:
 	// stream, which shares the tables and their kResampleMaxRatios slots: a slot is live while any setting of any stream uses it
 	// output: the stream's THIRD setting (include/smst.h, "Output resample"), the delivery rate over the batch's rate, which exact() serves
 	// behind the engine; it shares the tables and the slots as well
-	enum ResampleSetting { kResampleClip = 0, kResampleStream = 1, kResampleOut = 2 };
+	// streaming output: the stream's FOURTH setting (include/smst.h, "Stream output resample"), the delivery rate over the batch's rate in the
+	// streaming calls; it shares the tables and the slots too
+	enum ResampleSetting { kResampleClip = 0, kResampleStream = 1, kResampleOut = 2, kResampleStreamOut = 3 };
 	void setResample(int stream, int up, int down, int setting = kResampleClip);
 	bool outResampled(int stream) const { return outResampleSlot[stream] >= 0; }
 	void outResampleOf(int stream, int &up, int &down) const;
@@ -143,6 +145,11 @@ public:
 	// shape and table (device) of a stream that has the streaming setting
 	const ResampleShape &streamResampleShape(int stream) const { return resampleSlots[streamResampleSlot[stream]].shape; }
 	const float *streamResampleTaps(int stream) const { return resampleSlots[streamResampleSlot[stream]].taps; }
+	bool streamOutResampled(int stream) const { return streamOutResampleSlot[stream] >= 0; }
+	void streamOutResampleOf(int stream, int &up, int &down) const;
+	// shape and table (device) of a stream that has the streaming output setting
+	const ResampleShape &streamOutResampleShape(int stream) const { return resampleSlots[streamOutResampleSlot[stream]].shape; }
+	const float *streamOutResampleTaps(int stream) const { return resampleSlots[streamOutResampleSlot[stream]].taps; }
 	void resampleOf(int stream, int &up, int &down) const;
 	long long resampledLengthOf(int stream, long long inSamples) const; // Nr of a clip of the stream (inSamples itself where it has no ratio)
 	// The limiter's lookahead H in frames (include/smst.h, "Limiter"), 1 ... kLimitMaxLookahead, the batch's one.  prepareLimiter() puts the
@@ -364,7 +371,7 @@ private:
 	size_t clipRawCapacity = 0;
 	struct ResampleSlot { ResampleShape shape{0, 0, 0, 0, 0}; float *taps = nullptr; int users = 0; };
 	ResampleSlot resampleSlots[kResampleMaxRatios];
-	std::vector<int> resampleSlot, streamResampleSlot, outResampleSlot; // per stream, the slot of its whole-clip, of its streaming and of its output ratio (-1: none)
+	std::vector<int> resampleSlot, streamResampleSlot, outResampleSlot, streamOutResampleSlot; // per stream, the slot of its whole-clip, its streaming, its output and its streaming output ratio (-1: none)
 	// a device scratch that holds `need` floats, allocated with `room` more; true: it was replaced (the old one freed behind a synchronise).  workspace: counted in workspaceBytes()
 	bool growScratch(float *&scratch, size_t &capacity, size_t need, size_t room, bool workspace);
 	StreamParams *dParams = nullptr, *hParams = nullptr; // (hParams: pinned staging of uploadParams())

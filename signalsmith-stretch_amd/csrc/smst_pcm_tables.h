@@ -15,6 +15,7 @@
 // ResampleTableLayout  the table a whole-clip call with a resampled stream adds on the input side (the engine's; two sets as the above)
 // StreamResampleTableLayout  the table a streaming call adds on the input side where a stream has the stream-resample setting
 // ResampleOutTableLayout  the table a whole-clip call with an out-resampled stream adds on the output side (the engine's; two sets)
+// StreamResampleOutTableLayout  the table a streaming call adds on the output side where a stream has the stream-output-resample setting
 #pragma once
 #include "smst_device.h"
 #include <cstddef>
@@ -123,6 +124,18 @@ struct ResampleOutTableLayout {
 	ResampleOutEntry *entries(void *base) const { return pcmTableAt<ResampleOutEntry>(base, entries()); }
 };
 static_assert(alignof(ResampleOutEntry) <= 16, "the entries begin on a 16-byte boundary where the table does");
+
+// StreamResampleOutTableLayout: what a streaming call adds on the output side where a stream of the batch has the setting of include/smst.h,
+// "Stream output resample" -- a table of its own, pinned host staging with a device twin, uploaded in ONE copy.  One section:
+//   entries  [S] StreamResampleOutEntry  taps, shape, Nd, E, Dl, delivered, rendered and the set of lines the call reads (L == 0: no setting)
+struct StreamResampleOutTableLayout {
+	size_t S;
+	explicit StreamResampleOutTableLayout(int streams) : S(size_t(streams)) {}
+	size_t entries() const { return 0; }
+	size_t bytes() const { return entries() + S*sizeof(StreamResampleOutEntry); }
+	StreamResampleOutEntry *entries(void *base) const { return pcmTableAt<StreamResampleOutEntry>(base, entries()); }
+};
+static_assert(alignof(StreamResampleOutEntry) <= 16 && sizeof(StreamResampleOutEntry)%8 == 0, "the entries begin on a 16-byte boundary where the table does");
 
 struct PcmMeters {
 	size_t S;

@@ -1,5 +1,5 @@
 // State that outlives a tile or a call (carry, history, reset, seek, flush, pre-roll, pass-through), the launch counters, the self-test of smst_complex.h,
-// and (smst_pcm.h, smst_clip.h, smst_resample.h, smst_resample_out.h, smst_stream_resample.h, smst_loudness.h, smst_loudness_range.h, smst_true_peak.h, smst_limiter.h, smst_stream_limiter.h, smst_stream_meter.h) the interleaved-PCM converters, the clip copies, the
+// and (smst_pcm.h, smst_clip.h, smst_resample.h, smst_resample_out.h, smst_stream_resample.h, smst_stream_resample_out.h, smst_loudness.h, smst_loudness_range.h, smst_true_peak.h, smst_limiter.h, smst_stream_limiter.h, smst_stream_meter.h) the interleaved-PCM converters, the clip copies, the
 // sample-rate converters in front of and behind the engine, the loudness passes and meters, the true-peak pass and the limiter's two passes, whole-clip and streaming, of the batch API's boundary.
 #include "smst_recurrence.h"
 #include "smst_pcm.h"
@@ -7,6 +7,7 @@
 #include "smst_resample.h"
 #include "smst_resample_out.h"
 #include "smst_stream_resample.h"
+#include "smst_stream_resample_out.h"
 #include "smst_loudness.h"
 #include "smst_loudness_range.h"
 #include "smst_true_peak.h"
@@ -283,7 +284,7 @@ void launchFftComplexSelfTest(const float *in, float *out, int n, hipStream_t st
 static std::atomic<long long> gLaunchCounts[LK_COUNT];
 static const char *const kLaunchNames[LK_COUNT] = {
 	"vocoder_aligned", "vocoder_twisted", "vocoder_interior", "vocoder_staged", "vocoder_gather", "vocoder_n", "vocoder_one", "vocoder_across", "vocoder_continuous", "chain_unfused",
-	"analyse_teams", "analyse_pairs", "analyse_twist", "twist_rows", "analyse_fast", "analyse_generic", "synth_teams", "synth_fast", "synth_generic", "synth_emit", "emit_carried", "feed_one_pass", "pcm_in", "pcm_out", "clip_in", "clip_out", "pcm_out_dithered", "clip_out_dithered", "pcm_out_levelled", "clip_out_levelled", "clip_peak", "clip_loudness", "clip_true_peak", "clip_limit_need", "clip_limit_gain", "clip_out_limited", "clip_loudness_range", "clip_resample", "pcm_limit_feed", "pcm_limit_gain", "pcm_out_limited", "pcm_stream_resample", "pcm_stream_meter", "pcm_stream_meter_read", "pcm_stream_meter_scan", "clip_resample_out"};
+	"analyse_teams", "analyse_pairs", "analyse_twist", "twist_rows", "analyse_fast", "analyse_generic", "synth_teams", "synth_fast", "synth_generic", "synth_emit", "emit_carried", "feed_one_pass", "pcm_in", "pcm_out", "clip_in", "clip_out", "pcm_out_dithered", "clip_out_dithered", "pcm_out_levelled", "clip_out_levelled", "clip_peak", "clip_loudness", "clip_true_peak", "clip_limit_need", "clip_limit_gain", "clip_out_limited", "clip_loudness_range", "clip_resample", "pcm_limit_feed", "pcm_limit_gain", "pcm_out_limited", "pcm_stream_resample", "pcm_stream_meter", "pcm_stream_meter_read", "pcm_stream_meter_scan", "clip_resample_out", "pcm_stream_resample_out", "pcm_stream_resample_out_copy"};
 void countLaunch(LaunchKind k) { gLaunchCounts[k].fetch_add(1, std::memory_order_relaxed); }
 long long launchCount(const char *name) {
 	for (int i = 0; i < LK_COUNT; ++i) if (name && std::strcmp(name, kLaunchNames[i]) == 0) return gLaunchCounts[i].load(std::memory_order_relaxed);
