@@ -671,20 +671,50 @@ int smst_debug_limiter_window(int lookahead, float *out);
  *   9 frames with v(0) = 1, cut as 3, 6: r = 3f755556 3f555556 3f2aaaab 3f0aaaab 3f000000 3f0aaaab 3f2aaaab 3f555556 3f755556; the output
  *   is 80000000 x4, bf000000, 80000000 x4; limitedFrames 9.
  *
+ *   True-peak detector.  A per-stream flag of its own beside the setting (smst_batch_set_pcm_stream_limiter_true_peak), so that a live
+ *   stream meets a ceiling given in dBTP.  It is NOT smst_batch_set_pcm_true_peak, which stays refused in the streaming calls, and it is
+ *   inert while the stream's setting is off.  The taps of "True peak" reach 6 frames ahead of a frame, so need of a frame exists 6 frames
+ *   later: let D = 2H + 6 (SMST_STREAM_LIMITER_TRUE_PEAK_DELAY = 6).  The T frames a flagged stream has been handed so far are the first T
+ *   frames of "Limiter"'s steps 2 to 7 applied to the clip [D frames of +0.0, v(0), v(1), ... v(T - 1)], where g is the fixed gain, need
+ *   uses |g|, the detector is step 2 WITH the true-peak phases -- "True peak"'s own float64 sums, each rounded once, NaNs skipped --, the
+ *   ceiling is the stream limiter's and the window the batch's.  Frame i < T depends on need up to i + 2H, which depends on the clip up
+ *   to i + 2H + 6 < T + D: the clip's right edge never enters, the result does not depend on the cuts, and the streaming form is, bit for
+ *   bit, the clip limiter with its true-peak flag on.  Everything above carries over with D in the place of 2H: the leading D zeros are
+ *   treated as frames; a flush does not empty the line, and to end a stream its flush is asked for D frames more; the meters, the dither
+ *   counter and the other streams of the call behave as described; the clearing rules are the same, and the flag's setter clears the
+ *   stream's line as well, on or off, because the delay changes.  smst_batch_pcm_stream_limiter_latency_of reports a stream's own delay:
+ *   0, 2H or 2H + 6.  Behind a stream output resample the limiter sees the delivered frames as ever; the delays add up to Dl + 2H + 6.
+ *   Known answers (float32 bit patterns).  H = 2, mono, g = 1, ceiling 1, flag on, 24 frames with v(6) = v(7) = 1 and the rest 0, cut as
+ *   5, 1, 7, 11 (D = 10): r of the frames written = 3f800000 x12, 3f7bba48 3f6ee91e 3f5dd23c 3f510112 3f4cbb59 3f510112 3f5dd23c 3f6ee91e
+ *   3f7bba48, 3f800000 x3; the float32 output is 3f4cbb59 at frame 16 and 3f510112 at frame 17, 0 elsewhere -- the inter-sample crest
+ *   belongs to v(6): need = 1/1.2504163 --; minGain 3f4cbb59, limitedFrames 9.  H = 1, mono, g = -1, ceiling 1, flag on, 12 frames with
+ *   v(0) = v(1) = 1, cut as 3, 9 (D = 8): r = 3f800000 x6, 3f732ed6 3f598c83 3f4cbb59 3f598c83 3f732ed6, 3f800000; the output is 80000000
+ *   x8, bf4cbb59, bf598c83, 80000000 x2; limitedFrames 5.
+ *
  * What it guarantees: what the clip limiter guarantees.  The SAMPLE peak of u is at most the ceiling, up to the roundings tabulated under
- * "Clip-free ceilings"; the TRUE peak is not bounded -- "Limiter" quotes the measured overshoots per H.
+ * "Clip-free ceilings" -- with the flag too: the true-peak need is never above the sample need.  The TRUE peak of a stream without the flag
+ * is not bounded: on the signals of "Limiter"'s measurement (white noise, AM tones, sparse spikes, 12 dB over a ceiling of 0.5) the numpy
+ * mirror's output stands 59 % over the ceiling at H = 72 and 36, 61 % at H = 8 and 67 % at H = 1.  With the flag it is the clip limiter's
+ * measured property, because the outputs are the same bits: 2.4e-6 over at H = 72, 2.5e-5 at H = 36, 3.3e-3 (0.03 dB) at H = 8 and 17 %
+ * at H = 1 (EXPERIMENTS.md, "Stream limiter, true-peak detector") -- a short lookahead weakens a dBTP promise here as it does there.
  *
  * How.  Per stream, in device memory and counted in smst_batch_workspace_bytes: need of the last 4H frames, the last 2H frames of every
  * channel (v, before the gain) and the meter words, allocated by the first setter call with on != 0 -- which makes the batch a levelled one
  * and puts the window on the device --, never in a call.  The lines exist twice: every kernel of a call reads one set and writes the other,
  * and everything is ordered by the batch's stream, so one pair serves calls in flight.  Three kernels (csrc/smst_stream_limiter.h):
  * need of the call's frames behind the carried ones; the curve, by the clip limiter's own steps 4 to 6 (one device function for both); and
- * a limited conversion -- a kernel of its own -- whose loader takes frame i from the line (i < 2H) or from the call's image at i - 2H.  The
+ * a limited conversion -- a kernel of its own -- whose loader takes frame i from the line (i < 2H) or from the call's image at i - 2H.  A
+ * flagged stream has a feed kernel of its own, which forms need of the c frames v(p - 6) ... v(p + c - 7) of a call of c frames after p
+ * emitted ones from the 11 frames carried in front of them and the call's image, with the phases' one definition (truePeakFrameBits); it
+ * carries its last 2H + 11 frames per channel -- a uniform length: the 11 of the taps and the 2H + 6 of the delay overlap in 6 --, two
+ * sets again, allocated by the first call of the flag's setter with on != 0 and counted in smst_batch_workspace_bytes.  The gain pass is
+ * the same launch for both kinds; a call in which no flagged stream has frames launches exactly what it launched before the flag
+ * existed.  The flag is bit 4 of the level entry's fourth word.  The
  * work rows ([streams][4H + longest limited call] and [streams][longest limited call] floats) grow with the first call that needs them; a
  * steady-state call allocates nothing and no host synchronisation is added.  The setting is bit 2 of the fourth word of the stream's level
  * entry, the ceiling rides in the word a FIXED entry does not use; smst_batch_pcm_level keeps reporting the level's own ceiling.
- * Out of scope: a true-peak detector (its 12 taps would add latency of their own), a lookahead per stream, the planar calls,
- * smst_batch_exact_pcm, release shaping, stretch_cli (a whole-file tool, which has --limit).
+ * Out of scope: a lookahead per stream, oversampled gain application, the planar calls, smst_batch_exact_pcm, release shaping, stretch_cli
+ * (a whole-file tool, which has --limit).
  * SMST_ERR_INVALID with a message, before anything runs: a stream index out of range, a null batch, a ceiling that is NaN or <= 0 (+inf is
  * allowed: no limit); smst_batch_exact_pcm with a participating stream that has the setting on (the whole-clip form is
  * smst_batch_set_pcm_limiter). */
@@ -693,14 +723,22 @@ int smst_debug_limiter_window(int lookahead, float *out);
 int smst_batch_set_pcm_stream_limiter(smst_batch *b, int stream, int on, float ceiling);
 /* on and ceiling may be null */
 int smst_batch_pcm_stream_limiter(const smst_batch *b, int stream, int *on, float *ceiling);
-/* 2H: the frames by which a limited stream's output is late */
+/* 2H: the frames by which a limited stream's output is late (a stream with the true-peak flag below: 6 more, which _latency_of reports) */
 int smst_batch_pcm_stream_limiter_latency(const smst_batch *b, int *frames);
+#define SMST_STREAM_LIMITER_TRUE_PEAK_DELAY 6 /* frames: what the taps of "True peak" reach ahead (kTruePeakTrail) */
+/* the setting's true-peak flag ("True-peak detector" above).  stream = -1: every stream.  Clears the line of the stream(s), on or off.  The
+ * first call with on != 0 allocates the lines the flag carries (and, in a batch whose setting was never on, the window and the setting's lines) */
+int smst_batch_set_pcm_stream_limiter_true_peak(smst_batch *b, int stream, int on);
+/* on may be null */
+int smst_batch_pcm_stream_limiter_true_peak(const smst_batch *b, int stream, int *on);
+/* the frames by which this stream's output is late: 0 with the setting off, 2H with it on, 2H + 6 with the flag as well.  frames may be null */
+int smst_batch_pcm_stream_limiter_latency_of(const smst_batch *b, int stream, int *frames);
 /* per stream, over the calls since the last take: minGain[s] = the lowest r written, limitedFrames[s] = the frames written with r < 1; 1 and
  * 0 where nothing was limited.  Either may be null.  Synchronises the batch and clears the meters. */
 int smst_batch_take_pcm_stream_limiter(smst_batch *b, float *minGain, long long *limitedFrames);
 /* test hook: `calls` output conversions in sequence on one device stream, with the carried lines, on a planar fp32 image (host pointer,
  * strides in floats) that holds each stream's frames in order.  counts: [calls][streams], negative = the stream takes no part in that call.
- * gains, ceilings, flags: [streams]; flags: 1 = setting on.  r: [streams][maxFrames] as written (delayed; 1 for a stream without the setting
+ * gains, ceilings, flags: [streams]; flags: bit 0 (1) = setting on, bit 1 (2) = the true-peak detector as well (inert without bit 0).  r: [streams][maxFrames] as written (delayed; 1 for a stream without the setting
  * and behind the frames written); frames: interleaved float32 [streams][maxFrames][channels], the F32 output (+0.0 behind the frames
  * written).  maxFrames >= the sum of every stream's counts.  minGain, limitedFrames: [streams], the meters of all the calls.  Any output
  * pointer may be null. */

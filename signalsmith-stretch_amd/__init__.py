@@ -35,6 +35,7 @@ LOUDNESS_RANGE_TILE = 256                                   # short-term powers 
 LOUDNESS_CHUNK = 256                                         # frames one lane of the loudness passes filters (SMST_LOUDNESS_CHUNK)
 TRUE_PEAK_TILE = 1024                                        # frames one workgroup of the true-peak pass measures (SMST_TRUE_PEAK_TILE)
 LIMITER_TILE, LIMITER_MAX_LOOKAHEAD, LIMITER_DEFAULT_LOOKAHEAD = 1024, 1024, 72  # frames one workgroup of the limiter's passes takes; the lookahead's bound and default (SMST_LIMITER_*)
+STREAM_LIMITER_TRUE_PEAK_DELAY = 6  # frames a stream with the stream limiter's true-peak flag is late beyond 2*lookahead (SMST_STREAM_LIMITER_TRUE_PEAK_DELAY)
 _FRAME_DTYPES = {"int16": PCM_S16, "float32": PCM_F32, "int32": PCM_S32, "float16": PCM_F16}  # (packed int24 travels as uint8 [..., 3])
 _FRAME_DTYPE_OF = {PCM_S16: "int16", PCM_F32: "float32", PCM_S32: "int32", PCM_F16: "float16", PCM_S24: "uint8"}
 _fp = C.POINTER(C.c_float)
@@ -159,6 +160,9 @@ _SIGNATURES = {
     "smst_batch_set_pcm_stream_limiter": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_float]),
     "smst_batch_pcm_stream_limiter": (C.c_int, [C.c_void_p, C.c_int, _ip, _fp]),
     "smst_batch_pcm_stream_limiter_latency": (C.c_int, [C.c_void_p, _ip]),
+    "smst_batch_set_pcm_stream_limiter_true_peak": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
+    "smst_batch_pcm_stream_limiter_true_peak": (C.c_int, [C.c_void_p, C.c_int, _ip]),
+    "smst_batch_pcm_stream_limiter_latency_of": (C.c_int, [C.c_void_p, C.c_int, _ip]),
     "smst_batch_take_pcm_stream_limiter": (C.c_int, [C.c_void_p, _fp, C.POINTER(_ll)]),
     "smst_debug_pcm_stream_limit": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _ip, C.c_void_p, _ll, _ll, _fp, _fp, _ip, C.c_int, _fp, _fp, C.c_int, _fp, C.POINTER(_ll)]),
     "smst_batch_set_pcm_loudness_range": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_double]),
@@ -436,7 +440,8 @@ def debug_limiter_window(lookahead, lib=None):
 
 def debug_pcm_stream_limit(counts, channels, image, image_ss, image_cs, gains, ceilings, flags, lookahead, max_frames, device=0, lib=None):
     """smst_debug_pcm_stream_limit on a numpy image (planar float32 that holds each stream's frames in order; strides in floats; counts int
-    [calls, S], negative: the stream takes no part in that call; gains, ceilings, flags: [S], flags 1 = the setting on) -> (r: float32
+    [calls, S], negative: the stream takes no part in that call; gains, ceilings, flags: [S], flags 1 = the setting on, 3 = with the true-peak
+    detector, 2H + 6 frames late) -> (r: float32
     [S, max_frames] as written; frames: float32 [S, max_frames, channels], the F32 output; min gain: float32 [S]; limited frames: int64 [S])"""
     lib = lib if lib is not None else load_library()
     g, c, f = np.ascontiguousarray(gains, np.float32), np.ascontiguousarray(ceilings, np.float32), np.ascontiguousarray(flags, np.int32)
@@ -1058,6 +1063,23 @@ class StretchBatch:
         """-> 2*lookahead: the frames by which a limited stream's output is late"""
         frames = C.c_int(0)
         _check(self.lib, self.lib.smst_batch_pcm_stream_limiter_latency(self.h, C.byref(frames)))
+        return frames.value
+
+    def set_pcm_stream_limiter_true_peak(self, on=True, stream=-1):
+        """The stream limiter's true-peak flag (include/smst.h, "Stream limiter"): the detector sees the three inter-sample phases of "True
+        peak" as well, the output comes 2*lookahead + 6 frames late, and the stream is, bit for bit, the clip limiter with its true-peak
+        flag.  Inert while the stream's setting is off.  Clears the stream's line; stream = -1: every stream."""
+        _check(self.lib, self.lib.smst_batch_set_pcm_stream_limiter_true_peak(self.h, int(stream), 1 if on else 0))
+
+    def pcm_stream_limiter_true_peak(self, stream):
+        on = C.c_int(0)
+        _check(self.lib, self.lib.smst_batch_pcm_stream_limiter_true_peak(self.h, int(stream), C.byref(on)))
+        return bool(on.value)
+
+    def pcm_stream_limiter_latency_of(self, stream):
+        """-> the frames by which the stream's output is late: 0 with the setting off, 2*lookahead with it on, 6 more with the flag"""
+        frames = C.c_int(0)
+        _check(self.lib, self.lib.smst_batch_pcm_stream_limiter_latency_of(self.h, int(stream), C.byref(frames)))
         return frames.value
 
     def take_pcm_stream_limiter(self):

@@ -92,12 +92,14 @@ struct PcmOutState {
 	// the stream limiter (smst_batch_set_pcm_stream_limiter; include/smst.h, "Stream limiter"): the setting and its ceiling, and which of the
 	// stream's two carried lines the next call reads.  The lines -- both sets in one buffer, sized for the lookahead they were allocated at --
 	// and the two meter words per stream exist from the first setter call with `on`; the need and r rows of a call grow on demand, as the
-	// images do.  streamLimitView: where the kernels find all of that (smst::PcmStreamLimit)
-	struct StreamLimit { unsigned char on = 0, set = 0; float ceiling = 1.0f; };
+	// images do.  streamLimitView: where the kernels find all of that (smst::PcmStreamLimit).  truePeak: the stream's true-peak flag
+	// (smst_batch_set_pcm_stream_limiter_true_peak), inert while `on` is 0; the lines it carries -- both sets in a buffer of their own, sized
+	// as the others are -- exist from the first setter call with the flag on
+	struct StreamLimit { unsigned char on = 0, set = 0, truePeak = 0; float ceiling = 1.0f; };
 	std::vector<StreamLimit> streamLimit;
-	DeviceFloats dLimitLines, dLimitRows;
+	DeviceFloats dLimitLines, dLimitRows, dLimitTruePeakLines;
 	Buffer<int, false> dLimitMeters;
-	int limitLinesH = 0;
+	int limitLinesH = 0, limitTruePeakLinesH = 0;
 	smst::PcmStreamLimit streamLimitView;
 	std::vector<int> hLimitMeters;
 	// the stream meter (smst_batch_set_pcm_stream_meter; include/smst.h, "Stream meter"): the setting, the entry made of its rate, the frames
@@ -149,7 +151,7 @@ struct PcmOutState {
 		if (hipMemcpy(dMeters, hMeters.data(), meters.bytes(), hipMemcpyHostToDevice) != hipSuccess) throw smst::Error("hipMemcpy (PCM level) failed", true);
 	}
 	size_t workspaceBytes() const {
-		return (dOvers ? pcmOversBytes(S) : 0) + (dMeters ? smst::PcmMeters(S).bytes() : 0) + (dLimitLines.cap + dLimitRows.cap)*sizeof(float) + dLimitMeters.cap*sizeof(int) +
+		return (dOvers ? pcmOversBytes(S) : 0) + (dMeters ? smst::PcmMeters(S).bytes() : 0) + (dLimitLines.cap + dLimitRows.cap + dLimitTruePeakLines.cap)*sizeof(float) + dLimitMeters.cap*sizeof(int) +
 		       dMeterConfig.cap*sizeof(smst::StreamMeterConfig) + (dMeterState.cap + dMeterSub.cap + dMeterRead.cap + dMeterScan.cap)*sizeof(double) + dMeterFrames.cap*sizeof(float) +
 		       dMeterWords.cap*sizeof(int) + dMeterTables.cap;
 	}
@@ -214,6 +216,7 @@ struct PcmOutState {
 			streamLimitView.H = H;
 			dLimitRows.release(); // (their pitch depends on H: the next limited call grows them)
 		}
+		if (dLimitTruePeakLines && limitTruePeakLinesH != H) allocateStreamLimitTruePeakLines(e);
 		if (!dLimitMeters) {
 			dLimitMeters.allocate((size_t)2*S, "stream limiter meters");
 			hLimitMeters.assign((size_t)2*S, 0);
@@ -222,6 +225,16 @@ struct PcmOutState {
 		streamLimitView.meters = dLimitMeters;
 		streamLimitView.window = e.limiterWindow();
 		clearStreamLimitLines(e, -1);
+	}
+	// The lines of the true-peak flag for the engine's lookahead H, as +0.0: allocated where they are missing or were made for another H (no
+	// call in flight reads them then: the lookahead's setter has synchronised, and before the first flag no call knows them)
+	void allocateStreamLimitTruePeakLines(Batch &e) {
+		const int H = e.limiterLookahead();
+		const size_t set = smst::pcmStreamLimitTruePeakSetFloats(S, C, H);
+		dLimitTruePeakLines.allocate(2*set, "stream limiter true-peak lines");
+		limitTruePeakLinesH = H;
+		for (int k = 0; k < 2; ++k) streamLimitView.truePeakFrames[k] = dLimitTruePeakLines + k*set;
+		if (hipMemsetAsync(dLimitTruePeakLines, 0, 2*set*sizeof(float), e.stream()) != hipSuccess) throw smst::Error("hipMemsetAsync (stream limiter true-peak lines) failed", true);
 	}
 	// need <- 1, frames <- +0.0 for the stream (-1: every one), in the batch's stream order
 	void clearStreamLimitLines(Batch &e, int stream) {
@@ -242,15 +255,42 @@ struct PcmOutState {
 		forStreams(stream, [&](int s) { streamLimit[s].on = on ? 1 : 0; streamLimit[s].ceiling = ceiling; });
 		clearStreamLimitLines(e, stream);
 	}
+	// The flag beside the setting: the delay of the stream(s) changes, so their lines are cleared, on or off.  The first call with `on`
+	// allocates the flag's lines (and, where the setting has never been on, what that carries: a flagged stream's need line is one of those)
+	void setStreamLimiterTruePeak(Batch &e, int stream, int on) {
+		forStreams(stream, [](int) {}); // (refused before anything is allocated)
+		if (on) {
+			if (hipSetDevice(e.device()) != hipSuccess) throw smst::Error("hipSetDevice failed", true);
+			if (!e.limiterWindow()) e.prepareLimiter(); // (the window goes to the device here, not in a call)
+			if (!dLimitLines) prepareStreamLimitLines(e);
+			if (!dLimitTruePeakLines || limitTruePeakLinesH != e.limiterLookahead()) allocateStreamLimitTruePeakLines(e);
+		}
+		forStreams(stream, [&](int s) { streamLimit[s].truePeak = on ? 1 : 0; });
+		clearStreamLimitLines(e, stream);
+	}
 	bool anyStreamLimit() const {
 		if (levelled) for (const StreamLimit &l : streamLimit) if (l.on) return true;
 		return false;
 	}
-	// the largest count of a stream that a streaming call of these counts limits: the setting, a FIXED level and frames
-	int mostStreamLimited(const int *n) const {
-		int most = 0;
-		if (anyStreamLimit()) for (int s = 0; s < S; ++s) if (streamLimit[s].on && level[s].mode == SMST_LEVEL_FIXED) most = std::max(most, n[s]);
+	// the largest count of a stream that a streaming call of these counts limits: the setting, a FIXED level and frames; truePeak (may be
+	// null): the largest among those of them that have the true-peak flag
+	int mostStreamLimited(const int *n, int *truePeak = nullptr) const {
+		int most = 0, flagged = 0;
+		if (anyStreamLimit()) for (int s = 0; s < S; ++s) if (streamLimit[s].on && level[s].mode == SMST_LEVEL_FIXED) {
+			most = std::max(most, n[s]);
+			if (streamLimit[s].truePeak) flagged = std::max(flagged, n[s]);
+		}
+		if (truePeak) *truePeak = flagged;
 		return most;
+	}
+	// ... and among those without the flag
+	int mostStreamLimitedPlain(const int *n) const {
+		int most = 0;
+		if (anyStreamLimit()) for (int s = 0; s < S; ++s) if (streamLimit[s].on && !streamLimit[s].truePeak && level[s].mode == SMST_LEVEL_FIXED) most = std::max(most, n[s]);
+		return most;
+	}
+	int streamLimitLatency(const Batch &e, int s) const {
+		return streamLimit[s].on ? 2*e.limiterLookahead() + (streamLimit[s].truePeak ? SMST_STREAM_LIMITER_TRUE_PEAK_DELAY : 0) : 0;
 	}
 	// the rows of a call whose longest limited count is `most`, before the engine is called (a growth frees, which synchronises the device)
 	void ensureStreamLimitRows(Batch &e, int most, long long &allocs) {
@@ -440,11 +480,11 @@ struct PcmOutState {
 	}
 	unsigned flags(int s) const { return (truePeak[s] ? smst::kPcmFlagTruePeak : 0u) | (limiter[s] ? smst::kPcmFlagLimiter : 0u); }
 	// a call's level entry: a FIXED stream with the stream limiter's setting carries that limiter's ceiling in the word its mode does not use,
-	// the setting in bit 2 of the flags and the set of lines the call reads in bit 3
+	// the setting in bit 2 of the flags, the set of lines the call reads in bit 3 and the setting's true-peak flag in bit 4
 	smst::PcmLevel levelEntry(int s) const {
 		const bool limit = streamLimit[s].on && level[s].mode == SMST_LEVEL_FIXED;
-		return smst::PcmLevel{unsigned(level[s].mode), level[s].gain, limit ? streamLimit[s].ceiling : level[s].ceiling,
-		                      flags(s) | (limit ? smst::kPcmFlagStreamLimiter | (streamLimit[s].set ? smst::kPcmFlagStreamLimitSet : 0u) : 0u)};
+		const unsigned limitFlags = smst::kPcmFlagStreamLimiter | (streamLimit[s].set ? smst::kPcmFlagStreamLimitSet : 0u) | (streamLimit[s].truePeak ? smst::kPcmFlagStreamLimitTruePeak : 0u);
+		return smst::PcmLevel{unsigned(level[s].mode), level[s].gain, limit ? streamLimit[s].ceiling : level[s].ceiling, flags(s) | (limit ? limitFlags : 0u)};
 	}
 	void setLoudnessWeights(const float *weights) {
 		for (int c = 0; weights && c < C; ++c) if (!(std::isfinite(weights[c]) && weights[c] >= 0)) throw smst::Error("loudness: a channel weight is negative or not finite");
@@ -628,6 +668,7 @@ struct smst_batch {
 		Buffer<unsigned char, false> resDev; // allocated -- both sets -- by the first setter call with a ratio other than 1/1
 		Buffer<unsigned char, true> outResHost; // the output side's table of a call with a stream-out-resampled stream (smst::StreamResampleOutTableLayout),
 		Buffer<unsigned char, false> outResDev; // allocated -- both sets -- by the first setter call with a ratio other than 1/1
+		int mostLimitedPlain = 0, mostLimitedTruePeak = 0; // ... of one without and of one with the stream limiter's true-peak flag
 		int mostLimited = 0; // the largest count of a stream that the call's output limits ("Stream limiter"); 0: the call launches what it did without the setting
 		int mostDelivered = 0, deliveredLen = 1, outSpanPitch = 4; // "Stream output resample": the largest Nd of a stream with the setting (0: as mostLimited), the row length of the delivered image, what sizes the LDS
 	};
@@ -976,7 +1017,7 @@ static smst_batch::PcmTable &beginPcmCall(smst_batch *b) {
 		}
 	}
 	c.out = smst::PcmOutCall();
-	c.mostLimited = 0;
+	c.mostLimited = c.mostLimitedPlain = c.mostLimitedTruePeak = 0;
 	c.mostDelivered = 0;
 	return c;
 }
@@ -1157,7 +1198,8 @@ static int pcmPrepareOut(smst_batch *b, smst_batch::PcmTable &c, const int *n, i
 	if (memory == SMST_MEM_HOST && k.most > 0) ensurePcmBytes(b, b->hPcmOut, b->dPcmOut, (size_t)S*pcmRowElems(k.most, C)*pcmElemBytes(format));
 	hipSetDevice(e.device());
 	b->pcmOut.ensureStreamMeterScan(e.device(), b->pcmOut.mostStreamMetered(smst::PcmTableLayout(S).outCounts(c.host)), 0, b->stagingAllocs);
-	c.mostLimited = b->pcmOut.mostStreamLimited(smst::PcmTableLayout(S).outCounts(c.host));
+	c.mostLimited = b->pcmOut.mostStreamLimited(smst::PcmTableLayout(S).outCounts(c.host), &c.mostLimitedTruePeak);
+	c.mostLimitedPlain = c.mostLimitedTruePeak > 0 ? b->pcmOut.mostStreamLimitedPlain(smst::PcmTableLayout(S).outCounts(c.host)) : c.mostLimited;
 	if (c.mostLimited > 0) b->pcmOut.ensureStreamLimitRows(e, c.mostLimited, b->stagingAllocs);
 	pcmUploadOutTable(b, c, format, true);
 	return k.len;
@@ -1183,8 +1225,8 @@ static void pcmStageOut(smst_batch *b, smst_batch::PcmTable &c, void *out, long 
 	// a call that limits a stream: the two passes and the limited conversion (a kernel of its own) in the place of the levelled one
 	auto convert = [&](void *raw, long long rawSS, long long rawFS) {
 		if (c.mostLimited > 0) {
-			smst::launchPcmOutLimited(format, b->dOut, (long long)C*maxLen, maxLen, raw, rawSS, rawFS, at.outCounts(c.dev), S, C, most, c.mostLimited, c.out.overs, e.stream(), c.out.dither, c.out.level,
-			                          b->pcmOut.streamLimitView);
+			smst::launchPcmOutLimited(format, b->dOut, (long long)C*maxLen, maxLen, raw, rawSS, rawFS, at.outCounts(c.dev), S, C, most, c.mostLimitedPlain, c.mostLimitedTruePeak, c.out.overs, e.stream(), c.out.dither,
+			                          c.out.level, b->pcmOut.streamLimitView);
 			b->pcmOut.advanceStreamLimit(n);
 		} else {
 			smst::launchPcmOut(format, b->dOut, (long long)C*maxLen, maxLen, raw, rawSS, rawFS, at.outCounts(c.dev), S, C, most, c.out.overs, e.stream(), c.out.dither, c.out.level);
@@ -1277,6 +1319,19 @@ int smst_batch_pcm_stream_limiter(const smst_batch *b, int stream, int *on, floa
 int smst_batch_pcm_stream_limiter_latency(const smst_batch *b, int *frames) {
 	if (!b || !b->engine) return fail("null batch");
 	if (frames) *frames = 2*b->engine->limiterLookahead();
+	return SMST_OK;
+}
+int smst_batch_set_pcm_stream_limiter_true_peak(smst_batch *b, int stream, int on) { BATCH_CALL(b->pcmOut.setStreamLimiterTruePeak(*b->engine, stream, on)) }
+int smst_batch_pcm_stream_limiter_true_peak(const smst_batch *b, int stream, int *on) {
+	if (!b || !b->engine) return fail("null batch");
+	if (stream < 0 || stream >= b->engine->streams()) return fail("stream index out of range");
+	if (on) *on = b->pcmOut.streamLimit[stream].truePeak;
+	return SMST_OK;
+}
+int smst_batch_pcm_stream_limiter_latency_of(const smst_batch *b, int stream, int *frames) {
+	if (!b || !b->engine) return fail("null batch");
+	if (stream < 0 || stream >= b->engine->streams()) return fail("stream index out of range");
+	if (frames) *frames = b->pcmOut.streamLimitLatency(*b->engine, stream);
 	return SMST_OK;
 }
 int smst_batch_take_pcm_stream_limiter(smst_batch *b, float *minGain, long long *limitedFrames) {
@@ -2290,16 +2345,19 @@ int smst_debug_pcm_stream_limit(int device, int streams, int channels, int calls
 		if (!std::isfinite(gains[s])) throw smst::Error("stream limit: a gain is not finite");
 	}
 	hip(hipSetDevice(device));
-	const size_t len = size_t(std::max(longest, 1)), pitch = (len + 3)/4*4, set = smst::pcmStreamLimitSetFloats(S, Cn, H);
+	const size_t len = size_t(std::max(longest, 1)), pitch = (len + 3)/4*4, set = smst::pcmStreamLimitSetFloats(S, Cn, H), setTruePeak = smst::pcmStreamLimitTruePeakSetFloats(S, Cn, H);
+	bool anyTruePeak = false;
+	for (int s = 0; s < S; ++s) anyTruePeak = anyTruePeak || (flags[s] & 3) == 3;
 	const smst::PcmTableLayout at(S);
 	const smst::PcmMeters meters(S);
 	Buffer<unsigned char, false> dTable;
-	Buffer<float, false> dImage, dOut, dLines, dRows, dWin;
+	Buffer<float, false> dImage, dOut, dLines, dTruePeakLines, dRows, dWin;
 	Buffer<int, false> dWords, dLimitMeters;
 	dTable.allocate(at.bytes(), "stream limit");
 	dImage.allocate((size_t)S*Cn*len, "stream limit");
 	dOut.allocate((size_t)S*len*Cn, "stream limit");
 	dLines.allocate(2*set, "stream limit");
+	if (anyTruePeak) dTruePeakLines.allocate(2*setTruePeak, "stream limit");
 	dRows.allocate((size_t)S*(4*H + 2*pitch), "stream limit");
 	dWin.allocate((size_t)2*H + 1, "stream limit");
 	dWords.allocate(meters.words(), "stream limit");
@@ -2314,6 +2372,7 @@ int smst_debug_pcm_stream_limit(int device, int streams, int channels, int calls
 	hip(hipMemset(dLimitMeters, 0, (size_t)2*S*sizeof(int)));
 	smst::PcmStreamLimit lim;
 	for (int k = 0; k < 2; ++k) { lim.need[k] = dLines + k*set; lim.frames[k] = dLines + k*set + (size_t)S*4*H; }
+	if (anyTruePeak) for (int k = 0; k < 2; ++k) lim.truePeakFrames[k] = dTruePeakLines + k*setTruePeak;
 	lim.meters = dLimitMeters;
 	lim.needRow = dRows; lim.needPitch = (long long)(4*H + pitch);
 	lim.rRow = dRows + (size_t)S*(4*H + pitch); lim.rPitch = (long long)pitch;
@@ -2325,21 +2384,22 @@ int smst_debug_pcm_stream_limit(int device, int streams, int channels, int calls
 	std::vector<unsigned char> whichSet((size_t)S, 0);
 	const smst::PcmLevelIo io = meters.io(at.level(dTable.p), dWords);
 	for (int k = 0; k < calls; ++k) {
-		int most = 0, mostLimited = 0;
+		int most = 0, mostLimited = 0, mostPlain = 0, mostTruePeak = 0;
 		for (int s = 0; s < S; ++s) {
 			const int n = std::max(counts[(size_t)k*S + s], 0);
-			const bool on = (flags[s] & 1) != 0;
+			const bool on = (flags[s] & 1) != 0, late = on && (flags[s] & 2) != 0;
 			at.outCounts(table.data())[s] = n;
 			at.level(table.data())[s] = smst::PcmLevel{smst::kPcmLevelFixed, gains[s], on ? ceilings[s] : 1.0f,
-			                                           on ? smst::kPcmFlagStreamLimiter | (whichSet[s] ? smst::kPcmFlagStreamLimitSet : 0u) : 0u};
+			                                           on ? smst::kPcmFlagStreamLimiter | (whichSet[s] ? smst::kPcmFlagStreamLimitSet : 0u) | (late ? smst::kPcmFlagStreamLimitTruePeak : 0u) : 0u};
 			most = std::max(most, n);
 			if (on) mostLimited = std::max(mostLimited, n);
+			if (on) (late ? mostTruePeak : mostPlain) = std::max(late ? mostTruePeak : mostPlain, n);
 			for (int c = 0; c < Cn; ++c) std::copy(image + s*imageSS + c*imageCS + done[s], image + s*imageSS + c*imageCS + done[s] + n, hImage.begin() + ((size_t)s*Cn + c)*len);
 		}
 		if (most < 1) continue;
 		hip(hipMemcpy(dImage, hImage.data(), hImage.size()*sizeof(float), hipMemcpyHostToDevice));
 		hip(hipMemcpy(dTable, table.data(), table.size(), hipMemcpyHostToDevice));
-		if (mostLimited > 0) smst::launchPcmOutLimited(SMST_PCM_F32, dImage, (long long)(Cn*len), (long long)len, dOut, (long long)(len*Cn), Cn, at.outCounts(dTable.p), S, Cn, most, mostLimited, nullptr, nullptr, nullptr, io, lim);
+		if (mostLimited > 0) smst::launchPcmOutLimited(SMST_PCM_F32, dImage, (long long)(Cn*len), (long long)len, dOut, (long long)(len*Cn), Cn, at.outCounts(dTable.p), S, Cn, most, mostPlain, mostTruePeak, nullptr, nullptr, nullptr, io, lim);
 		else smst::launchPcmOut(SMST_PCM_F32, dImage, (long long)(Cn*len), (long long)len, dOut, (long long)(len*Cn), Cn, at.outCounts(dTable.p), S, Cn, most, nullptr, nullptr, nullptr, io);
 		hip(hipGetLastError());
 		hip(hipStreamSynchronize(nullptr));

@@ -169,7 +169,7 @@ __host__ __device__ inline bool analysisWindowInCall(int B, int M, int I, int in
 // form" tests assert through these that BOTH forms really ran.
 enum LaunchKind {
 	LK_VOC_ALIGNED, LK_VOC_TWISTED, LK_VOC_INTERIOR, LK_VOC_STAGED, LK_VOC_GATHER, LK_VOC_N, LK_VOC_ONE, LK_VOC_ACROSS, LK_VOC_CONT, LK_CHAIN_UNFUSED,
-	LK_ANALYSE_TEAMS, LK_ANALYSE_PAIRS, LK_ANALYSE_TWIST, LK_TWIST_ROWS, LK_ANALYSE_FAST, LK_ANALYSE_GENERIC, LK_SYNTH_TEAMS, LK_SYNTH_FAST, LK_SYNTH_GENERIC, LK_SYNTH_EMIT, LK_EMIT_CARRIED, LK_FEED_ONE_PASS, LK_PCM_IN, LK_PCM_OUT, LK_CLIP_IN, LK_CLIP_OUT, LK_PCM_OUT_DITHERED, LK_CLIP_OUT_DITHERED, LK_PCM_OUT_LEVELLED, LK_CLIP_OUT_LEVELLED, LK_CLIP_PEAK, LK_CLIP_LOUDNESS, LK_CLIP_TRUE_PEAK, LK_CLIP_LIMIT_NEED, LK_CLIP_LIMIT_GAIN, LK_CLIP_OUT_LIMITED, LK_CLIP_LOUDNESS_RANGE, LK_CLIP_RESAMPLE, LK_PCM_LIMIT_FEED, LK_PCM_LIMIT_GAIN, LK_PCM_OUT_LIMITED, LK_PCM_STREAM_RESAMPLE, LK_PCM_STREAM_METER, LK_PCM_STREAM_METER_READ, LK_PCM_STREAM_METER_SCAN, LK_CLIP_RESAMPLE_OUT, LK_PCM_STREAM_RESAMPLE_OUT, LK_PCM_STREAM_RESAMPLE_OUT_COPY, LK_COUNT
+	LK_ANALYSE_TEAMS, LK_ANALYSE_PAIRS, LK_ANALYSE_TWIST, LK_TWIST_ROWS, LK_ANALYSE_FAST, LK_ANALYSE_GENERIC, LK_SYNTH_TEAMS, LK_SYNTH_FAST, LK_SYNTH_GENERIC, LK_SYNTH_EMIT, LK_EMIT_CARRIED, LK_FEED_ONE_PASS, LK_PCM_IN, LK_PCM_OUT, LK_CLIP_IN, LK_CLIP_OUT, LK_PCM_OUT_DITHERED, LK_CLIP_OUT_DITHERED, LK_PCM_OUT_LEVELLED, LK_CLIP_OUT_LEVELLED, LK_CLIP_PEAK, LK_CLIP_LOUDNESS, LK_CLIP_TRUE_PEAK, LK_CLIP_LIMIT_NEED, LK_CLIP_LIMIT_GAIN, LK_CLIP_OUT_LIMITED, LK_CLIP_LOUDNESS_RANGE, LK_CLIP_RESAMPLE, LK_PCM_LIMIT_FEED, LK_PCM_LIMIT_GAIN, LK_PCM_OUT_LIMITED, LK_PCM_STREAM_RESAMPLE, LK_PCM_STREAM_METER, LK_PCM_STREAM_METER_READ, LK_PCM_STREAM_METER_SCAN, LK_CLIP_RESAMPLE_OUT, LK_PCM_STREAM_RESAMPLE_OUT, LK_PCM_STREAM_RESAMPLE_OUT_COPY, LK_PCM_LIMIT_FEED_TRUE_PEAK, LK_COUNT
 };
 long long launchCount(const char *name); // -1: unknown name
 
@@ -241,6 +241,9 @@ constexpr unsigned kPcmFlagTruePeak = 1u, kPcmFlagLimiter = 2u;
 // the entry's ceiling word -- a FIXED entry has no use for it otherwise -- then holds the stream limiter's ceiling.  kPcmFlagStreamLimitSet:
 // which of the stream's two carried lines the call reads (it writes the other one)
 constexpr unsigned kPcmFlagStreamLimiter = 4u, kPcmFlagStreamLimitSet = 8u;
+// kPcmFlagStreamLimitTruePeak: the stream limiter's true-peak flag (include/smst.h, "Stream limiter"), inert without kPcmFlagStreamLimiter:
+// the detector sees the three inter-sample phases as well (kPcmLimitFeedTruePeak), and the output is 6 frames later still
+constexpr unsigned kPcmFlagStreamLimitTruePeak = 16u;
 // kClipOut takes the loudness mode's gain gL from loudGain[s], which kLoudGate (smst_loudness.h) left there, and limits it by ceiling/peak.
 constexpr unsigned kPcmLevelFixed = 0u, kPcmLevelProtect = 1u, kPcmLevelNormalise = 2u, kPcmLevelLoudness = 3u;
 struct PcmLevelIo { const PcmLevel *table = nullptr; int *peaks = nullptr; float *applied = nullptr; int *clipPeak = nullptr; const float *loudGain = nullptr;
@@ -334,10 +337,15 @@ void launchClipLimit(const float *image, long long imageStreamStride, long long 
 // [2H zeros, every frame emitted so far].  What a batch carries, device: per stream two LINES -- need of the last 4H frames, [S][4H], and the
 // last 2H frames of every channel before the gain, [S][C][2H] --, of which a call reads the one its entry's kPcmFlagStreamLimitSet names and
 // writes the other, and the two meter words of kClipLimitGain, [2][S], which accumulate until they are taken.  What a call works in: the
-// need row [S][needPitch >= 4H + longest limited count] and the r row [S][rPitch >= that count], stream-ordered scratch as the images are
+// need row [S][needPitch >= 4H + longest limited count] and the r row [S][rPitch >= that count], stream-ordered scratch as the images are.
+// A stream with kPcmFlagStreamLimitTruePeak is 2H + 6 frames late: need of a frame waits for the 6 frames its taps reach ahead.  Its need
+// line is the one above -- need of the last 4H frames whose taps are complete --; its frames are carried in lines of their own, the last
+// pcmStreamLimitTruePeakLine(H) = 2H + 11 frames of every channel, [S][C][2H + 11], two sets as above (null until a stream first gets the
+// flag): the first 5 are the reach of the oldest missing need's taps, the 2H + 6 behind them what the output is late by
 struct PcmStreamLimit {
 	float *need[2] = {nullptr, nullptr};
 	float *frames[2] = {nullptr, nullptr};
+	float *truePeakFrames[2] = {nullptr, nullptr};
 	int *meters = nullptr;
 	float *needRow = nullptr, *rRow = nullptr;
 	long long needPitch = 0, rPitch = 0;
@@ -345,14 +353,19 @@ struct PcmStreamLimit {
 	int H = 0;
 };
 inline size_t pcmStreamLimitSetFloats(int S, int C, int H) { return (size_t)S*4*H + (size_t)S*C*2*H; } // one set of lines: need, then the frames
-// need <- 1, frames <- +0.0 in both sets of `stream` (-1: of every stream), on `st`
+constexpr int kStreamLimitTruePeakDelay = kTruePeakTrail;                                                // SMST_STREAM_LIMITER_TRUE_PEAK_DELAY
+inline __host__ __device__ int pcmStreamLimitTruePeakLine(int H) { return 2*H + kTruePeakLead + kTruePeakTrail; }
+inline size_t pcmStreamLimitTruePeakSetFloats(int S, int C, int H) { return (size_t)S*C*pcmStreamLimitTruePeakLine(H); } // one set of the flag's lines
+// need <- 1, frames <- +0.0 in both sets of `stream` (-1: of every stream), the flag's lines included where they exist, on `st`
 void launchPcmLimitClear(const PcmStreamLimit &lim, int S, int C, int stream, hipStream_t st);
-// launchPcmOut's levelled form for a call in which a limited stream has frames (maxLimited >= 1: the largest count of such a stream): the two
-// passes, then the conversion -- a kernel of its own -- that takes a limited stream's frame i from its line (i < 2H) or from the image at
-// i - 2H and multiplies it by r as well; a stream without the setting gets the levelled form's bytes.  Three launches on `st`
+// launchPcmOut's levelled form for a call in which a limited stream has frames (maxLimited: the largest count of such a stream without the
+// true-peak flag, maxTruePeak: of one with it; one of them >= 1): the two passes, then the conversion -- a kernel of its own -- that takes
+// a limited stream's frame i from its line (i < 2H, or 2H + 6) or from the image behind it and multiplies it by r as well; a stream without
+// the setting gets the levelled form's bytes.  Three launches on `st` -- with maxTruePeak < 1 exactly those of a batch that has no flag --,
+// four where streams of both kinds have frames: each feed kernel takes its own kind
 void launchPcmOutLimited(int format, const float *in, long long inStreamStride, long long inChannelStride, void *out, long long outStreamStride, long long outFrameStride,
-                         const int *counts, int S, int C, int maxFrames, int maxLimited, unsigned *overs, hipStream_t st, const PcmDither *dither, const PcmLevelIo &level,
-                         const PcmStreamLimit &lim);
+                         const int *counts, int S, int C, int maxFrames, int maxLimited, int maxTruePeak, unsigned *overs, hipStream_t st, const PcmDither *dither,
+                         const PcmLevelIo &level, const PcmStreamLimit &lim);
 // Sample-rate conversion of whole clips in front of the engine (include/smst.h, "Resample", has the definition; smst_resample.h the kernel).
 // A ratio L/M, reduced, the batch's rate over the clip's: N frames become Nr = ceil(N*L/M), frame n at input position n*M/L, formed by the T = 2H
 // taps of its phase's row of a Kaiser-windowed sinc in float64, rounded once.  ResampleShape: what a ratio fixes -- H, T and the pitch of a

@@ -303,12 +303,12 @@ __device__ inline void pcmMaxPeak(int *__restrict__ peaks, int s, unsigned peak)
 // |v| of this lane's elements as its bits, NaN skipped; a run of zeros is not multiplied (0*inf would be a NaN).  Nothing else.
 // Limit ("Limiter" of include/smst.h; the levelled form only): where `limit` is set -- r of the run's first frame, one float per frame --
 // the quantiser takes u = w*r, one more fp32 multiply of its own; a stream whose `limit` is null gets the levelled form's bytes.
-// Delayed ("Stream limiter" of include/smst.h; the limited form only): where `line` is set -- the stream's carried frames, [C][lineFrames] --
-// frame i of the run is frame i of the line for i < lineFrames and frame i - lineFrames of the image behind it: the loader of the delayed
-// stream, and nothing else; a stream whose `line` is null is loaded as ever.
+// Delayed ("Stream limiter" of include/smst.h; the limited form only): where `line` is set -- the last lineFrames of the stream's carried
+// frames, rows of linePitch floats, one per channel -- frame i of the run is frame i of the line for i < lineFrames and frame i - lineFrames
+// of the image behind it: the loader of the delayed stream, and nothing else; a stream whose `line` is null is loaded as ever.
 template <typename T, bool Dith, bool Level = false, bool Limit = false, bool Delayed = false> __device__ inline bool pcmTileOut(const float *__restrict__ in, long long inChannelStride, T *__restrict__ run, long long outFrameStride, long long frames,
 		int t, int C, float *tile, unsigned &over, PcmDither dp, float gain = 1.0f, unsigned *peak = nullptr, const float *__restrict__ limit = nullptr,
-		const float *__restrict__ line = nullptr, int lineFrames = 0) {
+		const float *__restrict__ line = nullptr, int lineFrames = 0, int linePitch = 0) {
 	typedef PcmFormat<T> F;
 	const int tid = threadIdx.x;
 	long long e0;
@@ -324,7 +324,7 @@ template <typename T, bool Dith, bool Level = false, bool Limit = false, bool De
 			if (i < 0 || i >= count) continue;
 			if constexpr (Delayed) if (line) {
 				const long long f = f0 + fl;
-				tile[pcmSlot(i)] = f < lineFrames ? line[(size_t)c*lineFrames + f] : in[(size_t)c*inChannelStride + (f - lineFrames)];
+				tile[pcmSlot(i)] = f < lineFrames ? line[(size_t)c*linePitch + f] : in[(size_t)c*inChannelStride + (f - lineFrames)];
 				continue;
 			}
 			tile[pcmSlot(i)] = src ? src[(size_t)c*inChannelStride + fl] : 0.0f;

@@ -284,7 +284,7 @@ void launchFftComplexSelfTest(const float *in, float *out, int n, hipStream_t st
 static std::atomic<long long> gLaunchCounts[LK_COUNT];
 static const char *const kLaunchNames[LK_COUNT] = {
 	"vocoder_aligned", "vocoder_twisted", "vocoder_interior", "vocoder_staged", "vocoder_gather", "vocoder_n", "vocoder_one", "vocoder_across", "vocoder_continuous", "chain_unfused",
-	"analyse_teams", "analyse_pairs", "analyse_twist", "twist_rows", "analyse_fast", "analyse_generic", "synth_teams", "synth_fast", "synth_generic", "synth_emit", "emit_carried", "feed_one_pass", "pcm_in", "pcm_out", "clip_in", "clip_out", "pcm_out_dithered", "clip_out_dithered", "pcm_out_levelled", "clip_out_levelled", "clip_peak", "clip_loudness", "clip_true_peak", "clip_limit_need", "clip_limit_gain", "clip_out_limited", "clip_loudness_range", "clip_resample", "pcm_limit_feed", "pcm_limit_gain", "pcm_out_limited", "pcm_stream_resample", "pcm_stream_meter", "pcm_stream_meter_read", "pcm_stream_meter_scan", "clip_resample_out", "pcm_stream_resample_out", "pcm_stream_resample_out_copy"};
+	"analyse_teams", "analyse_pairs", "analyse_twist", "twist_rows", "analyse_fast", "analyse_generic", "synth_teams", "synth_fast", "synth_generic", "synth_emit", "emit_carried", "feed_one_pass", "pcm_in", "pcm_out", "clip_in", "clip_out", "pcm_out_dithered", "clip_out_dithered", "pcm_out_levelled", "clip_out_levelled", "clip_peak", "clip_loudness", "clip_true_peak", "clip_limit_need", "clip_limit_gain", "clip_out_limited", "clip_loudness_range", "clip_resample", "pcm_limit_feed", "pcm_limit_gain", "pcm_out_limited", "pcm_stream_resample", "pcm_stream_meter", "pcm_stream_meter_read", "pcm_stream_meter_scan", "clip_resample_out", "pcm_stream_resample_out", "pcm_stream_resample_out_copy", "pcm_limit_feed_true_peak"};
 void countLaunch(LaunchKind k) { gLaunchCounts[k].fetch_add(1, std::memory_order_relaxed); }
 long long launchCount(const char *name) {
 	for (int i = 0; i < LK_COUNT; ++i) if (name && std::strcmp(name, kLaunchNames[i]) == 0) return gLaunchCounts[i].load(std::memory_order_relaxed);

@@ -14,7 +14,9 @@ that drift of the host or the device hits all of them alike:
   k  d with a fixed gain of 0.5 on every stream (set_pcm_level): the levelled kernel   (k - d = what the gain and the peak meter add to a step)
   l  d with a fixed gain of +12 dB and the stream limiter at -1 dBFS on every stream (set_pcm_stream_limiter): the two passes and the limited kernel
      (l - k = what the two passes and the delayed loader add to a step)
-The dithered, levelled and limited rows are not in the default set: --variants d,e,f,g,h,i,j,k,l.  The time of the output conversion KERNEL alone (kPcmOut<T, false> /
+  m  l with the stream limiter's true-peak flag on every stream (set_pcm_stream_limiter_true_peak): the true-peak feed kernel in the place of
+     the sample-peak one   (m - l = what the three phases of the detector add to a step)
+The dithered, levelled and limited rows are not in the default set: --variants d,e,f,g,h,i,j,k,l,m.  The time of the output conversion KERNEL alone (kPcmOut<T, false> /
 kPcmOut<T, true> per format) is read from a kernel trace of such a run.
 A step's time is the host clock around one call that ends synchronised.  Prints one JSON line."""
 import argparse
@@ -62,7 +64,7 @@ def main():
     if "c" in variants:
         b, out = pkg.StretchBatch(S, Cn, preset="default", sample_rate=sr), np.zeros((S, m, Cn), np.int16)
         runs["c"] = lambda b=b, out=out: b.processFrames(s16, m, out=out)
-    if any(k in variants for k in "defghijkl"):
+    if any(k in variants for k in "defghijklm"):
         import torch
     if "d" in variants:
         b, x, out = pkg.StretchBatch(S, Cn, preset="default", sample_rate=sr), torch.from_numpy(s16).cuda(), torch.zeros((S, m, Cn), dtype=torch.int16, device="cuda")
@@ -86,6 +88,13 @@ def main():
         b.set_pcm_stream_limiter(True, 10**(-1/20))
         torch.cuda.synchronize()
         runs["l"] = lambda b=b, x=x, out=out: (b.processFrames(x, m, out=out, ordered=False), b.synchronize())
+    if "m" in variants:
+        b, x, out = pkg.StretchBatch(S, Cn, preset="default", sample_rate=sr), torch.from_numpy(s16).cuda(), torch.zeros((S, m, Cn), dtype=torch.int16, device="cuda")
+        b.set_pcm_level(pkg.LEVEL_FIXED, 10**(12/20))
+        b.set_pcm_stream_limiter(True, 10**(-1/20))
+        b.set_pcm_stream_limiter_true_peak(True)
+        torch.cuda.synchronize()
+        runs["m"] = lambda b=b, x=x, out=out: (b.processFrames(x, m, out=out, ordered=False), b.synchronize())
     if any(k in variants for k in "hij"):
         codes = np.clip(np.round(f32.astype(np.float64)*8388608.0), -8388608, 8388607).astype(np.int32)
         s24 = np.stack([codes & 255, (codes >> 8) & 255, (codes >> 16) & 255], -1).astype(np.uint8)
@@ -130,6 +139,9 @@ def main():
         if "l" in times and base in times:
             extra = result["step_ms"]["l"]["median"] - result["step_ms"][base]["median"]
             result.setdefault("stream_limit", {})[base] = dict(against=base, extra_ms=extra, share_of_step=extra/result["step_ms"]["l"]["median"])
+    if "m" in times and "l" in times:
+        extra = result["step_ms"]["m"]["median"] - result["step_ms"]["l"]["median"]
+        result.setdefault("stream_limit", {})["m"] = dict(against="l", extra_ms=extra, share_of_step=extra/result["step_ms"]["m"]["median"])
     print(json.dumps(result))
 
 

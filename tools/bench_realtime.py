@@ -4,7 +4,8 @@
 Prints one JSON object: per batch size the median / p99 time per quantum and how many streams that sustains in real time.
 This pattern is bound by kernel launches and the per-call host scheduling, not by the kernels.
 --frames=s16|f32 runs the same pattern through processFrames on interleaved frames in device memory; --gain=dB gives every stream a fixed
-gain and --stream-limit=dBFS turns the stream limiter on at that ceiling (include/smst.h, "Stream limiter"; both need --frames)."""
+gain and --stream-limit=dBFS turns the stream limiter on at that ceiling (include/smst.h, "Stream limiter"; both need --frames);
+--stream-limit-true-peak gives that limiter its true-peak detector: the ceiling is then one in dBTP, met 6 frames later."""
 import argparse, importlib, json, os, sys, time
 os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")  # the engine's pipeline streams get hardware queues of their own (INTEGRATION.md); before the HIP runtime starts
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -22,10 +23,13 @@ def main():
     ap.add_argument("--frames", default=None, choices=["s16", "f32"], help="interleaved frames through processFrames instead of planar float32")
     ap.add_argument("--gain", type=float, default=None, help="dB: a fixed gain on every stream's frame output (needs --frames)")
     ap.add_argument("--stream-limit", type=float, default=None, help="dBFS: the stream limiter's ceiling (needs --frames)")
+    ap.add_argument("--stream-limit-true-peak", action="store_true", help="the stream limiter's true-peak flag (needs --stream-limit)")
     ap.add_argument("--lookahead", type=int, default=None, help="the limiter's lookahead in frames (default: the library's, 72)")
     args = ap.parse_args()
     if (args.gain is not None or args.stream_limit is not None) and not args.frames:
         ap.error("--gain and --stream-limit act on the frame output: give --frames=s16 or --frames=f32")
+    if args.stream_limit_true_peak and args.stream_limit is None:
+        ap.error("--stream-limit-true-peak is a flag of the stream limiter: give --stream-limit=dBFS")
     import torch
     pkg = importlib.import_module("signalsmith-stretch_amd")
     sr, C, Q = 48000, args.channels, args.quantum
@@ -48,6 +52,8 @@ def main():
                 b.set_pcm_level(pkg.LEVEL_FIXED, 10**(args.gain/20))
             if args.stream_limit is not None:
                 b.set_pcm_stream_limiter(True, 10**(args.stream_limit/20))
+            if args.stream_limit_true_peak:
+                b.set_pcm_stream_limiter_true_peak(True)
         times = []
         for q in range(args.quanta + 50):
             xin = x[:, q*n_in:(q + 1)*n_in] if args.frames else x[:, :, q*n_in:(q + 1)*n_in]
@@ -70,7 +76,7 @@ def main():
     out = {"pattern": "%s(%d, %d) per quantum, %d ch 48 kHz preset %s, device-resident, 1 sync per quantum" % (what, n_in, Q, C, args.preset),
            "stretch": args.stretch, "quanta_timed": args.quanta, "rows": rows}
     if args.frames:
-        out.update(frames=args.frames, gain_db=args.gain, stream_limit_dbfs=args.stream_limit)
+        out.update(frames=args.frames, gain_db=args.gain, stream_limit_dbfs=args.stream_limit, stream_limit_true_peak=args.stream_limit_true_peak)
     print(json.dumps(out))
 
 
